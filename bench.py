@@ -198,6 +198,48 @@ def parity_check(args, rb, batch, th, stride, step, max_size, lim):
     return out
 
 
+DUMP_BYTES = 60 * 10**6          # --dump-outputs: array bytes in all (the .npy headers stay inside 64 MB with this)
+DUMP_RAYS = 65536                # rays whose d_ray and final state are written (every ray of a smaller batch)
+DUMP_SEED = 0
+
+
+def dump_outputs(batch, out_dir):
+    """--dump-outputs: what the last pass returned to a caller, on a fixed sample of the batch's rays in the caller's ray order,
+    one DIR/<name>.npy per array -- d_ray [3, n] and final [9, n] (fp64) of n = min(R, DUMP_RAYS) rays, and of as many of those
+    rays as DUMP_BYTES leaves room for, the recorded rows s_ray [rows, 6, m] (and n_ray [rows, m] when kept) in the record's
+    dtype.  ray_index / traj_ray_index hold the sampled rays' positions in the batch (as float64).  The sample is a function
+    of the arguments alone, so two builds run with the same arguments write the same rays."""
+    import torch
+    R = batch.R
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.arange(R) if R <= DUMP_RAYS else np.sort(rng.choice(R, DUMP_RAYS, replace=False))
+    out = {"ray_index": idx.astype(np.float64), "d_ray": batch.d_ray()[:, idx], "final": batch.final()[:, idx]}
+    t = batch.device_tensors()
+    if "s_ray" in t:
+        s = t["s_ray"]
+        n = t.get("n_ray")
+        rows = s.shape[0]
+        per_row = s.element_size() * (6 + (n is not None))              # bytes of one ray's one row
+        left = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 8 * len(idx)      # ... and traj_ray_index
+        m = int(max(1, min(len(idx), left // (rows * per_row))))
+        rows = int(min(rows, left // (m * per_row)))                     # a single ray's record larger than the budget: its head
+        tidx = np.sort(rng.choice(idx, m, replace=False))
+        slots = tidx
+        if "perm" in t:                                                  # sort_rays: slot k of the record holds ray perm[k]
+            slot_of = np.empty(R, dtype=np.int64)
+            slot_of[t["perm"].cpu().numpy()] = np.arange(R)
+            slots = slot_of[tidx]
+        sel = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).to(s.device)
+        out["traj_ray_index"] = tidx.astype(np.float64)
+        out["s_ray"] = s[:rows].index_select(2, sel).cpu().numpy()
+        if n is not None:
+            out["n_ray"] = n[:rows].index_select(1, sel).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def trace_step(args, rb):
     c = rb.constants(SCEN[args.scenario]["choice"])
     if args.scenario == "fisheye":
@@ -305,7 +347,12 @@ def main():
     ap.add_argument("--fused", action="store_true",
                     help="rtmi_params.reference_order = 2: fused forms wherever there is one -- op7 too (outside 1e-9 on interface)")
     ap.add_argument("--parity-stride", type=int, default=512, help="parity_check: every this-many-th ray (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one computed (d_ray, final state, recorded rows; a fixed "
+                         "sample of the rays, at most 64 MB) as DIR/<name>.npy; with N > 1, rank 0's shard")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.method is None:
         args.method = 11 if args.scenario == "anisotropy" else 6
     if args.mode == "lane":
@@ -578,6 +625,9 @@ def main():
         if args.parity_stride > 0 and args.chunk <= 0:
             out["parity_check"] = parity_check(args, rb, batch, th, stride, step, max_size, lim)
             parity_failed = not out["parity_check"]["ok"]
+        if args.dump_outputs:
+            shapes = dump_outputs(batch, args.dump_outputs)
+            print(f"bench.py: wrote {', '.join(f'{k}{v}' for k, v in shapes.items())} to {args.dump_outputs}", file=sys.stderr)
     batch.close()
 
     # The secondary record of the default N > 1 line: the WEAK configuration on the same ranks -- 1 048 576 rays per GPU of an
