@@ -6,25 +6,6 @@
 
 #include "rt_polytab.h"
 
-#ifndef RTMI_CHORD_SERIES
-// the step's arclength from the advancement's closed form (chord_length) instead of the positions: 1 for the first-order
-// advancement (op1/op2: the chord IS DELTA_S; op1 12.5 -> 11.8 ms), 2 for the second-order one as well (measured slower:
-// the vote and eps carried across the lookup cost more than the square root -- headline 14.9 -> 15.5 ms, cfg2 2.20 -> 2.48)
-#define RTMI_CHORD_SERIES 1
-#endif
-#ifndef RTMI_POLY_BATCH
-#define RTMI_POLY_BATCH 1     // scalar loads of a lookup: 0 row by row, 1 one spline + n then the other (measured best), 2 all at once (spills SGPRs)
-#endif
-#ifndef RTMI_FLAT_MAP
-#define RTMI_FLAT_MAP 1     // 0 compiles the flat-cell map's tests out of the lookups (A/B of what they cost a field without flat cells)
-#endif
-#ifndef RTMI_LAT_RELOAD
-#define RTMI_LAT_RELOAD 0   // k_advance_lat's kept cell: 0 reloaded with vector loads (vmcnt(0): also waits for the row stores before), 1 through the scalar cache + copies
-#endif
-#ifndef RTMI_POLY
-#define RTMI_POLY 1     // 1: the fast-form step methods look the field up as one polynomial per cell (PolyGather); 0: B-spline sums
-#endif
-
 // A wave vote straight from the predicate.  HIP's __ballot(int) converts the bool to an int and compares it with zero again
 // (v_cndmask + v_cmp per vote, 12 vector instructions per step of the bench kernel); the builtin takes the i1.
 __device__ __forceinline__ unsigned long long rt_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
@@ -40,15 +21,11 @@ __device__ __forceinline__ double fma_(double a, double b, double c) { return __
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // a*b + c where c is a loop-invariant constant held in a VGPR pair: written as the three-address v_fma_f64.  Left to the
 // compiler this becomes v_mov_b64 (copy the constant) + v_fmac_f64 (accumulate into the copy), two instructions for one.
-#ifndef RTMI_NO_FMA3
 __device__ __forceinline__ double fma_const(double a, double b, double c) {
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
-#else
-__device__ __forceinline__ double fma_const(double a, double b, double c) { return __builtin_fma(a, b, c); }
-#endif
 __device__ __forceinline__ float fma_const(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // ---------------------------------------------------------------- sin/cos
@@ -158,43 +135,14 @@ template <typename T> __device__ __forceinline__ void sincos_add_small(T s, T c,
     *so = fma_(c, sk, fma_(-s, ck1, s));
     *co = fma_(-s, sk, fma_(-c, ck1, c));
 }
-// The same for |k| < 2^-9 (a turn of 0.1 degree per step: every step of the vert_heterogeneous and interface fans, 4e-4 and
-// less): one series term fewer each -- the dropped ones are k^6/5040 < 2^-66 of sin k and k^6/720 < 2^-63 of 1: nothing
-// in fp64 -- 10 instructions for 13.  Measured (A/B, one session, profiles/r03_ab_small_savings.txt): vert_heterogeneous without
-// recording 8.78 -> 8.52 ms, the recording headline unchanged, but fisheye -- whose turns are not tiny, and which now pays
-// a second vote -- 7.9 -> 8.7 ms and the few-waves build 2.20 -> 2.24: off.
-#ifndef RTMI_TINY_ROT
-#define RTMI_TINY_ROT 0
-#endif
-template <typename T> __device__ __forceinline__ void sincos_add_tiny(T s, T c, T k, T* so, T* co) {
-    const T z = k * k;
-    const T ps = fma_const(z, T(1.0 / 120.0), T(-1.0 / 6.0));
-    const T sk = fma_(z * k, ps, k);                 // sin k
-    const T pc = fma_const(z, T(-1.0 / 24.0), T(0.5));
-    const T ck1 = z * pc;                            // 1 - cos k
-    *so = fma_(c, sk, fma_(-s, ck1, s));
-    *co = fma_(-s, sk, fma_(-c, ck1, c));
-}
-// Which formula a lane uses depends on its own k only (tiny / small / a full evaluation at `target`); the votes select a
-// layout without exec-mask bookkeeping for the two common cases that every lane of the wave is tiny, or every lane small.
+// Which formula a lane uses depends on its own k only (small / a full evaluation at `target`); the vote selects a layout
+// without exec-mask bookkeeping for the common case that every lane of the wave is small.  (A shorter series for tiny turns,
+// |k| < 2^-9, with a second vote was measured and not kept: vert_heterogeneous 8.78 -> 8.52 ms, but fisheye 7.9 -> 8.7 ms
+// and the few-waves build 2.20 -> 2.24, profiles/r03_ab_small_savings.txt.)
 // (the full evaluation is at base + (add_k ? k : 0), formed only where it is needed)
 template <typename T, bool ADD_K> __device__ __forceinline__ void sincos_add_select(double base, T s, T c, T k, T* so, T* co, bool refresh) {
     const T ak = M<T>::abs_(k);
     const bool small = ak < M<T>::small_angle && !refresh;
-#if RTMI_TINY_ROT
-    const bool tiny = ak < T(0.001953125) && !refresh;
-    if (rt_ballot(!tiny) == 0ull) {
-        sincos_add_tiny(s, c, k, so, co);
-    } else if (rt_ballot(!small || tiny) == 0ull) {
-        sincos_add_small(s, c, k, so, co);
-    } else if (tiny) {
-        sincos_add_tiny(s, c, k, so, co);
-    } else if (small) {
-        sincos_add_small(s, c, k, so, co);
-    } else {
-        M<T>::sincos_(ADD_K ? base + (double)k : base, so, co);
-    }
-#else
     if (rt_ballot(!small) == 0ull) {
         sincos_add_small(s, c, k, so, co);
     } else if (small) {
@@ -202,7 +150,6 @@ template <typename T, bool ADD_K> __device__ __forceinline__ void sincos_add_sel
     } else {
         M<T>::sincos_(ADD_K ? base + (double)k : base, so, co);
     }
-#endif
 }
 template <typename T> __device__ __forceinline__ void sincos_add(double theta, T s, T c, T k, T* so, T* co) {
     sincos_add_select<T, true>(theta, s, c, k, so, co, false);
@@ -257,7 +204,6 @@ template <typename T> struct FieldDev {
 // rematerialises constants every iteration).  Every kernel that looks the field up has its FieldDev at offset 0 of the
 // kernel-argument segment (k_advance / k_trace_refill / k_init: BatchDev::F is the first member; k_field_eval: first
 // argument), so a rare branch can re-read it from there; the empty asm keeps the loads inside the branch.
-#ifndef RTMI_NO_KERNARG_FIELD
 template <typename T> __device__ __forceinline__ FieldDev<T> rare_field(const FieldDev<T>&) {
     typedef const FieldDev<T> __attribute__((address_space(4))) * KP;
     KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
@@ -266,9 +212,6 @@ template <typename T> __device__ __forceinline__ FieldDev<T> rare_field(const Fi
     __builtin_memcpy(&out, p, sizeof(out));      // scalar loads from the constant address space
     return out;                                   // scalar loads, live only inside the branch
 }
-#else
-template <typename T> __device__ __forceinline__ const FieldDev<T>& rare_field(const FieldDev<T>& F) { return F; }
-#endif
 
 template <typename T> __device__ __forceinline__ T axis_at(int i, int q, T a, T h, T b) {
     return i >= q - 1 ? b : M<T>::lin(i, h, a);
@@ -509,12 +452,6 @@ __device__ __forceinline__ void lookup_global_rows(const FieldDev<T>& F, const C
     gx = sx; gy = sy;
 }
 
-#ifndef RTMI_TILE_PHASES
-#define RTMI_TILE_PHASES 4     // the 4x4 window is read from the LDS tile and summed in this many groups of rows
-#endif
-#ifndef RTMI_GLOBAL_PHASES
-#define RTMI_GLOBAL_PHASES 2
-#endif
 // Gather policy 1: every lookup reads its 36 coefficients from global memory (L1/L2-resident in practice).
 // FLATMAP (rt_exact.h, the reference-order step where the medium is constant): false in the builds for fields whose flat-cell map is
 // empty -- the flat path is not even compiled in there (as run-time tests it cost the vert_heterogeneous fan in reference order a third).
@@ -536,7 +473,6 @@ template <typename T, bool FLATMAP = true> struct GlobalGather {
 // Wave-wide min / max of an int, returned wave-uniform.  DPP row shifts and row broadcasts (an inclusive scan within each
 // row of 16, then rows 0/2 into 1/3 and the lower half into the upper) leave the result in lane 63: six v_min/v_max with
 // a DPP operand and one v_readlane, instead of six ds_bpermute round trips through the LDS crossbar (__shfl_xor).
-#ifndef RTMI_SHFL_REDUCE
 template <bool MIN> __device__ __forceinline__ int wave_reduce_i(int v) {
     constexpr int ident = MIN ? 0x7fffffff : (int)0x80000000;
     auto op = [](int a, int b) { return MIN ? (b < a ? b : a) : (b > a ? b : a); };
@@ -550,18 +486,6 @@ template <bool MIN> __device__ __forceinline__ int wave_reduce_i(int v) {
 }
 __device__ __forceinline__ int wave_min_i(int v) { return wave_reduce_i<true>(v); }
 __device__ __forceinline__ int wave_max_i(int v) { return wave_reduce_i<false>(v); }
-#else
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
-}
-#endif
 
 // Gather policy 2: a wave-private LDS tile of the field.  The rays of a wave travel together (they leave one
 // origin with neighbouring angles), so their 4x4 windows overlap almost completely and move ~0.15 cell per step:
@@ -571,7 +495,7 @@ __device__ __forceinline__ int wave_max_i(int v) {
 // reads global memory for that lookup -- the coefficient VALUES are the same bits either way, so results do not
 // depend on the policy.  No block barrier: the tile is private to one wave and LDS executes a wave's DS
 // instructions in order; fetch() must be reached in wave-uniform control flow (it votes and shuffles).
-template <typename T, int PHASES = RTMI_TILE_PHASES> struct LdsGather {
+template <typename T> struct LdsGather {
     static constexpr bool kUniformWindow = false;
     static constexpr int TILE = 16;                 // coefficient rows/cols held
     static constexpr int GPITCH = TILE + 1;         // pairs per g row (one pad pair against bank aliasing)
@@ -670,49 +594,34 @@ template <typename T, int PHASES = RTMI_TILE_PHASES> struct LdsGather {
         }
     }
 
-    // fetch + field_combine.  With every lane in the tile the window is read and summed in RTMI_TILE_PHASES groups of rows
-    // (same sums in the same order as field_combine, so the same bits).  Row by row (RTMI_TILE_PHASES 4): 4 LDS reads in
-    // flight instead of 16 and 128 instead of 182 VGPRs, i.e. four waves per SIMD without spilling for op2/op6.
+    // fetch + field_combine.  With every lane in the tile the window is read and summed row by row (same sums in the same
+    // order as field_combine, so the same bits): 4 LDS reads in flight instead of 16 and 128 instead of 182 VGPRs, i.e. four
+    // waves per SIMD without spilling for op2/op6.
     __device__ __forceinline__ void lookup(const FieldDev<T>& F, const Cell<T>& c, bool active, T& n, T& gx, T& gy) {
         int cx, cy;
         const bool fits = place(F, c, active, cx, cy);
         if (rt_ballot(!fits) == 0ull || fits) {   // every lane in the tile (the common, wave-uniform case), or this one is
-            if constexpr (PHASES > 1) {
             const RT_LDS Pair<T>* gw = gt + cy * GPITCH + cx;
             const RT_LDS T* zw = zt + (cy + 1) * ZPITCH + (cx + 1);
             const T z0 = zw[0], z1 = zw[1], z2 = zw[ZPITCH], z3 = zw[ZPITCH + 1];
-            constexpr int ROWS = 4 / PHASES;
             T sx = 0, sy = 0;
 #pragma unroll
-            for (int ph = 0; ph < PHASES; ph++) {
-                Pair<T> a[ROWS][4];
+            for (int r = 0; r < 4; r++) {
+                Pair<T> a[4];
 #pragma unroll
-                for (int r = 0; r < ROWS; r++) {
+                for (int q = 0; q < 4; q++) a[q] = gw[r * GPITCH + q];
+                T rx = a[0].x * c.wx[0], ry = a[0].y * c.wx[0];
 #pragma unroll
-                    for (int q = 0; q < 4; q++) a[r][q] = gw[(ph * ROWS + r) * GPITCH + q];
+                for (int q = 1; q < 4; q++) {
+                    rx = fma_(a[q].x, c.wx[q], rx);
+                    ry = fma_(a[q].y, c.wx[q], ry);
                 }
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    T rx = a[r][0].x * c.wx[0], ry = a[r][0].y * c.wx[0];
-#pragma unroll
-                    for (int q = 1; q < 4; q++) {
-                        rx = fma_(a[r][q].x, c.wx[q], rx);
-                        ry = fma_(a[r][q].y, c.wx[q], ry);
-                    }
-                    const int rr = ph * ROWS + r;
-                    sx = rr == 0 ? rx * c.wy[0] : fma_(rx, c.wy[rr], sx);
-                    sy = rr == 0 ? ry * c.wy[0] : fma_(ry, c.wy[rr], sy);
-                }
-                asm volatile("" : "+v"(sx), "+v"(sy) : : "memory");   // the next rows' reads stay behind these sums
+                sx = r == 0 ? rx * c.wy[0] : fma_(rx, c.wy[r], sx);
+                sy = r == 0 ? ry * c.wy[0] : fma_(ry, c.wy[r], sy);
+                asm volatile("" : "+v"(sx), "+v"(sy) : : "memory");   // the next row's reads stay behind these sums
             }
             n = bilinear(c, z0, z1, z2, z3);
             gx = sx; gy = sy;
-            } else {   // PHASES == 1: the whole window in flight at once (the latency build: registers to spare, nothing to hide behind)
-            T z[4];
-            Pair<T> g[4][4];
-            read_tile(cx, cy, z, g);
-            field_combine(c, z, g, n, gx, gy);
-            }
         } else {
             // this lane's window is outside the tile (or at a grid end): row by row from global memory, so that this rare
             // branch does not set the kernel's register count (36 coefficients + 18 addresses in flight did)
@@ -728,12 +637,12 @@ template <typename G> struct IsPoly { static constexpr bool value = false; };
 template <typename T, int MODE, bool FLAT> struct PolyGather;
 template <typename T, int MODE, bool FLAT> struct IsPoly<PolyGather<T, MODE, FLAT>> { static constexpr bool value = true; };
 template <typename G> struct HasFlatMap { static constexpr bool value = false; };
-template <typename T, int MODE, bool FLAT> struct HasFlatMap<PolyGather<T, MODE, FLAT>> { static constexpr bool value = RTMI_FLAT_MAP && FLAT; };
+template <typename T, int MODE, bool FLAT> struct HasFlatMap<PolyGather<T, MODE, FLAT>> { static constexpr bool value = FLAT; };
 template <typename G> struct ReportsSteep { static constexpr bool value = false; };
-template <typename T, int MODE, bool FLAT> struct ReportsSteep<PolyGather<T, MODE, FLAT>> { static constexpr bool value = RTMI_FLAT_MAP && FLAT && sizeof(T) == 8; };
+template <typename T, int MODE, bool FLAT> struct ReportsSteep<PolyGather<T, MODE, FLAT>> { static constexpr bool value = FLAT && sizeof(T) == 8; };
 template <typename T, bool FLAT> struct PolyLaneKept;
 template <typename T, bool FLAT> struct IsPoly<PolyLaneKept<T, FLAT>> { static constexpr bool value = true; };
-template <typename T, bool FLAT> struct ReportsSteep<PolyLaneKept<T, FLAT>> { static constexpr bool value = RTMI_FLAT_MAP && FLAT && sizeof(T) == 8; };
+template <typename T, bool FLAT> struct ReportsSteep<PolyLaneKept<T, FLAT>> { static constexpr bool value = FLAT && sizeof(T) == 8; };
 // ... and gathers the step loops call prefetch() on after every step
 template <typename G> struct HasPrefetch { static constexpr bool value = false; };
 template <typename T, bool FLAT> struct HasPrefetch<PolyLaneKept<T, FLAT>> { static constexpr bool value = true; };
@@ -766,7 +675,7 @@ __device__ __forceinline__ void GlobalGather<T, FLATMAP>::lookup(const FieldDev<
     // 24.0 vs 30.2 ms with the full record (four phases / four waves per SIMD: 15.2 / 24.1 ms).
     Cell<T> cc = c;   // an idle lane reads the grid's first window instead of its stale cell (one shared cache line)
     cc.jx = active ? c.jx : 0; cc.jy = active ? c.jy : 0; cc.lx = active ? c.lx : 3; cc.ly = active ? c.ly : 3;
-    lookup_global_rows<T, RTMI_GLOBAL_PHASES>(F, cc, n, gx, gy);
+    lookup_global_rows<T, 2>(F, cc, n, gx, gy);
 }
 
 // ---------------------------------------------------------------- the field as one polynomial per cell (rt_polytab.h)
@@ -833,12 +742,9 @@ __device__ __forceinline__ float fma_vus(float a, float u, float c) {
     asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(u), "s"(c));
     return d;
 }
-// Horner in u for one row.  SC 1: the coefficients are scalar-register values; SC 2: they are vector registers that must
-// survive the lookup (the kept cell of PolyGather's CACHED mode): three-address fma, or the compiler copies each addend for
-// its two-address v_fmac.  Same operations in every form: same bits.
+// Horner in u for one row.  SC 1: the coefficients are scalar-register values.  Same operations in every form: same bits.
 template <typename T, int SC> __device__ __forceinline__ T poly_row(Quad<T> a, T u) {
     if constexpr (SC == 1) return fma_vus(fma_vus(fma_sus(a.w, u, a.z), u, a.y), u, a.x);
-    else if constexpr (SC == 2) return fma_const(fma_const(fma_const(a.w, u, a.z), u, a.y), u, a.x);
     else return fma_(fma_(fma_(a.w, u, a.z), u, a.y), u, a.x);
 }
 template <typename T, int SC, typename ROW> __device__ __forceinline__ T poly_bicubic(ROW row, int base, T u, T v) {
@@ -848,7 +754,6 @@ template <typename T, int SC, typename ROW> __device__ __forceinline__ T poly_bi
 }
 template <typename T, int SC> __device__ __forceinline__ T poly_bilinear(Quad<T> b, T u, T v) {
     if constexpr (SC == 1) return fma_(fma_sus(b.w, u, b.z), v, fma_sus(b.y, u, b.x));
-    else if constexpr (SC == 2) return fma_(fma_const(b.w, u, b.z), v, fma_const(b.y, u, b.x));
     else return fma_(fma_(b.w, u, b.z), v, fma_(b.y, u, b.x));
 }
 
@@ -859,13 +764,11 @@ template <typename T, int SC> __device__ __forceinline__ T poly_bilinear(Quad<T>
 //   own cell with vector loads.  A fan's wave sits in ONE cell on 98 % of its steps (64 neighbouring rays of 1 M span 4 % of
 //   a cell) and in two on the rest.
 //   !SCALAR: every lane reads its own cell with vector loads (two rows in flight): the per-ray-DELTA_S sweep, field_path 1.
-//   CACHED (the build for at most two waves per SIMD, k_advance_lat): nothing hides a scalar load's latency there (six waits
-//   of ~130 clocks per step measured: cfg2 3.3 ms against 2.3 with the LDS tile), and registers are plentiful, so the wave
-//   KEEPS its cell's 36 coefficients in vector registers (every lane the same values) and reloads them only when the first
-//   live lane's cell changes -- every seventh step on the vert fan; a lookup in the kept cell is 33 fma and no memory access.
+// (The build for few waves, k_advance_lat, keeps every lane's own cell instead: PolyLaneKept below.  Keeping the WAVE's cell
+// in vector registers there, as rounds 3-4 did, was measured slower: see k_advance_lat.)
 // The arithmetic is poly_bicubic / poly_bilinear on the same numbers either way: the result does not depend on the policy,
 // on the wave mates or on which round served the lane.
-constexpr int kPolyLane = 0, kPolyScalar = 1, kPolyCached = 2;
+constexpr int kPolyLane = 0, kPolyScalar = 1;
 // The flat-cell map (FieldDev::flat).  An entry is the cell's constant index, or -- for an ordinary cell -- a NaN: in fp32 fields
 // all-ones bits; in fp64 fields the high word all ones and the low word the cell's STEEPNESS as float bits (0 for most cells).
 // Steepness (k_polytab; rtmi.hip "critical rays"): lambda = sqrt(|Hessian of n| / n) over the cell, the rate (per unit length) at
@@ -913,43 +816,31 @@ template <typename T> __device__ __forceinline__ bool flat_uniform(const FieldDe
 // compiled in.  Left in as run-time tests on a scalar they cost the fisheye fan 4.5 % and the vert fan 1.4 % (register allocation
 // of kernels that sit at their budget, not the two scalar instructions: profiles/r04_ab_flat_tests_cost.txt), so the two hot
 // kernels (k_advance and k_advance_sliced on the wave-shared path) exist in both forms and the host picks.
-template <typename T, int MODE, bool FLAT = true> struct PolyGather {
+// (alignas(8): as a 4-byte object the gather is promoted to registers in another order than the kernels' other locals, and
+// k_field_eval comes out with the same instructions in another register assignment; 8 keeps its code as it was.)
+template <typename T, int MODE, bool FLAT = true> struct alignas(8) PolyGather {
     static constexpr bool SCALAR = MODE == kPolyScalar;
-    static constexpr bool CACHED = MODE == kPolyCached;
-    static constexpr int NA = CACHED ? 9 : 1;     // rows held
     static constexpr bool kPoly = true;
     typedef const Quad<T> __attribute__((address_space(4)))* ScalarRows;
     static __device__ __forceinline__ void eval_scalar(ScalarRows p, T u, T v, T& n, T& gx, T& gy) {
-#if RTMI_POLY_BATCH == 0
-        auto row = [&](int k) -> Quad<T> { return p[k]; };
-        gx = poly_bicubic<T, 1>(row, 0, u, v);
-        gy = poly_bicubic<T, 1>(row, 4, u, v);
-        n = poly_bilinear<T, 1>(p[8], u, v);
-#else
         // scalar loads return out of order, so every wait is for all of them: ask for as many rows at once as the scalar
-        // registers hold (RTMI_POLY_BATCH 1: one spline + n, then the other; 2: everything) instead of row by row
+        // registers hold -- one spline + n, then the other (measured best: row by row waits more often, all nine at once
+        // spills SGPRs)
         Quad<T> a[9];
 #pragma unroll
         for (int k = 0; k < 4; k++) a[k] = p[k];
         a[8] = p[8];
-#if RTMI_POLY_BATCH == 2
-#pragma unroll
-        for (int k = 4; k < 8; k++) a[k] = p[k];
-#endif
         auto row = [&](int k) -> Quad<T> { return a[k]; };
         gx = poly_bicubic<T, 1>(row, 0, u, v);
         n = poly_bilinear<T, 1>(a[8], u, v);
-#if RTMI_POLY_BATCH == 1
         asm volatile("" : "+v"(gx), "+v"(n) : : "memory");
 #pragma unroll
         for (int k = 4; k < 8; k++) a[k] = p[k];
-#endif
         gy = poly_bicubic<T, 1>(row, 4, u, v);
-#endif
     }
     // one lane, its own cell: the flat-cell rule first (a flat cell's coefficients are never read), else the polynomial
     static __device__ __forceinline__ void eval_lane(const FieldDev<T>& F, int cell, T u, T v, T& n, T& gx, T& gy, float& lam) {
-        if (RTMI_FLAT_MAP && FLAT && F.flat) {
+        if (FLAT && F.flat) {
             T cf;
             if (flat_lane(F, cell, cf, lam)) { n = cf; gx = T(0); gy = T(0); return; }
         }
@@ -957,18 +848,6 @@ template <typename T, int MODE, bool FLAT = true> struct PolyGather {
     }
     static __device__ __forceinline__ void eval_lane_poly(const FieldDev<T>& F, int cell, T u, T v, T& n, T& gx, T& gy) {
         const Quad<T>* p = reinterpret_cast<const Quad<T>*>(F.poly + (size_t)cell * kPolyStride);
-        if constexpr (CACHED) {
-            // this build has the registers: all nine rows in flight, one memory latency (the cells of a wave that straddles a
-            // grid line were all used a step ago: L1 hits)
-            Quad<T> a[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) a[k] = p[k];
-            auto row = [&](int k) -> Quad<T> { return a[k]; };
-            gx = poly_bicubic<T, 0>(row, 0, u, v);
-            gy = poly_bicubic<T, 0>(row, 4, u, v);
-            n = poly_bilinear<T, 0>(a[8], u, v);
-            return;
-        }
         T g[2];
 #pragma unroll
         for (int s = 0; s < 2; s++) {
@@ -984,83 +863,21 @@ template <typename T, int MODE, bool FLAT = true> struct PolyGather {
         gx = g[0]; gy = g[1];
         n = poly_bilinear<T, 0>(p[8], u, v);
     }
-    // CACHED: the kept cell and its nine rows (wave-uniform values in vector registers); lanes outside it read their own cell
-    // (218 VGPRs, two waves per SIMD).  Tried and measured slower, A/B in one session each: TWO kept cells (a wave that is
-    // crossing a grid line has lanes on both sides for a few steps; the cell ahead into the slot not served from last) --
-    // 304 VGPRs and twice the control flow: cfg2 2.59 vs 2.21 ms, a one-cell-wide fan 2.00 vs 1.86; reloading through the
-    // scalar cache with 72 copies into the vector registers (no vmcnt wait behind the trajectory stores): 2.54 vs 2.25 ms.
-    int tagA;
-    float lamA;           // CACHED: the kept cell's steepness
     // critical rays (hover_update): the hover sum beyond which a fused fp64 op1/2/6/8 step ends its ray for the re-trace, in units of
     // steepness (kHoverLimit / DELTA_S); +inf where nothing is handed over.  Set by the kernels from BatchDev::hov_limit.
     float hov_limit = __builtin_inff();
-    Quad<T> rowsA[NA];
     // Does this lookup report steepness?  Only where the map's tests are compiled in, and only fp64 (the fp32 map has no room
     // for it and fp32 batches have no reference to be re-traced against).
-    static constexpr bool kSteep = RTMI_FLAT_MAP && FLAT && sizeof(T) == 8;
-    __device__ __forceinline__ void init() { tagA = -1; lamA = 0.f; }
-    template <int N> static __device__ __forceinline__ void eval_rows(const Quad<T> (&rows)[N], T u, T v, T& n, T& gx, T& gy) {
-        auto row = [&](int k) -> Quad<T> { return rows[N == 9 ? k : 0]; };
-        gx = poly_bicubic<T, 2>(row, 0, u, v);
-        gy = poly_bicubic<T, 2>(row, 4, u, v);
-        n = poly_bilinear<T, 2>(rows[N == 9 ? 8 : 0], u, v);
-    }
-    template <int N> static __device__ __forceinline__ void load_rows(Quad<T> (&rows)[N], const FieldDev<T>& F, int cu, float& lam) {
-        lam = 0.f;
-        if (RTMI_FLAT_MAP && FLAT && F.flat) {       // a flat cell is kept as the polynomial (b0, 0, ...): eval_rows then gives (b0, 0, 0) exactly
-            T cf;
-            if (flat_uniform(F, cu, cf, lam)) {
-#pragma unroll
-                for (int k = 0; k < N; k++) rows[k] = Quad<T>{T(0), T(0), T(0), T(0)};
-                rows[N == 9 ? 8 : 0].x = cf;
-                return;
-            }
-        }
-#if RTMI_LAT_RELOAD == 1
-        // through the scalar cache, three rows at a time, copied into the kept cell's vector registers: scalar loads count in
-        // lgkmcnt, so this reload does not wait for the trajectory stores of the steps before (vmcnt is one in-order counter)
-        {
-            ScalarRows p = (ScalarRows)(F.poly + (size_t)cu * kPolyStride);
-            asm volatile("" : "+s"(p));
-#pragma unroll
-            for (int g = 0; g < N; g += 3) {
-                Quad<T> a0 = p[g], a1 = p[g + 1 < N ? g + 1 : g], a2 = p[g + 2 < N ? g + 2 : g];
-                rows[g] = a0;
-                if (g + 1 < N) rows[g + 1] = a1;
-                if (g + 2 < N) rows[g + 2] = a2;
-                asm volatile("" : "+v"(rows[g]) : : "memory");
-            }
-            return;
-        }
-#endif
-        // every lane loads the same 288 bytes (one address per instruction: a broadcast in the texture path)
-        typedef const Quad<T> __attribute__((address_space(1)))* GlobalRows;
-        GlobalRows p = (GlobalRows)(F.poly + (size_t)cu * kPolyStride);
-        asm volatile("" : "+v"(p));          // a per-lane address on purpose: vector loads into vector registers
-#pragma unroll
-        for (int k = 0; k < N; k++) rows[k] = p[k];
-        // retire the loads here, in the rare branch: left pending they make every later step's first use of a row wait for
-        // vmcnt(0), which also counts the trajectory stores of the step before
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-    }
+    static constexpr bool kSteep = FLAT && sizeof(T) == 8;
     // lam: the steepness of the cell the lane's point lies in (0 in almost every cell, see FlatBits above), for Ray::hov
     __device__ __forceinline__ void lookup_xy(const FieldDev<T>& F, bool active, T x, T y, T& n, T& gx, T& gy, float& lam) {
         PolyCell<T> c;
         const unsigned long long live = rt_ballot(active);
         poly_locate(F, x, y, live, c);
         lam = 0.f;
-        if constexpr (CACHED || SCALAR) {
+        if constexpr (SCALAR) {
             // no live lane (the step loops leave before this can happen): nothing addresses the table with an idle lane's cell
             if (live == 0ull) { n = T(1); gx = T(0); gy = T(0); return; }
-        }
-        if constexpr (CACHED) {
-            const int cu = __builtin_amdgcn_readlane(c.cell, __builtin_ctzll(live));
-            if (cu != tagA) { load_rows(rowsA, F, cu, lamA); tagA = cu; }
-            // every lane evaluates the first live lane's cell in straight-line code; lanes of another cell are redone
-            eval_rows(rowsA, c.u, c.v, n, gx, gy);
-            lam = lamA;
-            if (active && c.cell != cu) eval_lane(F, c.cell, c.u, c.v, n, gx, gy, lam);
-        } else if constexpr (SCALAR) {
             // the first live lane's cell; when every live lane is in it (98 % of a fan's wave-steps) all lanes evaluate its
             // polynomial in straight-line code -- an idle lane too, at its own (u, v) in [0, 1)^2: finite, and nobody reads it
             int cu = __builtin_amdgcn_readlane(c.cell, __builtin_ctzll(live));
@@ -1069,7 +886,7 @@ template <typename T, int MODE, bool FLAT = true> struct PolyGather {
             ScalarRows p = (ScalarRows)(F.poly + (size_t)cu * kPolyStride);
             asm volatile("" : "+s"(p));
             if ((rt_ballot(c.cell != cu) & live) == 0ull) {
-                if (RTMI_FLAT_MAP && FLAT && F.flat) {
+                if (FLAT && F.flat) {
                     T cf;
                     if (flat_uniform(F, cu, cf, lam)) { n = cf; gx = T(0); gy = T(0); return; }     // scalar branch: the map entry is wave-uniform
                 }
@@ -1089,7 +906,7 @@ template <typename T, int MODE, bool FLAT = true> struct PolyGather {
                     if (c.cell == cu) {
                         T cf;
                         float lu = 0.f;
-                        if (RTMI_FLAT_MAP && FLAT && F.flat && flat_uniform(F, cu, cf, lu)) { n = cf; gx = T(0); gy = T(0); }
+                        if (FLAT && F.flat && flat_uniform(F, cu, cf, lu)) { n = cf; gx = T(0); gy = T(0); }
                         else eval_scalar(p, c.u, c.v, n, gx, gy);
                         lam = lu;
                         todo = false;
@@ -1114,7 +931,7 @@ template <typename T, int MODE, bool FLAT = true> struct PolyGather {
 // in (a ray stays ~10 steps in a cell), all ten loads of a new cell go out together, and the step loop starts them a step AHEAD
 // (prefetch: where the ray will be after the next step if it goes on as it goes now), so they travel while the step's arithmetic
 // runs.  A wrong guess costs a reload at the point of use, never a wrong value: the tag is the cell the registers hold.
-// The polynomial is evaluated on vector registers exactly as PolyGather's kept cell is (the same Horner chain, the same bits);
+// The polynomial is evaluated on vector registers exactly as PolyGather's per-lane path is (the same Horner chain, the same bits);
 // a flat cell's entry overrides it with (constant, 0, 0) like flat_lane does.
 template <typename T, bool FLAT = true> struct PolyLaneKept {
     static constexpr bool kPoly = true;
@@ -1130,7 +947,7 @@ template <typename T, bool FLAT = true> struct PolyLaneKept {
     }
     __device__ __forceinline__ void load(const FieldDev<T>& F, int cell) {
         tag = cell;
-        if (RTMI_FLAT_MAP && FLAT) ent = F.flat ? reinterpret_cast<const B*>(F.poly)[(long)cell - (long)F.flat] : ~(B)0;
+        if (FLAT) ent = F.flat ? reinterpret_cast<const B*>(F.poly)[(long)cell - (long)F.flat] : ~(B)0;
         const Quad<T>* p = reinterpret_cast<const Quad<T>*>(F.poly + (size_t)cell * kPolyStride);
 #pragma unroll
         for (int k = 0; k < 9; k++) rows[k] = p[k];
@@ -1144,7 +961,7 @@ template <typename T, bool FLAT = true> struct PolyLaneKept {
         gy = poly_bicubic<T, 0>(row, 4, c.u, c.v);
         n = poly_bilinear<T, 0>(rows[8], c.u, c.v);
         lam = 0.f;
-        if (RTMI_FLAT_MAP && FLAT) {
+        if (FLAT) {
             const bool fl = flat_entry<T>(ent);
             lam = fl ? 0.f : steep_of<T>(ent);
             if (fl) { n = __builtin_bit_cast(T, ent); gx = T(0); gy = T(0); }
@@ -1224,9 +1041,7 @@ template <typename T> __device__ __forceinline__ void adv_first(const Ray<T>& r,
         fy = fma_(r.uy, step, r.y);
     }
 }
-// eps: the step's chord is DELTA_S sqrt(1 + eps) -- the displacement is DELTA_S u + (DELTA_S^2 / 2n) v with v = grad n - (grad n . u) u
-// perpendicular to the unit tangent u, so eps = (DELTA_S / 2n)^2 |v|^2 (see chord_length)
-template <typename T> __device__ __forceinline__ void adv_second(const Ray<T>& r, const Consts<T>& k, Acc& fx, Acc& fy, T& eps) {
+template <typename T> __device__ __forceinline__ void adv_second(const Ray<T>& r, const Consts<T>& k, Acc& fx, Acc& fy) {
     const T d = fma_(r.gy, r.uy, r.gx * r.ux);  // np.dot on 2 elements rounds exactly like this
     const T s = k.step2h * r.rn;                // step**2 / (2 n)
     const T vx = fma_(-d, r.ux, r.gx), vy = fma_(-d, r.uy, r.gy);
@@ -1237,25 +1052,19 @@ template <typename T> __device__ __forceinline__ void adv_second(const Ray<T>& r
         fx = fma_(vx, s, fma_(r.ux, k.step, r.x));
         fy = fma_(vy, s, fma_(r.uy, k.step, r.y));
     }
-#if RTMI_CHORD_SERIES > 1
-    const T q = (k.step * T(0.5)) * r.rn;       // the constant product folds on the host side of the loop
-    eps = q * q * fma_(vy, vy, vx * vx);
-#else
-    eps = T(-1);
-#endif
 }
 // The arclength of one step, np.linalg.norm(old - new) in the reference (:785).  The reference takes it from the ROUNDED
 // positions (a 2.6e-3 difference of coordinates of order 5: 2e-13 relative noise per step); from the advancement itself it is
 // DELTA_S sqrt(1 + eps) exactly, and for eps < 2^-26 (everywhere but within a few cells of the interface scenario's jump)
 // DELTA_S (1 + eps/2) to 2^-55: one fma instead of two subtractions, a square root by rsq + 6 and its transcendental.  eps < 0:
-// no closed form (curvature advancement): from the positions.  Per-lane choice; the vote selects the layout.
+// no closed form (the second-order and curvature advancements): from the positions.  Per-lane choice; the vote selects the
+// layout.  (The second-order advancement's eps = (DELTA_S / 2n)^2 |grad n - (grad n . u) u|^2 was measured slower: the vote
+// and eps carried across the lookup cost more than the square root -- headline 14.9 -> 15.5 ms, cfg2 2.20 -> 2.48.)
 template <typename T> __device__ __forceinline__ T chord_length(const Consts<T>& k, const Ray<T>& r, Acc fx, Acc fy, T eps) {
-#if RTMI_CHORD_SERIES
     const bool series = eps >= T(0) && eps < T(1.4901161193847656e-08);
     if (rt_ballot(!series) == 0ull) return fma_(k.step * T(0.5), eps, k.step);
     if (series) return fma_(k.step * T(0.5), eps, k.step);
     if (eps >= T(0)) return k.step * M<T>::sqrt_(T(1) + eps);
-#endif
     const T dx = (T)(r.x - fx), dy = (T)(r.y - fy);
     return M<T>::sqrt_(fma_(dy, dy, dx * dx));  // np.linalg.norm on 2 elements
 }
@@ -1298,10 +1107,7 @@ template <typename T> __device__ __forceinline__ Acc ang_rk2(const Ray<T>& r, T 
 // theta + atan(ys / yc) with |ys / yc| << 1 -- a reciprocal and a five-term series (|t| < 2^-5: the next term is t^10/11 <
 // 2^-53) instead of a full atan2 of the untouched components (~65 instructions in ocml) -- and it is better conditioned too:
 // the products with n that the two components share cancel before anything is rounded.  A lane whose turn is larger, or
-// whose vector points backwards, takes atan2 itself; the vote only selects the layout.  RTMI_ATAN_NEAR 0: always atan2.
-#ifndef RTMI_ATAN_NEAR
-#define RTMI_ATAN_NEAR 1
-#endif
+// whose vector points backwards, takes atan2 itself; the vote only selects the layout.
 template <typename T> __device__ __forceinline__ Acc angle_near(Acc theta, T ux, T uy, T ys, T yc) {
     const T t = ys * rcp_full(yc);
     const bool near = yc > T(0) && M<T>::abs_(t) < T(0.03125) && __builtin_fabs(theta) <= Acc(3.141592653589793);   // (a launch angle beyond +-pi: atan2 folds it)
@@ -1321,13 +1127,9 @@ template <typename T> __device__ __forceinline__ Acc angle_near(Acc theta, T ux,
     return near ? series() : full();
 }
 template <typename T> __device__ __forceinline__ Acc ang_cost(const Ray<T>& r, T step, T fgx, T fgy) {
-#if RTMI_ATAN_NEAR
     // P = n u + I (momentum + impulse): across the tangent I x u... = I_y u_x - I_x u_y, along it n + I . u (|u| = 1)
     const T ix = impulse(r.gx, fgx, step), iy = impulse(r.gy, fgy, step);
     return angle_near<T>(r.th, r.ux, r.uy, fma_(iy, r.ux, -(ix * r.uy)), r.n + fma_(ix, r.ux, iy * r.uy));
-#else
-    return (Acc)M<T>::atan2_(fma_(r.n, r.uy, impulse(r.gy, fgy, step)), fma_(r.n, r.ux, impulse(r.gx, fgx, step)));
-#endif
 }
 
 // golden() (:175-199) on a cost functor; recomputes both cost values every iteration like the
@@ -1380,9 +1182,9 @@ __device__ __forceinline__ T ang_golden_aniso(const Ray<T>& r, const Consts<T>& 
 // ---- opN (:469-764), split around the field lookup: advancement, then angle determination
 template <typename T, int METHOD>
 __device__ __forceinline__ bool op_advance(const Consts<T>& k, const Ray<T>& r, Acc& fx, Acc& fy, T& eps) {
-    if constexpr (METHOD == 1 || METHOD == 2) { adv_first(r, k.step, fx, fy); eps = RTMI_CHORD_SERIES ? T(0) : T(-1); return true; }   // |u| = 1: the chord is DELTA_S
+    if constexpr (METHOD == 1 || METHOD == 2) { adv_first(r, k.step, fx, fy); eps = T(0); return true; }   // |u| = 1: the chord is DELTA_S (op1 12.5 -> 11.8 ms)
     else if constexpr (METHOD == 3 || METHOD == 4 || METHOD == 5 || METHOD == 10) { eps = T(-1); return adv_curv(r, k, fx, fy); }
-    else { adv_second(r, k, fx, fy, eps); return true; }
+    else { adv_second(r, k, fx, fy); eps = T(-1); return true; }
 }
 template <typename T, int METHOD>
 __device__ __forceinline__ Acc op_angle(const Consts<T>& k, const Ray<T>& r, bool flag, Acc fx, Acc fy, T fn, T fgx, T fgy, T frn) {
@@ -1397,11 +1199,7 @@ __device__ __forceinline__ Acc op_angle(const Consts<T>& k, const Ray<T>& r, boo
     else {  // 7: finite_diff (:370-372) over [P0, P1, P2, P3] = [h0, h1, (x,y), f]; position differences in fp64
         const T vx = (T)(Acc(11) * fx - Acc(18) * r.x + Acc(9) * (Acc)r.hx1 - Acc(2) * (Acc)r.hx0);
         const T vy = (T)(Acc(11) * fy - Acc(18) * r.y + Acc(9) * (Acc)r.hy1 - Acc(2) * (Acc)r.hy0);
-#if RTMI_ATAN_NEAR
         return angle_near<T>(r.th, r.ux, r.uy, fma_(vy, r.ux, -(vx * r.uy)), fma_(vx, r.ux, vy * r.uy));
-#else
-        return (Acc)M<T>::atan2_(vy, vx);
-#endif
     }
 }
 
@@ -1477,28 +1275,14 @@ inline bool is_exact_method(int method) { return method == 3 || method == 4 || m
 // reference.  1024 rather than a shorter period: with lane refill the lanes of a wave are at rows of their own, and a
 // wave takes the slow two-formula layout whenever any of its 64 lanes refreshes (6 % of its steps at 1024, 22 % at 256).
 constexpr int kUnitRefresh = 1024;
-#ifndef RTMI_UNIT_REFRESH_F32
 // fp32 batches keep the from-scratch sincos: rotating in fp32 with a refresh every 16 rows gains 6 % on cfg4 but moves end
 // points from 3.9e-7 to 1.5e-6 of the fp64 path (every 64 rows: 6e-6) -- measured on 65 536-ray fans, not adopted.
-#define RTMI_UNIT_REFRESH_F32 0     // > 0: fp32 op2/op6 rotate the unit vector too, recomputing it every this many rows
-#endif
-template <typename T, int METHOD> struct RotatesUnit {
-    static constexpr bool value = (RTMI_UNIT_REFRESH_F32 > 0) && (METHOD == 2 || METHOD == 6);
-    static constexpr int refresh = RTMI_UNIT_REFRESH_F32 > 0 ? RTMI_UNIT_REFRESH_F32 : 1;
-};
-// op1 and op8 as well (RTMI_ROT_18): their new angle is the old one plus a small turn too (angle_near), so their unit tangent
-// is rotated like op2/op6's.  op7 is not: its two extra state arrays' slots are the history's.
-#ifndef RTMI_ROT_18
-#define RTMI_ROT_18 1
-#endif
-constexpr bool rotating_method(int m) { return m == 2 || m == 6 || (RTMI_ROT_18 && RTMI_ATAN_NEAR && (m == 1 || m == 8)); }
-template <int METHOD> struct RotatesUnit<double, METHOD> {
-    static constexpr bool value = rotating_method(METHOD);
-    static constexpr int refresh = kUnitRefresh;
-};
-inline bool rotates_unit(int method, bool f64) {
-    return f64 ? rotating_method(method) : (RTMI_UNIT_REFRESH_F32 > 0 && (method == 2 || method == 6));
-}
+template <typename T, int METHOD> struct RotatesUnit { static constexpr bool value = false; };
+// op1 and op8 as well: their new angle is the old one plus a small turn too (angle_near), so their unit tangent is rotated
+// like op2/op6's.  op7 is not: its two extra state arrays' slots are the history's.
+constexpr bool rotating_method(int m) { return m == 2 || m == 6 || m == 1 || m == 8; }
+template <int METHOD> struct RotatesUnit<double, METHOD> { static constexpr bool value = rotating_method(METHOD); };
+inline bool rotates_unit(int method, bool f64) { return f64 && rotating_method(method); }
 
 // One iteration of trazar's loop for row index i (the row being produced); returns "still inside the box".
 // For op7 rows 1 and 2 are the bootstrap steps (:833-864): first- and second-order backward differences and
@@ -1578,7 +1362,7 @@ __device__ __forceinline__ bool ray_step(const FieldDev<T>& F, const Consts<T>& 
         fth = op_angle<T, METHOD>(k, r, flag, fx, fy, fn, fgx, fgy, frn);
     }
     if constexpr (RotatesUnit<T, METHOD>::value)
-        store_update<T, ISO, true>(k, r, fx, fy, fth, fn, fgx, fgy, frn, eps, (i & (RotatesUnit<T, METHOD>::refresh - 1)) == 0);
+        store_update<T, ISO, true>(k, r, fx, fy, fth, fn, fgx, fgy, frn, eps, (i & (kUnitRefresh - 1)) == 0);
     else
         store_update<T, ISO>(k, r, fx, fy, fth, fn, fgx, fgy, frn, eps);
     bool calm = true;

@@ -49,25 +49,15 @@ __device__ __attribute__((noinline)) SinCos sincos_(double x) {
 // coefficients per wave-step through the vector L1, which keeps evicting the table's lines (52 of an interface x op9 step's
 // 86 vector-memory instructions are table reads).  Staged once per block by stage_sincos_tab() (rtmi.hip calls it at the top of
 // every kernel body that can reach sincos_inline); the out-of-line sincos_ / sin_ / cos_ keep reading the table in memory.
-#ifndef RTMI_LDS_SINCOS
-#define RTMI_LDS_SINCOS 1
-#endif
 __device__ __forceinline__ RT_LDS double* sincos_tab_lds() {
     __shared__ double t[4 * RT_SINCOS_TAB_ENTRIES];
     return (RT_LDS double*)t;
 }
 __device__ __forceinline__ void stage_sincos_tab() {       // every thread of the block
-#if RTMI_LDS_SINCOS
     RT_LDS double* t = sincos_tab_lds();
     for (int i = (int)threadIdx.x; i < 4 * RT_SINCOS_TAB_ENTRIES; i += (int)blockDim.x) t[i] = kSinCosTab[i];
     __syncthreads();
-#endif
 }
-#if RTMI_LDS_SINCOS
-#define RT_EX_SINCOS_TAB ((const RT_LDS double*)sincos_tab_lds())
-#else
-#define RT_EX_SINCOS_TAB kSinCosTab
-#endif
 // sin and cos of one angle, glibc's bits, INLINE for the two ranges a golden-section bracket point lies in (theta -+ h with
 // h <= 0.6: 2^-26 <= |x| < 0.855469, the table step on x itself, and |x| < 2.426265, through pi/2 - |x|); anything else
 // calls sincos_().  Same operations as gl::sin / gl::cos: same bits.  For exact_lt_iso below, which pays this twice per
@@ -75,16 +65,17 @@ __device__ __forceinline__ void stage_sincos_tab() {       // every thread of th
 // of the methods that gain from having them inline (sincos_sel, inline_sincos).
 __device__ __forceinline__ SinCos sincos_inline(double x) {
     const unsigned k = gl::hi_word_(x);
+    const RT_LDS double* tab = sincos_tab_lds();
     SinCos r;
     if (k - 0x3e500000u < 0x3feb6000u - 0x3e500000u) {
-        r.s = gl::table_sin(RT_EX_SINCOS_TAB, x, 0.0);
-        r.c = gl::table_cos(RT_EX_SINCOS_TAB, x, 0.0);
+        r.s = gl::table_sin(tab, x, 0.0);
+        r.c = gl::table_cos(tab, x, 0.0);
     } else if (k - 0x3feb6000u < 0x400368fdu - 0x3feb6000u) {
         const double y = gl::kHp0 - __builtin_fabs(x);
-        r.s = __builtin_copysign(gl::table_cos(RT_EX_SINCOS_TAB, y, gl::kHp1), x);
+        r.s = __builtin_copysign(gl::table_cos(tab, y, gl::kHp1), x);
         const double a = y + gl::kHp1;
         const double da = (y - a) + gl::kHp1;
-        r.c = gl::table_sin(RT_EX_SINCOS_TAB, a, da);
+        r.c = gl::table_sin(tab, a, da);
     } else {
         r = sincos_(x);
     }
@@ -259,9 +250,6 @@ __device__ __forceinline__ void field_combine(const Cell<double>& c, const doubl
 // per lookup in the per-lane form), no address arithmetic, no knot arithmetic, and none of the 72 vector registers the window
 // is staged in.  The operations on the per-lane numbers (x, y, the basis values, the sums) are axis_exact's and
 // field_combine's, one for one: the same bits.  A wave in several cells takes the per-lane form.
-#ifndef RTMI_EXACT_UNIFORM
-#define RTMI_EXACT_UNIFORM 1
-#endif
 // The per-lane fallback reads its 4 x 4 window in this many groups of rows (1: all 36 coefficients in flight, 72 staging registers).
 // fpbisp's sums run row by row anyway -- same order, same bits -- and with the window path in front of it the fallback no longer
 // has to be the fast one, only not to set the kernel's register count: in two groups op3's kernel has 117 instead of 143 vector
@@ -363,7 +351,7 @@ constexpr bool window_votes(int method) { return method != 9; }
 template <int PH = 1, bool EST = true, bool VOTE = false, typename G>
 __device__ __forceinline__ void n_gradient(const FieldDev<double>& F, G& gather, bool active, double x, double y,
                                            double& n, double& gx, double& gy, int* cellp = nullptr) {
-    if constexpr (RTMI_EXACT_UNIFORM && G::kUniformWindow) {
+    if constexpr (G::kUniformWindow) {
         const unsigned long long live = rt_ballot(active && F.window != 0);     // no lane is asked when the batch does not use the window
         if (live != 0ull) {
             const int lead = __builtin_ctzll(live);
@@ -390,7 +378,7 @@ __device__ __forceinline__ void n_gradient(const FieldDev<double>& F, G& gather,
     Cell<double> c;
     ex::field_locate(F, x, y, c);
     if (cellp) *cellp = c.jy * F.ncx + c.jx;
-    if constexpr (RTMI_EXACT_UNIFORM && G::kUniformWindow && PH > 1) {
+    if constexpr (G::kUniformWindow && PH > 1) {
         // the per-lane gather with the window consumed in groups of rows: fpbisp's sums run row by row anyway (same order, same
         // bits), and the kernel's register count is no longer set by 72 staging registers of a path a coherent wave rarely takes
         Cell<double> cc = c;   // an idle lane reads the grid's first window instead of its stale cell (one shared cache line)
@@ -507,10 +495,9 @@ struct GoldBounds { double K1, LIP, K2, K3; };
 // third-order expansion of the cost about one angle: |e_x| + |e_y| there, and the cost's first three derivatives
 struct GoldExpansion { double g0, F1, F2, F3; };
 
-#ifndef RTMI_GOLD_TAYLOR_FROM
-#define RTMI_GOLD_TAYLOR_FROM 11   // iterations of phase A; bracket width pi*GR^11 = 1.6e-2 when phase T takes over (A/B: 14: 170 ms for cfg5, 12: 159.5, 11: 156.4, 10: 160, 9: 164)
-#endif
-constexpr int kGoldTaylorFrom = RTMI_GOLD_TAYLOR_FROM;
+// iterations of phase A; bracket width pi*GR^11 = 1.6e-2 when phase T takes over (A/B: 14: 170 ms for cfg5, 12: 159.5, 11: 156.4,
+// 10: 160, 9: 164)
+constexpr int kGoldTaylorFrom = 11;
 static_assert(kGoldTaylorFrom <= RT_GOLD_ROT_ENTRIES, "phase A rotates through rt_golden_rot.h");
 __device__ const double kGoldRot[2 * RT_GOLD_ROT_ENTRIES] = {RT_GOLD_ROT_VALUES};
 constexpr double kU = 1.1102230246251565e-16;   // 2^-53
@@ -580,10 +567,7 @@ __device__ __forceinline__ double golden_filtered(FastA fast_a, double EA, Expan
     const double eps0 = kU * (16.0 + 4.0 * __builtin_fabs(th));
     const double F2h = 0.5 * T.F2, F36 = T.F3 * (1.0 / 6.0);
     // |d4F/dt4| <= 4 (E0 E4 + 4 E1 E3 + 3 E2^2), E0 = sup |e| <= g0 + E1 rho, for rho <= kRhoMax
-#ifndef RTMI_GOLD_RHO_MAX
-#define RTMI_GOLD_RHO_MAX 0.03125
-#endif
-    constexpr double kRhoMax = RTMI_GOLD_RHO_MAX;
+    constexpr double kRhoMax = 0.03125;
     const double M4c = (1.001 / 12.0) * 4.0 * fma_(T.g0 + E[1] * kRhoMax, E[4], fma_(4.0 * E[1], E[3], 3.0 * E[2] * E[2]));
     // V's coefficients: F1 = 2 e.e1 inherits e's absolute error e_abs (e is a cancelled difference, its derivative is not);
     // F2, F3 and the evaluation of V a relative 64u of their terms (|sigma| <= 2 rho, |pi2| <= 3 rho^2)
@@ -912,7 +896,7 @@ __device__ __forceinline__ void derive(const Consts<double>& k, Ray<double>& r) 
 __device__ __forceinline__ bool grad_stale(const Ray<double>& r) { return r.rn == 1.0 || r.rn == 3.0; }
 __device__ __forceinline__ bool in_flat_cell(const Ray<double>& r) { return r.rn >= 2.0; }
 __device__ __forceinline__ void set_flat_flags(Ray<double>& r, bool stale, bool flat) { r.rn = (flat ? 2.0 : 0.0) + (stale ? 1.0 : 0.0); }
-template <int METHOD> constexpr bool flat_shortcut() { return RTMI_FLAT_MAP && (METHOD == 1 || METHOD == 2 || METHOD == 6 || METHOD == 8); }
+template <int METHOD> constexpr bool flat_shortcut() { return METHOD == 1 || METHOD == 2 || METHOD == 6 || METHOD == 8; }
 template <typename G> struct IsGlobalGather { static constexpr bool value = false; };
 template <> struct IsGlobalGather<GlobalGather<double, true>> { static constexpr bool value = true; };
 

@@ -560,9 +560,8 @@ static int field_finish_impl(rtmi_field* f, double delta) {
             unsigned long long* dcnt = nullptr;      // [0] bits of max |gradient-spline coefficient|, [1] flat cells, [2] steep cells
             HIP_TRY(hipMalloc(&dcnt, 3 * sizeof(unsigned long long)));
             unsigned long long hcnt[3] = {0, 0, 0};
-            // steep: lambda >= kSteepRate / the grid's shorter side (RTMI_STEEP_RATE overrides, for calibration runs)
-            const double steep_rate = getenv("RTMI_STEEP_RATE") ? atof(getenv("RTMI_STEEP_RATE")) : kSteepRate;
-            const double lam0 = steep_rate / std::fmin(f->bx - f->ax, f->by - f->ay);
+            // steep: lambda >= kSteepRate / the grid's shorter side
+            const double lam0 = kSteepRate / std::fmin(f->bx - f->ax, f->by - f->ay);
             hipError_t e = hipMemsetAsync(dcnt, 0, sizeof(hcnt), st);
             if (e == hipSuccess) {
                 hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, st, f->dCdx, f->dCdy, nz, dcnt);
@@ -579,8 +578,8 @@ static int field_finish_impl(rtmi_field* f, double delta) {
             if (e == hipSuccess) e = hipStreamSynchronize(st);  // the host tables go out of scope
             (void)hipFree(dcnt);
             HIP_TRY(e);
-            f->flat_cells = getenv("RTMI_NO_FLAT") ? 0 : (long)hcnt[1];     // RTMI_NO_FLAT=1: A/B without the map
-            f->steep_cells = getenv("RTMI_NO_FLAT") ? 0 : (long)hcnt[2];
+            f->flat_cells = (long)hcnt[1];
+            f->steep_cells = (long)hcnt[2];
             memcpy(&f->gmax, &hcnt[0], sizeof(double));
             if (getenv("RTMI_DEBUG")) fprintf(stderr, "rtmi: field %d x %d: %ld of %zu cells flat, %ld steep (lambda >= %.3g)\n", qx, qy, (long)hcnt[1], ncell, (long)hcnt[2], lam0);
         }
@@ -820,11 +819,7 @@ template <> __device__ __forceinline__ void derive_rt<double>(const BatchDev<dou
     else if (a.iso) rt::derive<double, true>(a.K, r);
     else rt::derive<double, false>(a.K, r);
 }
-#if RTMI_POLY
 template <typename T> using InitGather = rt::PolyGather<T, rt::kPolyLane>;     // the fast forms' lookup, one lane per ray
-#else
-template <typename T> using InitGather = rt::GlobalGather<T>;
-#endif
 template <typename T> __device__ __forceinline__ void n_gradient_rt(const BatchDev<T>& a, T x, T y, T& n, T& gx, T& gy) {
     InitGather<T> gg;
     rt::n_gradient(a.F, gg, true, x, y, n, gx, gy);
@@ -939,42 +934,33 @@ template <typename T> __device__ __forceinline__ void idle_ray(const BatchDev<T>
 
 // Gather policy of a step kernel.  Reference-order methods (rt_exact.h: FITPACK's sums on the B-spline window): the LDS tile
 // (LDS) or global gathers.  Fast-form methods and every fp32 batch: the cell's polynomial (rt::PolyGather), through the scalar
-// cache for a coherent wave (LDS) or with per-lane loads.  RTMI_POLY 0 builds the fast forms on the B-spline window as well.
-template <typename T, int METHOD> constexpr bool uses_poly() { return RTMI_POLY && (!rt::IsExact<T, METHOD>::value || (METHOD & rt::kFastField) != 0); }
-#ifndef RTMI_LAT_LANEKEPT
-#define RTMI_LAT_LANEKEPT 1
-#endif
+// cache for a coherent wave (LDS) or with per-lane loads.
+template <typename T, int METHOD> constexpr bool uses_poly() { return !rt::IsExact<T, METHOD>::value || (METHOD & rt::kFastField) != 0; }
 template <typename T, int METHOD, bool LDS> constexpr bool uses_tile() { return LDS && !uses_poly<T, METHOD>(); }
 // NOFLAT: the field has no flat cell (rt::PolyGather's FLAT false: the flat-cell map's tests compiled out).
-template <typename T, int METHOD, bool LDS, int PH = RTMI_TILE_PHASES, bool NOFLAT = false, bool POLY = uses_poly<T, METHOD>()> struct GatherOf { using type = rt::GlobalGather<T, !NOFLAT>; };
-template <typename T, int METHOD, int PH, bool NOFLAT> struct GatherOf<T, METHOD, true, PH, NOFLAT, false> { using type = rt::LdsGather<T, PH>; };
-template <typename T, int METHOD, bool LDS, int PH, bool NOFLAT> struct GatherOf<T, METHOD, LDS, PH, NOFLAT, true> {
-#if RTMI_LAT_LANEKEPT
-    // PH 1: k_advance_lat -- every lane its own kept cell, the next cell's loads a step ahead (rt::PolyLaneKept)
-    using type = std::conditional_t<LDS && PH == 1, rt::PolyLaneKept<T, !NOFLAT>, rt::PolyGather<T, !LDS ? rt::kPolyLane : rt::kPolyScalar, !NOFLAT>>;
-#else
-    using type = rt::PolyGather<T, !LDS ? rt::kPolyLane : PH == 1 ? rt::kPolyCached : rt::kPolyScalar, !NOFLAT>;   // PH 1: k_advance_lat
-#endif
+template <typename T, int METHOD, bool LDS, bool NOFLAT = false, bool POLY = uses_poly<T, METHOD>()> struct GatherOf { using type = rt::GlobalGather<T, !NOFLAT>; };
+template <typename T, int METHOD, bool NOFLAT> struct GatherOf<T, METHOD, true, NOFLAT, false> { using type = rt::LdsGather<T>; };
+template <typename T, int METHOD, bool LDS, bool NOFLAT> struct GatherOf<T, METHOD, LDS, NOFLAT, true> {
+    using type = rt::PolyGather<T, !LDS ? rt::kPolyLane : rt::kPolyScalar, !NOFLAT>;
 };
 template <typename T, bool LDS, bool FM> __device__ __forceinline__ void gather_init(rt::GlobalGather<T, FM>&, T*) {}
 // the per-lane gather of a build with the flat path compiled in (reference-order op1/2/6/8 on a field with flat cells) carries gflat
 template <typename T, typename G> __device__ __forceinline__ void gather_flat_bound(G&, const BatchDev<T>&) {}
 template <> __device__ __forceinline__ void gather_flat_bound<double, rt::GlobalGather<double, true>>(rt::GlobalGather<double, true>& g, const BatchDev<double>& a) { g.gflat = a.gflat; }
-template <typename T, bool LDS, int MODE, bool FLAT> __device__ __forceinline__ void gather_init(rt::PolyGather<T, MODE, FLAT>& g, T*) { g.init(); }
+template <typename T, bool LDS, int MODE, bool FLAT> __device__ __forceinline__ void gather_init(rt::PolyGather<T, MODE, FLAT>&, T*) {}
 template <typename T, bool LDS, bool FLAT> __device__ __forceinline__ void gather_init(rt::PolyLaneKept<T, FLAT>& g, T*) { g.init(); }
 // LDS of a step kernel in units of T: the reference-order methods' tile; the polynomial lookup needs none.  (An L2 prefetch of
 // the cells ahead -- global_load_lds into a per-wave sink whenever the wave's cell changes -- was measured: interface 23.6 ->
 // 23.0 ms, but fisheye, a new cell every step, 8.3 -> 9.1, vert_heterogeneous 8.8 -> 9.0, fp32 48.7 -> 49.6: not kept.)
-template <typename T, int METHOD, bool LDS, int PH = RTMI_TILE_PHASES> constexpr int kernel_lds_elems() {
-    return uses_tile<T, METHOD, LDS>() ? 4 * rt::LdsGather<T, PH>::ELEMS : 2;
+template <typename T, int METHOD, bool LDS> constexpr int kernel_lds_elems() {
+    return uses_tile<T, METHOD, LDS>() ? 4 * rt::LdsGather<T>::ELEMS : 2;
 }
-template <typename T, bool LDS, int PH> __device__ __forceinline__ void gather_init(rt::LdsGather<T, PH>& g, T* lds) {
-    g.init(lds + (threadIdx.x >> 6) * rt::LdsGather<T, PH>::ELEMS);
+template <typename T, bool LDS> __device__ __forceinline__ void gather_init(rt::LdsGather<T>& g, T* lds) {
+    g.init(lds + (threadIdx.x >> 6) * rt::LdsGather<T>::ELEMS);
 }
 
 // A ray's state is stored once, when it terminates: the batch members that needs (state slab, istep, alive) are re-read
 // from the kernel-argument segment there instead of occupying scalar registers for the whole loop (see rt::rare_field).
-#ifndef RTMI_NO_KERNARG_FIELD
 template <typename T> __device__ __forceinline__ BatchDev<T> rare_batch(const BatchDev<T>&) {
     static_assert(__builtin_offsetof(BatchDev<T>, F) == 0, "rt::rare_field reads the FieldDev at offset 0 of the kernel arguments");
     typedef const BatchDev<T> __attribute__((address_space(4))) * KP;
@@ -984,52 +970,21 @@ template <typename T> __device__ __forceinline__ BatchDev<T> rare_batch(const Ba
     __builtin_memcpy(&out, p, sizeof(out));      // scalar loads from the constant address space
     return out;
 }
-#else
-template <typename T> __device__ __forceinline__ const BatchDev<T>& rare_batch(const BatchDev<T>& a) { return a; }
-#endif
 
 // ---- trajectory rows through a wave-uniform buffer descriptor
 // In k_advance every live lane of a wave is at the same row (they start together and step together), so a row's
 // address splits into a wave-uniform part -- row base + block offset, kept in SGPRs as a buffer descriptor -- a
 // per-quantity scalar offset (q*R elements) and a per-lane constant (lane*sizeof(T)).  That removes the per-lane
 // 64-bit address arithmetic of write_row (seven v_mad_u64_u32 / v_lshl_add_u64 chains per step) and frees their
-// registers.  RTMI_ROW_STORE_AUX sets the stores' cache policy (0 plain, 2 nt, 16 sc1, 18 sc1 nt).
-#ifndef RTMI_TILE_WAVES
-#define RTMI_TILE_WAVES 4      // waves per SIMD the LDS-tile variant of k_advance is built for (the light methods)
-#endif
-// op2 and op6 (one field lookup per step, no golden section, no curvature terms) fit one more wave per SIMD than the rest;
-// with the cell-polynomial lookup op1/7/8 do too (they spill 60-90 bytes per lane at 128 VGPRs and are still 8-10 % faster at
-// four waves than at three: op1 8.97 -> 8.03 ms)
-constexpr bool light_method(int m) { return m == 2 || m == 6 || (RTMI_POLY && (m == 1 || m == 7 || m == 8)); }
-// op4 and the golden-section methods carry the most state: their tile builds keep two waves per SIMD
-constexpr bool heavy_method(int m) { return m == 4 || m == 5 || m >= 9; }
-#ifndef RTMI_GLOBAL_WAVES
-#define RTMI_GLOBAL_WAVES 3    // waves per SIMD the fp64 global-gather builds are compiled for
-#endif
-#ifndef RTMI_GOLD_WAVES
-#define RTMI_GOLD_WAVES 3      // waves per SIMD the golden-section builds (op5/9/10/11, global gather) are compiled for
-#endif
-#ifndef RTMI_SLICED_SLEEP
-#define RTMI_SLICED_SLEEP 32   // s_sleep argument (x64 clocks) between two polls of a bundle's slice counter
-#endif
-#ifndef RTMI_F32_SLICED_WAVES
-#define RTMI_F32_SLICED_WAVES 5   // the fp32 k_advance fits five waves per SIMD by itself (94 VGPRs); the sliced build has to be told
-#endif
-#ifndef RTMI_F32_WAVES
-#define RTMI_F32_WAVES 4       // waves per SIMD the fp32 builds of k_advance are compiled for
-#endif
-#ifndef RTMI_STEP_PAIRS
-#define RTMI_STEP_PAIRS 2      // 1: op2/op6 fp64, 2: every fast-form build -- two steps per loop iteration (see advance_loop)
-#endif
-#ifndef RTMI_ROW_STORE_AUX
-#define RTMI_ROW_STORE_AUX 2   // nt: rows are written once and never read by the kernel (measured 3-5 % over plain stores)
-#endif
+// registers.
+// The stores' cache policy: nt -- rows are written once and never read by the kernel (measured 3-5 % over plain stores).
+constexpr int kRowStoreAux = 2;
 typedef unsigned rt_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t rs, int voff, int soff, double v) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(rt_u32x2, v), rs, voff, soff, RTMI_ROW_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(rt_u32x2, v), rs, voff, soff, kRowStoreAux);
 }
 __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t rs, int voff, int soff, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, voff, soff, RTMI_ROW_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, voff, soff, kRowStoreAux);
 }
 // A pointer every lane of the wave holds the same value of, pinned to scalar registers.  The compiler keeps the row
 // pointers of advance_loop in VGPRs (their loop-carried updates get moved to the VALU) and would otherwise wrap every
@@ -1044,11 +999,9 @@ __device__ __forceinline__ T* wave_uniform_ptr(T* p) {
 template <typename T>
 __device__ __forceinline__ void write_row_uniform(const BatchDev<T>& a, T* rowp, T* nrowp, int voff, const rt::Ray<T>& r) {
     int qR = (int)(a.R * (long)sizeof(T));                              // byte distance between quantities (< 2^31 / 6: pick_advance)
-#ifndef RTMI_NO_QR_LAUNDER
     // the multiples of qR are formed here, per row, with one scalar instruction each: hoisted out of the step loop they
     // do not fit the scalar registers and come back through v_readlane + 5 wait states apiece
     asm volatile("" : "+s"(qR));
-#endif
     rowp = wave_uniform_ptr(rowp);
     nrowp = wave_uniform_ptr(nrowp);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(rowp, 0, 0x7fffffff, 0x00020000);
@@ -1143,9 +1096,10 @@ __device__ __forceinline__ void advance_loop(const BatchDev<T>& a, const rt::Con
         if constexpr (rt::HasPrefetch<G>::value) gather.prefetch(a.F, alive, (T)r.x + r.ux * K.step, (T)r.y + r.uy * K.step);
         return true;
     };
-    if constexpr (RTMI_STEP_PAIRS == 2 ? !rt::IsExact<T, METHOD>::value : (RTMI_STEP_PAIRS && light_method(METHOD) && sizeof(T) == 8)) {
-        // Two steps per loop iteration: the second step's results land in the registers the first step's inputs left, so
-        // the ~15 register copies that rotate the new state into the loop-carried registers every step disappear.
+    if constexpr (!rt::IsExact<T, METHOD>::value) {
+        // Two steps per loop iteration (every fast-form build): the second step's results land in the registers the first
+        // step's inputs left, so the ~15 register copies that rotate the new state into the loop-carried registers every step
+        // disappear.
         for (int it = 0; it < nsteps; it += 2) {
             if (!one_step()) break;
             if (it + 1 >= nsteps) break;
@@ -1157,37 +1111,46 @@ __device__ __forceinline__ void advance_loop(const BatchDev<T>& a, const rt::Con
     }
 }
 
-template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH = false, int PH = RTMI_TILE_PHASES, bool NOFLAT = false>
+// LAT: the build for few waves (k_advance_lat), whose gather is rt::PolyLaneKept
+template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH = false, bool NOFLAT = false, bool LAT = false>
 __device__ __forceinline__ bool advance_bundle(const BatchDev<T>& a, T* lds, long blk, int nsteps);
 
 // Which 256-ray bundle a hardware block takes.  Blocks are dealt to the eight XCDs round-robin (block h runs on XCD h % 8,
 // as the h / 8-th block there), each XCD with an L2 of its own; neighbouring bundles of a fan walk through the same cells of
-// the field, so RTMI_XCD_GROUP consecutive bundles go to ONE XCD (its L2 then serves the second to G-th from the first's
-// misses) while the groups still interleave over the XCDs (a contiguous eighth of the fan per XCD is badly balanced:
-// DESIGN.md 5.1).  Identity for the blocks past the last whole round of 8 x G.
-#ifndef RTMI_XCD_GROUP
-#define RTMI_XCD_GROUP 8     // measured (A/B, one session): interface 24.6 -> 23.6 ms at 8, 24.0 at 4; vert, fisheye, fp32 unchanged
-#endif
+// the field, so G consecutive bundles go to ONE XCD (its L2 then serves the second to G-th from the first's misses) while
+// the groups still interleave over the XCDs (a contiguous eighth of the fan per XCD is badly balanced: DESIGN.md 5.1).
+// Identity for the blocks past the last whole round of 8 x G.
 __device__ __forceinline__ unsigned xcd_grouped_block(unsigned h, unsigned nblocks) {
-#if RTMI_XCD_GROUP > 1
-    constexpr unsigned G = RTMI_XCD_GROUP, ROUND = 8u * G;
+    constexpr unsigned G = 8;     // measured (A/B, one session): interface 24.6 -> 23.6 ms at 8, 24.0 at 4; vert, fisheye, fp32 unchanged
+    constexpr unsigned ROUND = 8u * G;
     if (h < nblocks / ROUND * ROUND) {
         const unsigned xcd = h & 7u, idx = h >> 3;
         return ((idx / G) * 8u + xcd) * G + idx % G;
     }
-#endif
     return h;
+}
+
+// op2 and op6 (one field lookup per step, no golden section, no curvature terms) fit one more wave per SIMD than the rest;
+// with the cell-polynomial lookup op1/7/8 do too (they spill 60-90 bytes per lane at 128 VGPRs and are still 8-10 % faster at
+// four waves than at three: op1 8.97 -> 8.03 ms)
+constexpr bool light_method(int m) { return m == 2 || m == 6 || m == 1 || m == 7 || m == 8; }
+// op4 and the golden-section methods carry the most state: their tile builds keep two waves per SIMD
+constexpr bool heavy_method(int m) { return m == 4 || m == 5 || m >= 9; }
+// Waves per SIMD a step kernel is built for: the fp32 builds f32_waves; the LDS-tile builds four for the light methods, two
+// for the heavy ones and three for the rest; the fp64 global-gather builds (the golden-section ones too) three.
+template <typename T> constexpr int advance_waves(int m, bool lds, int f32_waves) {
+    return sizeof(T) == 4 ? f32_waves : lds ? (light_method(m) ? 4 : heavy_method(m) ? 2 : 3) : 3;
 }
 
 // The loop at :866-879: one lane per ray, state in registers for up to nsteps DELTA_S steps.
 // ISO (gamma == 1) drops the anisotropic factor's dead arithmetic; LDS selects the wave-private field tile
 // (rt::LdsGather) over per-lookup global gathers.  Results are bit-identical across all four variants.
-// Register budgets (RTMI_*_WAVES): the fp64 tile variant fits four waves per SIMD (128 VGPRs, the window read and summed
+// Register budgets (advance_waves): the fp64 tile variant fits four waves per SIMD (128 VGPRs, the window read and summed
 // row by row), the fp64 global-gather variants three (137-168 VGPRs, gathers in two halves); none of them spills.
 // Every lane runs every iteration until no lane of its wave is active; a ray's state is stored the moment it
 // terminates (or when the launch's step budget ends), so idle lanes never write.
 template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool NOFLAT = false>
-__global__ __launch_bounds__(256, sizeof(T) == 4 ? RTMI_F32_WAVES : LDS ? (light_method(METHOD) ? RTMI_TILE_WAVES : heavy_method(METHOD) ? 2 : 3) : ((METHOD == 5 || METHOD >= 9) ? RTMI_GOLD_WAVES : RTMI_GLOBAL_WAVES))
+__global__ __launch_bounds__(256, advance_waves<T>(METHOD, LDS, 4))
 void k_advance(BatchDev<T> a, int nsteps) {
     __shared__ __attribute__((aligned(16))) T lds[kernel_lds_elems<T, METHOD, LDS>()];
     if (a.prio > 0) __builtin_amdgcn_s_setprio(3);     // the re-trace of a few hundred critical rays beside the main kernel's waves
@@ -1198,7 +1161,7 @@ void k_advance(BatchDev<T> a, int nsteps) {
         bundle += a.blk_rot;
         bundle = bundle >= gridDim.x ? bundle - gridDim.x : bundle;
     }
-    advance_bundle<T, METHOD, ISO, LDS, VAR, false, RTMI_TILE_PHASES, NOFLAT>(a, lds, (long)bundle * blockDim.x, nsteps);
+    advance_bundle<T, METHOD, ISO, LDS, VAR, false, NOFLAT>(a, lds, (long)bundle * blockDim.x, nsteps);
 }
 // The kernel built for FEW waves: a batch of <= 2 waves per SIMD (cfg2's 65 536 rays: one) has nothing to hide a step's
 // dependent chain behind -- 1 800 cycles per step at one wave per SIMD against 545 of issue -- so this build spends registers
@@ -1211,12 +1174,13 @@ void k_advance(BatchDev<T> a, int nsteps) {
 // NOFLAT: for a field whose flat-cell map is empty (vert_heterogeneous, fisheye): neither the map's tests nor the hover sum are compiled in
 template <typename T, int METHOD, bool ISO, bool NOFLAT = false>
 __global__ __launch_bounds__(256, 2) void k_advance_lat(BatchDev<T> a, int nsteps) {
-    __shared__ __attribute__((aligned(16))) T lds[uses_tile<T, METHOD, true>() ? 4 * rt::LdsGather<T, 1>::ELEMS : 2];
-    advance_bundle<T, METHOD, ISO, true, false, false, 1, NOFLAT>(a, lds, (long)blockIdx.x * blockDim.x, nsteps);
+    static_assert(uses_poly<T, METHOD>(), "k_advance_lat is built for the fast forms only");
+    __shared__ __attribute__((aligned(16))) T lds[2];
+    advance_bundle<T, METHOD, ISO, true, false, false, NOFLAT, true>(a, lds, (long)blockIdx.x * blockDim.x, nsteps);
 }
-template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH, int PH, bool NOFLAT>
+template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH, bool NOFLAT, bool LAT>
 __device__ __forceinline__ bool advance_bundle(const BatchDev<T>& a, T* lds, long blk, int nsteps) {
-    typename GatherOf<T, METHOD, LDS, PH, NOFLAT>::type gather;
+    std::conditional_t<LAT, rt::PolyLaneKept<T, !NOFLAT>, typename GatherOf<T, METHOD, LDS, NOFLAT>::type> gather;
     gather_init<T, LDS>(gather, lds);
     if constexpr (rt::IsExact<T, METHOD>::value && rt::ex::flat_shortcut<rt::base_method(METHOD)>()) gather_flat_bound<T>(gather, a);
     if constexpr (rt::IsExact<T, METHOD>::value) {
@@ -1280,7 +1244,8 @@ __device__ __forceinline__ unsigned long long realtime_ticks() { return __builti
 // entry load / entry store (s_waitcnt is not a memory operation to it, and the barrier's fence is workgroup scope).
 __device__ __forceinline__ void compiler_fence() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
 template <typename T, int METHOD, bool ISO, bool LDS, bool NOFLAT = false>
-__global__ __launch_bounds__(256, sizeof(T) == 4 ? RTMI_F32_SLICED_WAVES : LDS ? (light_method(METHOD) ? RTMI_TILE_WAVES : heavy_method(METHOD) ? 2 : 3) : ((METHOD == 5 || METHOD >= 9) ? RTMI_GOLD_WAVES : RTMI_GLOBAL_WAVES))
+// (the fp32 k_advance fits five waves per SIMD by itself, 94 VGPRs; the sliced build has to be told)
+__global__ __launch_bounds__(256, advance_waves<T>(METHOD, LDS, 5))
 void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, unsigned long long* ctl, unsigned long long timeout_ticks) {
     __shared__ __attribute__((aligned(16))) T lds[kernel_lds_elems<T, METHOD, LDS>()];
     __shared__ unsigned long long s_entry;
@@ -1320,7 +1285,7 @@ void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, uns
                         const unsigned long long now = realtime_ticks();
                         if (f != f0 || p != p0) { f0 = f; p0 = p; t0 = now; }         // progress somewhere: start over
                         else if (now - t0 > timeout_ticks) break;
-                        __builtin_amdgcn_s_sleep(RTMI_SLICED_SLEEP);
+                        __builtin_amdgcn_s_sleep(32);                                // x64 clocks between two polls
                         e = ld_u64(entries + (i - NB));
                     }
                     if (e == 0ull) { __hip_atomic_store(stalled, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); e = kStop; }
@@ -1343,7 +1308,7 @@ void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, uns
             const unsigned k = (unsigned)(e >> 32);           // slices this bundle has had
             const int nsteps = k == 0u ? 4 * slice : k == 1u ? 2 * slice : slice;
             compiler_fence();
-            const bool alive = advance_bundle<T, METHOD, ISO, LDS, false, true, RTMI_TILE_PHASES, NOFLAT>(a, lds, bundle * 256, nsteps);
+            const bool alive = advance_bundle<T, METHOD, ISO, LDS, false, true, NOFLAT>(a, lds, bundle * 256, nsteps);
             compiler_fence();                                // no state store of the bundle moves below the entry store
             __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0): this lane's state stores are acknowledged
             const int any = __builtin_amdgcn_readfirstlane(__syncthreads_or(alive));
@@ -1369,11 +1334,8 @@ void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, uns
 // never depends on its lane or wave mates, so results are bit-identical to k_advance.
 // Exit: the queue is exhausted and no lane is live -- reached by every wave because each ray takes at most
 // max_size steps and the queue only advances.
-#ifndef RTMI_REFILL_WAVES
-#define RTMI_REFILL_WAVES 3
-#endif
 template <typename T, int METHOD, bool ISO, bool LDS>
-__global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : light_method(METHOD) ? RTMI_REFILL_WAVES : 2) void k_trace_refill(BatchDev<T> a, int refill_min, int chunk) {
+__global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : light_method(METHOD) ? 3 : 2) void k_trace_refill(BatchDev<T> a, int refill_min, int chunk) {
     __shared__ __attribute__((aligned(16))) T lds[kernel_lds_elems<T, METHOD, LDS>()];
     typename GatherOf<T, METHOD, LDS>::type gather;
     gather_init<T, LDS>(gather, lds);
@@ -1612,11 +1574,7 @@ static int batch_staging(rtmi_batch* b, size_t bytes, void** out) {
 
 // The reference-order lookup's wave-uniform window (rt::ex::lookup_uniform) from two waves per SIMD on: 1024 SIMDs x 64 lanes x 2
 // (FieldDev::window) when rtmi_params.field_path is 0 (auto); 3 asks for it whatever the size, 1 and 2 never use it.
-// RTMI_WINDOW_MIN_RAYS overrides the size (0: always, a huge number: never) for A/B runs.
-static long window_min_rays() {
-    static const long v = [] { const char* e = getenv("RTMI_WINDOW_MIN_RAYS"); return e ? atol(e) : 131072L; }();
-    return v;
-}
+constexpr long kWindowMinRays = 131072;
 // ... except for the golden-section methods on a fan that enters a new cell on (nearly) every step: the fisheye fan at its calibrated
 // DELTA_S = 2 pi / 303 (two cells per step) runs op9 in 165 ms with the window and 48 without, op5 in 78 / 54 -- the other
 // reference-order methods gain there as everywhere (op3 53 -> 46 ms, op7 37 -> 29, op6 in reference order 40 -> 32), and op5 / op9
@@ -1629,15 +1587,10 @@ static bool window_loses(const rtmi_batch* b) {
     const rtmi_field* f = b->field;
     return std::fabs(b->p.step) > 0.5 * std::fmin(f->hx, f->hy);
 }
-// rt::kHoverLimit (RTMI_HOVER_LIMIT overrides it, for calibration runs)
-static float hover_limit() {
-    static const float v = [] { const char* e = getenv("RTMI_HOVER_LIMIT"); return e ? (float)atof(e) : rt::kHoverLimit; }();
-    return v;
-}
 template <typename T> static BatchDev<T> batch_dev(const rtmi_batch* b) {
     BatchDev<T> a;
     a.F = field_dev<T>(b->field, b->p.exact_basis);
-    a.F.window = (b->p.field_path == 3 || (b->p.field_path == 0 && b->R >= window_min_rays() && !window_loses(b))) ? 1 : 0;
+    a.F.window = (b->p.field_path == 3 || (b->p.field_path == 0 && b->R >= kWindowMinRays && !window_loses(b))) ? 1 : 0;
     const rtmi_params& p = b->p;
     a.K.step = (T)p.step;
     a.K.step2h = (T)(libm_square(p.step) / 2.0);    // numpy scalar step**2 is libm pow (:330); /2 is exact
@@ -1659,7 +1612,7 @@ template <typename T> static BatchDev<T> batch_dev(const rtmi_batch* b) {
     a.perm = b->perm;
     a.vstep = (const T*)b->vstep; a.vstep2h = (const T*)b->vstep2h; a.vmax = b->vmax;
     a.hov = b->rt ? b->rt->hov : nullptr;
-    a.hov_limit = b->rt ? hover_limit() : INFINITY;
+    a.hov_limit = b->rt ? rt::kHoverLimit : INFINITY;
     a.rq_cap = b->rt ? b->rt->cap : 0u;
     a.rq = b->rt ? b->rt->rq : nullptr;
     a.rq_host = b->rt ? b->rt->host_count + 4 : nullptr;
@@ -1801,9 +1754,9 @@ static const void* advance_lat_fn(int m, bool iso, bool noflat) {
 }
 static const void* pick_advance(const rtmi_batch* b) {
     const bool iso = b->p.gamma == 1.0 && b->p.method < 10, lds = use_lds_tile(b);
-    // at most two waves per SIMD's worth of rays: the latency build (env RTMI_NO_LAT=1 keeps the throughput build, for A/B)
+    // at most two waves per SIMD's worth of rays: the latency build
     if (lds && b->p.dtype == RTMI_F64 && (b->p.method == 2 || b->p.method == 6) && !b->vstep && uniform_rows_ok(b) &&
-        !ref_order(b->p) && b->lat_waves_per_simd > 0 && (b->R + 63) / 64 <= (int64_t)2 * b->lat_simds && !getenv("RTMI_NO_LAT"))
+        !ref_order(b->p) && b->lat_waves_per_simd > 0 && (b->R + 63) / 64 <= (int64_t)2 * b->lat_simds)
         return advance_lat_fn(b->p.method, iso, b->field->flat_cells == 0 && b->field->steep_cells == 0);
     // the VAR build: per-ray DELTA_S / max_size when set, and per-lane row bookkeeping always
     if (b->vstep || !uniform_rows_ok(b))
@@ -2438,7 +2391,7 @@ static bool retrace_wanted(const rtmi_batch* b) {
     const rtmi_params& p = b->p;
     return !b->is_retrace_sub && !p.no_retrace && p.dtype == RTMI_F64 && b->field->steep_cells > 0 &&
            (p.reference_order == RTMI_ORDER_DEFAULT || p.reference_order == RTMI_ORDER_FAST_FIELD) &&
-           rt::rotates_unit(p.method, true) && !getenv("RTMI_NO_RETRACE");
+           rt::rotates_unit(p.method, true);
 }
 // slots of the queue: a few hundred rays of a million are critical on the interface fan -- room for 1/128 of the batch, for 1 024 at
 // least (a small batch may be ALL window: 380 of the 4 096 rays around the interface fan's split), never for more than the batch
@@ -2464,8 +2417,8 @@ constexpr int kRetraceCus = 8;         // compute units set aside for the re-tra
 //   k_retrace_ref: the reference-order part.  A lane leaves its loop at the hand-back (state stored, alive = 1) or when its ray ends
 //   (alive = 0); no lane steps in two forms in one iteration.  marked_only: the final sweep for rays whose fused tail hovered again
 //   (alive = 2, see k_retrace_tail) -- those are taken in reference order to their END.
-//   k_retrace_tail: the fused part of the rays that were handed back, with the few-waves lookup (the wave's cell kept in vector
-//   registers, rt::kPolyCached): 0.75 us per step where per-lane loads two rows at a time take 3.
+//   k_retrace_tail: the fused part of the rays that were handed back, with the few-waves lookup (every lane keeps its own cell in
+//   vector registers and starts the next one's loads a step ahead, rt::PolyLaneKept).
 template <int METHOD>
 __global__ __launch_bounds__(64, 3) void k_retrace_ref(BatchDev<double> s, BatchDev<double> m, const unsigned long long* rq, unsigned lo, unsigned hi,
                                                        int marked_only, unsigned long long* dbg) {
