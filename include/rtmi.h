@@ -154,7 +154,8 @@ typedef struct {
                                 adds up, per ray and step, the steepness of the cell times |v . g| (v the ray's normal, g the
                                 unit gradient): the exponent of the factor by which the trajectory amplifies a rounding
                                 difference along a wall.  A ray whose sum says more than ~1e3 times is stopped, queued
-                                and re-traced from its launch conditions in the reference's operation order (a hidden batch of the
+                                and re-traced from its launch conditions, or from the state rtmi_batch_set_state set, in the
+                                reference's operation order (a hidden batch of the
                                 same parameters, launched beside the main kernel); its rows and final state replace the fused
                                 ones -- the oracle's bits.  A few hundred rays of a million on the interface fan; the re-trace runs on
                                 eight compute units of its own beside the main kernel (which gets a stream of the batch's own
@@ -181,7 +182,9 @@ int rtmi_batch_create(const rtmi_field *f, const rtmi_params *p, int64_t R, cons
  * (:868): opN(i_angle, init_n, i_grad, i_unitv, i_vpos, coef_i, grd, z, step) with caller-chosen inputs.
  * fp64 op1/op2/op6/op8 batches carry the unit tangent (cos theta, sin theta) as ray state (it is advanced by rotation, not
  * recomputed from theta every step); a state set here restarts it from sin/cos of theta -- a state of the caller's own
- * making has no other.  To continue a run from a checkpoint use rtmi_batch_get_state / rtmi_batch_restore_state. */
+ * making has no other.  To continue a run from a checkpoint use rtmi_batch_get_state / rtmi_batch_restore_state.
+ * A batch that re-traces its critical rays (rtmi_params.no_retrace) re-traces them from the state set here, not from the
+ * launch conditions, until the next rtmi_batch_reset; rays handed over by an rtmi_step and not yet read are discarded. */
 int rtmi_batch_set_state(rtmi_batch *b, const double *state9, const double *hist4, const int32_t *istep);
 /* Checkpoint: copy the current ray state to host buffers (any may be NULL), caller's ray order: state9 and istep as in
  * rtmi_batch_set_state; aux4[4][R] = the method's private state -- op7: the position history (hist4); fp64 op1/2/6/8: rows 0-1
@@ -189,7 +192,8 @@ int rtmi_batch_set_state(rtmi_batch *b, const double *state9, const double *hist
  * left the box, :878, or ran out of rows). */
 int rtmi_batch_get_state(rtmi_batch *b, double *state9, double *aux4, int32_t *istep, uint8_t *alive);
 /* Resume: rtmi_batch_set_state with the method's private state taken from aux4 as rtmi_batch_get_state returned it.  On a
- * batch with the same parameters the run continues bit for bit (the reference has no counterpart: :866 runs to the end). */
+ * batch with the same parameters the run continues bit for bit (the reference has no counterpart: :866 runs to the end).
+ * The batch must also have the same launch conditions: its critical rays are re-traced from them (rtmi_params.no_retrace). */
 int rtmi_batch_restore_state(rtmi_batch *b, const double *state9, const double *aux4, const int32_t *istep,
                              const uint8_t *alive);
 /* Give every ray its own DELTA_S and max_size (host arrays [R], caller's ray order): one batch then holds the whole
@@ -202,7 +206,8 @@ int rtmi_batch_set_per_ray(rtmi_batch *b, const double *step, const int32_t *max
  * (caller-owned ext_s_ray / ext_n_ray included) unless params.lazy_clear is set, see there. */
 int rtmi_batch_reset(rtmi_batch *b);
 /* One launch that advances every live ray by at most nsteps DELTA_S steps (the body of the loop at :866-879;
- * nsteps = 1 is exactly one call of selected_func + store_update_results per ray). */
+ * nsteps = 1 is exactly one call of selected_func + store_update_results per ray).  Rays it hands over to the re-trace of
+ * critical rays (rtmi_params.no_retrace) can be at their END at the next call that reads results. */
 int rtmi_step(rtmi_batch *b, int32_t nsteps);
 /* `count` times rtmi_step(b, nsteps), submitted as ONE hipGraph (a chain of `count` kernel nodes, built on first use and kept
  * while nsteps / count / the kernel stay the same): a host that advances the batch a few steps at a time pays one call and
@@ -284,9 +289,11 @@ typedef struct {
     double auto_ms[2][RTMI_AUTO_SAMPLES];   /* the exploration record: kernel time of each timed run under [0] the time-sliced and
                                            [1] the plain schedule, in the order they were taken; auto_n[k] of them are valid */
     uint32_t auto_n[2];
-    uint32_t retraced;                  /* critical rays re-traced in reference order since create/reset (rtmi_params.no_retrace) */
+    uint32_t retraced;                  /* critical rays re-traced in reference order since create / reset / set_state / restore_state
+                                           (rtmi_params.no_retrace); rays still queued when the state is set are discarded, uncounted */
     uint32_t retrace_overflow;          /* ... and rays that qualified but found the hand-over queue full (1/128 of the batch, at least
-                                           256): they stay in the fused form.  Expected 0 */
+                                           1 024 and at most 65 536 slots, never more than the batch rounded up to 64): they stay in the
+                                           fused form.  Expected 0 */
     uint64_t retraced_total;            /* re-traced over the batch's whole life */
     uint32_t dispatch_first;            /* the 256-ray bundle the plain kernel's first hardware block takes: 0, or -- learnt from the batch's
                                            first rtmi_run that handed critical rays over, kept for its re-runs like the AUTO schedule --

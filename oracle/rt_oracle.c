@@ -726,6 +726,69 @@ RTO_API long rto_trazar(const rto_field *f, const rto_params *p, int R, const do
     return total;
 }
 
+/* rto_trazar's loop continued from a given state instead of state_init: what rtmi_batch_set_state asks of the device.
+ * state9[9][R] = x, y, theta, n, gx, gy, dist_sim, dist_real, T; hist4[4][R] (op7, may be NULL otherwise) = the two
+ * positions before (x, y), oldest first; istep[R] = the row the state is at.  The derived quantities (ux, uy, coef, mx, my,
+ * nray) follow from the state as store_update derives them.  Rows istep+1 .. are written, no row at or before istep;
+ * d_ray / final as rto_trazar.  op7 bootstraps (:833-864) only the rows 1-2 still ahead of istep. */
+RTO_API long rto_trazar_from_state(const rto_field *f, const rto_params *p, int R, const double *state9, const double *hist4,
+                                   const int *istep, double *s_ray, double *n_ray, double *d_ray, double *final) {
+    long total = 0;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : total) num_threads(p->nthreads > 0 ? p->nthreads : 1)
+#endif
+    for (int k = 0; k < R; k++) {
+        rto_ctx c = { f, p->method, p->gamma, p->gamma_step, p->step, libm_square(p->step) };
+        rto_state s;
+        memset(&s, 0, sizeof s);
+        const size_t RR = (size_t)R;
+        s.x = state9[0 * RR + k]; s.y = state9[1 * RR + k]; s.theta = state9[2 * RR + k];
+        s.n = state9[3 * RR + k]; s.gx = state9[4 * RR + k]; s.gy = state9[5 * RR + k];
+        s.dist_sim = state9[6 * RR + k]; s.dist_real = state9[7 * RR + k]; s.T = state9[8 * RR + k];
+        s.ux = cos(s.theta); s.uy = sin(s.theta);
+        s.coef = anisotropy_sc(s.uy, s.ux, c.gamma);
+        moments_f(s.n, s.uy, s.ux, s.ux, s.uy, c.gamma, &s.mx, &s.my);
+        s.nray = s.coef * s.n;
+        if (hist4) {
+            s.hx[0] = hist4[0 * RR + k]; s.hy[0] = hist4[1 * RR + k];
+            s.hx[1] = hist4[2 * RR + k]; s.hy[1] = hist4[3 * RR + k];
+        }
+        s.hx[2] = s.x; s.hy[2] = s.y;
+        const long i0 = istep[k];
+        long i = i0, loop_iter = i0 + 1;
+        double fx, fy, fth, fn, fgx, fgy;
+        if (p->method == 7 && i0 < 2) { /* the bootstrap rows still ahead, no boundary test */
+            for (i = i0 + 1; i <= 2 && i < p->max_size; i++) {
+                adv_second(&s, &c, &fx, &fy);
+                rto_n_gradient(f, fx, fy, &fn, &fgx, &fgy);
+                double vx, vy;
+                if (i == 1) { vx = fx - s.hx[2]; vy = fy - s.hy[2]; }
+                else { vx = 3 * fx - 4 * s.hx[2] + s.hx[1]; vy = 3 * fy - 4 * s.hy[2] + s.hy[1]; }
+                fth = np_arctan2(vy, vx);
+                store_update(&c, &s, fx, fy, fth, fn, fgx, fgy);
+                write_row(p, s_ray, n_ray, R, k, i, &s);
+            }
+            i = 2; loop_iter = 3;
+        }
+        for (long it = loop_iter; it < p->max_size; it++) {
+            i = it;
+            op_step(&c, &s, &fx, &fy, &fth, &fn, &fgx, &fgy);
+            store_update(&c, &s, fx, fy, fth, fn, fgx, fgy);
+            write_row(p, s_ray, n_ray, R, k, i, &s);
+            if (s.x > p->box[1] || s.x < p->box[0] || s.y > p->box[3] || s.y < p->box[2]) break;
+        }
+        d_ray[0 * RR + k] = s.dist_real;
+        d_ray[1 * RR + k] = s.dist_sim;
+        d_ray[2 * RR + k] = (double)i;
+        if (final) {
+            double v[9] = { s.x, s.y, s.theta, s.n, s.gx, s.gy, s.mx, s.my, s.T };
+            for (int q = 0; q < 9; q++) final[(size_t)q * R + k] = v[q];
+        }
+        total += i;
+    }
+    return total;
+}
+
 RTO_API int rto_max_threads(void) {
 #ifdef _OPENMP
     return omp_get_max_threads();

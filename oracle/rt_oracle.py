@@ -68,6 +68,8 @@ def lib(which=None):
         L.rto_single_step.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp]
         L.rto_trazar.restype = C.c_long
         L.rto_trazar.argtypes = [C.c_void_p, C.POINTER(_Params), C.c_int] + [_dp] * 7
+        L.rto_trazar_from_state.restype = C.c_long
+        L.rto_trazar_from_state.argtypes = [C.c_void_p, C.POINTER(_Params), C.c_int, _dp, _dp, C.POINTER(C.c_int)] + [_dp] * 4
         L.rto_max_threads.restype = C.c_int
         L.rto_set_field_solver.argtypes = [C.c_int]
         L.rto_np_exp_many.argtypes = [_dp, _dp, C.c_long]
@@ -151,11 +153,7 @@ def single_step(field, method, gamma, step, st, hist=None):
     return out
 
 
-def trazar(field, method, gamma, step, max_size, box, x0, y0, theta0, record_stride=1, rec_rows=None,
-           nthreads=1, gamma_step=None, want_n_ray=False):
-    """RT_bench.py:766-948.  Returns dict(s_ray [rows,6,R] or None, n_ray, d_ray [3,R], final [9,R], steps)."""
-    th = _f64(theta0); R = len(th)
-    x0 = _f64(np.broadcast_to(x0, (R,))); y0 = _f64(np.broadcast_to(y0, (R,)))
+def _params(method, gamma, step, max_size, box, record_stride, nthreads, gamma_step):
     p = _Params()
     p.method = int(method); p.gamma = float(gamma)
     p.gamma_step = float(gamma if gamma_step is None else gamma_step)
@@ -163,15 +161,50 @@ def trazar(field, method, gamma, step, max_size, box, x0, y0, theta0, record_str
     for i in range(4):
         p.box[i] = float(box[i])
     p.record_stride = int(record_stride); p.nthreads = int(nthreads)
+    return p
+
+
+def _outputs(p, R, max_size, record_stride, rec_rows, want_n_ray):
     s_ray = n_ray = None
     if record_stride:
         rows = int(rec_rows) if rec_rows is not None else (int(max_size) + record_stride - 1) // record_stride
         p.rec_rows = rows
         s_ray = np.zeros((rows, 6, R))
         n_ray = np.zeros((rows, R)) if want_n_ray else None
-    d_ray = np.zeros((3, R)); final = np.zeros((9, R))
+    return s_ray, n_ray, np.zeros((3, R)), np.zeros((9, R))
+
+
+def trazar(field, method, gamma, step, max_size, box, x0, y0, theta0, record_stride=1, rec_rows=None,
+           nthreads=1, gamma_step=None, want_n_ray=False):
+    """RT_bench.py:766-948.  Returns dict(s_ray [rows,6,R] or None, n_ray, d_ray [3,R], final [9,R], steps)."""
+    th = _f64(theta0); R = len(th)
+    x0 = _f64(np.broadcast_to(x0, (R,))); y0 = _f64(np.broadcast_to(y0, (R,)))
+    p = _params(method, gamma, step, max_size, box, record_stride, nthreads, gamma_step)
+    s_ray, n_ray, d_ray, final = _outputs(p, R, max_size, record_stride, rec_rows, want_n_ray)
     steps = field.L.rto_trazar(field.h, C.byref(p), R, _p(x0), _p(y0), _p(th), _p(s_ray), _p(n_ray), _p(d_ray),
                              _p(final))
+    return dict(s_ray=s_ray, n_ray=n_ray, d_ray=d_ray, final=final, steps=int(steps))
+
+
+def trazar_from_state(field, method, gamma, step, max_size, box, state9, hist4=None, istep=0, record_stride=1, rec_rows=None,
+                      nthreads=1, gamma_step=None, want_n_ray=False):
+    """trazar's loop (:866-879) continued from a given state, as rtmi_batch_set_state asks of the device.
+    state9 [9,R] = x, y, theta, n, dn/dx, dn/dy, dist_sim, dist_real, T; hist4 [4,R] (op7) = the two positions before,
+    oldest first (x, y, x, y); istep [R] (or one int) = the row each state is at.  Rows after istep only are written (the
+    others stay 0).  Returns what trazar returns; d_ray holds dist_real, dist_sim, last row (NOT state9's order)."""
+    st = _f64(state9); R = st.shape[1]
+    assert st.shape == (9, R)
+    h = None
+    if hist4 is not None:
+        h = _f64(hist4)
+        assert h.shape == (4, R)
+    elif int(method) == 7:
+        raise ValueError("op7 needs hist4 (the two positions before each state)")
+    ist = np.ascontiguousarray(np.broadcast_to(np.asarray(istep, dtype=np.int32), (R,)))
+    p = _params(method, gamma, step, max_size, box, record_stride, nthreads, gamma_step)
+    s_ray, n_ray, d_ray, final = _outputs(p, R, max_size, record_stride, rec_rows, want_n_ray)
+    steps = field.L.rto_trazar_from_state(field.h, C.byref(p), R, _p(st), _p(h), ist.ctypes.data_as(C.POINTER(C.c_int)),
+                                          _p(s_ray), _p(n_ray), _p(d_ray), _p(final))
     return dict(s_ray=s_ray, n_ray=n_ray, d_ray=d_ray, final=final, steps=int(steps))
 
 

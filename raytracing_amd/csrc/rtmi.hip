@@ -1534,6 +1534,12 @@ struct Retrace {
     bool pending = false;                 // advance kernels ran since the queue was last drained
     unsigned long long* dbg = nullptr;    // RTMI_DEBUG: device [8] statistics of k_retrace
     unsigned overflow = 0;                // rays that found the queue full this pass (they stay fused)
+    // rtmi_batch_set_state: the state each ray was given, in slot order -- org [9][R] (state9's order), org_istep [R] -- from which
+    // its re-trace starts instead of the launch conditions (from_set).  Allocated on the first set_state; a reset and
+    // rtmi_batch_restore_state go back to the launch conditions.
+    double* org = nullptr;
+    int* org_istep = nullptr;
+    bool from_set = false;
     unsigned swept = 0;                   // rays whose fused tail hovered again and that were re-traced in reference order throughout
     uint64_t total = 0;                   // rays re-traced over the batch's life
     // Dispatch order learnt from the batch's first pass with critical rays (like RTMI_LAUNCH_AUTO's schedule: knowledge a re-run batch
@@ -2035,7 +2041,10 @@ RTMI_EXPORT int rtmi_batch_reset(rtmi_batch* b) {
     return batch_init_state(b, b->dirty || !b->p.lazy_clear);
 }
 
-template <typename T> __global__ void k_set_state(BatchDev<T> a, const double* st, const double* hist, const int* istep, const unsigned char* live) {
+// org / org_istep (a batch that re-traces its critical rays, rtmi_batch_set_state): each ray's state9 and istep are also kept,
+// in slot order, as the state its re-trace starts from (Retrace::org)
+template <typename T> __global__ void k_set_state(BatchDev<T> a, const double* st, const double* hist, const int* istep, const unsigned char* live,
+                                                  double* org, int* org_istep) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.R) return;
     const long o = out_index(a, k);
@@ -2056,6 +2065,10 @@ template <typename T> __global__ void k_set_state(BatchDev<T> a, const double* s
     }
     if (a.hov) a.hov[k] = (a.rot && hist && live) ? (float)hist[(size_t)2 * a.R + o] : 0.f;     // the hover sum of a checkpoint (aux4 row 2)
     if (istep) a.istep[k] = istep[o];
+    if (org) {
+        for (int q = 0; q < 9; q++) org[(size_t)q * a.R + k] = st[(size_t)q * a.R + o];
+        org_istep[k] = a.istep[k];
+    }
     // a checkpoint knows which rays had left the box (a position outside it does not say so: op7's bootstrap rows skip the test)
     a.alive[k] = (live ? live[o] != 0 : true) && a.istep[k] + 1 < max_size_of(a, k);
 }
@@ -2080,6 +2093,22 @@ static int set_state_impl(rtmi_batch* b, const double* state9, const double* his
     ARG_TRY(b && state9, std::string(who) + ": null");
     DEVICE_TRY(b->field, who);
     const size_t R = (size_t)b->R;
+    // Rays an rtmi_step handed over and nobody has read yet belong to the state being replaced: their re-trace would land on the
+    // new one.  The queue is discarded (retrace_reset waits for the kernels that may still fill it) and its counts start over.
+    double* org = nullptr;
+    int* org_istep = nullptr;
+    if (b->rt) {
+        Retrace* t = b->rt;
+        const int rcr = retrace_reset(b);
+        if (rcr) return rcr;
+        if (!live) {       // a state of the caller's making: critical rays are re-traced from it (a checkpoint's from the launch conditions)
+            if (!t->org) {
+                HIP_TRY(hipMalloc(&t->org, 9 * R * sizeof(double) + R * sizeof(int)));
+                t->org_istep = (int*)(t->org + 9 * R);
+            }
+            org = t->org; org_istep = t->org_istep;
+        }
+    }
     b->dirty = true;
     b->dirty_state = true;
     void* stg = nullptr;
@@ -2095,13 +2124,16 @@ static int set_state_impl(rtmi_batch* b, const double* state9, const double* his
     if (e == hipSuccess) {
         const dim3 g((unsigned)((R + 255) / 256)), blk(256);
         if (b->p.dtype == RTMI_F64)
-            hipLaunchKernelGGL(k_set_state<double>, g, blk, 0, b->stream, batch_dev<double>(b), d, hist4 ? d + 9 * R : nullptr, istep ? di : nullptr, live ? dl : nullptr);
+            hipLaunchKernelGGL(k_set_state<double>, g, blk, 0, b->stream, batch_dev<double>(b), d, hist4 ? d + 9 * R : nullptr, istep ? di : nullptr, live ? dl : nullptr,
+                               org, org_istep);
         else
-            hipLaunchKernelGGL(k_set_state<float>, g, blk, 0, b->stream, batch_dev<float>(b), d, hist4 ? d + 9 * R : nullptr, istep ? di : nullptr, live ? dl : nullptr);
+            hipLaunchKernelGGL(k_set_state<float>, g, blk, 0, b->stream, batch_dev<float>(b), d, hist4 ? d + 9 * R : nullptr, istep ? di : nullptr, live ? dl : nullptr,
+                               org, org_istep);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    if (org) b->rt->from_set = true;
     return RTMI_OK;
 }
 RTMI_EXPORT int rtmi_batch_set_state(rtmi_batch* b, const double* state9, const double* hist4, const int32_t* istep) {
@@ -2421,7 +2453,7 @@ constexpr int kRetraceCus = 8;         // compute units set aside for the re-tra
 //   vector registers and starts the next one's loads a step ahead, rt::PolyLaneKept).
 template <int METHOD>
 __global__ __launch_bounds__(64, 3) void k_retrace_ref(BatchDev<double> s, BatchDev<double> m, const unsigned long long* rq, unsigned lo, unsigned hi,
-                                                       int marked_only, unsigned long long* dbg) {
+                                                       int marked_only, unsigned long long* dbg, const double* org, const int* org_istep) {
     typedef double T;
     __builtin_amdgcn_s_setprio(3);          // beside the main kernel's waves: a handful of waves on the critical path of the call
     const unsigned j = lo + blockIdx.x * blockDim.x + threadIdx.x;
@@ -2438,7 +2470,17 @@ __global__ __launch_bounds__(64, 3) void k_retrace_ref(BatchDev<double> s, Batch
     rt::Ray<T> r;
     int i = 0, out = 0;
     bool alive = valid && max_size > 1, handed = false;
-    if (valid) {                             // the initial conditions, as init_ray of a reference-order batch
+    if (valid && org) {                      // the state rtmi_batch_set_state gave the ray, as k_set_state stores it for a reference-order batch
+        const size_t R = (size_t)m.R;
+        r.x = org[k]; r.y = org[R + k]; r.th = org[2 * R + k];
+        r.n = org[3 * R + k]; r.gx = org[4 * R + k]; r.gy = org[5 * R + k];
+        rt::ex::derive(K, r);
+        r.dsim = org[6 * R + k]; r.dreal = org[7 * R + k]; r.tt = org[8 * R + k];
+        r.hx0 = r.hy0 = r.hx1 = r.hy1 = 0;
+        r.hov = 0.f;
+        i = org_istep[k];                    // rows up to here are not this run's: none is written
+        alive = i + 1 < max_size;
+    } else if (valid) {                      // the initial conditions, as init_ray of a reference-order batch
         r.x = m.x0[k]; r.y = m.y0[k]; r.th = m.th0[k];
         rt::ex::n_gradient(s.F, gg, true, (T)r.x, (T)r.y, r.n, r.gx, r.gy);
         rt::ex::derive(K, r);
@@ -2546,9 +2588,10 @@ static const void* retrace_tail_fn(int method, bool iso) {
     return tab[method == 1 ? 0 : method == 2 ? 1 : method == 6 ? 2 : 3][iso ? 1 : 0];
 }
 // ... and back: the re-traced ray's rows and final state over the fused ones.  A row the fused run wrote past the re-traced
-// ray's last row (the two may leave the box a row apart) reads 0 like every row past a ray's end (:802).
+// ray's last row (the two may leave the box a row apart) reads 0 like every row past a ray's end (:802).  org_istep (a re-trace
+// from the states rtmi_batch_set_state gave): only the rows after each ray's own are the run's.
 template <typename T>
-__global__ void k_retrace_scatter(BatchDev<T> m, BatchDev<T> s, const unsigned long long* rq, unsigned lo, unsigned hi) {
+__global__ void k_retrace_scatter(BatchDev<T> m, BatchDev<T> s, const unsigned long long* rq, unsigned lo, unsigned hi, const int* org_istep) {
     const unsigned j = lo + blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= hi) return;
     const unsigned long long e = rq[1 + j];
@@ -2559,7 +2602,8 @@ __global__ void k_retrace_scatter(BatchDev<T> m, BatchDev<T> s, const unsigned l
         const long rs = si / m.stride < s.rec_rows - 1 ? si / m.stride : s.rec_rows - 1;       // last recorded row of the re-trace
         long top = fused_last / m.stride > rs ? fused_last / m.stride : rs;
         top = top < m.rec_rows - 1 ? top : m.rec_rows - 1;
-        for (long row = blockIdx.y; row <= top; row += gridDim.y) {
+        const long first = org_istep ? org_istep[k] / m.stride + 1 : 0;
+        for (long row = first + blockIdx.y; row <= top; row += gridDim.y) {
 #pragma unroll
             for (int q = 0; q < 6; q++)
                 m.s_ray[((size_t)row * 6 + q) * m.R + k] = row <= rs ? s.s_ray[((size_t)row * 6 + q) * s.R + j] : T(0);
@@ -2583,7 +2627,7 @@ static void retrace_destroy(rtmi_batch* b) {
     if (!t) return;
     for (hipStream_t a : t->aux) if (a) (void)hipStreamSynchronize(a);
     if (t->sub) rtmi_batch_destroy(t->sub);
-    (void)hipFree(t->rq); (void)hipFree(t->hov); (void)hipFree(t->dbg);
+    (void)hipFree(t->rq); (void)hipFree(t->hov); (void)hipFree(t->dbg); (void)hipFree(t->org);
     if (t->host_count) (void)hipHostFree(t->host_count);
     if (t->ev_main) (void)hipEventDestroy(t->ev_main);
     for (hipEvent_t e : t->ev_aux) if (e) (void)hipEventDestroy(e);
@@ -2671,6 +2715,7 @@ static int retrace_reset(rtmi_batch* b) {
     memset(t->host_count, 0, (4 + (size_t)t->cap) * sizeof(unsigned));
     HIP_TRY(hipMemsetAsync(t->sub->counters + 3, 0, sizeof(unsigned long long), b->stream));
     t->launched = t->scattered = 0; t->pending = false; t->overflow = 0;
+    t->from_set = false;
     return RTMI_OK;
 }
 
@@ -2680,7 +2725,9 @@ static int retrace_launch_chunk(rtmi_batch* b, unsigned lo, unsigned hi, hipStre
     BatchDev<double> m = batch_dev<double>(b), s = batch_dev<double>(t->sub);
     const unsigned long long* rq = t->rq;
     unsigned long long* dbg = t->dbg;
-    void* args[] = {&s, &m, &rq, &lo, &hi, &marked_only, &dbg};
+    const double* org = t->from_set ? t->org : nullptr;
+    const int* org_istep = t->from_set ? t->org_istep : nullptr;
+    void* args[] = {&s, &m, &rq, &lo, &hi, &marked_only, &dbg, &org, &org_istep};
     const unsigned lanes = 64;         // rays per block = per wave (fewer -- 32, 16, 8 -- was tried: a lone wave's step is not shorter for it)
     HIP_TRY(hipLaunchKernel(retrace_ref_fn(b->p.method), dim3((hi - lo + lanes - 1) / lanes), dim3(lanes), args, 0, st));
     if (!marked_only) {
@@ -2797,7 +2844,7 @@ static int retrace_drain(rtmi_batch* b, bool overlap) {
         const long rows = b->p.record_stride ? (long)b->p.rec_rows : 1;
         const dim3 g((n + 63) / 64, (unsigned)std::min<long>(rows, 1024)), blk(64);
         hipLaunchKernelGGL(k_retrace_scatter<double>, g, blk, 0, b->stream, batch_dev<double>(b), batch_dev<double>(t->sub),
-                           (const unsigned long long*)t->rq, t->scattered, t->launched);
+                           (const unsigned long long*)t->rq, t->scattered, t->launched, (const int*)(t->from_set ? t->org_istep : nullptr));
         HIP_TRY(hipGetLastError());
         t->total += n;
         if (!t->rot_learned && overlap && t->scattered == 0 && !getenv("RTMI_NO_DISPATCH_ORDER")) {

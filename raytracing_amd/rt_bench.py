@@ -128,8 +128,9 @@ class StepMethod:
             if history is None:
                 raise ValueError("op7 needs history=[P0, P1] (the two positions before i_vpos; VECTOR_LIST, :73)")
             hist = np.ascontiguousarray(np.asarray(history, dtype=np.float64).reshape(4, 1))
+        # one step from a given state has nothing to hand over to a re-trace (rtmi_params.no_retrace)
         b = Batch(fld, self.method, step, max_size=1 << 20, box=(-1e300, 1e300, -1e300, 1e300), gamma=g,
-                  thetas=[i_angle], x0=[i_vpos[0]], y0=[i_vpos[1]], record_stride=0)
+                  thetas=[i_angle], x0=[i_vpos[0]], y0=[i_vpos[1]], record_stride=0, retrace=False)
         b.set_state(st, hist, np.array([3], dtype=np.int32))
         b.step(1)
         fin = b.final()[:, 0]

@@ -186,3 +186,66 @@ def test_delta_s_sweep_matches_reference(scen, oracle_fields):
             assert abs(rb.closure_error(r["s_ray"]) - ref[0]) < 1e-9
         else:
             assert abs(rb.moment_cv(r["s_ray"], R) - ref[0]) < 1e-9
+
+
+def _state_at(r, k, method):
+    """state9 (and op7's hist4) of trajectory r at row k: what rtmi_batch_set_state takes (d_ray holds dist_real, dist_sim)."""
+    fin, d = r["final"], r["d_ray"]
+    st9 = np.concatenate([fin[:6], d[1:2], d[0:1], fin[8:9]])
+    hist4 = None
+    if method == 7:
+        s = r["s_ray"]
+        prev = lambda j: s[j, :2] if j >= 0 else np.zeros_like(s[0, :2])      # state_init's history is zeros before row 0
+        hist4 = np.concatenate([prev(k - 2), prev(k - 1)])
+    return st9, hist4
+
+
+@pytest.mark.parametrize("name,scen,m", traj_fixtures())
+def test_trazar_from_state_continues_bit_for_bit(name, scen, m, oracle_fields):
+    """rto_trazar_from_state, the reference for runs continued from a caller-set state (rtmi_batch_set_state): a run stopped at
+    row k (max_size = k + 1) and continued from its final state is the unsplit run, bit for bit -- rows k+1 .., final, d_ray and
+    the step total -- for every method on every trajectory fixture's rays; at rows inside op7's bootstrap (1, 2, 3) and after
+    some rays have left the box (only the live ones are continued)."""
+    t = golden("traj_" + name)
+    F = oracle_fields(scen)
+    x0, y0, th = traj_inputs(t, scen)
+    gam, step, ms, box = float(t["gamma"]), float(t["step"]), int(t["max_size"]), t["box"]
+    R = len(th)
+    rows = int(t["d_ray"][2].max()) + 2
+    full = O.trazar(F, m, gam, step, ms, box, x0, y0, th, record_stride=1, rec_rows=rows, nthreads=4)
+    d2 = full["d_ray"][2]
+    ks = [2, 3, 200] + ([1] if m == 7 else [])
+    if d2.min() + 7 < d2.max():                               # a k after some rays have ended (all fixtures but one-ray ones)
+        ks.append(int(d2.min()) + 7)
+    for k in ks:
+        part = O.trazar(F, m, gam, step, k + 1, box, x0, y0, th, record_stride=1, rec_rows=k + 1, nthreads=4)
+        live = np.flatnonzero(d2 > k)
+        assert len(live) > 0
+        st9, hist4 = _state_at(part, k, m)
+        st9 = st9[:, live]
+        hist4 = hist4[:, live] if hist4 is not None else None
+        cont = O.trazar_from_state(F, m, gam, step, ms, box, st9, hist4, k, record_stride=1, rec_rows=rows, nthreads=4)
+        assert not cont["s_ray"][:k + 1].any(), "rows at or before istep are not the continuation's"
+        assert np.array_equal(cont["s_ray"][k + 1:], full["s_ray"][k + 1:, :, live]), f"k={k}"
+        assert np.array_equal(cont["final"], full["final"][:, live]) and np.array_equal(cont["d_ray"], full["d_ray"][:, live])
+        assert cont["steps"] == int(d2[live].sum())
+
+
+def test_trazar_from_state_edges(oracle_fields):
+    """istep = max_size - 1: no step, final is the state given; istep = max_size - 2: exactly one; a state outside the box
+    takes exactly one step (the reference tests the box after the step, :878)."""
+    F = oracle_fields("vert_heterogeneous")
+    box = LIMITS["vert_heterogeneous"]
+    st9 = np.zeros((9, 3))
+    st9[:3] = [[0.5, 0.7, 9.0], [-1.0, -0.5, -1.0], [0.3, 1.1, 0.2]]         # the third ray lies outside the box
+    st9[3:6] = np.stack(F.n_gradient(st9[0], st9[1]))
+    st9[6:] = [[1.0], [1.2], [0.3]]
+    ms = 50
+    r = O.trazar_from_state(F, 6, 1, 0.01, ms, box, st9, None, [ms - 1, ms - 2, 5], record_stride=1)
+    assert np.array_equal(r["d_ray"][2], [ms - 1, ms - 1, 6])
+    assert np.array_equal(r["final"][:6, 0], st9[:6, 0]) and r["final"][8, 0] == st9[8, 0]
+    assert r["d_ray"][0, 0] == st9[7, 0] and r["d_ray"][1, 0] == st9[6, 0]
+    assert not r["s_ray"][:, :, 0].any() and r["s_ray"][ms - 1, 0, 1] == r["final"][0, 1]
+    one = O.single_step(F, 6, 1, 0.01, np.concatenate([st9[:6], np.ones((1, 3))]).T)
+    assert np.array_equal(r["final"][:6, 1:].T, one[1:])
+    assert r["final"][0, 2] > box[1] and r["s_ray"][6, 0, 2] == r["final"][0, 2] and not r["s_ray"][7:, :, 2].any()
