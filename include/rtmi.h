@@ -142,13 +142,19 @@ typedef struct {
                                 op7 too (up to 8e-9 from the reference on the interface scenario); fp32 batches always run fused
                                 forms.  RTMI_ORDER_FAST_FIELD (3): as DEFAULT, but op7 takes its reference-order step -- the
                                 advancement's operation order, numpy's arctan2, glibc's sin / cos -- on the fused field lookup:
-                                2.3 times faster, <= 8e-11 from the reference except on rays grazing a sharp interface at its
-                                critical angle (2.6e-9 on one sampled ray of the 1 M-ray interface fan).  Such rays -- a handful
-                                of a million, running along a sharp interface -- are ill-conditioned in the reference itself
+                                2.3 times faster, <= 1e-10 from the reference except on rays grazing a sharp interface at its
+                                critical angle (2.6e-9 on one sampled ray of the 1 M-ray interface fan).  On every ray of the 1 M-ray
+                                vert_heterogeneous and fisheye fans: 9.5e-11 and 3.5e-11 (tests/test_gpu_every_ray.py) -- the
+                                lookup's last-bit differences random-walk through op7's differenced positions over a ray's
+                                steps, no one step adding more than 5e-14.  Rays grazing a sharp interface -- a handful
+                                of a million -- are ill-conditioned in the reference itself
                                 (its rows move 1e-6 for a 1e-12 change of the launch angle): there only the reference-order
                                 forms agree with it to 1e-9 -- which is why a DEFAULT fp64 op1/2/6/8 batch finds those rays on the way
                                 and re-traces them in reference order by itself (no_retrace below): every ray of a default batch is
-                                within 1e-9 of the reference */
+                                within 1e-9 of the reference, with the same step count.  Checked on EVERY ray of the 1 M-ray fans
+                                against a reference-order batch of the same fan (tests/test_gpu_every_ray.py): at most 8.4e-14
+                                (vert_heterogeneous), 1.9e-12 (fisheye), 2.1e-11 (interface) and 1.1e-10 (the interface's wall
+                                tilted by 3 and 11 degrees against the grid) over final state, d_ray and every 16th row */
     int32_t no_retrace;      /* 0 (default): a fused fp64 op1/2/6/8 batch on a field with a sharp transition (cells whose Hessian of n
                                 is large against the size of the grid: the interface scenario; none in fisheye / vert_heterogeneous)
                                 adds up, per ray and step, the steepness of the cell times |v . g| (v the ray's normal, g the
@@ -165,6 +171,9 @@ typedef struct {
                                 batch's first run; rays are independent (RT_bench.py:807), so no other ray's bits change.  rtmi_run does
                                 this before it returns; after rtmi_step it happens at the next call that reads results (rays handed
                                 over are no longer live, and are then at their END, ahead of the others).  1: never (A/B runs).
+                                Every ray of the 1 M-ray interface fan, and of the same wall tilted by 3 and 11 degrees, is
+                                within 1e-9 of a reference-order batch with the re-trace on (475 - 1 063 rays re-traced, the queue
+                                never full) and the fused forms alone leave 2 - 6 rays beyond it (tests/test_gpu_every_ray.py).
                                 The measure is calibrated on walls (the interface scenario's, also tilted against the grid);
                                 ill-conditioning of another kind -- e.g. the focusing of a strongly bent wall in a field given
                                 by samples -- is not seen by it: RTMI_ORDER_REFERENCE is the answer there.

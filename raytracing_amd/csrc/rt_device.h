@@ -1253,9 +1253,10 @@ constexpr int kRefOrder = 16;
 // reference's (its angle differentiates them: rtmi.hip, ref_order); n and grad n enter a position only through the second-order
 // term (DELTA_S^2 / 2n)(grad n - ...) ~ 1e-6, where the lookup's 1e-15 relative difference from FITPACK's moves a rounding on
 // few steps.  Everything else of the step -- the advancement's operation order, numpy's arctan2, glibc's sin / cos -- is
-// rt::ex's, bit for bit.  <= 8e-11 from the reference on 4 096- and 65 536-ray fans of every scenario at 2.3 times the speed of
-// reference order throughout; NOT the default, because a ray that grazes a sharp interface at its critical angle amplifies
-// the few rounding differences past 1e-9 (one of 16 384 sampled rays of the 1 M-ray interface fan: 2.6e-9).
+// rt::ex's, bit for bit.  <= 8e-11 from the reference on 4 096- and 65 536-ray fans of every scenario, 9.5e-11 on every ray of
+// the 1 M-ray vert_heterogeneous fan (the moved roundings random-walk over a ray's steps, and a million rays reach further into
+// the tail), at 2.3 times the speed of reference order throughout; NOT the default, because a ray that grazes a sharp
+// interface at its critical angle amplifies the few rounding differences past 1e-9 (one of 16 384 sampled rays of the 1 M-ray interface fan: 2.6e-9).
 constexpr int kFastField = 32;
 constexpr int base_method(int m) { return m & 15; }
 template <typename T, int METHOD> struct IsExact { static constexpr bool value = false; };
