@@ -264,6 +264,72 @@ int rtmi_isochrones(rtmi_batch *b, int32_t ntimes, const double *times, double *
 int rtmi_wavefronts(rtmi_batch *b, int32_t ntimes, const double *times, int32_t nfine, int64_t *count, double *nodes,
                     double *fine);
 
+/* Receiver-line crossings: where, when and at what angle each recorded ray crosses the line a x + b y = c (line[3] = a, b, c;
+ * (a, b) != (0, 0)).  (a, b) is normalised to a unit normal (a', b') and c to c'; a point's coordinate along the line is
+ * u = a' y - b' x, the signed distance of row i is f_i = a' x_i + b' y_i - c'.  Step i (rows i-1 -> i, 1 <= i <= the ray's last
+ * row) crosses when f_{i-1} < 0 <= f_i or f_{i-1} > 0 >= f_i: a ray starting on the line does not cross at row 0, a row on the
+ * line counts once, and the final step of a ray that left the box is included (a box edge is a valid receiver line).  On the
+ * step, the cubic Hermite curve H(tau) through rows i-1 and i with end tangents L (cos theta, sin theta) (L the chord length,
+ * theta the recorded angle) is solved for a' H_x + b' H_y = c' by bracketed Newton from the linear-interpolation tau (a step that
+ * leaves the bracket bisects; stop at g = 0, a bracket narrower than 2^-52 or 64 iterations).  Reported at the root tau*:
+ *   u, x, y   H(tau*) and its line coordinate
+ *   T         cubic Hermite between T_{i-1} and T_i with end slopes L (p_x cos theta + p_y sin theta) of the row, which is
+ *             coef*n = dT/ds in the isotropic and the anisotropic case (RT_bench.py:217-245): no n_ray needed
+ *   theta     the direction of H'(tau*)
+ *   s         i - 1 + tau*, the fractional step
+ * count[R]: crossings of each ray (it may exceed kmax; the first kmax are stored), -1 for a ray whose trajectory reaches past
+ * rec_rows (its crossings beyond the record are unknown).  out[kmax][6][R] = u, x, y, T, theta, s; NaN past count.  Host
+ * buffers, fp64, the caller's ray order; both dtypes.  Needs record_stride 1 (else RTMI_ERR_ARG).  One lane per ray reads x and
+ * y of every row and the other columns on crossing steps only.  The calling thread's current device must be the batch's. */
+int rtmi_crossings(rtmi_batch *b, const double line[3], int32_t kmax, int32_t *count, double *out);
+
+/* Two-point ray tracing: the rays from S sources to J receivers on one line (the shooting method, two-point form).
+ * Parameters of rtmi_two_point; a zero field takes its default. */
+typedef struct {
+    int32_t max_arrivals;    /* A: brackets (hence arrivals) kept per source and receiver (default 4, at most 64) */
+    int32_t max_crossings;   /* kmax: crossings of the line followed per ray (default 4, at most 64) */
+    int32_t max_iter;        /* refinement iterations (default 60) */
+    int32_t reserved0;
+    double tol;              /* converged when |u - u_j| <= tol (default 1e-10) */
+    int64_t mem_budget;      /* device bytes for trajectory records (default 8 GiB): sources are processed in groups below it */
+    int64_t reserved[4];
+} rtmi_two_point_params;
+typedef enum { RTMI_ARRIVAL_EMPTY = -1, RTMI_ARRIVAL_CONVERGED = 1, RTMI_ARRIVAL_STALLED = 2, RTMI_ARRIVAL_TRUNCATED = 3 } rtmi_arrival_status;
+typedef struct {
+    int32_t iterations;      /* refinement iterations of the longest group */
+    int32_t groups;          /* source groups the memory budget asked for */
+    int64_t rec_rows;        /* rows of the fan's record: the longest fan ray's last row + 1 (the count pass) */
+    uint64_t overflow;       /* brackets dropped because a (source, receiver) already had max_arrivals */
+    double fan_ms;           /* host wall time, with the stream synchronised: count pass, fan trace and its crossings */
+    double bracket_ms;       /* ... bracketing */
+    double refine_ms;        /* ... all refinement iterations */
+    double reserved[4];
+} rtmi_two_point_stats;
+/* f, p: the field and the trace parameters, used as given (method, step, max_size, box, gamma, gamma_step, reference_order,
+ * no_retrace, launch_mode, field_path, ...) except that the solver sets record_stride, rec_rows, sort_rays (0), no_n_ray (1),
+ * lazy_clear and the ext_* pointers itself.  fp64 only (RTMI_ERR_ARG for fp32).  sx, sy [S]: sources; thetas [M >= 2]: the
+ * launch fan shared by all sources; line[3] as rtmi_crossings; receivers_u [J]: receiver coordinates u on the line, finite and
+ * strictly increasing.  tp may be NULL (defaults); stats may be NULL.
+ * 1. Fan: a count pass (record_stride 0) sizes the record to the longest ray; the S x M rays are traced, in source groups when
+ *    S M rec_rows 48 bytes exceed the budget, and their crossings taken (rtmi_crossings).
+ * 2. Brackets: for adjacent fan rays m, m+1 of one source and each crossing index c < min(count_m, count_m+1), every receiver
+ *    with min(u) <= u_j < max(u) of the pair gets a bracket; at most A per (source, receiver) (the rest are counted in
+ *    stats.overflow, and which are kept then depends on the order of device atomics), sorted by (m, c).
+ * 3. Refinement: per iteration one ray per active bracket is traced at its angle (a batch of S J A rays relaunched with new
+ *    angles; finished brackets take no step), its c-th crossing taken, and Illinois regula falsi on u(theta) - u_j updates the
+ *    theta bracket (a step outside it bisects).  A bracket ends CONVERGED (|u - u_j| <= tol), STALLED (its theta ends are
+ *    adjacent doubles -- a discontinuity such as a shadow edge or a change of branch --, the ray has lost its c-th crossing, or
+ *    max_iter ran out) or TRUNCATED (the ray ran past the refinement record, the fan's rows plus an eighth; never reported as
+ *    a value).  One integer is read back per iteration.
+ * Outputs (host): count[S][J] converged arrivals, nbad[S][J] stalled or truncated brackets, arrivals[S][J][A][9] = launch theta,
+ * T, u, x, y, theta at the receiver, u - u_j, iterations, status (rtmi_arrival_status): converged arrivals first sorted by T, then
+ * the others (NaN in the value columns, the last angle traced in column 0), then empty slots.
+ * Each converged arrival is exactly what rtmi_crossings gives on a fresh batch of the same parameters traced from that source at
+ * the reported launch angle.  The calling thread's current device must be the field's. */
+int rtmi_two_point(const rtmi_field *f, const rtmi_params *p, int32_t S, const double *sx, const double *sy, int32_t M,
+                   const double *thetas, const double line[3], int32_t J, const double *receivers_u, const rtmi_two_point_params *tp,
+                   int32_t *count, int32_t *nbad, double *arrivals, rtmi_two_point_stats *stats);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

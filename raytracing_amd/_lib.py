@@ -57,6 +57,19 @@ class ShardStats(C.Structure):
                 ("run_seconds", C.c_double), ("kernel_ms_max", C.c_double), ("auto_fallbacks", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class TwoPointParams(C.Structure):
+    _fields_ = [("max_arrivals", C.c_int32), ("max_crossings", C.c_int32), ("max_iter", C.c_int32), ("reserved0", C.c_int32),
+                ("tol", C.c_double), ("mem_budget", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
+class TwoPointStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("groups", C.c_int32), ("rec_rows", C.c_int64), ("overflow", C.c_uint64),
+                ("fan_ms", C.c_double), ("bracket_ms", C.c_double), ("refine_ms", C.c_double), ("reserved", C.c_double * 4)]
+
+
+# rtmi_arrival_status
+ARRIVAL_EMPTY, ARRIVAL_CONVERGED, ARRIVAL_STALLED, ARRIVAL_TRUNCATED = -1, 1, 2, 3
+
 SHARD_AUTO, SHARD_RCCL, SHARD_COPY = 0, 1, 2
 # every symbol include/rtmi.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -88,6 +101,9 @@ SYMBOLS = {
     "rtmi_metric": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "rtmi_isochrones": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "rtmi_wavefronts": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
+    "rtmi_crossings": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, _dp]),
+    "rtmi_two_point": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp,
+                                 C.POINTER(TwoPointParams), _ip, _ip, _dp, C.POINTER(TwoPointStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

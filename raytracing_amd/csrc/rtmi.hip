@@ -2041,6 +2041,44 @@ RTMI_EXPORT int rtmi_batch_reset(rtmi_batch* b) {
     return batch_init_state(b, b->dirty || !b->p.lazy_clear);
 }
 
+// New launch angles (and optionally per-ray max_size) from device memory, then a reset.  The angles replace the batch's stored
+// launch conditions, so that the re-trace of critical rays (which restarts from b->launch) follows them.  Host code only: plain
+// device-to-device copies, which is why a sorted batch (perm) is refused.
+int rtmi_internal_relaunch(rtmi_batch* b, const double* theta0, const int32_t* max_size) {
+    ARG_TRY(b && theta0, "rtmi_internal_relaunch: null");
+    if (b->perm) return fail(RTMI_ERR_STATE, "rtmi_internal_relaunch: not on a batch with sort_rays");
+    ARG_TRY(!(max_size && b->p.launch_mode != RTMI_LAUNCH_PLAIN && b->p.launch_mode != RTMI_LAUNCH_AUTO),
+            "rtmi_internal_relaunch: per-ray max_size runs on the one-lane-per-ray kernel (RTMI_LAUNCH_PLAIN or RTMI_LAUNCH_AUTO)");
+    DEVICE_TRY(b->field, "rtmi_internal_relaunch");
+    drop_graph(b);
+    const size_t R = (size_t)b->R;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpyAsync(b->launch + 2 * R, theta0, R * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+    if (max_size) {
+        if (!b->vstep) {   // the uniform step as per-ray values: the VAR build then gives every ray the bits of the uniform one
+            std::vector<double> h1, h2;
+            std::vector<float> f1, f2;
+            try {
+                if (b->p.dtype == RTMI_F64) { h1.assign(R, b->p.step); h2.assign(R, libm_square(b->p.step) / 2.0); }
+                else { f1.assign(R, (float)b->p.step); f2.assign(R, (float)(libm_square(b->p.step) / 2.0)); }
+            } catch (const std::exception& e) {
+                return fail(RTMI_ERR_ALLOC, std::string("rtmi_internal_relaunch: ") + e.what());
+            }
+            HIP_TRY(hipMalloc(&b->vstep, R * b->esz));
+            HIP_TRY(hipMalloc(&b->vstep2h, R * b->esz));
+            HIP_TRY(hipMalloc(&b->vmax, R * sizeof(int)));
+            const void* p1 = b->p.dtype == RTMI_F64 ? (const void*)h1.data() : (const void*)f1.data();
+            const void* p2 = b->p.dtype == RTMI_F64 ? (const void*)h2.data() : (const void*)f2.data();
+            HIP_TRY(hipMemcpy(b->vstep, p1, R * b->esz, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(b->vstep2h, p2, R * b->esz, hipMemcpyHostToDevice));
+            b->kfn = pick_advance(b);
+        }
+        HIP_TRY(hipMemcpyAsync(b->vmax, max_size, R * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
+    }
+    b->dirty = true;   // new launch conditions: rows of the previous pass are not rewritten
+    return batch_init_state(b, true);
+}
+
 // org / org_istep (a batch that re-traces its critical rays, rtmi_batch_set_state): each ray's state9 and istep are also kept,
 // in slot order, as the state its re-trace starts from (Retrace::org)
 template <typename T> __global__ void k_set_state(BatchDev<T> a, const double* st, const double* hist, const int* istep, const unsigned char* live,

@@ -13,3 +13,8 @@ int rtmi_internal_isochrones_device(rtmi_batch* b, int32_t ntimes, const double*
 // dst -- DEVICE memory on the batch's device -- by a kernel enqueued on `stream` (a hipStream_t) after the batch's own stream
 // has been synchronised.  For shard.hip's device-to-device read-back.
 int rtmi_internal_pack_device(rtmi_batch* b, int what, double* dst, void* stream);
+// Relaunch: theta0 [R] (DEVICE, fp64) become the batch's launch angles -- the stored launch conditions that the re-trace of
+// critical rays restarts from, not only the ray state -- and the batch is reset (trajectory arrays cleared).  max_size [R]
+// (DEVICE, may be NULL) sets per-ray max_size as rtmi_batch_set_per_ray does, with the batch's own DELTA_S; values below 2 are
+// allowed here (1: the ray takes no step).  Not on a batch with sort_rays (RTMI_ERR_STATE).  For twopoint.hip's refinement.
+int rtmi_internal_relaunch(rtmi_batch* b, const double* theta0, const int32_t* max_size);

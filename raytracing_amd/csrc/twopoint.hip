@@ -1,0 +1,498 @@
+// twopoint.hip -- receiver-line crossings of recorded rays (rtmi_crossings) and two-point ray tracing from sources to
+// receivers on a line (rtmi_two_point): the shooting method of the reference's paper setting, in its two-point form.
+// Batches are read through the public rtmi_batch_view; the only hook into rtmi.hip is rtmi_internal_relaunch.
+//
+// The crossing arithmetic is written in one fixed order (compiled with -ffp-contract=off, sin/cos glibc's own through
+// rt_libm.h) so that tests/crossing_ref.py, a numpy restatement, gives the same bits; the receiver angle goes through the
+// device's atan2 (within an ulp of numpy's).  DESIGN.md section 9 describes the rules.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/rtmi.h"
+#include "rt_libm.h"
+#include "rtmi_internal.h"
+
+#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
+#define TP_TRY(expr)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+#define TP_ARG(cond, msg)                                                    \
+    do {                                                                     \
+        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
+    } while (0)
+#define TP_RC(expr)                  \
+    do {                             \
+        const int rc_ = (expr);      \
+        if (rc_) return rc_;         \
+    } while (0)
+
+namespace {
+
+__device__ const double kTab[4 * RT_SINCOS_TAB_ENTRIES] = {RT_SINCOS_TAB_VALUES};
+__device__ __forceinline__ double sin_g(double x) { return rt::gl::in_range(x) ? rt::gl::sin(kTab, x) : sin(x); }
+__device__ __forceinline__ double cos_g(double x) { return rt::gl::in_range(x) ? rt::gl::cos(kTab, x) : cos(x); }
+
+// The normalised line a' x + b' y = c' (host, fp64).  tests/crossing_ref.py normalises the same way.
+struct Line { double a, b, c; };
+static bool make_line(const double* l, Line* out) {
+    const double nrm = std::sqrt(l[0] * l[0] + l[1] * l[1]);
+    if (!(nrm > 0) || !std::isfinite(nrm) || !std::isfinite(l[2])) return false;
+    *out = Line{l[0] / nrm, l[1] / nrm, l[2] / nrm};
+    return true;
+}
+
+// The cubic Hermite basis at tau, and its derivative
+struct Basis { double h00, h10, h01, h11; };
+__device__ __forceinline__ Basis basis(double t) {
+    const double t2 = t * t, t3 = t2 * t;
+    return Basis{(2.0 * t3 - 3.0 * t2) + 1.0, (t3 - 2.0 * t2) + t, 3.0 * t2 - 2.0 * t3, t3 - t2};
+}
+__device__ __forceinline__ Basis dbasis(double t) {
+    const double t2 = t * t;
+    return Basis{6.0 * t2 - 6.0 * t, (3.0 * t2 - 4.0 * t) + 1.0, 6.0 * t - 6.0 * t2, 3.0 * t2 - 2.0 * t};
+}
+__device__ __forceinline__ double herm(const Basis& h, double p0, double m0, double p1, double m1) {
+    return ((p0 * h.h00 + m0 * h.h10) + p1 * h.h01) + m1 * h.h11;
+}
+
+// One lane per ray (slot k), looping over its rows [row][6][R].  x and y are read on every row; the other columns only on a
+// step that crosses.  count[o] = crossings (-1: the trajectory reaches past rec_rows), out[kmax][6][R] = u x y T theta s.
+template <typename T>
+__global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t* perm, long R, long rec_rows, Line L, int kmax,
+                            int32_t* count, double* out) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= R) return;
+    const long o = perm ? (long)perm[k] : k;
+    const size_t P = (size_t)6 * R;
+    const T* col = s_ray + k;
+    const long last = istep[k];
+    int n = 0;
+    if (last >= rec_rows) {
+        n = -1;
+    } else {
+        double x0 = (double)col[0], y0 = (double)col[R];
+        double f0 = (L.a * x0 + L.b * y0) - L.c;
+        for (long i = 1; i <= last; i++) {
+            const double x1 = (double)col[(size_t)i * P], y1 = (double)col[(size_t)i * P + R];
+            const double f1 = (L.a * x1 + L.b * y1) - L.c;
+            if ((f0 < 0.0 && f1 >= 0.0) || (f0 > 0.0 && f1 <= 0.0)) {
+                if (n < kmax) {
+                    const T* r0 = col + (size_t)(i - 1) * P;
+                    const T* r1 = col + (size_t)i * P;
+                    const double th0 = (double)r0[5 * R], th1 = (double)r1[5 * R];
+                    const double c0 = cos_g(th0), s0 = sin_g(th0), c1 = cos_g(th1), s1 = sin_g(th1);
+                    const double dx = x1 - x0, dy = y1 - y0;
+                    const double len = sqrt(dx * dx + dy * dy);
+                    const double tx0 = len * c0, ty0 = len * s0, tx1 = len * c1, ty1 = len * s1;
+                    const double d0 = len * (L.a * c0 + L.b * s0), d1 = len * (L.a * c1 + L.b * s1);
+                    // bracketed Newton on g(tau) = a' H_x + b' H_y - c', from the linear-interpolation tau
+                    double tau = f1 == 0.0 ? 1.0 : f0 / (f0 - f1);
+                    double lo = 0.0, hi = 1.0;
+                    for (int it = 0; it < 64 && f1 != 0.0; it++) {
+                        const double g = herm(basis(tau), f0, d0, f1, d1);
+                        if (g == 0.0) break;
+                        if ((g < 0.0) == (f0 < 0.0)) lo = tau; else hi = tau;
+                        if (hi - lo < 0x1p-52) break;
+                        const double gd = herm(dbasis(tau), f0, d0, f1, d1);
+                        const double tn = tau - g / gd;
+                        tau = (tn > lo && tn < hi) ? tn : 0.5 * (lo + hi);
+                    }
+                    const Basis h = basis(tau), hd = dbasis(tau);
+                    const double x = herm(h, x0, tx0, x1, tx1), y = herm(h, y0, ty0, y1, ty1);
+                    const double m0 = (double)r0[2 * R] * c0 + (double)r0[3 * R] * s0;     // p . (cos, sin) = dT/ds
+                    const double m1 = (double)r1[2 * R] * c1 + (double)r1[3 * R] * s1;
+                    const double tt = herm(h, (double)r0[4 * R], len * m0, (double)r1[4 * R], len * m1);
+                    const double th = atan2(herm(hd, y0, ty0, y1, ty1), herm(hd, x0, tx0, x1, tx1));
+                    const double v[6] = {L.a * y - L.b * x, x, y, tt, th, (double)(i - 1) + tau};
+                    for (int q = 0; q < 6; q++) out[((size_t)n * 6 + q) * R + o] = v[q];
+                }
+                n++;
+            }
+            x0 = x1; y0 = y1; f0 = f1;
+        }
+    }
+    count[o] = n;
+    for (int c = n < 0 ? 0 : n; c < kmax; c++)
+        for (int q = 0; q < 6; q++) out[((size_t)c * 6 + q) * R + o] = NAN;
+}
+
+int crossings_device(rtmi_batch* b, const Line& L, int kmax, int32_t* d_count, double* d_out, hipStream_t st, const char* who) {
+    rtmi_device_view v;
+    TP_RC(rtmi_batch_view(b, &v));
+    if (v.record_stride != 1)
+        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": needs the full trajectory (record_stride 1)").c_str());
+    TP_RC(rtmi_sync(b));
+    const dim3 g((unsigned)((v.R + 255) / 256)), blk(256);
+    if (v.dtype == RTMI_F64)
+        hipLaunchKernelGGL(k_crossings<double>, g, blk, 0, st, (const double*)v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L,
+                           kmax, d_count, d_out);
+    else
+        hipLaunchKernelGGL(k_crossings<float>, g, blk, 0, st, (const float*)v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L,
+                           kmax, d_count, d_out);
+    TP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
+// ------------------------------------------------------------------ two-point
+enum : int32_t { ST_EMPTY = -1, ST_ACTIVE = 0, ST_CONVERGED = RTMI_ARRIVAL_CONVERGED, ST_STALLED = RTMI_ARRIVAL_STALLED,
+                 ST_TRUNCATED = RTMI_ARRIVAL_TRUNCATED };
+
+// One bracket (source, receiver, slot): the crossing index it follows and the Illinois state on theta.
+struct Bracket {
+    double ta, tb, fa, fb;    // theta ends and u - u_j there
+    double th;                // the angle traced next / last traced
+    int32_t c, side, status, iters;
+    int32_t key;              // m * kmax + c: the fan pair and crossing it came from (the sort key)
+    int32_t pad_;
+    double res[6];            // u x y T theta(receiver) at the converged crossing
+};
+
+__device__ __forceinline__ double falsi(double ta, double tb, double fa, double fb) {
+    const double t = (ta * fb - tb * fa) / (fb - fa);
+    const double lo = fmin(ta, tb), hi = fmax(ta, tb);
+    return (t > lo && t < hi) ? t : ta + 0.5 * (tb - ta);
+}
+
+// the max of istep over rays -> *m (initialised to 0)
+__global__ void k_max_istep(const int32_t* istep, long R, int32_t* m) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < R) atomicMax(m, istep[k]);
+}
+
+// One thread per (source, fan pair m, crossing c): every receiver u_j in [min, max) of the pair's two u gets a bracket.
+__global__ void k_brackets(const int32_t* count, const double* cr, long Rg, int S, int M, int kmax, const double* thetas,
+                           const double* ru, int J, int A, int32_t* nslot, Bracket* br, unsigned long long* overflow) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)(M - 1) * kmax;
+    if (t >= (long)S * per) return;
+    const int s = (int)(t / per), m = (int)(t % per / kmax), c = (int)(t % kmax);
+    const long r0 = (long)s * M + m, r1 = r0 + 1;
+    const int n = min(count[r0], count[r1]);
+    if (c >= n) return;
+    const double ua = cr[(size_t)c * 6 * Rg + r0], ub = cr[(size_t)c * 6 * Rg + r1];
+    const double lo = fmin(ua, ub), hi = fmax(ua, ub);
+    if (!(lo < hi)) return;
+    int j0 = 0, j1 = J;                                // first j with ru[j] >= lo
+    while (j0 < j1) {
+        const int mid = (j0 + j1) >> 1;
+        if (ru[mid] < lo) j0 = mid + 1; else j1 = mid;
+    }
+    for (int j = j0; j < J && ru[j] < hi; j++) {
+        const int slot = atomicAdd(nslot + (size_t)s * J + j, 1);
+        if (slot >= A) { atomicAdd(overflow, 1ull); continue; }
+        Bracket& q = br[((size_t)s * J + j) * A + slot];
+        q.ta = thetas[m]; q.tb = thetas[m + 1];
+        q.fa = ua - ru[j]; q.fb = ub - ru[j];
+        q.th = q.fa == 0.0 ? q.ta : q.fb == 0.0 ? q.tb : falsi(q.ta, q.tb, q.fa, q.fb);
+        q.c = c; q.side = 0; q.status = ST_ACTIVE; q.iters = 0; q.key = m * kmax + c;
+    }
+}
+
+// Per (source, receiver): slots in (m, c) order, so that the result does not depend on the order of the atomics; empty
+// slots are marked.  Then the theta to trace and the per-ray max_size (1 for a slot with nothing to trace).
+__global__ void k_sort_brackets(int SJ, int A, const int32_t* nslot, Bracket* br, double* th, int32_t* ms, int32_t max_size) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= SJ) return;
+    Bracket* q = br + (size_t)t * A;
+    const int n = min(nslot[t], A);
+    for (int i = 1; i < n; i++)
+        for (int j = i; j > 0 && q[j - 1].key > q[j].key; j--) { const Bracket w = q[j]; q[j] = q[j - 1]; q[j - 1] = w; }
+    for (int i = 0; i < A; i++) {
+        if (i >= n) q[i].status = ST_EMPTY;
+        th[(size_t)t * A + i] = i < n ? q[i].th : 0.0;
+        ms[(size_t)t * A + i] = i < n ? max_size : 1;
+    }
+}
+
+// After a trace of every active bracket's theta: converged / stalled / truncated, or the next Illinois angle.
+__global__ void k_update(long NB, int J, int A, const double* ru, const int32_t* count, const double* cr, double tol, Bracket* br,
+                         double* th, int32_t* ms, int32_t* active) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= NB) return;
+    Bracket& q = br[t];
+    if (q.status != ST_ACTIVE) return;
+    const double uj = ru[(t / A) % J];
+    q.iters++;
+    const int n = count[t];
+    if (n < 0) { q.status = ST_TRUNCATED; ms[t] = 1; return; }
+    if (n <= q.c) { q.status = ST_STALLED; ms[t] = 1; return; }      // the branch is lost: a discontinuity in theta
+    const double u = cr[(size_t)q.c * 6 * NB + t];
+    const double f = u - uj;
+    if (fabs(f) <= tol) {
+        q.status = ST_CONVERGED;
+        for (int c = 0; c < 5; c++) q.res[c] = cr[((size_t)q.c * 6 + c) * NB + t];
+        q.res[5] = f;
+        ms[t] = 1;
+        return;
+    }
+    // Illinois: a retained end whose side is kept twice in a row has its value halved
+    if ((f < 0.0) == (q.fb < 0.0)) {
+        q.tb = q.th; q.fb = f;
+        if (q.side == -1) q.fa *= 0.5;
+        q.side = -1;
+    } else {
+        q.ta = q.th; q.fa = f;
+        if (q.side == 1) q.fb *= 0.5;
+        q.side = 1;
+    }
+    if (q.ta == q.tb || nextafter(q.ta, q.tb) == q.tb) { q.status = ST_STALLED; ms[t] = 1; return; }
+    q.th = falsi(q.ta, q.tb, q.fa, q.fb);
+    th[t] = q.th;
+    atomicAdd(active, 1);
+}
+
+// Per (source, receiver): converged arrivals first, by T (ties in (m, c) order), then the others in (m, c) order.
+// out[A][9] per pair: launch theta, T, u, x, y, theta at the receiver, u - u_j, iterations, status.
+__global__ void k_output(int SJ, int A, const Bracket* br, double* out, int32_t* cnt, int32_t* bad) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= SJ) return;
+    const Bracket* q = br + (size_t)t * A;
+    double* o = out + (size_t)t * A * 9;
+    int nc = 0, nb = 0, w = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int i = 0; i < A; i++) {
+            const bool conv = q[i].status == ST_CONVERGED;
+            if (q[i].status == ST_EMPTY || conv != (pass == 0)) continue;
+            int at = w;
+            if (conv) {    // insertion by T among the converged ones written so far (stable: keeps (m, c) order on ties)
+                while (at > 0 && o[(size_t)(at - 1) * 9 + 1] > q[i].res[3]) {
+                    for (int f = 0; f < 9; f++) o[(size_t)at * 9 + f] = o[(size_t)(at - 1) * 9 + f];
+                    at--;
+                }
+                nc++;
+            } else {
+                nb++;
+            }
+            double* e = o + (size_t)at * 9;
+            e[0] = q[i].th;
+            e[1] = conv ? q[i].res[3] : NAN;
+            e[2] = conv ? q[i].res[0] : NAN;
+            e[3] = conv ? q[i].res[1] : NAN;
+            e[4] = conv ? q[i].res[2] : NAN;
+            e[5] = conv ? q[i].res[4] : NAN;
+            e[6] = conv ? q[i].res[5] : NAN;
+            e[7] = (double)q[i].iters;
+            e[8] = (double)(q[i].status == ST_ACTIVE ? ST_STALLED : q[i].status);     // max_iter ran out: reported as stalled
+            w++;
+        }
+    }
+    for (int i = w; i < A; i++) {
+        double* e = o + (size_t)i * 9;
+        for (int f = 0; f < 8; f++) e[f] = NAN;
+        e[8] = (double)ST_EMPTY;
+    }
+    cnt[t] = nc;
+    bad[t] = nb;
+}
+
+// device allocations of one call, freed on every way out
+struct DevMem {
+    std::vector<void*> p;
+    template <typename T> hipError_t get(T** out, size_t bytes) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
+        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
+        return e;
+    }
+    ~DevMem() { for (void* v : p) (void)hipFree(v); }
+};
+struct BatchGuard {
+    rtmi_batch* b = nullptr;
+    ~BatchGuard() { rtmi_batch_destroy(b); }
+};
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
+};
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_crossings(rtmi_batch* b, const double line[3], int32_t kmax, int32_t* count, double* out) {
+    const char* who = "rtmi_crossings";
+    TP_ARG(b && line && count && out, "rtmi_crossings: null");
+    TP_ARG(kmax >= 1, "rtmi_crossings: kmax must be >= 1");
+    Line L;
+    TP_ARG(make_line(line, &L), "rtmi_crossings: the line needs (a, b) != (0, 0) and finite coefficients");
+    rtmi_device_view v;
+    TP_RC(rtmi_batch_view(b, &v));
+    TP_ARG(v.record_stride == 1, "rtmi_crossings: needs the full trajectory (record_stride 1)");
+    const size_t R = (size_t)v.R;
+    DevMem mem;
+    int32_t* dc = nullptr;
+    double* dout = nullptr;
+    TP_TRY(mem.get(&dc, R * sizeof(int32_t)));
+    TP_TRY(mem.get(&dout, (size_t)kmax * 6 * R * sizeof(double)));
+    TP_RC(crossings_device(b, L, kmax, dc, dout, nullptr, who));
+    TP_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    TP_TRY(hipMemcpy(out, dout, (size_t)kmax * 6 * R * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_t S, const double* sx, const double* sy, int32_t M,
+                               const double* thetas, const double line[3], int32_t J, const double* receivers_u,
+                               const rtmi_two_point_params* tp, int32_t* count, int32_t* nbad, double* arrivals,
+                               rtmi_two_point_stats* stats) {
+    const char* who = "rtmi_two_point";
+    TP_ARG(f && p && sx && sy && thetas && line && receivers_u && count && nbad && arrivals, "rtmi_two_point: null");
+    TP_ARG(S >= 1 && M >= 2 && J >= 1, "rtmi_two_point: needs S >= 1 sources, M >= 2 launch angles and J >= 1 receivers");
+    TP_ARG(p->dtype == RTMI_F64, "rtmi_two_point: fp64 only");
+    Line L;
+    TP_ARG(make_line(line, &L), "rtmi_two_point: the line needs (a, b) != (0, 0) and finite coefficients");
+    for (int j = 0; j < J; j++)
+        TP_ARG(std::isfinite(receivers_u[j]) && (j == 0 || receivers_u[j] > receivers_u[j - 1]),
+               "rtmi_two_point: receivers_u must be finite and strictly increasing");
+    for (int m = 0; m < M; m++) TP_ARG(std::isfinite(thetas[m]), "rtmi_two_point: launch angles must be finite");
+    rtmi_two_point_params q{};
+    if (tp) q = *tp;
+    const int A = q.max_arrivals ? q.max_arrivals : 4, K = q.max_crossings ? q.max_crossings : 4;
+    const int max_iter = q.max_iter ? q.max_iter : 60;
+    const double tol = q.tol != 0.0 ? q.tol : 1e-10;
+    const int64_t budget = q.mem_budget ? q.mem_budget : (int64_t)8 << 30;
+    TP_ARG(A >= 1 && A <= 64 && K >= 1 && K <= 64 && max_iter >= 1 && tol > 0 && budget > 0,
+           "rtmi_two_point: max_arrivals and max_crossings must be in [1, 64], max_iter >= 1, tol > 0, mem_budget > 0");
+    TP_ARG((int64_t)S * M < (1ll << 31) && (int64_t)S * J * A < (1ll << 31), "rtmi_two_point: too many rays");
+
+    rtmi_two_point_stats st{};
+    StreamGuard sg;
+    TP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    const hipStream_t strm = sg.s;
+    rtmi_params pb = *p;
+    pb.sort_rays = 0; pb.ext_s_ray = nullptr; pb.ext_n_ray = nullptr; pb.no_n_ray = 1; pb.lazy_clear = 0;
+    DevMem mem;
+    int32_t* dmax = nullptr;
+    double *dth = nullptr, *dru = nullptr;
+    TP_TRY(mem.get(&dmax, sizeof(int32_t)));
+    TP_TRY(mem.get(&dth, (size_t)M * 8));
+    TP_TRY(mem.get(&dru, (size_t)J * 8));
+    TP_TRY(hipMemcpy(dth, thetas, (size_t)M * 8, hipMemcpyHostToDevice));
+    TP_TRY(hipMemcpy(dru, receivers_u, (size_t)J * 8, hipMemcpyHostToDevice));
+
+    // 1. the count pass: every source's fan without a record; its longest ray sizes the record
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> hx, hy, ht;
+    try {
+        hx.resize((size_t)S * M); hy.resize((size_t)S * M); ht.resize((size_t)S * M);
+    } catch (const std::exception& e) {
+        return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": " + e.what()).c_str());
+    }
+    for (int s = 0; s < S; s++)
+        for (int m = 0; m < M; m++) { hx[(size_t)s * M + m] = sx[s]; hy[(size_t)s * M + m] = sy[s]; ht[(size_t)s * M + m] = thetas[m]; }
+    int32_t fan_rows = 0;
+    {
+        rtmi_params pc = pb;
+        pc.record_stride = 0; pc.rec_rows = 0;
+        BatchGuard bc;
+        TP_RC(rtmi_batch_create(f, &pc, (int64_t)S * M, hx.data(), hy.data(), ht.data(), (void*)strm, &bc.b));
+        TP_RC(rtmi_run(bc.b));
+        rtmi_device_view v;
+        TP_RC(rtmi_batch_view(bc.b, &v));
+        TP_TRY(hipMemsetAsync(dmax, 0, sizeof(int32_t), strm));
+        hipLaunchKernelGGL(k_max_istep, dim3((unsigned)((v.R + 255) / 256)), dim3(256), 0, strm, v.istep, (long)v.R, dmax);
+        TP_TRY(hipGetLastError());
+        TP_TRY(hipMemcpyAsync(&fan_rows, dmax, sizeof(int32_t), hipMemcpyDeviceToHost, strm));
+        TP_TRY(hipStreamSynchronize(strm));
+    }
+    const int64_t rec_fan = (int64_t)fan_rows + 1;
+    // refinement rays may run a little longer than any fan ray; those that run past the record are reported as truncated
+    const int64_t rec_ref = std::min<int64_t>(p->max_size, rec_fan + rec_fan / 8 + 16);
+    const int64_t per_src = 48 * std::max<int64_t>((int64_t)M * rec_fan, (int64_t)J * A * rec_ref);
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(S, budget / per_src));
+    st.rec_rows = rec_fan;
+    st.fan_ms += ms_since(t0);
+
+    for (int s0 = 0; s0 < S; s0 += G) {
+        const int Sg = std::min(G, S - s0);
+        const long Rf = (long)Sg * M, NB = (long)Sg * J * A;
+        DevMem gm;
+        int32_t *fc = nullptr, *nslot = nullptr, *ms = nullptr, *rc = nullptr, *active = nullptr, *dcnt = nullptr, *dbad = nullptr;
+        double *fcr = nullptr, *rcr = nullptr, *th = nullptr, *dout = nullptr;
+        Bracket* br = nullptr;
+        unsigned long long* dover = nullptr;
+        TP_TRY(gm.get(&fc, Rf * 4)); TP_TRY(gm.get(&fcr, (size_t)K * 6 * Rf * 8));
+        TP_TRY(gm.get(&nslot, (size_t)Sg * J * 4)); TP_TRY(gm.get(&br, NB * sizeof(Bracket)));
+        TP_TRY(gm.get(&ms, NB * 4)); TP_TRY(gm.get(&th, NB * 8));
+        TP_TRY(gm.get(&rc, NB * 4)); TP_TRY(gm.get(&rcr, (size_t)K * 6 * NB * 8));
+        TP_TRY(gm.get(&active, 4)); TP_TRY(gm.get(&dover, 8));
+        TP_TRY(gm.get(&dcnt, (size_t)Sg * J * 4)); TP_TRY(gm.get(&dbad, (size_t)Sg * J * 4)); TP_TRY(gm.get(&dout, NB * 9 * 8));
+
+        // 2. the fan, recorded, and its crossings
+        t0 = std::chrono::steady_clock::now();
+        {
+            rtmi_params pf = pb;
+            pf.record_stride = 1; pf.rec_rows = rec_fan;
+            BatchGuard bf;
+            TP_RC(rtmi_batch_create(f, &pf, Rf, hx.data() + (size_t)s0 * M, hy.data() + (size_t)s0 * M, ht.data() + (size_t)s0 * M,
+                                    (void*)strm, &bf.b));
+            TP_RC(rtmi_run(bf.b));
+            TP_RC(crossings_device(bf.b, L, K, fc, fcr, strm, who));
+            TP_TRY(hipStreamSynchronize(strm));
+        }
+        st.fan_ms += ms_since(t0);
+
+        // 3. brackets
+        t0 = std::chrono::steady_clock::now();
+        TP_TRY(hipMemsetAsync(nslot, 0, (size_t)Sg * J * 4, strm));
+        TP_TRY(hipMemsetAsync(dover, 0, 8, strm));
+        const long nt = (long)Sg * (M - 1) * K;
+        hipLaunchKernelGGL(k_brackets, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, strm, fc, fcr, Rf, Sg, M, K, dth, dru, J, A, nslot,
+                           br, dover);
+        hipLaunchKernelGGL(k_sort_brackets, dim3((unsigned)((Sg * J + 255) / 256)), dim3(256), 0, strm, Sg * J, A, nslot, br, th, ms,
+                           p->max_size);
+        TP_TRY(hipGetLastError());
+        unsigned long long over = 0;
+        TP_TRY(hipMemcpyAsync(&over, dover, 8, hipMemcpyDeviceToHost, strm));
+        TP_TRY(hipStreamSynchronize(strm));
+        st.overflow += over;
+        st.bracket_ms += ms_since(t0);
+
+        // 4. refinement: one ray per bracket per iteration; brackets that are done get max_size 1 and take no step
+        t0 = std::chrono::steady_clock::now();
+        {
+            rtmi_params pr = pb;
+            pr.record_stride = 1; pr.rec_rows = rec_ref;
+            pr.launch_mode = RTMI_LAUNCH_PLAIN;
+            std::vector<double> hxr((size_t)NB), hyr((size_t)NB), htr((size_t)NB, 0.0);
+            for (long t = 0; t < NB; t++) { hxr[t] = sx[s0 + t / ((long)J * A)]; hyr[t] = sy[s0 + t / ((long)J * A)]; }
+            BatchGuard brt;
+            TP_RC(rtmi_batch_create(f, &pr, NB, hxr.data(), hyr.data(), htr.data(), (void*)strm, &brt.b));
+            int it = 0;
+            for (; it < max_iter; it++) {
+                TP_RC(rtmi_internal_relaunch(brt.b, th, ms));
+                TP_RC(rtmi_run(brt.b));
+                TP_RC(crossings_device(brt.b, L, K, rc, rcr, strm, who));
+                TP_TRY(hipMemsetAsync(active, 0, 4, strm));
+                hipLaunchKernelGGL(k_update, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, strm, NB, J, A, dru, rc, rcr, tol, br, th, ms,
+                                   active);
+                TP_TRY(hipGetLastError());
+                int32_t h_active = 0;
+                TP_TRY(hipMemcpyAsync(&h_active, active, 4, hipMemcpyDeviceToHost, strm));
+                TP_TRY(hipStreamSynchronize(strm));
+                if (h_active == 0) { it++; break; }
+            }
+            st.iterations = std::max(st.iterations, it);
+        }
+        st.refine_ms += ms_since(t0);
+
+        // 5. output
+        hipLaunchKernelGGL(k_output, dim3((unsigned)((Sg * J + 255) / 256)), dim3(256), 0, strm, Sg * J, A, br, dout, dcnt, dbad);
+        TP_TRY(hipGetLastError());
+        TP_TRY(hipMemcpyAsync(arrivals + (size_t)s0 * J * A * 9, dout, NB * 9 * 8, hipMemcpyDeviceToHost, strm));
+        TP_TRY(hipMemcpyAsync(count + (size_t)s0 * J, dcnt, (size_t)Sg * J * 4, hipMemcpyDeviceToHost, strm));
+        TP_TRY(hipMemcpyAsync(nbad + (size_t)s0 * J, dbad, (size_t)Sg * J * 4, hipMemcpyDeviceToHost, strm));
+        TP_TRY(hipStreamSynchronize(strm));
+        st.groups++;
+    }
+    if (stats) *stats = st;
+    return RTMI_OK;
+}

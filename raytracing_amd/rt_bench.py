@@ -407,6 +407,21 @@ class Batch:
         check(lib().rtmi_isochrones(self._h, len(t), dptr(t), dptr(out)))
         return out
 
+    def crossings(self, line, kmax=4):
+        """Where each recorded ray crosses the line a x + b y = c (line = (a, b, c)): rtmi_crossings.  Returns a dict with
+        count [R] (crossings per ray, -1 when the trajectory reaches past the record) and u, x, y, T, theta, s [kmax, R]
+        (u the coordinate along the line, s the fractional step; NaN past count).  Needs record_stride 1."""
+        ln = np.ascontiguousarray(line, dtype=np.float64)
+        if ln.shape != (3,):
+            raise ValueError("line must be (a, b, c)")
+        count = np.empty(self.R, dtype=np.int32)
+        out = np.empty((int(kmax), 6, self.R))
+        check(lib().rtmi_crossings(self._h, dptr(ln), int(kmax), count.ctypes.data_as(_lib._ip), dptr(out)))
+        d = {"count": count}
+        for q, k in enumerate(CROSSING_FIELDS):
+            d[k] = out[:, q].copy()
+        return d
+
     def wavefronts(self, times, nfine=100):
         """The reference's wavefront extraction (RT_bench.py:1005-1044) on the device: one dict per traveltime with the
         points of the wavefront sorted by y -- 'y', 'x', 'angle' (ray angle), 'dxdy' (derivative of the PCHIP interpolant
@@ -558,6 +573,62 @@ class Shard:
             self.close()
         except Exception:
             pass
+
+
+CROSSING_FIELDS = ("u", "x", "y", "T", "theta", "s")                            # rtmi_crossings' out[kmax][6][R]
+ARRIVAL_FIELDS = ("theta0", "T", "u", "x", "y", "theta", "residual", "iterations", "status")   # rtmi_two_point's arrivals[..][9]
+
+
+def two_point(selected_func, field, sources, line, receivers_u, *, thetas, step, max_size, box, gamma=1, reference_order=False,
+              retrace=True, tol=1e-10, max_arrivals=4, max_crossings=4, max_iter=60, mem_budget=0, gamma_step=None,
+              launch_mode="auto", field_path=0, stats=False):
+    """Rays from each source to each receiver on the line a x + b y = c (line = (a, b, c)), all on the device
+    (rtmi_two_point): a fan of launch angles `thetas` per source, brackets between adjacent fan rays, Illinois regula falsi on
+    the launch angle.  sources: (S, 2) array of (x, y); receivers_u: [J] coordinates along the line (u = a' y - b' x with
+    (a', b') the unit normal), strictly increasing.  Returns a dict of [S, J, A] arrays -- theta0 (launch angle), T, u, x, y,
+    theta (angle at the receiver), residual (u - u_j), iterations, status (rtmi_arrival_status) -- with the converged
+    arrivals first, sorted by T; count [S, J] (converged arrivals) and nbad [S, J] (stalled or truncated brackets); with
+    stats=True also 'stats' (iterations, groups, rec_rows, overflow, fan_ms, bracket_ms, refine_ms)."""
+    src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
+    sx = np.ascontiguousarray(src[:, 0]); sy = np.ascontiguousarray(src[:, 1])
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    ru = np.ascontiguousarray(receivers_u, dtype=np.float64)
+    ln = np.ascontiguousarray(line, dtype=np.float64)
+    if ln.shape != (3,):
+        raise ValueError("line must be (a, b, c)")
+    S, M, J, A = len(sx), len(th), len(ru), int(max_arrivals)
+    p = Params()
+    p.method = _method_id(selected_func); p.dtype = field.dtype
+    p.gamma = float(gamma); p.gamma_step = float(gamma if gamma_step is None else gamma_step)
+    p.step = float(step); p.max_size = int(max_size)
+    for i in range(4):
+        p.box[i] = float(box[i])
+    p.launch_mode = LAUNCH_MODES[launch_mode] if isinstance(launch_mode, str) else int(launch_mode)
+    p.field_path = int(field_path)
+    p.reference_order = ORDERS[reference_order] if isinstance(reference_order, str) else int(reference_order)
+    p.no_retrace = int(not retrace)
+    tp = _lib.TwoPointParams()
+    tp.max_arrivals = A; tp.max_crossings = int(max_crossings); tp.max_iter = int(max_iter); tp.tol = float(tol)
+    tp.mem_budget = int(mem_budget)
+    count = np.empty((S, J), dtype=np.int32); nbad = np.empty((S, J), dtype=np.int32)
+    arr = np.empty((S, J, A, len(ARRIVAL_FIELDS)))
+    st = _lib.TwoPointStats()
+    check(lib().rtmi_two_point(field._h, C.byref(p), S, dptr(sx), dptr(sy), M, dptr(th), dptr(ln), J, dptr(ru), C.byref(tp),
+                               count.ctypes.data_as(_lib._ip), nbad.ctypes.data_as(_lib._ip), dptr(arr), C.byref(st)))
+    out = {k: arr[..., q].copy() for q, k in enumerate(ARRIVAL_FIELDS)}
+    out["iterations"] = np.nan_to_num(out["iterations"], nan=0.0).astype(np.int32)      # empty slots: 0
+    out["status"] = out["status"].astype(np.int32)
+    out["count"] = count
+    out["nbad"] = nbad
+    if stats:
+        out["stats"] = {k: getattr(st, k) for k, _ in _lib.TwoPointStats._fields_ if k != "reserved"}
+    return out
+
+
+def first_arrivals(selected_func, field, sources, line, receivers_u, **kw):
+    """The [S, J] table of first-arrival traveltimes (NaN where no ray converged): two_point's smallest T."""
+    r = two_point(selected_func, field, sources, line, receivers_u, **kw)
+    return np.where(r["count"] > 0, r["T"][..., 0], np.nan)
 
 
 def device_sincos(x):
