@@ -330,6 +330,47 @@ int rtmi_two_point(const rtmi_field *f, const rtmi_params *p, int32_t S, const d
                    const double *thetas, const double line[3], int32_t J, const double *receivers_u, const rtmi_two_point_params *tp,
                    int32_t *count, int32_t *nbad, double *arrivals, rtmi_two_point_stats *stats);
 
+/* Dynamic (paraxial) ray tracing along recorded rays: the geometrical spreading, the caustic index and the amplitude of every
+ * ray, at its end and at its crossings of a receiver line.  The reference builds a Hessian of n and never reads it
+ * (RT_bench.py:459-462); this is what it would be for.  DESIGN.md section 10.
+ * Arclength s, ray tangent t = (cos theta, sin theta), normal e = (-sin theta, cos theta), n_e = grad n . e,
+ * n_ee = e^T (dg/dx) e with g the gradient the step methods read.  Cerveny's paraxial system dQ/dT = v^2 P, dP/dT = -V_nn Q / v
+ * (v = 1/n) in s:
+ *     dQ/ds = P / n,    dP/ds = K Q,    K = n_ee - 2 n_e^2 / n,
+ * carried for two solutions from row 0: the plane wave (Q1, P1) = (1, 0) and the point source (Q2, P2) = (0, 1).
+ *   J    = n0 Q2 = dq/dtheta0, the perpendicular spread of the ray tube per radian of launch angle (n0: n at the source)
+ *   G    = (n_r |J|)^(-1/2), the spreading factor (n_r: n at the receiver)
+ *   kmah = the number of sign changes of Q2 so far (caustics passed)
+ * The 2-D Helmholtz equation (Laplacian + omega^2 n^2) u = -delta(x - x0) has the ray solution
+ *     u = A exp(i (omega T - kmah pi/2 + pi/4)),    A = G / sqrt(8 pi omega)
+ * (convention exp(-i omega t), outgoing exp(+i omega T); from div(A^2 grad T) = 0, matched to (i/4) H0^(1)(omega n0 r) at the
+ * source): each caustic retards the phase by pi/2.
+ * Field quantities come from the cell polynomials the fast-form step methods evaluate (rtmi_debug_field_lookup): n from the
+ * bilinear part, g and its Jacobian from the two bicubic gradient fits differentiated (rtmi_field_eval_dgrad); a flat cell gives
+ * K = 0.  The reference's Hessian fits (second differences of the samples) are not used: on the interface scenario they differ
+ * from the derivative of the gradient fits by half the scale.
+ * Per step of chord length L between rows i-1 and i: kick-drift-kick (Stormer-Verlet), P += L/2 K_{i-1} Q, Q += L mean(1/n) P,
+ * P += L/2 K_i Q -- three shears, so Q1 P2 - Q2 P1 = 1 to rounding; second order, like op6.  A crossing of the line (the rule and
+ * tau* of rtmi_crossings) is a partial step of length tau* L with K and 1/n interpolated linearly along the step; its n_r is that
+ * interpolated n.  fp64 arithmetic; fp32 records are widened.  One lane per ray reads x, y and theta of every row and looks the
+ * field up once per row (wave-uniform cells through the scalar cache).
+ *   line      NULL: the end of each ray only; else a x + b y = c as rtmi_crossings
+ *   count[R]  crossings per ray, exactly rtmi_crossings' (may be NULL without a line: then 0, and -1 for a ray whose trajectory
+ *             runs past rec_rows)
+ *   at_line   [kmax][7][R]: Q1 P1 Q2 P2 J G kmah at the first kmax crossings, in rtmi_crossings' order; NaN past count
+ *   at_end    [7][R]: the same at each ray's last row (NaN for a ray that runs past rec_rows)
+ * Host buffers, fp64, the caller's ray order; rays handed over to the re-trace of critical rays are drained first.
+ * RTMI_ERR_ARG: record_stride != 1; op10 / op11 or gamma != 1 (anisotropic dynamic ray tracing is another system).
+ * RTMI_ERR_STATE: a batch to which rtmi_batch_set_state / rtmi_batch_restore_state gave any ray a row other than 0 (istep NULL
+ * counts as such once the batch has stepped) since its create / reset: its rows before that row are not a trajectory from the
+ * source, and integration starts at row 0.  The calling thread's current device must be the batch's. */
+int rtmi_paraxial(rtmi_batch *b, const double line[3], int32_t kmax, int32_t *count, double *at_line, double *at_end);
+/* The Jacobian of the gradient as rtmi_paraxial evaluates it: the derivatives of the cell polynomials of the two gradient fits
+ * at npts host points (d/dx = inv_hx d/du; outside the grid, FITPACK's argument clamp as in the lookup) -> d(dn/dx)/dx,
+ * d(dn/dx)/dy, d(dn/dy)/dx, d(dn/dy)/dy (host, fp64). */
+int rtmi_field_eval_dgrad(const rtmi_field *f, int64_t npts, const double *x, const double *y, double *gx_x, double *gx_y,
+                          double *gy_x, double *gy_y);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

@@ -104,6 +104,8 @@ SYMBOLS = {
     "rtmi_crossings": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, _dp]),
     "rtmi_two_point": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp,
                                  C.POINTER(TwoPointParams), _ip, _ip, _dp, C.POINTER(TwoPointStats)]),
+    "rtmi_paraxial": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, _dp, _dp]),
+    "rtmi_field_eval_dgrad": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 6),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

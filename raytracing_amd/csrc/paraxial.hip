@@ -1,0 +1,343 @@
+// paraxial.hip -- dynamic (paraxial) ray tracing along recorded rays (rtmi_paraxial): geometrical spreading, the caustic
+// index and the ray amplitude of every ray, at the end of the ray and at its crossings of a receiver line; and the
+// derivatives of the two gradient fits the kernel evaluates them with (rtmi_field_eval_dgrad).  DESIGN.md section 10.
+//
+// A post-pass over a batch's record, like k_crossings: one lane per ray walks its rows 0 .. last, reads x, y and theta of
+// every row and looks the field up once per row (a step's end lookup is the next step's start lookup).  The lookup is the
+// fast-form step methods' own cell polynomial (rt_polytab.h), differentiated: n from the bilinear part, g and its Jacobian
+// from the two bicubics.  A wave whose lanes share one cell reads the cell's 36 coefficients through the scalar cache, as
+// rt::PolyGather does; otherwise every lane reads its own.  Arithmetic is fp64 in one fixed order (-ffp-contract=off, sin/cos
+// glibc's own through rt_libm.h) so that tests/paraxial_ref.py, a numpy restatement, follows it operation for operation.
+// Batches are read through the public rtmi_batch_view; the field and the batch's parameters through two internal hooks.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/rtmi.h"
+#include "rt_crossing.h"
+#include "rtmi_internal.h"
+
+#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
+#define PX_TRY(expr)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+#define PX_ARG(cond, msg)                                                    \
+    do {                                                                     \
+        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
+    } while (0)
+#define PX_RC(expr)                  \
+    do {                             \
+        const int rc_ = (expr);      \
+        if (rc_) return rc_;         \
+    } while (0)
+
+namespace {
+
+constexpr int kCols = 7;        // Q1 P1 Q2 P2 J G kmah
+constexpr int kStride = 40;     // rt::kPolyStride: numbers per cell of the table
+
+// rtmi_internal_poly with the table typed (T: the field's dtype)
+template <typename T> struct PolyF {
+    const T* poly;
+    long flat;
+    int ncx, ncy;
+    double ax, bx, inv_hx, ay, by, inv_hy;
+};
+
+// n, g = (dn/dx, dn/dy) and the Jacobian of g: gxy = d(dn/dx)/dy and so on
+struct NG2 { double n, gx, gy, gxx, gxy, gyx, gyy; };
+struct CellPos { int cell; double u, v; };
+
+// rt::poly_locate in fp64: u = (x - a) inv_h - j with the product taken exactly; FITPACK's argument clamp outside the grid
+__device__ __forceinline__ void axis_clamped(double x, double a, double b, double inv_h, int ncell, double& xa, double& jf) {
+    x = x < a ? a : x;
+    x = x > b ? b : x;
+    xa = x - a;
+    jf = floor(xa * inv_h);
+    jf = jf < 0.0 ? 0.0 : (jf > (double)(ncell - 1) ? (double)(ncell - 1) : jf);
+}
+template <typename T> __device__ __forceinline__ CellPos locate(const PolyF<T>& F, double x, double y) {
+    double xa = x - F.ax, ya = y - F.ay;
+    double jfx = floor(xa * F.inv_hx), jfy = floor(ya * F.inv_hy);
+    int jx = (int)jfx, jy = (int)jfy;
+    if ((unsigned)jx >= (unsigned)F.ncx) { axis_clamped(x, F.ax, F.bx, F.inv_hx, F.ncx, xa, jfx); jx = (int)jfx; }
+    if ((unsigned)jy >= (unsigned)F.ncy) { axis_clamped(y, F.ay, F.by, F.inv_hy, F.ncy, ya, jfy); jy = (int)jfy; }
+    CellPos c;
+    c.u = __builtin_fma(xa, F.inv_hx, -jfx);
+    c.v = __builtin_fma(ya, F.inv_hy, -jfy);
+    c.cell = jy * F.ncx + jx;
+    return c;
+}
+
+// The flat-cell map (rt::FieldDev::flat, rt_polytab.h): a flat cell's entry is its constant n, an ordinary cell's a NaN pattern
+template <typename T> __device__ __forceinline__ bool flat_cell(const PolyF<T>& F, int cell, double& c) {
+    if (!F.flat) return false;
+    if constexpr (sizeof(T) == 8) {
+        const unsigned long long b = reinterpret_cast<const unsigned long long*>(F.poly)[(long)cell - F.flat];
+        if ((unsigned)(b >> 32) == 0xffffffffu) return false;
+        c = __builtin_bit_cast(double, b);
+    } else {
+        const unsigned b = reinterpret_cast<const unsigned*>(F.poly)[(long)cell - F.flat];
+        if (b == 0xffffffffu) return false;
+        c = (double)__builtin_bit_cast(float, b);
+    }
+    return true;
+}
+
+// One cell's polynomials and their derivatives at (u, v).  ROW(k) yields row k's four coefficients (powers 0..3 of u) as fp64:
+// rows 0-3 the d/dx spline (k the power of v), 4-7 the d/dy spline, 8 n's bilinear b0 + b1 u + b2 v + b3 u v.  Value and
+// Horner order as rt::poly_bicubic / poly_bilinear (the same bits as the step kernels' lookup); d/du and d/dv by Horner too.
+template <typename ROW> __device__ __forceinline__ NG2 eval_cell(ROW row, double u, double v, double ihx, double ihy) {
+    double g[2], gu[2], gv[2];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        double r[4], dr[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double4 a = row(4 * s + k);
+            r[k] = __builtin_fma(__builtin_fma(__builtin_fma(a.w, u, a.z), u, a.y), u, a.x);
+            dr[k] = __builtin_fma(__builtin_fma(3.0 * a.w, u, 2.0 * a.z), u, a.y);
+        }
+        g[s] = __builtin_fma(__builtin_fma(__builtin_fma(r[3], v, r[2]), v, r[1]), v, r[0]);
+        gu[s] = __builtin_fma(__builtin_fma(__builtin_fma(dr[3], v, dr[2]), v, dr[1]), v, dr[0]);
+        gv[s] = __builtin_fma(__builtin_fma(3.0 * r[3], v, 2.0 * r[2]), v, r[1]);
+    }
+    const double4 b = row(8);
+    NG2 o;
+    o.n = __builtin_fma(__builtin_fma(b.w, u, b.z), v, __builtin_fma(b.y, u, b.x));
+    o.gx = g[0]; o.gy = g[1];
+    o.gxx = gu[0] * ihx; o.gxy = gv[0] * ihy;
+    o.gyx = gu[1] * ihx; o.gyy = gv[1] * ihy;
+    return o;
+}
+
+template <typename T> using Quad = T __attribute__((ext_vector_type(4)));
+template <typename T> __device__ __forceinline__ double4 widen(Quad<T> q) { return double4{(double)q.x, (double)q.y, (double)q.z, (double)q.w}; }
+
+// The lookup at (x, y) of every lane that is executing.  Wave-uniform cell (the common case: neighbouring rays of a fan): the
+// map entry and the 36 coefficients through the scalar cache; otherwise per-lane vector loads.  Same numbers, same arithmetic.
+template <typename T> __device__ __forceinline__ NG2 lookup(const PolyF<T>& F, double x, double y) {
+    const CellPos c = locate(F, x, y);
+    double cf;
+    const int cu = __builtin_amdgcn_readfirstlane(c.cell);
+    if (__builtin_amdgcn_ballot_w64(c.cell != cu) == 0ull) {
+        if (flat_cell(F, cu, cf)) return NG2{cf, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        typedef const Quad<T> __attribute__((address_space(4)))* SP;
+        SP p = (SP)(F.poly + (size_t)cu * kStride);
+        asm volatile("" : "+s"(p));
+        return eval_cell([&](int k) { return widen<T>(p[k]); }, c.u, c.v, F.inv_hx, F.inv_hy);
+    }
+    if (flat_cell(F, c.cell, cf)) return NG2{cf, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const Quad<T>* p = reinterpret_cast<const Quad<T>*>(F.poly + (size_t)c.cell * kStride);
+    return eval_cell([&](int k) { return widen<T>(p[k]); }, c.u, c.v, F.inv_hx, F.inv_hy);
+}
+
+// K = n_ee - 2 n_e^2 / n for the ray normal e = (-sin theta, cos theta): dP/ds = K Q
+__device__ __forceinline__ double kappa(const NG2& f, double c, double s) {
+    const double ex = -s, ey = c;
+    const double ne = f.gx * ex + f.gy * ey;
+    const double nee = ex * (f.gxx * ex + f.gxy * ey) + ey * (f.gyx * ex + f.gyy * ey);
+    return nee - 2.0 * ne * ne / f.n;
+}
+
+// The plane-wave (Q1, P1) and point-source (Q2, P2) solutions of dQ/ds = P / n, dP/ds = K Q
+struct Tube { double q1, p1, q2, p2; };
+// One step of length h, kick-drift-kick (Stormer-Verlet): ka, kb = K at its ends, wm = the mean of 1/n at its ends.  Each of
+// the three updates is a shear, so the step's matrix has determinant 1 and Q1 P2 - Q2 P1 stays 1 to rounding.
+__device__ __forceinline__ void kdk(Tube& t, double h, double ka, double kb, double wm) {
+    const double a = 0.5 * h * ka, d = h * wm, b = 0.5 * h * kb;
+    t.p1 = t.p1 + a * t.q1; t.p2 = t.p2 + a * t.q2;
+    t.q1 = t.q1 + d * t.p1; t.q2 = t.q2 + d * t.p2;
+    t.p1 = t.p1 + b * t.q1; t.p2 = t.p2 + b * t.q2;
+}
+// a caustic: Q2 changes sign (a row exactly at Q2 = 0 counts once, on the way in)
+__device__ __forceinline__ int sign_change(double a, double b) { return ((a > 0.0 && b <= 0.0) || (a < 0.0 && b >= 0.0)) ? 1 : 0; }
+
+// the 7 columns of one answer: Q1 P1 Q2 P2, J = n0 Q2, G = (n_r |J|)^-1/2, kmah
+__device__ __forceinline__ void put(double* out, long R, long o, const Tube& t, double n0, double nr, int kmah) {
+    const double J = n0 * t.q2;
+    const double v[kCols] = {t.q1, t.p1, t.q2, t.p2, J, 1.0 / sqrt(nr * fabs(J)), (double)kmah};
+#pragma unroll
+    for (int q = 0; q < kCols; q++) out[(size_t)q * R + o] = v[q];
+}
+__device__ __forceinline__ void put_nan(double* out, long R, long o) {
+#pragma unroll
+    for (int q = 0; q < kCols; q++) out[(size_t)q * R + o] = NAN;
+}
+
+struct ParaxArgs {
+    const void* s_ray;          // [rec_rows][6][R] of the batch's dtype
+    const int32_t* istep;       // [R] last written row
+    const int32_t* perm;        // [R] or NULL: slot k holds the caller's ray perm[k]
+    long R, rec_rows;
+    Line L;
+    int has_line, kmax;
+    int32_t* count;             // [R] or NULL
+    double* at_line;            // [kmax][7][R] (has_line)
+    double* at_end;             // [7][R]
+};
+
+// One lane per ray (slot k); answers in the caller's order.  A crossing of the line (the rule and tau* of rtmi_crossings) gets
+// a partial step of length tau* L with K and 1/n interpolated linearly in tau along the step.
+template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= A.R) return;
+    const long R = A.R;
+    const long o = A.perm ? (long)A.perm[k] : k;
+    const size_t P = (size_t)6 * R;
+    const T* col = reinterpret_cast<const T*>(A.s_ray) + k;
+    const long last = A.istep[k];
+    const Line L = A.L;
+    int n = 0;
+    if (last >= A.rec_rows) {
+        n = -1;
+        put_nan(A.at_end, R, o);
+    } else {
+        double x0 = (double)col[0], y0 = (double)col[R];
+        const double th0 = (double)col[5 * R];
+        double c0 = cos_g(th0), s0 = sin_g(th0);
+        NG2 f = lookup(F, x0, y0);
+        const double nsrc = f.n;
+        double k0 = kappa(f, c0, s0), w0 = 1.0 / f.n, nl = f.n;
+        double f0 = (L.a * x0 + L.b * y0) - L.c;
+        Tube t{1.0, 0.0, 0.0, 1.0};
+        int kmah = 0;
+        // the next row's three loads go out a step ahead
+        double xn = 0.0, yn = 0.0, tn = 0.0;
+        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; tn = (double)col[P + 5 * R]; }
+        for (long i = 1; i <= last; i++) {
+            const double x1 = xn, y1 = yn, th1 = tn;
+            if (i < last) {
+                const T* r = col + (size_t)(i + 1) * P;
+                xn = (double)r[0]; yn = (double)r[R]; tn = (double)r[5 * R];
+            }
+            const double c1 = cos_g(th1), s1 = sin_g(th1);
+            f = lookup(F, x1, y1);
+            const double k1 = kappa(f, c1, s1), w1 = 1.0 / f.n;
+            const double dx = x1 - x0, dy = y1 - y0;
+            const double len = sqrt(dx * dx + dy * dy);
+            if (A.has_line) {
+                const double f1 = (L.a * x1 + L.b * y1) - L.c;
+                if (crosses(f0, f1)) {
+                    if (n < A.kmax) {
+                        const double d0 = len * (L.a * c0 + L.b * s0), d1 = len * (L.a * c1 + L.b * s1);
+                        const double tau = cross_tau(f0, d0, f1, d1);
+                        const double kt = k0 + tau * (k1 - k0), wt = w0 + tau * (w1 - w0);
+                        Tube u = t;
+                        kdk(u, tau * len, k0, kt, 0.5 * (w0 + wt));
+                        put(A.at_line + (size_t)n * kCols * R, R, o, u, nsrc, 1.0 / wt, kmah + sign_change(t.q2, u.q2));
+                    }
+                    n++;
+                }
+                f0 = f1;
+            }
+            const double q2 = t.q2;
+            kdk(t, len, k0, k1, 0.5 * (w0 + w1));
+            kmah += sign_change(q2, t.q2);
+            x0 = x1; y0 = y1; c0 = c1; s0 = s1; k0 = k1; w0 = w1; nl = f.n;
+        }
+        put(A.at_end, R, o, t, nsrc, nl, kmah);
+    }
+    if (A.count) A.count[o] = n;
+    if (A.has_line)
+        for (int c = n < 0 ? 0 : n; c < A.kmax; c++) put_nan(A.at_line + (size_t)c * kCols * R, R, o);
+}
+
+template <typename T> __global__ void k_field_dgrad(PolyF<T> F, long npts, const double* x, const double* y, double* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    const NG2 f = lookup(F, x[i], y[i]);
+    out[i] = f.gxx;
+    out[npts + i] = f.gxy;
+    out[2 * npts + i] = f.gyx;
+    out[3 * npts + i] = f.gyy;
+}
+
+template <typename T> PolyF<T> poly_f(const rtmi_internal_poly& v) {
+    return PolyF<T>{(const T*)v.poly, v.flat, v.ncx, v.ncy, v.ax, v.bx, v.inv_hx, v.ay, v.by, v.inv_hy};
+}
+
+// device allocations of one call, freed on every way out
+struct DevMem {
+    std::vector<void*> p;
+    template <typename T> hipError_t get(T** out, size_t bytes) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
+        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
+        return e;
+    }
+    ~DevMem() { for (void* v : p) (void)hipFree(v); }
+};
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax, int32_t* count, double* at_line, double* at_end) {
+    const char* who = "rtmi_paraxial";
+    PX_ARG(b && at_end, "rtmi_paraxial: null");
+    Line L{0.0, 0.0, 0.0};
+    if (line) {
+        PX_ARG(count && at_line, "rtmi_paraxial: a line needs count and at_line");
+        PX_ARG(kmax >= 1, "rtmi_paraxial: kmax must be >= 1");
+        PX_ARG(make_line(line, &L), "rtmi_paraxial: the line needs (a, b) != (0, 0) and finite coefficients");
+    }
+    const rtmi_field* f = nullptr;
+    rtmi_params p{};
+    int from_state = 0;
+    PX_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
+    PX_ARG(p.record_stride == 1, "rtmi_paraxial: needs the full trajectory (record_stride 1)");
+    PX_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
+           "rtmi_paraxial: isotropic media only (op1..op9, gamma 1): anisotropic dynamic ray tracing is another system");
+    if (from_state)
+        return rtmi_internal_fail(RTMI_ERR_STATE, "rtmi_paraxial: rtmi_batch_set_state gave rays a row other than 0: their rows "
+                                                  "before it are not a trajectory from the source (reset the batch)");
+    rtmi_internal_poly pv;
+    PX_RC(rtmi_internal_field_poly(f, &pv));
+    rtmi_device_view v;
+    PX_RC(rtmi_batch_view(b, &v));          // drains the rays handed over to the re-trace of critical rays
+    PX_RC(rtmi_sync(b));
+    const size_t R = (size_t)v.R;
+    const int K = line ? kmax : 0;
+    DevMem mem;
+    int32_t* dc = nullptr;
+    double *dl = nullptr, *de = nullptr;
+    PX_TRY(mem.get(&dc, R * sizeof(int32_t)));
+    PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
+    if (K) PX_TRY(mem.get(&dl, (size_t)K * kCols * R * sizeof(double)));
+    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L, line ? 1 : 0, K, dc, dl, de};
+    const dim3 g((unsigned)((R + 255) / 256)), blk(256);
+    if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
+    else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
+    PX_TRY(hipGetLastError());
+    PX_TRY(hipMemcpy(at_end, de, (size_t)kCols * R * sizeof(double), hipMemcpyDeviceToHost));
+    if (count) PX_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (K) PX_TRY(hipMemcpy(at_line, dl, (size_t)K * kCols * R * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_field_eval_dgrad(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* gx_x,
+                                      double* gx_y, double* gy_x, double* gy_y) {
+    const char* who = "rtmi_field_eval_dgrad";
+    PX_ARG(f && x && y && gx_x && gx_y && gy_x && gy_y, "rtmi_field_eval_dgrad: null");
+    PX_ARG(npts >= 0, "rtmi_field_eval_dgrad: npts < 0");
+    rtmi_internal_poly pv;
+    PX_RC(rtmi_internal_field_poly(f, &pv));
+    if (npts == 0) return RTMI_OK;
+    const size_t nb = (size_t)npts * sizeof(double);
+    DevMem mem;
+    double* d = nullptr;
+    PX_TRY(mem.get(&d, 6 * nb));
+    PX_TRY(hipMemcpy(d, x, nb, hipMemcpyHostToDevice));
+    PX_TRY(hipMemcpy(d + npts, y, nb, hipMemcpyHostToDevice));
+    const dim3 g((unsigned)((npts + 255) / 256)), blk(256);
+    if (pv.dtype == RTMI_F64) hipLaunchKernelGGL(k_field_dgrad<double>, g, blk, 0, nullptr, poly_f<double>(pv), (long)npts, d, d + npts, d + 2 * npts);
+    else hipLaunchKernelGGL(k_field_dgrad<float>, g, blk, 0, nullptr, poly_f<float>(pv), (long)npts, d, d + npts, d + 2 * npts);
+    PX_TRY(hipGetLastError());
+    double* outs[4] = {gx_x, gx_y, gy_x, gy_y};
+    for (int q = 0; q < 4; q++) PX_TRY(hipMemcpy(outs[q], d + (2 + q) * npts, nb, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}

@@ -735,6 +735,19 @@ static int field_eval_impl(const rtmi_field* f, int64_t npts, const double* x, c
     if (rc) return fail(rc, std::string(who) + ": HIP failure");
     return RTMI_OK;
 }
+template <typename T> static void poly_view(const rtmi_field* f, rtmi_internal_poly* out) {
+    const rt::FieldDev<T> F = field_dev<T>(f, 0);
+    out->poly = F.poly; out->flat = F.flat; out->dtype = f->dtype; out->ncx = F.ncx; out->ncy = F.qy - 1;
+    out->ax = (double)F.ax; out->bx = (double)F.bx; out->inv_hx = (double)F.inv_hx;
+    out->ay = (double)F.ay; out->by = (double)F.by; out->inv_hy = (double)F.inv_hy;
+}
+int rtmi_internal_field_poly(const rtmi_field* f, rtmi_internal_poly* out) {
+    ARG_TRY(f && out, "rtmi_internal_field_poly: null");
+    DEVICE_TRY(f, "rtmi_internal_field_poly");
+    if (f->dtype == RTMI_F64) poly_view<double>(f, out);
+    else poly_view<float>(f, out);
+    return RTMI_OK;
+}
 RTMI_EXPORT int rtmi_field_eval(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* n,
                                 double* gx, double* gy) {
     return field_eval_impl(f, npts, x, y, n, gx, gy, false, "rtmi_field_eval");
@@ -1480,6 +1493,7 @@ struct rtmi_batch {
     unsigned long long* sliced_ctl = nullptr;   // launch_mode 2: head, pushed, finished, stalled, queue entries (k_advance_sliced)
     bool dirty = false;          // rows may hold data a re-run will not overwrite (set_state / set_per_ray since the last clear)
     bool dirty_state = false;    // rtmi_batch_set_state ran since create / reset
+    bool state_rows = false;     // ... and gave some ray a row other than 0 (rtmi_internal_batch_info: rtmi_paraxial refuses the batch)
     // RTMI_LAUNCH_AUTO: kernel time of the last complete run from the launch conditions under each schedule
     // ([0] sliced, [1] plain; < 0: not measured yet), and what the last rtmi_run used
     double auto_ms[2][RTMI_AUTO_SAMPLES] = {{0, 0, 0}, {0, 0, 0}};
@@ -1820,6 +1834,7 @@ static int batch_init_state(rtmi_batch* b, bool clear_traj) {
     // the events of the pass before stay on the list (they are folded into total_kernel_ms at the next stats call or when the
     // list is full): a caller timing many passes reads the kernel time of all of them without a host sync per pass
     b->kernel_ms = 0; b->launches = 0; b->pass_ev_start = b->ev_used; b->dirty_state = false;
+    b->state_rows = false;
     return RTMI_OK;
 }
 
@@ -2041,6 +2056,14 @@ RTMI_EXPORT int rtmi_batch_reset(rtmi_batch* b) {
     return batch_init_state(b, b->dirty || !b->p.lazy_clear);
 }
 
+int rtmi_internal_batch_info(rtmi_batch* b, const rtmi_field** f, rtmi_params* p, int* rows_from_state) {
+    ARG_TRY(b && f && p && rows_from_state, "rtmi_internal_batch_info: null");
+    *f = b->field;
+    *p = b->p;
+    *rows_from_state = b->state_rows ? 1 : 0;
+    return RTMI_OK;
+}
+
 // New launch angles (and optionally per-ray max_size) from device memory, then a reset.  The angles replace the batch's stored
 // launch conditions, so that the re-trace of critical rays (which restarts from b->launch) follows them.  Host code only: plain
 // device-to-device copies, which is why a sorted batch (perm) is refused.
@@ -2149,6 +2172,8 @@ static int set_state_impl(rtmi_batch* b, const double* state9, const double* his
     }
     b->dirty = true;
     b->dirty_state = true;
+    // istep NULL keeps each ray's row: the rows it has stepped to, unless nothing has run since create / reset
+    b->state_rows = istep ? std::any_of(istep, istep + R, [](int32_t i) { return i != 0; }) : (b->state_rows || b->launches != 0);
     void* stg = nullptr;
     int rc = batch_staging(b, 13 * R * sizeof(double) + R * sizeof(int) + R, &stg);
     if (rc) return rc;

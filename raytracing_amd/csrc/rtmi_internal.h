@@ -18,3 +18,16 @@ int rtmi_internal_pack_device(rtmi_batch* b, int what, double* dst, void* stream
 // (DEVICE, may be NULL) sets per-ray max_size as rtmi_batch_set_per_ray does, with the batch's own DELTA_S; values below 2 are
 // allowed here (1: the ray takes no step).  Not on a batch with sort_rays (RTMI_ERR_STATE).  For twopoint.hip's refinement.
 int rtmi_internal_relaunch(rtmi_batch* b, const double* theta0, const int32_t* max_size);
+// The field's per-cell polynomial table (rt_polytab.h) as the fast-form step kernels see it (rt::FieldDev), widened to fp64: for
+// paraxial.hip, which evaluates the same polynomials and their derivatives.  flat: 0, or the distance (in elements) from the
+// flat-cell map to poly (rt::FieldDev::flat).  The calling thread's current device must be the field's (RTMI_ERR_ARG).
+struct rtmi_internal_poly {
+    const void* poly;
+    long flat;
+    int dtype, ncx, ncy;
+    double ax, bx, inv_hx, ay, by, inv_hy;
+};
+int rtmi_internal_field_poly(const rtmi_field* f, rtmi_internal_poly* out);
+// A batch's field and parameters; *rows_from_state = 1 when rtmi_batch_set_state / restore_state gave any ray a state at a row
+// other than 0 since the last create / reset (its rows before that row are not a trajectory from its launch point).
+int rtmi_internal_batch_info(rtmi_batch* b, const rtmi_field** f, rtmi_params* p, int* rows_from_state);

@@ -2,8 +2,8 @@
 // receivers on a line (rtmi_two_point): the shooting method of the reference's paper setting, in its two-point form.
 // Batches are read through the public rtmi_batch_view; the only hook into rtmi.hip is rtmi_internal_relaunch.
 //
-// The crossing arithmetic is written in one fixed order (compiled with -ffp-contract=off, sin/cos glibc's own through
-// rt_libm.h) so that tests/crossing_ref.py, a numpy restatement, gives the same bits; the receiver angle goes through the
+// The crossing arithmetic (rt_crossing.h) is written in one fixed order (compiled with -ffp-contract=off, sin/cos glibc's own
+// through rt_libm.h) so that tests/crossing_ref.py, a numpy restatement, gives the same bits; the receiver angle goes through the
 // device's atan2 (within an ulp of numpy's).  DESIGN.md section 9 describes the rules.
 #include <hip/hip_runtime.h>
 
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../../include/rtmi.h"
-#include "rt_libm.h"
+#include "rt_crossing.h"
 #include "rtmi_internal.h"
 
 #define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
@@ -35,33 +35,6 @@
     } while (0)
 
 namespace {
-
-__device__ const double kTab[4 * RT_SINCOS_TAB_ENTRIES] = {RT_SINCOS_TAB_VALUES};
-__device__ __forceinline__ double sin_g(double x) { return rt::gl::in_range(x) ? rt::gl::sin(kTab, x) : sin(x); }
-__device__ __forceinline__ double cos_g(double x) { return rt::gl::in_range(x) ? rt::gl::cos(kTab, x) : cos(x); }
-
-// The normalised line a' x + b' y = c' (host, fp64).  tests/crossing_ref.py normalises the same way.
-struct Line { double a, b, c; };
-static bool make_line(const double* l, Line* out) {
-    const double nrm = std::sqrt(l[0] * l[0] + l[1] * l[1]);
-    if (!(nrm > 0) || !std::isfinite(nrm) || !std::isfinite(l[2])) return false;
-    *out = Line{l[0] / nrm, l[1] / nrm, l[2] / nrm};
-    return true;
-}
-
-// The cubic Hermite basis at tau, and its derivative
-struct Basis { double h00, h10, h01, h11; };
-__device__ __forceinline__ Basis basis(double t) {
-    const double t2 = t * t, t3 = t2 * t;
-    return Basis{(2.0 * t3 - 3.0 * t2) + 1.0, (t3 - 2.0 * t2) + t, 3.0 * t2 - 2.0 * t3, t3 - t2};
-}
-__device__ __forceinline__ Basis dbasis(double t) {
-    const double t2 = t * t;
-    return Basis{6.0 * t2 - 6.0 * t, (3.0 * t2 - 4.0 * t) + 1.0, 6.0 * t - 6.0 * t2, 3.0 * t2 - 2.0 * t};
-}
-__device__ __forceinline__ double herm(const Basis& h, double p0, double m0, double p1, double m1) {
-    return ((p0 * h.h00 + m0 * h.h10) + p1 * h.h01) + m1 * h.h11;
-}
 
 // One lane per ray (slot k), looping over its rows [row][6][R].  x and y are read on every row; the other columns only on a
 // step that crosses.  count[o] = crossings (-1: the trajectory reaches past rec_rows), out[kmax][6][R] = u x y T theta s.
@@ -83,7 +56,7 @@ __global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t*
         for (long i = 1; i <= last; i++) {
             const double x1 = (double)col[(size_t)i * P], y1 = (double)col[(size_t)i * P + R];
             const double f1 = (L.a * x1 + L.b * y1) - L.c;
-            if ((f0 < 0.0 && f1 >= 0.0) || (f0 > 0.0 && f1 <= 0.0)) {
+            if (crosses(f0, f1)) {
                 if (n < kmax) {
                     const T* r0 = col + (size_t)(i - 1) * P;
                     const T* r1 = col + (size_t)i * P;
@@ -93,18 +66,7 @@ __global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t*
                     const double len = sqrt(dx * dx + dy * dy);
                     const double tx0 = len * c0, ty0 = len * s0, tx1 = len * c1, ty1 = len * s1;
                     const double d0 = len * (L.a * c0 + L.b * s0), d1 = len * (L.a * c1 + L.b * s1);
-                    // bracketed Newton on g(tau) = a' H_x + b' H_y - c', from the linear-interpolation tau
-                    double tau = f1 == 0.0 ? 1.0 : f0 / (f0 - f1);
-                    double lo = 0.0, hi = 1.0;
-                    for (int it = 0; it < 64 && f1 != 0.0; it++) {
-                        const double g = herm(basis(tau), f0, d0, f1, d1);
-                        if (g == 0.0) break;
-                        if ((g < 0.0) == (f0 < 0.0)) lo = tau; else hi = tau;
-                        if (hi - lo < 0x1p-52) break;
-                        const double gd = herm(dbasis(tau), f0, d0, f1, d1);
-                        const double tn = tau - g / gd;
-                        tau = (tn > lo && tn < hi) ? tn : 0.5 * (lo + hi);
-                    }
+                    const double tau = cross_tau(f0, d0, f1, d1);
                     const Basis h = basis(tau), hd = dbasis(tau);
                     const double x = herm(h, x0, tx0, x1, tx1), y = herm(h, y0, ty0, y1, ty1);
                     const double m0 = (double)r0[2 * R] * c0 + (double)r0[3 * R] * s0;     // p . (cos, sin) = dT/ds

@@ -218,6 +218,15 @@ class Field:
         check(lib().rtmi_debug_field_lookup(self._h, len(x), dptr(x), dptr(y), dptr(n), dptr(gx), dptr(gy)))
         return n, gx, gy
 
+    def dgrad(self, x, y):
+        """The Jacobian of the gradient as rtmi_paraxial evaluates it (rtmi_field_eval_dgrad): the derivatives of the cell
+        polynomials of the two gradient fits -> d(dn/dx)/dx, d(dn/dx)/dy, d(dn/dy)/dx, d(dn/dy)/dy."""
+        x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.float64)
+        y = np.ascontiguousarray(np.atleast_1d(y), dtype=np.float64)
+        out = [np.empty_like(x) for _ in range(4)]
+        check(lib().rtmi_field_eval_dgrad(self._h, len(x), dptr(x), dptr(y), *[dptr(o) for o in out]))
+        return tuple(out)
+
     def close(self):
         if self._h:
             lib().rtmi_field_destroy(self._h)
@@ -422,6 +431,28 @@ class Batch:
             d[k] = out[:, q].copy()
         return d
 
+    def paraxial(self, line=None, kmax=4):
+        """Dynamic ray tracing along the recorded rays (rtmi_paraxial): the plane-wave (Q1, P1) and point-source (Q2, P2)
+        solutions of the paraxial system, the spread J = n0 Q2 per radian of launch angle, the spreading factor
+        G = (n |J|)^-1/2 and the caustic count kmah.  Returns a dict of [R] arrays Q1, P1, Q2, P2, J, G, kmah at the end of each
+        ray (NaN for a ray whose trajectory reaches past the record); with a line (a, b, c) also count [R] (rtmi_crossings')
+        and 'at_line', a dict of the same seven as [kmax, R] arrays at the crossings (NaN past count).  Needs record_stride 1,
+        op1..op9 and gamma 1."""
+        end = np.empty((len(PARAXIAL_FIELDS), self.R))
+        if line is None:
+            check(lib().rtmi_paraxial(self._h, None, 0, None, None, dptr(end)))
+            return {k: end[q].copy() for q, k in enumerate(PARAXIAL_FIELDS)}
+        ln = np.ascontiguousarray(line, dtype=np.float64)
+        if ln.shape != (3,):
+            raise ValueError("line must be (a, b, c)")
+        count = np.empty(self.R, dtype=np.int32)
+        at = np.empty((int(kmax), len(PARAXIAL_FIELDS), self.R))
+        check(lib().rtmi_paraxial(self._h, dptr(ln), int(kmax), count.ctypes.data_as(_lib._ip), dptr(at), dptr(end)))
+        d = {k: end[q].copy() for q, k in enumerate(PARAXIAL_FIELDS)}
+        d["count"] = count
+        d["at_line"] = {k: at[:, q].copy() for q, k in enumerate(PARAXIAL_FIELDS)}
+        return d
+
     def wavefronts(self, times, nfine=100):
         """The reference's wavefront extraction (RT_bench.py:1005-1044) on the device: one dict per traveltime with the
         points of the wavefront sorted by y -- 'y', 'x', 'angle' (ray angle), 'dxdy' (derivative of the PCHIP interpolant
@@ -577,18 +608,20 @@ class Shard:
 
 CROSSING_FIELDS = ("u", "x", "y", "T", "theta", "s")                            # rtmi_crossings' out[kmax][6][R]
 ARRIVAL_FIELDS = ("theta0", "T", "u", "x", "y", "theta", "residual", "iterations", "status")   # rtmi_two_point's arrivals[..][9]
+PARAXIAL_FIELDS = ("Q1", "P1", "Q2", "P2", "J", "G", "kmah")                     # rtmi_paraxial's [7] columns
 
 
 def two_point(selected_func, field, sources, line, receivers_u, *, thetas, step, max_size, box, gamma=1, reference_order=False,
               retrace=True, tol=1e-10, max_arrivals=4, max_crossings=4, max_iter=60, mem_budget=0, gamma_step=None,
-              launch_mode="auto", field_path=0, stats=False):
+              launch_mode="auto", field_path=0, stats=False, paraxial=False):
     """Rays from each source to each receiver on the line a x + b y = c (line = (a, b, c)), all on the device
     (rtmi_two_point): a fan of launch angles `thetas` per source, brackets between adjacent fan rays, Illinois regula falsi on
     the launch angle.  sources: (S, 2) array of (x, y); receivers_u: [J] coordinates along the line (u = a' y - b' x with
     (a', b') the unit normal), strictly increasing.  Returns a dict of [S, J, A] arrays -- theta0 (launch angle), T, u, x, y,
     theta (angle at the receiver), residual (u - u_j), iterations, status (rtmi_arrival_status) -- with the converged
     arrivals first, sorted by T; count [S, J] (converged arrivals) and nbad [S, J] (stalled or truncated brackets); with
-    stats=True also 'stats' (iterations, groups, rec_rows, overflow, fan_ms, bracket_ms, refine_ms)."""
+    stats=True also 'stats' (iterations, groups, rec_rows, overflow, fan_ms, bracket_ms, refine_ms).  With paraxial=True also
+    [S, J, A] arrays Q2, P2, J, G, kmah of the converged arrivals (NaN elsewhere): _two_point_paraxial."""
     src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
     sx = np.ascontiguousarray(src[:, 0]); sy = np.ascontiguousarray(src[:, 1])
     th = np.ascontiguousarray(thetas, dtype=np.float64)
@@ -622,7 +655,60 @@ def two_point(selected_func, field, sources, line, receivers_u, *, thetas, step,
     out["nbad"] = nbad
     if stats:
         out["stats"] = {k: getattr(st, k) for k, _ in _lib.TwoPointStats._fields_ if k != "reserved"}
+    if paraxial:
+        out.update(_two_point_paraxial(field, p, sx, sy, ln, out, int(max_crossings)))
     return out
+
+
+def _two_point_paraxial(field, p, sx, sy, line, arr, kmax):
+    """The paraxial columns of two_point's converged arrivals, by public calls only: one fresh batch of the
+    converged (source, launch angle) rays with the solver's parameters -- sized by a count pass without a record, as
+    rtmi_two_point sizes its own --, its crossings and its paraxial quantities at them; each arrival takes the crossing whose
+    u and T are bit-equal to its own (rtmi_two_point's promise: its arrivals are exactly what rtmi_crossings gives on such a
+    fresh batch)."""
+    keys = ("Q2", "P2", "J", "G", "kmah")
+    res = {k: np.full(arr["T"].shape, np.nan) for k in keys}
+    idx = np.argwhere(arr["status"] == _lib.ARRIVAL_CONVERGED)
+    if len(idx) == 0:
+        return res
+    R = len(idx)
+    x0 = np.ascontiguousarray(sx[idx[:, 0]]); y0 = np.ascontiguousarray(sy[idx[:, 0]])
+    th = np.ascontiguousarray(arr["theta0"][tuple(idx.T)])
+    q = Params.from_buffer_copy(p)
+    q.sort_rays = 0; q.no_n_ray = 1; q.lazy_clear = 0; q.ext_s_ray = None; q.ext_n_ray = None
+
+    def batch(stride, rows):
+        q.record_stride = stride; q.rec_rows = rows
+        h = C.c_void_p()
+        check(lib().rtmi_batch_create(field._h, C.byref(q), R, dptr(x0), dptr(y0), dptr(th), None, C.byref(h)))
+        return h
+    h = batch(0, 0)
+    try:
+        check(lib().rtmi_run(h))
+        d = np.empty((3, R))
+        check(lib().rtmi_read_d_ray(h, dptr(d)))
+    finally:
+        lib().rtmi_batch_destroy(h)
+    h = batch(1, int(d[2].max()) + 1)
+    try:
+        check(lib().rtmi_run(h))
+        cnt = np.empty(R, dtype=np.int32)
+        cr = np.empty((kmax, len(CROSSING_FIELDS), R))
+        check(lib().rtmi_crossings(h, dptr(line), kmax, cnt.ctypes.data_as(_lib._ip), dptr(cr)))
+        pc = np.empty(R, dtype=np.int32)
+        at = np.empty((kmax, len(PARAXIAL_FIELDS), R))
+        end = np.empty((len(PARAXIAL_FIELDS), R))
+        check(lib().rtmi_paraxial(h, dptr(line), kmax, pc.ctypes.data_as(_lib._ip), dptr(at), dptr(end)))
+    finally:
+        lib().rtmi_batch_destroy(h)
+    iu, iT = CROSSING_FIELDS.index("u"), CROSSING_FIELDS.index("T")
+    for r, (s_, j, a) in enumerate(idx):
+        hit = np.nonzero((cr[:, iu, r] == arr["u"][s_, j, a]) & (cr[:, iT, r] == arr["T"][s_, j, a]))[0]
+        if len(hit) == 0:
+            raise RuntimeError(f"two_point: no crossing of the re-traced ray matches arrival {(s_, j, a)}")
+        for k in keys:
+            res[k][s_, j, a] = at[hit[0], PARAXIAL_FIELDS.index(k), r]
+    return res
 
 
 def first_arrivals(selected_func, field, sources, line, receivers_u, **kw):
