@@ -14,6 +14,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/rtmi.h"
@@ -1011,7 +1012,7 @@ __device__ __forceinline__ T* wave_uniform_ptr(T* p) {
 // rowp / nrowp: this block's slice of the current row of s_ray / n_ray (wave-uniform pointers the loop advances)
 template <typename T>
 __device__ __forceinline__ void write_row_uniform(const BatchDev<T>& a, T* rowp, T* nrowp, int voff, const rt::Ray<T>& r) {
-    int qR = (int)(a.R * (long)sizeof(T));                              // byte distance between quantities (< 2^31 / 6: pick_advance)
+    int qR = (int)(a.R * (long)sizeof(T));                              // byte distance between quantities (< 2^31 / 6: step_build)
     // the multiples of qR are formed here, per row, with one scalar instruction each: hoisted out of the step loop they
     // do not fit the scalar registers and come back through v_readlane + 5 wait states apiece
     asm volatile("" : "+s"(qR));
@@ -1214,7 +1215,7 @@ __device__ __forceinline__ bool advance_bundle(const BatchDev<T>& a, T* lds, lon
     // Rows are recorded through the wave-uniform descriptor path (UROW) by every build except the VAR one: the host
     // launches a non-VAR build only while every live ray of the batch is at the same row (always, unless
     // rtmi_batch_set_state gave rays rows of their own) and a row's six quantities lie within 31-bit byte offsets of each
-    // other (pick_advance); the VAR build keeps the per-lane row bookkeeping.
+    // other (step_build); the VAR build keeps the per-lane row bookkeeping.
     // Drain the state loads here: a load still pending at the loop header stays "pending" in the compiler's wait-count
     // model around the back edge, and every first use in the loop then waits for vmcnt(0), i.e. for the previous
     // step's row stores to be acknowledged.
@@ -1461,6 +1462,20 @@ __global__ void k_f32_to_f64(const float* in, double* out, size_t n) {
     if (i < n) out[i] = (double)in[i];
 }
 
+// What a plain launch runs besides the ordinary k_advance build: the VAR build (per-ray DELTA_S / max_size, per-lane row
+// bookkeeping) or k_advance_lat (few waves).  The sliced and refill schedules have one build each whatever the flavour.
+enum StepFlavour { kOrdinary = 0, kPerRay = 1, kFewWaves = 2 };
+// The build key: everything the choice of a step kernel depends on, decided by step_build alone.
+struct StepBuild {
+    int dtype = RTMI_F64;
+    int ki = 0;                 // kernel method (batch_kernel_index)
+    bool iso = false;           // gamma == 1 below op10
+    bool lds = false;           // the gather policy (use_lds_tile)
+    bool noflat = false;        // the field has neither flat nor steep cells: the builds without its map's tests
+    int flavour = kOrdinary;
+    int slot() const { return (iso ? 1 : 0) | (lds ? 2 : 0) | (noflat ? 4 : 0) | flavour << 3; }
+    bool operator==(const StepBuild& o) const { return dtype == o.dtype && ki == o.ki && slot() == o.slot(); }
+};
 struct rtmi_batch {
     const rtmi_field* field = nullptr;
     rtmi_params p{};
@@ -1485,10 +1500,7 @@ struct rtmi_batch {
     double total_kernel_ms = 0;  // all advance launches since create (a reset does not clear it)
     uint64_t total_launches = 0;
     uint32_t launches = 0;
-    const void* kfn = nullptr;
-    const void* kfn_refill = nullptr;
     int persistent_blocks = 0;   // resident 256-thread blocks of the refill kernel on this device
-    const void* kfn_sliced = nullptr;
     int sliced_blocks = 0;       // resident 256-thread blocks of the sliced kernel on this device
     unsigned long long* sliced_ctl = nullptr;   // launch_mode 2: head, pushed, finished, stalled, queue entries (k_advance_sliced)
     bool dirty = false;          // rows may hold data a re-run will not overwrite (set_state / set_per_ray since the last clear)
@@ -1500,16 +1512,17 @@ struct rtmi_batch {
     int auto_n[2] = {0, 0};      // timed runs per schedule so far
     int auto_kept = -1;          // -1 while exploring; then 0 (sliced) or 1 (plain) for the rest of the batch's life
     double gold_sup[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // gold_sup_derivatives(gamma_step) for op10/op11
-    int lat_simds = 0, lat_waves_per_simd = 0;       // SIMDs of the device (CUs x 4); > 0 once known (pick_advance's latency rule)
+    int lat_simds = 0;           // SIMDs of the device (CUs x 4; step_build's few-waves rule)
     int mode_used = RTMI_LAUNCH_PLAIN;
+    const void* kfn_used = nullptr;   // the kernel of the last launch (until then the plain launch's)
     uint32_t auto_fallbacks = 0; // RTMI_LAUNCH_AUTO: sliced launches that abandoned a wait and were finished by the plain kernel
     void* staging = nullptr;     // device scratch of the read / metric / set_state paths, grown on demand, freed with the batch
     size_t staging_bytes = 0;
     // rtmi_step_repeat: `count` launches of `nsteps` steps as one hipGraph (a chain of kernel nodes), kept while the same
-    // kernel, step count and launch count are asked for
+    // build, step count and launch count are asked for
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
-    const void* graph_kfn = nullptr;
+    StepBuild graph_build;
     int graph_nsteps = 0, graph_count = 0, graph_block = 0;
     struct Retrace* rt = nullptr;   // critical rays handed over to a reference-order re-trace (nullptr: this batch hands nothing over)
     bool is_retrace_sub = false;    // this batch IS such a re-trace batch (owned by another batch's Retrace)
@@ -1642,81 +1655,6 @@ template <typename T> static BatchDev<T> batch_dev(const rtmi_batch* b) {
     return a;
 }
 
-// kernel variant tables: [kernel method][iso][lds].  Kernel methods: the step methods 1..11, then op1/2/6/7/8 in the reference's
-// operation order (METHOD = method | rt::kRefOrder, fp64 only: the fp32 tables alias the ordinary builds there).
-// Anisotropic-only methods (op10/op11) have no ISO build.
-// Index 16: op7 with RTMI_ORDER_FAST_FIELD -- the reference-order step on the fast field lookup (rt::kFastField).
-constexpr int kKernelMethods = 17;
-constexpr int kmethod_of(int idx) {
-    return idx < 11 ? idx + 1 : idx == 16 ? (7 | rt::kRefOrder | rt::kFastField) : (idx == 11 ? 1 : idx == 12 ? 2 : idx == 13 ? 6 : idx == 14 ? 7 : 8) | rt::kRefOrder;
-}
-static int kernel_index(int method, bool ref_order, bool fast_field) {
-    if (!ref_order || rt::is_exact_method(method)) return method - 1;
-    if (fast_field) return 16;
-    return method == 1 ? 11 : method == 2 ? 12 : method == 6 ? 13 : method == 7 ? 14 : 15;
-}
-template <typename T> constexpr int km(int idx) { return sizeof(T) == 4 ? rt::base_method(kmethod_of(idx)) : kmethod_of(idx); }
-constexpr bool iso_ok(int m) { return rt::base_method(m) < 10; }
-#define RTMI_ADV_(T, I) \
-    {{(const void*)k_advance<T, km<T>(I), false, false, false>, (const void*)k_advance<T, km<T>(I), false, true, false>}, \
-     {(const void*)k_advance<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), false, false>, (const void*)k_advance<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), true, false>}}
-// the wave-shared builds for a field without flat cells (NOFLAT; only the polynomial lookup has the map's tests): [kernel method][iso]
-#define RTMI_ADVNF_(T, I) \
-    {(const void*)k_advance<T, km<T>(I), false, true, false, uses_poly<T, km<T>(I)>()>, \
-     (const void*)k_advance<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), true, false, uses_poly<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1)>()>}
-#define RTMI_SLICEDNF_(T, I) \
-    {(const void*)k_advance_sliced<T, km<T>(I), false, true, uses_poly<T, km<T>(I)>()>, \
-     (const void*)k_advance_sliced<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), true, uses_poly<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1)>()>}
-// ... and the per-lane-gather builds of op1/2/6/8 in reference order (kernel indices 11, 12, 13, 15) for a field whose map is empty: without
-// the flat path of the reference-order step (rt::GlobalGather's FLATMAP).  Every other index: the ordinary build again.
-constexpr bool ref1268(int idx) { return idx == 11 || idx == 12 || idx == 13 || idx == 15; }
-#define RTMI_ADVNF0_(T, I) \
-    {(const void*)k_advance<T, km<T>(I), false, false, false, sizeof(T) == 8 && ref1268(I)>, \
-     (const void*)k_advance<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), false, false, sizeof(T) == 8 && ref1268(I) && iso_ok(km<T>(I))>}
-#define RTMI_SLICEDNF0_(T, I) \
-    {(const void*)k_advance_sliced<T, km<T>(I), false, false, sizeof(T) == 8 && ref1268(I)>, \
-     (const void*)k_advance_sliced<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), false, sizeof(T) == 8 && ref1268(I) && iso_ok(km<T>(I))>}
-#define RTMI_ADVVAR_(T, I) \
-    {(const void*)k_advance<T, km<T>(I), false, false, true>, (const void*)k_advance<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), false, true>}
-#define RTMI_REFILL_(T, I) \
-    {{(const void*)k_trace_refill<T, km<T>(I), false, false>, (const void*)k_trace_refill<T, km<T>(I), false, true>}, \
-     {(const void*)k_trace_refill<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), false>, (const void*)k_trace_refill<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), true>}}
-#define RTMI_SLICED_(T, I) \
-    {{(const void*)k_advance_sliced<T, km<T>(I), false, false>, (const void*)k_advance_sliced<T, km<T>(I), false, true>}, \
-     {(const void*)k_advance_sliced<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), false>, (const void*)k_advance_sliced<T, (iso_ok(km<T>(I)) ? km<T>(I) : 1), iso_ok(km<T>(I)), true>}}
-#define RTMI_ALL16_(X, T) X(T, 0), X(T, 1), X(T, 2), X(T, 3), X(T, 4), X(T, 5), X(T, 6), X(T, 7), X(T, 8), X(T, 9), X(T, 10), X(T, 11), X(T, 12), X(T, 13), X(T, 14), X(T, 15), X(T, 16)
-template <typename T> static const void* sliced_fn(int ki, bool iso, bool lds, bool noflat) {
-    static const void* const tab[kKernelMethods][2][2] = {RTMI_ALL16_(RTMI_SLICED_, T)};
-    static const void* const tabnf[kKernelMethods][2] = {RTMI_ALL16_(RTMI_SLICEDNF_, T)};
-    static const void* const tabnf0[kKernelMethods][2] = {RTMI_ALL16_(RTMI_SLICEDNF0_, T)};
-    if (!lds && noflat) return tabnf0[ki][iso ? 1 : 0];
-    return lds && noflat ? tabnf[ki][iso ? 1 : 0] : tab[ki][iso ? 1 : 0][lds ? 1 : 0];
-}
-template <typename T> static const void* advance_fn(int ki, bool iso, bool lds, bool noflat) {
-    static const void* const tab[kKernelMethods][2][2] = {RTMI_ALL16_(RTMI_ADV_, T)};
-    static const void* const tabnf[kKernelMethods][2] = {RTMI_ALL16_(RTMI_ADVNF_, T)};
-    static const void* const tabnf0[kKernelMethods][2] = {RTMI_ALL16_(RTMI_ADVNF0_, T)};
-    if (!lds && noflat) return tabnf0[ki][iso ? 1 : 0];
-    return lds && noflat ? tabnf[ki][iso ? 1 : 0] : tab[ki][iso ? 1 : 0][lds ? 1 : 0];
-}
-// per-ray DELTA_S / max_size builds (global gather only): [kernel method][iso]
-template <typename T> static const void* advance_var_fn(int ki, bool iso) {
-    static const void* const tab[kKernelMethods][2] = {RTMI_ALL16_(RTMI_ADVVAR_, T)};
-    return tab[ki][iso ? 1 : 0];
-}
-template <typename T> static const void* refill_fn(int ki, bool iso, bool lds) {
-    static const void* const tab[kKernelMethods][2][2] = {RTMI_ALL16_(RTMI_REFILL_, T)};
-    return tab[ki][iso ? 1 : 0][lds ? 1 : 0];
-}
-#undef RTMI_SLICED_
-#undef RTMI_ADV_
-#undef RTMI_ADVNF_
-#undef RTMI_ADVNF0_
-#undef RTMI_SLICEDNF0_
-#undef RTMI_SLICEDNF_
-#undef RTMI_ADVVAR_
-#undef RTMI_REFILL_
-#undef RTMI_ALL16_
 // VRCP14PD's table (rt_rcp14_table.h) decoded once per device, for rt::ex::atan2_
 __global__ void k_rcp14_init() {
     unsigned short v = RT_RCP14_T0;
@@ -1747,7 +1685,6 @@ static int ensure_rcp14_table(hipStream_t st) {
 }
 // the fp64 batch runs rt_exact.h's arithmetic: always for op3/4/5/9/10/11, for the others when ref_order() says so
 static bool batch_exact(const rtmi_batch* b) { return b->p.dtype == RTMI_F64 && (rt::is_exact_method(b->p.method) || ref_order(b->p)); }
-static int batch_kernel_index(const rtmi_batch* b) { return kernel_index(b->p.method, ref_order(b->p), fast_field_order(b->p)); }
 // field_path 0 (auto): which gather policy the step kernels are built with.
 static bool use_lds_tile(const rtmi_batch* b) {
     if (b->p.field_path == 1) return false;
@@ -1763,26 +1700,6 @@ static bool use_lds_tile(const rtmi_batch* b) {
 // reset) and 6 quantities x R values within 31-bit byte offsets
 static bool uniform_rows_ok(const rtmi_batch* b) {
     return b->p.record_stride == 0 || (!b->dirty_state && (double)b->R * (double)b->esz * 6.0 < 2147483647.0);
-}
-// op2/op6 fp64 tile builds for few waves (k_advance_lat): [method 2 | 6][iso]
-static const void* advance_lat_fn(int m, bool iso, bool noflat) {
-    static const void* const tab[2][2][2] = {{{(const void*)k_advance_lat<double, 2, false, false>, (const void*)k_advance_lat<double, 2, false, true>},
-                                              {(const void*)k_advance_lat<double, 2, true, false>, (const void*)k_advance_lat<double, 2, true, true>}},
-                                             {{(const void*)k_advance_lat<double, 6, false, false>, (const void*)k_advance_lat<double, 6, false, true>},
-                                              {(const void*)k_advance_lat<double, 6, true, false>, (const void*)k_advance_lat<double, 6, true, true>}}};
-    return tab[m == 6 ? 1 : 0][iso ? 1 : 0][noflat ? 1 : 0];
-}
-static const void* pick_advance(const rtmi_batch* b) {
-    const bool iso = b->p.gamma == 1.0 && b->p.method < 10, lds = use_lds_tile(b);
-    // at most two waves per SIMD's worth of rays: the latency build
-    if (lds && b->p.dtype == RTMI_F64 && (b->p.method == 2 || b->p.method == 6) && !b->vstep && uniform_rows_ok(b) &&
-        !ref_order(b->p) && b->lat_waves_per_simd > 0 && (b->R + 63) / 64 <= (int64_t)2 * b->lat_simds)
-        return advance_lat_fn(b->p.method, iso, b->field->flat_cells == 0 && b->field->steep_cells == 0);
-    // the VAR build: per-ray DELTA_S / max_size when set, and per-lane row bookkeeping always
-    if (b->vstep || !uniform_rows_ok(b))
-        return b->p.dtype == RTMI_F64 ? advance_var_fn<double>(batch_kernel_index(b), iso) : advance_var_fn<float>(batch_kernel_index(b), iso);
-    const bool noflat = b->field->flat_cells == 0 && b->field->steep_cells == 0;      // nothing in this field's map: the builds without its tests
-    return b->p.dtype == RTMI_F64 ? advance_fn<double>(batch_kernel_index(b), iso, lds, noflat) : advance_fn<float>(batch_kernel_index(b), iso, lds, noflat);
 }
 // queue entries beyond the implicit first NB: every bundle is pushed back once per slice it survives
 static unsigned long long sliced_capacity(const rtmi_batch* b, int slice) {
@@ -1807,14 +1724,101 @@ static unsigned long long sliced_timeout_ticks(const rtmi_batch* b, int slice) {
 }
 // can this batch run the time-sliced schedule at all (queue within 256 MB, uniform DELTA_S, rays in lockstep)?
 static bool sliced_feasible(const rtmi_batch* b) { return sliced_capacity(b, sliced_steps(b)) <= (1ull << 25); }
-static const void* pick_sliced(const rtmi_batch* b) {
-    const bool iso = b->p.gamma == 1.0 && b->p.method < 10, lds = use_lds_tile(b);
-    const bool noflat = b->field->flat_cells == 0 && b->field->steep_cells == 0;
-    return b->p.dtype == RTMI_F64 ? sliced_fn<double>(batch_kernel_index(b), iso, lds, noflat) : sliced_fn<float>(batch_kernel_index(b), iso, lds, noflat);
+
+// ------------------------------------------------------------------ which step kernel a batch runs
+// Kernel methods: the step methods 1..11, then op1/2/6/7/8 in the reference's operation order (METHOD = method | rt::kRefOrder,
+// fp64 only), then at 16 op7 with RTMI_ORDER_FAST_FIELD -- the reference-order step on the fast field lookup (rt::kFastField).
+constexpr int kKernelMethods = 17;
+constexpr int kmethod_of(int idx) {
+    return idx < 11 ? idx + 1 : idx == 16 ? (7 | rt::kRefOrder | rt::kFastField) : (idx == 11 ? 1 : idx == 12 ? 2 : idx == 13 ? 6 : idx == 14 ? 7 : 8) | rt::kRefOrder;
 }
-static const void* pick_refill(const rtmi_batch* b) {
-    const bool iso = b->p.gamma == 1.0 && b->p.method < 10, lds = use_lds_tile(b);
-    return b->p.dtype == RTMI_F64 ? refill_fn<double>(batch_kernel_index(b), iso, lds) : refill_fn<float>(batch_kernel_index(b), iso, lds);
+static int kernel_index(int method, bool ref_order, bool fast_field) {
+    if (!ref_order || rt::is_exact_method(method)) return method - 1;
+    if (fast_field) return 16;
+    return method == 1 ? 11 : method == 2 ? 12 : method == 6 ? 13 : method == 7 ? 14 : 15;
+}
+static int batch_kernel_index(const rtmi_batch* b) { return kernel_index(b->p.method, ref_order(b->p), fast_field_order(b->p)); }
+
+static StepBuild step_build(const rtmi_batch* b) {
+    StepBuild k;
+    k.dtype = b->p.dtype;
+    k.ki = batch_kernel_index(b);
+    k.iso = b->p.gamma == 1.0 && b->p.method < 10;
+    k.lds = use_lds_tile(b);
+    k.noflat = b->field->flat_cells == 0 && b->field->steep_cells == 0;
+    // at most two waves per SIMD's worth of rays: the latency build
+    if (k.lds && k.dtype == RTMI_F64 && (b->p.method == 2 || b->p.method == 6) && !b->vstep && uniform_rows_ok(b) && !ref_order(b->p) &&
+        (b->R + 63) / 64 <= (int64_t)2 * b->lat_simds)
+        k.flavour = kFewWaves;
+    else if (b->vstep || !uniform_rows_ok(b))
+        k.flavour = kPerRay;
+    return k;
+}
+
+// The kernel of kernel method I, key slot S (StepBuild::slot) under schedule SCHED.  The rules:
+//   fp32 has no reference order: its methods 11..16 are the ordinary builds again;
+//   op10/op11 have no ISO build;
+//   NOFLAT leaves out the polynomial lookup's map tests in the LDS-tile builds, and the flat path of the reference-order step
+//   (rt::GlobalGather's FLATMAP) in the fp64 global-gather builds of op1/2/6/8; every other build keeps its map;
+//   the VAR build gathers globally with the map; k_advance_lat is built for fp64 op2/op6 with the tile policy only.
+constexpr int kSlots = 3 << 3;
+template <typename T, int I, int S, int SCHED> static const void* build_kernel() {
+    constexpr int M = sizeof(T) == 4 ? rt::base_method(kmethod_of(I)) : kmethod_of(I);
+    constexpr bool ISO = (S & 1) && rt::base_method(M) < 10, LDS = (S & 2) != 0;
+    constexpr bool NOFLAT = (S & 4) && (LDS ? uses_poly<T, M>() : sizeof(T) == 8 && (I == 11 || I == 12 || I == 13 || I == 15));
+    if constexpr (SCHED == RTMI_LAUNCH_SLICED) return (const void*)k_advance_sliced<T, M, ISO, LDS, NOFLAT>;
+    else if constexpr (SCHED == RTMI_LAUNCH_REFILL) return (const void*)k_trace_refill<T, M, ISO, LDS>;
+    else if constexpr (S >> 3 == kPerRay) return (const void*)k_advance<T, M, ISO, false, true>;
+    else if constexpr (S >> 3 == kOrdinary) return (const void*)k_advance<T, M, ISO, LDS, false, NOFLAT>;
+    else if constexpr (sizeof(T) == 8 && (M == 2 || M == 6) && LDS) return (const void*)k_advance_lat<T, M, ISO, NOFLAT>;
+    else return nullptr;
+}
+template <typename T, int SCHED, size_t... N> static const void* build_table(size_t n, std::index_sequence<N...>) {
+    static const void* const tab[] = {build_kernel<T, (int)(N / kSlots), (int)(N % kSlots), SCHED>()...};
+    return tab[n];
+}
+template <typename T> static const void* step_kernel_t(size_t n, int sched) {
+    constexpr auto all = std::make_index_sequence<kKernelMethods * kSlots>();
+    return sched == RTMI_LAUNCH_SLICED ? build_table<T, RTMI_LAUNCH_SLICED>(n, all)
+         : sched == RTMI_LAUNCH_REFILL ? build_table<T, RTMI_LAUNCH_REFILL>(n, all) : build_table<T, RTMI_LAUNCH_PLAIN>(n, all);
+}
+// sched: RTMI_LAUNCH_PLAIN (k_advance or k_advance_lat), RTMI_LAUNCH_SLICED (k_advance_sliced) or RTMI_LAUNCH_REFILL (k_trace_refill)
+static const void* step_kernel(const StepBuild& k, int sched) {
+    const size_t n = (size_t)k.ki * kSlots + (size_t)k.slot();
+    return k.dtype == RTMI_F64 ? step_kernel_t<double>(n, sched) : step_kernel_t<float>(n, sched);
+}
+
+// One launch of build k's kernel under a schedule with the batch's present arguments and grid, handed to `use` as kernel node
+// parameters (launched at once, or added to a graph).  nsteps: the launch's step budget (plain) or the slice (sliced).
+template <typename T, typename F> static hipError_t with_step_node_t(const rtmi_batch* b, const StepBuild& k, int sched, int nsteps, F&& use) {
+    BatchDev<T> a = batch_dev<T>(b);
+    int refill_min = b->p.refill_min > 0 ? b->p.refill_min : 32, chunk = 16;
+    unsigned long long capacity = 0, timeout = 0, *ctl = b->sliced_ctl;
+    void* plain[] = {&a, &nsteps};
+    void* refill[] = {&a, &refill_min, &chunk};
+    void* sliced[] = {&a, &nsteps, &capacity, &ctl, &timeout};
+    const long bundles = (b->R + 255) / 256;
+    hipKernelNodeParams kp{};
+    kp.func = const_cast<void*>(step_kernel(k, sched));
+    kp.blockDim = dim3(256);
+    if (sched == RTMI_LAUNCH_PLAIN) {
+        const int bs = b->p.block_size > 0 ? b->p.block_size : 256;
+        kp.gridDim = dim3((unsigned)((b->R + bs - 1) / bs));
+        kp.blockDim = dim3(bs);
+        kp.kernelParams = plain;
+    } else if (sched == RTMI_LAUNCH_SLICED) {
+        capacity = sliced_capacity(b, nsteps);
+        timeout = sliced_timeout_ticks(b, nsteps);
+        kp.gridDim = dim3((unsigned)(bundles < b->sliced_blocks ? bundles : b->sliced_blocks));
+        kp.kernelParams = sliced;
+    } else {
+        kp.gridDim = dim3((unsigned)(bundles < b->persistent_blocks ? bundles : b->persistent_blocks));
+        kp.kernelParams = refill;
+    }
+    return use(kp);
+}
+template <typename F> static hipError_t with_step_node(const rtmi_batch* b, const StepBuild& k, int sched, int nsteps, F&& use) {
+    return k.dtype == RTMI_F64 ? with_step_node_t<double>(b, k, sched, nsteps, use) : with_step_node_t<float>(b, k, sched, nsteps, use);
 }
 
 // clear_traj: zero the trajectory arrays (np.zeros, :802-803).  A reset with unchanged launch conditions rewrites
@@ -1946,14 +1950,13 @@ RTMI_EXPORT int rtmi_batch_create(const rtmi_field* f, const rtmi_params* p, int
         int dev = 0, cus = 0, per_cu = 0;
         HIP_TRY(hipGetDevice(&dev));
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        b->lat_simds = cus * 4; b->lat_waves_per_simd = 1;
-        b->kfn = pick_advance(b);
-        b->kfn_refill = pick_refill(b);
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, b->kfn_refill, 256, 0));
+        b->lat_simds = cus * 4;
+        const StepBuild k = step_build(b);
+        b->kfn_used = step_kernel(k, RTMI_LAUNCH_PLAIN);
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel(k, RTMI_LAUNCH_REFILL), 256, 0));
         b->persistent_blocks = cus * (per_cu > 0 ? per_cu : 1);
         if (b->p.launch_mode == RTMI_LAUNCH_SLICED || b->p.launch_mode == RTMI_LAUNCH_AUTO) {
-            b->kfn_sliced = pick_sliced(b);
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, b->kfn_sliced, 256, 0));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel(k, RTMI_LAUNCH_SLICED), 256, 0));
             b->sliced_blocks = cus * (per_cu > 0 ? per_cu : 1);
             if (getenv("RTMI_DEBUG")) fprintf(stderr, "rtmi: sliced kernel: %d CUs x %d resident blocks\n", cus, per_cu);
             // one queue entry per slice a bundle survives: tiny slices on a large batch with a large max_size would ask for
@@ -2013,7 +2016,7 @@ RTMI_EXPORT int rtmi_batch_set_per_ray(rtmi_batch* b, const double* step, const 
                 "rtmi_batch_set_per_ray: every max_size must be in [2 (4 for op7), params.max_size]");
         h2[k] = libm_square(step[k]) / 2.0;   // numpy scalar step**2 (:330)
     }
-    if (!b->vstep) {   // all three or none: pick_advance keys on vstep alone
+    if (!b->vstep) {   // all three or none: step_build keys on vstep alone
         void *v1 = nullptr, *v2 = nullptr;
         int* v3 = nullptr;
         hipError_t ea = hipMalloc(&v1, R * b->esz);
@@ -2043,7 +2046,6 @@ RTMI_EXPORT int rtmi_batch_set_per_ray(rtmi_batch* b, const double* step, const 
     }
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("rtmi_batch_set_per_ray: ") + hipGetErrorString(e));
-    b->kfn = pick_advance(b);
     b->dirty = true;   // rows written under the previous steps would no longer be rewritten: clear on the next reset
     return RTMI_OK;
 }
@@ -2094,7 +2096,6 @@ int rtmi_internal_relaunch(rtmi_batch* b, const double* theta0, const int32_t* m
             const void* p2 = b->p.dtype == RTMI_F64 ? (const void*)h2.data() : (const void*)f2.data();
             HIP_TRY(hipMemcpy(b->vstep, p1, R * b->esz, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(b->vstep2h, p2, R * b->esz, hipMemcpyHostToDevice));
-            b->kfn = pick_advance(b);
         }
         HIP_TRY(hipMemcpyAsync(b->vmax, max_size, R * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
     }
@@ -2244,15 +2245,6 @@ static int fold_events(rtmi_batch* b) {
     return RTMI_OK;
 }
 
-template <typename T> static void launch_advance(rtmi_batch* b, int nsteps) {
-    BatchDev<T> a = batch_dev<T>(b);
-    b->kfn = pick_advance(b);   // depends on state that changes after create (set_state, set_per_ray)
-    void* args[] = {&a, &nsteps};
-    const int bs = b->p.block_size > 0 ? b->p.block_size : 256;
-    const dim3 g((unsigned)((b->R + bs - 1) / bs)), blk(bs);
-    (void)hipLaunchKernel(b->kfn, g, blk, args, 0, b->stream);
-}
-
 static int next_event_pair(rtmi_batch* b, std::pair<hipEvent_t, hipEvent_t>** out) {
     if (b->ev_used == b->events.size()) {
         if (b->events.size() >= 1024) {
@@ -2278,34 +2270,27 @@ RTMI_EXPORT int rtmi_step(rtmi_batch* b, int32_t nsteps);
 static void drop_graph(rtmi_batch* b) {
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     if (b->graph) (void)hipGraphDestroy(b->graph);
-    b->graph_exec = nullptr; b->graph = nullptr; b->graph_kfn = nullptr; b->graph_nsteps = b->graph_count = 0;
+    b->graph_exec = nullptr; b->graph = nullptr; b->graph_nsteps = b->graph_count = 0;
 }
-// A chain of `count` kernel nodes, each the advance kernel for `nsteps` steps with the batch's present arguments.
-template <typename T> static hipError_t build_step_graph(rtmi_batch* b, int nsteps, int count) {
+// A chain of `count` kernel nodes, each build k's plain launch for `nsteps` steps with the batch's present arguments.
+static hipError_t build_step_graph(rtmi_batch* b, const StepBuild& k, int nsteps, int count, int bs) {
     drop_graph(b);
-    BatchDev<T> a = batch_dev<T>(b);
-    b->kfn = pick_advance(b);
-    const int bs = b->p.block_size > 0 ? b->p.block_size : 256;
     hipError_t e = hipGraphCreate(&b->graph, 0);
     if (e != hipSuccess) return e;
-    void* args[] = {&a, &nsteps};
-    hipKernelNodeParams kp{};
-    kp.func = const_cast<void*>(b->kfn);
-    kp.gridDim = dim3((unsigned)((b->R + bs - 1) / bs));
-    kp.blockDim = dim3(bs);
-    kp.sharedMemBytes = 0;
-    kp.kernelParams = args;
-    kp.extra = nullptr;
-    hipGraphNode_t prev = nullptr;
-    for (int i = 0; i < count; i++) {
-        hipGraphNode_t node = nullptr;
-        e = hipGraphAddKernelNode(&node, b->graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp);
-        if (e != hipSuccess) return e;
-        prev = node;
-    }
+    e = with_step_node(b, k, RTMI_LAUNCH_PLAIN, nsteps, [&](const hipKernelNodeParams& kp) {
+        hipGraphNode_t prev = nullptr;
+        for (int i = 0; i < count; i++) {
+            hipGraphNode_t node = nullptr;
+            const hipError_t en = hipGraphAddKernelNode(&node, b->graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp);
+            if (en != hipSuccess) return en;
+            prev = node;
+        }
+        return hipSuccess;
+    });
+    if (e != hipSuccess) return e;
     e = hipGraphInstantiate(&b->graph_exec, b->graph, nullptr, nullptr, 0);
     if (e != hipSuccess) return e;
-    b->graph_kfn = b->kfn; b->graph_nsteps = nsteps; b->graph_count = count; b->graph_block = bs;
+    b->graph_build = k; b->graph_nsteps = nsteps; b->graph_count = count; b->graph_block = bs;
     return hipSuccess;
 }
 
@@ -2316,10 +2301,11 @@ RTMI_EXPORT int rtmi_step_repeat(rtmi_batch* b, int32_t nsteps, int32_t count) {
     ARG_TRY(b->p.block_size == 0 || (b->p.block_size % 64 == 0 && b->p.block_size <= 256),
             "rtmi_step_repeat: block_size must be a multiple of 64, at most 256");
     const int bs = b->p.block_size > 0 ? b->p.block_size : 256;
-    // the graph holds the kernel arguments by value: rebuilt when anything they derive from may have changed (the kernel
-    // choice follows set_state / set_per_ray; reset and restore keep the same buffers and parameters)
-    if (!b->graph_exec || b->graph_kfn != pick_advance(b) || b->graph_nsteps != nsteps || b->graph_count != count || b->graph_block != bs) {
-        const hipError_t e = b->p.dtype == RTMI_F64 ? build_step_graph<double>(b, nsteps, count) : build_step_graph<float>(b, nsteps, count);
+    // the graph holds the kernel arguments by value: rebuilt when anything they derive from may have changed (the build
+    // follows set_state / set_per_ray; reset and restore keep the same buffers and parameters)
+    const StepBuild k = step_build(b);
+    if (!b->graph_exec || !(b->graph_build == k) || b->graph_nsteps != nsteps || b->graph_count != count || b->graph_block != bs) {
+        const hipError_t e = build_step_graph(b, k, nsteps, count, bs);
         if (e != hipSuccess) {   // no graph: the same launches one by one
             drop_graph(b);
             (void)hipGetLastError();
@@ -2336,10 +2322,10 @@ RTMI_EXPORT int rtmi_step_repeat(rtmi_batch* b, int32_t nsteps, int32_t count) {
     HIP_TRY(hipEventRecord(evp->second, b->stream));
     b->launches += (uint32_t)count; b->total_launches += (uint64_t)count;
     b->mode_used = RTMI_LAUNCH_PLAIN;
+    b->kfn_used = step_kernel(k, RTMI_LAUNCH_PLAIN);
     return RTMI_OK;
 }
 
-// drain: the launch runs every ray to its end (rtmi_run) -- critical rays are re-traced beside it, inside its timing events
 // A run the host watches (rtmi_run) on a batch with compute units set aside for the re-trace (Retrace::masked): between the
 // opening and the closing event on the caller's stream, the batch's launches go to its own stream, whose CU mask is the
 // complement of the re-trace streams'.  enter() after the opening event, leave() before the closing one; an error path in
@@ -2372,6 +2358,34 @@ int OwnStream::leave() {
     return RTMI_OK;
 }
 
+// One launch of the step kernel for a schedule, timed by an event pair on the caller's stream (*evp).  nsteps: the step budget
+// (plain) or the slice (sliced).  drain: the launch runs every ray to its end (rtmi_run; sliced and refill always do) -- on
+// the batch's own stream (OwnStream), with critical rays re-traced beside it, inside its timing events.
+static int timed_launch(rtmi_batch* b, int sched, int nsteps, bool drain, std::pair<hipEvent_t, hipEvent_t>** evp) {
+    int rc = next_event_pair(b, evp);
+    if (rc) return rc;
+    auto* ev = *evp;
+    if (sched == RTMI_LAUNCH_SLICED) HIP_TRY(hipMemsetAsync(b->sliced_ctl, 0, (4 + sliced_capacity(b, nsteps)) * sizeof(unsigned long long), b->stream));
+    if (sched == RTMI_LAUNCH_REFILL) HIP_TRY(hipMemsetAsync(b->counters + 2, 0, sizeof(unsigned long long), b->stream));   // refill queue head
+    HIP_TRY(hipEventRecord(ev->first, b->stream));
+    OwnStream own;
+    if (drain) { const int rco = own.enter(b); if (rco) return rco; }
+    (void)with_step_node(b, step_build(b), sched, nsteps, [&](const hipKernelNodeParams& kp) {
+        b->kfn_used = kp.func;
+        return hipLaunchKernel(kp.func, kp.gridDim, kp.blockDim, kp.kernelParams, 0, b->stream);
+    });
+    HIP_TRY(hipGetLastError());
+    if (b->rt) {
+        b->rt->pending = true;
+        if (drain) { const int rcd = retrace_drain(b, true); if (rcd) return rcd; }
+    }
+    { const int rco = own.leave(); if (rco) return rco; }
+    HIP_TRY(hipEventRecord(ev->second, b->stream));
+    b->launches++; b->total_launches++;
+    b->mode_used = sched;
+    return RTMI_OK;
+}
+
 static int step_impl(rtmi_batch* b, int32_t nsteps, bool drain) {
     ARG_TRY(b, "rtmi_step: null");
     ARG_TRY(nsteps > 0, "rtmi_step: nsteps must be > 0");
@@ -2379,24 +2393,7 @@ static int step_impl(rtmi_batch* b, int32_t nsteps, bool drain) {
     ARG_TRY(b->p.block_size == 0 || (b->p.block_size % 64 == 0 && b->p.block_size <= 256),
             "rtmi_step: block_size must be a multiple of 64, at most 256");
     std::pair<hipEvent_t, hipEvent_t>* evp = nullptr;
-    int rc0 = next_event_pair(b, &evp);
-    if (rc0) return rc0;
-    auto& ev = *evp;
-    HIP_TRY(hipEventRecord(ev.first, b->stream));
-    OwnStream own;
-    if (drain) { const int rco = own.enter(b); if (rco) return rco; }
-    if (b->p.dtype == RTMI_F64) launch_advance<double>(b, nsteps);
-    else launch_advance<float>(b, nsteps);
-    HIP_TRY(hipGetLastError());
-    if (b->rt) {
-        b->rt->pending = true;
-        if (drain) { const int rcd = retrace_drain(b, true); if (rcd) return rcd; }
-    }
-    { const int rco = own.leave(); if (rco) return rco; }
-    HIP_TRY(hipEventRecord(ev.second, b->stream));
-    b->launches++; b->total_launches++;
-    b->mode_used = RTMI_LAUNCH_PLAIN;
-    return RTMI_OK;
+    return timed_launch(b, RTMI_LAUNCH_PLAIN, nsteps, drain, &evp);
 }
 RTMI_EXPORT int rtmi_step(rtmi_batch* b, int32_t nsteps) { return step_impl(b, nsteps, false); }
 
@@ -2409,54 +2406,13 @@ static int read_counters(rtmi_batch* b) {
     return RTMI_OK;
 }
 
-static int next_event_pair(rtmi_batch* b, std::pair<hipEvent_t, hipEvent_t>** out);
-
-template <typename T> static void launch_refill(const rtmi_batch* b) {
-    BatchDev<T> a = batch_dev<T>(b);
-    int refill_min = b->p.refill_min > 0 ? b->p.refill_min : 32;
-    int chunk = 16;
-    void* args[] = {&a, &refill_min, &chunk};
-    long need = (b->R + 255) / 256;
-    const dim3 g((unsigned)(need < b->persistent_blocks ? need : b->persistent_blocks)), blk(256);
-    (void)hipLaunchKernel(b->kfn_refill, g, blk, args, 0, b->stream);
-}
-
-template <typename T> static void launch_sliced(const rtmi_batch* b, int slice, unsigned long long capacity) {
-    BatchDev<T> a = batch_dev<T>(b);
-    unsigned long long* ctl = b->sliced_ctl;
-    unsigned long long timeout = sliced_timeout_ticks(b, slice);
-    void* args[] = {&a, &slice, &capacity, &ctl, &timeout};
-    const long need = (b->R + 255) / 256;
-    const dim3 g((unsigned)(need < b->sliced_blocks ? need : b->sliced_blocks)), blk(256);
-    (void)hipLaunchKernel(b->kfn_sliced, g, blk, args, 0, b->stream);
-}
-
 // the time-sliced schedule can take this run: queue allocated, uniform DELTA_S, rows through the wave-uniform descriptor
 static bool sliced_ready(const rtmi_batch* b) { return b->sliced_ctl && !b->vstep && uniform_rows_ok(b); }
 
 static int run_sliced(rtmi_batch* b, std::pair<hipEvent_t, hipEvent_t>** evp) {
     // persistent blocks, bundles advanced in time slices (k_advance_sliced)
-    int rc = next_event_pair(b, evp);
+    int rc = timed_launch(b, RTMI_LAUNCH_SLICED, sliced_steps(b), true, evp);
     if (rc) return rc;
-    auto* ev = *evp;
-    const int slice = sliced_steps(b);
-    const unsigned long long capacity = sliced_capacity(b, slice);
-    HIP_TRY(hipMemsetAsync(b->sliced_ctl, 0, (4 + capacity) * sizeof(unsigned long long), b->stream));
-    HIP_TRY(hipEventRecord(ev->first, b->stream));
-    OwnStream own;
-    { const int rco = own.enter(b); if (rco) return rco; }
-    if (b->p.dtype == RTMI_F64) launch_sliced<double>(b, slice, capacity);
-    else launch_sliced<float>(b, slice, capacity);
-    HIP_TRY(hipGetLastError());
-    if (b->rt) {       // critical rays: re-traced beside the launch
-        b->rt->pending = true;
-        const int rcd = retrace_drain(b, true);
-        if (rcd) return rcd;
-    }
-    { const int rco = own.leave(); if (rco) return rco; }
-    HIP_TRY(hipEventRecord(ev->second, b->stream));
-    b->launches++; b->total_launches++;
-    b->mode_used = RTMI_LAUNCH_SLICED;
     rc = read_counters(b);
     if (rc) return rc;
     if (b->h_counters[1] != 0) {   // every wait is bounded: a launch that gave one up reports here instead of hanging
@@ -2977,24 +2933,8 @@ RTMI_EXPORT int rtmi_run(rtmi_batch* b) {
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (b->p.launch_mode == RTMI_LAUNCH_REFILL) {
         // persistent waves with lane refill: one launch drains the ray queue
-        rc = next_event_pair(b, &ev);
+        rc = timed_launch(b, RTMI_LAUNCH_REFILL, 0, true, &ev);
         if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(b->counters + 2, 0, sizeof(unsigned long long), b->stream));   // refill queue head
-        HIP_TRY(hipEventRecord(ev->first, b->stream));
-        OwnStream own;
-        { const int rco = own.enter(b); if (rco) return rco; }
-        if (b->p.dtype == RTMI_F64) launch_refill<double>(b);
-        else launch_refill<float>(b);
-        HIP_TRY(hipGetLastError());
-        if (b->rt) {
-            b->rt->pending = true;
-            const int rcd = retrace_drain(b, true);
-            if (rcd) return rcd;
-        }
-        { const int rco = own.leave(); if (rco) return rco; }
-        HIP_TRY(hipEventRecord(ev->second, b->stream));
-        b->launches++; b->total_launches++;
-        b->mode_used = RTMI_LAUNCH_REFILL;
         return read_counters(b);
     }
     // per-ray DELTA_S or rays at rows of their own (the VAR build's cases) always run the plain launch
@@ -3379,8 +3319,7 @@ RTMI_EXPORT int rtmi_batch_stats(rtmi_batch* b, rtmi_stats* s) {
     hipFuncAttributes fa;
     s->vgprs = s->sgprs = s->lds_bytes = 0;
     s->launch_mode_used = (uint32_t)b->mode_used;
-    const void* kfn = b->mode_used == RTMI_LAUNCH_REFILL ? b->kfn_refill : (b->mode_used == RTMI_LAUNCH_SLICED && b->kfn_sliced) ? b->kfn_sliced : b->kfn;
-    if (hipFuncGetAttributes(&fa, kfn) == hipSuccess) { s->vgprs = fa.numRegs; s->lds_bytes = (uint32_t)fa.sharedSizeBytes; }
+    if (hipFuncGetAttributes(&fa, b->kfn_used) == hipSuccess) { s->vgprs = fa.numRegs; s->lds_bytes = (uint32_t)fa.sharedSizeBytes; }
     return RTMI_OK;
 }
 
