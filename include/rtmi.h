@@ -371,6 +371,65 @@ int rtmi_paraxial(rtmi_batch *b, const double line[3], int32_t kmax, int32_t *co
 int rtmi_field_eval_dgrad(const rtmi_field *f, int64_t npts, const double *x, const double *y, double *gx_x, double *gx_y,
                           double *gy_x, double *gy_y);
 
+/* First-arrival traveltime tables on a regular grid: the traveltime, and with it the launch angle, the direction and the
+ * amplitude, from each source to every node of a grid, out of recorded fans of rays (the ray-cell method).  DESIGN.md 11.
+ * The batch's R rays, in the caller's order, are S = R / fan_size fans of M = fan_size rays: rays [s M, (s+1) M) belong to source
+ * s, ordered by launch angle.  Node (ix, iy) is X = gx0 + ix gdx, Y = gy0 + iy gdy, computed in exactly that form.
+ *   Cells      adjacent rays m, m+1 and rows i, i+1 with 0 <= i < min(last_m, last_m+1) (last = the ray's last written row)
+ *              span cell (m, i) with corners A = (m, i), B = (m+1, i), C = (m, i+1), D = (m+1, i+1), split into the triangles
+ *              ABD (half 0) and ADC (half 1), taken as A D B and A C D: counter-clockwise in a fan ordered by increasing launch angle.
+ *   Gap rule   a cell is skipped when |P_B - P_A| or |P_D - P_C| exceeds max_gap, or |wrap(theta_B - theta_A)| or
+ *              |wrap(theta_D - theta_C)| exceeds max_dtheta (wrap(d) = d - 2 pi rint(d / 2 pi)): a fan that splits -- the interface's
+ *              critical angle parts reflected from transmitted rays -- is not smeared across the gap.
+ *   Triangles  zero signed area: skipped; negative (a fold, where arrivals multiply; every triangle of a fan ordered by
+ *              decreasing angle): re-oriented and kept.  With vertices
+ *              V0 V1 V2 counter-clockwise, the edge function of a -> b at p is (b - a) x (p - a), taken from the lexicographically
+ *              smaller endpoint (so that the two triangles sharing an edge get one value of opposite signs); the weights of p are
+ *              w0 = e(V1, V2, p), w1 = e(V2, V0, p), w2 = e(V0, V1, p).
+ *   Fill rule  p is covered when it lies in the triangle's closed bounding box and every w_k > 0, or w_k == 0 on a top-left edge
+ *              (b - a pointing down, or left when horizontal): within one unfolded sheet of triangles a node on a shared edge or
+ *              vertex is counted by exactly one triangle.
+ *   Values     f(p) = ((w0 f0 + w1 f1) + w2 f2) / ((w0 + w1) + w2) over the triangle's corners, for T, theta0 (the launch
+ *              angle), theta (corner k taken as theta_A + wrap(theta_k - theta_A)), ray = m + f(0 on A C, 1 on B D), step =
+ *              i + f(0 on row i, 1 on row i+1); with amplitude: J (rtmi_paraxial's, at every row), G = (n |J|)^-1/2 with J and
+ *              n = |(p_x, p_y)| of the rows interpolated, and kmah of the corner of the largest weight (the first on a tie).
+ *   Tie rule   the first arrival is the covering triangle of least T; among bit-equal T the least key (m rec_rows + i) 2 + half.
+ * Three passes with 64-bit atomics give the same bits in every schedule, launch mode, ray sorting and source grouping.
+ * Not covered (count 0, NaN): nodes beyond the shorter of two neighbouring rays' ends, nodes in gaps the rules reject, and
+ * caustics thinner than the fan's spacing (their branches are missed, and count is short).
+ *   count  [S][ny][nx]          covering triangles: the arrival branches (1 in a simple fan, 3 in a triplication)
+ *   out    [S][ncols][ny][nx]   T theta0 theta ray step (ncols 5), then J G kmah with amplitude (ncols 8); NaN where count is 0
+ * Host buffers, fp64, the caller's fan order; both dtypes (fp32 records are widened), every method.  Needs record_stride 1.
+ * RTMI_ERR_ARG before any device work: record_stride != 1, R % fan_size != 0, fan_size < 2, nx or ny < 1, gdx or gdy <= 0 or
+ * not finite, amplitude on op10 / op11 or gamma != 1 (rtmi_paraxial's rule).  RTMI_ERR_STATE: rtmi_paraxial's rule on
+ * rtmi_batch_set_state.  Rays handed over to the re-trace of critical rays are drained first.  The calling thread's current
+ * device must be the batch's. */
+typedef struct {
+    double gx0, gdx;         /* x of node 0 and the spacing (> 0) */
+    int64_t nx;              /* nodes along x (>= 1); nx ny <= 2^31 */
+    double gy0, gdy;
+    int64_t ny;
+    double max_gap;          /* 0: 8 max(gdx, gdy).  A cell wider than that is too coarse to interpolate over (the error of
+                                linear T grows as the square of its width), and it bounds each triangle's node loop */
+    double max_dtheta;       /* 0: 0.25 rad.  Neighbours of a dense fan turn by far less; a reflected ray and its transmitted
+                                neighbour at the interface's critical angle differ by more than 0.7 rad */
+    int32_t amplitude;       /* 1: also J G kmah (op1..op9, gamma 1) */
+    int32_t reserved0;
+    int64_t reserved[4];
+} rtmi_grid_params;
+typedef struct {
+    int64_t cells;           /* cells formed */
+    int64_t skipped_cells;   /* ... of which the gap rule skipped */
+    int64_t triangles;       /* triangles rasterized (non-zero area) */
+    int64_t folded;          /* ... of which re-oriented (negative area: folds) */
+    uint64_t atomics[3];     /* pass 1 count adds, pass 1 T minima, pass 2 key minima issued (the last two depend on the schedule) */
+    double pass_ms[3];       /* device time of each pass (HIP events) */
+    double max_gap, max_dtheta;   /* the values used */
+    double reserved[4];
+} rtmi_grid_stats;
+int rtmi_first_arrival_grid(rtmi_batch *b, int32_t fan_size, const rtmi_grid_params *gp, int32_t *count, double *out,
+                            rtmi_grid_stats *st);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */
@@ -481,6 +540,16 @@ int rtmi_debug_field_lookup(const rtmi_field *f, int64_t npts, const double *x, 
  * the next exploration run takes (RTMI_LAUNCH_SLICED / RTMI_LAUNCH_PLAIN; -1 once exploration is over), *decision = the schedule
  * that would be kept on these samples (medians; the plain launch only if more than 3 % ahead).  Either pointer may be NULL. */
 int rtmi_debug_auto_rule(const double *sliced_ms, int ns, const double *plain_ms, int np, int *next, int *decision);
+/* Diagnostic: J = n0 Q2 and kmah after every recorded row of every ray, as rtmi_first_arrival_grid's amplitude columns read them
+ * (rtmi_paraxial's kernel storing what it carries; the last row's J is at_end's J bit for bit).  J, kmah [rec_rows][R], host,
+ * the caller's ray order; NaN / -1 past each ray's last row.  rtmi_paraxial's argument and state rules. */
+int rtmi_debug_paraxial_rows(rtmi_batch *b, double *J, int32_t *kmah);
+/* Diagnostic: rtmi_first_arrival_grid's three kernels on caller-supplied rows, no batch: x, y, T, theta [rows][R] (host, fp64),
+ * last [R] (each ray's last row, < rows), theta0 [R].  For edge cases traced rays never hit exactly: nodes on shared edges, bit-equal
+ * ties, synthetic folds.  gp->amplitude must be 0; count and out as rtmi_first_arrival_grid (ncols 5); st may be NULL. */
+int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, const double *x, const double *y, const double *T,
+                         const double *theta, const int32_t *last, const double *theta0, const rtmi_grid_params *gp,
+                         int32_t *count, double *out, rtmi_grid_stats *st);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,18 @@ class TwoPointStats(C.Structure):
                 ("fan_ms", C.c_double), ("bracket_ms", C.c_double), ("refine_ms", C.c_double), ("reserved", C.c_double * 4)]
 
 
+class GridParams(C.Structure):
+    _fields_ = [("gx0", C.c_double), ("gdx", C.c_double), ("nx", C.c_int64), ("gy0", C.c_double), ("gdy", C.c_double),
+                ("ny", C.c_int64), ("max_gap", C.c_double), ("max_dtheta", C.c_double), ("amplitude", C.c_int32),
+                ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class GridStats(C.Structure):
+    _fields_ = [("cells", C.c_int64), ("skipped_cells", C.c_int64), ("triangles", C.c_int64), ("folded", C.c_int64),
+                ("atomics", C.c_uint64 * 3), ("pass_ms", C.c_double * 3), ("max_gap", C.c_double), ("max_dtheta", C.c_double),
+                ("reserved", C.c_double * 4)]
+
+
 # rtmi_arrival_status
 ARRIVAL_EMPTY, ARRIVAL_CONVERGED, ARRIVAL_STALLED, ARRIVAL_TRUNCATED = -1, 1, 2, 3
 
@@ -106,6 +118,7 @@ SYMBOLS = {
                                  C.POINTER(TwoPointParams), _ip, _ip, _dp, C.POINTER(TwoPointStats)]),
     "rtmi_paraxial": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, _dp, _dp]),
     "rtmi_field_eval_dgrad": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 6),
+    "rtmi_first_arrival_grid": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(GridParams), _ip, _dp, C.POINTER(GridStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),
@@ -123,6 +136,9 @@ SYMBOLS = {
     "rtmi_debug_sincos": (C.c_int, [C.c_int64, _dp, _dp, _dp]),
     "rtmi_debug_field_lookup": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 5),
     "rtmi_debug_auto_rule": (C.c_int, [_dp, C.c_int, _dp, C.c_int, _ip, _ip]),
+    "rtmi_debug_paraxial_rows": (C.c_int, [C.c_void_p, _dp, _ip]),
+    "rtmi_debug_grid_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [_ip, _dp, C.POINTER(GridParams), _ip, _dp,
+                                                                             C.POINTER(GridStats)]),
 }
 
 _lib = None

@@ -180,6 +180,8 @@ struct ParaxArgs {
     int32_t* count;             // [R] or NULL
     double* at_line;            // [kmax][7][R] (has_line)
     double* at_end;             // [7][R]
+    double* row_J;              // [rec_rows][R] or NULL: J after every row, slot order (rtmi_internal_paraxial_rows)
+    int32_t* row_kmah;          // [rec_rows][R], with row_J
 };
 
 // One lane per ray (slot k); answers in the caller's order.  A crossing of the line (the rule and tau* of rtmi_crossings) gets
@@ -207,6 +209,7 @@ template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
         double f0 = (L.a * x0 + L.b * y0) - L.c;
         Tube t{1.0, 0.0, 0.0, 1.0};
         int kmah = 0;
+        if (A.row_J) { A.row_J[k] = nsrc * t.q2; A.row_kmah[k] = 0; }
         // the next row's three loads go out a step ahead
         double xn = 0.0, yn = 0.0, tn = 0.0;
         if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; tn = (double)col[P + 5 * R]; }
@@ -239,6 +242,7 @@ template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
             const double q2 = t.q2;
             kdk(t, len, k0, k1, 0.5 * (w0 + w1));
             kmah += sign_change(q2, t.q2);
+            if (A.row_J) { A.row_J[(size_t)i * R + k] = nsrc * t.q2; A.row_kmah[(size_t)i * R + k] = kmah; }
             x0 = x1; y0 = y1; c0 = c1; s0 = s1; k0 = k1; w0 = w1; nl = f.n;
         }
         put(A.at_end, R, o, t, nsrc, nl, kmah);
@@ -308,7 +312,7 @@ RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax,
     PX_TRY(mem.get(&dc, R * sizeof(int32_t)));
     PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
     if (K) PX_TRY(mem.get(&dl, (size_t)K * kCols * R * sizeof(double)));
-    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L, line ? 1 : 0, K, dc, dl, de};
+    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr};
     const dim3 g((unsigned)((R + 255) / 256)), blk(256);
     if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
     else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
@@ -316,6 +320,68 @@ RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax,
     PX_TRY(hipMemcpy(at_end, de, (size_t)kCols * R * sizeof(double), hipMemcpyDeviceToHost));
     if (count) PX_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (K) PX_TRY(hipMemcpy(at_line, dl, (size_t)K * kCols * R * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// J = n0 Q2 and kmah after every recorded row of every ray, into DEVICE buffers of the batch's device ([rec_rows][R], slot order;
+// rows past a ray's last row are left as they were).  The J of a ray's last row is rtmi_paraxial's at_end J, bit for bit: the
+// same kernel with the same arithmetic, storing what it carries.  The checks are rtmi_paraxial's.
+int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah) {
+    const char* who = "rtmi_internal_paraxial_rows";
+    PX_ARG(b && row_J && row_kmah, "rtmi_internal_paraxial_rows: null");
+    const rtmi_field* f = nullptr;
+    rtmi_params p{};
+    int from_state = 0;
+    PX_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
+    PX_ARG(p.record_stride == 1, "amplitudes need the full trajectory (record_stride 1)");
+    PX_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
+           "amplitudes: isotropic media only (op1..op9, gamma 1): anisotropic dynamic ray tracing is another system");
+    if (from_state)
+        return rtmi_internal_fail(RTMI_ERR_STATE, "amplitudes: rtmi_batch_set_state gave rays a row other than 0: their rows "
+                                                  "before it are not a trajectory from the source (reset the batch)");
+    rtmi_internal_poly pv;
+    PX_RC(rtmi_internal_field_poly(f, &pv));
+    rtmi_device_view v;
+    PX_RC(rtmi_batch_view(b, &v));
+    PX_RC(rtmi_sync(b));
+    const size_t R = (size_t)v.R;
+    DevMem mem;
+    double* de = nullptr;
+    PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
+    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah};
+    const dim3 g((unsigned)((R + 255) / 256)), blk(256);
+    if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
+    else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
+    PX_TRY(hipGetLastError());
+    PX_TRY(hipDeviceSynchronize());
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_debug_paraxial_rows(rtmi_batch* b, double* J, int32_t* kmah) {
+    const char* who = "rtmi_debug_paraxial_rows";
+    PX_ARG(b && J && kmah, "rtmi_debug_paraxial_rows: null");
+    rtmi_device_view v;
+    PX_RC(rtmi_batch_view(b, &v));
+    const size_t R = (size_t)v.R, n = (size_t)v.rec_rows * R;
+    DevMem mem;
+    double* dj = nullptr;
+    int32_t* dk = nullptr;
+    PX_TRY(mem.get(&dj, n * sizeof(double)));
+    PX_TRY(mem.get(&dk, n * sizeof(int32_t)));
+    PX_TRY(hipMemset(dj, 0xff, n * sizeof(double)));
+    PX_TRY(hipMemset(dk, 0xff, n * sizeof(int32_t)));
+    PX_RC(rtmi_internal_paraxial_rows(b, dj, dk));
+    std::vector<double> hj(n);
+    std::vector<int32_t> hk(n), perm(v.perm ? R : 0);
+    PX_TRY(hipMemcpy(hj.data(), dj, n * sizeof(double), hipMemcpyDeviceToHost));
+    PX_TRY(hipMemcpy(hk.data(), dk, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (v.perm) PX_TRY(hipMemcpy(perm.data(), v.perm, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)v.rec_rows; i++)
+        for (size_t k = 0; k < R; k++) {
+            const size_t o = v.perm ? (size_t)perm[k] : k;
+            J[i * R + o] = hj[i * R + k];
+            kmah[i * R + o] = hk[i * R + k];
+        }
     return RTMI_OK;
 }
 

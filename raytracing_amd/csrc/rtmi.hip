@@ -2066,6 +2066,12 @@ int rtmi_internal_batch_info(rtmi_batch* b, const rtmi_field** f, rtmi_params* p
     return RTMI_OK;
 }
 
+int rtmi_internal_batch_rays(rtmi_batch* b, int64_t* R) {
+    ARG_TRY(b && R, "rtmi_internal_batch_rays: null");
+    *R = b->R;
+    return RTMI_OK;
+}
+
 // New launch angles (and optionally per-ray max_size) from device memory, then a reset.  The angles replace the batch's stored
 // launch conditions, so that the re-trace of critical rays (which restarts from b->launch) follows them.  Host code only: plain
 // device-to-device copies, which is why a sorted batch (perm) is refused.

@@ -31,3 +31,8 @@ int rtmi_internal_field_poly(const rtmi_field* f, rtmi_internal_poly* out);
 // A batch's field and parameters; *rows_from_state = 1 when rtmi_batch_set_state / restore_state gave any ray a state at a row
 // other than 0 since the last create / reset (its rows before that row are not a trajectory from its launch point).
 int rtmi_internal_batch_info(rtmi_batch* b, const rtmi_field** f, rtmi_params* p, int* rows_from_state);
+// A batch's ray count, host-side (no device work): for argument checks that come before any.
+int rtmi_internal_batch_rays(rtmi_batch* b, int64_t* R);
+// paraxial.hip: J = n0 Q2 and the caustic count after every recorded row, written to DEVICE buffers [rec_rows][R] (slot order)
+// by rtmi_paraxial's kernel; with rtmi_paraxial's checks.  For ttgrid.hip's amplitude columns.
+int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah);

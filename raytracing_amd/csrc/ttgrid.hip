@@ -1,0 +1,477 @@
+// ttgrid.hip -- first-arrival traveltime (and amplitude) tables on a regular grid from recorded fans of rays
+// (rtmi_first_arrival_grid, rtmi_debug_grid_rows): the ray-cell method.  DESIGN.md section 11.
+//
+// Adjacent rays m, m+1 of one fan and rows i, i+1 span the cell (m, i) with corners A = (m, i), B = (m+1, i), C = (m, i+1),
+// D = (m+1, i+1); it is split into the triangles ABD (half 0) and ADC (half 1), over which T, the launch angle, the direction
+// and the spread are linear.  Every grid node keeps the smallest T of the triangles that cover it, in three passes that give
+// the same bits in every schedule: (1) rasterize, atomicMin on the bits of T (T >= 0: the IEEE order is the integer order) and
+// count the covering triangles; (2) rasterize again, and where a triangle's T bits equal the node's minimum, atomicMin on the
+// triangle's key (m rec_rows + i) 2 + half; (3) one lane per node decodes the winning key and evaluates the columns with the
+// function that gave T in pass 1.  Each atomicMin is preceded by a plain load and skipped when it cannot win.
+//
+// One lane per cell column (source s, ray pair m, m+1) walks the rows of both rays, each row's x, y, T, theta read once per
+// lane (the neighbouring lane reads the same lines).  Arithmetic is fp64 in one fixed order (-ffp-contract=off), so that
+// tests/ttgrid_ref.py, a numpy restatement, follows it operation for operation.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/rtmi.h"
+#include "rtmi_internal.h"
+
+#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
+#define TG_TRY(expr)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+#define TG_ARG(cond, msg)                                                    \
+    do {                                                                     \
+        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
+    } while (0)
+#define TG_RC(expr)                  \
+    do {                             \
+        const int rc_ = (expr);      \
+        if (rc_) return rc_;         \
+    } while (0)
+
+namespace {
+
+constexpr int kColsT = 5;                   // T theta0 theta ray step
+constexpr int kColsA = 8;                   // ... J G kmah
+constexpr double kTwoPi = 6.283185307179586;
+constexpr unsigned long long kEmpty = ~0ull;
+// the defaults of rtmi_grid_params (include/rtmi.h says why)
+constexpr double kGapCells = 8.0;
+constexpr double kDtheta = 0.25;
+
+// stats counters (device, uint64): cells, skipped, triangles, folded, pass-1 adds, pass-1 mins, pass-2 mins
+enum { C_CELLS, C_SKIP, C_TRI, C_FOLD, C_ADD1, C_MIN1, C_MIN2, C_N };
+
+struct Grid {
+    double gx0, gdx, gy0, gdy;
+    int nx, ny;
+    double max_gap, max_dtheta;
+    double inv_gdx, inv_gdy;    // for the cell pre-test only (cell_has_node); every node test is exact
+};
+
+struct Rec {
+    const void* s_ray;          // [rec_rows][6][R] of T: x, y, p_x, p_y, T, theta
+    const int32_t* istep;       // [R] last written row (slot order)
+    const int32_t* slot;        // [R] or NULL: slot of the caller's ray o (the inverse of rtmi_device_view.perm)
+    const double* theta0;       // [R] caller order, or NULL: row 0's theta
+    const double* row_J;        // [rec_rows][R] slot order, or NULL (no amplitude)
+    const int32_t* row_kmah;
+    long R, rec_rows;
+    int M, S;
+};
+
+struct Nodes {
+    unsigned long long* tmin;   // [S][ny][nx]
+    unsigned long long* key;
+    int32_t* count;
+    unsigned long long* ctr;    // [C_N]
+};
+
+struct V2 { double x, y; };
+struct Corner { double x, y, t, th; };
+
+template <typename T> __device__ __forceinline__ Corner corner(const Rec& r, long k, long i) {
+    const T* p = reinterpret_cast<const T*>(r.s_ray) + (size_t)i * 6 * r.R + k;
+    return Corner{(double)p[0], (double)p[r.R], (double)p[4 * r.R], (double)p[5 * r.R]};
+}
+
+__device__ __forceinline__ double wrap(double d) { return d - kTwoPi * rint(d / kTwoPi); }
+
+// cross(b - a, p - a), anchored at the lexicographically smaller endpoint: edge(b, a, p) == -edge(a, b, p) bit for bit, so
+// that two triangles sharing an edge see one value with opposite signs
+__device__ __forceinline__ double edge(V2 a, V2 b, V2 p) {
+    if (a.x < b.x || (a.x == b.x && a.y < b.y)) return (b.x - a.x) * (p.y - a.y) - (b.y - a.y) * (p.x - a.x);
+    return -((a.x - b.x) * (p.y - b.y) - (a.y - b.y) * (p.x - b.x));
+}
+// the top-left rule of a counter-clockwise triangle (y up): an edge whose direction points down, or left when horizontal
+__device__ __forceinline__ bool top_left(V2 a, V2 b) {
+    const double dy = b.y - a.y;
+    return dy < 0.0 || (dy == 0.0 && b.x - a.x < 0.0);
+}
+
+// One triangle of a cell: its vertices v[0..2] counter-clockwise and which cell corner (0 A, 1 B, 2 C, 3 D) each one is.
+struct Tri {
+    V2 v[3];
+    int c[3];
+    double xmin, xmax, ymin, ymax;
+    int folded;
+};
+// half 0: triangle ABD taken as A D B, half 1: ADC taken as A C D -- counter-clockwise in a fan whose rays are ordered by
+// increasing launch angle.  false: zero signed area (skipped); a negative area (a fold) is re-oriented
+__device__ __forceinline__ bool tri_setup(const V2 q[4], int half, Tri& t) {
+    t.c[0] = 0; t.c[1] = half ? 2 : 3; t.c[2] = half ? 3 : 1;
+    t.v[0] = q[t.c[0]]; t.v[1] = q[t.c[1]]; t.v[2] = q[t.c[2]];
+    const double a = edge(t.v[0], t.v[1], t.v[2]);
+    if (a == 0.0 || !(a == a)) return false;
+    t.folded = a < 0.0;
+    if (t.folded) {
+        const V2 v = t.v[1]; t.v[1] = t.v[2]; t.v[2] = v;
+        const int c = t.c[1]; t.c[1] = t.c[2]; t.c[2] = c;
+    }
+    t.xmin = fmin(fmin(t.v[0].x, t.v[1].x), t.v[2].x); t.xmax = fmax(fmax(t.v[0].x, t.v[1].x), t.v[2].x);
+    t.ymin = fmin(fmin(t.v[0].y, t.v[1].y), t.v[2].y); t.ymax = fmax(fmax(t.v[0].y, t.v[1].y), t.v[2].y);
+    return true;
+}
+// Barycentric weights (unnormalised) of p; true when p is inside the closed bounding box and inside the triangle by the
+// top-left rule: w_k >= 0 for the edge opposite vertex k, with equality only on a top or left edge
+__device__ __forceinline__ bool tri_weights(const Tri& t, V2 p, double w[3]) {
+    if (p.x < t.xmin || p.x > t.xmax || p.y < t.ymin || p.y > t.ymax) return false;
+    w[0] = edge(t.v[1], t.v[2], p);
+    w[1] = edge(t.v[2], t.v[0], p);
+    w[2] = edge(t.v[0], t.v[1], p);
+    const bool i0 = w[0] > 0.0 || (w[0] == 0.0 && top_left(t.v[1], t.v[2]));
+    const bool i1 = w[1] > 0.0 || (w[1] == 0.0 && top_left(t.v[2], t.v[0]));
+    const bool i2 = w[2] > 0.0 || (w[2] == 0.0 && top_left(t.v[0], t.v[1]));
+    return i0 && i1 && i2;
+}
+// the linear interpolant: ((w0 f0 + w1 f1) + w2 f2) / ((w0 + w1) + w2)
+__device__ __forceinline__ double interp(const double w[3], double f0, double f1, double f2) {
+    return ((w[0] * f0 + w[1] * f1) + w[2] * f2) / ((w[0] + w[1]) + w[2]);
+}
+
+__device__ __forceinline__ V2 node_xy(const Grid& g, int ix, int iy) { return V2{g.gx0 + (double)ix * g.gdx, g.gy0 + (double)iy * g.gdy}; }
+// the node index range that can hold [lo, hi] (one node of margin; the exact test is tri_weights' bounding box)
+__device__ __forceinline__ void node_range(double lo, double hi, double o, double h, int n, int& a, int& b) {
+    double fa = floor((lo - o) / h) - 1.0, fb = ceil((hi - o) / h) + 1.0;
+    fa = fa < 0.0 ? 0.0 : (fa > (double)n ? (double)n : fa);
+    fb = fb > (double)(n - 1) ? (double)(n - 1) : (fb < -1.0 ? -1.0 : fb);
+    a = (int)fa; b = (int)fb;
+}
+
+// the cell rule: both rays present at rows i and i+1 (the caller's loop), neighbours no further apart than max_gap at either
+// row, and turned against each other by no more than max_dtheta
+__device__ __forceinline__ bool cell_ok(const Grid& g, const Corner& a, const Corner& b, const Corner& c, const Corner& d) {
+    const double dx0 = b.x - a.x, dy0 = b.y - a.y, dx1 = d.x - c.x, dy1 = d.y - c.y;
+    if (!(sqrt(dx0 * dx0 + dy0 * dy0) <= g.max_gap) || !(sqrt(dx1 * dx1 + dy1 * dy1) <= g.max_gap)) return false;
+    return fabs(wrap(b.th - a.th)) <= g.max_dtheta && fabs(wrap(d.th - c.th)) <= g.max_dtheta;
+}
+
+// Can [lo, hi] hold a node coordinate o + i h, 0 <= i < n?  Conservative by 1e-6 of a spacing (far above the rounding of o + i h):
+// a false answer is exact, so skipping the cell's node loops changes no result.  No division: most cells of a dense fan hold no node.
+__device__ __forceinline__ bool axis_has_node(double lo, double hi, double o, double inv, int n) {
+    const double a = ceil((lo - o) * inv - 1e-6), b = floor((hi - o) * inv + 1e-6);
+    return a <= b && b >= 0.0 && a <= (double)(n - 1);
+}
+__device__ __forceinline__ bool cell_has_node(const Grid& g, const V2 q[4]) {
+    const double xl = fmin(fmin(q[0].x, q[1].x), fmin(q[2].x, q[3].x)), xh = fmax(fmax(q[0].x, q[1].x), fmax(q[2].x, q[3].x));
+    if (!axis_has_node(xl, xh, g.gx0, g.inv_gdx, g.nx)) return false;
+    const double yl = fmin(fmin(q[0].y, q[1].y), fmin(q[2].y, q[3].y)), yh = fmax(fmax(q[0].y, q[1].y), fmax(q[2].y, q[3].y));
+    return axis_has_node(yl, yh, g.gy0, g.inv_gdy, g.ny);
+}
+
+__device__ __forceinline__ long last_row(const Rec& r, long k) {
+    const long l = r.istep[k];
+    return l < r.rec_rows - 1 ? l : r.rec_rows - 1;
+}
+__device__ __forceinline__ long slot_of(const Rec& r, long o) { return r.slot ? (long)r.slot[o] : o; }
+
+__device__ __forceinline__ void block_add(unsigned long long* acc, int q, unsigned long long v) {
+    if (v) atomicAdd(&acc[q], v);
+}
+
+// Passes 1 and 2: one lane per (source, ray pair).  pass 1: T minimum and count; pass 2: the key of the winner.
+template <typename T> __global__ void k_raster(Grid g, Rec r, Nodes nd, int pass) {
+    __shared__ unsigned long long acc[C_N];
+    if (threadIdx.x < C_N) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long pairs = (long)r.M - 1;
+    unsigned long long n_cells = 0, n_skip = 0, n_tri = 0, n_fold = 0, n_add = 0, n_min = 0;
+    if (lane < (long)r.S * pairs) {
+        const long s = lane / pairs, m = lane - s * pairs;
+        const long o = s * r.M + m;
+        const long k0 = slot_of(r, o), k1 = slot_of(r, o + 1);
+        const long l0 = last_row(r, k0), l1 = last_row(r, k1);
+        const long L = l0 < l1 ? l0 : l1;
+        const size_t base = (size_t)s * g.ny * g.nx;
+        Corner A = corner<T>(r, k0, 0), B = corner<T>(r, k1, 0);
+        for (long i = 0; i < L; i++) {
+            const Corner C = corner<T>(r, k0, i + 1), D = corner<T>(r, k1, i + 1);
+            n_cells++;
+            if (!cell_ok(g, A, B, C, D)) {
+                n_skip++;
+            } else {
+                const V2 q[4] = {{A.x, A.y}, {B.x, B.y}, {C.x, C.y}, {D.x, D.y}};
+                const double tq[4] = {A.t, B.t, C.t, D.t};
+                const bool nodes = cell_has_node(g, q);
+                for (int half = 0; half < 2; half++) {
+                    Tri t;
+                    if (!tri_setup(q, half, t)) continue;
+                    n_tri++;
+                    n_fold += t.folded;
+                    if (!nodes) continue;
+                    const unsigned long long key = ((unsigned long long)(m * r.rec_rows + i) << 1) | (unsigned long long)half;
+                    int x0, x1, y0, y1;
+                    node_range(t.xmin, t.xmax, g.gx0, g.gdx, g.nx, x0, x1);
+                    node_range(t.ymin, t.ymax, g.gy0, g.gdy, g.ny, y0, y1);
+                    for (int iy = y0; iy <= y1; iy++)
+                        for (int ix = x0; ix <= x1; ix++) {
+                            double w[3];
+                            if (!tri_weights(t, node_xy(g, ix, iy), w)) continue;
+                            const double tv = interp(w, tq[t.c[0]], tq[t.c[1]], tq[t.c[2]]);
+                            if (!(tv >= 0.0 && tv < INFINITY)) continue;
+                            const unsigned long long bits = (unsigned long long)__double_as_longlong(tv);
+                            const size_t at = base + (size_t)iy * g.nx + ix;
+                            if (pass == 1) {
+                                atomicAdd(&nd.count[at], 1);
+                                n_add++;
+                                if (bits < __hip_atomic_load(&nd.tmin[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                                    atomicMin(&nd.tmin[at], bits);
+                                    n_min++;
+                                }
+                            } else if (bits == __hip_atomic_load(&nd.tmin[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &&
+                                       key < __hip_atomic_load(&nd.key[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                                atomicMin(&nd.key[at], key);
+                                n_min++;
+                            }
+                        }
+                }
+            }
+            A = C; B = D;
+        }
+    }
+    if (pass == 1) {
+        block_add(acc, C_CELLS, n_cells); block_add(acc, C_SKIP, n_skip); block_add(acc, C_TRI, n_tri);
+        block_add(acc, C_FOLD, n_fold); block_add(acc, C_ADD1, n_add); block_add(acc, C_MIN1, n_min);
+    } else {
+        block_add(acc, C_MIN2, n_min);
+    }
+    __syncthreads();
+    if (threadIdx.x < C_N && acc[threadIdx.x]) atomicAdd(&nd.ctr[threadIdx.x], acc[threadIdx.x]);
+}
+
+// Pass 3: one lane per node.  out[s][col][ny][nx]; NaN where no triangle covers the node.
+template <typename T> __global__ void k_columns(Grid g, Rec r, Nodes nd, double* out, int ncols) {
+    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)g.nx * g.ny;
+    if (id >= (long)r.S * per) return;
+    const long s = id / per, at = id - s * per;
+    const int iy = (int)(at / g.nx), ix = (int)(at - (long)iy * g.nx);
+    double* o = out + (size_t)s * ncols * per + at;
+    const unsigned long long key = nd.key[id];
+    if (nd.count[id] == 0 || key == kEmpty) {
+        for (int q = 0; q < ncols; q++) o[(size_t)q * per] = NAN;
+        return;
+    }
+    const int half = (int)(key & 1ull);
+    const long m = (long)((key >> 1) / (unsigned long long)r.rec_rows), i = (long)((key >> 1) - (unsigned long long)m * r.rec_rows);
+    const long oa = s * r.M + m;
+    const long k[4] = {slot_of(r, oa), slot_of(r, oa + 1), slot_of(r, oa), slot_of(r, oa + 1)};
+    const long row[4] = {i, i, i + 1, i + 1};
+    Corner c4[4];
+    for (int q = 0; q < 4; q++) c4[q] = corner<T>(r, k[q], row[q]);
+    const V2 q4[4] = {{c4[0].x, c4[0].y}, {c4[1].x, c4[1].y}, {c4[2].x, c4[2].y}, {c4[3].x, c4[3].y}};
+    Tri t;
+    tri_setup(q4, half, t);
+    double w[3];
+    tri_weights(t, node_xy(g, ix, iy), w);
+    const int a = t.c[0], b = t.c[1], c = t.c[2];
+    double th0[4];
+    for (int q = 0; q < 4; q++)
+        th0[q] = r.theta0 ? r.theta0[oa + (q & 1)] : (double)reinterpret_cast<const T*>(r.s_ray)[5 * r.R + k[q]];
+    double thu[4];
+    for (int q = 0; q < 4; q++) thu[q] = c4[0].th + wrap(c4[q].th - c4[0].th);
+    const double fr[4] = {0.0, 1.0, 0.0, 1.0}, fs[4] = {0.0, 0.0, 1.0, 1.0};
+    o[0] = interp(w, c4[a].t, c4[b].t, c4[c].t);
+    o[per] = interp(w, th0[a], th0[b], th0[c]);
+    o[2 * per] = interp(w, thu[a], thu[b], thu[c]);
+    o[3 * per] = (double)m + interp(w, fr[a], fr[b], fr[c]);
+    o[4 * per] = (double)i + interp(w, fs[a], fs[b], fs[c]);
+    if (ncols == kColsA) {
+        double J[4], n[4];
+        int km[4];
+        for (int q = 0; q < 4; q++) {
+            J[q] = r.row_J[(size_t)row[q] * r.R + k[q]];
+            km[q] = r.row_kmah[(size_t)row[q] * r.R + k[q]];
+            const T* p = reinterpret_cast<const T*>(r.s_ray) + (size_t)row[q] * 6 * r.R + k[q];
+            const double px = (double)p[2 * r.R], py = (double)p[3 * r.R];
+            n[q] = sqrt(px * px + py * py);
+        }
+        const double Jn = interp(w, J[a], J[b], J[c]);
+        const double nn = interp(w, n[a], n[b], n[c]);
+        // kmah: the corner of the largest weight (the first in a, b, c on a tie)
+        const int kk = w[0] >= w[1] ? (w[0] >= w[2] ? a : c) : (w[1] >= w[2] ? b : c);
+        o[5 * per] = Jn;
+        o[6 * per] = 1.0 / sqrt(nn * fabs(Jn));
+        o[7 * per] = (double)km[kk];
+    }
+}
+
+__global__ void k_inverse(const int32_t* perm, int32_t* slot, long R) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < R) slot[perm[k]] = (int32_t)k;
+}
+
+// device allocations of one call, freed on every way out
+struct DevMem {
+    std::vector<void*> p;
+    template <typename T> hipError_t get(T** out, size_t bytes) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
+        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
+        return e;
+    }
+    ~DevMem() { for (void* v : p) (void)hipFree(v); }
+};
+struct Events {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
+};
+
+// the grid parameters checked and the defaults filled in (host)
+int grid_of(const rtmi_grid_params* gp, const char* who, Grid* g) {
+    TG_ARG(gp, (std::string(who) + ": null grid parameters").c_str());
+    TG_ARG(gp->nx >= 1 && gp->ny >= 1, (std::string(who) + ": nx and ny must be >= 1").c_str());
+    TG_ARG((double)gp->nx * (double)gp->ny <= (double)(1L << 31), (std::string(who) + ": more than 2^31 nodes per source").c_str());
+    TG_ARG(gp->gdx > 0.0 && gp->gdy > 0.0 && std::isfinite(gp->gdx) && std::isfinite(gp->gdy),
+           (std::string(who) + ": gdx and gdy must be finite and > 0").c_str());
+    TG_ARG(std::isfinite(gp->gx0) && std::isfinite(gp->gy0), (std::string(who) + ": gx0 and gy0 must be finite").c_str());
+    TG_ARG(gp->max_gap >= 0.0 && std::isfinite(gp->max_gap) && gp->max_dtheta >= 0.0 && std::isfinite(gp->max_dtheta),
+           (std::string(who) + ": max_gap and max_dtheta must be finite and >= 0").c_str());
+    TG_ARG(gp->amplitude == 0 || gp->amplitude == 1, (std::string(who) + ": amplitude must be 0 or 1").c_str());
+    *g = Grid{gp->gx0, gp->gdx, gp->gy0, gp->gdy, (int)gp->nx, (int)gp->ny,
+              gp->max_gap > 0.0 ? gp->max_gap : kGapCells * (gp->gdx > gp->gdy ? gp->gdx : gp->gdy),
+              gp->max_dtheta > 0.0 ? gp->max_dtheta : kDtheta, 1.0 / gp->gdx, 1.0 / gp->gdy};
+    return RTMI_OK;
+}
+
+// The three passes on a record already on the device (r's pointers), results to the host.
+int run_grid(const char* who, int dtype, const Grid& g, Rec r, int32_t* count, double* out, rtmi_grid_stats* st) {
+    const size_t per = (size_t)g.nx * g.ny, nodes = per * (size_t)r.S;
+    const int ncols = r.row_J ? kColsA : kColsT;
+    DevMem mem;
+    Nodes nd{};
+    double* dout = nullptr;
+    TG_TRY(mem.get(&nd.tmin, nodes * sizeof(unsigned long long)));
+    TG_TRY(mem.get(&nd.key, nodes * sizeof(unsigned long long)));
+    TG_TRY(mem.get(&nd.count, nodes * sizeof(int32_t)));
+    TG_TRY(mem.get(&nd.ctr, C_N * sizeof(unsigned long long)));
+    TG_TRY(mem.get(&dout, nodes * ncols * sizeof(double)));
+    TG_TRY(hipMemset(nd.tmin, 0xff, nodes * sizeof(unsigned long long)));
+    TG_TRY(hipMemset(nd.key, 0xff, nodes * sizeof(unsigned long long)));
+    TG_TRY(hipMemset(nd.count, 0, nodes * sizeof(int32_t)));
+    TG_TRY(hipMemset(nd.ctr, 0, C_N * sizeof(unsigned long long)));
+    Events ev;
+    for (hipEvent_t& e : ev.e) TG_TRY(hipEventCreate(&e));
+    const long lanes = (long)r.S * (r.M - 1);
+    const dim3 blk(256), gl((unsigned)((lanes + 255) / 256)), gn((unsigned)((nodes + 255) / 256));
+    TG_TRY(hipEventRecord(ev.e[0], nullptr));
+    for (int pass = 1; pass <= 2; pass++) {
+        if (lanes > 0) {
+            if (dtype == RTMI_F64) hipLaunchKernelGGL(k_raster<double>, gl, blk, 0, nullptr, g, r, nd, pass);
+            else hipLaunchKernelGGL(k_raster<float>, gl, blk, 0, nullptr, g, r, nd, pass);
+            TG_TRY(hipGetLastError());
+        }
+        TG_TRY(hipEventRecord(ev.e[pass], nullptr));
+    }
+    if (dtype == RTMI_F64) hipLaunchKernelGGL(k_columns<double>, gn, blk, 0, nullptr, g, r, nd, dout, ncols);
+    else hipLaunchKernelGGL(k_columns<float>, gn, blk, 0, nullptr, g, r, nd, dout, ncols);
+    TG_TRY(hipGetLastError());
+    TG_TRY(hipEventRecord(ev.e[3], nullptr));
+    TG_TRY(hipEventSynchronize(ev.e[3]));
+    TG_TRY(hipMemcpy(count, nd.count, nodes * sizeof(int32_t), hipMemcpyDeviceToHost));
+    TG_TRY(hipMemcpy(out, dout, nodes * ncols * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        unsigned long long c[C_N];
+        TG_TRY(hipMemcpy(c, nd.ctr, sizeof(c), hipMemcpyDeviceToHost));
+        *st = rtmi_grid_stats{};
+        st->cells = (int64_t)c[C_CELLS]; st->skipped_cells = (int64_t)c[C_SKIP];
+        st->triangles = (int64_t)c[C_TRI]; st->folded = (int64_t)c[C_FOLD];
+        st->atomics[0] = c[C_ADD1]; st->atomics[1] = c[C_MIN1]; st->atomics[2] = c[C_MIN2];
+        st->max_gap = g.max_gap; st->max_dtheta = g.max_dtheta;
+        for (int q = 0; q < 3; q++) {
+            float ms = 0.0f;
+            TG_TRY(hipEventElapsedTime(&ms, ev.e[q], ev.e[q + 1]));
+            st->pass_ms[q] = ms;
+        }
+    }
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_first_arrival_grid(rtmi_batch* b, int32_t fan_size, const rtmi_grid_params* gp, int32_t* count, double* out,
+                                        rtmi_grid_stats* st) {
+    const char* who = "rtmi_first_arrival_grid";
+    TG_ARG(b && count && out, "rtmi_first_arrival_grid: null");
+    Grid g;
+    TG_RC(grid_of(gp, who, &g));
+    TG_ARG(fan_size >= 2, "rtmi_first_arrival_grid: fan_size must be >= 2");
+    const rtmi_field* f = nullptr;
+    rtmi_params p{};
+    int from_state = 0;
+    TG_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
+    TG_ARG(p.record_stride == 1, "rtmi_first_arrival_grid: needs the full trajectory (record_stride 1)");
+    if (gp->amplitude)
+        TG_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
+               "rtmi_first_arrival_grid: amplitude needs an isotropic medium (op1..op9, gamma 1), as rtmi_paraxial");
+    if (from_state)
+        return rtmi_internal_fail(RTMI_ERR_STATE, "rtmi_first_arrival_grid: rtmi_batch_set_state gave rays a row other than 0: "
+                                                  "their rows before it are not a trajectory from the source (reset the batch)");
+    int64_t nrays = 0;
+    TG_RC(rtmi_internal_batch_rays(b, &nrays));
+    TG_ARG(nrays % fan_size == 0, "rtmi_first_arrival_grid: the batch's ray count is not a multiple of fan_size");
+    rtmi_device_view v;
+    TG_RC(rtmi_batch_view(b, &v));          // drains the rays handed over to the re-trace of critical rays
+    TG_RC(rtmi_sync(b));
+    const size_t R = (size_t)v.R;
+    DevMem mem;
+    int32_t* slot = nullptr;
+    double* rj = nullptr;
+    int32_t* rk = nullptr;
+    if (v.perm) {
+        TG_TRY(mem.get(&slot, R * sizeof(int32_t)));
+        hipLaunchKernelGGL(k_inverse, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, nullptr, v.perm, slot, (long)R);
+        TG_TRY(hipGetLastError());
+    }
+    if (gp->amplitude) {
+        const size_t cells = (size_t)v.rec_rows * R;
+        TG_TRY(mem.get(&rj, cells * sizeof(double)));
+        TG_TRY(mem.get(&rk, cells * sizeof(int32_t)));
+        TG_TRY(hipMemset(rj, 0xff, cells * sizeof(double)));         // NaN (and kmah -1) on rows no ray reaches
+        TG_TRY(hipMemset(rk, 0xff, cells * sizeof(int32_t)));
+        TG_RC(rtmi_internal_paraxial_rows(b, rj, rk));
+    }
+    const Rec r{v.s_ray, v.istep, slot, nullptr, rj, rk, (long)v.R, (long)v.rec_rows, (int)fan_size, (int)(v.R / fan_size)};
+    return run_grid(who, v.dtype, g, r, count, out, st);
+}
+
+RTMI_EXPORT int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, const double* x, const double* y, const double* T,
+                                     const double* theta, const int32_t* last, const double* theta0, const rtmi_grid_params* gp,
+                                     int32_t* count, double* out, rtmi_grid_stats* st) {
+    const char* who = "rtmi_debug_grid_rows";
+    TG_ARG(x && y && T && theta && last && theta0 && count && out, "rtmi_debug_grid_rows: null");
+    Grid g;
+    TG_RC(grid_of(gp, who, &g));
+    TG_ARG(!gp->amplitude, "rtmi_debug_grid_rows: no amplitude on caller-supplied rows");
+    TG_ARG(rows >= 1 && R >= 2, "rtmi_debug_grid_rows: rows >= 1 and R >= 2");
+    TG_ARG(fan_size >= 2 && R % fan_size == 0, "rtmi_debug_grid_rows: R must be a multiple of fan_size >= 2");
+    for (int32_t k = 0; k < R; k++) TG_ARG(last[k] >= 0 && last[k] < rows, "rtmi_debug_grid_rows: last must lie in [0, rows)");
+    const size_t n = (size_t)rows * R;
+    std::vector<double> rec(6 * n, 0.0);
+    for (size_t i = 0; i < (size_t)rows; i++)
+        for (size_t k = 0; k < (size_t)R; k++) {
+            const size_t a = i * R + k, d = i * 6 * R + k;
+            rec[d] = x[a]; rec[d + R] = y[a]; rec[d + 4 * R] = T[a]; rec[d + 5 * R] = theta[a];
+        }
+    DevMem mem;
+    double *drec = nullptr, *dth0 = nullptr;
+    int32_t* dlast = nullptr;
+    TG_TRY(mem.get(&drec, rec.size() * sizeof(double)));
+    TG_TRY(mem.get(&dth0, (size_t)R * sizeof(double)));
+    TG_TRY(mem.get(&dlast, (size_t)R * sizeof(int32_t)));
+    TG_TRY(hipMemcpy(drec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+    TG_TRY(hipMemcpy(dth0, theta0, (size_t)R * sizeof(double), hipMemcpyHostToDevice));
+    TG_TRY(hipMemcpy(dlast, last, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice));
+    const Rec r{drec, dlast, nullptr, dth0, nullptr, nullptr, (long)R, (long)rows, (int)fan_size, (int)(R / fan_size)};
+    return run_grid(who, RTMI_F64, g, r, count, out, st);
+}

@@ -453,6 +453,25 @@ class Batch:
         d["at_line"] = {k: at[:, q].copy() for q, k in enumerate(PARAXIAL_FIELDS)}
         return d
 
+    def first_arrival_grid(self, grid, fan_size=None, max_gap=None, max_dtheta=None, amplitude=False, stats=False):
+        """First-arrival traveltime table on a regular grid from the recorded fans (rtmi_first_arrival_grid): the batch's rays
+        are R / fan_size fans of fan_size rays each (default: one fan), ordered by launch angle.  grid = (gx0, gdx, nx, gy0,
+        gdy, ny): node (ix, iy) at (gx0 + ix gdx, gy0 + iy gdy).  max_gap / max_dtheta: the gap rule (None: the library's
+        defaults, 8 grid spacings and 0.25 rad).  Returns a dict of [S, ny, nx] arrays: count (arrival branches covering the
+        node) and T, theta0, theta, ray, step of the first arrival (NaN where count is 0); with amplitude=True also J, G, kmah
+        (op1..op9, gamma 1); with stats=True also 'stats'.  Needs record_stride 1."""
+        M = self.R if fan_size is None else int(fan_size)
+        return _grid_call(lambda gp, cnt, out, st: lib().rtmi_first_arrival_grid(self._h, M, gp, cnt, out, st),
+                          self.R // M if M >= 1 else 0, grid, max_gap, max_dtheta, amplitude, stats)
+
+    def paraxial_rows(self):
+        """J and kmah after every recorded row ([rec_rows, R] each; NaN / -1 past a ray's end): rtmi_debug_paraxial_rows."""
+        v = self.view()
+        J = np.empty((int(v.rec_rows), self.R))
+        km = np.empty((int(v.rec_rows), self.R), dtype=np.int32)
+        check(lib().rtmi_debug_paraxial_rows(self._h, dptr(J), km.ctypes.data_as(_lib._ip)))
+        return J, km
+
     def wavefronts(self, times, nfine=100):
         """The reference's wavefront extraction (RT_bench.py:1005-1044) on the device: one dict per traveltime with the
         points of the wavefront sorted by y -- 'y', 'x', 'angle' (ray angle), 'dxdy' (derivative of the PCHIP interpolant
@@ -708,6 +727,116 @@ def _two_point_paraxial(field, p, sx, sy, line, arr, kmax):
             raise RuntimeError(f"two_point: no crossing of the re-traced ray matches arrival {(s_, j, a)}")
         for k in keys:
             res[k][s_, j, a] = at[hit[0], PARAXIAL_FIELDS.index(k), r]
+    return res
+
+
+GRID_FIELDS = ("T", "theta0", "theta", "ray", "step")                            # rtmi_first_arrival_grid's out columns
+GRID_AMPLITUDE_FIELDS = ("J", "G", "kmah")                                       # ... and with amplitude
+
+
+def grid_params(grid, max_gap=None, max_dtheta=None, amplitude=False):
+    """rtmi_grid_params of grid = (gx0, gdx, nx, gy0, gdy, ny); None / 0 take the library's defaults"""
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    gp = _lib.GridParams()
+    gp.gx0 = float(gx0); gp.gdx = float(gdx); gp.nx = int(nx)
+    gp.gy0 = float(gy0); gp.gdy = float(gdy); gp.ny = int(ny)
+    gp.max_gap = float(max_gap or 0.0); gp.max_dtheta = float(max_dtheta or 0.0)
+    gp.amplitude = int(bool(amplitude))
+    return gp
+
+
+def _grid_call(call, S, grid, max_gap, max_dtheta, amplitude, stats):
+    gp = grid_params(grid, max_gap, max_dtheta, amplitude)
+    names = GRID_FIELDS + (GRID_AMPLITUDE_FIELDS if amplitude else ())
+    nx, ny = max(int(gp.nx), 0), max(int(gp.ny), 0)
+    count = np.zeros((max(S, 0), ny, nx), dtype=np.int32)
+    out = np.empty((max(S, 0), len(names), ny, nx))
+    st = _lib.GridStats()
+    check(call(C.byref(gp), count.ctypes.data_as(_lib._ip), dptr(out), C.byref(st)))
+    d = {"count": count}
+    for q, k in enumerate(names):
+        d[k] = out[:, q].copy()
+    if stats:
+        d["stats"] = grid_stats(st)
+    return d
+
+
+def grid_stats(st):
+    return {"cells": st.cells, "skipped_cells": st.skipped_cells, "triangles": st.triangles, "folded": st.folded,
+            "atomics": [int(v) for v in st.atomics], "pass_ms": [float(v) for v in st.pass_ms], "max_gap": st.max_gap,
+            "max_dtheta": st.max_dtheta}
+
+
+def debug_grid_rows(x, y, T, theta, last, theta0, grid, fan_size=None, max_gap=None, max_dtheta=None, stats=False):
+    """rtmi_first_arrival_grid's kernels on caller-supplied rows (rtmi_debug_grid_rows): x, y, T, theta [rows, R], last [R],
+    theta0 [R].  Returns what Batch.first_arrival_grid returns (no amplitude)."""
+    x, y, T, th = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, y, T, theta))
+    rows, R = x.shape
+    assert y.shape == T.shape == th.shape == (rows, R)
+    la = np.ascontiguousarray(last, dtype=np.int32)
+    t0 = np.ascontiguousarray(theta0, dtype=np.float64)
+    assert la.shape == t0.shape == (R,)
+    M = R if fan_size is None else int(fan_size)
+    return _grid_call(lambda gp, cnt, out, st: lib().rtmi_debug_grid_rows(rows, R, M, dptr(x), dptr(y), dptr(T), dptr(th),
+                                                                          la.ctypes.data_as(_lib._ip), dptr(t0), gp, cnt, out, st),
+                      R // M if M >= 1 else 0, grid, max_gap, max_dtheta, False, stats)
+
+
+def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_size, box, gamma=1, amplitude=False, mem_budget=0,
+                     max_gap=None, max_dtheta=None, stats=False, **batch_kw):
+    """First-arrival tables from many sources onto one grid, by public calls only: a fan of launch angles
+    `thetas` per source (sources: (S, 2) array of (x, y)).  1. A count pass without a record sizes rec_rows to the longest ray.
+    2. Sources are grouped so that each group's record (48 bytes per row and ray in fp64, 24 in fp32; 12 more with amplitude,
+    for the per-row J and kmah) stays under mem_budget (default 8 GiB).  3. One batch per group is traced and its grid taken
+    (Batch.first_arrival_grid).  Each source's table depends on its own rays only, so the grouping changes no bit.  batch_kw go
+    to Batch (launch_mode, sort_rays, reference_order, ...).  Returns a dict of [S, ny, nx] arrays as first_arrival_grid; with
+    stats=True also 'stats' (rec_rows, groups, count_ms, trace_ms, grid_ms: host wall times, and the grid calls' summed
+    counters)."""
+    src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    S, M = len(src), len(th)
+    batch_kw = dict(batch_kw)
+    batch_kw.pop("keep_n_ray", None)
+    t0 = time.perf_counter()
+    c = Batch(field, selected_func, step, max_size, box, gamma, np.tile(th, S), np.repeat(src[:, 0], M), np.repeat(src[:, 1], M),
+              record_stride=0, keep_n_ray=False, **batch_kw)
+    try:
+        c.run()
+        rows = int(c.d_ray()[2].max()) + 1
+    finally:
+        c.close()
+    t1 = time.perf_counter()
+    per_ray = rows * ((48 if field.dtype == F64 else 24) + (12 if amplitude else 0))
+    budget = int(mem_budget) if mem_budget else 8 << 30
+    G = max(1, min(S, budget // max(per_ray * M, 1)))
+    res, tot = None, {"rec_rows": rows, "groups": 0, "count_ms": (t1 - t0) * 1e3, "trace_ms": 0.0, "grid_ms": 0.0}
+    for g0 in range(0, S, G):
+        sg = src[g0:g0 + G]
+        ta = time.perf_counter()
+        b = Batch(field, selected_func, step, max_size, box, gamma, np.tile(th, len(sg)), np.repeat(sg[:, 0], M),
+                  np.repeat(sg[:, 1], M), record_stride=1, rec_rows=rows, keep_n_ray=False, **batch_kw)
+        try:
+            b.run()
+            b.sync()
+            tb = time.perf_counter()
+            r = b.first_arrival_grid(grid, fan_size=M, max_gap=max_gap, max_dtheta=max_dtheta, amplitude=amplitude, stats=True)
+        finally:
+            b.close()
+        tc = time.perf_counter()
+        tot["groups"] += 1
+        tot["trace_ms"] += (tb - ta) * 1e3
+        tot["grid_ms"] += (tc - tb) * 1e3
+        st = r.pop("stats")
+        for k in ("cells", "skipped_cells", "triangles", "folded"):
+            tot[k] = tot.get(k, 0) + st[k]
+        tot["atomics"] = [a + b_ for a, b_ in zip(tot.get("atomics", [0, 0, 0]), st["atomics"])]
+        tot["pass_ms"] = [a + b_ for a, b_ in zip(tot.get("pass_ms", [0.0] * 3), st["pass_ms"])]
+        if res is None:
+            res = {k: np.empty((S,) + v.shape[1:], dtype=v.dtype) for k, v in r.items()}
+        for k, v in r.items():
+            res[k][g0:g0 + len(sg)] = v
+    if stats:
+        res["stats"] = tot
     return res
 
 
