@@ -430,6 +430,37 @@ typedef struct {
 int rtmi_first_arrival_grid(rtmi_batch *b, int32_t fan_size, const rtmi_grid_params *gp, int32_t *count, double *out,
                             rtmi_grid_stats *st);
 
+/* Traveltime sensitivity kernels: the Frechet derivative A of every reported traveltime with respect to the n samples
+ * Z[qy][qx] of the batch's field (rtmi_field_read's Z), the rows held fixed, and its transpose.  n is the bilinear spline of the
+ * samples and every recorded T is a trapezoid sum of coef n (RT_bench.py:873-874), so each reported T is exactly linear in Z and
+ * A Z gives it back.  DESIGN.md section 12.
+ *   Rows        a batch's recorded rows 0 .. last_m of ray m (record_stride 1), as rtmi_crossings reads them.
+ *   Weights     a point (x, y) has the weights phi = (1-u)(1-v), u(1-v), (1-u)v, uv on Z[i][j], Z[i][j+1], Z[i+1][j],
+ *               Z[i+1][j+1]: the cell (j, i) and (u, v) of the field lookup (FITPACK's argument clamp, the interval of the
+ *               linspace axis, u = (x - a) inv_hx - j).
+ *   Slowness    ds_i = coef_i sum(phi(x_i, y_i) dZ): coef_i = 1 for op1..op9, anisotropy(theta_i, gamma) with the batch's gamma
+ *               for op10 / op11 (sin / cos as the step kernels evaluate them).
+ *   End of ray  dT_end = sum_{i=1..last} L_i (ds_{i-1} + ds_i) / 2, L_i = |P_i - P_{i-1}| the chord; NaN for a ray that runs past
+ *               rec_rows.
+ *   Crossing    c of the line, with rtmi_crossings' rule, step i and tau*, and the Hermite basis h00..h11 at tau*:
+ *               dT* = h00 dT_{i-1} + h01 dT_i + L_i (h10 ds_{i-1} + h11 ds_i), the derivative of rtmi_crossings' T column.
+ * A maps dZ [qy][qx] to (dT_line [kmax][R], dT_end [R]); A^T maps weights (w_line, w_end) to g [qy][qx] with <A dZ, w> =
+ * <dZ, A^T w>.  NaN or absent weights count as 0, and so do weights past a ray's count.  A is accumulated in fp64 in one fixed
+ * order per ray.  A^T rounds each lane's fp64 partial sum of a cell once to a fixed-point integer (the quantum 2^scale_exp,
+ * from the largest per-ray bound) and adds integers into 128-bit accumulators: the same bits in every schedule, launch mode,
+ * ray sorting and ray order.  Host buffers, fp64, the caller's ray order; both dtypes (fp32 records are widened), every method.
+ * Rays handed over to the re-trace of critical rays are drained first.  RTMI_ERR_ARG before any device work: a line with
+ * kmax outside 1..64 or (a, b) = (0, 0), a null buffer; then record_stride != 1.  RTMI_ERR_STATE: rtmi_paraxial's rule on
+ * rtmi_batch_set_state.  The calling thread's current device must be the batch's. */
+typedef struct { double kernel_ms; int64_t atomics; int32_t scale_exp; int32_t reserved0; int64_t reserved[4]; } rtmi_sensitivity_stats;
+/* A: dZ [qy][qx] of the batch's field (host fp64) -> count [R] (rtmi_crossings'), dT_line [kmax][R] (NaN past count), dT_end [R];
+   line NULL: end only (count and dT_line may then be NULL). */
+int rtmi_traveltime_perturb(rtmi_batch *b, const double line[3], int32_t kmax, const double *dZ,
+                            int32_t *count, double *dT_line, double *dT_end, rtmi_sensitivity_stats *st);
+/* A^T: w_line [kmax][R] and/or w_end [R] (either may be NULL) -> g [qy][qx] (host fp64, overwritten). */
+int rtmi_traveltime_backproject(rtmi_batch *b, const double line[3], int32_t kmax, const double *w_line,
+                                const double *w_end, double *g, rtmi_sensitivity_stats *st);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

@@ -79,6 +79,11 @@ class GridStats(C.Structure):
                 ("reserved", C.c_double * 4)]
 
 
+class SensitivityStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("atomics", C.c_int64), ("scale_exp", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved", C.c_int64 * 4)]
+
+
 # rtmi_arrival_status
 ARRIVAL_EMPTY, ARRIVAL_CONVERGED, ARRIVAL_STALLED, ARRIVAL_TRUNCATED = -1, 1, 2, 3
 
@@ -119,6 +124,8 @@ SYMBOLS = {
     "rtmi_paraxial": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, _dp, _dp]),
     "rtmi_field_eval_dgrad": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 6),
     "rtmi_first_arrival_grid": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(GridParams), _ip, _dp, C.POINTER(GridStats)]),
+    "rtmi_traveltime_perturb": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _ip, _dp, _dp, C.POINTER(SensitivityStats)]),
+    "rtmi_traveltime_backproject": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(SensitivityStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -1,0 +1,521 @@
+// sensitivity.hip -- traveltime sensitivity kernels along recorded rays (rtmi_traveltime_perturb, rtmi_traveltime_backproject):
+// the Frechet derivative A of every reported traveltime with respect to the n samples Z[qy][qx] of the field, with the rows
+// held fixed, and its transpose.  DESIGN.md section 12.
+//
+// n is the bilinear spline of the samples (rtmi.h: "bilinear coefficients == n samples"), every recorded T is a trapezoid sum
+// of s = coef n over the rows, and rtmi_crossings' T is a cubic Hermite blend of two rows' T and s: each is exactly linear in Z.
+//   A   one lane per ray walks its rows, gathers 4 samples of dZ per row and carries dT in fp64 in one fixed order.
+//   A^T one lane per ray walks its rows with the weight each row carries, keeps fp64 partial sums for the samples of its current
+//       cell and flushes them when the cell changes: each partial is rounded once to a fixed-point integer (a power-of-two
+//       quantum chosen from the largest per-ray bound, an order-independent maximum), the lanes of a wave that flush the same
+//       cell add their integers with shuffles, and one lane adds the group's sum into a two-word (128-bit) accumulator per
+//       sample.  Integer sums do not depend on their order: the result has the same bits under every schedule.
+// Batches are read through the public rtmi_batch_view; the field and the batch's parameters through two internal hooks.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/rtmi.h"
+#include "rt_crossing.h"
+#include "rtmi_internal.h"
+
+#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
+#define SN_TRY(expr)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+#define SN_ARG(cond, msg)                                                    \
+    do {                                                                     \
+        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
+    } while (0)
+#define SN_RC(expr)                  \
+    do {                             \
+        const int rc_ = (expr);      \
+        if (rc_) return rc_;         \
+    } while (0)
+
+namespace {
+
+constexpr int kMaxLine = 64;      // kmax: at most this many crossings per ray
+constexpr int kFixBits = 57;      // a flushed partial is below 2^57 quanta: 64 lanes' sum fits in an int64
+
+// The field's map from a point to its cell and (u, v): rt::poly_locate in fp64 (paraxial.hip's locate), FITPACK's argument clamp
+// outside the grid.  The indices are clamped once more so that no row, however odd, addresses outside the samples.
+struct Axes {
+    double ax, bx, inv_hx, ay, by, inv_hy;
+    int qx, qy;                   // samples per axis; cells qx - 1, qy - 1
+};
+struct Cell { int jx, jy; double u, v; };
+
+__device__ __forceinline__ void axis_clamped(double x, double a, double b, double inv_h, int ncell, double& xa, double& jf) {
+    x = x < a ? a : x;
+    x = x > b ? b : x;
+    xa = x - a;
+    jf = floor(xa * inv_h);
+    jf = jf < 0.0 ? 0.0 : (jf > (double)(ncell - 1) ? (double)(ncell - 1) : jf);
+}
+__device__ __forceinline__ Cell locate(const Axes& F, double x, double y) {
+    const int ncx = F.qx - 1, ncy = F.qy - 1;
+    double xa = x - F.ax, ya = y - F.ay;
+    double jfx = floor(xa * F.inv_hx), jfy = floor(ya * F.inv_hy);
+    int jx = (int)jfx, jy = (int)jfy;
+    if ((unsigned)jx >= (unsigned)ncx) { axis_clamped(x, F.ax, F.bx, F.inv_hx, ncx, xa, jfx); jx = (int)jfx; }
+    if ((unsigned)jy >= (unsigned)ncy) { axis_clamped(y, F.ay, F.by, F.inv_hy, ncy, ya, jfy); jy = (int)jfy; }
+    Cell c;
+    c.u = __builtin_fma(xa, F.inv_hx, -jfx);
+    c.v = __builtin_fma(ya, F.inv_hy, -jfy);
+    c.jx = jx < 0 ? 0 : (jx > ncx - 1 ? ncx - 1 : jx);
+    c.jy = jy < 0 ? 0 : (jy > ncy - 1 ? ncy - 1 : jy);
+    return c;
+}
+// the sample weights (1-u)(1-v), u(1-v), (1-u)v, uv on Z[j][i], Z[j][i+1], Z[j+1][i], Z[j+1][i+1]
+struct Phi { double w00, w01, w10, w11; };
+__device__ __forceinline__ Phi phi(const Cell& c) {
+    const double u1 = 1.0 - c.u, v1 = 1.0 - c.v;
+    return Phi{u1 * v1, c.u * v1, u1 * c.v, c.u * c.v};
+}
+
+// anisotropy(theta, gamma) as the step kernels evaluate it (rt_device.h aniso), sin / cos glibc's through rt_libm.h
+__device__ __forceinline__ double coef_of(double th, double gamma) {
+    const double s = sin_g(th), c = cos_g(th);
+    const double gs = gamma * s;
+    return sqrt(__builtin_fma(gs, gs, c * c));
+}
+
+struct Args {
+    const void* s_ray;            // [rec_rows][6][R] of the batch's dtype
+    const int32_t* istep;         // [R] last written row
+    const int32_t* perm;          // [R] or NULL: slot k holds the caller's ray perm[k]
+    const double* dist;           // [R] dist_sim (slot order): the bound of the fixed-point scale
+    long R, rec_rows;
+    Axes F;
+    Line L;
+    int has_line, kmax, aniso;
+    double gamma;
+};
+
+// ------------------------------------------------------------------------------------------------------------ A
+// One lane per ray.  dT_i = dT_{i-1} + (L_i (ds_{i-1} + ds_i)) 0.5, ds = coef sum(phi dZ); at a crossing (the rule and tau* of
+// rtmi_crossings) dT* = ((dT_{i-1} h00 + (L ds_{i-1}) h10) + dT_i h01) + (L ds_i) h11, rtmi_crossings' herm with dT for T.
+template <typename T>
+__global__ void k_perturb(Args A, const double* dZ, int32_t* count, double* dT_line, double* dT_end) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= A.R) return;
+    const long R = A.R;
+    const long o = A.perm ? (long)A.perm[k] : k;
+    const size_t P = (size_t)6 * R;
+    const T* col = reinterpret_cast<const T*>(A.s_ray) + k;
+    const long last = A.istep[k];
+    const Line L = A.L;
+    const int qx = A.F.qx;
+    auto ds_at = [&](double x, double y, double th) {
+        const Cell c = locate(A.F, x, y);
+        const Phi w = phi(c);
+        const double* z = dZ + (size_t)c.jy * qx + c.jx;
+        const double s = ((w.w00 * z[0] + w.w01 * z[1]) + w.w10 * z[qx]) + w.w11 * z[qx + 1];
+        return A.aniso ? coef_of(th, A.gamma) * s : s;
+    };
+    int n = 0;
+    if (last >= A.rec_rows) {
+        n = -1;
+        dT_end[o] = NAN;
+    } else {
+        double x0 = (double)col[0], y0 = (double)col[R];
+        double th0 = A.aniso ? (double)col[5 * R] : 0.0;
+        double s0 = ds_at(x0, y0, th0);
+        double f0 = (L.a * x0 + L.b * y0) - L.c;
+        double dT = 0.0;
+        // the next row's loads go out a step ahead
+        double xn = 0.0, yn = 0.0, tn = 0.0;
+        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; if (A.aniso) tn = (double)col[P + 5 * R]; }
+        for (long i = 1; i <= last; i++) {
+            const double x1 = xn, y1 = yn, th1 = tn;
+            if (i < last) {
+                const T* r = col + (size_t)(i + 1) * P;
+                xn = (double)r[0]; yn = (double)r[R];
+                if (A.aniso) tn = (double)r[5 * R];
+            }
+            const double s1 = ds_at(x1, y1, th1);
+            const double dx = x1 - x0, dy = y1 - y0;
+            const double len = sqrt(dx * dx + dy * dy);
+            const double dTn = dT + (len * (s0 + s1)) * 0.5;
+            if (A.has_line) {
+                const double f1 = (L.a * x1 + L.b * y1) - L.c;
+                if (crosses(f0, f1)) {
+                    if (n < A.kmax) {
+                        const T* r0 = col + (size_t)(i - 1) * P;
+                        const T* r1 = col + (size_t)i * P;
+                        const double ta = (double)r0[5 * R], tb = (double)r1[5 * R];
+                        const double d0 = len * (L.a * cos_g(ta) + L.b * sin_g(ta)), d1 = len * (L.a * cos_g(tb) + L.b * sin_g(tb));
+                        const Basis h = basis(cross_tau(f0, d0, f1, d1));
+                        dT_line[(size_t)n * R + o] = herm(h, dT, len * s0, dTn, len * s1);
+                    }
+                    n++;
+                }
+                f0 = f1;
+            }
+            dT = dTn;
+            x0 = x1; y0 = y1; s0 = s1;
+        }
+        dT_end[o] = dT;
+    }
+    if (count) count[o] = n;
+    if (A.has_line)
+        for (int c = n < 0 ? 0 : n; c < A.kmax; c++) dT_line[(size_t)c * R + o] = NAN;
+}
+
+// ------------------------------------------------------------------------------------------------------------ A^T
+__device__ __forceinline__ double w0(double w) { return w == w ? w : 0.0; }       // NaN weights count as 0
+
+// The crossings of a ray's rows with the line (rtmi_crossings' rule), counted
+template <typename T> __device__ __forceinline__ int count_crossings(const T* col, long R, long last, const Line& L) {
+    const size_t P = (size_t)6 * R;
+    double f0 = (L.a * (double)col[0] + L.b * (double)col[R]) - L.c;
+    int n = 0;
+    for (long i = 1; i <= last; i++) {
+        const T* r = col + (size_t)i * P;
+        const double f1 = (L.a * (double)r[0] + L.b * (double)r[R]) - L.c;
+        n += crosses(f0, f1) ? 1 : 0;
+        f0 = f1;
+    }
+    return n;
+}
+
+// Per ray: a bound on any partial sum its lane can flush, (|w_end| + sum_c |w_c|) 2 len coef_max (a row's weights total at most
+// 1.15 len coef_max per unit of weight: DESIGN.md 12), and its maximum over rays (non-negative doubles order as their bits).
+__global__ void k_bound(Args A, const double* w_line, const double* w_end, double coef_max, unsigned long long* maxb) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= A.R) return;
+    const long o = A.perm ? (long)A.perm[k] : k;
+    if (A.istep[k] >= A.rec_rows) return;
+    double w = w_end ? fabs(w0(w_end[o])) : 0.0;
+    if (w_line)
+        for (int c = 0; c < A.kmax; c++) w += fabs(w0(w_line[(size_t)c * A.R + o]));
+    const double b = w * (2.0 * A.dist[k]) * coef_max;
+    if (b > 0.0) atomicMax(maxb, (unsigned long long)__double_as_longlong(b));
+}
+
+__global__ void k_fill(unsigned long long* p, size_t n, unsigned long long v) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// The group's integer sum s added to sample q's 128-bit accumulator (lo, hi), sign-extended: the low word's carry, read from the
+// value the add returned, goes to the high word; the high word is written only when it changes.
+__device__ __forceinline__ int add128(unsigned long long* lo, unsigned long long* hi, size_t q, long long s) {
+    if (s == 0) return 0;
+    const unsigned long long a = (unsigned long long)s;
+    const unsigned long long old = atomicAdd(lo + q, a);
+    const unsigned long long h = (s < 0 ? ~0ull : 0ull) + ((old + a) < old ? 1ull : 0ull);
+    if (h == 0) return 1;
+    atomicAdd(hi + q, h);
+    return 2;
+}
+
+// One lane per ray.  Step i (rows i-1, i) gives both rows (L_i 0.5) W_i, W_i = w_end + the weights of the crossings after
+// step i; a crossing c < min(count, kmax) on step i gives row i-1 w_c L_i (0.5 h01 + h10) and row i w_c L_i (0.5 h01 + h11).
+// A row's weight times its coef, times phi, goes into the lane's partial sums of its cell.
+template <typename T>
+__global__ void k_backproject(Args A, const double* w_line, const double* w_end, const unsigned long long* maxb,
+                              unsigned long long* lo, unsigned long long* hi, unsigned long long* natomics) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = k < A.R;
+    const long R = A.R;
+    const long o = in ? (A.perm ? (long)A.perm[k] : k) : 0;
+    const size_t P = (size_t)6 * R;
+    const T* col = reinterpret_cast<const T*>(A.s_ray) + (in ? k : 0);
+    long last = in ? (long)A.istep[k] : -1;
+    if (last >= A.rec_rows) last = -1;                      // past the record: no reported traveltime, no weight
+    const Line L = A.L;
+    const int qx = A.F.qx;
+    int ex;
+    (void)frexp(__longlong_as_double((long long)*maxb), &ex);
+    const int e = ex - kFixBits;                            // quantum 2^e: every partial is below 2^57 quanta
+    // crossings that carry a weight: the first min(count, kmax)
+    const bool line = A.has_line && w_line != nullptr;
+    const int K = (line && last >= 0) ? min(count_crossings(col, R, last, L), A.kmax) : 0;
+    const double we = (w_end && last >= 0) ? w0(w_end[o]) : 0.0;
+    auto wc = [&](int c) { return w0(w_line[(size_t)c * R + o]); };
+    auto weight_after = [&](int c0) {                       // w_end + the weights of crossings c0 .. K-1
+        double w = we;
+        for (int c = c0; c < K; c++) w += wc(c);
+        return w;
+    };
+    double W = weight_after(0);
+    // the lane's current cell and its partial sums
+    int cx = -1, cy = -1;
+    double p[4] = {0.0, 0.0, 0.0, 0.0};
+    long long nat = 0;
+    const int lane = (int)(threadIdx.x & 63);
+    // every lane of the wave calls this together; lanes with `go` hand over p for cell (cx, cy)
+    auto flush = [&](bool go) {
+        unsigned long long todo = __ballot(go);
+        long long m[4] = {0, 0, 0, 0};
+        if (go) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) m[q] = (long long)rint(ldexp(p[q], -e));
+        }
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int lx = __shfl(cx, leader), ly = __shfl(cy, leader);
+            const bool mem = go && cx == lx && cy == ly;
+            const unsigned long long mm = __ballot(mem);
+            long long v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[q] = mem ? m[q] : 0;
+            if (__popcll(mm) > 1) {
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) v[q] += __shfl_xor(v[q], off);
+            }
+            if (lane == leader) {
+                const size_t b = (size_t)ly * qx + lx;
+                nat += add128(lo, hi, b, v[0]);
+                nat += add128(lo, hi, b + 1, v[1]);
+                nat += add128(lo, hi, b + qx, v[2]);
+                nat += add128(lo, hi, b + qx + 1, v[3]);
+            }
+            todo &= ~mm;
+        }
+    };
+    // row j's weight a (coef not yet applied) at (x, y): into the partials, after a flush when the cell changes
+    auto deposit = [&](bool act, double x, double y, double th, double a) {
+        Cell c{0, 0, 0.0, 0.0};
+        bool go = false;
+        if (act) {
+            c = locate(A.F, x, y);
+            go = (c.jx != cx || c.jy != cy) && cx >= 0;
+        }
+        flush(go);
+        if (act) {
+            if (c.jx != cx || c.jy != cy) { cx = c.jx; cy = c.jy; p[0] = p[1] = p[2] = p[3] = 0.0; }
+            const double wr = A.aniso ? a * coef_of(th, A.gamma) : a;
+            const Phi f = phi(c);
+            p[0] += wr * f.w00; p[1] += wr * f.w01; p[2] += wr * f.w10; p[3] += wr * f.w11;
+        }
+    };
+    const bool live = last >= 0 && (we != 0.0 || K > 0);
+    double x0 = 0.0, y0 = 0.0, th0 = 0.0, f0 = 0.0, xn = 0.0, yn = 0.0, tn = 0.0;
+    if (live) {
+        x0 = (double)col[0]; y0 = (double)col[R];
+        if (A.aniso) th0 = (double)col[5 * R];
+        f0 = (L.a * x0 + L.b * y0) - L.c;
+        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; if (A.aniso) tn = (double)col[P + 5 * R]; }
+    }
+    const long end = live ? last : 0;
+    double aprev = 0.0;                                     // row i-1's weight so far
+    int n = 0;
+    for (long i = 1;; i++) {
+        const bool act = i <= end;
+        if (__ballot(act) == 0ull) break;
+        double x1 = 0.0, y1 = 0.0, th1 = 0.0, acur = 0.0;
+        if (act) {
+            x1 = xn; y1 = yn; th1 = tn;
+            if (i < end) {
+                const T* r = col + (size_t)(i + 1) * P;
+                xn = (double)r[0]; yn = (double)r[R];
+                if (A.aniso) tn = (double)r[5 * R];
+            }
+            const double dx = x1 - x0, dy = y1 - y0;
+            const double len = sqrt(dx * dx + dy * dy);
+            if (line) {
+                const double f1 = (L.a * x1 + L.b * y1) - L.c;
+                if (crosses(f0, f1)) {
+                    if (n < K) {
+                        const T* r0 = col + (size_t)(i - 1) * P;
+                        const T* r1 = col + (size_t)i * P;
+                        const double ta = (double)r0[5 * R], tb = (double)r1[5 * R];
+                        const double d0 = len * (L.a * cos_g(ta) + L.b * sin_g(ta)), d1 = len * (L.a * cos_g(tb) + L.b * sin_g(tb));
+                        const Basis h = basis(cross_tau(f0, d0, f1, d1));
+                        const double w = wc(n);
+                        aprev += (w * len) * (0.5 * h.h01 + h.h10);
+                        acur = (w * len) * (0.5 * h.h01 + h.h11);
+                        W = weight_after(n + 1);
+                    }
+                    n++;
+                }
+                f0 = f1;
+            }
+            const double half = (W * len) * 0.5;
+            aprev += half;
+            acur += half;
+        }
+        deposit(act, x0, y0, th0, aprev);                   // row i-1 is complete
+        if (act) { aprev = acur; x0 = x1; y0 = y1; th0 = th1; }
+    }
+    deposit(live, x0, y0, th0, aprev);                      // the last row
+    flush(cx >= 0);
+    // one count per wave
+    for (int off = 1; off < 64; off <<= 1) nat += __shfl_xor(nat, off);
+    if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
+}
+
+// device allocations of one call, freed on every way out
+struct DevMem {
+    std::vector<void*> p;
+    template <typename T> hipError_t get(T** out, size_t bytes) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
+        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
+        return e;
+    }
+    ~DevMem() { for (void* v : p) (void)hipFree(v); }
+};
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// The checks both entries share, then the batch's rows and the field's axes
+int prepare(rtmi_batch* b, const double* line, int32_t kmax, const char* who, Args* A, rtmi_device_view* v) {
+    const rtmi_field* f = nullptr;
+    rtmi_params p{};
+    int from_state = 0;
+    SN_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
+    if (p.record_stride != 1)
+        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": needs the full trajectory (record_stride 1)").c_str());
+    if (from_state)
+        return rtmi_internal_fail(RTMI_ERR_STATE, (std::string(who) + ": rtmi_batch_set_state gave rays a row other than 0: their "
+                                                   "rows before it are not a trajectory from the source (reset the batch)").c_str());
+    rtmi_internal_poly pv;
+    SN_RC(rtmi_internal_field_poly(f, &pv));
+    int qx = 0, qy = 0;
+    SN_RC(rtmi_field_dims(f, &qx, &qy));
+    SN_RC(rtmi_batch_view(b, v));          // drains the rays handed over to the re-trace of critical rays
+    SN_RC(rtmi_sync(b));
+    Line L{0.0, 0.0, 0.0};
+    if (line) (void)make_line(line, &L);
+    *A = Args{v->s_ray, v->istep, v->perm, v->dist_sim, (long)v->R, (long)v->rec_rows,
+              Axes{pv.ax, pv.bx, pv.inv_hx, pv.ay, pv.by, pv.inv_hy, qx, qy}, L, line ? 1 : 0, line ? kmax : 0,
+              p.method >= 10 ? 1 : 0, p.gamma};
+    return RTMI_OK;
+}
+
+int check_line(const double* line, int32_t kmax, const char* who) {
+    if (!line) return RTMI_OK;
+    Line L;
+    if (kmax < 1 || kmax > kMaxLine)
+        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": kmax must be in 1..64").c_str());
+    if (!make_line(line, &L))
+        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": the line needs (a, b) != (0, 0) and finite coefficients").c_str());
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_traveltime_perturb(rtmi_batch* b, const double line[3], int32_t kmax, const double* dZ, int32_t* count,
+                                        double* dT_line, double* dT_end, rtmi_sensitivity_stats* st) {
+    const char* who = "rtmi_traveltime_perturb";
+    SN_RC(check_line(line, kmax, who));
+    SN_ARG(dZ && dT_end, "rtmi_traveltime_perturb: null dZ or dT_end");
+    SN_ARG(!line || (count && dT_line), "rtmi_traveltime_perturb: a line needs count and dT_line");
+    SN_ARG(b, "rtmi_traveltime_perturb: null batch");
+    Args A;
+    rtmi_device_view v;
+    SN_RC(prepare(b, line, kmax, who, &A, &v));
+    const size_t R = (size_t)v.R, nz = (size_t)A.F.qx * A.F.qy, K = (size_t)A.kmax;
+    DevMem mem;
+    double *dz = nullptr, *de = nullptr, *dl = nullptr;
+    int32_t* dc = nullptr;
+    SN_TRY(mem.get(&dz, nz * sizeof(double)));
+    SN_TRY(mem.get(&de, R * sizeof(double)));
+    SN_TRY(mem.get(&dc, R * sizeof(int32_t)));
+    if (K) SN_TRY(mem.get(&dl, K * R * sizeof(double)));
+    SN_TRY(hipMemcpy(dz, dZ, nz * sizeof(double), hipMemcpyHostToDevice));
+    Events ev;
+    SN_TRY(hipEventCreate(&ev.a));
+    SN_TRY(hipEventCreate(&ev.b));
+    const dim3 g((unsigned)((R + 255) / 256)), blk(256);
+    SN_TRY(hipEventRecord(ev.a, nullptr));
+    if (R) {
+        if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_perturb<double>, g, blk, 0, nullptr, A, dz, dc, dl, de);
+        else hipLaunchKernelGGL(k_perturb<float>, g, blk, 0, nullptr, A, dz, dc, dl, de);
+        SN_TRY(hipGetLastError());
+    }
+    SN_TRY(hipEventRecord(ev.b, nullptr));
+    SN_TRY(hipEventSynchronize(ev.b));
+    SN_TRY(hipMemcpy(dT_end, de, R * sizeof(double), hipMemcpyDeviceToHost));
+    if (count) SN_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (K) SN_TRY(hipMemcpy(dT_line, dl, K * R * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        *st = rtmi_sensitivity_stats{};
+        float ms = 0.f;
+        SN_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        st->kernel_ms = ms;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_traveltime_backproject(rtmi_batch* b, const double line[3], int32_t kmax, const double* w_line,
+                                            const double* w_end, double* g, rtmi_sensitivity_stats* st) {
+    const char* who = "rtmi_traveltime_backproject";
+    SN_RC(check_line(line, kmax, who));
+    SN_ARG(g, "rtmi_traveltime_backproject: null g");
+    SN_ARG(!w_line || line, "rtmi_traveltime_backproject: w_line needs a line");
+    SN_ARG(b, "rtmi_traveltime_backproject: null batch");
+    Args A;
+    rtmi_device_view v;
+    SN_RC(prepare(b, line, kmax, who, &A, &v));
+    const size_t R = (size_t)v.R, nz = (size_t)A.F.qx * A.F.qy, K = (size_t)A.kmax;
+    DevMem mem;
+    double *dwl = nullptr, *dwe = nullptr;
+    unsigned long long *acc = nullptr, *misc = nullptr;    // acc: lo [nz], hi [nz]; misc: the bound, the atomics issued
+    SN_TRY(mem.get(&acc, 2 * nz * sizeof(unsigned long long)));
+    SN_TRY(mem.get(&misc, 2 * sizeof(unsigned long long)));
+    if (w_line) {
+        SN_TRY(mem.get(&dwl, K * R * sizeof(double)));
+        SN_TRY(hipMemcpy(dwl, w_line, K * R * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (w_end) {
+        SN_TRY(mem.get(&dwe, R * sizeof(double)));
+        SN_TRY(hipMemcpy(dwe, w_end, R * sizeof(double), hipMemcpyHostToDevice));
+    }
+    SN_TRY(hipMemset(misc, 0, 2 * sizeof(unsigned long long)));
+    SN_TRY(hipMemset(acc + nz, 0, nz * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_fill, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, nullptr, acc, nz, 1ull << 63);   // the low words' bias
+    SN_TRY(hipGetLastError());
+    const double coef_max = A.aniso ? fmax(1.0, fabs(A.gamma)) : 1.0;
+    Events ev;
+    SN_TRY(hipEventCreate(&ev.a));
+    SN_TRY(hipEventCreate(&ev.b));
+    const dim3 gr((unsigned)((R + 255) / 256)), blk(256);
+    SN_TRY(hipEventRecord(ev.a, nullptr));
+    if (R) {
+        hipLaunchKernelGGL(k_bound, gr, blk, 0, nullptr, A, dwl, dwe, coef_max, misc);
+        SN_TRY(hipGetLastError());
+        if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_backproject<double>, gr, blk, 0, nullptr, A, dwl, dwe, misc, acc, acc + nz, misc + 1);
+        else hipLaunchKernelGGL(k_backproject<float>, gr, blk, 0, nullptr, A, dwl, dwe, misc, acc, acc + nz, misc + 1);
+        SN_TRY(hipGetLastError());
+    }
+    SN_TRY(hipEventRecord(ev.b, nullptr));
+    SN_TRY(hipEventSynchronize(ev.b));
+    std::vector<unsigned long long> h(2 * nz);
+    unsigned long long hm[2];
+    SN_TRY(hipMemcpy(h.data(), acc, 2 * nz * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    SN_TRY(hipMemcpy(hm, misc, sizeof(hm), hipMemcpyDeviceToHost));
+    double maxb;
+    std::memcpy(&maxb, &hm[0], sizeof(double));
+    int ex;
+    (void)std::frexp(maxb, &ex);
+    const int e = ex - kFixBits;
+    // value = hi 2^64 + lo - 2^63 quanta, exact in 128 bits; one rounding to fp64
+    for (size_t i = 0; i < nz; i++) {
+        const __int128 q = (__int128)(((unsigned __int128)h[nz + i] << 64) | h[i]) - ((__int128)1 << 63);
+        g[i] = std::ldexp((double)q, e);
+    }
+    if (st) {
+        *st = rtmi_sensitivity_stats{};
+        float ms = 0.f;
+        SN_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        st->kernel_ms = ms;
+        st->atomics = (int64_t)hm[1];
+        st->scale_exp = e;
+    }
+    return RTMI_OK;
+}

@@ -464,6 +464,56 @@ class Batch:
         return _grid_call(lambda gp, cnt, out, st: lib().rtmi_first_arrival_grid(self._h, M, gp, cnt, out, st),
                           self.R // M if M >= 1 else 0, grid, max_gap, max_dtheta, amplitude, stats)
 
+    def traveltime_perturb(self, dZ, line=None, kmax=4, stats=False):
+        """The Frechet derivative of the reported traveltimes applied to a change dZ [qy, qx] of the field's n samples, the rows
+        held fixed (rtmi_traveltime_perturb): returns {"end": [R], "line": [kmax, R], "count": [R]} -- the change of each ray's
+        traveltime at its end (NaN past the record) and at its crossings of the line (a, b, c) (NaN past count; without a line
+        "line" is [0, R] and "count" is None); with stats=True also 'stats'.  Needs record_stride 1."""
+        qx, qy = self.field.qx, self.field.qy
+        dz = np.ascontiguousarray(dZ, dtype=np.float64)
+        if dz.shape != (qy, qx):
+            raise ValueError(f"dZ must have shape ({qy}, {qx})")
+        end = np.empty(self.R)
+        st = _lib.SensitivityStats()
+        if line is None:
+            check(lib().rtmi_traveltime_perturb(self._h, None, 0, dptr(dz), None, None, dptr(end), C.byref(st)))
+            d = {"end": end, "line": np.empty((0, self.R)), "count": None}
+        else:
+            ln = np.ascontiguousarray(line, dtype=np.float64)
+            if ln.shape != (3,):
+                raise ValueError("line must be (a, b, c)")
+            count = np.empty(self.R, dtype=np.int32)
+            out = np.empty((max(int(kmax), 0), self.R))
+            check(lib().rtmi_traveltime_perturb(self._h, dptr(ln), int(kmax), dptr(dz), count.ctypes.data_as(_lib._ip), dptr(out),
+                                                dptr(end), C.byref(st)))
+            d = {"end": end, "line": out, "count": count}
+        if stats:
+            d["stats"] = sensitivity_stats(st)
+        return d
+
+    def traveltime_backproject(self, w_end=None, w_line=None, line=None, kmax=4, stats=False):
+        """The transpose (rtmi_traveltime_backproject): weights w_end [R] on the ray ends and / or w_line [kmax, R] on the
+        crossings of the line (a, b, c) -> g [qy, qx] on the field's n samples, with <A dZ, w> = <dZ, g>.  NaN or absent
+        weights count as 0.  The result has the same bits in every schedule, ray sorting and ray order.  With stats=True returns
+        (g, stats)."""
+        we = None if w_end is None else np.ascontiguousarray(w_end, dtype=np.float64)
+        if we is not None and we.shape != (self.R,):
+            raise ValueError(f"w_end must have shape ({self.R},)")
+        wl = None if w_line is None else np.ascontiguousarray(w_line, dtype=np.float64)
+        if wl is not None and wl.shape != (int(kmax), self.R):
+            raise ValueError(f"w_line must have shape ({int(kmax)}, {self.R})")
+        ln = None
+        if line is not None:
+            ln = np.ascontiguousarray(line, dtype=np.float64)
+            if ln.shape != (3,):
+                raise ValueError("line must be (a, b, c)")
+        g = np.empty((self.field.qy, self.field.qx))
+        st = _lib.SensitivityStats()
+        check(lib().rtmi_traveltime_backproject(self._h, None if ln is None else dptr(ln), int(kmax) if ln is not None else 0,
+                                                None if wl is None else dptr(wl), None if we is None else dptr(we), dptr(g),
+                                                C.byref(st)))
+        return (g, sensitivity_stats(st)) if stats else g
+
     def paraxial_rows(self):
         """J and kmah after every recorded row ([rec_rows, R] each; NaN / -1 past a ray's end): rtmi_debug_paraxial_rows."""
         v = self.view()
@@ -632,7 +682,7 @@ PARAXIAL_FIELDS = ("Q1", "P1", "Q2", "P2", "J", "G", "kmah")                    
 
 def two_point(selected_func, field, sources, line, receivers_u, *, thetas, step, max_size, box, gamma=1, reference_order=False,
               retrace=True, tol=1e-10, max_arrivals=4, max_crossings=4, max_iter=60, mem_budget=0, gamma_step=None,
-              launch_mode="auto", field_path=0, stats=False, paraxial=False):
+              launch_mode="auto", field_path=0, stats=False, paraxial=False, sensitivity=False):
     """Rays from each source to each receiver on the line a x + b y = c (line = (a, b, c)), all on the device
     (rtmi_two_point): a fan of launch angles `thetas` per source, brackets between adjacent fan rays, Illinois regula falsi on
     the launch angle.  sources: (S, 2) array of (x, y); receivers_u: [J] coordinates along the line (u = a' y - b' x with
@@ -640,7 +690,8 @@ def two_point(selected_func, field, sources, line, receivers_u, *, thetas, step,
     theta (angle at the receiver), residual (u - u_j), iterations, status (rtmi_arrival_status) -- with the converged
     arrivals first, sorted by T; count [S, J] (converged arrivals) and nbad [S, J] (stalled or truncated brackets); with
     stats=True also 'stats' (iterations, groups, rec_rows, overflow, fan_ms, bracket_ms, refine_ms).  With paraxial=True also
-    [S, J, A] arrays Q2, P2, J, G, kmah of the converged arrivals (NaN elsewhere): _two_point_paraxial."""
+    [S, J, A] arrays Q2, P2, J, G, kmah of the converged arrivals (NaN elsewhere): _two_point_paraxial.  With sensitivity=True
+    also 'sensitivity', a TravelTimeSensitivity over the converged arrivals (close() it when done)."""
     src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
     sx = np.ascontiguousarray(src[:, 0]); sy = np.ascontiguousarray(src[:, 1])
     th = np.ascontiguousarray(thetas, dtype=np.float64)
@@ -676,7 +727,102 @@ def two_point(selected_func, field, sources, line, receivers_u, *, thetas, step,
         out["stats"] = {k: getattr(st, k) for k, _ in _lib.TwoPointStats._fields_ if k != "reserved"}
     if paraxial:
         out.update(_two_point_paraxial(field, p, sx, sy, ln, out, int(max_crossings)))
+    if sensitivity:
+        out["sensitivity"] = TravelTimeSensitivity(field, p, sx, sy, ln, out, int(max_crossings))
     return out
+
+
+def sensitivity_stats(st):
+    return {"kernel_ms": st.kernel_ms, "atomics": int(st.atomics), "scale_exp": int(st.scale_exp)}
+
+
+class TravelTimeSensitivity:
+    """The Frechet derivative of two_point's converged arrival traveltimes with respect to the field's n samples Z [qy, qx]
+    (the ray-tomography Jacobian, rays held fixed), built by public calls only, as _two_point_paraxial is: one fresh batch of
+    the converged (source, launch angle) rays with the solver's parameters -- sized by a count pass --, kept alive here; each
+    arrival takes the crossing whose u and T are bit-equal to its own.  index [n_arrivals, 3]: the (s, j, a) of each row;
+    shape = (n_arrivals, qy * qx); matvec(dZ) -> dT [n_arrivals], rmatvec(r) -> g [qy * qx]; as_linear_operator() for
+    scipy.sparse.linalg (lsqr); close() frees the batch."""
+
+    def __init__(self, field, p, sx, sy, line, arr, kmax):
+        self.field = field
+        self.line = np.ascontiguousarray(line, dtype=np.float64)
+        self.kmax = int(kmax)
+        self.index = np.argwhere(arr["status"] == _lib.ARRIVAL_CONVERGED)
+        self.shape = (len(self.index), field.qy * field.qx)
+        self._h = None
+        R = len(self.index)
+        self._rays = R
+        if R == 0:
+            self._cross = np.zeros(0, dtype=np.int64)
+            return
+        x0 = np.ascontiguousarray(sx[self.index[:, 0]]); y0 = np.ascontiguousarray(sy[self.index[:, 0]])
+        th = np.ascontiguousarray(arr["theta0"][tuple(self.index.T)])
+        q = Params.from_buffer_copy(p)
+        q.sort_rays = 0; q.no_n_ray = 1; q.lazy_clear = 0; q.ext_s_ray = None; q.ext_n_ray = None
+
+        def batch(stride, rows):
+            q.record_stride = stride; q.rec_rows = rows
+            h = C.c_void_p()
+            check(lib().rtmi_batch_create(field._h, C.byref(q), R, dptr(x0), dptr(y0), dptr(th), None, C.byref(h)))
+            return h
+        h = batch(0, 0)
+        try:
+            check(lib().rtmi_run(h))
+            d = np.empty((3, R))
+            check(lib().rtmi_read_d_ray(h, dptr(d)))
+        finally:
+            lib().rtmi_batch_destroy(h)
+        self._h = batch(1, int(d[2].max()) + 1)
+        check(lib().rtmi_run(self._h))
+        cnt = np.empty(R, dtype=np.int32)
+        cr = np.empty((self.kmax, len(CROSSING_FIELDS), R))
+        check(lib().rtmi_crossings(self._h, dptr(self.line), self.kmax, cnt.ctypes.data_as(_lib._ip), dptr(cr)))
+        iu, iT = CROSSING_FIELDS.index("u"), CROSSING_FIELDS.index("T")
+        self._cross = np.empty(R, dtype=np.int64)
+        for r, (s_, j, a) in enumerate(self.index):
+            hit = np.nonzero((cr[:, iu, r] == arr["u"][s_, j, a]) & (cr[:, iT, r] == arr["T"][s_, j, a]))[0]
+            if len(hit) == 0:
+                self.close()
+                raise RuntimeError(f"two_point: no crossing of the re-traced ray matches arrival {(s_, j, a)}")
+            self._cross[r] = hit[0]
+
+    def matvec(self, dZ):
+        """dT [n_arrivals] of the converged arrivals for dZ ([qy, qx] or flat [qy * qx])"""
+        if self._rays == 0:
+            return np.zeros(0)
+        dz = np.asarray(dZ, dtype=np.float64).reshape(self.field.qy, self.field.qx)
+        out = np.empty((self.kmax, self._rays))
+        cnt = np.empty(self._rays, dtype=np.int32)
+        end = np.empty(self._rays)
+        check(lib().rtmi_traveltime_perturb(self._h, dptr(self.line), self.kmax, dptr(np.ascontiguousarray(dz)),
+                                            cnt.ctypes.data_as(_lib._ip), dptr(out), dptr(end), None))
+        return out[self._cross, np.arange(self._rays)].copy()
+
+    def rmatvec(self, r):
+        """g [qy * qx] = A^T r for residuals r [n_arrivals]"""
+        if self._rays == 0:
+            return np.zeros(self.shape[1])
+        w = np.zeros((self.kmax, self._rays))
+        w[self._cross, np.arange(self._rays)] = np.asarray(r, dtype=np.float64).reshape(-1)
+        g = np.empty((self.field.qy, self.field.qx))
+        check(lib().rtmi_traveltime_backproject(self._h, dptr(self.line), self.kmax, dptr(w), None, dptr(g), None))
+        return g.reshape(-1)
+
+    def as_linear_operator(self):
+        from scipy.sparse.linalg import LinearOperator
+        return LinearOperator(self.shape, matvec=self.matvec, rmatvec=self.rmatvec, dtype=np.float64)
+
+    def close(self):
+        if self._h:
+            lib().rtmi_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _two_point_paraxial(field, p, sx, sy, line, arr, kmax):
