@@ -461,6 +461,73 @@ int rtmi_traveltime_perturb(rtmi_batch *b, const double line[3], int32_t kmax, c
 int rtmi_traveltime_backproject(rtmi_batch *b, const double line[3], int32_t kmax, const double *w_line,
                                 const double *w_end, double *g, rtmi_sensitivity_stats *st);
 
+/* Gaussian beam summation: the frequency-domain wavefield of each source on a regular grid, summed over the beams of its recorded
+ * fan (Cerveny, Popov & Psencik 1982; Hill 1990).  Finite through caustics, foci and shadow edges, where rtmi_paraxial's G is
+ * infinite and a first-arrival table holds one branch or none.  DESIGN.md section 13.
+ * The batch's R rays are S = R / fan_size fans as in rtmi_first_arrival_grid.  Ray m of a fan has launch angle theta0_m (strictly
+ * monotone within the fan) and the trapezoid weight w_m in theta0 (|theta0_1 - theta0_0| / 2 at the ends, |theta0_m+1 -
+ * theta0_m-1| / 2 inside), times 0.5 (1 - cos(pi d / edge_taper)) where d, the angular distance to the fan's nearer end, is below
+ * edge_taper.  Nodes as rtmi_grid_params.  For each frequency omega and node R:
+ *   u(R, omega) = e^{i pi/4} sqrt(eps n0) / (4 pi) sum_m sum_{steps i of ray m that own R} w_m (n |Q|)^(-1/2)
+ *                 exp(-omega Im(M) q^2 / 2) exp(i [omega (T + Re(M) q^2 / 2) - phi / 2])
+ *   Q = Q2 - i eps Q1, P = P2 - i eps P1   rtmi_paraxial's plane-wave and point-source solutions after each row (its propagator
+ *                                          on the same lookups); M = P / Q, and Im M = eps / |Q|^2 > 0 by the Wronskian
+ *   phi                                    arg Q, unwrapped along the ray from -pi/2 at row 0 (each row adds the wrapped change
+ *                                          of atan2): after each caustic it is ray theory's -kmah pi / 2
+ *   n0, n                                  n at the ray's row 0 and at the row (rtmi_paraxial's lookup)
+ *   eps > 0                                the beam parameter, one per call for all frequencies (Hill's choice).  A beam's 1/e
+ *                                          half-width at the source is sqrt(2 eps / omega); at distance D from the source the
+ *                                          beam is narrowest for eps ~ D / n0, the rule of thumb for choosing it
+ * With this normalisation stationary phase over theta0 gives back the ray-theory Green's function of rtmi_paraxial
+ * G / sqrt(8 pi omega) exp(i (omega T - kmah pi/2 + pi/4)); in a homogeneous medium (i/4) H0^(1)(omega n r).
+ * Ownership: with d_j = (R - X_j) . t_j and t_j = (cos theta_j, sin theta_j), step i (rows i-1 and i, 1 <= i <= the ray's last row)
+ * owns R when d_{i-1} >= 0 > d_i.  Along a straight or gently curving ray a node has one owning step; nodes behind row 0 or past
+ * the last row have none; near a tight bend several steps may own it, and each counts.  A step that turns by more than 1 rad
+ * (t_{i-1} . t_i < cos 1) owns no node.
+ * Interpolation at lambda = d_{i-1} / (d_{i-1} - d_i): the position linearly; the tangent as the blend t = t_{i-1} +
+ * lambda (t_i - t_{i-1}), whose normal gives q^2 = ((R - X) . (-t_y, t_x))^2 / (t . t); T as the cubic Hermite of rtmi_crossings
+ * between T_{i-1} and T_i with end slopes L n (L the chord); Re M, Im M, phi and w (n |Q|)^(-1/2) linearly in lambda between
+ * the rows' values.  That is second order in the step, as linear Q and P would be, and it needs no complex division, square root
+ * or arctangent per pair.
+ * Cutoff: a pair with omega Im(M) q^2 / 2 > cutoff contributes nothing at that omega.  A step's footprint is the wedge between its
+ * two normals clipped to |q| <= q_max = sqrt(2 cutoff max(|Q_{i-1}|^2, |Q_i|^2) / (omega_min eps)), capped at max_width: a pair
+ * with |q| > q_max contributes nothing, and steps whose q_max the cap cut are counted in the stats.
+ * Device: (1) rtmi_paraxial's kernel stores Q1 P1 Q2 P2 and n after every row, and one lane per ray derives each row's values;
+ * (2) a count pass, an exclusive scan, a fill and a stable radix sort give every 16 x 16 tile of nodes its steps in (m, i) order;
+ * (3) one block per tile and one lane per node stage the steps through LDS, test ownership, q_max and the cutoff once per pair
+ * and add one complex exponential per frequency into fp64 registers, in list order.  No floating-point atomics: the same bits in
+ * every launch_mode, with sort_rays on and off, twice in a row and in every source grouping.  exp and sincos are the device's own
+ * (ocml's), not glibc's.
+ *   u  [S][nw][ny][nx][2] (re, im), host fp64, the caller's fan order.  Both dtypes (fp32 records are widened); op1..op9, gamma 1.
+ * A ray that runs past rec_rows contributes up to its last recorded row.  Rays handed over to the re-trace of critical rays are
+ * drained first.  RTMI_ERR_ARG before any device work: a null pointer, the grid as in rtmi_grid_params, nw < 1, an omega or eps
+ * that is not finite and > 0, a cutoff, max_width or edge_taper that is negative or not finite; then record_stride != 1, R %
+ * fan_size != 0, fan_size < 2, op10 / op11 or gamma != 1, and launch angles not strictly monotone within a fan.  RTMI_ERR_STATE:
+ * rtmi_paraxial's rule on rtmi_batch_set_state.  The calling thread's current device must be the batch's. */
+typedef struct {
+    double gx0, gdx;         /* nodes as rtmi_grid_params: X = gx0 + ix gdx, Y = gy0 + iy gdy */
+    int64_t nx;
+    double gy0, gdy;
+    int64_t ny;
+    double eps;              /* the beam parameter (> 0) */
+    double cutoff;           /* 0: 18 (a pair at the cutoff weighs e^-18 = 1.5e-8 of the beam's peak) */
+    double max_width;        /* 0: 64 max(gdx, gdy), the cap of q_max */
+    double edge_taper;       /* radians; 0: no taper */
+    int64_t reserved[4];
+} rtmi_beam_params;
+typedef struct {
+    int64_t segments;        /* steps binned: the rays' steps 1 .. last */
+    int64_t tile_entries;    /* (tile, step) entries of the sorted lists */
+    int64_t pairs_tested;    /* (node, step) ownership tests */
+    int64_t pairs_inside;    /* ... owned, within q_max and inside the cutoff at the lowest omega */
+    int64_t capped;          /* steps whose q_max the cap max_width cut */
+    double prep_ms, bin_ms, gather_ms;   /* device time of each pass (HIP events) */
+    double cutoff, max_width;            /* the values used */
+    double reserved[4];
+} rtmi_beam_stats;
+int rtmi_gaussian_beams(rtmi_batch *b, int32_t fan_size, const rtmi_beam_params *bp, int32_t nw, const double *omega,
+                        double *u, rtmi_beam_stats *st);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

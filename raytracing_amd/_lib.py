@@ -84,6 +84,18 @@ class SensitivityStats(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+class BeamParams(C.Structure):
+    _fields_ = [("gx0", C.c_double), ("gdx", C.c_double), ("nx", C.c_int64), ("gy0", C.c_double), ("gdy", C.c_double),
+                ("ny", C.c_int64), ("eps", C.c_double), ("cutoff", C.c_double), ("max_width", C.c_double),
+                ("edge_taper", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
+class BeamStats(C.Structure):
+    _fields_ = [("segments", C.c_int64), ("tile_entries", C.c_int64), ("pairs_tested", C.c_int64), ("pairs_inside", C.c_int64),
+                ("capped", C.c_int64), ("prep_ms", C.c_double), ("bin_ms", C.c_double), ("gather_ms", C.c_double),
+                ("cutoff", C.c_double), ("max_width", C.c_double), ("reserved", C.c_double * 4)]
+
+
 # rtmi_arrival_status
 ARRIVAL_EMPTY, ARRIVAL_CONVERGED, ARRIVAL_STALLED, ARRIVAL_TRUNCATED = -1, 1, 2, 3
 
@@ -126,6 +138,7 @@ SYMBOLS = {
     "rtmi_first_arrival_grid": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(GridParams), _ip, _dp, C.POINTER(GridStats)]),
     "rtmi_traveltime_perturb": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _ip, _dp, _dp, C.POINTER(SensitivityStats)]),
     "rtmi_traveltime_backproject": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(SensitivityStats)]),
+    "rtmi_gaussian_beams": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BeamParams), C.c_int32, _dp, _dp, C.POINTER(BeamStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -182,7 +182,13 @@ struct ParaxArgs {
     double* at_end;             // [7][R]
     double* row_J;              // [rec_rows][R] or NULL: J after every row, slot order (rtmi_internal_paraxial_rows)
     int32_t* row_kmah;          // [rec_rows][R], with row_J
+    double* row_tube;           // [rec_rows][5][R] or NULL: Q1 P1 Q2 P2 n after every row, slot order (rtmi_internal_paraxial_tube)
 };
+
+__device__ __forceinline__ void put_tube(double* out, long R, long i, long k, const Tube& t, double n) {
+    double* p = out + (size_t)i * 5 * R + k;
+    p[0] = t.q1; p[R] = t.p1; p[2 * R] = t.q2; p[3 * R] = t.p2; p[4 * R] = n;
+}
 
 // One lane per ray (slot k); answers in the caller's order.  A crossing of the line (the rule and tau* of rtmi_crossings) gets
 // a partial step of length tau* L with K and 1/n interpolated linearly in tau along the step.
@@ -193,7 +199,8 @@ template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
     const long o = A.perm ? (long)A.perm[k] : k;
     const size_t P = (size_t)6 * R;
     const T* col = reinterpret_cast<const T*>(A.s_ray) + k;
-    const long last = A.istep[k];
+    long last = A.istep[k];
+    if (A.row_tube && last >= A.rec_rows) last = A.rec_rows - 1;    // beams take a truncated ray's recorded rows
     const Line L = A.L;
     int n = 0;
     if (last >= A.rec_rows) {
@@ -210,6 +217,7 @@ template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
         Tube t{1.0, 0.0, 0.0, 1.0};
         int kmah = 0;
         if (A.row_J) { A.row_J[k] = nsrc * t.q2; A.row_kmah[k] = 0; }
+        if (A.row_tube) put_tube(A.row_tube, R, 0, k, t, nsrc);
         // the next row's three loads go out a step ahead
         double xn = 0.0, yn = 0.0, tn = 0.0;
         if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; tn = (double)col[P + 5 * R]; }
@@ -243,6 +251,7 @@ template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
             kdk(t, len, k0, k1, 0.5 * (w0 + w1));
             kmah += sign_change(q2, t.q2);
             if (A.row_J) { A.row_J[(size_t)i * R + k] = nsrc * t.q2; A.row_kmah[(size_t)i * R + k] = kmah; }
+            if (A.row_tube) put_tube(A.row_tube, R, i, k, t, f.n);
             x0 = x1; y0 = y1; c0 = c1; s0 = s1; k0 = k1; w0 = w1; nl = f.n;
         }
         put(A.at_end, R, o, t, nsrc, nl, kmah);
@@ -312,7 +321,7 @@ RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax,
     PX_TRY(mem.get(&dc, R * sizeof(int32_t)));
     PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
     if (K) PX_TRY(mem.get(&dl, (size_t)K * kCols * R * sizeof(double)));
-    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr};
+    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr, nullptr};
     const dim3 g((unsigned)((R + 255) / 256)), blk(256);
     if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
     else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
@@ -323,12 +332,9 @@ RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax,
     return RTMI_OK;
 }
 
-// J = n0 Q2 and kmah after every recorded row of every ray, into DEVICE buffers of the batch's device ([rec_rows][R], slot order;
-// rows past a ray's last row are left as they were).  The J of a ray's last row is rtmi_paraxial's at_end J, bit for bit: the
-// same kernel with the same arithmetic, storing what it carries.  The checks are rtmi_paraxial's.
-int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah) {
-    const char* who = "rtmi_internal_paraxial_rows";
-    PX_ARG(b && row_J && row_kmah, "rtmi_internal_paraxial_rows: null");
+namespace {
+// rtmi_paraxial's kernel with its per-row outputs (row_J and row_kmah, or row_tube) into DEVICE buffers; rtmi_paraxial's checks
+int paraxial_rows(const char* who, rtmi_batch* b, double* row_J, int32_t* row_kmah, double* row_tube) {
     const rtmi_field* f = nullptr;
     rtmi_params p{};
     int from_state = 0;
@@ -348,13 +354,32 @@ int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah)
     DevMem mem;
     double* de = nullptr;
     PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
-    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah};
+    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah,
+                row_tube};
     const dim3 g((unsigned)((R + 255) / 256)), blk(256);
     if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
     else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
     PX_TRY(hipGetLastError());
     PX_TRY(hipDeviceSynchronize());
     return RTMI_OK;
+}
+}  // namespace
+
+// J = n0 Q2 and kmah after every recorded row of every ray, into DEVICE buffers of the batch's device ([rec_rows][R], slot order;
+// rows past a ray's last row are left as they were).  The J of a ray's last row is rtmi_paraxial's at_end J, bit for bit: the
+// same kernel with the same arithmetic, storing what it carries.  The checks are rtmi_paraxial's.
+int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah) {
+    const char* who = "rtmi_internal_paraxial_rows";
+    PX_ARG(b && row_J && row_kmah, "rtmi_internal_paraxial_rows: null");
+    return paraxial_rows(who, b, row_J, row_kmah, nullptr);
+}
+
+// Q1 P1 Q2 P2 and n after every recorded row ([rec_rows][5][R], slot order), the same kernel storing what it carries; a ray
+// that runs past rec_rows is walked over its recorded rows.  For the Gaussian beams (beams.hip).
+int rtmi_internal_paraxial_tube(rtmi_batch* b, double* row_tube) {
+    const char* who = "rtmi_internal_paraxial_tube";
+    PX_ARG(b && row_tube, "rtmi_internal_paraxial_tube: null");
+    return paraxial_rows(who, b, nullptr, nullptr, row_tube);
 }
 
 RTMI_EXPORT int rtmi_debug_paraxial_rows(rtmi_batch* b, double* J, int32_t* kmah) {

@@ -2072,6 +2072,19 @@ int rtmi_internal_batch_rays(rtmi_batch* b, int64_t* R) {
     return RTMI_OK;
 }
 
+int rtmi_internal_batch_theta0(rtmi_batch* b, double* theta0) {
+    ARG_TRY(b && theta0, "rtmi_internal_batch_theta0: null");
+    DEVICE_TRY(b->field, "rtmi_internal_batch_theta0");
+    const size_t R = (size_t)b->R;
+    std::vector<double> th(R);
+    std::vector<int> perm(b->perm ? R : 0);
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(th.data(), b->launch + 2 * R, R * sizeof(double), hipMemcpyDeviceToHost));
+    if (b->perm) HIP_TRY(hipMemcpy(perm.data(), b->perm, R * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < R; k++) theta0[b->perm ? (size_t)perm[k] : k] = th[k];
+    return RTMI_OK;
+}
+
 // New launch angles (and optionally per-ray max_size) from device memory, then a reset.  The angles replace the batch's stored
 // launch conditions, so that the re-trace of critical rays (which restarts from b->launch) follows them.  Host code only: plain
 // device-to-device copies, which is why a sorted batch (perm) is refused.

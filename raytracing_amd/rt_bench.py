@@ -464,6 +464,17 @@ class Batch:
         return _grid_call(lambda gp, cnt, out, st: lib().rtmi_first_arrival_grid(self._h, M, gp, cnt, out, st),
                           self.R // M if M >= 1 else 0, grid, max_gap, max_dtheta, amplitude, stats)
 
+    def gaussian_beams(self, grid, omegas, eps, fan_size=None, cutoff=None, max_width=None, edge_taper=0, stats=False):
+        """Gaussian beam summation (rtmi_gaussian_beams): the frequency-domain wavefield of each fan's source at every node of
+        grid = (gx0, gdx, nx, gy0, gdy, ny), summed over the fan's beams.  The batch's rays are R / fan_size fans (default: one),
+        each with strictly monotone launch angles.  omegas: the frequencies; eps: the beam parameter (narrowest beams at
+        distance D for eps ~ D / n0); cutoff / max_width: None takes the library's defaults (18, 64 grid spacings); edge_taper:
+        radians of cosine taper at both ends of each fan.  Returns complex128 [S, nw, ny, nx]; with stats=True (u, stats).
+        Needs record_stride 1, op1..op9 and gamma 1."""
+        M = self.R if fan_size is None else int(fan_size)
+        return _beam_call(lambda bp, nw, om, u, st: lib().rtmi_gaussian_beams(self._h, M, bp, nw, om, u, st),
+                          self.R // M if M >= 1 else 0, grid, omegas, eps, cutoff, max_width, edge_taper, stats)
+
     def traveltime_perturb(self, dZ, line=None, kmax=4, stats=False):
         """The Frechet derivative of the reported traveltimes applied to a change dZ [qy, qx] of the field's n samples, the rows
         held fixed (rtmi_traveltime_perturb): returns {"end": [R], "line": [kmax, R], "count": [R]} -- the change of each ray's
@@ -984,6 +995,85 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     if stats:
         res["stats"] = tot
     return res
+
+
+def beam_params(grid, eps, cutoff=None, max_width=None, edge_taper=0):
+    """rtmi_beam_params of grid = (gx0, gdx, nx, gy0, gdy, ny) and the beam parameter eps; None / 0 take the library's defaults"""
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    bp = _lib.BeamParams()
+    bp.gx0 = float(gx0); bp.gdx = float(gdx); bp.nx = int(nx)
+    bp.gy0 = float(gy0); bp.gdy = float(gdy); bp.ny = int(ny)
+    bp.eps = float(eps); bp.cutoff = float(cutoff or 0.0); bp.max_width = float(max_width or 0.0)
+    bp.edge_taper = float(edge_taper or 0.0)
+    return bp
+
+
+def beam_stats(st):
+    return {"segments": st.segments, "tile_entries": st.tile_entries, "pairs_tested": st.pairs_tested,
+            "pairs_inside": st.pairs_inside, "capped": st.capped, "prep_ms": st.prep_ms, "bin_ms": st.bin_ms,
+            "gather_ms": st.gather_ms, "cutoff": st.cutoff, "max_width": st.max_width}
+
+
+def _beam_call(call, S, grid, omegas, eps, cutoff, max_width, edge_taper, stats):
+    bp = beam_params(grid, eps, cutoff, max_width, edge_taper)
+    om = np.ascontiguousarray(np.atleast_1d(omegas), dtype=np.float64)
+    nx, ny = max(int(bp.nx), 0), max(int(bp.ny), 0)
+    u = np.zeros((max(S, 0), len(om), ny, nx, 2))
+    st = _lib.BeamStats()
+    check(call(C.byref(bp), len(om), dptr(om), dptr(u), C.byref(st)))
+    u = u[..., 0] + 1j * u[..., 1]
+    return (u, beam_stats(st)) if stats else u
+
+
+def beam_table(selected_func, field, sources, grid, omegas, *, thetas, eps, step, max_size, box, gamma=1, mem_budget=0,
+               cutoff=None, max_width=None, edge_taper=0, stats=False, **batch_kw):
+    """Gaussian-beam wavefields from many sources onto one grid, by public calls only: traveltime_table's count
+    pass and memory-bounded source groups, then Batch.gaussian_beams per group.  Per row and ray a group holds the record (48
+    bytes in fp64, 24 in fp32) and the beam pass's own 144 (Q1 P1 Q2 P2 n and eleven per-row values), under mem_budget (default
+    8 GiB).  Each source's field depends on its own rays only, so the grouping changes no bit.  Returns complex128
+    [S, nw, ny, nx]; with stats=True (u, stats): rec_rows, groups, count_ms, trace_ms, beam_ms (host wall times) and the beam
+    calls' summed counters."""
+    src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    S, M = len(src), len(th)
+    batch_kw = dict(batch_kw)
+    batch_kw.pop("keep_n_ray", None)
+    t0 = time.perf_counter()
+    c = Batch(field, selected_func, step, max_size, box, gamma, np.tile(th, S), np.repeat(src[:, 0], M), np.repeat(src[:, 1], M),
+              record_stride=0, keep_n_ray=False, **batch_kw)
+    try:
+        c.run()
+        rows = int(c.d_ray()[2].max()) + 1
+    finally:
+        c.close()
+    t1 = time.perf_counter()
+    per_ray = rows * ((48 if field.dtype == F64 else 24) + 144)
+    budget = int(mem_budget) if mem_budget else 8 << 30
+    G = max(1, min(S, budget // max(per_ray * M, 1)))
+    res, tot = None, {"rec_rows": rows, "groups": 0, "count_ms": (t1 - t0) * 1e3, "trace_ms": 0.0, "beam_ms": 0.0}
+    for g0 in range(0, S, G):
+        sg = src[g0:g0 + G]
+        ta = time.perf_counter()
+        b = Batch(field, selected_func, step, max_size, box, gamma, np.tile(th, len(sg)), np.repeat(sg[:, 0], M),
+                  np.repeat(sg[:, 1], M), record_stride=1, rec_rows=rows, keep_n_ray=False, **batch_kw)
+        try:
+            b.run()
+            b.sync()
+            tb = time.perf_counter()
+            u, st = b.gaussian_beams(grid, omegas, eps, fan_size=M, cutoff=cutoff, max_width=max_width, edge_taper=edge_taper,
+                                     stats=True)
+        finally:
+            b.close()
+        tc = time.perf_counter()
+        tot["groups"] += 1
+        tot["trace_ms"] += (tb - ta) * 1e3
+        tot["beam_ms"] += (tc - tb) * 1e3
+        for k in ("segments", "tile_entries", "pairs_tested", "pairs_inside", "capped", "prep_ms", "bin_ms", "gather_ms"):
+            tot[k] = tot.get(k, 0) + st[k]
+        if res is None:
+            res = np.empty((S,) + u.shape[1:], dtype=u.dtype)
+        res[g0:g0 + len(sg)] = u
+    return (res, tot) if stats else res
 
 
 def first_arrivals(selected_func, field, sources, line, receivers_u, **kw):
