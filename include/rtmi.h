@@ -528,6 +528,60 @@ typedef struct {
 int rtmi_gaussian_beams(rtmi_batch *b, int32_t fan_size, const rtmi_beam_params *bp, int32_t nw, const double *omega,
                         double *u, rtmi_beam_stats *st);
 
+/* Kirchhoff migration and modelling from traveltime tables: the diffraction-stack operator pair L^T (traces -> image, optionally
+ * split into opening-angle bins: angle-domain common-image gathers) and L (reflectivity model -> traces), exact transposes of
+ * each other up to rounding, so that the pair passes a dot-product test and can be handed to LSQR.  DESIGN.md section 14.
+ * Inputs, all host fp64 unless said otherwise:
+ *   tables   T [P][ny][nx], and optionally amp [P][ny][nx] and theta [P][ny][nx], for P surface positions on one grid of nx x ny
+ *            nodes (the layout of rtmi_first_arrival_grid's T, G and theta columns; sources and receivers both index this one
+ *            set: reciprocity)
+ *   traces   N traces of nt samples, sample j at time t0 + j dt; trace k has the table indices isrc[k], irec[k] (int32, in [0, P))
+ *            and an optional weight w[k] (absent: 1)
+ *   bins     nbin >= 0 angle bins of width dopen radians (nbin = 0: no angles, theta not needed, one image plane; below,
+ *            nb = max(nbin, 1))
+ * For trace k and node x, with s = isrc[k], r = irec[k], every operation a separate fp64 operation in this order:
+ *     tau = T[s][x] + T[r][x]
+ *     f   = (tau - t0) * inv_dt            inv_dt = 1 / dt, computed once on the host
+ *     j   = floor(f),  a = f - j
+ *     c   = (w[k] * amp[s][x]) * amp[r][x] (factors that are absent are left out, not multiplied by 1)
+ *     nbin > 0:  d = theta[s][x] - theta[r][x];  h = 0.5 * |d - 2 pi rint(d / (2 pi))|;  b = floor(h / dopen)   else b = 0
+ * The pair contributes iff every table value it reads is finite, 0 <= j <= nt - 2, and b < nb.  NaN is how
+ * rtmi_first_arrival_grid marks nodes a fan does not cover; such pairs contribute nothing, silently.
+ *   migrate  image[b][x] += c * (data[k][j] + a * (data[k][j+1] - data[k][j])), accumulated per (b, x) in fp64 in the caller's
+ *            trace order k = 0 .. N-1, starting from 0.  No atomics, no reordering of traces: the result is defined bit for bit
+ *            and a loop over k reproduces it.  One lane per node; a shot-ordered trace list lets a lane keep the source's table
+ *            values while s does not change (a wave-uniform test, not a sort).
+ *   model    data[k][j] += (c * m[b][x]) * (1 - a) and data[k][j+1] += (c * m[b][x]) * a, starting from 0.  Each contribution is
+ *            rounded once to an integer number of quanta 2^scale_exp and the integers are added into 128-bit accumulators (one
+ *            block per trace, its accumulators in LDS): exact and commutative, so the same bits twice in a row and in every
+ *            trace order.  scale_exp = ex - 57, with max|w| max|amp|^2 max|m| = f 2^ex, f in [0.5, 1), the maxima over finite
+ *            values (absent factors 1): a bound that does not depend on order.  One rounding to fp64 per sample at the end.  A
+ *            model value that is not finite contributes nothing.
+ * rtmi_kirchhoff_create copies tables and geometry to the calling thread's current device (fp64 as given); the handle keeps them,
+ * so a least-squares loop applies the pair without uploading them again.  The calling thread's current device must be the
+ * handle's in the other calls.  RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null kp, T, isrc,
+ * irec or out; nx, ny, P, N < 1; nt < 2; nx ny > 2^31; dt or t0 not finite or dt <= 0; nbin < 0, nbin > 32; nbin > 0 with a null
+ * theta or a dopen that is not finite and > 0; an index outside [0, P); a w that is not finite.  Null handle or buffer in the
+ * other calls: RTMI_ERR_ARG.
+ * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), anti-alias filtering of steep
+ * operators, later arrivals (the tables are first arrivals), fp32 storage, device-resident data and image buffers, several GPUs. */
+typedef struct rtmi_kirchhoff rtmi_kirchhoff;
+typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, reserved0; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_params;
+typedef struct {
+    double kernel_ms;        /* device time of the kernel (HIP events) */
+    double upload_ms;        /* host wall time of this call's copy of data / model to the device */
+    int64_t pairs;           /* N nx ny */
+    int64_t contributing;    /* ... of which contribute, counted on the device */
+    int32_t scale_exp;       /* model: the quantum is 2^scale_exp (0 from migrate) */
+    int32_t reserved0;
+    int64_t reserved[4];
+} rtmi_kirchhoff_stats;
+int rtmi_kirchhoff_create(const rtmi_kirchhoff_params *kp, const double *T, const double *amp, const double *theta,
+                          const int32_t *isrc, const int32_t *irec, const double *w, rtmi_kirchhoff **out);
+int rtmi_kirchhoff_migrate(rtmi_kirchhoff *k, const double *data, double *image, rtmi_kirchhoff_stats *st);  /* [N][nt] -> [nb][ny][nx] */
+int rtmi_kirchhoff_model(rtmi_kirchhoff *k, const double *model, double *data, rtmi_kirchhoff_stats *st);    /* [nb][ny][nx] -> [N][nt] */
+void rtmi_kirchhoff_destroy(rtmi_kirchhoff *k);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

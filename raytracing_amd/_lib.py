@@ -96,6 +96,17 @@ class BeamStats(C.Structure):
                 ("cutoff", C.c_double), ("max_width", C.c_double), ("reserved", C.c_double * 4)]
 
 
+class KirchhoffParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("P", C.c_int64), ("N", C.c_int64), ("nt", C.c_int64),
+                ("t0", C.c_double), ("dt", C.c_double), ("nbin", C.c_int32), ("reserved0", C.c_int32), ("dopen", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+
+class KirchhoffStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("upload_ms", C.c_double), ("pairs", C.c_int64), ("contributing", C.c_int64),
+                ("scale_exp", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
 # rtmi_arrival_status
 ARRIVAL_EMPTY, ARRIVAL_CONVERGED, ARRIVAL_STALLED, ARRIVAL_TRUNCATED = -1, 1, 2, 3
 
@@ -139,6 +150,10 @@ SYMBOLS = {
     "rtmi_traveltime_perturb": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _ip, _dp, _dp, C.POINTER(SensitivityStats)]),
     "rtmi_traveltime_backproject": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(SensitivityStats)]),
     "rtmi_gaussian_beams": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BeamParams), C.c_int32, _dp, _dp, C.POINTER(BeamStats)]),
+    "rtmi_kirchhoff_create": (C.c_int, [C.POINTER(KirchhoffParams), _dp, _dp, _dp, _ip, _ip, _dp, C.POINTER(C.c_void_p)]),
+    "rtmi_kirchhoff_migrate": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_model": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_destroy": (None, [C.c_void_p]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

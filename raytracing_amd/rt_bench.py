@@ -1076,6 +1076,96 @@ def beam_table(selected_func, field, sources, grid, omegas, *, thetas, eps, step
     return (res, tot) if stats else res
 
 
+def kirchhoff_stats(st):
+    return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "pairs": int(st.pairs), "contributing": int(st.contributing),
+            "scale_exp": int(st.scale_exp)}
+
+
+class Kirchhoff:
+    """Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_*, include/rtmi.h).  T [P, ny, nx]:
+    traveltime_table's T for P surface positions; isrc, irec [N]: each trace's source and receiver position in [0, P); nt samples
+    per trace at t0 + j dt; amp, theta [P, ny, nx] and weights [N] optional; nbin > 0 splits the image into opening-angle bins of
+    width dopen (needs theta).  The tables stay on the device until close().
+      migrate(data [N, nt]) -> image [nb, ny, nx] ([ny, nx] when nbin == 0), defined bit for bit by the trace order
+      model(m)              -> data [N, nt], the transpose; the same bits in every trace order
+      as_linear_operator()  scipy LinearOperator of shape (N nt, nb ny nx): matvec = model, rmatvec = migrate
+    With stats=True the calls return (result, stats)."""
+
+    def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None):
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 3:
+            raise ValueError("Kirchhoff: T must be [P, ny, nx]")
+        P, ny, nx = T.shape
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (amp, theta)]
+        for a, name in zip(opt, ("amp", "theta")):
+            if a is not None and a.shape != T.shape:
+                raise ValueError(f"Kirchhoff: {name} must have T's shape")
+        si = np.ascontiguousarray(isrc, dtype=np.int32).reshape(-1)
+        ri = np.ascontiguousarray(irec, dtype=np.int32).reshape(-1)
+        if si.shape != ri.shape:
+            raise ValueError("Kirchhoff: isrc and irec must have one length")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w is not None and w.shape != si.shape:
+            raise ValueError("Kirchhoff: weights must have isrc's length")
+        kp = _lib.KirchhoffParams()
+        kp.nx, kp.ny, kp.P, kp.N, kp.nt = nx, ny, P, len(si), int(nt)
+        kp.t0 = float(t0); kp.dt = float(dt); kp.nbin = int(nbin); kp.dopen = float(dopen or 0.0)
+        self.N, self.nt, self.nb, self.nbin, self.ny, self.nx = len(si), int(nt), max(int(nbin), 1), int(nbin), ny, nx
+        self.shape = (self.N * self.nt, self.nb * ny * nx)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().rtmi_kirchhoff_create(C.byref(kp), dptr(T), dptr(opt[0]), dptr(opt[1]), si.ctypes.data_as(_lib._ip),
+                                          ri.ctypes.data_as(_lib._ip), dptr(w), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_table(cls, tab, isrc, irec, nt, dt, t0=0.0, amplitude=False, weights=None, nbin=0, dopen=None):
+        """From traveltime_table's dict: its T, its theta when nbin > 0, and its G as amp when amplitude is asked for."""
+        return cls(tab["T"], isrc, irec, nt, dt, t0=t0, amp=tab["G"] if amplitude else None,
+                   theta=tab["theta"] if nbin else None, weights=weights, nbin=nbin, dopen=dopen)
+
+    def _open(self):
+        if not self._h:
+            raise RuntimeError("Kirchhoff: the handle is closed")
+        return self._h
+
+    def migrate(self, data, stats=False):
+        d = np.ascontiguousarray(data, dtype=np.float64)
+        if d.size != self.N * self.nt:
+            raise ValueError("Kirchhoff.migrate: data must be [N, nt]")
+        img = np.empty((self.nb, self.ny, self.nx))
+        st = _lib.KirchhoffStats()
+        check(lib().rtmi_kirchhoff_migrate(self._open(), dptr(d), dptr(img), C.byref(st)))
+        if self.nbin == 0:
+            img = img[0]
+        return (img, kirchhoff_stats(st)) if stats else img
+
+    def model(self, m, stats=False):
+        mm = np.ascontiguousarray(m, dtype=np.float64)
+        if mm.size != self.nb * self.ny * self.nx:
+            raise ValueError("Kirchhoff.model: m must be [nb, ny, nx]")
+        d = np.empty((self.N, self.nt))
+        st = _lib.KirchhoffStats()
+        check(lib().rtmi_kirchhoff_model(self._open(), dptr(mm), dptr(d), C.byref(st)))
+        return (d, kirchhoff_stats(st)) if stats else d
+
+    def as_linear_operator(self):
+        from scipy.sparse.linalg import LinearOperator
+        return LinearOperator(self.shape, matvec=lambda m: self.model(m).reshape(-1),
+                              rmatvec=lambda d: self.migrate(d).reshape(-1), dtype=np.float64)
+
+    def close(self):
+        if self._h:
+            lib().rtmi_kirchhoff_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def first_arrivals(selected_func, field, sources, line, receivers_u, **kw):
     """The [S, J] table of first-arrival traveltimes (NaN where no ray converged): two_point's smallest T."""
     r = two_point(selected_func, field, sources, line, receivers_u, **kw)

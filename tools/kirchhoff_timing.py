@@ -1,0 +1,104 @@
+"""Times rtmi_kirchhoff_migrate and rtmi_kirchhoff_model on a survey-sized case: vert_heterogeneous closed-form tables (v = 18 +
+2 y), 64 sources x 256 receivers drawn from 256 positions at y = -2.4 (16 384 traces, shot-ordered), 512 x 256 nodes over the
+box, nt = 2 048 at dt = 0.0005; each kernel without angle bins and with 16.  Medians of --reps calls: the kernel's HIP-event
+time (rtmi_kirchhoff_stats.kernel_ms) and the host wall time of the whole call (copies included), against the bytes floor --
+every table, trace and image access counted once, at 6 TB/s.  Also the numpy restatement's time on the tests' standard case,
+for contrast.  Each case runs in a child process of its own under a time limit, and the first failure ends the run.  Prints
+one JSON line per measurement.
+Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+POS_Y = -2.4
+CASES = ("migrate", "migrate_bins16", "model", "model_bins16")
+LIMIT_S = 240
+
+
+def tables(pos_x, grid):
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    X, Y = np.meshgrid(gx0 + np.arange(nx) * gdx, gy0 + np.arange(ny) * gdy)
+    T, th = [], []
+    for xs in pos_x:
+        r2 = (X - xs) ** 2 + (Y - POS_Y) ** 2
+        T.append(0.5 * np.arccosh(1.0 + 2.0 * r2 / ((18.0 + 2.0 * POS_Y) * (18.0 + 2.0 * Y))))
+        xc = ((X ** 2 - xs ** 2) + (Y + 9) ** 2 - (POS_Y + 9) ** 2) / (2 * (X - xs))
+        sg = np.sign(xc - xs)
+        th.append(np.arctan2(-sg * (X - xc), sg * (Y + 9)))
+    return np.stack(T), np.stack(th)
+
+
+def run_case(name, reps):
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, th = tables(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    N, nn = len(isrc), T[0].size
+    nbin = 16 if name.endswith("bins16") else 0
+    nb = max(nbin, 1)
+    op = rb.Kirchhoff(T, isrc, irec, nt, dt, theta=th if nbin else None, nbin=nbin, dopen=np.pi / 32 if nbin else None)
+    rng = np.random.default_rng(1)
+    tab = 2 if nbin else 1                                   # T, and theta with bins
+    if name.startswith("migrate"):
+        x = rng.standard_normal((N, nt))
+        call = lambda: op.migrate(x, stats=True)[1]          # noqa: E731
+        nbytes = 8 * ((N + len(src)) * nn * tab + N * nt + nb * nn)
+    else:
+        x = rng.standard_normal((nb,) + T.shape[1:])
+        call = lambda: op.model(x, stats=True)[1]            # noqa: E731
+        nbytes = 8 * (2 * N * nn * tab + N * nn + N * nt)
+    call()                                                   # warm-up: code objects
+    ks, ws = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        st = call()
+        ws.append((time.perf_counter() - t0) * 1e3)
+        ks.append(st["kernel_ms"])
+    op.close()
+    k = float(np.median(ks))
+    print(json.dumps({"what": name, "N": N, "nodes": nn, "nt": nt, "nbin": nbin, "pairs": st["pairs"], "contributing": st["contributing"],
+                      "kernel_ms_median": k, "kernel_ms": ks, "wall_ms_median": float(np.median(ws)), "upload_ms": st["upload_ms"],
+                      "bytes": nbytes, "floor_ms_at_6TBps": nbytes / 6e12 * 1e3, "pairs_per_s": st["pairs"] / (k * 1e-3),
+                      "scale_exp": st["scale_exp"]}), flush=True)
+
+
+def restatement():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import kirchhoff_ref as K
+    isrc, irec = K.geometry()
+    T = K.closed_T()
+    d = K.scatterer_data(isrc, irec)
+    t0 = time.perf_counter()
+    _, cnt = K.migrate(T, isrc, irec, d, K.DT)
+    t = time.perf_counter() - t0
+    print(json.dumps({"what": "numpy restatement, migrate, standard case", "pairs": len(isrc) * T[0].size, "contributing": cnt,
+                      "seconds": t, "pairs_per_s": len(isrc) * T[0].size / t}), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--case", choices=CASES + ("restatement",))
+    a = ap.parse_args()
+    if a.case == "restatement":
+        restatement()
+    elif a.case:
+        run_case(a.case, a.reps)
+    else:
+        for c in CASES + ("restatement",):
+            rc = subprocess.call(["timeout", "-k", "10", str(LIMIT_S), sys.executable, os.path.abspath(__file__), "--case", c,
+                                  "--reps", str(a.reps)])
+            if rc != 0:
+                sys.exit(f"kirchhoff_timing: case {c} ended with status {rc}; stopping")
