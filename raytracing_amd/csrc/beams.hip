@@ -17,25 +17,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
 #include "rt_crossing.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
-#define BM_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define BM_ARG(cond, msg)                                                    \
-    do {                                                                     \
-        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
-    } while (0)
-#define BM_RC(expr)                  \
-    do {                             \
-        const int rc_ = (expr);      \
-        if (rc_) return rc_;         \
-    } while (0)
+#include "rtmi_host.h"
 
 namespace {
 
@@ -338,74 +321,37 @@ __global__ __launch_bounds__(kBlock) void k_gather(Beam B, GatherArgs A) {
     }
 }
 
-__global__ void k_inverse(const int32_t* perm, int32_t* slot, long R) {
-    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < R) slot[perm[k]] = (int32_t)k;
-}
-
-// device allocations of one call, freed on every way out
-struct DevMem {
-    std::vector<void*> p;
-    template <typename T> hipError_t get(T** out, size_t bytes) {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
-        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
-        return e;
-    }
-    ~DevMem() { for (void* v : p) (void)hipFree(v); }
-};
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
-};
-
-dim3 blocks(long n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace
 
 RTMI_EXPORT int rtmi_gaussian_beams(rtmi_batch* b, int32_t fan_size, const rtmi_beam_params* bp, int32_t nw, const double* omega,
                                     double* u, rtmi_beam_stats* st) {
     const char* who = "rtmi_gaussian_beams";
     // ---- arguments, on the host
-    BM_ARG(bp && omega && u, "rtmi_gaussian_beams: null");
-    BM_ARG(bp->nx >= 1 && bp->ny >= 1, "rtmi_gaussian_beams: nx and ny must be >= 1");
-    BM_ARG((double)bp->nx * (double)bp->ny <= (double)(1L << 31), "rtmi_gaussian_beams: more than 2^31 nodes per source");
-    BM_ARG(bp->gdx > 0.0 && bp->gdy > 0.0 && std::isfinite(bp->gdx) && std::isfinite(bp->gdy),
-           "rtmi_gaussian_beams: gdx and gdy must be finite and > 0");
-    BM_ARG(std::isfinite(bp->gx0) && std::isfinite(bp->gy0), "rtmi_gaussian_beams: gx0 and gy0 must be finite");
-    BM_ARG(bp->eps > 0.0 && std::isfinite(bp->eps), "rtmi_gaussian_beams: eps must be finite and > 0");
-    BM_ARG(bp->cutoff >= 0.0 && std::isfinite(bp->cutoff) && bp->max_width >= 0.0 && std::isfinite(bp->max_width) &&
-               bp->edge_taper >= 0.0 && std::isfinite(bp->edge_taper),
-           "rtmi_gaussian_beams: cutoff, max_width and edge_taper must be finite and >= 0");
-    BM_ARG(nw >= 1, "rtmi_gaussian_beams: nw must be >= 1");
+    RTMI_ARG(bp && omega && u, "null");
+    RTMI_RC(check_grid_axes(who, *bp));
+    RTMI_ARG(bp->eps > 0.0 && std::isfinite(bp->eps), "eps must be finite and > 0");
+    RTMI_ARG(bp->cutoff >= 0.0 && std::isfinite(bp->cutoff) && bp->max_width >= 0.0 && std::isfinite(bp->max_width) &&
+                 bp->edge_taper >= 0.0 && std::isfinite(bp->edge_taper),
+             "cutoff, max_width and edge_taper must be finite and >= 0");
+    RTMI_ARG(nw >= 1, "nw must be >= 1");
     double omin = INFINITY;
     for (int32_t q = 0; q < nw; q++) {
-        BM_ARG(omega[q] > 0.0 && std::isfinite(omega[q]), "rtmi_gaussian_beams: every omega must be finite and > 0");
+        RTMI_ARG(omega[q] > 0.0 && std::isfinite(omega[q]), "every omega must be finite and > 0");
         omin = omega[q] < omin ? omega[q] : omin;
     }
-    BM_ARG(b, "rtmi_gaussian_beams: null batch");
-    BM_ARG(fan_size >= 2, "rtmi_gaussian_beams: fan_size must be >= 2");
-    const rtmi_field* f = nullptr;
-    rtmi_params p{};
-    int from_state = 0;
-    BM_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
-    BM_ARG(p.record_stride == 1, "rtmi_gaussian_beams: needs the full trajectory (record_stride 1)");
-    BM_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
-           "rtmi_gaussian_beams: isotropic media only (op1..op9, gamma 1), as rtmi_paraxial");
-    if (from_state)
-        return rtmi_internal_fail(RTMI_ERR_STATE, "rtmi_gaussian_beams: rtmi_batch_set_state gave rays a row other than 0: their "
-                                                  "rows before it are not a trajectory from the source (reset the batch)");
-    int64_t nrays = 0;
-    BM_RC(rtmi_internal_batch_rays(b, &nrays));
-    BM_ARG(nrays % fan_size == 0, "rtmi_gaussian_beams: the batch's ray count is not a multiple of fan_size");
-    const long R = (long)nrays, M = fan_size, S = R / M;
+    RTMI_ARG(b, "null batch");
+    RTMI_ARG(fan_size >= 2, "fan_size must be >= 2");
+    Recorded rec;
+    RTMI_RC(recorded(who, b, kRecIsotropic | kRecFromLaunch, fan_size, &rec));
+    const rtmi_device_view& v = rec.v;
+    const long R = (long)v.R, M = fan_size, S = R / M;
     std::vector<double> th0(R), w(R);
-    BM_RC(rtmi_internal_batch_theta0(b, th0.data()));
+    RTMI_RC(rtmi_internal_batch_theta0(b, th0.data()));
     for (long s = 0; s < S; s++) {
         const double* t = th0.data() + s * M;
         const double dir = t[1] > t[0] ? 1.0 : -1.0;
         for (long m = 1; m < M; m++)
-            BM_ARG(dir * (t[m] - t[m - 1]) > 0.0, "rtmi_gaussian_beams: launch angles must be strictly monotone within a fan");
+            RTMI_ARG(dir * (t[m] - t[m - 1]) > 0.0, "launch angles must be strictly monotone within a fan");
         for (long m = 0; m < M; m++) {
             double q = 0.5 * fabs(t[m < M - 1 ? m + 1 : m] - t[m > 0 ? m - 1 : m]);
             const double d = fmin(fabs(t[m] - t[0]), fabs(t[m] - t[M - 1]));
@@ -417,104 +363,101 @@ RTMI_EXPORT int rtmi_gaussian_beams(rtmi_batch* b, int32_t fan_size, const rtmi_
            (int)((bp->ny + kTile - 1) / kTile), 0, bp->eps, bp->cutoff > 0.0 ? bp->cutoff : kCutoff,
            bp->max_width > 0.0 ? bp->max_width : kWidthCells * (bp->gdx > bp->gdy ? bp->gdx : bp->gdy), omin};
     B.ntiles = (long)B.ntx * B.nty;
-    BM_ARG((double)S * (double)B.ntiles < 2147483648.0, "rtmi_gaussian_beams: more than 2^31 tiles");
+    RTMI_ARG((double)S * (double)B.ntiles < 2147483648.0, "more than 2^31 tiles");
 
     // ---- (1) prep
-    rtmi_device_view v;
-    BM_RC(rtmi_batch_view(b, &v));          // drains the rays handed over to the re-trace of critical rays
-    BM_RC(rtmi_sync(b));
     DevMem mem;
-    Events ev;
-    for (hipEvent_t& e : ev.e) BM_TRY(hipEventCreate(&e));
+    EventMarks<4> ev;
+    RTMI_HIP(ev.create());
     unsigned long long* ctr = nullptr;
-    BM_TRY(mem.get(&ctr, C_N * sizeof(unsigned long long)));
-    BM_TRY(hipMemset(ctr, 0, C_N * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&ctr, C_N * sizeof(unsigned long long)));
+    RTMI_HIP(hipMemset(ctr, 0, C_N * sizeof(unsigned long long)));
     double *tube = nullptr, *dw = nullptr;
     int32_t* slot = nullptr;
     long long *nrows = nullptr, *rowbase = nullptr;
-    BM_TRY(mem.get(&tube, (size_t)v.rec_rows * 5 * R * sizeof(double)));
-    BM_TRY(mem.get(&dw, (size_t)R * sizeof(double)));
-    BM_TRY(mem.get(&nrows, (size_t)(R + 1) * sizeof(long long)));
-    BM_TRY(mem.get(&rowbase, (size_t)(R + 1) * sizeof(long long)));
-    BM_TRY(hipMemcpy(dw, w.data(), (size_t)R * sizeof(double), hipMemcpyHostToDevice));
-    BM_TRY(hipEventRecord(ev.e[0], nullptr));
-    BM_RC(rtmi_internal_paraxial_tube(b, tube));
+    RTMI_HIP(mem.get(&tube, (size_t)v.rec_rows * 5 * R * sizeof(double)));
+    RTMI_HIP(mem.get(&dw, (size_t)R * sizeof(double)));
+    RTMI_HIP(mem.get(&nrows, (size_t)(R + 1) * sizeof(long long)));
+    RTMI_HIP(mem.get(&rowbase, (size_t)(R + 1) * sizeof(long long)));
+    RTMI_HIP(hipMemcpy(dw, w.data(), (size_t)R * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(ev.mark(0));
+    RTMI_RC(rtmi_internal_paraxial_tube(who, b, tube));
     if (v.perm) {
-        BM_TRY(mem.get(&slot, (size_t)R * sizeof(int32_t)));
-        hipLaunchKernelGGL(k_inverse, blocks(R), dim3(256), 0, nullptr, v.perm, slot, R);
-        BM_TRY(hipGetLastError());
+        RTMI_HIP(mem.get(&slot, (size_t)R * sizeof(int32_t)));
+        hipLaunchKernelGGL(k_inverse<int32_t>, blocks(R), dim3(256), 0, nullptr, v.perm, slot, R);
+        RTMI_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_rows, blocks(R + 1), dim3(256), 0, nullptr, v.istep, slot, R, (long)v.rec_rows, nrows);
-    BM_TRY(hipGetLastError());
+    RTMI_HIP(hipGetLastError());
     size_t scan_bytes = 0;
     void* scan_tmp = nullptr;
-    BM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nrows, rowbase, (int)(R + 1)));
-    BM_TRY(mem.get(&scan_tmp, scan_bytes));
-    BM_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, nrows, rowbase, (int)(R + 1)));
+    RTMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nrows, rowbase, (int)(R + 1)));
+    RTMI_HIP(mem.get(&scan_tmp, scan_bytes));
+    RTMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, nrows, rowbase, (int)(R + 1)));
     long long Gll = 0;
-    BM_TRY(hipMemcpy(&Gll, rowbase + R, sizeof(long long), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(&Gll, rowbase + R, sizeof(long long), hipMemcpyDeviceToHost));
     const long G = (long)Gll, nseg = G - R;
-    BM_ARG(G < 2147483647L, "rtmi_gaussian_beams: more than 2^31 recorded rows in the batch");
+    RTMI_ARG(G < 2147483647L, "more than 2^31 recorded rows in the batch");
     double* rv = nullptr;
     int32_t* row_ray = nullptr;
     uint32_t* seg_row = nullptr;
-    BM_TRY(mem.get(&rv, (size_t)kRowCols * G * sizeof(double)));
-    BM_TRY(mem.get(&row_ray, (size_t)G * sizeof(int32_t)));
-    BM_TRY(mem.get(&seg_row, (size_t)nseg * sizeof(uint32_t)));
+    RTMI_HIP(mem.get(&rv, (size_t)kRowCols * G * sizeof(double)));
+    RTMI_HIP(mem.get(&row_ray, (size_t)G * sizeof(int32_t)));
+    RTMI_HIP(mem.get(&seg_row, (size_t)nseg * sizeof(uint32_t)));
     const PrepArgs pa{v.s_ray, v.istep, slot, tube, rowbase, dw, R, (long)v.rec_rows, G, bp->eps, rv, row_ray, seg_row};
     if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_prep<double>, blocks(R), dim3(256), 0, nullptr, pa);
     else hipLaunchKernelGGL(k_prep<float>, blocks(R), dim3(256), 0, nullptr, pa);
-    BM_TRY(hipGetLastError());
-    BM_TRY(hipEventRecord(ev.e[1], nullptr));
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
 
     // ---- (2) binning
     const long tiles = S * B.ntiles;
     uint32_t *begin = nullptr, *end = nullptr;
-    BM_TRY(mem.get(&begin, (size_t)tiles * sizeof(uint32_t)));
-    BM_TRY(mem.get(&end, (size_t)tiles * sizeof(uint32_t)));
-    BM_TRY(hipMemset(begin, 0, (size_t)tiles * sizeof(uint32_t)));
-    BM_TRY(hipMemset(end, 0, (size_t)tiles * sizeof(uint32_t)));
+    RTMI_HIP(mem.get(&begin, (size_t)tiles * sizeof(uint32_t)));
+    RTMI_HIP(mem.get(&end, (size_t)tiles * sizeof(uint32_t)));
+    RTMI_HIP(hipMemset(begin, 0, (size_t)tiles * sizeof(uint32_t)));
+    RTMI_HIP(hipMemset(end, 0, (size_t)tiles * sizeof(uint32_t)));
     unsigned long long *cnt = nullptr, *offs = nullptr;
-    BM_TRY(mem.get(&cnt, (size_t)(nseg + 1) * sizeof(unsigned long long)));
-    BM_TRY(mem.get(&offs, (size_t)(nseg + 1) * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&cnt, (size_t)(nseg + 1) * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&offs, (size_t)(nseg + 1) * sizeof(unsigned long long)));
     BinArgs ba{rv, G, nseg, seg_row, row_ray, (int)M, cnt, offs, nullptr, nullptr, ctr};
     hipLaunchKernelGGL(k_count, blocks(nseg + 1), dim3(256), 0, nullptr, B, ba);
-    BM_TRY(hipGetLastError());
+    RTMI_HIP(hipGetLastError());
     size_t cnt_bytes = 0;
     void* cnt_tmp = nullptr;
-    BM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cnt_bytes, cnt, offs, (int)(nseg + 1)));
-    BM_TRY(mem.get(&cnt_tmp, cnt_bytes));
-    BM_TRY(hipcub::DeviceScan::ExclusiveSum(cnt_tmp, cnt_bytes, cnt, offs, (int)(nseg + 1)));
+    RTMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cnt_bytes, cnt, offs, (int)(nseg + 1)));
+    RTMI_HIP(mem.get(&cnt_tmp, cnt_bytes));
+    RTMI_HIP(hipcub::DeviceScan::ExclusiveSum(cnt_tmp, cnt_bytes, cnt, offs, (int)(nseg + 1)));
     unsigned long long E = 0;
-    BM_TRY(hipMemcpy(&E, offs + nseg, sizeof(E), hipMemcpyDeviceToHost));
-    BM_ARG(E < 2147483648ull, "rtmi_gaussian_beams: more than 2^31 tile entries (a smaller grid or fewer sources per call)");
+    RTMI_HIP(hipMemcpy(&E, offs + nseg, sizeof(E), hipMemcpyDeviceToHost));
+    RTMI_ARG(E < 2147483648ull, "more than 2^31 tile entries (a smaller grid or fewer sources per call)");
     const uint32_t* sorted = nullptr;
     if (E > 0) {
         uint32_t *keys = nullptr, *keys2 = nullptr, *vals = nullptr, *vals2 = nullptr;
-        BM_TRY(mem.get(&keys, E * sizeof(uint32_t)));
-        BM_TRY(mem.get(&keys2, E * sizeof(uint32_t)));
-        BM_TRY(mem.get(&vals, E * sizeof(uint32_t)));
-        BM_TRY(mem.get(&vals2, E * sizeof(uint32_t)));
+        RTMI_HIP(mem.get(&keys, E * sizeof(uint32_t)));
+        RTMI_HIP(mem.get(&keys2, E * sizeof(uint32_t)));
+        RTMI_HIP(mem.get(&vals, E * sizeof(uint32_t)));
+        RTMI_HIP(mem.get(&vals2, E * sizeof(uint32_t)));
         ba.keys = keys; ba.vals = vals;
         hipLaunchKernelGGL(k_fill, blocks(nseg), dim3(256), 0, nullptr, B, ba);
-        BM_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
         int bits = 1;
         while (bits < 32 && ((unsigned long long)tiles >> bits) != 0ull) bits++;
         size_t sort_bytes = 0;
         void* sort_tmp = nullptr;
-        BM_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, keys2, vals, vals2, (int)E, 0, bits));
-        BM_TRY(mem.get(&sort_tmp, sort_bytes));
-        BM_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys, keys2, vals, vals2, (int)E, 0, bits));
+        RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, keys2, vals, vals2, (int)E, 0, bits));
+        RTMI_HIP(mem.get(&sort_tmp, sort_bytes));
+        RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys, keys2, vals, vals2, (int)E, 0, bits));
         hipLaunchKernelGGL(k_ranges, blocks((long)E), dim3(256), 0, nullptr, keys2, (long)E, begin, end);
-        BM_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
         sorted = vals2;
     }
-    BM_TRY(hipEventRecord(ev.e[2], nullptr));
+    RTMI_HIP(ev.mark(2));
 
     // ---- (3) gather, kNwb frequencies per launch
     double* du = nullptr;
     const size_t un = (size_t)S * nw * bp->ny * bp->nx * 2;
-    BM_TRY(mem.get(&du, un * sizeof(double)));
+    RTMI_HIP(mem.get(&du, un * sizeof(double)));
     for (int32_t w0 = 0; w0 < nw; w0 += kNwb) {
         GatherArgs ga{};
         ga.rv = rv; ga.G = G; ga.vals = sorted; ga.begin = begin; ga.end = end;
@@ -522,24 +465,20 @@ RTMI_EXPORT int rtmi_gaussian_beams(rtmi_batch* b, int32_t fan_size, const rtmi_
         for (int q = 0; q < kNwb; q++) ga.om[q] = q < ga.nwg ? omega[w0 + q] : 0.0;
         ga.w0 = w0; ga.nw = nw; ga.u = du; ga.ctr = ctr; ga.count_pairs = w0 == 0;
         hipLaunchKernelGGL(k_gather, dim3((unsigned)tiles), dim3(kBlock), 0, nullptr, B, ga);
-        BM_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
     }
-    BM_TRY(hipEventRecord(ev.e[3], nullptr));
-    BM_TRY(hipEventSynchronize(ev.e[3]));
-    BM_TRY(hipMemcpy(u, du, un * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(ev.mark(3));
+    RTMI_HIP(ev.wait(3));
+    RTMI_HIP(hipMemcpy(u, du, un * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         unsigned long long c[C_N];
-        BM_TRY(hipMemcpy(c, ctr, sizeof(c), hipMemcpyDeviceToHost));
+        RTMI_HIP(hipMemcpy(c, ctr, sizeof(c), hipMemcpyDeviceToHost));
         *st = rtmi_beam_stats{};
         st->segments = nseg; st->tile_entries = (int64_t)E;
         st->pairs_tested = (int64_t)c[C_TESTED]; st->pairs_inside = (int64_t)c[C_INSIDE]; st->capped = (int64_t)c[C_CAPPED];
         st->cutoff = B.cutoff; st->max_width = B.maxw;
         double* ms[3] = {&st->prep_ms, &st->bin_ms, &st->gather_ms};
-        for (int q = 0; q < 3; q++) {
-            float t = 0.0f;
-            BM_TRY(hipEventElapsedTime(&t, ev.e[q], ev.e[q + 1]));
-            *ms[q] = t;
-        }
+        for (int q = 0; q < 3; q++) RTMI_HIP(ev.ms(q, q + 1, ms[q]));
     }
     return RTMI_OK;
 }

@@ -7,7 +7,7 @@
 //        T, amp and theta of the source are kept while the source index does not change (a wave-uniform test).
 //   L    one block per trace.  The trace's samples are two-word (128-bit) fixed-point accumulators in LDS; the lanes sweep the
 //        nodes, round each contribution once to an integer number of quanta 2^scale_exp and add it with a returning 64-bit LDS
-//        atomic (the carry into the high word is read off the returned old value: sensitivity.hip's add128).  Integer sums
+//        atomic (the carry into the high word is read off the returned old value: rt_fix128.h).  Integer sums
 //        commute, so the result has the same bits in every schedule and trace order.  The block converts and stores its trace.
 // The tables and the geometry live on the device in the handle; data and image cross the bus on every call.
 #include <hip/hip_runtime.h>
@@ -20,24 +20,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
-#define KH_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define KH_ARG(cond, msg)                                                                          \
-    do {                                                                                           \
-        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": " + (msg)).c_str()); \
-    } while (0)
+#include "rt_fix128.h"
+#include "rtmi_host.h"
 
 namespace {
 
 constexpr int kMaxBins = 32;
-constexpr int kFixBits = 57;          // a contribution is below 2^57 quanta (2^58 with its roundings): it fits an int64
 constexpr int kWindow = 4096;         // samples of a trace held in LDS at a time: 4096 x 16 B = 64 KiB
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 
@@ -141,38 +129,7 @@ __global__ void k_migrate(KArgs A, const double* __restrict__ data, double* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------ L
-// Sample i's accumulator is (lo[i], hi[i]) = hi 2^64 + lo - 2^63 quanta: lo starts at the bias 2^63, so that sums of either sign
-// stay clear of the word's ends and the high word is touched only on a real carry.
-__device__ __forceinline__ void add128(unsigned long long* lo, unsigned long long* hi, int i, long long s) {
-    if (s == 0) return;
-    const unsigned long long a = (unsigned long long)s;
-    const unsigned long long old = atomicAdd(lo + i, a);
-    const unsigned long long h = (s < 0 ? ~0ull : 0ull) + ((old + a) < old ? 1ull : 0ull);
-    if (h) atomicAdd(hi + i, h);
-}
-
-// hi 2^64 + lo - 2^63 as the nearest double (ties to even): one rounding.
-__device__ __forceinline__ double fix_to_double(unsigned long long lo, unsigned long long hi) {
-    if (!(lo >> 63)) hi -= 1ull;                              // the borrow of lo - 2^63
-    lo ^= 1ull << 63;
-    const bool neg = (hi >> 63) != 0;
-    if (neg) {                                                // two's complement negation of (hi, lo)
-        lo = ~lo + 1ull;
-        hi = ~hi + (lo == 0 ? 1ull : 0ull);
-    }
-    double v;
-    if (hi == 0) {
-        v = (double)lo;
-    } else {
-        const int sh = __clzll((long long)hi);                // 0 .. 63; the top 64 bits, the rest folded into a sticky bit
-        unsigned long long top = sh ? ((hi << sh) | (lo >> (64 - sh))) : hi;
-        const unsigned long long rest = sh ? (lo << sh) : lo;
-        top |= rest ? 1ull : 0ull;
-        v = ldexp((double)top, 64 - sh);
-    }
-    return neg ? -v : v;
-}
-
+// Sample i's accumulator is (lo[i], hi[i]) of rt_fix128.h.
 // One block per trace; data [N][nt]; counts [N].  The trace is processed in windows of at most kWindow samples.
 template <bool AMP, bool BINS>
 __global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, double* __restrict__ data,
@@ -194,7 +151,7 @@ __global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, dou
     unsigned long long cnt = 0;
     for (long j0 = 0; j0 < A.nt; j0 += W) {
         const long j1 = (j0 + W < A.nt) ? j0 + W : A.nt;      // the window [j0, j1)
-        for (int i = tid; i < W; i += BS) { lo[i] = 1ull << 63; hi[i] = 0ull; }
+        for (int i = tid; i < W; i += BS) { lo[i] = rt::kFixBias; hi[i] = 0ull; }
         __syncthreads();
 #pragma unroll 2
         for (long x = tid; x < A.nn; x += BS) {
@@ -206,11 +163,11 @@ __global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, dou
             const double cm = p.c * m[(size_t)p.b * A.nn + x];
             if (!(fabs(cm) < INFINITY)) continue;             // a non-finite model value contributes nothing
             const double v0 = cm * (1.0 - p.a), v1 = cm * p.a;
-            if (p.j >= j0) add128(lo, hi, (int)(p.j - j0), (long long)rint(ldexp(v0, -e)));
-            if (p.j + 1 < j1) add128(lo, hi, (int)(p.j + 1 - j0), (long long)rint(ldexp(v1, -e)));
+            if (p.j >= j0) (void)rt::add128(lo, hi, (int)(p.j - j0), (long long)rint(ldexp(v0, -e)));
+            if (p.j + 1 < j1) (void)rt::add128(lo, hi, (int)(p.j + 1 - j0), (long long)rint(ldexp(v1, -e)));
         }
         __syncthreads();
-        for (long i = tid; i < j1 - j0; i += BS) data[(size_t)k * A.nt + j0 + i] = ldexp(fix_to_double(lo[i], hi[i]), e);
+        for (long i = tid; i < j1 - j0; i += BS) data[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(lo[i], hi[i]), e);
         __syncthreads();
     }
     cnt = wave_sum(cnt);
@@ -222,11 +179,6 @@ __global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, dou
         counts[k] = t;
     }
 }
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -259,14 +211,14 @@ int migrate_block(int nb) { return nb > 16 ? 128 : 256; }    // [bin][lane] fp64
 
 int check_device(const rtmi_kirchhoff* k, const char* who) {
     int dev = -1;
-    KH_TRY(hipGetDevice(&dev));
-    KH_ARG(dev == k->device, "the calling thread's current device is not the handle's");
+    RTMI_HIP(hipGetDevice(&dev));
+    RTMI_ARG(dev == k->device, "the calling thread's current device is not the handle's");
     return RTMI_OK;
 }
 
 int read_counts(const rtmi_kirchhoff* k, size_t n, int64_t* total, const char* who) {
     std::vector<unsigned long long> h(n);
-    KH_TRY(hipMemcpy(h.data(), k->counts, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(h.data(), k->counts, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     unsigned long long t = 0;
     for (unsigned long long v : h) t += v;
     *total = (int64_t)t;
@@ -278,36 +230,36 @@ int read_counts(const rtmi_kirchhoff* k, size_t n, int64_t* total, const char* w
 RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const double* T, const double* amp, const double* theta,
                                       const int32_t* isrc, const int32_t* irec, const double* w, rtmi_kirchhoff** out) {
     const char* who = "rtmi_kirchhoff_create";
-    KH_ARG(out, "null out");
+    RTMI_ARG(out, "null out");
     *out = nullptr;
-    KH_ARG(kp, "null kp");
-    KH_ARG(T, "null T");
-    KH_ARG(isrc, "null isrc");
-    KH_ARG(irec, "null irec");
-    KH_ARG(kp->nx >= 1, "nx must be >= 1");
-    KH_ARG(kp->ny >= 1, "ny must be >= 1");
-    KH_ARG(kp->P >= 1, "P must be >= 1");
-    KH_ARG(kp->N >= 1, "N must be >= 1");
-    KH_ARG(kp->nt >= 2, "nt must be >= 2");
-    KH_ARG(kp->nx <= (1ll << 31) && kp->ny <= (1ll << 31) && kp->nx * kp->ny <= (1ll << 31), "nx ny must be <= 2^31");
-    KH_ARG(kp->P <= INT32_MAX, "P must fit the int32 indices");
-    KH_ARG(kp->N <= INT32_MAX, "N must be below 2^31 (one block per trace)");
-    KH_ARG(std::isfinite(kp->dt) && kp->dt > 0.0, "dt must be finite and > 0");
-    KH_ARG(std::isfinite(kp->t0), "t0 must be finite");
-    KH_ARG(kp->nbin >= 0 && kp->nbin <= kMaxBins, "nbin must be in 0..32");
+    RTMI_ARG(kp, "null kp");
+    RTMI_ARG(T, "null T");
+    RTMI_ARG(isrc, "null isrc");
+    RTMI_ARG(irec, "null irec");
+    RTMI_ARG(kp->nx >= 1, "nx must be >= 1");
+    RTMI_ARG(kp->ny >= 1, "ny must be >= 1");
+    RTMI_ARG(kp->P >= 1, "P must be >= 1");
+    RTMI_ARG(kp->N >= 1, "N must be >= 1");
+    RTMI_ARG(kp->nt >= 2, "nt must be >= 2");
+    RTMI_ARG(kp->nx <= (1ll << 31) && kp->ny <= (1ll << 31) && kp->nx * kp->ny <= (1ll << 31), "nx ny must be <= 2^31");
+    RTMI_ARG(kp->P <= INT32_MAX, "P must fit the int32 indices");
+    RTMI_ARG(kp->N <= INT32_MAX, "N must be below 2^31 (one block per trace)");
+    RTMI_ARG(std::isfinite(kp->dt) && kp->dt > 0.0, "dt must be finite and > 0");
+    RTMI_ARG(std::isfinite(kp->t0), "t0 must be finite");
+    RTMI_ARG(kp->nbin >= 0 && kp->nbin <= kMaxBins, "nbin must be in 0..32");
     if (kp->nbin > 0) {
-        KH_ARG(theta, "nbin > 0 needs theta");
-        KH_ARG(std::isfinite(kp->dopen) && kp->dopen > 0.0, "dopen must be finite and > 0");
+        RTMI_ARG(theta, "nbin > 0 needs theta");
+        RTMI_ARG(std::isfinite(kp->dopen) && kp->dopen > 0.0, "dopen must be finite and > 0");
     }
     for (int64_t k = 0; k < kp->N; k++) {
-        KH_ARG(isrc[k] >= 0 && isrc[k] < kp->P, "isrc has an index outside [0, P)");
-        KH_ARG(irec[k] >= 0 && irec[k] < kp->P, "irec has an index outside [0, P)");
+        RTMI_ARG(isrc[k] >= 0 && isrc[k] < kp->P, "isrc has an index outside [0, P)");
+        RTMI_ARG(irec[k] >= 0 && irec[k] < kp->P, "irec has an index outside [0, P)");
     }
     double max_w = 1.0;
     if (w) {
         max_w = 0.0;
         for (int64_t k = 0; k < kp->N; k++) {
-            KH_ARG(std::isfinite(w[k]), "w has a value that is not finite");
+            RTMI_ARG(std::isfinite(w[k]), "w has a value that is not finite");
             max_w = std::fmax(max_w, std::fabs(w[k]));
         }
     }
@@ -366,92 +318,79 @@ RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const dou
 
 RTMI_EXPORT int rtmi_kirchhoff_migrate(rtmi_kirchhoff* k, const double* data, double* image, rtmi_kirchhoff_stats* st) {
     const char* who = "rtmi_kirchhoff_migrate";
-    KH_ARG(k, "null handle");
-    KH_ARG(data, "null data");
-    KH_ARG(image, "null image");
-    const int rc = check_device(k, who);
-    if (rc) return rc;
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(data, "null data");
+    RTMI_ARG(image, "null image");
+    RTMI_RC(check_device(k, who));
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
     const double t_up = now_ms();
-    KH_TRY(hipMemcpy(k->data, data, N * nt * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(k->data, data, N * nt * sizeof(double), hipMemcpyHostToDevice));
     const double upload_ms = now_ms() - t_up;
-    Events ev;
-    KH_TRY(hipEventCreate(&ev.a));
-    KH_TRY(hipEventCreate(&ev.b));
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
     const int BS = migrate_block(k->nb);
     const dim3 grid((unsigned)((nn + BS - 1) / BS)), blk(BS);
     const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
     const size_t lds = bins ? (size_t)k->nb * BS * sizeof(double) : 0;
     const KArgs A = k->args();
-    KH_TRY(hipEventRecord(ev.a, nullptr));
+    RTMI_HIP(ev.mark(0));
     if (has_amp && bins) hipLaunchKernelGGL((k_migrate<true, true>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
     else if (has_amp) hipLaunchKernelGGL((k_migrate<true, false>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
     else if (bins) hipLaunchKernelGGL((k_migrate<false, true>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
     else hipLaunchKernelGGL((k_migrate<false, false>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
-    KH_TRY(hipGetLastError());
-    KH_TRY(hipEventRecord(ev.b, nullptr));
-    KH_TRY(hipEventSynchronize(ev.b));
-    KH_TRY(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    RTMI_HIP(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         *st = rtmi_kirchhoff_stats{};
-        float ms = 0.f;
-        KH_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        st->kernel_ms = ms;
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
         st->upload_ms = upload_ms;
         st->pairs = (int64_t)(N * nn);
-        const int rc2 = read_counts(k, grid.x, &st->contributing, who);
-        if (rc2) return rc2;
+        RTMI_RC(read_counts(k, grid.x, &st->contributing, who));
     }
     return RTMI_OK;
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_model(rtmi_kirchhoff* k, const double* model, double* data, rtmi_kirchhoff_stats* st) {
     const char* who = "rtmi_kirchhoff_model";
-    KH_ARG(k, "null handle");
-    KH_ARG(model, "null model");
-    KH_ARG(data, "null data");
-    const int rc = check_device(k, who);
-    if (rc) return rc;
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(model, "null model");
+    RTMI_ARG(data, "null data");
+    RTMI_RC(check_device(k, who));
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
     // the quantum: |contribution| <= max|w| max|amp|^2 max|m| = f 2^ex with f in [0.5, 1), so it is below 2^57 quanta 2^(ex - 57)
     double max_m = 0.0;
     for (size_t i = 0; i < nm; i++)
         if (std::isfinite(model[i])) max_m = std::fmax(max_m, std::fabs(model[i]));
     const double bound = (k->max_w * k->max_amp) * k->max_amp * max_m;
-    int ex = 0;
-    if (std::isfinite(bound)) (void)std::frexp(bound, &ex);
-    else ex = 1025;
-    const int e = ex - kFixBits;
+    const int e = std::isfinite(bound) ? rt::fix_exponent(bound) : 1025 - rt::kFixBits;
     const double t_up = now_ms();
-    KH_TRY(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
     const double upload_ms = now_ms() - t_up;
-    Events ev;
-    KH_TRY(hipEventCreate(&ev.a));
-    KH_TRY(hipEventCreate(&ev.b));
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
     const int W = (int)(nt < (size_t)kWindow ? nt : (size_t)kWindow);
     const dim3 grid((unsigned)N), blk(256);
     const size_t lds = (size_t)W * 2 * sizeof(unsigned long long);
     const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
     const KArgs A = k->args();
-    KH_TRY(hipEventRecord(ev.a, nullptr));
+    RTMI_HIP(ev.mark(0));
     if (has_amp && bins) hipLaunchKernelGGL((k_model<true, true>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
     else if (has_amp) hipLaunchKernelGGL((k_model<true, false>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
     else if (bins) hipLaunchKernelGGL((k_model<false, true>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
     else hipLaunchKernelGGL((k_model<false, false>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
-    KH_TRY(hipGetLastError());
-    KH_TRY(hipEventRecord(ev.b, nullptr));
-    KH_TRY(hipEventSynchronize(ev.b));
-    KH_TRY(hipMemcpy(data, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    RTMI_HIP(hipMemcpy(data, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         *st = rtmi_kirchhoff_stats{};
-        float ms = 0.f;
-        KH_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        st->kernel_ms = ms;
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
         st->upload_ms = upload_ms;
         st->pairs = (int64_t)(N * nn);
         st->scale_exp = e;
-        const int rc2 = read_counts(k, N, &st->contributing, who);
-        if (rc2) return rc2;
+        RTMI_RC(read_counts(k, N, &st->contributing, who));
     }
     return RTMI_OK;
 }

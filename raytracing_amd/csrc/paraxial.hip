@@ -16,30 +16,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
 #include "rt_crossing.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
-#define PX_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define PX_ARG(cond, msg)                                                    \
-    do {                                                                     \
-        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
-    } while (0)
-#define PX_RC(expr)                  \
-    do {                             \
-        const int rc_ = (expr);      \
-        if (rc_) return rc_;         \
-    } while (0)
+#include "rt_polytab.h"
+#include "rtmi_host.h"
 
 namespace {
 
 constexpr int kCols = 7;        // Q1 P1 Q2 P2 J G kmah
-constexpr int kStride = 40;     // rt::kPolyStride: numbers per cell of the table
+constexpr int kStride = rt::kPolyStride;
 
 // rtmi_internal_poly with the table typed (T: the field's dtype)
 template <typename T> struct PolyF {
@@ -53,25 +37,9 @@ template <typename T> struct PolyF {
 struct NG2 { double n, gx, gy, gxx, gxy, gyx, gyy; };
 struct CellPos { int cell; double u, v; };
 
-// rt::poly_locate in fp64: u = (x - a) inv_h - j with the product taken exactly; FITPACK's argument clamp outside the grid
-__device__ __forceinline__ void axis_clamped(double x, double a, double b, double inv_h, int ncell, double& xa, double& jf) {
-    x = x < a ? a : x;
-    x = x > b ? b : x;
-    xa = x - a;
-    jf = floor(xa * inv_h);
-    jf = jf < 0.0 ? 0.0 : (jf > (double)(ncell - 1) ? (double)(ncell - 1) : jf);
-}
 template <typename T> __device__ __forceinline__ CellPos locate(const PolyF<T>& F, double x, double y) {
-    double xa = x - F.ax, ya = y - F.ay;
-    double jfx = floor(xa * F.inv_hx), jfy = floor(ya * F.inv_hy);
-    int jx = (int)jfx, jy = (int)jfy;
-    if ((unsigned)jx >= (unsigned)F.ncx) { axis_clamped(x, F.ax, F.bx, F.inv_hx, F.ncx, xa, jfx); jx = (int)jfx; }
-    if ((unsigned)jy >= (unsigned)F.ncy) { axis_clamped(y, F.ay, F.by, F.inv_hy, F.ncy, ya, jfy); jy = (int)jfy; }
-    CellPos c;
-    c.u = __builtin_fma(xa, F.inv_hx, -jfx);
-    c.v = __builtin_fma(ya, F.inv_hy, -jfy);
-    c.cell = jy * F.ncx + jx;
-    return c;
+    const rt::PolyPos c = rt::locate(F, F.ncx, F.ncy, x, y);
+    return CellPos{c.jy * F.ncx + c.jx, c.u, c.v};
 }
 
 // The flat-cell map (rt::FieldDev::flat, rt_polytab.h): a flat cell's entry is its constant n, an ordinary cell's a NaN pattern
@@ -275,132 +243,93 @@ template <typename T> PolyF<T> poly_f(const rtmi_internal_poly& v) {
     return PolyF<T>{(const T*)v.poly, v.flat, v.ncx, v.ncy, v.ax, v.bx, v.inv_hx, v.ay, v.by, v.inv_hy};
 }
 
-// device allocations of one call, freed on every way out
-struct DevMem {
-    std::vector<void*> p;
-    template <typename T> hipError_t get(T** out, size_t bytes) {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
-        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
-        return e;
-    }
-    ~DevMem() { for (void* v : p) (void)hipFree(v); }
-};
+// k_paraxial on a batch's rows: a's outputs are the caller's, its first five members come from the view
+int launch(const char* who, const Recorded& r, ParaxArgs a) {
+    a.s_ray = r.v.s_ray; a.istep = r.v.istep; a.perm = r.v.perm; a.R = (long)r.v.R; a.rec_rows = (long)r.v.rec_rows;
+    if (r.v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, blocks(a.R), dim3(256), 0, nullptr, poly_f<double>(r.poly), a);
+    else hipLaunchKernelGGL(k_paraxial<float>, blocks(a.R), dim3(256), 0, nullptr, poly_f<float>(r.poly), a);
+    RTMI_HIP(hipGetLastError());
+    return RTMI_OK;
+}
+constexpr unsigned kNeeds = kRecIsotropic | kRecPoly | kRecFromLaunch;
 
 }  // namespace
 
 RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax, int32_t* count, double* at_line, double* at_end) {
     const char* who = "rtmi_paraxial";
-    PX_ARG(b && at_end, "rtmi_paraxial: null");
+    RTMI_ARG(b && at_end, "null");
     Line L{0.0, 0.0, 0.0};
     if (line) {
-        PX_ARG(count && at_line, "rtmi_paraxial: a line needs count and at_line");
-        PX_ARG(kmax >= 1, "rtmi_paraxial: kmax must be >= 1");
-        PX_ARG(make_line(line, &L), "rtmi_paraxial: the line needs (a, b) != (0, 0) and finite coefficients");
+        RTMI_ARG(count && at_line, "a line needs count and at_line");
+        RTMI_ARG(kmax >= 1, "kmax must be >= 1");
+        RTMI_ARG(make_line(line, &L), "the line needs (a, b) != (0, 0) and finite coefficients");
     }
-    const rtmi_field* f = nullptr;
-    rtmi_params p{};
-    int from_state = 0;
-    PX_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
-    PX_ARG(p.record_stride == 1, "rtmi_paraxial: needs the full trajectory (record_stride 1)");
-    PX_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
-           "rtmi_paraxial: isotropic media only (op1..op9, gamma 1): anisotropic dynamic ray tracing is another system");
-    if (from_state)
-        return rtmi_internal_fail(RTMI_ERR_STATE, "rtmi_paraxial: rtmi_batch_set_state gave rays a row other than 0: their rows "
-                                                  "before it are not a trajectory from the source (reset the batch)");
-    rtmi_internal_poly pv;
-    PX_RC(rtmi_internal_field_poly(f, &pv));
-    rtmi_device_view v;
-    PX_RC(rtmi_batch_view(b, &v));          // drains the rays handed over to the re-trace of critical rays
-    PX_RC(rtmi_sync(b));
-    const size_t R = (size_t)v.R;
+    Recorded r;
+    RTMI_RC(recorded(who, b, kNeeds, 0, &r));
+    const size_t R = (size_t)r.v.R;
     const int K = line ? kmax : 0;
     DevMem mem;
     int32_t* dc = nullptr;
     double *dl = nullptr, *de = nullptr;
-    PX_TRY(mem.get(&dc, R * sizeof(int32_t)));
-    PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
-    if (K) PX_TRY(mem.get(&dl, (size_t)K * kCols * R * sizeof(double)));
-    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr, nullptr};
-    const dim3 g((unsigned)((R + 255) / 256)), blk(256);
-    if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
-    else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
-    PX_TRY(hipGetLastError());
-    PX_TRY(hipMemcpy(at_end, de, (size_t)kCols * R * sizeof(double), hipMemcpyDeviceToHost));
-    if (count) PX_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (K) PX_TRY(hipMemcpy(at_line, dl, (size_t)K * kCols * R * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(mem.get(&dc, R * sizeof(int32_t)));
+    RTMI_HIP(mem.get(&de, (size_t)kCols * R * sizeof(double)));
+    if (K) RTMI_HIP(mem.get(&dl, (size_t)K * kCols * R * sizeof(double)));
+    RTMI_RC(launch(who, r, ParaxArgs{nullptr, nullptr, nullptr, 0, 0, L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr, nullptr}));
+    RTMI_HIP(hipMemcpy(at_end, de, (size_t)kCols * R * sizeof(double), hipMemcpyDeviceToHost));
+    if (count) RTMI_HIP(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (K) RTMI_HIP(hipMemcpy(at_line, dl, (size_t)K * kCols * R * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 
 namespace {
 // rtmi_paraxial's kernel with its per-row outputs (row_J and row_kmah, or row_tube) into DEVICE buffers; rtmi_paraxial's checks
 int paraxial_rows(const char* who, rtmi_batch* b, double* row_J, int32_t* row_kmah, double* row_tube) {
-    const rtmi_field* f = nullptr;
-    rtmi_params p{};
-    int from_state = 0;
-    PX_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
-    PX_ARG(p.record_stride == 1, "amplitudes need the full trajectory (record_stride 1)");
-    PX_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
-           "amplitudes: isotropic media only (op1..op9, gamma 1): anisotropic dynamic ray tracing is another system");
-    if (from_state)
-        return rtmi_internal_fail(RTMI_ERR_STATE, "amplitudes: rtmi_batch_set_state gave rays a row other than 0: their rows "
-                                                  "before it are not a trajectory from the source (reset the batch)");
-    rtmi_internal_poly pv;
-    PX_RC(rtmi_internal_field_poly(f, &pv));
-    rtmi_device_view v;
-    PX_RC(rtmi_batch_view(b, &v));
-    PX_RC(rtmi_sync(b));
-    const size_t R = (size_t)v.R;
+    Recorded r;
+    RTMI_RC(recorded(who, b, kNeeds, 0, &r));
     DevMem mem;
     double* de = nullptr;
-    PX_TRY(mem.get(&de, (size_t)kCols * R * sizeof(double)));
-    ParaxArgs a{v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah,
-                row_tube};
-    const dim3 g((unsigned)((R + 255) / 256)), blk(256);
-    if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, g, blk, 0, nullptr, poly_f<double>(pv), a);
-    else hipLaunchKernelGGL(k_paraxial<float>, g, blk, 0, nullptr, poly_f<float>(pv), a);
-    PX_TRY(hipGetLastError());
-    PX_TRY(hipDeviceSynchronize());
+    RTMI_HIP(mem.get(&de, (size_t)kCols * (size_t)r.v.R * sizeof(double)));
+    RTMI_RC(launch(who, r, ParaxArgs{nullptr, nullptr, nullptr, 0, 0, Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah,
+                                     row_tube}));
+    RTMI_HIP(hipDeviceSynchronize());
     return RTMI_OK;
 }
 }  // namespace
 
 // J = n0 Q2 and kmah after every recorded row of every ray, into DEVICE buffers of the batch's device ([rec_rows][R], slot order;
 // rows past a ray's last row are left as they were).  The J of a ray's last row is rtmi_paraxial's at_end J, bit for bit: the
-// same kernel with the same arithmetic, storing what it carries.  The checks are rtmi_paraxial's.
-int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah) {
-    const char* who = "rtmi_internal_paraxial_rows";
-    PX_ARG(b && row_J && row_kmah, "rtmi_internal_paraxial_rows: null");
+// same kernel with the same arithmetic, storing what it carries.  The checks are rtmi_paraxial's, under the caller's name.
+int rtmi_internal_paraxial_rows(const char* who, rtmi_batch* b, double* row_J, int32_t* row_kmah) {
+    RTMI_ARG(b && row_J && row_kmah, "null");
     return paraxial_rows(who, b, row_J, row_kmah, nullptr);
 }
 
 // Q1 P1 Q2 P2 and n after every recorded row ([rec_rows][5][R], slot order), the same kernel storing what it carries; a ray
 // that runs past rec_rows is walked over its recorded rows.  For the Gaussian beams (beams.hip).
-int rtmi_internal_paraxial_tube(rtmi_batch* b, double* row_tube) {
-    const char* who = "rtmi_internal_paraxial_tube";
-    PX_ARG(b && row_tube, "rtmi_internal_paraxial_tube: null");
+int rtmi_internal_paraxial_tube(const char* who, rtmi_batch* b, double* row_tube) {
+    RTMI_ARG(b && row_tube, "null");
     return paraxial_rows(who, b, nullptr, nullptr, row_tube);
 }
 
 RTMI_EXPORT int rtmi_debug_paraxial_rows(rtmi_batch* b, double* J, int32_t* kmah) {
     const char* who = "rtmi_debug_paraxial_rows";
-    PX_ARG(b && J && kmah, "rtmi_debug_paraxial_rows: null");
+    RTMI_ARG(b && J && kmah, "null");
     rtmi_device_view v;
-    PX_RC(rtmi_batch_view(b, &v));
+    RTMI_RC(rtmi_batch_view(b, &v));
     const size_t R = (size_t)v.R, n = (size_t)v.rec_rows * R;
     DevMem mem;
     double* dj = nullptr;
     int32_t* dk = nullptr;
-    PX_TRY(mem.get(&dj, n * sizeof(double)));
-    PX_TRY(mem.get(&dk, n * sizeof(int32_t)));
-    PX_TRY(hipMemset(dj, 0xff, n * sizeof(double)));
-    PX_TRY(hipMemset(dk, 0xff, n * sizeof(int32_t)));
-    PX_RC(rtmi_internal_paraxial_rows(b, dj, dk));
+    RTMI_HIP(mem.get(&dj, n * sizeof(double)));
+    RTMI_HIP(mem.get(&dk, n * sizeof(int32_t)));
+    RTMI_HIP(hipMemset(dj, 0xff, n * sizeof(double)));
+    RTMI_HIP(hipMemset(dk, 0xff, n * sizeof(int32_t)));
+    RTMI_RC(rtmi_internal_paraxial_rows(who, b, dj, dk));
     std::vector<double> hj(n);
     std::vector<int32_t> hk(n), perm(v.perm ? R : 0);
-    PX_TRY(hipMemcpy(hj.data(), dj, n * sizeof(double), hipMemcpyDeviceToHost));
-    PX_TRY(hipMemcpy(hk.data(), dk, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (v.perm) PX_TRY(hipMemcpy(perm.data(), v.perm, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(hj.data(), dj, n * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(hk.data(), dk, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (v.perm) RTMI_HIP(hipMemcpy(perm.data(), v.perm, R * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < (size_t)v.rec_rows; i++)
         for (size_t k = 0; k < R; k++) {
             const size_t o = v.perm ? (size_t)perm[k] : k;
@@ -413,22 +342,22 @@ RTMI_EXPORT int rtmi_debug_paraxial_rows(rtmi_batch* b, double* J, int32_t* kmah
 RTMI_EXPORT int rtmi_field_eval_dgrad(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* gx_x,
                                       double* gx_y, double* gy_x, double* gy_y) {
     const char* who = "rtmi_field_eval_dgrad";
-    PX_ARG(f && x && y && gx_x && gx_y && gy_x && gy_y, "rtmi_field_eval_dgrad: null");
-    PX_ARG(npts >= 0, "rtmi_field_eval_dgrad: npts < 0");
+    RTMI_ARG(f && x && y && gx_x && gx_y && gy_x && gy_y, "null");
+    RTMI_ARG(npts >= 0, "npts < 0");
     rtmi_internal_poly pv;
-    PX_RC(rtmi_internal_field_poly(f, &pv));
+    RTMI_RC(rtmi_internal_field_poly(f, &pv));
     if (npts == 0) return RTMI_OK;
     const size_t nb = (size_t)npts * sizeof(double);
     DevMem mem;
     double* d = nullptr;
-    PX_TRY(mem.get(&d, 6 * nb));
-    PX_TRY(hipMemcpy(d, x, nb, hipMemcpyHostToDevice));
-    PX_TRY(hipMemcpy(d + npts, y, nb, hipMemcpyHostToDevice));
-    const dim3 g((unsigned)((npts + 255) / 256)), blk(256);
+    RTMI_HIP(mem.get(&d, 6 * nb));
+    RTMI_HIP(hipMemcpy(d, x, nb, hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(d + npts, y, nb, hipMemcpyHostToDevice));
+    const dim3 g = blocks(npts), blk(256);
     if (pv.dtype == RTMI_F64) hipLaunchKernelGGL(k_field_dgrad<double>, g, blk, 0, nullptr, poly_f<double>(pv), (long)npts, d, d + npts, d + 2 * npts);
     else hipLaunchKernelGGL(k_field_dgrad<float>, g, blk, 0, nullptr, poly_f<float>(pv), (long)npts, d, d + npts, d + 2 * npts);
-    PX_TRY(hipGetLastError());
+    RTMI_HIP(hipGetLastError());
     double* outs[4] = {gx_x, gx_y, gy_x, gy_y};
-    for (int q = 0; q < 4; q++) PX_TRY(hipMemcpy(outs[q], d + (2 + q) * npts, nb, hipMemcpyDeviceToHost));
+    for (int q = 0; q < 4; q++) RTMI_HIP(hipMemcpy(outs[q], d + (2 + q) * npts, nb, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }

@@ -150,4 +150,30 @@ RT_PT_HD inline bool poly_cell_flat(const double c[36], double thr) {
     return __builtin_fabs(c[33]) <= t && __builtin_fabs(c[34]) <= t && __builtin_fabs(c[35]) <= t;
 }
 
+// The map from a point to its cell (jx, jy) and (u, v) in fp64, for the post-trace kernels that walk recorded rows (paraxial.hip,
+// sensitivity.hip): rt::poly_locate (rt_device.h) with u = (x - a) inv_h - j taken from the exact product, and FITPACK's argument
+// clamp on an axis whose index falls outside the grid (a NaN coordinate leaves its index as the conversion gives it).
+struct PolyPos { int jx, jy; double u, v; };
+RT_PT_HD inline __attribute__((always_inline)) void axis_clamped(double x, double a, double b, double inv_h, int ncell, double& xa,
+                                                                 double& jf) {
+    x = x < a ? a : x;
+    x = x > b ? b : x;
+    xa = x - a;
+    jf = floor(xa * inv_h);
+    jf = jf < 0.0 ? 0.0 : (jf > (double)(ncell - 1) ? (double)(ncell - 1) : jf);
+}
+// F: anything with the axes ax, bx, inv_hx, ay, by, inv_hy (rtmi_internal_poly's); ncx, ncy: cells per axis
+template <typename F> RT_PT_HD inline __attribute__((always_inline)) PolyPos locate(const F& f, int ncx, int ncy, double x, double y) {
+    double xa = x - f.ax, ya = y - f.ay;
+    double jfx = floor(xa * f.inv_hx), jfy = floor(ya * f.inv_hy);
+    int jx = (int)jfx, jy = (int)jfy;
+    if ((unsigned)jx >= (unsigned)ncx) { axis_clamped(x, f.ax, f.bx, f.inv_hx, ncx, xa, jfx); jx = (int)jfx; }
+    if ((unsigned)jy >= (unsigned)ncy) { axis_clamped(y, f.ay, f.by, f.inv_hy, ncy, ya, jfy); jy = (int)jfy; }
+    PolyPos c;
+    c.u = __builtin_fma(xa, f.inv_hx, -jfx);
+    c.v = __builtin_fma(ya, f.inv_hy, -jfy);
+    c.jx = jx; c.jy = jy;
+    return c;
+}
+
 }  // namespace rt

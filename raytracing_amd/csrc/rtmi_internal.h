@@ -34,11 +34,12 @@ int rtmi_internal_batch_info(rtmi_batch* b, const rtmi_field** f, rtmi_params* p
 // A batch's ray count, host-side (no device work): for argument checks that come before any.
 int rtmi_internal_batch_rays(rtmi_batch* b, int64_t* R);
 // paraxial.hip: J = n0 Q2 and the caustic count after every recorded row, written to DEVICE buffers [rec_rows][R] (slot order)
-// by rtmi_paraxial's kernel; with rtmi_paraxial's checks.  For ttgrid.hip's amplitude columns.
-int rtmi_internal_paraxial_rows(rtmi_batch* b, double* row_J, int32_t* row_kmah);
+// by rtmi_paraxial's kernel; with rtmi_paraxial's checks, reported under `who`, the public entry's name.  For ttgrid.hip's
+// amplitude columns.
+int rtmi_internal_paraxial_rows(const char* who, rtmi_batch* b, double* row_J, int32_t* row_kmah);
 // paraxial.hip: Q1 P1 Q2 P2 and n after every recorded row, written to a DEVICE buffer [rec_rows][5][R] (slot order; rows past a
 // ray's last row are left as they were) by rtmi_paraxial's kernel; with rtmi_paraxial's checks.  A ray that runs past rec_rows
 // gets its recorded rows.  For beams.hip.
-int rtmi_internal_paraxial_tube(rtmi_batch* b, double* row_tube);
+int rtmi_internal_paraxial_tube(const char* who, rtmi_batch* b, double* row_tube);
 // A batch's launch angles theta0 [R] in the caller's ray order, copied to a host buffer.
 int rtmi_internal_batch_theta0(rtmi_batch* b, double* theta0);

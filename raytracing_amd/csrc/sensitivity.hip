@@ -19,58 +19,27 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
 #include "rt_crossing.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
-#define SN_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define SN_ARG(cond, msg)                                                    \
-    do {                                                                     \
-        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
-    } while (0)
-#define SN_RC(expr)                  \
-    do {                             \
-        const int rc_ = (expr);      \
-        if (rc_) return rc_;         \
-    } while (0)
+#include "rt_fix128.h"
+#include "rt_polytab.h"
+#include "rtmi_host.h"
 
 namespace {
 
 constexpr int kMaxLine = 64;      // kmax: at most this many crossings per ray
-constexpr int kFixBits = 57;      // a flushed partial is below 2^57 quanta: 64 lanes' sum fits in an int64
 
-// The field's map from a point to its cell and (u, v): rt::poly_locate in fp64 (paraxial.hip's locate), FITPACK's argument clamp
-// outside the grid.  The indices are clamped once more so that no row, however odd, addresses outside the samples.
+// The field's map from a point to its cell and (u, v): rt::locate (rt_polytab.h).  The indices are clamped once more so that no
+// row, however odd, addresses outside the samples.
 struct Axes {
     double ax, bx, inv_hx, ay, by, inv_hy;
     int qx, qy;                   // samples per axis; cells qx - 1, qy - 1
 };
-struct Cell { int jx, jy; double u, v; };
-
-__device__ __forceinline__ void axis_clamped(double x, double a, double b, double inv_h, int ncell, double& xa, double& jf) {
-    x = x < a ? a : x;
-    x = x > b ? b : x;
-    xa = x - a;
-    jf = floor(xa * inv_h);
-    jf = jf < 0.0 ? 0.0 : (jf > (double)(ncell - 1) ? (double)(ncell - 1) : jf);
-}
+typedef rt::PolyPos Cell;
 __device__ __forceinline__ Cell locate(const Axes& F, double x, double y) {
     const int ncx = F.qx - 1, ncy = F.qy - 1;
-    double xa = x - F.ax, ya = y - F.ay;
-    double jfx = floor(xa * F.inv_hx), jfy = floor(ya * F.inv_hy);
-    int jx = (int)jfx, jy = (int)jfy;
-    if ((unsigned)jx >= (unsigned)ncx) { axis_clamped(x, F.ax, F.bx, F.inv_hx, ncx, xa, jfx); jx = (int)jfx; }
-    if ((unsigned)jy >= (unsigned)ncy) { axis_clamped(y, F.ay, F.by, F.inv_hy, ncy, ya, jfy); jy = (int)jfy; }
-    Cell c;
-    c.u = __builtin_fma(xa, F.inv_hx, -jfx);
-    c.v = __builtin_fma(ya, F.inv_hy, -jfy);
-    c.jx = jx < 0 ? 0 : (jx > ncx - 1 ? ncx - 1 : jx);
-    c.jy = jy < 0 ? 0 : (jy > ncy - 1 ? ncy - 1 : jy);
+    Cell c = rt::locate(F, ncx, ncy, x, y);
+    c.jx = c.jx < 0 ? 0 : (c.jx > ncx - 1 ? ncx - 1 : c.jx);
+    c.jy = c.jy < 0 ? 0 : (c.jy > ncy - 1 ? ncy - 1 : c.jy);
     return c;
 }
 // the sample weights (1-u)(1-v), u(1-v), (1-u)v, uv on Z[j][i], Z[j][i+1], Z[j+1][i], Z[j+1][i+1]
@@ -205,18 +174,6 @@ __global__ void k_fill(unsigned long long* p, size_t n, unsigned long long v) {
     if (i < n) p[i] = v;
 }
 
-// The group's integer sum s added to sample q's 128-bit accumulator (lo, hi), sign-extended: the low word's carry, read from the
-// value the add returned, goes to the high word; the high word is written only when it changes.
-__device__ __forceinline__ int add128(unsigned long long* lo, unsigned long long* hi, size_t q, long long s) {
-    if (s == 0) return 0;
-    const unsigned long long a = (unsigned long long)s;
-    const unsigned long long old = atomicAdd(lo + q, a);
-    const unsigned long long h = (s < 0 ? ~0ull : 0ull) + ((old + a) < old ? 1ull : 0ull);
-    if (h == 0) return 1;
-    atomicAdd(hi + q, h);
-    return 2;
-}
-
 // One lane per ray.  Step i (rows i-1, i) gives both rows (L_i 0.5) W_i, W_i = w_end + the weights of the crossings after
 // step i; a crossing c < min(count, kmax) on step i gives row i-1 w_c L_i (0.5 h01 + h10) and row i w_c L_i (0.5 h01 + h11).
 // A row's weight times its coef, times phi, goes into the lane's partial sums of its cell.
@@ -233,9 +190,7 @@ __global__ void k_backproject(Args A, const double* w_line, const double* w_end,
     if (last >= A.rec_rows) last = -1;                      // past the record: no reported traveltime, no weight
     const Line L = A.L;
     const int qx = A.F.qx;
-    int ex;
-    (void)frexp(__longlong_as_double((long long)*maxb), &ex);
-    const int e = ex - kFixBits;                            // quantum 2^e: every partial is below 2^57 quanta
+    const int e = rt::fix_exponent(__longlong_as_double((long long)*maxb));    // quantum 2^e: every partial is below 2^57 quanta
     // crossings that carry a weight: the first min(count, kmax)
     const bool line = A.has_line && w_line != nullptr;
     const int K = (line && last >= 0) ? min(count_crossings(col, R, last, L), A.kmax) : 0;
@@ -276,10 +231,10 @@ __global__ void k_backproject(Args A, const double* w_line, const double* w_end,
             }
             if (lane == leader) {
                 const size_t b = (size_t)ly * qx + lx;
-                nat += add128(lo, hi, b, v[0]);
-                nat += add128(lo, hi, b + 1, v[1]);
-                nat += add128(lo, hi, b + qx, v[2]);
-                nat += add128(lo, hi, b + qx + 1, v[3]);
+                nat += rt::add128(lo, hi, b, v[0]);
+                nat += rt::add128(lo, hi, b + 1, v[1]);
+                nat += rt::add128(lo, hi, b + qx, v[2]);
+                nat += rt::add128(lo, hi, b + qx + 1, v[3]);
             }
             todo &= ~mm;
         }
@@ -356,54 +311,26 @@ __global__ void k_backproject(Args A, const double* w_line, const double* w_end,
     if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
 }
 
-// device allocations of one call, freed on every way out
-struct DevMem {
-    std::vector<void*> p;
-    template <typename T> hipError_t get(T** out, size_t bytes) {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
-        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
-        return e;
-    }
-    ~DevMem() { for (void* v : p) (void)hipFree(v); }
-};
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 // The checks both entries share, then the batch's rows and the field's axes
 int prepare(rtmi_batch* b, const double* line, int32_t kmax, const char* who, Args* A, rtmi_device_view* v) {
-    const rtmi_field* f = nullptr;
-    rtmi_params p{};
-    int from_state = 0;
-    SN_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
-    if (p.record_stride != 1)
-        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": needs the full trajectory (record_stride 1)").c_str());
-    if (from_state)
-        return rtmi_internal_fail(RTMI_ERR_STATE, (std::string(who) + ": rtmi_batch_set_state gave rays a row other than 0: their "
-                                                   "rows before it are not a trajectory from the source (reset the batch)").c_str());
-    rtmi_internal_poly pv;
-    SN_RC(rtmi_internal_field_poly(f, &pv));
+    Recorded r;
+    RTMI_RC(recorded(who, b, kRecPoly | kRecFromLaunch, 0, &r));
     int qx = 0, qy = 0;
-    SN_RC(rtmi_field_dims(f, &qx, &qy));
-    SN_RC(rtmi_batch_view(b, v));          // drains the rays handed over to the re-trace of critical rays
-    SN_RC(rtmi_sync(b));
+    RTMI_RC(rtmi_field_dims(r.f, &qx, &qy));
+    *v = r.v;
     Line L{0.0, 0.0, 0.0};
     if (line) (void)make_line(line, &L);
     *A = Args{v->s_ray, v->istep, v->perm, v->dist_sim, (long)v->R, (long)v->rec_rows,
-              Axes{pv.ax, pv.bx, pv.inv_hx, pv.ay, pv.by, pv.inv_hy, qx, qy}, L, line ? 1 : 0, line ? kmax : 0,
-              p.method >= 10 ? 1 : 0, p.gamma};
+              Axes{r.poly.ax, r.poly.bx, r.poly.inv_hx, r.poly.ay, r.poly.by, r.poly.inv_hy, qx, qy}, L, line ? 1 : 0, line ? kmax : 0,
+              r.p.method >= 10 ? 1 : 0, r.p.gamma};
     return RTMI_OK;
 }
 
 int check_line(const double* line, int32_t kmax, const char* who) {
     if (!line) return RTMI_OK;
     Line L;
-    if (kmax < 1 || kmax > kMaxLine)
-        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": kmax must be in 1..64").c_str());
-    if (!make_line(line, &L))
-        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": the line needs (a, b) != (0, 0) and finite coefficients").c_str());
+    RTMI_ARG(kmax >= 1 && kmax <= kMaxLine, "kmax must be in 1..64");
+    RTMI_ARG(make_line(line, &L), "the line needs (a, b) != (0, 0) and finite coefficients");
     return RTMI_OK;
 }
 
@@ -412,42 +339,39 @@ int check_line(const double* line, int32_t kmax, const char* who) {
 RTMI_EXPORT int rtmi_traveltime_perturb(rtmi_batch* b, const double line[3], int32_t kmax, const double* dZ, int32_t* count,
                                         double* dT_line, double* dT_end, rtmi_sensitivity_stats* st) {
     const char* who = "rtmi_traveltime_perturb";
-    SN_RC(check_line(line, kmax, who));
-    SN_ARG(dZ && dT_end, "rtmi_traveltime_perturb: null dZ or dT_end");
-    SN_ARG(!line || (count && dT_line), "rtmi_traveltime_perturb: a line needs count and dT_line");
-    SN_ARG(b, "rtmi_traveltime_perturb: null batch");
+    RTMI_RC(check_line(line, kmax, who));
+    RTMI_ARG(dZ && dT_end, "null dZ or dT_end");
+    RTMI_ARG(!line || (count && dT_line), "a line needs count and dT_line");
+    RTMI_ARG(b, "null batch");
     Args A;
     rtmi_device_view v;
-    SN_RC(prepare(b, line, kmax, who, &A, &v));
+    RTMI_RC(prepare(b, line, kmax, who, &A, &v));
     const size_t R = (size_t)v.R, nz = (size_t)A.F.qx * A.F.qy, K = (size_t)A.kmax;
     DevMem mem;
     double *dz = nullptr, *de = nullptr, *dl = nullptr;
     int32_t* dc = nullptr;
-    SN_TRY(mem.get(&dz, nz * sizeof(double)));
-    SN_TRY(mem.get(&de, R * sizeof(double)));
-    SN_TRY(mem.get(&dc, R * sizeof(int32_t)));
-    if (K) SN_TRY(mem.get(&dl, K * R * sizeof(double)));
-    SN_TRY(hipMemcpy(dz, dZ, nz * sizeof(double), hipMemcpyHostToDevice));
-    Events ev;
-    SN_TRY(hipEventCreate(&ev.a));
-    SN_TRY(hipEventCreate(&ev.b));
-    const dim3 g((unsigned)((R + 255) / 256)), blk(256);
-    SN_TRY(hipEventRecord(ev.a, nullptr));
+    RTMI_HIP(mem.get(&dz, nz * sizeof(double)));
+    RTMI_HIP(mem.get(&de, R * sizeof(double)));
+    RTMI_HIP(mem.get(&dc, R * sizeof(int32_t)));
+    if (K) RTMI_HIP(mem.get(&dl, K * R * sizeof(double)));
+    RTMI_HIP(hipMemcpy(dz, dZ, nz * sizeof(double), hipMemcpyHostToDevice));
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    const dim3 g = blocks((long)R), blk(256);
+    RTMI_HIP(ev.mark(0));
     if (R) {
         if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_perturb<double>, g, blk, 0, nullptr, A, dz, dc, dl, de);
         else hipLaunchKernelGGL(k_perturb<float>, g, blk, 0, nullptr, A, dz, dc, dl, de);
-        SN_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
     }
-    SN_TRY(hipEventRecord(ev.b, nullptr));
-    SN_TRY(hipEventSynchronize(ev.b));
-    SN_TRY(hipMemcpy(dT_end, de, R * sizeof(double), hipMemcpyDeviceToHost));
-    if (count) SN_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (K) SN_TRY(hipMemcpy(dT_line, dl, K * R * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    RTMI_HIP(hipMemcpy(dT_end, de, R * sizeof(double), hipMemcpyDeviceToHost));
+    if (count) RTMI_HIP(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (K) RTMI_HIP(hipMemcpy(dT_line, dl, K * R * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         *st = rtmi_sensitivity_stats{};
-        float ms = 0.f;
-        SN_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        st->kernel_ms = ms;
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
     }
     return RTMI_OK;
 }
@@ -455,65 +379,56 @@ RTMI_EXPORT int rtmi_traveltime_perturb(rtmi_batch* b, const double line[3], int
 RTMI_EXPORT int rtmi_traveltime_backproject(rtmi_batch* b, const double line[3], int32_t kmax, const double* w_line,
                                             const double* w_end, double* g, rtmi_sensitivity_stats* st) {
     const char* who = "rtmi_traveltime_backproject";
-    SN_RC(check_line(line, kmax, who));
-    SN_ARG(g, "rtmi_traveltime_backproject: null g");
-    SN_ARG(!w_line || line, "rtmi_traveltime_backproject: w_line needs a line");
-    SN_ARG(b, "rtmi_traveltime_backproject: null batch");
+    RTMI_RC(check_line(line, kmax, who));
+    RTMI_ARG(g, "null g");
+    RTMI_ARG(!w_line || line, "w_line needs a line");
+    RTMI_ARG(b, "null batch");
     Args A;
     rtmi_device_view v;
-    SN_RC(prepare(b, line, kmax, who, &A, &v));
+    RTMI_RC(prepare(b, line, kmax, who, &A, &v));
     const size_t R = (size_t)v.R, nz = (size_t)A.F.qx * A.F.qy, K = (size_t)A.kmax;
     DevMem mem;
     double *dwl = nullptr, *dwe = nullptr;
     unsigned long long *acc = nullptr, *misc = nullptr;    // acc: lo [nz], hi [nz]; misc: the bound, the atomics issued
-    SN_TRY(mem.get(&acc, 2 * nz * sizeof(unsigned long long)));
-    SN_TRY(mem.get(&misc, 2 * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&acc, 2 * nz * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&misc, 2 * sizeof(unsigned long long)));
     if (w_line) {
-        SN_TRY(mem.get(&dwl, K * R * sizeof(double)));
-        SN_TRY(hipMemcpy(dwl, w_line, K * R * sizeof(double), hipMemcpyHostToDevice));
+        RTMI_HIP(mem.get(&dwl, K * R * sizeof(double)));
+        RTMI_HIP(hipMemcpy(dwl, w_line, K * R * sizeof(double), hipMemcpyHostToDevice));
     }
     if (w_end) {
-        SN_TRY(mem.get(&dwe, R * sizeof(double)));
-        SN_TRY(hipMemcpy(dwe, w_end, R * sizeof(double), hipMemcpyHostToDevice));
+        RTMI_HIP(mem.get(&dwe, R * sizeof(double)));
+        RTMI_HIP(hipMemcpy(dwe, w_end, R * sizeof(double), hipMemcpyHostToDevice));
     }
-    SN_TRY(hipMemset(misc, 0, 2 * sizeof(unsigned long long)));
-    SN_TRY(hipMemset(acc + nz, 0, nz * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_fill, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, nullptr, acc, nz, 1ull << 63);   // the low words' bias
-    SN_TRY(hipGetLastError());
+    RTMI_HIP(hipMemset(misc, 0, 2 * sizeof(unsigned long long)));
+    RTMI_HIP(hipMemset(acc + nz, 0, nz * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_fill, blocks((long)nz), dim3(256), 0, nullptr, acc, nz, rt::kFixBias);   // the low words' bias
+    RTMI_HIP(hipGetLastError());
     const double coef_max = A.aniso ? fmax(1.0, fabs(A.gamma)) : 1.0;
-    Events ev;
-    SN_TRY(hipEventCreate(&ev.a));
-    SN_TRY(hipEventCreate(&ev.b));
-    const dim3 gr((unsigned)((R + 255) / 256)), blk(256);
-    SN_TRY(hipEventRecord(ev.a, nullptr));
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    const dim3 gr = blocks((long)R), blk(256);
+    RTMI_HIP(ev.mark(0));
     if (R) {
         hipLaunchKernelGGL(k_bound, gr, blk, 0, nullptr, A, dwl, dwe, coef_max, misc);
-        SN_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
         if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_backproject<double>, gr, blk, 0, nullptr, A, dwl, dwe, misc, acc, acc + nz, misc + 1);
         else hipLaunchKernelGGL(k_backproject<float>, gr, blk, 0, nullptr, A, dwl, dwe, misc, acc, acc + nz, misc + 1);
-        SN_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
     }
-    SN_TRY(hipEventRecord(ev.b, nullptr));
-    SN_TRY(hipEventSynchronize(ev.b));
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
     std::vector<unsigned long long> h(2 * nz);
     unsigned long long hm[2];
-    SN_TRY(hipMemcpy(h.data(), acc, 2 * nz * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    SN_TRY(hipMemcpy(hm, misc, sizeof(hm), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(h.data(), acc, 2 * nz * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(hm, misc, sizeof(hm), hipMemcpyDeviceToHost));
     double maxb;
     std::memcpy(&maxb, &hm[0], sizeof(double));
-    int ex;
-    (void)std::frexp(maxb, &ex);
-    const int e = ex - kFixBits;
-    // value = hi 2^64 + lo - 2^63 quanta, exact in 128 bits; one rounding to fp64
-    for (size_t i = 0; i < nz; i++) {
-        const __int128 q = (__int128)(((unsigned __int128)h[nz + i] << 64) | h[i]) - ((__int128)1 << 63);
-        g[i] = std::ldexp((double)q, e);
-    }
+    const int e = rt::fix_exponent(maxb);
+    for (size_t i = 0; i < nz; i++) g[i] = std::ldexp(rt::fix_to_double(h[i], h[nz + i]), e);      // one rounding to fp64
     if (st) {
         *st = rtmi_sensitivity_stats{};
-        float ms = 0.f;
-        SN_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        st->kernel_ms = ms;
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
         st->atomics = (int64_t)hm[1];
         st->scale_exp = e;
     }

@@ -19,24 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
-#define TG_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define TG_ARG(cond, msg)                                                    \
-    do {                                                                     \
-        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
-    } while (0)
-#define TG_RC(expr)                  \
-    do {                             \
-        const int rc_ = (expr);      \
-        if (rc_) return rc_;         \
-    } while (0)
+#include "rtmi_host.h"
 
 namespace {
 
@@ -306,38 +289,13 @@ template <typename T> __global__ void k_columns(Grid g, Rec r, Nodes nd, double*
     }
 }
 
-__global__ void k_inverse(const int32_t* perm, int32_t* slot, long R) {
-    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < R) slot[perm[k]] = (int32_t)k;
-}
-
-// device allocations of one call, freed on every way out
-struct DevMem {
-    std::vector<void*> p;
-    template <typename T> hipError_t get(T** out, size_t bytes) {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
-        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
-        return e;
-    }
-    ~DevMem() { for (void* v : p) (void)hipFree(v); }
-};
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
-};
-
 // the grid parameters checked and the defaults filled in (host)
 int grid_of(const rtmi_grid_params* gp, const char* who, Grid* g) {
-    TG_ARG(gp, (std::string(who) + ": null grid parameters").c_str());
-    TG_ARG(gp->nx >= 1 && gp->ny >= 1, (std::string(who) + ": nx and ny must be >= 1").c_str());
-    TG_ARG((double)gp->nx * (double)gp->ny <= (double)(1L << 31), (std::string(who) + ": more than 2^31 nodes per source").c_str());
-    TG_ARG(gp->gdx > 0.0 && gp->gdy > 0.0 && std::isfinite(gp->gdx) && std::isfinite(gp->gdy),
-           (std::string(who) + ": gdx and gdy must be finite and > 0").c_str());
-    TG_ARG(std::isfinite(gp->gx0) && std::isfinite(gp->gy0), (std::string(who) + ": gx0 and gy0 must be finite").c_str());
-    TG_ARG(gp->max_gap >= 0.0 && std::isfinite(gp->max_gap) && gp->max_dtheta >= 0.0 && std::isfinite(gp->max_dtheta),
-           (std::string(who) + ": max_gap and max_dtheta must be finite and >= 0").c_str());
-    TG_ARG(gp->amplitude == 0 || gp->amplitude == 1, (std::string(who) + ": amplitude must be 0 or 1").c_str());
+    RTMI_ARG(gp, "null grid parameters");
+    RTMI_RC(check_grid_axes(who, *gp));
+    RTMI_ARG(gp->max_gap >= 0.0 && std::isfinite(gp->max_gap) && gp->max_dtheta >= 0.0 && std::isfinite(gp->max_dtheta),
+             "max_gap and max_dtheta must be finite and >= 0");
+    RTMI_ARG(gp->amplitude == 0 || gp->amplitude == 1, "amplitude must be 0 or 1");
     *g = Grid{gp->gx0, gp->gdx, gp->gy0, gp->gdy, (int)gp->nx, (int)gp->ny,
               gp->max_gap > 0.0 ? gp->max_gap : kGapCells * (gp->gdx > gp->gdy ? gp->gdx : gp->gdy),
               gp->max_dtheta > 0.0 ? gp->max_dtheta : kDtheta, 1.0 / gp->gdx, 1.0 / gp->gdy};
@@ -351,48 +309,44 @@ int run_grid(const char* who, int dtype, const Grid& g, Rec r, int32_t* count, d
     DevMem mem;
     Nodes nd{};
     double* dout = nullptr;
-    TG_TRY(mem.get(&nd.tmin, nodes * sizeof(unsigned long long)));
-    TG_TRY(mem.get(&nd.key, nodes * sizeof(unsigned long long)));
-    TG_TRY(mem.get(&nd.count, nodes * sizeof(int32_t)));
-    TG_TRY(mem.get(&nd.ctr, C_N * sizeof(unsigned long long)));
-    TG_TRY(mem.get(&dout, nodes * ncols * sizeof(double)));
-    TG_TRY(hipMemset(nd.tmin, 0xff, nodes * sizeof(unsigned long long)));
-    TG_TRY(hipMemset(nd.key, 0xff, nodes * sizeof(unsigned long long)));
-    TG_TRY(hipMemset(nd.count, 0, nodes * sizeof(int32_t)));
-    TG_TRY(hipMemset(nd.ctr, 0, C_N * sizeof(unsigned long long)));
-    Events ev;
-    for (hipEvent_t& e : ev.e) TG_TRY(hipEventCreate(&e));
+    RTMI_HIP(mem.get(&nd.tmin, nodes * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&nd.key, nodes * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&nd.count, nodes * sizeof(int32_t)));
+    RTMI_HIP(mem.get(&nd.ctr, C_N * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&dout, nodes * ncols * sizeof(double)));
+    RTMI_HIP(hipMemset(nd.tmin, 0xff, nodes * sizeof(unsigned long long)));
+    RTMI_HIP(hipMemset(nd.key, 0xff, nodes * sizeof(unsigned long long)));
+    RTMI_HIP(hipMemset(nd.count, 0, nodes * sizeof(int32_t)));
+    RTMI_HIP(hipMemset(nd.ctr, 0, C_N * sizeof(unsigned long long)));
+    EventMarks<4> ev;
+    RTMI_HIP(ev.create());
     const long lanes = (long)r.S * (r.M - 1);
-    const dim3 blk(256), gl((unsigned)((lanes + 255) / 256)), gn((unsigned)((nodes + 255) / 256));
-    TG_TRY(hipEventRecord(ev.e[0], nullptr));
+    const dim3 blk(256), gl = blocks(lanes), gn = blocks((long)nodes);
+    RTMI_HIP(ev.mark(0));
     for (int pass = 1; pass <= 2; pass++) {
         if (lanes > 0) {
             if (dtype == RTMI_F64) hipLaunchKernelGGL(k_raster<double>, gl, blk, 0, nullptr, g, r, nd, pass);
             else hipLaunchKernelGGL(k_raster<float>, gl, blk, 0, nullptr, g, r, nd, pass);
-            TG_TRY(hipGetLastError());
+            RTMI_HIP(hipGetLastError());
         }
-        TG_TRY(hipEventRecord(ev.e[pass], nullptr));
+        RTMI_HIP(ev.mark(pass));
     }
     if (dtype == RTMI_F64) hipLaunchKernelGGL(k_columns<double>, gn, blk, 0, nullptr, g, r, nd, dout, ncols);
     else hipLaunchKernelGGL(k_columns<float>, gn, blk, 0, nullptr, g, r, nd, dout, ncols);
-    TG_TRY(hipGetLastError());
-    TG_TRY(hipEventRecord(ev.e[3], nullptr));
-    TG_TRY(hipEventSynchronize(ev.e[3]));
-    TG_TRY(hipMemcpy(count, nd.count, nodes * sizeof(int32_t), hipMemcpyDeviceToHost));
-    TG_TRY(hipMemcpy(out, dout, nodes * ncols * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(3));
+    RTMI_HIP(ev.wait(3));
+    RTMI_HIP(hipMemcpy(count, nd.count, nodes * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(out, dout, nodes * ncols * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         unsigned long long c[C_N];
-        TG_TRY(hipMemcpy(c, nd.ctr, sizeof(c), hipMemcpyDeviceToHost));
+        RTMI_HIP(hipMemcpy(c, nd.ctr, sizeof(c), hipMemcpyDeviceToHost));
         *st = rtmi_grid_stats{};
         st->cells = (int64_t)c[C_CELLS]; st->skipped_cells = (int64_t)c[C_SKIP];
         st->triangles = (int64_t)c[C_TRI]; st->folded = (int64_t)c[C_FOLD];
         st->atomics[0] = c[C_ADD1]; st->atomics[1] = c[C_MIN1]; st->atomics[2] = c[C_MIN2];
         st->max_gap = g.max_gap; st->max_dtheta = g.max_dtheta;
-        for (int q = 0; q < 3; q++) {
-            float ms = 0.0f;
-            TG_TRY(hipEventElapsedTime(&ms, ev.e[q], ev.e[q + 1]));
-            st->pass_ms[q] = ms;
-        }
+        for (int q = 0; q < 3; q++) RTMI_HIP(ev.ms(q, q + 1, &st->pass_ms[q]));
     }
     return RTMI_OK;
 }
@@ -402,44 +356,30 @@ int run_grid(const char* who, int dtype, const Grid& g, Rec r, int32_t* count, d
 RTMI_EXPORT int rtmi_first_arrival_grid(rtmi_batch* b, int32_t fan_size, const rtmi_grid_params* gp, int32_t* count, double* out,
                                         rtmi_grid_stats* st) {
     const char* who = "rtmi_first_arrival_grid";
-    TG_ARG(b && count && out, "rtmi_first_arrival_grid: null");
+    RTMI_ARG(b && count && out, "null");
     Grid g;
-    TG_RC(grid_of(gp, who, &g));
-    TG_ARG(fan_size >= 2, "rtmi_first_arrival_grid: fan_size must be >= 2");
-    const rtmi_field* f = nullptr;
-    rtmi_params p{};
-    int from_state = 0;
-    TG_RC(rtmi_internal_batch_info(b, &f, &p, &from_state));
-    TG_ARG(p.record_stride == 1, "rtmi_first_arrival_grid: needs the full trajectory (record_stride 1)");
-    if (gp->amplitude)
-        TG_ARG(p.method >= 1 && p.method <= 9 && p.gamma == 1.0,
-               "rtmi_first_arrival_grid: amplitude needs an isotropic medium (op1..op9, gamma 1), as rtmi_paraxial");
-    if (from_state)
-        return rtmi_internal_fail(RTMI_ERR_STATE, "rtmi_first_arrival_grid: rtmi_batch_set_state gave rays a row other than 0: "
-                                                  "their rows before it are not a trajectory from the source (reset the batch)");
-    int64_t nrays = 0;
-    TG_RC(rtmi_internal_batch_rays(b, &nrays));
-    TG_ARG(nrays % fan_size == 0, "rtmi_first_arrival_grid: the batch's ray count is not a multiple of fan_size");
-    rtmi_device_view v;
-    TG_RC(rtmi_batch_view(b, &v));          // drains the rays handed over to the re-trace of critical rays
-    TG_RC(rtmi_sync(b));
+    RTMI_RC(grid_of(gp, who, &g));
+    RTMI_ARG(fan_size >= 2, "fan_size must be >= 2");
+    Recorded rec;
+    RTMI_RC(recorded(who, b, (gp->amplitude ? kRecIsotropic : 0u) | kRecFromLaunch, fan_size, &rec));
+    const rtmi_device_view& v = rec.v;
     const size_t R = (size_t)v.R;
     DevMem mem;
     int32_t* slot = nullptr;
     double* rj = nullptr;
     int32_t* rk = nullptr;
     if (v.perm) {
-        TG_TRY(mem.get(&slot, R * sizeof(int32_t)));
-        hipLaunchKernelGGL(k_inverse, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, nullptr, v.perm, slot, (long)R);
-        TG_TRY(hipGetLastError());
+        RTMI_HIP(mem.get(&slot, R * sizeof(int32_t)));
+        hipLaunchKernelGGL(k_inverse<int32_t>, blocks((long)R), dim3(256), 0, nullptr, v.perm, slot, (long)R);
+        RTMI_HIP(hipGetLastError());
     }
     if (gp->amplitude) {
         const size_t cells = (size_t)v.rec_rows * R;
-        TG_TRY(mem.get(&rj, cells * sizeof(double)));
-        TG_TRY(mem.get(&rk, cells * sizeof(int32_t)));
-        TG_TRY(hipMemset(rj, 0xff, cells * sizeof(double)));         // NaN (and kmah -1) on rows no ray reaches
-        TG_TRY(hipMemset(rk, 0xff, cells * sizeof(int32_t)));
-        TG_RC(rtmi_internal_paraxial_rows(b, rj, rk));
+        RTMI_HIP(mem.get(&rj, cells * sizeof(double)));
+        RTMI_HIP(mem.get(&rk, cells * sizeof(int32_t)));
+        RTMI_HIP(hipMemset(rj, 0xff, cells * sizeof(double)));         // NaN (and kmah -1) on rows no ray reaches
+        RTMI_HIP(hipMemset(rk, 0xff, cells * sizeof(int32_t)));
+        RTMI_RC(rtmi_internal_paraxial_rows(who, b, rj, rk));
     }
     const Rec r{v.s_ray, v.istep, slot, nullptr, rj, rk, (long)v.R, (long)v.rec_rows, (int)fan_size, (int)(v.R / fan_size)};
     return run_grid(who, v.dtype, g, r, count, out, st);
@@ -449,13 +389,13 @@ RTMI_EXPORT int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, 
                                      const double* theta, const int32_t* last, const double* theta0, const rtmi_grid_params* gp,
                                      int32_t* count, double* out, rtmi_grid_stats* st) {
     const char* who = "rtmi_debug_grid_rows";
-    TG_ARG(x && y && T && theta && last && theta0 && count && out, "rtmi_debug_grid_rows: null");
+    RTMI_ARG(x && y && T && theta && last && theta0 && count && out, "null");
     Grid g;
-    TG_RC(grid_of(gp, who, &g));
-    TG_ARG(!gp->amplitude, "rtmi_debug_grid_rows: no amplitude on caller-supplied rows");
-    TG_ARG(rows >= 1 && R >= 2, "rtmi_debug_grid_rows: rows >= 1 and R >= 2");
-    TG_ARG(fan_size >= 2 && R % fan_size == 0, "rtmi_debug_grid_rows: R must be a multiple of fan_size >= 2");
-    for (int32_t k = 0; k < R; k++) TG_ARG(last[k] >= 0 && last[k] < rows, "rtmi_debug_grid_rows: last must lie in [0, rows)");
+    RTMI_RC(grid_of(gp, who, &g));
+    RTMI_ARG(!gp->amplitude, "no amplitude on caller-supplied rows");
+    RTMI_ARG(rows >= 1 && R >= 2, "rows >= 1 and R >= 2");
+    RTMI_ARG(fan_size >= 2 && R % fan_size == 0, "R must be a multiple of fan_size >= 2");
+    for (int32_t k = 0; k < R; k++) RTMI_ARG(last[k] >= 0 && last[k] < rows, "last must lie in [0, rows)");
     const size_t n = (size_t)rows * R;
     std::vector<double> rec(6 * n, 0.0);
     for (size_t i = 0; i < (size_t)rows; i++)
@@ -466,12 +406,12 @@ RTMI_EXPORT int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, 
     DevMem mem;
     double *drec = nullptr, *dth0 = nullptr;
     int32_t* dlast = nullptr;
-    TG_TRY(mem.get(&drec, rec.size() * sizeof(double)));
-    TG_TRY(mem.get(&dth0, (size_t)R * sizeof(double)));
-    TG_TRY(mem.get(&dlast, (size_t)R * sizeof(int32_t)));
-    TG_TRY(hipMemcpy(drec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
-    TG_TRY(hipMemcpy(dth0, theta0, (size_t)R * sizeof(double), hipMemcpyHostToDevice));
-    TG_TRY(hipMemcpy(dlast, last, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice));
+    RTMI_HIP(mem.get(&drec, rec.size() * sizeof(double)));
+    RTMI_HIP(mem.get(&dth0, (size_t)R * sizeof(double)));
+    RTMI_HIP(mem.get(&dlast, (size_t)R * sizeof(int32_t)));
+    RTMI_HIP(hipMemcpy(drec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(dth0, theta0, (size_t)R * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(dlast, last, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice));
     const Rec r{drec, dlast, nullptr, dth0, nullptr, nullptr, (long)R, (long)rows, (int)fan_size, (int)(R / fan_size)};
     return run_grid(who, RTMI_F64, g, r, count, out, st);
 }

@@ -1,6 +1,7 @@
 // twopoint.hip -- receiver-line crossings of recorded rays (rtmi_crossings) and two-point ray tracing from sources to
 // receivers on a line (rtmi_two_point): the shooting method of the reference's paper setting, in its two-point form.
-// Batches are read through the public rtmi_batch_view; the only hook into rtmi.hip is rtmi_internal_relaunch.
+// Batches are read through the checks of rtmi_host.h (recorded) and the public rtmi_batch_view; the refinement relaunches its
+// batch through rtmi_internal_relaunch.
 //
 // The crossing arithmetic (rt_crossing.h) is written in one fixed order (compiled with -ffp-contract=off, sin/cos glibc's own
 // through rt_libm.h) so that tests/crossing_ref.py, a numpy restatement, gives the same bits; the receiver angle goes through the
@@ -14,25 +15,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
 #include "rt_crossing.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
-#define TP_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define TP_ARG(cond, msg)                                                    \
-    do {                                                                     \
-        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, (msg));        \
-    } while (0)
-#define TP_RC(expr)                  \
-    do {                             \
-        const int rc_ = (expr);      \
-        if (rc_) return rc_;         \
-    } while (0)
+#include "rtmi_host.h"
 
 namespace {
 
@@ -86,21 +70,23 @@ __global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t*
         for (int q = 0; q < 6; q++) out[((size_t)c * 6 + q) * R + o] = NAN;
 }
 
-int crossings_device(rtmi_batch* b, const Line& L, int kmax, int32_t* d_count, double* d_out, hipStream_t st, const char* who) {
-    rtmi_device_view v;
-    TP_RC(rtmi_batch_view(b, &v));
-    if (v.record_stride != 1)
-        return rtmi_internal_fail(RTMI_ERR_ARG, (std::string(who) + ": needs the full trajectory (record_stride 1)").c_str());
-    TP_RC(rtmi_sync(b));
-    const dim3 g((unsigned)((v.R + 255) / 256)), blk(256);
+// k_crossings on the rows of a view, enqueued on st
+int crossings_launch(const rtmi_device_view& v, const Line& L, int kmax, int32_t* d_count, double* d_out, hipStream_t st, const char* who) {
+    const dim3 g = blocks((long)v.R), blk(256);
     if (v.dtype == RTMI_F64)
         hipLaunchKernelGGL(k_crossings<double>, g, blk, 0, st, (const double*)v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L,
                            kmax, d_count, d_out);
     else
         hipLaunchKernelGGL(k_crossings<float>, g, blk, 0, st, (const float*)v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L,
                            kmax, d_count, d_out);
-    TP_TRY(hipGetLastError());
+    RTMI_HIP(hipGetLastError());
     return RTMI_OK;
+}
+// Crossings read rows wherever they came from: a batch continued from rtmi_batch_set_state is not refused.
+int crossings_device(rtmi_batch* b, const Line& L, int kmax, int32_t* d_count, double* d_out, hipStream_t st, const char* who) {
+    Recorded r;
+    RTMI_RC(recorded(who, b, 0, 0, &r));
+    return crossings_launch(r.v, L, kmax, d_count, d_out, st, who);
 }
 
 // ------------------------------------------------------------------ two-point
@@ -255,17 +241,6 @@ __global__ void k_output(int SJ, int A, const Bracket* br, double* out, int32_t*
     bad[t] = nb;
 }
 
-// device allocations of one call, freed on every way out
-struct DevMem {
-    std::vector<void*> p;
-    template <typename T> hipError_t get(T** out, size_t bytes) {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, bytes ? bytes : 8);
-        if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
-        return e;
-    }
-    ~DevMem() { for (void* v : p) (void)hipFree(v); }
-};
 struct BatchGuard {
     rtmi_batch* b = nullptr;
     ~BatchGuard() { rtmi_batch_destroy(b); }
@@ -282,22 +257,21 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 RTMI_EXPORT int rtmi_crossings(rtmi_batch* b, const double line[3], int32_t kmax, int32_t* count, double* out) {
     const char* who = "rtmi_crossings";
-    TP_ARG(b && line && count && out, "rtmi_crossings: null");
-    TP_ARG(kmax >= 1, "rtmi_crossings: kmax must be >= 1");
+    RTMI_ARG(b && line && count && out, "null");
+    RTMI_ARG(kmax >= 1, "kmax must be >= 1");
     Line L;
-    TP_ARG(make_line(line, &L), "rtmi_crossings: the line needs (a, b) != (0, 0) and finite coefficients");
-    rtmi_device_view v;
-    TP_RC(rtmi_batch_view(b, &v));
-    TP_ARG(v.record_stride == 1, "rtmi_crossings: needs the full trajectory (record_stride 1)");
-    const size_t R = (size_t)v.R;
+    RTMI_ARG(make_line(line, &L), "the line needs (a, b) != (0, 0) and finite coefficients");
+    Recorded r;
+    RTMI_RC(recorded(who, b, 0, 0, &r));
+    const size_t R = (size_t)r.v.R;
     DevMem mem;
     int32_t* dc = nullptr;
     double* dout = nullptr;
-    TP_TRY(mem.get(&dc, R * sizeof(int32_t)));
-    TP_TRY(mem.get(&dout, (size_t)kmax * 6 * R * sizeof(double)));
-    TP_RC(crossings_device(b, L, kmax, dc, dout, nullptr, who));
-    TP_TRY(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
-    TP_TRY(hipMemcpy(out, dout, (size_t)kmax * 6 * R * sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(mem.get(&dc, R * sizeof(int32_t)));
+    RTMI_HIP(mem.get(&dout, (size_t)kmax * 6 * R * sizeof(double)));
+    RTMI_RC(crossings_launch(r.v, L, kmax, dc, dout, nullptr, who));
+    RTMI_HIP(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(out, dout, (size_t)kmax * 6 * R * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 
@@ -306,39 +280,39 @@ RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_
                                const rtmi_two_point_params* tp, int32_t* count, int32_t* nbad, double* arrivals,
                                rtmi_two_point_stats* stats) {
     const char* who = "rtmi_two_point";
-    TP_ARG(f && p && sx && sy && thetas && line && receivers_u && count && nbad && arrivals, "rtmi_two_point: null");
-    TP_ARG(S >= 1 && M >= 2 && J >= 1, "rtmi_two_point: needs S >= 1 sources, M >= 2 launch angles and J >= 1 receivers");
-    TP_ARG(p->dtype == RTMI_F64, "rtmi_two_point: fp64 only");
+    RTMI_ARG(f && p && sx && sy && thetas && line && receivers_u && count && nbad && arrivals, "null");
+    RTMI_ARG(S >= 1 && M >= 2 && J >= 1, "needs S >= 1 sources, M >= 2 launch angles and J >= 1 receivers");
+    RTMI_ARG(p->dtype == RTMI_F64, "fp64 only");
     Line L;
-    TP_ARG(make_line(line, &L), "rtmi_two_point: the line needs (a, b) != (0, 0) and finite coefficients");
+    RTMI_ARG(make_line(line, &L), "the line needs (a, b) != (0, 0) and finite coefficients");
     for (int j = 0; j < J; j++)
-        TP_ARG(std::isfinite(receivers_u[j]) && (j == 0 || receivers_u[j] > receivers_u[j - 1]),
-               "rtmi_two_point: receivers_u must be finite and strictly increasing");
-    for (int m = 0; m < M; m++) TP_ARG(std::isfinite(thetas[m]), "rtmi_two_point: launch angles must be finite");
+        RTMI_ARG(std::isfinite(receivers_u[j]) && (j == 0 || receivers_u[j] > receivers_u[j - 1]),
+               "receivers_u must be finite and strictly increasing");
+    for (int m = 0; m < M; m++) RTMI_ARG(std::isfinite(thetas[m]), "launch angles must be finite");
     rtmi_two_point_params q{};
     if (tp) q = *tp;
     const int A = q.max_arrivals ? q.max_arrivals : 4, K = q.max_crossings ? q.max_crossings : 4;
     const int max_iter = q.max_iter ? q.max_iter : 60;
     const double tol = q.tol != 0.0 ? q.tol : 1e-10;
     const int64_t budget = q.mem_budget ? q.mem_budget : (int64_t)8 << 30;
-    TP_ARG(A >= 1 && A <= 64 && K >= 1 && K <= 64 && max_iter >= 1 && tol > 0 && budget > 0,
-           "rtmi_two_point: max_arrivals and max_crossings must be in [1, 64], max_iter >= 1, tol > 0, mem_budget > 0");
-    TP_ARG((int64_t)S * M < (1ll << 31) && (int64_t)S * J * A < (1ll << 31), "rtmi_two_point: too many rays");
+    RTMI_ARG(A >= 1 && A <= 64 && K >= 1 && K <= 64 && max_iter >= 1 && tol > 0 && budget > 0,
+           "max_arrivals and max_crossings must be in [1, 64], max_iter >= 1, tol > 0, mem_budget > 0");
+    RTMI_ARG((int64_t)S * M < (1ll << 31) && (int64_t)S * J * A < (1ll << 31), "too many rays");
 
     rtmi_two_point_stats st{};
     StreamGuard sg;
-    TP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    RTMI_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     const hipStream_t strm = sg.s;
     rtmi_params pb = *p;
     pb.sort_rays = 0; pb.ext_s_ray = nullptr; pb.ext_n_ray = nullptr; pb.no_n_ray = 1; pb.lazy_clear = 0;
     DevMem mem;
     int32_t* dmax = nullptr;
     double *dth = nullptr, *dru = nullptr;
-    TP_TRY(mem.get(&dmax, sizeof(int32_t)));
-    TP_TRY(mem.get(&dth, (size_t)M * 8));
-    TP_TRY(mem.get(&dru, (size_t)J * 8));
-    TP_TRY(hipMemcpy(dth, thetas, (size_t)M * 8, hipMemcpyHostToDevice));
-    TP_TRY(hipMemcpy(dru, receivers_u, (size_t)J * 8, hipMemcpyHostToDevice));
+    RTMI_HIP(mem.get(&dmax, sizeof(int32_t)));
+    RTMI_HIP(mem.get(&dth, (size_t)M * 8));
+    RTMI_HIP(mem.get(&dru, (size_t)J * 8));
+    RTMI_HIP(hipMemcpy(dth, thetas, (size_t)M * 8, hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(dru, receivers_u, (size_t)J * 8, hipMemcpyHostToDevice));
 
     // 1. the count pass: every source's fan without a record; its longest ray sizes the record
     auto t0 = std::chrono::steady_clock::now();
@@ -355,15 +329,15 @@ RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_
         rtmi_params pc = pb;
         pc.record_stride = 0; pc.rec_rows = 0;
         BatchGuard bc;
-        TP_RC(rtmi_batch_create(f, &pc, (int64_t)S * M, hx.data(), hy.data(), ht.data(), (void*)strm, &bc.b));
-        TP_RC(rtmi_run(bc.b));
+        RTMI_RC(rtmi_batch_create(f, &pc, (int64_t)S * M, hx.data(), hy.data(), ht.data(), (void*)strm, &bc.b));
+        RTMI_RC(rtmi_run(bc.b));
         rtmi_device_view v;
-        TP_RC(rtmi_batch_view(bc.b, &v));
-        TP_TRY(hipMemsetAsync(dmax, 0, sizeof(int32_t), strm));
-        hipLaunchKernelGGL(k_max_istep, dim3((unsigned)((v.R + 255) / 256)), dim3(256), 0, strm, v.istep, (long)v.R, dmax);
-        TP_TRY(hipGetLastError());
-        TP_TRY(hipMemcpyAsync(&fan_rows, dmax, sizeof(int32_t), hipMemcpyDeviceToHost, strm));
-        TP_TRY(hipStreamSynchronize(strm));
+        RTMI_RC(rtmi_batch_view(bc.b, &v));
+        RTMI_HIP(hipMemsetAsync(dmax, 0, sizeof(int32_t), strm));
+        hipLaunchKernelGGL(k_max_istep, blocks((long)v.R), dim3(256), 0, strm, v.istep, (long)v.R, dmax);
+        RTMI_HIP(hipGetLastError());
+        RTMI_HIP(hipMemcpyAsync(&fan_rows, dmax, sizeof(int32_t), hipMemcpyDeviceToHost, strm));
+        RTMI_HIP(hipStreamSynchronize(strm));
     }
     const int64_t rec_fan = (int64_t)fan_rows + 1;
     // refinement rays may run a little longer than any fan ray; those that run past the record are reported as truncated
@@ -381,12 +355,12 @@ RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_
         double *fcr = nullptr, *rcr = nullptr, *th = nullptr, *dout = nullptr;
         Bracket* br = nullptr;
         unsigned long long* dover = nullptr;
-        TP_TRY(gm.get(&fc, Rf * 4)); TP_TRY(gm.get(&fcr, (size_t)K * 6 * Rf * 8));
-        TP_TRY(gm.get(&nslot, (size_t)Sg * J * 4)); TP_TRY(gm.get(&br, NB * sizeof(Bracket)));
-        TP_TRY(gm.get(&ms, NB * 4)); TP_TRY(gm.get(&th, NB * 8));
-        TP_TRY(gm.get(&rc, NB * 4)); TP_TRY(gm.get(&rcr, (size_t)K * 6 * NB * 8));
-        TP_TRY(gm.get(&active, 4)); TP_TRY(gm.get(&dover, 8));
-        TP_TRY(gm.get(&dcnt, (size_t)Sg * J * 4)); TP_TRY(gm.get(&dbad, (size_t)Sg * J * 4)); TP_TRY(gm.get(&dout, NB * 9 * 8));
+        RTMI_HIP(gm.get(&fc, Rf * 4)); RTMI_HIP(gm.get(&fcr, (size_t)K * 6 * Rf * 8));
+        RTMI_HIP(gm.get(&nslot, (size_t)Sg * J * 4)); RTMI_HIP(gm.get(&br, NB * sizeof(Bracket)));
+        RTMI_HIP(gm.get(&ms, NB * 4)); RTMI_HIP(gm.get(&th, NB * 8));
+        RTMI_HIP(gm.get(&rc, NB * 4)); RTMI_HIP(gm.get(&rcr, (size_t)K * 6 * NB * 8));
+        RTMI_HIP(gm.get(&active, 4)); RTMI_HIP(gm.get(&dover, 8));
+        RTMI_HIP(gm.get(&dcnt, (size_t)Sg * J * 4)); RTMI_HIP(gm.get(&dbad, (size_t)Sg * J * 4)); RTMI_HIP(gm.get(&dout, NB * 9 * 8));
 
         // 2. the fan, recorded, and its crossings
         t0 = std::chrono::steady_clock::now();
@@ -394,27 +368,27 @@ RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_
             rtmi_params pf = pb;
             pf.record_stride = 1; pf.rec_rows = rec_fan;
             BatchGuard bf;
-            TP_RC(rtmi_batch_create(f, &pf, Rf, hx.data() + (size_t)s0 * M, hy.data() + (size_t)s0 * M, ht.data() + (size_t)s0 * M,
+            RTMI_RC(rtmi_batch_create(f, &pf, Rf, hx.data() + (size_t)s0 * M, hy.data() + (size_t)s0 * M, ht.data() + (size_t)s0 * M,
                                     (void*)strm, &bf.b));
-            TP_RC(rtmi_run(bf.b));
-            TP_RC(crossings_device(bf.b, L, K, fc, fcr, strm, who));
-            TP_TRY(hipStreamSynchronize(strm));
+            RTMI_RC(rtmi_run(bf.b));
+            RTMI_RC(crossings_device(bf.b, L, K, fc, fcr, strm, who));
+            RTMI_HIP(hipStreamSynchronize(strm));
         }
         st.fan_ms += ms_since(t0);
 
         // 3. brackets
         t0 = std::chrono::steady_clock::now();
-        TP_TRY(hipMemsetAsync(nslot, 0, (size_t)Sg * J * 4, strm));
-        TP_TRY(hipMemsetAsync(dover, 0, 8, strm));
+        RTMI_HIP(hipMemsetAsync(nslot, 0, (size_t)Sg * J * 4, strm));
+        RTMI_HIP(hipMemsetAsync(dover, 0, 8, strm));
         const long nt = (long)Sg * (M - 1) * K;
-        hipLaunchKernelGGL(k_brackets, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, strm, fc, fcr, Rf, Sg, M, K, dth, dru, J, A, nslot,
+        hipLaunchKernelGGL(k_brackets, blocks(nt), dim3(256), 0, strm, fc, fcr, Rf, Sg, M, K, dth, dru, J, A, nslot,
                            br, dover);
-        hipLaunchKernelGGL(k_sort_brackets, dim3((unsigned)((Sg * J + 255) / 256)), dim3(256), 0, strm, Sg * J, A, nslot, br, th, ms,
+        hipLaunchKernelGGL(k_sort_brackets, blocks(Sg * J), dim3(256), 0, strm, Sg * J, A, nslot, br, th, ms,
                            p->max_size);
-        TP_TRY(hipGetLastError());
+        RTMI_HIP(hipGetLastError());
         unsigned long long over = 0;
-        TP_TRY(hipMemcpyAsync(&over, dover, 8, hipMemcpyDeviceToHost, strm));
-        TP_TRY(hipStreamSynchronize(strm));
+        RTMI_HIP(hipMemcpyAsync(&over, dover, 8, hipMemcpyDeviceToHost, strm));
+        RTMI_HIP(hipStreamSynchronize(strm));
         st.overflow += over;
         st.bracket_ms += ms_since(t0);
 
@@ -427,19 +401,19 @@ RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_
             std::vector<double> hxr((size_t)NB), hyr((size_t)NB), htr((size_t)NB, 0.0);
             for (long t = 0; t < NB; t++) { hxr[t] = sx[s0 + t / ((long)J * A)]; hyr[t] = sy[s0 + t / ((long)J * A)]; }
             BatchGuard brt;
-            TP_RC(rtmi_batch_create(f, &pr, NB, hxr.data(), hyr.data(), htr.data(), (void*)strm, &brt.b));
+            RTMI_RC(rtmi_batch_create(f, &pr, NB, hxr.data(), hyr.data(), htr.data(), (void*)strm, &brt.b));
             int it = 0;
             for (; it < max_iter; it++) {
-                TP_RC(rtmi_internal_relaunch(brt.b, th, ms));
-                TP_RC(rtmi_run(brt.b));
-                TP_RC(crossings_device(brt.b, L, K, rc, rcr, strm, who));
-                TP_TRY(hipMemsetAsync(active, 0, 4, strm));
-                hipLaunchKernelGGL(k_update, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, strm, NB, J, A, dru, rc, rcr, tol, br, th, ms,
+                RTMI_RC(rtmi_internal_relaunch(brt.b, th, ms));
+                RTMI_RC(rtmi_run(brt.b));
+                RTMI_RC(crossings_device(brt.b, L, K, rc, rcr, strm, who));
+                RTMI_HIP(hipMemsetAsync(active, 0, 4, strm));
+                hipLaunchKernelGGL(k_update, blocks(NB), dim3(256), 0, strm, NB, J, A, dru, rc, rcr, tol, br, th, ms,
                                    active);
-                TP_TRY(hipGetLastError());
+                RTMI_HIP(hipGetLastError());
                 int32_t h_active = 0;
-                TP_TRY(hipMemcpyAsync(&h_active, active, 4, hipMemcpyDeviceToHost, strm));
-                TP_TRY(hipStreamSynchronize(strm));
+                RTMI_HIP(hipMemcpyAsync(&h_active, active, 4, hipMemcpyDeviceToHost, strm));
+                RTMI_HIP(hipStreamSynchronize(strm));
                 if (h_active == 0) { it++; break; }
             }
             st.iterations = std::max(st.iterations, it);
@@ -447,12 +421,12 @@ RTMI_EXPORT int rtmi_two_point(const rtmi_field* f, const rtmi_params* p, int32_
         st.refine_ms += ms_since(t0);
 
         // 5. output
-        hipLaunchKernelGGL(k_output, dim3((unsigned)((Sg * J + 255) / 256)), dim3(256), 0, strm, Sg * J, A, br, dout, dcnt, dbad);
-        TP_TRY(hipGetLastError());
-        TP_TRY(hipMemcpyAsync(arrivals + (size_t)s0 * J * A * 9, dout, NB * 9 * 8, hipMemcpyDeviceToHost, strm));
-        TP_TRY(hipMemcpyAsync(count + (size_t)s0 * J, dcnt, (size_t)Sg * J * 4, hipMemcpyDeviceToHost, strm));
-        TP_TRY(hipMemcpyAsync(nbad + (size_t)s0 * J, dbad, (size_t)Sg * J * 4, hipMemcpyDeviceToHost, strm));
-        TP_TRY(hipStreamSynchronize(strm));
+        hipLaunchKernelGGL(k_output, blocks(Sg * J), dim3(256), 0, strm, Sg * J, A, br, dout, dcnt, dbad);
+        RTMI_HIP(hipGetLastError());
+        RTMI_HIP(hipMemcpyAsync(arrivals + (size_t)s0 * J * A * 9, dout, NB * 9 * 8, hipMemcpyDeviceToHost, strm));
+        RTMI_HIP(hipMemcpyAsync(count + (size_t)s0 * J, dcnt, (size_t)Sg * J * 4, hipMemcpyDeviceToHost, strm));
+        RTMI_HIP(hipMemcpyAsync(nbad + (size_t)s0 * J, dbad, (size_t)Sg * J * 4, hipMemcpyDeviceToHost, strm));
+        RTMI_HIP(hipStreamSynchronize(strm));
         st.groups++;
     }
     if (stats) *stats = st;

@@ -18,8 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtmi.h"
-#include "rtmi_internal.h"
+#include "rtmi_host.h"
 
 namespace {
 __device__ __forceinline__ double sgn_(double v) { return (v > 0) - (v < 0); }
@@ -141,21 +140,20 @@ __global__ void k_fine(long R, const unsigned long long* count, const double* no
 }
 }  // namespace
 
-#define WF_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) { rc = rtmi_internal_fail(RTMI_ERR_HIP, (std::string("rtmi_wavefronts: ") + #expr + ": " + hipGetErrorString(e_)).c_str()); goto done; } \
-    } while (0)
-
-extern "C" __attribute__((visibility("default"))) int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* times, int32_t nfine,
-                                                                      int64_t* count, double* nodes, double* fine) {
-    if (!b || !times || !count || !nodes) return rtmi_internal_fail(RTMI_ERR_ARG, "rtmi_wavefronts: null");
-    if (nfine < 0 || nfine == 1 || (nfine > 0 && !fine)) return rtmi_internal_fail(RTMI_ERR_ARG, "rtmi_wavefronts: nfine must be 0 or >= 2 (with a fine buffer)");
+RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* times, int32_t nfine, int64_t* count, double* nodes,
+                                double* fine) {
+    const char* who = "rtmi_wavefronts";
+    RTMI_ARG(b && times && count && nodes, "null");
+    RTMI_ARG(!(nfine < 0 || nfine == 1 || (nfine > 0 && !fine)), "nfine must be 0 or >= 2 (with a fine buffer)");
+    RTMI_ARG(ntimes > 0 && ntimes <= 4096, "ntimes must be in [1, 4096]");
+    Recorded rec;       // the stage below makes these checks too, under rtmi_isochrones' name
+    RTMI_RC(recorded(who, b, 0, 0, &rec));
     double* iso = nullptr;
     long R = 0;
     hipStream_t st = nullptr;
-    int rc = rtmi_internal_isochrones_device(b, ntimes, times, &iso, &R, (void**)&st);
-    if (rc) return rc;
+    RTMI_RC(rtmi_internal_isochrones_device(b, ntimes, times, &iso, &R, (void**)&st));
+    DevMem mem;
+    mem.adopt(iso);
     // Traveltimes are processed in chunks of `tc` (all of them, unless that needs more than ~1 GB of work arrays: 92 bytes per
     // point): per chunk ONE stable radix sort of every point by y, one more by the traveltime it belongs to (which regroups the
     // y-sorted points per wavefront: each has exactly R of them, the rays that do not reach it at the end with y = +inf), the
@@ -178,44 +176,39 @@ extern "C" __attribute__((visibility("default"))) int rtmi_wavefronts(rtmi_batch
     try {
         hcount.resize((size_t)tc);
     } catch (const std::exception&) {
-        rc = rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_wavefronts: host allocation failed");
-        goto done;
+        return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_wavefronts: host allocation failed");
     }
-    WF_TRY(hipMalloc(&keys, N * 8)); WF_TRY(hipMalloc(&keys2, N * 8));
-    WF_TRY(hipMalloc(&vals, N * 4)); WF_TRY(hipMalloc(&vals2, N * 4));
-    WF_TRY(hipMalloc(&fk, N * 4)); WF_TRY(hipMalloc(&fk2, N * 4));
-    WF_TRY(hipMalloc(&dn, 7 * N * 8)); WF_TRY(hipMalloc(&dd, N * 8));
-    WF_TRY(hipMalloc(&dcount, (size_t)tc * 8));
-    if (nfine) WF_TRY(hipMalloc(&df, (size_t)tc * 2 * (size_t)nfine * 8));
-    WF_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp1, keys, keys2, vals, vals2, (int)N, 0, 64, st));
-    WF_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp2, fk, fk2, vals2, vals, (int)N, 0, fbits, st));
-    WF_TRY(hipMalloc(&tmp, std::max(tmp1, tmp2)));
+    RTMI_HIP(mem.get(&keys, N * 8)); RTMI_HIP(mem.get(&keys2, N * 8));
+    RTMI_HIP(mem.get(&vals, N * 4)); RTMI_HIP(mem.get(&vals2, N * 4));
+    RTMI_HIP(mem.get(&fk, N * 4)); RTMI_HIP(mem.get(&fk2, N * 4));
+    RTMI_HIP(mem.get(&dn, 7 * N * 8)); RTMI_HIP(mem.get(&dd, N * 8));
+    RTMI_HIP(mem.get(&dcount, (size_t)tc * 8));
+    if (nfine) RTMI_HIP(mem.get(&df, (size_t)tc * 2 * (size_t)nfine * 8));
+    RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp1, keys, keys2, vals, vals2, (int)N, 0, 64, st));
+    RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp2, fk, fk2, vals2, vals, (int)N, 0, fbits, st));
+    RTMI_HIP(mem.get(&tmp, std::max(tmp1, tmp2)));
     for (int t0 = 0; t0 < ntimes; t0 += tc) {
         const int nt = std::min(tc, ntimes - t0);
         const size_t n = (size_t)nt * Rz;
         const double* iso_c = iso + (size_t)t0 * 3 * Rz;
-        const dim3 grd((unsigned)((Rz + 255) / 256), (unsigned)nt);
-        WF_TRY(hipMemsetAsync(dcount, 0, (size_t)nt * 8, st));
+        const dim3 grd(blocks(R).x, (unsigned)nt);
+        RTMI_HIP(hipMemsetAsync(dcount, 0, (size_t)nt * 8, st));
         hipLaunchKernelGGL(k_keys, grd, blk, 0, st, iso_c, R, keys, vals, dcount);
-        WF_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp1, keys, keys2, vals, vals2, (int)n, 0, 64, st));           // every point by y
+        RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp1, keys, keys2, vals, vals2, (int)n, 0, 64, st));           // every point by y
         if (nt > 1) {
-            hipLaunchKernelGGL(k_frame_keys, dim3((unsigned)((n + 255) / 256)), blk, 0, st, vals2, R, (long)n, fk);
-            WF_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp2, fk, fk2, vals2, vals, (int)n, 0, fbits, st));          // stable: regrouped per traveltime
+            hipLaunchKernelGGL(k_frame_keys, blocks((long)n), blk, 0, st, vals2, R, (long)n, fk);
+            RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp2, fk, fk2, vals2, vals, (int)n, 0, fbits, st));          // stable: regrouped per traveltime
         }
         const int* order = nt > 1 ? vals : vals2;
         hipLaunchKernelGGL(k_gather, grd, blk, 0, st, iso_c, R, order, dcount, dn);
         hipLaunchKernelGGL(k_nodes, grd, blk, 0, st, R, dcount, dn, dd);
-        if (nfine) hipLaunchKernelGGL(k_fine, dim3((nfine + 255) / 256, (unsigned)nt), blk, 0, st, R, dcount, dn, dd, (int)nfine, df);
-        WF_TRY(hipGetLastError());
-        WF_TRY(hipMemcpyAsync(hcount.data(), dcount, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
-        WF_TRY(hipMemcpyAsync(nodes + (size_t)t0 * 7 * Rz, dn, 7 * n * 8, hipMemcpyDeviceToHost, st));
-        if (nfine) WF_TRY(hipMemcpyAsync(fine + (size_t)t0 * 2 * nfine, df, (size_t)nt * 2 * (size_t)nfine * 8, hipMemcpyDeviceToHost, st));
-        WF_TRY(hipStreamSynchronize(st));
+        if (nfine) hipLaunchKernelGGL(k_fine, dim3(blocks(nfine).x, (unsigned)nt), blk, 0, st, R, dcount, dn, dd, (int)nfine, df);
+        RTMI_HIP(hipGetLastError());
+        RTMI_HIP(hipMemcpyAsync(hcount.data(), dcount, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+        RTMI_HIP(hipMemcpyAsync(nodes + (size_t)t0 * 7 * Rz, dn, 7 * n * 8, hipMemcpyDeviceToHost, st));
+        if (nfine) RTMI_HIP(hipMemcpyAsync(fine + (size_t)t0 * 2 * nfine, df, (size_t)nt * 2 * (size_t)nfine * 8, hipMemcpyDeviceToHost, st));
+        RTMI_HIP(hipStreamSynchronize(st));
         for (int i = 0; i < nt; i++) count[t0 + i] = (int64_t)hcount[i];
     }
-done:
-    (void)hipFree(iso); (void)hipFree(keys); (void)hipFree(keys2); (void)hipFree(vals); (void)hipFree(vals2);
-    (void)hipFree(fk); (void)hipFree(fk2);
-    (void)hipFree(dn); (void)hipFree(dd); (void)hipFree(df); (void)hipFree(dcount); (void)hipFree(tmp);
-    return rc;
+    return RTMI_OK;
 }
