@@ -6,10 +6,6 @@
 
 #include "rt_polytab.h"
 
-// A wave vote straight from the predicate.  HIP's __ballot(int) converts the bool to an int and compares it with zero again
-// (v_cndmask + v_cmp per vote, 12 vector instructions per step of the bench kernel); the builtin takes the i1.
-__device__ __forceinline__ unsigned long long rt_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-
 namespace rt {
 
 // The library is compiled with -ffp-contract=off: every fusion below is an explicit fma(), so a value is
@@ -771,15 +767,12 @@ template <typename T, int SC> __device__ __forceinline__ T poly_bilinear(Quad<T>
 constexpr int kPolyLane = 0, kPolyScalar = 1;
 // The flat-cell map (FieldDev::flat).  An entry is the cell's constant index, or -- for an ordinary cell -- a NaN: in fp32 fields
 // all-ones bits; in fp64 fields the high word all ones and the low word the cell's STEEPNESS as float bits (0 for most cells).
-// Steepness (k_polytab; rtmi.hip "critical rays"): lambda = sqrt(|Hessian of n| / n) over the cell, the rate (per unit length) at
+// Steepness (k_polytab, field.hip; rtmi.hip "critical rays"): lambda = sqrt(|Hessian of n| / n) over the cell, the rate (per unit length) at
 // which a ray running along the iso-lines of a transition that sharp drifts away from its neighbours, kept when it is at least
 // FieldDev-wide lambda_0 (so: only in cells of a SHARP transition -- the interface scenario's sigmoid; no cell of the fisheye or
 // vert_heterogeneous grids).  The fused step kernels add it up over the steps a ray hovers in such cells (Ray::hov) to find the
 // few rays per million whose trajectory amplifies rounding differences past the 1e-9 the path is held to; those are re-traced in
-// the reference's operation order (rtmi.hip, retrace).
-template <typename T> struct FlatBits;
-template <> struct FlatBits<double> { typedef unsigned long long type; };
-template <> struct FlatBits<float> { typedef unsigned type; };
+// the reference's operation order (rtmi.hip, retrace).  The entry's types and encoding: rt::FlatBits, rt::steep_entry_bits (rt_polytab.h).
 template <typename T> __device__ __forceinline__ bool flat_entry(typename FlatBits<T>::type b) {
     if constexpr (sizeof(T) == 8) return (unsigned)(b >> 32) != 0xffffffffu;
     else return b != ~(typename FlatBits<T>::type)0;
@@ -787,9 +780,6 @@ template <typename T> __device__ __forceinline__ bool flat_entry(typename FlatBi
 template <typename T> __device__ __forceinline__ float steep_of(typename FlatBits<T>::type b) {
     if constexpr (sizeof(T) == 8) return __builtin_bit_cast(float, (unsigned)b);     // only read when !flat_entry(b)
     else return 0.f;
-}
-__host__ __device__ inline unsigned long long steep_entry_bits(float lam) {
-    return 0xffffffff00000000ull | (unsigned long long)__builtin_bit_cast(unsigned, lam);
 }
 // per lane (vector load): the lanes of an incoherent wave, the one-lane-per-point lookups.  lam: the cell's steepness (0: none)
 template <typename T> __device__ __forceinline__ bool flat_lane(const FieldDev<T>& F, int cell, T& c, float& lam) {

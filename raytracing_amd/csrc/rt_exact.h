@@ -171,9 +171,8 @@ __device__ __forceinline__ double impulse(double a, double b, double step) { ret
 // thm 8.3 -- no overflow or underflow here: 0 <= a <= 1, d ~ the grid pitch): 3 instructions for the 11 of the IEEE sequence
 // (v_div_scale x2, v_rcp, four fma, v_div_fmas, v_div_fixup), 110 fewer per lookup.  Bits: every test that holds a
 // reference-order method to the oracle's bits runs through it (the oracle divides).
-// The table (rtmi.hip, fp_axis_tab_build) holds kAxisTab doubles per cell index: the seven reciprocals and a zero (what this
+// The table (field.hip, fp_axis_tab_build) holds kAxisTab (rt_polytab.h) doubles per cell index: the seven reciprocals and a zero (what this
 // function reads), then the cell's knots and the seven differences themselves for a wave that shares ONE cell (AxisTab below).
-constexpr int kAxisTab = 24;
 __device__ __forceinline__ void axis_exact(double v, int q, double a, double h, double b, double ih, const double* rd, int& j, int& l,
                                            double wl[2], double w[4]) {
     double t0, t1;

@@ -31,6 +31,12 @@
 #define RT_PT_HD
 #endif
 
+#if defined(__HIPCC__)
+// A wave vote straight from the predicate.  HIP's __ballot(int) converts the bool to an int and compares it with zero again
+// (v_cndmask + v_cmp per vote, 12 vector instructions per step of the bench kernel); the builtin takes the i1.
+__device__ __forceinline__ unsigned long long rt_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+#endif
+
 namespace rt {
 
 constexpr int kPolyStride = 40;
@@ -149,6 +155,19 @@ RT_PT_HD inline bool poly_cell_flat(const double c[36], double thr) {
     const double t = kPolyFlatN * __builtin_fabs(c[32]);
     return __builtin_fabs(c[33]) <= t && __builtin_fabs(c[34]) <= t && __builtin_fabs(c[35]) <= t;
 }
+
+// An entry of the flat-cell map in front of the table (what it means: rt_device.h, "The flat-cell map"): its integer type, and the
+// entry of an ordinary fp64 cell -- the high word all ones, the low word the cell's steepness as float bits.
+template <typename T> struct FlatBits;
+template <> struct FlatBits<double> { typedef unsigned long long type; };
+template <> struct FlatBits<float> { typedef unsigned type; };
+RT_PT_HD inline unsigned long long steep_entry_bits(float lam) {
+    return 0xffffffff00000000ull | (unsigned long long)__builtin_bit_cast(unsigned, lam);
+}
+
+// Doubles per cell index in the per-axis table of the reference-order lookup (field.hip fp_axis_tab_build writes it, rt_exact.h
+// AxisTab reads it)
+namespace ex { constexpr int kAxisTab = 24; }
 
 // The map from a point to its cell (jx, jy) and (u, v) in fp64, for the post-trace kernels that walk recorded rows (paraxial.hip,
 // sensitivity.hip): rt::poly_locate (rt_device.h) with u = (x - a) inv_h - j taken from the exact product, and FITPACK's argument

@@ -1,10 +1,11 @@
-// rtmi_host.h -- the host-side support layer of the post-trace translation units (wavefront, twopoint, paraxial, ttgrid,
-// sensitivity, beams, kirchhoff): the ways out of an entry, one call's device memory and event marks, grid sizing, and the
-// checks every entry that reads a batch's recorded rows makes.  A new post-trace unit starts from this header (DESIGN.md
-// section 15).  Everything is in an anonymous namespace: each unit gets its own copy, as with rt_crossing.h.
+// rtmi_host.h -- the host-side support layer of every translation unit: the ways out of an entry, one call's device memory and
+// event marks, grid sizing, and the checks every entry that reads a batch's recorded rows makes.  A new post-trace unit starts
+// from this header (DESIGN.md sections 15 and 16).  Everything is in an anonymous namespace: each unit gets its own copy, as with
+// rt_crossing.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -29,6 +30,19 @@
         const int rc_ = (expr);      \
         if (rc_) return rc_;         \
     } while (0)
+// The same two for the entries that spell their own name into the message (rtmi.hip, shard.hip): a HIP failure is reported with
+// the place in the source instead.
+#define HIP_TRY(expr)                                                                                                       \
+    do {                                                                                                                    \
+        hipError_t e_ = (expr);                                                                                             \
+        if (e_ != hipSuccess)                                                                                               \
+            return rtmi_internal_fail(RTMI_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + \
+                                                     std::to_string(__LINE__) + ")").c_str());                              \
+    } while (0)
+#define ARG_TRY(cond, msg)                                                                  \
+    do {                                                                                    \
+        if (!(cond)) return rtmi_internal_fail(RTMI_ERR_ARG, std::string(msg).c_str());     \
+    } while (0)
 
 namespace {
 
@@ -42,6 +56,7 @@ struct DevMem {
         return e;
     }
     void adopt(void* v) { p.push_back(v); }      // a buffer another unit allocated for this call
+    void release(void* v) { p.erase(std::find(p.begin(), p.end(), v)); }     // ... and one this call hands to its caller
     ~DevMem() { for (void* v : p) (void)hipFree(v); }
 };
 
@@ -65,6 +80,9 @@ template <int N> struct EventMarks {
     }
     ~EventMarks() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
 };
+
+// f(T()) with T the element type of a field or batch: the one place where a dtype becomes a template argument
+template <typename F> auto by_dtype(int dtype, F&& f) { return dtype == RTMI_F64 ? f(double()) : f(float()); }
 
 // one lane per item, 256 lanes per block
 dim3 blocks(long n) { return dim3((unsigned)((n + 255) / 256)); }

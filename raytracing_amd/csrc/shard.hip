@@ -28,25 +28,11 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/rtmi.h"
-#include "rtmi_internal.h"
-
-#define RTMI_EXPORT extern "C" __attribute__((visibility("default")))
+#include "rtmi_host.h"
 
 namespace {
 
 int fail(int code, const std::string& msg) { return rtmi_internal_fail(code, msg.c_str()); }
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(RTMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ \
-                                          ":" + std::to_string(__LINE__) + ")");                        \
-    } while (0)
-#define ARG_TRY(cond, msg)                              \
-    do {                                                \
-        if (!(cond)) return fail(RTMI_ERR_ARG, (msg));  \
-    } while (0)
 
 // Every rtmi_shard_* entry walks over the shard's devices with hipSetDevice; the caller's current device is put back on every
 // exit path (the rest of the ABI rejects handles whose field lives on another device, and a caller's torch tensors would land

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""np.exp (float64 arrays) vs its restatement in oracle/rt_oracle.c (np_exp) and raytracing_amd/csrc/rtmi.hip.
+"""np.exp (float64 arrays) vs its restatement in oracle/rt_oracle.c (np_exp) and raytracing_amd/csrc/field.hip.
 
 The reference samples the interface field with np.exp on the meshgrid (RT_bench.py:107).  On AVX512_SKX machines numpy's
 wheels route float64 exp to Intel SVML's `__svml_exp8_ha` (numpy/_core/src/umath/svml/linux/avx512/svml_z0_exp_d_ha.s,
