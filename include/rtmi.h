@@ -681,6 +681,16 @@ void rtmi_shard_destroy(rtmi_shard *s);
  * glibc 2.35's sin()/cos(), i.e. numpy's np.sin/np.cos, bit for bit for |x| < 105414350) evaluated on the device
  * for n host values.  s[n], c[n]: host, fp64. */
 int rtmi_debug_sincos(int64_t n, const double *x, double *s, double *c);
+/* Diagnostic: numpy's float64 arctan2 as the library restates it for op4/5-style angle updates (Intel SVML's __svml_atan28_ha
+ * on its main path, both operands in [2^-1020, 2^993); anything else is the device's atan2) evaluated on the device for n host
+ * pairs.  out[n]: host, fp64.  Decodes the reciprocal table on the current device first if no batch has yet. */
+int rtmi_debug_arctan2(int64_t n, const double *y, const double *x, double *out);
+/* Diagnostic: the 65 536-entry VRCP14PD table rtmi_debug_arctan2's function reads, as decoded on the current device (decoding it
+ * first if nothing has yet).  out65536: host. */
+int rtmi_debug_rcp14_table(uint16_t *out65536);
+/* Diagnostic: numpy's float64 ARRAY exp as the interface scenario's field build evaluates it (SVML's __svml_exp8_ha on its main
+ * path, |x| < 707.7; the device's exp beyond) on the device for n host values.  out[n]: host, fp64. */
+int rtmi_debug_exp(int64_t n, const double *x, double *out);
 /* Diagnostic: the lookup the fast-form step methods (op1/2/6/7/8, every fp32 batch) make -- the grid cell's polynomial
  * (one per cell, converted from FITPACK's splines on the true knots at field build) -- for npts host points
  * -> n, dn/dx, dn/dy (host, fp64).  Within 1e-15 of the field's scale of rtmi_field_eval (FITPACK's own arithmetic,

@@ -28,6 +28,7 @@ constexpr double kSteepRate = 40.0;
 // rounded toward zero onto a 2^-4 grid -- r = x - N*ln2 in two pieces, a degree-6 polynomial in three interleaved pairs,
 // 2^(j/16) from a 16-entry table with its correction term, scaled by 2^floor(N).  |x| >= 707.7 (SVML's scalar fall-back):
 // ocml's exp -- there 1 + e rounds to e or to 1 and the interface's n is sqrt(2) or 1 whatever the last bits of e.
+// On the device: tests/test_gpu_elementary.py (rtmi_debug_exp, below) -- the oracle's bits on 2.6e6 main-path arguments.
 __device__ static double np_exp(double x) {
     static const double T16[16] = {0x1.0000000000000p+0, 0x1.0b5586cf9890fp+0, 0x1.172b83c7d517bp+0, 0x1.2387a6e756238p+0,
         0x1.306fe0a31b715p+0, 0x1.3dea64c123422p+0, 0x1.4bfdad5362a27p+0, 0x1.5ab07dd485429p+0, 0x1.6a09e667f3bcdp+0,
@@ -514,5 +515,28 @@ RTMI_EXPORT int rtmi_field_read(const rtmi_field* f, double* x, double* y, doubl
     if (Z) RTMI_HIP(hipMemcpy(Z, f->dZ, nz, hipMemcpyDeviceToHost));
     if (cdy) RTMI_HIP(hipMemcpy(cdy, f->dCdy, nz, hipMemcpyDeviceToHost));
     if (cdx) RTMI_HIP(hipMemcpy(cdx, f->dCdx, nz, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ------------------------------------------------------------------ diagnostic: numpy's array exp (np_exp) on the device
+__global__ void k_debug_exp(long n, const double* x, double* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = np_exp(x[i]);
+}
+
+RTMI_EXPORT int rtmi_debug_exp(int64_t n, const double* x, double* out) {
+    ARG_TRY(x && out, "rtmi_debug_exp: null");
+    ARG_TRY(n >= 0, "rtmi_debug_exp: n < 0");
+    if (n == 0) return RTMI_OK;
+    const char* who = "rtmi_debug_exp";
+    DevMem mem;
+    double* d = nullptr;
+    const size_t nb = (size_t)n * sizeof(double);
+    RTMI_HIP(mem.get(&d, 2 * nb));
+    RTMI_HIP(hipMemcpy(d, x, nb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_exp, blocks(n), dim3(256), 0, nullptr, (long)n, d, d + n);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipMemcpy(out, d + n, nb, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }

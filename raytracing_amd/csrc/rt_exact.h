@@ -93,6 +93,8 @@ template <bool INL> __device__ __forceinline__ SinCos sincos_sel(double x) {
 // last bit for 7 % of arguments) -- same text as oracle/rt_oracle.c np_arctan2, see there; tools/check_np_atan2.py: 0
 // mismatches against np.arctan2 on 1.6e7 argument pairs.  Its reciprocal starts from the VRCP14PD instruction, which is a
 // table of the operand's top 16 mantissa bits (rt_rcp14_table.h; decoded into g_rcp14 once per device by k_rcp14_init).
+// On the device: tests/test_gpu_elementary.py (rtmi_debug_arctan2, rtmi_debug_rcp14_table) -- the oracle's bits on 2.1e6 pairs that
+// read every table entry, and all 65 536 decoded entries the header's.
 __device__ unsigned short g_rcp14[65536];
 __device__ const unsigned long long kRcp14Words[RT_RCP14_WORDS] = {RT_RCP14_DELTAS};
 __device__ __forceinline__ double vrcp14pd(double x) {

@@ -2759,3 +2759,36 @@ RTMI_EXPORT int rtmi_debug_sincos(int64_t n, const double* x, double* s, double*
     RTMI_HIP(hipMemcpy(c, d + 2 * n, nb, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
+
+// ------------------------------------------------------------------ diagnostic: numpy's arctan2 (rt::ex::atan2_) and its table
+__global__ void k_debug_arctan2(long n, const double* y, const double* x, double* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = rt::ex::atan2_(y[i], x[i]);
+}
+
+RTMI_EXPORT int rtmi_debug_arctan2(int64_t n, const double* y, const double* x, double* out) {
+    ARG_TRY(y && x && out, "rtmi_debug_arctan2: null");
+    ARG_TRY(n >= 0, "rtmi_debug_arctan2: n < 0");
+    if (n == 0) return RTMI_OK;
+    const char* who = "rtmi_debug_arctan2";
+    RTMI_RC(ensure_rcp14_table(nullptr));
+    DevMem mem;
+    double* d = nullptr;
+    const size_t nb = (size_t)n * sizeof(double);
+    RTMI_HIP(mem.get(&d, 3 * nb));
+    RTMI_HIP(hipMemcpy(d, y, nb, hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(d + n, x, nb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_arctan2, blocks(n), dim3(256), 0, nullptr, (long)n, d, d + n, d + 2 * n);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipMemcpy(out, d + 2 * n, nb, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_debug_rcp14_table(uint16_t* out65536) {
+    ARG_TRY(out65536, "rtmi_debug_rcp14_table: null");
+    const char* who = "rtmi_debug_rcp14_table";
+    RTMI_RC(ensure_rcp14_table(nullptr));
+    RTMI_HIP(hipMemcpyFromSymbol(out65536, HIP_SYMBOL(rt::ex::g_rcp14), 65536 * sizeof(uint16_t)));
+    return RTMI_OK;
+}

@@ -1180,6 +1180,30 @@ def device_sincos(x):
     return s, c
 
 
+def device_arctan2(y, x):
+    """The library's restatement of numpy's float64 arctan2 (rtmi_debug_arctan2: rt::ex::atan2_), evaluated on the device."""
+    y, x = np.broadcast_arrays(np.asarray(y, dtype=np.float64), np.asarray(x, dtype=np.float64))
+    y = np.ascontiguousarray(y); x = np.ascontiguousarray(x)
+    out = np.empty_like(x)
+    check(lib().rtmi_debug_arctan2(x.size, dptr(y), dptr(x), dptr(out)))
+    return out
+
+
+def device_exp(x):
+    """The field build's restatement of numpy's float64 array exp (rtmi_debug_exp: np_exp of k_sample), evaluated on the device."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    check(lib().rtmi_debug_exp(x.size, dptr(x), dptr(out)))
+    return out
+
+
+def device_rcp14_table():
+    """The VRCP14PD table device_arctan2 reads, as decoded on the current device (rtmi_debug_rcp14_table) -> uint16 [65536]."""
+    out = np.empty(65536, dtype=np.uint16)
+    check(lib().rtmi_debug_rcp14_table(out.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return out
+
+
 _ACC = ("x", "y", "theta", "dist_sim", "dist_real", "T")
 
 

@@ -78,6 +78,43 @@ def test_field_is_the_references_bits(scen, rb, fields):
     assert np.abs(gx - g["gx"]).max() <= 4e-15 * scale and np.abs(gy - g["gy"]).max() <= 4e-15 * scale
 
 
+OFF_DEFAULT = [("interface", (-1, 2, -0.35, 0.4), 0.0173, (521, 391)),      # all 391 exp arguments in np_exp's main path
+               ("interface", (0, 1, -1, 1), 0.11, (64, 73)),
+               ("interface", (-2, 3, -3.3, -2.2), 0.0091, (1209, 781)),     # 477 arguments in the main path, the rest overflow
+               ("fisheye", (-0.5, 0.7, -0.9, 0.2), 0.031, (233, 230)),
+               ("vert_heterogeneous", (-1, 1, -2, 0), 0.07, (115, 115))]
+
+
+@pytest.mark.parametrize("scen,limits,delta,shape", OFF_DEFAULT, ids=[f"{c[0]}-{c[3][0]}x{c[3][1]}" for c in OFF_DEFAULT])
+def test_field_off_the_default_shape_is_the_oracles_bits(scen, limits, delta, shape, rb):
+    """rtmi_field_build at extents and pitches other than the scenarios' own (k_sample and the device's linspace run nowhere
+    else): grids whose sides are no multiple of a block (64 is one block of k_givens / k_fpback / k_polytab exactly, 73 one and a
+    bit, the others several and a ragged last one).  All five arrays are the oracle's bit for bit; n_gradient at 2 000 random
+    points of the grid is within test_field_is_the_references_bits' bounds of the oracle's; and the interface scenario's Z is
+    what rtmi_debug_exp gives on the same -y / 0.005 through the scenario's formula, which ties that entry to k_sample."""
+    from oracle import rt_oracle as O
+    import elementary_sets as E
+    F, OF = rb.Field.build(scen, limits, delta), O.Field(scen, limits, delta)
+    try:
+        assert (F.qx, F.qy) == shape == (OF.qx, OF.qy)
+        x, y, Z, cdy, cdx = F.arrays()
+        for a, b in zip((x, y, Z, cdy, cdx), OF.arrays()):
+            assert _bits_equal(a, b), f"{np.sum(a != b)} of {a.size} differ"
+        rng = np.random.default_rng(shape[0])
+        px, py = rng.uniform(x[0], x[-1], 2000), rng.uniform(y[0], y[-1], 2000)
+        (n, gx, gy), (on, ogx, ogy) = F.n_gradient(px, py), OF.n_gradient(px, py)
+        scale = max(np.abs(cdx).max(), np.abs(cdy).max())
+        assert np.abs(n - on).max() <= 1e-15 * np.abs(Z).max()
+        assert np.abs(gx - ogx).max() <= 4e-15 * scale and np.abs(gy - ogy).max() <= 4e-15 * scale
+        if scen == "interface":
+            arg = -y / 0.005
+            assert np.sum(np.abs(arg) < E.EXP_MAIN) == {391: 391, 73: 63, 781: 477}[F.qy]
+            col = E.interface_n(rb.device_exp(arg))
+            assert _bits_equal(Z, np.repeat(col[:, None], F.qx, axis=1))
+    finally:
+        F.close()
+
+
 def _bits_equal(a, b):
     return np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64))
 
