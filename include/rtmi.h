@@ -245,7 +245,9 @@ int rtmi_metric(rtmi_batch *b, int kind, double *out);
 /* Isochrone points: per-ray PCHIP interpolation (scipy PchipInterpolator's algorithm) of x, y, theta at the given
  * traveltimes, from the recorded T column -- the per-ray stage of the reference's wavefront extraction
  * (RT_bench.py:987-1003).  out[ntimes][3][R], host, fp64; NaN where a ray never reaches that traveltime
- * (the reference skips such rays, :997).  Needs record_stride 1. */
+ * (the reference skips such rays, :997), a ray with fewer than two rows included, and NaN for a time before the ray's first
+ * recorded T (scipy would extrapolate there; the reference never asks).  The last recorded T itself is reached.
+ * Needs record_stride 1. */
 int rtmi_isochrones(rtmi_batch *b, int32_t ntimes, const double *times, double *out);
 
 /* Wavefronts: the across-ray stage of the reference's wavefront extraction (RT_bench.py:1005-1026, 1043-1044).  For each
@@ -257,7 +259,10 @@ int rtmi_isochrones(rtmi_batch *b, int32_t ntimes, const double *times, double *
  *   nodes[ntimes][7][R]      per sorted position j < count: y, x, ray angle, dx/dy, normal angle, |ray angle - normal angle|,
  *                            ray index (caller's order); NaN at j >= count, and in the derived columns when count < 2
  *   fine[ntimes][2][nfine]   x, y of the interpolated wavefront (NaN when count < 2); nfine = 0 skips it (fine may be NULL)
- * Needs record_stride 1.  Points with equal y make scipy raise; here they give NaN in the derived columns.
+ * Needs record_stride 1.  Two points with equal y (-0.0 and +0.0 are equal) make scipy raise; here such a wavefront keeps
+ * count and its y, x, ray angle and ray index columns, and has NaN throughout dx/dy, normal angle, |ray angle - normal angle|
+ * and fine -- at every point, not at the tied ones alone, since scipy refuses the data set as a whole.  The other wavefronts of
+ * the call are not affected.
  * All `ntimes` wavefronts are made in ONE pass (one sort of every point by y, a stable regrouping per traveltime, one PCHIP
  * stage, one copy to the host): the 45 frames of the reference's animation (travel_time = 0.01 + 0.01 frame, :1066-1102) are
  * one call. */

@@ -7,7 +7,7 @@
 // handled in one pass -- the reference's animation (:1066-1102) re-does the whole extraction per frame, 45 times.
 // Third-party arithmetic restated: scipy.interpolate.PchipInterpolator (scipy 1.15.3 in the build image):
 // _find_derivatives (Fritsch-Butland weighted harmonic mean, three-point end rule), CubicHermiteSpline's power-basis
-// coefficients, PPoly's Horner evaluation and .derivative().
+// coefficients, PPoly's evaluation (a sum of powers, lowest first) and .derivative().
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -80,14 +80,23 @@ __global__ void k_gather(const double* iso, long R, const int* order, const unsi
     nd[2 * R + j] = ok ? it[2 * R + k] : NAN;    // ray angle
     nd[6 * R + j] = ok ? (double)k : NAN;        // ray index (caller's order)
 }
+// tie[t] (zeroed by the caller) = 1 when two neighbours of wavefront t's sorted points have the same y (-0.0 and +0.0 are the
+// same): scipy refuses such a data set as a whole, so the whole wavefront gets no interpolant.  Every lane that sees a tie
+// stores the same 1.
+__global__ void k_ties(long R, const unsigned long long* count, const double* nodes_all, int* tie) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (j + 1 >= (long)count[t]) return;               // count <= R
+    const double* y = nodes_all + (size_t)t * 7 * R;
+    if (y[j + 1] == y[j]) tie[t] = 1;
+}
 // derivative of the interpolant at its own points, angles (:1021-1026, :1032)
-__global__ void k_nodes(long R, const unsigned long long* count, double* nodes_all, double* deriv_all) {
+__global__ void k_nodes(long R, const unsigned long long* count, const int* tie, double* nodes_all, double* deriv_all) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
     const long n = (long)count[t];
     if (j >= R) return;
     double* nodes = nodes_all + (size_t)t * 7 * R;
     double d = NAN, slope = NAN, normal = NAN, diff = NAN;
-    if (j < n && n >= 2) {
+    if (j < n && n >= 2 && !tie[t]) {
         const double *y = nodes, *x = nodes + R;
         d = pchip_deriv(y, x, j, n);
         slope = d;
@@ -110,7 +119,8 @@ __global__ void k_nodes(long R, const unsigned long long* count, double* nodes_a
     nodes[5 * R + j] = diff;
 }
 // the interpolant on nfine equally spaced y between the first and the last point (:1043-1044, :1096-1097)
-__global__ void k_fine(long R, const unsigned long long* count, const double* nodes_all, const double* deriv_all, int nfine, double* fine_all) {
+__global__ void k_fine(long R, const unsigned long long* count, const int* tie, const double* nodes_all, const double* deriv_all, int nfine,
+                       double* fine_all) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     const long t = blockIdx.y;
     if (q >= nfine) return;
@@ -119,7 +129,7 @@ __global__ void k_fine(long R, const unsigned long long* count, const double* no
     const double* deriv = deriv_all + (size_t)t * R;
     double* fine = fine_all + (size_t)t * 2 * nfine;
     double xf = NAN, yf = NAN;
-    if (n >= 2) {
+    if (n >= 2 && !tie[t]) {
         const double *y = nodes, *x = nodes + R;
         const double a = y[0], b = y[n - 1];
         const double step = (b - a) / (double)(nfine - 1);
@@ -133,7 +143,7 @@ __global__ void k_fine(long R, const unsigned long long* count, const double* no
         const double d0 = deriv[lo], d1 = deriv[lo + 1];
         const double tq = (d0 + d1 - 2 * m) / dx;
         const double c0 = tq / dx, c1 = (m - d0) / dx - tq;
-        xf = ((c0 * s + c1) * s + d0) * s + x[lo];                           // PPoly: Horner in (y - y_lo)
+        xf = ((c0 * s + c1) * s + d0) * s + x[lo];                           // Horner in (y - y_lo); PPoly sums the powers
     }
     fine[q] = xf;
     fine[nfine + q] = yf;
@@ -167,6 +177,7 @@ RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* tim
     int *vals = nullptr, *vals2 = nullptr;
     unsigned *fk = nullptr, *fk2 = nullptr;
     unsigned long long* dcount = nullptr;
+    int* dtie = nullptr;
     std::vector<unsigned long long> hcount;
     void* tmp = nullptr;
     size_t tmp1 = 0, tmp2 = 0;
@@ -183,6 +194,7 @@ RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* tim
     RTMI_HIP(mem.get(&fk, N * 4)); RTMI_HIP(mem.get(&fk2, N * 4));
     RTMI_HIP(mem.get(&dn, 7 * N * 8)); RTMI_HIP(mem.get(&dd, N * 8));
     RTMI_HIP(mem.get(&dcount, (size_t)tc * 8));
+    RTMI_HIP(mem.get(&dtie, (size_t)tc * 4));
     if (nfine) RTMI_HIP(mem.get(&df, (size_t)tc * 2 * (size_t)nfine * 8));
     RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp1, keys, keys2, vals, vals2, (int)N, 0, 64, st));
     RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp2, fk, fk2, vals2, vals, (int)N, 0, fbits, st));
@@ -193,6 +205,7 @@ RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* tim
         const double* iso_c = iso + (size_t)t0 * 3 * Rz;
         const dim3 grd(blocks(R).x, (unsigned)nt);
         RTMI_HIP(hipMemsetAsync(dcount, 0, (size_t)nt * 8, st));
+        RTMI_HIP(hipMemsetAsync(dtie, 0, (size_t)nt * 4, st));
         hipLaunchKernelGGL(k_keys, grd, blk, 0, st, iso_c, R, keys, vals, dcount);
         RTMI_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp1, keys, keys2, vals, vals2, (int)n, 0, 64, st));           // every point by y
         if (nt > 1) {
@@ -201,8 +214,9 @@ RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* tim
         }
         const int* order = nt > 1 ? vals : vals2;
         hipLaunchKernelGGL(k_gather, grd, blk, 0, st, iso_c, R, order, dcount, dn);
-        hipLaunchKernelGGL(k_nodes, grd, blk, 0, st, R, dcount, dn, dd);
-        if (nfine) hipLaunchKernelGGL(k_fine, dim3(blocks(nfine).x, (unsigned)nt), blk, 0, st, R, dcount, dn, dd, (int)nfine, df);
+        hipLaunchKernelGGL(k_ties, grd, blk, 0, st, R, dcount, dn, dtie);
+        hipLaunchKernelGGL(k_nodes, grd, blk, 0, st, R, dcount, dtie, dn, dd);
+        if (nfine) hipLaunchKernelGGL(k_fine, dim3(blocks(nfine).x, (unsigned)nt), blk, 0, st, R, dcount, dtie, dn, dd, (int)nfine, df);
         RTMI_HIP(hipGetLastError());
         RTMI_HIP(hipMemcpyAsync(hcount.data(), dcount, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
         RTMI_HIP(hipMemcpyAsync(nodes + (size_t)t0 * 7 * Rz, dn, 7 * n * 8, hipMemcpyDeviceToHost, st));

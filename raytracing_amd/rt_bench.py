@@ -538,7 +538,8 @@ class Batch:
         points of the wavefront sorted by y -- 'y', 'x', 'angle' (ray angle), 'dxdy' (derivative of the PCHIP interpolant
         x(y) at the points), 'normal' (normal angle), 'angle_diff' (|ray angle - normal angle|), 'ray' (ray indices) --
         and 'x_fine', 'y_fine' (the interpolated wavefront on nfine points).  Wavefronts with < 2 points have empty
-        derived arrays, like the reference, which skips them (:1011)."""
+        derived arrays, like the reference, which skips them (:1011); one with two points of equal y (scipy raises) has NaN
+        throughout its derived arrays."""
         t = np.ascontiguousarray(times, dtype=np.float64)
         nt = len(t)
         count = np.zeros(nt, dtype=np.int64)
