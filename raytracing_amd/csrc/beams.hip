@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rt_crossing.h"
+#include "rt_rows.h"
 #include "rtmi_host.h"
 
 namespace {
@@ -59,44 +60,38 @@ __device__ __forceinline__ double step_qmax(const Beam& B, double qqa, double qq
 
 // ------------------------------------------------------------------------------------------------------------ (1) prep
 struct PrepArgs {
-    const void* s_ray;          // [rec_rows][6][R] of T
-    const int32_t* istep;       // [R] slot order
     const int32_t* slot;        // [R] or NULL: slot of the caller's ray o
     const double* tube;         // [rec_rows][5][R] slot order: Q1 P1 Q2 P2 n
     const long long* rowbase;   // [R + 1] caller order: the ray's first global row
     const double* w;            // [R] caller order: quadrature weight (trapezoid, taper)
-    long R, rec_rows, G;
+    long G;
     double eps;
     double* rv;                 // [kRowCols][G]
     int32_t* row_ray;           // [G]: the caller's ray of each row
     uint32_t* seg_row;          // [G - R]: the first row of each step, in (ray, step) order
 };
 
-__device__ __forceinline__ long rows_of(const int32_t* istep, const int32_t* slot, long rec_rows, long o) {
-    const long l = istep[slot ? (long)slot[o] : o];
-    return (l < rec_rows - 1 ? l : rec_rows - 1) + 1;
+// nrows[o] = the recorded rows of the caller's ray o, nrows[R] = 0
+template <typename T> __global__ void k_rows(Rows<T> rec, const int32_t* slot, long long* nrows) {
+    const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o < rec.R) nrows[o] = rec.last_recorded(slot ? (long)slot[o] : o) + 1;
+    else if (o == rec.R) nrows[rec.R] = 0;
 }
 
-__global__ void k_rows(const int32_t* istep, const int32_t* slot, long R, long rec_rows, long long* nrows) {
+template <typename T> __global__ void k_prep(Rows<T> rec, PrepArgs A) {
     const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o < R) nrows[o] = rows_of(istep, slot, rec_rows, o);
-    else if (o == R) nrows[R] = 0;
-}
-
-template <typename T> __global__ void k_prep(PrepArgs A) {
-    const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= A.R) return;
-    const long R = A.R, G = A.G;
+    if (o >= rec.R) return;
+    const long R = rec.R, G = A.G;
     const long k = A.slot ? (long)A.slot[o] : o;
-    const long nr = rows_of(A.istep, A.slot, A.rec_rows, o);
+    const long nr = rec.last_recorded(k) + 1;
     const long g0 = (long)A.rowbase[o];
-    const T* col = reinterpret_cast<const T*>(A.s_ray) + k;
+    const T* col = rec.row(0, k);
     const double eps = A.eps;
     const double W = A.w[o] * sqrt(eps * A.tube[4 * R + k]) / (4.0 * kPi);
     double phi = -0.5 * kPi, aprev = -0.5 * kPi;
     for (long j = 0; j < nr; j++) {
-        const T* r = col + (size_t)j * 6 * R;
-        const double x = (double)r[0], y = (double)r[R], t = (double)r[4 * R], th = (double)r[5 * R];
+        const T* r = col + (size_t)j * rec.pitch();
+        const double x = (double)r[COL_X * R], y = (double)r[COL_Y * R], t = (double)r[COL_T * R], th = (double)r[COL_TH * R];
         const double* q = A.tube + (size_t)j * 5 * R + k;
         const double q1 = q[0], p1 = q[R], q2 = q[2 * R], p2 = q[3 * R], n = q[4 * R];
         const double eq1 = eps * q1, ep1 = eps * p1;
@@ -387,7 +382,7 @@ RTMI_EXPORT int rtmi_gaussian_beams(rtmi_batch* b, int32_t fan_size, const rtmi_
         hipLaunchKernelGGL(k_inverse<int32_t>, blocks(R), dim3(256), 0, nullptr, v.perm, slot, R);
         RTMI_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_rows, blocks(R + 1), dim3(256), 0, nullptr, v.istep, slot, R, (long)v.rec_rows, nrows);
+    by_dtype(v.dtype, [&](auto t) { hipLaunchKernelGGL(k_rows<decltype(t)>, blocks(R + 1), dim3(256), 0, nullptr, rows_of<decltype(t)>(v), slot, nrows); });
     RTMI_HIP(hipGetLastError());
     size_t scan_bytes = 0;
     void* scan_tmp = nullptr;
@@ -404,9 +399,8 @@ RTMI_EXPORT int rtmi_gaussian_beams(rtmi_batch* b, int32_t fan_size, const rtmi_
     RTMI_HIP(mem.get(&rv, (size_t)kRowCols * G * sizeof(double)));
     RTMI_HIP(mem.get(&row_ray, (size_t)G * sizeof(int32_t)));
     RTMI_HIP(mem.get(&seg_row, (size_t)nseg * sizeof(uint32_t)));
-    const PrepArgs pa{v.s_ray, v.istep, slot, tube, rowbase, dw, R, (long)v.rec_rows, G, bp->eps, rv, row_ray, seg_row};
-    if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_prep<double>, blocks(R), dim3(256), 0, nullptr, pa);
-    else hipLaunchKernelGGL(k_prep<float>, blocks(R), dim3(256), 0, nullptr, pa);
+    const PrepArgs pa{slot, tube, rowbase, dw, G, bp->eps, rv, row_ray, seg_row};
+    by_dtype(v.dtype, [&](auto t) { hipLaunchKernelGGL(k_prep<decltype(t)>, blocks(R), dim3(256), 0, nullptr, rows_of<decltype(t)>(v), pa); });
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(ev.mark(1));
 

@@ -18,6 +18,7 @@
 
 #include "rt_crossing.h"
 #include "rt_polytab.h"
+#include "rt_rows.h"
 #include "rtmi_host.h"
 
 namespace {
@@ -139,10 +140,6 @@ __device__ __forceinline__ void put_nan(double* out, long R, long o) {
 }
 
 struct ParaxArgs {
-    const void* s_ray;          // [rec_rows][6][R] of the batch's dtype
-    const int32_t* istep;       // [R] last written row
-    const int32_t* perm;        // [R] or NULL: slot k holds the caller's ray perm[k]
-    long R, rec_rows;
     Line L;
     int has_line, kmax;
     int32_t* count;             // [R] or NULL
@@ -160,23 +157,22 @@ __device__ __forceinline__ void put_tube(double* out, long R, long i, long k, co
 
 // One lane per ray (slot k); answers in the caller's order.  A crossing of the line (the rule and tau* of rtmi_crossings) gets
 // a partial step of length tau* L with K and 1/n interpolated linearly in tau along the step.
-template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
+template <typename T> __global__ void k_paraxial(PolyF<T> F, Rows<T> rec, ParaxArgs A) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= A.R) return;
-    const long R = A.R;
-    const long o = A.perm ? (long)A.perm[k] : k;
-    const size_t P = (size_t)6 * R;
-    const T* col = reinterpret_cast<const T*>(A.s_ray) + k;
-    long last = A.istep[k];
-    if (A.row_tube && last >= A.rec_rows) last = A.rec_rows - 1;    // beams take a truncated ray's recorded rows
+    if (k >= rec.R) return;
+    const long R = rec.R;
+    const long o = rec.caller(k);
+    const size_t P = rec.pitch();
+    const T* col = rec.row(0, k);
+    const long last = A.row_tube ? rec.last_recorded(k) : rec.last(k);    // beams take a truncated ray's recorded rows
     const Line L = A.L;
     int n = 0;
-    if (last >= A.rec_rows) {
+    if (last >= rec.rec_rows) {
         n = -1;
         put_nan(A.at_end, R, o);
     } else {
-        double x0 = (double)col[0], y0 = (double)col[R];
-        const double th0 = (double)col[5 * R];
+        double x0 = (double)col[COL_X * R], y0 = (double)col[COL_Y * R];
+        const double th0 = (double)col[COL_TH * R];
         double c0 = cos_g(th0), s0 = sin_g(th0);
         NG2 f = lookup(F, x0, y0);
         const double nsrc = f.n;
@@ -188,12 +184,12 @@ template <typename T> __global__ void k_paraxial(PolyF<T> F, ParaxArgs A) {
         if (A.row_tube) put_tube(A.row_tube, R, 0, k, t, nsrc);
         // the next row's three loads go out a step ahead
         double xn = 0.0, yn = 0.0, tn = 0.0;
-        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; tn = (double)col[P + 5 * R]; }
+        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + COL_Y * R]; tn = (double)col[P + COL_TH * R]; }
         for (long i = 1; i <= last; i++) {
             const double x1 = xn, y1 = yn, th1 = tn;
             if (i < last) {
                 const T* r = col + (size_t)(i + 1) * P;
-                xn = (double)r[0]; yn = (double)r[R]; tn = (double)r[5 * R];
+                xn = (double)r[COL_X * R]; yn = (double)r[COL_Y * R]; tn = (double)r[COL_TH * R];
             }
             const double c1 = cos_g(th1), s1 = sin_g(th1);
             f = lookup(F, x1, y1);
@@ -243,11 +239,11 @@ template <typename T> PolyF<T> poly_f(const rtmi_internal_poly& v) {
     return PolyF<T>{(const T*)v.poly, v.flat, v.ncx, v.ncy, v.ax, v.bx, v.inv_hx, v.ay, v.by, v.inv_hy};
 }
 
-// k_paraxial on a batch's rows: a's outputs are the caller's, its first five members come from the view
-int launch(const char* who, const Recorded& r, ParaxArgs a) {
-    a.s_ray = r.v.s_ray; a.istep = r.v.istep; a.perm = r.v.perm; a.R = (long)r.v.R; a.rec_rows = (long)r.v.rec_rows;
-    if (r.v.dtype == RTMI_F64) hipLaunchKernelGGL(k_paraxial<double>, blocks(a.R), dim3(256), 0, nullptr, poly_f<double>(r.poly), a);
-    else hipLaunchKernelGGL(k_paraxial<float>, blocks(a.R), dim3(256), 0, nullptr, poly_f<float>(r.poly), a);
+// k_paraxial on a batch's rows
+int launch(const char* who, const Recorded& r, const ParaxArgs& a) {
+    by_dtype(r.v.dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_paraxial<decltype(t)>, blocks((long)r.v.R), dim3(256), 0, nullptr, poly_f<decltype(t)>(r.poly), rows_of<decltype(t)>(r.v), a);
+    });
     RTMI_HIP(hipGetLastError());
     return RTMI_OK;
 }
@@ -274,7 +270,7 @@ RTMI_EXPORT int rtmi_paraxial(rtmi_batch* b, const double line[3], int32_t kmax,
     RTMI_HIP(mem.get(&dc, R * sizeof(int32_t)));
     RTMI_HIP(mem.get(&de, (size_t)kCols * R * sizeof(double)));
     if (K) RTMI_HIP(mem.get(&dl, (size_t)K * kCols * R * sizeof(double)));
-    RTMI_RC(launch(who, r, ParaxArgs{nullptr, nullptr, nullptr, 0, 0, L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr, nullptr}));
+    RTMI_RC(launch(who, r, ParaxArgs{L, line ? 1 : 0, K, dc, dl, de, nullptr, nullptr, nullptr}));
     RTMI_HIP(hipMemcpy(at_end, de, (size_t)kCols * R * sizeof(double), hipMemcpyDeviceToHost));
     if (count) RTMI_HIP(hipMemcpy(count, dc, R * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (K) RTMI_HIP(hipMemcpy(at_line, dl, (size_t)K * kCols * R * sizeof(double), hipMemcpyDeviceToHost));
@@ -289,8 +285,7 @@ int paraxial_rows(const char* who, rtmi_batch* b, double* row_J, int32_t* row_km
     DevMem mem;
     double* de = nullptr;
     RTMI_HIP(mem.get(&de, (size_t)kCols * (size_t)r.v.R * sizeof(double)));
-    RTMI_RC(launch(who, r, ParaxArgs{nullptr, nullptr, nullptr, 0, 0, Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah,
-                                     row_tube}));
+    RTMI_RC(launch(who, r, ParaxArgs{Line{0.0, 0.0, 0.0}, 0, 0, nullptr, nullptr, de, row_J, row_kmah, row_tube}));
     RTMI_HIP(hipDeviceSynchronize());
     return RTMI_OK;
 }
@@ -354,8 +349,9 @@ RTMI_EXPORT int rtmi_field_eval_dgrad(const rtmi_field* f, int64_t npts, const d
     RTMI_HIP(hipMemcpy(d, x, nb, hipMemcpyHostToDevice));
     RTMI_HIP(hipMemcpy(d + npts, y, nb, hipMemcpyHostToDevice));
     const dim3 g = blocks(npts), blk(256);
-    if (pv.dtype == RTMI_F64) hipLaunchKernelGGL(k_field_dgrad<double>, g, blk, 0, nullptr, poly_f<double>(pv), (long)npts, d, d + npts, d + 2 * npts);
-    else hipLaunchKernelGGL(k_field_dgrad<float>, g, blk, 0, nullptr, poly_f<float>(pv), (long)npts, d, d + npts, d + 2 * npts);
+    by_dtype(pv.dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_field_dgrad<decltype(t)>, g, blk, 0, nullptr, poly_f<decltype(t)>(pv), (long)npts, d, d + npts, d + 2 * npts);
+    });
     RTMI_HIP(hipGetLastError());
     double* outs[4] = {gx_x, gx_y, gy_x, gy_y};
     for (int q = 0; q < 4; q++) RTMI_HIP(hipMemcpy(outs[q], d + (2 + q) * npts, nb, hipMemcpyDeviceToHost));

@@ -1499,6 +1499,11 @@ int rtmi_internal_batch_info(rtmi_batch* b, const rtmi_field** f, rtmi_params* p
     return RTMI_OK;
 }
 
+int rtmi_internal_on_device(const char* who, const rtmi_field* f) {
+    DEVICE_TRY(f, who);
+    return RTMI_OK;
+}
+
 int rtmi_internal_batch_rays(rtmi_batch* b, int64_t* R) {
     ARG_TRY(b && R, "rtmi_internal_batch_rays: null");
     *R = b->R;
@@ -2584,110 +2589,6 @@ RTMI_EXPORT int rtmi_metric(rtmi_batch* b, int kind, double* out) {
                 "rtmi_metric: the exit-angle metric needs the full trajectory (record_stride 1, rec_rows >= max_size)");
     if (kind == RTMI_METRIC_PX_CV) ARG_TRY(b->p.record_stride >= 1, "rtmi_metric: the p_x metric needs recorded rows");
     return read_per_ray("rtmi_metric", b, kind == RTMI_METRIC_SNELL_ERROR ? kMetricSnell : kind == RTMI_METRIC_CLOSURE ? kMetricClosure : kMetricPxCv, 1, out);
-}
-
-// ------------------------------------------------------------------ isochrones
-// Per-ray PCHIP interpolation of (x, y, theta) at fixed traveltimes -- the first stage of the reference's
-// wavefront extraction (RT_bench.py:987-1003: scipy PchipInterpolator(t_ray, v_ray) evaluated at travel_time).
-// scipy's algorithm restated: shape-preserving derivative estimates (Fritsch-Butland weighted harmonic mean,
-// three-point end formula with the two sign guards), cubic Hermite in the power basis of (t - T_j).
-namespace {
-__device__ __forceinline__ double sgn_(double v) { return (v > 0) - (v < 0); }
-__device__ __forceinline__ double pchip_edge(double h0, double h1, double m0, double m1) {
-    double d = ((2 * h0 + h1) * m0 - h0 * m1) / (h0 + h1);
-    if (sgn_(d) != sgn_(m0)) d = 0;
-    else if (sgn_(m0) != sgn_(m1) && fabs(d) > 3 * fabs(m0)) d = 3 * m0;
-    return d;
-}
-template <typename T> struct Column {   // s_ray[:, q, k]
-    const T* base; size_t pitch;
-    __device__ __forceinline__ double operator()(long row) const { return (double)base[(size_t)row * pitch]; }
-};
-// derivative estimate at point j of an n-point (n >= 3) data set
-template <typename T> __device__ __forceinline__ double pchip_deriv(const Column<T>& tt, const Column<T>& yy, long j, long n) {
-    if (j == 0) {
-        const double h0 = tt(1) - tt(0), h1 = tt(2) - tt(1);
-        return pchip_edge(h0, h1, (yy(1) - yy(0)) / h0, (yy(2) - yy(1)) / h1);
-    }
-    if (j == n - 1) {
-        const double h0 = tt(n - 1) - tt(n - 2), h1 = tt(n - 2) - tt(n - 3);
-        return pchip_edge(h0, h1, (yy(n - 1) - yy(n - 2)) / h0, (yy(n - 2) - yy(n - 3)) / h1);
-    }
-    const double ha = tt(j) - tt(j - 1), hb = tt(j + 1) - tt(j);
-    const double ma = (yy(j) - yy(j - 1)) / ha, mb = (yy(j + 1) - yy(j)) / hb;
-    if (sgn_(ma) != sgn_(mb) || ma == 0 || mb == 0) return 0;
-    const double w1 = 2 * hb + ha, w2 = hb + 2 * ha;
-    return 1.0 / ((w1 / ma + w2 / mb) / (w1 + w2));
-}
-}  // namespace
-
-template <typename T> __global__ void k_isochrone(BatchDev<T> a, int ntimes, const double* times, double* out) {
-    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.R) return;
-    // rows 0..last_i of this ray (:993); a batch created with rec_rows < max_size holds only the first rec_rows of them
-    const long n = a.istep[k] + 1 < a.rec_rows ? a.istep[k] + 1 : a.rec_rows;
-    const size_t pitch = (size_t)6 * a.R;
-    const Column<T> tt{a.s_ray + (size_t)4 * a.R + k, pitch};
-    const int qsel[3] = {0, 1, 5};                      // x, y, theta (:993)
-    for (int it = 0; it < ntimes; it++) {
-        const double t = times[it];
-        double res[3] = {NAN, NAN, NAN};
-        if (n >= 2 && tt(n - 1) >= t && t >= tt(0)) {   // np.max(t_ray) >= travel_time (:997)
-            long lo = 0, hi = n - 1;                     // T[lo] <= t < T[hi] (right end closed)
-            while (hi - lo > 1) {
-                const long mid = (lo + hi) >> 1;
-                if (tt(mid) <= t) lo = mid; else hi = mid;
-            }
-            const double dx = tt(lo + 1) - tt(lo), s = t - tt(lo);
-            for (int q = 0; q < 3; q++) {
-                const Column<T> yy{a.s_ray + (size_t)qsel[q] * a.R + k, pitch};
-                const double y0 = yy(lo), y1 = yy(lo + 1), slope = (y1 - y0) / dx;
-                double d0, d1;
-                if (n == 2) { d0 = d1 = slope; }
-                else { d0 = pchip_deriv(tt, yy, lo, n); d1 = pchip_deriv(tt, yy, lo + 1, n); }
-                const double tq = (d0 + d1 - 2 * slope) / dx;           // CubicHermiteSpline coefficients
-                const double c0 = tq / dx, c1 = (slope - d0) / dx - tq;
-                res[q] = y0 + d0 * s + c1 * (s * s) + c0 * (s * s * s);
-            }
-        }
-        for (int q = 0; q < 3; q++) out[((size_t)it * 3 + q) * a.R + out_index(a, k)] = res[q];
-    }
-}
-
-// the per-ray isochrone stage with its result left on the device (shared with wavefront.hip)
-int rtmi_internal_isochrones_device(rtmi_batch* b, int32_t ntimes, const double* times, double** d_out, long* R, void** stream) {
-    ARG_TRY(b && times && d_out, "rtmi_isochrones: null");
-    ARG_TRY(ntimes > 0 && ntimes <= 4096, "rtmi_isochrones: ntimes must be in [1, 4096]");
-    ARG_TRY(b->p.record_stride == 1, "rtmi_isochrones: needs the full trajectory (record_stride 1)");
-    DEVICE_TRY(b->field, "rtmi_isochrones");
-    RETRACE_FLUSH(b);
-    const char* who = "rtmi_isochrones";
-    DevMem mem;
-    double *d = nullptr, *dt = nullptr;
-    RTMI_HIP(mem.get(&d, (size_t)ntimes * 3 * (size_t)b->R * sizeof(double)));
-    RTMI_HIP(mem.get(&dt, ntimes * sizeof(double)));
-    RTMI_HIP(hipMemcpyAsync(dt, times, ntimes * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    by_dtype(b->p.dtype, [&](auto t) {
-        hipLaunchKernelGGL(k_isochrone<decltype(t)>, dim3((unsigned)((b->R + 127) / 128)), dim3(128), 0, b->stream, batch_dev<decltype(t)>(b), (int)ntimes, dt, d);
-    });
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(hipStreamSynchronize(b->stream));
-    mem.release(d);
-    *d_out = d;
-    if (R) *R = (long)b->R;
-    if (stream) *stream = (void*)b->stream;
-    return RTMI_OK;
-}
-
-RTMI_EXPORT int rtmi_isochrones(rtmi_batch* b, int32_t ntimes, const double* times, double* out) {
-    ARG_TRY(out, "rtmi_isochrones: null");
-    const char* who = "rtmi_isochrones";
-    double* d = nullptr;
-    RTMI_RC(rtmi_internal_isochrones_device(b, ntimes, times, &d, nullptr, nullptr));
-    DevMem mem;
-    mem.adopt(d);
-    RTMI_HIP(hipMemcpy(out, d, (size_t)ntimes * 3 * (size_t)b->R * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
 }
 
 RTMI_EXPORT int rtmi_batch_view(rtmi_batch* b, rtmi_device_view* v) {

@@ -1,7 +1,7 @@
 // rtmi_host.h -- the host-side support layer of every translation unit: the ways out of an entry, one call's device memory and
 // event marks, grid sizing, and the checks every entry that reads a batch's recorded rows makes.  A new post-trace unit starts
-// from this header (DESIGN.md sections 15 and 16).  Everything is in an anonymous namespace: each unit gets its own copy, as with
-// rt_crossing.h.
+// from this header and from rt_rows.h, the record as its kernels read it (DESIGN.md sections 15 to 17).  Everything is in an
+// anonymous namespace: each unit gets its own copy, as with rt_crossing.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,8 +55,6 @@ struct DevMem {
         if (e == hipSuccess) { p.push_back(v); *out = (T*)v; }
         return e;
     }
-    void adopt(void* v) { p.push_back(v); }      // a buffer another unit allocated for this call
-    void release(void* v) { p.erase(std::find(p.begin(), p.end(), v)); }     // ... and one this call hands to its caller
     ~DevMem() { for (void* v : p) (void)hipFree(v); }
 };
 
@@ -108,6 +106,7 @@ enum : unsigned {
     kRecIsotropic = 1,      // op1..op9 with gamma 1 only
     kRecPoly = 2,           // the field's polynomial view (Recorded::poly)
     kRecFromLaunch = 4,     // every ray's rows must run from its launch point: a batch with rows from rtmi_batch_set_state is refused
+    kRecOnDevice = 8,       // the calling thread's current device must be the field's
 };
 // ... and what it gets
 struct Recorded {
@@ -117,7 +116,8 @@ struct Recorded {
     rtmi_internal_poly poly;
 };
 // The checks on the host, in this order -- record_stride 1, isotropic, from the launch point, a whole number of fans (fan_size 0:
-// not asked) -- then the view, which drains the rays handed over to the re-trace of critical rays, with the batch's stream idle.
+// not asked), the field's device -- then the view, which drains the rays handed over to the re-trace of critical rays, with the
+// batch's stream idle.
 int recorded(const char* who, rtmi_batch* b, unsigned needs, int64_t fan_size, Recorded* r) {
     int from_state = 0;
     RTMI_RC(rtmi_internal_batch_info(b, &r->f, &r->p, &from_state));
@@ -135,6 +135,7 @@ int recorded(const char* who, rtmi_batch* b, unsigned needs, int64_t fan_size, R
         RTMI_ARG(nrays % fan_size == 0, "the batch's ray count is not a multiple of fan_size");
     }
     if (needs & kRecPoly) RTMI_RC(rtmi_internal_field_poly(r->f, &r->poly));
+    if (needs & kRecOnDevice) RTMI_RC(rtmi_internal_on_device(who, r->f));
     RTMI_RC(rtmi_batch_view(b, &r->v));
     RTMI_RC(rtmi_sync(b));
     return RTMI_OK;

@@ -6,9 +6,8 @@
 
 // sets rtmi_last_error() and returns `code`
 int rtmi_internal_fail(int code, const char* msg);
-// rtmi_isochrones with the result left on the device: *d_out = [ntimes][3][R] fp64 (caller hipFree's it), in the CALLER's
-// ray order; *R and *stream (a hipStream_t) describe the batch.  The stream is synchronised when this returns.
-int rtmi_internal_isochrones_device(rtmi_batch* b, int32_t ntimes, const double* times, double** d_out, long* R, void** stream);
+// RTMI_ERR_ARG, reported under `who`, unless the calling thread's current device is the field's.
+int rtmi_internal_on_device(const char* who, const rtmi_field* f);
 // what 0: d_ray [3][R] (rtmi_read_d_ray's content), 1: final [9][R] (rtmi_read_final's), fp64, the caller's ray order, written to
 // dst -- DEVICE memory on the batch's device -- by a kernel enqueued on `stream` (a hipStream_t) after the batch's own stream
 // has been synchronised.  For shard.hip's device-to-device read-back.

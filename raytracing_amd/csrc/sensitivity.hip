@@ -22,6 +22,7 @@
 #include "rt_crossing.h"
 #include "rt_fix128.h"
 #include "rt_polytab.h"
+#include "rt_rows.h"
 #include "rtmi_host.h"
 
 namespace {
@@ -57,11 +58,7 @@ __device__ __forceinline__ double coef_of(double th, double gamma) {
 }
 
 struct Args {
-    const void* s_ray;            // [rec_rows][6][R] of the batch's dtype
-    const int32_t* istep;         // [R] last written row
-    const int32_t* perm;          // [R] or NULL: slot k holds the caller's ray perm[k]
     const double* dist;           // [R] dist_sim (slot order): the bound of the fixed-point scale
-    long R, rec_rows;
     Axes F;
     Line L;
     int has_line, kmax, aniso;
@@ -72,14 +69,14 @@ struct Args {
 // One lane per ray.  dT_i = dT_{i-1} + (L_i (ds_{i-1} + ds_i)) 0.5, ds = coef sum(phi dZ); at a crossing (the rule and tau* of
 // rtmi_crossings) dT* = ((dT_{i-1} h00 + (L ds_{i-1}) h10) + dT_i h01) + (L ds_i) h11, rtmi_crossings' herm with dT for T.
 template <typename T>
-__global__ void k_perturb(Args A, const double* dZ, int32_t* count, double* dT_line, double* dT_end) {
+__global__ void k_perturb(Rows<T> rec, Args A, const double* dZ, int32_t* count, double* dT_line, double* dT_end) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= A.R) return;
-    const long R = A.R;
-    const long o = A.perm ? (long)A.perm[k] : k;
-    const size_t P = (size_t)6 * R;
-    const T* col = reinterpret_cast<const T*>(A.s_ray) + k;
-    const long last = A.istep[k];
+    if (k >= rec.R) return;
+    const long R = rec.R;
+    const long o = rec.caller(k);
+    const size_t P = rec.pitch();
+    const T* col = rec.row(0, k);
+    const long last = rec.last(k);
     const Line L = A.L;
     const int qx = A.F.qx;
     auto ds_at = [&](double x, double y, double th) {
@@ -90,24 +87,24 @@ __global__ void k_perturb(Args A, const double* dZ, int32_t* count, double* dT_l
         return A.aniso ? coef_of(th, A.gamma) * s : s;
     };
     int n = 0;
-    if (last >= A.rec_rows) {
+    if (last >= rec.rec_rows) {
         n = -1;
         dT_end[o] = NAN;
     } else {
-        double x0 = (double)col[0], y0 = (double)col[R];
-        double th0 = A.aniso ? (double)col[5 * R] : 0.0;
+        double x0 = (double)col[COL_X * R], y0 = (double)col[COL_Y * R];
+        double th0 = A.aniso ? (double)col[COL_TH * R] : 0.0;
         double s0 = ds_at(x0, y0, th0);
         double f0 = (L.a * x0 + L.b * y0) - L.c;
         double dT = 0.0;
         // the next row's loads go out a step ahead
         double xn = 0.0, yn = 0.0, tn = 0.0;
-        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; if (A.aniso) tn = (double)col[P + 5 * R]; }
+        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + COL_Y * R]; if (A.aniso) tn = (double)col[P + COL_TH * R]; }
         for (long i = 1; i <= last; i++) {
             const double x1 = xn, y1 = yn, th1 = tn;
             if (i < last) {
                 const T* r = col + (size_t)(i + 1) * P;
-                xn = (double)r[0]; yn = (double)r[R];
-                if (A.aniso) tn = (double)r[5 * R];
+                xn = (double)r[COL_X * R]; yn = (double)r[COL_Y * R];
+                if (A.aniso) tn = (double)r[COL_TH * R];
             }
             const double s1 = ds_at(x1, y1, th1);
             const double dx = x1 - x0, dy = y1 - y0;
@@ -119,7 +116,7 @@ __global__ void k_perturb(Args A, const double* dZ, int32_t* count, double* dT_l
                     if (n < A.kmax) {
                         const T* r0 = col + (size_t)(i - 1) * P;
                         const T* r1 = col + (size_t)i * P;
-                        const double ta = (double)r0[5 * R], tb = (double)r1[5 * R];
+                        const double ta = (double)r0[COL_TH * R], tb = (double)r1[COL_TH * R];
                         const double d0 = len * (L.a * cos_g(ta) + L.b * sin_g(ta)), d1 = len * (L.a * cos_g(tb) + L.b * sin_g(tb));
                         const Basis h = basis(cross_tau(f0, d0, f1, d1));
                         dT_line[(size_t)n * R + o] = herm(h, dT, len * s0, dTn, len * s1);
@@ -142,13 +139,14 @@ __global__ void k_perturb(Args A, const double* dZ, int32_t* count, double* dT_l
 __device__ __forceinline__ double w0(double w) { return w == w ? w : 0.0; }       // NaN weights count as 0
 
 // The crossings of a ray's rows with the line (rtmi_crossings' rule), counted
-template <typename T> __device__ __forceinline__ int count_crossings(const T* col, long R, long last, const Line& L) {
-    const size_t P = (size_t)6 * R;
-    double f0 = (L.a * (double)col[0] + L.b * (double)col[R]) - L.c;
+template <typename T> __device__ __forceinline__ int count_crossings(const Rows<T>& rec, long k, long last, const Line& L) {
+    const long R = rec.R;
+    const T* col = rec.row(0, k);
+    double f0 = (L.a * (double)col[COL_X * R] + L.b * (double)col[COL_Y * R]) - L.c;
     int n = 0;
     for (long i = 1; i <= last; i++) {
-        const T* r = col + (size_t)i * P;
-        const double f1 = (L.a * (double)r[0] + L.b * (double)r[R]) - L.c;
+        const T* r = col + (size_t)i * rec.pitch();
+        const double f1 = (L.a * (double)r[COL_X * R] + L.b * (double)r[COL_Y * R]) - L.c;
         n += crosses(f0, f1) ? 1 : 0;
         f0 = f1;
     }
@@ -157,14 +155,15 @@ template <typename T> __device__ __forceinline__ int count_crossings(const T* co
 
 // Per ray: a bound on any partial sum its lane can flush, (|w_end| + sum_c |w_c|) 2 len coef_max (a row's weights total at most
 // 1.15 len coef_max per unit of weight: DESIGN.md 12), and its maximum over rays (non-negative doubles order as their bits).
-__global__ void k_bound(Args A, const double* w_line, const double* w_end, double coef_max, unsigned long long* maxb) {
+template <typename T>
+__global__ void k_bound(Rows<T> rec, Args A, const double* w_line, const double* w_end, double coef_max, unsigned long long* maxb) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= A.R) return;
-    const long o = A.perm ? (long)A.perm[k] : k;
-    if (A.istep[k] >= A.rec_rows) return;
+    if (k >= rec.R) return;
+    const long o = rec.caller(k);
+    if (rec.last(k) >= rec.rec_rows) return;
     double w = w_end ? fabs(w0(w_end[o])) : 0.0;
     if (w_line)
-        for (int c = 0; c < A.kmax; c++) w += fabs(w0(w_line[(size_t)c * A.R + o]));
+        for (int c = 0; c < A.kmax; c++) w += fabs(w0(w_line[(size_t)c * rec.R + o]));
     const double b = w * (2.0 * A.dist[k]) * coef_max;
     if (b > 0.0) atomicMax(maxb, (unsigned long long)__double_as_longlong(b));
 }
@@ -178,22 +177,22 @@ __global__ void k_fill(unsigned long long* p, size_t n, unsigned long long v) {
 // step i; a crossing c < min(count, kmax) on step i gives row i-1 w_c L_i (0.5 h01 + h10) and row i w_c L_i (0.5 h01 + h11).
 // A row's weight times its coef, times phi, goes into the lane's partial sums of its cell.
 template <typename T>
-__global__ void k_backproject(Args A, const double* w_line, const double* w_end, const unsigned long long* maxb,
+__global__ void k_backproject(Rows<T> rec, Args A, const double* w_line, const double* w_end, const unsigned long long* maxb,
                               unsigned long long* lo, unsigned long long* hi, unsigned long long* natomics) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in = k < A.R;
-    const long R = A.R;
-    const long o = in ? (A.perm ? (long)A.perm[k] : k) : 0;
-    const size_t P = (size_t)6 * R;
-    const T* col = reinterpret_cast<const T*>(A.s_ray) + (in ? k : 0);
-    long last = in ? (long)A.istep[k] : -1;
-    if (last >= A.rec_rows) last = -1;                      // past the record: no reported traveltime, no weight
+    const bool in = k < rec.R;
+    const long R = rec.R;
+    const long o = in ? rec.caller(k) : 0;
+    const size_t P = rec.pitch();
+    const T* col = rec.row(0, in ? k : 0);
+    long last = in ? rec.last(k) : -1;
+    if (last >= rec.rec_rows) last = -1;                      // past the record: no reported traveltime, no weight
     const Line L = A.L;
     const int qx = A.F.qx;
     const int e = rt::fix_exponent(__longlong_as_double((long long)*maxb));    // quantum 2^e: every partial is below 2^57 quanta
     // crossings that carry a weight: the first min(count, kmax)
     const bool line = A.has_line && w_line != nullptr;
-    const int K = (line && last >= 0) ? min(count_crossings(col, R, last, L), A.kmax) : 0;
+    const int K = (line && last >= 0) ? min(count_crossings(rec, in ? k : 0, last, L), A.kmax) : 0;
     const double we = (w_end && last >= 0) ? w0(w_end[o]) : 0.0;
     auto wc = [&](int c) { return w0(w_line[(size_t)c * R + o]); };
     auto weight_after = [&](int c0) {                       // w_end + the weights of crossings c0 .. K-1
@@ -258,10 +257,10 @@ __global__ void k_backproject(Args A, const double* w_line, const double* w_end,
     const bool live = last >= 0 && (we != 0.0 || K > 0);
     double x0 = 0.0, y0 = 0.0, th0 = 0.0, f0 = 0.0, xn = 0.0, yn = 0.0, tn = 0.0;
     if (live) {
-        x0 = (double)col[0]; y0 = (double)col[R];
-        if (A.aniso) th0 = (double)col[5 * R];
+        x0 = (double)col[COL_X * R]; y0 = (double)col[COL_Y * R];
+        if (A.aniso) th0 = (double)col[COL_TH * R];
         f0 = (L.a * x0 + L.b * y0) - L.c;
-        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + R]; if (A.aniso) tn = (double)col[P + 5 * R]; }
+        if (last >= 1) { xn = (double)col[P]; yn = (double)col[P + COL_Y * R]; if (A.aniso) tn = (double)col[P + COL_TH * R]; }
     }
     const long end = live ? last : 0;
     double aprev = 0.0;                                     // row i-1's weight so far
@@ -274,8 +273,8 @@ __global__ void k_backproject(Args A, const double* w_line, const double* w_end,
             x1 = xn; y1 = yn; th1 = tn;
             if (i < end) {
                 const T* r = col + (size_t)(i + 1) * P;
-                xn = (double)r[0]; yn = (double)r[R];
-                if (A.aniso) tn = (double)r[5 * R];
+                xn = (double)r[COL_X * R]; yn = (double)r[COL_Y * R];
+                if (A.aniso) tn = (double)r[COL_TH * R];
             }
             const double dx = x1 - x0, dy = y1 - y0;
             const double len = sqrt(dx * dx + dy * dy);
@@ -285,7 +284,7 @@ __global__ void k_backproject(Args A, const double* w_line, const double* w_end,
                     if (n < K) {
                         const T* r0 = col + (size_t)(i - 1) * P;
                         const T* r1 = col + (size_t)i * P;
-                        const double ta = (double)r0[5 * R], tb = (double)r1[5 * R];
+                        const double ta = (double)r0[COL_TH * R], tb = (double)r1[COL_TH * R];
                         const double d0 = len * (L.a * cos_g(ta) + L.b * sin_g(ta)), d1 = len * (L.a * cos_g(tb) + L.b * sin_g(tb));
                         const Basis h = basis(cross_tau(f0, d0, f1, d1));
                         const double w = wc(n);
@@ -320,8 +319,7 @@ int prepare(rtmi_batch* b, const double* line, int32_t kmax, const char* who, Ar
     *v = r.v;
     Line L{0.0, 0.0, 0.0};
     if (line) (void)make_line(line, &L);
-    *A = Args{v->s_ray, v->istep, v->perm, v->dist_sim, (long)v->R, (long)v->rec_rows,
-              Axes{r.poly.ax, r.poly.bx, r.poly.inv_hx, r.poly.ay, r.poly.by, r.poly.inv_hy, qx, qy}, L, line ? 1 : 0, line ? kmax : 0,
+    *A = Args{v->dist_sim, Axes{r.poly.ax, r.poly.bx, r.poly.inv_hx, r.poly.ay, r.poly.by, r.poly.inv_hy, qx, qy}, L, line ? 1 : 0, line ? kmax : 0,
               r.p.method >= 10 ? 1 : 0, r.p.gamma};
     return RTMI_OK;
 }
@@ -360,8 +358,7 @@ RTMI_EXPORT int rtmi_traveltime_perturb(rtmi_batch* b, const double line[3], int
     const dim3 g = blocks((long)R), blk(256);
     RTMI_HIP(ev.mark(0));
     if (R) {
-        if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_perturb<double>, g, blk, 0, nullptr, A, dz, dc, dl, de);
-        else hipLaunchKernelGGL(k_perturb<float>, g, blk, 0, nullptr, A, dz, dc, dl, de);
+        by_dtype(v.dtype, [&](auto t) { hipLaunchKernelGGL(k_perturb<decltype(t)>, g, blk, 0, nullptr, rows_of<decltype(t)>(v), A, dz, dc, dl, de); });
         RTMI_HIP(hipGetLastError());
     }
     RTMI_HIP(ev.mark(1));
@@ -410,10 +407,10 @@ RTMI_EXPORT int rtmi_traveltime_backproject(rtmi_batch* b, const double line[3],
     const dim3 gr = blocks((long)R), blk(256);
     RTMI_HIP(ev.mark(0));
     if (R) {
-        hipLaunchKernelGGL(k_bound, gr, blk, 0, nullptr, A, dwl, dwe, coef_max, misc);
-        RTMI_HIP(hipGetLastError());
-        if (v.dtype == RTMI_F64) hipLaunchKernelGGL(k_backproject<double>, gr, blk, 0, nullptr, A, dwl, dwe, misc, acc, acc + nz, misc + 1);
-        else hipLaunchKernelGGL(k_backproject<float>, gr, blk, 0, nullptr, A, dwl, dwe, misc, acc, acc + nz, misc + 1);
+        by_dtype(v.dtype, [&](auto t) {
+            hipLaunchKernelGGL(k_bound<decltype(t)>, gr, blk, 0, nullptr, rows_of<decltype(t)>(v), A, dwl, dwe, coef_max, misc);
+            hipLaunchKernelGGL(k_backproject<decltype(t)>, gr, blk, 0, nullptr, rows_of<decltype(t)>(v), A, dwl, dwe, misc, acc, acc + nz, misc + 1);
+        });
         RTMI_HIP(hipGetLastError());
     }
     RTMI_HIP(ev.mark(1));

@@ -439,10 +439,9 @@ RTMI_EXPORT int rtmi_shard_gather_rows(rtmi_shard* s, int64_t row0, int64_t nrow
         r = rtmi_sync(s->batches[i]);                      // the rows are complete (rtmi_run is synchronous; rtmi_step is not)
         if (r) return r;
         const dim3 g((unsigned)((v.R + 255) / 256), (unsigned)(nvec < 1024 ? nvec : 1024)), blk(256);
-        if (v.dtype == RTMI_F64)
-            hipLaunchKernelGGL(k_rows_pack<double>, g, blk, 0, s->streams[i], (const double*)v.s_ray, v.perm, (long)v.R, (long)row0, (long)every, nvec, dst);
-        else
-            hipLaunchKernelGGL(k_rows_pack<float>, g, blk, 0, s->streams[i], (const float*)v.s_ray, v.perm, (long)v.R, (long)row0, (long)every, nvec, dst);
+        by_dtype(v.dtype, [&](auto t) {
+            hipLaunchKernelGGL(k_rows_pack<decltype(t)>, g, blk, 0, s->streams[i], (const decltype(t)*)v.s_ray, v.perm, (long)v.R, (long)row0, (long)every, nvec, dst);
+        });
         HIP_TRY(hipGetLastError());
         return RTMI_OK;
     });

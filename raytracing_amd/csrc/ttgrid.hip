@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_rows.h"
 #include "rtmi_host.h"
 
 namespace {
@@ -41,14 +42,12 @@ struct Grid {
     double inv_gdx, inv_gdy;    // for the cell pre-test only (cell_has_node); every node test is exact
 };
 
+// what the passes read beside the rows, and the fans: S sources of M rays each
 struct Rec {
-    const void* s_ray;          // [rec_rows][6][R] of T: x, y, p_x, p_y, T, theta
-    const int32_t* istep;       // [R] last written row (slot order)
     const int32_t* slot;        // [R] or NULL: slot of the caller's ray o (the inverse of rtmi_device_view.perm)
     const double* theta0;       // [R] caller order, or NULL: row 0's theta
     const double* row_J;        // [rec_rows][R] slot order, or NULL (no amplitude)
     const int32_t* row_kmah;
-    long R, rec_rows;
     int M, S;
 };
 
@@ -62,9 +61,9 @@ struct Nodes {
 struct V2 { double x, y; };
 struct Corner { double x, y, t, th; };
 
-template <typename T> __device__ __forceinline__ Corner corner(const Rec& r, long k, long i) {
-    const T* p = reinterpret_cast<const T*>(r.s_ray) + (size_t)i * 6 * r.R + k;
-    return Corner{(double)p[0], (double)p[r.R], (double)p[4 * r.R], (double)p[5 * r.R]};
+template <typename T> __device__ __forceinline__ Corner corner(const Rows<T>& rec, long k, long i) {
+    const T* p = rec.row(i, k);
+    return Corner{(double)p[COL_X * rec.R], (double)p[COL_Y * rec.R], (double)p[COL_T * rec.R], (double)p[COL_TH * rec.R]};
 }
 
 __device__ __forceinline__ double wrap(double d) { return d - kTwoPi * rint(d / kTwoPi); }
@@ -151,10 +150,6 @@ __device__ __forceinline__ bool cell_has_node(const Grid& g, const V2 q[4]) {
     return axis_has_node(yl, yh, g.gy0, g.inv_gdy, g.ny);
 }
 
-__device__ __forceinline__ long last_row(const Rec& r, long k) {
-    const long l = r.istep[k];
-    return l < r.rec_rows - 1 ? l : r.rec_rows - 1;
-}
 __device__ __forceinline__ long slot_of(const Rec& r, long o) { return r.slot ? (long)r.slot[o] : o; }
 
 __device__ __forceinline__ void block_add(unsigned long long* acc, int q, unsigned long long v) {
@@ -162,7 +157,7 @@ __device__ __forceinline__ void block_add(unsigned long long* acc, int q, unsign
 }
 
 // Passes 1 and 2: one lane per (source, ray pair).  pass 1: T minimum and count; pass 2: the key of the winner.
-template <typename T> __global__ void k_raster(Grid g, Rec r, Nodes nd, int pass) {
+template <typename T> __global__ void k_raster(Grid g, Rows<T> rec, Rec r, Nodes nd, int pass) {
     __shared__ unsigned long long acc[C_N];
     if (threadIdx.x < C_N) acc[threadIdx.x] = 0ull;
     __syncthreads();
@@ -173,12 +168,12 @@ template <typename T> __global__ void k_raster(Grid g, Rec r, Nodes nd, int pass
         const long s = lane / pairs, m = lane - s * pairs;
         const long o = s * r.M + m;
         const long k0 = slot_of(r, o), k1 = slot_of(r, o + 1);
-        const long l0 = last_row(r, k0), l1 = last_row(r, k1);
+        const long l0 = rec.last_recorded(k0), l1 = rec.last_recorded(k1);
         const long L = l0 < l1 ? l0 : l1;
         const size_t base = (size_t)s * g.ny * g.nx;
-        Corner A = corner<T>(r, k0, 0), B = corner<T>(r, k1, 0);
+        Corner A = corner(rec, k0, 0), B = corner(rec, k1, 0);
         for (long i = 0; i < L; i++) {
-            const Corner C = corner<T>(r, k0, i + 1), D = corner<T>(r, k1, i + 1);
+            const Corner C = corner(rec, k0, i + 1), D = corner(rec, k1, i + 1);
             n_cells++;
             if (!cell_ok(g, A, B, C, D)) {
                 n_skip++;
@@ -192,7 +187,7 @@ template <typename T> __global__ void k_raster(Grid g, Rec r, Nodes nd, int pass
                     n_tri++;
                     n_fold += t.folded;
                     if (!nodes) continue;
-                    const unsigned long long key = ((unsigned long long)(m * r.rec_rows + i) << 1) | (unsigned long long)half;
+                    const unsigned long long key = ((unsigned long long)(m * rec.rec_rows + i) << 1) | (unsigned long long)half;
                     int x0, x1, y0, y1;
                     node_range(t.xmin, t.xmax, g.gx0, g.gdx, g.nx, x0, x1);
                     node_range(t.ymin, t.ymax, g.gy0, g.gdy, g.ny, y0, y1);
@@ -233,7 +228,7 @@ template <typename T> __global__ void k_raster(Grid g, Rec r, Nodes nd, int pass
 }
 
 // Pass 3: one lane per node.  out[s][col][ny][nx]; NaN where no triangle covers the node.
-template <typename T> __global__ void k_columns(Grid g, Rec r, Nodes nd, double* out, int ncols) {
+template <typename T> __global__ void k_columns(Grid g, Rows<T> rec, Rec r, Nodes nd, double* out, int ncols) {
     const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long per = (long)g.nx * g.ny;
     if (id >= (long)r.S * per) return;
@@ -246,12 +241,12 @@ template <typename T> __global__ void k_columns(Grid g, Rec r, Nodes nd, double*
         return;
     }
     const int half = (int)(key & 1ull);
-    const long m = (long)((key >> 1) / (unsigned long long)r.rec_rows), i = (long)((key >> 1) - (unsigned long long)m * r.rec_rows);
+    const long m = (long)((key >> 1) / (unsigned long long)rec.rec_rows), i = (long)((key >> 1) - (unsigned long long)m * rec.rec_rows);
     const long oa = s * r.M + m;
     const long k[4] = {slot_of(r, oa), slot_of(r, oa + 1), slot_of(r, oa), slot_of(r, oa + 1)};
     const long row[4] = {i, i, i + 1, i + 1};
     Corner c4[4];
-    for (int q = 0; q < 4; q++) c4[q] = corner<T>(r, k[q], row[q]);
+    for (int q = 0; q < 4; q++) c4[q] = corner(rec, k[q], row[q]);
     const V2 q4[4] = {{c4[0].x, c4[0].y}, {c4[1].x, c4[1].y}, {c4[2].x, c4[2].y}, {c4[3].x, c4[3].y}};
     Tri t;
     tri_setup(q4, half, t);
@@ -260,7 +255,7 @@ template <typename T> __global__ void k_columns(Grid g, Rec r, Nodes nd, double*
     const int a = t.c[0], b = t.c[1], c = t.c[2];
     double th0[4];
     for (int q = 0; q < 4; q++)
-        th0[q] = r.theta0 ? r.theta0[oa + (q & 1)] : (double)reinterpret_cast<const T*>(r.s_ray)[5 * r.R + k[q]];
+        th0[q] = r.theta0 ? r.theta0[oa + (q & 1)] : (double)rec.row(0, k[q])[COL_TH * rec.R];
     double thu[4];
     for (int q = 0; q < 4; q++) thu[q] = c4[0].th + wrap(c4[q].th - c4[0].th);
     const double fr[4] = {0.0, 1.0, 0.0, 1.0}, fs[4] = {0.0, 0.0, 1.0, 1.0};
@@ -273,10 +268,10 @@ template <typename T> __global__ void k_columns(Grid g, Rec r, Nodes nd, double*
         double J[4], n[4];
         int km[4];
         for (int q = 0; q < 4; q++) {
-            J[q] = r.row_J[(size_t)row[q] * r.R + k[q]];
-            km[q] = r.row_kmah[(size_t)row[q] * r.R + k[q]];
-            const T* p = reinterpret_cast<const T*>(r.s_ray) + (size_t)row[q] * 6 * r.R + k[q];
-            const double px = (double)p[2 * r.R], py = (double)p[3 * r.R];
+            J[q] = r.row_J[(size_t)row[q] * rec.R + k[q]];
+            km[q] = r.row_kmah[(size_t)row[q] * rec.R + k[q]];
+            const T* p = rec.row(row[q], k[q]);
+            const double px = (double)p[COL_PX * rec.R], py = (double)p[COL_PY * rec.R];
             n[q] = sqrt(px * px + py * py);
         }
         const double Jn = interp(w, J[a], J[b], J[c]);
@@ -302,8 +297,9 @@ int grid_of(const rtmi_grid_params* gp, const char* who, Grid* g) {
     return RTMI_OK;
 }
 
-// The three passes on a record already on the device (r's pointers), results to the host.
-int run_grid(const char* who, int dtype, const Grid& g, Rec r, int32_t* count, double* out, rtmi_grid_stats* st) {
+// The three passes on a record already on the device, results to the host.
+template <typename T> int run_grid(const char* who, const Grid& g, const Rows<T>& rec, const Rec& r, int32_t* count, double* out,
+                                   rtmi_grid_stats* st) {
     const size_t per = (size_t)g.nx * g.ny, nodes = per * (size_t)r.S;
     const int ncols = r.row_J ? kColsA : kColsT;
     DevMem mem;
@@ -325,14 +321,12 @@ int run_grid(const char* who, int dtype, const Grid& g, Rec r, int32_t* count, d
     RTMI_HIP(ev.mark(0));
     for (int pass = 1; pass <= 2; pass++) {
         if (lanes > 0) {
-            if (dtype == RTMI_F64) hipLaunchKernelGGL(k_raster<double>, gl, blk, 0, nullptr, g, r, nd, pass);
-            else hipLaunchKernelGGL(k_raster<float>, gl, blk, 0, nullptr, g, r, nd, pass);
+            hipLaunchKernelGGL(k_raster<T>, gl, blk, 0, nullptr, g, rec, r, nd, pass);
             RTMI_HIP(hipGetLastError());
         }
         RTMI_HIP(ev.mark(pass));
     }
-    if (dtype == RTMI_F64) hipLaunchKernelGGL(k_columns<double>, gn, blk, 0, nullptr, g, r, nd, dout, ncols);
-    else hipLaunchKernelGGL(k_columns<float>, gn, blk, 0, nullptr, g, r, nd, dout, ncols);
+    hipLaunchKernelGGL(k_columns<T>, gn, blk, 0, nullptr, g, rec, r, nd, dout, ncols);
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(ev.mark(3));
     RTMI_HIP(ev.wait(3));
@@ -381,8 +375,8 @@ RTMI_EXPORT int rtmi_first_arrival_grid(rtmi_batch* b, int32_t fan_size, const r
         RTMI_HIP(hipMemset(rk, 0xff, cells * sizeof(int32_t)));
         RTMI_RC(rtmi_internal_paraxial_rows(who, b, rj, rk));
     }
-    const Rec r{v.s_ray, v.istep, slot, nullptr, rj, rk, (long)v.R, (long)v.rec_rows, (int)fan_size, (int)(v.R / fan_size)};
-    return run_grid(who, v.dtype, g, r, count, out, st);
+    const Rec r{slot, nullptr, rj, rk, (int)fan_size, (int)(v.R / fan_size)};
+    return by_dtype(v.dtype, [&](auto t) { return run_grid(who, g, rows_of<decltype(t)>(v), r, count, out, st); });
 }
 
 RTMI_EXPORT int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, const double* x, const double* y, const double* T,
@@ -412,6 +406,6 @@ RTMI_EXPORT int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, 
     RTMI_HIP(hipMemcpy(drec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
     RTMI_HIP(hipMemcpy(dth0, theta0, (size_t)R * sizeof(double), hipMemcpyHostToDevice));
     RTMI_HIP(hipMemcpy(dlast, last, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice));
-    const Rec r{drec, dlast, nullptr, dth0, nullptr, nullptr, (long)R, (long)rows, (int)fan_size, (int)(R / fan_size)};
-    return run_grid(who, RTMI_F64, g, r, count, out, st);
+    const Rec r{nullptr, dth0, nullptr, nullptr, (int)fan_size, (int)(R / fan_size)};
+    return run_grid(who, g, Rows<double>{drec, dlast, nullptr, (long)R, (long)rows}, r, count, out, st);
 }

@@ -16,35 +16,35 @@
 #include <vector>
 
 #include "rt_crossing.h"
+#include "rt_rows.h"
 #include "rtmi_host.h"
 
 namespace {
 
-// One lane per ray (slot k), looping over its rows [row][6][R].  x and y are read on every row; the other columns only on a
-// step that crosses.  count[o] = crossings (-1: the trajectory reaches past rec_rows), out[kmax][6][R] = u x y T theta s.
-template <typename T>
-__global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t* perm, long R, long rec_rows, Line L, int kmax,
-                            int32_t* count, double* out) {
+// One lane per ray (slot k), looping over its rows.  x and y are read on every row; the other columns only on a step that
+// crosses.  count[o] = crossings (-1: the trajectory reaches past rec_rows), out[kmax][6][R] = u x y T theta s.
+template <typename T> __global__ void k_crossings(Rows<T> rec, Line L, int kmax, int32_t* count, double* out) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= R) return;
-    const long o = perm ? (long)perm[k] : k;
-    const size_t P = (size_t)6 * R;
-    const T* col = s_ray + k;
-    const long last = istep[k];
+    if (k >= rec.R) return;
+    const long R = rec.R;
+    const long o = rec.caller(k);
+    const size_t P = rec.pitch();
+    const T* col = rec.row(0, k);
+    const long last = rec.last(k);
     int n = 0;
-    if (last >= rec_rows) {
+    if (last >= rec.rec_rows) {
         n = -1;
     } else {
-        double x0 = (double)col[0], y0 = (double)col[R];
+        double x0 = (double)col[COL_X * R], y0 = (double)col[COL_Y * R];
         double f0 = (L.a * x0 + L.b * y0) - L.c;
         for (long i = 1; i <= last; i++) {
-            const double x1 = (double)col[(size_t)i * P], y1 = (double)col[(size_t)i * P + R];
+            const double x1 = (double)col[(size_t)i * P], y1 = (double)col[(size_t)i * P + COL_Y * R];
             const double f1 = (L.a * x1 + L.b * y1) - L.c;
             if (crosses(f0, f1)) {
                 if (n < kmax) {
                     const T* r0 = col + (size_t)(i - 1) * P;
                     const T* r1 = col + (size_t)i * P;
-                    const double th0 = (double)r0[5 * R], th1 = (double)r1[5 * R];
+                    const double th0 = (double)r0[COL_TH * R], th1 = (double)r1[COL_TH * R];
                     const double c0 = cos_g(th0), s0 = sin_g(th0), c1 = cos_g(th1), s1 = sin_g(th1);
                     const double dx = x1 - x0, dy = y1 - y0;
                     const double len = sqrt(dx * dx + dy * dy);
@@ -53,9 +53,9 @@ __global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t*
                     const double tau = cross_tau(f0, d0, f1, d1);
                     const Basis h = basis(tau), hd = dbasis(tau);
                     const double x = herm(h, x0, tx0, x1, tx1), y = herm(h, y0, ty0, y1, ty1);
-                    const double m0 = (double)r0[2 * R] * c0 + (double)r0[3 * R] * s0;     // p . (cos, sin) = dT/ds
-                    const double m1 = (double)r1[2 * R] * c1 + (double)r1[3 * R] * s1;
-                    const double tt = herm(h, (double)r0[4 * R], len * m0, (double)r1[4 * R], len * m1);
+                    const double m0 = (double)r0[COL_PX * R] * c0 + (double)r0[COL_PY * R] * s0;     // p . (cos, sin) = dT/ds
+                    const double m1 = (double)r1[COL_PX * R] * c1 + (double)r1[COL_PY * R] * s1;
+                    const double tt = herm(h, (double)r0[COL_T * R], len * m0, (double)r1[COL_T * R], len * m1);
                     const double th = atan2(herm(hd, y0, ty0, y1, ty1), herm(hd, x0, tx0, x1, tx1));
                     const double v[6] = {L.a * y - L.b * x, x, y, tt, th, (double)(i - 1) + tau};
                     for (int q = 0; q < 6; q++) out[((size_t)n * 6 + q) * R + o] = v[q];
@@ -72,13 +72,7 @@ __global__ void k_crossings(const T* s_ray, const int32_t* istep, const int32_t*
 
 // k_crossings on the rows of a view, enqueued on st
 int crossings_launch(const rtmi_device_view& v, const Line& L, int kmax, int32_t* d_count, double* d_out, hipStream_t st, const char* who) {
-    const dim3 g = blocks((long)v.R), blk(256);
-    if (v.dtype == RTMI_F64)
-        hipLaunchKernelGGL(k_crossings<double>, g, blk, 0, st, (const double*)v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L,
-                           kmax, d_count, d_out);
-    else
-        hipLaunchKernelGGL(k_crossings<float>, g, blk, 0, st, (const float*)v.s_ray, v.istep, v.perm, (long)v.R, (long)v.rec_rows, L,
-                           kmax, d_count, d_out);
+    by_dtype(v.dtype, [&](auto t) { hipLaunchKernelGGL(k_crossings<decltype(t)>, blocks((long)v.R), dim3(256), 0, st, rows_of<decltype(t)>(v), L, kmax, d_count, d_out); });
     RTMI_HIP(hipGetLastError());
     return RTMI_OK;
 }

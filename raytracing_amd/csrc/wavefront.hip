@@ -1,13 +1,12 @@
-// wavefront.hip -- the across-ray stage of the reference's wavefront extraction (RT_bench.py:1005-1026, 1043-1044) on
-// the device: per traveltime, the isochrone points of the rays that reach it (rtmi_isochrones' per-ray PCHIP stage,
-// :987-1003) are sorted by y (np.argsort, :1016), scipy's PchipInterpolator x(y) is built through them (:1020), and its
-// derivative at the points (:1021-1022), the tangent / normal angles (:1025-1026), |ray angle - normal angle| (:1032) and
-// the interpolant on nfine equally spaced y (:1043-1044) are evaluated.  One lane per point; the sort is rocPRIM's radix
-// sort through hipCUB (library code: this stage is a consumer of the hot path, not part of it).  Every traveltime of a call is
-// handled in one pass -- the reference's animation (:1066-1102) re-does the whole extraction per frame, 45 times.
-// Third-party arithmetic restated: scipy.interpolate.PchipInterpolator (scipy 1.15.3 in the build image):
-// _find_derivatives (Fritsch-Butland weighted harmonic mean, three-point end rule), CubicHermiteSpline's power-basis
-// coefficients, PPoly's evaluation (a sum of powers, lowest first) and .derivative().
+// wavefront.hip -- the reference's wavefront extraction (RT_bench.py:987-1026, 1043-1044) on the device, in two stages.
+// Per ray (rtmi_isochrones, :987-1003): scipy's PchipInterpolator(t_ray, v_ray) of x, y and theta over the recorded
+// traveltimes, evaluated at fixed traveltimes; one lane per ray.  Across rays (rtmi_wavefronts, :1005-1044): per traveltime,
+// the isochrone points of the rays that reach it are sorted by y (np.argsort, :1016), PchipInterpolator x(y) is built through
+// them (:1020), and its derivative at the points (:1021-1022), the tangent / normal angles (:1025-1026), |ray angle - normal
+// angle| (:1032) and the interpolant on nfine equally spaced y (:1043-1044) are evaluated.  One lane per point; the sort is
+// rocPRIM's radix sort through hipCUB (library code: this stage is a consumer of the hot path, not part of it).  Every
+// traveltime of a call is handled in one pass -- the reference's animation (:1066-1102) re-does the whole extraction per
+// frame, 45 times.  scipy's arithmetic is restated in rt_pchip.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -18,32 +17,39 @@
 #include <string>
 #include <vector>
 
+#include "rt_pchip.h"
+#include "rt_rows.h"
 #include "rtmi_host.h"
 
 namespace {
-__device__ __forceinline__ double sgn_(double v) { return (v > 0) - (v < 0); }
-__device__ __forceinline__ double pchip_edge(double h0, double h1, double m0, double m1) {
-    double d = ((2 * h0 + h1) * m0 - h0 * m1) / (h0 + h1);
-    if (sgn_(d) != sgn_(m0)) d = 0;
-    else if (sgn_(m0) != sgn_(m1) && fabs(d) > 3 * fabs(m0)) d = 3 * m0;
-    return d;
-}
-// scipy's derivative estimate at point j of the n-point data set (t, v), n >= 2
-__device__ double pchip_deriv(const double* t, const double* v, long j, long n) {
-    if (n == 2) return (v[1] - v[0]) / (t[1] - t[0]);
-    if (j == 0) {
-        const double h0 = t[1] - t[0], h1 = t[2] - t[1];
-        return pchip_edge(h0, h1, (v[1] - v[0]) / h0, (v[2] - v[1]) / h1);
+// The per-ray stage: x, y, theta (:993) of every ray at the traveltimes `times`, out [ntimes][3][R] in the caller's ray order;
+// NaN where the ray's record does not reach the traveltime.
+template <typename T> __global__ void k_isochrone(Rows<T> rec, int ntimes, const double* times, double* out) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= rec.R) return;
+    // rows 0..last_i of this ray (:993); a batch created with rec_rows < max_size holds only the first rec_rows of them
+    const long n = rec.last_recorded(k) + 1;
+    const size_t pitch = rec.pitch();
+    const T* col = rec.row(0, k);
+    auto tt = [&](long i) { return (double)col[(size_t)COL_T * rec.R + (size_t)i * pitch]; };
+    const int qsel[3] = {COL_X, COL_Y, COL_TH};
+    for (int it = 0; it < ntimes; it++) {
+        const double t = times[it];
+        double res[3] = {NAN, NAN, NAN};
+        if (n >= 2 && tt(n - 1) >= t && t >= tt(0)) {   // np.max(t_ray) >= travel_time (:997)
+            const long lo = rt::pchip_interval(tt, n, t);
+            const double dx = tt(lo + 1) - tt(lo), s = t - tt(lo);
+            for (int q = 0; q < 3; q++) {
+                auto yy = [&](long i) { return (double)col[(size_t)qsel[q] * rec.R + (size_t)i * pitch]; };
+                const double y0 = yy(lo), y1 = yy(lo + 1), slope = (y1 - y0) / dx;
+                double d0, d1;
+                if (n == 2) { d0 = d1 = slope; }
+                else { d0 = rt::pchip_deriv(tt, yy, lo, n); d1 = rt::pchip_deriv(tt, yy, lo + 1, n); }
+                res[q] = rt::pchip_cubic(dx, y0, slope, d0, d1).powers(s);
+            }
+        }
+        for (int q = 0; q < 3; q++) out[((size_t)it * 3 + q) * rec.R + rec.caller(k)] = res[q];
     }
-    if (j == n - 1) {
-        const double h0 = t[n - 1] - t[n - 2], h1 = t[n - 2] - t[n - 3];
-        return pchip_edge(h0, h1, (v[n - 1] - v[n - 2]) / h0, (v[n - 2] - v[n - 3]) / h1);
-    }
-    const double ha = t[j] - t[j - 1], hb = t[j + 1] - t[j];
-    const double ma = (v[j] - v[j - 1]) / ha, mb = (v[j + 1] - v[j]) / hb;
-    if (sgn_(ma) != sgn_(mb) || ma == 0 || mb == 0) return 0;
-    const double w1 = 2 * hb + ha, w2 = hb + 2 * ha;
-    return 1.0 / ((w1 / ma + w2 / mb) / (w1 + w2));
 }
 
 // All the kernels below work on a CHUNK of traveltimes at once (blockIdx.y = traveltime within the chunk): the reference's movie
@@ -97,17 +103,14 @@ __global__ void k_nodes(long R, const unsigned long long* count, const int* tie,
     double* nodes = nodes_all + (size_t)t * 7 * R;
     double d = NAN, slope = NAN, normal = NAN, diff = NAN;
     if (j < n && n >= 2 && !tie[t]) {
-        const double *y = nodes, *x = nodes + R;
-        d = pchip_deriv(y, x, j, n);
+        auto y = [=](long i) { return nodes[i]; };
+        auto x = [=](long i) { return nodes[R + i]; };
+        d = rt::pchip_deriv(y, x, j, n);
         slope = d;
         if (j == n - 1) {
-            // PPoly.derivative() evaluated at the last breakpoint uses the last interval at its right end:
-            // ((3 c0) s + 2 c1) s + c2 with CubicHermiteSpline's coefficients of interval n-2
-            const double dx = y[n - 1] - y[n - 2], m = (x[n - 1] - x[n - 2]) / dx;
-            const double d0 = pchip_deriv(y, x, n - 2, n);
-            const double tq = (d0 + d - 2 * m) / dx;
-            const double c0 = tq / dx, c1 = (m - d0) / dx - tq;
-            slope = (3 * c0 * dx + 2 * c1) * dx + d0;
+            // PPoly.derivative() evaluated at the last breakpoint uses the last interval at its right end
+            const double dx = y(n - 1) - y(n - 2), m = (x(n - 1) - x(n - 2)) / dx;
+            slope = rt::pchip_cubic(dx, x(n - 2), m, rt::pchip_deriv(y, x, n - 2, n), d).deriv(dx);
         }
         const double tangent = M_PI / 2 - atan(slope);       // (:1025)
         normal = tangent - M_PI / 2;                          // (:1026)
@@ -134,21 +137,44 @@ __global__ void k_fine(long R, const unsigned long long* count, const int* tie, 
         const double a = y[0], b = y[n - 1];
         const double step = (b - a) / (double)(nfine - 1);
         yf = q == nfine - 1 ? b : (double)q * step + a;                     // numpy.linspace
-        long lo = 0, hi = n - 1;
-        while (hi - lo > 1) {
-            const long mid = (lo + hi) >> 1;
-            if (y[mid] <= yf) lo = mid; else hi = mid;
-        }
+        const long lo = rt::pchip_interval([=](long i) { return y[i]; }, n, yf);
         const double dx = y[lo + 1] - y[lo], s = yf - y[lo], m = (x[lo + 1] - x[lo]) / dx;
-        const double d0 = deriv[lo], d1 = deriv[lo + 1];
-        const double tq = (d0 + d1 - 2 * m) / dx;
-        const double c0 = tq / dx, c1 = (m - d0) / dx - tq;
-        xf = ((c0 * s + c1) * s + d0) * s + x[lo];                           // Horner in (y - y_lo); PPoly sums the powers
+        xf = rt::pchip_cubic(dx, x[lo], m, deriv[lo], deriv[lo + 1]).horner(s);       // Horner in (y - y_lo); PPoly sums the powers
     }
     fine[q] = xf;
     fine[nfine + q] = yf;
 }
+// The per-ray stage of a batch with its checks, reported under rtmi_isochrones' name: rec becomes the batch's record, *iso =
+// [ntimes][3][R] fp64 on the device, one of mem's allocations, complete when this returns.
+int isochrones_device(rtmi_batch* b, int32_t ntimes, const double* times, DevMem& mem, Recorded& rec, double** iso) {
+    const char* who = "rtmi_isochrones";
+    RTMI_ARG(b && times, "null");
+    RTMI_ARG(ntimes > 0 && ntimes <= 4096, "ntimes must be in [1, 4096]");
+    RTMI_RC(recorded(who, b, kRecOnDevice, 0, &rec));
+    const rtmi_device_view& v = rec.v;
+    double* dt = nullptr;
+    RTMI_HIP(mem.get(iso, (size_t)ntimes * 3 * (size_t)v.R * sizeof(double)));
+    RTMI_HIP(mem.get(&dt, ntimes * sizeof(double)));
+    RTMI_HIP(hipMemcpy(dt, times, ntimes * sizeof(double), hipMemcpyHostToDevice));
+    by_dtype(v.dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_isochrone<decltype(t)>, dim3((unsigned)((v.R + 127) / 128)), dim3(128), 0, nullptr, rows_of<decltype(t)>(v), (int)ntimes, dt, *iso);
+    });
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipDeviceSynchronize());
+    return RTMI_OK;
+}
 }  // namespace
+
+RTMI_EXPORT int rtmi_isochrones(rtmi_batch* b, int32_t ntimes, const double* times, double* out) {
+    const char* who = "rtmi_isochrones";
+    RTMI_ARG(out, "null");
+    DevMem mem;
+    Recorded rec;
+    double* d = nullptr;
+    RTMI_RC(isochrones_device(b, ntimes, times, mem, rec, &d));
+    RTMI_HIP(hipMemcpy(out, d, (size_t)ntimes * 3 * (size_t)rec.v.R * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
 
 RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* times, int32_t nfine, int64_t* count, double* nodes,
                                 double* fine) {
@@ -158,12 +184,11 @@ RTMI_EXPORT int rtmi_wavefronts(rtmi_batch* b, int32_t ntimes, const double* tim
     RTMI_ARG(ntimes > 0 && ntimes <= 4096, "ntimes must be in [1, 4096]");
     Recorded rec;       // the stage below makes these checks too, under rtmi_isochrones' name
     RTMI_RC(recorded(who, b, 0, 0, &rec));
-    double* iso = nullptr;
-    long R = 0;
-    hipStream_t st = nullptr;
-    RTMI_RC(rtmi_internal_isochrones_device(b, ntimes, times, &iso, &R, (void**)&st));
     DevMem mem;
-    mem.adopt(iso);
+    double* iso = nullptr;
+    RTMI_RC(isochrones_device(b, ntimes, times, mem, rec, &iso));
+    const long R = (long)rec.v.R;
+    const hipStream_t st = nullptr;     // the batch's stream is idle after recorded(): everything below runs on the null stream
     // Traveltimes are processed in chunks of `tc` (all of them, unless that needs more than ~1 GB of work arrays: 92 bytes per
     // point): per chunk ONE stable radix sort of every point by y, one more by the traveltime it belongs to (which regroups the
     // y-sorted points per wavefront: each has exactly R of them, the rays that do not reach it at the end with y = +inf), the

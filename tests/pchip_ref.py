@@ -1,4 +1,4 @@
-"""numpy restatement, in np.longdouble, of what rtmi_isochrones (k_isochrone, rtmi.hip) and rtmi_wavefronts (wavefront.hip)
+"""numpy restatement, in np.longdouble, of what rtmi_isochrones and rtmi_wavefronts (wavefront.hip, through rt_pchip.h)
 restate in fp64: scipy 1.15.3's PchipInterpolator -- _find_derivatives and _edge_case, CubicHermiteSpline's power-basis
 coefficients, PPoly's evaluation (a sum of powers of t - T_j, lowest first) and PPoly.derivative().  Test infrastructure.
 

@@ -66,3 +66,31 @@ def test_every_entry_checks_the_record_before_it_reads_it():
             assert msg.startswith(f"librtmi error {want}: {entry}: ") and "set_state" in msg, (name, msg)
     b.close()
     F.close()
+
+
+def test_isochrones_and_wavefronts_refuse_another_device():
+    """With another device current, the per-ray stage refuses the batch before it asks for its rows: both entries report it under
+    rtmi_isochrones' name (-1).  Needs two GPUs."""
+    import ctypes as C
+    from raytracing_amd import _lib
+    from raytracing_amd import rt_bench as rb
+    n = C.c_int(0)
+    _lib.check(_lib.lib().rtmi_device_count(C.byref(n)))
+    if n.value < 2:
+        pytest.skip(f"needs 2 GPUs, this host has {n.value}")
+    _lib.check(_lib.lib().rtmi_set_device(0))
+    F = rb.Field.build("vert_heterogeneous", LIMITS["vert_heterogeneous"], rb.DELTA)
+    ms = int(np.ceil(80 / rb.DELTA_S) + 1)
+    th = np.linspace(0.05, np.pi / 2 - 0.05, 64)
+    b = rb.Batch(F, rb.op6, rb.DELTA_S, ms, LIMITS["vert_heterogeneous"], 1, th, -2.0, -2.0, keep_n_ray=False)
+    b.run()
+    try:
+        _lib.check(_lib.lib().rtmi_set_device(1))
+        for name in ("isochrones", "wavefronts"):
+            code, msg = _code(ENTRIES[name][1], b)
+            assert code == -1, (name, code, msg)
+            assert msg.startswith("librtmi error -1: rtmi_isochrones: the field lives on device"), (name, msg)
+    finally:
+        _lib.check(_lib.lib().rtmi_set_device(0))
+    b.close()
+    F.close()

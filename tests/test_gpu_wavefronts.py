@@ -1,4 +1,4 @@
-"""GPU: rtmi_isochrones (k_isochrone<double>, <float>) and rtmi_wavefronts (wavefront.hip) against tests/pchip_ref.py -- scipy's
+"""GPU: rtmi_isochrones (k_isochrone<double>, <float>) and rtmi_wavefronts (both wavefront.hip) against tests/pchip_ref.py -- scipy's
 PCHIP restated in longdouble -- applied to the DEVICE's OWN rows (b.rows(), b.d_ray()): the trajectory is not in question here,
 the interpolation is.  tests/test_pchip_ref.py holds the restatement to scipy and shows, on the oracle's rows of the same fans,
 that they visit every derivative rule; the census is asserted again here from the rows read back.
