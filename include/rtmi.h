@@ -401,7 +401,8 @@ int rtmi_field_eval_dgrad(const rtmi_field *f, int64_t npts, const double *x, co
  *   Tie rule   the first arrival is the covering triangle of least T; among bit-equal T the least key (m rec_rows + i) 2 + half.
  * Three passes with 64-bit atomics give the same bits in every schedule, launch mode, ray sorting and source grouping.
  * Not covered (count 0, NaN): nodes beyond the shorter of two neighbouring rays' ends, nodes in gaps the rules reject, and
- * caustics thinner than the fan's spacing (their branches are missed, and count is short).
+ * caustics thinner than the fan's spacing (their branches are missed, and count is short).  The later branches of a node with
+ * count > 1: rtmi_arrival_grid.
  *   count  [S][ny][nx]          covering triangles: the arrival branches (1 in a simple fan, 3 in a triplication)
  *   out    [S][ncols][ny][nx]   T theta0 theta ray step (ncols 5), then J G kmah with amplitude (ncols 8); NaN where count is 0
  * Host buffers, fp64, the caller's fan order; both dtypes (fp32 records are widened), every method.  Needs record_stride 1.
@@ -434,6 +435,44 @@ typedef struct {
 } rtmi_grid_stats;
 int rtmi_first_arrival_grid(rtmi_batch *b, int32_t fan_size, const rtmi_grid_params *gp, int32_t *count, double *out,
                             rtmi_grid_stats *st);
+
+/* Later and most energetic arrivals on a grid: where rtmi_first_arrival_grid keeps the covering triangle of least T, this keeps
+ * the karr first of a node's candidates in a chosen order.  DESIGN.md 18.  Fans, cells, gap rule, triangles, fill rule, values
+ * and key = (m rec_rows + i) 2 + half are rtmi_first_arrival_grid's, unchanged.
+ *   Candidates  of a node: exactly the (triangle, node) pairs those rules accept with 0 <= T < inf, T the interpolated value.
+ *   Criterion   RTMI_ARRIVAL_BY_TIME: c = T.  RTMI_ARRIVAL_BY_AMPLITUDE: c = n |J|, the product nn * fabs(Jn) under the square
+ *               root of the G column (G = c^-1/2), in the same operation order: the least c is the largest amplitude.  A c that
+ *               is not >= 0 and < inf is taken as +inf.  This order needs what amplitude = 1 needs (op1..op9, gamma 1), whether
+ *               or not the amplitude columns are asked for.
+ *   Order       a node's candidates sorted by (the bits of c, key); arrival k is the k-th of them, 0 <= k < karr.
+ *   count  [S][ny][nx]                the number of candidates, as rtmi_first_arrival_grid's
+ *   out    [S][karr][ncols][ny][nx]   rtmi_first_arrival_grid's columns (ncols 5, or 8 with amplitude); NaN for k >= count
+ * karr = 1 by time is rtmi_first_arrival_grid bit for bit.  out may be NULL: count and st->candidates only (what the list will
+ * take, before it is allocated).  No minimum atomics: the candidates are counted, an exclusive scan gives every node its range
+ * of one list of exactly sum(count) entries of 16 bytes (the bits of c, key), a second walk fills it, and one lane per node
+ * selects its karr least entries by value -- the same bits in every schedule, launch mode, ray sorting and source grouping.
+ * Device memory beyond the first-arrival call's: 16 sum(count) bytes, and karr times the output.  RTMI_ERR_ARG before any
+ * device work: rtmi_first_arrival_grid's cases, karr outside 1 .. RTMI_MAX_ARRIVALS, an unknown order, RTMI_ARRIVAL_BY_AMPLITUDE
+ * on op10 / op11 or gamma != 1.  RTMI_ERR_ARG also when S nx ny >= 2^31 - 1 (fewer sources per call).  Everything else as
+ * rtmi_first_arrival_grid. */
+#define RTMI_MAX_ARRIVALS 16
+enum { RTMI_ARRIVAL_BY_TIME = 0, RTMI_ARRIVAL_BY_AMPLITUDE = 1 };
+typedef struct {
+    int32_t karr;            /* arrivals kept per node, 1 .. RTMI_MAX_ARRIVALS */
+    int32_t order;           /* RTMI_ARRIVAL_BY_TIME or RTMI_ARRIVAL_BY_AMPLITUDE */
+    int64_t reserved[4];
+} rtmi_arrival_params;
+typedef struct {
+    int64_t cells, skipped_cells, triangles, folded;   /* as rtmi_grid_stats */
+    uint64_t atomics[3];     /* count adds of the count pass, cursor adds of the fill pass (both sum(count)), 0 */
+    double pass_ms[3];       /* device time of the count, fill and output passes (HIP events) */
+    double max_gap, max_dtheta;
+    double reserved[4];
+    int64_t candidates;      /* sum(count): the list holds 16 bytes for each */
+    double scan_ms;          /* device time of the scan between the count and the fill pass */
+} rtmi_arrival_stats;
+int rtmi_arrival_grid(rtmi_batch *b, int32_t fan_size, const rtmi_grid_params *gp, const rtmi_arrival_params *ap,
+                      int32_t *count, double *out, rtmi_arrival_stats *st);
 
 /* Traveltime sensitivity kernels: the Frechet derivative A of every reported traveltime with respect to the n samples
  * Z[qy][qx] of the batch's field (rtmi_field_read's Z), the rows held fixed, and its transpose.  n is the bilinear spline of the
@@ -717,6 +756,14 @@ int rtmi_debug_paraxial_rows(rtmi_batch *b, double *J, int32_t *kmah);
 int rtmi_debug_grid_rows(int32_t rows, int32_t R, int32_t fan_size, const double *x, const double *y, const double *T,
                          const double *theta, const int32_t *last, const double *theta0, const rtmi_grid_params *gp,
                          int32_t *count, double *out, rtmi_grid_stats *st);
+/* Diagnostic: rtmi_arrival_grid's kernels on caller-supplied rows, no batch: x, y, T, theta, last, theta0 as rtmi_debug_grid_rows,
+ * and J, kmah, n [rows][R] (host; n the refractive index at every row) -- all three required with gp->amplitude or
+ * RTMI_ARRIVAL_BY_AMPLITUDE, ignored otherwise and then NULL if wished.  For more sheets over a node than traced fans give, bit-equal
+ * criteria and amplitude orders set by hand.  count, out (NULL: count only) and st as rtmi_arrival_grid. */
+int rtmi_debug_arrival_rows(int32_t rows, int32_t R, int32_t fan_size, const double *x, const double *y, const double *T,
+                            const double *theta, const int32_t *last, const double *theta0, const double *J, const int32_t *kmah,
+                            const double *n, const rtmi_grid_params *gp, const rtmi_arrival_params *ap, int32_t *count,
+                            double *out, rtmi_arrival_stats *st);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,14 @@ class GridStats(C.Structure):
                 ("reserved", C.c_double * 4)]
 
 
+class ArrivalParams(C.Structure):
+    _fields_ = [("karr", C.c_int32), ("order", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class ArrivalStats(C.Structure):
+    _fields_ = GridStats._fields_ + [("candidates", C.c_int64), ("scan_ms", C.c_double)]
+
+
 class SensitivityStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("atomics", C.c_int64), ("scale_exp", C.c_int32), ("reserved0", C.c_int32),
                 ("reserved", C.c_int64 * 4)]
@@ -107,6 +115,9 @@ class KirchhoffStats(C.Structure):
                 ("scale_exp", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
 
 
+# rtmi_arrival_grid's orders and largest karr
+ARRIVAL_BY_TIME, ARRIVAL_BY_AMPLITUDE, MAX_ARRIVALS = 0, 1, 16
+ARRIVAL_ORDERS = {"time": ARRIVAL_BY_TIME, "amplitude": ARRIVAL_BY_AMPLITUDE}
 # rtmi_arrival_status
 ARRIVAL_EMPTY, ARRIVAL_CONVERGED, ARRIVAL_STALLED, ARRIVAL_TRUNCATED = -1, 1, 2, 3
 
@@ -147,6 +158,8 @@ SYMBOLS = {
     "rtmi_paraxial": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, _dp, _dp]),
     "rtmi_field_eval_dgrad": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 6),
     "rtmi_first_arrival_grid": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(GridParams), _ip, _dp, C.POINTER(GridStats)]),
+    "rtmi_arrival_grid": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(GridParams), C.POINTER(ArrivalParams), _ip, _dp,
+                                    C.POINTER(ArrivalStats)]),
     "rtmi_traveltime_perturb": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _ip, _dp, _dp, C.POINTER(SensitivityStats)]),
     "rtmi_traveltime_backproject": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(SensitivityStats)]),
     "rtmi_gaussian_beams": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BeamParams), C.c_int32, _dp, _dp, C.POINTER(BeamStats)]),
@@ -177,6 +190,8 @@ SYMBOLS = {
     "rtmi_debug_paraxial_rows": (C.c_int, [C.c_void_p, _dp, _ip]),
     "rtmi_debug_grid_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [_ip, _dp, C.POINTER(GridParams), _ip, _dp,
                                                                              C.POINTER(GridStats)]),
+    "rtmi_debug_arrival_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [_ip, _dp, _dp, _ip, _dp, C.POINTER(GridParams),
+                                          C.POINTER(ArrivalParams), _ip, _dp, C.POINTER(ArrivalStats)]),
 }
 
 _lib = None

@@ -464,6 +464,16 @@ class Batch:
         return _grid_call(lambda gp, cnt, out, st: lib().rtmi_first_arrival_grid(self._h, M, gp, cnt, out, st),
                           self.R // M if M >= 1 else 0, grid, max_gap, max_dtheta, amplitude, stats)
 
+    def arrival_grid(self, grid, arrivals=1, order="time", fan_size=None, max_gap=None, max_dtheta=None, amplitude=False, stats=False,
+                     count_only=False):
+        """The `arrivals` first arrivals per node of the recorded fans (rtmi_arrival_grid), by order "time" (the earliest) or
+        "amplitude" (the most energetic first: the least n |J|; op1..op9, gamma 1).  Arguments as first_arrival_grid.  Returns
+        its dict with arrays of shape [S, arrivals, ny, nx], NaN past a node's count; count is [S, ny, nx].  stats adds
+        'candidates' (the sum of count) and 'scan_ms'.  count_only: count (and stats) alone, before the candidate list exists."""
+        M = self.R if fan_size is None else int(fan_size)
+        return _arrival_call(lambda gp, ap, cnt, out, st: lib().rtmi_arrival_grid(self._h, M, gp, ap, cnt, out, st),
+                             self.R // M if M >= 1 else 0, grid, arrivals, order, max_gap, max_dtheta, amplitude, stats, count_only)
+
     def gaussian_beams(self, grid, omegas, eps, fan_size=None, cutoff=None, max_width=None, edge_taper=0, stats=False):
         """Gaussian beam summation (rtmi_gaussian_beams): the frequency-domain wavefield of each fan's source at every node of
         grid = (gx0, gdx, nx, gy0, gdy, ny), summed over the fan's beams.  The batch's rays are R / fan_size fans (default: one),
@@ -940,8 +950,55 @@ def debug_grid_rows(x, y, T, theta, last, theta0, grid, fan_size=None, max_gap=N
                       R // M if M >= 1 else 0, grid, max_gap, max_dtheta, False, stats)
 
 
+def arrival_params(arrivals=1, order="time"):
+    """rtmi_arrival_params: order "time" or "amplitude" (or the constant itself)"""
+    ap = _lib.ArrivalParams()
+    ap.karr = int(arrivals)
+    ap.order = _lib.ARRIVAL_ORDERS[order] if isinstance(order, str) else int(order)
+    return ap
+
+
+def _arrival_call(call, S, grid, arrivals, order, max_gap, max_dtheta, amplitude, stats, count_only=False):
+    gp = grid_params(grid, max_gap, max_dtheta, amplitude)
+    ap = arrival_params(arrivals, order)
+    names = GRID_FIELDS + (GRID_AMPLITUDE_FIELDS if amplitude else ())
+    nx, ny, K = max(int(gp.nx), 0), max(int(gp.ny), 0), min(max(int(ap.karr), 0), _lib.MAX_ARRIVALS)
+    count = np.zeros((max(S, 0), ny, nx), dtype=np.int32)
+    out = None if count_only else np.empty((max(S, 0), K, len(names), ny, nx))
+    st = _lib.ArrivalStats()
+    check(call(C.byref(gp), C.byref(ap), count.ctypes.data_as(_lib._ip), dptr(out), C.byref(st)))
+    d = {"count": count}
+    if out is not None:
+        for q, k in enumerate(names):
+            d[k] = out[:, :, q].copy()
+    if stats:
+        d["stats"] = dict(grid_stats(st), candidates=int(st.candidates), scan_ms=float(st.scan_ms))
+    return d
+
+
+def debug_arrival_rows(x, y, T, theta, last, theta0, grid, arrivals=1, order="time", J=None, kmah=None, n=None, fan_size=None,
+                       max_gap=None, max_dtheta=None, amplitude=False, stats=False):
+    """rtmi_arrival_grid's kernels on caller-supplied rows (rtmi_debug_arrival_rows): x, y, T, theta [rows, R], last [R],
+    theta0 [R]; J, kmah, n [rows, R] for the amplitude columns and for order "amplitude".  Returns what Batch.arrival_grid returns."""
+    x, y, T, th = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, y, T, theta))
+    rows, R = x.shape
+    assert y.shape == T.shape == th.shape == (rows, R)
+    la = np.ascontiguousarray(last, dtype=np.int32)
+    t0 = np.ascontiguousarray(theta0, dtype=np.float64)
+    assert la.shape == t0.shape == (R,)
+    Ja, na = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (J, n))
+    ka = None if kmah is None else np.ascontiguousarray(kmah, dtype=np.int32)
+    assert all(a is None or a.shape == (rows, R) for a in (Ja, ka, na))
+    M = R if fan_size is None else int(fan_size)
+    ip = _lib._ip
+    return _arrival_call(lambda gp, ap, cnt, out, st: lib().rtmi_debug_arrival_rows(
+        rows, R, M, dptr(x), dptr(y), dptr(T), dptr(th), la.ctypes.data_as(ip), dptr(t0), dptr(Ja),
+        None if ka is None else ka.ctypes.data_as(ip), dptr(na), gp, ap, cnt, out, st),
+        R // M if M >= 1 else 0, grid, arrivals, order, max_gap, max_dtheta, amplitude, stats)
+
+
 def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_size, box, gamma=1, amplitude=False, mem_budget=0,
-                     max_gap=None, max_dtheta=None, stats=False, **batch_kw):
+                     max_gap=None, max_dtheta=None, stats=False, arrivals=None, order="time", **batch_kw):
     """First-arrival tables from many sources onto one grid, by public calls only: a fan of launch angles
     `thetas` per source (sources: (S, 2) array of (x, y)).  1. A count pass without a record sizes rec_rows to the longest ray.
     2. Sources are grouped so that each group's record (48 bytes per row and ray in fp64, 24 in fp32; 12 more with amplitude,
@@ -949,7 +1006,9 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     (Batch.first_arrival_grid).  Each source's table depends on its own rays only, so the grouping changes no bit.  batch_kw go
     to Batch (launch_mode, sort_rays, reference_order, ...).  Returns a dict of [S, ny, nx] arrays as first_arrival_grid; with
     stats=True also 'stats' (rec_rows, groups, count_ms, trace_ms, grid_ms: host wall times, and the grid calls' summed
-    counters)."""
+    counters).  arrivals=K (with order "time" or "amplitude") takes Batch.arrival_grid instead: arrays of [S, K, ny, nx], count
+    [S, ny, nx]; a group's candidate list (16 bytes per candidate, counted by a count-only call before it is allocated) then
+    counts against mem_budget too, and a group over it is traced again in halves."""
     src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
     th = np.ascontiguousarray(thetas, dtype=np.float64)
     S, M = len(src), len(th)
@@ -964,11 +1023,13 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     finally:
         c.close()
     t1 = time.perf_counter()
-    per_ray = rows * ((48 if field.dtype == F64 else 24) + (12 if amplitude else 0))
+    by_amp = arrivals is not None and _lib.ARRIVAL_ORDERS.get(order, order) == _lib.ARRIVAL_BY_AMPLITUDE
+    per_ray = rows * ((48 if field.dtype == F64 else 24) + (12 if amplitude or by_amp else 0))
     budget = int(mem_budget) if mem_budget else 8 << 30
     G = max(1, min(S, budget // max(per_ray * M, 1)))
     res, tot = None, {"rec_rows": rows, "groups": 0, "count_ms": (t1 - t0) * 1e3, "trace_ms": 0.0, "grid_ms": 0.0}
-    for g0 in range(0, S, G):
+    g0 = 0
+    while g0 < S:
         sg = src[g0:g0 + G]
         ta = time.perf_counter()
         b = Batch(field, selected_func, step, max_size, box, gamma, np.tile(th, len(sg)), np.repeat(sg[:, 0], M),
@@ -977,9 +1038,19 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
             b.run()
             b.sync()
             tb = time.perf_counter()
-            r = b.first_arrival_grid(grid, fan_size=M, max_gap=max_gap, max_dtheta=max_dtheta, amplitude=amplitude, stats=True)
+            gkw = dict(fan_size=M, max_gap=max_gap, max_dtheta=max_dtheta, amplitude=amplitude, stats=True)
+            if arrivals is None:
+                r = b.first_arrival_grid(grid, **gkw)
+            else:
+                gkw.update(arrivals=arrivals, order=order)
+                listed = 16 * b.arrival_grid(grid, count_only=True, **gkw)["stats"]["candidates"]
+                fits = len(sg) == 1 or per_ray * M * len(sg) + listed <= budget
+                r = b.arrival_grid(grid, **gkw) if fits else None
         finally:
             b.close()
+        if r is None:                           # the candidate list would not fit beside the record: a smaller group
+            G = max(1, len(sg) // 2)
+            continue
         tc = time.perf_counter()
         tot["groups"] += 1
         tot["trace_ms"] += (tb - ta) * 1e3
@@ -989,10 +1060,13 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
             tot[k] = tot.get(k, 0) + st[k]
         tot["atomics"] = [a + b_ for a, b_ in zip(tot.get("atomics", [0, 0, 0]), st["atomics"])]
         tot["pass_ms"] = [a + b_ for a, b_ in zip(tot.get("pass_ms", [0.0] * 3), st["pass_ms"])]
+        if arrivals is not None:
+            tot["candidates"] = tot.get("candidates", 0) + st["candidates"]
         if res is None:
             res = {k: np.empty((S,) + v.shape[1:], dtype=v.dtype) for k, v in r.items()}
         for k, v in r.items():
             res[k][g0:g0 + len(sg)] = v
+        g0 += len(sg)
     if stats:
         res["stats"] = tot
     return res
