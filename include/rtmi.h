@@ -83,6 +83,24 @@ int rtmi_field_read(const rtmi_field *f, double *x, double *y, double *Z, double
 /* n_gradient(vector, grd, z) (:141-156) for npts host points -> n, dn/dx, dn/dy (host buffers). */
 int rtmi_field_eval(const rtmi_field *f, int64_t npts, const double *x, const double *y,
                     double *n, double *gx, double *gy);
+/* X-INVARIANT ("LAYERED") FIELDS.  rtmi_field_layered: 1 when the field build found the medium to depend on y alone, else 0.
+ * A field is x-invariant when (a) every row of its sample array Z[qy][qx] holds ONE bit pattern (compared exactly, no
+ * tolerance), (b) it has neither flat nor steep cells, and (c) what its fitted splines still carry of x is rounding residue:
+ * every coefficient of the d/dx polynomial and every u-dependent coefficient of the d/dy polynomial of every cell is within 2^-40
+ * of the grid's largest gradient-spline coefficient, every u-dependent coefficient of n's polynomial within 2^-40 of its constant
+ * term.  vert_heterogeneous (n = 1/(18 + 2y)) and any caller-sampled v(z) model are; the interface scenario is x-invariant in its
+ * samples but has steep and flat cells and stays on the general lookup on purpose (its critical rays amplify rounding, and the
+ * flat-cell map is already its fast path).  A field that fails any of the three is built and run as before.
+ * On an x-invariant field the fast-form fp64 step kernels (op1/2/6/8, op7 with RTMI_ORDER_FUSED; every schedule, flavour and
+ * field_path) look n and grad n up BY THE ROW ALONE, at the abscissa of the grid's middle column with u = 0:
+ *     dn/dx = +0,   dn/dy = ((g3 v + g2) v + g1) v + g0,   n = b2 v + b0,
+ * g_k and (b0, b2) the u-free coefficients of cell (ncx/2, jy)'s polynomials, v and jy -- FITPACK's argument clamp included --
+ * as the general lookup finds them; x is not located.  That differs from the general lookup by the residue named above (< 1e-13 of
+ * the field's and the gradient's scale, far inside the 1e-9 the path is held to) and is the same bits in every build, so a batch's
+ * results do not depend on how it runs.  rtmi_field_eval, rtmi_debug_field_lookup, the reference-order methods, fp32 batches and
+ * every post-trace call (rtmi_paraxial, ...) read the general tables, which are unchanged.  y-invariant media (n = f(x)) are NOT
+ * detected: they run on the general lookup. */
+int rtmi_field_layered(const rtmi_field *f);
 void rtmi_field_destroy(rtmi_field *f);
 
 /* -------------------------------------------------------------------- batch */
@@ -741,6 +759,11 @@ int rtmi_debug_exp(int64_t n, const double *x, double *out);
  * n_gradient :141-156) in every cell; tests compare it bit for bit with the host restatement of the same table. */
 int rtmi_debug_field_lookup(const rtmi_field *f, int64_t npts, const double *x, const double *y, double *n,
                             double *gx, double *gy);
+/* Diagnostic: the lookup the fast-form fp64 step kernels make on an x-invariant field (rtmi_field_layered: the rule stated
+ * there), through the kernels' own device function, for npts host points -> n, dn/dx (+0), dn/dy (host, fp64).
+ * RTMI_ERR_UNSUPPORTED for a field that is not x-invariant. */
+int rtmi_debug_field_lookup_layered(const rtmi_field *f, int64_t npts, const double *x, const double *y, double *n,
+                                    double *gx, double *gy);
 /* Diagnostic (host only, no device needed): RTMI_LAUNCH_AUTO's rule on a recorded sequence.  Given the kernel times taken so far
  * under the time-sliced (sliced_ms[ns]) and the plain (plain_ms[np]) schedule, ns, np <= RTMI_AUTO_SAMPLES: *next = the schedule
  * the next exploration run takes (RTMI_LAUNCH_SLICED / RTMI_LAUNCH_PLAIN; -1 once exploration is over), *decision = the schedule

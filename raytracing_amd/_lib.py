@@ -186,6 +186,8 @@ SYMBOLS = {
     "rtmi_debug_rcp14_table": (C.c_int, [C.POINTER(C.c_uint16)]),
     "rtmi_debug_exp": (C.c_int, [C.c_int64, _dp, _dp]),
     "rtmi_debug_field_lookup": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 5),
+    "rtmi_debug_field_lookup_layered": (C.c_int, [C.c_void_p, C.c_int64] + [_dp] * 5),
+    "rtmi_field_layered": (C.c_int, [C.c_void_p]),
     "rtmi_debug_auto_rule": (C.c_int, [_dp, C.c_int, _dp, C.c_int, _ip, _ip]),
     "rtmi_debug_paraxial_rows": (C.c_int, [C.c_void_p, _dp, _ip]),
     "rtmi_debug_grid_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [_ip, _dp, C.POINTER(GridParams), _ip, _dp,

@@ -221,6 +221,41 @@ __global__ void k_polytab(const double* Z, const double* cdx, const double* cdy,
     if ((threadIdx.x & 63) == 0 && votes) atomicAdd(nflat, (unsigned long long)__popcll(votes));
     if ((threadIdx.x & 63) == 0 && svotes) atomicAdd(nflat + 1, (unsigned long long)__popcll(svotes));
 }
+// x-invariant ("layered") fields (rt_device.h, "the lookup by depth alone"; include/rtmi.h).  k_layered_check counts the cells
+// that break the rule's conditions: a sample of the cell's corners whose bit pattern differs from its row's first (exact, no
+// tolerance), or residue the rule would drop that is not small -- a coefficient of the d/dx polynomial or a u-dependent one of
+// the d/dy polynomial beyond 2^-40 of the grid's largest gradient-spline coefficient, a u-dependent one of n's beyond 2^-40 of
+// its constant term (a NaN fails every comparison).  Reads the finished table.
+constexpr double kLayerRel = 0x1p-40;
+template <typename T>
+__global__ void k_layered_check(const double* Z, int qx, int qy, const T* poly, const unsigned long long* gmax_bits, unsigned long long* nbad) {
+    const int jx = blockIdx.x * blockDim.x + threadIdx.x, jy = blockIdx.y;
+    bool bad = false;
+    if (jx < qx - 1 && jy < qy - 1) {
+        const unsigned long long* r0 = reinterpret_cast<const unsigned long long*>(Z) + (size_t)jy * qx;
+        const unsigned long long* r1 = r0 + qx;
+        bad = r0[jx] != r0[0] || r0[jx + 1] != r0[0] || r1[jx] != r1[0] || r1[jx + 1] != r1[0];
+        const T* c = poly + ((size_t)jy * (qx - 1) + jx) * rt::kPolyStride;
+        const double thr = __builtin_bit_cast(double, *gmax_bits) * kLayerRel;
+        for (int i = 0; i < 16; i++) bad = bad || !(fabs((double)c[i]) <= thr);
+        for (int k = 0; k < 4; k++)
+            for (int p = 1; p < 4; p++) bad = bad || !(fabs((double)c[16 + 4 * k + p]) <= thr);
+        const double tn = fabs((double)c[32]) * kLayerRel;
+        bad = bad || !(fabs((double)c[33]) <= tn) || !(fabs((double)c[35]) <= tn);
+    }
+    const unsigned long long votes = rt_ballot(bad);
+    if ((threadIdx.x & 63) == 0 && votes) atomicAdd(nbad, (unsigned long long)__popcll(votes));
+}
+// The row table of a layered field: row jy's {g0, g1, g2, g3, b0, b2, 0, 0} -- the u-free coefficients of cell (ncx / 2, jy), the
+// table's own bits -- rt::kLayerStride * (jy + 1) elements in front of the table (rt::layer_row).
+template <typename T> __global__ void k_layered_rows(T* poly, int ncx, int ncy) {
+    const int jy = blockIdx.x * blockDim.x + threadIdx.x;
+    if (jy >= ncy) return;
+    const T* c = poly + ((size_t)jy * ncx + ncx / 2) * rt::kPolyStride;
+    T* o = poly - (size_t)rt::kLayerStride * ((size_t)jy + 1);
+    o[0] = c[16]; o[1] = c[20]; o[2] = c[24]; o[3] = c[28];
+    o[4] = c[32]; o[5] = c[34]; o[6] = T(0); o[7] = T(0);
+}
 // max |v| over two arrays as the bit pattern of a non-negative double (ordered like the integers)
 __global__ void k_absmax(const double* a, const double* b, size_t n, unsigned long long* out) {
     unsigned long long m = 0;
@@ -408,6 +443,28 @@ static int field_finish_impl(const char* who, rtmi_field* f, double delta, DevMe
     f->flat_cells = (long)hcnt[1];
     f->steep_cells = (long)hcnt[2];
     memcpy(&f->gmax, &hcnt[0], sizeof(double));
+    // x-invariant?  Only a field without flat and steep cells can be (the map's region then holds the row table), and the grid
+    // must be wide enough for the region to hold a line per row.
+    if (f->flat_cells == 0 && f->steep_cells == 0 && (size_t)rt::kLayerStride * (qy - 1) <= (size_t)f->flat_pad) {
+        unsigned long long nbad = 0;
+        RTMI_HIP(hipMemsetAsync(dcnt + 1, 0, sizeof(nbad), st));
+        by_dtype(f->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_layered_check<T>, pg, pb, 0, st, f->dZ, qx, qy, (const T*)f->poly, dcnt, dcnt + 1);
+        });
+        RTMI_HIP(hipGetLastError());
+        RTMI_HIP(hipMemcpyAsync(&nbad, dcnt + 1, sizeof(nbad), hipMemcpyDeviceToHost, st));
+        RTMI_HIP(hipStreamSynchronize(st));
+        if (nbad == 0) {
+            by_dtype(f->dtype, [&](auto t) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(k_layered_rows<T>, dim3((qy - 1 + 63) / 64), dim3(64), 0, st, (T*)f->poly, qx - 1, qy - 1);
+            });
+            RTMI_HIP(hipGetLastError());
+            RTMI_HIP(hipStreamSynchronize(st));
+            f->layered = 1;
+        }
+    }
     if (getenv("RTMI_DEBUG")) fprintf(stderr, "rtmi: field %d x %d: %ld of %zu cells flat, %ld steep (lambda >= %.3g)\n", qx, qy, (long)hcnt[1], ncell, (long)hcnt[2], lam0);
     return RTMI_OK;
 }
@@ -499,6 +556,8 @@ RTMI_EXPORT int rtmi_field_dims(const rtmi_field* f, int* qx, int* qy) {
     *qx = f->qx; *qy = f->qy;
     return RTMI_OK;
 }
+
+RTMI_EXPORT int rtmi_field_layered(const rtmi_field* f) { return f ? f->layered : 0; }
 
 RTMI_EXPORT int rtmi_field_read(const rtmi_field* f, double* x, double* y, double* Z, double* cdy, double* cdx) {
     const char* who = "rtmi_field_read";

@@ -642,6 +642,11 @@ template <typename T, bool FLAT> struct ReportsSteep<PolyLaneKept<T, FLAT>> { st
 // ... and gathers the step loops call prefetch() on after every step
 template <typename G> struct HasPrefetch { static constexpr bool value = false; };
 template <typename T, bool FLAT> struct HasPrefetch<PolyLaneKept<T, FLAT>> { static constexpr bool value = true; };
+// ... and the lookups of an x-invariant field (LayerGather, LayerLaneKept below): no flat-cell map, no steepness
+template <typename T, int MODE> struct LayerGather;
+template <typename T, int MODE> struct IsPoly<LayerGather<T, MODE>> { static constexpr bool value = true; };
+template <typename T> struct LayerLaneKept;
+template <typename T> struct IsPoly<LayerLaneKept<T>> { static constexpr bool value = true; };
 // ... and the steepness of the cell (flat-cell map, FlatBits): 0 for every lookup that is not a PolyGather with the map compiled in
 template <typename T, typename G>
 __device__ __forceinline__ void n_gradient(const FieldDev<T>& F, G& gather, bool active, T x, T y, T& n, T& gx, T& gy, float& lam) {
@@ -968,6 +973,151 @@ template <typename T, bool FLAT = true> struct PolyLaneKept {
             const int cell = (int)jfy * F.ncx + (int)jfx;
             if (cell != tag) load(F, cell);
         }
+    }
+};
+
+// ---------------------------------------------------------------- x-invariant ("layered") fields: the lookup by depth alone
+// A field whose samples are bit-identical along x (n = f(y): the headline's 1/(18 + 2y), any v(z) model), without flat or steep
+// cells, has fitted splines that do not depend on x either -- up to the rounding residue of the fit: the d/dx spline is what
+// np.gradient's edge formula leaves of equal samples, and the u-dependent coefficients of the d/dy and n polynomials are a few
+// ulp of the u-free ones.  The field build checks that (field.hip, k_layered_check: equal bit patterns along every row, and the
+// residue within 2^-40 of the grid's gradient scale) and then the fast-form step kernels look such a field up BY THIS RULE: n
+// and grad n at the abscissa of the grid's middle column with u = 0,
+//     dn/dx = +0,   dn/dy = ((g3 v + g2) v + g1) v + g0,   n = b2 v + b0,
+// g_k = A_dy[k][0] and (b0, b2) of cell (ncx / 2, jy); v and jy -- FITPACK's argument clamp (quirk Q4) included -- exactly as
+// poly_locate finds them; x is not located at all.  Per step that is 5 fma instead of 33, and one 64-byte line of a per-row
+// table instead of five lines of a cell's entry.  The rule is the lookup's definition on such a field for every fast-form
+// step kernel -- every schedule, flavour and field path -- so results do not depend on which build ran; the general table, the
+// reference-order builds, rtmi_field_eval and the post-trace units read what they always read.
+// The row table: row jy's line {g0, g1, g2, g3, b0, b2, 0, 0} sits kLayerStride (rt_polytab.h) * (jy + 1) elements IN FRONT of FieldDev::poly,
+// in the region that holds the flat-cell map on other fields (unused on these: they have no flat or steep cell) -- reached from
+// the members the lookup has in registers anyway, FieldDev does not grow.
+template <typename T> __device__ __forceinline__ const Quad<T>* layer_row(const FieldDev<T>& F, int jy) {
+    return reinterpret_cast<const Quad<T>*>(F.poly) - 2 * ((long)jy + 1);
+}
+// the y half of poly_locate: same clamp, same v
+template <typename T> __device__ __forceinline__ void layer_locate(const FieldDev<T>& F, T y, unsigned long long live, int& jy, T& v) {
+    T ya = y - F.ay;
+    T jfy = floor_(ya * F.inv_hy);
+    jy = (int)jfy;
+    const unsigned long long outy = rt_ballot((unsigned)jy >= (unsigned)(F.qy - 1));
+    if ((outy & live) != 0ull) {
+        const FieldDev<T> G = rare_field(F);
+        if ((unsigned)jy >= (unsigned)(G.qy - 1)) poly_axis_clamped(y, G.ay, G.by, G.inv_hy, G.qy - 1, ya, jfy, jy);
+    }
+    v = fma_(ya, F.inv_hy, -jfy);
+}
+// The three service forms of PolyGather / PolyLaneKept: a wave-uniform row through the scalar cache (two rounds for a wave in
+// two rows, then per lane), per-lane loads, and the kept row of k_advance_lat.  Same fma chain in every form: same bits.
+template <typename T, int MODE> struct alignas(8) LayerGather {
+    static constexpr bool SCALAR = MODE == kPolyScalar;
+    static constexpr bool kPoly = true;
+    typedef const Quad<T> __attribute__((address_space(4)))* ScalarRows;
+    static __device__ __forceinline__ void eval_scalar(ScalarRows p, T v, T& n, T& gy) {
+        const Quad<T> g = p[0], b = p[1];
+        gy = fma_vus(fma_vus(fma_sus(g.w, v, g.z), v, g.y), v, g.x);
+        n = fma_sus(b.y, v, b.x);
+    }
+    static __device__ __forceinline__ void eval_lane(const FieldDev<T>& F, int jy, T v, T& n, T& gy) {
+        const Quad<T>* p = layer_row(F, jy);
+        const Quad<T> g = p[0];
+        const Pair<T> b = *reinterpret_cast<const Pair<T>*>(p + 1);
+        gy = fma_(fma_(fma_(g.w, v, g.z), v, g.y), v, g.x);
+        n = fma_(b.y, v, b.x);
+    }
+    __device__ __forceinline__ void lookup_xy(const FieldDev<T>& F, bool active, T, T y, T& n, T& gx, T& gy) {
+        const unsigned long long live = rt_ballot(active);
+        int jy;
+        T v;
+        layer_locate(F, y, live, jy, v);
+        n = T(1); gx = T(0); gy = T(0);              // what an idle lane steps on with (finite; nobody reads its state)
+        if constexpr (SCALAR) {
+            if (live == 0ull) return;                // nothing addresses the table with an idle lane's row
+            int ju = __builtin_amdgcn_readlane(jy, __builtin_ctzll(live));
+            // the row's address from the scalar, pinned to scalar registers before any comparison with the per-lane row (see PolyGather)
+            ScalarRows p = (ScalarRows)layer_row(F, ju);
+            asm volatile("" : "+s"(p));
+            if ((rt_ballot(jy != ju) & live) == 0ull) {
+                eval_scalar(p, v, n, gy);            // every lane, an idle one too at its own v: finite, and nobody reads it
+                return;
+            }
+            bool todo = active;
+#pragma nounroll
+            for (int round = 0; round < 2; ++round) {
+                if (rt_ballot(todo) == 0ull) break;
+                if (todo) {
+                    ju = __builtin_amdgcn_readfirstlane(jy);
+                    p = (ScalarRows)layer_row(F, ju);
+                    asm volatile("" : "+s"(p));
+                    if (jy == ju) {
+                        eval_scalar(p, v, n, gy);
+                        todo = false;
+                    }
+                }
+            }
+            if (todo) eval_lane(F, jy, v, n, gy);
+        } else {
+            if (active) eval_lane(F, jy, v, n, gy);
+        }
+    }
+    __device__ __forceinline__ void lookup_xy(const FieldDev<T>& F, bool active, T x, T y, T& n, T& gx, T& gy, float& lam) {
+        lam = 0.f;
+        lookup_xy(F, active, x, y, n, gx, gy);
+    }
+};
+// k_advance_lat's form.  That build spends registers on latency (two waves per SIMD at most: nothing else hides a load), and a row's
+// line is 12 registers where a cell's entry is 72: every lane keeps the row its ray is in AND the kHalo rows on either side.  A ray
+// that moves to the next row (every ~7 steps on the headline's grid) finds it in registers, shifts the window and starts the load
+// of the row that enters it kHalo rows ahead -- a dozen steps before it can be needed, where PolyLaneKept's one-step-ahead
+// prefetch of a whole cell still waits at the point of use now and then.  The common step touches no memory and waits for none;
+// a jump of more than one row (a long step on a fine grid) reloads the window.  Window slots past the grid's ends hold the end row
+// again (never evaluated: jy is in the grid).  Same fma chain on the same numbers as LayerGather: same bits.
+template <typename T> struct LayerLaneKept {
+    static constexpr bool kPoly = true;
+    static constexpr int kHalo = 2, kRows = 2 * kHalo + 1;
+    int tag;                   // the row g[kHalo], b[kHalo] hold; -1: nothing yet
+    Quad<T> g[kRows];
+    Pair<T> b[kRows];
+    __device__ __forceinline__ void init() {
+        tag = -1;
+#pragma unroll
+        for (int k = 0; k < kRows; k++) { g[k] = Quad<T>{T(0), T(0), T(0), T(0)}; b[k] = Pair<T>{T(0), T(0)}; }
+    }
+    static __device__ __forceinline__ void load(const FieldDev<T>& F, int jy, Quad<T>& go, Pair<T>& bo) {
+        jy = jy < 0 ? 0 : (jy > F.qy - 2 ? F.qy - 2 : jy);
+        const Quad<T>* p = layer_row(F, jy);
+        go = p[0];
+        bo = *reinterpret_cast<const Pair<T>*>(p + 1);
+    }
+    __device__ __forceinline__ void lookup_xy(const FieldDev<T>& F, bool active, T, T y, T& n, T& gx, T& gy) {
+        int jy;
+        T v;
+        layer_locate(F, y, rt_ballot(active), jy, v);
+        if (active && jy != tag) {
+            if (tag >= 0 && jy == tag + 1) {
+#pragma unroll
+                for (int k = 0; k + 1 < kRows; k++) { g[k] = g[k + 1]; b[k] = b[k + 1]; }
+                load(F, jy + kHalo, g[kRows - 1], b[kRows - 1]);
+            } else if (tag >= 0 && jy == tag - 1) {
+#pragma unroll
+                for (int k = kRows - 1; k > 0; k--) { g[k] = g[k - 1]; b[k] = b[k - 1]; }
+                load(F, jy - kHalo, g[0], b[0]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kRows; k++) load(F, jy - kHalo + k, g[k], b[k]);
+            }
+            tag = jy;
+        }
+        const Quad<T> gm = g[kHalo];
+        const Pair<T> bm = b[kHalo];
+        gy = fma_(fma_(fma_(gm.w, v, gm.z), v, gm.y), v, gm.x);
+        n = fma_(bm.y, v, bm.x);
+        gx = T(0);
+        if (!active) { n = T(1); gy = T(0); }      // what an idle lane steps on with (finite; nobody reads its state)
+    }
+    __device__ __forceinline__ void lookup_xy(const FieldDev<T>& F, bool active, T x, T y, T& n, T& gx, T& gy, float& lam) {
+        lam = 0.f;
+        lookup_xy(F, active, x, y, n, gx, gy);
     }
 };
 

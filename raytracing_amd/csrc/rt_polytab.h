@@ -40,6 +40,8 @@ __device__ __forceinline__ unsigned long long rt_ballot(bool p) { return __built
 namespace rt {
 
 constexpr int kPolyStride = 40;
+// elements per row of the row table of an x-invariant field (rt_device.h, "the lookup by depth alone"): one 64-byte line in fp64
+constexpr int kLayerStride = 8;
 
 // cubic knot interval of cell j on an m-point axis (the 4-coefficient window starts at l - 3)
 RT_PT_HD inline int poly_interval(int j, int m) { const int l = j + 2; return l < 3 ? 3 : (l > m - 1 ? m - 1 : l); }

@@ -135,6 +135,17 @@ __global__ void k_field_eval(rt::FieldDev<T> F, long npts, const double* x, cons
     n[i] = a; gx[i] = b; gy[i] = c;
 }
 
+// the lookup of an x-invariant field by its row alone (rt::LayerGather, per-lane form), one lane per point
+template <typename T>
+__global__ void k_field_eval_layered(rt::FieldDev<T> F, long npts, const double* x, const double* y, double* n, double* gx, double* gy) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    T a, b, c;
+    rt::LayerGather<T, rt::kPolyLane> gg;
+    rt::n_gradient(F, gg, true, (T)x[i], (T)y[i], a, b, c);
+    n[i] = a; gx[i] = b; gy[i] = c;
+}
+
 RTMI_EXPORT int rtmi_abi_version(void) { return RTMI_ABI_VERSION; }
 RTMI_EXPORT const char* rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT int rtmi_set_device(int device) {
@@ -147,8 +158,9 @@ RTMI_EXPORT int rtmi_device_count(int* count) {
     return RTMI_OK;
 }
 
+// fast: 0 FITPACK's arithmetic, 1 the cell's polynomial, 2 the layered rule
 static int field_eval_impl(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* n, double* gx,
-                           double* gy, bool fast, const char* who) {
+                           double* gy, int fast, const char* who) {
     RTMI_ARG(f && x && y && n && gx && gy, "null");
     RTMI_ARG(npts >= 0, "npts < 0");
     DEVICE_TRY(f, who);
@@ -163,7 +175,8 @@ static int field_eval_impl(const rtmi_field* f, int64_t npts, const double* x, c
     double *dn = d + 2 * npts, *dgx = d + 3 * npts, *dgy = d + 4 * npts;
     by_dtype(f->dtype, [&](auto t) {
         using T = decltype(t);
-        if (fast) hipLaunchKernelGGL((k_field_eval<T, true>), blocks(npts), dim3(256), 0, st, field_dev<T>(f, 0), (long)npts, d, d + npts, dn, dgx, dgy);
+        if (fast == 2) hipLaunchKernelGGL((k_field_eval_layered<T>), blocks(npts), dim3(256), 0, st, field_dev<T>(f, 0), (long)npts, d, d + npts, dn, dgx, dgy);
+        else if (fast) hipLaunchKernelGGL((k_field_eval<T, true>), blocks(npts), dim3(256), 0, st, field_dev<T>(f, 0), (long)npts, d, d + npts, dn, dgx, dgy);
         else hipLaunchKernelGGL((k_field_eval<T, false>), blocks(npts), dim3(256), 0, st, field_dev<T>(f, 1), (long)npts, d, d + npts, dn, dgx, dgy);
     });
     RTMI_HIP(hipGetLastError());
@@ -187,11 +200,17 @@ int rtmi_internal_field_poly(const rtmi_field* f, rtmi_internal_poly* out) {
 }
 RTMI_EXPORT int rtmi_field_eval(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* n,
                                 double* gx, double* gy) {
-    return field_eval_impl(f, npts, x, y, n, gx, gy, false, "rtmi_field_eval");
+    return field_eval_impl(f, npts, x, y, n, gx, gy, 0, "rtmi_field_eval");
 }
 RTMI_EXPORT int rtmi_debug_field_lookup(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* n,
                                         double* gx, double* gy) {
-    return field_eval_impl(f, npts, x, y, n, gx, gy, true, "rtmi_debug_field_lookup");
+    return field_eval_impl(f, npts, x, y, n, gx, gy, 1, "rtmi_debug_field_lookup");
+}
+RTMI_EXPORT int rtmi_debug_field_lookup_layered(const rtmi_field* f, int64_t npts, const double* x, const double* y, double* n,
+                                                double* gx, double* gy) {
+    ARG_TRY(f, "rtmi_debug_field_lookup_layered: null");
+    if (!f->layered) return fail(RTMI_ERR_UNSUPPORTED, "rtmi_debug_field_lookup_layered: the field is not x-invariant (rtmi_field_layered)");
+    return field_eval_impl(f, npts, x, y, n, gx, gy, 2, "rtmi_debug_field_lookup_layered");
 }
 
 // ================================================================== ray batch
@@ -393,12 +412,20 @@ template <typename T, int METHOD, bool NOFLAT> struct GatherOf<T, METHOD, true, 
 template <typename T, int METHOD, bool LDS, bool NOFLAT> struct GatherOf<T, METHOD, LDS, NOFLAT, true> {
     using type = rt::PolyGather<T, !LDS ? rt::kPolyLane : rt::kPolyScalar, !NOFLAT>;
 };
+// LAYER: the build for an x-invariant field (rt::LayerGather: the lookup by the row alone), fast forms only and always with NOFLAT
+template <typename T, int METHOD, bool LDS, bool NOFLAT, bool LAYER> struct StepGatherOf { using type = typename GatherOf<T, METHOD, LDS, NOFLAT>::type; };
+template <typename T, int METHOD, bool LDS, bool NOFLAT> struct StepGatherOf<T, METHOD, LDS, NOFLAT, true> {
+    static_assert(uses_poly<T, METHOD>() && !rt::IsExact<T, METHOD>::value, "the layered lookup serves the fast-form step methods only");
+    using type = rt::LayerGather<T, !LDS ? rt::kPolyLane : rt::kPolyScalar>;
+};
 template <typename T, bool LDS, bool FM> __device__ __forceinline__ void gather_init(rt::GlobalGather<T, FM>&, T*) {}
 // the per-lane gather of a build with the flat path compiled in (reference-order op1/2/6/8 on a field with flat cells) carries gflat
 template <typename T, typename G> __device__ __forceinline__ void gather_flat_bound(G&, const BatchDev<T>&) {}
 template <> __device__ __forceinline__ void gather_flat_bound<double, rt::GlobalGather<double, true>>(rt::GlobalGather<double, true>& g, const BatchDev<double>& a) { g.gflat = a.gflat; }
 template <typename T, bool LDS, int MODE, bool FLAT> __device__ __forceinline__ void gather_init(rt::PolyGather<T, MODE, FLAT>&, T*) {}
 template <typename T, bool LDS, bool FLAT> __device__ __forceinline__ void gather_init(rt::PolyLaneKept<T, FLAT>& g, T*) { g.init(); }
+template <typename T, bool LDS, int MODE> __device__ __forceinline__ void gather_init(rt::LayerGather<T, MODE>&, T*) {}
+template <typename T, bool LDS> __device__ __forceinline__ void gather_init(rt::LayerLaneKept<T>& g, T*) { g.init(); }
 // LDS of a step kernel in units of T: the reference-order methods' tile; the polynomial lookup needs none.  (An L2 prefetch of
 // the cells ahead -- global_load_lds into a per-wave sink whenever the wave's cell changes -- was measured: interface 23.6 ->
 // 23.0 ms, but fisheye, a new cell every step, 8.3 -> 9.1, vert_heterogeneous 8.8 -> 9.0, fp32 48.7 -> 49.6: not kept.)
@@ -562,7 +589,7 @@ __device__ __forceinline__ void advance_loop(const BatchDev<T>& a, const rt::Con
 }
 
 // LAT: the build for few waves (k_advance_lat), whose gather is rt::PolyLaneKept
-template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH = false, bool NOFLAT = false, bool LAT = false>
+template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH = false, bool NOFLAT = false, bool LAT = false, bool LAYER = false>
 __device__ __forceinline__ bool advance_bundle(const BatchDev<T>& a, T* lds, long blk, int nsteps);
 
 // Which 256-ray bundle a hardware block takes.  Blocks are dealt to the eight XCDs round-robin (block h runs on XCD h % 8,
@@ -599,19 +626,19 @@ template <typename T> constexpr int advance_waves(int m, bool lds, int f32_waves
 // row by row), the fp64 global-gather variants three (137-168 VGPRs, gathers in two halves); none of them spills.
 // Every lane runs every iteration until no lane of its wave is active; a ray's state is stored the moment it
 // terminates (or when the launch's step budget ends), so idle lanes never write.
-template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool NOFLAT = false>
+template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool NOFLAT = false, bool LAYER = false>
 __global__ __launch_bounds__(256, advance_waves<T>(METHOD, LDS, 4))
 void k_advance(BatchDev<T> a, int nsteps) {
     __shared__ __attribute__((aligned(16))) T lds[kernel_lds_elems<T, METHOD, LDS>()];
     if (a.prio > 0) __builtin_amdgcn_s_setprio(3);     // the re-trace of a few hundred critical rays beside the main kernel's waves
     unsigned bundle = xcd_grouped_block(blockIdx.x, gridDim.x);
-    if constexpr (!NOFLAT && sizeof(T) == 8 && rt::rotating_method(METHOD)) {
+    if constexpr (!NOFLAT && !LAYER && sizeof(T) == 8 && rt::rotating_method(METHOD)) {
         // a re-run batch that handed critical rays over last time starts with THEIR bundles (Retrace::rot): the re-trace is one long
         // dependent chain per ray and ends the pass the later the later it starts
         bundle += a.blk_rot;
         bundle = bundle >= gridDim.x ? bundle - gridDim.x : bundle;
     }
-    advance_bundle<T, METHOD, ISO, LDS, VAR, false, NOFLAT>(a, lds, (long)bundle * blockDim.x, nsteps);
+    advance_bundle<T, METHOD, ISO, LDS, VAR, false, NOFLAT, false, LAYER>(a, lds, (long)bundle * blockDim.x, nsteps);
 }
 // The kernel built for FEW waves: a batch of <= 2 waves per SIMD (cfg2's 65 536 rays: one) has nothing to hide a step's
 // dependent chain behind -- 1 800 cycles per step at one wave per SIMD against 545 of issue -- so this build spends registers
@@ -622,15 +649,17 @@ void k_advance(BatchDev<T> a, int nsteps) {
 // 2.26 -> 2.11 ms, 32 768 rays full 2.93 -> 2.46, the fisheye shard of 8 4.78 -> 4.06, strong8 full 3.30 -> 3.21; strong8
 // without the record loses 5 % (2.27 -> 2.39).  Same arithmetic as every other build: same bits.
 // NOFLAT: for a field whose flat-cell map is empty (vert_heterogeneous, fisheye): neither the map's tests nor the hover sum are compiled in
-template <typename T, int METHOD, bool ISO, bool NOFLAT = false>
+// LAYER: for an x-invariant field -- every lane keeps its ROW's line (rt::LayerLaneKept)
+template <typename T, int METHOD, bool ISO, bool NOFLAT = false, bool LAYER = false>
 __global__ __launch_bounds__(256, 2) void k_advance_lat(BatchDev<T> a, int nsteps) {
     static_assert(uses_poly<T, METHOD>(), "k_advance_lat is built for the fast forms only");
     __shared__ __attribute__((aligned(16))) T lds[2];
-    advance_bundle<T, METHOD, ISO, true, false, false, NOFLAT, true>(a, lds, (long)blockIdx.x * blockDim.x, nsteps);
+    advance_bundle<T, METHOD, ISO, true, false, false, NOFLAT, true, LAYER>(a, lds, (long)blockIdx.x * blockDim.x, nsteps);
 }
-template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH, bool NOFLAT, bool LAT>
+template <typename T, int METHOD, bool ISO, bool LDS, bool VAR, bool COH, bool NOFLAT, bool LAT, bool LAYER>
 __device__ __forceinline__ bool advance_bundle(const BatchDev<T>& a, T* lds, long blk, int nsteps) {
-    std::conditional_t<LAT, rt::PolyLaneKept<T, !NOFLAT>, typename GatherOf<T, METHOD, LDS, NOFLAT>::type> gather;
+    std::conditional_t<LAT, std::conditional_t<LAYER, rt::LayerLaneKept<T>, rt::PolyLaneKept<T, !NOFLAT>>,
+                       typename StepGatherOf<T, METHOD, LDS, NOFLAT, LAYER>::type> gather;
     gather_init<T, LDS>(gather, lds);
     if constexpr (rt::IsExact<T, METHOD>::value && rt::ex::flat_shortcut<rt::base_method(METHOD)>()) gather_flat_bound<T>(gather, a);
     if constexpr (rt::IsExact<T, METHOD>::value) {
@@ -693,7 +722,7 @@ __device__ __forceinline__ unsigned long long realtime_ticks() { return __builti
 // coherence point, s_waitcnt vmcnt(0) and the block barrier; this keeps the optimizer from moving state accesses across the
 // entry load / entry store (s_waitcnt is not a memory operation to it, and the barrier's fence is workgroup scope).
 __device__ __forceinline__ void compiler_fence() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
-template <typename T, int METHOD, bool ISO, bool LDS, bool NOFLAT = false>
+template <typename T, int METHOD, bool ISO, bool LDS, bool NOFLAT = false, bool LAYER = false>
 // (the fp32 k_advance fits five waves per SIMD by itself, 94 VGPRs; the sliced build has to be told)
 __global__ __launch_bounds__(256, advance_waves<T>(METHOD, LDS, 5))
 void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, unsigned long long* ctl, unsigned long long timeout_ticks) {
@@ -758,7 +787,7 @@ void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, uns
             const unsigned k = (unsigned)(e >> 32);           // slices this bundle has had
             const int nsteps = k == 0u ? 4 * slice : k == 1u ? 2 * slice : slice;
             compiler_fence();
-            const bool alive = advance_bundle<T, METHOD, ISO, LDS, false, true, NOFLAT>(a, lds, bundle * 256, nsteps);
+            const bool alive = advance_bundle<T, METHOD, ISO, LDS, false, true, NOFLAT, false, LAYER>(a, lds, bundle * 256, nsteps);
             compiler_fence();                                // no state store of the bundle moves below the entry store
             __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0): this lane's state stores are acknowledged
             const int any = __builtin_amdgcn_readfirstlane(__syncthreads_or(alive));
@@ -784,17 +813,17 @@ void k_advance_sliced(BatchDev<T> a, int slice, unsigned long long capacity, uns
 // never depends on its lane or wave mates, so results are bit-identical to k_advance.
 // Exit: the queue is exhausted and no lane is live -- reached by every wave because each ray takes at most
 // max_size steps and the queue only advances.
-template <typename T, int METHOD, bool ISO, bool LDS>
+template <typename T, int METHOD, bool ISO, bool LDS, bool LAYER = false>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : light_method(METHOD) ? 3 : 2) void k_trace_refill(BatchDev<T> a, int refill_min, int chunk) {
     __shared__ __attribute__((aligned(16))) T lds[kernel_lds_elems<T, METHOD, LDS>()];
-    typename GatherOf<T, METHOD, LDS>::type gather;
+    typename StepGatherOf<T, METHOD, LDS, false, LAYER>::type gather;
     gather_init<T, LDS>(gather, lds);
     if constexpr (rt::IsExact<T, METHOD>::value && rt::ex::flat_shortcut<rt::base_method(METHOD)>()) gather_flat_bound<T>(gather, a);
     if constexpr (rt::IsExact<T, METHOD>::value) {
         if constexpr (rt::ex::inline_sincos(rt::base_method(METHOD)) || (METHOD & rt::kFastField) != 0) rt::ex::stage_sincos_tab();
     }
     const bool RECORD = a.stride != 0;
-    constexpr bool RHOV = rt::ReportsSteep<typename GatherOf<T, METHOD, LDS>::type>::value && rt::RotatesUnit<T, METHOD>::value;
+    constexpr bool RHOV = rt::ReportsSteep<decltype(gather)>::value && rt::RotatesUnit<T, METHOD>::value;
     rt::Consts<T> K = a.K;
     if constexpr (RHOV) gather.hov_limit = a.hov_limit / (float)K.step;
     const unsigned lane = threadIdx.x & 63;
@@ -901,15 +930,19 @@ __global__ void k_f32_to_f64(const float* in, double* out, size_t n) {
 // What a plain launch runs besides the ordinary k_advance build: the VAR build (per-ray DELTA_S / max_size, per-lane row
 // bookkeeping) or k_advance_lat (few waves).  The sliced and refill schedules have one build each whatever the flavour.
 enum StepFlavour { kOrdinary = 0, kPerRay = 1, kFewWaves = 2 };
+enum StepFlat { kFlatMap = 0, kNoFlat = 1, kLayered = 2 };
 // The build key: everything the choice of a step kernel depends on, decided by step_build alone.
 struct StepBuild {
     int dtype = RTMI_F64;
     int ki = 0;                 // kernel method (batch_kernel_index)
     bool iso = false;           // gamma == 1 below op10
     bool lds = false;           // the gather policy (use_lds_tile)
-    bool noflat = false;        // the field has neither flat nor steep cells: the builds without its map's tests
+    // the flat axis: kFlatMap -- the field has flat or steep cells; kNoFlat -- it has neither: the builds without its map's tests;
+    // kLayered -- it has neither AND is x-invariant (rtmi_field::layered): the fast-form fp64 builds that look it up by the row alone
+    // (rt::LayerGather); every other build of a layered field is its kNoFlat one
+    int flat = kFlatMap;
     int flavour = kOrdinary;
-    int slot() const { return (iso ? 1 : 0) | (lds ? 2 : 0) | (noflat ? 4 : 0) | flavour << 3; }
+    int slot() const { return (iso ? 1 : 0) | (lds ? 2 : 0) | flat << 2 | flavour << 4; }
     bool operator==(const StepBuild& o) const { return dtype == o.dtype && ki == o.ki && slot() == o.slot(); }
 };
 struct rtmi_batch {
@@ -1181,7 +1214,7 @@ static StepBuild step_build(const rtmi_batch* b) {
     k.ki = batch_kernel_index(b);
     k.iso = b->p.gamma == 1.0 && b->p.method < 10;
     k.lds = use_lds_tile(b);
-    k.noflat = b->field->flat_cells == 0 && b->field->steep_cells == 0;
+    k.flat = b->field->flat_cells != 0 || b->field->steep_cells != 0 ? kFlatMap : b->field->layered ? kLayered : kNoFlat;
     // at most two waves per SIMD's worth of rays: the latency build
     if (k.lds && k.dtype == RTMI_F64 && (b->p.method == 2 || b->p.method == 6) && !b->vstep && uniform_rows_ok(b) && !ref_order(b->p) &&
         (b->R + 63) / 64 <= (int64_t)2 * b->lat_simds)
@@ -1197,15 +1230,27 @@ static StepBuild step_build(const rtmi_batch* b) {
 //   NOFLAT leaves out the polynomial lookup's map tests in the LDS-tile builds, and the flat path of the reference-order step
 //   (rt::GlobalGather's FLATMAP) in the fp64 global-gather builds of op1/2/6/8; every other build keeps its map;
 //   the VAR build gathers globally with the map; k_advance_lat is built for fp64 op2/op6 with the tile policy only.
-constexpr int kSlots = 3 << 3;
+//   kLayered selects the builds on rt::LayerGather for the fused fp64 op1/2/6/7/8 -- under every schedule, flavour and gather
+//   policy, so that a batch on such a field gives the same bits however it runs -- and is kNoFlat for every other kernel method.
+constexpr int kSlots = 3 << 4;
 template <typename T, int I, int S, int SCHED> static const void* build_kernel() {
     constexpr int M = sizeof(T) == 4 ? rt::base_method(kmethod_of(I)) : kmethod_of(I);
     constexpr bool ISO = (S & 1) && rt::base_method(M) < 10, LDS = (S & 2) != 0;
-    constexpr bool NOFLAT = (S & 4) && (LDS ? uses_poly<T, M>() : sizeof(T) == 8 && (I == 11 || I == 12 || I == 13 || I == 15));
-    if constexpr (SCHED == RTMI_LAUNCH_SLICED) return (const void*)k_advance_sliced<T, M, ISO, LDS, NOFLAT>;
+    constexpr int FLAT = (S >> 2) & 3, FLAVOUR = S >> 4;
+    constexpr bool LAYER = FLAT == kLayered && sizeof(T) == 8 && uses_poly<T, M>() && !rt::IsExact<T, M>::value;
+    constexpr bool NOFLAT = (FLAT == kNoFlat || FLAT == kLayered) && (LDS ? uses_poly<T, M>() : sizeof(T) == 8 && (I == 11 || I == 12 || I == 13 || I == 15));
+    if constexpr (LAYER) {
+        if constexpr (SCHED == RTMI_LAUNCH_SLICED) return (const void*)k_advance_sliced<T, M, ISO, LDS, true, true>;
+        else if constexpr (SCHED == RTMI_LAUNCH_REFILL) return (const void*)k_trace_refill<T, M, ISO, LDS, true>;
+        else if constexpr (FLAVOUR == kPerRay) return (const void*)k_advance<T, M, ISO, false, true, true, true>;
+        else if constexpr (FLAVOUR == kOrdinary) return (const void*)k_advance<T, M, ISO, LDS, false, true, true>;
+        else if constexpr ((M == 2 || M == 6) && LDS) return (const void*)k_advance_lat<T, M, ISO, true, true>;
+        else return nullptr;
+    }
+    else if constexpr (SCHED == RTMI_LAUNCH_SLICED) return (const void*)k_advance_sliced<T, M, ISO, LDS, NOFLAT>;
     else if constexpr (SCHED == RTMI_LAUNCH_REFILL) return (const void*)k_trace_refill<T, M, ISO, LDS>;
-    else if constexpr (S >> 3 == kPerRay) return (const void*)k_advance<T, M, ISO, false, true>;
-    else if constexpr (S >> 3 == kOrdinary) return (const void*)k_advance<T, M, ISO, LDS, false, NOFLAT>;
+    else if constexpr (FLAVOUR == kPerRay) return (const void*)k_advance<T, M, ISO, false, true>;
+    else if constexpr (FLAVOUR == kOrdinary) return (const void*)k_advance<T, M, ISO, LDS, false, NOFLAT>;
     else if constexpr (sizeof(T) == 8 && (M == 2 || M == 6) && LDS) return (const void*)k_advance_lat<T, M, ISO, NOFLAT>;
     else return nullptr;
 }

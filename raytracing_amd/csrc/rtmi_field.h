@@ -22,6 +22,8 @@ struct rtmi_field {
     long flat_cells = 0;         // cells the map marks flat
     double gmax = 0;             // the largest gradient-spline coefficient of the grid in magnitude (k_absmax)
     long steep_cells = 0;        // fp64 fields: cells whose map entry carries a steepness (k_polytab); with neither kind the kernels never look at the map
+    int layered = 0;             // 1: the samples do not depend on x and the fast-form step kernels look the field up by its row alone (rtmi.h, rtmi_field_layered);
+                                 // the row table then sits in the map's region, rt::kLayerStride * (row + 1) elements in front of poly
     double* rdiv = nullptr;      // [qx][24] then [qy][24]: reciprocals of the knot differences fpbspl divides by, knots, differences (rt_exact.h, AxisTab)
     hipStream_t stream = nullptr;
 };

@@ -218,6 +218,20 @@ class Field:
         check(lib().rtmi_debug_field_lookup(self._h, len(x), dptr(x), dptr(y), dptr(n), dptr(gx), dptr(gy)))
         return n, gx, gy
 
+    @property
+    def layered(self):
+        """1 when the medium depends on y alone and the fast-form fp64 step kernels look it up by the row (rtmi_field_layered)."""
+        return int(lib().rtmi_field_layered(self._h))
+
+    def lookup_layered(self, x, y):
+        """The lookup of an x-invariant field by its row alone, as the step kernels make it (rtmi_debug_field_lookup_layered)
+        -> n, dn/dx (+0), dn/dy.  Raises for a field that is not x-invariant."""
+        x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.float64)
+        y = np.ascontiguousarray(np.atleast_1d(y), dtype=np.float64)
+        n = np.empty_like(x); gx = np.empty_like(x); gy = np.empty_like(x)
+        check(lib().rtmi_debug_field_lookup_layered(self._h, len(x), dptr(x), dptr(y), dptr(n), dptr(gx), dptr(gy)))
+        return n, gx, gy
+
     def dgrad(self, x, y):
         """The Jacobian of the gradient as rtmi_paraxial evaluates it (rtmi_field_eval_dgrad): the derivatives of the cell
         polynomials of the two gradient fits -> d(dn/dx)/dx, d(dn/dx)/dy, d(dn/dy)/dx, d(dn/dy)/dy."""
