@@ -626,7 +626,8 @@ int rtmi_gaussian_beams(rtmi_batch *b, int32_t fan_size, const rtmi_beam_params 
  * theta or a dopen that is not finite and > 0; an index outside [0, P); a w that is not finite.  Null handle or buffer in the
  * other calls: RTMI_ERR_ARG.
  * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), anti-alias filtering of steep
- * operators, later arrivals (the tables are first arrivals), fp32 storage, device-resident data and image buffers, several GPUs. */
+ * operators, fp32 storage, device-resident data and image buffers, several GPUs.  Several arrivals per node and their caustic
+ * phase: rtmi_kirchhoff_create_multi below. */
 typedef struct rtmi_kirchhoff rtmi_kirchhoff;
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, reserved0; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_params;
 typedef struct {
@@ -643,6 +644,45 @@ int rtmi_kirchhoff_create(const rtmi_kirchhoff_params *kp, const double *T, cons
 int rtmi_kirchhoff_migrate(rtmi_kirchhoff *k, const double *data, double *image, rtmi_kirchhoff_stats *st);  /* [N][nt] -> [nb][ny][nx] */
 int rtmi_kirchhoff_model(rtmi_kirchhoff *k, const double *model, double *data, rtmi_kirchhoff_stats *st);    /* [nb][ny][nx] -> [N][nt] */
 void rtmi_kirchhoff_destroy(rtmi_kirchhoff *k);
+
+/* The same pair over several arrivals per node, each pair of a source and a receiver arrival rotated by the phase its caustic
+ * count implies.  DESIGN.md section 19.  Inputs as above, except:
+ *   tables   T [P][K][ny][nx], and optionally amp, theta and kmah of that shape (host fp64; the [S, K, ny, nx] layout of
+ *            rtmi_arrival_grid's T, G, theta and kmah columns), K = karr in 1 .. RTMI_KIRCHHOFF_MAX_ARRIVALS.  A slot a node
+ *            does not have is NaN in T, as rtmi_arrival_grid leaves it.  kmah holds integer-valued doubles; the handle keeps
+ *            kmah mod 4 as int8 on the device.
+ *   traces   two channels of [N][nt]: channel 0 is the trace, channel 1 the channel that gets Hilbert-transformed: the full trace
+ *            is d = ch0 + H ch1, H the Hilbert transform with H[cos] = sin (the imaginary part of the analytic signal).  H is the
+ *            caller's (a global filter along t); the operator pair below is between the model and the two channels.
+ * For trace k, node x and the arrivals ks = 0 .. K-1 of table s = isrc[k] (outer loop) and kr = 0 .. K-1 of table r = irec[k]
+ * (inner loop): tau, f, j, a, c and b exactly as above from T[s][ks][x], T[r][kr][x] and the amp and theta of those two slots.
+ *     with kmah:  m = kmah[s][ks][x] + kmah[r][kr][x],  q = m mod 4        without:  q = 0
+ * The pair contributes iff the conditions above hold and, with kmah, both values are finite, non-negative and integer-valued.
+ * Phase.  The convention is rtmi_paraxial's and rtmi_gaussian_beams': exp(-i omega t), an arrival ~ exp(i (omega T - kmah pi/2)):
+ * each caustic retards the phase by pi/2.  A pulse s(t - tau) therefore arrives as
+ *     q = 0:  +s   (channel 0, sign +)        q = 1:  -Hs  (channel 1, sign -)
+ *     q = 2:  -s   (channel 0, sign -)        q = 3:  +Hs  (channel 1, sign +)
+ * four exact cases: a channel and a sign, no trigonometry.  With ch and sg the pair's channel and sign:
+ *   migrate2  image[b][x] += sg * (c * (ch[k][j] + a * (ch[k][j+1] - ch[k][j]))), accumulated per (b, x) in fp64 in the order k
+ *             ascending, then ks, then kr, starting from 0; a pair that does not contribute adds +0.  No atomics: a plain loop
+ *             reproduces the image bit for bit.  data1 may be NULL only if the handle has no kmah (it is not read then).
+ *   model2    ch[k][j] += sg * ((c * m[b][x]) * (1 - a)) and ch[k][j+1] += sg * ((c * m[b][x]) * a), starting from 0, in the
+ *             fixed-point scheme of rtmi_kirchhoff_model with the same scale_exp (the bound on one contribution is the same; a
+ *             sample now receives up to 2 K^2 contributions per node, 2^36 in all at most, below 2^94 quanta: two words still
+ *             hold it).  The same bits in every trace order and on every run.  data1 may be NULL only if the handle has no kmah;
+ *             without kmah a data1 that is given comes back as zeros.
+ * With K = 1 and no kmah the pair is rtmi_kirchhoff_migrate / _model, bit for bit.  The handle is destroyed by
+ * rtmi_kirchhoff_destroy.  rtmi_kirchhoff_migrate / _model on a handle of create_multi, and migrate2 / model2 on a handle of
+ * rtmi_kirchhoff_create, return RTMI_ERR_ARG.  Refused before any device work as above, and also: karr outside 1 .. 4; a null
+ * data1 on a handle that has kmah.  stats: pairs = N nx ny K^2.
+ * Not covered: the 2-D half-derivative / pi/4 filter and H itself (the caller filters), anti-alias filtering, fp32 tables,
+ * K > 4. */
+#define RTMI_KIRCHHOFF_MAX_ARRIVALS 4
+typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_multi_params;
+int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params *kp, const double *T, const double *amp, const double *theta,
+                                const double *kmah, const int32_t *isrc, const int32_t *irec, const double *w, rtmi_kirchhoff **out);
+int rtmi_kirchhoff_migrate2(rtmi_kirchhoff *k, const double *data0, const double *data1, double *image, rtmi_kirchhoff_stats *st);
+int rtmi_kirchhoff_model2(rtmi_kirchhoff *k, const double *model, double *data0, double *data1, rtmi_kirchhoff_stats *st);
 
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */

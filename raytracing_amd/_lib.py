@@ -110,6 +110,16 @@ class KirchhoffParams(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+class KirchhoffMultiParams(C.Structure):
+    """rtmi_kirchhoff_multi_params: KirchhoffParams with karr where that has reserved0"""
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("P", C.c_int64), ("N", C.c_int64), ("nt", C.c_int64),
+                ("t0", C.c_double), ("dt", C.c_double), ("nbin", C.c_int32), ("karr", C.c_int32), ("dopen", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+
+KIRCHHOFF_MAX_ARRIVALS = 4
+
+
 class KirchhoffStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("upload_ms", C.c_double), ("pairs", C.c_int64), ("contributing", C.c_int64),
                 ("scale_exp", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
@@ -167,6 +177,10 @@ SYMBOLS = {
     "rtmi_kirchhoff_migrate": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(KirchhoffStats)]),
     "rtmi_kirchhoff_model": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(KirchhoffStats)]),
     "rtmi_kirchhoff_destroy": (None, [C.c_void_p]),
+    "rtmi_kirchhoff_create_multi": (C.c_int, [C.POINTER(KirchhoffMultiParams), _dp, _dp, _dp, _dp, _ip, _ip, _dp,
+                                              C.POINTER(C.c_void_p)]),
+    "rtmi_kirchhoff_migrate2": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_model2": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(KirchhoffStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -9,6 +9,10 @@
 //        nodes, round each contribution once to an integer number of quanta 2^scale_exp and add it with a returning 64-bit LDS
 //        atomic (the carry into the high word is read off the returned old value: rt_fix128.h).  Integer sums
 //        commute, so the result has the same bits in every schedule and trace order.  The block converts and stores its trace.
+// Several arrivals per node (rtmi_kirchhoff_create_multi / _migrate2 / _model2): tables [P][K][nn], a trace
+// meets a node in K^2 pairs of a source and a receiver arrival, each rotated by the phase of its caustic count -- a choice of
+// one of two trace channels and a sign.  k_migrate_multi and k_model_multi are the two kernels above with the pair loops
+// unrolled over the template parameter K: the 2 K table values of a (trace, node) are loaded once and serve its K^2 pairs.
 // The tables and the geometry live on the device in the handle; data and image cross the bus on every call.
 #include <hip/hip_runtime.h>
 
@@ -180,6 +184,207 @@ __global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, dou
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ several arrivals
+// kmah on the device: the caustic count mod 4 as int8, -1 where the table's value is not a finite non-negative integer.
+constexpr int8_t kBadKmah = -1;
+
+// The K arrivals of one table at one node.  Absent columns are never read.
+template <int K> struct Arr { double T[K], A[K], H[K]; int m[K]; };
+
+template <int K, bool AMP, bool BINS, bool PHASE>
+__device__ __forceinline__ void load_arr(const KArgs& A, const int8_t* __restrict__ kmah, size_t at, Arr<K>& o) {
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        const size_t q = at + (size_t)i * A.nn;
+        o.T[i] = A.T[q];
+        o.A[i] = AMP ? A.amp[q] : 0.0;
+        o.H[i] = BINS ? A.theta[q] : 0.0;
+        o.m[i] = PHASE ? (int)kmah[q] : 0;
+    }
+}
+
+// The phase of a pair from its two counts: valid iff neither is kBadKmah; q = (ms + mr) mod 4 picks the channel (odd: 1) and the
+// sign (q = 1, 2: minus), rtmi.h's table.
+struct Phase { bool valid, odd, neg; };
+__device__ __forceinline__ Phase phase_of(int ms, int mr) {
+    const int q = ms + mr;
+    return Phase{(ms | mr) >= 0, (q & 1) != 0, ((q + 1) & 2) != 0};
+}
+
+// L^T.  data0, data1 [N][nt] (data1 is read only with PHASE); image [nb][nn]; counts [gridDim.x].  The sum runs over k, then ks,
+// then kr, as rtmi.h defines it.  All K^2 gathers of a trace are issued before the first add, outside the `contributes` test.
+template <int K, bool AMP, bool BINS, bool PHASE>
+__global__ void __launch_bounds__(256) k_migrate_multi(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ data0,
+                                const double* __restrict__ data1, double* __restrict__ image, unsigned long long* __restrict__ counts) {
+    extern __shared__ double acc[];                           // BINS: [nb][blockDim.x]
+    __shared__ unsigned long long wcnt[4];
+    constexpr int KK = K * K;
+    constexpr int kUnroll = K == 1 ? 4 : K == 2 ? 2 : 1;      // pairs in flight: 4, 8, 9, 16
+    const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
+    const long x0 = (long)blockIdx.x * BS + tid;
+    const bool in = x0 < A.nn;
+    const long x = in ? x0 : A.nn - 1;
+    double sum = 0.0;
+    if (BINS)
+        for (int b = 0; b < A.nb; b++) acc[b * BS + tid] = 0.0;
+    unsigned long long cnt = 0;
+    int sprev = -1;
+    Arr<K> S;
+#pragma unroll
+    for (int i = 0; i < K; i++) { S.T[i] = 0.0; S.A[i] = 0.0; S.H[i] = 0.0; S.m[i] = 0; }
+#pragma unroll kUnroll
+    for (long k = 0; k < A.N; k++) {
+        const int s = A.isrc[k], r = A.irec[k];
+        const double wk = A.w[k];
+        if (s != sprev) {                                     // wave-uniform, as in k_migrate
+            load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)s * K * A.nn + x, S);
+            sprev = s;
+        }
+        Arr<K> R;
+        load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)r * K * A.nn + x, R);
+        Pair p[KK];
+        bool neg[KK];
+        double d0[KK], d1[KK];
+#pragma unroll
+        for (int i = 0; i < KK; i++) {
+            const int ks = i / K, kr = i % K;
+            p[i] = pair_of<AMP, BINS>(A, S.T[ks], R.T[kr], S.A[ks], R.A[kr], S.H[ks], R.H[kr], wk);
+            const double* ch = data0;
+            neg[i] = false;
+            if (PHASE) {
+                const Phase ph = phase_of(S.m[ks], R.m[kr]);
+                p[i].ok = p[i].ok && ph.valid;
+                neg[i] = ph.neg;
+                ch = ph.odd ? data1 : data0;
+            }
+            const double* d = ch + (size_t)k * A.nt + p[i].j; // j = 0 when the range test failed: always in bounds
+            d0[i] = d[0];
+            d1[i] = d[1];
+        }
+#pragma unroll
+        for (int i = 0; i < KK; i++) {
+            const double cv = p[i].c * (d0[i] + p[i].a * (d1[i] - d0[i]));
+            const double v = neg[i] ? -cv : cv;
+            if (BINS) {
+                if (p[i].ok) acc[p[i].b * BS + tid] += v;
+            } else {
+                sum += p[i].ok ? v : 0.0;                     // sum is never -0: adding +0 changes no bit
+            }
+            cnt += (p[i].ok && in) ? 1ull : 0ull;
+        }
+    }
+    if (in) {
+        if (BINS)
+            for (int b = 0; b < A.nb; b++) image[(size_t)b * A.nn + x] = acc[b * BS + tid];
+        else
+            image[x] = sum;
+    }
+    cnt = wave_sum(cnt);
+    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t = 0;
+        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
+        counts[blockIdx.x] = t;
+    }
+}
+
+// L.  One block per trace; data0, data1 [N][nt] (data1 is written only with PHASE); counts [N].  Channel c's accumulators are
+// lo = fix + 2 c W, hi = lo + W; windows of W samples as in k_model.  Two channels double a block's LDS, which halves the blocks
+// a CU holds: the host launches 512 lanes with PHASE, so that the waves per CU stay what they were (any block size gives the
+// same bits).
+template <int K, bool AMP, bool BINS, bool PHASE>
+__global__ void __launch_bounds__(512) k_model_multi(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ m, int e, int W,
+                              double* __restrict__ data0, double* __restrict__ data1, unsigned long long* __restrict__ counts) {
+    extern __shared__ unsigned long long fix[];               // lo0 [W], hi0 [W] and, PHASE, lo1 [W], hi1 [W]
+    __shared__ unsigned long long wcnt[8];
+    constexpr int KK = K * K;
+    constexpr int kChannels = PHASE ? 2 : 1;
+    const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
+    const long k = blockIdx.x;
+    const int s = A.isrc[k], r = A.irec[k];
+    const double wk = A.w[k];
+    unsigned long long cnt = 0;
+    for (long j0 = 0; j0 < A.nt; j0 += W) {
+        const long j1 = (j0 + W < A.nt) ? j0 + W : A.nt;      // the window [j0, j1)
+        for (int i = tid; i < 2 * kChannels * W; i += BS) fix[i] = ((i / W) & 1) ? 0ull : rt::kFixBias;
+        __syncthreads();
+        for (long x = tid; x < A.nn; x += BS) {
+            Arr<K> S, R;
+            load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)s * K * A.nn + x, S);
+            load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)r * K * A.nn + x, R);
+            const double mx = BINS ? 0.0 : m[x];
+#pragma unroll
+            for (int i = 0; i < KK; i++) {
+                const int ks = i / K, kr = i % K;
+                Pair p = pair_of<AMP, BINS>(A, S.T[ks], R.T[kr], S.A[ks], R.A[kr], S.H[ks], R.H[kr], wk);
+                Phase ph{true, false, false};
+                if (PHASE) ph = phase_of(S.m[ks], R.m[kr]);
+                if (!(p.ok && ph.valid)) continue;
+                if (j0 == 0) cnt++;
+                if (p.j + 1 < j0 || p.j >= j1) continue;
+                const double cm = p.c * (BINS ? m[(size_t)p.b * A.nn + x] : mx);
+                if (!(fabs(cm) < INFINITY)) continue;         // a non-finite model value contributes nothing
+                const double u0 = cm * (1.0 - p.a), u1 = cm * p.a;
+                const double v0 = ph.neg ? -u0 : u0, v1 = ph.neg ? -u1 : u1;
+                unsigned long long* lo = fix + (ph.odd ? 2 * W : 0);
+                unsigned long long* hi = lo + W;
+                if (p.j >= j0) (void)rt::add128(lo, hi, (int)(p.j - j0), (long long)rint(ldexp(v0, -e)));
+                if (p.j + 1 < j1) (void)rt::add128(lo, hi, (int)(p.j + 1 - j0), (long long)rint(ldexp(v1, -e)));
+            }
+        }
+        __syncthreads();
+        for (long i = tid; i < j1 - j0; i += BS) {
+            data0[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(fix[i], fix[W + i]), e);
+            if (PHASE) data1[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(fix[2 * W + i], fix[3 * W + i]), e);
+        }
+        __syncthreads();
+    }
+    cnt = wave_sum(cnt);
+    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t = 0;
+        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
+        counts[k] = t;
+    }
+}
+
+// The kernel of (karr, amp, bins, phase): the flags become template arguments one at a time.
+struct MultiLaunch {
+    dim3 grid, blk;
+    size_t lds;
+    KArgs A;
+    const int8_t* kmah;
+    const double* in0;      // migrate: data0; model: the model
+    const double* in1;      // migrate: data1
+    double *out0, *out1;    // migrate: image, -; model: data0, data1
+    int e, W;
+    unsigned long long* counts;
+};
+template <bool MODEL, int K, bool... F>
+void launch_multi(const bool* f, const MultiLaunch& L) {
+    if constexpr (sizeof...(F) == 3) {
+        if constexpr (MODEL)
+            hipLaunchKernelGGL((k_model_multi<K, F...>), L.grid, L.blk, L.lds, nullptr, L.A, L.kmah, L.in0, L.e, L.W, L.out0, L.out1, L.counts);
+        else
+            hipLaunchKernelGGL((k_migrate_multi<K, F...>), L.grid, L.blk, L.lds, nullptr, L.A, L.kmah, L.in0, L.in1, L.out0, L.counts);
+    } else {
+        if (*f) launch_multi<MODEL, K, F..., true>(f + 1, L);
+        else launch_multi<MODEL, K, F..., false>(f + 1, L);
+    }
+}
+template <bool MODEL>
+void launch_multi(int karr, bool amp, bool bins, bool phase, const MultiLaunch& L) {
+    const bool f[3] = {amp, bins, phase};
+    switch (karr) {
+        case 1: launch_multi<MODEL, 1>(f, L); break;
+        case 2: launch_multi<MODEL, 2>(f, L); break;
+        case 3: launch_multi<MODEL, 3>(f, L); break;
+        default: launch_multi<MODEL, 4>(f, L); break;
+    }
+}
+
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -189,14 +394,16 @@ double now_ms() {
 struct rtmi_kirchhoff {
     rtmi_kirchhoff_params kp{};
     int device = 0, nb = 1;
+    int karr = 0;                             // 0: rtmi_kirchhoff_create's handle; K >= 1: create_multi's, tables [P][K][nn]
     size_t nn = 0;
     double max_w = 1.0, max_amp = 1.0;        // over finite values; the order-independent bound of the fixed-point scale
     double *T = nullptr, *amp = nullptr, *theta = nullptr, *w = nullptr, *data = nullptr, *image = nullptr;
     int32_t *isrc = nullptr, *irec = nullptr;
+    int8_t* kmah = nullptr;                   // multi: [P][K][nn], the count mod 4 or kBadKmah; NULL without kmah
     unsigned long long* counts = nullptr;     // max(N, migrate's blocks)
     size_t ncounts = 0;
     ~rtmi_kirchhoff() {
-        for (void* p : {(void*)T, (void*)amp, (void*)theta, (void*)w, (void*)data, (void*)image, (void*)isrc, (void*)irec, (void*)counts})
+        for (void* p : {(void*)T, (void*)amp, (void*)theta, (void*)w, (void*)data, (void*)image, (void*)isrc, (void*)irec, (void*)kmah, (void*)counts})
             if (p) (void)hipFree(p);
     }
     KArgs args() const {
@@ -227,12 +434,11 @@ int read_counts(const rtmi_kirchhoff* k, size_t n, int64_t* total, const char* w
 
 }  // namespace
 
-RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const double* T, const double* amp, const double* theta,
-                                      const int32_t* isrc, const int32_t* irec, const double* w, rtmi_kirchhoff** out) {
-    const char* who = "rtmi_kirchhoff_create";
-    RTMI_ARG(out, "null out");
-    *out = nullptr;
-    RTMI_ARG(kp, "null kp");
+namespace {
+
+// Both creates.  karr = 0: rtmi_kirchhoff_create (tables [P][nn], no kmah); karr >= 1: create_multi (tables [P][karr][nn]).
+int create_impl(const char* who, const rtmi_kirchhoff_params* kp, int karr, const double* T, const double* amp, const double* theta,
+                const double* kmah, const int32_t* isrc, const int32_t* irec, const double* w, rtmi_kirchhoff** out) {
     RTMI_ARG(T, "null T");
     RTMI_ARG(isrc, "null isrc");
     RTMI_ARG(irec, "null irec");
@@ -263,7 +469,8 @@ RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const dou
             max_w = std::fmax(max_w, std::fabs(w[k]));
         }
     }
-    const size_t nn = (size_t)kp->nx * (size_t)kp->ny, P = (size_t)kp->P, N = (size_t)kp->N, nt = (size_t)kp->nt;
+    const size_t nn = (size_t)kp->nx * (size_t)kp->ny, N = (size_t)kp->N, nt = (size_t)kp->nt;
+    const size_t P = (size_t)kp->P * (size_t)(karr > 0 ? karr : 1);        // tables of nn nodes
     const int nb = kp->nbin > 0 ? kp->nbin : 1;
     double max_amp = 1.0;
     if (amp) {
@@ -274,6 +481,7 @@ RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const dou
     rtmi_kirchhoff* k = new (std::nothrow) rtmi_kirchhoff;
     if (!k) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_kirchhoff_create: out of host memory");
     k->kp = *kp;
+    k->karr = karr;
     k->nb = nb;
     k->nn = nn;
     k->max_w = max_w;
@@ -295,7 +503,8 @@ RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const dou
         {(void**)&k->isrc, N * sizeof(int32_t), isrc},
         {(void**)&k->irec, N * sizeof(int32_t), irec},
         {(void**)&k->w, N * sizeof(double), nullptr},
-        {(void**)&k->data, N * nt * sizeof(double), nullptr},
+        {(void**)&k->kmah, kmah ? P * nn * sizeof(int8_t) : 0, nullptr},
+        {(void**)&k->data, (kmah ? 2 : 1) * N * nt * sizeof(double), nullptr},     // with kmah: channel 0, then channel 1
         {(void**)&k->image, (size_t)nb * nn * sizeof(double), nullptr},
         {(void**)&k->counts, k->ncounts * sizeof(unsigned long long), nullptr},
     };
@@ -312,8 +521,43 @@ RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const dou
     if (!w) ones.assign(N, 1.0);
     e = hipMemcpy(k->w, w ? w : ones.data(), N * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    if (kmah) {
+        std::vector<int8_t> km(P * nn);
+        for (size_t i = 0; i < P * nn; i++) {
+            const double v = kmah[i];
+            km[i] = (std::isfinite(v) && v >= 0.0 && v == std::floor(v)) ? (int8_t)std::fmod(v, 4.0) : kBadKmah;
+        }
+        e = hipMemcpy(k->kmah, km.data(), P * nn * sizeof(int8_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
     *out = k;
     return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const double* T, const double* amp, const double* theta,
+                                      const int32_t* isrc, const int32_t* irec, const double* w, rtmi_kirchhoff** out) {
+    const char* who = "rtmi_kirchhoff_create";
+    RTMI_ARG(out, "null out");
+    *out = nullptr;
+    RTMI_ARG(kp, "null kp");
+    return create_impl(who, kp, 0, T, amp, theta, nullptr, isrc, irec, w, out);
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params* mp, const double* T, const double* amp,
+                                            const double* theta, const double* kmah, const int32_t* isrc, const int32_t* irec,
+                                            const double* w, rtmi_kirchhoff** out) {
+    const char* who = "rtmi_kirchhoff_create_multi";
+    RTMI_ARG(out, "null out");
+    *out = nullptr;
+    RTMI_ARG(mp, "null kp");
+    RTMI_ARG(mp->karr >= 1 && mp->karr <= RTMI_KIRCHHOFF_MAX_ARRIVALS, "karr must be in 1..4");
+    rtmi_kirchhoff_params kp{};
+    kp.nx = mp->nx; kp.ny = mp->ny; kp.P = mp->P; kp.N = mp->N; kp.nt = mp->nt;
+    kp.t0 = mp->t0; kp.dt = mp->dt; kp.nbin = mp->nbin; kp.dopen = mp->dopen;
+    RTMI_ARG(kp.P <= INT32_MAX / RTMI_KIRCHHOFF_MAX_ARRIVALS, "P karr must fit the int32 indices");
+    return create_impl(who, &kp, mp->karr, T, amp, theta, kmah, isrc, irec, w, out);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_migrate(rtmi_kirchhoff* k, const double* data, double* image, rtmi_kirchhoff_stats* st) {
@@ -321,6 +565,7 @@ RTMI_EXPORT int rtmi_kirchhoff_migrate(rtmi_kirchhoff* k, const double* data, do
     RTMI_ARG(k, "null handle");
     RTMI_ARG(data, "null data");
     RTMI_ARG(image, "null image");
+    RTMI_ARG(k->karr == 0, "the handle is rtmi_kirchhoff_create_multi's: call rtmi_kirchhoff_migrate2");
     RTMI_RC(check_device(k, who));
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
     const double t_up = now_ms();
@@ -357,6 +602,7 @@ RTMI_EXPORT int rtmi_kirchhoff_model(rtmi_kirchhoff* k, const double* model, dou
     RTMI_ARG(k, "null handle");
     RTMI_ARG(model, "null model");
     RTMI_ARG(data, "null data");
+    RTMI_ARG(k->karr == 0, "the handle is rtmi_kirchhoff_create_multi's: call rtmi_kirchhoff_model2");
     RTMI_RC(check_device(k, who));
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
     // the quantum: |contribution| <= max|w| max|amp|^2 max|m| = f 2^ex with f in [0.5, 1), so it is below 2^57 quanta 2^(ex - 57)
@@ -389,6 +635,106 @@ RTMI_EXPORT int rtmi_kirchhoff_model(rtmi_kirchhoff* k, const double* model, dou
         RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
         st->upload_ms = upload_ms;
         st->pairs = (int64_t)(N * nn);
+        st->scale_exp = e;
+        RTMI_RC(read_counts(k, N, &st->contributing, who));
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_migrate2(rtmi_kirchhoff* k, const double* data0, const double* data1, double* image,
+                                        rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_migrate2";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(data0, "null data0");
+    RTMI_ARG(image, "null image");
+    RTMI_ARG(k->karr >= 1, "the handle is rtmi_kirchhoff_create's: call rtmi_kirchhoff_migrate");
+    RTMI_ARG(data1 || !k->kmah, "null data1 on a handle that has kmah");
+    RTMI_RC(check_device(k, who));
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
+    const bool phase = k->kmah != nullptr;
+    const double t_up = now_ms();
+    RTMI_HIP(hipMemcpy(k->data, data0, N * nt * sizeof(double), hipMemcpyHostToDevice));
+    if (phase) RTMI_HIP(hipMemcpy(k->data + N * nt, data1, N * nt * sizeof(double), hipMemcpyHostToDevice));
+    const double upload_ms = now_ms() - t_up;
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    const int BS = migrate_block(k->nb);
+    const bool bins = k->kp.nbin > 0;
+    MultiLaunch L{};
+    L.grid = dim3((unsigned)((nn + BS - 1) / BS));
+    L.blk = dim3(BS);
+    L.lds = bins ? (size_t)k->nb * BS * sizeof(double) : 0;
+    L.A = k->args();
+    L.kmah = k->kmah;
+    L.in0 = k->data;
+    L.in1 = phase ? k->data + N * nt : nullptr;
+    L.out0 = k->image;
+    L.counts = k->counts;
+    RTMI_HIP(ev.mark(0));
+    launch_multi<false>(k->karr, k->amp != nullptr, bins, phase, L);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    RTMI_HIP(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        *st = rtmi_kirchhoff_stats{};
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
+        st->upload_ms = upload_ms;
+        st->pairs = (int64_t)(N * nn) * k->karr * k->karr;
+        RTMI_RC(read_counts(k, L.grid.x, &st->contributing, who));
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_model2(rtmi_kirchhoff* k, const double* model, double* data0, double* data1, rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_model2";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(model, "null model");
+    RTMI_ARG(data0, "null data0");
+    RTMI_ARG(k->karr >= 1, "the handle is rtmi_kirchhoff_create's: call rtmi_kirchhoff_model");
+    RTMI_ARG(data1 || !k->kmah, "null data1 on a handle that has kmah");
+    RTMI_RC(check_device(k, who));
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
+    const bool phase = k->kmah != nullptr;
+    // the quantum: rtmi_kirchhoff_model's, from the same bound on one contribution (DESIGN.md 19 on the number of contributions)
+    double max_m = 0.0;
+    for (size_t i = 0; i < nm; i++)
+        if (std::isfinite(model[i])) max_m = std::fmax(max_m, std::fabs(model[i]));
+    const double bound = (k->max_w * k->max_amp) * k->max_amp * max_m;
+    const int e = std::isfinite(bound) ? rt::fix_exponent(bound) : 1025 - rt::kFixBits;
+    const double t_up = now_ms();
+    RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
+    const double upload_ms = now_ms() - t_up;
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    const size_t window = phase ? kWindow / 2 : kWindow;      // two channels share the 64 KiB
+    MultiLaunch L{};
+    L.W = (int)(nt < window ? nt : window);
+    L.e = e;
+    L.grid = dim3((unsigned)N);
+    L.blk = dim3(phase ? 512 : 256);
+    L.lds = (size_t)L.W * (phase ? 4 : 2) * sizeof(unsigned long long);
+    L.A = k->args();
+    L.kmah = k->kmah;
+    L.in0 = k->image;
+    L.out0 = k->data;
+    L.out1 = phase ? k->data + N * nt : nullptr;
+    L.counts = k->counts;
+    RTMI_HIP(ev.mark(0));
+    launch_multi<true>(k->karr, k->amp != nullptr, k->kp.nbin > 0, phase, L);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    RTMI_HIP(hipMemcpy(data0, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (data1) {
+        if (phase) RTMI_HIP(hipMemcpy(data1, k->data + N * nt, N * nt * sizeof(double), hipMemcpyDeviceToHost));
+        else std::memset(data1, 0, N * nt * sizeof(double));  // without kmah every pair is of channel 0
+    }
+    if (st) {
+        *st = rtmi_kirchhoff_stats{};
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
+        st->upload_ms = upload_ms;
+        st->pairs = (int64_t)(N * nn) * k->karr * k->karr;
         st->scale_exp = e;
         RTMI_RC(read_counts(k, N, &st->contributing, who));
     }

@@ -1170,23 +1170,47 @@ def kirchhoff_stats(st):
             "scale_exp": int(st.scale_exp)}
 
 
+def hilbert(d):
+    """The Hilbert transform along the last axis, H[cos] = sin: the imaginary part of scipy.signal.hilbert's analytic signal, by
+    numpy.fft with scipy's mask (DC and Nyquist zeroed, positive frequencies doubled).  Circular: the transform wraps around the
+    ends of the axis, so the caller pads a trace whose energy reaches them.  As a matrix it is a real antisymmetric circulant:
+    the transpose is -H up to rounding."""
+    d = np.asarray(d, dtype=np.float64)
+    n = d.shape[-1]
+    h = np.zeros(n)
+    if n % 2 == 0:
+        h[1:n // 2] = 2.0
+    else:
+        h[1:(n + 1) // 2] = 2.0
+    return np.fft.ifft(np.fft.fft(d, axis=-1) * h, axis=-1).imag
+
+
 class Kirchhoff:
-    """Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_*, include/rtmi.h; DESIGN.md 14).  T [P, ny, nx]:
+    """Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_*, include/rtmi.h; DESIGN.md 14, 19).  T [P, ny, nx]:
     traveltime_table's T for P surface positions; isrc, irec [N]: each trace's source and receiver position in [0, P); nt samples
     per trace at t0 + j dt; amp, theta [P, ny, nx] and weights [N] optional; nbin > 0 splits the image into opening-angle bins of
     width dopen (needs theta).  The tables stay on the device until close().
       migrate(data [N, nt]) -> image [nb, ny, nx] ([ny, nx] when nbin == 0), defined bit for bit by the trace order
       model(m)              -> data [N, nt], the transpose; the same bits in every trace order
       as_linear_operator()  scipy LinearOperator of shape (N nt, nb ny nx): matvec = model, rmatvec = migrate
-    With stats=True the calls return (result, stats)."""
+    With stats=True the calls return (result, stats).
+    A 4-D T [P, K, ny, nx] (traveltime_table(arrivals=K)'s layout; amp, theta and the optional kmah of that shape) makes a handle
+    over all K^2 pairs of a source and a receiver arrival, each rotated by its caustic phase (rtmi_kirchhoff_create_multi):
+      migrate_channels(d0, d1) -> image    and    model_channels(m) -> (ch0, ch1)
+    are the bit-defined transposes between the model and the two trace channels (d1 may be None, and ch1 is zeros, without kmah);
+    the full trace is ch0 + H ch1 with H = hilbert (circular: pad the traces), so on such a handle
+      model(m) = ch0 + hilbert(ch1)    and    migrate(d) = migrate_channels(d, -hilbert(d)),   its transpose since H^T = -H."""
 
-    def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None):
+    def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None, kmah=None):
         T = np.ascontiguousarray(T, dtype=np.float64)
-        if T.ndim != 3:
-            raise ValueError("Kirchhoff: T must be [P, ny, nx]")
-        P, ny, nx = T.shape
-        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (amp, theta)]
-        for a, name in zip(opt, ("amp", "theta")):
+        if T.ndim not in (3, 4):
+            raise ValueError("Kirchhoff: T must be [P, ny, nx] or [P, K, ny, nx]")
+        self.karr = T.shape[1] if T.ndim == 4 else 0
+        if kmah is not None and not self.karr:
+            raise ValueError("Kirchhoff: kmah needs T [P, K, ny, nx]")
+        P, ny, nx = T.shape[0], T.shape[-2], T.shape[-1]
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (amp, theta, kmah)]
+        for a, name in zip(opt, ("amp", "theta", "kmah")):
             if a is not None and a.shape != T.shape:
                 raise ValueError(f"Kirchhoff: {name} must have T's shape")
         si = np.ascontiguousarray(isrc, dtype=np.int32).reshape(-1)
@@ -1196,22 +1220,31 @@ class Kirchhoff:
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w is not None and w.shape != si.shape:
             raise ValueError("Kirchhoff: weights must have isrc's length")
-        kp = _lib.KirchhoffParams()
+        kp = _lib.KirchhoffMultiParams() if self.karr else _lib.KirchhoffParams()
         kp.nx, kp.ny, kp.P, kp.N, kp.nt = nx, ny, P, len(si), int(nt)
         kp.t0 = float(t0); kp.dt = float(dt); kp.nbin = int(nbin); kp.dopen = float(dopen or 0.0)
         self.N, self.nt, self.nb, self.nbin, self.ny, self.nx = len(si), int(nt), max(int(nbin), 1), int(nbin), ny, nx
         self.shape = (self.N * self.nt, self.nb * ny * nx)
+        self.has_kmah = kmah is not None
         self._h = None
         h = C.c_void_p()
-        check(lib().rtmi_kirchhoff_create(C.byref(kp), dptr(T), dptr(opt[0]), dptr(opt[1]), si.ctypes.data_as(_lib._ip),
-                                          ri.ctypes.data_as(_lib._ip), dptr(w), C.byref(h)))
+        if self.karr:
+            kp.karr = self.karr
+            check(lib().rtmi_kirchhoff_create_multi(C.byref(kp), dptr(T), dptr(opt[0]), dptr(opt[1]), dptr(opt[2]),
+                                                    si.ctypes.data_as(_lib._ip), ri.ctypes.data_as(_lib._ip), dptr(w), C.byref(h)))
+        else:
+            check(lib().rtmi_kirchhoff_create(C.byref(kp), dptr(T), dptr(opt[0]), dptr(opt[1]), si.ctypes.data_as(_lib._ip),
+                                              ri.ctypes.data_as(_lib._ip), dptr(w), C.byref(h)))
         self._h = h
 
     @classmethod
     def from_table(cls, tab, isrc, irec, nt, dt, t0=0.0, amplitude=False, weights=None, nbin=0, dopen=None):
-        """From traveltime_table's dict: its T, its theta when nbin > 0, and its G as amp when amplitude is asked for."""
+        """From traveltime_table's dict: its T, its theta when nbin > 0, and its G as amp when amplitude is asked for; with
+        arrivals=K tables (a 4-D T) also its kmah whenever the dict has one."""
+        multi = np.ndim(tab["T"]) == 4
         return cls(tab["T"], isrc, irec, nt, dt, t0=t0, amp=tab["G"] if amplitude else None,
-                   theta=tab["theta"] if nbin else None, weights=weights, nbin=nbin, dopen=dopen)
+                   theta=tab["theta"] if nbin else None, weights=weights, nbin=nbin, dopen=dopen,
+                   kmah=tab["kmah"] if multi and "kmah" in tab else None)
 
     def _open(self):
         if not self._h:
@@ -1219,6 +1252,9 @@ class Kirchhoff:
         return self._h
 
     def migrate(self, data, stats=False):
+        if self.karr:
+            d = np.ascontiguousarray(data, dtype=np.float64).reshape(self.N, self.nt)
+            return self.migrate_channels(d, -hilbert(d) if self.has_kmah else None, stats=stats)
         d = np.ascontiguousarray(data, dtype=np.float64)
         if d.size != self.N * self.nt:
             raise ValueError("Kirchhoff.migrate: data must be [N, nt]")
@@ -1230,6 +1266,10 @@ class Kirchhoff:
         return (img, kirchhoff_stats(st)) if stats else img
 
     def model(self, m, stats=False):
+        if self.karr:
+            (c0, c1), st = self.model_channels(m, stats=True)
+            d = c0 + hilbert(c1) if self.has_kmah else c0
+            return (d, st) if stats else d
         mm = np.ascontiguousarray(m, dtype=np.float64)
         if mm.size != self.nb * self.ny * self.nx:
             raise ValueError("Kirchhoff.model: m must be [nb, ny, nx]")
@@ -1237,6 +1277,34 @@ class Kirchhoff:
         st = _lib.KirchhoffStats()
         check(lib().rtmi_kirchhoff_model(self._open(), dptr(mm), dptr(d), C.byref(st)))
         return (d, kirchhoff_stats(st)) if stats else d
+
+    def _multi(self, who):
+        if not self.karr:
+            raise ValueError(f"Kirchhoff.{who}: the handle has one arrival per node (T [P, ny, nx]); use migrate / model")
+
+    def migrate_channels(self, d0, d1=None, stats=False):
+        """rtmi_kirchhoff_migrate2: (channel 0, channel 1) [N, nt] each -> image; d1 may be None only without kmah"""
+        self._multi("migrate_channels")
+        d = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (d0, d1)]
+        if any(a is not None and a.size != self.N * self.nt for a in d) or d[0] is None:
+            raise ValueError("Kirchhoff.migrate_channels: each channel must be [N, nt]")
+        img = np.empty((self.nb, self.ny, self.nx))
+        st = _lib.KirchhoffStats()
+        check(lib().rtmi_kirchhoff_migrate2(self._open(), dptr(d[0]), dptr(d[1]), dptr(img), C.byref(st)))
+        if self.nbin == 0:
+            img = img[0]
+        return (img, kirchhoff_stats(st)) if stats else img
+
+    def model_channels(self, m, stats=False):
+        """rtmi_kirchhoff_model2: m -> (channel 0, channel 1), [N, nt] each; channel 1 is zeros without kmah"""
+        self._multi("model_channels")
+        mm = np.ascontiguousarray(m, dtype=np.float64)
+        if mm.size != self.nb * self.ny * self.nx:
+            raise ValueError("Kirchhoff.model_channels: m must be [nb, ny, nx]")
+        d0 = np.empty((self.N, self.nt)); d1 = np.empty((self.N, self.nt))
+        st = _lib.KirchhoffStats()
+        check(lib().rtmi_kirchhoff_model2(self._open(), dptr(mm), dptr(d0), dptr(d1), C.byref(st)))
+        return ((d0, d1), kirchhoff_stats(st)) if stats else (d0, d1)
 
     def as_linear_operator(self):
         from scipy.sparse.linalg import LinearOperator

@@ -5,7 +5,12 @@ time (rtmi_kirchhoff_stats.kernel_ms) and the host wall time of the whole call (
 every table, trace and image access counted once, at 6 TB/s.  Also the numpy restatement's time on the tests' standard case,
 for contrast.  Each case runs in a child process of its own under a time limit, and the first failure ends the run.  Prints
 one JSON line per measurement.
-Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME]"""
+--arrivals K times the pair over several arrivals (rtmi_kirchhoff_migrate2 / _model2) on the same case, in one
+process with the one-arrival kernels it is measured against: the tables replicated into K slots, slot i later by 3 i ms so that
+the K^2 pairs of a (trace, node) are distinct and (nearly) all contribute; kmah = slot index.  It prints, for migrate and
+model: the one-arrival handle, K = 1 without kmah through the new kernels, and K slots without and with kmah, each with its
+time per pair relative to the one-arrival kernel.
+Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K]"""
 import argparse
 import json
 import os
@@ -74,6 +79,57 @@ def run_case(name, reps):
                       "scale_exp": st["scale_exp"]}), flush=True)
 
 
+def median_ms(call, reps):
+    call()                                                       # warm-up: code objects
+    ks = []
+    for _ in range(reps):
+        st = call()
+        ks.append(st["kernel_ms"])
+    return float(np.median(ks)), ks, st
+
+
+def run_arrivals(K, reps):
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, _ = tables(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    N, nn = len(isrc), T[0].size
+    rng = np.random.default_rng(1)
+    d0, d1 = rng.standard_normal((2, N, nt))
+    m = rng.standard_normal(T.shape[1:])
+    base = {}
+
+    def measure(what, op, karr, kmah):
+        for kind in ("migrate", "model"):
+            if kind == "migrate":
+                call = ((lambda: op.migrate_channels(d0, d1 if kmah else None, stats=True)[1]) if karr
+                        else (lambda: op.migrate(d0, stats=True)[1]))
+                nbytes = (N + len(src)) * max(karr, 1) * nn * (8 + kmah) + 8 * (N * nt * (1 + kmah) + nn)
+            else:
+                call = (lambda: op.model_channels(m, stats=True)[1]) if karr else (lambda: op.model(m, stats=True)[1])
+                nbytes = 2 * N * max(karr, 1) * nn * (8 + kmah) + 8 * (N * nn + N * nt * (1 + kmah))
+            k, ks, st = median_ms(call, reps)
+            per_pair = k / st["pairs"]
+            base.setdefault(kind, per_pair)                      # the one-arrival kernel is measured first
+            print(json.dumps({"what": f"{kind}, {what}", "arrivals": karr, "kmah": bool(kmah), "pairs": st["pairs"],
+                              "contributing": st["contributing"], "kernel_ms_median": k, "kernel_ms": ks, "bytes": nbytes,
+                              "floor_ms_at_6TBps": nbytes / 6e12 * 1e3, "pairs_per_s": st["pairs"] / (k * 1e-3),
+                              "ns_per_pair": per_pair * 1e6, "time_per_pair_vs_one_arrival_kernel": per_pair / base[kind]}), flush=True)
+        op.close()
+
+    measure("one-arrival handle (k_migrate / k_model)", rb.Kirchhoff(T, isrc, irec, nt, dt), 0, 0)
+    measure("K = 1 without kmah (k_migrate_multi / k_model_multi)", rb.Kirchhoff(T[:, None], isrc, irec, nt, dt), 1, 0)
+    TK = np.stack([T + 0.003 * i for i in range(K)], axis=1)
+    if K > 1:
+        measure(f"K = {K} without kmah", rb.Kirchhoff(TK, isrc, irec, nt, dt), K, 0)
+    km = np.broadcast_to(np.arange(K, dtype=np.float64)[None, :, None, None], TK.shape)
+    measure(f"K = {K} with kmah", rb.Kirchhoff(TK, isrc, irec, nt, dt, kmah=km), K, 1)
+
+
 def restatement():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import kirchhoff_ref as K
@@ -91,8 +147,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--case", choices=CASES + ("restatement",))
+    ap.add_argument("--arrivals", type=int, choices=(1, 2, 3, 4))
     a = ap.parse_args()
-    if a.case == "restatement":
+    if a.arrivals:
+        run_arrivals(a.arrivals, a.reps)
+    elif a.case == "restatement":
         restatement()
     elif a.case:
         run_case(a.case, a.reps)
