@@ -625,9 +625,9 @@ int rtmi_gaussian_beams(rtmi_batch *b, int32_t fan_size, const rtmi_beam_params 
  * irec or out; nx, ny, P, N < 1; nt < 2; nx ny > 2^31; dt or t0 not finite or dt <= 0; nbin < 0, nbin > 32; nbin > 0 with a null
  * theta or a dopen that is not finite and > 0; an index outside [0, P); a w that is not finite.  Null handle or buffer in the
  * other calls: RTMI_ERR_ARG.
- * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), anti-alias filtering of steep
- * operators, fp32 storage, device-resident data and image buffers, several GPUs.  Several arrivals per node and their caustic
- * phase: rtmi_kirchhoff_create_multi below. */
+ * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), fp32 storage, device-resident data
+ * and image buffers, several GPUs.  Several arrivals per node and their caustic phase: rtmi_kirchhoff_create_multi below;
+ * anti-alias filtering of steep operators: rtmi_kirchhoff_create_aa below. */
 typedef struct rtmi_kirchhoff rtmi_kirchhoff;
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, reserved0; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_params;
 typedef struct {
@@ -675,14 +675,63 @@ void rtmi_kirchhoff_destroy(rtmi_kirchhoff *k);
  * rtmi_kirchhoff_destroy.  rtmi_kirchhoff_migrate / _model on a handle of create_multi, and migrate2 / model2 on a handle of
  * rtmi_kirchhoff_create, return RTMI_ERR_ARG.  Refused before any device work as above, and also: karr outside 1 .. 4; a null
  * data1 on a handle that has kmah.  stats: pairs = N nx ny K^2.
- * Not covered: the 2-D half-derivative / pi/4 filter and H itself (the caller filters), anti-alias filtering, fp32 tables,
- * K > 4. */
+ * Not covered: the 2-D half-derivative / pi/4 filter and H itself (the caller filters), fp32 tables, K > 4. */
 #define RTMI_KIRCHHOFF_MAX_ARRIVALS 4
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_multi_params;
 int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params *kp, const double *T, const double *amp, const double *theta,
                                 const double *kmah, const int32_t *isrc, const int32_t *irec, const double *w, rtmi_kirchhoff **out);
 int rtmi_kirchhoff_migrate2(rtmi_kirchhoff *k, const double *data0, const double *data1, double *image, rtmi_kirchhoff_stats *st);
 int rtmi_kirchhoff_model2(rtmi_kirchhoff *k, const double *model, double *data0, double *data1, rtmi_kirchhoff_stats *st);
+
+/* The same pair, anti-aliased by operator slope: each (trace, node) pair reads, or spreads into, a copy of the trace that a
+ * triangle filter has smoothed the more, the more steeply the summation curve crosses neighbouring traces (a filter bank: Gray's
+ * method with triangle filters).  DESIGN.md section 20.  Inputs as for rtmi_kirchhoff_create_multi (tables [P][K][ny][nx], K = karr
+ * in 1 .. 4; K = 1 is also the layout of a one-arrival table [P][ny][nx]), and in addition:
+ *   pt       [P][K][ny][nx], of T's shape, required: dT/d(position coordinate) of each slot, time per length -- the derivative of
+ *            the traveltime with respect to the surface position along the line of positions.  By reciprocity it is
+ *            -n(p) (cos theta0 e_x + sin theta0 e_y) for a line of unit direction e, n(p) the refractive index at the position
+ *            and theta0 the slot's launch angle (rtmi_first_arrival_grid's and rtmi_arrival_grid's theta0 column).
+ *   lengths  asrc, arec, amid >= 0: the trace spacing along the source, receiver and midpoint axes; 0 switches that term off.  A
+ *            shot gather sets arec, a common-offset or zero-offset section amid.
+ *   levels   1 <= nlev <= RTMI_KIRCHHOFF_MAX_LEVELS half-widths hw[0] = 0 < hw[1] < ... < hw[nlev-1] <= 64, in samples.  Level l
+ *            is the trace filtered by the triangle of half-width k = hw[l]:
+ *                F_k x[j] = (sum over i = -k .. k with 0 <= j + i < nt of (k + 1 - |i|) * x[j+i]) * inv_k
+ *            inv_k = 1.0 / ((k + 1) (k + 1)) computed on the host, i ascending from a sum of 0.0, every product and add a separate
+ *            fp64 operation.  Samples outside the trace are left out, so F_k is a symmetric matrix.  Level 0 is the caller's
+ *            trace as given: no copy, no arithmetic.
+ * The pair of trace k, node x and arrivals ks, kr is rtmi_kirchhoff_migrate2's (tau, f, j, a, c, b, the phase, the order k, ks, kr),
+ * and with ps = pt[s][ks][x], pr = pt[r][kr][x], in this order and in separate fp64 operations:
+ *     q1 = fabs(ps) * asrc;  q2 = fabs(pr) * arec;  q3 = fabs(ps + pr) * amid
+ *     sl = fmax(fmax(q1, q2), q3) * inv_dt
+ *     l  = the smallest index with sl <= (double)hw[l], else nlev - 1
+ * The pair contributes iff migrate2's conditions hold and ps and pr are finite; a pair steeper than the last level contributes
+ * through the last level.
+ *   migrate2  on such a handle: image[b][x] += sg * (c * (B_l[k][j] + a * (B_l[k][j+1] - B_l[k][j]))) with B_l = F_hw[l] ch, in
+ *             migrate2's order: a plain loop reproduces the image bit for bit.
+ *   model2    on such a handle: the pair's two contributions go, in model2's fixed point with the same scale_exp, into the spread
+ *             S_l of its level and channel (one rounding to fp64 per sample of a spread); then
+ *                 ch[k][j] = S_0[k][j] + sum over l = 1 .. nlev - 1, ascending, of (F_hw[l] S_l[k])[j]        in fp64.
+ *             The spreads are exact integer sums and the final filter has one order: the same bits in every trace order and on
+ *             every run.  F_k is symmetric, so this is the transpose of migrate2 up to rounding.
+ * nlev = 1, or asrc = arec = amid = 0 with finite pt, is rtmi_kirchhoff_create_multi's pair bit for bit (image, traces,
+ * contributing, scale_exp).  stats: kernel_ms covers the filter and the pair kernel; reserved[0] is the device time, in
+ * nanoseconds, of the part that is not the pair kernel (migrate2: the bank's filter; model2: the sum over the levels).
+ * The handle holds [nlev][channels][N][nt] doubles on the device for the bank and the spreads (channels = 2 with kmah, else 1),
+ * allocated at create: RTMI_ERR_ALLOC if that fails.
+ * rtmi_kirchhoff_aa_filter returns the bank of one channel: bank[l] = F_hw[l] data, bank[0] = data.
+ * Refused before any device work, with rtmi_last_error naming the argument: everything rtmi_kirchhoff_create_multi refuses; a
+ * null pt; nlev outside 1 .. 8; hw[0] != 0, hw not strictly increasing or above 64; a length that is negative or not finite.
+ * rtmi_kirchhoff_migrate / _model on such a handle, and rtmi_kirchhoff_aa_filter on any other handle, return RTMI_ERR_ARG.
+ * Not covered: the half-derivative / wavelet filter and H (the caller's), a continuous triangle by double integration (it loses
+ * about 2 log2(nt) bits and has no bit-for-bit definition), fp32 tables or traces, K > 4. */
+#define RTMI_KIRCHHOFF_MAX_LEVELS 8
+typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen;
+                 int32_t nlev, reserved0; int32_t hw[RTMI_KIRCHHOFF_MAX_LEVELS]; double asrc, arec, amid;
+                 int64_t reserved[4]; } rtmi_kirchhoff_aa_params;
+int rtmi_kirchhoff_create_aa(const rtmi_kirchhoff_aa_params *kp, const double *T, const double *amp, const double *theta,
+                             const double *kmah, const double *pt, const int32_t *isrc, const int32_t *irec,
+                             const double *w, rtmi_kirchhoff **out);
+int rtmi_kirchhoff_aa_filter(rtmi_kirchhoff *k, const double *data, double *bank);   /* [N][nt] -> [nlev][N][nt] */
 
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */

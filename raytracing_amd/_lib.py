@@ -118,6 +118,15 @@ class KirchhoffMultiParams(C.Structure):
 
 
 KIRCHHOFF_MAX_ARRIVALS = 4
+KIRCHHOFF_MAX_LEVELS = 8
+
+
+class KirchhoffAAParams(C.Structure):
+    """rtmi_kirchhoff_aa_params: KirchhoffMultiParams, then the levels and the trace spacings of the anti-aliased pair"""
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("P", C.c_int64), ("N", C.c_int64), ("nt", C.c_int64),
+                ("t0", C.c_double), ("dt", C.c_double), ("nbin", C.c_int32), ("karr", C.c_int32), ("dopen", C.c_double),
+                ("nlev", C.c_int32), ("reserved0", C.c_int32), ("hw", C.c_int32 * KIRCHHOFF_MAX_LEVELS),
+                ("asrc", C.c_double), ("arec", C.c_double), ("amid", C.c_double), ("reserved", C.c_int64 * 4)]
 
 
 class KirchhoffStats(C.Structure):
@@ -181,6 +190,9 @@ SYMBOLS = {
                                               C.POINTER(C.c_void_p)]),
     "rtmi_kirchhoff_migrate2": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(KirchhoffStats)]),
     "rtmi_kirchhoff_model2": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_create_aa": (C.c_int, [C.POINTER(KirchhoffAAParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp,
+                                           C.POINTER(C.c_void_p)]),
+    "rtmi_kirchhoff_aa_filter": (C.c_int, [C.c_void_p, _dp, _dp]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -14,67 +14,10 @@
 // one of two trace channels and a sign.  k_migrate_multi and k_model_multi are the two kernels above with the pair loops
 // unrolled over the template parameter K: the 2 K table values of a (trace, node) are loaded once and serve its K^2 pairs.
 // The tables and the geometry live on the device in the handle; data and image cross the bus on every call.
-#include <hip/hip_runtime.h>
-
-#include <chrono>
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "rt_fix128.h"
-#include "rtmi_host.h"
+// What the pair's arithmetic, the handle and its creation share with the anti-aliased pair (kirchhoff_aa.hip): rt_kirchhoff.h.
+#include "rt_kirchhoff.h"
 
 namespace {
-
-constexpr int kMaxBins = 32;
-constexpr int kWindow = 4096;         // samples of a trace held in LDS at a time: 4096 x 16 B = 64 KiB
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-struct KArgs {
-    const double *T, *amp, *theta;    // [P][nn] (amp, theta: NULL when absent)
-    const int32_t *isrc, *irec;       // [N]
-    const double* w;                  // [N]; ones when the caller gave none (a factor 1 changes no bit)
-    long nn, N, nt;
-    double t0, inv_dt, dopen, ntm1;   // ntm1 = nt - 1: floor(f) <= nt - 2 iff f < nt - 1
-    int nb;
-};
-
-// What one (trace, node) pair reads and derives.  ok: the pair contributes (rtmi.h): every value read is finite, 0 <= j <= nt - 2
-// and the bin is below nb.  A non-finite T makes tau, hence f, non-finite, and the range test fails; likewise theta and h.
-struct Pair { bool ok; long j; double a, c; int b; };
-
-template <bool AMP, bool BINS>
-__device__ __forceinline__ Pair pair_of(const KArgs& A, double Ts, double Tr, double As, double Ar, double Hs, double Hr, double wk) {
-    Pair p;
-    const double tau = Ts + Tr;
-    const double f = (tau - A.t0) * A.inv_dt;
-    p.ok = f >= 0.0 && f < A.ntm1;
-    const double jf = floor(f);
-    p.a = f - jf;
-    p.j = p.ok ? (long)jf : 0;
-    p.c = wk;
-    if (AMP) {
-        p.ok = p.ok && fabs(As) < INFINITY && fabs(Ar) < INFINITY;
-        p.c = (wk * As) * Ar;
-    }
-    p.b = 0;
-    if (BINS) {
-        const double d = Hs - Hr;
-        const double h = 0.5 * fabs(d - kTwoPi * rint(d / kTwoPi));
-        const double hb = floor(h / A.dopen);
-        p.ok = p.ok && hb < (double)A.nb;
-        p.b = p.ok ? (int)hb : 0;
-    }
-    return p;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------------------ L^T
 // image [nb][nn]; counts [gridDim.x]: the block's contributing pairs (plain stores, summed by the host).
@@ -185,32 +128,6 @@ __global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, dou
 }
 
 // ------------------------------------------------------------------------------------------------------------ several arrivals
-// kmah on the device: the caustic count mod 4 as int8, -1 where the table's value is not a finite non-negative integer.
-constexpr int8_t kBadKmah = -1;
-
-// The K arrivals of one table at one node.  Absent columns are never read.
-template <int K> struct Arr { double T[K], A[K], H[K]; int m[K]; };
-
-template <int K, bool AMP, bool BINS, bool PHASE>
-__device__ __forceinline__ void load_arr(const KArgs& A, const int8_t* __restrict__ kmah, size_t at, Arr<K>& o) {
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        const size_t q = at + (size_t)i * A.nn;
-        o.T[i] = A.T[q];
-        o.A[i] = AMP ? A.amp[q] : 0.0;
-        o.H[i] = BINS ? A.theta[q] : 0.0;
-        o.m[i] = PHASE ? (int)kmah[q] : 0;
-    }
-}
-
-// The phase of a pair from its two counts: valid iff neither is kBadKmah; q = (ms + mr) mod 4 picks the channel (odd: 1) and the
-// sign (q = 1, 2: minus), rtmi.h's table.
-struct Phase { bool valid, odd, neg; };
-__device__ __forceinline__ Phase phase_of(int ms, int mr) {
-    const int q = ms + mr;
-    return Phase{(ms | mr) >= 0, (q & 1) != 0, ((q + 1) & 2) != 0};
-}
-
 // L^T.  data0, data1 [N][nt] (data1 is read only with PHASE); image [nb][nn]; counts [gridDim.x].  The sum runs over k, then ks,
 // then kr, as rtmi.h defines it.  All K^2 gathers of a trace are issued before the first add, outside the `contributes` test.
 template <int K, bool AMP, bool BINS, bool PHASE>
@@ -385,155 +302,6 @@ void launch_multi(int karr, bool amp, bool bins, bool phase, const MultiLaunch& 
     }
 }
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-}  // namespace
-
-struct rtmi_kirchhoff {
-    rtmi_kirchhoff_params kp{};
-    int device = 0, nb = 1;
-    int karr = 0;                             // 0: rtmi_kirchhoff_create's handle; K >= 1: create_multi's, tables [P][K][nn]
-    size_t nn = 0;
-    double max_w = 1.0, max_amp = 1.0;        // over finite values; the order-independent bound of the fixed-point scale
-    double *T = nullptr, *amp = nullptr, *theta = nullptr, *w = nullptr, *data = nullptr, *image = nullptr;
-    int32_t *isrc = nullptr, *irec = nullptr;
-    int8_t* kmah = nullptr;                   // multi: [P][K][nn], the count mod 4 or kBadKmah; NULL without kmah
-    unsigned long long* counts = nullptr;     // max(N, migrate's blocks)
-    size_t ncounts = 0;
-    ~rtmi_kirchhoff() {
-        for (void* p : {(void*)T, (void*)amp, (void*)theta, (void*)w, (void*)data, (void*)image, (void*)isrc, (void*)irec, (void*)kmah, (void*)counts})
-            if (p) (void)hipFree(p);
-    }
-    KArgs args() const {
-        return KArgs{T, amp, theta, isrc, irec, w, (long)nn, (long)kp.N, (long)kp.nt, kp.t0, 1.0 / kp.dt, kp.dopen,
-                     (double)(kp.nt - 1), nb};
-    }
-};
-
-namespace {
-
-int migrate_block(int nb) { return nb > 16 ? 128 : 256; }    // [bin][lane] fp64 in LDS stays within 32 KiB
-
-int check_device(const rtmi_kirchhoff* k, const char* who) {
-    int dev = -1;
-    RTMI_HIP(hipGetDevice(&dev));
-    RTMI_ARG(dev == k->device, "the calling thread's current device is not the handle's");
-    return RTMI_OK;
-}
-
-int read_counts(const rtmi_kirchhoff* k, size_t n, int64_t* total, const char* who) {
-    std::vector<unsigned long long> h(n);
-    RTMI_HIP(hipMemcpy(h.data(), k->counts, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long t = 0;
-    for (unsigned long long v : h) t += v;
-    *total = (int64_t)t;
-    return RTMI_OK;
-}
-
-}  // namespace
-
-namespace {
-
-// Both creates.  karr = 0: rtmi_kirchhoff_create (tables [P][nn], no kmah); karr >= 1: create_multi (tables [P][karr][nn]).
-int create_impl(const char* who, const rtmi_kirchhoff_params* kp, int karr, const double* T, const double* amp, const double* theta,
-                const double* kmah, const int32_t* isrc, const int32_t* irec, const double* w, rtmi_kirchhoff** out) {
-    RTMI_ARG(T, "null T");
-    RTMI_ARG(isrc, "null isrc");
-    RTMI_ARG(irec, "null irec");
-    RTMI_ARG(kp->nx >= 1, "nx must be >= 1");
-    RTMI_ARG(kp->ny >= 1, "ny must be >= 1");
-    RTMI_ARG(kp->P >= 1, "P must be >= 1");
-    RTMI_ARG(kp->N >= 1, "N must be >= 1");
-    RTMI_ARG(kp->nt >= 2, "nt must be >= 2");
-    RTMI_ARG(kp->nx <= (1ll << 31) && kp->ny <= (1ll << 31) && kp->nx * kp->ny <= (1ll << 31), "nx ny must be <= 2^31");
-    RTMI_ARG(kp->P <= INT32_MAX, "P must fit the int32 indices");
-    RTMI_ARG(kp->N <= INT32_MAX, "N must be below 2^31 (one block per trace)");
-    RTMI_ARG(std::isfinite(kp->dt) && kp->dt > 0.0, "dt must be finite and > 0");
-    RTMI_ARG(std::isfinite(kp->t0), "t0 must be finite");
-    RTMI_ARG(kp->nbin >= 0 && kp->nbin <= kMaxBins, "nbin must be in 0..32");
-    if (kp->nbin > 0) {
-        RTMI_ARG(theta, "nbin > 0 needs theta");
-        RTMI_ARG(std::isfinite(kp->dopen) && kp->dopen > 0.0, "dopen must be finite and > 0");
-    }
-    for (int64_t k = 0; k < kp->N; k++) {
-        RTMI_ARG(isrc[k] >= 0 && isrc[k] < kp->P, "isrc has an index outside [0, P)");
-        RTMI_ARG(irec[k] >= 0 && irec[k] < kp->P, "irec has an index outside [0, P)");
-    }
-    double max_w = 1.0;
-    if (w) {
-        max_w = 0.0;
-        for (int64_t k = 0; k < kp->N; k++) {
-            RTMI_ARG(std::isfinite(w[k]), "w has a value that is not finite");
-            max_w = std::fmax(max_w, std::fabs(w[k]));
-        }
-    }
-    const size_t nn = (size_t)kp->nx * (size_t)kp->ny, N = (size_t)kp->N, nt = (size_t)kp->nt;
-    const size_t P = (size_t)kp->P * (size_t)(karr > 0 ? karr : 1);        // tables of nn nodes
-    const int nb = kp->nbin > 0 ? kp->nbin : 1;
-    double max_amp = 1.0;
-    if (amp) {
-        max_amp = 0.0;
-        for (size_t i = 0; i < P * nn; i++)
-            if (std::isfinite(amp[i])) max_amp = std::fmax(max_amp, std::fabs(amp[i]));
-    }
-    rtmi_kirchhoff* k = new (std::nothrow) rtmi_kirchhoff;
-    if (!k) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_kirchhoff_create: out of host memory");
-    k->kp = *kp;
-    k->karr = karr;
-    k->nb = nb;
-    k->nn = nn;
-    k->max_w = max_w;
-    k->max_amp = max_amp;
-    const bool bins = kp->nbin > 0;
-    const size_t mblocks = (nn + migrate_block(nb) - 1) / migrate_block(nb);
-    k->ncounts = N > mblocks ? N : mblocks;
-    auto fail = [&](int code, const std::string& msg) {
-        delete k;
-        return rtmi_internal_fail(code, (std::string(who) + ": " + msg).c_str());
-    };
-    hipError_t e = hipGetDevice(&k->device);
-    if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e));
-    auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes); };
-    struct { void** p; size_t bytes; const void* src; } bufs[] = {
-        {(void**)&k->T, P * nn * sizeof(double), T},
-        {(void**)&k->amp, amp ? P * nn * sizeof(double) : 0, amp},
-        {(void**)&k->theta, bins ? P * nn * sizeof(double) : 0, theta},
-        {(void**)&k->isrc, N * sizeof(int32_t), isrc},
-        {(void**)&k->irec, N * sizeof(int32_t), irec},
-        {(void**)&k->w, N * sizeof(double), nullptr},
-        {(void**)&k->kmah, kmah ? P * nn * sizeof(int8_t) : 0, nullptr},
-        {(void**)&k->data, (kmah ? 2 : 1) * N * nt * sizeof(double), nullptr},     // with kmah: channel 0, then channel 1
-        {(void**)&k->image, (size_t)nb * nn * sizeof(double), nullptr},
-        {(void**)&k->counts, k->ncounts * sizeof(unsigned long long), nullptr},
-    };
-    for (auto& b : bufs) {
-        if (!b.bytes) continue;
-        e = get(b.p, b.bytes);
-        if (e != hipSuccess) return fail(RTMI_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
-        if (b.src) {
-            e = hipMemcpy(*b.p, b.src, b.bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-        }
-    }
-    std::vector<double> ones;
-    if (!w) ones.assign(N, 1.0);
-    e = hipMemcpy(k->w, w ? w : ones.data(), N * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    if (kmah) {
-        std::vector<int8_t> km(P * nn);
-        for (size_t i = 0; i < P * nn; i++) {
-            const double v = kmah[i];
-            km[i] = (std::isfinite(v) && v >= 0.0 && v == std::floor(v)) ? (int8_t)std::fmod(v, 4.0) : kBadKmah;
-        }
-        e = hipMemcpy(k->kmah, km.data(), P * nn * sizeof(int8_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    *out = k;
-    return RTMI_OK;
-}
-
 }  // namespace
 
 RTMI_EXPORT int rtmi_kirchhoff_create(const rtmi_kirchhoff_params* kp, const double* T, const double* amp, const double* theta,
@@ -552,11 +320,8 @@ RTMI_EXPORT int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params* m
     RTMI_ARG(out, "null out");
     *out = nullptr;
     RTMI_ARG(mp, "null kp");
-    RTMI_ARG(mp->karr >= 1 && mp->karr <= RTMI_KIRCHHOFF_MAX_ARRIVALS, "karr must be in 1..4");
     rtmi_kirchhoff_params kp{};
-    kp.nx = mp->nx; kp.ny = mp->ny; kp.P = mp->P; kp.N = mp->N; kp.nt = mp->nt;
-    kp.t0 = mp->t0; kp.dt = mp->dt; kp.nbin = mp->nbin; kp.dopen = mp->dopen;
-    RTMI_ARG(kp.P <= INT32_MAX / RTMI_KIRCHHOFF_MAX_ARRIVALS, "P karr must fit the int32 indices");
+    RTMI_RC(multi_params(who, mp, &kp));
     return create_impl(who, &kp, mp->karr, T, amp, theta, kmah, isrc, irec, w, out);
 }
 
@@ -605,12 +370,7 @@ RTMI_EXPORT int rtmi_kirchhoff_model(rtmi_kirchhoff* k, const double* model, dou
     RTMI_ARG(k->karr == 0, "the handle is rtmi_kirchhoff_create_multi's: call rtmi_kirchhoff_model2");
     RTMI_RC(check_device(k, who));
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
-    // the quantum: |contribution| <= max|w| max|amp|^2 max|m| = f 2^ex with f in [0.5, 1), so it is below 2^57 quanta 2^(ex - 57)
-    double max_m = 0.0;
-    for (size_t i = 0; i < nm; i++)
-        if (std::isfinite(model[i])) max_m = std::fmax(max_m, std::fabs(model[i]));
-    const double bound = (k->max_w * k->max_amp) * k->max_amp * max_m;
-    const int e = std::isfinite(bound) ? rt::fix_exponent(bound) : 1025 - rt::kFixBits;
+    const int e = model_exponent(k, model, nm);
     const double t_up = now_ms();
     RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
     const double upload_ms = now_ms() - t_up;
@@ -650,6 +410,7 @@ RTMI_EXPORT int rtmi_kirchhoff_migrate2(rtmi_kirchhoff* k, const double* data0, 
     RTMI_ARG(k->karr >= 1, "the handle is rtmi_kirchhoff_create's: call rtmi_kirchhoff_migrate");
     RTMI_ARG(data1 || !k->kmah, "null data1 on a handle that has kmah");
     RTMI_RC(check_device(k, who));
+    if (k->nlev) return rtmi_internal_kirchhoff_aa_migrate2(k, data0, data1, image, st);
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
     const bool phase = k->kmah != nullptr;
     const double t_up = now_ms();
@@ -694,14 +455,11 @@ RTMI_EXPORT int rtmi_kirchhoff_model2(rtmi_kirchhoff* k, const double* model, do
     RTMI_ARG(k->karr >= 1, "the handle is rtmi_kirchhoff_create's: call rtmi_kirchhoff_model");
     RTMI_ARG(data1 || !k->kmah, "null data1 on a handle that has kmah");
     RTMI_RC(check_device(k, who));
+    if (k->nlev) return rtmi_internal_kirchhoff_aa_model2(k, model, data0, data1, st);
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
     const bool phase = k->kmah != nullptr;
     // the quantum: rtmi_kirchhoff_model's, from the same bound on one contribution (DESIGN.md 19 on the number of contributions)
-    double max_m = 0.0;
-    for (size_t i = 0; i < nm; i++)
-        if (std::isfinite(model[i])) max_m = std::fmax(max_m, std::fabs(model[i]));
-    const double bound = (k->max_w * k->max_amp) * k->max_amp * max_m;
-    const int e = std::isfinite(bound) ? rt::fix_exponent(bound) : 1025 - rt::kFixBits;
+    const int e = model_exponent(k, model, nm);
     const double t_up = now_ms();
     RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
     const double upload_ms = now_ms() - t_up;

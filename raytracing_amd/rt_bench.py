@@ -1166,8 +1166,27 @@ def beam_table(selected_func, field, sources, grid, omegas, *, thetas, eps, step
 
 
 def kirchhoff_stats(st):
+    """aux_ms: on an anti-aliased handle the part of kernel_ms that is not the pair kernel (the bank's filter in migrate, the sum
+    over the levels in model); 0 elsewhere"""
     return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "pairs": int(st.pairs), "contributing": int(st.contributing),
-            "scale_exp": int(st.scale_exp)}
+            "scale_exp": int(st.scale_exp), "aux_ms": st.reserved[0] * 1e-6}
+
+
+ANTIALIAS_DEFAULTS = dict(hw=(0, 1, 2, 4, 8), asrc=0.0, arec=0.0, amid=0.0)
+
+
+def position_slope(tab, n_at_positions, direction=(1.0, 0.0)):
+    """pt of T's shape for Kirchhoff(..., pt=): the derivative of the table's traveltimes with respect to the surface position along
+    the line of unit `direction`, by reciprocity -n(p) (cos theta0 e_x + sin theta0 e_y) from the table's launch angles theta0
+    (traveltime_table's column).  n_at_positions [P]: the refractive index at each position (Field.n_gradient(x, y)[0]).  NaN
+    where the table has no arrival."""
+    th = np.asarray(tab["theta0"], dtype=np.float64)
+    n = np.asarray(n_at_positions, dtype=np.float64).reshape(-1)
+    if n.shape[0] != th.shape[0]:
+        raise ValueError("position_slope: n_at_positions must have one value per position")
+    ex, ey = float(direction[0]), float(direction[1])
+    n = n.reshape((-1,) + (1,) * (th.ndim - 1))
+    return -n * (np.cos(th) * ex + np.sin(th) * ey)
 
 
 def hilbert(d):
@@ -1199,18 +1218,25 @@ class Kirchhoff:
       migrate_channels(d0, d1) -> image    and    model_channels(m) -> (ch0, ch1)
     are the bit-defined transposes between the model and the two trace channels (d1 may be None, and ch1 is zeros, without kmah);
     the full trace is ch0 + H ch1 with H = hilbert (circular: pad the traces), so on such a handle
-      model(m) = ch0 + hilbert(ch1)    and    migrate(d) = migrate_channels(d, -hilbert(d)),   its transpose since H^T = -H."""
+      model(m) = ch0 + hilbert(ch1)    and    migrate(d) = migrate_channels(d, -hilbert(d)),   its transpose since H^T = -H.
+    With pt (of T's shape: dT/d(position), position_slope) the pair is anti-aliased by operator slope (rtmi_kirchhoff_create_aa,
+    DESIGN.md 20): antialias = dict(hw=(0, 1, 2, 4, 8), asrc=0.0, arec=0.0, amid=0.0), the triangle half-widths of the levels in
+    samples and the trace spacing along the source, receiver and midpoint axes (keys left out take these defaults).  A 3-D T is
+    then taken as K = 1; every call above works unchanged, and aa_filter(d) returns the bank [nlev, N, nt] of one channel."""
 
-    def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None, kmah=None):
+    def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None, kmah=None, pt=None,
+                 antialias=None):
         T = np.ascontiguousarray(T, dtype=np.float64)
         if T.ndim not in (3, 4):
             raise ValueError("Kirchhoff: T must be [P, ny, nx] or [P, K, ny, nx]")
+        if antialias is not None and pt is None:
+            raise ValueError("Kirchhoff: antialias needs pt")
         self.karr = T.shape[1] if T.ndim == 4 else 0
         if kmah is not None and not self.karr:
             raise ValueError("Kirchhoff: kmah needs T [P, K, ny, nx]")
         P, ny, nx = T.shape[0], T.shape[-2], T.shape[-1]
-        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (amp, theta, kmah)]
-        for a, name in zip(opt, ("amp", "theta", "kmah")):
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (amp, theta, kmah, pt)]
+        for a, name in zip(opt, ("amp", "theta", "kmah", "pt")):
             if a is not None and a.shape != T.shape:
                 raise ValueError(f"Kirchhoff: {name} must have T's shape")
         si = np.ascontiguousarray(isrc, dtype=np.int32).reshape(-1)
@@ -1220,7 +1246,17 @@ class Kirchhoff:
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w is not None and w.shape != si.shape:
             raise ValueError("Kirchhoff: weights must have isrc's length")
-        kp = _lib.KirchhoffMultiParams() if self.karr else _lib.KirchhoffParams()
+        self.antialias = None
+        if pt is not None:
+            unknown = set(antialias or {}) - set(ANTIALIAS_DEFAULTS)
+            if unknown:
+                raise ValueError(f"Kirchhoff: antialias has unknown keys {sorted(unknown)}")
+            self.antialias = dict(ANTIALIAS_DEFAULTS, **(antialias or {}))
+            self.antialias["hw"] = tuple(int(v) for v in self.antialias["hw"])
+            if len(self.antialias["hw"]) > _lib.KIRCHHOFF_MAX_LEVELS:
+                raise ValueError("Kirchhoff: antialias hw has more than 8 levels")
+            self.karr = self.karr or 1                 # a 3-D table is the K = 1 layout
+        kp = _lib.KirchhoffAAParams() if pt is not None else _lib.KirchhoffMultiParams() if self.karr else _lib.KirchhoffParams()
         kp.nx, kp.ny, kp.P, kp.N, kp.nt = nx, ny, P, len(si), int(nt)
         kp.t0 = float(t0); kp.dt = float(dt); kp.nbin = int(nbin); kp.dopen = float(dopen or 0.0)
         self.N, self.nt, self.nb, self.nbin, self.ny, self.nx = len(si), int(nt), max(int(nbin), 1), int(nbin), ny, nx
@@ -1228,7 +1264,17 @@ class Kirchhoff:
         self.has_kmah = kmah is not None
         self._h = None
         h = C.c_void_p()
-        if self.karr:
+        if pt is not None:
+            aa = self.antialias
+            kp.karr = self.karr
+            kp.nlev = len(aa["hw"])
+            for i, v in enumerate(aa["hw"]):
+                kp.hw[i] = v
+            kp.asrc, kp.arec, kp.amid = float(aa["asrc"]), float(aa["arec"]), float(aa["amid"])
+            self.nlev = kp.nlev
+            check(lib().rtmi_kirchhoff_create_aa(C.byref(kp), dptr(T), dptr(opt[0]), dptr(opt[1]), dptr(opt[2]), dptr(opt[3]),
+                                                 si.ctypes.data_as(_lib._ip), ri.ctypes.data_as(_lib._ip), dptr(w), C.byref(h)))
+        elif self.karr:
             kp.karr = self.karr
             check(lib().rtmi_kirchhoff_create_multi(C.byref(kp), dptr(T), dptr(opt[0]), dptr(opt[1]), dptr(opt[2]),
                                                     si.ctypes.data_as(_lib._ip), ri.ctypes.data_as(_lib._ip), dptr(w), C.byref(h)))
@@ -1238,13 +1284,20 @@ class Kirchhoff:
         self._h = h
 
     @classmethod
-    def from_table(cls, tab, isrc, irec, nt, dt, t0=0.0, amplitude=False, weights=None, nbin=0, dopen=None):
+    def from_table(cls, tab, isrc, irec, nt, dt, t0=0.0, amplitude=False, weights=None, nbin=0, dopen=None, antialias=None):
         """From traveltime_table's dict: its T, its theta when nbin > 0, and its G as amp when amplitude is asked for; with
-        arrivals=K tables (a 4-D T) also its kmah whenever the dict has one."""
+        arrivals=K tables (a 4-D T) also its kmah whenever the dict has one.  antialias: Kirchhoff's dict with two more keys,
+        n_at_positions [P] and optionally direction, from which position_slope takes pt off the table's theta0."""
         multi = np.ndim(tab["T"]) == 4
+        pt = None
+        if antialias is not None:
+            antialias = dict(antialias)
+            if "n_at_positions" not in antialias:
+                raise ValueError("Kirchhoff.from_table: antialias needs n_at_positions")
+            pt = position_slope(tab, antialias.pop("n_at_positions"), antialias.pop("direction", (1.0, 0.0)))
         return cls(tab["T"], isrc, irec, nt, dt, t0=t0, amp=tab["G"] if amplitude else None,
                    theta=tab["theta"] if nbin else None, weights=weights, nbin=nbin, dopen=dopen,
-                   kmah=tab["kmah"] if multi and "kmah" in tab else None)
+                   kmah=tab["kmah"] if multi and "kmah" in tab else None, pt=pt, antialias=antialias)
 
     def _open(self):
         if not self._h:
@@ -1305,6 +1358,17 @@ class Kirchhoff:
         st = _lib.KirchhoffStats()
         check(lib().rtmi_kirchhoff_model2(self._open(), dptr(mm), dptr(d0), dptr(d1), C.byref(st)))
         return ((d0, d1), kirchhoff_stats(st)) if stats else (d0, d1)
+
+    def aa_filter(self, d):
+        """rtmi_kirchhoff_aa_filter: one channel [N, nt] -> its bank [nlev, N, nt], level l the triangle of half-width hw[l]"""
+        if self.antialias is None:
+            raise ValueError("Kirchhoff.aa_filter: the handle has no pt (antialias)")
+        dd = np.ascontiguousarray(d, dtype=np.float64)
+        if dd.size != self.N * self.nt:
+            raise ValueError("Kirchhoff.aa_filter: d must be [N, nt]")
+        bank = np.empty((self.nlev, self.N, self.nt))
+        check(lib().rtmi_kirchhoff_aa_filter(self._open(), dptr(dd), dptr(bank)))
+        return bank
 
     def as_linear_operator(self):
         from scipy.sparse.linalg import LinearOperator

@@ -10,7 +10,12 @@ process with the one-arrival kernels it is measured against: the tables replicat
 the K^2 pairs of a (trace, node) are distinct and (nearly) all contribute; kmah = slot index.  It prints, for migrate and
 model: the one-arrival handle, K = 1 without kmah through the new kernels, and K slots without and with kmah, each with its
 time per pair relative to the one-arrival kernel.
-Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K]"""
+--antialias NLEV (with --arrivals K, default 1) times the pair anti-aliased by operator slope (rtmi_kirchhoff_create_aa; DESIGN.md
+20) on the same case against rtmi_kirchhoff_migrate2 / _model2 on the same inputs, in one process, the two handles called in
+turn: pt from the closed-form launch angles, arec = the position spacing (the case is shot gathers), the levels the first NLEV
+of 0, 1, 2, 4, 8, 16, 32, 64.  It prints, for migrate and model, the plain kernel, the anti-aliased pair kernel and its filter
+(migrate) or sum over the levels (model) apart, their ratio, and the bytes floor with the extra table and the bank.
+Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV]"""
 import argparse
 import json
 import os
@@ -130,6 +135,71 @@ def run_arrivals(K, reps):
     measure(f"K = {K} with kmah", rb.Kirchhoff(TK, isrc, irec, nt, dt, kmah=km), K, 1)
 
 
+HW = (0, 1, 2, 4, 8, 16, 32, 64)
+
+
+def launch_slope(pos_x, grid):
+    """pt = -n cos theta0 of the closed form: the launch angle of the arc from (xs, POS_Y) to each node"""
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    X, Y = np.meshgrid(gx0 + np.arange(nx) * gdx, gy0 + np.arange(ny) * gdy)
+    out = []
+    for xs in pos_x:
+        xc = ((X ** 2 - xs ** 2) + (Y + 9) ** 2 - (POS_Y + 9) ** 2) / (2 * (X - xs))
+        sg = np.sign(xc - xs)
+        out.append(-np.cos(np.arctan2(-sg * (xs - xc), sg * (POS_Y + 9))) / (18.0 + 2.0 * POS_Y))
+    return np.stack(out)
+
+
+def run_antialias(K, nlev, reps):
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, _ = tables(pos_x, grid)
+    pt = launch_slope(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    N, nn = len(isrc), T[0].size
+    rng = np.random.default_rng(1)
+    d0 = rng.standard_normal((N, nt))
+    m = rng.standard_normal(T.shape[1:])
+    TK = np.stack([T + 0.003 * i for i in range(K)], axis=1)
+    PK = np.stack([pt] * K, axis=1)
+    aa = dict(hw=HW[:nlev], arec=float(pos_x[1] - pos_x[0]))
+    plain = rb.Kirchhoff(TK, isrc, irec, nt, dt)
+    anti = rb.Kirchhoff(TK, isrc, irec, nt, dt, pt=PK, antialias=aa)
+    sweeps = -(-nt // min(nt, 4096 // nlev))                     # windows of the model kernel: each sweeps the nodes once
+    for kind in ("migrate", "model"):
+        if kind == "migrate":
+            calls = [lambda: plain.migrate_channels(d0, None, stats=True)[1], lambda: anti.migrate_channels(d0, None, stats=True)[1]]
+            tab = 8 * (N + len(src)) * K * nn
+            nbytes = [tab + 8 * (N * nt + nn), 2 * tab + 8 * (N * nt * (nlev + 2 * (nlev - 1)) + nn)]
+        else:
+            calls = [lambda: plain.model_channels(m, stats=True)[1], lambda: anti.model_channels(m, stats=True)[1]]
+            tab = 8 * 2 * N * K * nn
+            nbytes = [tab + 8 * (N * nn + N * nt), sweeps * (2 * tab + 8 * N * nn) + 8 * N * nt * (2 * nlev + 1)]
+        for c in calls:
+            c()                                                  # warm-up: code objects
+        ks, aux = [[], []], []
+        for _ in range(reps):                                    # in turn: both see the same state of the device
+            for i, c in enumerate(calls):
+                st = c()
+                ks[i].append(st["kernel_ms"])
+                if i:
+                    aux.append(st["aux_ms"])
+        k0, k1, ax = float(np.median(ks[0])), float(np.median(ks[1])), float(np.median(aux))
+        pair = float(np.median(np.array(ks[1]) - np.array(aux)))
+        print(json.dumps({"what": f"{kind}, K = {K}, {nlev} levels {list(HW[:nlev])}", "pairs": st["pairs"], "contributing": st["contributing"],
+                          "plain_kernel_ms": k0, "aa_total_ms": k1, "aa_pair_kernel_ms": pair,
+                          "aa_filter_ms" if kind == "migrate" else "aa_level_sum_ms": ax, "pair_kernel_ratio": pair / k0,
+                          "total_ratio": k1 / k0, "model_node_sweeps": sweeps if kind == "model" else None,
+                          "plain_bytes": nbytes[0], "aa_bytes": nbytes[1], "plain_floor_ms_at_6TBps": nbytes[0] / 6e12 * 1e3,
+                          "aa_floor_ms_at_6TBps": nbytes[1] / 6e12 * 1e3, "plain_kernel_ms_all": ks[0], "aa_total_ms_all": ks[1]}),
+              flush=True)
+    plain.close(); anti.close()
+
+
 def restatement():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import kirchhoff_ref as K
@@ -148,8 +218,11 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--case", choices=CASES + ("restatement",))
     ap.add_argument("--arrivals", type=int, choices=(1, 2, 3, 4))
+    ap.add_argument("--antialias", type=int, choices=range(1, 9), metavar="NLEV")
     a = ap.parse_args()
-    if a.arrivals:
+    if a.antialias:
+        run_antialias(a.arrivals or 1, a.antialias, a.reps)
+    elif a.arrivals:
         run_arrivals(a.arrivals, a.reps)
     elif a.case == "restatement":
         restatement()
