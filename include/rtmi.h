@@ -625,9 +625,9 @@ int rtmi_gaussian_beams(rtmi_batch *b, int32_t fan_size, const rtmi_beam_params 
  * irec or out; nx, ny, P, N < 1; nt < 2; nx ny > 2^31; dt or t0 not finite or dt <= 0; nbin < 0, nbin > 32; nbin > 0 with a null
  * theta or a dopen that is not finite and > 0; an index outside [0, P); a w that is not finite.  Null handle or buffer in the
  * other calls: RTMI_ERR_ARG.
- * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), fp32 storage, device-resident data
- * and image buffers, several GPUs.  Several arrivals per node and their caustic phase: rtmi_kirchhoff_create_multi below;
- * anti-alias filtering of steep operators: rtmi_kirchhoff_create_aa below. */
+ * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), fp32 storage, several GPUs.
+ * Device-resident data and image buffers: rtmi_kirchhoff_migrate_dev / _model_dev below.  Several arrivals per node and their
+ * caustic phase: rtmi_kirchhoff_create_multi below; anti-alias filtering of steep operators: rtmi_kirchhoff_create_aa below. */
 typedef struct rtmi_kirchhoff rtmi_kirchhoff;
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, reserved0; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_params;
 typedef struct {
@@ -732,6 +732,52 @@ int rtmi_kirchhoff_create_aa(const rtmi_kirchhoff_aa_params *kp, const double *T
                              const double *kmah, const double *pt, const int32_t *isrc, const int32_t *irec,
                              const double *w, rtmi_kirchhoff **out);
 int rtmi_kirchhoff_aa_filter(rtmi_kirchhoff *k, const double *data, double *bank);   /* [N][nt] -> [nlev][N][nt] */
+
+/* The pair on device pointers, and least-squares migration that stays on the device.  DESIGN.md section 21.
+ * rtmi_kirchhoff_migrate_dev / _model_dev are rtmi_kirchhoff_migrate2 / _model2 (on a handle of rtmi_kirchhoff_create:
+ * rtmi_kirchhoff_migrate / _model, d_data1 ignored) with every buffer in memory of the handle's device: d_data0, d_data1 [N][nt],
+ * d_image and d_model [nb][ny][nx], fp64, contiguous.  The same bits as the host-pointer calls on the same values: image, traces,
+ * contributing, scale_exp.  d_data1 follows data1's rules: NULL only without kmah; without kmah it is not read, and a d_data1
+ * given to model_dev comes back as zeros.  No transfer between host and device larger than the per-block counts; on a handle of
+ * rtmi_kirchhoff_create_aa the channels are copied on the device to and from the handle's level bank.  stats.upload_ms is 0.
+ * model's max|m| over the finite values is taken on the device (an exact reduction: any order gives the same bits) and 8 bytes
+ * are read back.  The host-pointer calls above are upload + these + download.  RTMI_ERR_ARG: a null handle or buffer; a pointer
+ * that hipPointerGetAttributes does not report as memory of the handle's device, or whose allocation ends before the buffer does.
+ *
+ * rtmi_kirchhoff_lsqr solves min |L x - data|^2 + damp^2 |x|^2 by LSQR (Paige and Saunders 1982) in the operation order of
+ * scipy.sparse.linalg.lsqr, from x = 0.  data [N][nt] and x [nb][ny][nx] are host fp64; the data go up once, x comes down once,
+ * and between them each iteration is model_dev, u = L v - alfa u and its norm, migrate_dev, v = L^T u - beta v and its norm, the
+ * scalar half-steps on the host (raytracing_amd/csrc/rt_lsqr.h) and the update of x and w; the host reads back a few 8-byte
+ * words per iteration.  Every step is defined bit for bit:
+ *   updates  y[i] = t[i] - fl(a * y[i]);  y[i] = fl(s * y[i]), s = 1 / beta or 1 / alfa computed on the host;
+ *            x[i] = x[i] + fl(c1 * w[i]), w[i] = v[i] - fl(c2 * w[i]) with c1 = phi / rho, c2 = theta / rho: every product and
+ *            every add or subtract a separate fp64 operation.
+ *   norm     M = max |x[i]|; M = 0: the norm is +0.  Else bound = fl(M * M), e = ex - 57 with bound = f 2^ex, f in [0.5, 1);
+ *            q[i] = rint(fl(x[i] * x[i]) * 2^-e), an integer of at most 2^57; S = sum of q[i], exact, in two 64-bit words;
+ *            norm = sqrt(S 2^e), S rounded once to fp64 and the even part of e applied after the root (the same bits, and
+ *            finite also where S 2^e exceeds fp64).  Integer sums commute: the same bits in every schedule.  If bound is not a
+ *            normal number (overflow, or below 2^-1022) the solver stops with istop = RTMI_LSQR_RANGE; inside the loop that
+ *            abandons the iteration: itn, the scalars, the history and x are those of the last iteration completed.
+ *   scalars  scipy's: _sym_ortho, the damp rotation, rhobar, phibar, theta, phi, rho, r1norm, r2norm, anorm, arnorm; the stop
+ *            tests 1 (istop 1), 2 (istop 2) and the iteration limit (istop 7); istop 0 with itn = 0 and x = 0 when data or
+ *            L^T data is zero.  xnorm enters test 1 as in scipy and is not reported.
+ * history, if not NULL, gets one row per iteration: alfa, beta, r1norm, arnorm.  stats: operator_ms the sum of the pair's
+ * kernel_ms, vector_ms the host wall time of the vector passes with their read-backs, total_ms the call's; bytes_device the
+ * call's own vectors (2 N nt + 4 nb ny nx doubles, freed at its end) plus the handle's staging.
+ * Handles: rtmi_kirchhoff_create, and create_multi / create_aa without kmah (channel 0 is the whole trace).
+ * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null handle, params, data or x; iter_lim < 1;
+ * damp, atol or btol negative or not finite; a handle with kmah; a data value that is not finite.
+ * Not covered: handles with kmah (their trace is ch0 + H ch1 and there is no Hilbert transform on the device), preconditioners,
+ * model masks, x0, conlim / acond / xnorm / var (acond and var need a vector norm more per iteration), scipy's stop tests 3 to 6,
+ * fp32 vectors, several GPUs. */
+#define RTMI_LSQR_RANGE 8
+typedef struct { int32_t iter_lim, reserved0; double damp, atol, btol; int64_t reserved[4]; } rtmi_lsqr_params;
+typedef struct { int32_t istop, itn; double r1norm, r2norm, anorm, arnorm; double total_ms, operator_ms, vector_ms;
+                 int64_t bytes_device; int64_t reserved[4]; } rtmi_lsqr_stats;
+int rtmi_kirchhoff_migrate_dev(rtmi_kirchhoff *k, const double *d_data0, const double *d_data1, double *d_image, rtmi_kirchhoff_stats *st);
+int rtmi_kirchhoff_model_dev(rtmi_kirchhoff *k, const double *d_model, double *d_data0, double *d_data1, rtmi_kirchhoff_stats *st);
+int rtmi_kirchhoff_lsqr(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const double *data, double *x, double *history,
+                        rtmi_lsqr_stats *st);
 
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
@@ -876,6 +922,10 @@ int rtmi_debug_arrival_rows(int32_t rows, int32_t R, int32_t fan_size, const dou
                             const double *theta, const int32_t *last, const double *theta0, const double *J, const int32_t *kmah,
                             const double *n, const rtmi_grid_params *gp, const rtmi_arrival_params *ap, int32_t *count,
                             double *out, rtmi_arrival_stats *st);
+
+/* Diagnostic: the norm of rtmi_kirchhoff_lsqr on n host doubles, host in and host out: *norm, and *e the quantum's exponent (0 for
+ * the zero vector).  RTMI_ERR_ARG: n < 1, a value that is not finite, max|x|^2 not a normal number. */
+int rtmi_debug_fix_norm(const double *x, int64_t n, double *norm, int32_t *e);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,19 @@ class KirchhoffStats(C.Structure):
                 ("scale_exp", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
 
 
+class LsqrParams(C.Structure):
+    _fields_ = [("iter_lim", C.c_int32), ("reserved0", C.c_int32), ("damp", C.c_double), ("atol", C.c_double), ("btol", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+
+class LsqrStats(C.Structure):
+    _fields_ = [("istop", C.c_int32), ("itn", C.c_int32), ("r1norm", C.c_double), ("r2norm", C.c_double), ("anorm", C.c_double),
+                ("arnorm", C.c_double), ("total_ms", C.c_double), ("operator_ms", C.c_double), ("vector_ms", C.c_double),
+                ("bytes_device", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
+LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
+
 # rtmi_arrival_grid's orders and largest karr
 ARRIVAL_BY_TIME, ARRIVAL_BY_AMPLITUDE, MAX_ARRIVALS = 0, 1, 16
 ARRIVAL_ORDERS = {"time": ARRIVAL_BY_TIME, "amplitude": ARRIVAL_BY_AMPLITUDE}
@@ -193,6 +206,9 @@ SYMBOLS = {
     "rtmi_kirchhoff_create_aa": (C.c_int, [C.POINTER(KirchhoffAAParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp,
                                            C.POINTER(C.c_void_p)]),
     "rtmi_kirchhoff_aa_filter": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "rtmi_kirchhoff_migrate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_model_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_lsqr": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, C.POINTER(LsqrStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),
@@ -220,6 +236,7 @@ SYMBOLS = {
                                                                              C.POINTER(GridStats)]),
     "rtmi_debug_arrival_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [_ip, _dp, _dp, _ip, _dp, C.POINTER(GridParams),
                                           C.POINTER(ArrivalParams), _ip, _dp, C.POINTER(ArrivalStats)]),
+    "rtmi_debug_fix_norm": (C.c_int, [_dp, C.c_int64, _dp, _ip]),
 }
 
 _lib = None

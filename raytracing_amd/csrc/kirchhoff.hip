@@ -13,7 +13,9 @@
 // meets a node in K^2 pairs of a source and a receiver arrival, each rotated by the phase of its caustic count -- a choice of
 // one of two trace channels and a sign.  k_migrate_multi and k_model_multi are the two kernels above with the pair loops
 // unrolled over the template parameter K: the 2 K table values of a (trace, node) are loaded once and serve its K^2 pairs.
-// The tables and the geometry live on the device in the handle; data and image cross the bus on every call.
+// The tables and the geometry live on the device in the handle.  Every kernel has one launch path, on device pointers
+// (rtmi_kirchhoff_migrate_dev / _model_dev); the host-pointer entries upload into the handle's staging buffers,
+// run that path on them and download.  The model's quantum comes from k_absmax_finite, a reduction over the model on the device.
 // What the pair's arithmetic, the handle and its creation share with the anti-aliased pair (kirchhoff_aa.hip): rt_kirchhoff.h.
 #include "rt_kirchhoff.h"
 
@@ -267,6 +269,31 @@ __global__ void __launch_bounds__(512) k_model_multi(KArgs A, const int8_t* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ max |x|
+// *out = the bits of max |x_i| over the finite x_i of n doubles, 0 when there is none; *out starts from 0.  A grid-stride pass,
+// 16-byte loads when x is 16-byte aligned (wide), a wave and a block reduction, one integer atomic max per block (block_max_to).
+// fmax is exact: any order gives the same bits.  The model's quantum (model_exponent) and the solver's norms read it.
+__global__ void __launch_bounds__(256) k_absmax_finite(const double* __restrict__ x, long n, bool wide, unsigned long long* __restrict__ out) {
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x, gsz = (long)gridDim.x * 256;
+    double m = 0.0;
+    auto take = [&](double v) {
+        const double a = fabs(v);
+        m = a < INFINITY ? fmax(m, a) : m;                    // NaN fails the compare
+    };
+    if (wide) {
+        const double2* x2 = (const double2*)x;
+        for (long i = gid; i < n / 2; i += gsz) {
+            const double2 v = x2[i];
+            take(v.x);
+            take(v.y);
+        }
+        if ((n & 1) && gid == 0) take(x[n - 1]);
+    } else {
+        for (long i = gid; i < n; i += gsz) take(x[i]);
+    }
+    block_max_to(out, m);
+}
+
 // The kernel of (karr, amp, bins, phase): the flags become template arguments one at a time.
 struct MultiLaunch {
     dim3 grid, blk;
@@ -325,17 +352,21 @@ RTMI_EXPORT int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params* m
     return create_impl(who, &kp, mp->karr, T, amp, theta, kmah, isrc, irec, w, out);
 }
 
-RTMI_EXPORT int rtmi_kirchhoff_migrate(rtmi_kirchhoff* k, const double* data, double* image, rtmi_kirchhoff_stats* st) {
-    const char* who = "rtmi_kirchhoff_migrate";
-    RTMI_ARG(k, "null handle");
-    RTMI_ARG(data, "null data");
-    RTMI_ARG(image, "null image");
-    RTMI_ARG(k->karr == 0, "the handle is rtmi_kirchhoff_create_multi's: call rtmi_kirchhoff_migrate2");
-    RTMI_RC(check_device(k, who));
-    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
-    const double t_up = now_ms();
-    RTMI_HIP(hipMemcpy(k->data, data, N * nt * sizeof(double), hipMemcpyHostToDevice));
-    const double upload_ms = now_ms() - t_up;
+// ------------------------------------------------------------------------------------------------------------ device pointers
+int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cus, const double* d_x, size_t n, double* out) {
+    RTMI_HIP(hipMemsetAsync(red, 0, sizeof(unsigned long long), nullptr));
+    const bool wide = ((uintptr_t)d_x & 15) == 0;
+    hipLaunchKernelGGL(k_absmax_finite, stride_blocks(cus, n, 2), dim3(256), 0, nullptr, d_x, (long)n, wide, red);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipMemcpy(out, red, sizeof(double), hipMemcpyDeviceToHost));         // the bits of a double
+    return RTMI_OK;
+}
+
+int rtmi_internal_kirchhoff_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
+                                        rtmi_kirchhoff_stats* st, bool counts) {
+    if (k->nlev) return rtmi_internal_kirchhoff_aa_migrate_dev(k, who, d0, d1, d_image, st, counts);
+    const size_t N = (size_t)k->kp.N, nn = k->nn;
+    const bool phase = k->kmah != nullptr;
     EventMarks<2> ev;
     RTMI_HIP(ev.create());
     const int BS = migrate_block(k->nb);
@@ -343,23 +374,160 @@ RTMI_EXPORT int rtmi_kirchhoff_migrate(rtmi_kirchhoff* k, const double* data, do
     const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
     const size_t lds = bins ? (size_t)k->nb * BS * sizeof(double) : 0;
     const KArgs A = k->args();
+    MultiLaunch L{};
+    L.grid = grid;
+    L.blk = blk;
+    L.lds = lds;
+    L.A = A;
+    L.kmah = k->kmah;
+    L.in0 = d0;
+    L.in1 = phase ? d1 : nullptr;
+    L.out0 = d_image;
+    L.counts = k->counts;
     RTMI_HIP(ev.mark(0));
-    if (has_amp && bins) hipLaunchKernelGGL((k_migrate<true, true>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
-    else if (has_amp) hipLaunchKernelGGL((k_migrate<true, false>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
-    else if (bins) hipLaunchKernelGGL((k_migrate<false, true>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
-    else hipLaunchKernelGGL((k_migrate<false, false>), grid, blk, lds, nullptr, A, k->data, k->image, k->counts);
+    if (k->karr) launch_multi<false>(k->karr, has_amp, bins, phase, L);
+    else if (has_amp && bins) hipLaunchKernelGGL((k_migrate<true, true>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
+    else if (has_amp) hipLaunchKernelGGL((k_migrate<true, false>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
+    else if (bins) hipLaunchKernelGGL((k_migrate<false, true>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
+    else hipLaunchKernelGGL((k_migrate<false, false>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(ev.mark(1));
     RTMI_HIP(ev.wait(1));
-    RTMI_HIP(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
+        const int kk = k->karr ? k->karr * k->karr : 1;
         *st = rtmi_kirchhoff_stats{};
         RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
-        st->upload_ms = upload_ms;
-        st->pairs = (int64_t)(N * nn);
-        RTMI_RC(read_counts(k, grid.x, &st->contributing, who));
+        st->pairs = (int64_t)(N * nn) * kk;
+        if (counts) RTMI_RC(read_counts(k, grid.x, &st->contributing, who));
     }
     return RTMI_OK;
+}
+
+int rtmi_internal_kirchhoff_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, double* d0, double* d1,
+                                      rtmi_kirchhoff_stats* st, bool counts) {
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
+    // the quantum: one bound on one contribution for every kind of handle (DESIGN.md 19 on the number of contributions)
+    double max_m = 0.0;
+    RTMI_RC(rtmi_internal_absmax_finite(who, k->red, k->cus, d_model, nm, &max_m));
+    const int e = model_exponent(k, max_m);
+    if (k->nlev) return rtmi_internal_kirchhoff_aa_model_dev(k, who, d_model, e, d0, d1, st, counts);
+    const bool phase = k->kmah != nullptr;
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    const size_t window = phase ? kWindow / 2 : kWindow;      // two channels share the 64 KiB
+    const int W = (int)(nt < window ? nt : window);
+    const dim3 grid((unsigned)N), blk(phase ? 512 : 256);
+    const size_t lds = (size_t)W * (phase ? 4 : 2) * sizeof(unsigned long long);
+    const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
+    const KArgs A = k->args();
+    MultiLaunch L{};
+    L.W = W;
+    L.e = e;
+    L.grid = grid;
+    L.blk = blk;
+    L.lds = lds;
+    L.A = A;
+    L.kmah = k->kmah;
+    L.in0 = d_model;
+    L.out0 = d0;
+    L.out1 = phase ? d1 : nullptr;
+    L.counts = k->counts;
+    RTMI_HIP(ev.mark(0));
+    if (k->karr) launch_multi<true>(k->karr, has_amp, bins, phase, L);
+    else if (has_amp && bins) hipLaunchKernelGGL((k_model<true, true>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
+    else if (has_amp) hipLaunchKernelGGL((k_model<true, false>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
+    else if (bins) hipLaunchKernelGGL((k_model<false, true>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
+    else hipLaunchKernelGGL((k_model<false, false>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    if (st) {
+        const int kk = k->karr ? k->karr * k->karr : 1;
+        *st = rtmi_kirchhoff_stats{};
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
+        st->pairs = (int64_t)(N * nn) * kk;
+        st->scale_exp = e;
+        if (counts) RTMI_RC(read_counts(k, N, &st->contributing, who));
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_migrate_dev(rtmi_kirchhoff* k, const double* d_data0, const double* d_data1, double* d_image,
+                                           rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_migrate_dev";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(d_data0, "null d_data0");
+    RTMI_ARG(d_image, "null d_image");
+    RTMI_ARG(d_data1 || !k->kmah, "null d_data1 on a handle that has kmah");
+    RTMI_RC(check_device(k, who));
+    const size_t per = (size_t)k->kp.N * (size_t)k->kp.nt * sizeof(double);
+    RTMI_RC(check_device_pointer(k, who, d_data0, per, "d_data0"));
+    if (k->kmah) RTMI_RC(check_device_pointer(k, who, d_data1, per, "d_data1"));
+    RTMI_RC(check_device_pointer(k, who, d_image, (size_t)k->nb * k->nn * sizeof(double), "d_image"));
+    return rtmi_internal_kirchhoff_migrate_dev(k, who, d_data0, d_data1, d_image, st, true);
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_model_dev(rtmi_kirchhoff* k, const double* d_model, double* d_data0, double* d_data1,
+                                         rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_model_dev";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(d_model, "null d_model");
+    RTMI_ARG(d_data0, "null d_data0");
+    RTMI_ARG(d_data1 || !k->kmah, "null d_data1 on a handle that has kmah");
+    RTMI_RC(check_device(k, who));
+    const size_t per = (size_t)k->kp.N * (size_t)k->kp.nt * sizeof(double);
+    const bool two = k->karr >= 1 && d_data1;                 // on a handle of rtmi_kirchhoff_create d_data1 is ignored
+    RTMI_RC(check_device_pointer(k, who, d_model, (size_t)k->nb * k->nn * sizeof(double), "d_model"));
+    RTMI_RC(check_device_pointer(k, who, d_data0, per, "d_data0"));
+    if (two) RTMI_RC(check_device_pointer(k, who, d_data1, per, "d_data1"));
+    RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, d_model, d_data0, d_data1, st, true));
+    if (two && !k->kmah) RTMI_HIP(hipMemset(d_data1, 0, per)); // without kmah every pair is of channel 0
+    return RTMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host pointers
+// upload into the handle's staging buffers, the body above on them, download
+namespace {
+
+int migrate_host(rtmi_kirchhoff* k, const char* who, const double* data0, const double* data1, double* image, rtmi_kirchhoff_stats* st) {
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
+    const bool phase = k->kmah != nullptr;
+    const double t_up = now_ms();
+    RTMI_HIP(hipMemcpy(k->data, data0, N * nt * sizeof(double), hipMemcpyHostToDevice));
+    if (phase) RTMI_HIP(hipMemcpy(k->data + N * nt, data1, N * nt * sizeof(double), hipMemcpyHostToDevice));
+    const double upload_ms = now_ms() - t_up;
+    RTMI_RC(rtmi_internal_kirchhoff_migrate_dev(k, who, k->data, phase ? k->data + N * nt : nullptr, k->image, st, true));
+    RTMI_HIP(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) st->upload_ms = upload_ms;
+    return RTMI_OK;
+}
+
+int model_host(rtmi_kirchhoff* k, const char* who, const double* model, double* data0, double* data1, rtmi_kirchhoff_stats* st) {
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nm = (size_t)k->nb * k->nn;
+    const bool phase = k->kmah != nullptr;
+    const double t_up = now_ms();
+    RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
+    const double upload_ms = now_ms() - t_up;
+    RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, k->image, k->data, phase ? k->data + N * nt : nullptr, st, true));
+    RTMI_HIP(hipMemcpy(data0, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (data1) {
+        if (phase) RTMI_HIP(hipMemcpy(data1, k->data + N * nt, N * nt * sizeof(double), hipMemcpyDeviceToHost));
+        else std::memset(data1, 0, N * nt * sizeof(double));  // without kmah every pair is of channel 0
+    }
+    if (st) st->upload_ms = upload_ms;
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_kirchhoff_migrate(rtmi_kirchhoff* k, const double* data, double* image, rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_migrate";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(data, "null data");
+    RTMI_ARG(image, "null image");
+    RTMI_ARG(k->karr == 0, "the handle is rtmi_kirchhoff_create_multi's: call rtmi_kirchhoff_migrate2");
+    RTMI_RC(check_device(k, who));
+    return migrate_host(k, who, data, nullptr, image, st);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_model(rtmi_kirchhoff* k, const double* model, double* data, rtmi_kirchhoff_stats* st) {
@@ -369,36 +537,7 @@ RTMI_EXPORT int rtmi_kirchhoff_model(rtmi_kirchhoff* k, const double* model, dou
     RTMI_ARG(data, "null data");
     RTMI_ARG(k->karr == 0, "the handle is rtmi_kirchhoff_create_multi's: call rtmi_kirchhoff_model2");
     RTMI_RC(check_device(k, who));
-    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
-    const int e = model_exponent(k, model, nm);
-    const double t_up = now_ms();
-    RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
-    const double upload_ms = now_ms() - t_up;
-    EventMarks<2> ev;
-    RTMI_HIP(ev.create());
-    const int W = (int)(nt < (size_t)kWindow ? nt : (size_t)kWindow);
-    const dim3 grid((unsigned)N), blk(256);
-    const size_t lds = (size_t)W * 2 * sizeof(unsigned long long);
-    const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
-    const KArgs A = k->args();
-    RTMI_HIP(ev.mark(0));
-    if (has_amp && bins) hipLaunchKernelGGL((k_model<true, true>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
-    else if (has_amp) hipLaunchKernelGGL((k_model<true, false>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
-    else if (bins) hipLaunchKernelGGL((k_model<false, true>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
-    else hipLaunchKernelGGL((k_model<false, false>), grid, blk, lds, nullptr, A, k->image, e, W, k->data, k->counts);
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(ev.mark(1));
-    RTMI_HIP(ev.wait(1));
-    RTMI_HIP(hipMemcpy(data, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (st) {
-        *st = rtmi_kirchhoff_stats{};
-        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
-        st->upload_ms = upload_ms;
-        st->pairs = (int64_t)(N * nn);
-        st->scale_exp = e;
-        RTMI_RC(read_counts(k, N, &st->contributing, who));
-    }
-    return RTMI_OK;
+    return model_host(k, who, model, data, nullptr, st);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_migrate2(rtmi_kirchhoff* k, const double* data0, const double* data1, double* image,
@@ -410,41 +549,7 @@ RTMI_EXPORT int rtmi_kirchhoff_migrate2(rtmi_kirchhoff* k, const double* data0, 
     RTMI_ARG(k->karr >= 1, "the handle is rtmi_kirchhoff_create's: call rtmi_kirchhoff_migrate");
     RTMI_ARG(data1 || !k->kmah, "null data1 on a handle that has kmah");
     RTMI_RC(check_device(k, who));
-    if (k->nlev) return rtmi_internal_kirchhoff_aa_migrate2(k, data0, data1, image, st);
-    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
-    const bool phase = k->kmah != nullptr;
-    const double t_up = now_ms();
-    RTMI_HIP(hipMemcpy(k->data, data0, N * nt * sizeof(double), hipMemcpyHostToDevice));
-    if (phase) RTMI_HIP(hipMemcpy(k->data + N * nt, data1, N * nt * sizeof(double), hipMemcpyHostToDevice));
-    const double upload_ms = now_ms() - t_up;
-    EventMarks<2> ev;
-    RTMI_HIP(ev.create());
-    const int BS = migrate_block(k->nb);
-    const bool bins = k->kp.nbin > 0;
-    MultiLaunch L{};
-    L.grid = dim3((unsigned)((nn + BS - 1) / BS));
-    L.blk = dim3(BS);
-    L.lds = bins ? (size_t)k->nb * BS * sizeof(double) : 0;
-    L.A = k->args();
-    L.kmah = k->kmah;
-    L.in0 = k->data;
-    L.in1 = phase ? k->data + N * nt : nullptr;
-    L.out0 = k->image;
-    L.counts = k->counts;
-    RTMI_HIP(ev.mark(0));
-    launch_multi<false>(k->karr, k->amp != nullptr, bins, phase, L);
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(ev.mark(1));
-    RTMI_HIP(ev.wait(1));
-    RTMI_HIP(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
-    if (st) {
-        *st = rtmi_kirchhoff_stats{};
-        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
-        st->upload_ms = upload_ms;
-        st->pairs = (int64_t)(N * nn) * k->karr * k->karr;
-        RTMI_RC(read_counts(k, L.grid.x, &st->contributing, who));
-    }
-    return RTMI_OK;
+    return migrate_host(k, who, data0, data1, image, st);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_model2(rtmi_kirchhoff* k, const double* model, double* data0, double* data1, rtmi_kirchhoff_stats* st) {
@@ -455,48 +560,7 @@ RTMI_EXPORT int rtmi_kirchhoff_model2(rtmi_kirchhoff* k, const double* model, do
     RTMI_ARG(k->karr >= 1, "the handle is rtmi_kirchhoff_create's: call rtmi_kirchhoff_model");
     RTMI_ARG(data1 || !k->kmah, "null data1 on a handle that has kmah");
     RTMI_RC(check_device(k, who));
-    if (k->nlev) return rtmi_internal_kirchhoff_aa_model2(k, model, data0, data1, st);
-    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
-    const bool phase = k->kmah != nullptr;
-    // the quantum: rtmi_kirchhoff_model's, from the same bound on one contribution (DESIGN.md 19 on the number of contributions)
-    const int e = model_exponent(k, model, nm);
-    const double t_up = now_ms();
-    RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
-    const double upload_ms = now_ms() - t_up;
-    EventMarks<2> ev;
-    RTMI_HIP(ev.create());
-    const size_t window = phase ? kWindow / 2 : kWindow;      // two channels share the 64 KiB
-    MultiLaunch L{};
-    L.W = (int)(nt < window ? nt : window);
-    L.e = e;
-    L.grid = dim3((unsigned)N);
-    L.blk = dim3(phase ? 512 : 256);
-    L.lds = (size_t)L.W * (phase ? 4 : 2) * sizeof(unsigned long long);
-    L.A = k->args();
-    L.kmah = k->kmah;
-    L.in0 = k->image;
-    L.out0 = k->data;
-    L.out1 = phase ? k->data + N * nt : nullptr;
-    L.counts = k->counts;
-    RTMI_HIP(ev.mark(0));
-    launch_multi<true>(k->karr, k->amp != nullptr, k->kp.nbin > 0, phase, L);
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(ev.mark(1));
-    RTMI_HIP(ev.wait(1));
-    RTMI_HIP(hipMemcpy(data0, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (data1) {
-        if (phase) RTMI_HIP(hipMemcpy(data1, k->data + N * nt, N * nt * sizeof(double), hipMemcpyDeviceToHost));
-        else std::memset(data1, 0, N * nt * sizeof(double));  // without kmah every pair is of channel 0
-    }
-    if (st) {
-        *st = rtmi_kirchhoff_stats{};
-        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
-        st->upload_ms = upload_ms;
-        st->pairs = (int64_t)(N * nn) * k->karr * k->karr;
-        st->scale_exp = e;
-        RTMI_RC(read_counts(k, N, &st->contributing, who));
-    }
-    return RTMI_OK;
+    return model_host(k, who, model, data0, data1, st);
 }
 
 RTMI_EXPORT void rtmi_kirchhoff_destroy(rtmi_kirchhoff* k) { delete k; }

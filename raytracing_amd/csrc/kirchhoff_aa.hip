@@ -9,7 +9,8 @@
 //   k_model_aa    k_model_multi with accumulators [level][channel][lo|hi][W] in LDS; each window's spreads go to the handle's
 //                 [nlev][channels][N][nt] buffer, one rounding each.
 //   k_aa_gather   one lane per sample: ch = S_0 + sum over l >= 1 of F_hw[l] S_l, l ascending, in place over level 0.
-// The handle's one buffer `data` [nlev][channels][N][nt] is the bank in migrate2 and the spreads in model2.
+// The handle's one buffer `data` [nlev][channels][N][nt] is the bank in migrate2 and the spreads in model2.  One launch path, on
+// device pointers (kirchhoff.hip's rtmi_internal_kirchhoff_migrate_dev / _model_dev lead here).
 #include "rt_kirchhoff.h"
 
 namespace {
@@ -327,15 +328,15 @@ RTMI_EXPORT int rtmi_kirchhoff_aa_filter(rtmi_kirchhoff* k, const double* data, 
     return RTMI_OK;
 }
 
-int rtmi_internal_kirchhoff_aa_migrate2(rtmi_kirchhoff* k, const double* data0, const double* data1, double* image,
-                                        rtmi_kirchhoff_stats* st) {
-    const char* who = "rtmi_kirchhoff_migrate2";
+// The handle's level 0 is where k_aa_filter reads the caller's channels and k_aa_gather leaves the traces: device pointers other
+// than the handle's own staging are copied to and from it on the device.
+int rtmi_internal_kirchhoff_aa_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
+                                           rtmi_kirchhoff_stats* st, bool counts) {
     const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
     const bool phase = k->kmah != nullptr;
-    const double t_up = now_ms();
-    RTMI_HIP(hipMemcpy(k->data, data0, N * nt * sizeof(double), hipMemcpyHostToDevice));
-    if (phase) RTMI_HIP(hipMemcpy(k->data + N * nt, data1, N * nt * sizeof(double), hipMemcpyHostToDevice));
-    const double upload_ms = now_ms() - t_up;
+    if (d0 != k->data) RTMI_HIP(hipMemcpyAsync(k->data, d0, N * nt * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+    if (phase && d1 != k->data + N * nt)
+        RTMI_HIP(hipMemcpyAsync(k->data + N * nt, d1, N * nt * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
     EventMarks<3> ev;
     RTMI_HIP(ev.create());
     const int BS = migrate_block(k->nb);
@@ -348,7 +349,7 @@ int rtmi_internal_kirchhoff_aa_migrate2(rtmi_kirchhoff* k, const double* data0, 
     L.Q = aa_args(k);
     L.kmah = k->kmah;
     L.buf = k->data;
-    L.image = k->image;
+    L.image = d_image;
     L.counts = k->counts;
     RTMI_HIP(ev.mark(0));
     if (k->nlev > 1)
@@ -360,28 +361,22 @@ int rtmi_internal_kirchhoff_aa_migrate2(rtmi_kirchhoff* k, const double* data0, 
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(ev.mark(2));
     RTMI_HIP(ev.wait(2));
-    RTMI_HIP(hipMemcpy(image, k->image, (size_t)k->nb * nn * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         *st = rtmi_kirchhoff_stats{};
         double filter_ms = 0.0;
         RTMI_HIP(ev.ms(0, 2, &st->kernel_ms));
         RTMI_HIP(ev.ms(0, 1, &filter_ms));
         st->reserved[0] = to_ns(filter_ms);
-        st->upload_ms = upload_ms;
         st->pairs = (int64_t)(N * nn) * k->karr * k->karr;
-        RTMI_RC(read_counts(k, L.grid.x, &st->contributing, who));
+        if (counts) RTMI_RC(read_counts(k, L.grid.x, &st->contributing, who));
     }
     return RTMI_OK;
 }
 
-int rtmi_internal_kirchhoff_aa_model2(rtmi_kirchhoff* k, const double* model, double* data0, double* data1, rtmi_kirchhoff_stats* st) {
-    const char* who = "rtmi_kirchhoff_model2";
-    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
+int rtmi_internal_kirchhoff_aa_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, int e, double* d0, double* d1,
+                                         rtmi_kirchhoff_stats* st, bool counts) {
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn;
     const bool phase = k->kmah != nullptr;
-    const int e = model_exponent(k, model, nm);
-    const double t_up = now_ms();
-    RTMI_HIP(hipMemcpy(k->image, model, nm * sizeof(double), hipMemcpyHostToDevice));
-    const double upload_ms = now_ms() - t_up;
     EventMarks<3> ev;
     RTMI_HIP(ev.create());
     const size_t window = (size_t)kWindow / ((size_t)k->nlev * channels(k));        // every level and channel shares the 64 KiB
@@ -395,7 +390,7 @@ int rtmi_internal_kirchhoff_aa_model2(rtmi_kirchhoff* k, const double* model, do
     L.A = k->args();
     L.Q = aa_args(k);
     L.kmah = k->kmah;
-    L.model = k->image;
+    L.model = d_model;
     L.buf = k->data;
     L.counts = k->counts;
     RTMI_HIP(ev.mark(0));
@@ -408,21 +403,17 @@ int rtmi_internal_kirchhoff_aa_model2(rtmi_kirchhoff* k, const double* model, do
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(ev.mark(2));
     RTMI_HIP(ev.wait(2));
-    RTMI_HIP(hipMemcpy(data0, k->data, N * nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (data1) {
-        if (phase) RTMI_HIP(hipMemcpy(data1, k->data + N * nt, N * nt * sizeof(double), hipMemcpyDeviceToHost));
-        else std::memset(data1, 0, N * nt * sizeof(double));  // without kmah every pair is of channel 0
-    }
+    if (d0 != k->data) RTMI_HIP(hipMemcpy(d0, k->data, N * nt * sizeof(double), hipMemcpyDeviceToDevice));
+    if (phase && d1 != k->data + N * nt) RTMI_HIP(hipMemcpy(d1, k->data + N * nt, N * nt * sizeof(double), hipMemcpyDeviceToDevice));
     if (st) {
         *st = rtmi_kirchhoff_stats{};
         double gather_ms = 0.0;
         RTMI_HIP(ev.ms(0, 2, &st->kernel_ms));
         RTMI_HIP(ev.ms(1, 2, &gather_ms));
         st->reserved[0] = to_ns(gather_ms);
-        st->upload_ms = upload_ms;
         st->pairs = (int64_t)(N * nn) * k->karr * k->karr;
         st->scale_exp = e;
-        RTMI_RC(read_counts(k, N, &st->contributing, who));
+        if (counts) RTMI_RC(read_counts(k, N, &st->contributing, who));
     }
     return RTMI_OK;
 }

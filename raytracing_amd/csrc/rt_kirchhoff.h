@@ -1,7 +1,8 @@
-// rt_kirchhoff.h -- what the two Kirchhoff units share (kirchhoff.hip: the plain pairs; kirchhoff_aa.hip: the anti-aliased pair):
-// the kernel arguments, one (trace, node) pair's arithmetic, the arrivals of a table at a node and their phase, the handle, its
-// argument checks and uploads.  Everything but the handle and the two cross-unit entries is in an anonymous namespace: each unit
-// gets its own copy, as with rtmi_host.h.  DESIGN.md sections 14, 19 and 20.
+// rt_kirchhoff.h -- what the Kirchhoff units share (kirchhoff.hip: the plain pairs; kirchhoff_aa.hip: the anti-aliased pair;
+// kirchhoff_lsqr.hip: least-squares migration over either): the kernel arguments, one (trace, node) pair's arithmetic, the arrivals
+// of a table at a node and their phase, a block's exact maximum, the handle, its argument checks and uploads.  Everything but the
+// handle and the cross-unit entries is in an anonymous namespace: each unit gets its own copy, as with rtmi_host.h.  DESIGN.md
+// sections 14, 19, 20 and 21.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +66,21 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     return v;
 }
 
+// The block's largest v (v >= 0, never NaN) into *slot, a double kept as its bits: non-negative doubles order as unsigned integers,
+// so one integer atomic max per block is the second stage of the reduction, and fmax is exact: the same bits in every schedule.
+// The slot starts from 0.  Blocks of 256 lanes.
+__device__ __forceinline__ void block_max_to(unsigned long long* slot, double v) {
+    __shared__ double wmax[4];
+    for (int off = 1; off < 64; off <<= 1) v = fmax(v, __shfl_xor(v, off));
+    const int tid = (int)threadIdx.x;
+    if ((tid & 63) == 0) wmax[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0) {
+        const double m = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+        if (m > 0.0) atomicMax(slot, (unsigned long long)__double_as_longlong(m));
+    }
+}
+
 // kmah on the device: the caustic count mod 4 as int8, -1 where the table's value is not a finite non-negative integer.
 constexpr int8_t kBadKmah = -1;
 
@@ -108,6 +124,8 @@ struct rtmi_kirchhoff {
     int8_t* kmah = nullptr;                   // multi: [P][K][nn], the count mod 4 or kBadKmah; NULL without kmah
     unsigned long long* counts = nullptr;     // max(N, migrate's blocks)
     size_t ncounts = 0;
+    unsigned long long* red = nullptr;        // kRedWords words a reduction leaves its result in (k_absmax_finite, kirchhoff_lsqr.hip)
+    int cus = 1;                              // the device's compute units: the grid-stride kernels launch a small multiple of it
     // rtmi_kirchhoff_create_aa's handle (nlev >= 1; 0 on every other handle): data is [nlev][channels][N][nt], level 0 the
     // caller's channels, levels 1 .. nlev - 1 the bank of migrate2 and, in model2, the spreads of every level
     int nlev = 0;
@@ -116,7 +134,7 @@ struct rtmi_kirchhoff {
     double* pt = nullptr;                     // [P][K][nn]
     ~rtmi_kirchhoff() {
         for (void* p : {(void*)T, (void*)amp, (void*)theta, (void*)w, (void*)data, (void*)image, (void*)isrc, (void*)irec, (void*)kmah, (void*)counts,
-                        (void*)pt})
+                        (void*)pt, (void*)red})
             if (p) (void)hipFree(p);
     }
     KArgs args() const {
@@ -125,13 +143,51 @@ struct rtmi_kirchhoff {
     }
 };
 
-// migrate2 / model2 on a handle of rtmi_kirchhoff_create_aa (kirchhoff_aa.hip); the callers have checked the arguments and the device
-int rtmi_internal_kirchhoff_aa_migrate2(rtmi_kirchhoff* k, const double* data0, const double* data1, double* image, rtmi_kirchhoff_stats* st);
-int rtmi_internal_kirchhoff_aa_model2(rtmi_kirchhoff* k, const double* model, double* data0, double* data1, rtmi_kirchhoff_stats* st);
+// The pair on device pointers, the one launch path of every kernel (kirchhoff.hip): any kind of handle, the
+// callers have checked the arguments and the device.  d1 is read, or written, only on a handle with kmah.  The handle's own
+// staging buffers may be passed (the host-pointer entries do): nothing is copied then.  st may be NULL; counts: also read back
+// and sum the per-block counts into st->contributing (N words), which a solver's loop leaves out.  upload_ms is 0.
+int rtmi_internal_kirchhoff_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
+                                        rtmi_kirchhoff_stats* st, bool counts);
+int rtmi_internal_kirchhoff_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, double* d0, double* d1,
+                                      rtmi_kirchhoff_stats* st, bool counts);
+// max |x_i| over the finite values of n doubles on the device (0 when there is none): k_absmax_finite and an 8-byte read-back.
+// red: a device word for the result (the handle's); cus: the device's compute units
+int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cus, const double* d_x, size_t n, double* out);
+// the same two on a handle of rtmi_kirchhoff_create_aa (kirchhoff_aa.hip); e: the model's quantum, taken by the caller
+int rtmi_internal_kirchhoff_aa_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
+                                           rtmi_kirchhoff_stats* st, bool counts);
+int rtmi_internal_kirchhoff_aa_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, int e, double* d0, double* d1,
+                                         rtmi_kirchhoff_stats* st, bool counts);
 
 namespace {
 
+constexpr size_t kRedWords = 8;
+
 int migrate_block(int nb) { return nb > 16 ? 128 : 256; }    // [bin][lane] fp64 in LDS stays within 32 KiB
+
+// blocks of 256 lanes for a grid-stride pass over n items, each lane taking `per` of them at a time: at most 4 blocks per CU
+dim3 stride_blocks(int cus, size_t n, size_t per) {
+    const size_t want = (n + 256 * per - 1) / (256 * per), cap = (size_t)4 * (size_t)cus;
+    return dim3((unsigned)(want < 1 ? 1 : want < cap ? want : cap));
+}
+
+// `bytes` at p are memory of the handle's device (hipPointerGetAttributes), and the allocation holds them all
+int check_device_pointer(const rtmi_kirchhoff* k, const char* who, const void* p, size_t bytes, const char* name) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();             // a plain host pointer: not an error of the runtime's to keep
+    const bool ok = e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == k->device;
+    RTMI_ARG(ok, std::string(name) + " is not memory of the handle's device");
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        RTMI_ARG(false, std::string(name) + ": the extent of its allocation could not be read");
+    }
+    RTMI_ARG((const char*)p + bytes <= (const char*)base + size, std::string(name) + " is shorter than the call needs");
+    return RTMI_OK;
+}
 
 int check_device(const rtmi_kirchhoff* k, const char* who) {
     int dev = -1;
@@ -149,11 +205,9 @@ int read_counts(const rtmi_kirchhoff* k, size_t n, int64_t* total, const char* w
     return RTMI_OK;
 }
 
-// model's quantum: |contribution| <= max|w| max|amp|^2 max|m| = f 2^ex with f in [0.5, 1), so it is below 2^57 quanta 2^(ex - 57)
-int model_exponent(const rtmi_kirchhoff* k, const double* model, size_t nm) {
-    double max_m = 0.0;
-    for (size_t i = 0; i < nm; i++)
-        if (std::isfinite(model[i])) max_m = std::fmax(max_m, std::fabs(model[i]));
+// model's quantum: |contribution| <= max|w| max|amp|^2 max|m| = f 2^ex with f in [0.5, 1), so it is below 2^57 quanta 2^(ex - 57);
+// max_m: max|m| over the finite values (rtmi_internal_absmax_finite)
+int model_exponent(const rtmi_kirchhoff* k, double max_m) {
     const double bound = (k->max_w * k->max_amp) * k->max_amp * max_m;
     return std::isfinite(bound) ? rt::fix_exponent(bound) : 1025 - rt::kFixBits;
 }
@@ -235,6 +289,8 @@ int create_impl(const char* who, const rtmi_kirchhoff_params* kp, int karr, cons
     };
     hipError_t e = hipGetDevice(&k->device);
     if (e != hipSuccess) return fail(RTMI_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e));
+    e = hipDeviceGetAttribute(&k->cus, hipDeviceAttributeMultiprocessorCount, k->device);
+    if (e != hipSuccess || k->cus < 1) return fail(RTMI_ERR_HIP, std::string("hipDeviceGetAttribute: ") + hipGetErrorString(e));
     auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes); };
     struct { void** p; size_t bytes; const void* src; } bufs[] = {
         {(void**)&k->T, P * nn * sizeof(double), T},
@@ -248,6 +304,7 @@ int create_impl(const char* who, const rtmi_kirchhoff_params* kp, int karr, cons
         {(void**)&k->data, levels * (kmah ? 2 : 1) * N * nt * sizeof(double), nullptr},   // with kmah: channel 0, then channel 1
         {(void**)&k->image, (size_t)nb * nn * sizeof(double), nullptr},
         {(void**)&k->counts, k->ncounts * sizeof(unsigned long long), nullptr},
+        {(void**)&k->red, kRedWords * sizeof(unsigned long long), nullptr},
     };
     for (auto& b : bufs) {
         if (!b.bytes) continue;

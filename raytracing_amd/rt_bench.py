@@ -1222,7 +1222,13 @@ class Kirchhoff:
     With pt (of T's shape: dT/d(position), position_slope) the pair is anti-aliased by operator slope (rtmi_kirchhoff_create_aa,
     DESIGN.md 20): antialias = dict(hw=(0, 1, 2, 4, 8), asrc=0.0, arec=0.0, amid=0.0), the triangle half-widths of the levels in
     samples and the trace spacing along the source, receiver and midpoint axes (keys left out take these defaults).  A 3-D T is
-    then taken as K = 1; every call above works unchanged, and aa_filter(d) returns the bank [nlev, N, nt] of one channel."""
+    then taken as K = 1; every call above works unchanged, and aa_filter(d) returns the bank [nlev, N, nt] of one channel.
+    On the device, for every kind of handle:
+      migrate_device(d0, d1=None) -> image    and    model_device(m) -> data, or (ch0, ch1) on a handle with kmah
+    take and return fp64 contiguous torch tensors on the handle's device: the bits of the calls above, no copy through the host.
+      lsqr(d, iter_lim, damp=0.0, atol=0.0, btol=0.0) -> dict(x, istop, itn, r1norm, r2norm, anorm, arnorm)
+    is least-squares migration by LSQR in scipy's operation order with every vector on the device (rtmi_kirchhoff_lsqr): the data
+    go up once and x comes down once; defined bit for bit.  The library refuses a handle with kmah."""
 
     def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None, kmah=None, pt=None,
                  antialias=None):
@@ -1370,6 +1376,84 @@ class Kirchhoff:
         check(lib().rtmi_kirchhoff_aa_filter(self._open(), dptr(dd), dptr(bank)))
         return bank
 
+    def _device_tensor(self, who, t, name, size):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"Kirchhoff.{who}: {name} must be a torch tensor")
+        if t.dtype != torch.float64:
+            raise TypeError(f"Kirchhoff.{who}: {name} must be float64")
+        if t.numel() != size:
+            raise ValueError(f"Kirchhoff.{who}: {name} must have {size} values")
+        if not t.is_contiguous():
+            raise ValueError(f"Kirchhoff.{who}: {name} must be contiguous")
+        return t
+
+    def _on_device(self, who, **tensors):
+        for name, t in tensors.items():
+            if t is not None and not t.is_cuda:       # which GPU it is on, the library checks against the handle's
+                raise ValueError(f"Kirchhoff.{who}: {name} must be a tensor on a GPU, not on the host")
+
+    def migrate_device(self, d0, d1=None, stats=False):
+        """rtmi_kirchhoff_migrate_dev: channel 0 and, on a handle with kmah, channel 1 [N, nt] -> image, torch tensors on the
+        handle's device"""
+        import torch
+        who = "migrate_device"
+        self._device_tensor(who, d0, "d0", self.N * self.nt)
+        if d1 is not None:
+            self._device_tensor(who, d1, "d1", self.N * self.nt)
+        elif self.has_kmah:
+            raise ValueError("Kirchhoff.migrate_device: a handle with kmah needs d1")
+        self._on_device(who, d0=d0, d1=d1)
+        h = self._open()
+        img = torch.empty((self.nb, self.ny, self.nx), dtype=torch.float64, device=d0.device)
+        st = _lib.KirchhoffStats()
+        torch.cuda.synchronize(d0.device)              # the library works on the null stream
+        check(lib().rtmi_kirchhoff_migrate_dev(h, d0.data_ptr(), None if d1 is None else d1.data_ptr(), img.data_ptr(), C.byref(st)))
+        if self.nbin == 0:
+            img = img[0]
+        return (img, kirchhoff_stats(st)) if stats else img
+
+    def model_device(self, m, stats=False):
+        """rtmi_kirchhoff_model_dev: m [nb, ny, nx] -> data [N, nt], or (ch0, ch1) on a handle with kmah; torch tensors on the
+        handle's device"""
+        import torch
+        self._device_tensor("model_device", m, "m", self.nb * self.ny * self.nx)
+        self._on_device("model_device", m=m)
+        h = self._open()
+        d0 = torch.empty((self.N, self.nt), dtype=torch.float64, device=m.device)
+        d1 = torch.empty((self.N, self.nt), dtype=torch.float64, device=m.device) if self.has_kmah else None
+        st = _lib.KirchhoffStats()
+        torch.cuda.synchronize(m.device)
+        check(lib().rtmi_kirchhoff_model_dev(h, m.data_ptr(), d0.data_ptr(), None if d1 is None else d1.data_ptr(), C.byref(st)))
+        out = (d0, d1) if self.has_kmah else d0
+        return (out, kirchhoff_stats(st)) if stats else out
+
+    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False):
+        """rtmi_kirchhoff_lsqr: min |L x - d|^2 + damp^2 |x|^2 from x = 0, every vector on the device.  -> dict: x shaped like
+        migrate's image, istop (scipy's 0, 1, 2, 7; _lib.LSQR_RANGE: a norm left fp64's normal range), itn, r1norm, r2norm, anorm,
+        arnorm; with history=True also history [itn, 4] (alfa, beta, r1norm, arnorm after each iteration); with stats=True also
+        stats (total_ms, operator_ms, vector_ms, bytes_device)."""
+        dd = np.ascontiguousarray(d, dtype=np.float64)
+        if dd.size != self.N * self.nt:
+            raise ValueError("Kirchhoff.lsqr: d must be [N, nt]")
+        iter_lim = int(iter_lim)
+        if iter_lim < 1:
+            raise ValueError("Kirchhoff.lsqr: iter_lim must be >= 1")
+        lp = _lib.LsqrParams()
+        lp.iter_lim, lp.damp, lp.atol, lp.btol = iter_lim, float(damp), float(atol), float(btol)
+        x = np.empty((self.nb, self.ny, self.nx))
+        hist = np.zeros((iter_lim, 4)) if history else None
+        st = _lib.LsqrStats()
+        check(lib().rtmi_kirchhoff_lsqr(self._open(), C.byref(lp), dptr(dd), dptr(x), dptr(hist), C.byref(st)))
+        out = {"x": x if self.nbin else x[0], "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm,
+               "anorm": st.anorm, "arnorm": st.arnorm}
+        if history:
+            out["history"] = hist[:st.itn].copy()
+        if stats:
+            out["stats"] = {"total_ms": st.total_ms, "operator_ms": st.operator_ms, "vector_ms": st.vector_ms,
+                            "bytes_device": int(st.bytes_device)}
+        return out
+
     def as_linear_operator(self):
         from scipy.sparse.linalg import LinearOperator
         return LinearOperator(self.shape, matvec=lambda m: self.model(m).reshape(-1),
@@ -1385,6 +1469,15 @@ class Kirchhoff:
             self.close()
         except Exception:
             pass
+
+
+def debug_fix_norm(x):
+    """rtmi_debug_fix_norm: the device's order-independent norm of a host vector -> (norm, e)"""
+    xx = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    nrm = C.c_double()
+    e = C.c_int32()
+    check(lib().rtmi_debug_fix_norm(dptr(xx), xx.size, C.byref(nrm), C.byref(e)))
+    return nrm.value, int(e.value)
 
 
 def first_arrivals(selected_func, field, sources, line, receivers_u, **kw):

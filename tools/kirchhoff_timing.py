@@ -15,7 +15,11 @@ time per pair relative to the one-arrival kernel.
 turn: pt from the closed-form launch angles, arec = the position spacing (the case is shot gathers), the levels the first NLEV
 of 0, 1, 2, 4, 8, 16, 32, 64.  It prints, for migrate and model, the plain kernel, the anti-aliased pair kernel and its filter
 (migrate) or sum over the levels (model) apart, their ratio, and the bytes floor with the extra table and the bank.
-Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV]"""
+--lsqr ITERS times least-squares migration on the same case, in one process: the host loop, scipy's lsqr over
+as_linear_operator() with atol = btol = 0 and iter_lim = ITERS, and the device loop, Kirchhoff.lsqr, on the same data (the model
+of a random reflectivity).  It prints, per iteration: the wall time of each loop, the sum of the two operators' kernel_ms in the
+device loop, its vector_ms, and what the device loop's iteration spends above the two kernels.
+Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV] [--lsqr ITERS]"""
 import argparse
 import json
 import os
@@ -200,6 +204,38 @@ def run_antialias(K, nlev, reps):
     plain.close(); anti.close()
 
 
+def run_lsqr(iters):
+    from scipy.sparse.linalg import lsqr
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, _ = tables(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    op = rb.Kirchhoff(T, isrc, irec, nt, dt)
+    d = op.model(np.random.default_rng(1).standard_normal(T.shape[1:]))
+    op.lsqr(d, 1)                                                # warm-up: code objects, both operators
+    t0 = time.perf_counter()
+    dev = op.lsqr(d, iters, stats=True)
+    t1 = time.perf_counter()
+    host = lsqr(op.as_linear_operator(), d.reshape(-1), atol=0, btol=0, iter_lim=iters)
+    t2 = time.perf_counter()
+    op.close()
+    st = dev["stats"]
+    n = dev["itn"]
+    # the device loop applies each operator once more than it iterates (the first L^T); scipy's loop does the same
+    dev_ms, host_ms = (t1 - t0) * 1e3 / n, (t2 - t1) * 1e3 / host[2]
+    print(json.dumps({"what": f"least-squares migration, {iters} iterations", "N": len(isrc), "nodes": T[0].size, "nt": nt,
+                      "itn_device": n, "itn_host": int(host[2]), "device_loop_wall_ms_per_iteration": dev_ms,
+                      "host_loop_wall_ms_per_iteration": host_ms, "host_over_device": host_ms / dev_ms,
+                      "operators_kernel_ms_per_iteration": st["operator_ms"] / n, "vector_ms_per_iteration": st["vector_ms"] / n,
+                      "device_loop_above_kernels_ms_per_iteration": dev_ms - st["operator_ms"] / n,
+                      "bytes_device": st["bytes_device"], "r1norm_device": dev["r1norm"], "r1norm_host": float(host[3]),
+                      "x_max_rel_diff": float(np.max(np.abs(dev["x"].reshape(-1) - host[0])) / np.max(np.abs(host[0])))}), flush=True)
+
+
 def restatement():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import kirchhoff_ref as K
@@ -219,8 +255,11 @@ if __name__ == "__main__":
     ap.add_argument("--case", choices=CASES + ("restatement",))
     ap.add_argument("--arrivals", type=int, choices=(1, 2, 3, 4))
     ap.add_argument("--antialias", type=int, choices=range(1, 9), metavar="NLEV")
+    ap.add_argument("--lsqr", type=int, metavar="ITERS")
     a = ap.parse_args()
-    if a.antialias:
+    if a.lsqr:
+        run_lsqr(a.lsqr)
+    elif a.antialias:
         run_antialias(a.arrivals or 1, a.antialias, a.reps)
     elif a.arrivals:
         run_arrivals(a.arrivals, a.reps)
