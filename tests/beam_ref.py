@@ -86,10 +86,18 @@ def ray_rows(s_ray, tube, o, nr, w_o, eps):
     return dict(x=x, y=y, c=np.cos(th), s=np.sin(th), T=T, n=n, re=re, im=im, phi=phi, amp=amp, qq=qq)
 
 
+NEAR = 1e-12      # relative distance of a deciding quantity from its threshold below which a pair counts as `near`
+
+
 def gaussian_beams(s_ray, last, field, theta0, fan_size, grid, omegas, eps, cutoff=None, max_width=None, edge_taper=0.0,
-                   tube=None):
+                   tube=None, counts=None):
     """s_ray [rows, 6, R], last [R] (each ray's last written row; rows past the record are cut), field: a SplineField (or any
-    callable of its signature), theta0 [R] the launch angles.  -> u [S, nw, ny, nx] complex128 as rtmi_gaussian_beams."""
+    callable of its signature), theta0 [R] the launch angles.  -> u [S, nw, ny, nx] complex128 as rtmi_gaussian_beams.
+    counts: a dict to fill with what rtmi_beam_stats counts, from every (step, node) pair: segments (the sum over rays of
+    rows - 1), capped (steps that pass the turn test and whose uncapped q_max exceeds max_width), owned and inside (pairs before
+    and after the q_max and cutoff tests at the lowest omega), inside_per_omega, and near: the owned pairs one of whose deciding
+    quantities lies within NEAR (relative) of its threshold -- d_{i-1} or d_i against 0 relative to |X - x| + |Y - y|, q^2
+    against q_max^2, omega_min g against the cutoff -- the pairs a last-bit difference in the rows' values could flip."""
     s_ray = np.asarray(s_ray)
     rows, _, R = s_ray.shape
     last = np.minimum(np.asarray(last, dtype=np.int64), rows - 1)
@@ -106,6 +114,7 @@ def gaussian_beams(s_ray, last, field, theta0, fan_size, grid, omegas, eps, cuto
     X, Y = (a.ravel() for a in nodes(grid))
     ar = np.zeros((S, len(om), X.size))
     ai = np.zeros((S, len(om), X.size))
+    cn = dict(segments=int(last.sum()), capped=0, owned=0, inside=0, inside_per_omega=[0] * len(om), near=0)
     for o in range(R):
         s = o // M
         v = ray_rows(s_ray, tube, o, int(last[o]) + 1, w[o], eps)
@@ -114,6 +123,8 @@ def gaussian_beams(s_ray, last, field, theta0, fan_size, grid, omegas, eps, cuto
         d = (X[None, :] - v["x"][:, None]) * v["c"][:, None] + (Y[None, :] - v["y"][:, None]) * v["s"][:, None]
         turn_ok = (v["c"][:-1] * v["c"][1:] + v["s"][:-1] * v["s"][1:]) >= COS_TURN
         own = (d[:-1] >= 0.0) & (d[1:] < 0.0) & turn_ok[:, None]
+        qm_step = np.sqrt(2.0 * cutoff * np.maximum(v["qq"][:-1], v["qq"][1:]) / (omin * eps))
+        cn["capped"] += int((turn_ok & (qm_step > maxw)).sum())
         i, k = np.nonzero(own)                     # row-major: by step, then node -- per node the device's (m, i) order
         if i.size == 0:
             continue
@@ -135,6 +146,11 @@ def gaussian_beams(s_ray, last, field, theta0, fan_size, grid, omegas, eps, cuto
         im = A["im"] + lam * (B["im"] - A["im"])
         g = 0.5 * im * q2
         keep = (q2 <= qm * qm) & ~(omin * g > cutoff)
+        cn["owned"] += int(i.size)
+        cn["inside"] += int(keep.sum())
+        cn["near"] += int(((np.abs(da) <= NEAR * (np.abs(Xk - A["x"]) + np.abs(Yk - A["y"]))) |
+                           (np.abs(db) <= NEAR * (np.abs(Xk - B["x"]) + np.abs(Yk - B["y"]))) |
+                           (np.abs(q2 - qm * qm) <= NEAR * (qm * qm)) | (np.abs(omin * g - cutoff) <= NEAR * cutoff)).sum())
         if not keep.any():
             continue
         sel = lambda a: a[keep]
@@ -152,12 +168,15 @@ def gaussian_beams(s_ray, last, field, theta0, fan_size, grid, omegas, eps, cuto
         for q, wq in enumerate(om):
             wg = wq * g
             ok = wg <= cutoff
+            cn["inside_per_omega"][q] += int(ok.sum())
             amp = am[ok] * np.exp(-wg[ok])
             arg = wq * h[ok] - hp[ok]
             np.add.at(ar[s, q], k[ok], amp * np.cos(arg))
             np.add.at(ai[s, q], k[ok], amp * np.sin(arg))
     c = 0.7071067811865476
     u = c * (ar - ai) + 1j * (c * (ar + ai))
+    if counts is not None:
+        counts.update(cn)
     return u.reshape(S, len(om), int(ny), int(nx))
 
 

@@ -2,7 +2,9 @@
 restatement (tests/beam_ref.py) on the device's own rows; a constant medium against the Hankel function; vert_heterogeneous
 against the library's ray-theory Green's function; the fisheye focus, where ray theory is infinite, and the caustic phase past
 it; the same bits in every schedule, under ray sorting, twice in a row and in every source grouping; fp32 against fp64.  Bounds
-are measurements on MI355X, recorded in DESIGN.md section 13."""
+are measurements on MI355X, recorded in DESIGN.md section 13.  Every restatement case here has a footprint wider than its grid
+and the default cutoff, max_width and edge_taper; tests/test_gpu_beam_edges.py holds the device to the restatement where the
+tiles, the caps, the cutoff, the frequency groups and the record's length decide something."""
 import numpy as np
 import pytest
 from scipy.special import hankel1
