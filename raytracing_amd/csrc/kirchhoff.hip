@@ -1,7 +1,7 @@
-// kirchhoff.hip -- Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_create / _migrate / _model /
-// _destroy): the diffraction-stack operator pair L^T (traces -> image, optionally split into opening-angle bins) and L
-// (reflectivity model -> traces), exact transposes of each other up to rounding.  include/rtmi.h states the operator; DESIGN.md
-// section 14 the kernels and the fixed-point derivation.
+// kirchhoff.hip -- Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_create / _create_multi, _migrate /
+// _model / _migrate2 / _model2 and their _dev forms, _destroy): the diffraction-stack operator pair L^T (traces -> image, optionally
+// split into opening-angle bins) and L (reflectivity model -> traces), exact transposes of each other up to rounding.
+// include/rtmi.h states the operator; DESIGN.md section 14 the kernels and the fixed-point derivation.
 //   L^T  one lane per image node, x fastest (table reads are coalesced).  The lane walks the traces in the caller's order and
 //        adds into an fp64 register (no bins) or into its own column of an LDS array [bin][lane]: no atomics, one fixed order.
 //        T, amp and theta of the source are kept while the source index does not change (a wave-uniform test).
@@ -9,24 +9,62 @@
 //        nodes, round each contribution once to an integer number of quanta 2^scale_exp and add it with a returning 64-bit LDS
 //        atomic (the carry into the high word is read off the returned old value: rt_fix128.h).  Integer sums
 //        commute, so the result has the same bits in every schedule and trace order.  The block converts and stores its trace.
-// Several arrivals per node (rtmi_kirchhoff_create_multi / _migrate2 / _model2): tables [P][K][nn], a trace
-// meets a node in K^2 pairs of a source and a receiver arrival, each rotated by the phase of its caustic count -- a choice of
-// one of two trace channels and a sign.  k_migrate_multi and k_model_multi are the two kernels above with the pair loops
-// unrolled over the template parameter K: the 2 K table values of a (trace, node) are loaded once and serve its K^2 pairs.
-// The tables and the geometry live on the device in the handle.  Every kernel has one launch path, on device pointers
+// One kernel text each, k_migrate and k_model <K, AMP, BINS, PHASE, AA>, serves every kind of handle:
+//   K      arrivals per node: tables [P][K][nn], a trace meets a node in K^2 pairs of a source and a receiver
+//          arrival; the pair loops are unrolled over K, the 2 K table values of a (trace, node) are loaded once and serve its K^2
+//          pairs.  A handle of rtmi_kirchhoff_create runs K = 1: its tables [P][nn] are that layout.
+//   PHASE  with kmah, each pair is rotated by the phase of its caustic count: a choice of one of two trace channels and a sign.
+//   AA     anti-aliased by operator slope (rtmi_kirchhoff_create_aa): one more table value per slot, pt, and
+//          per pair the choice of one level of a bank of filtered traces (L^T), or of per-level accumulators (L).  The bank's
+//          filter and the sum over the levels are kirchhoff_aa.hip's.
+// The tables and the geometry live on the device in the handle.  The kernels have one launch path, on device pointers
 // (rtmi_kirchhoff_migrate_dev / _model_dev); the host-pointer entries upload into the handle's staging buffers,
 // run that path on them and download.  The model's quantum comes from k_absmax_finite, a reduction over the model on the device.
-// What the pair's arithmetic, the handle and its creation share with the anti-aliased pair (kirchhoff_aa.hip): rt_kirchhoff.h.
+#include <type_traits>
+
 #include "rt_kirchhoff.h"
 
 namespace {
 
+// What the kernels of a handle that is not anti-aliased take in AAArgs' place: nothing.
+struct NoAA {
+    NoAA() = default;
+    __host__ __device__ NoAA(const AAArgs&) {}
+};
+template <bool AA> using AAOf = std::conditional_t<AA, AAArgs, NoAA>;
+
+// The level of a pair (rtmi.h): wave-uniform thresholds, 7 compares, no branch.  A NaN slope selects level 0; such a pair does not
+// contribute.
+__device__ __forceinline__ unsigned level_of(const AAArgs& Q, double inv_dt, double ps, double pr) {
+    const double q1 = fabs(ps) * Q.asrc;
+    const double q2 = fabs(pr) * Q.arec;
+    const double q3 = fabs(ps + pr) * Q.amid;
+    const double sl = fmax(fmax(q1, q2), q3) * inv_dt;
+    unsigned l = 0;
+#pragma unroll
+    for (int i = 0; i < kMaxLev - 1; i++) l += sl > Q.thr[i] ? 1u : 0u;
+    return l;
+}
+
+// pt of the K arrivals of one table at one node; without anti-aliasing there is none
+template <int K> __device__ __forceinline__ void load_pt(const AAArgs& Q, long nn, size_t at, double (&o)[K]) {
+#pragma unroll
+    for (int i = 0; i < K; i++) o[i] = Q.pt[at + (size_t)i * nn];
+}
+template <int K> __device__ __forceinline__ void load_pt(const NoAA&, long, size_t, double (&)[K]) {}
+
 // ------------------------------------------------------------------------------------------------------------ L^T
-// image [nb][nn]; counts [gridDim.x]: the block's contributing pairs (plain stores, summed by the host).
-template <bool AMP, bool BINS>
-__global__ void k_migrate(KArgs A, const double* __restrict__ data, double* __restrict__ image, unsigned long long* __restrict__ counts) {
+// data0, data1 [N][nt] (data1 is read only with PHASE); AA: data0 is the bank [nlev][channels][N][nt]; image [nb][nn]; counts
+// [gridDim.x]: the block's contributing pairs (plain stores, summed by the host).  The sum runs over k, then ks, then kr, as rtmi.h
+// defines it.  All K^2 gathers of a trace are issued before the first add, outside the `contributes` test; the level and, AA, the
+// channel move the gather's base address by selects and a multiply, never by a branch.
+template <int K, bool AMP, bool BINS, bool PHASE, bool AA>
+__global__ void __launch_bounds__(256) k_migrate(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ data0,
+                                                 const double* __restrict__ data1, double* __restrict__ image,
+                                                 unsigned long long* __restrict__ counts, AAOf<AA> Q) {
     extern __shared__ double acc[];                           // BINS: [nb][blockDim.x]
-    __shared__ unsigned long long wcnt[4];
+    constexpr int KK = K * K;
+    constexpr int kUnroll = K == 1 ? 4 : K == 2 ? 2 : 1;      // pairs in flight: 4, 8, 9, 16
     const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
     const long x0 = (long)blockIdx.x * BS + tid;
     const bool in = x0 < A.nn;
@@ -36,131 +74,23 @@ __global__ void k_migrate(KArgs A, const double* __restrict__ data, double* __re
         for (int b = 0; b < A.nb; b++) acc[b * BS + tid] = 0.0;
     unsigned long long cnt = 0;
     int sprev = -1;
-    double Ts = 0.0, As = 0.0, Hs = 0.0;
-#pragma unroll 4
-    for (long k = 0; k < A.N; k++) {
-        const int s = A.isrc[k], r = A.irec[k];
-        const double wk = A.w[k];
-        if (s != sprev) {                                     // wave-uniform: a shot-ordered list re-reads the source rarely
-            Ts = A.T[(size_t)s * A.nn + x];
-            if (AMP) As = A.amp[(size_t)s * A.nn + x];
-            if (BINS) Hs = A.theta[(size_t)s * A.nn + x];
-            sprev = s;
-        }
-        const double Tr = A.T[(size_t)r * A.nn + x];
-        const double Ar = AMP ? A.amp[(size_t)r * A.nn + x] : 0.0;
-        const double Hr = BINS ? A.theta[(size_t)r * A.nn + x] : 0.0;
-        const Pair p = pair_of<AMP, BINS>(A, Ts, Tr, As, Ar, Hs, Hr, wk);
-        const double* d = data + (size_t)k * A.nt + p.j;      // j = 0 when the pair does not contribute: always in bounds
-        const double d0 = d[0], d1 = d[1];
-        const double v = p.c * (d0 + p.a * (d1 - d0));
-        if (BINS) {
-            if (p.ok) acc[p.b * BS + tid] += v;
-        } else {
-            sum += p.ok ? v : 0.0;                            // sum is never -0: adding +0 changes no bit
-        }
-        cnt += (p.ok && in) ? 1ull : 0ull;
-    }
-    if (in) {
-        if (BINS)
-            for (int b = 0; b < A.nb; b++) image[(size_t)b * A.nn + x] = acc[b * BS + tid];
-        else
-            image[x] = sum;
-    }
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
-        counts[blockIdx.x] = t;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ L
-// Sample i's accumulator is (lo[i], hi[i]) of rt_fix128.h.
-// One block per trace; data [N][nt]; counts [N].  The trace is processed in windows of at most kWindow samples.
-template <bool AMP, bool BINS>
-__global__ void k_model(KArgs A, const double* __restrict__ m, int e, int W, double* __restrict__ data,
-                        unsigned long long* __restrict__ counts) {
-    extern __shared__ unsigned long long fix[];               // lo [W], hi [W]
-    __shared__ unsigned long long wcnt[4];
-    unsigned long long* lo = fix;
-    unsigned long long* hi = fix + W;
-    const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
-    const long k = blockIdx.x;
-    const int s = A.isrc[k], r = A.irec[k];
-    const double wk = A.w[k];
-    const double* Tsp = A.T + (size_t)s * A.nn;
-    const double* Trp = A.T + (size_t)r * A.nn;
-    const double* Asp = AMP ? A.amp + (size_t)s * A.nn : nullptr;
-    const double* Arp = AMP ? A.amp + (size_t)r * A.nn : nullptr;
-    const double* Hsp = BINS ? A.theta + (size_t)s * A.nn : nullptr;
-    const double* Hrp = BINS ? A.theta + (size_t)r * A.nn : nullptr;
-    unsigned long long cnt = 0;
-    for (long j0 = 0; j0 < A.nt; j0 += W) {
-        const long j1 = (j0 + W < A.nt) ? j0 + W : A.nt;      // the window [j0, j1)
-        for (int i = tid; i < W; i += BS) { lo[i] = rt::kFixBias; hi[i] = 0ull; }
-        __syncthreads();
-#pragma unroll 2
-        for (long x = tid; x < A.nn; x += BS) {
-            const Pair p = pair_of<AMP, BINS>(A, Tsp[x], Trp[x], AMP ? Asp[x] : 0.0, AMP ? Arp[x] : 0.0, BINS ? Hsp[x] : 0.0,
-                                              BINS ? Hrp[x] : 0.0, wk);
-            if (!p.ok) continue;
-            if (j0 == 0) cnt++;
-            if (p.j + 1 < j0 || p.j >= j1) continue;
-            const double cm = p.c * m[(size_t)p.b * A.nn + x];
-            if (!(fabs(cm) < INFINITY)) continue;             // a non-finite model value contributes nothing
-            const double v0 = cm * (1.0 - p.a), v1 = cm * p.a;
-            if (p.j >= j0) (void)rt::add128(lo, hi, (int)(p.j - j0), (long long)rint(ldexp(v0, -e)));
-            if (p.j + 1 < j1) (void)rt::add128(lo, hi, (int)(p.j + 1 - j0), (long long)rint(ldexp(v1, -e)));
-        }
-        __syncthreads();
-        for (long i = tid; i < j1 - j0; i += BS) data[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(lo[i], hi[i]), e);
-        __syncthreads();
-    }
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
-        counts[k] = t;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ several arrivals
-// L^T.  data0, data1 [N][nt] (data1 is read only with PHASE); image [nb][nn]; counts [gridDim.x].  The sum runs over k, then ks,
-// then kr, as rtmi.h defines it.  All K^2 gathers of a trace are issued before the first add, outside the `contributes` test.
-template <int K, bool AMP, bool BINS, bool PHASE>
-__global__ void __launch_bounds__(256) k_migrate_multi(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ data0,
-                                const double* __restrict__ data1, double* __restrict__ image, unsigned long long* __restrict__ counts) {
-    extern __shared__ double acc[];                           // BINS: [nb][blockDim.x]
-    __shared__ unsigned long long wcnt[4];
-    constexpr int KK = K * K;
-    constexpr int kUnroll = K == 1 ? 4 : K == 2 ? 2 : 1;      // pairs in flight: 4, 8, 9, 16
-    const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
-    const long x0 = (long)blockIdx.x * BS + tid;
-    const bool in = x0 < A.nn;
-    const long x = in ? x0 : A.nn - 1;
-    double sum = 0.0;
-    if (BINS)
-        for (int b = 0; b < A.nb; b++) acc[b * BS + tid] = 0.0;
-    unsigned long long cnt = 0;
-    int sprev = -1;
     Arr<K> S;
+    double Sp[K];
 #pragma unroll
-    for (int i = 0; i < K; i++) { S.T[i] = 0.0; S.A[i] = 0.0; S.H[i] = 0.0; S.m[i] = 0; }
+    for (int i = 0; i < K; i++) { S.T[i] = 0.0; S.A[i] = 0.0; S.H[i] = 0.0; S.m[i] = 0; Sp[i] = 0.0; }
 #pragma unroll kUnroll
     for (long k = 0; k < A.N; k++) {
         const int s = A.isrc[k], r = A.irec[k];
         const double wk = A.w[k];
-        if (s != sprev) {                                     // wave-uniform, as in k_migrate
+        if (s != sprev) {                                     // wave-uniform: a shot-ordered list re-reads the source rarely
             load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)s * K * A.nn + x, S);
+            load_pt<K>(Q, A.nn, (size_t)s * K * A.nn + x, Sp);
             sprev = s;
         }
         Arr<K> R;
+        double Rp[K];
         load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)r * K * A.nn + x, R);
+        load_pt<K>(Q, A.nn, (size_t)r * K * A.nn + x, Rp);
         Pair p[KK];
         bool neg[KK];
         double d0[KK], d1[KK];
@@ -169,14 +99,20 @@ __global__ void __launch_bounds__(256) k_migrate_multi(KArgs A, const int8_t* __
             const int ks = i / K, kr = i % K;
             p[i] = pair_of<AMP, BINS>(A, S.T[ks], R.T[kr], S.A[ks], R.A[kr], S.H[ks], R.H[kr], wk);
             const double* ch = data0;
+            size_t at = 0;
+            if constexpr (AA) {
+                p[i].ok = p[i].ok && fabs(Sp[ks]) < INFINITY && fabs(Rp[kr]) < INFINITY;
+                at = (size_t)level_of(Q, A.inv_dt, Sp[ks], Rp[kr]) * (size_t)Q.lstride;
+            }
             neg[i] = false;
             if (PHASE) {
                 const Phase ph = phase_of(S.m[ks], R.m[kr]);
                 p[i].ok = p[i].ok && ph.valid;
                 neg[i] = ph.neg;
-                ch = ph.odd ? data1 : data0;
+                if constexpr (AA) at += ph.odd ? (size_t)Q.cstride : 0;     // an offset here, a pointer there: DESIGN.md section 20
+                else ch = ph.odd ? data1 : data0;
             }
-            const double* d = ch + (size_t)k * A.nt + p[i].j; // j = 0 when the range test failed: always in bounds
+            const double* d = ch + at + (size_t)k * A.nt + p[i].j;          // j = 0 when the range test failed: always in bounds
             d0[i] = d[0];
             d1[i] = d[1];
         }
@@ -198,45 +134,45 @@ __global__ void __launch_bounds__(256) k_migrate_multi(KArgs A, const int8_t* __
         else
             image[x] = sum;
     }
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
-        counts[blockIdx.x] = t;
-    }
+    block_count_to(counts, blockIdx.x, cnt);
 }
 
-// L.  One block per trace; data0, data1 [N][nt] (data1 is written only with PHASE); counts [N].  Channel c's accumulators are
-// lo = fix + 2 c W, hi = lo + W; windows of W samples as in k_model.  Two channels double a block's LDS, which halves the blocks
-// a CU holds: the host launches 512 lanes with PHASE, so that the waves per CU stay what they were (any block size gives the
-// same bits).
-template <int K, bool AMP, bool BINS, bool PHASE>
-__global__ void __launch_bounds__(512) k_model_multi(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ m, int e, int W,
-                              double* __restrict__ data0, double* __restrict__ data1, unsigned long long* __restrict__ counts) {
-    extern __shared__ unsigned long long fix[];               // lo0 [W], hi0 [W] and, PHASE, lo1 [W], hi1 [W]
-    __shared__ unsigned long long wcnt[8];
+// ------------------------------------------------------------------------------------------------------------ L
+// One block per trace; data0, data1 [N][nt] (data1 is written only with PHASE); AA: data0 is the spreads [nlev][channels][N][nt];
+// counts [N].  Sample i's accumulator is (lo[i], hi[i]) of rt_fix128.h; accumulator q = level * channels + channel has
+// lo = fix + 2 q W, hi = lo + W.  The trace is processed in windows of W samples, at most kWindow over the accumulators: more
+// accumulators shrink the window, and two channels double a block's LDS, which halves the blocks a CU holds: the host launches 512
+// lanes with PHASE, so that the waves per CU stay what they were (any block size gives the same bits).
+template <int K, bool AMP, bool BINS, bool PHASE, bool AA>
+__global__ void __launch_bounds__(512) k_model(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ m, int e, int W,
+                                               double* __restrict__ data0, double* __restrict__ data1,
+                                               unsigned long long* __restrict__ counts, AAOf<AA> Q) {
+    extern __shared__ unsigned long long fix[];               // [nlev (AA)][channels][lo | hi][W]
     constexpr int KK = K * K;
     constexpr int kChannels = PHASE ? 2 : 1;
     const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
+    const int nacc = [&] { if constexpr (AA) return Q.nlev * kChannels; else return kChannels; }();
     const long k = blockIdx.x;
     const int s = A.isrc[k], r = A.irec[k];
     const double wk = A.w[k];
     unsigned long long cnt = 0;
     for (long j0 = 0; j0 < A.nt; j0 += W) {
         const long j1 = (j0 + W < A.nt) ? j0 + W : A.nt;      // the window [j0, j1)
-        for (int i = tid; i < 2 * kChannels * W; i += BS) fix[i] = ((i / W) & 1) ? 0ull : rt::kFixBias;
+        for (int i = tid; i < 2 * nacc * W; i += BS) fix[i] = ((i / W) & 1) ? 0ull : rt::kFixBias;
         __syncthreads();
         for (long x = tid; x < A.nn; x += BS) {
             Arr<K> S, R;
+            double Sp[K], Rp[K];
             load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)s * K * A.nn + x, S);
             load_arr<K, AMP, BINS, PHASE>(A, kmah, (size_t)r * K * A.nn + x, R);
+            load_pt<K>(Q, A.nn, (size_t)s * K * A.nn + x, Sp);
+            load_pt<K>(Q, A.nn, (size_t)r * K * A.nn + x, Rp);
             const double mx = BINS ? 0.0 : m[x];
 #pragma unroll
             for (int i = 0; i < KK; i++) {
                 const int ks = i / K, kr = i % K;
                 Pair p = pair_of<AMP, BINS>(A, S.T[ks], R.T[kr], S.A[ks], R.A[kr], S.H[ks], R.H[kr], wk);
+                if constexpr (AA) p.ok = p.ok && fabs(Sp[ks]) < INFINITY && fabs(Rp[kr]) < INFINITY;
                 Phase ph{true, false, false};
                 if (PHASE) ph = phase_of(S.m[ks], R.m[kr]);
                 if (!(p.ok && ph.valid)) continue;
@@ -246,27 +182,34 @@ __global__ void __launch_bounds__(512) k_model_multi(KArgs A, const int8_t* __re
                 if (!(fabs(cm) < INFINITY)) continue;         // a non-finite model value contributes nothing
                 const double u0 = cm * (1.0 - p.a), u1 = cm * p.a;
                 const double v0 = ph.neg ? -u0 : u0, v1 = ph.neg ? -u1 : u1;
-                unsigned long long* lo = fix + (ph.odd ? 2 * W : 0);
+                unsigned long long* lo;
+                if constexpr (AA) {
+                    const int q = (int)level_of(Q, A.inv_dt, Sp[ks], Rp[kr]) * kChannels + (ph.odd ? 1 : 0);
+                    lo = fix + (size_t)2 * q * W;
+                } else {
+                    lo = fix + (ph.odd ? 2 * W : 0);
+                }
                 unsigned long long* hi = lo + W;
                 if (p.j >= j0) (void)rt::add128(lo, hi, (int)(p.j - j0), (long long)rint(ldexp(v0, -e)));
                 if (p.j + 1 < j1) (void)rt::add128(lo, hi, (int)(p.j + 1 - j0), (long long)rint(ldexp(v1, -e)));
             }
         }
         __syncthreads();
-        for (long i = tid; i < j1 - j0; i += BS) {
-            data0[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(fix[i], fix[W + i]), e);
-            if (PHASE) data1[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(fix[2 * W + i], fix[3 * W + i]), e);
+        if constexpr (AA) {                                   // each window's spreads, one rounding each
+            for (int q = 0; q < nacc; q++) {
+                const unsigned long long* lo = fix + (size_t)2 * q * W;
+                double* out = data0 + (size_t)q * Q.cstride + (size_t)k * A.nt + j0;
+                for (long i = tid; i < j1 - j0; i += BS) out[i] = ldexp(rt::fix_to_double(lo[i], lo[W + i]), e);
+            }
+        } else {
+            for (long i = tid; i < j1 - j0; i += BS) {
+                data0[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(fix[i], fix[W + i]), e);
+                if (PHASE) data1[(size_t)k * A.nt + j0 + i] = ldexp(rt::fix_to_double(fix[2 * W + i], fix[3 * W + i]), e);
+            }
         }
         __syncthreads();
     }
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
-        counts[k] = t;
-    }
+    block_count_to(counts, k, cnt);
 }
 
 // ------------------------------------------------------------------------------------------------------------ max |x|
@@ -294,39 +237,83 @@ __global__ void __launch_bounds__(256) k_absmax_finite(const double* __restrict_
     block_max_to(out, m);
 }
 
-// The kernel of (karr, amp, bins, phase): the flags become template arguments one at a time.
-struct MultiLaunch {
+// One launch of either kernel.  migrate: in0, in1 the channels (AA: in0 the bank), out0 the image; model: in0 the model, out0, out1
+// the channels (AA: out0 the spreads).
+struct PairLaunch {
     dim3 grid, blk;
     size_t lds;
     KArgs A;
+    AAArgs Q;
     const int8_t* kmah;
-    const double* in0;      // migrate: data0; model: the model
-    const double* in1;      // migrate: data1
-    double *out0, *out1;    // migrate: image, -; model: data0, data1
+    const double *in0, *in1;
+    double *out0, *out1;
     int e, W;
     unsigned long long* counts;
 };
-template <bool MODEL, int K, bool... F>
-void launch_multi(const bool* f, const MultiLaunch& L) {
-    if constexpr (sizeof...(F) == 3) {
-        if constexpr (MODEL)
-            hipLaunchKernelGGL((k_model_multi<K, F...>), L.grid, L.blk, L.lds, nullptr, L.A, L.kmah, L.in0, L.e, L.W, L.out0, L.out1, L.counts);
+// The kernel of (model, aa, amp, bins, phase) and K: the flags become template arguments one at a time.
+template <int K, bool... F>
+void launch_pair(const bool* f, const PairLaunch& L) {
+    if constexpr (sizeof...(F) == 5) {
+        constexpr bool v[5] = {F...};
+        if constexpr (v[0])
+            hipLaunchKernelGGL((k_model<K, v[2], v[3], v[4], v[1]>), L.grid, L.blk, L.lds, nullptr, L.A, L.kmah, L.in0, L.e, L.W, L.out0, L.out1,
+                               L.counts, AAOf<v[1]>(L.Q));
         else
-            hipLaunchKernelGGL((k_migrate_multi<K, F...>), L.grid, L.blk, L.lds, nullptr, L.A, L.kmah, L.in0, L.in1, L.out0, L.counts);
+            hipLaunchKernelGGL((k_migrate<K, v[2], v[3], v[4], v[1]>), L.grid, L.blk, L.lds, nullptr, L.A, L.kmah, L.in0, L.in1, L.out0, L.counts,
+                               AAOf<v[1]>(L.Q));
     } else {
-        if (*f) launch_multi<MODEL, K, F..., true>(f + 1, L);
-        else launch_multi<MODEL, K, F..., false>(f + 1, L);
+        if (*f) launch_pair<K, F..., true>(f + 1, L);
+        else launch_pair<K, F..., false>(f + 1, L);
     }
 }
-template <bool MODEL>
-void launch_multi(int karr, bool amp, bool bins, bool phase, const MultiLaunch& L) {
-    const bool f[3] = {amp, bins, phase};
+// karr = 0, a handle of rtmi_kirchhoff_create: its tables [P][nn] are [P][1][nn]
+void launch_pair(int karr, bool model, bool aa, bool amp, bool bins, bool phase, const PairLaunch& L) {
+    const bool f[5] = {model, aa, amp, bins, phase};
     switch (karr) {
-        case 1: launch_multi<MODEL, 1>(f, L); break;
-        case 2: launch_multi<MODEL, 2>(f, L); break;
-        case 3: launch_multi<MODEL, 3>(f, L); break;
-        default: launch_multi<MODEL, 4>(f, L); break;
+        case 0:
+        case 1: launch_pair<1>(f, L); break;
+        case 2: launch_pair<2>(f, L); break;
+        case 3: launch_pair<3>(f, L); break;
+        default: launch_pair<4>(f, L); break;
     }
+}
+
+int64_t to_ns(double ms) { return (int64_t)std::llround(ms * 1e6); }
+
+// The one bracket of a launch, for both kernels and every kind of handle: the caller has set L's grid, block, LDS and pointers.
+// On an anti-aliased handle of more than one level the bank's filter runs before migrate's kernel and the sum over the levels after
+// model's; kernel_ms covers both and reserved[0] is that part of it in nanoseconds.
+int run_pair(rtmi_kirchhoff* k, const char* who, bool model, PairLaunch& L, rtmi_kirchhoff_stats* st, bool counts) {
+    const bool aa = k->nlev > 0, sweep = k->nlev > 1;
+    L.A = k->args();
+    if (aa) L.Q = k->aa_args();
+    L.kmah = k->kmah;
+    L.counts = k->counts;
+    EventMarks<4> ev;
+    RTMI_HIP(ev.create());
+    RTMI_HIP(ev.mark(0));
+    if (sweep && !model) RTMI_RC(rtmi_internal_kirchhoff_aa_sweep(k, who, false));
+    RTMI_HIP(ev.mark(1));
+    launch_pair(k->karr, model, aa, k->amp != nullptr, k->kp.nbin > 0, k->kmah != nullptr, L);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(2));
+    if (sweep && model) RTMI_RC(rtmi_internal_kirchhoff_aa_sweep(k, who, true));
+    RTMI_HIP(ev.mark(3));
+    RTMI_HIP(ev.wait(3));
+    if (st) {
+        const int kk = k->karr ? k->karr * k->karr : 1;
+        *st = rtmi_kirchhoff_stats{};
+        RTMI_HIP(ev.ms(aa && !model ? 0 : 1, aa && model ? 3 : 2, &st->kernel_ms));
+        if (aa) {
+            double aux_ms = 0.0;
+            RTMI_HIP(model ? ev.ms(2, 3, &aux_ms) : ev.ms(0, 1, &aux_ms));
+            st->reserved[0] = to_ns(aux_ms);
+        }
+        st->pairs = (int64_t)((size_t)k->kp.N * k->nn) * kk;
+        st->scale_exp = L.e;
+        if (counts) RTMI_RC(read_counts(k, L.grid.x, &st->contributing, who));
+    }
+    return RTMI_OK;
 }
 
 }  // namespace
@@ -362,93 +349,46 @@ int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cu
     return RTMI_OK;
 }
 
+// On an anti-aliased handle, level 0 of `data` is where the bank's filter reads the caller's channels and the sum over the levels
+// leaves the traces: device pointers other than the handle's own staging are copied to and from it on the device.
 int rtmi_internal_kirchhoff_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
                                         rtmi_kirchhoff_stats* st, bool counts) {
-    if (k->nlev) return rtmi_internal_kirchhoff_aa_migrate_dev(k, who, d0, d1, d_image, st, counts);
-    const size_t N = (size_t)k->kp.N, nn = k->nn;
-    const bool phase = k->kmah != nullptr;
-    EventMarks<2> ev;
-    RTMI_HIP(ev.create());
+    const size_t per = (size_t)k->kp.N * (size_t)k->kp.nt;
+    const bool phase = k->kmah != nullptr, aa = k->nlev > 0;
+    if (aa && d0 != k->data) RTMI_HIP(hipMemcpyAsync(k->data, d0, per * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+    if (aa && phase && d1 != k->data + per) RTMI_HIP(hipMemcpyAsync(k->data + per, d1, per * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
     const int BS = migrate_block(k->nb);
-    const dim3 grid((unsigned)((nn + BS - 1) / BS)), blk(BS);
-    const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
-    const size_t lds = bins ? (size_t)k->nb * BS * sizeof(double) : 0;
-    const KArgs A = k->args();
-    MultiLaunch L{};
-    L.grid = grid;
-    L.blk = blk;
-    L.lds = lds;
-    L.A = A;
-    L.kmah = k->kmah;
-    L.in0 = d0;
-    L.in1 = phase ? d1 : nullptr;
+    PairLaunch L{};
+    L.grid = dim3((unsigned)((k->nn + BS - 1) / BS));
+    L.blk = dim3(BS);
+    L.lds = k->kp.nbin > 0 ? (size_t)k->nb * BS * sizeof(double) : 0;
+    L.in0 = aa ? k->data : d0;
+    L.in1 = phase && !aa ? d1 : nullptr;
     L.out0 = d_image;
-    L.counts = k->counts;
-    RTMI_HIP(ev.mark(0));
-    if (k->karr) launch_multi<false>(k->karr, has_amp, bins, phase, L);
-    else if (has_amp && bins) hipLaunchKernelGGL((k_migrate<true, true>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
-    else if (has_amp) hipLaunchKernelGGL((k_migrate<true, false>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
-    else if (bins) hipLaunchKernelGGL((k_migrate<false, true>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
-    else hipLaunchKernelGGL((k_migrate<false, false>), grid, blk, lds, nullptr, A, d0, d_image, k->counts);
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(ev.mark(1));
-    RTMI_HIP(ev.wait(1));
-    if (st) {
-        const int kk = k->karr ? k->karr * k->karr : 1;
-        *st = rtmi_kirchhoff_stats{};
-        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
-        st->pairs = (int64_t)(N * nn) * kk;
-        if (counts) RTMI_RC(read_counts(k, grid.x, &st->contributing, who));
-    }
-    return RTMI_OK;
+    return run_pair(k, who, false, L, st, counts);
 }
 
 int rtmi_internal_kirchhoff_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, double* d0, double* d1,
                                       rtmi_kirchhoff_stats* st, bool counts) {
-    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nn = k->nn, nm = (size_t)k->nb * nn;
+    const size_t N = (size_t)k->kp.N, nt = (size_t)k->kp.nt, nm = (size_t)k->nb * k->nn;
+    const bool phase = k->kmah != nullptr, aa = k->nlev > 0;
     // the quantum: one bound on one contribution for every kind of handle (DESIGN.md 19 on the number of contributions)
     double max_m = 0.0;
     RTMI_RC(rtmi_internal_absmax_finite(who, k->red, k->cus, d_model, nm, &max_m));
-    const int e = model_exponent(k, max_m);
-    if (k->nlev) return rtmi_internal_kirchhoff_aa_model_dev(k, who, d_model, e, d0, d1, st, counts);
-    const bool phase = k->kmah != nullptr;
-    EventMarks<2> ev;
-    RTMI_HIP(ev.create());
-    const size_t window = phase ? kWindow / 2 : kWindow;      // two channels share the 64 KiB
-    const int W = (int)(nt < window ? nt : window);
-    const dim3 grid((unsigned)N), blk(phase ? 512 : 256);
-    const size_t lds = (size_t)W * (phase ? 4 : 2) * sizeof(unsigned long long);
-    const bool bins = k->kp.nbin > 0, has_amp = k->amp != nullptr;
-    const KArgs A = k->args();
-    MultiLaunch L{};
-    L.W = W;
-    L.e = e;
-    L.grid = grid;
-    L.blk = blk;
-    L.lds = lds;
-    L.A = A;
-    L.kmah = k->kmah;
+    const size_t nacc = (size_t)(aa ? k->nlev : 1) * (phase ? 2 : 1);     // every level and channel shares the 64 KiB
+    const size_t window = (size_t)kWindow / nacc;
+    PairLaunch L{};
+    L.W = (int)(nt < window ? nt : window);
+    L.e = model_exponent(k, max_m);
+    L.grid = dim3((unsigned)N);
+    L.blk = dim3(phase ? 512 : 256);
+    L.lds = (size_t)L.W * 2 * nacc * sizeof(unsigned long long);
     L.in0 = d_model;
-    L.out0 = d0;
-    L.out1 = phase ? d1 : nullptr;
-    L.counts = k->counts;
-    RTMI_HIP(ev.mark(0));
-    if (k->karr) launch_multi<true>(k->karr, has_amp, bins, phase, L);
-    else if (has_amp && bins) hipLaunchKernelGGL((k_model<true, true>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
-    else if (has_amp) hipLaunchKernelGGL((k_model<true, false>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
-    else if (bins) hipLaunchKernelGGL((k_model<false, true>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
-    else hipLaunchKernelGGL((k_model<false, false>), grid, blk, lds, nullptr, A, d_model, e, W, d0, k->counts);
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(ev.mark(1));
-    RTMI_HIP(ev.wait(1));
-    if (st) {
-        const int kk = k->karr ? k->karr * k->karr : 1;
-        *st = rtmi_kirchhoff_stats{};
-        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
-        st->pairs = (int64_t)(N * nn) * kk;
-        st->scale_exp = e;
-        if (counts) RTMI_RC(read_counts(k, N, &st->contributing, who));
-    }
+    L.out0 = aa ? k->data : d0;
+    L.out1 = phase && !aa ? d1 : nullptr;
+    RTMI_RC(run_pair(k, who, true, L, st, counts));
+    if (aa && d0 != k->data) RTMI_HIP(hipMemcpy(d0, k->data, N * nt * sizeof(double), hipMemcpyDeviceToDevice));
+    if (aa && phase && d1 != k->data + N * nt) RTMI_HIP(hipMemcpy(d1, k->data + N * nt, N * nt * sizeof(double), hipMemcpyDeviceToDevice));
     return RTMI_OK;
 }
 

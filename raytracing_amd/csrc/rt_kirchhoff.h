@@ -1,8 +1,9 @@
-// rt_kirchhoff.h -- what the Kirchhoff units share (kirchhoff.hip: the plain pairs; kirchhoff_aa.hip: the anti-aliased pair;
-// kirchhoff_lsqr.hip: least-squares migration over either): the kernel arguments, one (trace, node) pair's arithmetic, the arrivals
-// of a table at a node and their phase, a block's exact maximum, the handle, its argument checks and uploads.  Everything but the
-// handle and the cross-unit entries is in an anonymous namespace: each unit gets its own copy, as with rtmi_host.h.  DESIGN.md
-// sections 14, 19, 20 and 21.
+// rt_kirchhoff.h -- what the Kirchhoff units share (kirchhoff.hip: the migrate / model kernel pair of every kind of handle and its
+// one launch path; kirchhoff_aa.hip: the anti-aliased handle, its bank filter and level sum; kirchhoff_lsqr.hip: least-squares
+// migration over any handle): the kernel arguments, one (trace, node) pair's arithmetic, the arrivals of a table at a node and
+// their phase, a block's exact maximum and its count, the handle, its argument checks and uploads.  Everything but the handle and
+// the cross-unit entries is in an anonymous namespace: each unit gets its own copy, as with rtmi_host.h.  DESIGN.md sections 14,
+// 19, 20 and 21.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 namespace {
 
 constexpr int kMaxBins = 32;
+constexpr int kMaxLev = RTMI_KIRCHHOFF_MAX_LEVELS;
 constexpr int kWindow = 4096;         // samples of a trace held in LDS at a time: 4096 x 16 B = 64 KiB
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 
@@ -30,6 +32,15 @@ struct KArgs {
     long nn, N, nt;
     double t0, inv_dt, dopen, ntm1;   // ntm1 = nt - 1: floor(f) <= nt - 2 iff f < nt - 1
     int nb;
+};
+
+// What the kernels of an anti-aliased handle take besides (rtmi_kirchhoff_create_aa; the others take an empty struct in its place).
+struct AAArgs {
+    const double* pt;              // [P][K][nn]
+    double asrc, arec, amid;
+    double thr[kMaxLev - 1];       // (double)hw[l] for l < nlev - 1, +inf from there on: the level is the number of thresholds below sl
+    long lstride, cstride;         // doubles from one level to the next (channels N nt) and from channel 0 to channel 1 (N nt)
+    int nlev;
 };
 
 // What one (trace, node) pair reads and derives.  ok: the pair contributes (rtmi.h): every value read is finite, 0 <= j <= nt - 2
@@ -64,6 +75,20 @@ __device__ __forceinline__ Pair pair_of(const KArgs& A, double Ts, double Tr, do
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
     return v;
+}
+
+// The block's sum of cnt into counts[index] (a plain store; the host sums the blocks).  Blocks of at most 512 lanes.
+__device__ __forceinline__ void block_count_to(unsigned long long* counts, long index, unsigned long long cnt) {
+    __shared__ unsigned long long wcnt[8];
+    const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
+    cnt = wave_sum(cnt);
+    if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t = 0;
+        for (int q = 0; q < (BS + 63) / 64; q++) t += wcnt[q];
+        counts[index] = t;
+    }
 }
 
 // The block's largest v (v >= 0, never NaN) into *slot, a double kept as its bits: non-negative doubles order as unsigned integers,
@@ -141,10 +166,20 @@ struct rtmi_kirchhoff {
         return KArgs{T, amp, theta, isrc, irec, w, (long)nn, (long)kp.N, (long)kp.nt, kp.t0, 1.0 / kp.dt, kp.dopen,
                      (double)(kp.nt - 1), nb};
     }
+    AAArgs aa_args() const {
+        AAArgs Q{};
+        Q.pt = pt;
+        Q.asrc = asrc; Q.arec = arec; Q.amid = amid;
+        for (int l = 0; l < kMaxLev - 1; l++) Q.thr[l] = l < nlev - 1 ? (double)hw[l] : INFINITY;
+        Q.cstride = (long)((size_t)kp.N * (size_t)kp.nt);
+        Q.lstride = (kmah ? 2 : 1) * Q.cstride;
+        Q.nlev = nlev;
+        return Q;
+    }
 };
 
-// The pair on device pointers, the one launch path of every kernel (kirchhoff.hip): any kind of handle, the
-// callers have checked the arguments and the device.  d1 is read, or written, only on a handle with kmah.  The handle's own
+// The pair on device pointers, the one launch path of the two kernels (kirchhoff.hip): any kind of handle,
+// the callers have checked the arguments and the device.  d1 is read, or written, only on a handle with kmah.  The handle's own
 // staging buffers may be passed (the host-pointer entries do): nothing is copied then.  st may be NULL; counts: also read back
 // and sum the per-block counts into st->contributing (N words), which a solver's loop leaves out.  upload_ms is 0.
 int rtmi_internal_kirchhoff_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
@@ -154,11 +189,10 @@ int rtmi_internal_kirchhoff_model_dev(rtmi_kirchhoff* k, const char* who, const 
 // max |x_i| over the finite values of n doubles on the device (0 when there is none): k_absmax_finite and an 8-byte read-back.
 // red: a device word for the result (the handle's); cus: the device's compute units
 int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cus, const double* d_x, size_t n, double* out);
-// the same two on a handle of rtmi_kirchhoff_create_aa (kirchhoff_aa.hip); e: the model's quantum, taken by the caller
-int rtmi_internal_kirchhoff_aa_migrate_dev(rtmi_kirchhoff* k, const char* who, const double* d0, const double* d1, double* d_image,
-                                           rtmi_kirchhoff_stats* st, bool counts);
-int rtmi_internal_kirchhoff_aa_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, int e, double* d0, double* d1,
-                                         rtmi_kirchhoff_stats* st, bool counts);
+// What that path launches around the pair kernel on a handle of rtmi_kirchhoff_create_aa with more than one level
+// (kirchhoff_aa.hip), in place over the handle's `data`: before migrate, levels 1 .. nlev - 1 of the bank from level 0
+// (k_aa_filter); gather: after model, the sum of the filtered spreads of every level into level 0 (k_aa_gather).
+int rtmi_internal_kirchhoff_aa_sweep(rtmi_kirchhoff* k, const char* who, bool gather);
 
 namespace {
 

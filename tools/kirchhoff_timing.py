@@ -6,10 +6,10 @@ every table, trace and image access counted once, at 6 TB/s.  Also the numpy res
 for contrast.  Each case runs in a child process of its own under a time limit, and the first failure ends the run.  Prints
 one JSON line per measurement.
 --arrivals K times the pair over several arrivals (rtmi_kirchhoff_migrate2 / _model2) on the same case, in one
-process with the one-arrival kernels it is measured against: the tables replicated into K slots, slot i later by 3 i ms so that
+process with the one-arrival handle it is measured against: the tables replicated into K slots, slot i later by 3 i ms so that
 the K^2 pairs of a (trace, node) are distinct and (nearly) all contribute; kmah = slot index.  It prints, for migrate and
-model: the one-arrival handle, K = 1 without kmah through the new kernels, and K slots without and with kmah, each with its
-time per pair relative to the one-arrival kernel.
+model: the one-arrival handle, a create_multi handle of K = 1 without kmah (the same kernel instantiation), and K slots without
+and with kmah, each with its time per pair relative to the one-arrival handle.
 --antialias NLEV (with --arrivals K, default 1) times the pair anti-aliased by operator slope (rtmi_kirchhoff_create_aa; DESIGN.md
 20) on the same case against rtmi_kirchhoff_migrate2 / _model2 on the same inputs, in one process, the two handles called in
 turn: pt from the closed-form launch angles, arec = the position spacing (the case is shot gathers), the levels the first NLEV
@@ -123,15 +123,15 @@ def run_arrivals(K, reps):
                 nbytes = 2 * N * max(karr, 1) * nn * (8 + kmah) + 8 * (N * nn + N * nt * (1 + kmah))
             k, ks, st = median_ms(call, reps)
             per_pair = k / st["pairs"]
-            base.setdefault(kind, per_pair)                      # the one-arrival kernel is measured first
+            base.setdefault(kind, per_pair)                      # the one-arrival handle is measured first
             print(json.dumps({"what": f"{kind}, {what}", "arrivals": karr, "kmah": bool(kmah), "pairs": st["pairs"],
                               "contributing": st["contributing"], "kernel_ms_median": k, "kernel_ms": ks, "bytes": nbytes,
                               "floor_ms_at_6TBps": nbytes / 6e12 * 1e3, "pairs_per_s": st["pairs"] / (k * 1e-3),
                               "ns_per_pair": per_pair * 1e6, "time_per_pair_vs_one_arrival_kernel": per_pair / base[kind]}), flush=True)
         op.close()
 
-    measure("one-arrival handle (k_migrate / k_model)", rb.Kirchhoff(T, isrc, irec, nt, dt), 0, 0)
-    measure("K = 1 without kmah (k_migrate_multi / k_model_multi)", rb.Kirchhoff(T[:, None], isrc, irec, nt, dt), 1, 0)
+    measure("one-arrival handle (rtmi_kirchhoff_create)", rb.Kirchhoff(T, isrc, irec, nt, dt), 0, 0)
+    measure("K = 1 without kmah (rtmi_kirchhoff_create_multi)", rb.Kirchhoff(T[:, None], isrc, irec, nt, dt), 1, 0)
     TK = np.stack([T + 0.003 * i for i in range(K)], axis=1)
     if K > 1:
         measure(f"K = {K} without kmah", rb.Kirchhoff(TK, isrc, irec, nt, dt), K, 0)
