@@ -675,7 +675,8 @@ void rtmi_kirchhoff_destroy(rtmi_kirchhoff *k);
  * rtmi_kirchhoff_destroy.  rtmi_kirchhoff_migrate / _model on a handle of create_multi, and migrate2 / model2 on a handle of
  * rtmi_kirchhoff_create, return RTMI_ERR_ARG.  Refused before any device work as above, and also: karr outside 1 .. 4; a null
  * data1 on a handle that has kmah.  stats: pairs = N nx ny K^2.
- * Not covered: the 2-D half-derivative / pi/4 filter and H itself (the caller filters), fp32 tables, K > 4. */
+ * H on the device: rtmi_kirchhoff_hilbert below.
+ * Not covered: the 2-D half-derivative / pi/4 filter (the caller filters), fp32 tables, K > 4. */
 #define RTMI_KIRCHHOFF_MAX_ARRIVALS 4
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_multi_params;
 int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params *kp, const double *T, const double *amp, const double *theta,
@@ -722,7 +723,8 @@ int rtmi_kirchhoff_model2(rtmi_kirchhoff *k, const double *model, double *data0,
  * Refused before any device work, with rtmi_last_error naming the argument: everything rtmi_kirchhoff_create_multi refuses; a
  * null pt; nlev outside 1 .. 8; hw[0] != 0, hw not strictly increasing or above 64; a length that is negative or not finite.
  * rtmi_kirchhoff_migrate / _model on such a handle, and rtmi_kirchhoff_aa_filter on any other handle, return RTMI_ERR_ARG.
- * Not covered: the half-derivative / wavelet filter and H (the caller's), a continuous triangle by double integration (it loses
+ * H on the device: rtmi_kirchhoff_hilbert below.
+ * Not covered: the half-derivative / wavelet filter (the caller's), a continuous triangle by double integration (it loses
  * about 2 log2(nt) bits and has no bit-for-bit definition), fp32 tables or traces, K > 4. */
 #define RTMI_KIRCHHOFF_MAX_LEVELS 8
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen;
@@ -767,8 +769,8 @@ int rtmi_kirchhoff_aa_filter(rtmi_kirchhoff *k, const double *data, double *bank
  * Handles: rtmi_kirchhoff_create, and create_multi / create_aa without kmah (channel 0 is the whole trace).
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null handle, params, data or x; iter_lim < 1;
  * damp, atol or btol negative or not finite; a handle with kmah; a data value that is not finite.
- * Not covered: handles with kmah (their trace is ch0 + H ch1 and there is no Hilbert transform on the device), preconditioners,
- * model masks, x0, conlim / acond / xnorm / var (acond and var need a vector norm more per iteration), scipy's stop tests 3 to 6,
+ * Handles with kmah (their trace is ch0 + H ch1): rtmi_kirchhoff_lsqr_full below.
+ * Not covered: preconditioners, model masks, x0, conlim / acond / xnorm / var (acond and var need a vector norm more per iteration), scipy's stop tests 3 to 6,
  * fp32 vectors, several GPUs. */
 #define RTMI_LSQR_RANGE 8
 typedef struct { int32_t iter_lim, reserved0; double damp, atol, btol; int64_t reserved[4]; } rtmi_lsqr_params;
@@ -778,6 +780,39 @@ int rtmi_kirchhoff_migrate_dev(rtmi_kirchhoff *k, const double *d_data0, const d
 int rtmi_kirchhoff_model_dev(rtmi_kirchhoff *k, const double *d_model, double *d_data0, double *d_data1, rtmi_kirchhoff_stats *st);
 int rtmi_kirchhoff_lsqr(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const double *data, double *x, double *history,
                         rtmi_lsqr_stats *st);
+
+/* The Hilbert transform along the traces of a handle, on the device and defined bit for bit, and least-squares migration of the
+ * full trace of a handle with kmah.  DESIGN.md section 23.
+ * H is circular along the last axis of [N][nt] and linear, H[cos] = sin: as a matrix, the FFT form with DC and Nyquist zeroed and
+ * the positive frequencies doubled (scipy.signal.hilbert's imaginary part), evaluated in the time domain.  With n = nt,
+ * K = floor((n - 1) / 2) and a_k = pi k / n:
+ *   n even:  c_k = (2 / n) cot(a_k) for odd k,  c_k = 0 for even k                          k = 1 .. K
+ *   n odd :  c_k = (cot(a_k) - (-1)^k / sin(a_k)) / n                                       k = 1 .. K
+ *   y[i] = sum over k = 1 .. K ascending with c_k != 0 of fl(c_k * fl(x[(i - k) mod n] - x[(i + k) mod n]))
+ * The sum starts from +0.0; every subtract, product and add is a separate fp64 operation; n = 1 and n = 2 have no taps, y = +0.
+ * fl(a - b) = -fl(b - a), and a sum of negated terms is the negated sum: the matrix satisfies H^T = -H in every bit.
+ * rtmi_hilbert_taps writes c_1 .. c_K (host only, no device): evaluated in long double and rounded once to fp64, exact 0.0 at
+ * the even k of an even n (raytracing_amd/csrc/rt_hilbert.h, which also has the definition as a host loop).  y is defined bit for
+ * bit given the taps.  The input is not checked for finiteness: the bits are defined for finite input, and a sample that is not
+ * finite makes NaN wherever the formula does.
+ * rtmi_kirchhoff_hilbert: y = H x, host [N][nt] -> [N][nt], on any kind of handle: the handle supplies the device, N and nt.  The
+ * taps are uploaded at the first use and freed by rtmi_kirchhoff_destroy.
+ * rtmi_kirchhoff_hilbert_dev: d_y = (d_add ? d_add : +0) +- H d_x on memory of the handle's device, minus with negate != 0: with
+ * d_add the last operation is one fl(d_add[i] +- y[i]); without it the result is y or its exact negation.  d_y may be d_add.
+ * RTMI_ERR_ARG: a null handle, d_x or d_y; d_y equal to d_x or overlapping it; d_add overlapping d_y without being it; pointers
+ * as rtmi_kirchhoff_migrate_dev checks its own; nt > 16384 (the kernel holds a trace in LDS in one piece), naming nt.
+ * rtmi_kirchhoff_lsqr_full is rtmi_kirchhoff_lsqr for the full-trace operator of a handle with kmah: A x = ch0 + H ch1 with
+ * (ch0, ch1) = model2(x), one fl(ch0[i] + y[i]) per sample, and A^T u = migrate2(u, -H u), its transpose in every bit.  The same
+ * scalar recurrence, norm and update kernels, stop rules, history and stats, and the same refusals except that of kmah; nt > 16384
+ * on a handle with kmah is refused, naming nt.  The call holds two more N nt vectors (channel 1 of A v, and -H u); bytes_device
+ * counts them and the taps, and operator_ms includes the Hilbert kernels' event time.  On a handle without kmah the call is
+ * rtmi_kirchhoff_lsqr bit for bit and runs no H.
+ * Not covered: nt > 16384, an FFT form, a transform that is not circular (the caller pads), fp32 traces. */
+int rtmi_hilbert_taps(int64_t n, double *taps);   /* host only, no device: floor((n - 1) / 2) values, k = 1 ...; n >= 1 */
+int rtmi_kirchhoff_hilbert(rtmi_kirchhoff *k, const double *x, double *y);                 /* host [N][nt] -> [N][nt] */
+int rtmi_kirchhoff_hilbert_dev(rtmi_kirchhoff *k, const double *d_x, const double *d_add, int32_t negate, double *d_y);
+int rtmi_kirchhoff_lsqr_full(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const double *data, double *x, double *history,
+                             rtmi_lsqr_stats *st);
 
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
@@ -926,6 +961,10 @@ int rtmi_debug_arrival_rows(int32_t rows, int32_t R, int32_t fan_size, const dou
 /* Diagnostic: the norm of rtmi_kirchhoff_lsqr on n host doubles, host in and host out: *norm, and *e the quantum's exponent (0 for
  * the zero vector).  RTMI_ERR_ARG: n < 1, a value that is not finite, max|x|^2 not a normal number. */
 int rtmi_debug_fix_norm(const double *x, int64_t n, double *norm, int32_t *e);
+/* Diagnostic: rtmi_kirchhoff_hilbert_dev's kernel without a handle, host in and host out, on the calling thread's current device:
+ * y = (add ? add : +0) +- H x over [N][nt], minus with negate != 0; add may be NULL.  For the trace lengths no handle can have
+ * (nt = 1).  RTMI_ERR_ARG: a null x or y, N < 1, nt < 1, nt > 16384. */
+int rtmi_debug_hilbert(const double *x, int64_t N, int64_t nt, const double *add, int32_t negate, double *y);
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,7 @@ class LsqrStats(C.Structure):
 
 
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
+HILBERT_MAX_NT = 16384  # the longest trace rtmi_kirchhoff_hilbert takes: one copy of it in LDS
 
 # rtmi_arrival_grid's orders and largest karr
 ARRIVAL_BY_TIME, ARRIVAL_BY_AMPLITUDE, MAX_ARRIVALS = 0, 1, 16
@@ -209,6 +210,10 @@ SYMBOLS = {
     "rtmi_kirchhoff_migrate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KirchhoffStats)]),
     "rtmi_kirchhoff_model_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KirchhoffStats)]),
     "rtmi_kirchhoff_lsqr": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_hilbert_taps": (C.c_int, [C.c_int64, _dp]),
+    "rtmi_kirchhoff_hilbert": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "rtmi_kirchhoff_hilbert_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtmi_kirchhoff_lsqr_full": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, C.POINTER(LsqrStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),
@@ -237,6 +242,7 @@ SYMBOLS = {
     "rtmi_debug_arrival_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [_ip, _dp, _dp, _ip, _dp, C.POINTER(GridParams),
                                           C.POINTER(ArrivalParams), _ip, _dp, C.POINTER(ArrivalStats)]),
     "rtmi_debug_fix_norm": (C.c_int, [_dp, C.c_int64, _dp, _ip]),
+    "rtmi_debug_hilbert": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, C.c_int32, _dp]),
 }
 
 _lib = None

@@ -1,7 +1,9 @@
-// kirchhoff_lsqr.hip -- least-squares Kirchhoff migration that stays on the device (rtmi_kirchhoff_lsqr, rtmi_debug_fix_norm):
+// kirchhoff_lsqr.hip -- least-squares Kirchhoff migration that stays on the device (rtmi_kirchhoff_lsqr, rtmi_kirchhoff_lsqr_full,
+// rtmi_debug_fix_norm):
 // LSQR over the pair of kirchhoff.hip / kirchhoff_aa.hip on device pointers, every vector on the device from the one upload of the
 // data to the one download of the model.  include/rtmi.h states the contract; DESIGN.md section 21 the definitions, the memory and
-// what was measured; rt_lsqr.h the scalar recurrence (host, scipy's operation order).
+// what was measured; rt_lsqr.h the scalar recurrence (host, scipy's operation order).  _lsqr_full on a handle with kmah solves
+// for the full trace ch0 + H ch1 with the Hilbert transform of kirchhoff_hilbert.hip around the pair.
 // The vector passes are memory-bound: 256 lanes per block, grid-stride, at most 4 blocks per CU, 16-byte loads and stores when
 // every pointer of the pass is 16-byte aligned (`wide`; the solver's own allocations always are).
 //   k_axmy_absmax  y_i = t_i - fl(a y_i), and max |y_i| of the new y in the same pass (block_max_to)
@@ -12,6 +14,7 @@
 //                  same bits in every schedule.
 // Every product and every add or subtract is a separate fp64 operation: the kernels spell them __dmul_rn / __dadd_rn, and the
 // unit is built with -ffp-contract=off like the rest of the library.
+#include "rt_hilbert.h"
 #include "rt_kirchhoff.h"
 #include "rt_lsqr.h"
 
@@ -166,11 +169,10 @@ int scale(const char* who, const Vec& V, double* y, double s, size_t n) {
     return RTMI_OK;
 }
 
-}  // namespace
-
-RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
-                                    rtmi_lsqr_stats* st) {
-    const char* who = "rtmi_kirchhoff_lsqr";
+// Both solvers.  full: on a handle with kmah the operator is that of the full trace, A x = ch0 + H ch1 with (ch0, ch1) =
+// model2(x), and A^T u = migrate2(u, -H u), its transpose in every bit; on any other handle `full` changes nothing.
+int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
+             rtmi_lsqr_stats* st) {
     RTMI_ARG(k, "null handle");
     RTMI_ARG(lp, "null params");
     RTMI_ARG(data, "null data");
@@ -179,20 +181,27 @@ RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* l
     RTMI_ARG(std::isfinite(lp->damp) && lp->damp >= 0.0, "damp must be finite and >= 0");
     RTMI_ARG(std::isfinite(lp->atol) && lp->atol >= 0.0, "atol must be finite and >= 0");
     RTMI_ARG(std::isfinite(lp->btol) && lp->btol >= 0.0, "btol must be finite and >= 0");
-    RTMI_ARG(!k->kmah, "the handle has kmah: its trace is ch0 + H ch1, and there is no Hilbert transform on the device");
+    RTMI_ARG(full || !k->kmah, "the handle has kmah: its trace is ch0 + H ch1, which rtmi_kirchhoff_lsqr_full solves for");
+    const bool hil = full && k->kmah;
+    if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_check(k, who));
     const size_t per = (size_t)k->kp.N * (size_t)k->kp.nt, nm = (size_t)k->nb * k->nn;
     for (size_t i = 0; i < per; i++) RTMI_ARG(std::isfinite(data[i]), "data has a value that is not finite");
     RTMI_RC(check_device(k, who));
     const double t_begin = now_ms();
     DevMem mem;
     double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr;
-    for (double** p : {&u, &Av})
-        if (mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_kirchhoff_lsqr: hipMalloc failed");
+    double *Av1 = nullptr, *Hu = nullptr;                                             // channel 1 of A v, and -H u: with hil only
+    const char* no_mem = full ? "rtmi_kirchhoff_lsqr_full: hipMalloc failed" : "rtmi_kirchhoff_lsqr: hipMalloc failed";
+    for (double** p : {&u, &Av, &Av1, &Hu})
+        if ((hil || (p != &Av1 && p != &Hu)) && mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem);
     for (double** p : {&v, &w, &xd, &Atu})
-        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_kirchhoff_lsqr: hipMalloc failed");
+        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem);
     const Vec V{k->red, k->cus};
     rtmi_lsqr_stats out{};
-    out.bytes_device = (int64_t)((2 * per + 4 * nm) * sizeof(double) + ((size_t)(k->nlev ? k->nlev : 1) * per + nm) * sizeof(double) +
+    // the call's vectors, the handle's staging (with kmah: two channels per level) and, with hil, the taps
+    const size_t staging = (size_t)(k->nlev ? k->nlev : 1) * (k->kmah ? 2 : 1) * per + nm;
+    const size_t ntaps = hil ? (size_t)rt::hilbert_ntaps(k->kp.nt) : 0;
+    out.bytes_device = (int64_t)(((hil ? 4 : 2) * per + 4 * nm + staging + ntaps) * sizeof(double) +
                                  (k->ncounts + kRedWords) * sizeof(unsigned long long));
     double operator_ms = 0.0, vector_ms = 0.0;
     rtmi_kirchhoff_stats ks{};
@@ -210,6 +219,22 @@ RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* l
         return r;
     };
 
+    // t = A^T s and t = A s; the Hilbert kernels' event time counts as the operator's
+    auto At = [&](const double* s, double* t) {
+        double ms = 0.0;
+        if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_dev(k, who, s, nullptr, true, Hu, &ms));
+        RTMI_RC(rtmi_internal_kirchhoff_migrate_dev(k, who, s, hil ? Hu : nullptr, t, &ks, false));
+        operator_ms += ks.kernel_ms + ms;
+        return (int)RTMI_OK;
+    };
+    auto Ax = [&](const double* s, double* t) {
+        double ms = 0.0;
+        RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, s, t, hil ? Av1 : nullptr, &ks, false));
+        if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_dev(k, who, Av1, t, false, t, &ms));
+        operator_ms += ks.kernel_ms + ms;
+        return (int)RTMI_OK;
+    };
+
     RTMI_HIP(hipMemcpy(u, data, per * sizeof(double), hipMemcpyHostToDevice));       // the data go up once
     RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
     sec_begin();
@@ -219,8 +244,7 @@ RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* l
     if (go) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per));
     RTMI_HIP(sec_end());
     if (go) {
-        RTMI_RC(rtmi_internal_kirchhoff_migrate_dev(k, who, u, nullptr, v, &ks, false));
-        operator_ms += ks.kernel_ms;
+        RTMI_RC(At(u, v));
         sec_begin();
         RTMI_RC(rtmi_internal_absmax_finite(who, V.red, V.cus, v, nm, &M));
         RTMI_RC(norm_of(who, V, v, nm, M, &nrm, &e, &range));
@@ -235,8 +259,7 @@ RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* l
     // the last iteration that was completed.
     while (go && !rt::lsqr_done(S)) {
         const rt::LsqrState S0 = S;
-        RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, v, Av, nullptr, &ks, false));
-        operator_ms += ks.kernel_ms;
+        RTMI_RC(Ax(v, Av));
         sec_begin();
         RTMI_RC(axmy_norm(who, V, u, Av, S.alfa, per, &nrm, &range));                // u = A v - alfa u
         if (range) {
@@ -247,8 +270,7 @@ RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* l
         if (stepped) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per));
         RTMI_HIP(sec_end());
         if (stepped) {
-            RTMI_RC(rtmi_internal_kirchhoff_migrate_dev(k, who, u, nullptr, Atu, &ks, false));
-            operator_ms += ks.kernel_ms;
+            RTMI_RC(At(u, Atu));
             sec_begin();
             RTMI_RC(axmy_norm(who, V, v, Atu, S.beta, nm, &nrm, &range));            // v = A^T u - beta v
             if (range) {
@@ -279,6 +301,18 @@ RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* l
     out.vector_ms = vector_ms;
     if (st) *st = out;
     return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
+                                    rtmi_lsqr_stats* st) {
+    return lsqr_run("rtmi_kirchhoff_lsqr", false, k, lp, data, x, history, st);
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_lsqr_full(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
+                                         rtmi_lsqr_stats* st) {
+    return lsqr_run("rtmi_kirchhoff_lsqr_full", true, k, lp, data, x, history, st);
 }
 
 RTMI_EXPORT int rtmi_debug_fix_norm(const double* x, int64_t n, double* norm, int32_t* e) {

@@ -3,7 +3,7 @@
 // migration over any handle): the kernel arguments, one (trace, node) pair's arithmetic, the arrivals of a table at a node and
 // their phase, a block's exact maximum and its count, the handle, its argument checks and uploads.  Everything but the handle and
 // the cross-unit entries is in an anonymous namespace: each unit gets its own copy, as with rtmi_host.h.  DESIGN.md sections 14,
-// 19, 20 and 21.
+// 19, 20, 21 and 23.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -157,9 +157,10 @@ struct rtmi_kirchhoff {
     int hw[RTMI_KIRCHHOFF_MAX_LEVELS] = {};
     double asrc = 0.0, arec = 0.0, amid = 0.0;
     double* pt = nullptr;                     // [P][K][nn]
+    double* htaps = nullptr;                  // the Hilbert transform's taps for nt (rt_hilbert.h), uploaded at its first use
     ~rtmi_kirchhoff() {
         for (void* p : {(void*)T, (void*)amp, (void*)theta, (void*)w, (void*)data, (void*)image, (void*)isrc, (void*)irec, (void*)kmah, (void*)counts,
-                        (void*)pt, (void*)red})
+                        (void*)pt, (void*)red, (void*)htaps})
             if (p) (void)hipFree(p);
     }
     KArgs args() const {
@@ -193,6 +194,13 @@ int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cu
 // (kirchhoff_aa.hip), in place over the handle's `data`: before migrate, levels 1 .. nlev - 1 of the bank from level 0
 // (k_aa_filter); gather: after model, the sum of the filtered spreads of every level into level 0 (k_aa_gather).
 int rtmi_internal_kirchhoff_aa_sweep(rtmi_kirchhoff* k, const char* who, bool gather);
+// The Hilbert transform along the handle's traces on device pointers (kirchhoff_hilbert.hip):
+// d_y = (d_add ? d_add : +0) +- H d_x over [N][nt], minus with negate; d_y may be d_add, not d_x.  _check: RTMI_ERR_ARG naming nt
+// when a trace does not fit the kernel's LDS.  The callers have checked that, the arguments and the device.  The handle's taps
+// go up at the first call.  ms, if not NULL: the kernel's event time, waited for; with NULL the call does not wait.
+int rtmi_internal_kirchhoff_hilbert_check(const rtmi_kirchhoff* k, const char* who);
+int rtmi_internal_kirchhoff_hilbert_dev(rtmi_kirchhoff* k, const char* who, const double* d_x, const double* d_add, bool negate,
+                                        double* d_y, double* ms);
 
 namespace {
 

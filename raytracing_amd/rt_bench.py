@@ -1204,6 +1204,29 @@ def hilbert(d):
     return np.fft.ifft(np.fft.fft(d, axis=-1) * h, axis=-1).imag
 
 
+def hilbert_taps(n):
+    """rtmi_hilbert_taps: the taps c_1 .. c_K, K = (n - 1) // 2, of the time-domain form of `hilbert` that the device evaluates
+    (Kirchhoff.hilbert; include/rtmi.h has the formula).  Host only: no device is touched."""
+    n = int(n)
+    K = max((n - 1) // 2, 0)
+    taps = np.zeros(max(K, 1))                     # n = 1 and n = 2 have no taps: nothing is written
+    check(lib().rtmi_hilbert_taps(n, dptr(taps)))
+    return taps[:K]
+
+
+def debug_hilbert(x, add=None, negate=False):
+    """rtmi_debug_hilbert: Kirchhoff.hilbert_device's kernel on host arrays [N, nt] without a handle -> (add or +0) +- H x"""
+    xx = np.ascontiguousarray(x, dtype=np.float64)
+    if xx.ndim != 2:
+        raise ValueError("debug_hilbert: x must be [N, nt]")
+    aa = None if add is None else np.ascontiguousarray(add, dtype=np.float64)
+    if aa is not None and aa.shape != xx.shape:
+        raise ValueError("debug_hilbert: add must have x's shape")
+    y = np.empty_like(xx)
+    check(lib().rtmi_debug_hilbert(dptr(xx), xx.shape[0], xx.shape[1], dptr(aa), 1 if negate else 0, dptr(y)))
+    return y
+
+
 class Kirchhoff:
     """Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_*, include/rtmi.h).  T [P, ny, nx]:
     traveltime_table's T for P surface positions; isrc, irec [N]: each trace's source and receiver position in [0, P); nt samples
@@ -1228,7 +1251,11 @@ class Kirchhoff:
     take and return fp64 contiguous torch tensors on the handle's device: the bits of the calls above, no copy through the host.
       lsqr(d, iter_lim, damp=0.0, atol=0.0, btol=0.0) -> dict(x, istop, itn, r1norm, r2norm, anorm, arnorm)
     is least-squares migration by LSQR in scipy's operation order with every vector on the device (rtmi_kirchhoff_lsqr): the data
-    go up once and x comes down once; defined bit for bit.  The library refuses a handle with kmah."""
+    go up once and x comes down once; defined bit for bit.  The library refuses a handle with kmah, unless hilbert="device":
+    then the solver is rtmi_kirchhoff_lsqr_full, for the full trace ch0 + H ch1 with H on the device:
+      hilbert(d) -> H d on host arrays    and    hilbert_device(x, add=None, negate=False) -> (add or +0) +- H x on torch tensors
+    are that H, on every kind of handle, for nt <= 16384: the matrix of `hilbert` evaluated in the time domain and defined bit for
+    bit, its transpose -H in every bit.  model, migrate and as_linear_operator() keep the FFT form and their bits."""
 
     def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None, kmah=None, pt=None,
                  antialias=None):
@@ -1428,11 +1455,41 @@ class Kirchhoff:
         out = (d0, d1) if self.has_kmah else d0
         return (out, kirchhoff_stats(st)) if stats else out
 
-    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False):
+    def hilbert(self, d):
+        """rtmi_kirchhoff_hilbert: H d along the last axis of [N, nt] host arrays, evaluated on the device in the time domain"""
+        dd = np.ascontiguousarray(d, dtype=np.float64)
+        if dd.size != self.N * self.nt:
+            raise ValueError("Kirchhoff.hilbert: d must be [N, nt]")
+        y = np.empty((self.N, self.nt))
+        check(lib().rtmi_kirchhoff_hilbert(self._open(), dptr(dd), dptr(y)))
+        return y
+
+    def hilbert_device(self, x, add=None, negate=False):
+        """rtmi_kirchhoff_hilbert_dev: (add or +0) + H x, or - H x with negate, [N, nt] torch tensors on the handle's device.  With
+        add the result is written over add and add is returned; x is never written."""
+        import torch
+        who = "hilbert_device"
+        self._device_tensor(who, x, "x", self.N * self.nt)
+        if add is not None:
+            self._device_tensor(who, add, "add", self.N * self.nt)
+        self._on_device(who, x=x, add=add)
+        if add is not None and add.data_ptr() == x.data_ptr():
+            raise ValueError("Kirchhoff.hilbert_device: add may not be x")
+        h = self._open()
+        y = add if add is not None else torch.empty((self.N, self.nt), dtype=torch.float64, device=x.device)
+        torch.cuda.synchronize(x.device)               # the library works on the null stream
+        check(lib().rtmi_kirchhoff_hilbert_dev(h, x.data_ptr(), None if add is None else add.data_ptr(), 1 if negate else 0, y.data_ptr()))
+        return y
+
+    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False, hilbert=None):
         """rtmi_kirchhoff_lsqr: min |L x - d|^2 + damp^2 |x|^2 from x = 0, every vector on the device.  -> dict: x shaped like
         migrate's image, istop (scipy's 0, 1, 2, 7; _lib.LSQR_RANGE: a norm left fp64's normal range), itn, r1norm, r2norm, anorm,
         arnorm; with history=True also history [itn, 4] (alfa, beta, r1norm, arnorm after each iteration); with stats=True also
-        stats (total_ms, operator_ms, vector_ms, bytes_device)."""
+        stats (total_ms, operator_ms, vector_ms, bytes_device).  hilbert="device": rtmi_kirchhoff_lsqr_full, which on a handle
+        with kmah solves for the full trace ch0 + H ch1 (model's trace, with the device's H) and on any other handle is the same
+        call; None: a handle with kmah is refused."""
+        if hilbert not in (None, "device"):
+            raise ValueError('Kirchhoff.lsqr: hilbert must be None or "device"')
         dd = np.ascontiguousarray(d, dtype=np.float64)
         if dd.size != self.N * self.nt:
             raise ValueError("Kirchhoff.lsqr: d must be [N, nt]")
@@ -1444,7 +1501,8 @@ class Kirchhoff:
         x = np.empty((self.nb, self.ny, self.nx))
         hist = np.zeros((iter_lim, 4)) if history else None
         st = _lib.LsqrStats()
-        check(lib().rtmi_kirchhoff_lsqr(self._open(), C.byref(lp), dptr(dd), dptr(x), dptr(hist), C.byref(st)))
+        solver = lib().rtmi_kirchhoff_lsqr_full if hilbert == "device" else lib().rtmi_kirchhoff_lsqr
+        check(solver(self._open(), C.byref(lp), dptr(dd), dptr(x), dptr(hist), C.byref(st)))
         out = {"x": x if self.nbin else x[0], "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm,
                "anorm": st.anorm, "arnorm": st.arnorm}
         if history:

@@ -19,7 +19,12 @@ of 0, 1, 2, 4, 8, 16, 32, 64.  It prints, for migrate and model, the plain kerne
 as_linear_operator() with atol = btol = 0 and iter_lim = ITERS, and the device loop, Kirchhoff.lsqr, on the same data (the model
 of a random reflectivity).  It prints, per iteration: the wall time of each loop, the sum of the two operators' kernel_ms in the
 device loop, its vector_ms, and what the device loop's iteration spends above the two kernels.
-Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV] [--lsqr ITERS]"""
+--hilbert (with --arrivals K, default 2, and --lsqr ITERS, default 3) times the Hilbert transform on the device on
+the same case with a handle of K arrivals and kmah, in one process: k_hilbert alone on the [N, nt] traces (the wall time of
+Kirchhoff.hilbert_device, which ends with the stream idle: launch, kernel and the wait; median of --reps), rt_bench.hilbert (numpy's
+FFT on the host) on the same array for scale, and per iteration the wall time of Kirchhoff.lsqr(hilbert="device") against scipy's
+lsqr over as_linear_operator(), whose model and migrate go through the host's FFT.  --lsqr 0 leaves the two loops out.
+Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV] [--lsqr ITERS] [--hilbert]"""
 import argparse
 import json
 import os
@@ -236,6 +241,60 @@ def run_lsqr(iters):
                       "x_max_rel_diff": float(np.max(np.abs(dev["x"].reshape(-1) - host[0])) / np.max(np.abs(host[0])))}), flush=True)
 
 
+def run_hilbert(K, reps, iters):
+    import torch
+    from scipy.sparse.linalg import lsqr
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, _ = tables(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    N = len(isrc)
+    TK = np.stack([T + 0.003 * i for i in range(K)], axis=1)
+    km = np.broadcast_to(np.arange(K, dtype=np.float64)[None, :, None, None], TK.shape)
+    op = rb.Kirchhoff(TK, isrc, irec, nt, dt, kmah=km)
+    x = np.random.default_rng(1).standard_normal((N, nt))
+    tx = torch.from_numpy(x).to("cuda")
+    op.hilbert_device(tx)                                        # warm-up: code object, the taps
+    ws = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        ty = op.hilbert_device(tx)
+        ws.append((time.perf_counter() - t0) * 1e3)
+    t0 = time.perf_counter()
+    hf = rb.hilbert(x)
+    fft_ms = (time.perf_counter() - t0) * 1e3
+    diff = float(np.max(np.abs(ty.cpu().numpy() - hf)) / np.max(np.abs(hf)))
+    taps = nt // 4 if nt % 2 == 0 else (nt - 1) // 2
+    # the fp64 floor: 3 operations per output and tap, 4 cycles per wave instruction, 1024 SIMDs at 2.4 GHz
+    floor_ms = N * nt * taps * 3 / 64 * 4 / 1024 / 2.4e9 * 1e3
+    k = float(np.median(ws))
+    print(json.dumps({"what": "k_hilbert alone (launch, kernel, wait)", "N": N, "nt": nt, "taps": taps, "wall_ms_median": k, "wall_ms": ws,
+                      "fp64_issue_floor_ms": floor_ms, "wall_over_fp64_floor": k / floor_ms, "numpy_fft_on_the_host_ms": fft_ms,
+                      "max_diff_from_fft_over_max": diff}), flush=True)
+    if iters > 0:
+        d = op.model(np.random.default_rng(1).standard_normal(T.shape[1:]))
+        op.lsqr(d, 1, hilbert="device")                          # warm-up: code objects, both operators
+        t0 = time.perf_counter()
+        dev = op.lsqr(d, iters, stats=True, hilbert="device")
+        t1 = time.perf_counter()
+        host = lsqr(op.as_linear_operator(), d.reshape(-1), atol=0, btol=0, iter_lim=iters)
+        t2 = time.perf_counter()
+        st, n = dev["stats"], dev["itn"]
+        dev_ms, host_ms = (t1 - t0) * 1e3 / n, (t2 - t1) * 1e3 / host[2]
+        print(json.dumps({"what": f"least-squares migration of the full trace, K = {K} with kmah, {iters} iterations", "N": N,
+                          "nodes": T[0].size, "nt": nt, "itn_device": n, "itn_host": int(host[2]),
+                          "device_loop_wall_ms_per_iteration": dev_ms, "host_loop_wall_ms_per_iteration": host_ms,
+                          "host_over_device": host_ms / dev_ms, "operators_kernel_ms_per_iteration": st["operator_ms"] / n,
+                          "vector_ms_per_iteration": st["vector_ms"] / n, "bytes_device": st["bytes_device"],
+                          "r1norm_device": dev["r1norm"], "r1norm_host": float(host[3]),
+                          "x_max_rel_diff": float(np.max(np.abs(dev["x"].reshape(-1) - host[0])) / np.max(np.abs(host[0])))}), flush=True)
+    op.close()
+
+
 def restatement():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import kirchhoff_ref as K
@@ -256,8 +315,11 @@ if __name__ == "__main__":
     ap.add_argument("--arrivals", type=int, choices=(1, 2, 3, 4))
     ap.add_argument("--antialias", type=int, choices=range(1, 9), metavar="NLEV")
     ap.add_argument("--lsqr", type=int, metavar="ITERS")
+    ap.add_argument("--hilbert", action="store_true")
     a = ap.parse_args()
-    if a.lsqr:
+    if a.hilbert:
+        run_hilbert(a.arrivals or 2, a.reps, 3 if a.lsqr is None else a.lsqr)
+    elif a.lsqr:
         run_lsqr(a.lsqr)
     elif a.antialias:
         run_antialias(a.arrivals or 1, a.antialias, a.reps)
