@@ -814,6 +814,74 @@ int rtmi_kirchhoff_hilbert_dev(rtmi_kirchhoff *k, const double *d_x, const doubl
 int rtmi_kirchhoff_lsqr_full(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const double *data, double *x, double *history,
                              rtmi_lsqr_stats *st);
 
+/* Recorded rays compiled into a sparse ray-tomography matrix on the device, its products and LSQR on it.  DESIGN.md section 24.
+ * The matrix is the A of rtmi_traveltime_perturb / _backproject above -- the derivative of reported traveltimes with respect to
+ * the field's n samples Z [qy][qx], the rays held fixed -- with one row per observation, built once from a batch's record.  The
+ * handle keeps the matrix, not the record: after rtmi_tomo_append the batch may be destroyed, and a joint inversion over many
+ * sources appends source after source.
+ * rtmi_tomo_create: the handle takes the field's sample axes (qx, qy, the ends of both linspace axes, 1 / h) and lives on the
+ * field's device, the calling thread's current one (else RTMI_ERR_ARG); it keeps no reference to the field.
+ * rtmi_tomo_append: which [R] selects the observation of ray m, in the caller's ray order: -1 its end, c in 0 .. kmax - 1 crossing
+ * c of `line` by rtmi_crossings' rule, RTMI_TOMO_SKIP no row.  which NULL: the end of every ray, and line may be NULL.  Every ray
+ * not skipped gets one row, in the caller's ray order, numbered from *first_row, the handle's row count before the call.  An
+ * observation that does not exist (a ray past rec_rows, c >= the ray's count) gives an empty row.  nseg [R], if not NULL: the
+ * row's segments, 0 for an empty row, -1 for a skipped ray.  The batch's rules are rtmi_traveltime_backproject's (record_stride 1,
+ * critical rays drained first, the rtmi_batch_set_state rule, both dtypes, every method, op10 / op11 with the batch's gamma), and
+ * so are its errors; RTMI_ERR_ARG also for a field whose sample axes differ from the handle's, a which value outside
+ * -2 .. kmax - 1, and which >= 0 without a line.
+ * A row: the walk of rtmi_traveltime_backproject with weight 1 on this observation and 0 elsewhere gives each recorded row j that
+ * carries weight wr_j = a_j coef_j (a_j the trapezoid weight, with the Hermite terms on the crossing step, where the walk of a
+ * crossing ends).  A segment is one cell visit: the maximal run of consecutive weighted rows in the same cell (jx, jy); coming
+ * back to a cell starts a new one.  Its value is p[q] = sum over the run's rows of wr_j phi_q(row j), q = 0 .. 3, in row order,
+ * every product and every add a separate fp64 operation; its columns are base, base + 1, base + qx, base + qx + 1 with
+ * base = jy qx + jx.  Appends add blocks to the handle and never rebuild earlier ones.  The handle keeps Vmax = max |p| over
+ * everything appended.
+ * rtmi_tomo_read: the matrix in row order, a row's segments in visit order: row_ptr [rows + 1], base [segments],
+ * val [segments][4]; base and val may be NULL (sizes first), and with row_ptr NULL nothing is read.
+ * rtmi_tomo_apply: y [rows] from x [qy][qx]: acc = +0.0, then per segment in visit order
+ *   acc = fl(acc + fl(fl(fl(fl(p0 x0) + fl(p1 x1)) + fl(p2 x2)) + fl(p3 x3))), x0 .. x3 the segment's four samples; y_r = acc.
+ * One fixed order, the same bits in every schedule; an empty row gives +0.0.
+ * rtmi_tomo_transpose: g [qy][qx] from w [rows].  W = max |w_r| (the exact reduction of the Kirchhoff calls).  W = 0, no segments
+ * or Vmax = 0: g is all +0.0.  Else bound = fl(Vmax W), which must be a normal number (else RTMI_ERR_ARG; the solver stops with
+ * RTMI_LSQR_RANGE), e = ex - 57 with bound = f 2^ex, f in [0.5, 1); every product contributes rint(fl(p_q w_r) 2^-e) to the
+ * two-word integer of its sample, and each sample is rounded to fp64 once.  Integer sums commute: the same bits in every schedule,
+ * every order of appends and every order of rays within an append.  stats.atomics: the adds issued; stats.scale_exp: e.
+ * The host forms are upload + the _dev forms + download and refuse a value that is not finite (RTMI_ERR_ARG); the _dev forms take
+ * memory of the handle's device, checked as rtmi_kirchhoff_migrate_dev checks its own, read x as it is, and count a w_r that is
+ * not finite as 0.
+ * rtmi_tomo_lsqr: min |A x - rhs|^2 + damp^2 |x|^2 + lx^2 |Dx x|^2 + ly^2 |Dy x|^2 from x = 0, smooth = {lx, ly} or NULL for none,
+ * rhs [rows] and x [qy][qx] host fp64, every vector on the device in between.  Everything rtmi_kirchhoff_lsqr's comment defines
+ * holds word for word -- scalars, updates, norms, stop tests and istop values, history rows, the abandoned iteration on a range
+ * stop, stats -- the two solvers run one loop (raytracing_amd/csrc/rt_lsqr_device.h).  The operator is stacked:
+ * u = [A x | Dx x | Dy x], contiguous, of rows + qy (qx - 1) + (qy - 1) qx values (the difference blocks only with smooth):
+ *   (Dx x)[i][j] = fl(lx fl(x[i][j + 1] - x[i][j])),  (Dy x)[i][j] = fl(ly fl(x[i + 1][j] - x[i][j]));
+ *   transposed at node (i, j): r = fl(lx fl(ux[i][j - 1] - ux[i][j])), s = fl(ly fl(uy[i - 1][j] - uy[i][j])), a missing
+ *   neighbour +0.0, and g = fl(gA + fl(r + s)) with gA the transposed product above (W over the first `rows` values of u).
+ * operator_ms: the event time of the two products; bytes_device: the handle and the call's vectors.
+ * RTMI_ERR_ARG before any device work: a null handle, params, rhs or x; rtmi_kirchhoff_lsqr's rules for lp; a smooth value
+ * negative or not finite; an rhs value that is not finite; a handle with no rows.
+ * stats of _info and the products: rows, segments, padded_segments (the slots of the sliced storage: slices of 64 rows, each as
+ * wide as its longest row), bytes_device, compile_ms (the event time of the last append), vmax, qx, qy; the products add
+ * kernel_ms, and _transpose atomics and scale_exp.
+ * Not covered: row weights, model masks, x0, a second-order regulariser; removing rows from a handle; several GPUs, fp32 vectors;
+ * model parameterisations other than the field's own samples. */
+#define RTMI_TOMO_SKIP (-2)
+typedef struct rtmi_tomo rtmi_tomo;
+typedef struct { int64_t rows, segments, padded_segments, bytes_device, atomics; double compile_ms, kernel_ms, vmax;
+                 int32_t qx, qy, scale_exp, reserved0; int64_t reserved[4]; } rtmi_tomo_stats;
+int rtmi_tomo_create(const rtmi_field *f, rtmi_tomo **out);
+int rtmi_tomo_append(rtmi_tomo *t, rtmi_batch *b, const double line[3], int32_t kmax, const int32_t *which, int32_t *nseg,
+                     int64_t *first_row);
+int rtmi_tomo_read(const rtmi_tomo *t, int64_t *row_ptr, int32_t *base, double *val);
+int rtmi_tomo_info(const rtmi_tomo *t, rtmi_tomo_stats *st);
+int rtmi_tomo_apply(rtmi_tomo *t, const double *x, double *y, rtmi_tomo_stats *st);
+int rtmi_tomo_apply_dev(rtmi_tomo *t, const double *d_x, double *d_y, rtmi_tomo_stats *st);
+int rtmi_tomo_transpose(rtmi_tomo *t, const double *w, double *g, rtmi_tomo_stats *st);
+int rtmi_tomo_transpose_dev(rtmi_tomo *t, const double *d_w, double *d_g, rtmi_tomo_stats *st);
+int rtmi_tomo_lsqr(rtmi_tomo *t, const rtmi_lsqr_params *lp, const double smooth[2], const double *rhs, double *x, double *history,
+                   rtmi_lsqr_stats *st);
+void rtmi_tomo_destroy(rtmi_tomo *t);
+
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

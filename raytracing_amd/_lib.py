@@ -145,6 +145,13 @@ class LsqrStats(C.Structure):
                 ("bytes_device", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+class TomoStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("segments", C.c_int64), ("padded_segments", C.c_int64), ("bytes_device", C.c_int64),
+                ("atomics", C.c_int64), ("compile_ms", C.c_double), ("kernel_ms", C.c_double), ("vmax", C.c_double),
+                ("qx", C.c_int32), ("qy", C.c_int32), ("scale_exp", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
 HILBERT_MAX_NT = 16384  # the longest trace rtmi_kirchhoff_hilbert takes: one copy of it in LDS
 
@@ -214,6 +221,16 @@ SYMBOLS = {
     "rtmi_kirchhoff_hilbert": (C.c_int, [C.c_void_p, _dp, _dp]),
     "rtmi_kirchhoff_hilbert_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rtmi_kirchhoff_lsqr_full": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_tomo_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rtmi_tomo_append": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int32, _ip, _ip, C.POINTER(C.c_int64)]),
+    "rtmi_tomo_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), _ip, _dp]),
+    "rtmi_tomo_info": (C.c_int, [C.c_void_p, C.POINTER(TomoStats)]),
+    "rtmi_tomo_apply": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(TomoStats)]),
+    "rtmi_tomo_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TomoStats)]),
+    "rtmi_tomo_transpose": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(TomoStats)]),
+    "rtmi_tomo_transpose_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TomoStats)]),
+    "rtmi_tomo_lsqr": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_tomo_destroy": (None, [C.c_void_p]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -4,170 +4,12 @@
 // data to the one download of the model.  include/rtmi.h states the contract; DESIGN.md section 21 the definitions, the memory and
 // what was measured; rt_lsqr.h the scalar recurrence (host, scipy's operation order).  _lsqr_full on a handle with kmah solves
 // for the full trace ch0 + H ch1 with the Hilbert transform of kirchhoff_hilbert.hip around the pair.
-// The vector passes are memory-bound: 256 lanes per block, grid-stride, at most 4 blocks per CU, 16-byte loads and stores when
-// every pointer of the pass is 16-byte aligned (`wide`; the solver's own allocations always are).
-//   k_axmy_absmax  y_i = t_i - fl(a y_i), and max |y_i| of the new y in the same pass (block_max_to)
-//   k_scale        y_i = fl(s y_i)
-//   k_xw           x_i = x_i + fl(c1 w_i) and w_i = v_i - fl(c2 w_i)
-//   k_sumsq        the norm's integer sum: S += rint(ldexp(fl(x_i x_i), -e)), a two-word sum with an explicit carry per lane, per
-//                  wave and per block, then one two-word atomic add per block into one global pair.  Integer sums commute: the
-//                  same bits in every schedule.
-// Every product and every add or subtract is a separate fp64 operation: the kernels spell them __dmul_rn / __dadd_rn, and the
-// unit is built with -ffp-contract=off like the rest of the library.
+// The loop, its vector passes and the order-independent norm are rt_lsqr_device.h's, shared with tomo.hip.
 #include "rt_hilbert.h"
 #include "rt_kirchhoff.h"
-#include "rt_lsqr.h"
-
-static_assert(RTMI_LSQR_RANGE == rt::kLsqrRange, "rtmi.h and rt_lsqr.h name one istop");
+#include "rt_lsqr_device.h"
 
 namespace {
-
-// one pass's items of lane gid: f2(i) for the pairs (2 i, 2 i + 1) when wide, f1(i) for single items
-template <typename F2, typename F1>
-__device__ __forceinline__ void sweep(long n, bool wide, F2&& f2, F1&& f1) {
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x, gsz = (long)gridDim.x * 256;
-    if (wide) {
-        for (long i = gid; i < n / 2; i += gsz) f2(i);
-        if ((n & 1) && gid == 0) f1(n - 1);
-    } else {
-        for (long i = gid; i < n; i += gsz) f1(i);
-    }
-}
-
-__device__ __forceinline__ double axmy(double t, double a, double y) { return __dadd_rn(t, -__dmul_rn(a, y)); }
-
-__global__ void __launch_bounds__(256) k_axmy_absmax(double* __restrict__ y, const double* __restrict__ t, double a, long n, bool wide,
-                                                     unsigned long long* __restrict__ out) {
-    double m = 0.0;
-    sweep(n, wide,
-          [&](long i) {
-              const double2 yv = ((const double2*)y)[i], tv = ((const double2*)t)[i];
-              const double2 r = make_double2(axmy(tv.x, a, yv.x), axmy(tv.y, a, yv.y));
-              ((double2*)y)[i] = r;
-              m = fmax(m, fmax(fabs(r.x), fabs(r.y)));
-          },
-          [&](long i) {
-              const double r = axmy(t[i], a, y[i]);
-              y[i] = r;
-              m = fmax(m, fabs(r));
-          });
-    block_max_to(out, m);
-}
-
-__global__ void __launch_bounds__(256) k_scale(double* __restrict__ y, double s, long n, bool wide) {
-    sweep(n, wide,
-          [&](long i) {
-              const double2 v = ((const double2*)y)[i];
-              ((double2*)y)[i] = make_double2(__dmul_rn(s, v.x), __dmul_rn(s, v.y));
-          },
-          [&](long i) { y[i] = __dmul_rn(s, y[i]); });
-}
-
-__global__ void __launch_bounds__(256) k_xw(double* __restrict__ x, double* __restrict__ w, const double* __restrict__ v, double c1,
-                                            double c2, long n, bool wide) {
-    sweep(n, wide,
-          [&](long i) {
-              const double2 xv = ((const double2*)x)[i], wv = ((const double2*)w)[i], vv = ((const double2*)v)[i];
-              ((double2*)x)[i] = make_double2(__dadd_rn(xv.x, __dmul_rn(c1, wv.x)), __dadd_rn(xv.y, __dmul_rn(c1, wv.y)));
-              ((double2*)w)[i] = make_double2(axmy(vv.x, c2, wv.x), axmy(vv.y, c2, wv.y));
-          },
-          [&](long i) {
-              const double wi = w[i];
-              x[i] = __dadd_rn(x[i], __dmul_rn(c1, wi));
-              w[i] = axmy(v[i], c2, wi);
-          });
-}
-
-// acc = (lo, hi), an unsigned two-word integer that starts from 0.  A term is at most 2^57 quanta (rt_fix128.h).
-__global__ void __launch_bounds__(256) k_sumsq(const double* __restrict__ x, long n, int e, bool wide, unsigned long long* __restrict__ acc) {
-    __shared__ unsigned long long wlo[4], whi[4];
-    unsigned long long lo = 0ull, hi = 0ull;
-    auto term = [&](double v) {
-        const unsigned long long q = (unsigned long long)(long long)rint(ldexp(__dmul_rn(v, v), -e));
-        lo += q;
-        hi += lo < q ? 1ull : 0ull;
-    };
-    sweep(n, wide,
-          [&](long i) {
-              const double2 v = ((const double2*)x)[i];
-              term(v.x);
-              term(v.y);
-          },
-          [&](long i) { term(x[i]); });
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long olo = __shfl_xor(lo, off), ohi = __shfl_xor(hi, off);
-        lo += olo;
-        hi += ohi + (lo < olo ? 1ull : 0ull);
-    }
-    const int tid = (int)threadIdx.x;
-    if ((tid & 63) == 0) { wlo[tid >> 6] = lo; whi[tid >> 6] = hi; }
-    __syncthreads();
-    if (tid == 0) {
-        lo = wlo[0];
-        hi = whi[0];
-        for (int q = 1; q < 4; q++) {
-            lo += wlo[q];
-            hi += whi[q] + (lo < wlo[q] ? 1ull : 0ull);
-        }
-        // rt::add128 with a two-word addend: the low word's carry is read off the value the add returned
-        if (lo | hi) {
-            const unsigned long long old = lo ? atomicAdd(acc, lo) : 0ull;
-            const unsigned long long h = hi + ((old + lo) < old ? 1ull : 0ull);
-            if (h) atomicAdd(acc + 1, h);
-        }
-    }
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// The words of a handle's `red` this unit uses: [0] rtmi_internal_absmax_finite, [1] k_axmy_absmax, [2], [3] k_sumsq.
-struct Vec {
-    unsigned long long* red;
-    int cus;
-};
-
-// The norm of n finite doubles with max |x_i| = M: range = true, and no norm, when fl(M M) is not a normal number
-int norm_of(const char* who, const Vec& V, const double* d, size_t n, double M, double* norm, int* e_out, bool* range) {
-    *range = false;
-    *e_out = 0;
-    *norm = 0.0;
-    if (M == 0.0) return RTMI_OK;
-    const double bound = M * M;
-    if (!std::isnormal(bound)) {
-        *range = true;
-        return RTMI_OK;
-    }
-    const int e = rt::fix_exponent(bound);
-    RTMI_HIP(hipMemsetAsync(V.red + 2, 0, 2 * sizeof(unsigned long long), nullptr));
-    hipLaunchKernelGGL(k_sumsq, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, d, (long)n, e, aligned16(d), V.red + 2);
-    RTMI_HIP(hipGetLastError());
-    unsigned long long s[2] = {0, 0};
-    RTMI_HIP(hipMemcpy(s, V.red + 2, sizeof(s), hipMemcpyDeviceToHost));
-    const unsigned long long lo = s[0] + rt::kFixBias;         // the accumulator of rt_fix128.h: the low word carries the bias
-    const unsigned long long hi = s[1] + (lo < s[0] ? 1ull : 0ull);
-    // sqrt(S 2^e) with the even part of e taken out of the root: the same bits, and S 2^e itself may exceed fp64's range
-    const int odd = e & 1;
-    *norm = std::ldexp(std::sqrt(std::ldexp(rt::fix_to_double(lo, hi), odd)), (e - odd) / 2);
-    *e_out = e;
-    return RTMI_OK;
-}
-
-// y = t - a y, then the norm of the new y
-int axmy_norm(const char* who, const Vec& V, double* y, const double* t, double a, size_t n, double* norm, bool* range) {
-    RTMI_HIP(hipMemsetAsync(V.red + 1, 0, sizeof(unsigned long long), nullptr));
-    hipLaunchKernelGGL(k_axmy_absmax, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, t, a, (long)n, aligned16(y) && aligned16(t), V.red + 1);
-    RTMI_HIP(hipGetLastError());
-    double M = 0.0;
-    RTMI_HIP(hipMemcpy(&M, V.red + 1, sizeof(double), hipMemcpyDeviceToHost));
-    int e = 0;
-    return norm_of(who, V, y, n, M, norm, &e, range);
-}
-
-int scale(const char* who, const Vec& V, double* y, double s, size_t n) {
-    hipLaunchKernelGGL(k_scale, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, s, (long)n, aligned16(y));
-    RTMI_HIP(hipGetLastError());
-    return RTMI_OK;
-}
 
 // Both solvers.  full: on a handle with kmah the operator is that of the full trace, A x = ch0 + H ch1 with (ch0, ch1) =
 // model2(x), and A^T u = migrate2(u, -H u), its transpose in every bit; on any other handle `full` changes nothing.
@@ -177,10 +19,7 @@ int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_para
     RTMI_ARG(lp, "null params");
     RTMI_ARG(data, "null data");
     RTMI_ARG(x, "null x");
-    RTMI_ARG(lp->iter_lim >= 1, "iter_lim must be >= 1");
-    RTMI_ARG(std::isfinite(lp->damp) && lp->damp >= 0.0, "damp must be finite and >= 0");
-    RTMI_ARG(std::isfinite(lp->atol) && lp->atol >= 0.0, "atol must be finite and >= 0");
-    RTMI_ARG(std::isfinite(lp->btol) && lp->btol >= 0.0, "btol must be finite and >= 0");
+    RTMI_RC(lsqr_check_params(who, lp));
     RTMI_ARG(full || !k->kmah, "the handle has kmah: its trace is ch0 + H ch1, which rtmi_kirchhoff_lsqr_full solves for");
     const bool hil = full && k->kmah;
     if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_check(k, who));
@@ -203,24 +42,11 @@ int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_para
     const size_t ntaps = hil ? (size_t)rt::hilbert_ntaps(k->kp.nt) : 0;
     out.bytes_device = (int64_t)(((hil ? 4 : 2) * per + 4 * nm + staging + ntaps) * sizeof(double) +
                                  (k->ncounts + kRedWords) * sizeof(unsigned long long));
-    double operator_ms = 0.0, vector_ms = 0.0;
+    double operator_ms = 0.0;
     rtmi_kirchhoff_stats ks{};
-    rt::LsqrState S;
-    rt::lsqr_begin(S, lp->damp, lp->atol, lp->btol, lp->iter_lim);
-    bool range = false;
-    double nrm = 0.0, M = 0.0;
-    int e = 0;
-    // the time of a vector section: its passes and read-backs, to the point where the device is idle
-    double t_sec = 0.0;
-    auto sec_begin = [&]() { t_sec = now_ms(); };
-    auto sec_end = [&]() {
-        const hipError_t r = hipStreamSynchronize(nullptr);
-        vector_ms += now_ms() - t_sec;
-        return r;
-    };
 
     // t = A^T s and t = A s; the Hilbert kernels' event time counts as the operator's
-    auto At = [&](const double* s, double* t) {
+    auto At = [&](const double* s, double* t, bool*) {
         double ms = 0.0;
         if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_dev(k, who, s, nullptr, true, Hu, &ms));
         RTMI_RC(rtmi_internal_kirchhoff_migrate_dev(k, who, s, hil ? Hu : nullptr, t, &ks, false));
@@ -237,68 +63,10 @@ int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_para
 
     RTMI_HIP(hipMemcpy(u, data, per * sizeof(double), hipMemcpyHostToDevice));       // the data go up once
     RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
-    sec_begin();
-    RTMI_RC(rtmi_internal_absmax_finite(who, V.red, V.cus, u, per, &M));
-    RTMI_RC(norm_of(who, V, u, per, M, &nrm, &e, &range));
-    bool go = !range && rt::lsqr_first_beta(S, nrm);
-    if (go) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per));
-    RTMI_HIP(sec_end());
-    if (go) {
-        RTMI_RC(At(u, v));
-        sec_begin();
-        RTMI_RC(rtmi_internal_absmax_finite(who, V.red, V.cus, v, nm, &M));
-        RTMI_RC(norm_of(who, V, v, nm, M, &nrm, &e, &range));
-        go = !range && rt::lsqr_first_alfa(S, nrm);
-        if (go) {
-            RTMI_RC(scale(who, V, v, 1.0 / S.alfa, nm));
-            RTMI_HIP(hipMemcpyAsync(w, v, nm * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
-        }
-        RTMI_HIP(sec_end());
-    }
-    // A norm that leaves the range inside the loop abandons its iteration: itn, the scalars, the history and x are those of
-    // the last iteration that was completed.
-    while (go && !rt::lsqr_done(S)) {
-        const rt::LsqrState S0 = S;
-        RTMI_RC(Ax(v, Av));
-        sec_begin();
-        RTMI_RC(axmy_norm(who, V, u, Av, S.alfa, per, &nrm, &range));                // u = A v - alfa u
-        if (range) {
-            RTMI_HIP(sec_end());
-            break;
-        }
-        const bool stepped = rt::lsqr_beta(S, nrm);
-        if (stepped) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per));
-        RTMI_HIP(sec_end());
-        if (stepped) {
-            RTMI_RC(At(u, Atu));
-            sec_begin();
-            RTMI_RC(axmy_norm(who, V, v, Atu, S.beta, nm, &nrm, &range));            // v = A^T u - beta v
-            if (range) {
-                RTMI_HIP(sec_end());
-                S = S0;
-                break;
-            }
-            if (rt::lsqr_alfa(S, nrm)) RTMI_RC(scale(who, V, v, 1.0 / S.alfa, nm));
-            RTMI_HIP(sec_end());
-        }
-        rt::lsqr_rotate(S);
-        sec_begin();
-        hipLaunchKernelGGL(k_xw, stride_blocks(V.cus, nm, 2), dim3(256), 0, nullptr, xd, w, v, S.c1, S.c2, (long)nm,
-                           aligned16(xd) && aligned16(w) && aligned16(v));
-        RTMI_HIP(hipGetLastError());
-        RTMI_HIP(sec_end());
-        if (history) {
-            double* row = history + (size_t)(S.itn - 1) * 4;
-            row[0] = S.alfa; row[1] = S.beta; row[2] = S.r1norm; row[3] = S.arnorm;
-        }
-    }
+    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out));
     RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));           // the model comes down once
-    out.istop = range ? rt::kLsqrRange : S.istop;
-    out.itn = S.itn;
-    out.r1norm = S.r1norm; out.r2norm = S.r2norm; out.anorm = S.anorm; out.arnorm = S.arnorm;
     out.total_ms = now_ms() - t_begin;
     out.operator_ms = operator_ms;
-    out.vector_ms = vector_ms;
     if (st) *st = out;
     return RTMI_OK;
 }

@@ -1,13 +1,12 @@
 // rt_kirchhoff.h -- what the Kirchhoff units share (kirchhoff.hip: the migrate / model kernel pair of every kind of handle and its
 // one launch path; kirchhoff_aa.hip: the anti-aliased handle, its bank filter and level sum; kirchhoff_lsqr.hip: least-squares
 // migration over any handle): the kernel arguments, one (trace, node) pair's arithmetic, the arrivals of a table at a node and
-// their phase, a block's exact maximum and its count, the handle, its argument checks and uploads.  Everything but the handle and
+// their phase, a block's count, the handle, its argument checks and uploads.  Everything but the handle and
 // the cross-unit entries is in an anonymous namespace: each unit gets its own copy, as with rtmi_host.h.  DESIGN.md sections 14,
 // 19, 20, 21 and 23.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -91,21 +90,6 @@ __device__ __forceinline__ void block_count_to(unsigned long long* counts, long 
     }
 }
 
-// The block's largest v (v >= 0, never NaN) into *slot, a double kept as its bits: non-negative doubles order as unsigned integers,
-// so one integer atomic max per block is the second stage of the reduction, and fmax is exact: the same bits in every schedule.
-// The slot starts from 0.  Blocks of 256 lanes.
-__device__ __forceinline__ void block_max_to(unsigned long long* slot, double v) {
-    __shared__ double wmax[4];
-    for (int off = 1; off < 64; off <<= 1) v = fmax(v, __shfl_xor(v, off));
-    const int tid = (int)threadIdx.x;
-    if ((tid & 63) == 0) wmax[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) {
-        const double m = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
-        if (m > 0.0) atomicMax(slot, (unsigned long long)__double_as_longlong(m));
-    }
-}
-
 // kmah on the device: the caustic count mod 4 as int8, -1 where the table's value is not a finite non-negative integer.
 constexpr int8_t kBadKmah = -1;
 
@@ -130,10 +114,6 @@ struct Phase { bool valid, odd, neg; };
 __device__ __forceinline__ Phase phase_of(int ms, int mr) {
     const int q = ms + mr;
     return Phase{(ms | mr) >= 0, (q & 1) != 0, ((q + 1) & 2) != 0};
-}
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 }  // namespace
@@ -187,9 +167,6 @@ int rtmi_internal_kirchhoff_migrate_dev(rtmi_kirchhoff* k, const char* who, cons
                                         rtmi_kirchhoff_stats* st, bool counts);
 int rtmi_internal_kirchhoff_model_dev(rtmi_kirchhoff* k, const char* who, const double* d_model, double* d0, double* d1,
                                       rtmi_kirchhoff_stats* st, bool counts);
-// max |x_i| over the finite values of n doubles on the device (0 when there is none): k_absmax_finite and an 8-byte read-back.
-// red: a device word for the result (the handle's); cus: the device's compute units
-int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cus, const double* d_x, size_t n, double* out);
 // What that path launches around the pair kernel on a handle of rtmi_kirchhoff_create_aa with more than one level
 // (kirchhoff_aa.hip), in place over the handle's `data`: before migrate, levels 1 .. nlev - 1 of the bank from level 0
 // (k_aa_filter); gather: after model, the sum of the filtered spreads of every level into level 0 (k_aa_gather).
@@ -204,31 +181,11 @@ int rtmi_internal_kirchhoff_hilbert_dev(rtmi_kirchhoff* k, const char* who, cons
 
 namespace {
 
-constexpr size_t kRedWords = 8;
-
 int migrate_block(int nb) { return nb > 16 ? 128 : 256; }    // [bin][lane] fp64 in LDS stays within 32 KiB
 
-// blocks of 256 lanes for a grid-stride pass over n items, each lane taking `per` of them at a time: at most 4 blocks per CU
-dim3 stride_blocks(int cus, size_t n, size_t per) {
-    const size_t want = (n + 256 * per - 1) / (256 * per), cap = (size_t)4 * (size_t)cus;
-    return dim3((unsigned)(want < 1 ? 1 : want < cap ? want : cap));
-}
-
-// `bytes` at p are memory of the handle's device (hipPointerGetAttributes), and the allocation holds them all
+// `bytes` at p are memory of the handle's device, and the allocation holds them all (rtmi_host.h)
 int check_device_pointer(const rtmi_kirchhoff* k, const char* who, const void* p, size_t bytes, const char* name) {
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();             // a plain host pointer: not an error of the runtime's to keep
-    const bool ok = e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == k->device;
-    RTMI_ARG(ok, std::string(name) + " is not memory of the handle's device");
-    void* base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        RTMI_ARG(false, std::string(name) + ": the extent of its allocation could not be read");
-    }
-    RTMI_ARG((const char*)p + bytes <= (const char*)base + size, std::string(name) + " is shorter than the call needs");
-    return RTMI_OK;
+    return check_device_pointer(k->device, who, p, bytes, name);
 }
 
 int check_device(const rtmi_kirchhoff* k, const char* who) {

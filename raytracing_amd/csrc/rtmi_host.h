@@ -1,11 +1,13 @@
 // rtmi_host.h -- the host-side support layer of every translation unit: the ways out of an entry, one call's device memory and
-// event marks, grid sizing, and the checks every entry that reads a batch's recorded rows makes.  A new post-trace unit starts
+// event marks, grid sizing, a block's exact maximum, the check of a caller's device pointer, and the checks every entry that reads
+// a batch's recorded rows makes.  A new post-trace unit starts
 // from this header and from rt_rows.h, the record as its kernels read it (DESIGN.md sections 15 to 17).  Everything is in an
 // anonymous namespace: each unit gets its own copy, as with rt_crossing.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -84,6 +86,51 @@ template <typename F> auto by_dtype(int dtype, F&& f) { return dtype == RTMI_F64
 
 // one lane per item, 256 lanes per block
 dim3 blocks(long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// blocks of 256 lanes for a grid-stride pass over n items, each lane taking `per` of them at a time: at most 4 blocks per CU
+dim3 stride_blocks(int cus, size_t n, size_t per) {
+    const size_t want = (n + 256 * per - 1) / (256 * per), cap = (size_t)4 * (size_t)cus;
+    return dim3((unsigned)(want < 1 ? 1 : want < cap ? want : cap));
+}
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The words a handle keeps for the results of its reductions (rtmi_internal_absmax_finite, rt_lsqr_device.h)
+constexpr size_t kRedWords = 8;
+
+// The block's largest v (v >= 0, never NaN) into *slot, a double kept as its bits: non-negative doubles order as unsigned integers,
+// so one integer atomic max per block is the second stage of the reduction, and fmax is exact: the same bits in every schedule.
+// The slot starts from 0.  Blocks of 256 lanes.
+__device__ __forceinline__ void block_max_to(unsigned long long* slot, double v) {
+    __shared__ double wmax[4];
+    for (int off = 1; off < 64; off <<= 1) v = fmax(v, __shfl_xor(v, off));
+    const int tid = (int)threadIdx.x;
+    if ((tid & 63) == 0) wmax[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0) {
+        const double m = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+        if (m > 0.0) atomicMax(slot, (unsigned long long)__double_as_longlong(m));
+    }
+}
+
+// `bytes` at p are memory of `device`, a handle's (hipPointerGetAttributes), and the allocation holds them all
+int check_device_pointer(int device, const char* who, const void* p, size_t bytes, const char* name) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();             // a plain host pointer: not an error of the runtime's to keep
+    const bool ok = e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == device;
+    RTMI_ARG(ok, std::string(name) + " is not memory of the handle's device");
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        RTMI_ARG(false, std::string(name) + ": the extent of its allocation could not be read");
+    }
+    RTMI_ARG((const char*)p + bytes <= (const char*)base + size, std::string(name) + " is shorter than the call needs");
+    return RTMI_OK;
+}
 
 // slot[o] = the slot of the caller's ray o: the inverse of rtmi_device_view.perm.  A template, so that only the units that launch
 // it carry the kernel.

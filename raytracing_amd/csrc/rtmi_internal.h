@@ -1,5 +1,6 @@
 // rtmi_internal.h -- hooks between the translation units of librtmi.so (not part of the C ABI, hidden visibility).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/rtmi.h"
@@ -42,3 +43,7 @@ int rtmi_internal_paraxial_rows(const char* who, rtmi_batch* b, double* row_J, i
 int rtmi_internal_paraxial_tube(const char* who, rtmi_batch* b, double* row_tube);
 // A batch's launch angles theta0 [R] in the caller's ray order, copied to a host buffer.
 int rtmi_internal_batch_theta0(rtmi_batch* b, double* theta0);
+// kirchhoff.hip: max |x_i| over the finite values of n doubles on the device (0 when there is none): k_absmax_finite and an 8-byte
+// read-back.  red: a device word for the result (a handle's); cus: the device's compute units.  For every unit that scales a
+// fixed-point sum by an order-independent maximum.
+int rtmi_internal_absmax_finite(const char* who, unsigned long long* red, int cus, const double* d_x, size_t n, double* out);

@@ -1,0 +1,700 @@
+// tomo.hip -- recorded rays compiled into a sparse ray-tomography matrix that lives on the device (rtmi_tomo_create, _append,
+// _read, _info, _apply, _transpose, their _dev forms, rtmi_tomo_lsqr, _destroy).  include/rtmi.h states the contract; DESIGN.md
+// section 24 the definitions, the error bound and what was measured.
+//
+// A row of the matrix is one reported traveltime's derivative with respect to the field's samples; it is a list of segments, one
+// per cell visit of its ray: the cell's first sample `base` and four weights p[q].  rtmi_tomo_append walks a batch's rows with
+// walk_weighted (rt_sens_walk.h), the walk of rtmi_traveltime_backproject with weight 1 on the one observation, twice: a count pass
+// (the rows' lengths), a scan on the host over the lengths (rt_tomo.h: the slices' offsets), and a fill pass.  The batch is not
+// needed afterwards.  Storage is sliced by 64 rows (rt_tomo.h), so that the products run one lane per row with coalesced loads:
+//   k_tomo_apply      y_r = sum over the row's segments, in visit order, of ((p0 x0 + p1 x1) + p2 x2) + p3 x3, x gathered from the
+//                     4 samples of the segment's cell; one fixed order, no atomics.
+//   k_tomo_transpose  every product p_q w_r is rounded once to a fixed-point integer (quantum from Vmax max|w|, an order-independent
+//                     bound), the lanes of a wave whose next segments lie in the same cell add as one (the lane
+//                     furthest behind names the cell, so that neighbouring rays stay together although their segment indices
+//                     drift apart), and the sums go into two integer words per sample with adds that return nothing (add_split),
+//                     read as one integer and rounded once (rt_fix128.h): the same bits in every schedule and order of appends.
+// rtmi_tomo_lsqr runs the loop of rt_lsqr_device.h over the pair, stacked with the first-difference rows of the smoothing terms.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "rt_fix128.h"
+#include "rt_lsqr_device.h"
+#include "rt_sens_walk.h"
+#include "rt_tomo.h"
+#include "rtmi_host.h"
+
+static_assert(rt::kTomoSlice == 64, "a slice is a wave");
+
+// The transposed product's accumulators exist this many times; a block of rows adds into copy (block index mod kTomoCopies), and the
+// copies' integers are summed before the one rounding.  Rays of one source share their first cells: the copies spread the adds to
+// those few addresses.
+constexpr int kTomoCopies = 8;
+
+// One append's rows
+struct TomoBlock {
+    int64_t first = 0, rows = 0, segments = 0, padded = 0;
+    int32_t* len = nullptr;       // [rows]
+    int64_t* off = nullptr;       // [slices + 1]
+    int32_t* base = nullptr;      // [padded]
+    double* val = nullptr;        // [4 padded]
+    void release() {
+        for (void* p : {(void*)len, (void*)off, (void*)base, (void*)val})
+            if (p) (void)hipFree(p);
+        len = nullptr; off = nullptr; base = nullptr; val = nullptr;
+    }
+    size_t bytes() const {
+        return (size_t)rows * sizeof(int32_t) + (size_t)(rt::tomo_slices(rows) + 1) * sizeof(int64_t) + (size_t)padded * (sizeof(int32_t) + 4 * sizeof(double));
+    }
+};
+
+struct rtmi_tomo {
+    int device = 0, cus = 1;
+    Axes F{};
+    std::vector<TomoBlock> blocks;
+    int64_t rows = 0, segments = 0, padded = 0;
+    double vmax = 0.0, compile_ms = 0.0;
+    unsigned long long* acc = nullptr;        // [kTomoCopies] x (A [nz], B [nz]): the transposed product's split accumulators (add_split)
+    unsigned long long* red = nullptr;        // kRedWords reduction words (rt_lsqr_device.h: [0] .. [3]); [4] a fill pass's max |p|, [5] atomics
+    hipEvent_t ev[2] = {};
+    size_t nz() const { return (size_t)F.qx * (size_t)F.qy; }
+    size_t bytes() const {
+        size_t b = ((size_t)kTomoCopies * 2 * nz() + kRedWords) * sizeof(unsigned long long);
+        for (const TomoBlock& k : blocks) b += k.bytes();
+        return b;
+    }
+    ~rtmi_tomo() {
+        for (TomoBlock& b : blocks) b.release();
+        if (acc) (void)hipFree(acc);
+        if (red) (void)hipFree(red);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------------------ compile
+// walk_weighted's sinks.  Both end a ray observed at a crossing with that crossing's step: later rows carry no weight.
+struct CountSink {
+    static constexpr bool kStopAtLast = true;
+    int n;
+    __device__ __forceinline__ void flush(bool go, int, int, const double (&)[4]) { n += go ? 1 : 0; }
+};
+struct FillSink {
+    static constexpr bool kStopAtLast = true;
+    int32_t* base;
+    double* val;
+    int64_t off;                  // the slice's offset
+    int lane, qx, k, cap;         // cap: the row's length from the count pass: nothing is written past it
+    double vmax;
+    __device__ __forceinline__ void flush(bool go, int cx, int cy, const double (&p)[4]) {
+        if (go && k < cap) {
+            base[rt::tomo_slot(off, k, lane)] = cy * qx + cx;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                val[rt::tomo_value(off, k, q, lane)] = p[q];
+                vmax = fmax(vmax, fabs(p[q]));
+            }
+            k++;
+        }
+    }
+};
+
+// One lane per ray.  which [R] (the caller's ray order; NULL: every ray's end), rowof [R]: the ray's row in the block, -1 skipped.
+// FILL false: len[row] = the row's segments.  FILL true: the segments into the block's storage, and max |p| into *vmax.
+template <typename T, bool FILL>
+__global__ void __launch_bounds__(256) k_tomo_walk(Rows<T> rec, Args A, const int32_t* __restrict__ which, const int32_t* __restrict__ rowof,
+                                                   int32_t* __restrict__ len, const int64_t* __restrict__ off, int32_t* __restrict__ base,
+                                                   double* __restrict__ val, unsigned long long* __restrict__ vmax) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = k < rec.R;
+    const long o = in ? rec.caller(k) : 0;
+    const long row = in ? (long)rowof[o] : -1;
+    long last = (in && row >= 0) ? rec.last(k) : -1;
+    if (last >= rec.rec_rows) last = -1;                      // past the record: an empty row
+    const int wh = (in && which) ? which[o] : -1;
+    const bool line = A.has_line && wh >= 0;
+    int K = 0;
+    double we = 0.0;
+    if (last >= 0) {
+        if (wh < 0) {
+            we = 1.0;
+        } else if (wh < min(count_crossings(rec, k, last, A.L), A.kmax)) {
+            K = wh + 1;                                       // crossings 0 .. wh matter to the walk; wh carries the weight
+        } else {
+            last = -1;                                        // no such crossing: an empty row
+        }
+    }
+    auto wc = [&](int c) { return c == wh ? 1.0 : 0.0; };
+    if (!FILL) {
+        CountSink sink{0};
+        walk_weighted(rec, A, in ? k : 0, last, line, K, we, wc, sink);
+        if (row >= 0) len[row] = sink.n;
+    } else {
+        FillSink sink{base, val, row >= 0 ? off[row >> 6] : 0, (int)(row & 63), A.F.qx, 0, row >= 0 ? len[row] : 0, 0.0};
+        walk_weighted(rec, A, in ? k : 0, last, line, K, we, wc, sink);
+        block_max_to(vmax, sink.vmax);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ products
+// One lane per row of a block: y[r] for r < rows.
+__global__ void __launch_bounds__(256) k_tomo_apply(const int32_t* __restrict__ len, const int64_t* __restrict__ off, const int32_t* __restrict__ base,
+                                                    const double* __restrict__ val, long rows, int qx, const double* __restrict__ x,
+                                                    double* __restrict__ y) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int lane = (int)(r & 63);
+    const int64_t o = off[r >> 6];
+    const int n = len[r];
+    double acc = 0.0;
+    for (int k = 0; k < n; k++) {
+        const double* z = x + base[rt::tomo_slot(o, k, lane)];
+        const double p0 = val[rt::tomo_value(o, k, 0, lane)], p1 = val[rt::tomo_value(o, k, 1, lane)];
+        const double p2 = val[rt::tomo_value(o, k, 2, lane)], p3 = val[rt::tomo_value(o, k, 3, lane)];
+        const double t = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p0, z[0]), __dmul_rn(p1, z[1])), __dmul_rn(p2, z[qx])), __dmul_rn(p3, z[qx + 1]));
+        acc = __dadd_rn(acc, t);
+    }
+    y[r] = acc;
+}
+
+// s quanta into sample i of the split accumulators: the low 32 bits of s into A[i], the rest (signed) into B[i], so that
+// s = B 2^32 + A holds for the sums as well.  Neither add returns a value, so the wave does not wait for memory; below 2^32 adds
+// per sample neither word can wrap.  Returns the atomics issued.
+__device__ __forceinline__ int add_split(unsigned long long* A, unsigned long long* B, size_t i, long long s) {
+    if (s == 0) return 0;
+    atomicAdd(A + i, (unsigned long long)s & 0xffffffffull);
+    const long long h = s >> 32;
+    if (h == 0) return 1;
+    atomicAdd(B + i, (unsigned long long)h);
+    return 2;
+}
+
+// One lane per row of a block, a wave per slice.  A weight that is not finite counts as 0.
+__global__ void __launch_bounds__(256) k_tomo_transpose(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                                        const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
+                                                        const double* __restrict__ w, int e, unsigned long long* acc, size_t nz,
+                                                        unsigned long long* natomics) {
+    unsigned long long* const A = acc + (size_t)(blockIdx.x % kTomoCopies) * 2 * nz;
+    unsigned long long* const B = A + nz;
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool in = r < rows;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t o = in ? off[r >> 6] : 0;
+    const double wr = in ? w[r] : 0.0;
+    const int n = (in && fabs(wr) < INFINITY && wr != 0.0) ? len[r] : 0;
+    long long nat = 0;
+    // Neighbouring rays visit much the same cells, but not at the same segment index: a ray that clips a corner has one visit more.
+    // So the lanes do not step through k together.  Each holds its next segment; the lane that is furthest behind names a cell,
+    // every lane whose next segment is that cell joins its add and moves on, the others wait.  Which lanes add together changes no
+    // bit: the sums are integers.  The segment after the next is loaded a step ahead.
+    int k = 0, b = 0, nb = 0;
+    long long m[4] = {0, 0, 0, 0};
+    double np[4] = {0.0, 0.0, 0.0, 0.0};
+    auto load = [&](int kk) {                                 // segment kk into (nb, np)
+        if (kk < n) {
+            nb = base[rt::tomo_slot(o, kk, lane)];
+#pragma unroll
+            for (int q = 0; q < 4; q++) np[q] = val[rt::tomo_value(o, kk, q, lane)];
+        }
+    };
+    auto take = [&]() {                                       // (nb, np) becomes the lane's next segment
+        b = nb;
+#pragma unroll
+        for (int q = 0; q < 4; q++) m[q] = (long long)rint(ldexp(__dmul_rn(np[q], wr), -e));
+    };
+    load(0);
+    take();
+    load(1);
+    for (;;) {
+        const bool pend = k < n;
+        if (__ballot(pend) == 0ull) break;
+        int kmin = pend ? k : INT32_MAX;
+        for (int s = 1; s < 64; s <<= 1) kmin = min(kmin, __shfl_xor(kmin, s));
+        const int leader = __ffsll((long long)__ballot(pend && k == kmin)) - 1;
+        const int lb = __shfl(b, leader);
+        const bool mem = pend && b == lb;
+        long long v[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = mem ? m[q] : 0;
+        if (__popcll(__ballot(mem)) > 1) {
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1)
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] += __shfl_xor(v[q], s);
+        }
+        if (lane == leader) {
+            nat += add_split(A, B, (size_t)lb, v[0]);
+            nat += add_split(A, B, (size_t)lb + 1, v[1]);
+            nat += add_split(A, B, (size_t)lb + qx, v[2]);
+            nat += add_split(A, B, (size_t)lb + qx + 1, v[3]);
+        }
+        if (mem) {
+            k++;
+            take();
+            load(k + 1);
+        }
+    }
+    for (int s = 1; s < 64; s <<= 1) nat += __shfl_xor(nat, s);
+    if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
+}
+
+// The smoothing rows: ux [qy][qx - 1] = fl(lx fl(x[i][j + 1] - x[i][j])), uy [qy - 1][qx] = fl(ly fl(x[i + 1][j] - x[i][j]))
+__global__ void __launch_bounds__(256) k_tomo_diff(const double* __restrict__ x, int qx, int qy, double lx, double ly, double* __restrict__ ux,
+                                                   double* __restrict__ uy) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)qx * qy) return;
+    const int iy = (int)(i / qx), jx = (int)(i % qx);
+    const double c = x[i];
+    if (jx < qx - 1) ux[(size_t)iy * (qx - 1) + jx] = __dmul_rn(lx, __dadd_rn(x[i + 1], -c));
+    if (iy < qy - 1) uy[i] = __dmul_rn(ly, __dadd_rn(x[i + qx], -c));
+}
+
+// g = the accumulators, each sample's integer B 2^32 + A rounded once to fp64 (zero: +0.0 instead), plus, with ux, the transposed smoothing rows:
+// g = fl(gA + fl(r + s)), r = fl(lx fl(ux[i][j - 1] - ux[i][j])), s = fl(ly fl(uy[i - 1][j] - uy[i][j])), a missing neighbour +0.0
+__global__ void __launch_bounds__(256) k_tomo_finish(const unsigned long long* __restrict__ acc, int e,
+                                                     bool zero, int qx, int qy, const double* __restrict__ ux, const double* __restrict__ uy,
+                                                     double lx, double ly, double* __restrict__ g) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)qx * qy) return;
+    double v = 0.0;
+    if (!zero) {
+        // B 2^32 + A as the two words of rt_fix128.h (the low one biased), then its one rounding
+        const size_t nz = (size_t)qx * qy;
+        unsigned long long a = 0ull, bb = 0ull;                               // the copies' sums: below 2^32 adds in all, neither wraps
+        for (int c = 0; c < kTomoCopies; c++) {
+            a += acc[(size_t)c * 2 * nz + i];
+            bb += acc[(size_t)c * 2 * nz + nz + i];
+        }
+        unsigned long long lo = (bb << 32) + a;
+        unsigned long long hi = (unsigned long long)((long long)bb >> 32) + (lo < a ? 1ull : 0ull);
+        const unsigned long long lo2 = lo + rt::kFixBias;
+        hi += lo2 < lo ? 1ull : 0ull;
+        v = ldexp(rt::fix_to_double(lo2, hi), e);
+    }
+    if (ux) {
+        const int iy = (int)(i / qx), jx = (int)(i % qx);
+        const double xa = jx > 0 ? ux[(size_t)iy * (qx - 1) + jx - 1] : 0.0, xb = jx < qx - 1 ? ux[(size_t)iy * (qx - 1) + jx] : 0.0;
+        const double ya = iy > 0 ? uy[i - qx] : 0.0, yb = iy < qy - 1 ? uy[i] : 0.0;
+        const double r = __dmul_rn(lx, __dadd_rn(xa, -xb)), s = __dmul_rn(ly, __dadd_rn(ya, -yb));
+        v = __dadd_rn(v, __dadd_rn(r, s));
+    }
+    g[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host
+int on_device(const rtmi_tomo* t, const char* who) {
+    int dev = -1;
+    RTMI_HIP(hipGetDevice(&dev));
+    RTMI_ARG(dev == t->device, "the calling thread's current device is not the handle's");
+    return RTMI_OK;
+}
+
+void fill_stats(const rtmi_tomo* t, rtmi_tomo_stats* st) {
+    *st = rtmi_tomo_stats{};
+    st->rows = t->rows; st->segments = t->segments; st->padded_segments = t->padded;
+    st->bytes_device = (int64_t)t->bytes();
+    st->compile_ms = t->compile_ms;
+    st->vmax = t->vmax;
+    st->qx = t->F.qx; st->qy = t->F.qy;
+}
+
+// y [rows] = A x on device pointers; the callers have checked them.  ms: the kernels' event time, waited for.
+int apply_dev(rtmi_tomo* t, const char* who, const double* d_x, double* d_y, double* ms) {
+    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
+    for (const TomoBlock& b : t->blocks) {
+        hipLaunchKernelGGL(k_tomo_apply, blocks((long)b.rows), dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows, t->F.qx, d_x,
+                           d_y + b.first);
+        RTMI_HIP(hipGetLastError());
+    }
+    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
+    RTMI_HIP(hipEventSynchronize(t->ev[1]));
+    float f = 0.0f;
+    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
+    *ms = f;
+    return RTMI_OK;
+}
+
+// g [qy][qx] = A^T w (w [rows]) on device pointers, plus the transposed smoothing rows when ux is given.  *range: fl(Vmax max|w|)
+// is not a normal number, and nothing was written.
+int transpose_dev(rtmi_tomo* t, const char* who, const double* d_w, double* d_g, const double* ux, const double* uy, double lx, double ly,
+                  bool* range, double* ms, int64_t* atomics, int32_t* scale_exp) {
+    *range = false;
+    *ms = 0.0;
+    *atomics = 0;
+    *scale_exp = 0;
+    const size_t nz = t->nz();
+    double W = 0.0;
+    if (t->rows > 0 && t->segments > 0 && t->vmax > 0.0) RTMI_RC(rtmi_internal_absmax_finite(who, t->red, t->cus, d_w, (size_t)t->rows, &W));
+    const bool zero = !(W > 0.0);
+    int e = 0;
+    if (!zero) {
+        const double bound = t->vmax * W;
+        if (!std::isnormal(bound)) {
+            *range = true;
+            return RTMI_OK;
+        }
+        e = rt::fix_exponent(bound);
+    }
+    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
+    if (!zero) {
+        RTMI_HIP(hipMemsetAsync(t->acc, 0, (size_t)kTomoCopies * 2 * nz * sizeof(unsigned long long), nullptr));
+        RTMI_HIP(hipMemsetAsync(t->red + 5, 0, sizeof(unsigned long long), nullptr));
+        for (const TomoBlock& b : t->blocks) {
+            hipLaunchKernelGGL(k_tomo_transpose, blocks((long)b.rows), dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows, t->F.qx,
+                               d_w + b.first, e, t->acc, nz, t->red + 5);
+            RTMI_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_tomo_finish, blocks((long)nz), dim3(256), 0, nullptr, t->acc, e, zero, t->F.qx, t->F.qy, ux, uy, lx, ly, d_g);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
+    RTMI_HIP(hipEventSynchronize(t->ev[1]));
+    float f = 0.0f;
+    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
+    *ms = f;
+    if (!zero) {
+        unsigned long long n = 0;
+        RTMI_HIP(hipMemcpy(&n, t->red + 5, sizeof(n), hipMemcpyDeviceToHost));
+        *atomics = (int64_t)n;
+        *scale_exp = e;
+    }
+    return RTMI_OK;
+}
+
+int finite_all(const char* who, const double* p, size_t n, const char* msg) {
+    for (size_t i = 0; i < n; i++) RTMI_ARG(std::isfinite(p[i]), msg);
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_tomo_create(const rtmi_field* f, rtmi_tomo** out) {
+    const char* who = "rtmi_tomo_create";
+    RTMI_ARG(f, "null field");
+    RTMI_ARG(out, "null out");
+    rtmi_internal_poly poly;
+    RTMI_RC(rtmi_internal_field_poly(f, &poly));              // RTMI_ERR_ARG unless the current device is the field's
+    int qx = 0, qy = 0;
+    RTMI_RC(rtmi_field_dims(f, &qx, &qy));
+    RTMI_ARG(qx >= 2 && qy >= 2, "the field needs at least 2 samples per axis");
+    rtmi_tomo* t = new (std::nothrow) rtmi_tomo;
+    if (!t) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_tomo_create: out of host memory");
+    t->F = Axes{poly.ax, poly.bx, poly.inv_hx, poly.ay, poly.by, poly.inv_hy, qx, qy};
+    auto fail = [&](int code, const char* what, hipError_t e) {
+        delete t;
+        return rtmi_internal_fail(code, (std::string(who) + ": " + what + ": " + hipGetErrorString(e)).c_str());
+    };
+    hipError_t e = hipGetDevice(&t->device);
+    if (e != hipSuccess) return fail(RTMI_ERR_HIP, "hipGetDevice", e);
+    e = hipDeviceGetAttribute(&t->cus, hipDeviceAttributeMultiprocessorCount, t->device);
+    if (e != hipSuccess || t->cus < 1) return fail(RTMI_ERR_HIP, "hipDeviceGetAttribute", e);
+    e = hipMalloc((void**)&t->acc, (size_t)kTomoCopies * 2 * t->nz() * sizeof(unsigned long long));
+    if (e != hipSuccess) return fail(RTMI_ERR_ALLOC, "hipMalloc", e);
+    e = hipMalloc((void**)&t->red, kRedWords * sizeof(unsigned long long));
+    if (e != hipSuccess) return fail(RTMI_ERR_ALLOC, "hipMalloc", e);
+    for (hipEvent_t& v : t->ev) {
+        e = hipEventCreate(&v);
+        if (e != hipSuccess) return fail(RTMI_ERR_HIP, "hipEventCreate", e);
+    }
+    *out = t;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT void rtmi_tomo_destroy(rtmi_tomo* t) { delete t; }
+
+RTMI_EXPORT int rtmi_tomo_append(rtmi_tomo* t, rtmi_batch* b, const double line[3], int32_t kmax, const int32_t* which, int32_t* nseg,
+                                 int64_t* first_row) {
+    const char* who = "rtmi_tomo_append";
+    RTMI_ARG(t, "null handle");
+    RTMI_RC(check_line(line, kmax, who));
+    RTMI_ARG(b, "null batch");
+    int64_t R64 = 0;
+    RTMI_RC(rtmi_internal_batch_rays(b, &R64));
+    const size_t R = (size_t)R64;
+    if (which) {
+        const int32_t top = line ? kmax - 1 : -1;
+        for (size_t m = 0; m < R; m++) {
+            RTMI_ARG(which[m] >= RTMI_TOMO_SKIP, "which has a value below RTMI_TOMO_SKIP (-2)");
+            RTMI_ARG(line || which[m] < 0, "which names a crossing, which needs a line");
+            RTMI_ARG(which[m] <= top, "which has a value above kmax - 1");
+        }
+    }
+    Args A;
+    rtmi_device_view v;
+    RTMI_RC(prepare(b, which ? line : nullptr, kmax, who, &A, &v));
+    RTMI_RC(on_device(t, who));
+    const Axes& F = t->F;
+    RTMI_ARG(A.F.qx == F.qx && A.F.qy == F.qy && A.F.ax == F.ax && A.F.bx == F.bx && A.F.inv_hx == F.inv_hx && A.F.ay == F.ay &&
+                 A.F.by == F.by && A.F.inv_hy == F.inv_hy,
+             "the batch's field has other sample axes than the handle's");
+    RTMI_ARG((size_t)v.R == R, "the batch's view disagrees with its ray count");
+    // rows in the caller's ray order
+    std::vector<int32_t> rowof(R);
+    int64_t rows = 0;
+    for (size_t m = 0; m < R; m++) rowof[m] = (which && which[m] == RTMI_TOMO_SKIP) ? -1 : (int32_t)rows++;
+    if (first_row) *first_row = t->rows;
+    if (rows == 0) {
+        if (nseg)
+            for (size_t m = 0; m < R; m++) nseg[m] = -1;
+        t->compile_ms = 0.0;
+        return RTMI_OK;
+    }
+    TomoBlock blk;
+    blk.first = t->rows;
+    blk.rows = rows;
+    struct Guard {
+        TomoBlock* b;
+        ~Guard() { if (b) b->release(); }
+    } guard{&blk};
+    DevMem mem;
+    int32_t *d_which = nullptr, *d_rowof = nullptr;
+    RTMI_HIP(mem.get(&d_rowof, R * sizeof(int32_t)));
+    RTMI_HIP(hipMemcpy(d_rowof, rowof.data(), R * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (which) {
+        RTMI_HIP(mem.get(&d_which, R * sizeof(int32_t)));
+        RTMI_HIP(hipMemcpy(d_which, which, R * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    const int64_t ns = rt::tomo_slices(rows);
+    auto get = [&](void** p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 8) == hipSuccess; };
+    const char* no_mem = "rtmi_tomo_append: hipMalloc failed";
+    if (!get((void**)&blk.len, (size_t)rows * sizeof(int32_t)) || !get((void**)&blk.off, (size_t)(ns + 1) * sizeof(int64_t)))
+        return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem);
+    RTMI_HIP(hipMemset(blk.len, 0, (size_t)rows * sizeof(int32_t)));
+    const dim3 gr = blocks((long)R), bs(256);
+    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
+    by_dtype(v.dtype, [&](auto q) {
+        hipLaunchKernelGGL((k_tomo_walk<decltype(q), false>), gr, bs, 0, nullptr, rows_of<decltype(q)>(v), A, d_which, d_rowof, blk.len, nullptr,
+                           nullptr, nullptr, nullptr);
+    });
+    RTMI_HIP(hipGetLastError());
+    std::vector<int32_t> len((size_t)rows);
+    std::vector<int64_t> off((size_t)ns + 1);
+    RTMI_HIP(hipMemcpy(len.data(), blk.len, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    blk.segments = rt::tomo_offsets(len.data(), rows, off.data());
+    blk.padded = off[(size_t)ns];
+    if (!get((void**)&blk.base, (size_t)blk.padded * sizeof(int32_t)) || !get((void**)&blk.val, (size_t)blk.padded * 4 * sizeof(double)))
+        return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem);
+    RTMI_HIP(hipMemcpy(blk.off, off.data(), (size_t)(ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemsetAsync(blk.base, 0, (size_t)blk.padded * sizeof(int32_t), nullptr));
+    RTMI_HIP(hipMemsetAsync(blk.val, 0, (size_t)blk.padded * 4 * sizeof(double), nullptr));
+    RTMI_HIP(hipMemsetAsync(t->red + 4, 0, sizeof(unsigned long long), nullptr));
+    by_dtype(v.dtype, [&](auto q) {
+        hipLaunchKernelGGL((k_tomo_walk<decltype(q), true>), gr, bs, 0, nullptr, rows_of<decltype(q)>(v), A, d_which, d_rowof, blk.len, blk.off,
+                           blk.base, blk.val, t->red + 4);
+    });
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
+    RTMI_HIP(hipEventSynchronize(t->ev[1]));
+    float ms = 0.0f;
+    RTMI_HIP(hipEventElapsedTime(&ms, t->ev[0], t->ev[1]));
+    double vmax = 0.0;
+    RTMI_HIP(hipMemcpy(&vmax, t->red + 4, sizeof(double), hipMemcpyDeviceToHost));
+    if (nseg)
+        for (size_t m = 0; m < R; m++) nseg[m] = rowof[m] < 0 ? -1 : len[(size_t)rowof[m]];
+    t->blocks.push_back(blk);
+    guard.b = nullptr;
+    t->rows += rows;
+    t->segments += blk.segments;
+    t->padded += blk.padded;
+    t->vmax = std::fmax(t->vmax, vmax);
+    t->compile_ms = ms;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_info(const rtmi_tomo* t, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_info";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(st, "null stats");
+    fill_stats(t, st);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_read(const rtmi_tomo* t, int64_t* row_ptr, int32_t* base, double* val) {
+    const char* who = "rtmi_tomo_read";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(row_ptr || (!base && !val), "base and val need row_ptr");
+    if (!row_ptr) return RTMI_OK;
+    RTMI_RC(on_device(t, who));
+    int64_t at = 0;
+    row_ptr[0] = 0;
+    for (const TomoBlock& b : t->blocks) {
+        const int64_t ns = rt::tomo_slices(b.rows);
+        std::vector<int32_t> len((size_t)b.rows), hb;
+        std::vector<int64_t> off((size_t)ns + 1);
+        std::vector<double> hv;
+        RTMI_HIP(hipMemcpy(len.data(), b.len, (size_t)b.rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+        RTMI_HIP(hipMemcpy(off.data(), b.off, (size_t)(ns + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (base) {
+            hb.resize((size_t)b.padded);
+            RTMI_HIP(hipMemcpy(hb.data(), b.base, (size_t)b.padded * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        if (val) {
+            hv.resize((size_t)b.padded * 4);
+            RTMI_HIP(hipMemcpy(hv.data(), b.val, (size_t)b.padded * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        for (int64_t r = 0; r < b.rows; r++) {
+            const int64_t o = off[(size_t)(r >> 6)];
+            const int lane = (int)(r & 63);
+            for (int32_t k = 0; k < len[(size_t)r]; k++, at++) {
+                if (base) base[at] = hb[(size_t)rt::tomo_slot(o, k, lane)];
+                if (val)
+                    for (int q = 0; q < 4; q++) val[4 * at + q] = hv[(size_t)rt::tomo_value(o, k, q, lane)];
+            }
+            row_ptr[b.first + r + 1] = at;
+        }
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_apply_dev(rtmi_tomo* t, const double* d_x, double* d_y, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_apply_dev";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(d_x, "null d_x");
+    RTMI_ARG(d_y || t->rows == 0, "null d_y");
+    RTMI_RC(on_device(t, who));
+    RTMI_RC(check_device_pointer(t->device, who, d_x, t->nz() * sizeof(double), "d_x"));
+    if (t->rows) RTMI_RC(check_device_pointer(t->device, who, d_y, (size_t)t->rows * sizeof(double), "d_y"));
+    double ms = 0.0;
+    RTMI_RC(apply_dev(t, who, d_x, d_y, &ms));
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_apply(rtmi_tomo* t, const double* x, double* y, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_apply";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(x, "null x");
+    RTMI_ARG(y || t->rows == 0, "null y");
+    RTMI_RC(finite_all(who, x, t->nz(), "x has a value that is not finite"));
+    RTMI_RC(on_device(t, who));
+    DevMem mem;
+    double *dx = nullptr, *dy = nullptr;
+    RTMI_HIP(mem.get(&dx, t->nz() * sizeof(double)));
+    RTMI_HIP(mem.get(&dy, (size_t)t->rows * sizeof(double)));
+    RTMI_HIP(hipMemcpy(dx, x, t->nz() * sizeof(double), hipMemcpyHostToDevice));
+    double ms = 0.0;
+    RTMI_RC(apply_dev(t, who, dx, dy, &ms));
+    if (t->rows) RTMI_HIP(hipMemcpy(y, dy, (size_t)t->rows * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_transpose_dev(rtmi_tomo* t, const double* d_w, double* d_g, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_transpose_dev";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(d_w || t->rows == 0, "null d_w");
+    RTMI_ARG(d_g, "null d_g");
+    RTMI_RC(on_device(t, who));
+    if (t->rows) RTMI_RC(check_device_pointer(t->device, who, d_w, (size_t)t->rows * sizeof(double), "d_w"));
+    RTMI_RC(check_device_pointer(t->device, who, d_g, t->nz() * sizeof(double), "d_g"));
+    bool range = false;
+    double ms = 0.0;
+    int64_t atomics = 0;
+    int32_t e = 0;
+    RTMI_RC(transpose_dev(t, who, d_w, d_g, nullptr, nullptr, 0.0, 0.0, &range, &ms, &atomics, &e));
+    RTMI_ARG(!range, "Vmax max|w| is not a normal number (RTMI_LSQR_RANGE)");
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms; st->atomics = atomics; st->scale_exp = e;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_transpose(rtmi_tomo* t, const double* w, double* g, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_transpose";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(w || t->rows == 0, "null w");
+    RTMI_ARG(g, "null g");
+    RTMI_RC(finite_all(who, w, (size_t)t->rows, "w has a value that is not finite"));
+    RTMI_RC(on_device(t, who));
+    DevMem mem;
+    double *dw = nullptr, *dg = nullptr;
+    RTMI_HIP(mem.get(&dw, (size_t)t->rows * sizeof(double)));
+    RTMI_HIP(mem.get(&dg, t->nz() * sizeof(double)));
+    if (t->rows) RTMI_HIP(hipMemcpy(dw, w, (size_t)t->rows * sizeof(double), hipMemcpyHostToDevice));
+    bool range = false;
+    double ms = 0.0;
+    int64_t atomics = 0;
+    int32_t e = 0;
+    RTMI_RC(transpose_dev(t, who, dw, dg, nullptr, nullptr, 0.0, 0.0, &range, &ms, &atomics, &e));
+    RTMI_ARG(!range, "Vmax max|w| is not a normal number (RTMI_LSQR_RANGE)");
+    RTMI_HIP(hipMemcpy(g, dg, t->nz() * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms; st->atomics = atomics; st->scale_exp = e;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const double smooth[2], const double* rhs, double* x,
+                               double* history, rtmi_lsqr_stats* st) {
+    const char* who = "rtmi_tomo_lsqr";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(lp, "null params");
+    RTMI_ARG(rhs, "null rhs");
+    RTMI_ARG(x, "null x");
+    RTMI_RC(lsqr_check_params(who, lp));
+    if (smooth)
+        RTMI_ARG(std::isfinite(smooth[0]) && smooth[0] >= 0.0 && std::isfinite(smooth[1]) && smooth[1] >= 0.0,
+                 "smooth must be finite and >= 0");
+    RTMI_ARG(t->rows >= 1, "the handle has no rows");
+    RTMI_RC(finite_all(who, rhs, (size_t)t->rows, "rhs has a value that is not finite"));
+    RTMI_RC(on_device(t, who));
+    const double t_begin = now_ms();
+    const size_t rows = (size_t)t->rows, nm = t->nz(), qx = (size_t)t->F.qx, qy = (size_t)t->F.qy;
+    const size_t ndx = qy * (qx - 1), ndy = (qy - 1) * qx;
+    const size_t per = rows + (smooth ? ndx + ndy : 0);
+    const double lx = smooth ? smooth[0] : 0.0, ly = smooth ? smooth[1] : 0.0;
+    DevMem mem;
+    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr;
+    for (double** p : {&u, &Av})
+        if (mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_tomo_lsqr: hipMalloc failed");
+    for (double** p : {&v, &w, &xd, &Atu})
+        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_tomo_lsqr: hipMalloc failed");
+    const Vec V{t->red, t->cus};
+    rtmi_lsqr_stats out{};
+    out.bytes_device = (int64_t)((2 * per + 4 * nm) * sizeof(double) + t->bytes());
+    double operator_ms = 0.0;
+    // the stacked operator: t = [A s | Dx s | Dy s], and its transpose
+    auto Ax = [&](const double* s, double* y) {
+        double ms = 0.0;
+        RTMI_RC(apply_dev(t, who, s, y, &ms));
+        operator_ms += ms;
+        if (smooth) {
+            hipLaunchKernelGGL(k_tomo_diff, blocks((long)nm), dim3(256), 0, nullptr, s, (int)qx, (int)qy, lx, ly, y + rows, y + rows + ndx);
+            RTMI_HIP(hipGetLastError());
+        }
+        return (int)RTMI_OK;
+    };
+    auto At = [&](const double* s, double* g, bool* range) {
+        double ms = 0.0;
+        int64_t atomics = 0;
+        int32_t e = 0;
+        RTMI_RC(transpose_dev(t, who, s, g, smooth ? s + rows : nullptr, smooth ? s + rows + ndx : nullptr, lx, ly, range, &ms, &atomics, &e));
+        operator_ms += ms;
+        return (int)RTMI_OK;
+    };
+    RTMI_HIP(hipMemcpy(u, rhs, rows * sizeof(double), hipMemcpyHostToDevice));        // the right-hand side goes up once
+    if (per > rows) RTMI_HIP(hipMemsetAsync(u + rows, 0, (per - rows) * sizeof(double), nullptr));
+    RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
+    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out));
+    RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));           // the model comes down once
+    out.total_ms = now_ms() - t_begin;
+    out.operator_ms = operator_ms;
+    if (st) *st = out;
+    return RTMI_OK;
+}

@@ -861,6 +861,187 @@ class TravelTimeSensitivity:
             pass
 
 
+def tomo_stats(st):
+    return {k: getattr(st, k) for k, _ in _lib.TomoStats._fields_ if not k.startswith("reserved")}
+
+
+class Tomography:
+    """Recorded rays compiled into a sparse ray-tomography matrix on the device (rtmi_tomo_*): the Jacobian of reported
+    traveltimes with respect to the field's n samples Z [qy, qx], one row per observation.  The handle keeps the matrix, not the
+    record: after append the batch may be closed, so a joint inversion appends source after source.  shape = (rows, qy * qx)."""
+
+    def __init__(self, field):
+        self.qx, self.qy = field.qx, field.qy
+        self._h = None
+        h = C.c_void_p()
+        check(lib().rtmi_tomo_create(field._h, C.byref(h)))
+        self._h = h
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("Tomography: the handle is closed")
+        return self._h
+
+    @property
+    def shape(self):
+        return (self.info()["rows"], self.qy * self.qx)
+
+    def _append(self, batch_handle, R, which, line, kmax):
+        wh = None
+        if which is not None:
+            wh = np.ascontiguousarray(which, dtype=np.int32)
+            if wh.shape != (R,):
+                raise ValueError(f"which must have shape ({R},)")
+        ln = None
+        if line is not None:
+            ln = np.ascontiguousarray(line, dtype=np.float64)
+            if ln.shape != (3,):
+                raise ValueError("line must be (a, b, c)")
+        nseg = np.empty(R, dtype=np.int32)
+        first = C.c_int64()
+        check(lib().rtmi_tomo_append(self._open(), batch_handle, None if ln is None else dptr(ln), int(kmax) if ln is not None else 0,
+                                     None if wh is None else wh.ctypes.data_as(_lib._ip), nseg.ctypes.data_as(_lib._ip), C.byref(first)))
+        return int(first.value), nseg
+
+    def append(self, batch, which=None, line=None, kmax=4):
+        """One row per ray of `batch` (record_stride 1), in the caller's ray order: which [R] selects ray m's observation, -1 its
+        end, c >= 0 crossing c of line (a, b, c), _lib.TOMO_SKIP no row; None: every ray's end.  Returns (first_row, nseg [R]:
+        the row's segments, 0 for an empty row, -1 for a skipped ray).  The batch may be closed afterwards."""
+        return self._append(batch._h, batch.R, which, line, kmax)
+
+    def append_sensitivity(self, sens, rows=None):
+        """The arrivals of a TravelTimeSensitivity (two_point(..., sensitivity=True)) as rows, in its order; rows: only these
+        arrivals (indices into sens.index, ascending).  sens.close() is safe afterwards."""
+        if sens._rays == 0:
+            return self.info()["rows"], np.zeros(0, dtype=np.int32)
+        if not sens._h:
+            raise ValueError("Tomography.append_sensitivity: the sensitivity is closed")
+        which = np.asarray(sens._cross, dtype=np.int32)
+        if rows is not None:
+            keep = np.zeros(sens._rays, dtype=bool)
+            keep[np.asarray(rows, dtype=np.int64)] = True
+            which = np.where(keep, which, _lib.TOMO_SKIP).astype(np.int32)
+        return self._append(sens._h, sens._rays, which, sens.line, sens.kmax)
+
+    def info(self):
+        st = _lib.TomoStats()
+        check(lib().rtmi_tomo_info(self._open(), C.byref(st)))
+        return tomo_stats(st)
+
+    def matvec(self, x, stats=False):
+        """y [rows] = A x for x [qy, qx] (or flat), one fixed summation order"""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        if xx.size != self.qy * self.qx:
+            raise ValueError(f"Tomography.matvec: x must have {self.qy * self.qx} values")
+        y = np.empty(self.info()["rows"])
+        st = _lib.TomoStats()
+        check(lib().rtmi_tomo_apply(self._open(), dptr(xx), dptr(y), C.byref(st)))
+        return (y, tomo_stats(st)) if stats else y
+
+    def rmatvec(self, w, stats=False):
+        """g [qy, qx] = A^T w for w [rows]: the same bits in every schedule, order of appends and order of rays"""
+        ww = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if ww.size != self.info()["rows"]:
+            raise ValueError(f"Tomography.rmatvec: w must have {self.info()['rows']} values")
+        g = np.empty((self.qy, self.qx))
+        st = _lib.TomoStats()
+        check(lib().rtmi_tomo_transpose(self._open(), dptr(ww), dptr(g), C.byref(st)))
+        return (g, tomo_stats(st)) if stats else g
+
+    def _device_tensor(self, who, t, name):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"Tomography.{who}: {name} must be a torch tensor")
+        if t.dtype != torch.float64:
+            raise TypeError(f"Tomography.{who}: {name} must be float64")
+        if not t.is_contiguous():
+            raise ValueError(f"Tomography.{who}: {name} must be contiguous")
+        if not t.is_cuda:                              # which GPU it is on, and its length, the library checks
+            raise ValueError(f"Tomography.{who}: {name} must be a tensor on a GPU, not on the host")
+        return t
+
+    def matvec_device(self, x, out=None, stats=False):
+        """rtmi_tomo_apply_dev on torch tensors of the handle's device: x [qy, qx] -> y [rows] (out, if given)"""
+        import torch
+        self._device_tensor("matvec_device", x, "x")
+        y = torch.empty(self.info()["rows"], dtype=torch.float64, device=x.device) if out is None else self._device_tensor("matvec_device", out, "out")
+        st = _lib.TomoStats()
+        torch.cuda.synchronize(x.device)               # the library works on the null stream
+        check(lib().rtmi_tomo_apply_dev(self._open(), x.data_ptr(), y.data_ptr(), C.byref(st)))
+        return (y, tomo_stats(st)) if stats else y
+
+    def rmatvec_device(self, w, out=None, stats=False):
+        """rtmi_tomo_transpose_dev on torch tensors of the handle's device: w [rows] -> g [qy, qx] (out, if given)"""
+        import torch
+        self._device_tensor("rmatvec_device", w, "w")
+        g = torch.empty((self.qy, self.qx), dtype=torch.float64, device=w.device) if out is None else self._device_tensor("rmatvec_device", out, "out")
+        st = _lib.TomoStats()
+        torch.cuda.synchronize(w.device)
+        check(lib().rtmi_tomo_transpose_dev(self._open(), w.data_ptr(), g.data_ptr(), C.byref(st)))
+        return (g, tomo_stats(st)) if stats else g
+
+    def lsqr(self, rhs, damp=0.0, smooth=None, iter_lim=30, atol=0.0, btol=0.0, history=False, stats=False):
+        """rtmi_tomo_lsqr: min |A x - rhs|^2 + damp^2 |x|^2 + lx^2 |Dx x|^2 + ly^2 |Dy x|^2 from x = 0, smooth = (lx, ly) or None,
+        every vector on the device.  -> the dict of Kirchhoff.lsqr with x [qy, qx]."""
+        rr = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
+        if rr.size != self.info()["rows"]:
+            raise ValueError(f"Tomography.lsqr: rhs must have {self.info()['rows']} values")
+        iter_lim = int(iter_lim)
+        if iter_lim < 1:
+            raise ValueError("Tomography.lsqr: iter_lim must be >= 1")
+        lp = _lib.LsqrParams()
+        lp.iter_lim, lp.damp, lp.atol, lp.btol = iter_lim, float(damp), float(atol), float(btol)
+        sm = None if smooth is None else np.ascontiguousarray(smooth, dtype=np.float64)
+        if sm is not None and sm.shape != (2,):
+            raise ValueError("Tomography.lsqr: smooth must be (lx, ly)")
+        x = np.empty((self.qy, self.qx))
+        hist = np.zeros((iter_lim, 4)) if history else None
+        st = _lib.LsqrStats()
+        check(lib().rtmi_tomo_lsqr(self._open(), C.byref(lp), dptr(sm), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
+        out = {"x": x, "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm, "anorm": st.anorm,
+               "arnorm": st.arnorm}
+        if history:
+            out["history"] = hist[:st.itn].copy()
+        if stats:
+            out["stats"] = {"total_ms": st.total_ms, "operator_ms": st.operator_ms, "vector_ms": st.vector_ms,
+                            "bytes_device": int(st.bytes_device)}
+        return out
+
+    def read(self):
+        """rtmi_tomo_read: (row_ptr [rows + 1], base [segments], val [segments, 4]), rows in order, segments in visit order"""
+        i = self.info()
+        row_ptr = np.zeros(i["rows"] + 1, dtype=np.int64)
+        base = np.empty(i["segments"], dtype=np.int32)
+        val = np.empty((i["segments"], 4))
+        check(lib().rtmi_tomo_read(self._open(), row_ptr.ctypes.data_as(C.POINTER(C.c_int64)), base.ctypes.data_as(_lib._ip), dptr(val)))
+        return row_ptr, base, val
+
+    def to_csr(self):
+        """The matrix as scipy.sparse CSR [rows, qy * qx]; segments of a row that share a column are summed"""
+        import scipy.sparse as sp
+        row_ptr, base, val = self.read()
+        rows = len(row_ptr) - 1
+        r = np.repeat(np.arange(rows), np.diff(row_ptr))
+        b = base.astype(np.int64)
+        cols = np.stack([b, b + 1, b + self.qx, b + self.qx + 1], axis=1)
+        return sp.coo_matrix((val.ravel(), (np.repeat(r, 4), cols.ravel())), shape=(rows, self.qy * self.qx)).tocsr()
+
+    def as_linear_operator(self):
+        from scipy.sparse.linalg import LinearOperator
+        return LinearOperator(self.shape, matvec=lambda x: self.matvec(x), rmatvec=lambda w: self.rmatvec(w).reshape(-1), dtype=np.float64)
+
+    def close(self):
+        if self._h:
+            lib().rtmi_tomo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _two_point_paraxial(field, p, sx, sy, line, arr, kmax):
     """The paraxial columns of two_point's converged arrivals, by public calls only: one fresh batch of the
     converged (source, launch angle) rays with the solver's parameters -- sized by a count pass without a record, as

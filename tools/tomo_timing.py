@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""The compiled tomography matrix against the row-walking kernels on one fan in one process:
+segments, padding, bytes and compile time of rtmi_tomo_append; rtmi_tomo_apply against rtmi_traveltime_perturb and
+rtmi_tomo_transpose against rtmi_traveltime_backproject, warmed, alternating, medians of 5 kernel event times with the spread of
+each series and the floor of each (the bytes it must read over 6 TB/s); the solver's operator and vector time per iteration.
+The fan is the vert_heterogeneous op6 fan from (-2, -2), at the ray ends and with the line x = 4.
+
+    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM = 6.0e12                        # bytes per second: the floor's yardstick
+BOX = (-2, 5, -2.5, 1)
+LINE = (1.0, 0.0, 4.0)
+
+
+def series(v):
+    v = np.asarray(v, dtype=np.float64)
+    return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max())}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rays", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from raytracing_amd import rt_bench as rb
+    R = a.rays
+    F = rb.Field.build("vert_heterogeneous", BOX, rb.DELTA)
+    ms = int(np.ceil(80 / rb.DELTA_S) + 1)
+    th = np.linspace(0.0, np.pi / 2, R)
+    c = rb.Batch(F, rb.op6, rb.DELTA_S, ms, BOX, 1, th, -2.0, -2.0, record_stride=0)
+    c.run()
+    last = c.d_ray()[2]
+    c.close()
+    rows = int(last.max()) + 1
+    b = rb.Batch(F, rb.op6, rb.DELTA_S, ms, BOX, 1, th, -2.0, -2.0, rec_rows=rows, keep_n_ray=False)
+    b.run()
+    walked = float(np.sum(last) + R)
+    rec_bytes = rows * 6 * R * 8
+    out = {"rays": R, "rec_rows": rows, "rows_walked": walked, "record_bytes": rec_bytes, "row_walk_floor_ms": 16 * walked / HBM * 1e3}
+    zero = np.zeros(R, dtype=np.int32)
+    E = rb.Tomography(F)
+    E.append(b)
+    out["ends"] = E.info()
+    EL = rb.Tomography(F)
+    EL.append(b)
+    out["ends_then_line"] = {"ends_compile_ms": EL.info()["compile_ms"]}
+    EL.append(b, which=zero, line=LINE, kmax=1)
+    out["ends_then_line"].update(EL.info())
+    for name, T in (("ends", E), ("ends_then_line", EL)):
+        i = out[name]
+        i["padding_share"] = 1.0 - i["segments"] / max(i["padded_segments"], 1)
+        i["bytes_over_record"] = i["bytes_device"] / rec_bytes
+        i["product_floor_ms"] = (36 * i["segments"] + 12 * i["rows"]) / HBM * 1e3
+    rng = np.random.default_rng(0)
+    dz = rng.standard_normal((F.qy, F.qx))
+    we, wl = rng.standard_normal(R), rng.standard_normal((1, R))
+    pairs = {
+        "A_ends": (lambda: b.traveltime_perturb(dz, stats=True)["stats"]["kernel_ms"], lambda: E.matvec(dz, stats=True)[1]["kernel_ms"]),
+        "At_ends": (lambda: b.traveltime_backproject(w_end=we, stats=True)[1]["kernel_ms"],
+                    lambda: E.rmatvec(we, stats=True)[1]["kernel_ms"]),
+        "A_line": (lambda: b.traveltime_perturb(dz, line=LINE, kmax=1, stats=True)["stats"]["kernel_ms"],
+                   lambda: EL.matvec(dz, stats=True)[1]["kernel_ms"]),
+        "At_line": (lambda: b.traveltime_backproject(w_end=we, w_line=wl, line=LINE, kmax=1, stats=True)[1]["kernel_ms"],
+                    lambda: EL.rmatvec(np.r_[we, wl[0]], stats=True)[1]["kernel_ms"]),
+    }
+    for name, (walk, compiled) in pairs.items():
+        walk(); compiled()                                        # warm both
+        tw, tc = [], []
+        for _ in range(a.reps):                                   # alternating
+            tw.append(walk())
+            tc.append(compiled())
+        sw, sc = series(tw), series(tc)
+        spread = max(sw["max_ms"] - sw["min_ms"], sc["max_ms"] - sc["min_ms"])
+        out[name] = {"row_walk": sw, "compiled": sc, "spread_ms": spread,
+                     "compiled_is_faster_beyond_the_spread": bool(sw["median_ms"] - sc["median_ms"] > spread)}
+    out["At_ends"]["atomics"] = {"row_walk": b.traveltime_backproject(w_end=we, stats=True)[1]["atomics"],
+                                 "compiled": E.rmatvec(we, stats=True)[1]["atomics"]}
+    # the products agree with the walk
+    d = b.traveltime_perturb(dz)["end"]
+    y = E.matvec(dz)
+    out["A_ends"]["max_rel_diff"] = float(np.nanmax(np.abs(y - d)) / np.nanmax(np.abs(d)))
+    b.close()                                                     # the solver runs without the record
+    s = E.lsqr(rng.standard_normal(R), damp=1e-3, smooth=(0.5, 0.25), iter_lim=a.iters, stats=True)
+    out["lsqr"] = {"itn": s["itn"], "istop": s["istop"], "operator_ms_per_iteration": s["stats"]["operator_ms"] / max(s["itn"], 1),
+                   "vector_ms_per_iteration": s["stats"]["vector_ms"] / max(s["itn"], 1), "total_ms": s["stats"]["total_ms"],
+                   "bytes_device": s["stats"]["bytes_device"]}
+    E.close(); EL.close(); F.close()
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
