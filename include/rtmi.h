@@ -625,7 +625,8 @@ int rtmi_gaussian_beams(rtmi_batch *b, int32_t fan_size, const rtmi_beam_params 
  * irec or out; nx, ny, P, N < 1; nt < 2; nx ny > 2^31; dt or t0 not finite or dt <= 0; nbin < 0, nbin > 32; nbin > 0 with a null
  * theta or a dopen that is not finite and > 0; an index outside [0, P); a w that is not finite.  Null handle or buffer in the
  * other calls: RTMI_ERR_ARG.
- * Not covered: the 2-D half-derivative / wavelet shaping filter (the caller filters traces), fp32 storage, several GPUs.
+ * The 2-D half-derivative and the wavelet, as a filter along the traces on the device: rtmi_kirchhoff_set_filter below.
+ * Not covered: fp32 storage, several GPUs.
  * Device-resident data and image buffers: rtmi_kirchhoff_migrate_dev / _model_dev below.  Several arrivals per node and their
  * caustic phase: rtmi_kirchhoff_create_multi below; anti-alias filtering of steep operators: rtmi_kirchhoff_create_aa below. */
 typedef struct rtmi_kirchhoff rtmi_kirchhoff;
@@ -675,8 +676,9 @@ void rtmi_kirchhoff_destroy(rtmi_kirchhoff *k);
  * rtmi_kirchhoff_destroy.  rtmi_kirchhoff_migrate / _model on a handle of create_multi, and migrate2 / model2 on a handle of
  * rtmi_kirchhoff_create, return RTMI_ERR_ARG.  Refused before any device work as above, and also: karr outside 1 .. 4; a null
  * data1 on a handle that has kmah.  stats: pairs = N nx ny K^2.
- * H on the device: rtmi_kirchhoff_hilbert below.
- * Not covered: the 2-D half-derivative / pi/4 filter (the caller filters), fp32 tables, K > 4. */
+ * H on the device: rtmi_kirchhoff_hilbert below.  The 2-D half-derivative (the pi/4 filter) and the wavelet on the device:
+ * rtmi_kirchhoff_set_filter / rtmi_kirchhoff_filter below, and inside the least-squares operator rtmi_kirchhoff_lsqr_filtered.
+ * Not covered: fp32 tables, K > 4. */
 #define RTMI_KIRCHHOFF_MAX_ARRIVALS 4
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen; int64_t reserved[4]; } rtmi_kirchhoff_multi_params;
 int rtmi_kirchhoff_create_multi(const rtmi_kirchhoff_multi_params *kp, const double *T, const double *amp, const double *theta,
@@ -723,8 +725,9 @@ int rtmi_kirchhoff_model2(rtmi_kirchhoff *k, const double *model, double *data0,
  * Refused before any device work, with rtmi_last_error naming the argument: everything rtmi_kirchhoff_create_multi refuses; a
  * null pt; nlev outside 1 .. 8; hw[0] != 0, hw not strictly increasing or above 64; a length that is negative or not finite.
  * rtmi_kirchhoff_migrate / _model on such a handle, and rtmi_kirchhoff_aa_filter on any other handle, return RTMI_ERR_ARG.
- * H on the device: rtmi_kirchhoff_hilbert below.
- * Not covered: the half-derivative / wavelet filter (the caller's), a continuous triangle by double integration (it loses
+ * H on the device: rtmi_kirchhoff_hilbert below.  The half-derivative and the wavelet on the device: rtmi_kirchhoff_set_filter /
+ * rtmi_kirchhoff_filter below, and inside the least-squares operator rtmi_kirchhoff_lsqr_filtered.
+ * Not covered: a continuous triangle by double integration (it loses
  * about 2 log2(nt) bits and has no bit-for-bit definition), fp32 tables or traces, K > 4. */
 #define RTMI_KIRCHHOFF_MAX_LEVELS 8
 typedef struct { int64_t nx, ny, P, N, nt; double t0, dt; int32_t nbin, karr; double dopen;
@@ -813,6 +816,45 @@ int rtmi_kirchhoff_hilbert(rtmi_kirchhoff *k, const double *x, double *y);      
 int rtmi_kirchhoff_hilbert_dev(rtmi_kirchhoff *k, const double *d_x, const double *d_add, int32_t negate, double *d_y);
 int rtmi_kirchhoff_lsqr_full(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const double *data, double *x, double *history,
                              rtmi_lsqr_stats *st);
+
+/* A filter along the traces of a handle with the caller's taps -- typically the source wavelet convolved with the 2-D
+ * half-derivative -- its transpose, both on the device and defined bit for bit, and least-squares migration with the filter
+ * inside the operator.  DESIGN.md section 25.
+ * F is a linear (not circular) convolution along the last axis of [N][nt].  The taps are f[0 .. L) with an origin o, 0 <= o < L:
+ * tap o is lag zero (a zero-phase wavelet of 2 M + 1 taps has o = M, a causal filter o = 0).
+ *   F  :  y[i] = sum over k = 0 .. L - 1 ascending with 0 <= i - k + o < nt of fl(f[k] * x[i - k + o])
+ *   F^T:  y[i] = sum over k = 0 .. L - 1 ascending with 0 <= i + k - o < nt of fl(f[k] * x[i + k - o])
+ * The sum starts from +0.0; every product and add is a separate fp64 operation.  Terms outside the trace do not exist: F is the
+ * nt x nt Toeplitz matrix F[i][j] = f[i - j + o], and F^T is its transpose entry for entry, in every bit.  The taps must be
+ * finite; the input is not checked for finiteness: a sample that is not finite makes NaN or inf wherever the formula does
+ * (raytracing_amd/csrc/rt_filter.h has the definition as a host loop).
+ * rtmi_half_derivative_taps writes L causal taps (o = 0) of the half-derivative (host only, no device): g_0 = 1,
+ * g_k = g_(k-1) (2 k - 3) / (2 k), the coefficients of (1 - z)^(1/2) (the Gruenwald-Letnikov half-differentiator), each times
+ * 1 / sqrt(dt), evaluated in long double and rounded once to fp64.  The response is (1 - exp(-i w dt))^(1/2) / sqrt(dt), which
+ * tends to sqrt(i w) for w dt << 1; L taps leave out a tail whose absolute sum is exactly sum over k < L of g_k / sqrt(dt), the
+ * truncated filter's response at DC.  RTMI_ERR_ARG: null taps, L < 1, dt not finite or <= 0.  The usual filter is this convolved
+ * with the wavelet, the origin at the wavelet's centre.
+ * rtmi_kirchhoff_set_filter copies the taps to the handle's device, on every kind of handle; rtmi_kirchhoff_destroy frees them.  A
+ * second call replaces the first; L = 0 clears the filter (taps and origin are not read).  RTMI_ERR_ARG: a null handle; L < 0 or
+ * L > 2048; null taps with L > 0; origin outside [0, L); a tap that is not finite; nt > 16384, naming nt (the kernel holds a
+ * trace and the L - 1 zeros around it in LDS in one piece).
+ * rtmi_kirchhoff_filter: y = F x, or F^T x with transpose != 0, host [N][nt] -> [N][nt]; rtmi_kirchhoff_filter_dev the same on
+ * memory of the handle's device.  RTMI_ERR_STATE with no filter set.  RTMI_ERR_ARG: a null handle or buffer; d_y equal to d_x or
+ * overlapping it; pointers as rtmi_kirchhoff_migrate_dev checks its own.
+ * rtmi_kirchhoff_lsqr_filtered is rtmi_kirchhoff_lsqr_full with the filter inside the operator: with B the operator of
+ * rtmi_kirchhoff_lsqr_full, A x = F (B x) and A^T u = B^T (F^T u), its transpose in every bit.  The same scalar recurrence, norm
+ * and update kernels, stop rules, history, stats and refusals.  F is out of place: the call holds one more N nt vector (B v and
+ * F^T u are never live together); bytes_device counts it and the L taps, and operator_ms includes the filter kernels' event time.
+ * With no filter set the call is rtmi_kirchhoff_lsqr_full bit for bit, bytes_device included.
+ * Every other entry ignores a set filter: rtmi_kirchhoff_lsqr, _lsqr_full, the model, migrate and hilbert calls keep their bits.
+ * Not covered: circular filtering, L > 2048 or nt > 16384, an FFT form, per-trace or time-varying wavelets, wavelet estimation,
+ * fp32 traces. */
+int rtmi_half_derivative_taps(int64_t L, double dt, double *taps);                       /* host only, no device */
+int rtmi_kirchhoff_set_filter(rtmi_kirchhoff *k, const double *taps, int64_t L, int64_t origin);  /* L = 0, taps NULL: clear */
+int rtmi_kirchhoff_filter(rtmi_kirchhoff *k, const double *x, int32_t transpose, double *y);      /* host [N][nt] -> [N][nt] */
+int rtmi_kirchhoff_filter_dev(rtmi_kirchhoff *k, const double *d_x, int32_t transpose, double *d_y);
+int rtmi_kirchhoff_lsqr_filtered(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const double *data, double *x, double *history,
+                                 rtmi_lsqr_stats *st);
 
 /* Recorded rays compiled into a sparse ray-tomography matrix on the device, its products and LSQR on it.  DESIGN.md section 24.
  * The matrix is the A of rtmi_traveltime_perturb / _backproject above -- the derivative of reported traveltimes with respect to

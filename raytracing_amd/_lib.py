@@ -154,6 +154,8 @@ class TomoStats(C.Structure):
 TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
 HILBERT_MAX_NT = 16384  # the longest trace rtmi_kirchhoff_hilbert takes: one copy of it in LDS
+FILTER_MAX_NT = 16384   # the longest trace and ...
+FILTER_MAX_TAPS = 2048  # ... the most taps rtmi_kirchhoff_set_filter takes: the trace and the filter's zeros in LDS
 
 # rtmi_arrival_grid's orders and largest karr
 ARRIVAL_BY_TIME, ARRIVAL_BY_AMPLITUDE, MAX_ARRIVALS = 0, 1, 16
@@ -221,6 +223,11 @@ SYMBOLS = {
     "rtmi_kirchhoff_hilbert": (C.c_int, [C.c_void_p, _dp, _dp]),
     "rtmi_kirchhoff_hilbert_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rtmi_kirchhoff_lsqr_full": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_half_derivative_taps": (C.c_int, [C.c_int64, C.c_double, _dp]),
+    "rtmi_kirchhoff_set_filter": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int64]),
+    "rtmi_kirchhoff_filter": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp]),
+    "rtmi_kirchhoff_filter_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtmi_kirchhoff_lsqr_filtered": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, C.POINTER(LsqrStats)]),
     "rtmi_tomo_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rtmi_tomo_append": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int32, _ip, _ip, C.POINTER(C.c_int64)]),
     "rtmi_tomo_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), _ip, _dp]),

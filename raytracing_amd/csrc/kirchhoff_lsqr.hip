@@ -3,7 +3,8 @@
 // LSQR over the pair of kirchhoff.hip / kirchhoff_aa.hip on device pointers, every vector on the device from the one upload of the
 // data to the one download of the model.  include/rtmi.h states the contract; DESIGN.md section 21 the definitions, the memory and
 // what was measured; rt_lsqr.h the scalar recurrence (host, scipy's operation order).  _lsqr_full on a handle with kmah solves
-// for the full trace ch0 + H ch1 with the Hilbert transform of kirchhoff_hilbert.hip around the pair.
+// for the full trace ch0 + H ch1 with the Hilbert transform of kirchhoff_hilbert.hip around the pair;
+// rtmi_kirchhoff_lsqr_filtered puts the trace filter of kirchhoff_filter.hip and its transpose around that.
 // The loop, its vector passes and the order-independent norm are rt_lsqr_device.h's, shared with tomo.hip.
 #include "rt_hilbert.h"
 #include "rt_kirchhoff.h"
@@ -12,8 +13,11 @@
 namespace {
 
 // Both solvers.  full: on a handle with kmah the operator is that of the full trace, A x = ch0 + H ch1 with (ch0, ch1) =
-// model2(x), and A^T u = migrate2(u, -H u), its transpose in every bit; on any other handle `full` changes nothing.
-int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
+// model2(x), and A^T u = migrate2(u, -H u), its transpose in every bit; on any other handle `full` changes nothing.  filtered
+// (with full): on a handle with a filter set, with B that operator, A x = F (B x) and A^T u = B^T (F^T u); F is out of place, so
+// the call holds one more N nt vector, Fb, for B v and for F^T u, which are never live together.  With no filter set `filtered`
+// changes nothing.
+int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
              rtmi_lsqr_stats* st) {
     RTMI_ARG(k, "null handle");
     RTMI_ARG(lp, "null params");
@@ -21,7 +25,7 @@ int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_para
     RTMI_ARG(x, "null x");
     RTMI_RC(lsqr_check_params(who, lp));
     RTMI_ARG(full || !k->kmah, "the handle has kmah: its trace is ch0 + H ch1, which rtmi_kirchhoff_lsqr_full solves for");
-    const bool hil = full && k->kmah;
+    const bool hil = full && k->kmah, fil = filtered && k->ftaps;
     if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_check(k, who));
     const size_t per = (size_t)k->kp.N * (size_t)k->kp.nt, nm = (size_t)k->nb * k->nn;
     for (size_t i = 0; i < per; i++) RTMI_ARG(std::isfinite(data[i]), "data has a value that is not finite");
@@ -30,34 +34,42 @@ int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_para
     DevMem mem;
     double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr;
     double *Av1 = nullptr, *Hu = nullptr;                                             // channel 1 of A v, and -H u: with hil only
-    const char* no_mem = full ? "rtmi_kirchhoff_lsqr_full: hipMalloc failed" : "rtmi_kirchhoff_lsqr: hipMalloc failed";
-    for (double** p : {&u, &Av, &Av1, &Hu})
-        if ((hil || (p != &Av1 && p != &Hu)) && mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem);
+    double* Fb = nullptr;                                                             // B v, then F^T u: with fil only
+    const std::string no_mem = std::string(who) + ": hipMalloc failed";
+    const struct { double** p; bool wanted; } traces[] = {{&u, true}, {&Av, true}, {&Av1, hil}, {&Hu, hil}, {&Fb, fil}};
+    for (const auto& a : traces)
+        if (a.wanted && mem.get(a.p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
     for (double** p : {&v, &w, &xd, &Atu})
-        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem);
+        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
     const Vec V{k->red, k->cus};
     rtmi_lsqr_stats out{};
-    // the call's vectors, the handle's staging (with kmah: two channels per level) and, with hil, the taps
+    // the call's vectors, the handle's staging (with kmah: two channels per level) and, with hil and with fil, their taps
     const size_t staging = (size_t)(k->nlev ? k->nlev : 1) * (k->kmah ? 2 : 1) * per + nm;
-    const size_t ntaps = hil ? (size_t)rt::hilbert_ntaps(k->kp.nt) : 0;
-    out.bytes_device = (int64_t)(((hil ? 4 : 2) * per + 4 * nm + staging + ntaps) * sizeof(double) +
+    const size_t ntaps = (hil ? (size_t)rt::hilbert_ntaps(k->kp.nt) : 0) + (fil ? (size_t)k->fL : 0);
+    out.bytes_device = (int64_t)(((hil ? 4 : 2) * per + (fil ? per : 0) + 4 * nm + staging + ntaps) * sizeof(double) +
                                  (k->ncounts + kRedWords) * sizeof(unsigned long long));
     double operator_ms = 0.0;
     rtmi_kirchhoff_stats ks{};
 
-    // t = A^T s and t = A s; the Hilbert kernels' event time counts as the operator's
+    // t = A^T s and t = A s; the Hilbert and filter kernels' event time counts as the operator's
     auto At = [&](const double* s, double* t, bool*) {
-        double ms = 0.0;
+        double ms = 0.0, fms = 0.0;
+        if (fil) {
+            RTMI_RC(rtmi_internal_kirchhoff_filter_dev(k, who, s, true, Fb, &fms));
+            s = Fb;
+        }
         if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_dev(k, who, s, nullptr, true, Hu, &ms));
         RTMI_RC(rtmi_internal_kirchhoff_migrate_dev(k, who, s, hil ? Hu : nullptr, t, &ks, false));
-        operator_ms += ks.kernel_ms + ms;
+        operator_ms += ks.kernel_ms + ms + fms;
         return (int)RTMI_OK;
     };
     auto Ax = [&](const double* s, double* t) {
-        double ms = 0.0;
-        RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, s, t, hil ? Av1 : nullptr, &ks, false));
-        if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_dev(k, who, Av1, t, false, t, &ms));
-        operator_ms += ks.kernel_ms + ms;
+        double ms = 0.0, fms = 0.0;
+        double* b = fil ? Fb : t;                                                     // B s
+        RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, s, b, hil ? Av1 : nullptr, &ks, false));
+        if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_dev(k, who, Av1, b, false, b, &ms));
+        if (fil) RTMI_RC(rtmi_internal_kirchhoff_filter_dev(k, who, b, false, t, &fms));
+        operator_ms += ks.kernel_ms + ms + fms;
         return (int)RTMI_OK;
     };
 
@@ -75,12 +87,17 @@ int lsqr_run(const char* who, bool full, rtmi_kirchhoff* k, const rtmi_lsqr_para
 
 RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
                                     rtmi_lsqr_stats* st) {
-    return lsqr_run("rtmi_kirchhoff_lsqr", false, k, lp, data, x, history, st);
+    return lsqr_run("rtmi_kirchhoff_lsqr", false, false, k, lp, data, x, history, st);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_lsqr_full(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
                                          rtmi_lsqr_stats* st) {
-    return lsqr_run("rtmi_kirchhoff_lsqr_full", true, k, lp, data, x, history, st);
+    return lsqr_run("rtmi_kirchhoff_lsqr_full", true, false, k, lp, data, x, history, st);
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_lsqr_filtered(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x,
+                                             double* history, rtmi_lsqr_stats* st) {
+    return lsqr_run("rtmi_kirchhoff_lsqr_filtered", true, true, k, lp, data, x, history, st);
 }
 
 RTMI_EXPORT int rtmi_debug_fix_norm(const double* x, int64_t n, double* norm, int32_t* e) {

@@ -3,7 +3,7 @@
 // migration over any handle): the kernel arguments, one (trace, node) pair's arithmetic, the arrivals of a table at a node and
 // their phase, a block's count, the handle, its argument checks and uploads.  Everything but the handle and
 // the cross-unit entries is in an anonymous namespace: each unit gets its own copy, as with rtmi_host.h.  DESIGN.md sections 14,
-// 19, 20, 21 and 23.
+// 19, 20, 21, 23 and 25.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,9 +138,11 @@ struct rtmi_kirchhoff {
     double asrc = 0.0, arec = 0.0, amid = 0.0;
     double* pt = nullptr;                     // [P][K][nn]
     double* htaps = nullptr;                  // the Hilbert transform's taps for nt (rt_hilbert.h), uploaded at its first use
+    double* ftaps = nullptr;                  // rtmi_kirchhoff_set_filter's taps f[0 .. fL), NULL with no filter set (rt_filter.h)
+    int fL = 0, forigin = 0;
     ~rtmi_kirchhoff() {
         for (void* p : {(void*)T, (void*)amp, (void*)theta, (void*)w, (void*)data, (void*)image, (void*)isrc, (void*)irec, (void*)kmah, (void*)counts,
-                        (void*)pt, (void*)red, (void*)htaps})
+                        (void*)pt, (void*)red, (void*)htaps, (void*)ftaps})
             if (p) (void)hipFree(p);
     }
     KArgs args() const {
@@ -178,6 +180,10 @@ int rtmi_internal_kirchhoff_aa_sweep(rtmi_kirchhoff* k, const char* who, bool ga
 int rtmi_internal_kirchhoff_hilbert_check(const rtmi_kirchhoff* k, const char* who);
 int rtmi_internal_kirchhoff_hilbert_dev(rtmi_kirchhoff* k, const char* who, const double* d_x, const double* d_add, bool negate,
                                         double* d_y, double* ms);
+// The trace filter on device pointers (kirchhoff_filter.hip): d_y = F d_x over [N][nt], or F^T d_x with
+// transpose, with the taps of rtmi_kirchhoff_set_filter; d_y may not be d_x.  The callers have checked that a filter is set
+// (k->ftaps), the arguments and the device.  ms as above.
+int rtmi_internal_kirchhoff_filter_dev(rtmi_kirchhoff* k, const char* who, const double* d_x, bool transpose, double* d_y, double* ms);
 
 namespace {
 

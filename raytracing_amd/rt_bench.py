@@ -1408,6 +1408,18 @@ def debug_hilbert(x, add=None, negate=False):
     return y
 
 
+def half_derivative_taps(L, dt):
+    """rtmi_half_derivative_taps: L causal taps (origin 0) of the 2-D half-derivative sqrt(i w), the pi/4 filter, at the sample
+    interval dt: g_0 = 1, g_k = g_(k-1) (2 k - 3) / (2 k), each times 1 / sqrt(dt) (include/rtmi.h).  Host only: no device is
+    touched.  The filter of Kirchhoff.set_filter is usually this convolved with the wavelet:
+      ricker = ...                                                    # 2 M + 1 zero-phase taps, its centre at index M
+      op.set_filter(np.convolve(ricker, half_derivative_taps(L, dt)), origin=M)"""
+    L = int(L)
+    taps = np.zeros(max(L, 1))
+    check(lib().rtmi_half_derivative_taps(L, float(dt), dptr(taps)))
+    return taps[:L]
+
+
 class Kirchhoff:
     """Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_*, include/rtmi.h).  T [P, ny, nx]:
     traveltime_table's T for P surface positions; isrc, irec [N]: each trace's source and receiver position in [0, P); nt samples
@@ -1436,7 +1448,14 @@ class Kirchhoff:
     then the solver is rtmi_kirchhoff_lsqr_full, for the full trace ch0 + H ch1 with H on the device:
       hilbert(d) -> H d on host arrays    and    hilbert_device(x, add=None, negate=False) -> (add or +0) +- H x on torch tensors
     are that H, on every kind of handle, for nt <= 16384: the matrix of `hilbert` evaluated in the time domain and defined bit for
-    bit, its transpose -H in every bit.  model, migrate and as_linear_operator() keep the FFT form and their bits."""
+    bit, its transpose -H in every bit.  model, migrate and as_linear_operator() keep the FFT form and their bits.
+    The wavelet and the 2-D half-derivative on the device:
+      set_filter(taps, origin=0)    keeps taps f[0 .. L), L <= 2048, on the handle (None clears); tap `origin` is lag zero
+      filter(d, transpose=False) -> F d or F^T d on host arrays    and    filter_device(x, transpose=False) on torch tensors
+    are the linear convolution (F d)[i] = sum_k f[k] d[i - k + origin] along the traces, zero outside them, and its exact
+    transpose, defined bit for bit; the usual taps are np.convolve(ricker, half_derivative_taps(L, dt)) with origin at the
+    Ricker's centre.  lsqr(..., filtered=True) solves with that filter inside the operator, F (ch0 + H ch1), and its exact
+    transpose (rtmi_kirchhoff_lsqr_filtered).  Every other call ignores a set filter."""
 
     def __init__(self, T, isrc, irec, nt, dt, t0=0.0, amp=None, theta=None, weights=None, nbin=0, dopen=None, kmah=None, pt=None,
                  antialias=None):
@@ -1477,6 +1496,7 @@ class Kirchhoff:
         self.shape = (self.N * self.nt, self.nb * ny * nx)
         self.has_kmah = kmah is not None
         self._h = None
+        self._filter = None                            # (L, origin) of set_filter, None with no filter set
         h = C.c_void_p()
         if pt is not None:
             aa = self.antialias
@@ -1662,15 +1682,60 @@ class Kirchhoff:
         check(lib().rtmi_kirchhoff_hilbert_dev(h, x.data_ptr(), None if add is None else add.data_ptr(), 1 if negate else 0, y.data_ptr()))
         return y
 
-    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False, hilbert=None):
+    def set_filter(self, taps, origin=0):
+        """rtmi_kirchhoff_set_filter: keep the taps f[0 .. L), 1 <= L <= 2048, finite, on the handle's device; tap `origin` is
+        lag zero (0: causal; M for a zero-phase wavelet of 2 M + 1 taps).  None clears the filter.  A second call replaces the
+        first.  The usual composition: set_filter(np.convolve(ricker, half_derivative_taps(L, dt)), origin=M), M the index of
+        the Ricker's centre."""
+        if taps is None:
+            check(lib().rtmi_kirchhoff_set_filter(self._open(), None, 0, 0))
+            self._filter = None
+            return
+        f = np.ascontiguousarray(taps, dtype=np.float64)
+        if f.ndim != 1 or f.size < 1:
+            raise ValueError("Kirchhoff.set_filter: taps must be a vector of at least one value (None clears the filter)")
+        check(lib().rtmi_kirchhoff_set_filter(self._open(), dptr(f), f.size, int(origin)))    # the library checks the rest
+        self._filter = (int(f.size), int(origin))
+
+    def filter(self, d, transpose=False):
+        """rtmi_kirchhoff_filter: F d, or F^T d with transpose, along the last axis of [N, nt] host arrays, on the device"""
+        dd = np.ascontiguousarray(d, dtype=np.float64)
+        if dd.size != self.N * self.nt:
+            raise ValueError("Kirchhoff.filter: d must be [N, nt]")
+        y = np.empty((self.N, self.nt))
+        check(lib().rtmi_kirchhoff_filter(self._open(), dptr(dd), 1 if transpose else 0, dptr(y)))
+        return y
+
+    def filter_device(self, x, transpose=False):
+        """rtmi_kirchhoff_filter_dev: F x, or F^T x with transpose, [N, nt] torch tensors on the handle's device; x is never
+        written, the result is a new tensor"""
+        import torch
+        who = "filter_device"
+        self._device_tensor(who, x, "x", self.N * self.nt)
+        self._on_device(who, x=x)
+        h = self._open()
+        y = torch.empty((self.N, self.nt), dtype=torch.float64, device=x.device)
+        torch.cuda.synchronize(x.device)               # the library works on the null stream
+        check(lib().rtmi_kirchhoff_filter_dev(h, x.data_ptr(), 1 if transpose else 0, y.data_ptr()))
+        return y
+
+    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False, hilbert=None, filtered=False):
         """rtmi_kirchhoff_lsqr: min |L x - d|^2 + damp^2 |x|^2 from x = 0, every vector on the device.  -> dict: x shaped like
         migrate's image, istop (scipy's 0, 1, 2, 7; _lib.LSQR_RANGE: a norm left fp64's normal range), itn, r1norm, r2norm, anorm,
         arnorm; with history=True also history [itn, 4] (alfa, beta, r1norm, arnorm after each iteration); with stats=True also
         stats (total_ms, operator_ms, vector_ms, bytes_device).  hilbert="device": rtmi_kirchhoff_lsqr_full, which on a handle
         with kmah solves for the full trace ch0 + H ch1 (model's trace, with the device's H) and on any other handle is the same
-        call; None: a handle with kmah is refused."""
+        call; None: a handle with kmah is refused.  filtered=True: rtmi_kirchhoff_lsqr_filtered, the same with set_filter's F
+        inside the operator, A = F (ch0 + H ch1) and its exact transpose; it needs a filter, and on a handle with kmah
+        hilbert="device"."""
         if hilbert not in (None, "device"):
             raise ValueError('Kirchhoff.lsqr: hilbert must be None or "device"')
+        if filtered:
+            if getattr(self, "_filter", None) is None:
+                raise ValueError("Kirchhoff.lsqr: filtered=True needs a filter (set_filter)")
+            if hilbert is None and self.has_kmah:
+                raise ValueError('Kirchhoff.lsqr: filtered=True on a handle with kmah needs hilbert="device": the filtered trace is '
+                                 "F (ch0 + H ch1)")
         dd = np.ascontiguousarray(d, dtype=np.float64)
         if dd.size != self.N * self.nt:
             raise ValueError("Kirchhoff.lsqr: d must be [N, nt]")
@@ -1682,7 +1747,8 @@ class Kirchhoff:
         x = np.empty((self.nb, self.ny, self.nx))
         hist = np.zeros((iter_lim, 4)) if history else None
         st = _lib.LsqrStats()
-        solver = lib().rtmi_kirchhoff_lsqr_full if hilbert == "device" else lib().rtmi_kirchhoff_lsqr
+        solver = (lib().rtmi_kirchhoff_lsqr_filtered if filtered else
+                  lib().rtmi_kirchhoff_lsqr_full if hilbert == "device" else lib().rtmi_kirchhoff_lsqr)
         check(solver(self._open(), C.byref(lp), dptr(dd), dptr(x), dptr(hist), C.byref(st)))
         out = {"x": x if self.nbin else x[0], "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm,
                "anorm": st.anorm, "arnorm": st.arnorm}

@@ -24,7 +24,15 @@ the same case with a handle of K arrivals and kmah, in one process: k_hilbert al
 Kirchhoff.hilbert_device, which ends with the stream idle: launch, kernel and the wait; median of --reps), rt_bench.hilbert (numpy's
 FFT on the host) on the same array for scale, and per iteration the wall time of Kirchhoff.lsqr(hilbert="device") against scipy's
 lsqr over as_linear_operator(), whose model and migrate go through the host's FFT.  --lsqr 0 leaves the two loops out.
-Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV] [--lsqr ITERS] [--hilbert]"""
+--filter L (with --arrivals K, default 2, and --lsqr ITERS, default 3) times the trace filter on the device on the
+same case with a handle of K arrivals and kmah and L taps (a Ricker convolved with the half-derivative taps), in one process:
+k_trace_filter alone in both directions (the wall time of Kirchhoff.filter_device: launch, kernel and the wait; median of --reps)
+beside scipy.signal.oaconvolve on the host, and per iteration the wall time of Kirchhoff.lsqr(filtered=True) beside
+Kirchhoff.lsqr(hilbert="device") on the same handle and beside the host loop of the same operator -- scipy's lsqr over a
+LinearOperator made of model_channels / migrate_channels, rt_bench.hilbert and scipy.signal.oaconvolve -- the two loops
+alternating, twice each.  --lsqr 0 leaves the loops out.
+Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV] [--lsqr ITERS] [--hilbert]
+                                        [--filter L]"""
 import argparse
 import json
 import os
@@ -295,6 +303,93 @@ def run_hilbert(K, reps, iters):
     op.close()
 
 
+def run_filter(L, K, reps, iters):
+    import torch
+    from scipy.signal import oaconvolve
+    from scipy.sparse.linalg import LinearOperator, lsqr
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, _ = tables(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    N = len(isrc)
+    TK = np.stack([T + 0.003 * i for i in range(K)], axis=1)
+    km = np.broadcast_to(np.arange(K, dtype=np.float64)[None, :, None, None], TK.shape)
+    op = rb.Kirchhoff(TK, isrc, irec, nt, dt, kmah=km)
+    # a zero-phase Ricker of 2 M + 1 taps convolved with the half-derivative: L taps, the origin at the Ricker's centre
+    M = min(32, (L - 1) // 2)
+    u = (np.pi * 60.0 * (np.arange(2 * M + 1) - M) * dt) ** 2
+    f = np.convolve((1.0 - 2.0 * u) * np.exp(-u), rb.half_derivative_taps(L - 2 * M, dt))
+    assert f.size == L
+    op.set_filter(f, origin=M)
+
+    def host_F(b, transpose=False):
+        g = f[::-1] if transpose else f
+        o = L - 1 - M if transpose else M
+        return oaconvolve(b, g[None, :], axes=-1)[:, o:o + nt]
+
+    x = np.random.default_rng(1).standard_normal((N, nt))
+    tx = torch.from_numpy(x).to("cuda")
+    # the fp64 floor: 2 operations per output and tap, 4 cycles per wave instruction, 1024 SIMDs at 2.4 GHz
+    floor_ms = N * nt * L * 2 / 64 * 4 / 1024 / 2.4e9 * 1e3
+    for tr in (False, True):
+        op.filter_device(tx, transpose=tr)                       # warm-up: code object
+        ws = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            ty = op.filter_device(tx, transpose=tr)
+            ws.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        hf = host_F(x, tr)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        k = float(np.median(ws))
+        print(json.dumps({"what": f"k_trace_filter<{'true' if tr else 'false'}> alone (launch, kernel, wait)", "N": N, "nt": nt, "taps": L,
+                          "origin": M, "wall_ms_median": k, "wall_ms": ws, "fp64_issue_floor_ms": floor_ms,
+                          "wall_over_fp64_floor": k / floor_ms, "scipy_oaconvolve_on_the_host_ms": host_ms,
+                          "max_diff_from_host_over_max": float(np.max(np.abs(ty.cpu().numpy() - hf)) / np.max(np.abs(hf)))}), flush=True)
+    if iters > 0:
+        shape = T.shape[1:]
+
+        def matvec(m):
+            c0, c1 = op.model_channels(m.reshape(shape))
+            return host_F(c0 + rb.hilbert(c1)).reshape(-1)
+
+        def rmatvec(u):
+            ft = host_F(u.reshape(N, nt), transpose=True)
+            return op.migrate_channels(ft, -rb.hilbert(ft)).reshape(-1)
+        host_op = LinearOperator(op.shape, matvec=matvec, rmatvec=rmatvec, dtype=np.float64)
+        d = np.ascontiguousarray(matvec(np.random.default_rng(1).standard_normal(shape)).reshape(N, nt))
+        op.lsqr(d, 1, hilbert="device", filtered=True)           # warm-up: code objects, all operators
+        op.lsqr(d, 1, hilbert="device")
+        for run in (1, 2):
+            t0 = time.perf_counter()
+            dev = op.lsqr(d, iters, stats=True, hilbert="device", filtered=True)
+            t1 = time.perf_counter()
+            host = lsqr(host_op, d.reshape(-1), atol=0, btol=0, iter_lim=iters)
+            t2 = time.perf_counter()
+            plain = op.lsqr(d, iters, stats=True, hilbert="device")
+            t3 = time.perf_counter()
+            st, n = dev["stats"], dev["itn"]
+            dev_ms, host_ms, plain_ms = (t1 - t0) * 1e3 / n, (t2 - t1) * 1e3 / host[2], (t3 - t2) * 1e3 / plain["itn"]
+            print(json.dumps({"what": f"least-squares migration with the filter inside, K = {K} with kmah, L = {L}, {iters} iterations, "
+                                      f"run {run}", "N": N, "nodes": T[0].size, "nt": nt, "itn_device": n, "itn_host": int(host[2]),
+                              "filtered_device_loop_wall_ms_per_iteration": dev_ms,
+                              "unfiltered_device_loop_wall_ms_per_iteration": plain_ms, "filtered_over_unfiltered": dev_ms / plain_ms,
+                              "host_loop_wall_ms_per_iteration": host_ms, "host_over_device": host_ms / dev_ms,
+                              "operators_kernel_ms_per_iteration": st["operator_ms"] / n,
+                              "unfiltered_operators_kernel_ms_per_iteration": plain["stats"]["operator_ms"] / plain["itn"],
+                              "library_total_ms_per_iteration": st["total_ms"] / n,
+                              "unfiltered_library_total_ms_per_iteration": plain["stats"]["total_ms"] / plain["itn"],
+                              "vector_ms_per_iteration": st["vector_ms"] / n, "bytes_device": st["bytes_device"],
+                              "r1norm_device": dev["r1norm"], "r1norm_host": float(host[3]),
+                              "x_max_rel_diff": float(np.max(np.abs(dev["x"].reshape(-1) - host[0])) / np.max(np.abs(host[0])))}),
+                  flush=True)
+    op.close()
+
+
 def restatement():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import kirchhoff_ref as K
@@ -316,8 +411,13 @@ if __name__ == "__main__":
     ap.add_argument("--antialias", type=int, choices=range(1, 9), metavar="NLEV")
     ap.add_argument("--lsqr", type=int, metavar="ITERS")
     ap.add_argument("--hilbert", action="store_true")
+    ap.add_argument("--filter", type=int, metavar="L")
     a = ap.parse_args()
-    if a.hilbert:
+    if a.filter:
+        if not 3 <= a.filter <= 2048:
+            ap.error("--filter L: 3 <= L <= 2048")
+        run_filter(a.filter, a.arrivals or 2, a.reps, 3 if a.lsqr is None else a.lsqr)
+    elif a.hilbert:
         run_hilbert(a.arrivals or 2, a.reps, 3 if a.lsqr is None else a.lsqr)
     elif a.lsqr:
         run_lsqr(a.lsqr)
