@@ -773,7 +773,9 @@ int rtmi_kirchhoff_aa_filter(rtmi_kirchhoff *k, const double *data, double *bank
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null handle, params, data or x; iter_lim < 1;
  * damp, atol or btol negative or not finite; a handle with kmah; a data value that is not finite.
  * Handles with kmah (their trace is ch0 + H ch1): rtmi_kirchhoff_lsqr_full below.
- * Not covered: preconditioners, model masks, x0, conlim / acond / xnorm / var (acond and var need a vector norm more per iteration), scipy's stop tests 3 to 6,
+ * Row weights, a column scale (a diagonal preconditioner, and with zeros a model mask) and a start model:
+ * rtmi_kirchhoff_lsqr_weighted below.
+ * Not covered: conlim / acond / xnorm / var (acond and var need a vector norm more per iteration), scipy's stop tests 3 to 6,
  * fp32 vectors, several GPUs. */
 #define RTMI_LSQR_RANGE 8
 typedef struct { int32_t iter_lim, reserved0; double damp, atol, btol; int64_t reserved[4]; } rtmi_lsqr_params;
@@ -905,7 +907,8 @@ int rtmi_kirchhoff_lsqr_filtered(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, 
  * stats of _info and the products: rows, segments, padded_segments (the slots of the sliced storage: slices of 64 rows, each as
  * wide as its longest row), bytes_device, compile_ms (the event time of the last append), vmax, qx, qy; the products add
  * kernel_ms, and _transpose atomics and scale_exp.
- * Not covered: row weights, model masks, x0, a second-order regulariser; removing rows from a handle; several GPUs, fp32 vectors;
+ * Row weights, a column scale or mask and a start model: rtmi_tomo_lsqr_weighted below.
+ * Not covered: a second-order regulariser; removing rows from a handle; several GPUs, fp32 vectors;
  * model parameterisations other than the field's own samples. */
 #define RTMI_TOMO_SKIP (-2)
 typedef struct rtmi_tomo rtmi_tomo;
@@ -923,6 +926,68 @@ int rtmi_tomo_transpose_dev(rtmi_tomo *t, const double *d_w, double *d_g, rtmi_t
 int rtmi_tomo_lsqr(rtmi_tomo *t, const rtmi_lsqr_params *lp, const double smooth[2], const double *rhs, double *x, double *history,
                    rtmi_lsqr_stats *st);
 void rtmi_tomo_destroy(rtmi_tomo *t);
+
+/* Weighted, masked and warm-started LSQR on the device, for all four solvers above, and the illumination map of a Kirchhoff
+ * handle.  DESIGN.md section 26.
+ * rtmi_lsqr_options holds three host fp64 vectors, any of them NULL:
+ *   row_weight  wr [per], per the data's length (N nt; rows for the tomography solver): W = diag(wr)
+ *   col_scale   dc [nm], nm the model's length (nb ny nx; qy qx): D = diag(dc); dc[i] = 0 masks model value i
+ *   x0          [nm], the start model
+ * The solvers minimise |W A D y - W (b - A x0)|^2 + damp^2 |y|^2 over y by the loop of rtmi_kirchhoff_lsqr, and return
+ * x = x0 + D y.  damp acts on y, the scaled update, not on x.  Every product and every add is a separate fp64 operation, and a
+ * factor that is absent is left out, not multiplied by 1 (the rule c follows in the Kirchhoff contract):
+ *   right-hand side  with x0: r[i] = fl(b[i] - (A x0)[i]), one forward product of the operator as it is without options; without
+ *                    x0: r[i] = b[i].  Then u[i] = fl(wr[i] * r[i]).
+ *   forward          t = A s with s[i] = fl(dc[i] * v[i]), then t[i] = fl(wr[i] * t[i])
+ *   transposed       t = A^T s with s[i] = fl(wr[i] * u[i]), then t[i] = fl(dc[i] * t[i])
+ *   result           x[i] = fl(x0[i] + fl(dc[i] * y[i]))
+ * so that the updates read y[i] = fl(f[i] * t[i]) - fl(a * y[i]) with f the diagonal on that side.  The norms, the scalars, the
+ * stop tests, RTMI_LSQR_RANGE, the abandoned iteration and the history rows are rtmi_kirchhoff_lsqr's, word for word, of the
+ * weighted and scaled problem: the stop tests see that problem, r1norm is |W (b - A x)| when damp = 0 (with damp > 0 it is what
+ * scipy reports for the damped problem in y), anorm estimates |W A D|.  A model value with dc[i] = 0 comes back as x0[i]
+ * exactly, or as zero without x0.  Inside the iteration the weighting costs no pass more: the pass that scales u also writes
+ * fl(wr u) beside it, the pass that scales v also writes fl(dc v), and the two update passes read their diagonal; the call
+ * holds two more vectors per option given (wr and wr u; dc and dc v) and one for x0, all uploaded once and counted in
+ * bytes_device.
+ * rtmi_kirchhoff_lsqr_weighted: op selects the operator, and with it the handle rules, of one of the three entries above --
+ * RTMI_LSQR_OP_PLAIN rtmi_kirchhoff_lsqr (a handle with kmah is refused), RTMI_LSQR_OP_FULL rtmi_kirchhoff_lsqr_full,
+ * RTMI_LSQR_OP_FILTERED rtmi_kirchhoff_lsqr_filtered.  per = N nt, nm = nb ny nx.
+ * rtmi_tomo_lsqr_weighted: row_weight has `rows` values.  The smoothing rows lx Dx, ly Dy act on D y with a right-hand side of
+ * 0: they smooth the update, not the total model x0 + D y, and they carry no row weight.
+ * lo NULL, or all three pointers NULL, is the entry without options bit for bit: x, history, the norms and bytes_device; the
+ * loop then launches exactly the kernels it launches there.  A wr or dc of ones gives the x of no option: a product with 1.0
+ * is exact.  RTMI_ERR_ARG before any device work, naming the argument: everything the entry without options refuses; an op
+ * that is none of the three; a row_weight, col_scale or x0 value that is not finite.
+ *
+ * rtmi_kirchhoff_illumination: illum [nb][ny][nx] (host fp64; _dev: memory of the handle's device), on every kind of handle.
+ * For every pair (k, ks, kr, x) that migrate / migrate2 counts as contributing -- the same tau, f, j, a, c, b and the same rule,
+ * kmah's and pt's part of it included -- the term
+ *     fl(fl(c * c) * fl(fl(fl(1 - a) * fl(1 - a)) + fl(a * a)))
+ * is added into the sum of (b, x), which starts from +0.0, in migrate's order k, then ks, then kr.  One lane per node, no trace
+ * read and no atomics: the result is defined bit for bit and a plain loop reproduces it; a node that no pair reaches is +0.0.
+ * On a handle with one arrival per node and no anti-alias levels beyond level 0 this is diag(L^T L) exactly, the squared norm of
+ * the column of L of each model value: a pair puts c (1 - a) on sample j and c a on sample j + 1.  On a handle with kmah, with
+ * K > 1, with levels or with a filter set it is the same sum, and then an approximation of that diagonal which ignores the cross
+ * terms between the pairs of one trace that meet in a sample, the level filters, and H and F.  stats: kernel_ms, pairs and
+ * contributing as migrate reports them; scale_exp and upload_ms 0.  1 / sqrt(illum + eps max(illum)) is the usual col_scale.
+ * RTMI_ERR_ARG: a null handle or buffer; d_illum as rtmi_kirchhoff_migrate_dev checks d_image.
+ * Not covered: a second-order regulariser, conlim / var, smoothing of the total model rather than of the update, a
+ * preconditioner that is not diagonal, an illumination with the cross terms (the diagonal of the filtered operators). */
+#define RTMI_LSQR_OP_PLAIN 0
+#define RTMI_LSQR_OP_FULL 1
+#define RTMI_LSQR_OP_FILTERED 2
+typedef struct {
+    const double *row_weight;   /* [per] */
+    const double *col_scale;    /* [nm]  */
+    const double *x0;           /* [nm]  */
+    int64_t reserved[5];
+} rtmi_lsqr_options;
+int rtmi_kirchhoff_lsqr_weighted(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo, int32_t op,
+                                 const double *data, double *x, double *history, rtmi_lsqr_stats *st);
+int rtmi_tomo_lsqr_weighted(rtmi_tomo *t, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo, const double smooth[2],
+                            const double *rhs, double *x, double *history, rtmi_lsqr_stats *st);
+int rtmi_kirchhoff_illumination(rtmi_kirchhoff *k, double *illum, rtmi_kirchhoff_stats *st);          /* -> [nb][ny][nx] */
+int rtmi_kirchhoff_illumination_dev(rtmi_kirchhoff *k, double *d_illum, rtmi_kirchhoff_stats *st);
 
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */

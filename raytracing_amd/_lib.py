@@ -145,6 +145,11 @@ class LsqrStats(C.Structure):
                 ("bytes_device", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+class LsqrOptions(C.Structure):
+    """rtmi_lsqr_options: host fp64 vectors, any of them NULL"""
+    _fields_ = [("row_weight", _dp), ("col_scale", _dp), ("x0", _dp), ("reserved", C.c_int64 * 5)]
+
+
 class TomoStats(C.Structure):
     _fields_ = [("rows", C.c_int64), ("segments", C.c_int64), ("padded_segments", C.c_int64), ("bytes_device", C.c_int64),
                 ("atomics", C.c_int64), ("compile_ms", C.c_double), ("kernel_ms", C.c_double), ("vmax", C.c_double),
@@ -153,6 +158,7 @@ class TomoStats(C.Structure):
 
 TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
+LSQR_OP_PLAIN, LSQR_OP_FULL, LSQR_OP_FILTERED = 0, 1, 2     # RTMI_LSQR_OP_: rtmi_kirchhoff_lsqr_weighted's operator
 HILBERT_MAX_NT = 16384  # the longest trace rtmi_kirchhoff_hilbert takes: one copy of it in LDS
 FILTER_MAX_NT = 16384   # the longest trace and ...
 FILTER_MAX_TAPS = 2048  # ... the most taps rtmi_kirchhoff_set_filter takes: the trace and the filter's zeros in LDS
@@ -238,6 +244,12 @@ SYMBOLS = {
     "rtmi_tomo_transpose_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TomoStats)]),
     "rtmi_tomo_lsqr": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), _dp, _dp, _dp, _dp, C.POINTER(LsqrStats)]),
     "rtmi_tomo_destroy": (None, [C.c_void_p]),
+    "rtmi_kirchhoff_lsqr_weighted": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.c_int32, _dp, _dp, _dp,
+                                               C.POINTER(LsqrStats)]),
+    "rtmi_tomo_lsqr_weighted": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), _dp, _dp, _dp, _dp,
+                                          C.POINTER(LsqrStats)]),
+    "rtmi_kirchhoff_illumination": (C.c_int, [C.c_void_p, _dp, C.POINTER(KirchhoffStats)]),
+    "rtmi_kirchhoff_illumination_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(KirchhoffStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -1,7 +1,9 @@
 // kirchhoff.hip -- Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_create / _create_multi, _migrate /
-// _model / _migrate2 / _model2 and their _dev forms, _destroy): the diffraction-stack operator pair L^T (traces -> image, optionally
-// split into opening-angle bins) and L (reflectivity model -> traces), exact transposes of each other up to rounding.
-// include/rtmi.h states the operator; DESIGN.md section 14 the kernels and the fixed-point derivation.
+// _model / _migrate2 / _model2 and their _dev forms, _illumination / _illumination_dev, _destroy): the diffraction-stack operator
+// pair L^T (traces -> image, optionally split into opening-angle bins) and L (reflectivity model -> traces), exact transposes of
+// each other up to rounding.
+// include/rtmi.h states the operator; DESIGN.md section 14 the kernels and the fixed-point derivation; section 26 the illumination
+// map, k_illumination: the sum of the squared weights of L^T's contributing pairs per image value, k_migrate without its traces.
 //   L^T  one lane per image node, x fastest (table reads are coalesced).  The lane walks the traces in the caller's order and
 //        adds into an fp64 register (no bins) or into its own column of an LDS array [bin][lane]: no atomics, one fixed order.
 //        T, amp and theta of the source are kept while the source index does not change (a wave-uniform test).
@@ -135,6 +137,83 @@ __global__ void __launch_bounds__(256) k_migrate(KArgs A, const int8_t* __restri
             image[x] = sum;
     }
     block_count_to(counts, blockIdx.x, cnt);
+}
+
+// ------------------------------------------------------------------------------------------------------------ illumination
+// illum [nb][nn]: per (b, x) the sum over migrate's contributing pairs, in migrate's order, of (c c) ((1 - a)(1 - a) + a a): the
+// squared weights a pair puts on its two samples (rtmi.h).  k_migrate's lane layout, table reads and shot-ordered reuse of the
+// source's values, with no trace read: what is left is the table traffic.  kmah and pt only decide whether a pair contributes,
+// so they are wave-uniform pointer tests here, not template arguments: NULL on a handle without them.
+template <int K, bool AMP, bool BINS>
+__global__ void __launch_bounds__(256) k_illumination(KArgs A, const int8_t* __restrict__ kmah, const double* __restrict__ pt,
+                                                      double* __restrict__ illum, unsigned long long* __restrict__ counts) {
+    extern __shared__ double acc[];                           // BINS: [nb][blockDim.x]
+    constexpr int KK = K * K;
+    constexpr int kUnroll = K == 1 ? 4 : K == 2 ? 2 : 1;
+    const int tid = (int)threadIdx.x, BS = (int)blockDim.x;
+    const long x0 = (long)blockIdx.x * BS + tid;
+    const bool in = x0 < A.nn;
+    const long x = in ? x0 : A.nn - 1;                        // lanes past the image read its last node and store nothing
+    double sum = 0.0;
+    if (BINS)
+        for (int b = 0; b < A.nb; b++) acc[b * BS + tid] = 0.0;
+    unsigned long long cnt = 0;
+    int sprev = -1;
+    Arr<K> S;
+    double Sp[K];
+    // the values that only gate a pair: the caustic count (0 without kmah: valid) and pt (0.0 without pt: finite)
+    auto load_gates = [&](size_t at, Arr<K>& o, double (&p)[K]) {
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            const size_t q = at + (size_t)i * A.nn;
+            o.m[i] = kmah ? (int)kmah[q] : 0;
+            p[i] = pt ? pt[q] : 0.0;
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < K; i++) { S.T[i] = 0.0; S.A[i] = 0.0; S.H[i] = 0.0; S.m[i] = 0; Sp[i] = 0.0; }
+#pragma unroll kUnroll
+    for (long k = 0; k < A.N; k++) {
+        const int s = A.isrc[k], r = A.irec[k];
+        const double wk = A.w[k];
+        if (s != sprev) {                                     // wave-uniform, as in k_migrate
+            load_arr<K, AMP, BINS, false>(A, nullptr, (size_t)s * K * A.nn + x, S);
+            load_gates((size_t)s * K * A.nn + x, S, Sp);
+            sprev = s;
+        }
+        Arr<K> R;
+        double Rp[K];
+        load_arr<K, AMP, BINS, false>(A, nullptr, (size_t)r * K * A.nn + x, R);
+        load_gates((size_t)r * K * A.nn + x, R, Rp);
+#pragma unroll
+        for (int i = 0; i < KK; i++) {
+            const int ks = i / K, kr = i % K;
+            const Pair p = pair_of<AMP, BINS>(A, S.T[ks], R.T[kr], S.A[ks], R.A[kr], S.H[ks], R.H[kr], wk);
+            const bool ok = p.ok && (S.m[ks] | R.m[kr]) >= 0 && fabs(Sp[ks]) < INFINITY && fabs(Rp[kr]) < INFINITY;
+            const double om = 1.0 - p.a;
+            const double v = (p.c * p.c) * (om * om + p.a * p.a);
+            if (BINS) {
+                if (ok) acc[p.b * BS + tid] += v;
+            } else {
+                sum += ok ? v : 0.0;
+            }
+            cnt += (ok && in) ? 1ull : 0ull;
+        }
+    }
+    if (in) {
+        if (BINS)
+            for (int b = 0; b < A.nb; b++) illum[(size_t)b * A.nn + x] = acc[b * BS + tid];
+        else
+            illum[x] = sum;
+    }
+    block_count_to(counts, blockIdx.x, cnt);
+}
+
+template <int K> void launch_illumination(bool amp, bool bins, dim3 grid, dim3 blk, size_t lds, const KArgs& A, const int8_t* kmah,
+                                          const double* pt, double* illum, unsigned long long* counts) {
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, blk, lds, nullptr, A, kmah, pt, illum, counts); };
+    if (amp) { if (bins) go(k_illumination<K, true, true>); else go(k_illumination<K, true, false>); }
+    else     { if (bins) go(k_illumination<K, false, true>); else go(k_illumination<K, false, false>); }
 }
 
 // ------------------------------------------------------------------------------------------------------------ L
@@ -422,6 +501,59 @@ RTMI_EXPORT int rtmi_kirchhoff_model_dev(rtmi_kirchhoff* k, const double* d_mode
     if (two) RTMI_RC(check_device_pointer(k, who, d_data1, per, "d_data1"));
     RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, d_model, d_data0, d_data1, st, true));
     if (two && !k->kmah) RTMI_HIP(hipMemset(d_data1, 0, per)); // without kmah every pair is of channel 0
+    return RTMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ illumination
+namespace {
+
+// the kernel into d_illum [nb][nn], memory of the handle's device; st may be NULL
+int illumination_dev(rtmi_kirchhoff* k, const char* who, double* d_illum, rtmi_kirchhoff_stats* st) {
+    const int BS = migrate_block(k->nb);
+    const dim3 grid((unsigned)((k->nn + BS - 1) / BS)), blk(BS);
+    const bool amp = k->amp != nullptr, bins = k->kp.nbin > 0;
+    const size_t lds = bins ? (size_t)k->nb * BS * sizeof(double) : 0;
+    const KArgs A = k->args();
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    RTMI_HIP(ev.mark(0));
+    switch (k->karr) {
+        case 0:
+        case 1: launch_illumination<1>(amp, bins, grid, blk, lds, A, k->kmah, k->pt, d_illum, k->counts); break;
+        case 2: launch_illumination<2>(amp, bins, grid, blk, lds, A, k->kmah, k->pt, d_illum, k->counts); break;
+        case 3: launch_illumination<3>(amp, bins, grid, blk, lds, A, k->kmah, k->pt, d_illum, k->counts); break;
+        default: launch_illumination<4>(amp, bins, grid, blk, lds, A, k->kmah, k->pt, d_illum, k->counts); break;
+    }
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(ev.mark(1));
+    RTMI_HIP(ev.wait(1));
+    if (st) {
+        *st = rtmi_kirchhoff_stats{};
+        RTMI_HIP(ev.ms(0, 1, &st->kernel_ms));
+        st->pairs = (int64_t)((size_t)k->kp.N * k->nn) * (k->karr ? k->karr * k->karr : 1);
+        RTMI_RC(read_counts(k, grid.x, &st->contributing, who));
+    }
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_kirchhoff_illumination_dev(rtmi_kirchhoff* k, double* d_illum, rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_illumination_dev";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(d_illum, "null d_illum");
+    RTMI_RC(check_device(k, who));
+    RTMI_RC(check_device_pointer(k, who, d_illum, (size_t)k->nb * k->nn * sizeof(double), "d_illum"));
+    return illumination_dev(k, who, d_illum, st);
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_illumination(rtmi_kirchhoff* k, double* illum, rtmi_kirchhoff_stats* st) {
+    const char* who = "rtmi_kirchhoff_illumination";
+    RTMI_ARG(k, "null handle");
+    RTMI_ARG(illum, "null illum");
+    RTMI_RC(check_device(k, who));
+    RTMI_RC(illumination_dev(k, who, k->image, st));
+    RTMI_HIP(hipMemcpy(illum, k->image, (size_t)k->nb * k->nn * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

@@ -1,5 +1,5 @@
 // kirchhoff_lsqr.hip -- least-squares Kirchhoff migration that stays on the device (rtmi_kirchhoff_lsqr, rtmi_kirchhoff_lsqr_full,
-// rtmi_debug_fix_norm):
+// rtmi_kirchhoff_lsqr_filtered, rtmi_kirchhoff_lsqr_weighted, rtmi_debug_fix_norm):
 // LSQR over the pair of kirchhoff.hip / kirchhoff_aa.hip on device pointers, every vector on the device from the one upload of the
 // data to the one download of the model.  include/rtmi.h states the contract; DESIGN.md section 21 the definitions, the memory and
 // what was measured; rt_lsqr.h the scalar recurrence (host, scipy's operation order).  _lsqr_full on a handle with kmah solves
@@ -16,9 +16,10 @@ namespace {
 // model2(x), and A^T u = migrate2(u, -H u), its transpose in every bit; on any other handle `full` changes nothing.  filtered
 // (with full): on a handle with a filter set, with B that operator, A x = F (B x) and A^T u = B^T (F^T u); F is out of place, so
 // the call holds one more N nt vector, Fb, for B v and for F^T u, which are never live together.  With no filter set `filtered`
-// changes nothing.
-int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
-             rtmi_lsqr_stats* st) {
+// changes nothing.  lo: the options of rtmi_kirchhoff_lsqr_weighted, uploaded once; NULL, or every pointer of
+// it NULL, allocates nothing and runs the loop as it ran before there were options.
+int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+             const double* data, double* x, double* history, rtmi_lsqr_stats* st) {
     RTMI_ARG(k, "null handle");
     RTMI_ARG(lp, "null params");
     RTMI_ARG(data, "null data");
@@ -29,6 +30,7 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
     if (hil) RTMI_RC(rtmi_internal_kirchhoff_hilbert_check(k, who));
     const size_t per = (size_t)k->kp.N * (size_t)k->kp.nt, nm = (size_t)k->nb * k->nn;
     for (size_t i = 0; i < per; i++) RTMI_ARG(std::isfinite(data[i]), "data has a value that is not finite");
+    RTMI_RC(lsqr_check_options(who, lo, per, nm));
     RTMI_RC(check_device(k, who));
     const double t_begin = now_ms();
     DevMem mem;
@@ -41,12 +43,15 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
         if (a.wanted && mem.get(a.p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
     for (double** p : {&v, &w, &xd, &Atu})
         if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    LsqrOptions O;
+    size_t nopt = 0;
+    RTMI_RC(lsqr_upload_options(who, mem, lo, per, per, nm, &O, &nopt));
     const Vec V{k->red, k->cus};
     rtmi_lsqr_stats out{};
     // the call's vectors, the handle's staging (with kmah: two channels per level) and, with hil and with fil, their taps
     const size_t staging = (size_t)(k->nlev ? k->nlev : 1) * (k->kmah ? 2 : 1) * per + nm;
     const size_t ntaps = (hil ? (size_t)rt::hilbert_ntaps(k->kp.nt) : 0) + (fil ? (size_t)k->fL : 0);
-    out.bytes_device = (int64_t)(((hil ? 4 : 2) * per + (fil ? per : 0) + 4 * nm + staging + ntaps) * sizeof(double) +
+    out.bytes_device = (int64_t)(((hil ? 4 : 2) * per + (fil ? per : 0) + 4 * nm + nopt + staging + ntaps) * sizeof(double) +
                                  (k->ncounts + kRedWords) * sizeof(unsigned long long));
     double operator_ms = 0.0;
     rtmi_kirchhoff_stats ks{};
@@ -75,7 +80,7 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
 
     RTMI_HIP(hipMemcpy(u, data, per * sizeof(double), hipMemcpyHostToDevice));       // the data go up once
     RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
-    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out));
+    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out, O));
     RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));           // the model comes down once
     out.total_ms = now_ms() - t_begin;
     out.operator_ms = operator_ms;
@@ -87,17 +92,24 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
 
 RTMI_EXPORT int rtmi_kirchhoff_lsqr(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
                                     rtmi_lsqr_stats* st) {
-    return lsqr_run("rtmi_kirchhoff_lsqr", false, false, k, lp, data, x, history, st);
+    return lsqr_run("rtmi_kirchhoff_lsqr", false, false, k, lp, nullptr, data, x, history, st);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_lsqr_full(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x, double* history,
                                          rtmi_lsqr_stats* st) {
-    return lsqr_run("rtmi_kirchhoff_lsqr_full", true, false, k, lp, data, x, history, st);
+    return lsqr_run("rtmi_kirchhoff_lsqr_full", true, false, k, lp, nullptr, data, x, history, st);
 }
 
 RTMI_EXPORT int rtmi_kirchhoff_lsqr_filtered(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const double* data, double* x,
                                              double* history, rtmi_lsqr_stats* st) {
-    return lsqr_run("rtmi_kirchhoff_lsqr_filtered", true, true, k, lp, data, x, history, st);
+    return lsqr_run("rtmi_kirchhoff_lsqr_filtered", true, true, k, lp, nullptr, data, x, history, st);
+}
+
+RTMI_EXPORT int rtmi_kirchhoff_lsqr_weighted(rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, int32_t op,
+                                             const double* data, double* x, double* history, rtmi_lsqr_stats* st) {
+    const char* who = "rtmi_kirchhoff_lsqr_weighted";
+    RTMI_ARG(op == RTMI_LSQR_OP_PLAIN || op == RTMI_LSQR_OP_FULL || op == RTMI_LSQR_OP_FILTERED, "op must be one of RTMI_LSQR_OP_");
+    return lsqr_run(who, op != RTMI_LSQR_OP_PLAIN, op == RTMI_LSQR_OP_FILTERED, k, lp, lo, data, x, history, st);
 }
 
 RTMI_EXPORT int rtmi_debug_fix_norm(const double* x, int64_t n, double* norm, int32_t* e) {

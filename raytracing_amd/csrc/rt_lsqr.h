@@ -12,7 +12,8 @@
 // Included: _sym_ortho, the damp rotation, rhobar, phibar, theta, phi, rho, the right rotation z, xxnorm that r1norm needs under
 // damping, r1norm, r2norm, anorm, arnorm, the stop tests 1, 2 and 7 and the early returns.  xnorm enters test 1 as in scipy (it
 // comes from scalars alone) but is not reported.  Left out: conlim / acond and var (a vector norm more per iteration), the tests
-// 3 to 6 (acond, and the machine-precision guards), x0, show.
+// 3 to 6 (acond, and the machine-precision guards), show.  Row weights, a column scale and x0 need no scalar of their own: the
+// loop around these half-steps applies them to the vectors (rt_lsqr_device.h, LsqrOptions).
 #pragma once
 #include <cmath>
 

@@ -6,6 +6,8 @@
 // every pointer of the pass is 16-byte aligned (`wide`; the solvers' own allocations always are).
 //   k_axmy_absmax  y_i = t_i - fl(a y_i), and max |y_i| of the new y in the same pass (block_max_to)
 //   k_scale        y_i = fl(s y_i)
+//   k_axmy_absmax_f, k_scale_copy   the same two passes of the weighted loop (LsqrOptions): y_i = fl(f_i t_i) - fl(a y_i), and
+//                  y_i = fl(s y_i) with z_i = fl(f_i y_i) written beside it, the copy the next operator call reads
 //   k_xw           x_i = x_i + fl(c1 w_i) and w_i = v_i - fl(c2 w_i)
 //   k_sumsq        the norm's integer sum: S += rint(ldexp(fl(x_i x_i), -e)), a two-word sum with an explicit carry per lane, per
 //                  wave and per block, then one two-word atomic add per block into one global pair.  Integer sums commute: the
@@ -65,6 +67,65 @@ __global__ void __launch_bounds__(256) k_scale(double* __restrict__ y, double s,
               ((double2*)y)[i] = make_double2(__dmul_rn(s, v.x), __dmul_rn(s, v.y));
           },
           [&](long i) { y[i] = __dmul_rn(s, y[i]); });
+}
+
+// The two passes of the weighted loop (LsqrOptions below).  f is the diagonal the operator's result is multiplied by: the row
+// weights on A's side, the column scale on A^T's.
+__global__ void __launch_bounds__(256) k_axmy_absmax_f(double* __restrict__ y, const double* __restrict__ t, const double* __restrict__ f,
+                                                       double a, long n, bool wide, unsigned long long* __restrict__ out) {
+    double m = 0.0;
+    sweep(n, wide,
+          [&](long i) {
+              const double2 yv = ((const double2*)y)[i], tv = ((const double2*)t)[i], fv = ((const double2*)f)[i];
+              const double2 r = make_double2(axmy(__dmul_rn(fv.x, tv.x), a, yv.x), axmy(__dmul_rn(fv.y, tv.y), a, yv.y));
+              ((double2*)y)[i] = r;
+              m = fmax(m, fmax(fabs(r.x), fabs(r.y)));
+          },
+          [&](long i) {
+              const double r = axmy(__dmul_rn(f[i], t[i]), a, y[i]);
+              y[i] = r;
+              m = fmax(m, fabs(r));
+          });
+    block_max_to(out, m);
+}
+
+// y_i = fl(s y_i) and z_i = fl(f_i y_i) of the new y
+__global__ void __launch_bounds__(256) k_scale_copy(double* __restrict__ y, double* __restrict__ z, const double* __restrict__ f, double s,
+                                                    long n, bool wide) {
+    sweep(n, wide,
+          [&](long i) {
+              const double2 v = ((const double2*)y)[i], fv = ((const double2*)f)[i];
+              const double2 r = make_double2(__dmul_rn(s, v.x), __dmul_rn(s, v.y));
+              ((double2*)y)[i] = r;
+              ((double2*)z)[i] = make_double2(__dmul_rn(fv.x, r.x), __dmul_rn(fv.y, r.y));
+          },
+          [&](long i) {
+              const double r = __dmul_rn(s, y[i]);
+              y[i] = r;
+              z[i] = __dmul_rn(f[i], r);
+          });
+}
+
+// What the weighted loop runs once, outside the iteration: y_i = fl(y_i - t_i) (t given), then y_i = fl(f_i y_i) (f given) ...
+__global__ void __launch_bounds__(256) k_sub_mul(double* __restrict__ y, const double* __restrict__ t, const double* __restrict__ f, long n) {
+    sweep(n, false, [](long) {},
+          [&](long i) {
+              double r = y[i];
+              if (t) r = __dadd_rn(r, -t[i]);
+              if (f) r = __dmul_rn(f[i], r);
+              y[i] = r;
+          });
+}
+
+// ... and the result: x_i = fl(x0_i + fl(dc_i x_i)), an absent factor left out
+__global__ void __launch_bounds__(256) k_result(double* __restrict__ x, const double* __restrict__ dc, const double* __restrict__ x0, long n) {
+    sweep(n, false, [](long) {},
+          [&](long i) {
+              double r = x[i];
+              if (dc) r = __dmul_rn(dc[i], r);
+              if (x0) r = __dadd_rn(x0[i], r);
+              x[i] = r;
+          });
 }
 
 __global__ void __launch_bounds__(256) k_xw(double* __restrict__ x, double* __restrict__ w, const double* __restrict__ v, double c1,
@@ -157,10 +218,14 @@ int norm_of(const char* who, const Vec& V, const double* d, size_t n, double M, 
     return RTMI_OK;
 }
 
-// y = t - a y, then the norm of the new y
-int axmy_norm(const char* who, const Vec& V, double* y, const double* t, double a, size_t n, double* norm, bool* range) {
+// y = t - a y, or with f: y = f t - a y, then the norm of the new y
+int axmy_norm(const char* who, const Vec& V, double* y, const double* t, const double* f, double a, size_t n, double* norm, bool* range) {
     RTMI_HIP(hipMemsetAsync(V.red + 1, 0, sizeof(unsigned long long), nullptr));
-    hipLaunchKernelGGL(k_axmy_absmax, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, t, a, (long)n, aligned16(y) && aligned16(t), V.red + 1);
+    if (f)
+        hipLaunchKernelGGL(k_axmy_absmax_f, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, t, f, a, (long)n,
+                           aligned16(y) && aligned16(t) && aligned16(f), V.red + 1);
+    else
+        hipLaunchKernelGGL(k_axmy_absmax, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, t, a, (long)n, aligned16(y) && aligned16(t), V.red + 1);
     RTMI_HIP(hipGetLastError());
     double M = 0.0;
     RTMI_HIP(hipMemcpy(&M, V.red + 1, sizeof(double), hipMemcpyDeviceToHost));
@@ -168,8 +233,13 @@ int axmy_norm(const char* who, const Vec& V, double* y, const double* t, double 
     return norm_of(who, V, y, n, M, norm, &e, range);
 }
 
-int scale(const char* who, const Vec& V, double* y, double s, size_t n) {
-    hipLaunchKernelGGL(k_scale, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, s, (long)n, aligned16(y));
+// y = s y; with f also z = f y of the new y
+int scale(const char* who, const Vec& V, double* y, double s, size_t n, double* z = nullptr, const double* f = nullptr) {
+    if (f)
+        hipLaunchKernelGGL(k_scale_copy, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, z, f, s, (long)n,
+                           aligned16(y) && aligned16(z) && aligned16(f));
+    else
+        hipLaunchKernelGGL(k_scale, stride_blocks(V.cus, n, 2), dim3(256), 0, nullptr, y, s, (long)n, aligned16(y));
     RTMI_HIP(hipGetLastError());
     return RTMI_OK;
 }
@@ -189,14 +259,80 @@ struct LsqrVectors {
     double *u, *Av, *v, *w, *x, *Atu;
 };
 
+// The options of a weighted solve, on the device (include/rtmi.h, rtmi_lsqr_options): the row weights wr
+// [per], the column scale dc [nm] and the start model x0 [nm], any of them NULL, and beside them the two vectors the weighting
+// costs: uw = wr u [per] with wr, vd = dc v [nm] with dc, which the fused passes write and the operator calls read.  nrhs: the
+// leading values of u that are data (A x0 is subtracted from them; rows after them, a regulariser's, keep a right-hand side of 0).
+struct LsqrOptions {
+    const double *wr = nullptr, *dc = nullptr, *x0 = nullptr;
+    double *uw = nullptr, *vd = nullptr;
+    size_t nrhs = 0;
+    bool any() const { return wr || dc || x0; }
+};
+
+// The rule for the caller's options, before any device work: finite values.  nwr: the values row_weight has.
+int lsqr_check_options(const char* who, const rtmi_lsqr_options* lo, size_t nwr, size_t nm) {
+    if (!lo) return RTMI_OK;
+    if (lo->row_weight)
+        for (size_t i = 0; i < nwr; i++) RTMI_ARG(std::isfinite(lo->row_weight[i]), "row_weight has a value that is not finite");
+    if (lo->col_scale)
+        for (size_t i = 0; i < nm; i++) RTMI_ARG(std::isfinite(lo->col_scale[i]), "col_scale has a value that is not finite");
+    if (lo->x0)
+        for (size_t i = 0; i < nm; i++) RTMI_ARG(std::isfinite(lo->x0[i]), "x0 has a value that is not finite");
+    return RTMI_OK;
+}
+
+// The one upload of the options into memory of `mem`, and the vectors beside them.  Rows nwr .. per - 1 carry no weight: their
+// factor is 1.0, and a product with 1.0 changes no bit.  *doubles: what was allocated, for bytes_device.
+int lsqr_upload_options(const char* who, DevMem& mem, const rtmi_lsqr_options* lo, size_t nwr, size_t per, size_t nm, LsqrOptions* O,
+                        size_t* doubles) {
+    *O = LsqrOptions{};
+    *doubles = 0;
+    O->nrhs = nwr;
+    if (!lo) return RTMI_OK;
+    const std::string no_mem = std::string(who) + ": hipMalloc failed";
+    auto up = [&](const double* src, size_t n, size_t total, const double** dst) {
+        double* d = nullptr;
+        if (mem.get(&d, total * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(d, src, n * sizeof(double), hipMemcpyHostToDevice));
+        if (total > n) {
+            const std::vector<double> ones(total - n, 1.0);
+            RTMI_HIP(hipMemcpy(d + n, ones.data(), (total - n) * sizeof(double), hipMemcpyHostToDevice));
+        }
+        *dst = d;
+        *doubles += total;
+        return (int)RTMI_OK;
+    };
+    if (lo->row_weight) {
+        RTMI_RC(up(lo->row_weight, nwr, per, &O->wr));
+        if (mem.get(&O->uw, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        *doubles += per;
+    }
+    if (lo->col_scale) {
+        RTMI_RC(up(lo->col_scale, nm, nm, &O->dc));
+        if (mem.get(&O->vd, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        *doubles += nm;
+    }
+    if (lo->x0) RTMI_RC(up(lo->x0, nm, nm, &O->x0));
+    return RTMI_OK;
+}
+
 // The loop of both solvers, from u = the right-hand side and x = 0, both on the device already, to x on the device.
 // Ax(s, t): t = A s, s of nm and t of per values; At(s, t, &range): t = A^T s, which may report that a bound of its own left
 // fp64's normal range (range = true: it is treated as a norm out of range).  Both return an RTMI_ code.  Fills out's istop, itn,
 // the four norms and vector_ms; history [iter_lim][4] may be NULL.
+// With options O the loop is that of the operator W A D on the right-hand side W (b - A x0), and x = x0 + D y at the end:
+//   before   u = fl(wr fl(u - A x0)) over the data rows, one forward product and one pass
+//   A        reads vd = fl(dc v), which the pass that scales v wrote beside it; its result enters u = fl(wr t) - fl(alfa u)
+//   A^T      reads uw = fl(wr u), which the pass that scales u wrote beside it; its result enters v = fl(dc t) - fl(beta v)
+//   after    x = fl(x0 + fl(dc x)), one pass
+// so an iteration has the passes it had, each reading one vector more (the diagonal) or writing one more (the copy).  An absent
+// option is left out, not multiplied by 1: with none of them the loop launches exactly the kernels it launched without options.
 template <typename AX, typename AT>
 int lsqr_loop(const char* who, const Vec& V, const rtmi_lsqr_params* lp, size_t per, size_t nm, const LsqrVectors& B, AX&& Ax, AT&& At,
-              double* history, rtmi_lsqr_stats* out) {
+              double* history, rtmi_lsqr_stats* out, const LsqrOptions& O = LsqrOptions{}) {
     double *const u = B.u, *const Av = B.Av, *const v = B.v, *const w = B.w, *const xd = B.x, *const Atu = B.Atu;
+    const double *const uin = O.wr ? O.uw : u, *const vin = O.dc ? O.vd : v;          // what A^T and A read
     double vector_ms = 0.0;
     rt::LsqrState S;
     rt::lsqr_begin(S, lp->damp, lp->atol, lp->btol, lp->iter_lim);
@@ -211,24 +347,37 @@ int lsqr_loop(const char* who, const Vec& V, const rtmi_lsqr_params* lp, size_t 
         vector_ms += now_ms() - t_sec;
         return r;
     };
+    auto sub_mul = [&](double* y, const double* t, const double* f, size_t n) {
+        hipLaunchKernelGGL(k_sub_mul, stride_blocks(V.cus, n, 1), dim3(256), 0, nullptr, y, t, f, (long)n);
+        RTMI_HIP(hipGetLastError());
+        return (int)RTMI_OK;
+    };
 
+    if (O.x0) RTMI_RC(Ax(O.x0, Av));                                                 // the residual of the start model
     sec_begin();
+    if (O.x0 && O.wr && O.nrhs == per) {
+        RTMI_RC(sub_mul(u, Av, O.wr, per));                                          // both in one pass: the same two roundings
+    } else {
+        if (O.x0) RTMI_RC(sub_mul(u, Av, nullptr, O.nrhs));
+        if (O.wr) RTMI_RC(sub_mul(u, nullptr, O.wr, per));
+    }
     RTMI_RC(rtmi_internal_absmax_finite(who, V.red, V.cus, u, per, &M));
     RTMI_RC(norm_of(who, V, u, per, M, &nrm, &e, &range));
     bool go = !range && rt::lsqr_first_beta(S, nrm);
-    if (go) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per));
+    if (go) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per, O.uw, O.wr));
     RTMI_HIP(sec_end());
     if (go) {
-        RTMI_RC(At(u, v, &range));
+        RTMI_RC(At(uin, v, &range));
         go = !range;
     }
     if (go) {
         sec_begin();
+        if (O.dc) RTMI_RC(sub_mul(v, nullptr, O.dc, nm));
         RTMI_RC(rtmi_internal_absmax_finite(who, V.red, V.cus, v, nm, &M));
         RTMI_RC(norm_of(who, V, v, nm, M, &nrm, &e, &range));
         go = !range && rt::lsqr_first_alfa(S, nrm);
         if (go) {
-            RTMI_RC(scale(who, V, v, 1.0 / S.alfa, nm));
+            RTMI_RC(scale(who, V, v, 1.0 / S.alfa, nm, O.vd, O.dc));
             RTMI_HIP(hipMemcpyAsync(w, v, nm * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
         }
         RTMI_HIP(sec_end());
@@ -237,30 +386,32 @@ int lsqr_loop(const char* who, const Vec& V, const rtmi_lsqr_params* lp, size_t 
     // the last iteration that was completed.
     while (go && !rt::lsqr_done(S)) {
         const rt::LsqrState S0 = S;
-        RTMI_RC(Ax(v, Av));
+        RTMI_RC(Ax(vin, Av));
         sec_begin();
-        RTMI_RC(axmy_norm(who, V, u, Av, S.alfa, per, &nrm, &range));                // u = A v - alfa u
+        RTMI_RC(axmy_norm(who, V, u, Av, O.wr, S.alfa, per, &nrm, &range));          // u = A v - alfa u
         if (range) {
             RTMI_HIP(sec_end());
             break;
         }
         const bool stepped = rt::lsqr_beta(S, nrm);
-        if (stepped) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per));
+        if (stepped) RTMI_RC(scale(who, V, u, 1.0 / S.beta, per, O.uw, O.wr));
         RTMI_HIP(sec_end());
         if (stepped) {
-            RTMI_RC(At(u, Atu, &range));
+            RTMI_RC(At(uin, Atu, &range));
             if (range) {
                 S = S0;
                 break;
             }
             sec_begin();
-            RTMI_RC(axmy_norm(who, V, v, Atu, S.beta, nm, &nrm, &range));            // v = A^T u - beta v
+            RTMI_RC(axmy_norm(who, V, v, Atu, O.dc, S.beta, nm, &nrm, &range));      // v = A^T u - beta v
             if (range) {
                 RTMI_HIP(sec_end());
                 S = S0;
                 break;
             }
-            if (rt::lsqr_alfa(S, nrm)) RTMI_RC(scale(who, V, v, 1.0 / S.alfa, nm));
+            // a v that is not scaled (alfa = 0: v is zero) still needs its copy: a factor 1.0 changes no bit of v
+            if (rt::lsqr_alfa(S, nrm)) RTMI_RC(scale(who, V, v, 1.0 / S.alfa, nm, O.vd, O.dc));
+            else if (O.dc) RTMI_RC(scale(who, V, v, 1.0, nm, O.vd, O.dc));
             RTMI_HIP(sec_end());
         }
         rt::lsqr_rotate(S);
@@ -273,6 +424,12 @@ int lsqr_loop(const char* who, const Vec& V, const rtmi_lsqr_params* lp, size_t 
             double* row = history + (size_t)(S.itn - 1) * 4;
             row[0] = S.alfa; row[1] = S.beta; row[2] = S.r1norm; row[3] = S.arnorm;
         }
+    }
+    if (O.dc || O.x0) {
+        sec_begin();
+        hipLaunchKernelGGL(k_result, stride_blocks(V.cus, nm, 1), dim3(256), 0, nullptr, xd, O.dc, O.x0, (long)nm);
+        RTMI_HIP(hipGetLastError());
+        RTMI_HIP(sec_end());
     }
     out->istop = range ? rt::kLsqrRange : S.istop;
     out->itn = S.itn;

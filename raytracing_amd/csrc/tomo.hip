@@ -1,6 +1,6 @@
 // tomo.hip -- recorded rays compiled into a sparse ray-tomography matrix that lives on the device (rtmi_tomo_create, _append,
-// _read, _info, _apply, _transpose, their _dev forms, rtmi_tomo_lsqr, _destroy).  include/rtmi.h states the contract; DESIGN.md
-// section 24 the definitions, the error bound and what was measured.
+// _read, _info, _apply, _transpose, their _dev forms, rtmi_tomo_lsqr, rtmi_tomo_lsqr_weighted, _destroy).  include/rtmi.h states
+// the contract; DESIGN.md section 24 the definitions, the error bound and what was measured; section 26 the weighted solver.
 //
 // A row of the matrix is one reported traveltime's derivative with respect to the field's samples; it is a list of segments, one
 // per cell visit of its ray: the cell's first sample `base` and four weights p[q].  rtmi_tomo_append walks a batch's rows with
@@ -640,9 +640,12 @@ RTMI_EXPORT int rtmi_tomo_transpose(rtmi_tomo* t, const double* w, double* g, rt
     return RTMI_OK;
 }
 
-RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const double smooth[2], const double* rhs, double* x,
-                               double* history, rtmi_lsqr_stats* st) {
-    const char* who = "rtmi_tomo_lsqr";
+namespace {
+
+// Both solvers' body.  lo: the options of rtmi_tomo_lsqr_weighted, uploaded once; NULL, or every pointer of it NULL, allocates
+// nothing and runs the loop as it ran before there were options.
+int tomo_lsqr_run(const char* who, rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
+                  const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
     RTMI_ARG(t, "null handle");
     RTMI_ARG(lp, "null params");
     RTMI_ARG(rhs, "null rhs");
@@ -653,6 +656,7 @@ RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const d
                  "smooth must be finite and >= 0");
     RTMI_ARG(t->rows >= 1, "the handle has no rows");
     RTMI_RC(finite_all(who, rhs, (size_t)t->rows, "rhs has a value that is not finite"));
+    RTMI_RC(lsqr_check_options(who, lo, (size_t)t->rows, t->nz()));
     RTMI_RC(on_device(t, who));
     const double t_begin = now_ms();
     const size_t rows = (size_t)t->rows, nm = t->nz(), qx = (size_t)t->F.qx, qy = (size_t)t->F.qy;
@@ -662,12 +666,16 @@ RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const d
     DevMem mem;
     double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr;
     for (double** p : {&u, &Av})
-        if (mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_tomo_lsqr: hipMalloc failed");
+        if (mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc failed").c_str());
     for (double** p : {&v, &w, &xd, &Atu})
-        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_tomo_lsqr: hipMalloc failed");
+        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc failed").c_str());
+    // the row weights cover the `rows` observations; the smoothing rows carry none
+    LsqrOptions O;
+    size_t nopt = 0;
+    RTMI_RC(lsqr_upload_options(who, mem, lo, rows, per, nm, &O, &nopt));
     const Vec V{t->red, t->cus};
     rtmi_lsqr_stats out{};
-    out.bytes_device = (int64_t)((2 * per + 4 * nm) * sizeof(double) + t->bytes());
+    out.bytes_device = (int64_t)((2 * per + 4 * nm + nopt) * sizeof(double) + t->bytes());
     double operator_ms = 0.0;
     // the stacked operator: t = [A s | Dx s | Dy s], and its transpose
     auto Ax = [&](const double* s, double* y) {
@@ -691,10 +699,22 @@ RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const d
     RTMI_HIP(hipMemcpy(u, rhs, rows * sizeof(double), hipMemcpyHostToDevice));        // the right-hand side goes up once
     if (per > rows) RTMI_HIP(hipMemsetAsync(u + rows, 0, (per - rows) * sizeof(double), nullptr));
     RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
-    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out));
+    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out, O));
     RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));           // the model comes down once
     out.total_ms = now_ms() - t_begin;
     out.operator_ms = operator_ms;
     if (st) *st = out;
     return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const double smooth[2], const double* rhs, double* x,
+                               double* history, rtmi_lsqr_stats* st) {
+    return tomo_lsqr_run("rtmi_tomo_lsqr", t, lp, nullptr, smooth, rhs, x, history, st);
+}
+
+RTMI_EXPORT int rtmi_tomo_lsqr_weighted(rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
+                                        const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
+    return tomo_lsqr_run("rtmi_tomo_lsqr_weighted", t, lp, lo, smooth, rhs, x, history, st);
 }

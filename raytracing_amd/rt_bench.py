@@ -980,9 +980,16 @@ class Tomography:
         check(lib().rtmi_tomo_transpose_dev(self._open(), w.data_ptr(), g.data_ptr(), C.byref(st)))
         return (g, tomo_stats(st)) if stats else g
 
-    def lsqr(self, rhs, damp=0.0, smooth=None, iter_lim=30, atol=0.0, btol=0.0, history=False, stats=False):
+    def coverage(self):
+        """A^T of a vector of ones, [qy, qx]: 0 where no ray passes -- for a mask (coverage() != 0) or a column scale"""
+        return self.rmatvec(np.ones(self.info()["rows"]))
+
+    def lsqr(self, rhs, damp=0.0, smooth=None, iter_lim=30, atol=0.0, btol=0.0, history=False, stats=False, row_weight=None,
+             col_scale=None, x0=None):
         """rtmi_tomo_lsqr: min |A x - rhs|^2 + damp^2 |x|^2 + lx^2 |Dx x|^2 + ly^2 |Dy x|^2 from x = 0, smooth = (lx, ly) or None,
-        every vector on the device.  -> the dict of Kirchhoff.lsqr with x [qy, qx]."""
+        every vector on the device.  -> the dict of Kirchhoff.lsqr with x [qy, qx].  row_weight [rows], col_scale and x0 [qy, qx]:
+        rtmi_tomo_lsqr_weighted, min |W A D y - W (rhs - A x0)|^2 + damp^2 |y|^2 + the smoothing terms of D y, and x = x0 + D y; a
+        col_scale of 0 freezes a sample at x0's value."""
         rr = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
         if rr.size != self.info()["rows"]:
             raise ValueError(f"Tomography.lsqr: rhs must have {self.info()['rows']} values")
@@ -997,7 +1004,11 @@ class Tomography:
         x = np.empty((self.qy, self.qx))
         hist = np.zeros((iter_lim, 4)) if history else None
         st = _lib.LsqrStats()
-        check(lib().rtmi_tomo_lsqr(self._open(), C.byref(lp), dptr(sm), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
+        if row_weight is None and col_scale is None and x0 is None:
+            check(lib().rtmi_tomo_lsqr(self._open(), C.byref(lp), dptr(sm), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
+        else:
+            lo, keep = _lsqr_options("Tomography.lsqr", rr.size, self.qy * self.qx, row_weight, col_scale, x0)
+            check(lib().rtmi_tomo_lsqr_weighted(self._open(), C.byref(lp), C.byref(lo), dptr(sm), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
         out = {"x": x, "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm, "anorm": st.anorm,
                "arnorm": st.arnorm}
         if history:
@@ -1420,6 +1431,31 @@ def half_derivative_taps(L, dt):
     return taps[:L]
 
 
+def illumination_scale(illum, eps=1e-3):
+    """The column scale of an illumination map: 1 / sqrt(illum + eps max(illum)), and 0 (a masked value) where illum is 0"""
+    ill = np.asarray(illum, dtype=np.float64)
+    top = float(ill.max()) if ill.size else 0.0
+    out = np.zeros_like(ill)
+    lit = ill > 0.0
+    out[lit] = 1.0 / np.sqrt(ill[lit] + float(eps) * top)
+    return out
+
+
+def _lsqr_options(who, per, nm, row_weight, col_scale, x0):
+    """-> (rtmi_lsqr_options, the arrays it points into, which the caller keeps alive over the call)"""
+    lo = _lib.LsqrOptions()
+    keep = []
+    for field, a, n in (("row_weight", row_weight, per), ("col_scale", col_scale, nm), ("x0", x0, nm)):
+        if a is None:
+            continue
+        aa = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if aa.size != n:
+            raise ValueError(f"{who}: {field} must have {n} values")
+        keep.append(aa)
+        setattr(lo, field, dptr(aa))
+    return lo, keep
+
+
 class Kirchhoff:
     """Kirchhoff migration and modelling from traveltime tables (rtmi_kirchhoff_*, include/rtmi.h).  T [P, ny, nx]:
     traveltime_table's T for P surface positions; isrc, irec [N]: each trace's source and receiver position in [0, P); nt samples
@@ -1719,7 +1755,31 @@ class Kirchhoff:
         check(lib().rtmi_kirchhoff_filter_dev(h, x.data_ptr(), 1 if transpose else 0, y.data_ptr()))
         return y
 
-    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False, hilbert=None, filtered=False):
+    def illumination(self, stats=False):
+        """rtmi_kirchhoff_illumination: per image value the sum over migrate's contributing pairs of c^2 ((1 - a)^2 + a^2), shaped
+        like migrate's image; diag(L^T L) exactly on a handle with one arrival and no anti-alias levels, else that diagonal
+        without the cross terms, the level filters, H and F"""
+        ill = np.empty((self.nb, self.ny, self.nx))
+        st = _lib.KirchhoffStats()
+        check(lib().rtmi_kirchhoff_illumination(self._open(), dptr(ill), C.byref(st)))
+        if self.nbin == 0:
+            ill = ill[0]
+        return (ill, kirchhoff_stats(st)) if stats else ill
+
+    def illumination_device(self, stats=False):
+        """rtmi_kirchhoff_illumination_dev: illumination() into a new torch tensor on the current GPU, which must be the handle's"""
+        import torch
+        h = self._open()
+        ill = torch.empty((self.nb, self.ny, self.nx), dtype=torch.float64, device="cuda")
+        st = _lib.KirchhoffStats()
+        torch.cuda.synchronize(ill.device)             # the library works on the null stream
+        check(lib().rtmi_kirchhoff_illumination_dev(h, ill.data_ptr(), C.byref(st)))
+        if self.nbin == 0:
+            ill = ill[0]
+        return (ill, kirchhoff_stats(st)) if stats else ill
+
+    def lsqr(self, d, iter_lim, damp=0.0, atol=0.0, btol=0.0, history=False, stats=False, hilbert=None, filtered=False,
+             row_weight=None, col_scale=None, x0=None, eps=1e-3):
         """rtmi_kirchhoff_lsqr: min |L x - d|^2 + damp^2 |x|^2 from x = 0, every vector on the device.  -> dict: x shaped like
         migrate's image, istop (scipy's 0, 1, 2, 7; _lib.LSQR_RANGE: a norm left fp64's normal range), itn, r1norm, r2norm, anorm,
         arnorm; with history=True also history [itn, 4] (alfa, beta, r1norm, arnorm after each iteration); with stats=True also
@@ -1727,7 +1787,11 @@ class Kirchhoff:
         with kmah solves for the full trace ch0 + H ch1 (model's trace, with the device's H) and on any other handle is the same
         call; None: a handle with kmah is refused.  filtered=True: rtmi_kirchhoff_lsqr_filtered, the same with set_filter's F
         inside the operator, A = F (ch0 + H ch1) and its exact transpose; it needs a filter, and on a handle with kmah
-        hilbert="device"."""
+        hilbert="device".
+        row_weight [N, nt], col_scale and x0 shaped like the image: rtmi_kirchhoff_lsqr_weighted, min |W L D y - W (d - L x0)|^2 +
+        damp^2 |y|^2 and x = x0 + D y, with the operator hilbert= / filtered= choose; a col_scale of 0 masks a value, which comes
+        back as x0's.  col_scale="illumination": 1 / sqrt(illum + eps max(illum)) of illumination(), 0 where illum is 0.  Without
+        these keywords the call is the one it was."""
         if hilbert not in (None, "device"):
             raise ValueError('Kirchhoff.lsqr: hilbert must be None or "device"')
         if filtered:
@@ -1747,9 +1811,18 @@ class Kirchhoff:
         x = np.empty((self.nb, self.ny, self.nx))
         hist = np.zeros((iter_lim, 4)) if history else None
         st = _lib.LsqrStats()
-        solver = (lib().rtmi_kirchhoff_lsqr_filtered if filtered else
-                  lib().rtmi_kirchhoff_lsqr_full if hilbert == "device" else lib().rtmi_kirchhoff_lsqr)
-        check(solver(self._open(), C.byref(lp), dptr(dd), dptr(x), dptr(hist), C.byref(st)))
+        if row_weight is None and col_scale is None and x0 is None:
+            solver = (lib().rtmi_kirchhoff_lsqr_filtered if filtered else
+                      lib().rtmi_kirchhoff_lsqr_full if hilbert == "device" else lib().rtmi_kirchhoff_lsqr)
+            check(solver(self._open(), C.byref(lp), dptr(dd), dptr(x), dptr(hist), C.byref(st)))
+        else:
+            if isinstance(col_scale, str):
+                if col_scale != "illumination":
+                    raise ValueError('Kirchhoff.lsqr: col_scale must be an array or "illumination"')
+                col_scale = illumination_scale(self.illumination(), eps)
+            lo, keep = _lsqr_options("Kirchhoff.lsqr", self.N * self.nt, self.nb * self.ny * self.nx, row_weight, col_scale, x0)
+            op = _lib.LSQR_OP_FILTERED if filtered else _lib.LSQR_OP_FULL if hilbert == "device" else _lib.LSQR_OP_PLAIN
+            check(lib().rtmi_kirchhoff_lsqr_weighted(self._open(), C.byref(lp), C.byref(lo), op, dptr(dd), dptr(x), dptr(hist), C.byref(st)))
         out = {"x": x if self.nbin else x[0], "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm,
                "anorm": st.anorm, "arnorm": st.arnorm}
         if history:

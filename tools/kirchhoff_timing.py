@@ -31,8 +31,12 @@ beside scipy.signal.oaconvolve on the host, and per iteration the wall time of K
 Kirchhoff.lsqr(hilbert="device") on the same handle and beside the host loop of the same operator -- scipy's lsqr over a
 LinearOperator made of model_channels / migrate_channels, rt_bench.hilbert and scipy.signal.oaconvolve -- the two loops
 alternating, twice each.  --lsqr 0 leaves the loops out.
+--lsqr ITERS --weighted times the weighted loop on the same case and data beside the plain one, in one process, the
+two alternating --reps times: row weights, a column scale (1 / sqrt(illumination + 1e-3 max)) and a start model all set.  It
+prints, per iteration, the medians and the spread of operator_ms and vector_ms of both loops, the bytes the vector passes of one
+iteration move in each, and the kernel time of rtmi_kirchhoff_illumination beside migrate's on the same handle.
 Usage: python tools/kirchhoff_timing.py [--reps K] [--case NAME] [--arrivals K] [--antialias NLEV] [--lsqr ITERS] [--hilbert]
-                                        [--filter L]"""
+                                        [--filter L] [--weighted]"""
 import argparse
 import json
 import os
@@ -249,6 +253,54 @@ def run_lsqr(iters):
                       "x_max_rel_diff": float(np.max(np.abs(dev["x"].reshape(-1) - host[0])) / np.max(np.abs(host[0])))}), flush=True)
 
 
+def series(v):
+    v = np.asarray(v, dtype=np.float64)
+    return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max())}
+
+
+def run_lsqr_weighted(iters, reps):
+    from raytracing_amd import rt_bench as rb
+    P, nt, dt = 256, 2048, 0.0005
+    grid = (-2.0, 7.0 / 511, 512, -2.5, 3.5 / 255, 256)
+    pos_x = np.linspace(-1.5, 4.5, P) + 1e-3
+    T, _ = tables(pos_x, grid)
+    src = np.arange(0, P, 4)
+    isrc = np.repeat(src, P).astype(np.int32)
+    irec = np.tile(np.arange(P), len(src)).astype(np.int32)
+    N, nn = len(isrc), T[0].size
+    op = rb.Kirchhoff(T, isrc, irec, nt, dt)
+    rng = np.random.default_rng(1)
+    d = op.model(rng.standard_normal(T.shape[1:]))
+    x = rng.standard_normal((N, nt))
+    ki, kis, sti = median_ms(lambda: op.illumination(stats=True)[1], reps)
+    km, kms, stm = median_ms(lambda: op.migrate(x, stats=True)[1], reps)
+    print(json.dumps({"what": "rtmi_kirchhoff_illumination beside migrate, kernel event time", "pairs": sti["pairs"],
+                      "contributing": sti["contributing"], "migrate_contributing": stm["contributing"], "illumination_ms_median": ki,
+                      "migrate_ms_median": km, "illumination_over_migrate": ki / km, "illumination_ms": kis, "migrate_ms": kms}), flush=True)
+    opt = dict(row_weight=0.5 + rng.random((N, nt)), col_scale=rb.illumination_scale(op.illumination()), x0=0.1 * rng.standard_normal(T.shape[1:]))
+    op.lsqr(d, 1)                                                # warm-up: code objects
+    op.lsqr(d, 1, **opt)
+    runs = {"plain": [], "weighted": []}
+    for _ in range(reps):                                        # alternating: both see the same state of the device
+        for name, kw in (("plain", {}), ("weighted", opt)):
+            r = op.lsqr(d, iters, stats=True, **kw)
+            runs[name].append((r["stats"]["operator_ms"] / r["itn"], r["stats"]["vector_ms"] / r["itn"], r["stats"]["bytes_device"]))
+    op.close()
+    per, nm = N * nt, nn
+    # one iteration's vector passes, every access counted once: axmy (2 reads, 1 write) + sumsq (1) + scale (1, 1) on each side, and
+    # x, w (3 reads, 2 writes); weighted: the diagonal read by axmy and by scale, the copy written by scale
+    plain_b = 8 * (6 * per + 6 * nm + 5 * nm)
+    weighted_b = plain_b + 8 * (3 * per + 3 * nm)
+    out = {"what": f"weighted beside plain least-squares migration, {iters} iterations, {reps} alternating runs", "N": N, "nodes": nn, "nt": nt,
+           "vector_bytes_per_iteration_plain": plain_b, "vector_bytes_per_iteration_weighted": weighted_b, "byte_ratio": weighted_b / plain_b}
+    for name, v in runs.items():
+        out[f"{name}_operator_ms_per_iteration"] = series([a[0] for a in v])
+        out[f"{name}_vector_ms_per_iteration"] = series([a[1] for a in v])
+        out[f"{name}_bytes_device"] = v[0][2]
+    out["vector_ms_ratio"] = out["weighted_vector_ms_per_iteration"]["median"] / out["plain_vector_ms_per_iteration"]["median"]
+    print(json.dumps(out), flush=True)
+
+
 def run_hilbert(K, reps, iters):
     import torch
     from scipy.sparse.linalg import lsqr
@@ -412,6 +464,7 @@ if __name__ == "__main__":
     ap.add_argument("--lsqr", type=int, metavar="ITERS")
     ap.add_argument("--hilbert", action="store_true")
     ap.add_argument("--filter", type=int, metavar="L")
+    ap.add_argument("--weighted", action="store_true")
     a = ap.parse_args()
     if a.filter:
         if not 3 <= a.filter <= 2048:
@@ -419,6 +472,8 @@ if __name__ == "__main__":
         run_filter(a.filter, a.arrivals or 2, a.reps, 3 if a.lsqr is None else a.lsqr)
     elif a.hilbert:
         run_hilbert(a.arrivals or 2, a.reps, 3 if a.lsqr is None else a.lsqr)
+    elif a.lsqr and a.weighted:
+        run_lsqr_weighted(a.lsqr, a.reps)
     elif a.lsqr:
         run_lsqr(a.lsqr)
     elif a.antialias:

@@ -5,7 +5,11 @@ rtmi_tomo_transpose against rtmi_traveltime_backproject, warmed, alternating, me
 each series and the floor of each (the bytes it must read over 6 TB/s); the solver's operator and vector time per iteration.
 The fan is the vert_heterogeneous op6 fan from (-2, -2), at the ray ends and with the line x = 4.
 
-    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--out FILE.json]
+--weighted: also the weighted solver beside the plain one on the same right-hand side, the two alternating
+--reps times: row weights, a column scale that freezes the samples outside coverage(), and a start model, all set; per-iteration
+operator_ms and vector_ms of both as median, min and max.
+
+    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--weighted] [--out FILE.json]
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--rays", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--weighted", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from raytracing_amd import rt_bench as rb
@@ -95,6 +100,25 @@ def main():
     out["lsqr"] = {"itn": s["itn"], "istop": s["istop"], "operator_ms_per_iteration": s["stats"]["operator_ms"] / max(s["itn"], 1),
                    "vector_ms_per_iteration": s["stats"]["vector_ms"] / max(s["itn"], 1), "total_ms": s["stats"]["total_ms"],
                    "bytes_device": s["stats"]["bytes_device"]}
+    if a.weighted:
+        rhs = rng.standard_normal(R)
+        opt = dict(row_weight=0.5 + rng.random(R), col_scale=(0.5 + rng.random((F.qy, F.qx))) * (E.coverage() != 0),
+                   x0=1e-2 * rng.standard_normal((F.qy, F.qx)))
+        E.lsqr(rhs, damp=1e-3, smooth=(0.5, 0.25), iter_lim=1, **opt)            # warm-up: the weighted passes' code objects
+        runs = {"plain": [], "weighted": []}
+        for _ in range(a.reps):                                   # alternating
+            for name, kw in (("plain", {}), ("weighted", opt)):
+                s = E.lsqr(rhs, damp=1e-3, smooth=(0.5, 0.25), iter_lim=a.iters, stats=True, **kw)
+                n = max(s["itn"], 1)
+                runs[name].append((s["stats"]["operator_ms"] / n, s["stats"]["vector_ms"] / n, s["stats"]["bytes_device"]))
+        nd = F.qy * (F.qx - 1) + (F.qy - 1) * F.qx
+        per, nm = R + nd, F.qy * F.qx
+        plain_b = 8 * (6 * per + 6 * nm + 5 * nm)                 # every access of one iteration's passes counted once
+        out["lsqr_weighted"] = {"vector_bytes_per_iteration_plain": plain_b, "vector_bytes_per_iteration_weighted": plain_b + 8 * 3 * (per + nm),
+                                "byte_ratio": 1.0 + 3 * (per + nm) / (6 * per + 11 * nm)}
+        for name, v in runs.items():
+            out["lsqr_weighted"][name] = {"operator_ms_per_iteration": series([q[0] for q in v]),
+                                          "vector_ms_per_iteration": series([q[1] for q in v]), "bytes_device": v[0][2]}
     E.close(); EL.close(); F.close()
     text = json.dumps(out, indent=1)
     print(text)
