@@ -907,9 +907,9 @@ int rtmi_kirchhoff_lsqr_filtered(rtmi_kirchhoff *k, const rtmi_lsqr_params *lp, 
  * stats of _info and the products: rows, segments, padded_segments (the slots of the sliced storage: slices of 64 rows, each as
  * wide as its longest row), bytes_device, compile_ms (the event time of the last append), vmax, qx, qy; the products add
  * kernel_ms, and _transpose atomics and scale_exp.
- * Row weights, a column scale or mask and a start model: rtmi_tomo_lsqr_weighted below.
- * Not covered: a second-order regulariser; removing rows from a handle; several GPUs, fp32 vectors;
- * model parameterisations other than the field's own samples. */
+ * Row weights, a column scale or mask and a start model: rtmi_tomo_lsqr_weighted below.  A model basis (a coarse B-spline grid,
+ * or any banded separable one) and second-difference rows: rtmi_tomo_lsqr_basis, further below.
+ * Not covered: removing rows from a handle; several GPUs, fp32 vectors. */
 #define RTMI_TOMO_SKIP (-2)
 typedef struct rtmi_tomo rtmi_tomo;
 typedef struct { int64_t rows, segments, padded_segments, bytes_device, atomics; double compile_ms, kernel_ms, vmax;
@@ -971,8 +971,8 @@ void rtmi_tomo_destroy(rtmi_tomo *t);
  * terms between the pairs of one trace that meet in a sample, the level filters, and H and F.  stats: kernel_ms, pairs and
  * contributing as migrate reports them; scale_exp and upload_ms 0.  1 / sqrt(illum + eps max(illum)) is the usual col_scale.
  * RTMI_ERR_ARG: a null handle or buffer; d_illum as rtmi_kirchhoff_migrate_dev checks d_image.
- * Not covered: a second-order regulariser, conlim / var, smoothing of the total model rather than of the update, a
- * preconditioner that is not diagonal, an illumination with the cross terms (the diagonal of the filtered operators). */
+ * Not covered: a second-order regulariser for the Kirchhoff solvers (the tomography solver has one: rtmi_tomo_lsqr_basis),
+ * conlim / var, smoothing of the total model rather than of the update, a preconditioner that is not diagonal, an illumination with the cross terms (the diagonal of the filtered operators). */
 #define RTMI_LSQR_OP_PLAIN 0
 #define RTMI_LSQR_OP_FULL 1
 #define RTMI_LSQR_OP_FILTERED 2
@@ -988,6 +988,64 @@ int rtmi_tomo_lsqr_weighted(rtmi_tomo *t, const rtmi_lsqr_params *lp, const rtmi
                             const double *rhs, double *x, double *history, rtmi_lsqr_stats *st);
 int rtmi_kirchhoff_illumination(rtmi_kirchhoff *k, double *illum, rtmi_kirchhoff_stats *st);          /* -> [nb][ny][nx] */
 int rtmi_kirchhoff_illumination_dev(rtmi_kirchhoff *k, double *d_illum, rtmi_kirchhoff_stats *st);
+
+/* A model basis and second-difference smoothing for the tomography solver.  DESIGN.md section 27.
+ * An axis basis of a fine axis of q samples onto m coefficients with bandwidth B (1 .. 4) is first [q] (int32) and wgt [q][B]
+ * (fp64): fine index j carries weight wgt[j][b] on coefficient first[j] + b.  0 <= first[j] <= m - B, first is non-decreasing,
+ * every weight is finite; zero weights are allowed, and so is a coefficient that no fine index reaches (a column of zeros).
+ * Anything else is RTMI_ERR_ARG, naming the axis and the index.  The fine indices that reach coefficient l are one range
+ * [lo[l], hi[l]): lo[l] the first j with first[j] >= l - B + 1, hi[l] one past the last j with first[j] <= l
+ * (raytracing_amd/csrc/rt_tomo_basis.h computes them and has the pair below as host loops).
+ * P = Py (x) Px maps c [my][mx] to x [qy][qx], qx and qy the tomography handle's.  Every product and add is a separate fp64 operation:
+ *   prolong   x[i][j]: acc = +0.0; for a = 0 .. By - 1: r = +0.0, for b = 0 .. Bx - 1: r = fl(r + fl(wx[j][b] c[fy[i] + a][fx[j] + b])),
+ *             then acc = fl(acc + fl(wy[i][a] r)).
+ *   restrict  g = P^T x in two passes, no atomics: t[i][l] = +0.0, then for j ascending over [lo_x[l], hi_x[l])
+ *             t = fl(t + fl(wx[j][l - fx[j]] x[i][j])); g[k][l] = +0.0, then for i ascending over [lo_y[k], hi_y[k])
+ *             g = fl(g + fl(wy[i][k - fy[i]] t[i][l])).  An empty range gives +0.0.  The same bits under every launch shape.
+ * Both read the same weights: P^T is the transpose of P entry for entry in exact arithmetic.
+ * rtmi_bspline_axis (host only, no device): uniform B-splines of degree 0, 1 or 3, B = degree + 1, on n = m - degree intervals
+ * (n = m for degree 0); q >= 2, m >= degree + 1, first [q], wgt [q][B].  e = min(floor(j n / (q - 1)), n - 1) in integers,
+ * first[j] = e, t = (j n - e (q - 1)) / (q - 1) in long double; degree 3, with u = 1 - t: u u u / 6, ((3 t - 6) t t + 4) / 6,
+ * (((-3 t + 3) t + 3) t + 1) / 6, t t t / 6; degree 1: 1 - t, t; degree 0: 1; evaluated in long double and rounded once to fp64,
+ * the convention of rtmi_half_derivative_taps.  Degree 0 with m = q is the identity.
+ * rtmi_tomo_basis_create: the basis takes qx, qy and the device from t (the calling thread's current one, else RTMI_ERR_ARG),
+ * copies the axes and keeps no reference to t; t [qy][mx] of restrict lives in the basis handle.  The host forms are upload +
+ * the _dev forms + download and refuse a value that is not finite; the _dev forms take memory of the basis's device, checked as
+ * rtmi_tomo_apply_dev checks its own.
+ * rtmi_tomo_lsqr_basis: the loop's model is the coefficient grid G = [my][mx]; with p NULL it is [qy][qx] and P is left out
+ * altogether.  It minimises |W A P D y - W (b - A x0)|^2 + damp^2 |y|^2 plus the regulariser rows of D y over y [G], by the loop of
+ * rtmi_kirchhoff_lsqr.  row_weight has `rows` values; col_scale has |G| values -- my mx with a basis: the entry cannot see
+ * the length behind the pointer --; x0 is a fine start model [qy][qx].
+ *   forward     s = fl(dc v) (left out without dc), xf = P s, A xf by rtmi_tomo_apply_dev's kernel, then the regulariser rows of s
+ *   transposed  gf = A^T u[:rows] by rtmi_tomo_transpose_dev's kernels, gA = P^T gf, then the regulariser's transposed terms are
+ *               added; a range stop of A^T is the loop's RTMI_LSQR_RANGE
+ *   result      c = fl(dc y), or y without dc; x = P c; with x0, x = fl(x0 + x).  c [G] may be NULL; with p NULL, x is c plus x0.
+ * The regulariser acts on G of gy x gx values; reg = {d1 = {lx, ly}, d2 = {mx2, my2}}.  A pair equal to {0, 0}, or a NULL reg,
+ * is absent and its rows are not allocated; a negative or non-finite value is RTMI_ERR_ARG.  Stacked order [A | Dx | Dy | Dxx | Dyy]:
+ * d1 gives rtmi_tomo_lsqr's Dx and Dy, word for word, on G; d2 gives
+ *   (Dxx s)[k][l] = fl(mx2 fl(fl(s[k][l] + s[k][l + 2]) - fl(2 s[k][l + 1]))) on [gy][gx - 2], Dyy alike on [gy - 2][gx] (an
+ *   axis with fewer than 3 values has no rows); transposed at a node r2 = fl(mx2 fl(fl(uxx[k][l - 2] + uxx[k][l]) - fl(2 uxx[k][l - 1]))),
+ *   s2 alike in y, a missing neighbour +0.0.
+ * The node's gradient is fl(gA + fl(r + s)) with d1 only, fl(gA + fl(r2 + s2)) with d2 only, fl(gA + fl(fl(r + s) + fl(r2 + s2)))
+ * with both.  The rows smooth the update D y on G, with a right-hand side of 0 and no row weight.
+ * With p NULL and d2 absent the entry is rtmi_tomo_lsqr_weighted bit for bit, launch for launch; with lo empty as well,
+ * rtmi_tomo_lsqr: x, the history, the four norms, itn and istop.  operator_ms includes the basis and regulariser-transpose
+ * kernels' event time; bytes_device counts the handle, the basis and the call's vectors.
+ * RTMI_ERR_ARG before any device work: everything rtmi_tomo_lsqr_weighted refuses; a basis whose qx, qy or device differ from t's.
+ * Not covered: smoothing of the total model (the start model plus P D y) rather than of the update; non-uniform or clamped knots from a helper (a
+ * caller can pass any banded axis); B > 4; a compiled A P; several GPUs; fp32 vectors. */
+typedef struct rtmi_tomo_basis rtmi_tomo_basis;
+int rtmi_bspline_axis(int32_t q, int32_t m, int32_t degree, int32_t *first, double *wgt);            /* host only, no device */
+int rtmi_tomo_basis_create(const rtmi_tomo *t, int32_t mx, int32_t bx, const int32_t *first_x, const double *wgt_x,
+                           int32_t my, int32_t by, const int32_t *first_y, const double *wgt_y, rtmi_tomo_basis **out);
+int rtmi_tomo_basis_prolong(rtmi_tomo_basis *p, const double *c, double *x);                         /* host [my][mx] -> [qy][qx] */
+int rtmi_tomo_basis_restrict(rtmi_tomo_basis *p, const double *x, double *g);                        /* host [qy][qx] -> [my][mx] */
+int rtmi_tomo_basis_prolong_dev(rtmi_tomo_basis *p, const double *d_c, double *d_x);
+int rtmi_tomo_basis_restrict_dev(rtmi_tomo_basis *p, const double *d_x, double *d_g);
+void rtmi_tomo_basis_destroy(rtmi_tomo_basis *p);
+typedef struct { double d1[2], d2[2]; int64_t reserved[4]; } rtmi_tomo_reg;                          /* {lx, ly}, {mx2, my2} */
+int rtmi_tomo_lsqr_basis(rtmi_tomo *t, rtmi_tomo_basis *p, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo,
+                         const rtmi_tomo_reg *reg, const double *rhs, double *c, double *x, double *history, rtmi_lsqr_stats *st);
 
 typedef struct {
     void *s_ray, *n_ray;                 /* device, dtype, layouts above */

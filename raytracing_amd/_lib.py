@@ -156,6 +156,11 @@ class TomoStats(C.Structure):
                 ("qx", C.c_int32), ("qy", C.c_int32), ("scale_exp", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
 
 
+class TomoReg(C.Structure):
+    """rtmi_tomo_reg: the first- and second-difference weights of rtmi_tomo_lsqr_basis, {lx, ly} and {mx2, my2}"""
+    _fields_ = [("d1", C.c_double * 2), ("d2", C.c_double * 2), ("reserved", C.c_int64 * 4)]
+
+
 TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
 LSQR_OP_PLAIN, LSQR_OP_FULL, LSQR_OP_FILTERED = 0, 1, 2     # RTMI_LSQR_OP_: rtmi_kirchhoff_lsqr_weighted's operator
@@ -250,6 +255,16 @@ SYMBOLS = {
                                           C.POINTER(LsqrStats)]),
     "rtmi_kirchhoff_illumination": (C.c_int, [C.c_void_p, _dp, C.POINTER(KirchhoffStats)]),
     "rtmi_kirchhoff_illumination_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(KirchhoffStats)]),
+    "rtmi_bspline_axis": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _ip, _dp]),
+    "rtmi_tomo_basis_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, C.c_int32, C.c_int32, _ip, _dp,
+                                         C.POINTER(C.c_void_p)]),
+    "rtmi_tomo_basis_prolong": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "rtmi_tomo_basis_restrict": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "rtmi_tomo_basis_prolong_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtmi_tomo_basis_restrict_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtmi_tomo_basis_destroy": (None, [C.c_void_p]),
+    "rtmi_tomo_lsqr_basis": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), _dp,
+                                       _dp, _dp, _dp, C.POINTER(LsqrStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -15,6 +15,8 @@
 //                     drift apart), and the sums go into two integer words per sample with adds that return nothing (add_split),
 //                     read as one integer and rounded once (rt_fix128.h): the same bits in every schedule and order of appends.
 // rtmi_tomo_lsqr runs the loop of rt_lsqr_device.h over the pair, stacked with the first-difference rows of the smoothing terms.
+// The last part of the file is the model basis (rtmi_tomo_basis_*, rtmi_tomo_lsqr_basis): its own kernels
+// and entries, which call the products above as they are.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,6 +30,7 @@
 #include "rt_lsqr_device.h"
 #include "rt_sens_walk.h"
 #include "rt_tomo.h"
+#include "rt_tomo_basis.h"
 #include "rtmi_host.h"
 
 static_assert(rt::kTomoSlice == 64, "a slice is a wave");
@@ -717,4 +720,420 @@ RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const d
 RTMI_EXPORT int rtmi_tomo_lsqr_weighted(rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
                                         const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
     return tomo_lsqr_run("rtmi_tomo_lsqr_weighted", t, lp, lo, smooth, rhs, x, history, st);
+}
+
+// ------------------------------------------------------------------------------------------------------------ model basis
+// A separable model basis P = Py (x) Px from a coefficient grid c [my][mx] to the field's samples x [qy][qx], its exact transpose,
+// second-difference rows, and the solver that takes both (rtmi_tomo_basis_*, rtmi_tomo_lsqr_basis; DESIGN.md section 27;
+// rt_tomo_basis.h has the axis rules, the ranges and the pair as host loops).
+//   k_basis_prolong     one lane per fine node: up to By Bx reads of c, which is small and stays in L2
+//   k_basis_restrict_x  t [qy][mx]: a block takes one fine row and kBasisTile neighbouring coefficients, whose ranges overlap and
+//                       together are one run of fine indices; the run goes through LDS in pieces of kBasisChunk samples, in
+//                       ascending order, and every lane walks the part of its own range that lies in the piece, ascending
+//   k_basis_restrict_y  g [my][mx]: lanes along l (coalesced), a loop over the range of fine rows, ascending
+// No atomics: every sum has one owner and one order, the same bits under every launch shape.
+struct rtmi_tomo_basis {
+    int device = 0, qx = 0, qy = 0, mx = 0, my = 0, bx = 0, by = 0;
+    int32_t *fx = nullptr, *fy = nullptr, *lox = nullptr, *hix = nullptr, *loy = nullptr, *hiy = nullptr;
+    double *wx = nullptr, *wy = nullptr;
+    double* t = nullptr;                        // [qy][mx]: between the two passes of the transposed operator
+    size_t nf() const { return (size_t)qx * (size_t)qy; }
+    size_t ng() const { return (size_t)mx * (size_t)my; }
+    size_t bytes() const {
+        return ((size_t)qx + (size_t)qy + 2 * ((size_t)mx + (size_t)my)) * sizeof(int32_t) +
+               ((size_t)qx * bx + (size_t)qy * by + (size_t)qy * mx) * sizeof(double);
+    }
+    ~rtmi_tomo_basis() {
+        for (void* p : {(void*)fx, (void*)fy, (void*)lox, (void*)hix, (void*)loy, (void*)hiy, (void*)wx, (void*)wy, (void*)t})
+            if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+constexpr int kBasisTile = 256;       // coefficients of one block of k_basis_restrict_x: one per lane
+constexpr int kBasisChunk = 1024;     // fine samples of a row in LDS at a time
+
+__global__ void __launch_bounds__(256) k_basis_prolong(const double* __restrict__ c, int qx, int qy, int mx, int bx, int by,
+                                                       const int32_t* __restrict__ fx, const double* __restrict__ wx,
+                                                       const int32_t* __restrict__ fy, const double* __restrict__ wy, double* __restrict__ x) {
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= (long)qx * qy) return;
+    const int i = (int)(n / qx), j = (int)(n % qx);
+    const double* cc = c + (size_t)fy[i] * mx + fx[j];
+    double acc = 0.0;
+    for (int a = 0; a < by; a++) {
+        double r = 0.0;
+        for (int b = 0; b < bx; b++) r = __dadd_rn(r, __dmul_rn(wx[(size_t)j * bx + b], cc[(size_t)a * mx + b]));
+        acc = __dadd_rn(acc, __dmul_rn(wy[(size_t)i * by + a], r));
+    }
+    x[n] = acc;
+}
+
+// grid (qy, tiles of l)
+__global__ void __launch_bounds__(kBasisTile) k_basis_restrict_x(const double* __restrict__ x, int qx, int mx, int bx,
+                                                                  const int32_t* __restrict__ fx, const double* __restrict__ wx,
+                                                                  const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                                                  double* __restrict__ t) {
+    __shared__ double row[kBasisChunk];
+    const int i = (int)blockIdx.x, l0 = (int)blockIdx.y * kBasisTile, l = l0 + (int)threadIdx.x;
+    const int l1 = min(l0 + kBasisTile, mx) - 1;                     // the tile's last coefficient; l0 <= l1 < mx
+    const int j0 = lo[l0], j1 = hi[l1];                              // lo and hi are non-decreasing: the tile's run of fine indices
+    const bool mine = l < mx;
+    const int mlo = mine ? lo[l] : 0, mhi = mine ? hi[l] : 0;
+    const double* xr = x + (size_t)i * qx;
+    double s = 0.0;
+    for (int c0 = j0; c0 < j1; c0 += kBasisChunk) {
+        const int c1 = min(c0 + kBasisChunk, j1);
+        for (int j = c0 + (int)threadIdx.x; j < c1; j += kBasisTile) row[j - c0] = xr[j];
+        __syncthreads();
+        for (int j = max(mlo, c0); j < min(mhi, c1); j++) s = __dadd_rn(s, __dmul_rn(wx[(size_t)j * bx + (l - fx[j])], row[j - c0]));
+        __syncthreads();
+    }
+    if (mine) t[(size_t)i * mx + l] = s;
+}
+
+// grid (my, blocks of l)
+__global__ void __launch_bounds__(256) k_basis_restrict_y(const double* __restrict__ t, int mx, int by, const int32_t* __restrict__ fy,
+                                                          const double* __restrict__ wy, const int32_t* __restrict__ lo,
+                                                          const int32_t* __restrict__ hi, double* __restrict__ g) {
+    const int k = (int)blockIdx.x, l = (int)blockIdx.y * 256 + (int)threadIdx.x;
+    if (l >= mx) return;
+    double s = 0.0;
+    for (int i = lo[k]; i < hi[k]; i++) s = __dadd_rn(s, __dmul_rn(wy[(size_t)i * by + (k - fy[i])], t[(size_t)i * mx + l]));
+    g[(size_t)k * mx + l] = s;
+}
+
+// The second-difference rows on a grid of gy x gx values: uxx [gy][gx - 2] = fl(mx fl(fl(s[k][l] + s[k][l + 2]) - fl(2 s[k][l + 1]))),
+// uyy [gy - 2][gx] alike in y; an axis with fewer than 3 values has no rows
+__global__ void __launch_bounds__(256) k_tomo_diff2(const double* __restrict__ s, int gx, int gy, double mx, double my, double* __restrict__ uxx,
+                                                    double* __restrict__ uyy) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)gx * gy) return;
+    const int k = (int)(i / gx), l = (int)(i % gx);
+    const double c = s[i];
+    if (l < gx - 2) uxx[(size_t)k * (gx - 2) + l] = __dmul_rn(mx, __dadd_rn(__dadd_rn(c, s[i + 2]), -__dmul_rn(2.0, s[i + 1])));
+    if (k < gy - 2) uyy[i] = __dmul_rn(my, __dadd_rn(__dadd_rn(c, s[i + 2 * (long)gx]), -__dmul_rn(2.0, s[i + gx])));
+}
+
+// The regulariser's transposed terms on the grid, added to g = gA in place.  First differences (ux given): k_tomo_finish's r and s.
+// Second differences (uxx given): r2 = fl(mx fl(fl(uxx[k][l - 2] + uxx[k][l]) - fl(2 uxx[k][l - 1]))), s2 alike in y, a missing
+// neighbour +0.0.  g = fl(gA + fl(r + s)), fl(gA + fl(r2 + s2)), or with both fl(gA + fl(fl(r + s) + fl(r2 + s2))).
+__global__ void __launch_bounds__(256) k_tomo_reg_t(double* __restrict__ g, int gx, int gy, const double* __restrict__ ux,
+                                                    const double* __restrict__ uy, double lx, double ly, const double* __restrict__ uxx,
+                                                    const double* __restrict__ uyy, double mx, double my) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)gx * gy) return;
+    const int k = (int)(i / gx), l = (int)(i % gx);
+    double d1 = 0.0, d2 = 0.0;
+    if (ux) {
+        const double xa = l > 0 ? ux[(size_t)k * (gx - 1) + l - 1] : 0.0, xb = l < gx - 1 ? ux[(size_t)k * (gx - 1) + l] : 0.0;
+        const double ya = k > 0 ? uy[i - gx] : 0.0, yb = k < gy - 1 ? uy[i] : 0.0;
+        d1 = __dadd_rn(__dmul_rn(lx, __dadd_rn(xa, -xb)), __dmul_rn(ly, __dadd_rn(ya, -yb)));
+    }
+    if (uxx) {
+        const size_t w = (size_t)(gx > 2 ? gx - 2 : 0), o = (size_t)k * w;
+        const double xa = l >= 2 ? uxx[o + l - 2] : 0.0, xb = (l >= 1 && l < gx - 1) ? uxx[o + l - 1] : 0.0, xc = l < gx - 2 ? uxx[o + l] : 0.0;
+        const double ya = k >= 2 ? uyy[i - 2 * (long)gx] : 0.0, yb = (k >= 1 && k < gy - 1) ? uyy[i - gx] : 0.0, yc = k < gy - 2 ? uyy[i] : 0.0;
+        d2 = __dadd_rn(__dmul_rn(mx, __dadd_rn(__dadd_rn(xa, xc), -__dmul_rn(2.0, xb))),
+                       __dmul_rn(my, __dadd_rn(__dadd_rn(ya, yc), -__dmul_rn(2.0, yb))));
+    }
+    g[i] = __dadd_rn(g[i], ux && uxx ? __dadd_rn(d1, d2) : ux ? d1 : d2);
+}
+
+int basis_on_device(const rtmi_tomo_basis* p, const char* who) {
+    int dev = -1;
+    RTMI_HIP(hipGetDevice(&dev));
+    RTMI_ARG(dev == p->device, "the calling thread's current device is not the basis's");
+    return RTMI_OK;
+}
+
+// launches only: the callers have checked the pointers and wait for the stream themselves
+int basis_prolong_dev(rtmi_tomo_basis* p, const char* who, const double* d_c, double* d_x) {
+    hipLaunchKernelGGL(k_basis_prolong, blocks((long)p->nf()), dim3(256), 0, nullptr, d_c, p->qx, p->qy, p->mx, p->bx, p->by, p->fx, p->wx, p->fy,
+                       p->wy, d_x);
+    RTMI_HIP(hipGetLastError());
+    return RTMI_OK;
+}
+
+int basis_restrict_dev(rtmi_tomo_basis* p, const char* who, const double* d_x, double* d_g) {
+    hipLaunchKernelGGL(k_basis_restrict_x, dim3((unsigned)p->qy, (unsigned)((p->mx + kBasisTile - 1) / kBasisTile)), dim3(kBasisTile), 0, nullptr,
+                       d_x, p->qx, p->mx, p->bx, p->fx, p->wx, p->lox, p->hix, p->t);
+    RTMI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_basis_restrict_y, dim3((unsigned)p->my, (unsigned)((p->mx + 255) / 256)), dim3(256), 0, nullptr, p->t, p->mx, p->by, p->fy,
+                       p->wy, p->loy, p->hiy, d_g);
+    RTMI_HIP(hipGetLastError());
+    return RTMI_OK;
+}
+
+// upload + launch + download of one of the pair: n_in values in, n_out values out
+int basis_host_call(rtmi_tomo_basis* p, const char* who, bool restrict_, const double* in, double* out) {
+    const size_t n_in = restrict_ ? p->nf() : p->ng(), n_out = restrict_ ? p->ng() : p->nf();
+    RTMI_RC(finite_all(who, in, n_in, restrict_ ? "x has a value that is not finite" : "c has a value that is not finite"));
+    RTMI_RC(basis_on_device(p, who));
+    DevMem mem;
+    double *di = nullptr, *dout = nullptr;
+    RTMI_HIP(mem.get(&di, n_in * sizeof(double)));
+    RTMI_HIP(mem.get(&dout, n_out * sizeof(double)));
+    RTMI_HIP(hipMemcpy(di, in, n_in * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_RC(restrict_ ? basis_restrict_dev(p, who, di, dout) : basis_prolong_dev(p, who, di, dout));
+    RTMI_HIP(hipMemcpy(out, dout, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_bspline_axis(int32_t q, int32_t m, int32_t degree, int32_t* first, double* wgt) {
+    const char* who = "rtmi_bspline_axis";
+    RTMI_ARG(first, "null first");
+    RTMI_ARG(wgt, "null wgt");
+    RTMI_ARG(degree == 0 || degree == 1 || degree == 3, "degree must be 0, 1 or 3");
+    RTMI_ARG(q >= 2, "q must be >= 2");
+    RTMI_ARG(m >= degree + 1, "m must be >= degree + 1");
+    RTMI_ARG(rt::bspline_axis(q, m, degree, first, wgt), "sizes the helper cannot do");
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_basis_create(const rtmi_tomo* t, int32_t mx, int32_t bx, const int32_t* first_x, const double* wgt_x, int32_t my,
+                                       int32_t by, const int32_t* first_y, const double* wgt_y, rtmi_tomo_basis** out) {
+    const char* who = "rtmi_tomo_basis_create";
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(first_x, "null first_x");
+    RTMI_ARG(wgt_x, "null wgt_x");
+    RTMI_ARG(first_y, "null first_y");
+    RTMI_ARG(wgt_y, "null wgt_y");
+    RTMI_ARG(out, "null out");
+    RTMI_ARG(mx >= 1 && my >= 1, "mx and my must be >= 1");
+    const int qx = t->F.qx, qy = t->F.qy;
+    struct One { const char* name; int q, m, B; const int32_t* first; const double* wgt; };
+    for (const One& a : {One{"x", qx, mx, bx, first_x, wgt_x}, One{"y", qy, my, by, first_y, wgt_y}}) {
+        int64_t at = -1;
+        const char* why = rt::basis_axis_check(a.q, a.m, a.B, a.first, a.wgt, &at);
+        if (why) RTMI_ARG(false, std::string("axis ") + a.name + (at >= 0 ? ", index " + std::to_string(at) : std::string()) + ": " + why);
+    }
+    RTMI_RC(on_device(t, who));
+    rtmi_tomo_basis* p = new (std::nothrow) rtmi_tomo_basis;
+    if (!p) return rtmi_internal_fail(RTMI_ERR_ALLOC, "rtmi_tomo_basis_create: out of host memory");
+    p->device = t->device;
+    p->qx = qx; p->qy = qy; p->mx = mx; p->my = my; p->bx = bx; p->by = by;
+    std::vector<int32_t> lox((size_t)mx), hix((size_t)mx), loy((size_t)my), hiy((size_t)my);
+    rt::basis_ranges(qx, mx, bx, first_x, lox.data(), hix.data());
+    rt::basis_ranges(qy, my, by, first_y, loy.data(), hiy.data());
+    auto up = [&](auto** dst, const auto* src, size_t n) {
+        hipError_t e = hipMalloc((void**)dst, n * sizeof(**dst));
+        if (e == hipSuccess) e = hipMemcpy(*dst, src, n * sizeof(**dst), hipMemcpyHostToDevice);
+        return e;
+    };
+    hipError_t e = up(&p->fx, first_x, (size_t)qx);
+    if (e == hipSuccess) e = up(&p->fy, first_y, (size_t)qy);
+    if (e == hipSuccess) e = up(&p->wx, wgt_x, (size_t)qx * bx);
+    if (e == hipSuccess) e = up(&p->wy, wgt_y, (size_t)qy * by);
+    if (e == hipSuccess) e = up(&p->lox, lox.data(), (size_t)mx);
+    if (e == hipSuccess) e = up(&p->hix, hix.data(), (size_t)mx);
+    if (e == hipSuccess) e = up(&p->loy, loy.data(), (size_t)my);
+    if (e == hipSuccess) e = up(&p->hiy, hiy.data(), (size_t)my);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->t, (size_t)qy * mx * sizeof(double));
+    if (e != hipSuccess) {
+        delete p;
+        return rtmi_internal_fail(e == hipErrorOutOfMemory ? RTMI_ERR_ALLOC : RTMI_ERR_HIP,
+                                  (std::string(who) + ": device memory: " + hipGetErrorString(e)).c_str());
+    }
+    *out = p;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT void rtmi_tomo_basis_destroy(rtmi_tomo_basis* p) { delete p; }
+
+RTMI_EXPORT int rtmi_tomo_basis_prolong(rtmi_tomo_basis* p, const double* c, double* x) {
+    const char* who = "rtmi_tomo_basis_prolong";
+    RTMI_ARG(p, "null handle");
+    RTMI_ARG(c, "null c");
+    RTMI_ARG(x, "null x");
+    return basis_host_call(p, who, false, c, x);
+}
+
+RTMI_EXPORT int rtmi_tomo_basis_restrict(rtmi_tomo_basis* p, const double* x, double* g) {
+    const char* who = "rtmi_tomo_basis_restrict";
+    RTMI_ARG(p, "null handle");
+    RTMI_ARG(x, "null x");
+    RTMI_ARG(g, "null g");
+    return basis_host_call(p, who, true, x, g);
+}
+
+RTMI_EXPORT int rtmi_tomo_basis_prolong_dev(rtmi_tomo_basis* p, const double* d_c, double* d_x) {
+    const char* who = "rtmi_tomo_basis_prolong_dev";
+    RTMI_ARG(p, "null handle");
+    RTMI_ARG(d_c, "null d_c");
+    RTMI_ARG(d_x, "null d_x");
+    RTMI_RC(basis_on_device(p, who));
+    RTMI_RC(check_device_pointer(p->device, who, d_c, p->ng() * sizeof(double), "d_c"));
+    RTMI_RC(check_device_pointer(p->device, who, d_x, p->nf() * sizeof(double), "d_x"));
+    RTMI_RC(basis_prolong_dev(p, who, d_c, d_x));
+    RTMI_HIP(hipStreamSynchronize(nullptr));
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_basis_restrict_dev(rtmi_tomo_basis* p, const double* d_x, double* d_g) {
+    const char* who = "rtmi_tomo_basis_restrict_dev";
+    RTMI_ARG(p, "null handle");
+    RTMI_ARG(d_x, "null d_x");
+    RTMI_ARG(d_g, "null d_g");
+    RTMI_RC(basis_on_device(p, who));
+    RTMI_RC(check_device_pointer(p->device, who, d_x, p->nf() * sizeof(double), "d_x"));
+    RTMI_RC(check_device_pointer(p->device, who, d_g, p->ng() * sizeof(double), "d_g"));
+    RTMI_RC(basis_restrict_dev(p, who, d_x, d_g));
+    RTMI_HIP(hipStreamSynchronize(nullptr));
+    return RTMI_OK;
+}
+
+namespace {
+
+// The solver over the coefficient grid G ([my][mx] with a basis, [qy][qx] without), with first- and second-difference rows on G.
+// The loop sees the options row_weight and col_scale; the start model is a fine one, so its residual is taken here, before the
+// loop, and it is added here, after P: the same two roundings the loop gives them.
+int tomo_lsqr_basis_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                        const double* d1, const double* d2, const double* rhs, double* c, double* x, double* history, rtmi_lsqr_stats* st) {
+    const size_t rows = (size_t)t->rows, nm = t->nz();
+    const size_t gx = p ? (size_t)p->mx : (size_t)t->F.qx, gy = p ? (size_t)p->my : (size_t)t->F.qy, ng = gx * gy;
+    const size_t n1x = d1 ? gy * (gx - 1) : 0, n1y = d1 ? (gy - 1) * gx : 0;
+    const size_t n2x = d2 && gx > 2 ? gy * (gx - 2) : 0, n2y = d2 && gy > 2 ? (gy - 2) * gx : 0;
+    const size_t per = rows + n1x + n1y + n2x + n2y;
+    const double t_begin = now_ms();
+    const std::string no_mem = std::string(who) + ": hipMalloc failed";
+    DevMem mem;
+    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *yd = nullptr, *Atu = nullptr, *xf = nullptr, *gf = nullptr, *x0 = nullptr;
+    for (double** q : {&u, &Av})
+        if (mem.get(q, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    for (double** q : {&v, &w, &yd, &Atu})
+        if (mem.get(q, ng * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    size_t fine = 0;                                                                  // the call's vectors on the fine grid
+    if (p) {
+        for (double** q : {&xf, &gf})
+            if (mem.get(q, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        fine += 2;
+    }
+    if (lo && lo->x0) {
+        if (mem.get(&x0, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(x0, lo->x0, nm * sizeof(double), hipMemcpyHostToDevice));
+        fine += 1;
+    }
+    rtmi_lsqr_options inner{};
+    if (lo) { inner.row_weight = lo->row_weight; inner.col_scale = lo->col_scale; }
+    LsqrOptions O;
+    size_t nopt = 0;
+    RTMI_RC(lsqr_upload_options(who, mem, &inner, rows, per, ng, &O, &nopt));
+    const Vec V{t->red, t->cus};
+    EventMarks<2> ev;
+    RTMI_HIP(ev.create());
+    rtmi_lsqr_stats out{};
+    out.bytes_device = (int64_t)((2 * per + 4 * ng + fine * nm + nopt) * sizeof(double) + t->bytes() + (p ? p->bytes() : 0));
+    double operator_ms = 0.0;
+    // the stacked operator [A P | Dx | Dy | Dxx | Dyy] on s [G], and its transpose
+    auto Ax = [&](const double* s, double* y) {
+        double ms = 0.0, pms = 0.0;
+        if (p) {
+            RTMI_HIP(ev.mark(0));
+            RTMI_RC(basis_prolong_dev(p, who, s, xf));
+            RTMI_HIP(ev.mark(1));
+        }
+        RTMI_RC(apply_dev(t, who, p ? xf : s, y, &ms));
+        if (p) RTMI_HIP(ev.ms(0, 1, &pms));
+        operator_ms += ms + pms;
+        if (d1) {
+            hipLaunchKernelGGL(k_tomo_diff, blocks((long)ng), dim3(256), 0, nullptr, s, (int)gx, (int)gy, d1[0], d1[1], y + rows, y + rows + n1x);
+            RTMI_HIP(hipGetLastError());
+        }
+        if (d2) {
+            hipLaunchKernelGGL(k_tomo_diff2, blocks((long)ng), dim3(256), 0, nullptr, s, (int)gx, (int)gy, d2[0], d2[1], y + rows + n1x + n1y,
+                               y + rows + n1x + n1y + n2x);
+            RTMI_HIP(hipGetLastError());
+        }
+        return (int)RTMI_OK;
+    };
+    auto At = [&](const double* s, double* g, bool* range) {
+        double ms = 0.0, pms = 0.0;
+        int64_t atomics = 0;
+        int32_t e = 0;
+        RTMI_RC(transpose_dev(t, who, s, p ? gf : g, nullptr, nullptr, 0.0, 0.0, range, &ms, &atomics, &e));
+        if (*range) return (int)RTMI_OK;
+        RTMI_HIP(ev.mark(0));
+        if (p) RTMI_RC(basis_restrict_dev(p, who, gf, g));
+        if (d1 || d2) {
+            hipLaunchKernelGGL(k_tomo_reg_t, blocks((long)ng), dim3(256), 0, nullptr, g, (int)gx, (int)gy, d1 ? s + rows : nullptr,
+                               d1 ? s + rows + n1x : nullptr, d1 ? d1[0] : 0.0, d1 ? d1[1] : 0.0, d2 ? s + rows + n1x + n1y : nullptr,
+                               d2 ? s + rows + n1x + n1y + n2x : nullptr, d2 ? d2[0] : 0.0, d2 ? d2[1] : 0.0);
+            RTMI_HIP(hipGetLastError());
+        }
+        RTMI_HIP(ev.mark(1));
+        RTMI_HIP(ev.wait(1));
+        RTMI_HIP(ev.ms(0, 1, &pms));
+        operator_ms += ms + pms;
+        return (int)RTMI_OK;
+    };
+    RTMI_HIP(hipMemcpy(u, rhs, rows * sizeof(double), hipMemcpyHostToDevice));
+    if (per > rows) RTMI_HIP(hipMemsetAsync(u + rows, 0, (per - rows) * sizeof(double), nullptr));
+    RTMI_HIP(hipMemsetAsync(yd, 0, ng * sizeof(double), nullptr));
+    if (x0) {                                                                         // u = fl(rhs - A x0) over the data rows
+        double ms = 0.0;
+        RTMI_RC(apply_dev(t, who, x0, Av, &ms));
+        operator_ms += ms;
+        hipLaunchKernelGGL(k_sub_mul, stride_blocks(V.cus, rows, 1), dim3(256), 0, nullptr, u, Av, (const double*)nullptr, (long)rows);
+        RTMI_HIP(hipGetLastError());
+    }
+    RTMI_RC(lsqr_loop(who, V, lp, per, ng, LsqrVectors{u, Av, v, w, yd, Atu}, Ax, At, history, &out, O));   // yd = fl(dc y): c
+    if (c) RTMI_HIP(hipMemcpy(c, yd, ng * sizeof(double), hipMemcpyDeviceToHost));
+    double* xd = yd;
+    if (p) {
+        RTMI_RC(basis_prolong_dev(p, who, yd, xf));
+        xd = xf;
+    }
+    if (x0) {
+        hipLaunchKernelGGL(k_result, stride_blocks(V.cus, nm, 1), dim3(256), 0, nullptr, xd, (const double*)nullptr, x0, (long)nm);
+        RTMI_HIP(hipGetLastError());
+    }
+    RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));
+    out.total_ms = now_ms() - t_begin;
+    out.operator_ms = operator_ms;
+    if (st) *st = out;
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_tomo_lsqr_basis(rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                                     const rtmi_tomo_reg* reg, const double* rhs, double* c, double* x, double* history,
+                                     rtmi_lsqr_stats* st) {
+    const char* who = "rtmi_tomo_lsqr_basis";
+    RTMI_ARG(t, "null handle");
+    const double *d1 = nullptr, *d2 = nullptr;
+    if (reg) {
+        for (const double v : {reg->d1[0], reg->d1[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d1 must be finite and >= 0");
+        for (const double v : {reg->d2[0], reg->d2[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d2 must be finite and >= 0");
+        if (reg->d1[0] != 0.0 || reg->d1[1] != 0.0) d1 = reg->d1;
+        if (reg->d2[0] != 0.0 || reg->d2[1] != 0.0) d2 = reg->d2;
+    }
+    if (p)
+        RTMI_ARG(p->qx == t->F.qx && p->qy == t->F.qy && p->device == t->device, "the basis was made for another shape or device than the handle's");
+    const bool start = lo && lo->x0;
+    // without a basis and without second differences this is rtmi_tomo_lsqr_weighted, launch for launch (c is x without a start model)
+    if (!p && !d2 && !(c && start)) {
+        RTMI_RC(tomo_lsqr_run(who, t, lp, lo, d1, rhs, x, history, st));
+        if (c) std::memcpy(c, x, t->nz() * sizeof(double));
+        return RTMI_OK;
+    }
+    RTMI_ARG(lp, "null params");
+    RTMI_ARG(rhs, "null rhs");
+    RTMI_ARG(x, "null x");
+    RTMI_RC(lsqr_check_params(who, lp));
+    RTMI_ARG(t->rows >= 1, "the handle has no rows");
+    RTMI_RC(finite_all(who, rhs, (size_t)t->rows, "rhs has a value that is not finite"));
+    if (lo) {
+        rtmi_lsqr_options coarse = *lo, fine = *lo;                               // col_scale has |G| values, x0 qy qx
+        coarse.x0 = nullptr;
+        fine.row_weight = nullptr; fine.col_scale = nullptr;
+        RTMI_RC(lsqr_check_options(who, &coarse, (size_t)t->rows, p ? p->ng() : t->nz()));
+        RTMI_RC(lsqr_check_options(who, &fine, 0, t->nz()));
+    }
+    RTMI_RC(on_device(t, who));
+    return tomo_lsqr_basis_run(who, t, p, lp, lo, d1, d2, rhs, c, x, history, st);
 }

@@ -951,13 +951,13 @@ class Tomography:
     def _device_tensor(self, who, t, name):
         import torch
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"Tomography.{who}: {name} must be a torch tensor")
+            raise TypeError(f"{type(self).__name__}.{who}: {name} must be a torch tensor")
         if t.dtype != torch.float64:
-            raise TypeError(f"Tomography.{who}: {name} must be float64")
+            raise TypeError(f"{type(self).__name__}.{who}: {name} must be float64")
         if not t.is_contiguous():
-            raise ValueError(f"Tomography.{who}: {name} must be contiguous")
+            raise ValueError(f"{type(self).__name__}.{who}: {name} must be contiguous")
         if not t.is_cuda:                              # which GPU it is on, and its length, the library checks
-            raise ValueError(f"Tomography.{who}: {name} must be a tensor on a GPU, not on the host")
+            raise ValueError(f"{type(self).__name__}.{who}: {name} must be a tensor on a GPU, not on the host")
         return t
 
     def matvec_device(self, x, out=None, stats=False):
@@ -985,11 +985,14 @@ class Tomography:
         return self.rmatvec(np.ones(self.info()["rows"]))
 
     def lsqr(self, rhs, damp=0.0, smooth=None, iter_lim=30, atol=0.0, btol=0.0, history=False, stats=False, row_weight=None,
-             col_scale=None, x0=None):
+             col_scale=None, x0=None, basis=None, smooth2=None):
         """rtmi_tomo_lsqr: min |A x - rhs|^2 + damp^2 |x|^2 + lx^2 |Dx x|^2 + ly^2 |Dy x|^2 from x = 0, smooth = (lx, ly) or None,
         every vector on the device.  -> the dict of Kirchhoff.lsqr with x [qy, qx].  row_weight [rows], col_scale and x0 [qy, qx]:
         rtmi_tomo_lsqr_weighted, min |W A D y - W (rhs - A x0)|^2 + damp^2 |y|^2 + the smoothing terms of D y, and x = x0 + D y; a
-        col_scale of 0 freezes a sample at x0's value."""
+        col_scale of 0 freezes a sample at x0's value.
+        basis (a TomoBasis of this handle's shape) or smooth2 = (mx2, my2), the second-difference weights: rtmi_tomo_lsqr_basis.
+        With a basis the unknowns are its coefficients [my, mx]: col_scale has that shape, smooth and smooth2 act on the
+        coefficient grid, x0 stays a fine model [qy, qx], and the dict gains "c" [my, mx] with x = x0 + P c."""
         rr = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
         if rr.size != self.info()["rows"]:
             raise ValueError(f"Tomography.lsqr: rhs must have {self.info()['rows']} values")
@@ -1004,13 +1007,36 @@ class Tomography:
         x = np.empty((self.qy, self.qx))
         hist = np.zeros((iter_lim, 4)) if history else None
         st = _lib.LsqrStats()
-        if row_weight is None and col_scale is None and x0 is None:
+        c = None
+        if basis is not None or smooth2 is not None:
+            reg = _lib.TomoReg()
+            if sm is not None:
+                reg.d1[0], reg.d1[1] = sm
+            if smooth2 is not None:
+                s2 = np.ascontiguousarray(smooth2, dtype=np.float64)
+                if s2.shape != (2,):
+                    raise ValueError("Tomography.lsqr: smooth2 must be (mx2, my2)")
+                reg.d2[0], reg.d2[1] = s2
+            if basis is not None and not isinstance(basis, TomoBasis):
+                raise TypeError("Tomography.lsqr: basis must be a TomoBasis")
+            ng = self.qy * self.qx if basis is None else basis.my * basis.mx
+            lo, keep = _lsqr_options("Tomography.lsqr", rr.size, ng, row_weight, col_scale, None)
+            if x0 is not None:
+                lo2, keep2 = _lsqr_options("Tomography.lsqr", rr.size, self.qy * self.qx, None, None, x0)
+                lo.x0 = lo2.x0
+            if basis is not None:
+                c = np.empty((basis.my, basis.mx))
+            check(lib().rtmi_tomo_lsqr_basis(self._open(), None if basis is None else basis._open(), C.byref(lp), C.byref(lo), C.byref(reg),
+                                             dptr(rr), dptr(c), dptr(x), dptr(hist), C.byref(st)))
+        elif row_weight is None and col_scale is None and x0 is None:
             check(lib().rtmi_tomo_lsqr(self._open(), C.byref(lp), dptr(sm), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
         else:
             lo, keep = _lsqr_options("Tomography.lsqr", rr.size, self.qy * self.qx, row_weight, col_scale, x0)
             check(lib().rtmi_tomo_lsqr_weighted(self._open(), C.byref(lp), C.byref(lo), dptr(sm), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
         out = {"x": x, "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm, "anorm": st.anorm,
                "arnorm": st.arnorm}
+        if c is not None:
+            out["c"] = c
         if history:
             out["history"] = hist[:st.itn].copy()
         if stats:
@@ -1044,6 +1070,103 @@ class Tomography:
     def close(self):
         if self._h:
             lib().rtmi_tomo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bspline_axis(q, m, degree):
+    """rtmi_bspline_axis: (first [q] int32, wgt [q, degree + 1]) of uniform B-splines of degree 0, 1 or 3 from m coefficients onto
+    q samples, the first and last sample on the ends of the knot span (include/rtmi.h).  Host only: no device is touched."""
+    q, m, degree = int(q), int(m), int(degree)
+    first = np.zeros(max(q, 1), dtype=np.int32)
+    wgt = np.zeros((max(q, 1), max(degree, 0) + 1))
+    check(lib().rtmi_bspline_axis(q, m, degree, first.ctypes.data_as(_lib._ip), dptr(wgt)))
+    return first, wgt
+
+
+class TomoBasis:
+    """A separable model basis P = Py (x) Px for a Tomography handle (rtmi_tomo_basis_*): coefficients c [my, mx] -> samples
+    x [qy, qx].  An axis is (first [q] int32, wgt [q, B]), B in 1 .. 4: sample j carries wgt[j, b] on coefficient first[j] + b;
+    first is non-decreasing.  prolong is P, restrict its transpose entry for entry; Tomography.lsqr(basis=...) solves for c.
+    The basis copies what it needs from the handle and may outlive it.  shape = (qy * qx, my * mx)."""
+
+    def __init__(self, tomo, first_x, wgt_x, first_y, wgt_y, mx, my):
+        self._h = None
+        self.qx, self.qy, self.mx, self.my = tomo.qx, tomo.qy, int(mx), int(my)
+        fx = np.ascontiguousarray(first_x, dtype=np.int32).reshape(-1)
+        fy = np.ascontiguousarray(first_y, dtype=np.int32).reshape(-1)
+        wx = np.ascontiguousarray(wgt_x, dtype=np.float64).reshape(len(fx), -1)
+        wy = np.ascontiguousarray(wgt_y, dtype=np.float64).reshape(len(fy), -1)
+        if len(fx) != self.qx or len(fy) != self.qy:
+            raise ValueError(f"TomoBasis: first_x and first_y must have {self.qx} and {self.qy} values, the handle's qx and qy")
+        h = C.c_void_p()
+        check(lib().rtmi_tomo_basis_create(tomo._open(), self.mx, wx.shape[1], fx.ctypes.data_as(_lib._ip), dptr(wx), self.my, wy.shape[1],
+                                           fy.ctypes.data_as(_lib._ip), dptr(wy), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def bspline(cls, tomo, mx, my, degree=3):
+        """Uniform B-splines (bspline_axis) of `degree` on both axes, or of (dx, dy)"""
+        dx, dy = (degree, degree) if np.ndim(degree) == 0 else degree
+        fx, wx = bspline_axis(tomo.qx, mx, dx)
+        fy, wy = bspline_axis(tomo.qy, my, dy)
+        return cls(tomo, fx, wx, fy, wy, mx, my)
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("TomoBasis: the handle is closed")
+        return self._h
+
+    @property
+    def shape(self):
+        return (self.qy * self.qx, self.my * self.mx)
+
+    def prolong(self, c):
+        """x [qy, qx] = P c for c [my, mx] (or flat)"""
+        cc = np.ascontiguousarray(c, dtype=np.float64)
+        if cc.size != self.my * self.mx:
+            raise ValueError(f"TomoBasis.prolong: c must have {self.my * self.mx} values")
+        x = np.empty((self.qy, self.qx))
+        check(lib().rtmi_tomo_basis_prolong(self._open(), dptr(cc), dptr(x)))
+        return x
+
+    def restrict(self, x):
+        """g [my, mx] = P^T x for x [qy, qx] (or flat): one fixed summation order, the same bits under every launch shape"""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        if xx.size != self.qy * self.qx:
+            raise ValueError(f"TomoBasis.restrict: x must have {self.qy * self.qx} values")
+        g = np.empty((self.my, self.mx))
+        check(lib().rtmi_tomo_basis_restrict(self._open(), dptr(xx), dptr(g)))
+        return g
+
+    _device_tensor = Tomography._device_tensor
+
+    def prolong_device(self, c, out=None):
+        """rtmi_tomo_basis_prolong_dev on torch tensors of the basis's device: c [my, mx] -> x [qy, qx] (out, if given)"""
+        import torch
+        self._device_tensor("prolong_device", c, "c")
+        x = torch.empty((self.qy, self.qx), dtype=torch.float64, device=c.device) if out is None else self._device_tensor("prolong_device", out, "out")
+        torch.cuda.synchronize(c.device)               # the library works on the null stream
+        check(lib().rtmi_tomo_basis_prolong_dev(self._open(), c.data_ptr(), x.data_ptr()))
+        return x
+
+    def restrict_device(self, x, out=None):
+        """rtmi_tomo_basis_restrict_dev on torch tensors of the basis's device: x [qy, qx] -> g [my, mx] (out, if given)"""
+        import torch
+        self._device_tensor("restrict_device", x, "x")
+        g = torch.empty((self.my, self.mx), dtype=torch.float64, device=x.device) if out is None else self._device_tensor("restrict_device", out, "out")
+        torch.cuda.synchronize(x.device)
+        check(lib().rtmi_tomo_basis_restrict_dev(self._open(), x.data_ptr(), g.data_ptr()))
+        return g
+
+    def close(self):
+        if self._h:
+            lib().rtmi_tomo_basis_destroy(self._h)
             self._h = None
 
     def __del__(self):

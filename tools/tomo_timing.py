@@ -9,7 +9,12 @@ The fan is the vert_heterogeneous op6 fan from (-2, -2), at the ray ends and wit
 --reps times: row weights, a column scale that freezes the samples outside coverage(), and a start model, all set; per-iteration
 operator_ms and vector_ms of both as median, min and max.
 
-    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--weighted] [--out FILE.json]
+--basis MX MY [--degree D [DY]] [--smooth2 A B]: also the solver over a B-spline model basis of MX x MY coefficients (DESIGN.md
+section 27) beside the solver over the field's samples, same handle and right-hand side, the two alternating --reps times after a
+warm-up of each; per-iteration operator_ms and vector_ms of both as median, min and max, the difference of the operator medians
+beside the spread, and the wall time of one prolong and one restrict call on device memory.
+
+    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--weighted] [--basis MX MY] [--out FILE.json]
 """
 import argparse
 import json
@@ -36,6 +41,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--weighted", action="store_true")
+    ap.add_argument("--basis", type=int, nargs=2, metavar=("MX", "MY"), default=None)
+    ap.add_argument("--degree", type=int, nargs="+", default=[3], metavar="D")
+    ap.add_argument("--smooth2", type=float, nargs=2, metavar=("A", "B"), default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from raytracing_amd import rt_bench as rb
@@ -119,6 +127,42 @@ def main():
         for name, v in runs.items():
             out["lsqr_weighted"][name] = {"operator_ms_per_iteration": series([q[0] for q in v]),
                                           "vector_ms_per_iteration": series([q[1] for q in v]), "bytes_device": v[0][2]}
+    if a.basis:
+        mx, my = a.basis
+        P = rb.TomoBasis.bspline(E, mx, my, degree=a.degree[0] if len(a.degree) == 1 else tuple(a.degree[:2]))
+        rhs = rng.standard_normal(R)
+        kw = dict(damp=1e-3, smooth=(0.5, 0.25), iter_lim=a.iters, stats=True)
+        bkw = dict(kw, basis=P, smooth2=tuple(a.smooth2) if a.smooth2 else None)
+        E.lsqr(rhs, **dict(bkw, iter_lim=1))                                  # warm-up: the basis kernels' code objects
+        E.lsqr(rhs, **dict(kw, iter_lim=1))
+        runs = {"fine": [], "basis": []}
+        for _ in range(a.reps):                                   # alternating
+            for name, k in (("fine", kw), ("basis", bkw)):
+                s = E.lsqr(rhs, **k)
+                n = max(s["itn"], 1)
+                runs[name].append((s["stats"]["operator_ms"] / n, s["stats"]["vector_ms"] / n, s["stats"]["bytes_device"], s["itn"]))
+        out["lsqr_basis"] = {"mx": mx, "my": my, "degree": list(a.degree), "smooth2": a.smooth2, "coefficients_over_samples": mx * my / (F.qx * F.qy)}
+        for name, v in runs.items():
+            out["lsqr_basis"][name] = {"operator_ms_per_iteration": series([q[0] for q in v]),
+                                       "vector_ms_per_iteration": series([q[1] for q in v]), "bytes_device": v[0][2], "itn": v[0][3]}
+        d = out["lsqr_basis"]
+        d["operator_ms_difference_of_medians"] = d["basis"]["operator_ms_per_iteration"]["median_ms"] - d["fine"]["operator_ms_per_iteration"]["median_ms"]
+        d["operator_ms_spread"] = max(v["operator_ms_per_iteration"]["max_ms"] - v["operator_ms_per_iteration"]["min_ms"] for v in (d["fine"], d["basis"]))
+        # the pair alone, on device memory: wall time of the call, which waits for the stream
+        import time
+        import torch
+        xd = torch.tensor(rng.standard_normal((F.qy, F.qx)), device="cuda")
+        cd = torch.tensor(rng.standard_normal((my, mx)), device="cuda")
+        gd, pd = torch.empty_like(cd), torch.empty_like(xd)
+        for name, call in (("prolong", lambda: P.prolong_device(cd, out=pd)), ("restrict", lambda: P.restrict_device(xd, out=gd))):
+            call()
+            ts = []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                call()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            d[name + "_call_ms"] = series(ts)
+        P.close()
     E.close(); EL.close(); F.close()
     text = json.dumps(out, indent=1)
     print(text)
