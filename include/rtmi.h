@@ -1047,8 +1047,49 @@ typedef struct { double d1[2], d2[2]; int64_t reserved[4]; } rtmi_tomo_reg;     
 int rtmi_tomo_lsqr_basis(rtmi_tomo *t, rtmi_tomo_basis *p, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo,
                          const rtmi_tomo_reg *reg, const double *rhs, double *c, double *x, double *history, rtmi_lsqr_stats *st);
 
+/* Many vectors at once on the tomography matrix: the products and the solver for nrhs right-hand sides.  DESIGN.md section 28.
+ * For resolution tests (checkerboards, spikes), bootstrap and jackknife, and noise sweeps: the same matrix, S vectors.  A vector
+ * is a plane: x [nrhs][qy][qx], y and w [nrhs][rows], g [nrhs][qy][qx], contiguous.  1 <= nrhs <= RTMI_LSQR_MULTI_MAX, else
+ * RTMI_ERR_ARG before any device work.
+ * Column s of every result has the bits the single-vector entry gives for column s alone:
+ *   rtmi_tomo_apply_multi      y_s = rtmi_tomo_apply (x_s): the same fixed order per row, the same five roundings per segment
+ *   rtmi_tomo_transpose_multi  g_s = rtmi_tomo_transpose (w_s): W_s = max |w_s|, bound_s = fl(Vmax W_s) and e_s are the column's
+ *                              own (one reduction launch and one read-back for all columns); W_s = 0 gives +0.0 everywhere; a
+ *                              bound_s that is not a normal number refuses the call as rtmi_tomo_transpose does, naming the first
+ *                              such column, before any product; every product contributes rint(fl(p_q w_rs) 2^-e_s) to the integer
+ *                              of its sample in column s, rounded once.
+ * A segment of the matrix is read once for a chunk of up to 8 columns; a product is one launch per append whatever nrhs is.  The
+ * accumulators of the transposed product are 128 B per sample and column, allocated by the first multi call (and grown by a call
+ * with more columns; RTMI_ERR_ALLOC if that fails, the handle stays usable) and counted in bytes_device from then on.
+ * stats: as the single products'; atomics is the sum over the columns, scale_exp the largest e_s of a column that is not zero.
+ * The host forms refuse a value that is not finite; the _dev forms take memory of the handle's device, checked as
+ * rtmi_tomo_apply_dev checks its own over all nrhs planes, and count a weight that is not finite as 0.
+ * rtmi_tomo_lsqr_multi: column s is rtmi_tomo_lsqr_basis (t, p, lp, lo_s, reg, rhs_s, ...) bit for bit -- x, c, the history rows,
+ * itn, istop and the four norms -- with the same NULL conventions: rhs [nrhs][rows], c [nrhs][my][mx] or NULL, x [nrhs][qy][qx],
+ * history [nrhs][iter_lim][4] or NULL (rows past a column's itn are zero), st [nrhs] or NULL.  lo->col_scale and lo->x0 are
+ * shared by all columns (A x0 is computed once); lo->row_weight is [rows] and shared, or with RTMI_LSQR_MULTI_ROW_WEIGHT in flags
+ * [nrhs][rows], one weighting per column (bootstrap, jackknife).  The columns advance in lock-step, one rt::LsqrState each; a
+ * column leaves the loop exactly where the single loop leaves -- a stop test, iter_lim, a zero right-hand side or first alfa, a
+ * norm or an A^T bound out of range (RTMI_LSQR_RANGE, that column's iteration abandoned) -- and from then on no kernel touches its
+ * vectors, while the others go on; the call ends when none is live.  Per iteration the two products and every vector pass are
+ * one launch, and every reduction one read-back, for all columns.  The timing fields and bytes_device of st[s] are the call's, the
+ * same in every column; operator_ms is the wall time of the products with their basis and regulariser kernels.
+ * RTMI_ERR_ARG before any device work: everything rtmi_tomo_lsqr_basis refuses (row_weight checked over all its nrhs rows values
+ * with the flag), a bad nrhs, flag bits other than RTMI_LSQR_MULTI_ROW_WEIGHT.
+ * Not covered: a start model or column scale of a column's own; multi-vector Kirchhoff solves; a column-ordered copy of the matrix; several GPUs; fp32
+ * vectors. */
+#define RTMI_LSQR_MULTI_MAX 64
+#define RTMI_LSQR_MULTI_ROW_WEIGHT 1
+int rtmi_tomo_apply_multi(rtmi_tomo *t, int32_t nrhs, const double *x, double *y, rtmi_tomo_stats *st);
+int rtmi_tomo_apply_multi_dev(rtmi_tomo *t, int32_t nrhs, const double *d_x, double *d_y, rtmi_tomo_stats *st);
+int rtmi_tomo_transpose_multi(rtmi_tomo *t, int32_t nrhs, const double *w, double *g, rtmi_tomo_stats *st);
+int rtmi_tomo_transpose_multi_dev(rtmi_tomo *t, int32_t nrhs, const double *d_w, double *d_g, rtmi_tomo_stats *st);
+int rtmi_tomo_lsqr_multi(rtmi_tomo *t, rtmi_tomo_basis *p, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo,
+                         const rtmi_tomo_reg *reg, int32_t nrhs, int32_t flags, const double *rhs, double *c, double *x,
+                         double *history, rtmi_lsqr_stats *st);
+
 typedef struct {
-    void *s_ray, *n_ray;                 /* device, dtype, layouts above */
+    void *s_ray, *n_ray;                /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */
     void *n, *gx, *gy;                   /*   BOTH precisions (fp32 batches add fp32 increments onto fp64 sums); */
     double *dist_sim, *dist_real, *T;    /*   n and its gradient are of the batch's dtype */

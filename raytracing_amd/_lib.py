@@ -164,6 +164,8 @@ class TomoReg(C.Structure):
 TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
 LSQR_OP_PLAIN, LSQR_OP_FULL, LSQR_OP_FILTERED = 0, 1, 2     # RTMI_LSQR_OP_: rtmi_kirchhoff_lsqr_weighted's operator
+LSQR_MULTI_MAX = 64     # RTMI_LSQR_MULTI_MAX: the most columns of one rtmi_tomo_*_multi call
+LSQR_MULTI_ROW_WEIGHT = 1   # RTMI_LSQR_MULTI_ROW_WEIGHT: rtmi_tomo_lsqr_multi's row_weight is [nrhs][rows]
 HILBERT_MAX_NT = 16384  # the longest trace rtmi_kirchhoff_hilbert takes: one copy of it in LDS
 FILTER_MAX_NT = 16384   # the longest trace and ...
 FILTER_MAX_TAPS = 2048  # ... the most taps rtmi_kirchhoff_set_filter takes: the trace and the filter's zeros in LDS
@@ -265,6 +267,12 @@ SYMBOLS = {
     "rtmi_tomo_basis_destroy": (None, [C.c_void_p]),
     "rtmi_tomo_lsqr_basis": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), _dp,
                                        _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_tomo_apply_multi": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(TomoStats)]),
+    "rtmi_tomo_apply_multi_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(TomoStats)]),
+    "rtmi_tomo_transpose_multi": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(TomoStats)]),
+    "rtmi_tomo_transpose_multi_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(TomoStats)]),
+    "rtmi_tomo_lsqr_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), C.c_int32,
+                                       C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(LsqrStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -15,8 +15,10 @@
 //                     drift apart), and the sums go into two integer words per sample with adds that return nothing (add_split),
 //                     read as one integer and rounded once (rt_fix128.h): the same bits in every schedule and order of appends.
 // rtmi_tomo_lsqr runs the loop of rt_lsqr_device.h over the pair, stacked with the first-difference rows of the smoothing terms.
-// The last part of the file is the model basis (rtmi_tomo_basis_*, rtmi_tomo_lsqr_basis): its own kernels
-// and entries, which call the products above as they are.
+// The model basis follows (rtmi_tomo_basis_*, rtmi_tomo_lsqr_basis): its own kernels and entries, which call
+// the products above as they are.  The last part is the same for S vectors at once (rtmi_tomo_apply_multi, _transpose_multi,
+// rtmi_tomo_lsqr_multi): k_tomo_apply_multi and k_tomo_transpose_multi read a segment once for a chunk of
+// columns held in registers, and the solver runs the loop of rt_lsqr_multi.h.  Column s has the bits of the single entries.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,10 +26,12 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rt_fix128.h"
 #include "rt_lsqr_device.h"
+#include "rt_lsqr_multi.h"
 #include "rt_sens_walk.h"
 #include "rt_tomo.h"
 #include "rt_tomo_basis.h"
@@ -65,10 +69,16 @@ struct rtmi_tomo {
     double vmax = 0.0, compile_ms = 0.0;
     unsigned long long* acc = nullptr;        // [kTomoCopies] x (A [nz], B [nz]): the transposed product's split accumulators (add_split)
     unsigned long long* red = nullptr;        // kRedWords reduction words (rt_lsqr_device.h: [0] .. [3]); [4] a fill pass's max |p|, [5] atomics
+    // the multi-vector calls', allocated by the first of them (ensure_multi): accm [acc_cols] x acc, grown when a call has more
+    // columns; redm [kMultiMax] x kRedM reduction words (rt_lsqr_multi.h)
+    unsigned long long *accm = nullptr, *redm = nullptr;
+    int acc_cols = 0;
     hipEvent_t ev[2] = {};
     size_t nz() const { return (size_t)F.qx * (size_t)F.qy; }
     size_t bytes() const {
         size_t b = ((size_t)kTomoCopies * 2 * nz() + kRedWords) * sizeof(unsigned long long);
+        b += (size_t)acc_cols * kTomoCopies * 2 * nz() * sizeof(unsigned long long);
+        if (redm) b += (size_t)kMultiMax * kRedM * sizeof(unsigned long long);
         for (const TomoBlock& k : blocks) b += k.bytes();
         return b;
     }
@@ -76,6 +86,8 @@ struct rtmi_tomo {
         for (TomoBlock& b : blocks) b.release();
         if (acc) (void)hipFree(acc);
         if (red) (void)hipFree(red);
+        if (accm) (void)hipFree(accm);
+        if (redm) (void)hipFree(redm);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -260,6 +272,21 @@ __global__ void __launch_bounds__(256) k_tomo_diff(const double* __restrict__ x,
     if (iy < qy - 1) uy[i] = __dmul_rn(ly, __dadd_rn(x[i + qx], -c));
 }
 
+// Sample i of the accumulators acc: the copies' integers B 2^32 + A summed, as the two words of rt_fix128.h (the low one biased),
+// rounded once to fp64 and scaled by 2^e
+__device__ __forceinline__ double acc_sample(const unsigned long long* __restrict__ acc, size_t nz, long i, int e) {
+    unsigned long long a = 0ull, bb = 0ull;                                   // the copies' sums: below 2^32 adds in all, neither wraps
+    for (int c = 0; c < kTomoCopies; c++) {
+        a += acc[(size_t)c * 2 * nz + i];
+        bb += acc[(size_t)c * 2 * nz + nz + i];
+    }
+    unsigned long long lo = (bb << 32) + a;
+    unsigned long long hi = (unsigned long long)((long long)bb >> 32) + (lo < a ? 1ull : 0ull);
+    const unsigned long long lo2 = lo + rt::kFixBias;
+    hi += lo2 < lo ? 1ull : 0ull;
+    return ldexp(rt::fix_to_double(lo2, hi), e);
+}
+
 // g = the accumulators, each sample's integer B 2^32 + A rounded once to fp64 (zero: +0.0 instead), plus, with ux, the transposed smoothing rows:
 // g = fl(gA + fl(r + s)), r = fl(lx fl(ux[i][j - 1] - ux[i][j])), s = fl(ly fl(uy[i - 1][j] - uy[i][j])), a missing neighbour +0.0
 __global__ void __launch_bounds__(256) k_tomo_finish(const unsigned long long* __restrict__ acc, int e,
@@ -268,20 +295,7 @@ __global__ void __launch_bounds__(256) k_tomo_finish(const unsigned long long* _
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)qx * qy) return;
     double v = 0.0;
-    if (!zero) {
-        // B 2^32 + A as the two words of rt_fix128.h (the low one biased), then its one rounding
-        const size_t nz = (size_t)qx * qy;
-        unsigned long long a = 0ull, bb = 0ull;                               // the copies' sums: below 2^32 adds in all, neither wraps
-        for (int c = 0; c < kTomoCopies; c++) {
-            a += acc[(size_t)c * 2 * nz + i];
-            bb += acc[(size_t)c * 2 * nz + nz + i];
-        }
-        unsigned long long lo = (bb << 32) + a;
-        unsigned long long hi = (unsigned long long)((long long)bb >> 32) + (lo < a ? 1ull : 0ull);
-        const unsigned long long lo2 = lo + rt::kFixBias;
-        hi += lo2 < lo ? 1ull : 0ull;
-        v = ldexp(rt::fix_to_double(lo2, hi), e);
-    }
+    if (!zero) v = acc_sample(acc, (size_t)qx * qy, i, e);
     if (ux) {
         const int iy = (int)(i / qx), jx = (int)(i % qx);
         const double xa = jx > 0 ? ux[(size_t)iy * (qx - 1) + jx - 1] : 0.0, xb = jx < qx - 1 ? ux[(size_t)iy * (qx - 1) + jx] : 0.0;
@@ -1136,4 +1150,569 @@ RTMI_EXPORT int rtmi_tomo_lsqr_basis(rtmi_tomo* t, rtmi_tomo_basis* p, const rtm
     }
     RTMI_RC(on_device(t, who));
     return tomo_lsqr_basis_run(who, t, p, lp, lo, d1, d2, rhs, c, x, history, st);
+}
+
+// ------------------------------------------------------------------------------------------------------------ many vectors at once
+// S <= kMultiMax vectors through one read of the matrix (rtmi_tomo_apply_multi, _transpose_multi, rtmi_tomo_lsqr_multi; DESIGN.md
+// section 28).  The vectors are planes: column c of x is x + c xs.  A kernel is compiled for chunks of C = 8, 4, 2 and 1
+// columns; a launch takes the widest that nrhs fills, with the chunk in blockIdx.y, so that a product is one launch per append
+// whatever nrhs is.  The last chunk may be partial: its missing columns are not written.
+namespace {
+
+// the chunk width of a call: the widest compiled one that nrhs fills
+int chunk_of(int nrhs) { return nrhs >= 8 ? 8 : nrhs >= 4 ? 4 : nrhs >= 2 ? 2 : 1; }
+
+// k_tomo_apply for the columns c0 .. c0 + C - 1: a segment's base and p are loaded once, the gathers and the five roundings are
+// the column's own.  A column past nrhs reads the last one's x and is not written.
+template <int C>
+__global__ void __launch_bounds__(256) k_tomo_apply_multi(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                                          const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
+                                                          int nrhs, const double* __restrict__ x, size_t xs, double* __restrict__ y, size_t ys) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int c0 = (int)blockIdx.y * C;
+    const int lane = (int)(r & 63);
+    const int64_t o = off[r >> 6];
+    const int n = len[r];
+    const double* xc[C];
+    double acc[C];
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        xc[j] = x + (size_t)min(c0 + j, nrhs - 1) * xs;
+        acc[j] = 0.0;
+    }
+    for (int k = 0; k < n; k++) {
+        const int b = base[rt::tomo_slot(o, k, lane)];
+        const double p0 = val[rt::tomo_value(o, k, 0, lane)], p1 = val[rt::tomo_value(o, k, 1, lane)];
+        const double p2 = val[rt::tomo_value(o, k, 2, lane)], p3 = val[rt::tomo_value(o, k, 3, lane)];
+#pragma unroll
+        for (int j = 0; j < C; j++) {
+            const double* z = xc[j] + b;
+            const double t = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p0, z[0]), __dmul_rn(p1, z[1])), __dmul_rn(p2, z[qx])), __dmul_rn(p3, z[qx + 1]));
+            acc[j] = __dadd_rn(acc[j], t);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < C; j++)
+        if (c0 + j < nrhs) y[(size_t)(c0 + j) * ys + r] = acc[j];
+}
+
+// Per column of a transposed product: the quantum's exponent; zero: the column contributes nothing and its result is +0.0
+// (W = 0); skip: the column is not the call's business, nothing of it is read or written
+struct TomoCols {
+    int e[kMultiMax];
+    unsigned long long zero, skip;
+};
+
+// k_tomo_transpose for the columns c0 .. c0 + C - 1.  The lanes step through the cells as there: the leader election, the kmin
+// reduction and the ballot happen once per step for the chunk; the integers, the wave sums and the adds are the column's own,
+// into the column's accumulators accm + c (kTomoCopies 2 nz).  A lane takes part when its weight is not zero in any column of the
+// chunk; where it is zero its products are integer zeros, which change no sum, and add_split skips them.
+template <int C>
+__global__ void __launch_bounds__(256) k_tomo_transpose_multi(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                                              const int32_t* __restrict__ base, const double* __restrict__ val, long rows,
+                                                              int qx, int nrhs, const double* __restrict__ w, size_t ws, TomoCols K,
+                                                              unsigned long long* accm, size_t nz, unsigned long long* natomics) {
+    const int c0 = (int)blockIdx.y * C;
+    const size_t copy = (size_t)(blockIdx.x % kTomoCopies) * 2 * nz;
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool in = r < rows;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t o = in ? off[r >> 6] : 0;
+    double wr[C];
+    int ec[C];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        const int c = c0 + j;
+        const bool use = c < nrhs && !(((K.zero | K.skip) >> (c & 63)) & 1ull);
+        double v = (in && use) ? w[(size_t)c * ws + r] : 0.0;
+        if (!(fabs(v) < INFINITY)) v = 0.0;                   // a weight that is not finite counts as 0
+        wr[j] = v;
+        ec[j] = K.e[c & 63];
+        any = any || v != 0.0;
+    }
+    const int n = (in && any) ? len[r] : 0;
+    long long nat = 0;
+    int k = 0, b = 0, nb = 0;
+    double p[4] = {0.0, 0.0, 0.0, 0.0}, np[4] = {0.0, 0.0, 0.0, 0.0};
+    auto load = [&](int kk) {                                 // segment kk into (nb, np)
+        if (kk < n) {
+            nb = base[rt::tomo_slot(o, kk, lane)];
+#pragma unroll
+            for (int q = 0; q < 4; q++) np[q] = val[rt::tomo_value(o, kk, q, lane)];
+        }
+    };
+    auto take = [&]() {                                       // (nb, np) becomes the lane's next segment
+        b = nb;
+#pragma unroll
+        for (int q = 0; q < 4; q++) p[q] = np[q];
+    };
+    load(0);
+    take();
+    load(1);
+    for (;;) {
+        const bool pend = k < n;
+        if (__ballot(pend) == 0ull) break;
+        int kmin = pend ? k : INT32_MAX;
+        for (int s = 1; s < 64; s <<= 1) kmin = min(kmin, __shfl_xor(kmin, s));
+        const int leader = __ffsll((long long)__ballot(pend && k == kmin)) - 1;
+        const int lb = __shfl(b, leader);
+        const bool mem = pend && b == lb;
+        const bool several = __popcll(__ballot(mem)) > 1;
+#pragma unroll
+        for (int j = 0; j < C; j++) {
+            if (c0 + j >= nrhs) break;
+            long long v[4] = {0, 0, 0, 0};
+            if (mem) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] = (long long)rint(ldexp(__dmul_rn(p[q], wr[j]), -ec[j]));
+            }
+            if (several) {
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) v[q] += __shfl_xor(v[q], s);
+            }
+            if (lane == leader) {
+                unsigned long long* const A = accm + (size_t)(c0 + j) * kTomoCopies * 2 * nz + copy;
+                unsigned long long* const B = A + nz;
+                nat += add_split(A, B, (size_t)lb, v[0]);
+                nat += add_split(A, B, (size_t)lb + 1, v[1]);
+                nat += add_split(A, B, (size_t)lb + qx, v[2]);
+                nat += add_split(A, B, (size_t)lb + qx + 1, v[3]);
+            }
+        }
+        if (mem) {
+            k++;
+            take();
+            load(k + 1);
+        }
+    }
+    for (int s = 1; s < 64; s <<= 1) nat += __shfl_xor(nat, s);
+    if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
+}
+
+// k_tomo_finish per column (blockIdx.y), without smoothing rows: g + c gs = the column's accumulators rounded once, +0.0 for a
+// zero column; a skipped column is not written
+__global__ void __launch_bounds__(256) k_tomo_finish_multi(const unsigned long long* __restrict__ accm, TomoCols K, size_t nz,
+                                                           double* __restrict__ g, size_t gs) {
+    const int c = (int)blockIdx.y;
+    if ((K.skip >> c) & 1ull) return;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)nz) return;
+    const bool zero = (K.zero >> c) & 1ull;
+    g[(size_t)c * gs + i] = zero ? 0.0 : acc_sample(accm + (size_t)c * kTomoCopies * 2 * nz, nz, i, K.e[c]);
+}
+
+// f(std::integral_constant<int, C>) for the chunk width of nrhs
+template <typename F> void by_chunk(int nrhs, F&& f) {
+    switch (chunk_of(nrhs)) {
+        case 8: f(std::integral_constant<int, 8>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        default: f(std::integral_constant<int, 1>()); break;
+    }
+}
+
+int check_nrhs(const char* who, int32_t nrhs) {
+    RTMI_ARG(nrhs >= 1 && nrhs <= kMultiMax, "nrhs must be in 1 .. 64");
+    return RTMI_OK;
+}
+
+unsigned long long all_cols(int nrhs) { return nrhs == 64 ? ~0ull : (col_bit(nrhs) - 1ull); }
+
+// The multi calls' device memory, on their first use: accumulators for nrhs columns (kept, and grown when a call has more), and
+// the reduction words
+int ensure_multi(rtmi_tomo* t, const char* who, int nrhs) {
+    if (!t->redm && hipMalloc((void**)&t->redm, (size_t)kMultiMax * kRedM * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        t->redm = nullptr;
+        return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc failed").c_str());
+    }
+    if (t->acc_cols < nrhs) {
+        if (t->accm) (void)hipFree(t->accm);
+        t->accm = nullptr;
+        t->acc_cols = 0;
+        if (hipMalloc((void**)&t->accm, (size_t)nrhs * kTomoCopies * 2 * t->nz() * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            t->accm = nullptr;
+            return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc of the accumulators of " + std::to_string(nrhs) +
+                                                       " columns failed").c_str());
+        }
+        t->acc_cols = nrhs;
+    }
+    return RTMI_OK;
+}
+
+// y + c ys [rows] = A (x + c xs) for c < nrhs, on device pointers the callers have checked: one launch per append
+int apply_multi_dev(rtmi_tomo* t, const char* who, int nrhs, const double* d_x, size_t xs, double* d_y, size_t ys, double* ms) {
+    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
+    const int C = chunk_of(nrhs);
+    for (const TomoBlock& b : t->blocks) {
+        const dim3 grid(blocks((long)b.rows).x, (unsigned)((nrhs + C - 1) / C));
+        by_chunk(nrhs, [&](auto c) {
+            hipLaunchKernelGGL((k_tomo_apply_multi<decltype(c)::value>), grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows,
+                               t->F.qx, nrhs, d_x, xs, d_y + b.first, ys);
+        });
+        RTMI_HIP(hipGetLastError());
+    }
+    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
+    RTMI_HIP(hipEventSynchronize(t->ev[1]));
+    float f = 0.0f;
+    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
+    *ms = f;
+    return RTMI_OK;
+}
+
+// g + c gs [qy][qx] = A^T (w + c ws) for the columns c of `mask`.  Every column has its own W, bound and exponent, from one
+// reduction launch and one read-back.  range [nrhs]: the column's bound is not a normal number, and nothing of it is written;
+// with `strict` the call then stops before any product.  exps [nrhs] (or NULL): the columns' exponents, 0 for a zero column.
+int transpose_multi_dev(rtmi_tomo* t, const char* who, int nrhs, const double* d_w, size_t ws, double* d_g, size_t gs,
+                        unsigned long long mask, bool strict, bool* range, double* ms, int64_t* atomics, int32_t* exps) {
+    *ms = 0.0;
+    if (atomics) *atomics = 0;
+    const size_t nz = t->nz();
+    RTMI_RC(ensure_multi(t, who, nrhs));
+    unsigned long long h[kMultiMax * kRedM] = {};
+    if (t->rows > 0 && t->segments > 0 && t->vmax > 0.0) {
+        const size_t bytes = (size_t)nrhs * kRedM * sizeof(unsigned long long);
+        RTMI_HIP(hipMemsetAsync(t->redm, 0, bytes, nullptr));
+        hipLaunchKernelGGL(k_absmax_finite_m, dim3(stride_blocks(t->cus, (size_t)t->rows, 1).x, (unsigned)nrhs), dim3(256), 0, nullptr, d_w, ws,
+                           (long)t->rows, mask, t->redm);
+        RTMI_HIP(hipGetLastError());
+        RTMI_HIP(hipMemcpy(h, t->redm, bytes, hipMemcpyDeviceToHost));
+    }
+    TomoCols K{};
+    K.skip = ~mask;
+    bool work = false, refused = false;
+    for (int c = 0; c < nrhs; c++) {
+        range[c] = false;
+        if (exps) exps[c] = 0;
+        if (!(mask & col_bit(c))) continue;
+        double W = 0.0;
+        std::memcpy(&W, &h[(size_t)c * kRedM], sizeof(double));
+        if (!(W > 0.0)) {
+            K.zero |= col_bit(c);
+            continue;
+        }
+        const double bound = t->vmax * W;
+        if (!std::isnormal(bound)) {
+            range[c] = true;
+            refused = true;
+            K.skip |= col_bit(c);
+            continue;
+        }
+        K.e[c] = rt::fix_exponent(bound);
+        if (exps) exps[c] = K.e[c];
+        work = true;
+    }
+    if (strict && refused) return RTMI_OK;
+    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
+    if (work) {
+        RTMI_HIP(hipMemsetAsync(t->accm, 0, (size_t)nrhs * kTomoCopies * 2 * nz * sizeof(unsigned long long), nullptr));
+        RTMI_HIP(hipMemsetAsync(t->red + 5, 0, sizeof(unsigned long long), nullptr));
+        const int C = chunk_of(nrhs);
+        for (const TomoBlock& b : t->blocks) {
+            const dim3 grid(blocks((long)b.rows).x, (unsigned)((nrhs + C - 1) / C));
+            by_chunk(nrhs, [&](auto c) {
+                hipLaunchKernelGGL((k_tomo_transpose_multi<decltype(c)::value>), grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val,
+                                   (long)b.rows, t->F.qx, nrhs, d_w + b.first, ws, K, t->accm, nz, t->red + 5);
+            });
+            RTMI_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_tomo_finish_multi, dim3(blocks((long)nz).x, (unsigned)nrhs), dim3(256), 0, nullptr, t->accm, K, nz, d_g, gs);
+    RTMI_HIP(hipGetLastError());
+    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
+    RTMI_HIP(hipEventSynchronize(t->ev[1]));
+    float f = 0.0f;
+    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
+    *ms = f;
+    if (work && atomics) {
+        unsigned long long n = 0;
+        RTMI_HIP(hipMemcpy(&n, t->red + 5, sizeof(n), hipMemcpyDeviceToHost));
+        *atomics = (int64_t)n;
+    }
+    return RTMI_OK;
+}
+
+// the public transposed calls' end: a refusal that names the first column out of range, else the stats
+int transpose_multi_done(const rtmi_tomo* t, const char* who, int nrhs, const bool* range, const int32_t* exps, double ms, int64_t atomics,
+                         rtmi_tomo_stats* st) {
+    for (int c = 0; c < nrhs; c++)
+        RTMI_ARG(!range[c], "column " + std::to_string(c) + ": Vmax max|w| is not a normal number (RTMI_LSQR_RANGE)");
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms; st->atomics = atomics;
+        int32_t e = 0;
+        bool first = true;
+        for (int c = 0; c < nrhs; c++)
+            if (exps[c] != 0 && (first || exps[c] > e)) { e = exps[c]; first = false; }
+        st->scale_exp = e;
+    }
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_tomo_apply_multi_dev(rtmi_tomo* t, int32_t nrhs, const double* d_x, double* d_y, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_apply_multi_dev";
+    RTMI_ARG(t, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_ARG(d_x, "null d_x");
+    RTMI_ARG(d_y || t->rows == 0, "null d_y");
+    RTMI_RC(on_device(t, who));
+    RTMI_RC(check_device_pointer(t->device, who, d_x, (size_t)nrhs * t->nz() * sizeof(double), "d_x"));
+    if (t->rows) RTMI_RC(check_device_pointer(t->device, who, d_y, (size_t)nrhs * (size_t)t->rows * sizeof(double), "d_y"));
+    double ms = 0.0;
+    RTMI_RC(apply_multi_dev(t, who, nrhs, d_x, t->nz(), d_y, (size_t)t->rows, &ms));
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_apply_multi(rtmi_tomo* t, int32_t nrhs, const double* x, double* y, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_apply_multi";
+    RTMI_ARG(t, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_ARG(x, "null x");
+    RTMI_ARG(y || t->rows == 0, "null y");
+    const size_t nx = (size_t)nrhs * t->nz(), ny = (size_t)nrhs * (size_t)t->rows;
+    RTMI_RC(finite_all(who, x, nx, "x has a value that is not finite"));
+    RTMI_RC(on_device(t, who));
+    DevMem mem;
+    double *dx = nullptr, *dy = nullptr;
+    RTMI_HIP(mem.get(&dx, nx * sizeof(double)));
+    RTMI_HIP(mem.get(&dy, ny * sizeof(double)));
+    RTMI_HIP(hipMemcpy(dx, x, nx * sizeof(double), hipMemcpyHostToDevice));
+    double ms = 0.0;
+    RTMI_RC(apply_multi_dev(t, who, nrhs, dx, t->nz(), dy, (size_t)t->rows, &ms));
+    if (ny) RTMI_HIP(hipMemcpy(y, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        fill_stats(t, st);
+        st->kernel_ms = ms;
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tomo_transpose_multi_dev(rtmi_tomo* t, int32_t nrhs, const double* d_w, double* d_g, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_transpose_multi_dev";
+    RTMI_ARG(t, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_ARG(d_w || t->rows == 0, "null d_w");
+    RTMI_ARG(d_g, "null d_g");
+    RTMI_RC(on_device(t, who));
+    if (t->rows) RTMI_RC(check_device_pointer(t->device, who, d_w, (size_t)nrhs * (size_t)t->rows * sizeof(double), "d_w"));
+    RTMI_RC(check_device_pointer(t->device, who, d_g, (size_t)nrhs * t->nz() * sizeof(double), "d_g"));
+    bool range[kMultiMax];
+    int32_t exps[kMultiMax];
+    double ms = 0.0;
+    int64_t atomics = 0;
+    RTMI_RC(transpose_multi_dev(t, who, nrhs, d_w, (size_t)t->rows, d_g, t->nz(), all_cols(nrhs), true, range, &ms, &atomics, exps));
+    return transpose_multi_done(t, who, nrhs, range, exps, ms, atomics, st);
+}
+
+RTMI_EXPORT int rtmi_tomo_transpose_multi(rtmi_tomo* t, int32_t nrhs, const double* w, double* g, rtmi_tomo_stats* st) {
+    const char* who = "rtmi_tomo_transpose_multi";
+    RTMI_ARG(t, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_ARG(w || t->rows == 0, "null w");
+    RTMI_ARG(g, "null g");
+    const size_t nw = (size_t)nrhs * (size_t)t->rows, ng = (size_t)nrhs * t->nz();
+    RTMI_RC(finite_all(who, w, nw, "w has a value that is not finite"));
+    RTMI_RC(on_device(t, who));
+    DevMem mem;
+    double *dw = nullptr, *dg = nullptr;
+    RTMI_HIP(mem.get(&dw, nw * sizeof(double)));
+    RTMI_HIP(mem.get(&dg, ng * sizeof(double)));
+    if (nw) RTMI_HIP(hipMemcpy(dw, w, nw * sizeof(double), hipMemcpyHostToDevice));
+    bool range[kMultiMax];
+    int32_t exps[kMultiMax];
+    double ms = 0.0;
+    int64_t atomics = 0;
+    RTMI_RC(transpose_multi_dev(t, who, nrhs, dw, (size_t)t->rows, dg, t->nz(), all_cols(nrhs), true, range, &ms, &atomics, exps));
+    RTMI_RC(transpose_multi_done(t, who, nrhs, range, exps, ms, atomics, nullptr));
+    RTMI_HIP(hipMemcpy(g, dg, ng * sizeof(double), hipMemcpyDeviceToHost));
+    return transpose_multi_done(t, who, nrhs, range, exps, ms, atomics, st);
+}
+
+namespace {
+
+// tomo_lsqr_basis_run for nrhs columns: the same stacked operator on planes, the loop of rt_lsqr_multi.h.  The products and the
+// vector passes are one launch for all columns; the basis and regulariser kernels, which work on model-sized vectors, are
+// launched per live column.  wr_cols: the row weights are [nrhs][rows], else [rows] for all.
+int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                        const double* d1, const double* d2, int S, bool wr_cols, const double* rhs, double* c, double* x, double* history,
+                        rtmi_lsqr_stats* st) {
+    const size_t rows = (size_t)t->rows, nm = t->nz();
+    const size_t gx = p ? (size_t)p->mx : (size_t)t->F.qx, gy = p ? (size_t)p->my : (size_t)t->F.qy, ng = gx * gy;
+    const size_t n1x = d1 ? gy * (gx - 1) : 0, n1y = d1 ? (gy - 1) * gx : 0;
+    const size_t n2x = d2 && gx > 2 ? gy * (gx - 2) : 0, n2y = d2 && gy > 2 ? (gy - 2) * gx : 0;
+    const size_t per = rows + n1x + n1y + n2x + n2y;
+    const double t_begin = now_ms();
+    const std::string no_mem = std::string(who) + ": hipMalloc failed";
+    RTMI_RC(ensure_multi(t, who, S));
+    DevMem mem;
+    size_t doubles = 0;
+    auto get = [&](double** q, size_t n) {
+        doubles += n;
+        return mem.get(q, n * sizeof(double)) == hipSuccess;
+    };
+    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *yd = nullptr, *Atu = nullptr, *xf = nullptr, *gf = nullptr, *x0 = nullptr,
+           *ax0 = nullptr;
+    for (double** q : {&u, &Av})
+        if (!get(q, S * per)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    for (double** q : {&v, &w, &yd, &Atu})
+        if (!get(q, S * ng)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    if (p)
+        for (double** q : {&xf, &gf})
+            if (!get(q, S * nm)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    LsqrOptions O;
+    O.nrhs = rows;
+    size_t wrs = 0;
+    if (lo && lo->x0) {
+        if (!get(&x0, nm) || !get(&ax0, rows)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(x0, lo->x0, nm * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (lo && lo->row_weight) {
+        // rows `rows` .. per - 1, a regulariser's, carry no weight: their factor is 1.0
+        const size_t nw = wr_cols ? (size_t)S : 1;
+        std::vector<double> h(nw * per, 1.0);
+        for (size_t s = 0; s < nw; s++) std::memcpy(h.data() + s * per, lo->row_weight + s * rows, rows * sizeof(double));
+        double* d = nullptr;
+        if (!get(&d, nw * per) || !get(&O.uw, S * per)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(d, h.data(), nw * per * sizeof(double), hipMemcpyHostToDevice));
+        O.wr = d;
+        wrs = wr_cols ? per : 0;
+    }
+    if (lo && lo->col_scale) {
+        double* d = nullptr;
+        if (!get(&d, ng) || !get(&O.vd, S * ng)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(d, lo->col_scale, ng * sizeof(double), hipMemcpyHostToDevice));
+        O.dc = d;
+    }
+    const VecM V{t->redm, t->cus, S};
+    const unsigned long long all = all_cols(S);
+    double operator_ms = 0.0;
+    auto each = [&](unsigned long long mask, auto&& f) {
+        for (int s = 0; s < S; s++)
+            if (mask & col_bit(s)) RTMI_RC(f((size_t)s));
+        return (int)RTMI_OK;
+    };
+    // the stacked operator [A P | Dx | Dy | Dxx | Dyy] on the planes s [S][G], and its transpose
+    auto Ax = [&](const double* s, double* y, unsigned long long mask) {
+        const double t0 = now_ms();
+        double ms = 0.0;
+        if (p) RTMI_RC(each(mask, [&](size_t k) { return basis_prolong_dev(p, who, s + k * ng, xf + k * nm); }));
+        RTMI_RC(apply_multi_dev(t, who, S, p ? xf : s, nm, y, per, &ms));
+        operator_ms += now_ms() - t0;
+        if (d1 || d2)
+            RTMI_RC(each(mask, [&](size_t k) {
+                const double* sk = s + k * ng;
+                double* yk = y + k * per + rows;
+                if (d1) hipLaunchKernelGGL(k_tomo_diff, blocks((long)ng), dim3(256), 0, nullptr, sk, (int)gx, (int)gy, d1[0], d1[1], yk, yk + n1x);
+                if (d2)
+                    hipLaunchKernelGGL(k_tomo_diff2, blocks((long)ng), dim3(256), 0, nullptr, sk, (int)gx, (int)gy, d2[0], d2[1], yk + n1x + n1y,
+                                       yk + n1x + n1y + n2x);
+                RTMI_HIP(hipGetLastError());
+                return (int)RTMI_OK;
+            }));
+        return (int)RTMI_OK;
+    };
+    auto At = [&](const double* s, double* g, unsigned long long mask, bool* range) {
+        const double t0 = now_ms();
+        double ms = 0.0;
+        RTMI_RC(transpose_multi_dev(t, who, S, s, per, p ? gf : g, p ? nm : ng, mask, false, range, &ms, nullptr, nullptr));
+        unsigned long long ok = 0ull;
+        for (int k = 0; k < S; k++)
+            if ((mask & col_bit(k)) && !range[k]) ok |= col_bit(k);
+        if (p || d1 || d2) {
+            RTMI_RC(each(ok, [&](size_t k) {
+                double* gk = g + k * ng;
+                const double* sk = s + k * per + rows;
+                if (p) RTMI_RC(basis_restrict_dev(p, who, gf + k * nm, gk));
+                if (d1 || d2) {
+                    hipLaunchKernelGGL(k_tomo_reg_t, blocks((long)ng), dim3(256), 0, nullptr, gk, (int)gx, (int)gy, d1 ? sk : nullptr,
+                                       d1 ? sk + n1x : nullptr, d1 ? d1[0] : 0.0, d1 ? d1[1] : 0.0, d2 ? sk + n1x + n1y : nullptr,
+                                       d2 ? sk + n1x + n1y + n2x : nullptr, d2 ? d2[0] : 0.0, d2 ? d2[1] : 0.0);
+                    RTMI_HIP(hipGetLastError());
+                }
+                return (int)RTMI_OK;
+            }));
+            RTMI_HIP(hipStreamSynchronize(nullptr));
+        }
+        operator_ms += now_ms() - t0;
+        return (int)RTMI_OK;
+    };
+    // the right-hand sides go up once: column s into the first `rows` values of plane s
+    RTMI_HIP(hipMemsetAsync(u, 0, (size_t)S * per * sizeof(double), nullptr));
+    RTMI_HIP(hipMemsetAsync(yd, 0, (size_t)S * ng * sizeof(double), nullptr));
+    RTMI_HIP(hipStreamSynchronize(nullptr));
+    RTMI_HIP(hipMemcpy2D(u, per * sizeof(double), rhs, rows * sizeof(double), rows * sizeof(double), (size_t)S, hipMemcpyHostToDevice));
+    if (x0) {                                                                         // u = fl(rhs - A x0) over the data rows; A x0 once
+        double ms = 0.0;
+        RTMI_RC(apply_dev(t, who, x0, ax0, &ms));
+        operator_ms += ms;
+        RTMI_RC(sub_mul_m(who, V, u, per, ax0, 0, nullptr, 0, rows, all));
+    }
+    std::vector<rtmi_lsqr_stats> out((size_t)S);
+    RTMI_RC(lsqr_loop_multi(who, V, lp, per, ng, LsqrVectors{u, Av, v, w, yd, Atu}, Ax, At, history, out.data(), O, wrs));   // yd = fl(dc y): c
+    if (c) RTMI_HIP(hipMemcpy(c, yd, (size_t)S * ng * sizeof(double), hipMemcpyDeviceToHost));
+    double* xd = yd;
+    if (p) {
+        RTMI_RC(each(all, [&](size_t k) { return basis_prolong_dev(p, who, yd + k * ng, xf + k * nm); }));
+        xd = xf;
+    }
+    if (x0) RTMI_RC(result_m(who, V, xd, nm, nullptr, x0, nm, all));
+    RTMI_HIP(hipMemcpy(x, xd, (size_t)S * nm * sizeof(double), hipMemcpyDeviceToHost));
+    const double total = now_ms() - t_begin;
+    const int64_t bytes = (int64_t)(doubles * sizeof(double) + t->bytes() + (p ? p->bytes() : 0));
+    for (int s = 0; s < S; s++) {
+        out[(size_t)s].total_ms = total;
+        out[(size_t)s].operator_ms = operator_ms;
+        out[(size_t)s].bytes_device = bytes;
+        if (st) st[s] = out[(size_t)s];
+    }
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_tomo_lsqr_multi(rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                                     const rtmi_tomo_reg* reg, int32_t nrhs, int32_t flags, const double* rhs, double* c, double* x,
+                                     double* history, rtmi_lsqr_stats* st) {
+    const char* who = "rtmi_tomo_lsqr_multi";
+    RTMI_ARG(t, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_ARG((flags & ~RTMI_LSQR_MULTI_ROW_WEIGHT) == 0, "flags has bits other than RTMI_LSQR_MULTI_ROW_WEIGHT");
+    const double *d1 = nullptr, *d2 = nullptr;
+    if (reg) {
+        for (const double v : {reg->d1[0], reg->d1[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d1 must be finite and >= 0");
+        for (const double v : {reg->d2[0], reg->d2[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d2 must be finite and >= 0");
+        if (reg->d1[0] != 0.0 || reg->d1[1] != 0.0) d1 = reg->d1;
+        if (reg->d2[0] != 0.0 || reg->d2[1] != 0.0) d2 = reg->d2;
+    }
+    if (p)
+        RTMI_ARG(p->qx == t->F.qx && p->qy == t->F.qy && p->device == t->device, "the basis was made for another shape or device than the handle's");
+    RTMI_ARG(lp, "null params");
+    RTMI_ARG(rhs, "null rhs");
+    RTMI_ARG(x, "null x");
+    RTMI_RC(lsqr_check_params(who, lp));
+    RTMI_ARG(t->rows >= 1, "the handle has no rows");
+    const size_t rows = (size_t)t->rows;
+    const bool wr_cols = (flags & RTMI_LSQR_MULTI_ROW_WEIGHT) != 0;
+    RTMI_RC(finite_all(who, rhs, (size_t)nrhs * rows, "rhs has a value that is not finite"));
+    if (lo) {
+        rtmi_lsqr_options coarse = *lo, fine = *lo;                               // col_scale has |G| values, x0 qy qx
+        coarse.x0 = nullptr;
+        fine.row_weight = nullptr; fine.col_scale = nullptr;
+        RTMI_RC(lsqr_check_options(who, &coarse, (wr_cols ? (size_t)nrhs : 1) * rows, p ? p->ng() : t->nz()));
+        RTMI_RC(lsqr_check_options(who, &fine, 0, t->nz()));
+    }
+    RTMI_RC(on_device(t, who));
+    if (history) std::memset(history, 0, (size_t)nrhs * (size_t)lp->iter_lim * 4 * sizeof(double));
+    return tomo_lsqr_multi_run(who, t, p, lp, lo, d1, d2, (int)nrhs, wr_cols, rhs, c, x, history, st);
 }

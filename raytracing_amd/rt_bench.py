@@ -1044,6 +1044,170 @@ class Tomography:
                             "bytes_device": int(st.bytes_device)}
         return out
 
+    # ---- many vectors at once (rtmi_tomo_*_multi): column s has the bits of the single call on column s
+    def matmat(self, X, stats=False):
+        """Y [S, rows] = A X[s] for X [S, qy, qx] (or [S, qy * qx]): rtmi_tomo_apply_multi in groups of at most 64 columns"""
+        xx = np.ascontiguousarray(X, dtype=np.float64)
+        nz = self.qy * self.qx
+        if xx.ndim < 2 or xx.size != xx.shape[0] * nz:
+            raise ValueError(f"Tomography.matmat: X must be [S, {self.qy}, {self.qx}] or [S, {nz}]")
+        S, rows = xx.shape[0], self.info()["rows"]
+        xx = xx.reshape(S, nz)
+        y = np.empty((S, rows))
+        st = _lib.TomoStats()
+        ms = 0.0
+        for a in range(0, S, _lib.LSQR_MULTI_MAX):
+            b = min(S, a + _lib.LSQR_MULTI_MAX)
+            check(lib().rtmi_tomo_apply_multi(self._open(), b - a, dptr(xx[a:b]), dptr(y[a:b]), C.byref(st)))
+            ms += st.kernel_ms
+        if stats:
+            out = tomo_stats(st) if S else self.info()
+            out["kernel_ms"] = ms
+            return y, out
+        return y
+
+    def rmatmat(self, W, stats=False):
+        """G [S, qy, qx] = A^T W[s] for W [S, rows]: rtmi_tomo_transpose_multi in groups of at most 64 columns"""
+        ww = np.ascontiguousarray(W, dtype=np.float64)
+        rows = self.info()["rows"]
+        if ww.ndim != 2 or ww.shape[1] != rows:
+            raise ValueError(f"Tomography.rmatmat: W must be [S, {rows}]")
+        S = ww.shape[0]
+        g = np.empty((S, self.qy, self.qx))
+        st = _lib.TomoStats()
+        ms, atomics = 0.0, 0
+        for a in range(0, S, _lib.LSQR_MULTI_MAX):
+            b = min(S, a + _lib.LSQR_MULTI_MAX)
+            check(lib().rtmi_tomo_transpose_multi(self._open(), b - a, dptr(ww[a:b]), dptr(g[a:b]), C.byref(st)))
+            ms += st.kernel_ms
+            atomics += st.atomics
+        if stats:
+            out = tomo_stats(st) if S else self.info()
+            out["kernel_ms"], out["atomics"] = ms, atomics
+            return g, out
+        return g
+
+    def matmat_device(self, X, out=None, stats=False):
+        """rtmi_tomo_apply_multi_dev on torch tensors of the handle's device: X [S, qy, qx] -> Y [S, rows] (out, if given), S <= 64"""
+        import torch
+        self._device_tensor("matmat_device", X, "X")
+        S = int(X.shape[0]) if X.dim() >= 2 else 0
+        y = torch.empty((S, self.info()["rows"]), dtype=torch.float64, device=X.device) if out is None else self._device_tensor("matmat_device", out, "out")
+        st = _lib.TomoStats()
+        torch.cuda.synchronize(X.device)               # the library works on the null stream
+        check(lib().rtmi_tomo_apply_multi_dev(self._open(), S, X.data_ptr(), y.data_ptr(), C.byref(st)))
+        return (y, tomo_stats(st)) if stats else y
+
+    def rmatmat_device(self, W, out=None, stats=False):
+        """rtmi_tomo_transpose_multi_dev on torch tensors of the handle's device: W [S, rows] -> G [S, qy, qx] (out, if given), S <= 64"""
+        import torch
+        self._device_tensor("rmatmat_device", W, "W")
+        S = int(W.shape[0]) if W.dim() >= 2 else 0
+        g = torch.empty((S, self.qy, self.qx), dtype=torch.float64, device=W.device) if out is None else self._device_tensor("rmatmat_device", out, "out")
+        st = _lib.TomoStats()
+        torch.cuda.synchronize(W.device)
+        check(lib().rtmi_tomo_transpose_multi_dev(self._open(), S, W.data_ptr(), g.data_ptr(), C.byref(st)))
+        return (g, tomo_stats(st)) if stats else g
+
+    def lsqr_multi(self, rhs, damp=0.0, smooth=None, iter_lim=30, atol=0.0, btol=0.0, history=False, stats=False, row_weight=None,
+                   col_scale=None, x0=None, basis=None, smooth2=None, group=None):
+        """rtmi_tomo_lsqr_multi: Tomography.lsqr for the S right-hand sides rhs [S, rows] in lock-step -> a list of S dicts of
+        Tomography.lsqr's shape, each with the bits of lsqr(rhs[s], ...).  The keyword arguments are lsqr's; col_scale and x0 are
+        shared by all columns, row_weight is [rows] for all or [S, rows], one weighting per column.  Any S: the call works in
+        groups of at most 64 columns, or of `group`."""
+        who = "Tomography.lsqr_multi"
+        rows, nz = self.info()["rows"], self.qy * self.qx
+        rr = np.ascontiguousarray(rhs, dtype=np.float64)
+        if rr.ndim != 2 or rr.shape[1] != rows:
+            raise ValueError(f"{who}: rhs must be [S, {rows}]")
+        S = rr.shape[0]
+        iter_lim = int(iter_lim)
+        if iter_lim < 1:
+            raise ValueError(f"{who}: iter_lim must be >= 1")
+        group = _lib.LSQR_MULTI_MAX if group is None else int(group)
+        if not 1 <= group <= _lib.LSQR_MULTI_MAX:
+            raise ValueError(f"{who}: group must be in 1 .. {_lib.LSQR_MULTI_MAX}")
+        lp = _lib.LsqrParams()
+        lp.iter_lim, lp.damp, lp.atol, lp.btol = iter_lim, float(damp), float(atol), float(btol)
+        reg = _lib.TomoReg()
+        for name, pair, dst in (("smooth", smooth, reg.d1), ("smooth2", smooth2, reg.d2)):
+            if pair is not None:
+                pp = np.ascontiguousarray(pair, dtype=np.float64)
+                if pp.shape != (2,):
+                    raise ValueError(f"{who}: {name} must be a pair")
+                dst[0], dst[1] = pp
+        if basis is not None and not isinstance(basis, TomoBasis):
+            raise TypeError(f"{who}: basis must be a TomoBasis")
+        gshape = (self.qy, self.qx) if basis is None else (basis.my, basis.mx)
+        lo, keep = _lsqr_options(who, rows, gshape[0] * gshape[1], None, col_scale, None)
+        if x0 is not None:
+            lo2, keep2 = _lsqr_options(who, rows, nz, None, None, x0)
+            lo.x0 = lo2.x0
+        wr, flags = None, 0
+        if row_weight is not None:
+            wr = np.ascontiguousarray(row_weight, dtype=np.float64)
+            if wr.shape == (S, rows) and wr.ndim == 2:
+                flags = _lib.LSQR_MULTI_ROW_WEIGHT
+            elif wr.size == rows and wr.ndim <= 1 or wr.shape == (1, rows):
+                wr = wr.reshape(rows)
+            else:
+                raise ValueError(f"{who}: row_weight must be [{rows}] or [S, {rows}]")
+        out = []
+        for a in range(0, S, group):
+            b = min(S, a + group)
+            n = b - a
+            x = np.empty((n, self.qy, self.qx))
+            c = np.empty((n,) + gshape) if basis is not None else None
+            hist = np.zeros((n, iter_lim, 4)) if history else None
+            st = (_lib.LsqrStats * n)()
+            if wr is not None:
+                wg = np.ascontiguousarray(wr[a:b]) if flags else wr
+                lo.row_weight = dptr(wg)
+            check(lib().rtmi_tomo_lsqr_multi(self._open(), None if basis is None else basis._open(), C.byref(lp), C.byref(lo), C.byref(reg),
+                                             n, flags, dptr(np.ascontiguousarray(rr[a:b])), dptr(c), dptr(x), dptr(hist), st))
+            for s in range(n):
+                o = {"x": x[s], "istop": int(st[s].istop), "itn": int(st[s].itn), "r1norm": st[s].r1norm, "r2norm": st[s].r2norm,
+                     "anorm": st[s].anorm, "arnorm": st[s].arnorm}
+                if c is not None:
+                    o["c"] = c[s]
+                if history:
+                    o["history"] = hist[s, :st[s].itn].copy()
+                if stats:
+                    o["stats"] = {"total_ms": st[s].total_ms, "operator_ms": st[s].operator_ms, "vector_ms": st[s].vector_ms,
+                                  "bytes_device": int(st[s].bytes_device)}
+                out.append(o)
+        return out
+
+    def recover(self, models, **lsqr_kw):
+        """The resolution test: d_s = A m_s (matmat), then lsqr_multi(d, **lsqr_kw) -> (the recovered models [S, qy, qx], the
+        dicts).  models [S, qy, qx], e.g. checkerboard(...) or spikes(...) stacked."""
+        mm = np.ascontiguousarray(models, dtype=np.float64)
+        if mm.ndim != 3 or mm.shape[1:] != (self.qy, self.qx):
+            raise ValueError(f"Tomography.recover: models must be [S, {self.qy}, {self.qx}]")
+        outs = self.lsqr_multi(self.matmat(mm), **lsqr_kw)
+        return np.stack([o["x"] for o in outs]) if outs else np.empty((0, self.qy, self.qx)), outs
+
+    def bootstrap(self, rhs, n, seed, results=False, **lsqr_kw):
+        """n bootstrap replicates of lsqr(rhs, ...): replicate k weighs row r by the square root of its multiplicity in a draw of
+        `rows` rows with replacement (bootstrap_weights(rows, n, seed)), times the caller's row_weight [rows], if given; one
+        lsqr_multi over them.  -> (mean, standard deviation with ddof 1) of x over the replicates, [qy, qx] each, and with
+        results=True the per-replicate dicts as well."""
+        rows = self.info()["rows"]
+        rr = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
+        if rr.size != rows:
+            raise ValueError(f"Tomography.bootstrap: rhs must have {rows} values")
+        w = bootstrap_weights(rows, n, seed)
+        base = lsqr_kw.pop("row_weight", None)
+        if base is not None:
+            bb = np.ascontiguousarray(base, dtype=np.float64).reshape(-1)
+            if bb.size != rows:
+                raise ValueError(f"Tomography.bootstrap: row_weight must have {rows} values")
+            w = w * bb[None, :]
+        outs = self.lsqr_multi(np.broadcast_to(rr, (len(w), rows)), row_weight=w, **lsqr_kw)
+        xs = np.stack([o["x"] for o in outs])
+        mean, std = xs.mean(axis=0), xs.std(axis=0, ddof=1)
+        return (mean, std, outs) if results else (mean, std)
+
     def read(self):
         """rtmi_tomo_read: (row_ptr [rows + 1], base [segments], val [segments, 4]), rows in order, segments in visit order"""
         i = self.info()
@@ -1077,6 +1241,42 @@ class Tomography:
             self.close()
         except Exception:
             pass
+
+
+def checkerboard(qy, qx, cell, amplitude=1.0):
+    """A checkerboard model [qy, qx] for Tomography.recover: squares of `cell` samples (or cell = (cy, cx)), +amplitude where
+    (i // cy + j // cx) is even -- the square at the origin --, -amplitude where it is odd.  Pure numpy."""
+    cy, cx = (int(cell), int(cell)) if np.ndim(cell) == 0 else (int(cell[0]), int(cell[1]))
+    if cy < 1 or cx < 1:
+        raise ValueError("checkerboard: cell must be >= 1")
+    odd = (np.arange(int(qy))[:, None] // cy + np.arange(int(qx))[None, :] // cx) % 2 == 1
+    return np.where(odd, -float(amplitude), float(amplitude))
+
+
+def spikes(qy, qx, nodes, amplitude=1.0):
+    """One spike model per node for Tomography.recover: [len(nodes), qy, qx], model s is `amplitude` at nodes[s] = (i, j) and
+    0.0 elsewhere.  Pure numpy."""
+    nn = np.asarray(nodes, dtype=np.int64).reshape(-1, 2)
+    if len(nn) and (nn.min() < 0 or nn[:, 0].max() >= qy or nn[:, 1].max() >= qx):
+        raise ValueError("spikes: a node lies outside the grid")
+    out = np.zeros((len(nn), int(qy), int(qx)))
+    out[np.arange(len(nn)), nn[:, 0], nn[:, 1]] = float(amplitude)
+    return out
+
+
+def bootstrap_weights(rows, n, seed):
+    """Row weights [n, rows] of n bootstrap replicates: replicate k draws `rows` row indices with replacement from
+    numpy.random.Generator(numpy.random.PCG64(seed)), the replicates one after the other from the one generator; a row's weight is
+    the square root of its multiplicity in the draw, 0.0 for a row not drawn, so that the weighted misfit counts a row as often
+    as it was drawn and every replicate's squared weights sum to `rows`.  Pure numpy."""
+    rows, n = int(rows), int(n)
+    if rows < 1 or n < 1:
+        raise ValueError("bootstrap_weights: rows and n must be >= 1")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    w = np.empty((n, rows))
+    for k in range(n):
+        w[k] = np.sqrt(np.bincount(rng.integers(0, rows, size=rows), minlength=rows).astype(np.float64))
+    return w
 
 
 def bspline_axis(q, m, degree):

@@ -14,7 +14,14 @@ section 27) beside the solver over the field's samples, same handle and right-ha
 warm-up of each; per-iteration operator_ms and vector_ms of both as median, min and max, the difference of the operator medians
 beside the spread, and the wall time of one prolong and one restrict call on device memory.
 
-    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--weighted] [--basis MX MY] [--out FILE.json]
+--multi S: the multi-vector entries against the single-vector ones, which are the yardstick, in one
+process, warmed and alternating, --reps times, medians with min and max: (a) the crosswell case of the tests (8 sources, 32
+receivers, about 253 rows): one lsqr_multi of 16 columns against 16 calls of lsqr, wall time; (b) the fan, ends only: matmat and
+rmatmat of S columns against S matvec and rmatvec calls (kernel event time, summed over the calls), and the solver's per-iteration
+operator + vector time at S columns against S single solves.  The batched path is accepted where its series lies below the
+series of the S single calls by more than the spread of the two.  With --multi the row-walk comparison above is left out.
+
+    python tools/tomo_timing.py [--rays 1048576] [--reps 5] [--iters 5] [--weighted] [--basis MX MY] [--multi S] [--out FILE.json]
 """
 import argparse
 import json
@@ -35,6 +42,99 @@ def series(v):
     return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max())}
 
 
+def versus(single, multi):
+    """two series of the same work: S single calls summed, and the one batched call"""
+    ss, sm = series(single), series(multi)
+    spread = max(ss["max_ms"] - ss["min_ms"], sm["max_ms"] - sm["min_ms"])
+    return {"single_calls": ss, "batched": sm, "spread_ms": spread, "ratio_of_medians": ss["median_ms"] / sm["median_ms"],
+            "batched_is_faster_beyond_the_spread": bool(ss["median_ms"] - sm["median_ms"] > spread)}
+
+
+def crosswell_multi(rb, reps, columns=16, iters=30):
+    """(a): the crosswell set-up of tests/test_gpu_tomo.py; the columns are the residual plus noise realisations"""
+    import time
+    F = rb.Field.build("vert_heterogeneous", BOX, rb.DELTA)
+    x, y, Z0 = F.arrays()[:3]
+    F.close()
+    X_, Y_ = np.meshgrid(x, y)
+    bump = np.exp(-((X_ - 1.0) ** 2 + (Y_ + 1.0) ** 2) / (2 * 0.7 * 0.7))
+    src = np.stack([np.full(8, -1.5), np.linspace(-2.2, 0.6, 8)], axis=1)
+
+    def shoot(Fq, **kw):
+        return rb.two_point(rb.op6, Fq, src, (1.0, 0.0, 4.0), np.linspace(-2.3, 0.8, 32), thetas=np.linspace(-1.5, 3.0, 512), step=rb.DELTA_S,
+                            max_size=int(np.ceil(80 / rb.DELTA_S) + 1), box=BOX, **kw)
+    Ft = rb.Field.from_samples(x, y, Z0 * (1 + 0.01 * bump), rb.DELTA)
+    obs = shoot(Ft)
+    Ft.close()
+    F0 = rb.Field.from_samples(x, y, Z0, rb.DELTA)
+    r0 = shoot(F0, sensitivity=True)
+    sens = r0["sensitivity"]
+    s_, j, a = sens.index.T
+    rows = np.nonzero((r0["count"][s_, j] == 1) & (obs["count"][s_, j] == 1) & (a == 0))[0]
+    res0 = obs["T"][s_[rows], j[rows], 0] - r0["T"][s_[rows], j[rows], 0]
+    T = rb.Tomography(F0)
+    T.append_sensitivity(sens, rows=rows)
+    sens.close()
+    F0.close()
+    rng = np.random.default_rng(1)
+    rhs = res0[None, :] + 0.05 * np.std(res0) * rng.standard_normal((columns, len(rows)))
+    kw = dict(damp=1e-3, iter_lim=iters)
+    T.lsqr(rhs[0], **kw); T.lsqr_multi(rhs, **kw)                  # warm both
+    ts, tm = [], []
+    for _ in range(reps):                                         # alternating
+        t0 = time.perf_counter()
+        one = [T.lsqr(r, **kw) for r in rhs]
+        ts.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        many = T.lsqr_multi(rhs, **kw)
+        tm.append((time.perf_counter() - t0) * 1e3)
+    out = versus(ts, tm)
+    out.update(rows=len(rows), columns=columns, iterations=[o["itn"] for o in many],
+               bit_equal=all(o["x"].tobytes() == q["x"].tobytes() and o["itn"] == q["itn"] for o, q in zip(one, many)))
+    T.close()
+    return out
+
+
+def fan_multi(rb, E, F, S, reps, iters):
+    """(b): the products and one solver iteration at S columns on the handle of the fan's ends"""
+    i = E.info()
+    R, nz = i["rows"], F.qy * F.qx
+    rng = np.random.default_rng(2)
+    X, W = rng.standard_normal((S, F.qy, F.qx)), rng.standard_normal((S, R))
+    # the matrix once (36 B per padded segment, the row lengths), the S vectors in and out, and for A^T the accumulators
+    # cleared, added into at least once and read by the finish: 128 S B per sample each way
+    out = {"columns": S,
+           "floor_ms": {"A": (36 * i["padded_segments"] + 4 * R + 8 * S * (R + nz)) / HBM * 1e3,
+                        "At": (36 * i["padded_segments"] + 4 * R + 8 * S * (R + nz) + 2 * 128 * S * nz) / HBM * 1e3}}
+    pairs = {"A": (lambda: sum(E.matvec(x, stats=True)[1]["kernel_ms"] for x in X), lambda: E.matmat(X, stats=True)[1]["kernel_ms"]),
+             "At": (lambda: sum(E.rmatvec(w, stats=True)[1]["kernel_ms"] for w in W), lambda: E.rmatmat(W, stats=True)[1]["kernel_ms"])}
+    for name, (single, multi) in pairs.items():
+        single(); multi()                                         # warm both
+        ts, tm = [], []
+        for _ in range(reps):                                     # alternating
+            ts.append(single())
+            tm.append(multi())
+        out[name] = versus(ts, tm)
+    out["A"]["bit_equal"] = bool(E.matmat(X[:2]).tobytes() == np.stack([E.matvec(x) for x in X[:2]]).tobytes())
+    out["At"]["bit_equal"] = bool(E.rmatmat(W[:2]).tobytes() == np.stack([E.rmatvec(w) for w in W[:2]]).tobytes())
+    kw = dict(damp=1e-3, smooth=(0.5, 0.25), iter_lim=iters, stats=True)
+    per_it = lambda o: (o["stats"]["operator_ms"] + o["stats"]["vector_ms"]) / max(o["itn"], 1)     # noqa: E731
+    E.lsqr(W[0], **kw); E.lsqr_multi(W, **kw)                      # warm both
+    ts, tm, tw, tmw = [], [], [], []
+    for _ in range(reps):                                         # alternating
+        one = [E.lsqr(w, **kw) for w in W]
+        ts.append(sum(per_it(o) for o in one))
+        tw.append(sum(o["stats"]["total_ms"] for o in one))
+        many = E.lsqr_multi(W, **kw)
+        tm.append(per_it(many[0]))
+        tmw.append(many[0]["stats"]["total_ms"])
+    out["solver_iteration"] = versus(ts, tm)
+    out["solver_call"] = versus(tw, tmw)
+    out["solver_iteration"]["bit_equal"] = all(o["x"].tobytes() == q["x"].tobytes() for o, q in zip(one, many))
+    out["solver_iteration"]["bytes_device"] = many[0]["stats"]["bytes_device"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rays", type=int, default=1 << 20)
@@ -44,9 +144,12 @@ def main():
     ap.add_argument("--basis", type=int, nargs=2, metavar=("MX", "MY"), default=None)
     ap.add_argument("--degree", type=int, nargs="+", default=[3], metavar="D")
     ap.add_argument("--smooth2", type=float, nargs=2, metavar=("A", "B"), default=None)
+    ap.add_argument("--multi", type=int, default=0, metavar="S")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from raytracing_amd import rt_bench as rb
+    if a.multi:
+        return multi_main(a, rb)
     R = a.rays
     F = rb.Field.build("vert_heterogeneous", BOX, rb.DELTA)
     ms = int(np.ceil(80 / rb.DELTA_S) + 1)
@@ -164,12 +267,40 @@ def main():
             d[name + "_call_ms"] = series(ts)
         P.close()
     E.close(); EL.close(); F.close()
+    finish(out, a.out)
+
+
+def finish(out, path):
     text = json.dumps(out, indent=1)
     print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
             fh.write(text + "\n")
+
+
+def multi_main(a, rb):
+    out = {"crosswell": crosswell_multi(rb, a.reps)}
+    print("crosswell:", json.dumps(out["crosswell"]), file=sys.stderr, flush=True)
+    R = a.rays
+    F = rb.Field.build("vert_heterogeneous", BOX, rb.DELTA)
+    ms = int(np.ceil(80 / rb.DELTA_S) + 1)
+    th = np.linspace(0.0, np.pi / 2, R)
+    c = rb.Batch(F, rb.op6, rb.DELTA_S, ms, BOX, 1, th, -2.0, -2.0, record_stride=0)
+    c.run()
+    rows = int(c.d_ray()[2].max()) + 1
+    c.close()
+    b = rb.Batch(F, rb.op6, rb.DELTA_S, ms, BOX, 1, th, -2.0, -2.0, rec_rows=rows, keep_n_ray=False)
+    b.run()
+    E = rb.Tomography(F)
+    E.append(b)
+    b.close()
+    out["rays"] = R
+    out["ends"] = E.info()
+    print("compiled:", json.dumps(out["ends"]), file=sys.stderr, flush=True)
+    out["fan"] = fan_multi(rb, E, F, a.multi, a.reps, a.iters)
+    E.close(); F.close()
+    finish(out, a.out)
 
 
 if __name__ == "__main__":
