@@ -161,6 +161,26 @@ class TomoReg(C.Structure):
     _fields_ = [("d1", C.c_double * 2), ("d2", C.c_double * 2), ("reserved", C.c_int64 * 4)]
 
 
+class LocatorParams(C.Structure):
+    """rtmi_locator_params: the grid of the tables and their number"""
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("P", C.c_int64), ("gx0", C.c_double), ("gdx", C.c_double),
+                ("gy0", C.c_double), ("gdy", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
+class LocateResult(C.Structure):
+    """rtmi_locate_result: one event's best node, its 3 x 3 windows and the refined location"""
+    _fields_ = [("node", C.c_int32), ("ix", C.c_int32), ("iy", C.c_int32), ("n", C.c_int32), ("sw", C.c_double), ("obj", C.c_double),
+                ("ref", C.c_double), ("t0", C.c_double), ("win_obj", C.c_double * 9), ("win_tau", C.c_double * 9), ("x", C.c_double),
+                ("y", C.c_double), ("t0_refined", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("cov", C.c_double * 3),
+                ("refined", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 2)]
+
+
+class LocateStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("upload_ms", C.c_double), ("triples", C.c_int64), ("contributing", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
+LOCATE_MAX_TABLES = 512  # RTMI_LOCATE_MAX_TABLES: the most tables (stations) of a locator
 TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
 LSQR_OP_PLAIN, LSQR_OP_FULL, LSQR_OP_FILTERED = 0, 1, 2     # RTMI_LSQR_OP_: rtmi_kirchhoff_lsqr_weighted's operator
@@ -273,6 +293,11 @@ SYMBOLS = {
     "rtmi_tomo_transpose_multi_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(TomoStats)]),
     "rtmi_tomo_lsqr_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), C.c_int32,
                                        C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_locator_create": (C.c_int, [C.POINTER(LocatorParams), _dp, C.POINTER(C.c_void_p)]),
+    "rtmi_locator_destroy": (None, [C.c_void_p]),
+    "rtmi_locate": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _ip, C.POINTER(LocateResult), _dp, C.POINTER(LocateStats)]),
+    "rtmi_locate_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LocateResult), C.c_void_p,
+                                  C.POINTER(LocateStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -2172,6 +2172,143 @@ class Kirchhoff:
             pass
 
 
+def locate_stats(st):
+    return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "triples": int(st.triples), "contributing": int(st.contributing),
+            "search_ms": st.reserved[0] * 1e-6}                   # k_locate's own part of kernel_ms
+
+
+class Locator:
+    """Event location by grid search over traveltime tables (rtmi_locator_*, rtmi_locate, include/rtmi.h).
+    T [P, ny, nx]: one table per station on grid = (gx0, gdx, nx, gy0, gdy, ny), traveltime_table's T with the stations as its
+    sources (reciprocity); the tables stay on the device until close().
+      locate(picks [E, P], weights=None, min_picks=None, maps=False, refine=True, stats=False) -> dict of arrays over the events:
+        x, y, t0         the location and origin time: the quadratic refinement through the 3 x 3 window where it is accepted
+                         (refined = 1), the best node's own otherwise, and always with refine=False
+        node, ix, iy     the best node (-1: no node has enough picks); count, obj, rms = sqrt(obj), sw there
+        cov [E, 2, 2]    the covariance of (x, y) of a refined event, NaN otherwise
+        win_obj, win_tau [E, 3, 3], dx, dy, t0_node, ref; with maps=True also maps [E, ny, nx], obj at every node
+      NaN in picks: no pick; weights [E, P] (1 / sigma^2; 0, negative and non-finite ones drop the pick); min_picks, an int or
+      [E]: the fewest contributing picks of a node (default: all the event's valid picks).
+      locate_device(picks, weights=None, min_picks=None, maps=False, ...) takes torch tensors on the handle's device (fp64 picks
+      and weights, int32 min_picks) and returns maps as a tensor on it: the same bits, no copy of them through the host.
+    With stats=True the calls return (result, stats)."""
+
+    def __init__(self, T, grid):
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 3:
+            raise ValueError("Locator: T must be [P, ny, nx]")
+        gx0, gdx, nx, gy0, gdy, ny = grid
+        if T.shape[1:] != (int(ny), int(nx)):
+            raise ValueError("Locator: T must be [P, ny, nx] of the grid")
+        lp = _lib.LocatorParams()
+        lp.nx, lp.ny, lp.P = int(nx), int(ny), T.shape[0]
+        lp.gx0, lp.gdx, lp.gy0, lp.gdy = float(gx0), float(gdx), float(gy0), float(gdy)
+        self.P, self.ny, self.nx, self.grid = T.shape[0], int(ny), int(nx), tuple(grid)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().rtmi_locator_create(C.byref(lp), dptr(T), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_table(cls, tab, grid):
+        """From traveltime_table's dict: its T [S, ny, nx], or slot 0 (the first arrival) of a T [S, K, ny, nx]"""
+        T = np.asarray(tab["T"])
+        return cls(T[:, 0] if T.ndim == 4 else T, grid)
+
+    def _open(self):
+        if not self._h:
+            raise RuntimeError("Locator: the handle is closed")
+        return self._h
+
+    def _result(self, res, E, refine):
+        a = np.frombuffer(res, dtype=np.dtype(_lib.LocateResult)).copy() if E else np.zeros(0, dtype=np.dtype(_lib.LocateResult))
+        out = {"node": a["node"].copy(), "ix": a["ix"].copy(), "iy": a["iy"].copy(), "count": a["n"].copy(), "sw": a["sw"].copy(),
+               "obj": a["obj"].copy(), "ref": a["ref"].copy(), "t0_node": a["t0"].copy(),
+               "win_obj": a["win_obj"].reshape(E, 3, 3).copy(), "win_tau": a["win_tau"].reshape(E, 3, 3).copy()}
+        with np.errstate(invalid="ignore"):
+            out["rms"] = np.sqrt(out["obj"])
+        cov = np.full((E, 2, 2), np.nan)
+        if refine:
+            out.update(x=a["x"].copy(), y=a["y"].copy(), t0=a["t0_refined"].copy(), dx=a["dx"].copy(), dy=a["dy"].copy(),
+                       refined=a["refined"].copy())
+            c = a["cov"].reshape(E, 3)
+            cov[:, 0, 0], cov[:, 0, 1], cov[:, 1, 0], cov[:, 1, 1] = c[:, 0], c[:, 1], c[:, 1], c[:, 2]
+        else:
+            gx0, gdx, _, gy0, gdy, _ = self.grid
+            none = out["node"] < 0
+            out.update(x=np.where(none, np.nan, float(gx0) + out["ix"] * float(gdx)), y=np.where(none, np.nan, float(gy0) + out["iy"] * float(gdy)),
+                       t0=out["t0_node"].copy(), dx=np.where(none, np.nan, 0.0), dy=np.where(none, np.nan, 0.0),
+                       refined=np.zeros(E, dtype=np.int32))
+        out["cov"] = cov
+        return out
+
+    def locate(self, picks, weights=None, min_picks=None, maps=False, refine=True, stats=False):
+        t = np.ascontiguousarray(picks, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.P:
+            raise ValueError(f"Locator.locate: picks must be [E, {self.P}]")
+        E = t.shape[0]
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w is not None and w.shape != t.shape:
+            raise ValueError("Locator.locate: weights must have the shape of picks")
+        need = None
+        if min_picks is not None:
+            need = np.ascontiguousarray(np.broadcast_to(np.asarray(min_picks, dtype=np.int32), (E,)))
+        h = self._open()
+        res = (_lib.LocateResult * E)()
+        m = np.empty((E, self.ny, self.nx)) if maps else None
+        st = _lib.LocateStats()
+        check(lib().rtmi_locate(h, E, dptr(t), dptr(w), None if need is None else need.ctypes.data_as(_lib._ip), res, dptr(m), C.byref(st)))
+        out = self._result(res, E, refine)
+        if maps:
+            out["maps"] = m
+        return (out, locate_stats(st)) if stats else out
+
+    def locate_device(self, picks, weights=None, min_picks=None, maps=False, refine=True, stats=False):
+        import torch
+        who = "Locator.locate_device"
+        for name, a, dt in (("picks", picks, torch.float64), ("weights", weights, torch.float64), ("min_picks", min_picks, torch.int32)):
+            if a is None:
+                continue
+            if not isinstance(a, torch.Tensor):
+                raise TypeError(f"{who}: {name} must be a torch tensor")
+            if a.dtype != dt:
+                raise TypeError(f"{who}: {name} must be {dt}")
+            if not a.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous")
+            if not a.is_cuda:                          # which GPU it is on, the library checks against the handle's
+                raise ValueError(f"{who}: {name} must be a tensor on a GPU, not on the host")
+        if picks.dim() != 2 or picks.shape[1] != self.P:
+            raise ValueError(f"{who}: picks must be [E, {self.P}]")
+        E = picks.shape[0]
+        if weights is not None and weights.shape != picks.shape:
+            raise ValueError(f"{who}: weights must have the shape of picks")
+        if min_picks is not None and tuple(min_picks.shape) != (E,):
+            raise ValueError(f"{who}: min_picks must be [E]")
+        h = self._open()
+        res = (_lib.LocateResult * E)()
+        m = torch.empty((E, self.ny, self.nx), dtype=torch.float64, device=picks.device) if maps else None
+        st = _lib.LocateStats()
+        torch.cuda.synchronize(picks.device)           # the library works on the null stream
+        check(lib().rtmi_locate_dev(h, E, picks.data_ptr(), None if weights is None else weights.data_ptr(),
+                                    None if min_picks is None else min_picks.data_ptr(), res, None if m is None else m.data_ptr(),
+                                    C.byref(st)))
+        out = self._result(res, E, refine)
+        if maps:
+            out["maps"] = m
+        return (out, locate_stats(st)) if stats else out
+
+    def close(self):
+        if self._h:
+            lib().rtmi_locator_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def debug_fix_norm(x):
     """rtmi_debug_fix_norm: the device's order-independent norm of a host vector -> (norm, e)"""
     xx = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Event location by grid search against the same objective in plain torch, in one process: the search
+kernel k_locate on the stock 737 x 539 grid (the vert_heterogeneous field's samples) with P = 32 tables, for E in {64, 1024,
+4096} events, warmed, alternating, medians of --reps device times with min and max.
+
+The yardstick exists without the library: broadcast tensor ops on the device, d = (t - ref)[:, :, None] - T[None], tau the mean
+over the stations, obj the mean of (d - tau)^2, argmin over the nodes, chunked over the events to fit memory (--torch-chunk
+events at a time, three [chunk, P, nodes] fp64 temporaries); timed with torch events around the whole loop.  Its node choices
+are compared with the kernel's.  The rule is DESIGN.md section 24's: the kernel is accepted where its series lies below torch's
+by more than the spread of the two.
+
+Also printed: triples per second, and the two floors of the kernel -- the table bytes one pass over every (tile, chunk) block
+must bring in over 6 TB/s, and the vector instructions per triple (counted in the ISA) at the chip's
+issue rate.
+
+    python tools/locate_timing.py [--events 64 1024 4096] [--tables 32] [--reps 5] [--weights] [--missing SHARE] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM = 6.0e12                        # bytes per second
+SIMDS, CLOCK = 1024, 2.4e9          # 256 CUs of 4 SIMDs; the clock the floor assumes (the chip holds less under load)
+F64_OPS = {False: 6, True: 9}       # fp64 vector instructions per triple in k_locate's two loops where a chunk has all its picks,
+                                    # without and with weights, read off the ISA (make asm UNIT=locate.hip); nothing else per triple
+F64_CYCLES = 4                      # cycles a wave's fp64 add or multiply holds its SIMD: 16 lanes per cycle
+CHUNK, TILE = 16, 256               # locate.hip's kChunk and kTile
+
+
+def series(v):
+    v = np.asarray(v, dtype=np.float64)
+    return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max())}
+
+
+def problem(P, E, seed=0):
+    """a constant medium on the stock grid: the times do not depend on the values, the node choices do"""
+    nx, ny = 737, 539
+    grid = (-5.0, 13.0 / (nx - 1), nx, -5.5, 9.5 / (ny - 1), ny)
+    rng = np.random.default_rng(seed)
+    X, Y = grid[0] + grid[1] * np.arange(nx), grid[3] + grid[4] * np.arange(ny)
+    sx, sy = rng.uniform(-6.0, 9.0, P), rng.uniform(-6.5, 5.0, P)
+    T = (1.0 / 14.0) * np.hypot(X[None, None, :] - sx[:, None, None], Y[None, :, None] - sy[:, None, None])
+    ex, ey = rng.uniform(X[0], X[-1], E), rng.uniform(Y[0], Y[-1], E)
+    t = rng.uniform(0.0, 60.0, E)[:, None] + (1.0 / 14.0) * np.hypot(ex[:, None] - sx[None, :], ey[:, None] - sy[None, :])
+    t += 1e-3 * rng.standard_normal(t.shape)
+    return grid, T, t
+
+
+def torch_locate(torch, Td, td, wd, chunk):
+    """the yardstick: (nodes [E], device ms)"""
+    P = Td.shape[0]
+    Tf = Td.reshape(1, P, -1)
+    nodes = torch.empty(td.shape[0], dtype=torch.int64, device=td.device)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for e0 in range(0, td.shape[0], chunk):
+        tr = td[e0:e0 + chunk] - td[e0:e0 + chunk, :1]
+        d = tr[:, :, None] - Tf
+        if wd is None and torch.isnan(tr).any():                  # missing picks: weights of 0 and 1
+            wd_ = torch.isfinite(td).to(torch.float64)
+            d = torch.nan_to_num(d)
+            w = wd_[e0:e0 + chunk, :, None]
+            sw = w.sum(dim=1, keepdim=True)
+            tau = (w * d).sum(dim=1, keepdim=True) / sw
+            obj = (w * (d - tau) ** 2).sum(dim=1) / sw[:, 0]
+        elif wd is None:
+            tau = d.mean(dim=1, keepdim=True)
+            obj = ((d - tau) ** 2).mean(dim=1)
+        else:
+            w = wd[e0:e0 + chunk, :, None]
+            sw = w.sum(dim=1, keepdim=True)
+            tau = (w * d).sum(dim=1, keepdim=True) / sw
+            obj = (w * (d - tau) ** 2).sum(dim=1) / sw[:, 0]
+        nodes[e0:e0 + chunk] = obj.argmin(dim=1)
+    b.record()
+    torch.cuda.synchronize()
+    return nodes.cpu().numpy(), a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--events", type=int, nargs="+", default=[64, 1024, 4096])
+    ap.add_argument("--tables", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--torch-chunk", type=int, default=8)
+    ap.add_argument("--weights", action="store_true")
+    ap.add_argument("--missing", type=float, default=0.0, help="share of the picks that are missing (NaN): the masked variant of the kernel")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from raytracing_amd import rt_bench as rb
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("locate_timing: no GPU; nothing is measured without one")
+    P = a.tables
+    grid, T, _ = problem(P, 1)
+    nn = T.shape[1] * T.shape[2]
+    L = rb.Locator(T, grid)
+    Td = torch.from_numpy(T).cuda()
+    out = {"grid": [grid[2], grid[5]], "tables": P, "weights": bool(a.weights), "missing": a.missing, "reps": a.reps, "cases": []}
+    for E in a.events:
+        _, _, t = problem(P, E, seed=E)
+        rng = np.random.default_rng(E + 1)
+        w = rng.uniform(0.5, 2.0, t.shape) if a.weights else None
+        if a.missing:
+            t[:, 1:][rng.random((E, P - 1)) < a.missing] = np.nan         # station 0 keeps its pick: ref as the yardstick takes it
+        td = torch.from_numpy(t).cuda()
+        wd = None if w is None else torch.from_numpy(w).cuda()
+        kernel = lambda: L.locate_device(td, wd, stats=True)                     # noqa: E731
+        kernel(); torch_locate(torch, Td, td, wd, a.torch_chunk)                 # warm both
+        tk, tc, tt = [], [], []
+        for _ in range(a.reps):                                                  # alternating
+            r, st = kernel()
+            tk.append(st["search_ms"])
+            tc.append(st["kernel_ms"])
+            nodes, ms = torch_locate(torch, Td, td, wd, a.torch_chunk)
+            tt.append(ms)
+        sk, st_, sc = series(tk), series(tt), series(tc)
+        spread = max(sk["max_ms"] - sk["min_ms"], st_["max_ms"] - st_["min_ms"])
+        triples = E * nn * P
+        blocks = -(-E // CHUNK) * -(-nn // TILE)
+        case = {"events": E, "triples": triples, "k_locate": sk, "all_kernels": sc, "torch": st_, "spread_ms": spread,
+                "ratio_of_medians": st_["median_ms"] / sk["median_ms"],
+                "kernel_is_faster_beyond_the_spread": bool(st_["median_ms"] - sk["median_ms"] > spread),
+                "triples_per_second": triples / (sk["median_ms"] * 1e-3),
+                "nodes_equal_to_torchs": int((nodes == r["node"]).sum()),
+                "floor_ms": {"table_bytes": 2 * blocks * P * TILE * 8 / HBM * 1e3,
+                             "valu_issue": triples / 64 * F64_OPS[bool(a.weights)] * F64_CYCLES / (SIMDS * CLOCK) * 1e3}}
+        print(json.dumps(case), file=sys.stderr, flush=True)
+        out["cases"].append(case)
+    L.close()
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
