@@ -1141,6 +1141,75 @@ int rtmi_locate(rtmi_locator *loc, int64_t E, const double *t, const double *w, 
 int rtmi_locate_dev(rtmi_locator *loc, int64_t E, const double *d_t, const double *d_w, const int32_t *d_need,
                     rtmi_locate_result *res, double *d_maps, rtmi_locate_stats *st);
 
+/* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
+ * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it
+ * is the caller's job); the traces are stacked along the traveltime moveout of every grid node for every candidate origin time,
+ * and events are the peaks of the stack.  All on the device, in fp64; every product, sum and quotient one rounded operation
+ * (raytracing_amd/csrc/rt_stack.h holds the arithmetic, tests/stack_ref.py restates it).
+ *   traces   c [P][nt], sample i of every station at time ct0 + i cdt; NaN marks a gap
+ *   weights  w [P] or NULL; station r is valid iff w is absent, or w[r] is finite and > 0
+ *   scan     o_m = o0 + (double)m * od, m = 0 .. M - 1
+ *   need     the fewest contributing stations of a candidate; 0: the number of valid stations
+ * inv = 1.0 / cdt, once.  For node x and scan index m, with r ascending over the valid stations and sums from +0.0:
+ *     f = ((o_m + T[r][x]) - ct0) * inv
+ *     the station contributes iff T[r][x] is finite, f >= 0, f < nt - 1, and with j = floor(f) both c[r][j] and c[r][j + 1] are finite
+ *     a = f - j;  v = (1.0 - a) * c[r][j] + a * c[r][j + 1]
+ *     n += 1;  sw = sw + w[r];  s = s + w[r] * v        (no weights: s = s + v, and sw = (double)n)
+ *     (x, m) is a candidate iff n >= max(need, 1);  S[m][x] = s / sw, and -inf where it is none
+ * The reductions are exact lexicographic maxima, the same bits under every schedule; an S that is NaN counts as -inf in them:
+ *     peak [M], peak_node [M]   the greatest S[m][.] and the least node index iy nx + ix of a candidate that attains it; no
+ *                               candidate: -inf and -1
+ *     best [ny][nx], best_m     the greatest S[.][x] and the least m of a candidate that attains it; none: -inf and -1.  Each is
+ *                               written where its pointer is not NULL
+ *     volume [M][ny][nx]        S itself, raw (a NaN stays one), written where the pointer is not NULL
+ * Events, by host arithmetic over peak and peak_node alone: m is eligible iff peak[m] >= threshold and peak_node[m] >= 0; the
+ * eligible m of greatest peak that is not masked is taken, ties to the least m, and masks every m' with |m' - m| <= min_sep;
+ * repeated until max_events are taken or none is left.  events [max_events] receives them in that order, *nev their number;
+ * stats.truncated says that eligible samples were left when max_events stopped the loop.
+ * Per event: m, node = peak_node[m], ix, iy, n and value = S there, t0 = o_m, and win [3][3][3], S recomputed at
+ * (m + dm, iy + j, ix + i), dm, j, i in {-1, 0, 1}, stored at [(dm + 1) 9 + (j + 1) 3 + (i + 1)]: bit-equal to the volume,
+ * NaN outside the grid or the scan.  Two refinements on the host, independent of each other -- each the vertex of a parabola
+ * along its own axes, with no cross terms between space and time; the window is returned for callers who want a joint fit:
+ *     space   rt_locate.h's quadratic through the negated middle slice: x, y, dx, dy as in rtmi_locate_result (the node's own and
+ *             dx = dy = 0 where it is not accepted)
+ *     time    with S-, S0, S+ the window's values at the node:  dm = ((S- - S+) / 2) / ((S- - 2 S0) + S+), accepted iff the three
+ *             are finite, the denominator is < 0 and |dm| <= 1; then t0_refined = o_m + dm * od, else dm = 0 and t0_refined = o_m
+ *     refined bit 0: the spatial step was accepted, bit 1: the temporal one
+ * stats: kernel_ms the device time of the kernels, upload_ms the host wall time of the copies to the device, triples = nx ny M P,
+ * contributing the triples that contributed; reserved[0] is the search kernel's own part of kernel_ms in nanoseconds, reserved[1]
+ * the number of parts the scan was split into.
+ * rtmi_locate_stack_dev takes c, w, peak, peak_node, best, best_m and volume as memory of the handle's device (events, nev and
+ * st stay host memory); rtmi_locate_stack is upload, that, download: the same bits.
+ * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null handle, sp, c, peak, peak_node or nev;
+ * events null with max_events > 0; nt < 2 or over 2^31; M < 1; cdt or od not finite and > 0; ct0 or o0 not finite; need, min_sep or
+ * max_events < 0; threshold NaN; M over 2^31 - 17 or more than 2^31 (tile of 256 nodes, chunk of 16 scan indices) pairs; the
+ * handle used on another device.
+ * Not covered: later arrivals, per-station polarity or phase (P and S tables as 2P stations), a joint space-time refinement, fp32
+ * traces, several GPUs, the characteristic function itself. */
+typedef struct {
+    int64_t nt, M;
+    double ct0, cdt, o0, od;
+    int64_t need;
+    double threshold;
+    int64_t min_sep, max_events;
+    int64_t reserved[4];
+} rtmi_stack_params;
+typedef struct {
+    int32_t m, node, ix, iy, n, reserved0;
+    double value, t0;
+    double win[27];
+    double x, y, t0_refined, dx, dy, dm;
+    int32_t refined, reserved1;
+    int64_t reserved[2];
+} rtmi_stack_event;
+typedef struct { double kernel_ms, upload_ms; int64_t triples, contributing; int32_t truncated, reserved0; int64_t reserved[4]; } rtmi_stack_stats;
+int rtmi_locate_stack(rtmi_locator *loc, const rtmi_stack_params *sp, const double *c, const double *w, double *peak,
+                      int32_t *peak_node, double *best, int32_t *best_m, double *volume, rtmi_stack_event *events, int64_t *nev,
+                      rtmi_stack_stats *st);
+int rtmi_locate_stack_dev(rtmi_locator *loc, const rtmi_stack_params *sp, const double *d_c, const double *d_w, double *d_peak,
+                          int32_t *d_peak_node, double *d_best, int32_t *d_best_m, double *d_volume, rtmi_stack_event *events,
+                          int64_t *nev, rtmi_stack_stats *st);
+
 typedef struct {
     void *s_ray, *n_ray;               /* device, dtype, layouts above */
     double *x, *y, *theta;               /* device SoA ray state, length R: the accumulated quantities are fp64 in */

@@ -180,6 +180,26 @@ class LocateStats(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+class StackParams(C.Structure):
+    """rtmi_stack_params: the trace axis, the origin-time scan and the event selection of rtmi_locate_stack"""
+    _fields_ = [("nt", C.c_int64), ("M", C.c_int64), ("ct0", C.c_double), ("cdt", C.c_double), ("o0", C.c_double), ("od", C.c_double),
+                ("need", C.c_int64), ("threshold", C.c_double), ("min_sep", C.c_int64), ("max_events", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
+class StackEvent(C.Structure):
+    """rtmi_stack_event: one event of the stack, its 3 x 3 x 3 window and the refined location and origin time"""
+    _fields_ = [("m", C.c_int32), ("node", C.c_int32), ("ix", C.c_int32), ("iy", C.c_int32), ("n", C.c_int32), ("reserved0", C.c_int32),
+                ("value", C.c_double), ("t0", C.c_double), ("win", C.c_double * 27), ("x", C.c_double), ("y", C.c_double),
+                ("t0_refined", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("dm", C.c_double), ("refined", C.c_int32),
+                ("reserved1", C.c_int32), ("reserved", C.c_int64 * 2)]
+
+
+class StackStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("upload_ms", C.c_double), ("triples", C.c_int64), ("contributing", C.c_int64),
+                ("truncated", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
 LOCATE_MAX_TABLES = 512  # RTMI_LOCATE_MAX_TABLES: the most tables (stations) of a locator
 TOMO_SKIP = -2          # RTMI_TOMO_SKIP: rtmi_tomo_append's `which` for a ray without a row
 LSQR_RANGE = 8          # RTMI_LSQR_RANGE: rtmi_kirchhoff_lsqr's own istop
@@ -298,6 +318,10 @@ SYMBOLS = {
     "rtmi_locate": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _ip, C.POINTER(LocateResult), _dp, C.POINTER(LocateStats)]),
     "rtmi_locate_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LocateResult), C.c_void_p,
                                   C.POINTER(LocateStats)]),
+    "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
+                                    C.POINTER(C.c_int64), C.POINTER(StackStats)]),
+    "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(StackEvent), C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_batch_view": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
     "rtmi_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "rtmi_batch_destroy": (None, [C.c_void_p]),

@@ -7,19 +7,9 @@
 //   k_locate_pick    one block per event: the least (key, node) of its partials
 //   k_locate_window  one wave per event: obj and tau at the nine nodes around the best one, by the same two steps
 // No atomics: every result is one lane's own chain of operations or an exact minimum, the same bits on every run.
-#include "rtmi_host.h"
+#include "rtmi_locator.h"
 
 #include "rt_locate.h"
-
-struct rtmi_locator {
-    rtmi_locator_params lp{};
-    int device = -1, cus = 0;
-    size_t nn = 0;
-    double* T = nullptr;
-    ~rtmi_locator() {
-        if (T) (void)hipFree(T);
-    }
-};
 
 namespace {
 
@@ -323,22 +313,6 @@ __global__ void __launch_bounds__(64) k_locate_window(const double* __restrict__
         o.n = n;
         o.sw = sw;
     }
-}
-
-#define RTMI_ALLOC(expr)                                                                                          \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) {                                                                                   \
-            (void)hipGetLastError();                                                                              \
-            return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-        }                                                                                                         \
-    } while (0)
-
-int check_device(const rtmi_locator* loc, const char* who) {
-    int dev = -1;
-    RTMI_HIP(hipGetDevice(&dev));
-    RTMI_ARG(dev == loc->device, "the calling thread's current device is not the handle's");
-    return RTMI_OK;
 }
 
 // what every form of the call refuses before it touches the device

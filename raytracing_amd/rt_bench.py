@@ -2177,6 +2177,12 @@ def locate_stats(st):
             "search_ms": st.reserved[0] * 1e-6}                   # k_locate's own part of kernel_ms
 
 
+def stack_stats(st):
+    return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "triples": int(st.triples), "contributing": int(st.contributing),
+            "truncated": bool(st.truncated), "search_ms": st.reserved[0] * 1e-6,            # k_stack's own part of kernel_ms
+            "parts": int(st.reserved[1])}                                                   # the parts the scan was split into
+
+
 class Locator:
     """Event location by grid search over traveltime tables (rtmi_locator_*, rtmi_locate, include/rtmi.h).
     T [P, ny, nx]: one table per station on grid = (gx0, gdx, nx, gy0, gdy, ny), traveltime_table's T with the stations as its
@@ -2191,6 +2197,8 @@ class Locator:
       [E]: the fewest contributing picks of a node (default: all the event's valid picks).
       locate_device(picks, weights=None, min_picks=None, maps=False, ...) takes torch tensors on the handle's device (fp64 picks
       and weights, int32 min_picks) and returns maps as a tensor on it: the same bits, no copy of them through the host.
+      stack(traces [P, nt], dt, t0, scan=(o0, od, M), ...) needs no picks: it stacks one characteristic function per station along
+      every node's moveout for every origin time of the scan and takes events from the peaks (see stack's own text).
     With stats=True the calls return (result, stats)."""
 
     def __init__(self, T, grid):
@@ -2296,6 +2304,112 @@ class Locator:
         if maps:
             out["maps"] = m
         return (out, locate_stats(st)) if stats else out
+
+    def _stack_params(self, who, nt, dt, t0, scan, min_stations, threshold, min_sep, max_events):
+        o0, od, M = scan
+        sp = _lib.StackParams()
+        sp.nt, sp.M, sp.ct0, sp.cdt, sp.o0, sp.od = int(nt), int(M), float(t0), float(dt), float(o0), float(od)
+        sp.need = 0 if min_stations is None else int(min_stations)
+        sp.threshold, sp.min_sep, sp.max_events = float(threshold), int(min_sep), int(max_events)
+        return sp
+
+    def _stack_events(self, ev, K, sp, refine):
+        a = np.frombuffer(ev, dtype=np.dtype(_lib.StackEvent))[:K].copy() if K else np.zeros(0, dtype=np.dtype(_lib.StackEvent))
+        out = {"m": a["m"].copy(), "node": a["node"].copy(), "ix": a["ix"].copy(), "iy": a["iy"].copy(), "count": a["n"].copy(),
+               "value": a["value"].copy(), "t0_node": a["t0"].copy(), "win": a["win"].reshape(K, 3, 3, 3).copy()}
+        if refine:
+            out.update(x=a["x"].copy(), y=a["y"].copy(), t0=a["t0_refined"].copy(), dx=a["dx"].copy(), dy=a["dy"].copy(),
+                       dm=a["dm"].copy(), refined=a["refined"].copy())
+        else:
+            gx0, gdx, _, gy0, gdy, _ = self.grid
+            out.update(x=float(gx0) + out["ix"] * float(gdx), y=float(gy0) + out["iy"] * float(gdy), t0=out["t0_node"].copy(),
+                       dx=np.zeros(K), dy=np.zeros(K), dm=np.zeros(K), refined=np.zeros(K, dtype=np.int32))
+        return out
+
+    def stack(self, traces, dt, t0=0.0, scan=(0.0, 1.0, 1), weights=None, min_stations=None, threshold=np.inf, min_sep=0, max_events=0,
+              maps=False, volume=False, refine=True, stats=False):
+        """Pick-free detection and location (rtmi_locate_stack, include/rtmi.h): traces [P, nt], one characteristic
+        function per station (an envelope, STA/LTA, kurtosis: computing it is the caller's job; NaN marks a gap), sample i at time
+        t0 + i dt, are stacked along every node's moveout for the origin times o0 + m od, m < M, of scan = (o0, od, M).
+        weights [P]: a station with a weight that is 0, negative or not finite is left out.  min_stations: the fewest stations
+        that must contribute to a node (default: every valid one).  Returns a dict:
+          peak, peak_node [M]   the detection series: the greatest stack of each origin time and the node that attains it
+                                (-inf and -1 where no node has enough stations)
+          m, node, ix, iy, count, value, t0_node, win [K, 3, 3, 3]   the events: the at most max_events greatest samples of peak
+                                that reach threshold, at least min_sep + 1 scan indices apart, in the order they are taken
+          x, y, t0, dx, dy, dm, refined   their refined location (bit 0 of refined) and origin time (bit 1); with refine=False
+                                the node's own
+          best, best_m [ny, nx] with maps=True: each node's greatest stack over the scan and its scan index;
+          volume [M, ny, nx] with volume=True: the stack itself.
+        stack_device takes traces and weights as torch tensors on the handle's device and returns peak, peak_node, best, best_m
+        and volume as tensors on it.  With stats=True the calls return (result, stats)."""
+        who = "Locator.stack"
+        c = np.ascontiguousarray(traces, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] != self.P:
+            raise ValueError(f"{who}: traces must be [{self.P}, nt]")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w is not None and w.shape != (self.P,):
+            raise ValueError(f"{who}: weights must be [{self.P}]")
+        sp = self._stack_params(who, c.shape[1], dt, t0, scan, min_stations, threshold, min_sep, max_events)
+        h = self._open()
+        M = max(int(sp.M), 0)
+        peak, peak_node = np.empty(M), np.empty(M, dtype=np.int32)
+        best = np.empty((self.ny, self.nx)) if maps else None
+        best_m = np.empty((self.ny, self.nx), dtype=np.int32) if maps else None
+        vol = np.empty((M, self.ny, self.nx)) if volume else None
+        ev = (_lib.StackEvent * max(int(sp.max_events), 1))()
+        nev, st = C.c_int64(0), _lib.StackStats()
+        ip = lambda a: None if a is None else a.ctypes.data_as(_lib._ip)                     # noqa: E731
+        check(lib().rtmi_locate_stack(h, C.byref(sp), dptr(c), dptr(w), dptr(peak), ip(peak_node), dptr(best), ip(best_m), dptr(vol),
+                                      ev, C.byref(nev), C.byref(st)))
+        out = self._stack_events(ev, int(nev.value), sp, refine)
+        out.update(peak=peak, peak_node=peak_node)
+        if maps:
+            out.update(best=best, best_m=best_m)
+        if volume:
+            out["volume"] = vol
+        return (out, stack_stats(st)) if stats else out
+
+    def stack_device(self, traces, dt, t0=0.0, scan=(0.0, 1.0, 1), weights=None, min_stations=None, threshold=np.inf, min_sep=0,
+                     max_events=0, maps=False, volume=False, refine=True, stats=False):
+        import torch
+        who = "Locator.stack_device"
+        for name, a in (("traces", traces), ("weights", weights)):
+            if a is None:
+                continue
+            if not isinstance(a, torch.Tensor):
+                raise TypeError(f"{who}: {name} must be a torch tensor")
+            if a.dtype != torch.float64:
+                raise TypeError(f"{who}: {name} must be {torch.float64}")
+            if not a.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous")
+            if not a.is_cuda:                          # which GPU it is on, the library checks against the handle's
+                raise ValueError(f"{who}: {name} must be a tensor on a GPU, not on the host")
+        if traces is None or traces.dim() != 2 or traces.shape[0] != self.P:
+            raise ValueError(f"{who}: traces must be [{self.P}, nt]")
+        if weights is not None and tuple(weights.shape) != (self.P,):
+            raise ValueError(f"{who}: weights must be [{self.P}]")
+        sp = self._stack_params(who, traces.shape[1], dt, t0, scan, min_stations, threshold, min_sep, max_events)
+        h = self._open()
+        M, dev = max(int(sp.M), 0), traces.device
+        peak = torch.empty(M, dtype=torch.float64, device=dev)
+        peak_node = torch.empty(M, dtype=torch.int32, device=dev)
+        best = torch.empty((self.ny, self.nx), dtype=torch.float64, device=dev) if maps else None
+        best_m = torch.empty((self.ny, self.nx), dtype=torch.int32, device=dev) if maps else None
+        vol = torch.empty((M, self.ny, self.nx), dtype=torch.float64, device=dev) if volume else None
+        ev = (_lib.StackEvent * max(int(sp.max_events), 1))()
+        nev, st = C.c_int64(0), _lib.StackStats()
+        p = lambda a: None if a is None else a.data_ptr()                                    # noqa: E731
+        torch.cuda.synchronize(dev)                    # the library works on the null stream
+        check(lib().rtmi_locate_stack_dev(h, C.byref(sp), p(traces), p(weights), p(peak), p(peak_node), p(best), p(best_m), p(vol),
+                                          ev, C.byref(nev), C.byref(st)))
+        out = self._stack_events(ev, int(nev.value), sp, refine)
+        out.update(peak=peak, peak_node=peak_node)
+        if maps:
+            out.update(best=best, best_m=best_m)
+        if volume:
+            out["volume"] = vol
+        return (out, stack_stats(st)) if stats else out
 
     def close(self):
         if self._h:

@@ -14,6 +14,12 @@ must bring in over 6 TB/s, and the vector instructions per triple (counted in th
 issue rate.
 
     python tools/locate_timing.py [--events 64 1024 4096] [--tables 32] [--reps 5] [--weights] [--missing SHARE] [--out FILE.json]
+
+--stack M [M ...] times the pick-free search instead: k_stack on the same grid and tables with traces of
+8192 samples, a tenth of them NaN, for the scan lengths given, without and with weights, against the same S, peak and best in
+plain torch (broadcast, gather, chunked over the scan), with the kernel's two floors: fp64 issue and gathered bytes.
+
+    python tools/locate_timing.py --stack 256 4096 [--tables 32] [--reps 5] [--torch-chunk 8] [--out FILE.json]
 """
 import argparse
 import json
@@ -82,8 +88,104 @@ def torch_locate(torch, Td, td, wd, chunk):
     return nodes.cpu().numpy(), a.elapsed_time(b)
 
 
+STACK_F64 = {False: 15, True: 17}   # fp64-rate vector instructions per triple in k_stack's station loop, without and with weights,
+                                    # read off the ISA (make asm UNIT=stack.hip)
+STACK_GATHER = 16                   # bytes a triple gathers from the traces: samples j and j + 1
+L2_BYTES_PER_S = 256 * 64 * 2.4e9   # 64 bytes per CU and cycle from the vector L1s, the most the gathers can be served at
+
+
+def torch_stack(torch, Td, cd, wd, o, ct0, inv, need, chunk):
+    """the yardstick of --stack: S by broadcast ops and gather, chunked over m -> (peak [M], best [nodes], device ms)"""
+    P, nt = cd.shape
+    Tf = Td.reshape(1, P, -1)
+    M = o.shape[0]
+    peak = torch.empty(M, dtype=torch.float64, device=Td.device)
+    best = torch.full((Tf.shape[2],), -np.inf, dtype=torch.float64, device=Td.device)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for m0 in range(0, M, chunk):
+        f = ((o[m0:m0 + chunk, None, None] + Tf) - ct0) * inv
+        inside = (f >= 0.0) & (f < nt - 1)
+        jf = torch.floor(f)
+        j = torch.where(inside, jf, torch.zeros_like(jf)).long()
+        src = cd[None].expand(j.shape[0], -1, -1)
+        c0, c1 = torch.gather(src, 2, j), torch.gather(src, 2, j + 1)
+        ok = inside & torch.isfinite(c0) & torch.isfinite(c1)
+        fr = f - jf
+        v = torch.where(ok, (1.0 - fr) * c0 + fr * c1, torch.zeros_like(f))
+        n = ok.sum(dim=1)
+        if wd is None:
+            s, sw = v.sum(dim=1), n.to(torch.float64)
+        else:
+            s, sw = (wd[None, :, None] * v).sum(dim=1), (wd[None, :, None] * ok).sum(dim=1)
+        S = torch.where(n >= need, s / sw, torch.full_like(s, -np.inf))
+        peak[m0:m0 + chunk] = S.max(dim=1).values
+        best = torch.maximum(best, S.max(dim=0).values)
+    b.record()
+    torch.cuda.synchronize()
+    return peak.cpu().numpy(), best.cpu().numpy(), a.elapsed_time(b)
+
+
+def stack_main(a):
+    """--stack M ...: the search kernel k_stack on the section-29 case with nt = 8192 samples per trace, a tenth of them NaN,
+    without and with weights, against the same S, peak and best in plain torch"""
+    from raytracing_amd import rt_bench as rb
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("locate_timing: no GPU; nothing is measured without one")
+    P, nt = a.tables, 8192
+    grid, T, _ = problem(P, 1)
+    nn = T.shape[1] * T.shape[2]
+    rng = np.random.default_rng(7)
+    c = rng.uniform(0.0, 1.0, (P, nt))
+    c[rng.random(c.shape) < 0.1] = np.nan
+    ct0, cdt, o0, od = 0.0, 1e-3, 0.5, 1e-3                    # T < 1.5 s: every read falls inside the traces
+    need = P // 2
+    L = rb.Locator(T, grid)
+    Td, cd = torch.from_numpy(T).cuda(), torch.from_numpy(c).cuda()
+    out = {"grid": [grid[2], grid[5]], "tables": P, "nt": nt, "reps": a.reps, "cases": []}
+    for M in a.stack:
+        for weights in (False, True):
+            wd = torch.from_numpy(rng.uniform(0.5, 2.0, P)).cuda() if weights else None
+            o = o0 + od * torch.arange(M, dtype=torch.float64, device="cuda")
+            kernel = lambda: L.stack_device(cd, cdt, t0=ct0, scan=(o0, od, M), weights=wd, min_stations=need, maps=True, stats=True)  # noqa: E731
+            yard = lambda: torch_stack(torch, Td, cd, wd, o, ct0, 1.0 / cdt, need, a.torch_chunk)                                      # noqa: E731
+            kernel(); yard()                                                        # warm both
+            tk, tc, tt = [], [], []
+            for _ in range(a.reps):                                                 # alternating
+                r, st = kernel()
+                tk.append(st["search_ms"])
+                tc.append(st["kernel_ms"])
+                peak, best, ms = yard()
+                tt.append(ms)
+            sk, st_, sc = series(tk), series(tt), series(tc)
+            spread = max(sk["max_ms"] - sk["min_ms"], st_["max_ms"] - st_["min_ms"])
+            triples = M * nn * P
+            kp, kb = r["peak"].cpu().numpy(), r["best"].cpu().numpy().reshape(-1)
+            floors = {"fp64_issue": triples / 64 * STACK_F64[weights] * F64_CYCLES / (SIMDS * CLOCK) * 1e3,
+                      "gather_bytes": triples * STACK_GATHER / L2_BYTES_PER_S * 1e3}
+            case = {"M": M, "weights": weights, "triples": triples, "contributing": st["contributing"], "parts": st["parts"],
+                    "k_stack": sk, "all_kernels": sc, "torch": st_, "spread_ms": spread,
+                    "ratio_of_medians": st_["median_ms"] / sk["median_ms"],
+                    "kernel_is_faster_beyond_the_spread": bool(st_["median_ms"] - sk["median_ms"] > spread),
+                    "triples_per_second": triples / (sk["median_ms"] * 1e-3),
+                    "peak_max_abs_diff_to_torch": float(np.abs(kp - peak).max()), "best_max_abs_diff_to_torch": float(np.abs(kb - best).max()),
+                    "floor_ms": floors, "binding_floor": max(floors, key=floors.get)}
+            print(json.dumps(case), file=sys.stderr, flush=True)
+            out["cases"].append(case)
+    L.close()
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--stack", type=int, nargs="+", default=None, metavar="M",
+                    help="time the stacking search k_stack (DESIGN.md section 30) for these scan lengths instead, e.g. --stack 256 4096")
     ap.add_argument("--events", type=int, nargs="+", default=[64, 1024, 4096])
     ap.add_argument("--tables", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
@@ -92,6 +194,8 @@ def main():
     ap.add_argument("--missing", type=float, default=0.0, help="share of the picks that are missing (NaN): the masked variant of the kernel")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.stack:
+        return stack_main(a)
     from raytracing_amd import rt_bench as rb
     import torch
     if not torch.cuda.is_available():
