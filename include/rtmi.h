@@ -1121,7 +1121,7 @@ int rtmi_tomo_lsqr_multi(rtmi_tomo *t, rtmi_tomo_basis *p, const rtmi_lsqr_param
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null lp, T, out, handle, t or res; nx, ny, P or
  * E < 1; nx ny > 2^31; P > RTMI_LOCATE_MAX_TABLES; gdx, gdy not finite and > 0, gx0, gy0 not finite; need[e] < 0 (rtmi_locate;
  * rtmi_locate_dev reads a negative need as 0); more than 2^31 (tile, event chunk) pairs; the handle used on another device.
- * Not covered: later arrivals, L1 or equal-differential-time objectives, fp32 tables, several GPUs. */
+ * Not covered: later arrivals, L1 objectives, fp32 tables, several GPUs. */
 #define RTMI_LOCATE_MAX_TABLES 512
 typedef struct rtmi_locator rtmi_locator;
 typedef struct { int64_t nx, ny, P; double gx0, gdx, gy0, gdy; int64_t reserved[4]; } rtmi_locator_params;
@@ -1140,6 +1140,64 @@ int rtmi_locate(rtmi_locator *loc, int64_t E, const double *t, const double *w, 
                 double *maps, rtmi_locate_stats *st);
 int rtmi_locate_dev(rtmi_locator *loc, int64_t E, const double *d_t, const double *d_w, const int32_t *d_need,
                     rtmi_locate_result *res, double *d_maps, rtmi_locate_stats *st);
+
+/* Robust event location by equal differential time (EDT; Zhou 1994, Font et al. 2004) on a locator's tables.  DESIGN.md section
+ * 31.  Where rtmi_locate's least squares lets one bad pick move the location by cells, EDT compares station pairs: it needs no
+ * origin time, a wrong pick spoils only its own pairs, and the share of every station in the sum names the bad pick.  All on
+ * the device, in fp64; every product, sum, quotient and square root one rounded operation, every sum from +0.0
+ * (raytracing_amd/csrc/rt_edt.h holds the arithmetic, tests/edt_ref.py restates it).
+ *   picks     t [E][P], optional w [E][P] (1 / sigma^2) and optional need [E] as in rtmi_locate; so are the rule for a valid
+ *             pick, ref and the staged tr = t - ref, bit for bit
+ *   variance  without weights v = sigma * sigma, sigma finite and > 0; with weights v_r = 1.0 / w[e][r] + sigma * sigma, sigma
+ *             finite and >= 0: a floor for the error of the model
+ *   pair      (a, b), a < b, both picks valid: g = 1.0 / (v_a + v_b); with weights h = sqrt(g), without them h is left out, not
+ *             multiplied by 1
+ * Node x of event e: a station contributes iff its pick is valid and T[r][x] is finite; n is their count; the node is a
+ * candidate iff n >= max(need[e], 2) (need absent: the event's number of valid picks).  Over the contributing pairs, a ascending
+ * in the outer loop, b > a ascending in the inner one:
+ *     d_r = tr_r - T[r][x];  u = d_a - d_b;  z = -((u * u) * g);  k = z < -700.0 ? +0.0 : exp(z)
+ *     S = S + h * k;  H = H + h           (no weights: S = S + k;  H = (double)(n (n - 1) / 2))
+ *     value = S / H, in [0, 1]; -inf at a node that is no candidate
+ * exp is numpy's array exp on float64, bit for bit, by the fma sequence and the two 16-entry tables of
+ * raytracing_amd/csrc/rt_np_exp.h; rtmi_edt_exp (host only, no device) hands it out for z in [-700, 0] (anything else, a NaN
+ * included, is RTMI_ERR_ARG).
+ * The best node is the candidate of greatest value (a NaN counts as -inf), ties to the least node index; no candidate:
+ * node = ix = iy = -1, n = npairs = 0 and every real output NaN.  At the best node and the eight around it (row j = iy - 1 ..
+ * iy + 1; NaN outside the grid), by the same steps in the same order, so bit-equal to maps:
+ *     win_val   value
+ *     omega_r   the share of station r: the sum over the contributing b != r, ascending, of h_rb k_rb, each k with the lower
+ *               station first in u
+ *     win_tau   tau = (sum_r omega_r d_r) / (sum_r omega_r), r ascending, products separate; NaN at a node that is no candidate
+ * t0 = ref + tau of the best node: NaN when every k of the node was cut to zero.  share_sum is the best node's sum of omega,
+ * npairs = n (n - 1) / 2 its contributing pairs.  share [E][P] (or NULL) receives the best node's omega, resid [E][P] (or NULL)
+ * d_r - tau there; both NaN at stations that do not contribute.  maps [E][ny][nx] (or NULL) receives value at every node.
+ * The refinement is rtmi_locate's quadratic (rt_locate.h, host arithmetic) on the negated win_val with win_tau, ref and sw = 1:
+ * x, y, dx, dy, t0_refined, refined as there.  No covariance is reported: -value is no misfit with a known scale; a caller who
+ * wants a pdf builds it from maps.
+ * stats: rtmi_locate_stats with triples = E nx ny P (P - 1) / 2 and contributing the contributing pairs; reserved[0] is the
+ * search kernel's own part of kernel_ms in nanoseconds, reserved[1] the number of groups of event chunks the call was walked in
+ * (with weights g and h are staged per (chunk of 16 events, pair), at most 256 MiB at a time; a positive ep->reserved[0] sets
+ * the chunks per group instead, for tests; no result depends on it).
+ * rtmi_locate_edt_dev takes t, w, need, share, resid and maps as memory of the handle's device (res and st stay host memory);
+ * rtmi_locate_edt is upload, that, download: the same bits.  Events are independent: any split of E over calls gives the same bits.
+ * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: what rtmi_locate refuses; a null ep; a sigma
+ * that is not as stated above; a negative ep->reserved[0].
+ * Not covered: L1 objectives, later arrivals, S - P pairs, a pdf or confidence ellipse from the map, fp32 tables, several GPUs. */
+typedef struct { double sigma; int64_t reserved[4]; } rtmi_edt_params;
+typedef struct {
+    int64_t node, ix, iy, n, npairs;
+    double value, ref, t0, share_sum;
+    double win_val[9], win_tau[9];
+    double x, y, t0_refined, dx, dy;
+    int32_t refined, reserved0;
+    int64_t reserved[2];
+} rtmi_edt_result;
+int rtmi_locate_edt(rtmi_locator *loc, const rtmi_edt_params *ep, int64_t E, const double *t, const double *w, const int32_t *need,
+                    rtmi_edt_result *res, double *share, double *resid, double *maps, rtmi_locate_stats *st);
+int rtmi_locate_edt_dev(rtmi_locator *loc, const rtmi_edt_params *ep, int64_t E, const double *d_t, const double *d_w,
+                        const int32_t *d_need, rtmi_edt_result *res, double *d_share, double *d_resid, double *d_maps,
+                        rtmi_locate_stats *st);
+int rtmi_edt_exp(const double *z, double *out, int64_t n);   /* host only, no device: out[i] = exp(z[i]), -700 <= z[i] <= 0 */
 
 /* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
  * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it

@@ -180,6 +180,20 @@ class LocateStats(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+class EdtParams(C.Structure):
+    """rtmi_edt_params: the pick error (or, with weights, the model-error floor) of rtmi_locate_edt"""
+    _fields_ = [("sigma", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
+class EdtResult(C.Structure):
+    """rtmi_edt_result: one event's best node by equal differential time, its 3 x 3 windows and the refined location"""
+    _fields_ = [("node", C.c_int64), ("ix", C.c_int64), ("iy", C.c_int64), ("n", C.c_int64), ("npairs", C.c_int64),
+                ("value", C.c_double), ("ref", C.c_double), ("t0", C.c_double), ("share_sum", C.c_double),
+                ("win_val", C.c_double * 9), ("win_tau", C.c_double * 9), ("x", C.c_double), ("y", C.c_double),
+                ("t0_refined", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("refined", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved", C.c_int64 * 2)]
+
+
 class StackParams(C.Structure):
     """rtmi_stack_params: the trace axis, the origin-time scan and the event selection of rtmi_locate_stack"""
     _fields_ = [("nt", C.c_int64), ("M", C.c_int64), ("ct0", C.c_double), ("cdt", C.c_double), ("o0", C.c_double), ("od", C.c_double),
@@ -318,6 +332,11 @@ SYMBOLS = {
     "rtmi_locate": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _ip, C.POINTER(LocateResult), _dp, C.POINTER(LocateStats)]),
     "rtmi_locate_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LocateResult), C.c_void_p,
                                   C.POINTER(LocateStats)]),
+    "rtmi_locate_edt": (C.c_int, [C.c_void_p, C.POINTER(EdtParams), C.c_int64, _dp, _dp, _ip, C.POINTER(EdtResult), _dp, _dp, _dp,
+                                  C.POINTER(LocateStats)]),
+    "rtmi_locate_edt_dev": (C.c_int, [C.c_void_p, C.POINTER(EdtParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(EdtResult), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LocateStats)]),
+    "rtmi_edt_exp": (C.c_int, [_dp, _dp, C.c_int64]),
     "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
                                     C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_np_exp.h"
 #include "rt_polytab.h"
 #include "rtmi_field.h"
 
@@ -28,35 +29,11 @@ constexpr double kSteepRate = 40.0;
 // rounded toward zero onto a 2^-4 grid -- r = x - N*ln2 in two pieces, a degree-6 polynomial in three interleaved pairs,
 // 2^(j/16) from a 16-entry table with its correction term, scaled by 2^floor(N).  |x| >= 707.7 (SVML's scalar fall-back):
 // ocml's exp -- there 1 + e rounds to e or to 1 and the interface's n is sqrt(2) or 1 whatever the last bits of e.
+// The main path is rt_np_exp.h's, one text with the host's and with rt_edt.h's.
 // On the device: tests/test_gpu_elementary.py (rtmi_debug_exp, below) -- the oracle's bits on 2.6e6 main-path arguments.
 __device__ static double np_exp(double x) {
-    static const double T16[16] = {0x1.0000000000000p+0, 0x1.0b5586cf9890fp+0, 0x1.172b83c7d517bp+0, 0x1.2387a6e756238p+0,
-        0x1.306fe0a31b715p+0, 0x1.3dea64c123422p+0, 0x1.4bfdad5362a27p+0, 0x1.5ab07dd485429p+0, 0x1.6a09e667f3bcdp+0,
-        0x1.7a11473eb0187p+0, 0x1.8ace5422aa0dbp+0, 0x1.9c49182a3f090p+0, 0x1.ae89f995ad3adp+0, 0x1.c199bdd85529cp+0,
-        0x1.d5818dcfba487p+0, 0x1.ea4afa2a490dap+0};
-    static const double TL16[16] = {0x0.0p+0, 0x1.79aa65d837b6dp-54, -0x1.01b15eaa59348p-55, 0x1.68efde3a8a894p-54,
-        0x1.34d754db0abb6p-55, 0x1.59f48a72a4c6dp-55, 0x1.690cebb7aafb0p-56, 0x1.063e1e21c5409p-54, -0x1.3b3efbf5e2228p-54,
-        -0x1.b32dcb94da51dp-56, 0x1.db72fc1f0eab4p-55, 0x1.1affc2b91ce27p-56, 0x1.c1a7792cb3387p-55, 0x1.36eae30af0cb3p-56,
-        0x1.4a385a63d07a7p-56, -0x1.ff7128fd391f0p-55};
-    const double L2E = 0x1.71547652b82fep+0, LN2H = 0x1.62e42fefa39efp-1, LN2L = 0x1.abc9e3b39803fp-56;
-    const double A = 0x1.7411836940c04p-10, B = 0x1.1101cbbc265c0p-7, C = 0x1.55557242d68fep-5, D = 0x1.5555553939732p-3,
-                 E = 0x1.000000000d008p-1, F = 0x1.fffffffffff70p-1;
     if (!(fabs(x) < 0x1.61da04cbafe44p+9)) return exp(x);
-    // floor of the EXACT product x*L2E on the 1/16 grid (== the toward-zero fma onto the shifter 1.5*2^48 + 1023)
-    const double p = x * L2E, e = __builtin_fma(x, L2E, -p);
-    double f16 = floor(p * 16.0);
-    if (f16 == p * 16.0 && e < 0) f16 -= 1.0;
-    const double N = f16 * 0.0625;
-    const int j = (int)((long long)f16 & 15);
-    double r = __builtin_fma(-N, LN2H, x);
-    r = __builtin_fma(-N, LN2L, r);
-    const double r2 = r * r;
-    const double P1 = __builtin_fma(A, r, B), P2 = __builtin_fma(C, r, D), P3 = __builtin_fma(E, r, F);
-    double q = __builtin_fma(r2, P1, P2);
-    q = __builtin_fma(r2, q, P3);
-    double t = __builtin_fma(q, r, TL16[j]);
-    t = __builtin_fma(T16[j], t, T16[j]);
-    return ldexp(t, (int)floor(N));
+    return rt::np_exp_main(x, rt::np_exp_tables());
 }
 
 __device__ static double scenario_n(int sc, double a, double b) {

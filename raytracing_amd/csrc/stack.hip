@@ -18,10 +18,8 @@
 
 namespace {
 
-constexpr int kTile = 256;              // nodes of a block, one per lane
-constexpr int kChunk = 16;              // scan indices whose running sums a lane keeps in registers
+// kTile nodes of a block, one per lane, and kChunk scan indices whose running sums a lane keeps in registers: rtmi_locator.h
 constexpr int kBlocksPerCu = 32;        // the search aims at this many blocks per CU, so that the last round of blocks is a small share
-constexpr unsigned kNoNode = 0xffffffffu;
 
 // what the window kernel leaves per event for the host
 struct DevWin {

@@ -2177,6 +2177,21 @@ def locate_stats(st):
             "search_ms": st.reserved[0] * 1e-6}                   # k_locate's own part of kernel_ms
 
 
+def edt_stats(st):
+    return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "triples": int(st.triples), "contributing": int(st.contributing),
+            "search_ms": st.reserved[0] * 1e-6,                    # k_edt's own part of kernel_ms
+            "groups": int(st.reserved[1])}                         # the groups of event chunks the call was walked in
+
+
+def edt_exp(z):
+    """rtmi_edt_exp: exp(z) for z in [-700, 0] as rtmi_locate_edt's device code evaluates it (numpy's array exp, restated), on the
+    host; tests/edt_ref.py takes its exp from here"""
+    zz = np.ascontiguousarray(z, dtype=np.float64)
+    out = np.empty_like(zz)
+    check(lib().rtmi_edt_exp(dptr(zz.reshape(-1)), dptr(out.reshape(-1)), zz.size))
+    return out
+
+
 def stack_stats(st):
     return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "triples": int(st.triples), "contributing": int(st.contributing),
             "truncated": bool(st.truncated), "search_ms": st.reserved[0] * 1e-6,            # k_stack's own part of kernel_ms
@@ -2197,6 +2212,8 @@ class Locator:
       [E]: the fewest contributing picks of a node (default: all the event's valid picks).
       locate_device(picks, weights=None, min_picks=None, maps=False, ...) takes torch tensors on the handle's device (fp64 picks
       and weights, int32 min_picks) and returns maps as a tensor on it: the same bits, no copy of them through the host.
+      locate_edt(picks, sigma, ...) is the robust search by equal differential time, for picks that may contain outliers
+      (see its own text); locate_edt_device its form on torch tensors.
       stack(traces [P, nt], dt, t0, scan=(o0, od, M), ...) needs no picks: it stacks one characteristic function per station along
       every node's moveout for every origin time of the scan and takes events from the peaks (see stack's own text).
     With stats=True the calls return (result, stats)."""
@@ -2304,6 +2321,109 @@ class Locator:
         if maps:
             out["maps"] = m
         return (out, locate_stats(st)) if stats else out
+
+    def _edt_result(self, res, E, refine):
+        a = np.frombuffer(res, dtype=np.dtype(_lib.EdtResult)).copy() if E else np.zeros(0, dtype=np.dtype(_lib.EdtResult))
+        out = {"node": a["node"].copy(), "ix": a["ix"].copy(), "iy": a["iy"].copy(), "count": a["n"].copy(), "npairs": a["npairs"].copy(),
+               "value": a["value"].copy(), "ref": a["ref"].copy(), "t0_node": a["t0"].copy(), "share_sum": a["share_sum"].copy(),
+               "win_val": a["win_val"].reshape(E, 3, 3).copy(), "win_tau": a["win_tau"].reshape(E, 3, 3).copy()}
+        if refine:
+            out.update(x=a["x"].copy(), y=a["y"].copy(), t0=a["t0_refined"].copy(), dx=a["dx"].copy(), dy=a["dy"].copy(),
+                       refined=a["refined"].copy())
+        else:
+            gx0, gdx, _, gy0, gdy, _ = self.grid
+            none = out["node"] < 0
+            out.update(x=np.where(none, np.nan, float(gx0) + out["ix"] * float(gdx)), y=np.where(none, np.nan, float(gy0) + out["iy"] * float(gdy)),
+                       t0=out["t0_node"].copy(), dx=np.where(none, np.nan, 0.0), dy=np.where(none, np.nan, 0.0),
+                       refined=np.zeros(E, dtype=np.int32))
+        return out
+
+    @staticmethod
+    def _edt_params(sigma, chunks_per_group):
+        ep = _lib.EdtParams()
+        ep.sigma = float(sigma)
+        ep.reserved[0] = int(chunks_per_group)
+        return ep
+
+    def locate_edt(self, picks, sigma, weights=None, min_picks=None, maps=False, refine=True, shares=False, stats=False,
+                   _chunks_per_group=0):
+        """Robust location by equal differential time (rtmi_locate_edt, include/rtmi.h): the node where the most
+        station pairs agree on their traveltime difference within sigma, whatever the origin time.  One bad pick spoils only its
+        own pairs, where `locate`'s least squares moves by cells.  picks, weights, min_picks as in `locate` (at least two picks
+        must contribute); sigma is the pick error in seconds, or with weights (1 / sigma_r^2) a floor for the model's error added
+        to every pick's variance (then it may be 0).  Returns a dict of arrays over the events:
+          x, y, t0         the refined location and origin time where the refinement is accepted, else the node's own
+          node, ix, iy     the best node (-1: no node has two and min_picks contributing picks); count, npairs, value in [0, 1]
+          win_val, win_tau [E, 3, 3], dx, dy, refined, t0_node, ref, share_sum; with maps=True also maps [E, ny, nx]
+          share, resid [E, P] with shares=True: each station's part of the best node's sum -- the station with a far smaller share
+                           than the others holds the bad pick -- and its residual against t0_node; NaN where it does not contribute
+        locate_edt_device takes torch tensors on the handle's device and returns maps, share and resid as tensors on it."""
+        who = "Locator.locate_edt"
+        t = np.ascontiguousarray(picks, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.P:
+            raise ValueError(f"{who}: picks must be [E, {self.P}]")
+        E = t.shape[0]
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w is not None and w.shape != t.shape:
+            raise ValueError(f"{who}: weights must have the shape of picks")
+        need = None
+        if min_picks is not None:
+            need = np.ascontiguousarray(np.broadcast_to(np.asarray(min_picks, dtype=np.int32), (E,)))
+        ep = self._edt_params(sigma, _chunks_per_group)
+        h = self._open()
+        res = (_lib.EdtResult * E)()
+        m = np.empty((E, self.ny, self.nx)) if maps else None
+        sh = np.empty((E, self.P)) if shares else None
+        rs = np.empty((E, self.P)) if shares else None
+        st = _lib.LocateStats()
+        check(lib().rtmi_locate_edt(h, C.byref(ep), E, dptr(t), dptr(w), None if need is None else need.ctypes.data_as(_lib._ip), res,
+                                    dptr(sh), dptr(rs), dptr(m), C.byref(st)))
+        out = self._edt_result(res, E, refine)
+        if maps:
+            out["maps"] = m
+        if shares:
+            out.update(share=sh, resid=rs)
+        return (out, edt_stats(st)) if stats else out
+
+    def locate_edt_device(self, picks, sigma, weights=None, min_picks=None, maps=False, refine=True, shares=False, stats=False,
+                          _chunks_per_group=0):
+        import torch
+        who = "Locator.locate_edt_device"
+        for name, a, dt in (("picks", picks, torch.float64), ("weights", weights, torch.float64), ("min_picks", min_picks, torch.int32)):
+            if a is None:
+                continue
+            if not isinstance(a, torch.Tensor):
+                raise TypeError(f"{who}: {name} must be a torch tensor")
+            if a.dtype != dt:
+                raise TypeError(f"{who}: {name} must be {dt}")
+            if not a.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous")
+            if not a.is_cuda:                          # which GPU it is on, the library checks against the handle's
+                raise ValueError(f"{who}: {name} must be a tensor on a GPU, not on the host")
+        if picks is None or picks.dim() != 2 or picks.shape[1] != self.P:
+            raise ValueError(f"{who}: picks must be [E, {self.P}]")
+        E = picks.shape[0]
+        if weights is not None and weights.shape != picks.shape:
+            raise ValueError(f"{who}: weights must have the shape of picks")
+        if min_picks is not None and tuple(min_picks.shape) != (E,):
+            raise ValueError(f"{who}: min_picks must be [E]")
+        ep = self._edt_params(sigma, _chunks_per_group)
+        h = self._open()
+        res = (_lib.EdtResult * E)()
+        dev = picks.device
+        m = torch.empty((E, self.ny, self.nx), dtype=torch.float64, device=dev) if maps else None
+        sh = torch.empty((E, self.P), dtype=torch.float64, device=dev) if shares else None
+        rs = torch.empty((E, self.P), dtype=torch.float64, device=dev) if shares else None
+        st = _lib.LocateStats()
+        p = lambda a: None if a is None else a.data_ptr()                                    # noqa: E731
+        torch.cuda.synchronize(dev)                    # the library works on the null stream
+        check(lib().rtmi_locate_edt_dev(h, C.byref(ep), E, p(picks), p(weights), p(min_picks), res, p(sh), p(rs), p(m), C.byref(st)))
+        out = self._edt_result(res, E, refine)
+        if maps:
+            out["maps"] = m
+        if shares:
+            out.update(share=sh, resid=rs)
+        return (out, edt_stats(st)) if stats else out
 
     def _stack_params(self, who, nt, dt, t0, scan, min_stations, threshold, min_sep, max_events):
         o0, od, M = scan

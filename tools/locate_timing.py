@@ -20,6 +20,14 @@ issue rate.
 plain torch (broadcast, gather, chunked over the scan), with the kernel's two floors: fp64 issue and gathered bytes.
 
     python tools/locate_timing.py --stack 256 4096 [--tables 32] [--reps 5] [--torch-chunk 8] [--out FILE.json]
+
+--edt times the search by equal differential time instead: k_edt on the same grid and tables for the event
+counts given (default 64 and 1024), without and with weights, and once more without weights with a tenth of the picks missing,
+against the same objective in plain torch: per event the differences of all station pairs broadcast over the nodes, exp, the sum
+over the pairs and argmax, one event at a time (five [pairs, nodes] fp64 temporaries of 1.6 GB at P = 32).  Pairs per second and the
+kernel's fp64 issue floor are printed with it.
+
+    python tools/locate_timing.py --edt [--events 64 1024] [--tables 32] [--reps 5] [--sigma 0.01] [--out FILE.json]
 """
 import argparse
 import json
@@ -182,10 +190,101 @@ def stack_main(a):
             fh.write(text + "\n")
 
 
+EDT_F64 = {False: 32, True: 34}     # fp64-rate vector instructions per (node, pair, event) in k_edt's inner loop where a chunk has
+                                    # all its picks, without and with weights, read off the ISA (make asm UNIT=edt.hip; DESIGN.md
+                                    # section 31): 513 and 545 in the loop body of 16 events
+
+
+def torch_edt(torch, Td, td, wd, sigma):
+    """the yardstick of --edt: (nodes [E], device ms); station 0 has a pick in every event"""
+    P = Td.shape[0]
+    Tf = Td.reshape(P, -1)
+    ij = torch.triu_indices(P, P, 1, device=Td.device)
+    ia, ib = ij[0], ij[1]
+    s2 = sigma * sigma
+    nodes = torch.empty(td.shape[0], dtype=torch.int64, device=td.device)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for e in range(td.shape[0]):
+        d = (td[e] - td[e, 0])[:, None] - Tf
+        u = d[ia] - d[ib]
+        if wd is None:
+            k = torch.exp(-(u * u) * (1.0 / (s2 + s2)))
+            ok = torch.isfinite(td[e])
+            if bool(ok.all()):
+                value = k.sum(dim=0) / ia.shape[0]
+            else:
+                value = torch.nan_to_num(k).sum(dim=0) / (ok[ia] & ok[ib]).sum()
+        else:
+            v = 1.0 / wd[e] + s2
+            g = 1.0 / (v[ia] + v[ib])
+            h = torch.sqrt(g)
+            value = (h[:, None] * torch.exp(-(u * u) * g[:, None])).sum(dim=0) / h.sum()
+        nodes[e] = value.argmax()
+    b.record()
+    torch.cuda.synchronize()
+    return nodes.cpu().numpy(), a.elapsed_time(b)
+
+
+def edt_main(a):
+    """--edt: the search kernel k_edt on the section-29 case against the same objective in plain torch"""
+    from raytracing_amd import rt_bench as rb
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("locate_timing: no GPU; nothing is measured without one")
+    P = a.tables
+    grid, T, _ = problem(P, 1)
+    nn = T.shape[1] * T.shape[2]
+    npairs = P * (P - 1) // 2
+    L = rb.Locator(T, grid)
+    Td = torch.from_numpy(T).cuda()
+    events = a.events if a.events != [64, 1024, 4096] else [64, 1024]
+    rows = [(E, weights, 0.0) for E in events for weights in (False, True)] + [(events[-1], False, 0.1)]
+    out = {"grid": [grid[2], grid[5]], "tables": P, "sigma": a.sigma, "reps": a.reps, "cases": []}
+    for E, weights, missing in rows:
+        _, _, t = problem(P, E, seed=E)
+        rng = np.random.default_rng(E + 1)
+        w = 1.0 / rng.uniform(0.005, 0.02, t.shape) ** 2 if weights else None
+        if missing:
+            t[:, 1:][rng.random((E, P - 1)) < missing] = np.nan           # station 0 keeps its pick: ref as the yardstick takes it
+        td = torch.from_numpy(t).cuda()
+        wd = None if w is None else torch.from_numpy(w).cuda()
+        kernel = lambda: L.locate_edt_device(td, a.sigma, wd, stats=True)                # noqa: E731
+        kernel(); torch_edt(torch, Td, td[:2], None if wd is None else wd[:2], a.sigma)     # warm both
+        tk, tc, tt = [], [], []
+        for _ in range(a.reps):                                                  # alternating
+            r, st = kernel()
+            tk.append(st["search_ms"])
+            tc.append(st["kernel_ms"])
+            nodes, ms = torch_edt(torch, Td, td, wd, a.sigma)
+            tt.append(ms)
+        sk, st_, sc = series(tk), series(tt), series(tc)
+        spread = max(sk["max_ms"] - sk["min_ms"], st_["max_ms"] - st_["min_ms"])
+        pairs = E * nn * npairs
+        case = {"events": E, "weights": weights, "missing": missing, "pairs": pairs, "contributing": st["contributing"], "groups": st["groups"],
+                "k_edt": sk, "all_kernels": sc, "torch": st_, "spread_ms": spread,
+                "ratio_of_medians": st_["median_ms"] / sk["median_ms"],
+                "kernel_is_faster_beyond_the_spread": bool(st_["median_ms"] - sk["median_ms"] > spread),
+                "pairs_per_second": st["contributing"] / (sk["median_ms"] * 1e-3),
+                "nodes_equal_to_torchs": int((nodes == r["node"]).sum()),
+                "floor_ms": {"fp64_issue": st["contributing"] / 64 * EDT_F64[weights] * F64_CYCLES / (SIMDS * CLOCK) * 1e3}}
+        print(json.dumps(case), file=sys.stderr, flush=True)
+        out["cases"].append(case)
+    L.close()
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--stack", type=int, nargs="+", default=None, metavar="M",
                     help="time the stacking search k_stack (DESIGN.md section 30) for these scan lengths instead, e.g. --stack 256 4096")
+    ap.add_argument("--edt", action="store_true", help="time the equal-differential-time search k_edt (DESIGN.md section 31) instead")
+    ap.add_argument("--sigma", type=float, default=0.01, help="--edt: the pick error in seconds")
     ap.add_argument("--events", type=int, nargs="+", default=[64, 1024, 4096])
     ap.add_argument("--tables", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
@@ -196,6 +295,8 @@ def main():
     a = ap.parse_args()
     if a.stack:
         return stack_main(a)
+    if a.edt:
+        return edt_main(a)
     from raytracing_amd import rt_bench as rb
     import torch
     if not torch.cuda.is_available():
