@@ -5,7 +5,8 @@
 // what was measured; rt_lsqr.h the scalar recurrence (host, scipy's operation order).  _lsqr_full on a handle with kmah solves
 // for the full trace ch0 + H ch1 with the Hilbert transform of kirchhoff_hilbert.hip around the pair;
 // rtmi_kirchhoff_lsqr_filtered puts the trace filter of kirchhoff_filter.hip and its transpose around that.
-// The loop, its vector passes and the order-independent norm are rt_lsqr_device.h's, shared with tomo.hip.
+// The loop, its vector passes and the order-independent norm are rt_lsqr_device.h's, shared with tomo.hip: a solve here is that
+// loop with one column.  A start model is taken out of the data before the loop and added to the model after it, here.
 #include "rt_hilbert.h"
 #include "rt_kirchhoff.h"
 #include "rt_lsqr_device.h"
@@ -17,7 +18,8 @@ namespace {
 // (with full): on a handle with a filter set, with B that operator, A x = F (B x) and A^T u = B^T (F^T u); F is out of place, so
 // the call holds one more N nt vector, Fb, for B v and for F^T u, which are never live together.  With no filter set `filtered`
 // changes nothing.  lo: the options of rtmi_kirchhoff_lsqr_weighted, uploaded once; NULL, or every pointer of
-// it NULL, allocates nothing and runs the loop as it ran before there were options.
+// it NULL, allocates nothing and runs the loop as it ran before there were options.  With x0 the right-hand side is
+// fl(wr fl(data - A x0)), one forward product and one pass that also does the loop's fl(wr u), and x = fl(x0 + x) after its fl(dc x).
 int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
              const double* data, double* x, double* history, rtmi_lsqr_stats* st) {
     RTMI_ARG(k, "null handle");
@@ -37,6 +39,7 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
     double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr;
     double *Av1 = nullptr, *Hu = nullptr;                                             // channel 1 of A v, and -H u: with hil only
     double* Fb = nullptr;                                                             // B v, then F^T u: with fil only
+    double* x0 = nullptr;
     const std::string no_mem = std::string(who) + ": hipMalloc failed";
     const struct { double** p; bool wanted; } traces[] = {{&u, true}, {&Av, true}, {&Av1, hil}, {&Hu, hil}, {&Fb, fil}};
     for (const auto& a : traces)
@@ -45,8 +48,13 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
         if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
     LsqrOptions O;
     size_t nopt = 0;
-    RTMI_RC(lsqr_upload_options(who, mem, lo, per, per, nm, &O, &nopt));
-    const Vec V{k->red, k->cus};
+    RTMI_RC(lsqr_upload_options(who, mem, lo, 1, false, per, per, nm, &O, &nopt));
+    if (lo && lo->x0) {
+        if (mem.get(&x0, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(x0, lo->x0, nm * sizeof(double), hipMemcpyHostToDevice));
+        nopt += nm;
+    }
+    const Vec V{k->red, k->cus, 1};
     rtmi_lsqr_stats out{};
     // the call's vectors, the handle's staging (with kmah: two channels per level) and, with hil and with fil, their taps
     const size_t staging = (size_t)(k->nlev ? k->nlev : 1) * (k->kmah ? 2 : 1) * per + nm;
@@ -57,7 +65,8 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
     rtmi_kirchhoff_stats ks{};
 
     // t = A^T s and t = A s; the Hilbert and filter kernels' event time counts as the operator's
-    auto At = [&](const double* s, double* t, bool*) {
+    auto At = [&](const double* s, double* t, unsigned long long, bool* range) {
+        range[0] = false;
         double ms = 0.0, fms = 0.0;
         if (fil) {
             RTMI_RC(rtmi_internal_kirchhoff_filter_dev(k, who, s, true, Fb, &fms));
@@ -68,7 +77,7 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
         operator_ms += ks.kernel_ms + ms + fms;
         return (int)RTMI_OK;
     };
-    auto Ax = [&](const double* s, double* t) {
+    auto Ax = [&](const double* s, double* t, unsigned long long) {
         double ms = 0.0, fms = 0.0;
         double* b = fil ? Fb : t;                                                     // B s
         RTMI_RC(rtmi_internal_kirchhoff_model_dev(k, who, s, b, hil ? Av1 : nullptr, &ks, false));
@@ -80,7 +89,22 @@ int lsqr_run(const char* who, bool full, bool filtered, rtmi_kirchhoff* k, const
 
     RTMI_HIP(hipMemcpy(u, data, per * sizeof(double), hipMemcpyHostToDevice));       // the data go up once
     RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
+    double start_ms = 0.0;                                                            // the start model's two passes: vector time
+    auto timed = [&](auto&& pass) {
+        const double t0 = now_ms();
+        RTMI_RC(pass());
+        RTMI_HIP(hipStreamSynchronize(nullptr));
+        start_ms += now_ms() - t0;
+        return (int)RTMI_OK;
+    };
+    if (x0) {
+        RTMI_RC(Ax(x0, Av, 1ull));
+        RTMI_RC(timed([&]() { return lsqr_sub_start(who, V, u, per, Av, per, O.wr, O.wrs); }));   // both in one pass: the same two roundings
+        O.rhs_weighted = O.wr != nullptr;
+    }
     RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out, O));
+    if (x0) RTMI_RC(timed([&]() { return lsqr_add_start(who, V, xd, nm, x0, nm); }));
+    out.vector_ms += start_ms;
     RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));           // the model comes down once
     out.total_ms = now_ms() - t_begin;
     out.operator_ms = operator_ms;
@@ -120,19 +144,19 @@ RTMI_EXPORT int rtmi_debug_fix_norm(const double* x, int64_t n, double* norm, in
     RTMI_ARG(n >= 1, "n must be >= 1");
     for (int64_t i = 0; i < n; i++) RTMI_ARG(std::isfinite(x[i]), "x has a value that is not finite");
     int dev = 0;
-    Vec V{};
+    Vec V{nullptr, 1, 1};
     RTMI_HIP(hipGetDevice(&dev));
     RTMI_HIP(hipDeviceGetAttribute(&V.cus, hipDeviceAttributeMultiprocessorCount, dev));
     DevMem mem;
     double* d = nullptr;
     RTMI_HIP(mem.get(&d, (size_t)n * sizeof(double)));
-    RTMI_HIP(mem.get(&V.red, kRedWords * sizeof(unsigned long long)));
+    RTMI_HIP(mem.get(&V.red, kRedM * sizeof(unsigned long long)));
     RTMI_HIP(hipMemcpy(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     double M = 0.0;
     bool range = false;
     int ee = 0;
-    RTMI_RC(rtmi_internal_absmax_finite(who, V.red, V.cus, d, (size_t)n, &M));
-    RTMI_RC(norm_of(who, V, d, (size_t)n, M, norm, &ee, &range));
+    RTMI_RC(absmax(who, V, d, (size_t)n, (size_t)n, 1ull, &M));
+    RTMI_RC(norms(who, V, d, (size_t)n, (size_t)n, 1ull, &M, norm, &range, &ee));
     RTMI_ARG(!range, "max|x|^2 is not a normal number (RTMI_LSQR_RANGE)");
     *e = ee;
     return RTMI_OK;

@@ -14,11 +14,12 @@
 //                     furthest behind names the cell, so that neighbouring rays stay together although their segment indices
 //                     drift apart), and the sums go into two integer words per sample with adds that return nothing (add_split),
 //                     read as one integer and rounded once (rt_fix128.h): the same bits in every schedule and order of appends.
-// rtmi_tomo_lsqr runs the loop of rt_lsqr_device.h over the pair, stacked with the first-difference rows of the smoothing terms.
-// The model basis follows (rtmi_tomo_basis_*, rtmi_tomo_lsqr_basis): its own kernels and entries, which call
-// the products above as they are.  The last part is the same for S vectors at once (rtmi_tomo_apply_multi, _transpose_multi,
-// rtmi_tomo_lsqr_multi): k_tomo_apply_multi and k_tomo_transpose_multi read a segment once for a chunk of
-// columns held in registers, and the solver runs the loop of rt_lsqr_multi.h.  Column s has the bits of the single entries.
+// Both are compiled for chunks of C = 8, 4, 2 and 1 columns (vectors are planes: column c of x is x + c xs; the transposed
+// product's width 1 is k_tomo_transpose1, the same arithmetic with the integers kept per lane), read a segment once
+// for the chunk, and serve the single entries as nrhs = 1 and rtmi_tomo_apply_multi, _transpose_multi with the caller's nrhs
+// (DESIGN.md section 28).  The model basis follows (rtmi_tomo_basis_*), then the one solver body,
+// tomo_lsqr_run: the loop of rt_lsqr_device.h over the stacked operator [A P | Dx | Dy | Dxx | Dyy] on S planes, which
+// rtmi_tomo_lsqr, _lsqr_weighted and _lsqr_basis run with S = 1 and rtmi_tomo_lsqr_multi with the caller's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,7 +32,6 @@
 
 #include "rt_fix128.h"
 #include "rt_lsqr_device.h"
-#include "rt_lsqr_multi.h"
 #include "rt_sens_walk.h"
 #include "rt_tomo.h"
 #include "rt_tomo_basis.h"
@@ -43,6 +43,7 @@ static_assert(rt::kTomoSlice == 64, "a slice is a wave");
 // copies' integers are summed before the one rounding.  Rays of one source share their first cells: the copies spread the adds to
 // those few addresses.
 constexpr int kTomoCopies = 8;
+constexpr size_t kTomoRed = (size_t)kMultiMax * kRedM + 2;
 
 // One append's rows
 struct TomoBlock {
@@ -67,27 +68,25 @@ struct rtmi_tomo {
     std::vector<TomoBlock> blocks;
     int64_t rows = 0, segments = 0, padded = 0;
     double vmax = 0.0, compile_ms = 0.0;
-    unsigned long long* acc = nullptr;        // [kTomoCopies] x (A [nz], B [nz]): the transposed product's split accumulators (add_split)
-    unsigned long long* red = nullptr;        // kRedWords reduction words (rt_lsqr_device.h: [0] .. [3]); [4] a fill pass's max |p|, [5] atomics
-    // the multi-vector calls', allocated by the first of them (ensure_multi): accm [acc_cols] x acc, grown when a call has more
-    // columns; redm [kMultiMax] x kRedM reduction words (rt_lsqr_multi.h)
-    unsigned long long *accm = nullptr, *redm = nullptr;
+    // [acc_cols] x [kTomoCopies] x (A [nz], B [nz]): the transposed product's split accumulators (add_split), one set per column:
+    // one column at create, grown when a call has more (ensure_cols)
+    unsigned long long* acc = nullptr;
     int acc_cols = 0;
+    // kTomoRed reduction words: [kMultiMax] x kRedM, the columns' of rt_lsqr_device.h, then a fill pass's max |p| and the atomics
+    unsigned long long* red = nullptr;
     hipEvent_t ev[2] = {};
     size_t nz() const { return (size_t)F.qx * (size_t)F.qy; }
     size_t bytes() const {
-        size_t b = ((size_t)kTomoCopies * 2 * nz() + kRedWords) * sizeof(unsigned long long);
-        b += (size_t)acc_cols * kTomoCopies * 2 * nz() * sizeof(unsigned long long);
-        if (redm) b += (size_t)kMultiMax * kRedM * sizeof(unsigned long long);
+        size_t b = ((size_t)acc_cols * kTomoCopies * 2 * nz() + kTomoRed) * sizeof(unsigned long long);
         for (const TomoBlock& k : blocks) b += k.bytes();
         return b;
     }
+    unsigned long long* red_vmax() const { return red + kTomoRed - 2; }
+    unsigned long long* red_atomics() const { return red + kTomoRed - 1; }
     ~rtmi_tomo() {
         for (TomoBlock& b : blocks) b.release();
         if (acc) (void)hipFree(acc);
         if (red) (void)hipFree(red);
-        if (accm) (void)hipFree(accm);
-        if (redm) (void)hipFree(redm);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -160,24 +159,44 @@ __global__ void __launch_bounds__(256) k_tomo_walk(Rows<T> rec, Args A, const in
 }
 
 // ------------------------------------------------------------------------------------------------------------ products
-// One lane per row of a block: y[r] for r < rows.
-__global__ void __launch_bounds__(256) k_tomo_apply(const int32_t* __restrict__ len, const int64_t* __restrict__ off, const int32_t* __restrict__ base,
-                                                    const double* __restrict__ val, long rows, int qx, const double* __restrict__ x,
-                                                    double* __restrict__ y) {
+// A product takes nrhs <= kMultiMax vectors through one read of the matrix.  A kernel is compiled for chunks of C = 8, 4, 2 and 1
+// columns; a launch takes the widest that nrhs fills, with the chunk in blockIdx.y, so that a product is one launch per append
+// whatever nrhs is.  The last chunk may be partial: its missing columns are not written.
+int chunk_of(int nrhs) { return nrhs >= 8 ? 8 : nrhs >= 4 ? 4 : nrhs >= 2 ? 2 : 1; }
+
+// One lane per row of a block: y[c][r] for r < rows and the columns c0 .. c0 + C - 1.  A segment's base and p are loaded once, the
+// gathers and the five roundings are the column's own.  A column past nrhs reads the last one's x and is not written.
+template <int C>
+__global__ void __launch_bounds__(256) k_tomo_apply(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                                    const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
+                                                    int nrhs, const double* __restrict__ x, size_t xs, double* __restrict__ y, size_t ys) {
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
+    const int c0 = (int)blockIdx.y * C;
     const int lane = (int)(r & 63);
     const int64_t o = off[r >> 6];
     const int n = len[r];
-    double acc = 0.0;
+    const double* xc[C];
+    double acc[C];
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        xc[j] = x + (size_t)min(c0 + j, nrhs - 1) * xs;
+        acc[j] = 0.0;
+    }
     for (int k = 0; k < n; k++) {
-        const double* z = x + base[rt::tomo_slot(o, k, lane)];
+        const int b = base[rt::tomo_slot(o, k, lane)];
         const double p0 = val[rt::tomo_value(o, k, 0, lane)], p1 = val[rt::tomo_value(o, k, 1, lane)];
         const double p2 = val[rt::tomo_value(o, k, 2, lane)], p3 = val[rt::tomo_value(o, k, 3, lane)];
-        const double t = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p0, z[0]), __dmul_rn(p1, z[1])), __dmul_rn(p2, z[qx])), __dmul_rn(p3, z[qx + 1]));
-        acc = __dadd_rn(acc, t);
+#pragma unroll
+        for (int j = 0; j < C; j++) {
+            const double* z = xc[j] + b;
+            const double t = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p0, z[0]), __dmul_rn(p1, z[1])), __dmul_rn(p2, z[qx])), __dmul_rn(p3, z[qx + 1]));
+            acc[j] = __dadd_rn(acc[j], t);
+        }
     }
-    y[r] = acc;
+#pragma unroll
+    for (int j = 0; j < C; j++)
+        if (c0 + j < nrhs) y[(size_t)(c0 + j) * ys + r] = acc[j];
 }
 
 // s quanta into sample i of the split accumulators: the low 32 bits of s into A[i], the rest (signed) into B[i], so that
@@ -192,11 +211,14 @@ __device__ __forceinline__ int add_split(unsigned long long* A, unsigned long lo
     return 2;
 }
 
-// One lane per row of a block, a wave per slice.  A weight that is not finite counts as 0.
-__global__ void __launch_bounds__(256) k_tomo_transpose(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
-                                                        const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
-                                                        const double* __restrict__ w, int e, unsigned long long* acc, size_t nz,
-                                                        unsigned long long* natomics) {
+// The transposed product of one column (nrhs = 1): one lane per row of a block, a wave per slice; the lanes step through the
+// cells as in k_tomo_transpose below.  With one column a lane forms its four integers when it takes its segment and keeps them,
+// not when it joins an add: 60 VGPRs against the template's 66 at C = 1, which by_chunk therefore does not instantiate.  The same
+// lanes take part, so the bits and the count of atomics are the template's.  A weight that is not finite counts as 0.
+__global__ void __launch_bounds__(256) k_tomo_transpose1(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                                         const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
+                                                         const double* __restrict__ w, int e, unsigned long long* acc, size_t nz,
+                                                         unsigned long long* natomics) {
     unsigned long long* const A = acc + (size_t)(blockIdx.x % kTomoCopies) * 2 * nz;
     unsigned long long* const B = A + nz;
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
@@ -206,10 +228,6 @@ __global__ void __launch_bounds__(256) k_tomo_transpose(const int32_t* __restric
     const double wr = in ? w[r] : 0.0;
     const int n = (in && fabs(wr) < INFINITY && wr != 0.0) ? len[r] : 0;
     long long nat = 0;
-    // Neighbouring rays visit much the same cells, but not at the same segment index: a ray that clips a corner has one visit more.
-    // So the lanes do not step through k together.  Each holds its next segment; the lane that is furthest behind names a cell,
-    // every lane whose next segment is that cell joins its add and moves on, the others wait.  Which lanes add together changes no
-    // bit: the sums are integers.  The segment after the next is loaded a step ahead.
     int k = 0, b = 0, nb = 0;
     long long m[4] = {0, 0, 0, 0};
     double np[4] = {0.0, 0.0, 0.0, 0.0};
@@ -261,6 +279,106 @@ __global__ void __launch_bounds__(256) k_tomo_transpose(const int32_t* __restric
     if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
 }
 
+// Per column of a transposed product: the quantum's exponent; zero: the column contributes nothing and its result is +0.0
+// (W = 0); skip: the column is not the call's business, nothing of it is read or written
+struct TomoCols {
+    int e[kMultiMax];
+    unsigned long long zero, skip;
+};
+
+// One lane per row of a block, a wave per slice, for the columns c0 .. c0 + C - 1.  A weight that is not finite counts as 0.  The
+// leader election, the kmin reduction and the ballot happen once per step for the chunk; the integers, the wave sums and the adds
+// are the column's own, into the column's accumulators acc + c (kTomoCopies 2 nz).  A lane takes part when its weight is not zero
+// in any column of the chunk; where it is zero its products are integer zeros, which change no sum, and add_split skips them.
+template <int C>
+__global__ void __launch_bounds__(256) k_tomo_transpose(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                                        const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
+                                                        int nrhs, const double* __restrict__ w, size_t ws, TomoCols K,
+                                                        unsigned long long* acc, size_t nz, unsigned long long* natomics) {
+    const int c0 = (int)blockIdx.y * C;
+    const size_t copy = (size_t)(blockIdx.x % kTomoCopies) * 2 * nz;
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool in = r < rows;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t o = in ? off[r >> 6] : 0;
+    double wr[C];
+    int ec[C];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        const int c = c0 + j;
+        const bool use = c < nrhs && !(((K.zero | K.skip) >> (c & 63)) & 1ull);
+        double v = (in && use) ? w[(size_t)c * ws + r] : 0.0;
+        if (!(fabs(v) < INFINITY)) v = 0.0;
+        wr[j] = v;
+        ec[j] = K.e[c & 63];
+        any = any || v != 0.0;
+    }
+    const int n = (in && any) ? len[r] : 0;
+    long long nat = 0;
+    // Neighbouring rays visit much the same cells, but not at the same segment index: a ray that clips a corner has one visit more.
+    // So the lanes do not step through k together.  Each holds its next segment; the lane that is furthest behind names a cell,
+    // every lane whose next segment is that cell joins its add and moves on, the others wait.  Which lanes add together changes no
+    // bit: the sums are integers.  The segment after the next is loaded a step ahead.
+    int k = 0, b = 0, nb = 0;
+    double p[4] = {0.0, 0.0, 0.0, 0.0}, np[4] = {0.0, 0.0, 0.0, 0.0};
+    auto load = [&](int kk) {                                 // segment kk into (nb, np)
+        if (kk < n) {
+            nb = base[rt::tomo_slot(o, kk, lane)];
+#pragma unroll
+            for (int q = 0; q < 4; q++) np[q] = val[rt::tomo_value(o, kk, q, lane)];
+        }
+    };
+    auto take = [&]() {                                       // (nb, np) becomes the lane's next segment
+        b = nb;
+#pragma unroll
+        for (int q = 0; q < 4; q++) p[q] = np[q];
+    };
+    load(0);
+    take();
+    load(1);
+    for (;;) {
+        const bool pend = k < n;
+        if (__ballot(pend) == 0ull) break;
+        int kmin = pend ? k : INT32_MAX;
+        for (int s = 1; s < 64; s <<= 1) kmin = min(kmin, __shfl_xor(kmin, s));
+        const int leader = __ffsll((long long)__ballot(pend && k == kmin)) - 1;
+        const int lb = __shfl(b, leader);
+        const bool mem = pend && b == lb;
+        const bool several = __popcll(__ballot(mem)) > 1;
+#pragma unroll
+        for (int j = 0; j < C; j++) {
+            if (c0 + j >= nrhs) break;
+            long long v[4] = {0, 0, 0, 0};
+            if (mem) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] = (long long)rint(ldexp(__dmul_rn(p[q], wr[j]), -ec[j]));
+            }
+            if (several) {
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) v[q] += __shfl_xor(v[q], s);
+            }
+            if (lane == leader) {
+                unsigned long long* const A = acc + (size_t)(c0 + j) * kTomoCopies * 2 * nz + copy;
+                unsigned long long* const B = A + nz;
+                nat += add_split(A, B, (size_t)lb, v[0]);
+                nat += add_split(A, B, (size_t)lb + 1, v[1]);
+                nat += add_split(A, B, (size_t)lb + qx, v[2]);
+                nat += add_split(A, B, (size_t)lb + qx + 1, v[3]);
+            }
+        }
+        if (mem) {
+            k++;
+            take();
+            load(k + 1);
+        }
+    }
+    for (int s = 1; s < 64; s <<= 1) nat += __shfl_xor(nat, s);
+    if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
+}
+
 // The smoothing rows: ux [qy][qx - 1] = fl(lx fl(x[i][j + 1] - x[i][j])), uy [qy - 1][qx] = fl(ly fl(x[i + 1][j] - x[i][j]))
 __global__ void __launch_bounds__(256) k_tomo_diff(const double* __restrict__ x, int qx, int qy, double lx, double ly, double* __restrict__ ux,
                                                    double* __restrict__ uy) {
@@ -287,23 +405,16 @@ __device__ __forceinline__ double acc_sample(const unsigned long long* __restric
     return ldexp(rt::fix_to_double(lo2, hi), e);
 }
 
-// g = the accumulators, each sample's integer B 2^32 + A rounded once to fp64 (zero: +0.0 instead), plus, with ux, the transposed smoothing rows:
-// g = fl(gA + fl(r + s)), r = fl(lx fl(ux[i][j - 1] - ux[i][j])), s = fl(ly fl(uy[i - 1][j] - uy[i][j])), a missing neighbour +0.0
-__global__ void __launch_bounds__(256) k_tomo_finish(const unsigned long long* __restrict__ acc, int e,
-                                                     bool zero, int qx, int qy, const double* __restrict__ ux, const double* __restrict__ uy,
-                                                     double lx, double ly, double* __restrict__ g) {
+// Per column (blockIdx.y): g + c gs = the column's accumulators, each sample's integer B 2^32 + A rounded once to fp64, +0.0 for a
+// zero column; a skipped column is not written.  A regulariser's transposed rows are added afterwards (k_tomo_reg_t).
+__global__ void __launch_bounds__(256) k_tomo_finish(const unsigned long long* __restrict__ acc, TomoCols K, size_t nz, double* __restrict__ g,
+                                                     size_t gs) {
+    const int c = (int)blockIdx.y;
+    if ((K.skip >> c) & 1ull) return;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)qx * qy) return;
-    double v = 0.0;
-    if (!zero) v = acc_sample(acc, (size_t)qx * qy, i, e);
-    if (ux) {
-        const int iy = (int)(i / qx), jx = (int)(i % qx);
-        const double xa = jx > 0 ? ux[(size_t)iy * (qx - 1) + jx - 1] : 0.0, xb = jx < qx - 1 ? ux[(size_t)iy * (qx - 1) + jx] : 0.0;
-        const double ya = iy > 0 ? uy[i - qx] : 0.0, yb = iy < qy - 1 ? uy[i] : 0.0;
-        const double r = __dmul_rn(lx, __dadd_rn(xa, -xb)), s = __dmul_rn(ly, __dadd_rn(ya, -yb));
-        v = __dadd_rn(v, __dadd_rn(r, s));
-    }
-    g[i] = v;
+    if (i >= (long)nz) return;
+    const bool zero = (K.zero >> c) & 1ull;
+    g[(size_t)c * gs + i] = zero ? 0.0 : acc_sample(acc + (size_t)c * kTomoCopies * 2 * nz, nz, i, K.e[c]);
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
@@ -323,65 +434,129 @@ void fill_stats(const rtmi_tomo* t, rtmi_tomo_stats* st) {
     st->qx = t->F.qx; st->qy = t->F.qy;
 }
 
-// y [rows] = A x on device pointers; the callers have checked them.  ms: the kernels' event time, waited for.
-int apply_dev(rtmi_tomo* t, const char* who, const double* d_x, double* d_y, double* ms) {
-    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
-    for (const TomoBlock& b : t->blocks) {
-        hipLaunchKernelGGL(k_tomo_apply, blocks((long)b.rows), dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows, t->F.qx, d_x,
-                           d_y + b.first);
-        RTMI_HIP(hipGetLastError());
+// f(std::integral_constant<int, C>) for the chunk width of nrhs when that is 8, 4 or 2; false for width 1, which is the caller's
+template <typename F> bool by_chunk(int nrhs, F&& f) {
+    switch (chunk_of(nrhs)) {
+        case 8: f(std::integral_constant<int, 8>()); return true;
+        case 4: f(std::integral_constant<int, 4>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        default: return false;
     }
-    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
-    RTMI_HIP(hipEventSynchronize(t->ev[1]));
-    float f = 0.0f;
-    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-    *ms = f;
+}
+
+int check_nrhs(const char* who, int32_t nrhs) {
+    RTMI_ARG(nrhs >= 1 && nrhs <= kMultiMax, "nrhs must be in 1 .. 64");
     return RTMI_OK;
 }
 
-// g [qy][qx] = A^T w (w [rows]) on device pointers, plus the transposed smoothing rows when ux is given.  *range: fl(Vmax max|w|)
-// is not a normal number, and nothing was written.
-int transpose_dev(rtmi_tomo* t, const char* who, const double* d_w, double* d_g, const double* ux, const double* uy, double lx, double ly,
-                  bool* range, double* ms, int64_t* atomics, int32_t* scale_exp) {
-    *range = false;
-    *ms = 0.0;
-    *atomics = 0;
-    *scale_exp = 0;
-    const size_t nz = t->nz();
-    double W = 0.0;
-    if (t->rows > 0 && t->segments > 0 && t->vmax > 0.0) RTMI_RC(rtmi_internal_absmax_finite(who, t->red, t->cus, d_w, (size_t)t->rows, &W));
-    const bool zero = !(W > 0.0);
-    int e = 0;
-    if (!zero) {
-        const double bound = t->vmax * W;
-        if (!std::isnormal(bound)) {
-            *range = true;
-            return RTMI_OK;
-        }
-        e = rt::fix_exponent(bound);
+// Accumulators for nrhs columns: kept, and replaced by a larger set when a call has more.  A growth that fails leaves the handle
+// without any, and the next call, of whatever width, allocates its own.
+int ensure_cols(rtmi_tomo* t, const char* who, int nrhs) {
+    if (t->acc_cols >= nrhs) return RTMI_OK;
+    if (t->acc) (void)hipFree(t->acc);
+    t->acc = nullptr;
+    t->acc_cols = 0;
+    if (hipMalloc((void**)&t->acc, (size_t)nrhs * kTomoCopies * 2 * t->nz() * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        t->acc = nullptr;
+        return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc of the accumulators of " + std::to_string(nrhs) +
+                                                   " columns failed").c_str());
     }
-    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
-    if (!zero) {
-        RTMI_HIP(hipMemsetAsync(t->acc, 0, (size_t)kTomoCopies * 2 * nz * sizeof(unsigned long long), nullptr));
-        RTMI_HIP(hipMemsetAsync(t->red + 5, 0, sizeof(unsigned long long), nullptr));
+    t->acc_cols = nrhs;
+    return RTMI_OK;
+}
+
+// A product's time: with ms, the kernels' event time between the two marks, waited for; without (the solver, which times its
+// operator calls on the wall clock), no marks and no wait: the caller waits for the stream itself
+hipError_t mark_begin(rtmi_tomo* t, const double* ms) { return ms ? hipEventRecord(t->ev[0], nullptr) : hipSuccess; }
+hipError_t mark_end(rtmi_tomo* t, double* ms) {
+    if (!ms) return hipSuccess;
+    float f = 0.0f;
+    hipError_t e = hipEventRecord(t->ev[1], nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(t->ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, t->ev[0], t->ev[1]);
+    *ms = f;
+    return e;
+}
+
+// y + c ys [rows] = A (x + c xs) for c < nrhs, on device pointers the callers have checked: one launch per append.  ms (or
+// NULL): see mark_end.
+int apply_dev(rtmi_tomo* t, const char* who, int nrhs, const double* d_x, size_t xs, double* d_y, size_t ys, double* ms) {
+    RTMI_HIP(mark_begin(t, ms));
+    const int C = chunk_of(nrhs);
+    for (const TomoBlock& b : t->blocks) {
+        const dim3 grid(blocks((long)b.rows).x, (unsigned)((nrhs + C - 1) / C));
+        auto launch = [&](auto c) {
+            hipLaunchKernelGGL((k_tomo_apply<decltype(c)::value>), grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows,
+                               t->F.qx, nrhs, d_x, xs, d_y + b.first, ys);
+        };
+        if (!by_chunk(nrhs, launch)) launch(std::integral_constant<int, 1>());
+        RTMI_HIP(hipGetLastError());
+    }
+    RTMI_HIP(mark_end(t, ms));
+    return RTMI_OK;
+}
+
+// g + c gs [qy][qx] = A^T (w + c ws) for the columns c of `mask`.  Every column has its own W, bound and exponent, from one
+// reduction launch and one read-back.  range [nrhs]: the column's bound fl(Vmax max|w|) is not a normal number, and nothing of it
+// is written; with `strict` the call then stops before any product.  atomics (or NULL: not read back), exps [nrhs] (or NULL): the
+// columns' exponents, 0 for a zero column.
+int transpose_dev(rtmi_tomo* t, const char* who, int nrhs, const double* d_w, size_t ws, double* d_g, size_t gs, unsigned long long mask,
+                  bool strict, bool* range, double* ms, int64_t* atomics, int32_t* exps) {
+    if (ms) *ms = 0.0;
+    if (atomics) *atomics = 0;
+    const size_t nz = t->nz();
+    RTMI_RC(ensure_cols(t, who, nrhs));
+    double W[kMultiMax] = {};
+    if (t->rows > 0 && t->segments > 0 && t->vmax > 0.0)
+        RTMI_RC(absmax(who, Vec{t->red, t->cus, nrhs}, d_w, ws, (size_t)t->rows, mask, W));
+    TomoCols K{};
+    K.skip = ~mask;
+    bool work = false, refused = false;
+    for (int c = 0; c < nrhs; c++) {
+        range[c] = false;
+        if (exps) exps[c] = 0;
+        if (!(mask & col_bit(c))) continue;
+        if (!(W[c] > 0.0)) {
+            K.zero |= col_bit(c);
+            continue;
+        }
+        const double bound = t->vmax * W[c];
+        if (!std::isnormal(bound)) {
+            range[c] = true;
+            refused = true;
+            K.skip |= col_bit(c);
+            continue;
+        }
+        K.e[c] = rt::fix_exponent(bound);
+        if (exps) exps[c] = K.e[c];
+        work = true;
+    }
+    if (strict && refused) return RTMI_OK;
+    RTMI_HIP(mark_begin(t, ms));
+    if (work) {
+        RTMI_HIP(hipMemsetAsync(t->acc, 0, (size_t)nrhs * kTomoCopies * 2 * nz * sizeof(unsigned long long), nullptr));
+        RTMI_HIP(hipMemsetAsync(t->red_atomics(), 0, sizeof(unsigned long long), nullptr));
+        const int C = chunk_of(nrhs);
         for (const TomoBlock& b : t->blocks) {
-            hipLaunchKernelGGL(k_tomo_transpose, blocks((long)b.rows), dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows, t->F.qx,
-                               d_w + b.first, e, t->acc, nz, t->red + 5);
+            const dim3 grid(blocks((long)b.rows).x, (unsigned)((nrhs + C - 1) / C));
+            const bool wider = by_chunk(nrhs, [&](auto c) {
+                hipLaunchKernelGGL((k_tomo_transpose<decltype(c)::value>), grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows,
+                                   t->F.qx, nrhs, d_w + b.first, ws, K, t->acc, nz, t->red_atomics());
+            });
+            if (!wider)                                       // one column, and it has work: neither zero nor skipped
+                hipLaunchKernelGGL(k_tomo_transpose1, grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows, t->F.qx,
+                                   d_w + b.first, K.e[0], t->acc, nz, t->red_atomics());
             RTMI_HIP(hipGetLastError());
         }
     }
-    hipLaunchKernelGGL(k_tomo_finish, blocks((long)nz), dim3(256), 0, nullptr, t->acc, e, zero, t->F.qx, t->F.qy, ux, uy, lx, ly, d_g);
+    hipLaunchKernelGGL(k_tomo_finish, dim3(blocks((long)nz).x, (unsigned)nrhs), dim3(256), 0, nullptr, t->acc, K, nz, d_g, gs);
     RTMI_HIP(hipGetLastError());
-    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
-    RTMI_HIP(hipEventSynchronize(t->ev[1]));
-    float f = 0.0f;
-    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-    *ms = f;
-    if (!zero) {
+    RTMI_HIP(mark_end(t, ms));
+    if (work && atomics) {
         unsigned long long n = 0;
-        RTMI_HIP(hipMemcpy(&n, t->red + 5, sizeof(n), hipMemcpyDeviceToHost));
+        RTMI_HIP(hipMemcpy(&n, t->red_atomics(), sizeof(n), hipMemcpyDeviceToHost));
         *atomics = (int64_t)n;
-        *scale_exp = e;
     }
     return RTMI_OK;
 }
@@ -415,7 +590,8 @@ RTMI_EXPORT int rtmi_tomo_create(const rtmi_field* f, rtmi_tomo** out) {
     if (e != hipSuccess || t->cus < 1) return fail(RTMI_ERR_HIP, "hipDeviceGetAttribute", e);
     e = hipMalloc((void**)&t->acc, (size_t)kTomoCopies * 2 * t->nz() * sizeof(unsigned long long));
     if (e != hipSuccess) return fail(RTMI_ERR_ALLOC, "hipMalloc", e);
-    e = hipMalloc((void**)&t->red, kRedWords * sizeof(unsigned long long));
+    t->acc_cols = 1;
+    e = hipMalloc((void**)&t->red, kTomoRed * sizeof(unsigned long long));
     if (e != hipSuccess) return fail(RTMI_ERR_ALLOC, "hipMalloc", e);
     for (hipEvent_t& v : t->ev) {
         e = hipEventCreate(&v);
@@ -502,10 +678,10 @@ RTMI_EXPORT int rtmi_tomo_append(rtmi_tomo* t, rtmi_batch* b, const double line[
     RTMI_HIP(hipMemcpy(blk.off, off.data(), (size_t)(ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     RTMI_HIP(hipMemsetAsync(blk.base, 0, (size_t)blk.padded * sizeof(int32_t), nullptr));
     RTMI_HIP(hipMemsetAsync(blk.val, 0, (size_t)blk.padded * 4 * sizeof(double), nullptr));
-    RTMI_HIP(hipMemsetAsync(t->red + 4, 0, sizeof(unsigned long long), nullptr));
+    RTMI_HIP(hipMemsetAsync(t->red_vmax(), 0, sizeof(unsigned long long), nullptr));
     by_dtype(v.dtype, [&](auto q) {
         hipLaunchKernelGGL((k_tomo_walk<decltype(q), true>), gr, bs, 0, nullptr, rows_of<decltype(q)>(v), A, d_which, d_rowof, blk.len, blk.off,
-                           blk.base, blk.val, t->red + 4);
+                           blk.base, blk.val, t->red_vmax());
     });
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
@@ -513,7 +689,7 @@ RTMI_EXPORT int rtmi_tomo_append(rtmi_tomo* t, rtmi_batch* b, const double line[
     float ms = 0.0f;
     RTMI_HIP(hipEventElapsedTime(&ms, t->ev[0], t->ev[1]));
     double vmax = 0.0;
-    RTMI_HIP(hipMemcpy(&vmax, t->red + 4, sizeof(double), hipMemcpyDeviceToHost));
+    RTMI_HIP(hipMemcpy(&vmax, t->red_vmax(), sizeof(double), hipMemcpyDeviceToHost));
     if (nseg)
         for (size_t m = 0; m < R; m++) nseg[m] = rowof[m] < 0 ? -1 : len[(size_t)rowof[m]];
     t->blocks.push_back(blk);
@@ -580,7 +756,7 @@ RTMI_EXPORT int rtmi_tomo_apply_dev(rtmi_tomo* t, const double* d_x, double* d_y
     RTMI_RC(check_device_pointer(t->device, who, d_x, t->nz() * sizeof(double), "d_x"));
     if (t->rows) RTMI_RC(check_device_pointer(t->device, who, d_y, (size_t)t->rows * sizeof(double), "d_y"));
     double ms = 0.0;
-    RTMI_RC(apply_dev(t, who, d_x, d_y, &ms));
+    RTMI_RC(apply_dev(t, who, 1, d_x, 0, d_y, 0, &ms));
     if (st) {
         fill_stats(t, st);
         st->kernel_ms = ms;
@@ -601,7 +777,7 @@ RTMI_EXPORT int rtmi_tomo_apply(rtmi_tomo* t, const double* x, double* y, rtmi_t
     RTMI_HIP(mem.get(&dy, (size_t)t->rows * sizeof(double)));
     RTMI_HIP(hipMemcpy(dx, x, t->nz() * sizeof(double), hipMemcpyHostToDevice));
     double ms = 0.0;
-    RTMI_RC(apply_dev(t, who, dx, dy, &ms));
+    RTMI_RC(apply_dev(t, who, 1, dx, 0, dy, 0, &ms));
     if (t->rows) RTMI_HIP(hipMemcpy(y, dy, (size_t)t->rows * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         fill_stats(t, st);
@@ -622,7 +798,7 @@ RTMI_EXPORT int rtmi_tomo_transpose_dev(rtmi_tomo* t, const double* d_w, double*
     double ms = 0.0;
     int64_t atomics = 0;
     int32_t e = 0;
-    RTMI_RC(transpose_dev(t, who, d_w, d_g, nullptr, nullptr, 0.0, 0.0, &range, &ms, &atomics, &e));
+    RTMI_RC(transpose_dev(t, who, 1, d_w, 0, d_g, 0, 1ull, true, &range, &ms, &atomics, &e));
     RTMI_ARG(!range, "Vmax max|w| is not a normal number (RTMI_LSQR_RANGE)");
     if (st) {
         fill_stats(t, st);
@@ -647,7 +823,7 @@ RTMI_EXPORT int rtmi_tomo_transpose(rtmi_tomo* t, const double* w, double* g, rt
     double ms = 0.0;
     int64_t atomics = 0;
     int32_t e = 0;
-    RTMI_RC(transpose_dev(t, who, dw, dg, nullptr, nullptr, 0.0, 0.0, &range, &ms, &atomics, &e));
+    RTMI_RC(transpose_dev(t, who, 1, dw, 0, dg, 0, 1ull, true, &range, &ms, &atomics, &e));
     RTMI_ARG(!range, "Vmax max|w| is not a normal number (RTMI_LSQR_RANGE)");
     RTMI_HIP(hipMemcpy(g, dg, t->nz() * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
@@ -655,85 +831,6 @@ RTMI_EXPORT int rtmi_tomo_transpose(rtmi_tomo* t, const double* w, double* g, rt
         st->kernel_ms = ms; st->atomics = atomics; st->scale_exp = e;
     }
     return RTMI_OK;
-}
-
-namespace {
-
-// Both solvers' body.  lo: the options of rtmi_tomo_lsqr_weighted, uploaded once; NULL, or every pointer of it NULL, allocates
-// nothing and runs the loop as it ran before there were options.
-int tomo_lsqr_run(const char* who, rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
-                  const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
-    RTMI_ARG(t, "null handle");
-    RTMI_ARG(lp, "null params");
-    RTMI_ARG(rhs, "null rhs");
-    RTMI_ARG(x, "null x");
-    RTMI_RC(lsqr_check_params(who, lp));
-    if (smooth)
-        RTMI_ARG(std::isfinite(smooth[0]) && smooth[0] >= 0.0 && std::isfinite(smooth[1]) && smooth[1] >= 0.0,
-                 "smooth must be finite and >= 0");
-    RTMI_ARG(t->rows >= 1, "the handle has no rows");
-    RTMI_RC(finite_all(who, rhs, (size_t)t->rows, "rhs has a value that is not finite"));
-    RTMI_RC(lsqr_check_options(who, lo, (size_t)t->rows, t->nz()));
-    RTMI_RC(on_device(t, who));
-    const double t_begin = now_ms();
-    const size_t rows = (size_t)t->rows, nm = t->nz(), qx = (size_t)t->F.qx, qy = (size_t)t->F.qy;
-    const size_t ndx = qy * (qx - 1), ndy = (qy - 1) * qx;
-    const size_t per = rows + (smooth ? ndx + ndy : 0);
-    const double lx = smooth ? smooth[0] : 0.0, ly = smooth ? smooth[1] : 0.0;
-    DevMem mem;
-    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr;
-    for (double** p : {&u, &Av})
-        if (mem.get(p, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc failed").c_str());
-    for (double** p : {&v, &w, &xd, &Atu})
-        if (mem.get(p, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc failed").c_str());
-    // the row weights cover the `rows` observations; the smoothing rows carry none
-    LsqrOptions O;
-    size_t nopt = 0;
-    RTMI_RC(lsqr_upload_options(who, mem, lo, rows, per, nm, &O, &nopt));
-    const Vec V{t->red, t->cus};
-    rtmi_lsqr_stats out{};
-    out.bytes_device = (int64_t)((2 * per + 4 * nm + nopt) * sizeof(double) + t->bytes());
-    double operator_ms = 0.0;
-    // the stacked operator: t = [A s | Dx s | Dy s], and its transpose
-    auto Ax = [&](const double* s, double* y) {
-        double ms = 0.0;
-        RTMI_RC(apply_dev(t, who, s, y, &ms));
-        operator_ms += ms;
-        if (smooth) {
-            hipLaunchKernelGGL(k_tomo_diff, blocks((long)nm), dim3(256), 0, nullptr, s, (int)qx, (int)qy, lx, ly, y + rows, y + rows + ndx);
-            RTMI_HIP(hipGetLastError());
-        }
-        return (int)RTMI_OK;
-    };
-    auto At = [&](const double* s, double* g, bool* range) {
-        double ms = 0.0;
-        int64_t atomics = 0;
-        int32_t e = 0;
-        RTMI_RC(transpose_dev(t, who, s, g, smooth ? s + rows : nullptr, smooth ? s + rows + ndx : nullptr, lx, ly, range, &ms, &atomics, &e));
-        operator_ms += ms;
-        return (int)RTMI_OK;
-    };
-    RTMI_HIP(hipMemcpy(u, rhs, rows * sizeof(double), hipMemcpyHostToDevice));        // the right-hand side goes up once
-    if (per > rows) RTMI_HIP(hipMemsetAsync(u + rows, 0, (per - rows) * sizeof(double), nullptr));
-    RTMI_HIP(hipMemsetAsync(xd, 0, nm * sizeof(double), nullptr));
-    RTMI_RC(lsqr_loop(who, V, lp, per, nm, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, &out, O));
-    RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));           // the model comes down once
-    out.total_ms = now_ms() - t_begin;
-    out.operator_ms = operator_ms;
-    if (st) *st = out;
-    return RTMI_OK;
-}
-
-}  // namespace
-
-RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const double smooth[2], const double* rhs, double* x,
-                               double* history, rtmi_lsqr_stats* st) {
-    return tomo_lsqr_run("rtmi_tomo_lsqr", t, lp, nullptr, smooth, rhs, x, history, st);
-}
-
-RTMI_EXPORT int rtmi_tomo_lsqr_weighted(rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
-                                        const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
-    return tomo_lsqr_run("rtmi_tomo_lsqr_weighted", t, lp, lo, smooth, rhs, x, history, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------ model basis
@@ -1000,446 +1097,13 @@ RTMI_EXPORT int rtmi_tomo_basis_restrict_dev(rtmi_tomo_basis* p, const double* d
     return RTMI_OK;
 }
 
-namespace {
-
-// The solver over the coefficient grid G ([my][mx] with a basis, [qy][qx] without), with first- and second-difference rows on G.
-// The loop sees the options row_weight and col_scale; the start model is a fine one, so its residual is taken here, before the
-// loop, and it is added here, after P: the same two roundings the loop gives them.
-int tomo_lsqr_basis_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
-                        const double* d1, const double* d2, const double* rhs, double* c, double* x, double* history, rtmi_lsqr_stats* st) {
-    const size_t rows = (size_t)t->rows, nm = t->nz();
-    const size_t gx = p ? (size_t)p->mx : (size_t)t->F.qx, gy = p ? (size_t)p->my : (size_t)t->F.qy, ng = gx * gy;
-    const size_t n1x = d1 ? gy * (gx - 1) : 0, n1y = d1 ? (gy - 1) * gx : 0;
-    const size_t n2x = d2 && gx > 2 ? gy * (gx - 2) : 0, n2y = d2 && gy > 2 ? (gy - 2) * gx : 0;
-    const size_t per = rows + n1x + n1y + n2x + n2y;
-    const double t_begin = now_ms();
-    const std::string no_mem = std::string(who) + ": hipMalloc failed";
-    DevMem mem;
-    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *yd = nullptr, *Atu = nullptr, *xf = nullptr, *gf = nullptr, *x0 = nullptr;
-    for (double** q : {&u, &Av})
-        if (mem.get(q, per * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-    for (double** q : {&v, &w, &yd, &Atu})
-        if (mem.get(q, ng * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-    size_t fine = 0;                                                                  // the call's vectors on the fine grid
-    if (p) {
-        for (double** q : {&xf, &gf})
-            if (mem.get(q, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-        fine += 2;
-    }
-    if (lo && lo->x0) {
-        if (mem.get(&x0, nm * sizeof(double)) != hipSuccess) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-        RTMI_HIP(hipMemcpy(x0, lo->x0, nm * sizeof(double), hipMemcpyHostToDevice));
-        fine += 1;
-    }
-    rtmi_lsqr_options inner{};
-    if (lo) { inner.row_weight = lo->row_weight; inner.col_scale = lo->col_scale; }
-    LsqrOptions O;
-    size_t nopt = 0;
-    RTMI_RC(lsqr_upload_options(who, mem, &inner, rows, per, ng, &O, &nopt));
-    const Vec V{t->red, t->cus};
-    EventMarks<2> ev;
-    RTMI_HIP(ev.create());
-    rtmi_lsqr_stats out{};
-    out.bytes_device = (int64_t)((2 * per + 4 * ng + fine * nm + nopt) * sizeof(double) + t->bytes() + (p ? p->bytes() : 0));
-    double operator_ms = 0.0;
-    // the stacked operator [A P | Dx | Dy | Dxx | Dyy] on s [G], and its transpose
-    auto Ax = [&](const double* s, double* y) {
-        double ms = 0.0, pms = 0.0;
-        if (p) {
-            RTMI_HIP(ev.mark(0));
-            RTMI_RC(basis_prolong_dev(p, who, s, xf));
-            RTMI_HIP(ev.mark(1));
-        }
-        RTMI_RC(apply_dev(t, who, p ? xf : s, y, &ms));
-        if (p) RTMI_HIP(ev.ms(0, 1, &pms));
-        operator_ms += ms + pms;
-        if (d1) {
-            hipLaunchKernelGGL(k_tomo_diff, blocks((long)ng), dim3(256), 0, nullptr, s, (int)gx, (int)gy, d1[0], d1[1], y + rows, y + rows + n1x);
-            RTMI_HIP(hipGetLastError());
-        }
-        if (d2) {
-            hipLaunchKernelGGL(k_tomo_diff2, blocks((long)ng), dim3(256), 0, nullptr, s, (int)gx, (int)gy, d2[0], d2[1], y + rows + n1x + n1y,
-                               y + rows + n1x + n1y + n2x);
-            RTMI_HIP(hipGetLastError());
-        }
-        return (int)RTMI_OK;
-    };
-    auto At = [&](const double* s, double* g, bool* range) {
-        double ms = 0.0, pms = 0.0;
-        int64_t atomics = 0;
-        int32_t e = 0;
-        RTMI_RC(transpose_dev(t, who, s, p ? gf : g, nullptr, nullptr, 0.0, 0.0, range, &ms, &atomics, &e));
-        if (*range) return (int)RTMI_OK;
-        RTMI_HIP(ev.mark(0));
-        if (p) RTMI_RC(basis_restrict_dev(p, who, gf, g));
-        if (d1 || d2) {
-            hipLaunchKernelGGL(k_tomo_reg_t, blocks((long)ng), dim3(256), 0, nullptr, g, (int)gx, (int)gy, d1 ? s + rows : nullptr,
-                               d1 ? s + rows + n1x : nullptr, d1 ? d1[0] : 0.0, d1 ? d1[1] : 0.0, d2 ? s + rows + n1x + n1y : nullptr,
-                               d2 ? s + rows + n1x + n1y + n2x : nullptr, d2 ? d2[0] : 0.0, d2 ? d2[1] : 0.0);
-            RTMI_HIP(hipGetLastError());
-        }
-        RTMI_HIP(ev.mark(1));
-        RTMI_HIP(ev.wait(1));
-        RTMI_HIP(ev.ms(0, 1, &pms));
-        operator_ms += ms + pms;
-        return (int)RTMI_OK;
-    };
-    RTMI_HIP(hipMemcpy(u, rhs, rows * sizeof(double), hipMemcpyHostToDevice));
-    if (per > rows) RTMI_HIP(hipMemsetAsync(u + rows, 0, (per - rows) * sizeof(double), nullptr));
-    RTMI_HIP(hipMemsetAsync(yd, 0, ng * sizeof(double), nullptr));
-    if (x0) {                                                                         // u = fl(rhs - A x0) over the data rows
-        double ms = 0.0;
-        RTMI_RC(apply_dev(t, who, x0, Av, &ms));
-        operator_ms += ms;
-        hipLaunchKernelGGL(k_sub_mul, stride_blocks(V.cus, rows, 1), dim3(256), 0, nullptr, u, Av, (const double*)nullptr, (long)rows);
-        RTMI_HIP(hipGetLastError());
-    }
-    RTMI_RC(lsqr_loop(who, V, lp, per, ng, LsqrVectors{u, Av, v, w, yd, Atu}, Ax, At, history, &out, O));   // yd = fl(dc y): c
-    if (c) RTMI_HIP(hipMemcpy(c, yd, ng * sizeof(double), hipMemcpyDeviceToHost));
-    double* xd = yd;
-    if (p) {
-        RTMI_RC(basis_prolong_dev(p, who, yd, xf));
-        xd = xf;
-    }
-    if (x0) {
-        hipLaunchKernelGGL(k_result, stride_blocks(V.cus, nm, 1), dim3(256), 0, nullptr, xd, (const double*)nullptr, x0, (long)nm);
-        RTMI_HIP(hipGetLastError());
-    }
-    RTMI_HIP(hipMemcpy(x, xd, nm * sizeof(double), hipMemcpyDeviceToHost));
-    out.total_ms = now_ms() - t_begin;
-    out.operator_ms = operator_ms;
-    if (st) *st = out;
-    return RTMI_OK;
-}
-
-}  // namespace
-
-RTMI_EXPORT int rtmi_tomo_lsqr_basis(rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
-                                     const rtmi_tomo_reg* reg, const double* rhs, double* c, double* x, double* history,
-                                     rtmi_lsqr_stats* st) {
-    const char* who = "rtmi_tomo_lsqr_basis";
-    RTMI_ARG(t, "null handle");
-    const double *d1 = nullptr, *d2 = nullptr;
-    if (reg) {
-        for (const double v : {reg->d1[0], reg->d1[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d1 must be finite and >= 0");
-        for (const double v : {reg->d2[0], reg->d2[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d2 must be finite and >= 0");
-        if (reg->d1[0] != 0.0 || reg->d1[1] != 0.0) d1 = reg->d1;
-        if (reg->d2[0] != 0.0 || reg->d2[1] != 0.0) d2 = reg->d2;
-    }
-    if (p)
-        RTMI_ARG(p->qx == t->F.qx && p->qy == t->F.qy && p->device == t->device, "the basis was made for another shape or device than the handle's");
-    const bool start = lo && lo->x0;
-    // without a basis and without second differences this is rtmi_tomo_lsqr_weighted, launch for launch (c is x without a start model)
-    if (!p && !d2 && !(c && start)) {
-        RTMI_RC(tomo_lsqr_run(who, t, lp, lo, d1, rhs, x, history, st));
-        if (c) std::memcpy(c, x, t->nz() * sizeof(double));
-        return RTMI_OK;
-    }
-    RTMI_ARG(lp, "null params");
-    RTMI_ARG(rhs, "null rhs");
-    RTMI_ARG(x, "null x");
-    RTMI_RC(lsqr_check_params(who, lp));
-    RTMI_ARG(t->rows >= 1, "the handle has no rows");
-    RTMI_RC(finite_all(who, rhs, (size_t)t->rows, "rhs has a value that is not finite"));
-    if (lo) {
-        rtmi_lsqr_options coarse = *lo, fine = *lo;                               // col_scale has |G| values, x0 qy qx
-        coarse.x0 = nullptr;
-        fine.row_weight = nullptr; fine.col_scale = nullptr;
-        RTMI_RC(lsqr_check_options(who, &coarse, (size_t)t->rows, p ? p->ng() : t->nz()));
-        RTMI_RC(lsqr_check_options(who, &fine, 0, t->nz()));
-    }
-    RTMI_RC(on_device(t, who));
-    return tomo_lsqr_basis_run(who, t, p, lp, lo, d1, d2, rhs, c, x, history, st);
-}
-
 // ------------------------------------------------------------------------------------------------------------ many vectors at once
-// S <= kMultiMax vectors through one read of the matrix (rtmi_tomo_apply_multi, _transpose_multi, rtmi_tomo_lsqr_multi; DESIGN.md
-// section 28).  The vectors are planes: column c of x is x + c xs.  A kernel is compiled for chunks of C = 8, 4, 2 and 1
-// columns; a launch takes the widest that nrhs fills, with the chunk in blockIdx.y, so that a product is one launch per append
-// whatever nrhs is.  The last chunk may be partial: its missing columns are not written.
+// The products' entries for nrhs planes (rtmi_tomo_apply_multi, _transpose_multi)
 namespace {
-
-// the chunk width of a call: the widest compiled one that nrhs fills
-int chunk_of(int nrhs) { return nrhs >= 8 ? 8 : nrhs >= 4 ? 4 : nrhs >= 2 ? 2 : 1; }
-
-// k_tomo_apply for the columns c0 .. c0 + C - 1: a segment's base and p are loaded once, the gathers and the five roundings are
-// the column's own.  A column past nrhs reads the last one's x and is not written.
-template <int C>
-__global__ void __launch_bounds__(256) k_tomo_apply_multi(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
-                                                          const int32_t* __restrict__ base, const double* __restrict__ val, long rows, int qx,
-                                                          int nrhs, const double* __restrict__ x, size_t xs, double* __restrict__ y, size_t ys) {
-    const long r = (long)blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const int c0 = (int)blockIdx.y * C;
-    const int lane = (int)(r & 63);
-    const int64_t o = off[r >> 6];
-    const int n = len[r];
-    const double* xc[C];
-    double acc[C];
-#pragma unroll
-    for (int j = 0; j < C; j++) {
-        xc[j] = x + (size_t)min(c0 + j, nrhs - 1) * xs;
-        acc[j] = 0.0;
-    }
-    for (int k = 0; k < n; k++) {
-        const int b = base[rt::tomo_slot(o, k, lane)];
-        const double p0 = val[rt::tomo_value(o, k, 0, lane)], p1 = val[rt::tomo_value(o, k, 1, lane)];
-        const double p2 = val[rt::tomo_value(o, k, 2, lane)], p3 = val[rt::tomo_value(o, k, 3, lane)];
-#pragma unroll
-        for (int j = 0; j < C; j++) {
-            const double* z = xc[j] + b;
-            const double t = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p0, z[0]), __dmul_rn(p1, z[1])), __dmul_rn(p2, z[qx])), __dmul_rn(p3, z[qx + 1]));
-            acc[j] = __dadd_rn(acc[j], t);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < C; j++)
-        if (c0 + j < nrhs) y[(size_t)(c0 + j) * ys + r] = acc[j];
-}
-
-// Per column of a transposed product: the quantum's exponent; zero: the column contributes nothing and its result is +0.0
-// (W = 0); skip: the column is not the call's business, nothing of it is read or written
-struct TomoCols {
-    int e[kMultiMax];
-    unsigned long long zero, skip;
-};
-
-// k_tomo_transpose for the columns c0 .. c0 + C - 1.  The lanes step through the cells as there: the leader election, the kmin
-// reduction and the ballot happen once per step for the chunk; the integers, the wave sums and the adds are the column's own,
-// into the column's accumulators accm + c (kTomoCopies 2 nz).  A lane takes part when its weight is not zero in any column of the
-// chunk; where it is zero its products are integer zeros, which change no sum, and add_split skips them.
-template <int C>
-__global__ void __launch_bounds__(256) k_tomo_transpose_multi(const int32_t* __restrict__ len, const int64_t* __restrict__ off,
-                                                              const int32_t* __restrict__ base, const double* __restrict__ val, long rows,
-                                                              int qx, int nrhs, const double* __restrict__ w, size_t ws, TomoCols K,
-                                                              unsigned long long* accm, size_t nz, unsigned long long* natomics) {
-    const int c0 = (int)blockIdx.y * C;
-    const size_t copy = (size_t)(blockIdx.x % kTomoCopies) * 2 * nz;
-    const long r = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool in = r < rows;
-    const int lane = (int)(threadIdx.x & 63);
-    const int64_t o = in ? off[r >> 6] : 0;
-    double wr[C];
-    int ec[C];
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < C; j++) {
-        const int c = c0 + j;
-        const bool use = c < nrhs && !(((K.zero | K.skip) >> (c & 63)) & 1ull);
-        double v = (in && use) ? w[(size_t)c * ws + r] : 0.0;
-        if (!(fabs(v) < INFINITY)) v = 0.0;                   // a weight that is not finite counts as 0
-        wr[j] = v;
-        ec[j] = K.e[c & 63];
-        any = any || v != 0.0;
-    }
-    const int n = (in && any) ? len[r] : 0;
-    long long nat = 0;
-    int k = 0, b = 0, nb = 0;
-    double p[4] = {0.0, 0.0, 0.0, 0.0}, np[4] = {0.0, 0.0, 0.0, 0.0};
-    auto load = [&](int kk) {                                 // segment kk into (nb, np)
-        if (kk < n) {
-            nb = base[rt::tomo_slot(o, kk, lane)];
-#pragma unroll
-            for (int q = 0; q < 4; q++) np[q] = val[rt::tomo_value(o, kk, q, lane)];
-        }
-    };
-    auto take = [&]() {                                       // (nb, np) becomes the lane's next segment
-        b = nb;
-#pragma unroll
-        for (int q = 0; q < 4; q++) p[q] = np[q];
-    };
-    load(0);
-    take();
-    load(1);
-    for (;;) {
-        const bool pend = k < n;
-        if (__ballot(pend) == 0ull) break;
-        int kmin = pend ? k : INT32_MAX;
-        for (int s = 1; s < 64; s <<= 1) kmin = min(kmin, __shfl_xor(kmin, s));
-        const int leader = __ffsll((long long)__ballot(pend && k == kmin)) - 1;
-        const int lb = __shfl(b, leader);
-        const bool mem = pend && b == lb;
-        const bool several = __popcll(__ballot(mem)) > 1;
-#pragma unroll
-        for (int j = 0; j < C; j++) {
-            if (c0 + j >= nrhs) break;
-            long long v[4] = {0, 0, 0, 0};
-            if (mem) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) v[q] = (long long)rint(ldexp(__dmul_rn(p[q], wr[j]), -ec[j]));
-            }
-            if (several) {
-#pragma unroll
-                for (int s = 1; s < 64; s <<= 1)
-#pragma unroll
-                    for (int q = 0; q < 4; q++) v[q] += __shfl_xor(v[q], s);
-            }
-            if (lane == leader) {
-                unsigned long long* const A = accm + (size_t)(c0 + j) * kTomoCopies * 2 * nz + copy;
-                unsigned long long* const B = A + nz;
-                nat += add_split(A, B, (size_t)lb, v[0]);
-                nat += add_split(A, B, (size_t)lb + 1, v[1]);
-                nat += add_split(A, B, (size_t)lb + qx, v[2]);
-                nat += add_split(A, B, (size_t)lb + qx + 1, v[3]);
-            }
-        }
-        if (mem) {
-            k++;
-            take();
-            load(k + 1);
-        }
-    }
-    for (int s = 1; s < 64; s <<= 1) nat += __shfl_xor(nat, s);
-    if (lane == 0 && nat) atomicAdd(natomics, (unsigned long long)nat);
-}
-
-// k_tomo_finish per column (blockIdx.y), without smoothing rows: g + c gs = the column's accumulators rounded once, +0.0 for a
-// zero column; a skipped column is not written
-__global__ void __launch_bounds__(256) k_tomo_finish_multi(const unsigned long long* __restrict__ accm, TomoCols K, size_t nz,
-                                                           double* __restrict__ g, size_t gs) {
-    const int c = (int)blockIdx.y;
-    if ((K.skip >> c) & 1ull) return;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)nz) return;
-    const bool zero = (K.zero >> c) & 1ull;
-    g[(size_t)c * gs + i] = zero ? 0.0 : acc_sample(accm + (size_t)c * kTomoCopies * 2 * nz, nz, i, K.e[c]);
-}
-
-// f(std::integral_constant<int, C>) for the chunk width of nrhs
-template <typename F> void by_chunk(int nrhs, F&& f) {
-    switch (chunk_of(nrhs)) {
-        case 8: f(std::integral_constant<int, 8>()); break;
-        case 4: f(std::integral_constant<int, 4>()); break;
-        case 2: f(std::integral_constant<int, 2>()); break;
-        default: f(std::integral_constant<int, 1>()); break;
-    }
-}
-
-int check_nrhs(const char* who, int32_t nrhs) {
-    RTMI_ARG(nrhs >= 1 && nrhs <= kMultiMax, "nrhs must be in 1 .. 64");
-    return RTMI_OK;
-}
-
-unsigned long long all_cols(int nrhs) { return nrhs == 64 ? ~0ull : (col_bit(nrhs) - 1ull); }
-
-// The multi calls' device memory, on their first use: accumulators for nrhs columns (kept, and grown when a call has more), and
-// the reduction words
-int ensure_multi(rtmi_tomo* t, const char* who, int nrhs) {
-    if (!t->redm && hipMalloc((void**)&t->redm, (size_t)kMultiMax * kRedM * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        t->redm = nullptr;
-        return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc failed").c_str());
-    }
-    if (t->acc_cols < nrhs) {
-        if (t->accm) (void)hipFree(t->accm);
-        t->accm = nullptr;
-        t->acc_cols = 0;
-        if (hipMalloc((void**)&t->accm, (size_t)nrhs * kTomoCopies * 2 * t->nz() * sizeof(unsigned long long)) != hipSuccess) {
-            (void)hipGetLastError();
-            t->accm = nullptr;
-            return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc of the accumulators of " + std::to_string(nrhs) +
-                                                       " columns failed").c_str());
-        }
-        t->acc_cols = nrhs;
-    }
-    return RTMI_OK;
-}
-
-// y + c ys [rows] = A (x + c xs) for c < nrhs, on device pointers the callers have checked: one launch per append
-int apply_multi_dev(rtmi_tomo* t, const char* who, int nrhs, const double* d_x, size_t xs, double* d_y, size_t ys, double* ms) {
-    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
-    const int C = chunk_of(nrhs);
-    for (const TomoBlock& b : t->blocks) {
-        const dim3 grid(blocks((long)b.rows).x, (unsigned)((nrhs + C - 1) / C));
-        by_chunk(nrhs, [&](auto c) {
-            hipLaunchKernelGGL((k_tomo_apply_multi<decltype(c)::value>), grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val, (long)b.rows,
-                               t->F.qx, nrhs, d_x, xs, d_y + b.first, ys);
-        });
-        RTMI_HIP(hipGetLastError());
-    }
-    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
-    RTMI_HIP(hipEventSynchronize(t->ev[1]));
-    float f = 0.0f;
-    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-    *ms = f;
-    return RTMI_OK;
-}
-
-// g + c gs [qy][qx] = A^T (w + c ws) for the columns c of `mask`.  Every column has its own W, bound and exponent, from one
-// reduction launch and one read-back.  range [nrhs]: the column's bound is not a normal number, and nothing of it is written;
-// with `strict` the call then stops before any product.  exps [nrhs] (or NULL): the columns' exponents, 0 for a zero column.
-int transpose_multi_dev(rtmi_tomo* t, const char* who, int nrhs, const double* d_w, size_t ws, double* d_g, size_t gs,
-                        unsigned long long mask, bool strict, bool* range, double* ms, int64_t* atomics, int32_t* exps) {
-    *ms = 0.0;
-    if (atomics) *atomics = 0;
-    const size_t nz = t->nz();
-    RTMI_RC(ensure_multi(t, who, nrhs));
-    unsigned long long h[kMultiMax * kRedM] = {};
-    if (t->rows > 0 && t->segments > 0 && t->vmax > 0.0) {
-        const size_t bytes = (size_t)nrhs * kRedM * sizeof(unsigned long long);
-        RTMI_HIP(hipMemsetAsync(t->redm, 0, bytes, nullptr));
-        hipLaunchKernelGGL(k_absmax_finite_m, dim3(stride_blocks(t->cus, (size_t)t->rows, 1).x, (unsigned)nrhs), dim3(256), 0, nullptr, d_w, ws,
-                           (long)t->rows, mask, t->redm);
-        RTMI_HIP(hipGetLastError());
-        RTMI_HIP(hipMemcpy(h, t->redm, bytes, hipMemcpyDeviceToHost));
-    }
-    TomoCols K{};
-    K.skip = ~mask;
-    bool work = false, refused = false;
-    for (int c = 0; c < nrhs; c++) {
-        range[c] = false;
-        if (exps) exps[c] = 0;
-        if (!(mask & col_bit(c))) continue;
-        double W = 0.0;
-        std::memcpy(&W, &h[(size_t)c * kRedM], sizeof(double));
-        if (!(W > 0.0)) {
-            K.zero |= col_bit(c);
-            continue;
-        }
-        const double bound = t->vmax * W;
-        if (!std::isnormal(bound)) {
-            range[c] = true;
-            refused = true;
-            K.skip |= col_bit(c);
-            continue;
-        }
-        K.e[c] = rt::fix_exponent(bound);
-        if (exps) exps[c] = K.e[c];
-        work = true;
-    }
-    if (strict && refused) return RTMI_OK;
-    RTMI_HIP(hipEventRecord(t->ev[0], nullptr));
-    if (work) {
-        RTMI_HIP(hipMemsetAsync(t->accm, 0, (size_t)nrhs * kTomoCopies * 2 * nz * sizeof(unsigned long long), nullptr));
-        RTMI_HIP(hipMemsetAsync(t->red + 5, 0, sizeof(unsigned long long), nullptr));
-        const int C = chunk_of(nrhs);
-        for (const TomoBlock& b : t->blocks) {
-            const dim3 grid(blocks((long)b.rows).x, (unsigned)((nrhs + C - 1) / C));
-            by_chunk(nrhs, [&](auto c) {
-                hipLaunchKernelGGL((k_tomo_transpose_multi<decltype(c)::value>), grid, dim3(256), 0, nullptr, b.len, b.off, b.base, b.val,
-                                   (long)b.rows, t->F.qx, nrhs, d_w + b.first, ws, K, t->accm, nz, t->red + 5);
-            });
-            RTMI_HIP(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL(k_tomo_finish_multi, dim3(blocks((long)nz).x, (unsigned)nrhs), dim3(256), 0, nullptr, t->accm, K, nz, d_g, gs);
-    RTMI_HIP(hipGetLastError());
-    RTMI_HIP(hipEventRecord(t->ev[1], nullptr));
-    RTMI_HIP(hipEventSynchronize(t->ev[1]));
-    float f = 0.0f;
-    RTMI_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[1]));
-    *ms = f;
-    if (work && atomics) {
-        unsigned long long n = 0;
-        RTMI_HIP(hipMemcpy(&n, t->red + 5, sizeof(n), hipMemcpyDeviceToHost));
-        *atomics = (int64_t)n;
-    }
-    return RTMI_OK;
-}
 
 // the public transposed calls' end: a refusal that names the first column out of range, else the stats
-int transpose_multi_done(const rtmi_tomo* t, const char* who, int nrhs, const bool* range, const int32_t* exps, double ms, int64_t atomics,
-                         rtmi_tomo_stats* st) {
+int transpose_done(const rtmi_tomo* t, const char* who, int nrhs, const bool* range, const int32_t* exps, double ms, int64_t atomics,
+                   rtmi_tomo_stats* st) {
     for (int c = 0; c < nrhs; c++)
         RTMI_ARG(!range[c], "column " + std::to_string(c) + ": Vmax max|w| is not a normal number (RTMI_LSQR_RANGE)");
     if (st) {
@@ -1466,7 +1130,7 @@ RTMI_EXPORT int rtmi_tomo_apply_multi_dev(rtmi_tomo* t, int32_t nrhs, const doub
     RTMI_RC(check_device_pointer(t->device, who, d_x, (size_t)nrhs * t->nz() * sizeof(double), "d_x"));
     if (t->rows) RTMI_RC(check_device_pointer(t->device, who, d_y, (size_t)nrhs * (size_t)t->rows * sizeof(double), "d_y"));
     double ms = 0.0;
-    RTMI_RC(apply_multi_dev(t, who, nrhs, d_x, t->nz(), d_y, (size_t)t->rows, &ms));
+    RTMI_RC(apply_dev(t, who, nrhs, d_x, t->nz(), d_y, (size_t)t->rows, &ms));
     if (st) {
         fill_stats(t, st);
         st->kernel_ms = ms;
@@ -1489,7 +1153,7 @@ RTMI_EXPORT int rtmi_tomo_apply_multi(rtmi_tomo* t, int32_t nrhs, const double* 
     RTMI_HIP(mem.get(&dy, ny * sizeof(double)));
     RTMI_HIP(hipMemcpy(dx, x, nx * sizeof(double), hipMemcpyHostToDevice));
     double ms = 0.0;
-    RTMI_RC(apply_multi_dev(t, who, nrhs, dx, t->nz(), dy, (size_t)t->rows, &ms));
+    RTMI_RC(apply_dev(t, who, nrhs, dx, t->nz(), dy, (size_t)t->rows, &ms));
     if (ny) RTMI_HIP(hipMemcpy(y, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         fill_stats(t, st);
@@ -1511,8 +1175,8 @@ RTMI_EXPORT int rtmi_tomo_transpose_multi_dev(rtmi_tomo* t, int32_t nrhs, const 
     int32_t exps[kMultiMax];
     double ms = 0.0;
     int64_t atomics = 0;
-    RTMI_RC(transpose_multi_dev(t, who, nrhs, d_w, (size_t)t->rows, d_g, t->nz(), all_cols(nrhs), true, range, &ms, &atomics, exps));
-    return transpose_multi_done(t, who, nrhs, range, exps, ms, atomics, st);
+    RTMI_RC(transpose_dev(t, who, nrhs, d_w, (size_t)t->rows, d_g, t->nz(), all_cols(nrhs), true, range, &ms, &atomics, exps));
+    return transpose_done(t, who, nrhs, range, exps, ms, atomics, st);
 }
 
 RTMI_EXPORT int rtmi_tomo_transpose_multi(rtmi_tomo* t, int32_t nrhs, const double* w, double* g, rtmi_tomo_stats* st) {
@@ -1533,20 +1197,33 @@ RTMI_EXPORT int rtmi_tomo_transpose_multi(rtmi_tomo* t, int32_t nrhs, const doub
     int32_t exps[kMultiMax];
     double ms = 0.0;
     int64_t atomics = 0;
-    RTMI_RC(transpose_multi_dev(t, who, nrhs, dw, (size_t)t->rows, dg, t->nz(), all_cols(nrhs), true, range, &ms, &atomics, exps));
-    RTMI_RC(transpose_multi_done(t, who, nrhs, range, exps, ms, atomics, nullptr));
+    RTMI_RC(transpose_dev(t, who, nrhs, dw, (size_t)t->rows, dg, t->nz(), all_cols(nrhs), true, range, &ms, &atomics, exps));
+    RTMI_RC(transpose_done(t, who, nrhs, range, exps, ms, atomics, nullptr));
     RTMI_HIP(hipMemcpy(g, dg, ng * sizeof(double), hipMemcpyDeviceToHost));
-    return transpose_multi_done(t, who, nrhs, range, exps, ms, atomics, st);
+    return transpose_done(t, who, nrhs, range, exps, ms, atomics, st);
 }
 
 namespace {
 
-// tomo_lsqr_basis_run for nrhs columns: the same stacked operator on planes, the loop of rt_lsqr_multi.h.  The products and the
-// vector passes are one launch for all columns; the basis and regulariser kernels, which work on model-sized vectors, are
-// launched per live column.  wr_cols: the row weights are [nrhs][rows], else [rows] for all.
-int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
-                        const double* d1, const double* d2, int S, bool wr_cols, const double* rhs, double* c, double* x, double* history,
-                        rtmi_lsqr_stats* st) {
+// ------------------------------------------------------------------------------------------------------------ solver
+// reg's weights, checked; *d1, *d2: the pair, or NULL when both of its weights are zero (the pair has no rows then)
+int check_reg(const char* who, const rtmi_tomo_reg* reg, const double** d1, const double** d2) {
+    *d1 = *d2 = nullptr;
+    if (!reg) return RTMI_OK;
+    for (const double v : {reg->d1[0], reg->d1[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d1 must be finite and >= 0");
+    for (const double v : {reg->d2[0], reg->d2[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d2 must be finite and >= 0");
+    if (reg->d1[0] != 0.0 || reg->d1[1] != 0.0) *d1 = reg->d1;
+    if (reg->d2[0] != 0.0 || reg->d2[1] != 0.0) *d2 = reg->d2;
+    return RTMI_OK;
+}
+
+// Every solver's body, for S columns: the loop of rt_lsqr_device.h over the coefficient grid G ([my][mx] with a basis, [qy][qx]
+// without), with first- (d1) and second-difference (d2) rows on G, on planes.  The products and the vector passes are one launch
+// for all columns; the basis and regulariser kernels, which work on model-sized vectors, are launched per live column.  The loop
+// sees the options row_weight ([S][rows] with wr_cols, else [rows] for all) and col_scale; the start model is a fine one, so its
+// residual is taken here, before the loop, and it is added here, after P.  The callers have checked the arguments.
+int tomo_lsqr_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double* d1,
+                  const double* d2, int S, bool wr_cols, const double* rhs, double* c, double* x, double* history, rtmi_lsqr_stats* st) {
     const size_t rows = (size_t)t->rows, nm = t->nz();
     const size_t gx = p ? (size_t)p->mx : (size_t)t->F.qx, gy = p ? (size_t)p->my : (size_t)t->F.qy, ng = gx * gy;
     const size_t n1x = d1 ? gy * (gx - 1) : 0, n1y = d1 ? (gy - 1) * gx : 0;
@@ -1554,15 +1231,14 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
     const size_t per = rows + n1x + n1y + n2x + n2y;
     const double t_begin = now_ms();
     const std::string no_mem = std::string(who) + ": hipMalloc failed";
-    RTMI_RC(ensure_multi(t, who, S));
+    RTMI_RC(ensure_cols(t, who, S));
     DevMem mem;
     size_t doubles = 0;
     auto get = [&](double** q, size_t n) {
         doubles += n;
         return mem.get(q, n * sizeof(double)) == hipSuccess;
     };
-    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *yd = nullptr, *Atu = nullptr, *xf = nullptr, *gf = nullptr, *x0 = nullptr,
-           *ax0 = nullptr;
+    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *yd = nullptr, *Atu = nullptr, *xf = nullptr, *gf = nullptr, *x0 = nullptr;
     for (double** q : {&u, &Av})
         if (!get(q, S * per)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
     for (double** q : {&v, &w, &yd, &Atu})
@@ -1570,31 +1246,16 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
     if (p)
         for (double** q : {&xf, &gf})
             if (!get(q, S * nm)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-    LsqrOptions O;
-    O.nrhs = rows;
-    size_t wrs = 0;
     if (lo && lo->x0) {
-        if (!get(&x0, nm) || !get(&ax0, rows)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        if (!get(&x0, nm)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
         RTMI_HIP(hipMemcpy(x0, lo->x0, nm * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (lo && lo->row_weight) {
-        // rows `rows` .. per - 1, a regulariser's, carry no weight: their factor is 1.0
-        const size_t nw = wr_cols ? (size_t)S : 1;
-        std::vector<double> h(nw * per, 1.0);
-        for (size_t s = 0; s < nw; s++) std::memcpy(h.data() + s * per, lo->row_weight + s * rows, rows * sizeof(double));
-        double* d = nullptr;
-        if (!get(&d, nw * per) || !get(&O.uw, S * per)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-        RTMI_HIP(hipMemcpy(d, h.data(), nw * per * sizeof(double), hipMemcpyHostToDevice));
-        O.wr = d;
-        wrs = wr_cols ? per : 0;
-    }
-    if (lo && lo->col_scale) {
-        double* d = nullptr;
-        if (!get(&d, ng) || !get(&O.vd, S * ng)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
-        RTMI_HIP(hipMemcpy(d, lo->col_scale, ng * sizeof(double), hipMemcpyHostToDevice));
-        O.dc = d;
-    }
-    const VecM V{t->redm, t->cus, S};
+    // the row weights cover the `rows` observations; a regulariser's rows carry none
+    LsqrOptions O;
+    size_t nopt = 0;
+    RTMI_RC(lsqr_upload_options(who, mem, lo, S, wr_cols, rows, per, ng, &O, &nopt));
+    doubles += nopt;
+    const Vec V{t->red, t->cus, S};
     const unsigned long long all = all_cols(S);
     double operator_ms = 0.0;
     auto each = [&](unsigned long long mask, auto&& f) {
@@ -1605,10 +1266,10 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
     // the stacked operator [A P | Dx | Dy | Dxx | Dyy] on the planes s [S][G], and its transpose
     auto Ax = [&](const double* s, double* y, unsigned long long mask) {
         const double t0 = now_ms();
-        double ms = 0.0;
         if (p) RTMI_RC(each(mask, [&](size_t k) { return basis_prolong_dev(p, who, s + k * ng, xf + k * nm); }));
-        RTMI_RC(apply_multi_dev(t, who, S, p ? xf : s, nm, y, per, &ms));
-        operator_ms += now_ms() - t0;
+        RTMI_RC(apply_dev(t, who, S, p ? xf : s, nm, y, per, nullptr));
+        RTMI_HIP(hipStreamSynchronize(nullptr));
+        operator_ms += now_ms() - t0;                         // the regulariser's forward rows are outside it
         if (d1 || d2)
             RTMI_RC(each(mask, [&](size_t k) {
                 const double* sk = s + k * ng;
@@ -1624,8 +1285,7 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
     };
     auto At = [&](const double* s, double* g, unsigned long long mask, bool* range) {
         const double t0 = now_ms();
-        double ms = 0.0;
-        RTMI_RC(transpose_multi_dev(t, who, S, s, per, p ? gf : g, p ? nm : ng, mask, false, range, &ms, nullptr, nullptr));
+        RTMI_RC(transpose_dev(t, who, S, s, per, p ? gf : g, p ? nm : ng, mask, false, range, nullptr, nullptr, nullptr));
         unsigned long long ok = 0ull;
         for (int k = 0; k < S; k++)
             if ((mask & col_bit(k)) && !range[k]) ok |= col_bit(k);
@@ -1642,8 +1302,8 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
                 }
                 return (int)RTMI_OK;
             }));
-            RTMI_HIP(hipStreamSynchronize(nullptr));
         }
+        RTMI_HIP(hipStreamSynchronize(nullptr));
         operator_ms += now_ms() - t0;
         return (int)RTMI_OK;
     };
@@ -1653,20 +1313,21 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
     RTMI_HIP(hipStreamSynchronize(nullptr));
     RTMI_HIP(hipMemcpy2D(u, per * sizeof(double), rhs, rows * sizeof(double), rows * sizeof(double), (size_t)S, hipMemcpyHostToDevice));
     if (x0) {                                                                         // u = fl(rhs - A x0) over the data rows; A x0 once
-        double ms = 0.0;
-        RTMI_RC(apply_dev(t, who, x0, ax0, &ms));
-        operator_ms += ms;
-        RTMI_RC(sub_mul_m(who, V, u, per, ax0, 0, nullptr, 0, rows, all));
+        const double t0 = now_ms();
+        RTMI_RC(apply_dev(t, who, 1, x0, 0, Av, 0, nullptr));
+        RTMI_RC(lsqr_sub_start(who, V, u, per, Av, rows));
+        RTMI_HIP(hipStreamSynchronize(nullptr));
+        operator_ms += now_ms() - t0;
     }
     std::vector<rtmi_lsqr_stats> out((size_t)S);
-    RTMI_RC(lsqr_loop_multi(who, V, lp, per, ng, LsqrVectors{u, Av, v, w, yd, Atu}, Ax, At, history, out.data(), O, wrs));   // yd = fl(dc y): c
+    RTMI_RC(lsqr_loop(who, V, lp, per, ng, LsqrVectors{u, Av, v, w, yd, Atu}, Ax, At, history, out.data(), O));   // yd = fl(dc y): c
     if (c) RTMI_HIP(hipMemcpy(c, yd, (size_t)S * ng * sizeof(double), hipMemcpyDeviceToHost));
     double* xd = yd;
     if (p) {
         RTMI_RC(each(all, [&](size_t k) { return basis_prolong_dev(p, who, yd + k * ng, xf + k * nm); }));
         xd = xf;
     }
-    if (x0) RTMI_RC(result_m(who, V, xd, nm, nullptr, x0, nm, all));
+    if (x0) RTMI_RC(lsqr_add_start(who, V, xd, nm, x0, nm));
     RTMI_HIP(hipMemcpy(x, xd, (size_t)S * nm * sizeof(double), hipMemcpyDeviceToHost));
     const double total = now_ms() - t_begin;
     const int64_t bytes = (int64_t)(doubles * sizeof(double) + t->bytes() + (p ? p->bytes() : 0));
@@ -1679,7 +1340,67 @@ int tomo_lsqr_multi_run(const char* who, rtmi_tomo* t, rtmi_tomo_basis* p, const
     return RTMI_OK;
 }
 
+// rtmi_tomo_lsqr and _weighted: their checks, then the body with one column, no basis and the first differences of `smooth`
+int tomo_lsqr_single(const char* who, rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
+                     const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
+    RTMI_ARG(t, "null handle");
+    RTMI_ARG(lp, "null params");
+    RTMI_ARG(rhs, "null rhs");
+    RTMI_ARG(x, "null x");
+    RTMI_RC(lsqr_check_params(who, lp));
+    if (smooth)
+        RTMI_ARG(std::isfinite(smooth[0]) && smooth[0] >= 0.0 && std::isfinite(smooth[1]) && smooth[1] >= 0.0,
+                 "smooth must be finite and >= 0");
+    RTMI_ARG(t->rows >= 1, "the handle has no rows");
+    RTMI_RC(finite_all(who, rhs, (size_t)t->rows, "rhs has a value that is not finite"));
+    RTMI_RC(lsqr_check_options(who, lo, (size_t)t->rows, t->nz()));
+    RTMI_RC(on_device(t, who));
+    return tomo_lsqr_run(who, t, nullptr, lp, lo, smooth, nullptr, 1, false, rhs, nullptr, x, history, st);
+}
+
+// rtmi_tomo_lsqr_basis and _multi, after their own arguments: the basis, the parameters, the nrhs right-hand sides and the options
+int check_solve(const char* who, const rtmi_tomo* t, const rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                size_t nrhs, size_t nwr, const double* rhs, const double* x) {
+    if (p)
+        RTMI_ARG(p->qx == t->F.qx && p->qy == t->F.qy && p->device == t->device, "the basis was made for another shape or device than the handle's");
+    RTMI_ARG(lp, "null params");
+    RTMI_ARG(rhs, "null rhs");
+    RTMI_ARG(x, "null x");
+    RTMI_RC(lsqr_check_params(who, lp));
+    RTMI_ARG(t->rows >= 1, "the handle has no rows");
+    RTMI_RC(finite_all(who, rhs, nrhs * (size_t)t->rows, "rhs has a value that is not finite"));
+    if (lo) {
+        rtmi_lsqr_options coarse = *lo, fine = *lo;                               // col_scale has |G| values, x0 qy qx
+        coarse.x0 = nullptr;
+        fine.row_weight = nullptr; fine.col_scale = nullptr;
+        RTMI_RC(lsqr_check_options(who, &coarse, nwr, p ? p->ng() : t->nz()));
+        RTMI_RC(lsqr_check_options(who, &fine, 0, t->nz()));
+    }
+    return on_device(t, who);
+}
+
 }  // namespace
+
+RTMI_EXPORT int rtmi_tomo_lsqr(rtmi_tomo* t, const rtmi_lsqr_params* lp, const double smooth[2], const double* rhs, double* x,
+                               double* history, rtmi_lsqr_stats* st) {
+    return tomo_lsqr_single("rtmi_tomo_lsqr", t, lp, nullptr, smooth, rhs, x, history, st);
+}
+
+RTMI_EXPORT int rtmi_tomo_lsqr_weighted(rtmi_tomo* t, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo, const double smooth[2],
+                                        const double* rhs, double* x, double* history, rtmi_lsqr_stats* st) {
+    return tomo_lsqr_single("rtmi_tomo_lsqr_weighted", t, lp, lo, smooth, rhs, x, history, st);
+}
+
+RTMI_EXPORT int rtmi_tomo_lsqr_basis(rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                                     const rtmi_tomo_reg* reg, const double* rhs, double* c, double* x, double* history,
+                                     rtmi_lsqr_stats* st) {
+    const char* who = "rtmi_tomo_lsqr_basis";
+    RTMI_ARG(t, "null handle");
+    const double *d1 = nullptr, *d2 = nullptr;
+    RTMI_RC(check_reg(who, reg, &d1, &d2));
+    RTMI_RC(check_solve(who, t, p, lp, lo, 1, (size_t)t->rows, rhs, x));
+    return tomo_lsqr_run(who, t, p, lp, lo, d1, d2, 1, false, rhs, c, x, history, st);
+}
 
 RTMI_EXPORT int rtmi_tomo_lsqr_multi(rtmi_tomo* t, rtmi_tomo_basis* p, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
                                      const rtmi_tomo_reg* reg, int32_t nrhs, int32_t flags, const double* rhs, double* c, double* x,
@@ -1689,30 +1410,9 @@ RTMI_EXPORT int rtmi_tomo_lsqr_multi(rtmi_tomo* t, rtmi_tomo_basis* p, const rtm
     RTMI_RC(check_nrhs(who, nrhs));
     RTMI_ARG((flags & ~RTMI_LSQR_MULTI_ROW_WEIGHT) == 0, "flags has bits other than RTMI_LSQR_MULTI_ROW_WEIGHT");
     const double *d1 = nullptr, *d2 = nullptr;
-    if (reg) {
-        for (const double v : {reg->d1[0], reg->d1[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d1 must be finite and >= 0");
-        for (const double v : {reg->d2[0], reg->d2[1]}) RTMI_ARG(std::isfinite(v) && v >= 0.0, "reg.d2 must be finite and >= 0");
-        if (reg->d1[0] != 0.0 || reg->d1[1] != 0.0) d1 = reg->d1;
-        if (reg->d2[0] != 0.0 || reg->d2[1] != 0.0) d2 = reg->d2;
-    }
-    if (p)
-        RTMI_ARG(p->qx == t->F.qx && p->qy == t->F.qy && p->device == t->device, "the basis was made for another shape or device than the handle's");
-    RTMI_ARG(lp, "null params");
-    RTMI_ARG(rhs, "null rhs");
-    RTMI_ARG(x, "null x");
-    RTMI_RC(lsqr_check_params(who, lp));
-    RTMI_ARG(t->rows >= 1, "the handle has no rows");
-    const size_t rows = (size_t)t->rows;
+    RTMI_RC(check_reg(who, reg, &d1, &d2));
     const bool wr_cols = (flags & RTMI_LSQR_MULTI_ROW_WEIGHT) != 0;
-    RTMI_RC(finite_all(who, rhs, (size_t)nrhs * rows, "rhs has a value that is not finite"));
-    if (lo) {
-        rtmi_lsqr_options coarse = *lo, fine = *lo;                               // col_scale has |G| values, x0 qy qx
-        coarse.x0 = nullptr;
-        fine.row_weight = nullptr; fine.col_scale = nullptr;
-        RTMI_RC(lsqr_check_options(who, &coarse, (wr_cols ? (size_t)nrhs : 1) * rows, p ? p->ng() : t->nz()));
-        RTMI_RC(lsqr_check_options(who, &fine, 0, t->nz()));
-    }
-    RTMI_RC(on_device(t, who));
+    RTMI_RC(check_solve(who, t, p, lp, lo, (size_t)nrhs, (wr_cols ? (size_t)nrhs : 1) * (size_t)t->rows, rhs, x));
     if (history) std::memset(history, 0, (size_t)nrhs * (size_t)lp->iter_lim * 4 * sizeof(double));
-    return tomo_lsqr_multi_run(who, t, p, lp, lo, d1, d2, (int)nrhs, wr_cols, rhs, c, x, history, st);
+    return tomo_lsqr_run(who, t, p, lp, lo, d1, d2, (int)nrhs, wr_cols, rhs, c, x, history, st);
 }

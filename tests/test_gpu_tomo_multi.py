@@ -4,12 +4,15 @@ bytes must be equal.  Products: every compiled chunk width (1, 2, 4, 8), a parti
 of the row storage, over three appends, with skipped rays, empty rows and permuted rays; columns whose exponents differ by
 hundreds, a zero column, weights that are not finite; the refusal of a column out of range; repetition; the device-pointer
 forms.  Solver: with and without a basis, every regulariser, shared and per-column options; columns that stop at different
-iterations in one call; history past itn; a swap of two columns; recover, bootstrap and the grouping of lsqr_multi; refusals."""
+iterations in one call; history past itn; a swap of two columns; recover, bootstrap and the grouping of lsqr_multi; refusals.
+The single entries are the batched code with one column, so section 3 holds the columns of one call to
+the host restatement directly, and checks planes of odd and even length and vectors 8 bytes off a 16-byte boundary."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import tomo_basis_ref as BR
 from conftest import LIMITS
 
 pytestmark = pytest.mark.gpu
@@ -409,7 +412,109 @@ def test_grouping_changes_no_byte(rb, coarse):
         same(a[s], T.lsqr(rhs[s], damp=1e-3, iter_lim=3, history=True, row_weight=wr[s]), keys=("x",))
 
 
-# ---------------------------------------------------------------- 3. refusals
+# ---------------------------------------------------------------- 3. one code for every width
+# The single solver is the batched one with one column, so "every column equals the single solver" compares two widths of one
+# code.  What holds a column to independent arithmetic is the host restatement, and what could differ between the widths is the
+# 16-byte form of the vector passes, which a launch of S > 1 columns takes only when every plane stride is even.
+def cubic(rb, T, mx, my):
+    """the cubic B-spline basis on the device and its restatement"""
+    (fx, wx), (fy, wy) = BR.bspline_axis(T.qx, mx, 3), BR.bspline_axis(T.qy, my, 3)
+    return rb.TomoBasis(T, fx, wx, fy, wy, mx, my), BR.Basis(fx, wx, fy, wy, mx, my)
+
+
+@pytest.fixture(scope="module")
+def matrix(coarse):
+    """what the restatement needs of `coarse`, read once"""
+    return coarse.read() + (coarse.info()["vmax"],)
+
+
+@pytest.mark.parametrize("kind", ["shared", "percol"])
+@pytest.mark.parametrize("reg", ["smooth", "smooth2"])
+@pytest.mark.parametrize("with_basis", [False, True], ids=["fine", "basis"])
+def test_solver_columns_equal_the_host_restatement_bit_for_bit(rb, coarse, matrix, with_basis, reg, kind):
+    T = coarse
+    rp, base, val, vmax = matrix
+    S = 3
+    P, R = cubic(rb, T, 9, 7) if with_basis else (None, None)
+    gy, gx = (7, 9) if with_basis else (T.qy, T.qx)
+    d1, d2 = REG[reg]
+    rhs = np.random.default_rng(71).standard_normal((S, T.info()["rows"]))
+    o = options(T, gy, gx, S, kind, seed=72)
+    outs = T.lsqr_multi(rhs, damp=1e-3, smooth=d1, smooth2=d2, basis=P, iter_lim=6, history=True, **o)
+    if P is not None:
+        P.close()
+    for s in range(S):
+        k = column(o, s)
+        ref = BR.lsqr(rp, base, val, T.qx, T.qy, rhs[s], 6, basis=R, d1=d1, d2=d2, wr=k["row_weight"], dc=k["col_scale"], x0=k["x0"],
+                      vmax=vmax, damp=1e-3)
+        assert ref["itn"] == 6 and ref["x"].any()
+        same(outs[s], ref, ("x", "c") if with_basis else ("x",))
+
+
+@pytest.fixture(scope="module")
+def skipped(rb, field):
+    """`coarse` less one ray: 64 rows"""
+    which = np.full(65, -1, dtype=np.int32)
+    which[17] = rb._lib.TOMO_SKIP
+    b = fan(rb, field, 65)
+    T = rb.Tomography(field)
+    T.append(b, which=which, line=LINE, kmax=4)
+    b.close()
+    yield T
+    T.close()
+
+
+def test_planes_of_odd_and_even_length(rb, coarse, skipped):
+    """The planes of a call with S > 1 columns start `per` (data) and `ng` (model) values apart: an odd one puts every second
+    plane 8 bytes off a 16-byte boundary.  65 or 64 rows with first differences on a 9 x 7 or an 8 x 7 coefficient grid give all
+    four parities of (per, ng); every pass of the loop has a diagonal to read or a copy to write."""
+    seen = set()
+    for T in (coarse, skipped):
+        rows = T.info()["rows"]
+        for mx in (9, 8):
+            P, _ = cubic(rb, T, mx, 7)
+            ng, per = mx * 7, rows + 7 * (mx - 1) + 6 * mx
+            seen.add((per % 2, ng % 2))
+            for S in (2, 3):
+                rhs = np.random.default_rng(81 + S).standard_normal((S, rows))
+                o = options(T, 7, mx, S, "percol", seed=82)
+                kw = dict(damp=1e-3, smooth=D1, basis=P, iter_lim=5, history=True)
+                outs = T.lsqr_multi(rhs, **kw, **o)
+                for s in range(S):
+                    ref = T.lsqr(rhs[s], **kw, **column(o, s))
+                    assert ref["itn"] == 5 and ref["x"].any()
+                    same(outs[s], ref)
+            P.close()
+    assert seen == {(0, 0), (0, 1), (1, 0), (1, 1)}
+
+
+def test_device_pointer_forms_take_a_view_that_is_8_bytes_off(rb, coarse, torch):
+    """one vector that starts 8 bytes past a 16-byte boundary is neither refused nor read 16 bytes wide: the bytes are those of
+    the host call, and the value before the view and the one after it are not touched"""
+    T = coarse
+    nz, rows = T.qy * T.qx, T.info()["rows"]
+    rng = np.random.default_rng(91)
+    x, w = rng.standard_normal(nz), rng.standard_normal(rows)
+
+    def off8(n, fill=None):
+        buf = torch.full((n + 3,), 7.0, dtype=torch.float64, device="cuda")
+        v = buf[1:n + 1] if buf.data_ptr() % 16 == 0 else buf[2:n + 2]
+        assert v.data_ptr() % 16 == 8 and v.is_contiguous()
+        if fill is not None:
+            v.copy_(torch.tensor(fill, device="cuda"))
+        return buf, v
+    (_, dx), (_, dw) = off8(nz, x), off8(rows, w)
+    (by, dy), (bg, dg) = off8(rows), off8(nz)
+    assert bits(T.matvec_device(dx, out=dy).cpu().numpy()) == bits(T.matvec(x))
+    assert bits(T.rmatvec_device(dw, out=dg).cpu().numpy()) == bits(T.rmatvec(w))
+    for buf, n in ((by, rows), (bg, nz)):
+        assert int((buf == 7.0).sum()) >= 3 and float(buf[0]) == 7.0 and float(buf[-1]) == 7.0
+    # one column of the batched form goes the same way
+    assert bits(T.matmat_device(dx.reshape(1, T.qy, T.qx)).cpu().numpy()) == bits(T.matvec(x))
+    assert bits(T.rmatmat_device(dw.reshape(1, rows)).cpu().numpy()) == bits(T.rmatvec(w))
+
+
+# ---------------------------------------------------------------- 4. refusals
 def test_refusals(rb, coarse):
     from raytracing_amd import _lib
     T = coarse

@@ -14,8 +14,8 @@ section 27) beside the solver over the field's samples, same handle and right-ha
 warm-up of each; per-iteration operator_ms and vector_ms of both as median, min and max, the difference of the operator medians
 beside the spread, and the wall time of one prolong and one restrict call on device memory.
 
---multi S: the multi-vector entries against the single-vector ones, which are the yardstick, in one
-process, warmed and alternating, --reps times, medians with min and max: (a) the crosswell case of the tests (8 sources, 32
+--multi S: the multi-vector entries against the single-vector ones, which are the same code with one
+column and the yardstick, in one process, warmed and alternating, --reps times, medians with min and max: (a) the crosswell case of the tests (8 sources, 32
 receivers, about 253 rows): one lsqr_multi of 16 columns against 16 calls of lsqr, wall time; (b) the fan, ends only: matmat and
 rmatmat of S columns against S matvec and rmatvec calls (kernel event time, summed over the calls), and the solver's per-iteration
 operator + vector time at S columns against S single solves.  The batched path is accepted where its series lies below the
