@@ -1121,6 +1121,8 @@ int rtmi_tomo_lsqr_multi(rtmi_tomo *t, rtmi_tomo_basis *p, const rtmi_lsqr_param
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null lp, T, out, handle, t or res; nx, ny, P or
  * E < 1; nx ny > 2^31; P > RTMI_LOCATE_MAX_TABLES; gdx, gdy not finite and > 0, gx0, gy0 not finite; need[e] < 0 (rtmi_locate;
  * rtmi_locate_dev reads a negative need as 0); more than 2^31 (tile, event chunk) pairs; the handle used on another device.
+ * The covariance above is a local Gaussian statement; rtmi_locate_pdf (below) reports the pdf of the whole map: expectation,
+ * covariance, confidence regions, marginals and samples.
  * Not covered: later arrivals, L1 objectives, fp32 tables, several GPUs. */
 #define RTMI_LOCATE_MAX_TABLES 512
 typedef struct rtmi_locator rtmi_locator;
@@ -1173,7 +1175,7 @@ int rtmi_locate_dev(rtmi_locator *loc, int64_t E, const double *d_t, const doubl
  * d_r - tau there; both NaN at stations that do not contribute.  maps [E][ny][nx] (or NULL) receives value at every node.
  * The refinement is rtmi_locate's quadratic (rt_locate.h, host arithmetic) on the negated win_val with win_tau, ref and sw = 1:
  * x, y, dx, dy, t0_refined, refined as there.  No covariance is reported: -value is no misfit with a known scale; a caller who
- * wants a pdf builds it from maps.
+ * wants a pdf, its covariance or its confidence regions calls rtmi_locate_edt_pdf (below).
  * stats: rtmi_locate_stats with triples = E nx ny P (P - 1) / 2 and contributing the contributing pairs; reserved[0] is the
  * search kernel's own part of kernel_ms in nanoseconds, reserved[1] the number of groups of event chunks the call was walked in
  * (with weights g and h are staged per (chunk of 16 events, pair), at most 256 MiB at a time; a positive ep->reserved[0] sets
@@ -1182,7 +1184,8 @@ int rtmi_locate_dev(rtmi_locator *loc, int64_t E, const double *d_t, const doubl
  * rtmi_locate_edt is upload, that, download: the same bits.  Events are independent: any split of E over calls gives the same bits.
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: what rtmi_locate refuses; a null ep; a sigma
  * that is not as stated above; a negative ep->reserved[0].
- * Not covered: L1 objectives, later arrivals, S - P pairs, a pdf or confidence ellipse from the map, fp32 tables, several GPUs. */
+ * The pdf of the map, its covariance and confidence regions: rtmi_locate_edt_pdf (below).
+ * Not covered: L1 objectives, later arrivals, S - P pairs, fp32 tables, several GPUs. */
 typedef struct { double sigma; int64_t reserved[4]; } rtmi_edt_params;
 typedef struct {
     int64_t node, ix, iy, n, npairs;
@@ -1198,6 +1201,73 @@ int rtmi_locate_edt_dev(rtmi_locator *loc, const rtmi_edt_params *ep, int64_t E,
                         const int32_t *d_need, rtmi_edt_result *res, double *d_share, double *d_resid, double *d_maps,
                         rtmi_locate_stats *st);
 int rtmi_edt_exp(const double *z, double *out, int64_t n);   /* host only, no device: out[i] = exp(z[i]), -700 <= z[i] <= 0 */
+
+/* The location pdf of a search on a locator's tables: expectation, covariance, confidence regions, marginals and samples, all
+ * from the map of rtmi_locate (rtmi_locate_pdf) or of rtmi_locate_edt (rtmi_locate_edt_pdf) while it is on the device.  DESIGN.md
+ * section 33.  The quadratic of rtmi_locate is a local Gaussian statement, NaN where the fit is refused and blind to a second
+ * lobe, a trade-off along a ray or a pdf cut off by the grid's rim; these entries sum over the whole map.  The arguments of the
+ * search are the search's own; res (or NULL) receives exactly what the plain search returns for them, bit for bit.  The entry
+ * walks the events in groups whose maps, with the group's histograms and sums, take at most 256 MiB of an internal buffer (at least
+ * one event): the search on the group with its maps into that buffer, then the kernels of this unit on it.  No map leaves the
+ * device, and no limit of the search on the events of one call applies to E here.
+ * (raytracing_amd/csrc/rt_pdf.h holds the arithmetic, tests/pdf_ref.py restates it.)  * marks the best node of the search,
+ * di = ix - ix*, dj = iy - iy*; every product, sum, quotient and square root of doubles is one rounded fp64 operation.
+ *   density  least squares: s2 = sigma * sigma; c = 0.5 / s2; b = sw* * c; at a node a = obj - obj*; z = -(a * b);
+ *                rho = z >= -700.0 ? exp(z) : +0.0, exp as in rtmi_locate_edt; a node whose obj is +inf or NaN has rho = 0.  With
+ *                weights in 1 / s^2 the caller passes sigma = 1; without weights sigma is the picks' standard deviation.
+ *            EDT: r = value / value*; rho = r^p by square and multiply from the most significant bit of p (acc = r; for every
+ *                lower bit, high to low: acc = acc * acc, and acc = acc * r where the bit is set); p = power, and power = 0 means
+ *                the best node's n, the number of readings.  A node that is no candidate has rho = 0; value* = 0 (every pair
+ *                cut): the event has no pdf.  pp->sigma is not read.
+ *   mass     m = (uint64)trunc(rho * 2^30): exact, m* = 2^30.  Every statistic below is an exact sum of integers, the same bits
+ *            in every order: Z = sum m; Sx = sum m di; Sy = sum m dj; Sxx = sum m di di; Sxy = sum m di dj; Syy = sum m dj dj (two
+ *            words each); rim = sum m over the nodes with ix in {0, nx - 1} or iy in {0, ny - 1}; nz = the number of nodes with
+ *            m > 0; a histogram of 992 bins with a node count and a mass each: for m >= 1, bin = 32 b + sub, b the index of the
+ *            leading one of m (0 .. 30), sub the five bits below it (shifted up where b < 5), monotone in m.
+ *   results  per event, host arithmetic from the sums; D(v) is the nearest double of the integer v, Zd = D(Z):
+ *            ax = D(Sx) / Zd; ay = D(Sy) / Zd; mean_x = (gx0 + ix* gdx) + ax gdx; mean_y alike
+ *            cov = {xx, xy, yy} = {(D(Sxx) / Zd - ax ax) (gdx gdx), (D(Sxy) / Zd - ax ay) (gdx gdy), (D(Syy) / Zd - ay ay) (gdy gdy)}
+ *            ellipse = {a, b, azimuth}: h = (cxx + cyy) 0.5; d = (cxx - cyy) 0.5; r = sqrt(d d + cxy cxy); a = sqrt(h + r);
+ *                b = sqrt(max(h - r, 0)); azimuth = 0.5 atan2(cxy, d), the major axis from +x in (-pi/2, pi/2]
+ *            area = (Zd / 2^30) (gdx gdy), the pdf's area in peak units; rim_fraction = D(rim) / Zd; nz; mass = Z
+ *            for level k, c = levels[k]: tq = (uint64)ceil(c Zd), at most Z; from the top bin down to the first bin B whose
+ *                cumulative mass M reaches tq, with C the cumulative count: level_count = C, level_area = C (gdx gdy),
+ *                level_fraction = D(M) / Zd >= c, level_rho = the least rho of bin B.  The region is the highest-density one to
+ *                the bin's resolution (3 % of rho): the exact region's count lies between C less count[B] and C.
+ *            An event with no candidate or no pdf (Z = 0) has counts 0 and every real output NaN.
+ *   mx [E][nx], my [E][ny] (or NULL): the marginals, D(column sum) / Zd and D(row sum) / Zd; NaN for an event without a pdf.
+ *   samples  [E][S] (int32 nodes) for the caller's uniforms u [E][S] in [0, 1): q = (uint64)(u Zd), at most Z - 1 (u <= 0 or NaN:
+ *            0); the sample is the least node, in node order, whose inclusive cumulative mass exceeds q.  -1 without a pdf.
+ * stats: the search's, summed over the groups, kernel_ms with this unit's kernels; reserved[1] is the number of groups,
+ * reserved[2] this unit's kernels' part of kernel_ms in nanoseconds.  A positive pp->reserved[0] sets the events per group and a
+ * positive pp->reserved[1] the tiles of 256 nodes per block of the mass pass, for tests; no result depends on either.
+ * The _dev forms take t, w, need, mx, my, u and samples as memory of the handle's device (res, pdf and st stay host memory); the
+ * host forms are upload, that, download: the same bits.  Events are independent: any split of E over calls gives the same bits.
+ * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: what the search refuses; a null pp or pdf; nx or
+ * ny above 65536 (with it every term of the sums fits an int64); nlevels outside 0 .. 8; a level not in (0, 1); S < 0, or S > 0
+ * with a null u or samples; power < 0 or > 4096; a negative pp->reserved[0] or [1]; for rtmi_locate_pdf a sigma not finite and > 0.
+ * Not covered: later arrivals, 3-D grids, a pdf from the stacking volume, more than 8 levels, region outlines or
+ * connected-component counts, several GPUs. */
+typedef struct { double sigma; int32_t power, nlevels; double levels[8]; int64_t S; int64_t reserved[4]; } rtmi_pdf_params;
+typedef struct {
+    double mean_x, mean_y, cov[3], ellipse[3], area, rim_fraction;
+    int64_t nz, mass;
+    int64_t level_count[8];
+    double level_area[8], level_fraction[8], level_rho[8];
+    int64_t reserved[4];
+} rtmi_pdf_result;
+int rtmi_locate_pdf(rtmi_locator *loc, const rtmi_pdf_params *pp, int64_t E, const double *t, const double *w, const int32_t *need,
+                    rtmi_locate_result *res, rtmi_pdf_result *pdf, double *mx, double *my, const double *u, int32_t *samples,
+                    rtmi_locate_stats *st);
+int rtmi_locate_pdf_dev(rtmi_locator *loc, const rtmi_pdf_params *pp, int64_t E, const double *d_t, const double *d_w,
+                        const int32_t *d_need, rtmi_locate_result *res, rtmi_pdf_result *pdf, double *d_mx, double *d_my,
+                        const double *d_u, int32_t *d_samples, rtmi_locate_stats *st);
+int rtmi_locate_edt_pdf(rtmi_locator *loc, const rtmi_edt_params *ep, const rtmi_pdf_params *pp, int64_t E, const double *t,
+                        const double *w, const int32_t *need, rtmi_edt_result *res, rtmi_pdf_result *pdf, double *mx, double *my,
+                        const double *u, int32_t *samples, rtmi_locate_stats *st);
+int rtmi_locate_edt_pdf_dev(rtmi_locator *loc, const rtmi_edt_params *ep, const rtmi_pdf_params *pp, int64_t E, const double *d_t,
+                            const double *d_w, const int32_t *d_need, rtmi_edt_result *res, rtmi_pdf_result *pdf, double *d_mx,
+                            double *d_my, const double *d_u, int32_t *d_samples, rtmi_locate_stats *st);
 
 /* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
  * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it

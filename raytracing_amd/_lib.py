@@ -194,6 +194,21 @@ class EdtResult(C.Structure):
                 ("reserved", C.c_int64 * 2)]
 
 
+class PdfParams(C.Structure):
+    """rtmi_pdf_params: the density's scale (least squares) or power (EDT), the confidence levels and the samples per event of
+    rtmi_locate_pdf and rtmi_locate_edt_pdf"""
+    _fields_ = [("sigma", C.c_double), ("power", C.c_int32), ("nlevels", C.c_int32), ("levels", C.c_double * 8), ("S", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
+class PdfResult(C.Structure):
+    """rtmi_pdf_result: one event's expectation, covariance, ellipse, area, rim fraction and confidence regions"""
+    _fields_ = [("mean_x", C.c_double), ("mean_y", C.c_double), ("cov", C.c_double * 3), ("ellipse", C.c_double * 3),
+                ("area", C.c_double), ("rim_fraction", C.c_double), ("nz", C.c_int64), ("mass", C.c_int64),
+                ("level_count", C.c_int64 * 8), ("level_area", C.c_double * 8), ("level_fraction", C.c_double * 8),
+                ("level_rho", C.c_double * 8), ("reserved", C.c_int64 * 4)]
+
+
 class StackParams(C.Structure):
     """rtmi_stack_params: the trace axis, the origin-time scan and the event selection of rtmi_locate_stack"""
     _fields_ = [("nt", C.c_int64), ("M", C.c_int64), ("ct0", C.c_double), ("cdt", C.c_double), ("o0", C.c_double), ("od", C.c_double),
@@ -337,6 +352,16 @@ SYMBOLS = {
     "rtmi_locate_edt_dev": (C.c_int, [C.c_void_p, C.POINTER(EdtParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(EdtResult), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LocateStats)]),
     "rtmi_edt_exp": (C.c_int, [_dp, _dp, C.c_int64]),
+    "rtmi_locate_pdf": (C.c_int, [C.c_void_p, C.POINTER(PdfParams), C.c_int64, _dp, _dp, _ip, C.POINTER(LocateResult),
+                                  C.POINTER(PdfResult), _dp, _dp, _dp, _ip, C.POINTER(LocateStats)]),
+    "rtmi_locate_pdf_dev": (C.c_int, [C.c_void_p, C.POINTER(PdfParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(LocateResult), C.POINTER(PdfResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(LocateStats)]),
+    "rtmi_locate_edt_pdf": (C.c_int, [C.c_void_p, C.POINTER(EdtParams), C.POINTER(PdfParams), C.c_int64, _dp, _dp, _ip,
+                                      C.POINTER(EdtResult), C.POINTER(PdfResult), _dp, _dp, _dp, _ip, C.POINTER(LocateStats)]),
+    "rtmi_locate_edt_pdf_dev": (C.c_int, [C.c_void_p, C.POINTER(EdtParams), C.POINTER(PdfParams), C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(EdtResult), C.POINTER(PdfResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(LocateStats)]),
     "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
                                     C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -2183,6 +2183,13 @@ def edt_stats(st):
             "groups": int(st.reserved[1])}                         # the groups of event chunks the call was walked in
 
 
+def pdf_stats(st):
+    return {"kernel_ms": st.kernel_ms, "upload_ms": st.upload_ms, "triples": int(st.triples), "contributing": int(st.contributing),
+            "search_ms": st.reserved[0] * 1e-6,                    # the search kernel's own part of kernel_ms
+            "groups": int(st.reserved[1]),                         # the groups of events the call was walked in
+            "pdf_ms": st.reserved[2] * 1e-6}                       # the pdf kernels' part of kernel_ms
+
+
 def edt_exp(z):
     """rtmi_edt_exp: exp(z) for z in [-700, 0] as rtmi_locate_edt's device code evaluates it (numpy's array exp, restated), on the
     host; tests/edt_ref.py takes its exp from here"""
@@ -2214,6 +2221,8 @@ class Locator:
       and weights, int32 min_picks) and returns maps as a tensor on it: the same bits, no copy of them through the host.
       locate_edt(picks, sigma, ...) is the robust search by equal differential time, for picks that may contain outliers
       (see its own text); locate_edt_device its form on torch tensors.
+      pdf(picks, sigma, method="l2" | "edt", ...) is either search with the pdf of its whole map: expectation, covariance,
+      confidence regions, marginals and samples (see its own text); pdf_device its form on torch tensors.
       stack(traces [P, nt], dt, t0, scan=(o0, od, M), ...) needs no picks: it stacks one characteristic function per station along
       every node's moveout for every origin time of the scan and takes events from the peaks (see stack's own text).
     With stats=True the calls return (result, stats)."""
@@ -2424,6 +2433,158 @@ class Locator:
         if shares:
             out.update(share=sh, resid=rs)
         return (out, edt_stats(st)) if stats else out
+
+    def _pdf_params(self, who, method, sigma, power, levels, samples, group, tiles):
+        if method not in ("l2", "edt"):
+            raise ValueError(f"{who}: method must be 'l2' or 'edt'")
+        levels = tuple(float(c) for c in levels)
+        if len(levels) > 8:
+            raise ValueError(f"{who}: at most 8 levels")
+        pp = _lib.PdfParams()
+        pp.sigma, pp.power, pp.nlevels, pp.S = float(sigma), int(power), len(levels), int(samples)
+        for k, c in enumerate(levels):
+            pp.levels[k] = c
+        pp.reserved[0], pp.reserved[1] = int(group), int(tiles)
+        return pp
+
+    def _pdf_result(self, pdf, E, nlevels):
+        a = np.frombuffer(pdf, dtype=np.dtype(_lib.PdfResult)).copy() if E else np.zeros(0, dtype=np.dtype(_lib.PdfResult))
+        c = a["cov"].reshape(E, 3)
+        cov = np.empty((E, 2, 2))
+        cov[:, 0, 0], cov[:, 0, 1], cov[:, 1, 0], cov[:, 1, 1] = c[:, 0], c[:, 1], c[:, 1], c[:, 2]
+        out = {"mean_x": a["mean_x"].copy(), "mean_y": a["mean_y"].copy(), "pdf_cov": cov, "ellipse": a["ellipse"].reshape(E, 3).copy(),
+               "area": a["area"].copy(), "rim_fraction": a["rim_fraction"].copy(), "nz": a["nz"].copy(), "mass": a["mass"].copy()}
+        for k in ("level_count", "level_area", "level_fraction", "level_rho"):
+            out[k] = a[k].reshape(E, 8)[:, :nlevels].copy()
+        return out
+
+    def _sample_places(self, node, rng, jitter):
+        """x, y of sampled nodes (NaN for -1), with a uniform offset within the cell where jitter"""
+        gx0, gdx, _, gy0, gdy, _ = self.grid
+        none = node < 0
+        ix, iy = (node % self.nx).astype(np.float64), (node // self.nx).astype(np.float64)
+        if jitter:
+            ix = ix + rng.uniform(-0.5, 0.5, node.shape)
+            iy = iy + rng.uniform(-0.5, 0.5, node.shape)
+        return np.where(none, np.nan, float(gx0) + ix * float(gdx)), np.where(none, np.nan, float(gy0) + iy * float(gdy))
+
+    def pdf(self, picks, sigma, method="l2", weights=None, min_picks=None, power=0, levels=(0.68, 0.95), marginals=False, samples=0,
+            seed=0, jitter=True, u=None, stats=False, _events_per_group=0, _tiles_per_block=0, _chunks_per_group=0):
+        """The location pdf of every event from the search's whole map, on the device (rtmi_locate_pdf, rtmi_locate_edt_pdf,
+        include/rtmi.h): where `locate`'s cov is a quadratic through nine nodes, this sums over all of them, so a
+        second lobe, a trade-off along a ray or a pdf cut off by the rim show.  method "l2": the density is
+        exp(-sw (obj - obj*) / (2 sigma^2)); with weights in 1 / s^2 pass sigma = 1, without weights the picks' standard
+        deviation.  method "edt": sigma is locate_edt's, the density is (value / value*)^power, power 0: the best node's number
+        of readings.  Returns the search's own keys (bit-equal to locate / locate_edt) and
+          mean_x, mean_y          the expectation
+          pdf_cov [E, 2, 2]       the covariance about it; ellipse [E, 3]: semi-axes and the major one's angle from +x
+          area                    the pdf's area in peak units; rim_fraction: the mass on the grid's rim; nz: the nodes with mass
+          level_count, level_area, level_fraction, level_rho [E, len(levels)]: the highest-density region that holds each level
+          mx [E, nx], my [E, ny]  with marginals=True
+          sample_node [E, S], sample_x, sample_y with samples=S: drawn with numpy.random.default_rng(seed), with a uniform
+                                  offset within the cell where jitter; u [E, S] in [0, 1) replaces the seeded uniforms
+        An event with no candidate or no pdf has counts 0 and NaN.  pdf_device takes torch tensors on the handle's device and
+        returns mx, my and sample_node as tensors on it (and no sample_x, sample_y)."""
+        who = "Locator.pdf"
+        pp = self._pdf_params(who, method, sigma, power, levels, samples, _events_per_group, _tiles_per_block)
+        t = np.ascontiguousarray(picks, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.P:
+            raise ValueError(f"{who}: picks must be [E, {self.P}]")
+        E, S = t.shape[0], int(samples)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w is not None and w.shape != t.shape:
+            raise ValueError(f"{who}: weights must have the shape of picks")
+        need = None
+        if min_picks is not None:
+            need = np.ascontiguousarray(np.broadcast_to(np.asarray(min_picks, dtype=np.int32), (E,)))
+        h = self._open()
+        pdf = (_lib.PdfResult * E)()
+        mx = np.empty((E, self.nx)) if marginals else None
+        my = np.empty((E, self.ny)) if marginals else None
+        rng = np.random.default_rng(seed)              # the uniforms first, then the offsets within the cell
+        if S > 0:
+            u = rng.random((E, S)) if u is None else np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (E, S):
+                raise ValueError(f"{who}: u must be [E, samples]")
+        else:
+            u = None
+        sm = np.empty((E, S), dtype=np.int32) if S > 0 else None
+        st = _lib.LocateStats()
+        ip = lambda a: None if a is None else a.ctypes.data_as(_lib._ip)                     # noqa: E731
+        if method == "l2":
+            res = (_lib.LocateResult * E)()
+            check(lib().rtmi_locate_pdf(h, C.byref(pp), E, dptr(t), dptr(w), ip(need), res, pdf, dptr(mx), dptr(my), dptr(u), ip(sm),
+                                        C.byref(st)))
+            out = self._result(res, E, True)
+        else:
+            ep = self._edt_params(sigma, _chunks_per_group)
+            res = (_lib.EdtResult * E)()
+            check(lib().rtmi_locate_edt_pdf(h, C.byref(ep), C.byref(pp), E, dptr(t), dptr(w), ip(need), res, pdf, dptr(mx), dptr(my),
+                                            dptr(u), ip(sm), C.byref(st)))
+            out = self._edt_result(res, E, True)
+        out.update(self._pdf_result(pdf, E, pp.nlevels))
+        if marginals:
+            out.update(mx=mx, my=my)
+        if S > 0:
+            x, y = self._sample_places(sm, rng, jitter)
+            out.update(sample_node=sm, sample_x=x, sample_y=y, sample_u=u)
+        return (out, pdf_stats(st)) if stats else out
+
+    def pdf_device(self, picks, sigma, method="l2", weights=None, min_picks=None, power=0, levels=(0.68, 0.95), marginals=False,
+                   samples=0, seed=0, u=None, stats=False, _events_per_group=0, _tiles_per_block=0, _chunks_per_group=0):
+        """`pdf` on torch tensors of the handle's device; u [E, samples] (fp64, on the device) replaces the seeded draw"""
+        import torch
+        who = "Locator.pdf_device"
+        for name, a, dt in (("picks", picks, torch.float64), ("weights", weights, torch.float64), ("min_picks", min_picks, torch.int32),
+                            ("u", u, torch.float64)):
+            if a is None:
+                continue
+            if not isinstance(a, torch.Tensor):
+                raise TypeError(f"{who}: {name} must be a torch tensor")
+            if a.dtype != dt:
+                raise TypeError(f"{who}: {name} must be {dt}")
+            if not a.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous")
+            if not a.is_cuda:                          # which GPU it is on, the library checks against the handle's
+                raise ValueError(f"{who}: {name} must be a tensor on a GPU, not on the host")
+        pp = self._pdf_params(who, method, sigma, power, levels, samples, _events_per_group, _tiles_per_block)
+        if picks is None or picks.dim() != 2 or picks.shape[1] != self.P:
+            raise ValueError(f"{who}: picks must be [E, {self.P}]")
+        E, S = picks.shape[0], int(samples)
+        if weights is not None and weights.shape != picks.shape:
+            raise ValueError(f"{who}: weights must have the shape of picks")
+        if min_picks is not None and tuple(min_picks.shape) != (E,):
+            raise ValueError(f"{who}: min_picks must be [E]")
+        if u is not None and tuple(u.shape) != (E, S):
+            raise ValueError(f"{who}: u must be [E, samples]")
+        h = self._open()
+        dev = picks.device
+        pdf = (_lib.PdfResult * E)()
+        mx = torch.empty((E, self.nx), dtype=torch.float64, device=dev) if marginals else None
+        my = torch.empty((E, self.ny), dtype=torch.float64, device=dev) if marginals else None
+        if S > 0 and u is None:
+            u = torch.from_numpy(np.random.default_rng(seed).random((E, S))).to(dev)
+        sm = torch.empty((E, S), dtype=torch.int32, device=dev) if S > 0 else None
+        st = _lib.LocateStats()
+        p = lambda a: None if a is None else a.data_ptr()                                    # noqa: E731
+        torch.cuda.synchronize(dev)                    # the library works on the null stream
+        if method == "l2":
+            res = (_lib.LocateResult * E)()
+            check(lib().rtmi_locate_pdf_dev(h, C.byref(pp), E, p(picks), p(weights), p(min_picks), res, pdf, p(mx), p(my), p(u), p(sm),
+                                            C.byref(st)))
+            out = self._result(res, E, True)
+        else:
+            ep = self._edt_params(sigma, _chunks_per_group)
+            res = (_lib.EdtResult * E)()
+            check(lib().rtmi_locate_edt_pdf_dev(h, C.byref(ep), C.byref(pp), E, p(picks), p(weights), p(min_picks), res, pdf, p(mx), p(my),
+                                                p(u), p(sm), C.byref(st)))
+            out = self._edt_result(res, E, True)
+        out.update(self._pdf_result(pdf, E, pp.nlevels))
+        if marginals:
+            out.update(mx=mx, my=my)
+        if S > 0:
+            out.update(sample_node=sm, sample_u=u)
+        return (out, pdf_stats(st)) if stats else out
 
     def _stack_params(self, who, nt, dt, t0, scan, min_stations, threshold, min_sep, max_events):
         o0, od, M = scan

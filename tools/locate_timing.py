@@ -28,6 +28,16 @@ over the pairs and argmax, one event at a time (five [pairs, nodes] fp64 tempora
 kernel's fp64 issue floor are printed with it.
 
     python tools/locate_timing.py --edt [--events 64 1024] [--tables 32] [--reps 5] [--sigma 0.01] [--out FILE.json]
+
+--pdf [--edt] times the location pdf of either search instead: Locator.pdf_device with two levels, both
+marginals and --samples samples per event, for the event counts given (default 64 and 1024), against the same statistics in plain
+torch on the device from the maps that locate_device(maps=True) / locate_edt_device(maps=True) return, which exists without the
+pdf entries: exp (or the power), sums for the moments and the marginals, a sort and a cumulative sum for the regions,
+searchsorted on a cumulative sum for the samples, --torch-chunk times 8 events at a time.  Both are timed as wall time between
+two idle devices, since both do host work.  Also printed: the bare search without maps, what the pdf kernels add to it (their
+own device time and the difference of the calls' device times), and their floor, one read of the maps at 6 TB/s.
+
+    python tools/locate_timing.py --pdf [--edt] [--events 64 1024] [--tables 32] [--reps 5] [--pdf-sigma 0.05] [--samples 256]
 """
 import argparse
 import json
@@ -279,12 +289,129 @@ def edt_main(a):
             fh.write(text + "\n")
 
 
+def torch_pdf(torch, maps, best, scale, power, levels, ud, nx, chunk):
+    """the yardstick of --pdf from maps [E, ny, nx] on the device: mean, covariance, region counts, marginals, samples; best [E]
+    (int64 nodes), scale [E] (least squares: sw* / (2 sigma^2)) or power [E] (EDT)"""
+    E = maps.shape[0]
+    flat = maps.reshape(E, -1)
+    out = {k: [] for k in ("mean", "cov", "count", "mx", "my", "sample")}
+    ix = (torch.arange(flat.shape[1], device=maps.device) % nx).to(torch.float64)
+    iy = (torch.arange(flat.shape[1], device=maps.device) // nx).to(torch.float64)
+    for e0 in range(0, E, chunk):
+        m = flat[e0:e0 + chunk]
+        ref = m.gather(1, best[e0:e0 + chunk, None])
+        if scale is not None:
+            rho = torch.exp(-(m - ref) * scale[e0:e0 + chunk, None])
+        else:
+            rho = torch.where(m >= 0, m / ref, torch.zeros_like(m)) ** power[e0:e0 + chunk, None]
+        rho = torch.nan_to_num(rho, nan=0.0, posinf=0.0)
+        Z = rho.sum(dim=1)
+        ax, ay = (rho * ix).sum(dim=1) / Z, (rho * iy).sum(dim=1) / Z
+        out["mean"].append(torch.stack([ax, ay], dim=1))
+        out["cov"].append(torch.stack([(rho * ix * ix).sum(dim=1) / Z - ax * ax, (rho * ix * iy).sum(dim=1) / Z - ax * ay,
+                                       (rho * iy * iy).sum(dim=1) / Z - ay * ay], dim=1))
+        grid2 = rho.reshape(rho.shape[0], -1, nx)
+        out["mx"].append(grid2.sum(dim=1) / Z[:, None])
+        out["my"].append(grid2.sum(dim=2) / Z[:, None])
+        top = torch.cumsum(torch.sort(rho, dim=1, descending=True).values, dim=1)
+        want = torch.tensor(levels, dtype=torch.float64, device=maps.device)[None, :] * Z[:, None]
+        out["count"].append(torch.searchsorted(top, want.contiguous()) + 1)
+        if ud is not None:
+            cum = torch.cumsum(rho, dim=1)
+            out["sample"].append(torch.searchsorted(cum, (ud[e0:e0 + chunk] * Z[:, None]).contiguous(), right=True))
+    return {k: torch.cat(v) for k, v in out.items() if v}
+
+
+def pdf_main(a):
+    """--pdf [--edt]: Locator.pdf_device against the same statistics in plain torch from the maps of the plain search"""
+    import time
+    from raytracing_amd import rt_bench as rb
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("locate_timing: no GPU; nothing is measured without one")
+    P = a.tables
+    grid, T, _ = problem(P, 1)
+    nx, ny = grid[2], grid[5]
+    nn = nx * ny
+    L = rb.Locator(T, grid)
+    kind = "edt" if a.edt else "l2"
+    sigma = a.sigma if a.edt else a.pdf_sigma
+    levels = (0.68, 0.95)
+    events = a.events if a.events != [64, 1024, 4096] else [64, 1024]
+    out = {"grid": [nx, ny], "tables": P, "kind": kind, "sigma": sigma, "samples": a.samples, "reps": a.reps, "cases": []}
+
+    def wall(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = f()
+        torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    for E in events:
+        _, _, t = problem(P, E, seed=E)
+        td = torch.from_numpy(t).cuda()
+        ud = torch.from_numpy(np.random.default_rng(E).random((E, a.samples))).cuda() if a.samples else None
+        search = (lambda **kw: L.locate_edt_device(td, sigma, stats=True, **kw)) if a.edt else (lambda **kw: L.locate_device(td, stats=True, **kw))
+        ours = lambda: L.pdf_device(td, sigma, method=kind, levels=levels, marginals=True, samples=a.samples, u=ud, stats=True)  # noqa: E731
+
+        def yard():
+            r, _ = search(maps=True)
+            best = torch.from_numpy(r["node"].astype(np.int64)).cuda()
+            if a.edt:
+                return torch_pdf(torch, r["maps"], best, None, torch.from_numpy(r["count"].astype(np.float64)).cuda(), levels, ud, nx,
+                                 8 * a.torch_chunk)
+            scale = torch.from_numpy(r["sw"] * (0.5 / (sigma * sigma))).cuda()
+            return torch_pdf(torch, r["maps"], best, scale, None, levels, ud, nx, 8 * a.torch_chunk)
+
+        ours(); yard(); search()                                                   # warm all three
+        tw, tk, tp, ty, tb = [], [], [], [], []
+        for _ in range(a.reps):                                                    # alternating
+            (r, st), ms = wall(ours)
+            tw.append(ms)
+            tk.append(st["kernel_ms"])
+            tp.append(st["pdf_ms"])
+            y, ms = wall(yard)
+            ty.append(ms)
+            tb.append(search()[1]["kernel_ms"])
+        sw_, sy, sk, sp, sb = series(tw), series(ty), series(tk), series(tp), series(tb)
+        spread = max(sw_["max_ms"] - sw_["min_ms"], sy["max_ms"] - sy["min_ms"])
+        has = r["mass"] > 0
+        gx0, gdx, _, gy0, gdy, _ = grid
+        mean = y["mean"].cpu().numpy()
+        off = np.maximum(np.abs((r["mean_x"] - gx0) / gdx - mean[:, 0]), np.abs((r["mean_y"] - gy0) / gdy - mean[:, 1]))[has]
+        count = y["count"].cpu().numpy()[has]
+        case = {"events": E, "groups": st["groups"], "pdf_call_wall": sw_, "torch_wall": sy, "spread_ms": spread,
+                "ratio_of_medians": sy["median_ms"] / sw_["median_ms"],
+                "pdf_call_is_faster_beyond_the_spread": bool(sy["median_ms"] - sw_["median_ms"] > spread),
+                "pdf_call_kernels": sk, "pdf_kernels": sp, "bare_search_kernels": sb,
+                "added_to_the_bare_search_ms": sk["median_ms"] - sb["median_ms"],
+                "floor_ms": {"one_read_of_the_maps": E * nn * 8 / HBM * 1e3},
+                "events_with_a_pdf": int(has.sum()), "mean_max_abs_diff_to_torch_cells": float(off.max()) if has.any() else None,
+                "median_nodes_in_the_95_region": float(np.median(r["level_count"][has, 1])) if has.any() else None,
+                "events_with_region_counts_at_or_above_torchs": int((r["level_count"][has] >= count).all(axis=1).sum()),
+                "region_count_least_difference_to_torchs": int((r["level_count"][has] - count).min()) if has.any() else None}
+        if a.samples and has.any():
+            case["samples_equal_to_torchs_share"] = float((r["sample_node"].cpu().numpy()[has] == y["sample"].cpu().numpy()[has]).mean())
+        print(json.dumps(case), file=sys.stderr, flush=True)
+        out["cases"].append(case)
+    L.close()
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--stack", type=int, nargs="+", default=None, metavar="M",
                     help="time the stacking search k_stack (DESIGN.md section 30) for these scan lengths instead, e.g. --stack 256 4096")
     ap.add_argument("--edt", action="store_true", help="time the equal-differential-time search k_edt (DESIGN.md section 31) instead")
     ap.add_argument("--sigma", type=float, default=0.01, help="--edt: the pick error in seconds")
+    ap.add_argument("--pdf", action="store_true", help="time the location pdf (DESIGN.md section 33) of the least-squares search, or with --edt of that one")
+    ap.add_argument("--pdf-sigma", type=float, default=0.05, help="--pdf without --edt: the picks' standard deviation in seconds")
+    ap.add_argument("--samples", type=int, default=256, help="--pdf: samples per event")
     ap.add_argument("--events", type=int, nargs="+", default=[64, 1024, 4096])
     ap.add_argument("--tables", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
@@ -295,6 +422,8 @@ def main():
     a = ap.parse_args()
     if a.stack:
         return stack_main(a)
+    if a.pdf:
+        return pdf_main(a)
     if a.edt:
         return edt_main(a)
     from raytracing_amd import rt_bench as rb
