@@ -420,8 +420,8 @@ int rtmi_field_eval_dgrad(const rtmi_field *f, int64_t npts, const double *x, co
  * Three passes with 64-bit atomics give the same bits in every schedule, launch mode, ray sorting and source grouping.
  * Not covered (count 0, NaN): nodes beyond the shorter of two neighbouring rays' ends, nodes in gaps the rules reject, and
  * caustics thinner than the fan's spacing (their branches are missed, and count is short).  The later branches of a node with
- * count > 1: rtmi_arrival_grid.
- *   count  [S][ny][nx]          covering triangles: the arrival branches (1 in a simple fan, 3 in a triplication)
+ * count > 1: rtmi_arrival_grid.  A value at the nodes that are not covered: rtmi_eikonal_fill.
+ *   count  [S][ny][nx]         covering triangles: the arrival branches (1 in a simple fan, 3 in a triplication)
  *   out    [S][ncols][ny][nx]   T theta0 theta ray step (ncols 5), then J G kmah with amplitude (ncols 8); NaN where count is 0
  * Host buffers, fp64, the caller's fan order; both dtypes (fp32 records are widened), every method.  Needs record_stride 1.
  * RTMI_ERR_ARG before any device work: record_stride != 1, R % fan_size != 0, fan_size < 2, nx or ny < 1, gdx or gdy <= 0 or
@@ -1268,6 +1268,77 @@ int rtmi_locate_edt_pdf(rtmi_locator *loc, const rtmi_edt_params *ep, const rtmi
 int rtmi_locate_edt_pdf_dev(rtmi_locator *loc, const rtmi_edt_params *ep, const rtmi_pdf_params *pp, int64_t E, const double *d_t,
                             const double *d_w, const int32_t *d_need, rtmi_edt_result *res, rtmi_pdf_result *pdf, double *d_mx,
                             double *d_my, const double *d_u, int32_t *d_samples, rtmi_locate_stats *st);
+
+/* Eikonal continuation of traveltime tables: a table that is defined at every node.  DESIGN.md section 34.  A ray-cell table
+ * (rtmi_first_arrival_grid) is count 0, NaN beyond the shorter of two neighbouring rays' ends, in gaps the gap rule rejects, in
+ * shadow zones and outside the fan's wedge; the first arrival that physically exists there, diffracted or a head wave, is what
+ * the eikonal equation |grad T| = n gives.  This entry solves it by the first-order Godunov upwind scheme and fast sweeping,
+ * seeded by the table's covered nodes and a small analytic ball round the source; a point-source solve without any rays is the
+ * same call on a table that is all NaN.  All on the device, in fp64; every product, sum, quotient and sqrt is one rounded
+ * operation (raytracing_amd/csrc/rt_eikonal.h holds the arithmetic, tests/eikonal_ref.py restates it); min(x, y) is y < x ? y : x.
+ *   grid     node (ix, iy) is X = gx0 + ix gdx, Y = gy0 + iy gdy, as in rtmi_grid_params
+ *   n        [ny][nx], the slowness at the nodes, shared by all sources
+ *   src      [S][2], the sources (x, y); they may lie off the nodes and off the grid
+ *   n_src    [S], the slowness at each source, evaluated by the caller
+ *   T        [S][ny][nx], read and written in place; NULL: every input is NaN and no table is returned
+ * States, with s = n at the node:
+ *   obstacle  s is not finite or s <= 0.  Never updated; as a neighbour it reads as +inf; its output is its input.
+ *   seeded    not an obstacle, and the input T is finite.  Frozen: it keeps its bits.
+ *   free      every other node (an input of NaN, +inf or -inf).  It starts from +inf.
+ *   ball      a free node with u = (X - xs) / gdx, v = (Y - ys) / gdy and u u + v v <= ball ball, where ball >= 0 and n_src is
+ *             finite and > 0: with dx = X - xs, dy = Y - ys its value is T = (0.5 (n_src + s)) sqrt(dx dx + dy dy), frozen from then on.
+ * The update of a free node, a neighbour outside the grid reading as +inf:
+ *     a = min(T[j][i-1], T[j][i+1]);  b = min(T[j-1][i], T[j+1][i]);  both +inf: no change
+ *     ta = a + gdx s;  tb = b + gdy s
+ *     b == +inf or ta <= b:       t = ta
+ *     else a == +inf or tb <= a:  t = tb
+ *     else wx = 1 / (gdx gdx); wy = 1 / (gdy gdy); A = wx + wy; B = a wx + b wy; e = a - b;
+ *          d = A (s s) - (wx wy) (e e);  t = d < 0 ? min(ta, tb) : (B + sqrt(d)) / A
+ *     T[j][i] = t iff t < T[j][i], which counts as one change
+ * A round is four Gauss-Seidel sweeps over the whole grid in the orders (+x, +y), (-x, +y), (-x, -y), (+x, -y), y the outer
+ * loop, each update reading its neighbours' current values.  Where no node is free, or no node is seeded or of the ball, no round
+ * runs (rounds 0, clean).  Else rounds repeat until one changes nothing (clean) or max_rounds have run.  The sweep order is the
+ * definition: the update is not provably monotone in its operands in floating point, so "the fixed point" defines no bits.  The
+ * nodes of one anti-diagonal of a sweep do not read one another, so the device, whose lanes share a diagonal, has these bits.
+ * At the end free nodes still at +inf are unreached and become NaN; every free node and node of the ball is written, no other.
+ *   rounds   [S][2] (host, or NULL): the rounds run, and 1 where the last of them was clean (or none ran), else 0
+ *   filled   [S][ny][nx] bytes (or NULL): 1 at the nodes the call gave a value, the ball included, else 0
+ *   stats    free_nodes (the ball's included) = filled + unreached, summed over the sources; rounds_max; changes; kernel_ms;
+ *            path: where one source's T, n and states (17 bytes per node) fit 128 KiB they live in the workgroup's LDS
+ *            (RTMI_EIKONAL_LDS), else in a work space in global memory (RTMI_EIKONAL_GLOBAL, 9 bytes per node and source, sources in
+ *            groups of at most 1 GiB).  ep->reserved[0] = 1 takes the global path on any grid, for tests; no result depends on it.
+ * One workgroup per source, the round loop inside the kernel; sources are independent: any split of S over calls gives the same
+ * bits.  rtmi_eikonal_fill_dev takes n, src, n_src, T and filled as memory of the calling thread's current device (rounds and
+ * stats stay host memory); rtmi_eikonal_fill is upload, that, download: the same bits.
+ * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null ep; nx or ny < 1; nx ny > 2^31; gdx or gdy
+ * not finite or <= 0; gx0 or gy0 not finite; S < 0; a null n, src or n_src with S > 0; max_rounds < 0; a ball that is not finite;
+ * ep->reserved[0] other than 0 or 1.
+ * Not covered: factored or higher-order schemes (the error near the source is first order: about 1 % of the largest T where the
+ * ball is the only seed); covered nodes never decrease, so a head wave does not undercut a table's geometric
+ * arrival; amplitudes, launch angles and count at filled nodes; anisotropy; 3-D; several GPUs; fp32 tables. */
+enum { RTMI_EIKONAL_LDS = 1, RTMI_EIKONAL_GLOBAL = 2 };
+typedef struct {
+    double gx0, gdx;         /* as in rtmi_grid_params */
+    int64_t nx;
+    double gy0, gdy;
+    int64_t ny;
+    double ball;             /* the radius of the source ball in cells; negative: no ball.  The Python layer's default is 2 */
+    int32_t max_rounds;      /* 0: 64 */
+    int32_t reserved0;
+    int64_t reserved[4];
+} rtmi_eikonal_params;
+typedef struct {
+    int64_t free_nodes, filled, unreached;
+    int64_t changes;         /* updates that lowered a node, all rounds and sources */
+    int32_t rounds_max;      /* the most rounds of any source */
+    int32_t path;            /* RTMI_EIKONAL_LDS or RTMI_EIKONAL_GLOBAL */
+    double kernel_ms;        /* device time (HIP events) */
+    int64_t reserved[4];
+} rtmi_eikonal_stats;
+int rtmi_eikonal_fill(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src, double *T,
+                      int32_t *rounds, uint8_t *filled, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_fill_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src, const double *d_n_src,
+                          double *d_T, int32_t *rounds, uint8_t *d_filled, rtmi_eikonal_stats *stats);
 
 /* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
  * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it

@@ -209,6 +209,22 @@ class PdfResult(C.Structure):
                 ("level_rho", C.c_double * 8), ("reserved", C.c_int64 * 4)]
 
 
+class EikonalParams(C.Structure):
+    """rtmi_eikonal_params: the grid as in GridParams, the source ball's radius in cells and the cap on the rounds"""
+    _fields_ = [("gx0", C.c_double), ("gdx", C.c_double), ("nx", C.c_int64), ("gy0", C.c_double), ("gdy", C.c_double),
+                ("ny", C.c_int64), ("ball", C.c_double), ("max_rounds", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved", C.c_int64 * 4)]
+
+
+class EikonalStats(C.Structure):
+    _fields_ = [("free_nodes", C.c_int64), ("filled", C.c_int64), ("unreached", C.c_int64), ("changes", C.c_int64),
+                ("rounds_max", C.c_int32), ("path", C.c_int32), ("kernel_ms", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
+EIKONAL_LDS, EIKONAL_GLOBAL = 1, 2      # rtmi_eikonal_stats.path
+EIKONAL_PATHS = {EIKONAL_LDS: "lds", EIKONAL_GLOBAL: "global"}
+
+
 class StackParams(C.Structure):
     """rtmi_stack_params: the trace axis, the origin-time scan and the event selection of rtmi_locate_stack"""
     _fields_ = [("nt", C.c_int64), ("M", C.c_int64), ("ct0", C.c_double), ("cdt", C.c_double), ("o0", C.c_double), ("od", C.c_double),
@@ -362,6 +378,10 @@ SYMBOLS = {
     "rtmi_locate_edt_pdf_dev": (C.c_int, [C.c_void_p, C.POINTER(EdtParams), C.POINTER(PdfParams), C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(EdtResult), C.POINTER(PdfResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(LocateStats)]),
+    "rtmi_eikonal_fill": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, _ip, C.POINTER(C.c_uint8),
+                                    C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_fill_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _ip,
+                                        C.c_void_p, C.POINTER(EikonalStats)]),
     "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
                                     C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

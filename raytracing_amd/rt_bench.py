@@ -1527,7 +1527,7 @@ def debug_arrival_rows(x, y, T, theta, last, theta0, grid, arrivals=1, order="ti
 
 
 def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_size, box, gamma=1, amplitude=False, mem_budget=0,
-                     max_gap=None, max_dtheta=None, stats=False, arrivals=None, order="time", **batch_kw):
+                     max_gap=None, max_dtheta=None, stats=False, arrivals=None, order="time", fill=None, **batch_kw):
     """First-arrival tables from many sources onto one grid, by public calls only: a fan of launch angles
     `thetas` per source (sources: (S, 2) array of (x, y)).  1. A count pass without a record sizes rec_rows to the longest ray.
     2. Sources are grouped so that each group's record (48 bytes per row and ray in fp64, 24 in fp32; 12 more with amplitude,
@@ -1537,7 +1537,12 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     stats=True also 'stats' (rec_rows, groups, count_ms, trace_ms, grid_ms: host wall times, and the grid calls' summed
     counters).  arrivals=K (with order "time" or "amplitude") takes Batch.arrival_grid instead: arrays of [S, K, ny, nx], count
     [S, ny, nx]; a group's candidate list (16 bytes per candidate, counted by a count-only call before it is allocated) then
-    counts against mem_budget too, and a group over it is traced again in halves."""
+    counts against mem_budget too, and a group over it is traced again in halves.  fill="eikonal" completes T after the ray-cell
+    pass (eikonal_fill with its defaults): every node the covered ones or the source can reach gets a first
+    arrival, with arrivals=K in slot 0 only, and 'filled' [S, ny, nx] (uint8) marks those nodes; count and the other columns
+    stay as they are, 0 and NaN there, since no ray reaches them.  fill=None is the ray-cell result alone."""
+    if fill not in (None, "eikonal"):
+        raise ValueError('traveltime_table: fill must be None or "eikonal"')
     src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
     th = np.ascontiguousarray(thetas, dtype=np.float64)
     S, M = len(src), len(th)
@@ -1596,8 +1601,143 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
         for k, v in r.items():
             res[k][g0:g0 + len(sg)] = v
         g0 += len(sg)
+    if fill is not None:
+        T0 = np.ascontiguousarray(res["T"][:, 0] if arrivals is not None else res["T"])
+        done = eikonal_fill(field, src, grid, T0, stats=True)
+        if arrivals is not None:
+            res["T"][:, 0] = done["T"]
+        else:
+            res["T"] = done["T"]
+        res["filled"] = done["filled"]
+        tot["eikonal"] = done["stats"]
     if stats:
         res["stats"] = tot
+    return res
+
+
+def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False):
+    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny)"""
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    ep = _lib.EikonalParams()
+    ep.gx0 = float(gx0); ep.gdx = float(gdx); ep.nx = int(nx)
+    ep.gy0 = float(gy0); ep.gdy = float(gdy); ep.ny = int(ny)
+    ep.ball = float(ball); ep.max_rounds = int(max_rounds)
+    ep.reserved[0] = int(bool(_global_path))
+    return ep
+
+
+def eikonal_stats(st):
+    return {"free_nodes": int(st.free_nodes), "filled": int(st.filled), "unreached": int(st.unreached), "changes": int(st.changes),
+            "rounds_max": int(st.rounds_max), "path": _lib.EIKONAL_PATHS.get(st.path, st.path), "kernel_ms": st.kernel_ms}
+
+
+def _eikonal_medium(who, field_or_n, src, grid, n_src):
+    """n [ny, nx] at the nodes and n_src [S] at the sources: a Field is sampled with Field.n_gradient, an array is n itself"""
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    if isinstance(field_or_n, Field):
+        X, Y = np.meshgrid(float(gx0) + np.arange(int(nx)) * float(gdx), float(gy0) + np.arange(int(ny)) * float(gdy))
+        n = field_or_n.n_gradient(X.reshape(-1), Y.reshape(-1))[0].reshape(int(ny), int(nx))
+        if n_src is None and len(src):
+            n_src = field_or_n.n_gradient(src[:, 0], src[:, 1])[0]
+    else:
+        n = field_or_n
+        if n_src is None and len(src):
+            raise ValueError(f"{who}: an array for n needs n_src=, the slowness at each source")
+    return n, (np.zeros(0) if n_src is None else n_src)
+
+
+def eikonal_fill(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+    """Complete traveltime tables by a first-arrival eikonal solve on the device (rtmi_eikonal_fill, include/rtmi.h; DESIGN.md
+    34): the first-order Godunov upwind scheme for |grad T| = n by fast sweeping, seeded by the finite nodes of T and an analytic
+    ball of `ball` cells round each source (negative: none).  field_or_n: a Field, sampled at the nodes and at the sources, or
+    n [ny, nx] with n_src [S].  sources [S, 2]; grid = (gx0, gdx, nx, gy0, gdy, ny); T [S, ny, nx] (not modified), or None: all
+    NaN, a point-source solve without rays.  Nodes where n is not finite or <= 0 are obstacles.  Returns a dict:
+      T [S, ny, nx]      finite inputs keep their bits; every other node that the seeds can reach has its first arrival; NaN
+                         where none can (and an obstacle keeps its input)
+      filled             [S, ny, nx] uint8, 1 where the call gave the value
+      rounds, converged  [S]: the rounds of four sweeps that ran (at most max_rounds, 0: 64), and whether the last changed nothing
+    and with stats=True 'stats'.  The error is first order in the spacing: about 1 % of the largest T where the ball is the
+    only seed, 1e-3 to 1e-4 in a shadow of a table that rays cover elsewhere -- shoot the full fan and let this fill the rest."""
+    who = "eikonal_fill"
+    src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
+    S, nx, ny = len(src), int(grid[2]), int(grid[5])
+    n, n_src = _eikonal_medium(who, field_or_n, src, grid, n_src)
+    n = np.ascontiguousarray(n, dtype=np.float64)
+    ns = np.ascontiguousarray(n_src, dtype=np.float64).reshape(-1)
+    if nx >= 1 and ny >= 1 and n.shape != (ny, nx):
+        raise ValueError(f"{who}: n must be [ny, nx] of the grid")
+    if len(ns) != S:
+        raise ValueError(f"{who}: n_src must be [S]")
+    shape = (S, max(ny, 0), max(nx, 0))
+    if T is None:
+        out = np.full(shape, np.nan)
+    else:
+        out = np.array(T, dtype=np.float64, order="C")
+        if out.shape != shape:
+            raise ValueError(f"{who}: T must be [S, ny, nx]")
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    filled = np.zeros(shape, dtype=np.uint8)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    check(lib().rtmi_eikonal_fill(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(out), rounds.ctypes.data_as(_lib._ip),
+                                  filled.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+    res = {"T": out, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy(), "filled": filled}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def eikonal_fill_device(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+    """eikonal_fill on torch tensors of one GPU, with no host copy of the tables (rtmi_eikonal_fill_dev): n [ny, nx], sources
+    [S, 2], n_src [S] and T [S, ny, nx] in fp64, contiguous; a Field in place of n is sampled as in eikonal_fill.  T is
+    completed IN PLACE and returned; None: a new table from an all-NaN input.  filled is a uint8 tensor on the device; rounds
+    and converged are numpy arrays.  The same bits."""
+    import torch
+    who = "eikonal_fill_device"
+    n = field_or_n
+    if isinstance(field_or_n, Field):
+        if not isinstance(sources, torch.Tensor):
+            raise TypeError(f"{who}: sources must be a torch tensor")
+        hn, hs = _eikonal_medium(who, field_or_n, sources.detach().cpu().numpy().reshape(-1, 2), grid,
+                                 None if n_src is None else n_src.detach().cpu().numpy())
+        n = torch.as_tensor(np.ascontiguousarray(hn), device=sources.device)
+        n_src = torch.as_tensor(np.ascontiguousarray(hs, dtype=np.float64), device=sources.device)
+    elif n_src is None:
+        raise ValueError(f"{who}: a tensor for n needs n_src=, the slowness at each source")
+    for name, a in (("n", n), ("sources", sources), ("n_src", n_src), ("T", T)):
+        if a is None and name == "T":
+            continue
+        if not isinstance(a, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a torch tensor")
+        if a.dtype != torch.float64:
+            raise TypeError(f"{who}: {name} must be torch.float64")
+        if not a.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+        if not a.is_cuda:
+            raise ValueError(f"{who}: {name} must be a tensor on a GPU, not on the host")
+    nx, ny = int(grid[2]), int(grid[5])
+    if sources.dim() != 2 or sources.shape[1] != 2:
+        raise ValueError(f"{who}: sources must be [S, 2]")
+    S = sources.shape[0]
+    if tuple(n.shape) != (ny, nx):
+        raise ValueError(f"{who}: n must be [ny, nx] of the grid")
+    if tuple(n_src.shape) != (S,):
+        raise ValueError(f"{who}: n_src must be [S]")
+    if T is None:
+        T = torch.full((S, ny, nx), float("nan"), dtype=torch.float64, device=n.device)
+    elif tuple(T.shape) != (S, ny, nx):
+        raise ValueError(f"{who}: T must be [S, ny, nx]")
+    filled = torch.zeros((S, ny, nx), dtype=torch.uint8, device=n.device)
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    torch.cuda.synchronize(n.device)               # the library works on the null stream
+    with torch.cuda.device(n.device):
+        check(lib().rtmi_eikonal_fill_dev(C.byref(ep), n.data_ptr(), S, sources.data_ptr(), n_src.data_ptr(), T.data_ptr(),
+                                          rounds.ctypes.data_as(_lib._ip), filled.data_ptr(), C.byref(st)))
+    res = {"T": T, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy(), "filled": filled}
+    if stats:
+        res["stats"] = eikonal_stats(st)
     return res
 
 
