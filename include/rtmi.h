@@ -1340,6 +1340,66 @@ int rtmi_eikonal_fill(const rtmi_eikonal_params *ep, const double *n, int64_t S,
 int rtmi_eikonal_fill_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src, const double *d_n_src,
                           double *d_T, int32_t *rounds, uint8_t *d_filled, rtmi_eikonal_stats *stats);
 
+/* The eikonal fill linearised about its result: the tangent dT = J dn and the adjoint g = J^T r.  DESIGN.md section 35.  The
+ * converged scheme is a causal network: every filled node took its value from at most one x-neighbour and one y-neighbour with a
+ * strictly smaller T.  Differentiating the update gives a sparse triangular system; solving it upwards in T is the tangent,
+ * downwards the adjoint, the gradient of any misfit of the table with respect to the medium, with no rays.  All on the device, in
+ * fp64, every product, sum, quotient and sqrt one rounded operation (raytracing_amd/csrc/rt_eikonal_lin.h holds the arithmetic,
+ * tests/eikonal_lin_ref.py restates it).  ep, n, src and n_src are those of the fill; T and filled [S][ny][nx] are what it
+ * returned.  Per source, with s = n and t = T at the node:
+ *   dead   s is an obstacle, or t is not finite: obstacles and unreached nodes
+ *   seed   not dead and filled is 0
+ *   ball   not dead, filled is 1 and the fill's ball rule holds for the node (on an input of NaN)
+ *   free   not dead, filled is 1, not of the ball
+ * As a neighbour a node reads t unless it is dead, and +inf if it is dead or outside the grid.  The coefficients of a free node
+ * from its neighbours' readings l (west), r (east), dn (south), up (north), with the fill's wx, wy, A:
+ *     a = min(l, r), the x-parent being east iff r < l;  b = min(dn, up), the y-parent being north iff up < dn
+ *     both +inf: no parent, ca = cb = cs = 0.  Else ta = a + gdx s;  tb = b + gdy s, and
+ *     b == +inf or ta <= b:       one-sided x:  ca = 1, cb = 0, cs = gdx
+ *     else a == +inf or tb <= a:  one-sided y:  ca = 0, cb = 1, cs = gdy
+ *     else B = a wx + b wy; e = a - b; d = A (s s) - (wx wy) (e e); q = d > 0 ? sqrt(d) : 0
+ *          q > 0:  tt = (B + q) / A;  ca = (wx (tt - a)) / q;  cb = (wy (tt - b)) / q;  cs = s / q
+ *          else:   one-sided y if tb < ta, else one-sided x
+ *     A branch that uses an axis names that axis' parent, unless the parent's reading is not strictly less than t: then the node
+ *     has no parent on that axis and the coefficient is 0 (gdx s can be absorbed in a, and a cycle would be possible).
+ * A node of the ball has no parent and cs = csrc = 0.5 sqrt(dx dx + dy dy), dx = X - xs, dy = Y - ys.  A seed has neither.
+ * Tangent.  dn [ny][nx], shared by the sources; dn_src [S] or NULL (+0.0); dT_seed [S][ny][nx] or NULL (+0.0), with which a
+ * caller chains the ray-based sensitivity of the covered nodes; dT [S][ny][nx]:
+ *     dead 0;  seed dT_seed;  ball (0.0 + cs dn) + csrc dn_src
+ *     free   acc = +0.0;  x-parent: acc = acc + ca dT[parent];  y-parent: acc = acc + cb dT[parent];  dT = acc + cs dn
+ * Adjoint.  r [S][ny][nx], ignored at dead nodes; lam [S][ny][nx]; g [S][ny][nx] or NULL; g_src [S] or NULL:
+ *     dead 0; else  acc = r;  for y in W, E, S, N, where y names this node as its parent on that axis: acc = acc + c lam[y], c
+ *     being y's ca (W, E) or cb (S, N);  lam = acc.  At a seed lam is the derivative with respect to the seed's T.
+ *     g = cs lam at free nodes and nodes of the ball, else +0.0;  g_src = the sum from +0.0 of csrc lam over the ball in node order
+ * Both maps are the unique fixed point of their gather, so their bits depend on no schedule; Gauss-Seidel sweeps find it, and so
+ * that rounds is defined too they are fixed: free nodes start from +0.0 (tangent), nodes that are not dead from r (adjoint); a
+ * round is four sweeps, y the outer loop, in the fill's orders for the tangent and in (-x, -y), (+x, -y), (+x, +y), (-x, +y) for
+ * the adjoint; the tangent visits the free nodes, the adjoint every node that is not dead; a node changes when the bits of its
+ * value change, so a NaN cannot spin.  No round runs where no node is free (rounds 0, clean); else rounds repeat until one
+ * changes nothing (clean) or max_rounds have run (0: 64).  rounds [S][2] as in the fill; where clean is 0 the values are those of
+ * the last sweep, NOT the fixed point.
+ *   stats    free_nodes = filled: the free nodes and the nodes of the ball, summed over the sources; unreached 0; changes;
+ *            rounds_max; kernel_ms; path: where a source's values, ca, cb, codes and the adjoint's masks of the neighbours that name
+ *            a node as a parent (26 bytes per node) fit 128 KiB they live in the workgroup's LDS, else in global memory (17 bytes
+ *            per node and source of work space beside the output, the adjoint 1 more; the tangent 8 more on both paths; sources
+ *            in groups of at most 1 GiB).  ep->reserved[0] = 1 takes the global path, for tests.
+ * The _dev forms take every array but rounds and stats as memory of the calling thread's current device; the host forms are
+ * upload, that, download: the same bits.  RTMI_ERR_ARG as in rtmi_eikonal_fill, and for a null T, filled, dn, dT, r or lam with S > 0.
+ * Not covered: several right-hand sides per source in one call; receivers off the nodes; a joint with rtmi_tomo_* handles or their
+ * LSQR loop; seeds that move; anisotropy; 3-D; fp32. */
+int rtmi_eikonal_tangent(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
+                         const double *T, const uint8_t *filled, const double *dn, const double *dn_src, const double *dT_seed,
+                         double *dT, int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_tangent_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src, const double *d_n_src,
+                             const double *d_T, const uint8_t *d_filled, const double *d_dn, const double *d_dn_src,
+                             const double *d_dT_seed, double *d_dT, int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_adjoint(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
+                         const double *T, const uint8_t *filled, const double *r, double *lam, double *g, double *g_src,
+                         int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_adjoint_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src, const double *d_n_src,
+                             const double *d_T, const uint8_t *d_filled, const double *d_r, double *d_lam, double *d_g,
+                             double *d_g_src, int32_t *rounds, rtmi_eikonal_stats *stats);
+
 /* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
  * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it
  * is the caller's job); the traces are stacked along the traveltime moveout of every grid node for every candidate origin time,

@@ -382,6 +382,14 @@ SYMBOLS = {
                                     C.POINTER(EikonalStats)]),
     "rtmi_eikonal_fill_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _ip,
                                         C.c_void_p, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_tangent": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), _dp, _dp, _dp,
+                                       _dp, _ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_tangent_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 8 +
+                                 [_ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_adjoint": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), _dp, _dp, _dp,
+                                       _dp, _ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_adjoint_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 8 +
+                                 [_ip, C.POINTER(EikonalStats)]),
     "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
                                     C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -11,19 +11,10 @@
 #include "rtmi_host.h"
 
 #include "rt_eikonal.h"
-
-#define RTMI_ALLOC(expr)                                                                                          \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) {                                                                                   \
-            (void)hipGetLastError();                                                                              \
-            return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": " + #expr + ": " + hipGetErrorString(e_)).c_str()); \
-        }                                                                                                         \
-    } while (0)
+#include "rt_eikonal_host.h"
 
 namespace {
 
-constexpr int kMaxBlock = 256;                          // lanes of a block: one wave per SIMD; a barrier costs more with more waves
 constexpr size_t kLdsBudget = (size_t)128 << 10;        // the LDS path's share of a CU's 160 KiB: T, n (8 bytes each) and the state per node
 constexpr size_t kLdsPerNode = 2 * sizeof(double) + 1;
 constexpr size_t kWorkBudget = (size_t)1 << 30;         // the global path's work space of one group of sources
@@ -43,17 +34,6 @@ struct EikArgs {
     uint8_t* state;             // global path: [S][ny][nx]
     unsigned long long* out;    // [S][kOutWords]
 };
-
-// the block's sum of v, the same in every lane; `slot` alternates between two calls in a row
-__device__ __forceinline__ unsigned long long block_sum(unsigned long long (*red)[kMaxBlock / 64], int slot, unsigned long long v) {
-    for (int off = 1; off < 64; off <<= 1) v += (unsigned long long)__shfl_xor((long long)v, off);
-    const int tid = (int)threadIdx.x, waves = (int)(blockDim.x >> 6);
-    if ((tid & 63) == 0) red[slot][tid >> 6] = v;
-    __syncthreads();
-    unsigned long long s = 0;
-    for (int k = 0; k < waves; k++) s += red[slot][k];
-    return s;
-}
 
 template <bool LDS> __global__ void __launch_bounds__(kMaxBlock) k_eikonal(const EikArgs a) {
     extern __shared__ double lds[];                     // LDS: [T | n | state]
@@ -142,23 +122,6 @@ template <bool LDS> __global__ void __launch_bounds__(kMaxBlock) k_eikonal(const
         o[2] = nfilled;
         o[3] = changes;
     }
-}
-
-// what every form of the call refuses before it touches the device
-int check_eikonal(const char* who, const rtmi_eikonal_params* ep, const void* n, int64_t S, const void* src, const void* n_src) {
-    RTMI_ARG(ep, "null ep");
-    RTMI_ARG(ep->nx >= 1 && ep->ny >= 1, "nx and ny must be >= 1");
-    RTMI_ARG((double)ep->nx * (double)ep->ny <= (double)(1L << 31), "more than 2^31 nodes per source");
-    RTMI_ARG(ep->gdx > 0.0 && ep->gdy > 0.0 && std::isfinite(ep->gdx) && std::isfinite(ep->gdy), "gdx and gdy must be finite and > 0");
-    RTMI_ARG(std::isfinite(ep->gx0) && std::isfinite(ep->gy0), "gx0 and gy0 must be finite");
-    RTMI_ARG(S >= 0, "S must be >= 0");
-    RTMI_ARG(S == 0 || n, "null n");
-    RTMI_ARG(S == 0 || src, "null src");
-    RTMI_ARG(S == 0 || n_src, "null n_src");
-    RTMI_ARG(ep->max_rounds >= 0, "max_rounds must be >= 0");
-    RTMI_ARG(std::isfinite(ep->ball), "ball must be finite");
-    RTMI_ARG(ep->reserved[0] == 0 || ep->reserved[0] == 1, "reserved[0] must be 0 or 1");
-    return RTMI_OK;
 }
 
 int eikonal_dev(const char* who, const rtmi_eikonal_params* ep, const double* d_n, int64_t S, const double* d_src, const double* d_n_src,

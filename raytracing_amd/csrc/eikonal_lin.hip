@@ -1,0 +1,396 @@
+// eikonal_lin.hip -- the eikonal fill linearised about its result: the tangent dT = J dn and the adjoint g = J^T r of the
+// converged Godunov scheme, as sweeps over the causal network of parents that the table defines (rtmi_eikonal_tangent,
+// rtmi_eikonal_adjoint and their _dev forms; include/rtmi.h).  The arithmetic of a node is
+// rt_eikonal_lin.h's; the kernel only decides who runs it when.
+//   k_eikonal_lin<LDS, ADJ>  one workgroup per source, the round loop inside.  A setup pass turns T, n and filled into each
+//                   node's ca, cb and code once; then the sweeps walk the anti-diagonals as k_eikonal does: a node's gather
+//                   reads the diagonals d - 1 and d + 1 only, so the lanes take one diagonal side by side and a block barrier
+//                   parts two diagonals: the serial sweep's bits.  The adjoint also turns the codes into each node's mask of the
+//                   neighbours that name it as a parent, so that its gather reads no neighbour's code.  LDS: the values, ca, cb,
+//                   the codes and the masks (26 bytes per node) live in the block's LDS; otherwise the values live in the output
+//                   table and the rest in a work space in global memory.  A node's constant term is read by that node alone and
+//                   stays in global memory on both paths: r itself (adjoint) or cs dn in a work space (tangent).
+// Every loop bound and every barrier is uniform across the block and max_rounds bounds the whole; no block waits for another.
+// No atomics on floating point; g_src is summed by one lane in node order.
+#include "rtmi_host.h"
+
+#include "rt_eikonal_lin.h"
+#include "rt_eikonal_host.h"
+
+namespace {
+
+constexpr size_t kLdsBudget = (size_t)128 << 10;        // the LDS path's share of a CU's 160 KiB
+constexpr size_t kLdsPerNode = 3 * sizeof(double) + 2;  // value, ca, cb, the code and the adjoint's mask
+constexpr size_t kWorkBudget = (size_t)1 << 30;         // the work space of one group of sources
+constexpr int kOutWords = 3;                            // per source: rounds | clean << 32, free and ball nodes, changes
+
+struct LinArgs {
+    rt::EikGrid g;
+    long nx, ny;
+    double ball;
+    int max_rounds;
+    const double* n;            // [ny][nx]
+    const double* src;          // [S][2]
+    const double* n_src;        // [S]
+    const double* T;            // [S][ny][nx]
+    const uint8_t* filled;      // [S][ny][nx]
+    const double* dn;           // tangent: [ny][nx]
+    const double* dn_src;       // tangent: [S] or NULL
+    const double* seed;         // tangent: [S][ny][nx] or NULL
+    const double* r;            // adjoint: [S][ny][nx]
+    double* v;                  // [S][ny][nx]: dT or lam
+    double* gout;               // adjoint: [S][ny][nx] or NULL
+    double* g_src;              // adjoint: [S] or NULL
+    double *ca, *cb;            // global path: [S][ny][nx]
+    uint8_t *code, *kids;       // global path: [S][ny][nx]; kids: adjoint
+    double* k;                  // tangent: [S][ny][nx]
+    unsigned long long* out;    // [S][kOutWords]
+};
+
+template <bool LDS, bool ADJ> __global__ void __launch_bounds__(kMaxBlock) k_eikonal_lin(const LinArgs a) {
+    extern __shared__ double lds[];                     // LDS: [v | ca | cb | code | kids]
+    __shared__ unsigned long long red[2][kMaxBlock / 64];
+    const int tid = (int)threadIdx.x, bd = (int)blockDim.x;
+    const long nx = a.nx, ny = a.ny, nn = nx * ny;
+    const size_t s = blockIdx.x;
+    const double xs = a.src[2 * s], ys = a.src[2 * s + 1], n_src = a.n_src[s];
+    const double* Ts = a.T + s * (size_t)nn;
+    const uint8_t* fs = a.filled + s * (size_t)nn;
+    double* vg = a.v + s * (size_t)nn;
+    double *v, *ca, *cb;
+    uint8_t *code, *kids;
+    if constexpr (LDS) {
+        v = lds;
+        ca = lds + nn;
+        cb = lds + 2 * nn;
+        code = (uint8_t*)(lds + 3 * nn);
+        kids = code + nn;
+    } else {
+        v = vg;
+        ca = a.ca + s * (size_t)nn;
+        cb = a.cb + s * (size_t)nn;
+        code = a.code + s * (size_t)nn;
+        kids = ADJ ? a.kids + s * (size_t)nn : nullptr;
+    }
+    // a node's constant term: r (adjoint), cs dn (tangent)
+    const double* kr;
+    if constexpr (ADJ) kr = a.r + s * (size_t)nn;
+    else kr = a.k + s * (size_t)nn;
+    long bi0 = 0, bi1 = -1, bj0 = 0, bj1 = -1;
+    if constexpr (ADJ) rt::eik_lin_ball_box(a.g, nx, ny, xs, ys, a.ball, &bi0, &bi1, &bj0, &bj1);
+    // the classes, the coefficients and the starting values
+    unsigned long long nfree = 0, nnodes = 0, nstray = 0;
+    for (long x = tid; x < nn; x += bd) {
+        const long i = x % nx, j = x / nx;
+        const rt::EikLinNode c = rt::eik_lin_node(a.g, nx, ny, i, j, a.n, Ts, fs, xs, ys, n_src, a.ball);
+        const uint8_t cls = rt::eik_lin_class(c.code);
+        ca[x] = c.ca;
+        cb[x] = c.cb;
+        code[x] = c.code;
+        if constexpr (ADJ) {
+            v[x] = cls == rt::kLinDead ? 0.0 : kr[x];
+            if (cls == rt::kLinBall && !(i >= bi0 && i <= bi1 && j >= bj0 && j <= bj1)) nstray++;
+        } else {
+            double k;
+            v[x] = rt::eik_lin_tangent_init(c, a.dn[x], a.dn_src ? a.dn_src[s] : 0.0, a.seed ? a.seed[s * (size_t)nn + x] : 0.0, &k);
+            a.k[s * (size_t)nn + x] = k;
+        }
+        if (cls >= rt::kLinFree) nnodes++;
+        if (cls == rt::kLinFree) nfree++;
+    }
+    nnodes = block_sum(red, 0, nnodes);
+    nstray = block_sum(red, 1, nstray);     // its barrier also parts the codes from the reads of the masks' pass
+    if constexpr (ADJ)
+        for (long x = tid; x < nn; x += bd) kids[x] = rt::eik_lin_kids(nx, ny, x % nx, x / nx, code);
+    nfree = block_sum(red, 0, nfree);       // its barrier also parts the starting values from the first diagonal's reads
+    int rounds = 0, clean = 1;
+    unsigned long long changes = 0;
+    if (nfree > 0) {
+        const long ndiag = nx + ny - 1;
+        while (rounds < a.max_rounds) {
+            rounds++;
+            unsigned long long mine = 0;
+            for (int k = 0; k < 4; k++) {
+                const bool xup = rt::eik_lin_xup(ADJ, k), yup = rt::eik_lin_yup(ADJ, k);
+                for (long d = 0; d < ndiag; d++) {
+                    // the diagonal p + q = d in the sweep's own coordinates: q in [q0, q1]
+                    const long q0 = d - (nx - 1) > 0 ? d - (nx - 1) : 0, q1 = d < ny - 1 ? d : ny - 1;
+                    for (long q = q0 + tid; q <= q1; q += bd) {
+                        const long p = d - q, i = xup ? p : nx - 1 - p, j = yup ? q : ny - 1 - q, x = j * nx + i;
+                        const uint8_t c = code[x];
+                        double t;
+                        if constexpr (ADJ) {
+                            if (rt::eik_lin_class(c) == rt::kLinDead) continue;
+                            t = rt::eik_lin_adjoint_gather(nx, x, kids[x], kr[x], ca, cb, v);
+                        } else {
+                            if (rt::eik_lin_class(c) != rt::kLinFree) continue;
+                            t = rt::eik_lin_tangent_gather(nx, x, c, ca[x], cb[x], kr[x], v);
+                        }
+                        if (rt::eik_bits(t) != rt::eik_bits(v[x])) {
+                            v[x] = t;
+                            mine++;
+                        }
+                    }
+                    __syncthreads();
+                }
+            }
+            const unsigned long long changed = block_sum(red, rounds & 1, mine);
+            changes += changed;
+            clean = changed == 0;
+            if (clean) break;
+        }
+    }
+    // the values out, and what the adjoint derives from them
+    for (long x = tid; x < nn; x += bd) {
+        const double val = v[x];
+        if constexpr (LDS) vg[x] = val;
+        if constexpr (ADJ) {
+            if (a.gout) {
+                double gv = 0.0;
+                if (rt::eik_lin_class(code[x]) >= rt::kLinFree)
+                    gv = rt::eik_lin_node(a.g, nx, ny, x % nx, x / nx, a.n, Ts, fs, xs, ys, n_src, a.ball).cs * val;
+                a.gout[s * (size_t)nn + x] = gv;
+            }
+        }
+    }
+    if constexpr (ADJ) {
+        if (a.g_src && tid == 0) {
+            // nstray is 0 unless the box missed a node of the ball: then every node is looked at
+            const long i0 = nstray ? 0 : bi0, i1 = nstray ? nx - 1 : bi1, j0 = nstray ? 0 : bj0, j1 = nstray ? ny - 1 : bj1;
+            double acc = 0.0;
+            for (long j = j0; j <= j1; j++)
+                for (long i = i0; i <= i1; i++)
+                    if (rt::eik_lin_class(code[j * nx + i]) == rt::kLinBall) acc = acc + rt::eik_lin_csrc(a.g, i, j, xs, ys) * v[j * nx + i];
+            a.g_src[s] = acc;
+        }
+    }
+    if (tid == 0) {
+        unsigned long long* o = a.out + s * kOutWords;
+        o[0] = (unsigned long long)(unsigned)rounds | (unsigned long long)(unsigned)clean << 32;
+        o[1] = nnodes;
+        o[2] = changes;
+    }
+}
+
+// One call on device memory: a holds the caller's pointers for all S sources
+template <bool ADJ> int lin_dev(const char* who, const rtmi_eikonal_params* ep, int64_t S, LinArgs a, int32_t* rounds,
+                                rtmi_eikonal_stats* stats) {
+    rtmi_eikonal_stats total{};
+    const size_t nn = (size_t)ep->nx * (size_t)ep->ny;
+    const size_t lds_bytes = (nn * kLdsPerNode + 7) / 8 * 8;
+    // reserved[0]: 1 takes the global path where the LDS path would do, for tests; no result depends on it
+    const bool lds = lds_bytes <= kLdsBudget && ep->reserved[0] != 1;
+    total.path = lds ? RTMI_EIKONAL_LDS : RTMI_EIKONAL_GLOBAL;
+    if (S > 0) {
+        const long diag = (long)std::min(ep->nx, ep->ny);
+        const int block = (int)std::min<long>(kMaxBlock, (diag + 63) / 64 * 64);
+        // the work space per node and source: ca, cb, the code and the adjoint's mask off the LDS path, and the tangent's constant term
+        const size_t per = (lds ? 0 : 2 * sizeof(double) + 1) + (ADJ ? (lds ? 0 : 1) : sizeof(double));
+        const size_t group = per ? std::min((size_t)S, std::max<size_t>(1, kWorkBudget / (nn * per))) : (size_t)S;
+        DevMem mem;
+        a.g = rt::eik_grid(ep->gx0, ep->gdx, ep->gy0, ep->gdy);
+        a.nx = (long)ep->nx;
+        a.ny = (long)ep->ny;
+        a.ball = ep->ball;
+        a.max_rounds = ep->max_rounds > 0 ? ep->max_rounds : rt::kEikDefaultRounds;
+        if (!lds) {
+            RTMI_ALLOC(mem.get(&a.ca, group * nn * sizeof(double)));
+            RTMI_ALLOC(mem.get(&a.cb, group * nn * sizeof(double)));
+            RTMI_ALLOC(mem.get(&a.code, group * nn));
+            if (ADJ) RTMI_ALLOC(mem.get(&a.kids, group * nn));
+        }
+        if (!ADJ) RTMI_ALLOC(mem.get(&a.k, group * nn * sizeof(double)));
+        unsigned long long* d_out = nullptr;
+        RTMI_ALLOC(mem.get(&d_out, (size_t)S * kOutWords * sizeof(unsigned long long)));
+        if (lds && lds_bytes > 65536)
+            RTMI_HIP(hipFuncSetAttribute((const void*)k_eikonal_lin<true, ADJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+        const LinArgs all = a;
+        EventMarks<2> marks;
+        RTMI_HIP(marks.create());
+        RTMI_HIP(marks.mark(0));
+        for (size_t s0 = 0; s0 < (size_t)S; s0 += group) {
+            const size_t gs = std::min(group, (size_t)S - s0);
+            a.src = all.src + 2 * s0;
+            a.n_src = all.n_src + s0;
+            a.T = all.T + s0 * nn;
+            a.filled = all.filled + s0 * nn;
+            a.dn_src = all.dn_src ? all.dn_src + s0 : nullptr;
+            a.seed = all.seed ? all.seed + s0 * nn : nullptr;
+            a.r = all.r ? all.r + s0 * nn : nullptr;
+            a.v = all.v + s0 * nn;
+            a.gout = all.gout ? all.gout + s0 * nn : nullptr;
+            a.g_src = all.g_src ? all.g_src + s0 : nullptr;
+            a.out = d_out + s0 * kOutWords;
+            if (lds) hipLaunchKernelGGL((k_eikonal_lin<true, ADJ>), dim3((unsigned)gs), dim3(block), lds_bytes, nullptr, a);
+            else hipLaunchKernelGGL((k_eikonal_lin<false, ADJ>), dim3((unsigned)gs), dim3(block), 0, nullptr, a);
+            RTMI_HIP(hipGetLastError());
+        }
+        RTMI_HIP(marks.mark(1));
+        RTMI_HIP(marks.wait(1));
+        RTMI_HIP(marks.ms(0, 1, &total.kernel_ms));
+        std::vector<unsigned long long> out((size_t)S * kOutWords);
+        RTMI_HIP(hipMemcpy(out.data(), d_out, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < (size_t)S; s++) {
+            const unsigned long long* o = &out[s * kOutWords];
+            const int32_t r = (int32_t)(o[0] & 0xffffffffull), clean = (int32_t)(o[0] >> 32);
+            if (rounds) {
+                rounds[2 * s] = r;
+                rounds[2 * s + 1] = clean;
+            }
+            total.free_nodes += (int64_t)o[1];
+            total.changes += (int64_t)o[2];
+            total.rounds_max = std::max(total.rounds_max, r);
+        }
+        total.filled = total.free_nodes;
+    }
+    if (stats) *stats = total;
+    return RTMI_OK;
+}
+
+// the pointers every form needs with S > 0, after check_eikonal
+int check_lin(const char* who, const void* T, const void* filled, const void* in, const char* in_name, const void* out, const char* out_name) {
+    RTMI_ARG(T, "null T");
+    RTMI_ARG(filled, "null filled");
+    RTMI_ARG(in, std::string("null ") + in_name);
+    RTMI_ARG(out, std::string("null ") + out_name);
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_eikonal_tangent_dev(const rtmi_eikonal_params* ep, const double* d_n, int64_t S, const double* d_src,
+                                         const double* d_n_src, const double* d_T, const uint8_t* d_filled, const double* d_dn,
+                                         const double* d_dn_src, const double* d_dT_seed, double* d_dT, int32_t* rounds,
+                                         rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_tangent_dev";
+    RTMI_RC(check_eikonal(who, ep, d_n, S, d_src, d_n_src));
+    LinArgs a{};
+    if (S > 0) {
+        RTMI_RC(check_lin(who, d_T, d_filled, d_dn, "dn", d_dT, "dT"));
+        int device = 0;
+        RTMI_HIP(hipGetDevice(&device));
+        const size_t nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn * sizeof(double);
+        RTMI_RC(check_device_pointer(device, who, d_n, nn * sizeof(double), "d_n"));
+        RTMI_RC(check_device_pointer(device, who, d_src, (size_t)S * 2 * sizeof(double), "d_src"));
+        RTMI_RC(check_device_pointer(device, who, d_n_src, (size_t)S * sizeof(double), "d_n_src"));
+        RTMI_RC(check_device_pointer(device, who, d_T, tab, "d_T"));
+        RTMI_RC(check_device_pointer(device, who, d_filled, (size_t)S * nn, "d_filled"));
+        RTMI_RC(check_device_pointer(device, who, d_dn, nn * sizeof(double), "d_dn"));
+        if (d_dn_src) RTMI_RC(check_device_pointer(device, who, d_dn_src, (size_t)S * sizeof(double), "d_dn_src"));
+        if (d_dT_seed) RTMI_RC(check_device_pointer(device, who, d_dT_seed, tab, "d_dT_seed"));
+        RTMI_RC(check_device_pointer(device, who, d_dT, tab, "d_dT"));
+    }
+    a.n = d_n; a.src = d_src; a.n_src = d_n_src; a.T = d_T; a.filled = d_filled;
+    a.dn = d_dn; a.dn_src = d_dn_src; a.seed = d_dT_seed; a.v = d_dT;
+    return lin_dev<false>(who, ep, S, a, rounds, stats);
+}
+
+RTMI_EXPORT int rtmi_eikonal_adjoint_dev(const rtmi_eikonal_params* ep, const double* d_n, int64_t S, const double* d_src,
+                                         const double* d_n_src, const double* d_T, const uint8_t* d_filled, const double* d_r,
+                                         double* d_lam, double* d_g, double* d_g_src, int32_t* rounds, rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_adjoint_dev";
+    RTMI_RC(check_eikonal(who, ep, d_n, S, d_src, d_n_src));
+    LinArgs a{};
+    if (S > 0) {
+        RTMI_RC(check_lin(who, d_T, d_filled, d_r, "r", d_lam, "lam"));
+        int device = 0;
+        RTMI_HIP(hipGetDevice(&device));
+        const size_t nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn * sizeof(double);
+        RTMI_RC(check_device_pointer(device, who, d_n, nn * sizeof(double), "d_n"));
+        RTMI_RC(check_device_pointer(device, who, d_src, (size_t)S * 2 * sizeof(double), "d_src"));
+        RTMI_RC(check_device_pointer(device, who, d_n_src, (size_t)S * sizeof(double), "d_n_src"));
+        RTMI_RC(check_device_pointer(device, who, d_T, tab, "d_T"));
+        RTMI_RC(check_device_pointer(device, who, d_filled, (size_t)S * nn, "d_filled"));
+        RTMI_RC(check_device_pointer(device, who, d_r, tab, "d_r"));
+        RTMI_RC(check_device_pointer(device, who, d_lam, tab, "d_lam"));
+        if (d_g) RTMI_RC(check_device_pointer(device, who, d_g, tab, "d_g"));
+        if (d_g_src) RTMI_RC(check_device_pointer(device, who, d_g_src, (size_t)S * sizeof(double), "d_g_src"));
+    }
+    a.n = d_n; a.src = d_src; a.n_src = d_n_src; a.T = d_T; a.filled = d_filled;
+    a.r = d_r; a.v = d_lam; a.gout = d_g; a.g_src = d_g_src;
+    return lin_dev<true>(who, ep, S, a, rounds, stats);
+}
+
+namespace {
+
+// the inputs both host forms upload
+struct LinUpload {
+    double *n = nullptr, *src = nullptr, *n_src = nullptr, *T = nullptr;
+    uint8_t* filled = nullptr;
+};
+
+int upload_lin(const char* who, DevMem& mem, const rtmi_eikonal_params* ep, int64_t S, const double* n, const double* src,
+               const double* n_src, const double* T, const uint8_t* filled, LinUpload* u) {
+    const size_t nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn;
+    RTMI_ALLOC(mem.get(&u->n, nn * sizeof(double)));
+    RTMI_ALLOC(mem.get(&u->src, (size_t)S * 2 * sizeof(double)));
+    RTMI_ALLOC(mem.get(&u->n_src, (size_t)S * sizeof(double)));
+    RTMI_ALLOC(mem.get(&u->T, tab * sizeof(double)));
+    RTMI_ALLOC(mem.get(&u->filled, tab));
+    RTMI_HIP(hipMemcpy(u->n, n, nn * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(u->src, src, (size_t)S * 2 * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(u->n_src, n_src, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(u->T, T, tab * sizeof(double), hipMemcpyHostToDevice));
+    RTMI_HIP(hipMemcpy(u->filled, filled, tab, hipMemcpyHostToDevice));
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_eikonal_tangent(const rtmi_eikonal_params* ep, const double* n, int64_t S, const double* src, const double* n_src,
+                                     const double* T, const uint8_t* filled, const double* dn, const double* dn_src,
+                                     const double* dT_seed, double* dT, int32_t* rounds, rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_tangent";
+    RTMI_RC(check_eikonal(who, ep, n, S, src, n_src));
+    LinArgs a{};
+    if (S == 0) return lin_dev<false>(who, ep, 0, a, rounds, stats);
+    RTMI_RC(check_lin(who, T, filled, dn, "dn", dT, "dT"));
+    const size_t nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn;
+    DevMem mem;
+    LinUpload u;
+    RTMI_RC(upload_lin(who, mem, ep, S, n, src, n_src, T, filled, &u));
+    double *d_dn = nullptr, *d_dn_src = nullptr, *d_seed = nullptr, *d_dT = nullptr;
+    RTMI_ALLOC(mem.get(&d_dn, nn * sizeof(double)));
+    RTMI_ALLOC(mem.get(&d_dT, tab * sizeof(double)));
+    RTMI_HIP(hipMemcpy(d_dn, dn, nn * sizeof(double), hipMemcpyHostToDevice));
+    if (dn_src) {
+        RTMI_ALLOC(mem.get(&d_dn_src, (size_t)S * sizeof(double)));
+        RTMI_HIP(hipMemcpy(d_dn_src, dn_src, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (dT_seed) {
+        RTMI_ALLOC(mem.get(&d_seed, tab * sizeof(double)));
+        RTMI_HIP(hipMemcpy(d_seed, dT_seed, tab * sizeof(double), hipMemcpyHostToDevice));
+    }
+    a.n = u.n; a.src = u.src; a.n_src = u.n_src; a.T = u.T; a.filled = u.filled;
+    a.dn = d_dn; a.dn_src = d_dn_src; a.seed = d_seed; a.v = d_dT;
+    RTMI_RC(lin_dev<false>(who, ep, S, a, rounds, stats));
+    RTMI_HIP(hipMemcpy(dT, d_dT, tab * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_eikonal_adjoint(const rtmi_eikonal_params* ep, const double* n, int64_t S, const double* src, const double* n_src,
+                                     const double* T, const uint8_t* filled, const double* r, double* lam, double* g, double* g_src,
+                                     int32_t* rounds, rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_adjoint";
+    RTMI_RC(check_eikonal(who, ep, n, S, src, n_src));
+    LinArgs a{};
+    if (S == 0) return lin_dev<true>(who, ep, 0, a, rounds, stats);
+    RTMI_RC(check_lin(who, T, filled, r, "r", lam, "lam"));
+    const size_t nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn;
+    DevMem mem;
+    LinUpload u;
+    RTMI_RC(upload_lin(who, mem, ep, S, n, src, n_src, T, filled, &u));
+    double *d_r = nullptr, *d_lam = nullptr, *d_g = nullptr, *d_g_src = nullptr;
+    RTMI_ALLOC(mem.get(&d_r, tab * sizeof(double)));
+    RTMI_ALLOC(mem.get(&d_lam, tab * sizeof(double)));
+    if (g) RTMI_ALLOC(mem.get(&d_g, tab * sizeof(double)));
+    if (g_src) RTMI_ALLOC(mem.get(&d_g_src, (size_t)S * sizeof(double)));
+    RTMI_HIP(hipMemcpy(d_r, r, tab * sizeof(double), hipMemcpyHostToDevice));
+    a.n = u.n; a.src = u.src; a.n_src = u.n_src; a.T = u.T; a.filled = u.filled;
+    a.r = d_r; a.v = d_lam; a.gout = d_g; a.g_src = d_g_src;
+    RTMI_RC(lin_dev<true>(who, ep, S, a, rounds, stats));
+    RTMI_HIP(hipMemcpy(lam, d_lam, tab * sizeof(double), hipMemcpyDeviceToHost));
+    if (g) RTMI_HIP(hipMemcpy(g, d_g, tab * sizeof(double), hipMemcpyDeviceToHost));
+    if (g_src) RTMI_HIP(hipMemcpy(g_src, d_g_src, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}

@@ -1741,6 +1741,230 @@ def eikonal_fill_device(field_or_n, sources, grid, T=None, *, n_src=None, ball=2
     return res
 
 
+def _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src):
+    """(n, src, n_src, T, filled, shape) of a host call of the linearised fill, contiguous and checked"""
+    src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
+    S, nx, ny = len(src), int(grid[2]), int(grid[5])
+    n, n_src = _eikonal_medium(who, field_or_n, src, grid, n_src)
+    n = np.ascontiguousarray(n, dtype=np.float64)
+    ns = np.ascontiguousarray(n_src, dtype=np.float64).reshape(-1)
+    shape = (S, max(ny, 0), max(nx, 0))
+    if nx >= 1 and ny >= 1 and n.shape != (ny, nx):
+        raise ValueError(f"{who}: n must be [ny, nx] of the grid")
+    if len(ns) != S:
+        raise ValueError(f"{who}: n_src must be [S]")
+    T = np.ascontiguousarray(fill_result["T"], dtype=np.float64)
+    filled = np.ascontiguousarray(fill_result["filled"], dtype=np.uint8)
+    if T.shape != shape or filled.shape != shape:
+        raise ValueError(f"{who}: fill_result's T and filled must be [S, ny, nx]")
+    return n, src, ns, T, filled, shape
+
+
+def _eikonal_lin_array(who, name, a, shape):
+    """a as a contiguous fp64 array of `shape`, or None"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"{who}: {name} must be {list(shape)}")
+    return a
+
+
+def eikonal_tangent(field_or_n, sources, grid, fill_result, dn, *, n_src=None, dn_src=None, dT_seed=None, ball=2.0, max_rounds=0,
+                    stats=False, _global_path=False):
+    """The tangent of the eikonal fill, dT = J dn, on the device (rtmi_eikonal_tangent, include/rtmi.h): what a
+    perturbation dn [ny, nx] of the slowness at the nodes, dn_src [S] of the slowness at the sources (None: 0) and dT_seed
+    [S, ny, nx] of the seeds (None: 0) does to the table that eikonal_fill returned.  field_or_n, sources, grid, n_src, ball as in
+    the eikonal_fill call that gave fill_result (its dict: T and filled are read).  Returns a dict: dT [S, ny, nx] (0 at
+    obstacles and unreached nodes, dT_seed at seeds), rounds and converged [S], and with stats=True 'stats'.  Where converged
+    is 0 the values are not final: raise max_rounds."""
+    who = "eikonal_tangent"
+    n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
+    S = shape[0]
+    dn = _eikonal_lin_array(who, "dn", dn, shape[1:])
+    dn_src = _eikonal_lin_array(who, "dn_src", dn_src, (S,))
+    dT_seed = _eikonal_lin_array(who, "dT_seed", dT_seed, shape)
+    dT = np.zeros(shape)
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    check(lib().rtmi_eikonal_tangent(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T), filled.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                     dptr(dn), dptr(dn_src), dptr(dT_seed), dptr(dT), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    res = {"dT": dT, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy()}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def eikonal_adjoint(field_or_n, sources, grid, fill_result, r, *, n_src=None, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+    """The adjoint of the eikonal fill, g = J^T r, on the device (rtmi_eikonal_adjoint): the gradient with respect to
+    the medium of any misfit of the table whose derivative with respect to T is r [S, ny, nx] (ignored at obstacles and
+    unreached nodes), by the adjoint-state method, with no rays.  Arguments as in eikonal_tangent.  Returns a dict:
+      g [S, ny, nx]      the gradient with respect to n at the nodes, per source (sum over the sources for the whole misfit)
+      g_src [S]          the gradient with respect to n_src
+      lam [S, ny, nx]    the adjoint state; at a seed it is the gradient with respect to the seed's T
+      rounds, converged  [S], as in eikonal_tangent
+    and with stats=True 'stats'."""
+    who = "eikonal_adjoint"
+    n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
+    S = shape[0]
+    r = _eikonal_lin_array(who, "r", r, shape)
+    lam, g, g_src = np.zeros(shape), np.zeros(shape), np.zeros(S)
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    check(lib().rtmi_eikonal_adjoint(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T), filled.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                     dptr(r), dptr(lam), dptr(g), dptr(g_src), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    res = {"lam": lam, "g": g, "g_src": g_src, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy()}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def _eikonal_lin_tensors(who, tensors):
+    """Check the torch tensors of a device call of the linearised fill: (name, tensor or None, dtype, shape) each"""
+    import torch
+    device = None
+    for name, a, dtype, shape in tensors:
+        if a is None:
+            continue
+        if not isinstance(a, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a torch tensor")
+        if a.dtype != dtype:
+            raise TypeError(f"{who}: {name} must be {dtype}")
+        if not a.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+        if not a.is_cuda:
+            raise ValueError(f"{who}: {name} must be a tensor on a GPU, not on the host")
+        if device is not None and a.device != device:
+            raise ValueError(f"{who}: {name} is on another device than n")
+        device = a.device
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{who}: {name} must be {list(shape)}")
+
+
+def eikonal_tangent_device(n, sources, grid, fill_result, dn, *, n_src, dn_src=None, dT_seed=None, ball=2.0, max_rounds=0,
+                           stats=False, _global_path=False):
+    """eikonal_tangent on torch tensors of one GPU, with no host copy (rtmi_eikonal_tangent_dev): n and dn [ny, nx], sources
+    [S, 2], n_src and dn_src [S], dT_seed [S, ny, nx] in fp64, contiguous; fill_result is eikonal_fill_device's dict (T fp64,
+    filled uint8, on the device).  dT is a new tensor on the device; rounds and converged are numpy arrays.  The same bits."""
+    import torch
+    who = "eikonal_tangent_device"
+    if not isinstance(sources, torch.Tensor) or sources.dim() != 2:
+        raise ValueError(f"{who}: sources must be a torch tensor [S, 2]")
+    S, nx, ny = sources.shape[0], int(grid[2]), int(grid[5])
+    f64 = torch.float64
+    _eikonal_lin_tensors(who, [("n", n, f64, (ny, nx)), ("sources", sources, f64, (S, 2)), ("n_src", n_src, f64, (S,)),
+                               ("T", fill_result["T"], f64, (S, ny, nx)), ("filled", fill_result["filled"], torch.uint8, (S, ny, nx)),
+                               ("dn", dn, f64, (ny, nx)), ("dn_src", dn_src, f64, (S,)), ("dT_seed", dT_seed, f64, (S, ny, nx))])
+    dT = torch.zeros((S, ny, nx), dtype=f64, device=n.device)
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    opt = lambda a: None if a is None else a.data_ptr()      # noqa: E731
+    torch.cuda.synchronize(n.device)               # the library works on the null stream
+    with torch.cuda.device(n.device):
+        check(lib().rtmi_eikonal_tangent_dev(C.byref(ep), n.data_ptr(), S, sources.data_ptr(), n_src.data_ptr(),
+                                             fill_result["T"].data_ptr(), fill_result["filled"].data_ptr(), dn.data_ptr(), opt(dn_src),
+                                             opt(dT_seed), dT.data_ptr(), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    res = {"dT": dT, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy()}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def eikonal_adjoint_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+    """eikonal_adjoint on torch tensors of one GPU (rtmi_eikonal_adjoint_dev): arguments as in eikonal_tangent_device, r
+    [S, ny, nx].  lam, g and g_src are new tensors on the device; rounds and converged are numpy arrays.  The same bits."""
+    import torch
+    who = "eikonal_adjoint_device"
+    if not isinstance(sources, torch.Tensor) or sources.dim() != 2:
+        raise ValueError(f"{who}: sources must be a torch tensor [S, 2]")
+    S, nx, ny = sources.shape[0], int(grid[2]), int(grid[5])
+    f64 = torch.float64
+    _eikonal_lin_tensors(who, [("n", n, f64, (ny, nx)), ("sources", sources, f64, (S, 2)), ("n_src", n_src, f64, (S,)),
+                               ("T", fill_result["T"], f64, (S, ny, nx)), ("filled", fill_result["filled"], torch.uint8, (S, ny, nx)),
+                               ("r", r, f64, (S, ny, nx))])
+    lam = torch.zeros((S, ny, nx), dtype=f64, device=n.device)
+    g = torch.zeros((S, ny, nx), dtype=f64, device=n.device)
+    g_src = torch.zeros((S,), dtype=f64, device=n.device)
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    torch.cuda.synchronize(n.device)               # the library works on the null stream
+    with torch.cuda.device(n.device):
+        check(lib().rtmi_eikonal_adjoint_dev(C.byref(ep), n.data_ptr(), S, sources.data_ptr(), n_src.data_ptr(),
+                                             fill_result["T"].data_ptr(), fill_result["filled"].data_ptr(), r.data_ptr(), lam.data_ptr(),
+                                             g.data_ptr(), g_src.data_ptr(), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    res = {"lam": lam, "g": g, "g_src": g_src, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy()}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def eikonal_source_weights(sources, grid):
+    """The bilinear weights of each source's cell: (idx [S, 4] node indices, w [S, 4]); w is all 0 for a source outside the grid"""
+    gx0, gdx, nx, gy0, gdy, ny = grid
+    nx, ny = int(nx), int(ny)
+    src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
+    u, v = (src[:, 0] - float(gx0)) / float(gdx), (src[:, 1] - float(gy0)) / float(gdy)
+    inside = (u >= 0) & (u <= nx - 1) & (v >= 0) & (v <= ny - 1)
+    i0 = np.clip(np.floor(np.where(inside, u, 0.0)).astype(np.int64), 0, max(nx - 2, 0))
+    j0 = np.clip(np.floor(np.where(inside, v, 0.0)).astype(np.int64), 0, max(ny - 2, 0))
+    i1, j1 = np.minimum(i0 + 1, nx - 1), np.minimum(j0 + 1, ny - 1)
+    fu, fv = np.where(i1 > i0, u - i0, 0.0), np.where(j1 > j0, v - j0, 0.0)
+    idx = np.stack([j0 * nx + i0, j0 * nx + i1, j1 * nx + i0, j1 * nx + i1], axis=1)
+    w = np.stack([(1 - fu) * (1 - fv), fu * (1 - fv), (1 - fu) * fv, fu * fv], axis=1) * inside[:, None]
+    return idx, w
+
+
+def eikonal_operator(field_or_n, sources, grid, fill_result, receivers, *, n_src=None, ball=2.0, max_rounds=0):
+    """The Jacobian of the filled tables at receiver nodes as a scipy LinearOperator, matrix-free, for LSQR or Gauss-Newton
+    (DESIGN.md 35): it maps dn [ny nx] to dT at `receivers` (node indices iy nx + ix, [R]) of every source; row s R + k is source
+    s, receiver k.  matvec is eikonal_tangent_device and a gather; rmatvec a scatter, eikonal_adjoint_device and a sum over the
+    sources.  n_src follows dn through the bilinear weights of the source's cell where the source lies inside the grid, else it
+    is held fixed.  field_or_n, sources, grid, n_src, ball as in the eikonal_fill call that gave fill_result; everything is
+    uploaded once.  A sweep that does not converge within max_rounds raises.  Receivers off the nodes: compose an interpolation."""
+    import torch
+    from scipy.sparse.linalg import LinearOperator
+    who = "eikonal_operator"
+    n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
+    S, ny, nx = shape
+    rec = np.asarray(receivers, dtype=np.int64).reshape(-1)
+    if len(rec) and (rec.min() < 0 or rec.max() >= ny * nx):
+        raise ValueError(f"{who}: receivers must be node indices in [0, ny nx)")
+    dev = torch.device("cuda")
+    up = lambda a: torch.as_tensor(a, device=dev)      # noqa: E731
+    d_n, d_src, d_ns, d_rec = up(n), up(src), up(ns), up(rec)
+    d_fill = {"T": up(T), "filled": up(filled)}
+    idx, w = eikonal_source_weights(src, grid)
+    d_idx, d_w = up(idx), up(w)
+    kw = dict(n_src=d_ns, ball=ball, max_rounds=max_rounds)
+
+    def done(res, what):
+        if not res["converged"].all():
+            raise RuntimeError(f"{who}: the {what} sweeps did not converge within max_rounds")
+        return res
+
+    def matvec(x):
+        d_dn = up(np.ascontiguousarray(x, dtype=np.float64).reshape(ny, nx))
+        d_dns = (d_dn.reshape(-1)[d_idx] * d_w).sum(dim=1)
+        res = done(eikonal_tangent_device(d_n, d_src, grid, d_fill, d_dn, dn_src=d_dns, **kw), "tangent")
+        return res["dT"].reshape(S, -1)[:, d_rec].reshape(-1).cpu().numpy()
+
+    def rmatvec(y):
+        d_r = torch.zeros((S, ny * nx), dtype=torch.float64, device=dev)
+        d_y = up(np.ascontiguousarray(y, dtype=np.float64).reshape(S, -1))
+        d_r.index_put_((torch.arange(S, device=dev)[:, None].expand(S, len(rec)), d_rec[None, :].expand(S, len(rec))), d_y,
+                       accumulate=True)
+        res = done(eikonal_adjoint_device(d_n, d_src, grid, d_fill, d_r.reshape(S, ny, nx), **kw), "adjoint")
+        g = res["g"].sum(dim=0).reshape(-1)
+        g.index_put_((d_idx.reshape(-1),), (res["g_src"][:, None] * d_w).reshape(-1), accumulate=True)
+        return g.cpu().numpy()
+
+    return LinearOperator((S * len(rec), ny * nx), matvec=matvec, rmatvec=rmatvec, dtype=np.float64)
+
+
 def beam_params(grid, eps, cutoff=None, max_width=None, edge_taper=0):
     """rtmi_beam_params of grid = (gx0, gdx, nx, gy0, gdy, ny) and the beam parameter eps; None / 0 take the library's defaults"""
     gx0, gdx, nx, gy0, gdy, ny = grid
