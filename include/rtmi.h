@@ -1385,8 +1385,8 @@ int rtmi_eikonal_fill_dev(const rtmi_eikonal_params *ep, const double *d_n, int6
  *            in groups of at most 1 GiB).  ep->reserved[0] = 1 takes the global path, for tests.
  * The _dev forms take every array but rounds and stats as memory of the calling thread's current device; the host forms are
  * upload, that, download: the same bits.  RTMI_ERR_ARG as in rtmi_eikonal_fill, and for a null T, filled, dn, dT, r or lam with S > 0.
- * Not covered: several right-hand sides per source in one call; receivers off the nodes; a joint with rtmi_tomo_* handles or their
- * LSQR loop; seeds that move; anisotropy; 3-D; fp32. */
+ * Not covered: several right-hand sides per source in one call; seeds that move; anisotropy; 3-D; fp32.  Receivers off the
+ * nodes and the LSQR loop on the device: rtmi_eikonal_tomo_* below. */
 int rtmi_eikonal_tangent(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
                          const double *T, const uint8_t *filled, const double *dn, const double *dn_src, const double *dT_seed,
                          double *dT, int32_t *rounds, rtmi_eikonal_stats *stats);
@@ -1399,6 +1399,90 @@ int rtmi_eikonal_adjoint(const rtmi_eikonal_params *ep, const double *n, int64_t
 int rtmi_eikonal_adjoint_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src, const double *d_n_src,
                              const double *d_T, const uint8_t *d_filled, const double *d_r, double *d_lam, double *d_g,
                              double *d_g_src, int32_t *rounds, rtmi_eikonal_stats *stats);
+
+/* First-arrival eikonal tomography that stays on the device: a handle over the linearised fill with receivers anywhere on the
+ * grid, its two products defined bit for bit, and LSQR on them.  DESIGN.md section 36.  raytracing_amd/csrc/rt_eikonal_tomo.h
+ * holds the host arithmetic, tests/eikonal_tomo_ref.py restates everything.  All fp64; every product and sum is one rounded
+ * operation, no contraction.
+ *   ep, n, src, n_src   those of rtmi_eikonal_fill (S >= 1 here)
+ *   rec [R][2]          receiver coordinates (x, y), shared by all sources; row s R + k is source s, receiver k
+ *   T, filled           [S][ny][nx], what a fill returned (this is how a table seeded by rays enters); both NULL: the handle
+ *                       fills its own tables from the ball (an all-NaN input) with rtmi_eikonal_fill_dev.  Only such a handle
+ *                       can be re-linearised.
+ * Everything is uploaded once and stays on the calling thread's current device, the handle's from then on.
+ * Cell weights of a point (x, y):  u = (x - gx0) / gdx;  i0 = min(max(floor(u), 0), max(nx - 2, 0));  i1 = min(i0 + 1, nx - 1);
+ *     fu = i1 > i0 ? u - i0 : 0;  the same in y (v, j0, j1, fv).  Corners in the order (i0, j0), (i1, j0), (i0, j1), (i1, j1) with
+ *     the weights (1 - fu)(1 - fv), fu (1 - fv), (1 - fu) fv, fu fv.  A source with u outside [0, nx - 1] or v outside [0, ny - 1]
+ *     has i0 = j0 = 0 and four weights +0.0: its n_src does not follow the model.
+ * sample(v, p) = ((w0 v0 + w1 v1) + w2 v2) + w3 v3, v_c the value at corner c of p.
+ * Live rows: row (s, k) is live iff none of the four corner nodes of receiver k is dead for source s (dead as in
+ *     rtmi_eikonal_tangent: an obstacle, or a T that is not finite).  The forward product of a dead row is +0.0, the transpose
+ *     does not read a dead row's entry, and the residual of a dead row is +0.0.
+ * Forward y = A dn:  dn_src[s] = sample(dn, src_s), +0.0 for a source outside the grid;
+ *     dT = rtmi_eikonal_tangent_dev(..., dn, dn_src, NULL);  y[s R + k] = sample(dT_s, rec_k).
+ * Transpose G = A^T y:
+ *     r_s[x] = the sum from +0.0, over the (receiver, corner) pairs whose node is x and whose row (s, k) is live, in increasing
+ *              4 k + corner, of fl(w y[s R + k]); +0.0 at a node no receiver touches
+ *     lam, g, g_src = rtmi_eikonal_adjoint_dev(..., r)
+ *     G[x] = the sum from +0.0 of g_s[x] over s in increasing order, then of fl(w g_src[s]) over the (source, corner) pairs whose
+ *            node is x, sources inside the grid only, in increasing 4 s + corner
+ * A tangent or adjoint call that reports clean 0 for any source makes the product return RTMI_ERR_STATE, naming the sweep;
+ * nothing is written.  The sums are gathers in one fixed order: no floating-point atomics, the same bits in every schedule.
+ * Residual: res[s R + k] = fl(pick - sample(T_s, rec_k)) on a live row whose pick is not NaN (a NaN marks an absent observation),
+ *     else +0.0.
+ * rtmi_eikonal_tomo_lsqr: the loop of rtmi_kirchhoff_lsqr / rtmi_tomo_lsqr_basis with one column over the stacked operator
+ *     [A | Dx | Dy | Dxx | Dyy] on the node grid [ny][nx]; lp, lo (row_weight [S R], col_scale [ny nx], x0 [ny nx]), reg and st
+ *     are those structs with their checks, the regulariser rows those of rtmi_tomo_lsqr_basis on gx = nx, gy = ny.  x0: A x0 is
+ *     taken out of rhs once, before the loop, and x0 is added after it.  rhs [S R] must be finite (a dead row's residual is
+ *     +0.0).  A dead row must carry a zero row_weight where row_weight is given (RTMI_ERR_ARG otherwise); without row_weight
+ *     it contributes 0 to both products.  A transposed product with a value that is not finite, or a norm out of fp64's range,
+ *     ends the solve with istop = RTMI_LSQR_RANGE.  A sweep that does not converge inside the loop returns RTMI_ERR_STATE, and x
+ *     is not written.  operator_ms and vector_ms as in rtmi_tomo_lsqr_multi.
+ * rtmi_eikonal_tomo_relinearise: a new medium n [ny][nx] for a self-filled handle (RTMI_ERR_STATE on any other): every table is
+ *     filled again from the ball on the device and the live rows are found again.  n_src [S] or NULL: a source inside the grid
+ *     gets sample(n, src_s), a source outside keeps its value.  The same bits as a new rtmi_eikonal_tomo_create with that n and
+ *     n_src.  If it fails the handle must be re-linearised again, or destroyed.
+ * rtmi_eikonal_tomo_info: rows = S R, live_rows, the shape, the nodes the receivers touch, the device bytes; live_per_source [S]
+ *     or NULL.  After a product, st holds sweep_ms (the sweep's kernel time), kernel_ms (this unit's kernels) and rounds_max.
+ * rtmi_eikonal_tomo_table: the handle's T, filled [S][ny][nx] and live [S R] bytes to host buffers, any of them NULL.
+ * Every entry but create, destroy, info, table and lsqr has a _dev form on memory of the handle's device; the host form is
+ * upload, that, download: the same bits.
+ * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: everything rtmi_eikonal_fill refuses; S < 1;
+ * R < 1; a null rec; a receiver coordinate that is not finite or lies outside [gx0, gx0 + (nx - 1) gdx] x [gy0, gy0 + (ny - 1)
+ * gdy]; exactly one of T and filled null; S R >= 2^29.  RTMI_ERR_STATE at create: a self-filled table that did not converge
+ * within max_rounds.
+ * Not covered: per-source receiver lists (use a zero row_weight); a B-spline basis for this solver; several columns per solve;
+ * joint rows with rtmi_tomo handles; seeds that move with the medium; anisotropy; 3-D; fp32. */
+typedef struct rtmi_eikonal_tomo rtmi_eikonal_tomo;
+typedef struct {
+    int64_t rows, live_rows; /* S R, and the live ones */
+    int64_t S, R, nx, ny;
+    int64_t touched;         /* nodes that are a corner of a receiver */
+    int64_t bytes_device;    /* the handle's */
+    int32_t self_filled;     /* 1: the handle filled its own tables */
+    int32_t path;            /* the sweeps': RTMI_EIKONAL_LDS or RTMI_EIKONAL_GLOBAL */
+    int32_t rounds_max;      /* of the last sweep (info: of the handle's own fill) */
+    int32_t reserved0;
+    double sweep_ms;         /* the sweep's device time (HIP events) */
+    double kernel_ms;        /* this unit's kernels (HIP events) */
+    double reduce_ms;        /* of them, a transpose's clearing of its flag and k_etomo_reduce */
+    int64_t reserved[3];
+} rtmi_eikonal_tomo_stats;
+int rtmi_eikonal_tomo_create(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
+                             const double *T, const uint8_t *filled, int64_t R, const double *rec, rtmi_eikonal_tomo **out);
+void rtmi_eikonal_tomo_destroy(rtmi_eikonal_tomo *h);
+int rtmi_eikonal_tomo_info(const rtmi_eikonal_tomo *h, rtmi_eikonal_tomo_stats *st, int64_t *live_per_source);
+int rtmi_eikonal_tomo_table(const rtmi_eikonal_tomo *h, double *T, uint8_t *filled, uint8_t *live);
+int rtmi_eikonal_tomo_apply(rtmi_eikonal_tomo *h, const double *dn, double *y, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_apply_dev(rtmi_eikonal_tomo *h, const double *d_dn, double *d_y, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_transpose(rtmi_eikonal_tomo *h, const double *y, double *G, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_transpose_dev(rtmi_eikonal_tomo *h, const double *d_y, double *d_G, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_residual(rtmi_eikonal_tomo *h, const double *picks, double *res);
+int rtmi_eikonal_tomo_residual_dev(rtmi_eikonal_tomo *h, const double *d_picks, double *d_res);
+int rtmi_eikonal_tomo_relinearise(rtmi_eikonal_tomo *h, const double *n, const double *n_src);
+int rtmi_eikonal_tomo_relinearise_dev(rtmi_eikonal_tomo *h, const double *d_n, const double *d_n_src);
+int rtmi_eikonal_tomo_lsqr(rtmi_eikonal_tomo *h, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo, const rtmi_tomo_reg *reg,
+                           const double *rhs, double *x, double *history, rtmi_lsqr_stats *st);
 
 /* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
  * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it

@@ -221,6 +221,14 @@ class EikonalStats(C.Structure):
                 ("rounds_max", C.c_int32), ("path", C.c_int32), ("kernel_ms", C.c_double), ("reserved", C.c_int64 * 4)]
 
 
+class EikonalTomoStats(C.Structure):
+    """rtmi_eikonal_tomo_stats: the shape and the live rows of an eikonal tomography handle, and the times of its last product"""
+    _fields_ = [("rows", C.c_int64), ("live_rows", C.c_int64), ("S", C.c_int64), ("R", C.c_int64), ("nx", C.c_int64),
+                ("ny", C.c_int64), ("touched", C.c_int64), ("bytes_device", C.c_int64), ("self_filled", C.c_int32),
+                ("path", C.c_int32), ("rounds_max", C.c_int32), ("reserved0", C.c_int32), ("sweep_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("reduce_ms", C.c_double), ("reserved", C.c_int64 * 3)]
+
+
 EIKONAL_LDS, EIKONAL_GLOBAL = 1, 2      # rtmi_eikonal_stats.path
 EIKONAL_PATHS = {EIKONAL_LDS: "lds", EIKONAL_GLOBAL: "global"}
 
@@ -390,6 +398,21 @@ SYMBOLS = {
                                        _dp, _ip, C.POINTER(EikonalStats)]),
     "rtmi_eikonal_adjoint_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 8 +
                                  [_ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_tomo_create": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int64, _dp,
+                                           C.POINTER(C.c_void_p)]),
+    "rtmi_eikonal_tomo_destroy": (None, [C.c_void_p]),
+    "rtmi_eikonal_tomo_info": (C.c_int, [C.c_void_p, C.POINTER(EikonalTomoStats), C.POINTER(C.c_int64)]),
+    "rtmi_eikonal_tomo_table": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "rtmi_eikonal_tomo_apply": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_transpose": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_transpose_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_residual": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "rtmi_eikonal_tomo_residual_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtmi_eikonal_tomo_relinearise": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "rtmi_eikonal_tomo_relinearise_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtmi_eikonal_tomo_lsqr": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), _dp, _dp, _dp,
+                                         C.POINTER(LsqrStats)]),
     "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
                                     C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1965,6 +1965,250 @@ def eikonal_operator(field_or_n, sources, grid, fill_result, receivers, *, n_src
     return LinearOperator((S * len(rec), ny * nx), matvec=matvec, rmatvec=rmatvec, dtype=np.float64)
 
 
+def eikonal_tomo_stats(st):
+    return {"rows": int(st.rows), "live_rows": int(st.live_rows), "S": int(st.S), "R": int(st.R), "nx": int(st.nx), "ny": int(st.ny),
+            "touched": int(st.touched), "bytes_device": int(st.bytes_device), "self_filled": bool(st.self_filled),
+            "path": _lib.EIKONAL_PATHS.get(st.path, st.path), "rounds_max": int(st.rounds_max), "sweep_ms": st.sweep_ms,
+            "kernel_ms": st.kernel_ms, "reduce_ms": st.reduce_ms}
+
+
+class EikonalTomography:
+    """First-arrival eikonal tomography that stays on the device (rtmi_eikonal_tomo_*, include/rtmi.h): the Jacobian
+    of the filled tables at `receivers` [R, 2], coordinates anywhere on the grid, as a handle with two bit-defined products, the
+    residual of picks, LSQR on the device and Gauss-Newton.  Row s R + k is source s, receiver k.  field_or_n, sources, grid,
+    n_src, ball, max_rounds as in eikonal_fill.  fill_result: the dict of the eikonal_fill call that gave the tables (this is how
+    a table seeded by rays enters); None: the handle fills its own from the ball, and only then can it be re-linearised.
+    n_src follows the model through the bilinear weights of the source's cell where the source lies inside the grid.  A row is
+    live where none of the four nodes round its receiver is an obstacle or unreached; other rows read and give 0."""
+
+    def __init__(self, field_or_n, sources, grid, receivers, *, fill_result=None, n_src=None, ball=2.0, max_rounds=0, _global_path=False):
+        who = "EikonalTomography"
+        self._h = None
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
+        S, nx, ny = len(src), int(grid[2]), int(grid[5])
+        n, ns = _eikonal_medium(who, field_or_n, src, grid, n_src)
+        n = np.ascontiguousarray(n, dtype=np.float64)
+        ns = np.ascontiguousarray(ns, dtype=np.float64).reshape(-1)
+        if nx >= 1 and ny >= 1 and n.shape != (ny, nx):
+            raise ValueError(f"{who}: n must be [ny, nx] of the grid")
+        if len(ns) != S:
+            raise ValueError(f"{who}: n_src must be [S]")
+        rec = np.ascontiguousarray(np.asarray(receivers, dtype=np.float64).reshape(-1, 2))
+        T = filled = None
+        if fill_result is not None:
+            T = np.ascontiguousarray(fill_result["T"], dtype=np.float64)
+            filled = np.ascontiguousarray(fill_result["filled"], dtype=np.uint8)
+            if T.shape != (S, ny, nx) or filled.shape != (S, ny, nx):
+                raise ValueError(f"{who}: fill_result's T and filled must be [S, ny, nx]")
+        self.grid, self.S, self.R, self.nx, self.ny = tuple(grid), S, len(rec), nx, ny
+        self.n, self.sources, self.receivers = n.copy(), src, rec
+        ep = eikonal_params(grid, ball, max_rounds, _global_path)
+        h = C.c_void_p()
+        check(lib().rtmi_eikonal_tomo_create(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
+                                             None if filled is None else filled.ctypes.data_as(C.POINTER(C.c_uint8)), len(rec), dptr(rec),
+                                             C.byref(h)))
+        self._h = h
+
+    def _open(self):
+        if self._h is None:
+            raise ValueError("EikonalTomography: the handle is closed")
+        return self._h
+
+    @property
+    def shape(self):
+        return (self.S * self.R, self.ny * self.nx)
+
+    def info(self):
+        """rows, live_rows, live_per_source [S], the shape, the nodes the receivers touch, the device bytes"""
+        st = _lib.EikonalTomoStats()
+        per = np.zeros(self.S, dtype=np.int64)
+        check(lib().rtmi_eikonal_tomo_info(self._open(), C.byref(st), per.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = eikonal_tomo_stats(st)
+        out["live_per_source"] = per
+        return out
+
+    def table(self):
+        """The handle's tables: T [S, ny, nx], filled [S, ny, nx] uint8 and live [S, R] uint8"""
+        T = np.empty((self.S, self.ny, self.nx))
+        filled = np.empty((self.S, self.ny, self.nx), dtype=np.uint8)
+        live = np.empty((self.S, self.R), dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        check(lib().rtmi_eikonal_tomo_table(self._open(), dptr(T), filled.ctypes.data_as(u8), live.ctypes.data_as(u8)))
+        return {"T": T, "filled": filled, "live": live}
+
+    def _host(self, who, a, size, name):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if a.size != size:
+            raise ValueError(f"EikonalTomography.{who}: {name} must have {size} values")
+        return a
+
+    def _device(self, who, t, size, name):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() != size:
+            raise ValueError(f"EikonalTomography.{who}: {name} must be a contiguous fp64 torch tensor of {size} values on the GPU")
+        torch.cuda.synchronize(t.device)               # the library works on the null stream
+        return t
+
+    def apply(self, dn, stats=False):
+        """y [S R] = A dn for dn [ny, nx] (rtmi_eikonal_tomo_apply); a sweep that does not converge raises"""
+        dn = self._host("apply", dn, self.ny * self.nx, "dn")
+        y = np.empty(self.S * self.R)
+        st = _lib.EikonalTomoStats()
+        check(lib().rtmi_eikonal_tomo_apply(self._open(), dptr(dn), dptr(y), C.byref(st)))
+        return (y, eikonal_tomo_stats(st)) if stats else y
+
+    def transpose(self, y, stats=False):
+        """G [ny, nx] = A^T y for y [S R] (rtmi_eikonal_tomo_transpose); a dead row's entry is not read"""
+        y = self._host("transpose", y, self.S * self.R, "y")
+        G = np.empty((self.ny, self.nx))
+        st = _lib.EikonalTomoStats()
+        check(lib().rtmi_eikonal_tomo_transpose(self._open(), dptr(y), dptr(G), C.byref(st)))
+        return (G, eikonal_tomo_stats(st)) if stats else G
+
+    def apply_device(self, dn, out=None, stats=False):
+        """apply on torch tensors of the handle's device, with no host copy (rtmi_eikonal_tomo_apply_dev): the same bits"""
+        import torch
+        dn = self._device("apply_device", dn, self.ny * self.nx, "dn")
+        y = torch.empty(self.S * self.R, dtype=torch.float64, device=dn.device) if out is None else self._device("apply_device", out, self.S * self.R, "out")
+        st = _lib.EikonalTomoStats()
+        with torch.cuda.device(dn.device):
+            check(lib().rtmi_eikonal_tomo_apply_dev(self._open(), dn.data_ptr(), y.data_ptr(), C.byref(st)))
+        return (y, eikonal_tomo_stats(st)) if stats else y
+
+    def transpose_device(self, y, out=None, stats=False):
+        """transpose on torch tensors of the handle's device (rtmi_eikonal_tomo_transpose_dev): the same bits"""
+        import torch
+        y = self._device("transpose_device", y, self.S * self.R, "y")
+        G = (torch.empty((self.ny, self.nx), dtype=torch.float64, device=y.device) if out is None
+             else self._device("transpose_device", out, self.ny * self.nx, "out"))
+        st = _lib.EikonalTomoStats()
+        with torch.cuda.device(y.device):
+            check(lib().rtmi_eikonal_tomo_transpose_dev(self._open(), y.data_ptr(), G.data_ptr(), C.byref(st)))
+        return (G, eikonal_tomo_stats(st)) if stats else G
+
+    def residual(self, picks):
+        """res [S R] = picks - the tables sampled at the receivers; +0.0 on a dead row and where the pick is NaN (absent)"""
+        picks = self._host("residual", picks, self.S * self.R, "picks")
+        res = np.empty(self.S * self.R)
+        check(lib().rtmi_eikonal_tomo_residual(self._open(), dptr(picks), dptr(res)))
+        return res
+
+    def residual_device(self, picks):
+        import torch
+        picks = self._device("residual_device", picks, self.S * self.R, "picks")
+        res = torch.empty(self.S * self.R, dtype=torch.float64, device=picks.device)
+        with torch.cuda.device(picks.device):
+            check(lib().rtmi_eikonal_tomo_residual_dev(self._open(), picks.data_ptr(), res.data_ptr()))
+        return res
+
+    def lsqr(self, rhs, iter_lim, damp=0.0, atol=0.0, btol=0.0, row_weight=None, col_scale=None, x0=None, smooth=None, smooth2=None,
+             history=False, stats=False):
+        """rtmi_eikonal_tomo_lsqr: min |W A D y - W (rhs - A x0)|^2 + damp^2 |y|^2 + the smoothing rows of D y on the node grid,
+        x = x0 + D y, every vector on the device.  smooth = (lx, ly), smooth2 = (mx2, my2) as in Tomography.lsqr.  row_weight
+        [S R] must be 0 on dead rows; col_scale and x0 [ny, nx].  -> the dict of Tomography.lsqr with x [ny, nx]."""
+        who = "EikonalTomography.lsqr"
+        rr = self._host("lsqr", rhs, self.S * self.R, "rhs")
+        iter_lim = int(iter_lim)
+        if iter_lim < 1:
+            raise ValueError(f"{who}: iter_lim must be >= 1")
+        lp = _lib.LsqrParams()
+        lp.iter_lim, lp.damp, lp.atol, lp.btol = iter_lim, float(damp), float(atol), float(btol)
+        reg = None
+        if smooth is not None or smooth2 is not None:
+            reg = _lib.TomoReg()
+            for name, pair, dst in (("smooth", smooth, reg.d1), ("smooth2", smooth2, reg.d2)):
+                if pair is not None:
+                    pp = np.ascontiguousarray(pair, dtype=np.float64)
+                    if pp.shape != (2,):
+                        raise ValueError(f"{who}: {name} must be a pair")
+                    dst[0], dst[1] = pp
+        lo = keep = None
+        if row_weight is not None or col_scale is not None or x0 is not None:
+            lo, keep = _lsqr_options(who, rr.size, self.ny * self.nx, row_weight, col_scale, x0)
+        x = np.empty((self.ny, self.nx))
+        hist = np.zeros((iter_lim, 4)) if history else None
+        st = _lib.LsqrStats()
+        check(lib().rtmi_eikonal_tomo_lsqr(self._open(), C.byref(lp), None if lo is None else C.byref(lo),
+                                           None if reg is None else C.byref(reg), dptr(rr), dptr(x), dptr(hist), C.byref(st)))
+        out = {"x": x, "istop": int(st.istop), "itn": int(st.itn), "r1norm": st.r1norm, "r2norm": st.r2norm, "anorm": st.anorm,
+               "arnorm": st.arnorm}
+        if history:
+            out["history"] = hist[:st.itn].copy()
+        if stats:
+            out["stats"] = {"total_ms": st.total_ms, "operator_ms": st.operator_ms, "vector_ms": st.vector_ms,
+                            "bytes_device": int(st.bytes_device)}
+        return out
+
+    def as_linear_operator(self):
+        """A scipy LinearOperator [S R, ny nx] over apply and transpose (host vectors: two PCIe crossings per product)"""
+        from scipy.sparse.linalg import LinearOperator
+        return LinearOperator(self.shape, matvec=self.apply, rmatvec=lambda y: self.transpose(y).reshape(-1), dtype=np.float64)
+
+    def relinearise(self, n, n_src=None):
+        """A new medium n [ny, nx] for a handle that filled its own tables: they are filled again on the device and the live rows
+        found again (rtmi_eikonal_tomo_relinearise).  n_src [S] or None: a source inside the grid gets n sampled at it."""
+        n = self._host("relinearise", n, self.ny * self.nx, "n")
+        ns = None if n_src is None else self._host("relinearise", n_src, self.S, "n_src")
+        check(lib().rtmi_eikonal_tomo_relinearise(self._open(), dptr(n), dptr(ns)))
+        self.n = n.reshape(self.ny, self.nx).copy()
+
+    def relinearise_device(self, n, n_src=None):
+        """relinearise on torch tensors of the handle's device (rtmi_eikonal_tomo_relinearise_dev): the same bits"""
+        import torch
+        n = self._device("relinearise_device", n, self.ny * self.nx, "n")
+        if n_src is not None:
+            n_src = self._device("relinearise_device", n_src, self.S, "n_src")
+        with torch.cuda.device(n.device):
+            check(lib().rtmi_eikonal_tomo_relinearise_dev(self._open(), n.data_ptr(), None if n_src is None else n_src.data_ptr()))
+        self.n = n.detach().cpu().numpy().reshape(self.ny, self.nx).copy()
+
+    def gauss_newton(self, picks, iters, **lsqr_kw):
+        """iters times: residual, lsqr, n += x, relinearise.  picks [S R], NaN where absent.  lsqr_kw: the keywords of lsqr
+        (iter_lim too; 30 if absent).  On each step col_scale defaults to 0 at obstacle nodes and 1 elsewhere, and row_weight is
+        0 on dead rows and absent picks (a given row_weight is multiplied by that mask).  Raises if a step would make n <= 0 at
+        a node that is no obstacle.  -> {"n": the last model, "rms": [iters + 1] the rms residual of every model over the rows in
+        use, "steps": the lsqr dicts}"""
+        who = "EikonalTomography.gauss_newton"
+        picks = self._host("gauss_newton", picks, self.S * self.R, "picks")
+        kw = dict(lsqr_kw)
+        iter_lim = kw.pop("iter_lim", 30)
+        given_w = kw.pop("row_weight", None)
+        given_c = kw.pop("col_scale", None)
+        present = ~np.isnan(picks)
+        rms, steps = [], []
+
+        def measure():
+            res = self.residual(picks)
+            used = present & (self.table()["live"].reshape(-1) != 0)
+            rms.append(float(np.sqrt((res * res).sum() / max(int(used.sum()), 1))))
+            return res, used
+
+        for _ in range(int(iters)):
+            res, used = measure()
+            open_ = np.isfinite(self.n) & (self.n > 0)
+            w = used.astype(np.float64) if given_w is None else np.asarray(given_w, dtype=np.float64).reshape(-1) * used
+            c = open_.astype(np.float64) if given_c is None else given_c
+            out = self.lsqr(res, iter_lim, row_weight=w, col_scale=c, **kw)
+            n1 = self.n + out["x"]
+            if (n1[open_] <= 0).any():
+                raise ValueError(f"{who}: the step would make n <= 0 at a node that is no obstacle (more damping or smoothing)")
+            self.relinearise(n1)
+            steps.append(out)
+        measure()
+        return {"n": self.n.copy(), "rms": np.array(rms), "steps": steps}
+
+    def close(self):
+        if self._h is not None:
+            lib().rtmi_eikonal_tomo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def beam_params(grid, eps, cutoff=None, max_width=None, edge_taper=0):
     """rtmi_beam_params of grid = (gx0, gdx, nx, gy0, gdy, ny) and the beam parameter eps; None / 0 take the library's defaults"""
     gx0, gdx, nx, gy0, gdy, ny = grid
