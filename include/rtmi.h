@@ -1385,7 +1385,7 @@ int rtmi_eikonal_fill_dev(const rtmi_eikonal_params *ep, const double *d_n, int6
  *            in groups of at most 1 GiB).  ep->reserved[0] = 1 takes the global path, for tests.
  * The _dev forms take every array but rounds and stats as memory of the calling thread's current device; the host forms are
  * upload, that, download: the same bits.  RTMI_ERR_ARG as in rtmi_eikonal_fill, and for a null T, filled, dn, dT, r or lam with S > 0.
- * Not covered: several right-hand sides per source in one call; seeds that move; anisotropy; 3-D; fp32.  Receivers off the
+ * Not covered: seeds that move; anisotropy; 3-D; fp32.  Several right-hand sides in one call: the _multi entries below.  Receivers off the
  * nodes and the LSQR loop on the device: rtmi_eikonal_tomo_* below. */
 int rtmi_eikonal_tangent(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
                          const double *T, const uint8_t *filled, const double *dn, const double *dn_src, const double *dT_seed,
@@ -1399,6 +1399,40 @@ int rtmi_eikonal_adjoint(const rtmi_eikonal_params *ep, const double *n, int64_t
 int rtmi_eikonal_adjoint_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src, const double *d_n_src,
                              const double *d_T, const uint8_t *d_filled, const double *d_r, double *d_lam, double *d_g,
                              double *d_g_src, int32_t *rounds, rtmi_eikonal_stats *stats);
+
+/* Several right-hand sides through the linearised fill in one call.  DESIGN.md section 37.  The arguments of the single entries
+ * plus nrhs = K, 1 <= K <= RTMI_LSQR_MULTI_MAX (else RTMI_ERR_ARG before any device work).  Columns are planes, contiguous:
+ *     dn [K][ny][nx];  dn_src [K][S] or NULL;  dT_seed [K][S][ny][nx] or NULL;  dT [K][S][ny][nx]
+ *     r, lam [K][S][ny][nx];  g [K][S][ny][nx] or NULL;  g_src [K][S] or NULL;  rounds [K][S][2]
+ * CONTRACT.  Column c of every output has the bits that the single entry gives on column c alone: dT, lam, g, g_src, rounds and
+ * clean, NaNs in the same places.  This holds by construction, not by tolerance: columns never read one another; a column's
+ * sweep is the fixed sweep of the single entry; and a round after a column's first clean round reproduces every value bit for
+ * bit, so it changes nothing and counts no change.  Columns are swept in chunks, and a chunk sweeps until its last column is
+ * clean or max_rounds have run; column c reports the first round in which it changed nothing with clean = 1, or max_rounds with
+ * clean = 0 and the values of the last sweep: the single call's rule.  No result depends on the chunk width.
+ *   stats    sums over the sources and the columns; changes counts each column up to its own last round; rounds_max over all;
+ *            path: where a chunk's values and its source's coefficients (8 C + 18 bytes per node, C the chunk width the call
+ *            chose from K, S, the device's CUs and the work budget) fit 128 KiB they live in LDS, else in global memory: 18
+ *            bytes per node and source that the source's chunks share, filled once per source, and 16 C per node and chunk
+ *            (8 C on the LDS path, the constant terms), in groups of at most 1 GiB.  ep->reserved[0] = 1 takes the global path, for tests;
+ *            ep->reserved[1] = 1, 4 or 8 takes that chunk width instead of the call's own choice, for tests too, and must
+ *            be 0 otherwise: any other value is RTMI_ERR_ARG.  The single entries do not read reserved[1].
+ * Not covered: a work space kept across calls; the diagonal-major layout; restricted sweeps; batched fills.  The products and
+ * the solver on several columns: rtmi_eikonal_tomo_*_multi below. */
+int rtmi_eikonal_tangent_multi(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
+                               const double *T, const uint8_t *filled, int32_t nrhs, const double *dn, const double *dn_src,
+                               const double *dT_seed, double *dT, int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_tangent_multi_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src,
+                                   const double *d_n_src, const double *d_T, const uint8_t *d_filled, int32_t nrhs,
+                                   const double *d_dn, const double *d_dn_src, const double *d_dT_seed, double *d_dT,
+                                   int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_adjoint_multi(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
+                               const double *T, const uint8_t *filled, int32_t nrhs, const double *r, double *lam, double *g,
+                               double *g_src, int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_adjoint_multi_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src,
+                                   const double *d_n_src, const double *d_T, const uint8_t *d_filled, int32_t nrhs,
+                                   const double *d_r, double *d_lam, double *d_g, double *d_g_src, int32_t *rounds,
+                                   rtmi_eikonal_stats *stats);
 
 /* First-arrival eikonal tomography that stays on the device: a handle over the linearised fill with receivers anywhere on the
  * grid, its two products defined bit for bit, and LSQR on them.  DESIGN.md section 36.  raytracing_amd/csrc/rt_eikonal_tomo.h
@@ -1451,8 +1485,8 @@ int rtmi_eikonal_adjoint_dev(const rtmi_eikonal_params *ep, const double *d_n, i
  * R < 1; a null rec; a receiver coordinate that is not finite or lies outside [gx0, gx0 + (nx - 1) gdx] x [gy0, gy0 + (ny - 1)
  * gdy]; exactly one of T and filled null; S R >= 2^29.  RTMI_ERR_STATE at create: a self-filled table that did not converge
  * within max_rounds.
- * Not covered: per-source receiver lists (use a zero row_weight); a B-spline basis for this solver; several columns per solve;
- * joint rows with rtmi_tomo handles; seeds that move with the medium; anisotropy; 3-D; fp32. */
+ * Not covered: per-source receiver lists (use a zero row_weight); a B-spline basis for this solver (several columns per solve:
+ * rtmi_eikonal_tomo_lsqr_multi below); joint rows with rtmi_tomo handles; seeds that move with the medium; anisotropy; 3-D; fp32. */
 typedef struct rtmi_eikonal_tomo rtmi_eikonal_tomo;
 typedef struct {
     int64_t rows, live_rows; /* S R, and the live ones */
@@ -1483,6 +1517,42 @@ int rtmi_eikonal_tomo_relinearise(rtmi_eikonal_tomo *h, const double *n, const d
 int rtmi_eikonal_tomo_relinearise_dev(rtmi_eikonal_tomo *h, const double *d_n, const double *d_n_src);
 int rtmi_eikonal_tomo_lsqr(rtmi_eikonal_tomo *h, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo, const rtmi_tomo_reg *reg,
                            const double *rhs, double *x, double *history, rtmi_lsqr_stats *st);
+
+/* The handle's products and solver on nrhs = K columns, 1 <= K <= RTMI_LSQR_MULTI_MAX, for checkerboard and spike recovery,
+ * bootstrap and jackknife over the picks and sweeps over noise.  DESIGN.md section 37.  Columns are planes, contiguous: dn, G and
+ * x [K][ny nx]; y and rhs [K][S R].
+ * CONTRACT.  Column c of every result is the single entry's result on column c, bit for bit (NaN by place): y, G; and for the
+ * solver x, the history rows up to itn, itn, istop and the four norms.  The sweeps are rtmi_eikonal_tangent_multi_dev and
+ * rtmi_eikonal_adjoint_multi_dev, the kernels round them take the column in blockIdx.y, and the loop is that of
+ * rtmi_tomo_lsqr_multi, whose passes treat every column alone.
+ *   rtmi_eikonal_tomo_apply_multi, _transpose_multi: as the single products.  A sweep that is not clean for any (source, column)
+ *       makes the call return RTMI_ERR_STATE, the message naming the sweep, the source and the column; the host forms then
+ *       write nothing.  A _dev form has by then written the columns of the groups before the failing one (see
+ *       rtmi_eikonal_tomo_set_column_group) and nothing of that group or of those after it.  A transposed column whose G is not finite is written as the single call writes it; the others are
+ *       untouched by it.
+ *   rtmi_eikonal_tomo_lsqr_multi: the signature of rtmi_tomo_lsqr_multi without a basis.  flags is 0 or
+ *       RTMI_LSQR_MULTI_ROW_WEIGHT, with which lo->row_weight is [K][S R]; col_scale and x0 are shared and A x0 is one single
+ *       product.  history [K][iter_lim][4] or NULL, zeroed first, so rows past a column's itn are zero; st [K] or NULL.  A column
+ *       whose transposed product is not finite gets RTMI_LSQR_RANGE and leaves the loop; the others go on.  A non-zero weight
+ *       on a dead row is refused, naming the row and, with per-column weights, the column.  The regulariser kernels are launched
+ *       per live column.
+ *   rtmi_eikonal_tomo_set_column_group: the columns swept together, cg in [0, 64]; 0, the default, is as many as keep the
+ *       handle's three work tables [cg][S][ny][nx] under 8 GiB.  The products walk K in groups of cg.  The tables are grown by
+ *       the first call that needs more, counted in bytes_device, and a growth that fails (RTMI_ERR_ALLOC) leaves the handle as
+ *       it was.  No result depends on cg.
+ * RTMI_ERR_ARG before the handle is read: a null handle, nrhs outside [1, 64], flag bits other than RTMI_LSQR_MULTI_ROW_WEIGHT,
+ * null params, rhs or x, a cg outside [0, 64].  (A handle made with an ep whose reserved[1] is not 0, 1, 4 or 8 gets
+ * RTMI_ERR_ARG from its batched sweeps.)
+ * Not covered: a start model or a column scale of its own for each column; a B-spline basis for this solver. */
+int rtmi_eikonal_tomo_apply_multi(rtmi_eikonal_tomo *h, int32_t nrhs, const double *dn, double *y, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_apply_multi_dev(rtmi_eikonal_tomo *h, int32_t nrhs, const double *d_dn, double *d_y, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_transpose_multi(rtmi_eikonal_tomo *h, int32_t nrhs, const double *y, double *G, rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_transpose_multi_dev(rtmi_eikonal_tomo *h, int32_t nrhs, const double *d_y, double *d_G,
+                                          rtmi_eikonal_tomo_stats *st);
+int rtmi_eikonal_tomo_lsqr_multi(rtmi_eikonal_tomo *h, const rtmi_lsqr_params *lp, const rtmi_lsqr_options *lo,
+                                 const rtmi_tomo_reg *reg, int32_t nrhs, int32_t flags, const double *rhs, double *x, double *history,
+                                 rtmi_lsqr_stats *st);
+int rtmi_eikonal_tomo_set_column_group(rtmi_eikonal_tomo *h, int32_t cg);
 
 /* Pick-free event detection and location on a locator's tables: source scanning, diffraction stacking, coalescence mapping.
  * DESIGN.md section 30.  Each station delivers a continuous characteristic function (an envelope, STA/LTA, kurtosis; computing it

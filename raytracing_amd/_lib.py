@@ -398,6 +398,14 @@ SYMBOLS = {
                                        _dp, _ip, C.POINTER(EikonalStats)]),
     "rtmi_eikonal_adjoint_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 8 +
                                  [_ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_tangent_multi": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32,
+                                             _dp, _dp, _dp, _dp, _ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_tangent_multi_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] +
+                                       [C.c_void_p] * 4 + [_ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_adjoint_multi": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32,
+                                             _dp, _dp, _dp, _dp, _ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_adjoint_multi_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] +
+                                       [C.c_void_p] * 4 + [_ip, C.POINTER(EikonalStats)]),
     "rtmi_eikonal_tomo_create": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int64, _dp,
                                            C.POINTER(C.c_void_p)]),
     "rtmi_eikonal_tomo_destroy": (None, [C.c_void_p]),
@@ -413,6 +421,13 @@ SYMBOLS = {
     "rtmi_eikonal_tomo_relinearise_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtmi_eikonal_tomo_lsqr": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), _dp, _dp, _dp,
                                          C.POINTER(LsqrStats)]),
+    "rtmi_eikonal_tomo_apply_multi": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_apply_multi_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_transpose_multi": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_transpose_multi_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(EikonalTomoStats)]),
+    "rtmi_eikonal_tomo_lsqr_multi": (C.c_int, [C.c_void_p, C.POINTER(LsqrParams), C.POINTER(LsqrOptions), C.POINTER(TomoReg), C.c_int32,
+                                               C.c_int32, _dp, _dp, _dp, C.POINTER(LsqrStats)]),
+    "rtmi_eikonal_tomo_set_column_group": (C.c_int, [C.c_void_p, C.c_int32]),
     "rtmi_locate_stack": (C.c_int, [C.c_void_p, C.POINTER(StackParams), _dp, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(StackEvent),
                                     C.POINTER(C.c_int64), C.POINTER(StackStats)]),
     "rtmi_locate_stack_dev": (C.c_int, [C.c_void_p, C.POINTER(StackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -394,3 +394,537 @@ RTMI_EXPORT int rtmi_eikonal_adjoint(const rtmi_eikonal_params* ep, const double
     if (g_src) RTMI_HIP(hipMemcpy(g_src, d_g_src, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
+
+// Several right-hand sides per source in one call (rtmi_eikonal_tangent_multi, rtmi_eikonal_adjoint_multi and their _dev forms;
+// DESIGN.md section 37).  Column c of every output has the bits the single entry gives on column c alone: columns never read one
+// another, a column's sweep is the fixed sweep above, and a round after a column's first clean round reproduces every value bit
+// for bit, so a chunk sweeps until its last column is clean and each column reports its own first clean round.
+//   k_eikonal_lin_setup, _kids   global path: ca, cb, the codes and the adjoint's masks of a group of sources, one lane per
+//                   (source, node), once per source: 18 bytes per node and source that the chunks of the source share
+//   k_eikonal_lin_multi<LDS, ADJ, C>  one workgroup per (source, chunk of C columns), the chunk in blockIdx.y.  The working
+//                   values and the constant terms of a chunk are column-minor, [node][C], so a node's C values are one access of
+//                   8 C bytes and the node's code, mask, ca and cb are read once for the C columns.  LDS: the values and the
+//                   source's coefficients (8 C + 18 bytes per node) in the block's LDS, computed by the block itself; else the
+//                   values in a work space.  The constant terms are in a work space on both paths.  A partial chunk's missing
+//                   columns are columns of zeros that no one reads or writes out.  The read-out pass writes the public planes.
+// Every loop bound and every barrier is uniform across the block, max_rounds bounds the whole, no block reads what another block of
+// the same launch writes, and there are no atomics.
+namespace {
+
+constexpr int kMultiWidths[] = {1, 4, 8};                // the compiled chunk widths
+
+struct LinMultiArgs {
+    rt::EikGrid g;
+    long nx, ny;
+    double ball;
+    int max_rounds;
+    int K;                      // columns of the call
+    int c0;                     // the first column of this launch
+    size_t S, s0;               // sources of the call (the planes' stride); the first source of this launch
+    const double* n;            // [ny][nx]
+    const double* src;          // [S][2]
+    const double* n_src;        // [S]
+    const double* T;            // [S][ny][nx]
+    const uint8_t* filled;      // [S][ny][nx]
+    const double* dn;           // tangent: [K][ny][nx]
+    const double* dn_src;       // tangent: [K][S] or NULL
+    const double* seed;         // tangent: [K][S][ny][nx] or NULL
+    const double* r;            // adjoint: [K][S][ny][nx]
+    double* v;                  // [K][S][ny][nx]: dT or lam
+    double* gout;               // adjoint: [K][S][ny][nx] or NULL
+    double* g_src;              // adjoint: [K][S] or NULL
+    double *ca, *cb;            // global path: [gs][ny][nx], the launch's sources
+    uint8_t *code, *kids;       // global path: [gs][ny][nx]; kids: adjoint
+    double* wv;                 // global path: [chunks][gs][ny nx][C], the working values
+    double* wk;                 // [chunks][gs][ny nx][C], the constant terms
+    unsigned long long* out;    // [K][S][kOutWords]
+};
+
+__global__ void __launch_bounds__(256) k_eikonal_lin_setup(const LinMultiArgs a, long total) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const long nn = a.nx * a.ny, x = t % nn;
+    const size_t s = a.s0 + (size_t)(t / nn);
+    const rt::EikLinNode c = rt::eik_lin_node(a.g, a.nx, a.ny, x % a.nx, x / a.nx, a.n, a.T + s * (size_t)nn, a.filled + s * (size_t)nn,
+                                              a.src[2 * s], a.src[2 * s + 1], a.n_src[s], a.ball);
+    a.ca[t] = c.ca;
+    a.cb[t] = c.cb;
+    a.code[t] = c.code;
+}
+
+__global__ void __launch_bounds__(256) k_eikonal_lin_kids(const LinMultiArgs a, long total) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const long nn = a.nx * a.ny, x = t % nn;
+    a.kids[t] = rt::eik_lin_kids(a.nx, a.ny, x % a.nx, x / a.nx, a.code + (t - x));
+}
+
+// the block's sums of C values, the same in every lane
+template <int C> __device__ __forceinline__ void block_sum_cols(unsigned long long (*red)[kMaxBlock / 64][C], int slot,
+                                                               unsigned long long* v) {
+    const int tid = (int)threadIdx.x, waves = (int)(blockDim.x >> 6);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        for (int off = 1; off < 64; off <<= 1) v[c] += (unsigned long long)__shfl_xor((long long)v[c], off);
+        if ((tid & 63) == 0) red[slot][tid >> 6][c] = v[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        unsigned long long s = 0;
+        for (int k = 0; k < waves; k++) s += red[slot][k][c];
+        v[c] = s;
+    }
+}
+
+template <bool LDS, bool ADJ, int C> __global__ void __launch_bounds__(kMaxBlock) k_eikonal_lin_multi(const LinMultiArgs a) {
+    extern __shared__ double lds[];                     // LDS: [v [nn][C] | ca | cb | code | kids]
+    __shared__ unsigned long long red[2][kMaxBlock / 64];
+    __shared__ unsigned long long redc[2][kMaxBlock / 64][C];
+    const int tid = (int)threadIdx.x, bd = (int)blockDim.x;
+    const long nx = a.nx, ny = a.ny, nn = nx * ny;
+    const size_t sl = blockIdx.x, s = a.s0 + sl, S = a.S;
+    const int col0 = a.c0 + (int)blockIdx.y * C;
+    const int ncol = a.K - col0 < C ? a.K - col0 : C;
+    const size_t slot = (size_t)blockIdx.y * gridDim.x + sl;
+    const double xs = a.src[2 * s], ys = a.src[2 * s + 1], n_src = a.n_src[s];
+    const double* Ts = a.T + s * (size_t)nn;
+    const uint8_t* fs = a.filled + s * (size_t)nn;
+    double *v, *ca, *cb;
+    uint8_t *code, *kids;
+    if constexpr (LDS) {
+        v = lds;
+        ca = lds + (size_t)C * nn;
+        cb = ca + nn;
+        code = (uint8_t*)(cb + nn);
+        kids = code + nn;
+    } else {
+        v = a.wv + slot * (size_t)nn * C;
+        ca = a.ca + sl * (size_t)nn;
+        cb = a.cb + sl * (size_t)nn;
+        code = a.code + sl * (size_t)nn;
+        kids = ADJ ? a.kids + sl * (size_t)nn : nullptr;
+    }
+    double* kr = a.wk + slot * (size_t)nn * C;          // a node's constant terms: r (adjoint), cs dn (tangent)
+    long bi0 = 0, bi1 = -1, bj0 = 0, bj1 = -1;
+    if constexpr (ADJ) rt::eik_lin_ball_box(a.g, nx, ny, xs, ys, a.ball, &bi0, &bi1, &bj0, &bj1);
+    // the classes, the coefficients where the block keeps its own, and every column's starting values and constant terms
+    unsigned long long nfree = 0, nnodes = 0, nstray = 0;
+    for (long x = tid; x < nn; x += bd) {
+        const long i = x % nx, j = x / nx;
+        rt::EikLinNode c{0.0, 0.0, 0.0, 0.0, 0};
+        if constexpr (LDS || !ADJ) {
+            c = rt::eik_lin_node(a.g, nx, ny, i, j, a.n, Ts, fs, xs, ys, n_src, a.ball);
+            if constexpr (LDS) {
+                ca[x] = c.ca;
+                cb[x] = c.cb;
+                code[x] = c.code;
+            }
+        } else {
+            c.code = code[x];
+        }
+        const uint8_t cls = rt::eik_lin_class(c.code);
+        double val[C], k[C];
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+            val[q] = 0.0;
+            k[q] = 0.0;
+            if (q < ncol) {
+                const size_t col = (size_t)(col0 + q), plane = (col * S + s) * (size_t)nn;
+                if constexpr (ADJ) {
+                    k[q] = a.r[plane + x];
+                    val[q] = cls == rt::kLinDead ? 0.0 : k[q];
+                } else {
+                    val[q] = rt::eik_lin_tangent_init(c, a.dn[col * (size_t)nn + x], a.dn_src ? a.dn_src[col * S + s] : 0.0,
+                                                      a.seed ? a.seed[plane + x] : 0.0, &k[q]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+            v[x * C + q] = val[q];
+            kr[x * C + q] = k[q];
+        }
+        if constexpr (ADJ)
+            if (cls == rt::kLinBall && !(i >= bi0 && i <= bi1 && j >= bj0 && j <= bj1)) nstray++;
+        if (cls >= rt::kLinFree) nnodes++;
+        if (cls == rt::kLinFree) nfree++;
+    }
+    nnodes = block_sum(red, 0, nnodes);
+    nstray = block_sum(red, 1, nstray);     // its barrier also parts the codes from the reads of the masks' pass
+    if constexpr (ADJ && LDS)
+        for (long x = tid; x < nn; x += bd) kids[x] = rt::eik_lin_kids(nx, ny, x % nx, x / nx, code);
+    nfree = block_sum(red, 0, nfree);       // its barrier also parts the starting values from the first diagonal's reads
+    // per column: the first round that changed nothing, or max_rounds and not clean.  All of it is uniform across the block
+    int rounds[C], clean[C];
+    unsigned long long changes[C];
+    bool done[C];
+#pragma unroll
+    for (int q = 0; q < C; q++) {
+        rounds[q] = 0;
+        clean[q] = 1;
+        changes[q] = 0;
+        done[q] = q >= ncol;
+    }
+    if (nfree > 0) {
+        const long ndiag = nx + ny - 1;
+        int round = 0;
+        bool all = false;
+        while (!all && round < a.max_rounds) {
+            round++;
+            unsigned long long mine[C];
+#pragma unroll
+            for (int q = 0; q < C; q++) mine[q] = 0;
+            for (int k = 0; k < 4; k++) {
+                const bool xup = rt::eik_lin_xup(ADJ, k), yup = rt::eik_lin_yup(ADJ, k);
+                for (long d = 0; d < ndiag; d++) {
+                    // the diagonal p + q = d in the sweep's own coordinates: q in [q0, q1]
+                    const long q0 = d - (nx - 1) > 0 ? d - (nx - 1) : 0, q1 = d < ny - 1 ? d : ny - 1;
+                    for (long q = q0 + tid; q <= q1; q += bd) {
+                        const long p = d - q, i = xup ? p : nx - 1 - p, j = yup ? q : ny - 1 - q, x = j * nx + i;
+                        const uint8_t c = code[x];
+                        double t[C];
+                        if constexpr (ADJ) {
+                            if (rt::eik_lin_class(c) == rt::kLinDead) continue;
+                            rt::eik_lin_adjoint_gather_cols<C>(nx, x, kids[x], kr, ca, cb, v, t);
+                        } else {
+                            if (rt::eik_lin_class(c) != rt::kLinFree) continue;
+                            rt::eik_lin_tangent_gather_cols<C>(nx, x, c, ca[x], cb[x], kr, v, t);
+                        }
+#pragma unroll
+                        for (int w = 0; w < C; w++)
+                            if (rt::eik_bits(t[w]) != rt::eik_bits(v[x * C + w])) {
+                                v[x * C + w] = t[w];
+                                mine[w]++;
+                            }
+                    }
+                    __syncthreads();
+                }
+            }
+            block_sum_cols<C>(redc, round & 1, mine);
+            all = true;
+#pragma unroll
+            for (int q = 0; q < C; q++) {
+                if (!done[q]) {
+                    changes[q] += mine[q];
+                    rounds[q] = round;
+                    clean[q] = mine[q] == 0;
+                    done[q] = mine[q] == 0;
+                }
+                all = all && done[q];
+            }
+        }
+    }
+    // the values out to the public planes, and what the adjoint derives from them
+    for (long x = tid; x < nn; x += bd) {
+        double cs = 0.0;
+        bool live = false;
+        if constexpr (ADJ) {
+            if (a.gout && rt::eik_lin_class(code[x]) >= rt::kLinFree) {
+                live = true;
+                cs = rt::eik_lin_node(a.g, nx, ny, x % nx, x / nx, a.n, Ts, fs, xs, ys, n_src, a.ball).cs;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+            if (q < ncol) {
+                const size_t plane = ((size_t)(col0 + q) * S + s) * (size_t)nn;
+                const double val = v[x * C + q];
+                a.v[plane + x] = val;
+                if constexpr (ADJ) {
+                    if (a.gout) {
+                        double gv = 0.0;
+                        if (live) gv = cs * val;
+                        a.gout[plane + x] = gv;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (ADJ) {
+        if (a.g_src && tid < ncol) {
+            // one lane per column, in node order.  nstray is 0 unless the box missed a node of the ball: then every node is looked at
+            const long i0 = nstray ? 0 : bi0, i1 = nstray ? nx - 1 : bi1, j0 = nstray ? 0 : bj0, j1 = nstray ? ny - 1 : bj1;
+            double acc = 0.0;
+            for (long j = j0; j <= j1; j++)
+                for (long i = i0; i <= i1; i++)
+                    if (rt::eik_lin_class(code[j * nx + i]) == rt::kLinBall)
+                        acc = acc + rt::eik_lin_csrc(a.g, i, j, xs, ys) * v[(j * nx + i) * C + tid];
+            a.g_src[(size_t)(col0 + tid) * S + s] = acc;
+        }
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+            if (q < ncol) {
+                unsigned long long* o = a.out + ((size_t)(col0 + q) * S + s) * kOutWords;
+                o[0] = (unsigned long long)(unsigned)rounds[q] | (unsigned long long)(unsigned)clean[q] << 32;
+                o[1] = nnodes;
+                o[2] = changes[q];
+            }
+        }
+    }
+}
+
+// How a call at chunk width C goes out: its path, and the sources (gs) and chunks (gc) of one launch, which keep the work space under
+// the budget: per source ca, cb, the code and the mask off the LDS path; per workgroup the constant terms, and the values off it
+struct MultiPlan {
+    int C;
+    bool lds;
+    size_t lds_bytes, chunks, gs, gc;
+};
+
+MultiPlan multi_plan(int C, int K, size_t S, size_t nn, bool force_global) {
+    MultiPlan p{};
+    p.C = C;
+    p.lds_bytes = (nn * ((size_t)C * sizeof(double) + kLdsPerNode - sizeof(double)) + 7) / 8 * 8;
+    p.lds = p.lds_bytes <= kLdsBudget && !force_global;
+    p.chunks = (size_t)(K + C - 1) / C;
+    const size_t per_src = p.lds ? 0 : nn * (kLdsPerNode - sizeof(double));
+    const size_t per_wg = nn * (size_t)C * sizeof(double) * (p.lds ? 1 : 2);
+    p.gs = std::min(S, kWorkBudget / (per_src + p.chunks * per_wg));
+    p.gc = p.chunks;
+    if (p.gs == 0) {
+        p.gs = 1;
+        p.gc = std::min(p.chunks, std::max<size_t>(1, (kWorkBudget - std::min(kWorkBudget, per_src)) / per_wg));
+    }
+    p.gc = std::min<size_t>(p.gc, 65535);
+    return p;
+}
+
+// The chunk width of a call: the widest compiled width that K fills and whose launches, under the work budget, still hold at least
+// one workgroup per CU, so the narrowest chunks that keep every CU busy; 1 where no width does.  Measured against the widest width
+// that K fills.  forced: ep->reserved[1], a compiled width for tests; no result depends on the width
+MultiPlan multi_choose(int K, size_t S, size_t nn, int cus, bool force_global, int64_t forced) {
+    if (forced) return multi_plan((int)forced, K, S, nn, force_global);
+    MultiPlan best = multi_plan(1, K, S, nn, force_global);
+    for (int w : kMultiWidths) {
+        if (w > K) continue;
+        const MultiPlan p = multi_plan(w, K, S, nn, force_global);
+        if (p.gs * p.gc >= (size_t)cus) best = p;
+    }
+    return best;
+}
+
+template <bool ADJ, int C> int lin_multi_launch(const char* who, bool lds, size_t lds_bytes, dim3 grid, int block, const LinMultiArgs& a) {
+    if (lds) {
+        // the kernel's static LDS (red and redc) counts against the 64 KiB that need no attribute
+        if (lds_bytes + sizeof(unsigned long long) * 2 * (kMaxBlock / 64) * (1 + C) > 65536)
+            RTMI_HIP(hipFuncSetAttribute((const void*)k_eikonal_lin_multi<true, ADJ, C>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)kLdsBudget));
+        hipLaunchKernelGGL((k_eikonal_lin_multi<true, ADJ, C>), grid, dim3(block), lds_bytes, nullptr, a);
+    } else {
+        hipLaunchKernelGGL((k_eikonal_lin_multi<false, ADJ, C>), grid, dim3(block), 0, nullptr, a);
+    }
+    RTMI_HIP(hipGetLastError());
+    return RTMI_OK;
+}
+
+// One batched call on device memory: a holds the caller's pointers for all S sources and K columns
+template <bool ADJ> int lin_multi_dev(const char* who, const rtmi_eikonal_params* ep, int64_t S, int K, LinMultiArgs a, int32_t* rounds,
+                                      rtmi_eikonal_stats* stats) {
+    rtmi_eikonal_stats total{};
+    const size_t nn = (size_t)ep->nx * (size_t)ep->ny;
+    int device = 0, cus = 0;
+    if (S > 0) {
+        RTMI_HIP(hipGetDevice(&device));
+        RTMI_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    }
+    const MultiPlan plan = multi_choose(K, (size_t)S, nn, cus, ep->reserved[0] == 1, ep->reserved[1]);
+    const int C = plan.C;
+    const size_t lds_bytes = plan.lds_bytes;
+    const bool lds = plan.lds;
+    total.path = lds ? RTMI_EIKONAL_LDS : RTMI_EIKONAL_GLOBAL;
+    if (S > 0) {
+        const long diag = (long)std::min(ep->nx, ep->ny);
+        const int block = (int)std::min<long>(kMaxBlock, (diag + 63) / 64 * 64);
+        const size_t chunks = plan.chunks, gs = plan.gs, gc = plan.gc;
+        DevMem mem;
+        a.g = rt::eik_grid(ep->gx0, ep->gdx, ep->gy0, ep->gdy);
+        a.nx = (long)ep->nx;
+        a.ny = (long)ep->ny;
+        a.ball = ep->ball;
+        a.max_rounds = ep->max_rounds > 0 ? ep->max_rounds : rt::kEikDefaultRounds;
+        a.K = K;
+        a.S = (size_t)S;
+        if (!lds) {
+            RTMI_ALLOC(mem.get(&a.ca, gs * nn * sizeof(double)));
+            RTMI_ALLOC(mem.get(&a.cb, gs * nn * sizeof(double)));
+            RTMI_ALLOC(mem.get(&a.code, gs * nn));
+            if (ADJ) RTMI_ALLOC(mem.get(&a.kids, gs * nn));
+            RTMI_ALLOC(mem.get(&a.wv, gs * gc * nn * (size_t)C * sizeof(double)));
+        }
+        RTMI_ALLOC(mem.get(&a.wk, gs * gc * nn * (size_t)C * sizeof(double)));
+        unsigned long long* d_out = nullptr;
+        RTMI_ALLOC(mem.get(&d_out, (size_t)K * (size_t)S * kOutWords * sizeof(unsigned long long)));
+        a.out = d_out;
+        EventMarks<2> marks;
+        RTMI_HIP(marks.create());
+        RTMI_HIP(marks.mark(0));
+        for (size_t s0 = 0; s0 < (size_t)S; s0 += gs) {
+            const size_t ns = std::min(gs, (size_t)S - s0);
+            a.s0 = s0;
+            if (!lds) {
+                const long lanes = (long)(ns * nn);
+                hipLaunchKernelGGL(k_eikonal_lin_setup, blocks(lanes), dim3(256), 0, nullptr, a, lanes);
+                if (ADJ) hipLaunchKernelGGL(k_eikonal_lin_kids, blocks(lanes), dim3(256), 0, nullptr, a, lanes);
+                RTMI_HIP(hipGetLastError());
+            }
+            for (size_t ch = 0; ch < chunks; ch += gc) {
+                const size_t nc = std::min(gc, chunks - ch);
+                a.c0 = (int)(ch * (size_t)C);
+                const dim3 grid((unsigned)ns, (unsigned)nc);
+                if (C == 1) RTMI_RC((lin_multi_launch<ADJ, 1>(who, lds, lds_bytes, grid, block, a)));
+                else if (C == 4) RTMI_RC((lin_multi_launch<ADJ, 4>(who, lds, lds_bytes, grid, block, a)));
+                else RTMI_RC((lin_multi_launch<ADJ, 8>(who, lds, lds_bytes, grid, block, a)));
+            }
+        }
+        RTMI_HIP(marks.mark(1));
+        RTMI_HIP(marks.wait(1));
+        RTMI_HIP(marks.ms(0, 1, &total.kernel_ms));
+        std::vector<unsigned long long> out((size_t)K * (size_t)S * kOutWords);
+        RTMI_HIP(hipMemcpy(out.data(), d_out, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t cs = 0; cs < (size_t)K * (size_t)S; cs++) {
+            const unsigned long long* o = &out[cs * kOutWords];
+            const int32_t r = (int32_t)(o[0] & 0xffffffffull), clean = (int32_t)(o[0] >> 32);
+            if (rounds) {
+                rounds[2 * cs] = r;
+                rounds[2 * cs + 1] = clean;
+            }
+            total.free_nodes += (int64_t)o[1];
+            total.changes += (int64_t)o[2];
+            total.rounds_max = std::max(total.rounds_max, r);
+        }
+        total.filled = total.free_nodes;
+    }
+    if (stats) *stats = total;
+    return RTMI_OK;
+}
+
+// after check_eikonal: the column count, and the width that tests may force
+int check_nrhs(const char* who, const rtmi_eikonal_params* ep, int32_t nrhs) {
+    RTMI_ARG(nrhs >= 1 && nrhs <= RTMI_LSQR_MULTI_MAX, "nrhs must be in [1, " + std::to_string(RTMI_LSQR_MULTI_MAX) + "], got " + std::to_string(nrhs));
+    bool known = ep->reserved[1] == 0;
+    for (int w : kMultiWidths) known = known || ep->reserved[1] == w;
+    RTMI_ARG(known, "reserved[1] must be 0 or a compiled chunk width (1, 4, 8)");
+    return RTMI_OK;
+}
+
+}  // namespace
+
+RTMI_EXPORT int rtmi_eikonal_tangent_multi_dev(const rtmi_eikonal_params* ep, const double* d_n, int64_t S, const double* d_src,
+                                               const double* d_n_src, const double* d_T, const uint8_t* d_filled, int32_t nrhs,
+                                               const double* d_dn, const double* d_dn_src, const double* d_dT_seed, double* d_dT,
+                                               int32_t* rounds, rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_tangent_multi_dev";
+    RTMI_RC(check_eikonal(who, ep, d_n, S, d_src, d_n_src));
+    RTMI_RC(check_nrhs(who, ep, nrhs));
+    LinMultiArgs a{};
+    if (S > 0) {
+        RTMI_RC(check_lin(who, d_T, d_filled, d_dn, "dn", d_dT, "dT"));
+        int device = 0;
+        RTMI_HIP(hipGetDevice(&device));
+        const size_t K = (size_t)nrhs, nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn * sizeof(double);
+        RTMI_RC(check_device_pointer(device, who, d_n, nn * sizeof(double), "d_n"));
+        RTMI_RC(check_device_pointer(device, who, d_src, (size_t)S * 2 * sizeof(double), "d_src"));
+        RTMI_RC(check_device_pointer(device, who, d_n_src, (size_t)S * sizeof(double), "d_n_src"));
+        RTMI_RC(check_device_pointer(device, who, d_T, tab, "d_T"));
+        RTMI_RC(check_device_pointer(device, who, d_filled, (size_t)S * nn, "d_filled"));
+        RTMI_RC(check_device_pointer(device, who, d_dn, K * nn * sizeof(double), "d_dn"));
+        if (d_dn_src) RTMI_RC(check_device_pointer(device, who, d_dn_src, K * (size_t)S * sizeof(double), "d_dn_src"));
+        if (d_dT_seed) RTMI_RC(check_device_pointer(device, who, d_dT_seed, K * tab, "d_dT_seed"));
+        RTMI_RC(check_device_pointer(device, who, d_dT, K * tab, "d_dT"));
+    }
+    a.n = d_n; a.src = d_src; a.n_src = d_n_src; a.T = d_T; a.filled = d_filled;
+    a.dn = d_dn; a.dn_src = d_dn_src; a.seed = d_dT_seed; a.v = d_dT;
+    return lin_multi_dev<false>(who, ep, S, nrhs, a, rounds, stats);
+}
+
+RTMI_EXPORT int rtmi_eikonal_adjoint_multi_dev(const rtmi_eikonal_params* ep, const double* d_n, int64_t S, const double* d_src,
+                                               const double* d_n_src, const double* d_T, const uint8_t* d_filled, int32_t nrhs,
+                                               const double* d_r, double* d_lam, double* d_g, double* d_g_src, int32_t* rounds,
+                                               rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_adjoint_multi_dev";
+    RTMI_RC(check_eikonal(who, ep, d_n, S, d_src, d_n_src));
+    RTMI_RC(check_nrhs(who, ep, nrhs));
+    LinMultiArgs a{};
+    if (S > 0) {
+        RTMI_RC(check_lin(who, d_T, d_filled, d_r, "r", d_lam, "lam"));
+        int device = 0;
+        RTMI_HIP(hipGetDevice(&device));
+        const size_t K = (size_t)nrhs, nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn * sizeof(double);
+        RTMI_RC(check_device_pointer(device, who, d_n, nn * sizeof(double), "d_n"));
+        RTMI_RC(check_device_pointer(device, who, d_src, (size_t)S * 2 * sizeof(double), "d_src"));
+        RTMI_RC(check_device_pointer(device, who, d_n_src, (size_t)S * sizeof(double), "d_n_src"));
+        RTMI_RC(check_device_pointer(device, who, d_T, tab, "d_T"));
+        RTMI_RC(check_device_pointer(device, who, d_filled, (size_t)S * nn, "d_filled"));
+        RTMI_RC(check_device_pointer(device, who, d_r, K * tab, "d_r"));
+        RTMI_RC(check_device_pointer(device, who, d_lam, K * tab, "d_lam"));
+        if (d_g) RTMI_RC(check_device_pointer(device, who, d_g, K * tab, "d_g"));
+        if (d_g_src) RTMI_RC(check_device_pointer(device, who, d_g_src, K * (size_t)S * sizeof(double), "d_g_src"));
+    }
+    a.n = d_n; a.src = d_src; a.n_src = d_n_src; a.T = d_T; a.filled = d_filled;
+    a.r = d_r; a.v = d_lam; a.gout = d_g; a.g_src = d_g_src;
+    return lin_multi_dev<true>(who, ep, S, nrhs, a, rounds, stats);
+}
+
+RTMI_EXPORT int rtmi_eikonal_tangent_multi(const rtmi_eikonal_params* ep, const double* n, int64_t S, const double* src,
+                                           const double* n_src, const double* T, const uint8_t* filled, int32_t nrhs, const double* dn,
+                                           const double* dn_src, const double* dT_seed, double* dT, int32_t* rounds,
+                                           rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_tangent_multi";
+    RTMI_RC(check_eikonal(who, ep, n, S, src, n_src));
+    RTMI_RC(check_nrhs(who, ep, nrhs));
+    LinMultiArgs a{};
+    if (S == 0) return lin_multi_dev<false>(who, ep, 0, nrhs, a, rounds, stats);
+    RTMI_RC(check_lin(who, T, filled, dn, "dn", dT, "dT"));
+    const size_t K = (size_t)nrhs, nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn;
+    DevMem mem;
+    LinUpload u;
+    RTMI_RC(upload_lin(who, mem, ep, S, n, src, n_src, T, filled, &u));
+    double *d_dn = nullptr, *d_dn_src = nullptr, *d_seed = nullptr, *d_dT = nullptr;
+    RTMI_ALLOC(mem.get(&d_dn, K * nn * sizeof(double)));
+    RTMI_ALLOC(mem.get(&d_dT, K * tab * sizeof(double)));
+    RTMI_HIP(hipMemcpy(d_dn, dn, K * nn * sizeof(double), hipMemcpyHostToDevice));
+    if (dn_src) {
+        RTMI_ALLOC(mem.get(&d_dn_src, K * (size_t)S * sizeof(double)));
+        RTMI_HIP(hipMemcpy(d_dn_src, dn_src, K * (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (dT_seed) {
+        RTMI_ALLOC(mem.get(&d_seed, K * tab * sizeof(double)));
+        RTMI_HIP(hipMemcpy(d_seed, dT_seed, K * tab * sizeof(double), hipMemcpyHostToDevice));
+    }
+    a.n = u.n; a.src = u.src; a.n_src = u.n_src; a.T = u.T; a.filled = u.filled;
+    a.dn = d_dn; a.dn_src = d_dn_src; a.seed = d_seed; a.v = d_dT;
+    RTMI_RC(lin_multi_dev<false>(who, ep, S, nrhs, a, rounds, stats));
+    RTMI_HIP(hipMemcpy(dT, d_dT, K * tab * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_eikonal_adjoint_multi(const rtmi_eikonal_params* ep, const double* n, int64_t S, const double* src,
+                                           const double* n_src, const double* T, const uint8_t* filled, int32_t nrhs, const double* r,
+                                           double* lam, double* g, double* g_src, int32_t* rounds, rtmi_eikonal_stats* stats) {
+    const char* who = "rtmi_eikonal_adjoint_multi";
+    RTMI_RC(check_eikonal(who, ep, n, S, src, n_src));
+    RTMI_RC(check_nrhs(who, ep, nrhs));
+    LinMultiArgs a{};
+    if (S == 0) return lin_multi_dev<true>(who, ep, 0, nrhs, a, rounds, stats);
+    RTMI_RC(check_lin(who, T, filled, r, "r", lam, "lam"));
+    const size_t K = (size_t)nrhs, nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn;
+    DevMem mem;
+    LinUpload u;
+    RTMI_RC(upload_lin(who, mem, ep, S, n, src, n_src, T, filled, &u));
+    double *d_r = nullptr, *d_lam = nullptr, *d_g = nullptr, *d_g_src = nullptr;
+    RTMI_ALLOC(mem.get(&d_r, K * tab * sizeof(double)));
+    RTMI_ALLOC(mem.get(&d_lam, K * tab * sizeof(double)));
+    if (g) RTMI_ALLOC(mem.get(&d_g, K * tab * sizeof(double)));
+    if (g_src) RTMI_ALLOC(mem.get(&d_g_src, K * (size_t)S * sizeof(double)));
+    RTMI_HIP(hipMemcpy(d_r, r, K * tab * sizeof(double), hipMemcpyHostToDevice));
+    a.n = u.n; a.src = u.src; a.n_src = u.n_src; a.T = u.T; a.filled = u.filled;
+    a.r = d_r; a.v = d_lam; a.gout = d_g; a.g_src = d_g_src;
+    RTMI_RC(lin_multi_dev<true>(who, ep, S, nrhs, a, rounds, stats));
+    RTMI_HIP(hipMemcpy(lam, d_lam, K * tab * sizeof(double), hipMemcpyDeviceToHost));
+    if (g) RTMI_HIP(hipMemcpy(g, d_g, K * tab * sizeof(double), hipMemcpyDeviceToHost));
+    if (g_src) RTMI_HIP(hipMemcpy(g_src, d_g_src, K * (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}

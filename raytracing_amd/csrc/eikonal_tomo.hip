@@ -16,6 +16,9 @@
 //   k_etomo_residual  one lane per (source, receiver): pick - sample(T_s, rec_k) on a live row with a pick, else +0.0
 // Every loop bound comes from the host-built tables.  No floating-point atomics.  The solver is the loop of rt_lsqr_device.h with
 // one column over [A | Dx | Dy | Dxx | Dyy] on the node grid, the regulariser rows those of rt_tomo_reg.h.
+// Several columns per call (rtmi_eikonal_tomo_apply_multi, _transpose_multi, their _dev forms, _lsqr_multi, _set_column_group;
+// DESIGN.md section 37): the sample, spread and reduce kernels take the column in blockIdx.y, the sweeps are the batched ones of
+// eikonal_lin.hip, the work tables hold a group of columns, and the loop runs its columns in lock-step.
 #include <cstring>
 #include <new>
 #include <type_traits>
@@ -40,14 +43,22 @@ struct rtmi_eikonal_tomo {
     int64_t nt = 0;                                     // nodes the receivers touch
     int32_t *tnode = nullptr, *toff = nullptr, *tpair = nullptr;
     int32_t *soff = nullptr, *spair = nullptr;          // [nn + 1] and the (source, corner) pairs
-    double *tab = nullptr, *r = nullptr, *g = nullptr;  // [S][nn]: dT or lam; the adjoint's right-hand side; g
-    double *dn_src = nullptr, *g_src = nullptr;         // [S]
+    // The work tables hold `cols` columns and are the handle's own allocations, not mem's: a call that sweeps more grows them
+    double *tab = nullptr, *r = nullptr, *g = nullptr;  // [cols][S][nn]: dT or lam; the adjoint's right-hand side; g
+    double *dn_src = nullptr, *g_src = nullptr;         // [cols][S]
+    int cols = 0;
+    int cg = 0;                                         // rtmi_eikonal_tomo_set_column_group: columns swept together; 0: the default
     unsigned long long* red = nullptr;                  // kRedWords: a Vec's, and [4] k_etomo_reduce's flag
+    unsigned long long* redm = nullptr;                 // many columns': kMultiMax x kRedM of a Vec, then kMultiMax flags; on first use
     size_t bytes = 0;
     std::vector<uint8_t> live_h;
     std::vector<int64_t> live_per;
     int64_t live_rows = 0;
     int32_t path = 0, fill_rounds = 0;
+    double** table(int i) { return i == 0 ? &tab : i == 1 ? &r : i == 2 ? &g : i == 3 ? &dn_src : &g_src; }
+    ~rtmi_eikonal_tomo() {
+        for (int i = 0; i < 5; i++) (void)hipFree(*table(i));
+    }
 };
 
 namespace {
@@ -57,9 +68,11 @@ static_assert(kFlagWord >= kRedM && kFlagWord < kRedWords, "the flag is a word o
 
 __global__ void __launch_bounds__(256) k_etomo_sample(const double* __restrict__ v, size_t vs, const int32_t* __restrict__ idx,
                                                       const double* __restrict__ w, const uint8_t* __restrict__ flag, size_t fs, long P,
-                                                      long total, bool keep, double* __restrict__ out) {
+                                                      long total, bool keep, double* __restrict__ out, size_t vcs, size_t ocs) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
+    v += blockIdx.y * vcs;                              // the column in blockIdx.y: its planes of v and of out
+    out += blockIdx.y * ocs;
     const long k = t % P, s = t / P;
     if (!flag[(size_t)s * fs + k]) {
         if (!keep) out[t] = 0.0;
@@ -81,9 +94,11 @@ __global__ void __launch_bounds__(256) k_etomo_live(const double* __restrict__ n
 __global__ void __launch_bounds__(256) k_etomo_spread(const double* __restrict__ y, const uint8_t* __restrict__ live, long R, long nt,
                                                       const int32_t* __restrict__ tnode, const int32_t* __restrict__ toff,
                                                       const int32_t* __restrict__ tpair, const double* __restrict__ w, size_t nn, long total,
-                                                      double* __restrict__ r) {
+                                                      double* __restrict__ r, size_t ycs, size_t rcs) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
+    y += blockIdx.y * ycs;                              // the column in blockIdx.y
+    r += blockIdx.y * rcs;
     const long q = t % nt, s = t / nt;
     double acc = 0.0;
     for (int32_t p = toff[q]; p < toff[q + 1]; p++) {
@@ -96,9 +111,14 @@ __global__ void __launch_bounds__(256) k_etomo_spread(const double* __restrict__
 
 __global__ void __launch_bounds__(256) k_etomo_reduce(const double* __restrict__ g, const double* __restrict__ g_src, long S, long nn,
                                                       const int32_t* __restrict__ soff, const int32_t* __restrict__ spair,
-                                                      const double* __restrict__ sw, double* __restrict__ G, unsigned long long* flag) {
+                                                      const double* __restrict__ sw, double* __restrict__ G, unsigned long long* flag,
+                                                      size_t gcs, size_t scs) {
     const long x = (long)blockIdx.x * 256 + threadIdx.x;
     if (x >= nn) return;
+    g += blockIdx.y * gcs;                              // the column in blockIdx.y: its planes, its G and its flag word
+    g_src += blockIdx.y * scs;
+    G += blockIdx.y * (size_t)nn;
+    flag += blockIdx.y;
     double acc = 0.0;
     for (long s = 0; s < S; s++) acc = acc + g[(size_t)s * nn + x];
     for (int32_t p = soff[x]; p < soff[x + 1]; p++) {
@@ -140,10 +160,49 @@ int not_clean(const char* who, const rtmi_eikonal_tomo* h, const std::vector<int
     return RTMI_OK;
 }
 
+// the same for the kc columns from column c0 on of a batched sweep: rounds [kc][S][2]
+int not_clean(const char* who, const rtmi_eikonal_tomo* h, const std::vector<int32_t>& rounds, int kc, int c0, const char* what) {
+    for (int c = 0; c < kc; c++)
+        for (int64_t s = 0; s < h->S; s++)
+            if (!rounds[2 * ((size_t)c * (size_t)h->S + (size_t)s) + 1])
+                return rtmi_internal_fail(RTMI_ERR_STATE, (std::string(who) + ": " + what + " of source " + std::to_string(s) + ", column " +
+                                                           std::to_string(c0 + c) + " did not converge within max_rounds").c_str());
+    return RTMI_OK;
+}
+
+// The work tables for `want` columns: kept, and replaced by a larger set when a call sweeps more together.  A growth that fails
+// leaves the tables the handle had, so every call that they serve still works
+int ensure_cols(rtmi_eikonal_tomo* h, const char* who, int want) {
+    if (h->cols >= want) return RTMI_OK;
+    const size_t tab = (size_t)h->S * h->nn * sizeof(double), vec = (size_t)h->S * sizeof(double);
+    double* fresh[5] = {};
+    for (int i = 0; i < 5; i++)
+        if (hipMalloc((void**)&fresh[i], (size_t)want * (i < 3 ? tab : vec)) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int k = 0; k < i; k++) (void)hipFree(fresh[k]);
+            return rtmi_internal_fail(RTMI_ERR_ALLOC, (std::string(who) + ": hipMalloc of the work tables of " + std::to_string(want) +
+                                                       " columns failed").c_str());
+        }
+    for (int i = 0; i < 5; i++) {
+        (void)hipFree(*h->table(i));
+        *h->table(i) = fresh[i];
+    }
+    h->bytes += (size_t)(want - h->cols) * (3 * tab + 2 * vec);
+    h->cols = want;
+    return RTMI_OK;
+}
+
+// the columns a batched call sweeps together: the caller's, or as many as keep the work tables under 8 GiB
+int column_group(const rtmi_eikonal_tomo* h, int K) {
+    const size_t per = (size_t)h->S * (3 * h->nn + 2) * sizeof(double);
+    const size_t fit = std::max<size_t>(1, ((size_t)8 << 30) / per);
+    return (int)std::min<size_t>((size_t)K, h->cg > 0 ? (size_t)h->cg : fit);
+}
+
 // the sources' samples of a model-sized vector: out [S]; keep: a source outside the grid keeps its value, else it gets +0.0
 int sample_sources(const rtmi_eikonal_tomo* h, const char* who, const double* d_v, bool keep, double* out) {
     hipLaunchKernelGGL(k_etomo_sample, blocks((long)h->S), dim3(256), 0, nullptr, d_v, (size_t)0, h->sidx, h->sw, h->inside, (size_t)0,
-                       (long)h->S, (long)h->S, keep, out);
+                       (long)h->S, (long)h->S, keep, out, (size_t)0, (size_t)0);
     RTMI_HIP(hipGetLastError());
     return RTMI_OK;
 }
@@ -210,7 +269,7 @@ int apply_dev(rtmi_eikonal_tomo* h, const char* who, const double* d_dn, double*
     RTMI_RC(not_clean(who, h, rounds, "the tangent sweep"));
     RTMI_HIP(marks.mark(2));
     hipLaunchKernelGGL(k_etomo_sample, blocks(rows), dim3(256), 0, nullptr, h->tab, h->nn, h->ridx, h->rw, h->live, (size_t)h->R, (long)h->R,
-                       rows, false, d_y);
+                       rows, false, d_y, (size_t)0, (size_t)0);
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(marks.mark(3));
     RTMI_HIP(marks.wait(3));
@@ -234,7 +293,7 @@ int transpose_dev(rtmi_eikonal_tomo* h, const char* who, const double* d_y, doub
     RTMI_HIP(hipMemsetAsync(h->r, 0, tab * sizeof(double), nullptr));
     const long lanes = (long)(h->S * h->nt);
     hipLaunchKernelGGL(k_etomo_spread, blocks(lanes), dim3(256), 0, nullptr, d_y, h->live, (long)h->R, (long)h->nt, h->tnode, h->toff, h->tpair,
-                       h->rw, h->nn, lanes, h->r);
+                       h->rw, h->nn, lanes, h->r, (size_t)0, (size_t)0);
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(marks.mark(1));
     std::vector<int32_t> rounds(2 * (size_t)h->S);
@@ -244,7 +303,7 @@ int transpose_dev(rtmi_eikonal_tomo* h, const char* who, const double* d_y, doub
     RTMI_HIP(marks.mark(2));
     RTMI_HIP(hipMemsetAsync(h->red + kFlagWord, 0, sizeof(unsigned long long), nullptr));
     hipLaunchKernelGGL(k_etomo_reduce, blocks((long)h->nn), dim3(256), 0, nullptr, h->g, h->g_src, (long)h->S, (long)h->nn, h->soff, h->spair,
-                       h->sw, d_G, h->red + kFlagWord);
+                       h->sw, d_G, h->red + kFlagWord, (size_t)0, (size_t)0);
     RTMI_HIP(hipGetLastError());
     RTMI_HIP(marks.mark(3));
     unsigned long long flag = 0;
@@ -259,6 +318,109 @@ int transpose_dev(rtmi_eikonal_tomo* h, const char* who, const double* d_y, doub
         pt->sweep_ms += es.kernel_ms;
         pt->rounds_max = std::max(pt->rounds_max, es.rounds_max);
     }
+    return RTMI_OK;
+}
+
+// ----------------------------------------------------------------------------------------------- several columns per product
+// Column c of a batched product is the product above on column c: the sweeps are rtmi_eikonal_tangent_multi_dev and
+// rtmi_eikonal_adjoint_multi_dev, whose columns have the single sweeps' bits, and the kernels round them take the column in
+// blockIdx.y.  K columns are walked in runs of at most column_group() consecutive columns of `mask`; a column outside it is
+// neither read nor written.
+
+// the many columns' reduction words, on first use
+int ensure_redm(rtmi_eikonal_tomo* h, const char* who) {
+    if (h->redm) return RTMI_OK;
+    const size_t words = (size_t)kMultiMax * kRedM + (size_t)kMultiMax;
+    RTMI_ALLOC(h->mem.get(&h->redm, words * sizeof(unsigned long long)));
+    RTMI_HIP(hipMemset(h->redm, 0, words * sizeof(unsigned long long)));
+    h->bytes += words * sizeof(unsigned long long);
+    return RTMI_OK;
+}
+
+// f(c0, kc) for every run of consecutive columns of mask, cut at cg columns
+template <typename F> int by_runs(int K, unsigned long long mask, int cg, F&& f) {
+    for (int c0 = 0; c0 < K;) {
+        if (!(mask & col_bit(c0))) { c0++; continue; }
+        int kc = 1;
+        while (kc < cg && c0 + kc < K && (mask & col_bit(c0 + kc))) kc++;
+        RTMI_RC(f(c0, kc));
+        c0 += kc;
+    }
+    return RTMI_OK;
+}
+
+// y + c ys = A (dn + c nn) for the columns c < K of mask, on device pointers
+int apply_multi_dev(rtmi_eikonal_tomo* h, const char* who, int K, const double* d_dn, double* d_y, size_t ys, unsigned long long mask,
+                    ProductTimes* pt) {
+    const long rows = (long)(h->S * h->R);
+    const int cg = column_group(h, K);
+    RTMI_RC(ensure_cols(h, who, cg));
+    const size_t tab = (size_t)h->S * h->nn;
+    std::vector<int32_t> rounds(2 * (size_t)cg * (size_t)h->S);
+    const double t0 = now_ms();
+    RTMI_RC(by_runs(K, mask, cg, [&](int c0, int kc) {
+        const double* dn = d_dn + (size_t)c0 * h->nn;
+        hipLaunchKernelGGL(k_etomo_sample, dim3(blocks((long)h->S).x, (unsigned)kc), dim3(256), 0, nullptr, dn, (size_t)0, h->sidx, h->sw,
+                           h->inside, (size_t)0, (long)h->S, (long)h->S, false, h->dn_src, h->nn, (size_t)h->S);
+        RTMI_HIP(hipGetLastError());
+        rtmi_eikonal_stats es{};
+        RTMI_RC(rtmi_eikonal_tangent_multi_dev(&h->ep, h->n, h->S, h->src, h->n_src, h->T, h->filled, kc, dn, h->dn_src, nullptr, h->tab,
+                                               rounds.data(), &es));
+        RTMI_RC(not_clean(who, h, rounds, kc, c0, "the tangent sweep"));
+        hipLaunchKernelGGL(k_etomo_sample, dim3(blocks(rows).x, (unsigned)kc), dim3(256), 0, nullptr, h->tab, h->nn, h->ridx, h->rw, h->live,
+                           (size_t)h->R, (long)h->R, rows, false, d_y + (size_t)c0 * ys, tab, ys);
+        RTMI_HIP(hipGetLastError());
+        if (pt) {
+            pt->sweep_ms += es.kernel_ms;
+            pt->rounds_max = std::max(pt->rounds_max, es.rounds_max);
+        }
+        return (int)RTMI_OK;
+    }));
+    RTMI_HIP(hipStreamSynchronize(nullptr));
+    if (pt) pt->kernel_ms += now_ms() - t0 - pt->sweep_ms;
+    return RTMI_OK;
+}
+
+// G + c nn = A^T (y + c ys) for the columns c < K of mask.  range [K] (or NULL): a value of the column's G is not finite
+int transpose_multi_dev(rtmi_eikonal_tomo* h, const char* who, int K, const double* d_y, size_t ys, double* d_G, unsigned long long mask,
+                        bool* range, ProductTimes* pt) {
+    const int cg = column_group(h, K);
+    RTMI_RC(ensure_cols(h, who, cg));
+    RTMI_RC(ensure_redm(h, who));
+    unsigned long long* flags = h->redm + (size_t)kMultiMax * kRedM;
+    const size_t tab = (size_t)h->S * h->nn;
+    const long lanes = (long)(h->S * h->nt);
+    std::vector<int32_t> rounds(2 * (size_t)cg * (size_t)h->S);
+    const double t0 = now_ms();
+    RTMI_RC(by_runs(K, mask, cg, [&](int c0, int kc) {
+        RTMI_HIP(hipMemsetAsync(h->r, 0, (size_t)kc * tab * sizeof(double), nullptr));
+        hipLaunchKernelGGL(k_etomo_spread, dim3(blocks(lanes).x, (unsigned)kc), dim3(256), 0, nullptr, d_y + (size_t)c0 * ys, h->live, (long)h->R,
+                           (long)h->nt, h->tnode, h->toff, h->tpair, h->rw, h->nn, lanes, h->r, ys, tab);
+        RTMI_HIP(hipGetLastError());
+        rtmi_eikonal_stats es{};
+        RTMI_RC(rtmi_eikonal_adjoint_multi_dev(&h->ep, h->n, h->S, h->src, h->n_src, h->T, h->filled, kc, h->r, h->tab, h->g, h->g_src,
+                                               rounds.data(), &es));
+        RTMI_RC(not_clean(who, h, rounds, kc, c0, "the adjoint sweep"));
+        RTMI_HIP(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(unsigned long long), nullptr));
+        hipLaunchKernelGGL(k_etomo_reduce, dim3(blocks((long)h->nn).x, (unsigned)kc), dim3(256), 0, nullptr, h->g, h->g_src, (long)h->S,
+                           (long)h->nn, h->soff, h->spair, h->sw, d_G + (size_t)c0 * h->nn, flags, tab, (size_t)h->S);
+        RTMI_HIP(hipGetLastError());
+        unsigned long long f[kMultiMax];
+        RTMI_HIP(hipMemcpy(f, flags, (size_t)kc * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (range)
+            for (int c = 0; c < kc; c++) range[c0 + c] = f[c] != 0;
+        if (pt) {
+            pt->sweep_ms += es.kernel_ms;
+            pt->rounds_max = std::max(pt->rounds_max, es.rounds_max);
+        }
+        return (int)RTMI_OK;
+    }));
+    if (pt) pt->kernel_ms += now_ms() - t0 - pt->sweep_ms;
+    return RTMI_OK;
+}
+
+int check_nrhs(const char* who, int32_t nrhs) {
+    RTMI_ARG(nrhs >= 1 && nrhs <= kMultiMax, "nrhs must be in [1, " + std::to_string(kMultiMax) + "], got " + std::to_string(nrhs));
     return RTMI_OK;
 }
 
@@ -371,11 +533,7 @@ RTMI_EXPORT int rtmi_eikonal_tomo_create(const rtmi_eikonal_params* ep, const do
     RTMI_ALLOC(up(&h->soff, soff.data(), soff.size()));
     RTMI_ALLOC(up(&h->spair, LS.pair.data(), LS.pair.size()));
     RTMI_ALLOC(up(&h->live, (const uint8_t*)nullptr, rows));
-    RTMI_ALLOC(up(&h->tab, (const double*)nullptr, tab));
-    RTMI_ALLOC(up(&h->r, (const double*)nullptr, tab));
-    RTMI_ALLOC(up(&h->g, (const double*)nullptr, tab));
-    RTMI_ALLOC(up(&h->dn_src, (const double*)nullptr, (size_t)S));
-    RTMI_ALLOC(up(&h->g_src, (const double*)nullptr, (size_t)S));
+    RTMI_RC(ensure_cols(h, who, 1));
     RTMI_ALLOC(up(&h->red, (const unsigned long long*)nullptr, kRedWords));
     RTMI_HIP(hipMemset(h->red, 0, kRedWords * sizeof(unsigned long long)));
     rtmi_eikonal_stats sweeps{};                              // a call with no source does no work and names the sweeps' path
@@ -592,5 +750,194 @@ RTMI_EXPORT int rtmi_eikonal_tomo_lsqr(rtmi_eikonal_tomo* h, const rtmi_lsqr_par
     out.operator_ms = operator_ms;
     out.bytes_device = (int64_t)(doubles * sizeof(double) + h->bytes);
     if (st) *st = out;
+    return RTMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ several columns: the entries
+RTMI_EXPORT int rtmi_eikonal_tomo_set_column_group(rtmi_eikonal_tomo* h, int32_t cg) {
+    const char* who = "rtmi_eikonal_tomo_set_column_group";
+    RTMI_ARG(h, "null handle");
+    RTMI_ARG(cg >= 0 && cg <= kMultiMax, "cg must be in [0, " + std::to_string(kMultiMax) + "], got " + std::to_string(cg));
+    h->cg = cg;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_eikonal_tomo_apply_multi_dev(rtmi_eikonal_tomo* h, int32_t nrhs, const double* d_dn, double* d_y,
+                                                  rtmi_eikonal_tomo_stats* st) {
+    const char* who = "rtmi_eikonal_tomo_apply_multi_dev";
+    RTMI_ARG(h, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_RC(on_device(h, who));
+    const size_t rows = (size_t)(h->S * h->R);
+    RTMI_RC(check_vec(h, who, d_dn, (size_t)nrhs * h->nn, "d_dn"));
+    RTMI_RC(check_vec(h, who, d_y, (size_t)nrhs * rows, "d_y"));
+    ProductTimes pt;
+    RTMI_RC(apply_multi_dev(h, who, nrhs, d_dn, d_y, rows, all_cols(nrhs), &pt));
+    fill_stats(h, pt, st);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_eikonal_tomo_transpose_multi_dev(rtmi_eikonal_tomo* h, int32_t nrhs, const double* d_y, double* d_G,
+                                                      rtmi_eikonal_tomo_stats* st) {
+    const char* who = "rtmi_eikonal_tomo_transpose_multi_dev";
+    RTMI_ARG(h, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_RC(on_device(h, who));
+    const size_t rows = (size_t)(h->S * h->R);
+    RTMI_RC(check_vec(h, who, d_y, (size_t)nrhs * rows, "d_y"));
+    RTMI_RC(check_vec(h, who, d_G, (size_t)nrhs * h->nn, "d_G"));
+    ProductTimes pt;
+    RTMI_RC(transpose_multi_dev(h, who, nrhs, d_y, rows, d_G, all_cols(nrhs), nullptr, &pt));
+    fill_stats(h, pt, st);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_eikonal_tomo_apply_multi(rtmi_eikonal_tomo* h, int32_t nrhs, const double* dn, double* y, rtmi_eikonal_tomo_stats* st) {
+    const char* who = "rtmi_eikonal_tomo_apply_multi";
+    RTMI_ARG(h, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    const size_t rows = (size_t)(h->S * h->R);
+    ProductTimes pt;
+    RTMI_RC(host_call(h, who, dn, (size_t)nrhs * h->nn, "dn", y, (size_t)nrhs * rows, "y", [&](const double* a, double* b) {
+        return apply_multi_dev(h, who, nrhs, a, b, rows, all_cols(nrhs), &pt);
+    }));
+    fill_stats(h, pt, st);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_eikonal_tomo_transpose_multi(rtmi_eikonal_tomo* h, int32_t nrhs, const double* y, double* G,
+                                                  rtmi_eikonal_tomo_stats* st) {
+    const char* who = "rtmi_eikonal_tomo_transpose_multi";
+    RTMI_ARG(h, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    const size_t rows = (size_t)(h->S * h->R);
+    ProductTimes pt;
+    RTMI_RC(host_call(h, who, y, (size_t)nrhs * rows, "y", G, (size_t)nrhs * h->nn, "G", [&](const double* a, double* b) {
+        return transpose_multi_dev(h, who, nrhs, a, rows, b, all_cols(nrhs), nullptr, &pt);
+    }));
+    fill_stats(h, pt, st);
+    return RTMI_OK;
+}
+
+// The solver on K columns: the loop of rt_lsqr_device.h in lock-step over planes, as rtmi_tomo_lsqr_multi runs it; the products are
+// the batched ones on the columns still in the loop, the regulariser kernels are launched per live column.  Column c has the bits of
+// rtmi_eikonal_tomo_lsqr on column c: every pass of the loop treats its columns alone, and so do the products.
+RTMI_EXPORT int rtmi_eikonal_tomo_lsqr_multi(rtmi_eikonal_tomo* h, const rtmi_lsqr_params* lp, const rtmi_lsqr_options* lo,
+                                             const rtmi_tomo_reg* reg, int32_t nrhs, int32_t flags, const double* rhs, double* x,
+                                             double* history, rtmi_lsqr_stats* st) {
+    const char* who = "rtmi_eikonal_tomo_lsqr_multi";
+    RTMI_ARG(h, "null handle");
+    RTMI_RC(check_nrhs(who, nrhs));
+    RTMI_ARG((flags & ~RTMI_LSQR_MULTI_ROW_WEIGHT) == 0, "flags has bits other than RTMI_LSQR_MULTI_ROW_WEIGHT");
+    RTMI_ARG(lp, "null params");
+    RTMI_ARG(rhs, "null rhs");
+    RTMI_ARG(x, "null x");
+    RTMI_RC(lsqr_check_params(who, lp));
+    const double *d1 = nullptr, *d2 = nullptr;
+    RTMI_RC(check_reg(who, reg, &d1, &d2));
+    const int K = (int)nrhs;
+    const bool wr_cols = (flags & RTMI_LSQR_MULTI_ROW_WEIGHT) != 0;
+    const size_t rows = (size_t)(h->S * h->R), ng = h->nn, gx = (size_t)h->ep.nx, gy = (size_t)h->ep.ny;
+    for (size_t i = 0; i < (size_t)K * rows; i++)
+        RTMI_ARG(std::isfinite(rhs[i]), "rhs has a value that is not finite in column " + std::to_string(i / rows));
+    const size_t nwr = (wr_cols ? (size_t)K : 1) * rows;
+    RTMI_RC(lsqr_check_options(who, lo, nwr, ng));
+    if (lo && lo->row_weight)
+        for (size_t i = 0; i < nwr; i++)
+            RTMI_ARG(h->live_h[i % rows] || lo->row_weight[i] == 0.0, "row_weight is not zero on dead row " + std::to_string(i % rows) +
+                                                                           (wr_cols ? " of column " + std::to_string(i / rows) : std::string()));
+    RTMI_RC(on_device(h, who));
+    const size_t n1x = d1 ? gy * (gx - 1) : 0, n1y = d1 ? (gy - 1) * gx : 0;
+    const size_t n2x = d2 && gx > 2 ? gy * (gx - 2) : 0, n2y = d2 && gy > 2 ? (gy - 2) * gx : 0;
+    const size_t per = rows + n1x + n1y + n2x + n2y;
+    const double t_begin = now_ms();
+    const std::string no_mem = std::string(who) + ": hipMalloc failed";
+    RTMI_RC(ensure_redm(h, who));
+    DevMem mem;
+    size_t doubles = 0;
+    auto get = [&](double** q, size_t n) {
+        doubles += n;
+        return mem.get(q, n * sizeof(double)) == hipSuccess;
+    };
+    double *u = nullptr, *Av = nullptr, *v = nullptr, *w = nullptr, *xd = nullptr, *Atu = nullptr, *x0 = nullptr;
+    for (double** q : {&u, &Av})
+        if (!get(q, (size_t)K * per)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    for (double** q : {&v, &w, &xd, &Atu})
+        if (!get(q, (size_t)K * ng)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+    if (lo && lo->x0) {
+        if (!get(&x0, ng)) return rtmi_internal_fail(RTMI_ERR_ALLOC, no_mem.c_str());
+        RTMI_HIP(hipMemcpy(x0, lo->x0, ng * sizeof(double), hipMemcpyHostToDevice));
+    }
+    LsqrOptions O;
+    size_t nopt = 0;
+    RTMI_RC(lsqr_upload_options(who, mem, lo, K, wr_cols, rows, per, ng, &O, &nopt));
+    doubles += nopt;
+    const Vec V{h->redm, h->cus, K};
+    double operator_ms = 0.0;
+    auto each = [&](unsigned long long mask, auto&& f) {
+        for (int c = 0; c < K; c++)
+            if (mask & col_bit(c)) RTMI_RC(f((size_t)c));
+        return (int)RTMI_OK;
+    };
+    auto Ax = [&](const double* s, double* y, unsigned long long mask) {
+        const double t0 = now_ms();
+        RTMI_RC(apply_multi_dev(h, who, K, s, y, per, mask, nullptr));
+        operator_ms += now_ms() - t0;                         // the regulariser's forward rows are outside it
+        if (d1 || d2)
+            RTMI_RC(each(mask, [&](size_t c) {
+                const double* sc = s + c * ng;
+                double* yk = y + c * per + rows;
+                if (d1) hipLaunchKernelGGL(k_tomo_diff, blocks((long)ng), dim3(256), 0, nullptr, sc, (int)gx, (int)gy, d1[0], d1[1], yk, yk + n1x);
+                if (d2)
+                    hipLaunchKernelGGL(k_tomo_diff2, blocks((long)ng), dim3(256), 0, nullptr, sc, (int)gx, (int)gy, d2[0], d2[1], yk + n1x + n1y,
+                                       yk + n1x + n1y + n2x);
+                RTMI_HIP(hipGetLastError());
+                return (int)RTMI_OK;
+            }));
+        return (int)RTMI_OK;
+    };
+    auto At = [&](const double* s, double* g, unsigned long long mask, bool* range) {
+        const double t0 = now_ms();
+        RTMI_RC(transpose_multi_dev(h, who, K, s, per, g, mask, range, nullptr));
+        unsigned long long ok = 0ull;
+        for (int c = 0; c < K; c++)
+            if ((mask & col_bit(c)) && !range[c]) ok |= col_bit(c);
+        if (d1 || d2)
+            RTMI_RC(each(ok, [&](size_t c) {
+                const double* sk = s + c * per + rows;
+                hipLaunchKernelGGL(k_tomo_reg_t, blocks((long)ng), dim3(256), 0, nullptr, g + c * ng, (int)gx, (int)gy, d1 ? sk : nullptr,
+                                   d1 ? sk + n1x : nullptr, d1 ? d1[0] : 0.0, d1 ? d1[1] : 0.0, d2 ? sk + n1x + n1y : nullptr,
+                                   d2 ? sk + n1x + n1y + n2x : nullptr, d2 ? d2[0] : 0.0, d2 ? d2[1] : 0.0);
+                RTMI_HIP(hipGetLastError());
+                return (int)RTMI_OK;
+            }));
+        RTMI_HIP(hipStreamSynchronize(nullptr));
+        operator_ms += now_ms() - t0;
+        return (int)RTMI_OK;
+    };
+    // the right-hand sides go up once: column c into the first S R values of plane c
+    RTMI_HIP(hipMemsetAsync(u, 0, (size_t)K * per * sizeof(double), nullptr));
+    RTMI_HIP(hipMemsetAsync(xd, 0, (size_t)K * ng * sizeof(double), nullptr));
+    RTMI_HIP(hipStreamSynchronize(nullptr));
+    RTMI_HIP(hipMemcpy2D(u, per * sizeof(double), rhs, rows * sizeof(double), rows * sizeof(double), (size_t)K, hipMemcpyHostToDevice));
+    if (x0) {                                                                         // u = fl(rhs - A x0) over the data rows; A x0 once
+        const double t0 = now_ms();
+        RTMI_RC(apply_dev(h, who, x0, Av, nullptr));
+        RTMI_RC(lsqr_sub_start(who, V, u, per, Av, rows));
+        RTMI_HIP(hipStreamSynchronize(nullptr));
+        operator_ms += now_ms() - t0;
+    }
+    if (history) std::memset(history, 0, (size_t)K * (size_t)lp->iter_lim * 4 * sizeof(double));
+    std::vector<rtmi_lsqr_stats> out((size_t)K);
+    RTMI_RC(lsqr_loop(who, V, lp, per, ng, LsqrVectors{u, Av, v, w, xd, Atu}, Ax, At, history, out.data(), O));
+    if (x0) RTMI_RC(lsqr_add_start(who, V, xd, ng, x0, ng));
+    RTMI_HIP(hipMemcpy(x, xd, (size_t)K * ng * sizeof(double), hipMemcpyDeviceToHost));
+    const double total = now_ms() - t_begin;
+    for (int c = 0; c < K; c++) {
+        out[(size_t)c].total_ms = total;
+        out[(size_t)c].operator_ms = operator_ms;
+        out[(size_t)c].bytes_device = (int64_t)(doubles * sizeof(double) + h->bytes);
+        if (st) st[c] = out[(size_t)c];
+    }
     return RTMI_OK;
 }

@@ -176,6 +176,43 @@ RT_EIK_HD double eik_lin_adjoint_gather(long nx, long x, uint8_t kids, double r,
     return acc;
 }
 
+// Both gathers on C columns at once (k_eikonal_lin_multi): v, k and r are column-minor, [ny nx][C], and column c of t gets what the
+// gather above gives on column c alone: the same operations in the same order, the node's code and coefficients read once
+template <int C> RT_EIK_HD void eik_lin_tangent_gather_cols(long nx, long x, uint8_t code, double ca, double cb, const double* k,
+                                                            const double* v, double* t) {
+    for (int c = 0; c < C; c++) t[c] = 0.0;
+    if (code & kLinXParent) {
+        const double* p = v + (code & kLinXEast ? x + 1 : x - 1) * C;
+        for (int c = 0; c < C; c++) t[c] = t[c] + ca * p[c];
+    }
+    if (code & kLinYParent) {
+        const double* p = v + (code & kLinYNorth ? x + nx : x - nx) * C;
+        for (int c = 0; c < C; c++) t[c] = t[c] + cb * p[c];
+    }
+    for (int c = 0; c < C; c++) t[c] = t[c] + k[x * C + c];
+}
+
+template <int C> RT_EIK_HD void eik_lin_adjoint_gather_cols(long nx, long x, uint8_t kids, const double* r, const double* ca,
+                                                            const double* cb, const double* v, double* t) {
+    for (int c = 0; c < C; c++) t[c] = r[x * C + c];
+    if (kids & kLinKidWest) {
+        const double w = ca[x - 1], *p = v + (x - 1) * C;
+        for (int c = 0; c < C; c++) t[c] = t[c] + w * p[c];
+    }
+    if (kids & kLinKidEast) {
+        const double w = ca[x + 1], *p = v + (x + 1) * C;
+        for (int c = 0; c < C; c++) t[c] = t[c] + w * p[c];
+    }
+    if (kids & kLinKidSouth) {
+        const double w = cb[x - nx], *p = v + (x - nx) * C;
+        for (int c = 0; c < C; c++) t[c] = t[c] + w * p[c];
+    }
+    if (kids & kLinKidNorth) {
+        const double w = cb[x + nx], *p = v + (x + nx) * C;
+        for (int c = 0; c < C; c++) t[c] = t[c] + w * p[c];
+    }
+}
+
 // the directions of sweep k of a round
 RT_EIK_HD bool eik_lin_xup(bool adjoint, int k) { return adjoint ? (k == 1 || k == 2) : (k == 0 || k == 3); }
 RT_EIK_HD bool eik_lin_yup(bool adjoint, int k) { return adjoint ? k >= 2 : k < 2; }

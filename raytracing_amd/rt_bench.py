@@ -1615,14 +1615,16 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     return res
 
 
-def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False):
-    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny)"""
+def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False, _width=0):
+    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny); _global_path and _width (the chunk width of the batched sweeps)
+    are for tests: no result depends on them"""
     gx0, gdx, nx, gy0, gdy, ny = grid
     ep = _lib.EikonalParams()
     ep.gx0 = float(gx0); ep.gdx = float(gdx); ep.nx = int(nx)
     ep.gy0 = float(gy0); ep.gdy = float(gdy); ep.ny = int(ny)
     ep.ball = float(ball); ep.max_rounds = int(max_rounds)
     ep.reserved[0] = int(bool(_global_path))
+    ep.reserved[1] = int(_width)
     return ep
 
 
@@ -1902,6 +1904,119 @@ def eikonal_adjoint_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0,
     return res
 
 
+def _eikonal_multi_result(out, rounds, st, stats):
+    out["rounds"], out["converged"] = rounds[:, :, 0].copy(), rounds[:, :, 1].copy()
+    if stats:
+        out["stats"] = eikonal_stats(st)
+    return out
+
+
+def eikonal_tangent_multi(field_or_n, sources, grid, fill_result, dn, *, n_src=None, dn_src=None, dT_seed=None, ball=2.0,
+                          max_rounds=0, stats=False, _global_path=False, _width=0):
+    """eikonal_tangent on K columns in one call (rtmi_eikonal_tangent_multi): dn [K, ny, nx], dn_src [K, S] or None,
+    dT_seed [K, S, ny, nx] or None, 1 <= K <= 64.  Returns a dict: dT [K, S, ny, nx], rounds and converged [K, S], and with
+    stats=True 'stats' (sums over the columns).  Column c has the bits of eikonal_tangent on column c alone."""
+    who = "eikonal_tangent_multi"
+    n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
+    S = shape[0]
+    dn = np.ascontiguousarray(dn, dtype=np.float64)
+    if dn.ndim != 3 or dn.shape[1:] != shape[1:]:
+        raise ValueError(f"{who}: dn must be [K, ny, nx]")
+    K = dn.shape[0]
+    dn_src = _eikonal_lin_array(who, "dn_src", dn_src, (K, S))
+    dT_seed = _eikonal_lin_array(who, "dT_seed", dT_seed, (K,) + shape)
+    dT = np.zeros((K,) + shape)
+    rounds = np.zeros((K, S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    st = _lib.EikonalStats()
+    check(lib().rtmi_eikonal_tangent_multi(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
+                                           filled.ctypes.data_as(C.POINTER(C.c_uint8)), K, dptr(dn), dptr(dn_src), dptr(dT_seed),
+                                           dptr(dT), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    return _eikonal_multi_result({"dT": dT}, rounds, st, stats)
+
+
+def eikonal_adjoint_multi(field_or_n, sources, grid, fill_result, r, *, n_src=None, ball=2.0, max_rounds=0, stats=False,
+                          _global_path=False, _width=0):
+    """eikonal_adjoint on K columns in one call (rtmi_eikonal_adjoint_multi): r [K, S, ny, nx], 1 <= K <= 64.
+    Returns a dict: lam and g [K, S, ny, nx], g_src, rounds and converged [K, S], and with stats=True 'stats'.  Column c has the
+    bits of eikonal_adjoint on column c alone."""
+    who = "eikonal_adjoint_multi"
+    n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
+    S = shape[0]
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    if r.ndim != 4 or r.shape[1:] != shape:
+        raise ValueError(f"{who}: r must be [K, S, ny, nx]")
+    K = r.shape[0]
+    lam, g, g_src = np.zeros((K,) + shape), np.zeros((K,) + shape), np.zeros((K, S))
+    rounds = np.zeros((K, S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    st = _lib.EikonalStats()
+    check(lib().rtmi_eikonal_adjoint_multi(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
+                                           filled.ctypes.data_as(C.POINTER(C.c_uint8)), K, dptr(r), dptr(lam), dptr(g), dptr(g_src),
+                                           rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    return _eikonal_multi_result({"lam": lam, "g": g, "g_src": g_src}, rounds, st, stats)
+
+
+def eikonal_tangent_multi_device(n, sources, grid, fill_result, dn, *, n_src, dn_src=None, dT_seed=None, ball=2.0, max_rounds=0,
+                                 stats=False, _global_path=False, _width=0):
+    """eikonal_tangent_multi on torch tensors of one GPU, with no host copy (rtmi_eikonal_tangent_multi_dev): as
+    eikonal_tangent_device with dn [K, ny, nx], dn_src [K, S], dT_seed [K, S, ny, nx].  dT [K, S, ny, nx] is a new tensor on the
+    device; rounds and converged [K, S] are numpy arrays.  The same bits."""
+    import torch
+    who = "eikonal_tangent_multi_device"
+    if not isinstance(sources, torch.Tensor) or sources.dim() != 2:
+        raise ValueError(f"{who}: sources must be a torch tensor [S, 2]")
+    if not isinstance(dn, torch.Tensor) or dn.dim() != 3:
+        raise ValueError(f"{who}: dn must be a torch tensor [K, ny, nx]")
+    S, K, nx, ny = sources.shape[0], dn.shape[0], int(grid[2]), int(grid[5])
+    f64 = torch.float64
+    _eikonal_lin_tensors(who, [("n", n, f64, (ny, nx)), ("sources", sources, f64, (S, 2)), ("n_src", n_src, f64, (S,)),
+                               ("T", fill_result["T"], f64, (S, ny, nx)), ("filled", fill_result["filled"], torch.uint8, (S, ny, nx)),
+                               ("dn", dn, f64, (K, ny, nx)), ("dn_src", dn_src, f64, (K, S)),
+                               ("dT_seed", dT_seed, f64, (K, S, ny, nx))])
+    dT = torch.zeros((K, S, ny, nx), dtype=f64, device=n.device)
+    rounds = np.zeros((K, S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    st = _lib.EikonalStats()
+    opt = lambda a: None if a is None else a.data_ptr()      # noqa: E731
+    torch.cuda.synchronize(n.device)               # the library works on the null stream
+    with torch.cuda.device(n.device):
+        check(lib().rtmi_eikonal_tangent_multi_dev(C.byref(ep), n.data_ptr(), S, sources.data_ptr(), n_src.data_ptr(),
+                                                   fill_result["T"].data_ptr(), fill_result["filled"].data_ptr(), K, dn.data_ptr(),
+                                                   opt(dn_src), opt(dT_seed), dT.data_ptr(), rounds.ctypes.data_as(_lib._ip),
+                                                   C.byref(st)))
+    return _eikonal_multi_result({"dT": dT}, rounds, st, stats)
+
+
+def eikonal_adjoint_multi_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0, max_rounds=0, stats=False, _global_path=False, _width=0):
+    """eikonal_adjoint_multi on torch tensors of one GPU (rtmi_eikonal_adjoint_multi_dev): r [K, S, ny, nx].  lam, g
+    [K, S, ny, nx] and g_src [K, S] are new tensors on the device; rounds and converged [K, S] are numpy arrays.  The same bits."""
+    import torch
+    who = "eikonal_adjoint_multi_device"
+    if not isinstance(sources, torch.Tensor) or sources.dim() != 2:
+        raise ValueError(f"{who}: sources must be a torch tensor [S, 2]")
+    if not isinstance(r, torch.Tensor) or r.dim() != 4:
+        raise ValueError(f"{who}: r must be a torch tensor [K, S, ny, nx]")
+    S, K, nx, ny = sources.shape[0], r.shape[0], int(grid[2]), int(grid[5])
+    f64 = torch.float64
+    _eikonal_lin_tensors(who, [("n", n, f64, (ny, nx)), ("sources", sources, f64, (S, 2)), ("n_src", n_src, f64, (S,)),
+                               ("T", fill_result["T"], f64, (S, ny, nx)), ("filled", fill_result["filled"], torch.uint8, (S, ny, nx)),
+                               ("r", r, f64, (K, S, ny, nx))])
+    lam = torch.zeros((K, S, ny, nx), dtype=f64, device=n.device)
+    g = torch.zeros((K, S, ny, nx), dtype=f64, device=n.device)
+    g_src = torch.zeros((K, S), dtype=f64, device=n.device)
+    rounds = np.zeros((K, S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    st = _lib.EikonalStats()
+    torch.cuda.synchronize(n.device)               # the library works on the null stream
+    with torch.cuda.device(n.device):
+        check(lib().rtmi_eikonal_adjoint_multi_dev(C.byref(ep), n.data_ptr(), S, sources.data_ptr(), n_src.data_ptr(),
+                                                   fill_result["T"].data_ptr(), fill_result["filled"].data_ptr(), K, r.data_ptr(),
+                                                   lam.data_ptr(), g.data_ptr(), g_src.data_ptr(), rounds.ctypes.data_as(_lib._ip),
+                                                   C.byref(st)))
+    return _eikonal_multi_result({"lam": lam, "g": g, "g_src": g_src}, rounds, st, stats)
+
+
 def eikonal_source_weights(sources, grid):
     """The bilinear weights of each source's cell: (idx [S, 4] node indices, w [S, 4]); w is all 0 for a source outside the grid"""
     gx0, gdx, nx, gy0, gdy, ny = grid
@@ -1981,7 +2096,8 @@ class EikonalTomography:
     n_src follows the model through the bilinear weights of the source's cell where the source lies inside the grid.  A row is
     live where none of the four nodes round its receiver is an obstacle or unreached; other rows read and give 0."""
 
-    def __init__(self, field_or_n, sources, grid, receivers, *, fill_result=None, n_src=None, ball=2.0, max_rounds=0, _global_path=False):
+    def __init__(self, field_or_n, sources, grid, receivers, *, fill_result=None, n_src=None, ball=2.0, max_rounds=0, _global_path=False,
+                 _width=0):
         who = "EikonalTomography"
         self._h = None
         src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
@@ -2002,7 +2118,7 @@ class EikonalTomography:
                 raise ValueError(f"{who}: fill_result's T and filled must be [S, ny, nx]")
         self.grid, self.S, self.R, self.nx, self.ny = tuple(grid), S, len(rec), nx, ny
         self.n, self.sources, self.receivers = n.copy(), src, rec
-        ep = eikonal_params(grid, ball, max_rounds, _global_path)
+        ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
         h = C.c_void_p()
         check(lib().rtmi_eikonal_tomo_create(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
                                              None if filled is None else filled.ctypes.data_as(C.POINTER(C.c_uint8)), len(rec), dptr(rec),
@@ -2138,6 +2254,164 @@ class EikonalTomography:
             out["stats"] = {"total_ms": st.total_ms, "operator_ms": st.operator_ms, "vector_ms": st.vector_ms,
                             "bytes_device": int(st.bytes_device)}
         return out
+
+    # ------------------------------------------------------------------------------------------ several columns
+    def set_column_group(self, cg):
+        """The columns the batched calls sweep together (rtmi_eikonal_tomo_set_column_group); 0: the default, as many as keep the
+        work tables under 8 GiB.  For callers short of memory; no result depends on it."""
+        check(lib().rtmi_eikonal_tomo_set_column_group(self._open(), int(cg)))
+
+    def _columns(self, who, a, per, name, shape):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim < 2 or a.shape[1:] not in ((per,), shape):
+            raise ValueError(f"EikonalTomography.{who}: {name} must be [K, {', '.join(str(v) for v in shape)}]")
+        return a.reshape(a.shape[0], per)
+
+    def _multi(self, fn, a, per_out, stats):
+        """one C call per group of at most 64 columns"""
+        K = a.shape[0]
+        out = np.empty((K, per_out))
+        sts = []
+        for lo in range(0, K, _lib.LSQR_MULTI_MAX):
+            hi = min(K, lo + _lib.LSQR_MULTI_MAX)
+            part, res = np.ascontiguousarray(a[lo:hi]), np.empty((hi - lo, per_out))
+            st = _lib.EikonalTomoStats()
+            check(fn(self._open(), hi - lo, dptr(part), dptr(res), C.byref(st)))
+            out[lo:hi] = res
+            sts.append(eikonal_tomo_stats(st))
+        return (out, sts) if stats else out
+
+    def matmat(self, X, stats=False):
+        """Y [K, S R] = A X for X [K, ny, nx] (rtmi_eikonal_tomo_apply_multi): column c has the bits of apply(X[c]).  Any K, in
+        groups of at most 64.  With stats=True -> (Y, the groups' stats)."""
+        X = self._columns("matmat", X, self.ny * self.nx, "X", (self.ny, self.nx))
+        return self._multi(lib().rtmi_eikonal_tomo_apply_multi, X, self.S * self.R, stats)
+
+    def rmatmat(self, Y, stats=False):
+        """G [K, ny, nx] = A^T Y for Y [K, S R] (rtmi_eikonal_tomo_transpose_multi): column c has the bits of transpose(Y[c])"""
+        Y = self._columns("rmatmat", Y, self.S * self.R, "Y", (self.S * self.R,))
+        res = self._multi(lib().rtmi_eikonal_tomo_transpose_multi, Y, self.ny * self.nx, stats)
+        G = (res[0] if stats else res).reshape(-1, self.ny, self.nx)
+        return (G, res[1]) if stats else G
+
+    def _multi_device(self, who, fn, t, per_in, per_out, out, stats):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dim() < 2:
+            raise ValueError(f"EikonalTomography.{who}: the input must be a torch tensor [K, ...]")
+        K = t.shape[0]
+        if not 1 <= K <= _lib.LSQR_MULTI_MAX:
+            raise ValueError(f"EikonalTomography.{who}: K must be in 1 .. {_lib.LSQR_MULTI_MAX}")
+        t = self._device(who, t, K * per_in, "the input")
+        res = torch.empty((K, per_out), dtype=torch.float64, device=t.device) if out is None else self._device(who, out, K * per_out, "out")
+        st = _lib.EikonalTomoStats()
+        with torch.cuda.device(t.device):
+            check(fn(self._open(), K, t.data_ptr(), res.data_ptr(), C.byref(st)))
+        return (res, eikonal_tomo_stats(st)) if stats else res
+
+    def matmat_device(self, X, out=None, stats=False):
+        """matmat on torch tensors of the handle's device, with no host copy (rtmi_eikonal_tomo_apply_multi_dev), K <= 64"""
+        return self._multi_device("matmat_device", lib().rtmi_eikonal_tomo_apply_multi_dev, X, self.ny * self.nx, self.S * self.R, out, stats)
+
+    def rmatmat_device(self, Y, out=None, stats=False):
+        """rmatmat on torch tensors of the handle's device (rtmi_eikonal_tomo_transpose_multi_dev), K <= 64 -> [K, ny, nx]"""
+        res = self._multi_device("rmatmat_device", lib().rtmi_eikonal_tomo_transpose_multi_dev, Y, self.S * self.R, self.ny * self.nx, out,
+                                 stats)
+        G = (res[0] if stats else res).reshape(-1, self.ny, self.nx)
+        return (G, res[1]) if stats else G
+
+    def lsqr_multi(self, rhs, iter_lim, damp=0.0, atol=0.0, btol=0.0, row_weight=None, col_scale=None, x0=None, smooth=None, smooth2=None,
+                   history=False, stats=False, group=None):
+        """rtmi_eikonal_tomo_lsqr_multi: lsqr for the K right-hand sides rhs [K, S R] in lock-step -> a list of K dicts of lsqr's
+        shape, each with the bits of lsqr(rhs[c], ...).  The keywords are lsqr's; col_scale and x0 are shared, row_weight is
+        [S R] for all or [K, S R], one weighting per column.  Any K: in groups of at most 64 columns, or of `group`."""
+        who = "EikonalTomography.lsqr_multi"
+        rows, nm = self.S * self.R, self.ny * self.nx
+        rr = np.ascontiguousarray(rhs, dtype=np.float64)
+        if rr.ndim != 2 or rr.shape[1] != rows:
+            raise ValueError(f"{who}: rhs must be [K, {rows}]")
+        K = rr.shape[0]
+        iter_lim = int(iter_lim)
+        if iter_lim < 1:
+            raise ValueError(f"{who}: iter_lim must be >= 1")
+        group = _lib.LSQR_MULTI_MAX if group is None else int(group)
+        if not 1 <= group <= _lib.LSQR_MULTI_MAX:
+            raise ValueError(f"{who}: group must be in 1 .. {_lib.LSQR_MULTI_MAX}")
+        lp = _lib.LsqrParams()
+        lp.iter_lim, lp.damp, lp.atol, lp.btol = iter_lim, float(damp), float(atol), float(btol)
+        reg = None
+        if smooth is not None or smooth2 is not None:
+            reg = _lib.TomoReg()
+            for name, pair, dst in (("smooth", smooth, reg.d1), ("smooth2", smooth2, reg.d2)):
+                if pair is not None:
+                    pp = np.ascontiguousarray(pair, dtype=np.float64)
+                    if pp.shape != (2,):
+                        raise ValueError(f"{who}: {name} must be a pair")
+                    dst[0], dst[1] = pp
+        wr, flags = None, 0
+        if row_weight is not None:
+            wr = np.ascontiguousarray(row_weight, dtype=np.float64)
+            if wr.ndim == 2 and wr.shape == (K, rows) and K != 1:
+                flags = _lib.LSQR_MULTI_ROW_WEIGHT
+            elif wr.size == rows:
+                wr = wr.reshape(rows)
+            else:
+                raise ValueError(f"{who}: row_weight must be [{rows}] or [K, {rows}]")
+        lo = keep = None
+        if wr is not None or col_scale is not None or x0 is not None:
+            lo, keep = _lsqr_options(who, rows, nm, None, col_scale, x0)
+        out = []
+        for a in range(0, K, group):
+            b = min(K, a + group)
+            n = b - a
+            x = np.empty((n, self.ny, self.nx))
+            hist = np.zeros((n, iter_lim, 4)) if history else None
+            st = (_lib.LsqrStats * n)()
+            if wr is not None:
+                wg = np.ascontiguousarray(wr[a:b]) if flags else wr
+                lo.row_weight = dptr(wg)
+            check(lib().rtmi_eikonal_tomo_lsqr_multi(self._open(), C.byref(lp), None if lo is None else C.byref(lo),
+                                                     None if reg is None else C.byref(reg), n, flags, dptr(np.ascontiguousarray(rr[a:b])),
+                                                     dptr(x), dptr(hist), st))
+            for s in range(n):
+                o = {"x": x[s], "istop": int(st[s].istop), "itn": int(st[s].itn), "r1norm": st[s].r1norm, "r2norm": st[s].r2norm,
+                     "anorm": st[s].anorm, "arnorm": st[s].arnorm}
+                if history:
+                    o["history"] = hist[s, :st[s].itn].copy()
+                if stats:
+                    o["stats"] = {"total_ms": st[s].total_ms, "operator_ms": st[s].operator_ms, "vector_ms": st[s].vector_ms,
+                                  "bytes_device": int(st[s].bytes_device)}
+                out.append(o)
+        return out
+
+    def recover(self, models, **lsqr_kw):
+        """The resolution test: d_c = A m_c (matmat), then lsqr_multi(d, **lsqr_kw) -> (the recovered models [K, ny, nx], the
+        dicts).  models [K, ny, nx], e.g. checkerboard(...) or spikes(...) stacked."""
+        mm = np.ascontiguousarray(models, dtype=np.float64)
+        if mm.ndim != 3 or mm.shape[1:] != (self.ny, self.nx):
+            raise ValueError(f"EikonalTomography.recover: models must be [K, {self.ny}, {self.nx}]")
+        outs = self.lsqr_multi(self.matmat(mm), **lsqr_kw)
+        return np.stack([o["x"] for o in outs]) if outs else np.empty((0, self.ny, self.nx)), outs
+
+    def bootstrap(self, rhs, n, seed, results=False, **lsqr_kw):
+        """n bootstrap replicates of lsqr(rhs, ...): replicate k weighs row r by the square root of its multiplicity in a draw of
+        S R rows with replacement (bootstrap_weights(S R, n, seed)), zeroed on dead rows, times the caller's row_weight [S R], if
+        given; one lsqr_multi over them.  -> (mean, standard deviation with ddof 1) of x over the replicates, [ny, nx] each, and
+        with results=True the per-replicate dicts as well."""
+        rows = self.S * self.R
+        rr = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
+        if rr.size != rows:
+            raise ValueError(f"EikonalTomography.bootstrap: rhs must have {rows} values")
+        w = bootstrap_weights(rows, n, seed) * (self.table()["live"].reshape(-1) != 0)[None, :]
+        base = lsqr_kw.pop("row_weight", None)
+        if base is not None:
+            bb = np.ascontiguousarray(base, dtype=np.float64).reshape(-1)
+            if bb.size != rows:
+                raise ValueError(f"EikonalTomography.bootstrap: row_weight must have {rows} values")
+            w = w * bb[None, :]
+        outs = self.lsqr_multi(np.broadcast_to(rr, (len(w), rows)), row_weight=w, **lsqr_kw)
+        xs = np.stack([o["x"] for o in outs])
+        mean, std = xs.mean(axis=0), xs.std(axis=0, ddof=1)
+        return (mean, std, outs) if results else (mean, std)
 
     def as_linear_operator(self):
         """A scipy LinearOperator [S R, ny nx] over apply and transpose (host vectors: two PCIe crossings per product)"""
