@@ -1434,6 +1434,53 @@ int rtmi_eikonal_adjoint_multi_dev(const rtmi_eikonal_params *ep, const double *
                                    const double *d_r, double *d_lam, double *d_g, double *d_g_src, int32_t *rounds,
                                    rtmi_eikonal_stats *stats);
 
+/* Launch angle, arrival direction, spreading and amplitude factor at the nodes the eikonal fill gave a value.  DESIGN.md section
+ * 38.  A table completed by rtmi_eikonal_fill has T everywhere the seeds reach and every other column only where rays cover the
+ * node.  The launch angle is constant along rays, grad T . grad theta0 = 0, and the first-order upwind form of that equation on the
+ * fill's own causal network is a weighted mean of the two parents' values with the tangent's coefficients: theta0 =
+ * (ca ta + cb tb) / (ca + cb).  So what the rays know at the covered nodes is carried to the filled ones by the tangent's gather;
+ * in 2-D the spreading is |dx / dtheta0| at constant T = 1 / |grad theta0|, and the direction is the upwind gradient of T.  No rays.
+ * All on the device but the ball's atan2, in fp64, every product, sum, quotient and sqrt one rounded operation
+ * (raytracing_amd/csrc/rt_eikonal_attr.h holds the arithmetic, tests/eikonal_attr_ref.py restates it).  ep, n, src, n_src, T and
+ * filled are those of rtmi_eikonal_tangent; classes, parents, ca and cb are its own.  Per source the result is a function of them and
+ * of the input theta0.  Every output is read and written in place, [S][ny][nx] (dir: [S][2][ny][nx], the planes px and py): only
+ * nodes of class ball or free are written, dead nodes and seeds keep their bits, so covered nodes keep the rays' values.
+ *   wrap(d), pi and 2 pi the nearest doubles:  d > pi: d - 2 pi;  d <= -pi: d + 2 pi;  else d (a NaN passes through)
+ * theta0.  ball: atan2(dy, dx), dx = X - xs, dy = Y - ys, by the host's libm over a box that holds the ball, uploaded (also by
+ *     the _dev form, which reads d_src back: a handful of nodes per source).
+ *     free: it starts from NaN.  A parent is usable iff its current value is finite.  With a the x-parent and b the y-parent:
+ *         both usable: w = cb / (ca + cb);  theta0 = ta + w wrap(tb - ta), and a NaN result is the canonical NaN
+ *         one usable: that parent's value;  none usable: the canonical NaN
+ *     The result is not wrapped again, so it stays congruent modulo 2 pi to the seeds' convention.  Parents are strictly earlier in
+ *     T, so the fixed point is unique and its bits depend on no schedule; so that rounds is defined the sweeps are the tangent's
+ *     four orders over the free nodes, a node changing when its bits change; no round runs where no node is free; max_rounds and
+ *     rounds [S][2] as in rtmi_eikonal_tangent.  Where clean is 0 nodes the sweeps have not reached are still NaN.
+ * dir (or NULL).  ball: r = sqrt(dx dx + dy dy);  r > 0: (dx / r, dy / r), else (0, 0).
+ *     free: t the node's T, a and b its parents';  gx = (t - a) / gdx for a west x-parent, (-(t - a)) / gdx for an east one, 0
+ *     without one;  gy likewise, + for a south parent;  m = sqrt(gx gx + gy gy);  m > 0: (gx / m, gy / m), else NaN in both planes.
+ *     There is no atan2 on the device: the arrival angle is atan2(py, px), the caller's.
+ * J, G (each or NULL), from the source's final theta0.  ball: J = r.  free: theta0 not finite: J and G NaN.  Else per axis, a
+ *     neighbour being usable iff it is inside the grid, not dead and its theta0 is finite (seeds count: the covered side is used):
+ *         both: ddx = wrap(tE - tW) / (2 gdx);  east only: wrap(tE - t) / gdx;  west only: wrap(t - tW) / gdx;  neither: 0
+ *     ddy alike;  m = sqrt(ddx ddx + ddy ddy);  J = 1 / m, +inf where m == 0.  G = 1 / sqrt(n J), rtmi_first_arrival_grid's order:
+ *     J = +inf gives G = 0 (a pure diffraction: every neighbour has the node's angle), J = 0 gives +inf (the source node).
+ *     The differences are central on purpose: upwind ones read grad theta0 = 0 at every node that copies its one parent.  The
+ *     price is a spike of G on the lines where two branches of the first arrival meet and theta0 jumps.
+ *   stats    as in rtmi_eikonal_tangent; path: a source's values, weights and codes (17 bytes per node) in the workgroup's LDS
+ *            where they fit 128 KiB, else the values in theta0 itself and 9 bytes per node and source of work space, sources in
+ *            groups of at most 1 GiB.  ep->reserved[0] = 1 takes the global path, for tests.  kernel_ms covers both kernels.
+ * One workgroup per source for theta0, the round loop inside; then one lane per (source, node) of the call for dir, J and G.
+ * Sources are independent.  The host form is upload, the _dev form, download: the same bits.  RTMI_ERR_ARG as in
+ * rtmi_eikonal_tangent, and for a null T, filled or theta0 with S > 0.
+ * The caustic index is not an output: it is 0 along a first arrival that met no caustic, which the caller sets.
+ * Not covered: the spikes on shock lines; count; later arrivals; anisotropy; 3-D; fp32. */
+int rtmi_eikonal_attributes(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,
+                            const double *T, const uint8_t *filled, double *theta0, double *dir, double *J, double *G,
+                            int32_t *rounds, rtmi_eikonal_stats *stats);
+int rtmi_eikonal_attributes_dev(const rtmi_eikonal_params *ep, const double *d_n, int64_t S, const double *d_src,
+                                const double *d_n_src, const double *d_T, const uint8_t *d_filled, double *d_theta0, double *d_dir,
+                                double *d_J, double *d_G, int32_t *rounds, rtmi_eikonal_stats *stats);
+
 /* First-arrival eikonal tomography that stays on the device: a handle over the linearised fill with receivers anywhere on the
  * grid, its two products defined bit for bit, and LSQR on them.  DESIGN.md section 36.  raytracing_amd/csrc/rt_eikonal_tomo.h
  * holds the host arithmetic, tests/eikonal_tomo_ref.py restates everything.  All fp64; every product and sum is one rounded

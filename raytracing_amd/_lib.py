@@ -406,6 +406,10 @@ SYMBOLS = {
                                              _dp, _dp, _dp, _dp, _ip, C.POINTER(EikonalStats)]),
     "rtmi_eikonal_adjoint_multi_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32] +
                                        [C.c_void_p] * 4 + [_ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_attributes": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), _dp, _dp, _dp,
+                                          _dp, _ip, C.POINTER(EikonalStats)]),
+    "rtmi_eikonal_attributes_dev": (C.c_int, [C.POINTER(EikonalParams), C.c_void_p, C.c_int64] + [C.c_void_p] * 8 +
+                                    [_ip, C.POINTER(EikonalStats)]),
     "rtmi_eikonal_tomo_create": (C.c_int, [C.POINTER(EikonalParams), _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int64, _dp,
                                            C.POINTER(C.c_void_p)]),
     "rtmi_eikonal_tomo_destroy": (None, [C.c_void_p]),

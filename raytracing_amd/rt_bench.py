@@ -1527,7 +1527,8 @@ def debug_arrival_rows(x, y, T, theta, last, theta0, grid, arrivals=1, order="ti
 
 
 def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_size, box, gamma=1, amplitude=False, mem_budget=0,
-                     max_gap=None, max_dtheta=None, stats=False, arrivals=None, order="time", fill=None, **batch_kw):
+                     max_gap=None, max_dtheta=None, stats=False, arrivals=None, order="time", fill=None, fill_attributes=False,
+                     **batch_kw):
     """First-arrival tables from many sources onto one grid, by public calls only: a fan of launch angles
     `thetas` per source (sources: (S, 2) array of (x, y)).  1. A count pass without a record sizes rec_rows to the longest ray.
     2. Sources are grouped so that each group's record (48 bytes per row and ray in fp64, 24 in fp32; 12 more with amplitude,
@@ -1540,9 +1541,14 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     counts against mem_budget too, and a group over it is traced again in halves.  fill="eikonal" completes T after the ray-cell
     pass (eikonal_fill with its defaults): every node the covered ones or the source can reach gets a first
     arrival, with arrivals=K in slot 0 only, and 'filled' [S, ny, nx] (uint8) marks those nodes; count and the other columns
-    stay as they are, 0 and NaN there, since no ray reaches them.  fill=None is the ray-cell result alone."""
+    stay as they are, 0 and NaN there, since no ray reaches them.  fill=None is the ray-cell result alone.  With
+    fill_attributes=True (it needs fill="eikonal") the filled nodes also get theta0 and theta, and with amplitude=True J and G,
+    carried from the covered nodes through the fill's network (eikonal_attributes), and kmah 0; with arrivals=K in
+    slot 0 only.  ray, step and count stay as they are."""
     if fill not in (None, "eikonal"):
         raise ValueError('traveltime_table: fill must be None or "eikonal"')
+    if fill_attributes and fill is None:
+        raise ValueError('traveltime_table: fill_attributes needs fill="eikonal"')
     src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
     th = np.ascontiguousarray(thetas, dtype=np.float64)
     S, M = len(src), len(th)
@@ -1610,6 +1616,16 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
             res["T"] = done["T"]
         res["filled"] = done["filled"]
         tot["eikonal"] = done["stats"]
+        if fill_attributes:
+            slot = (lambda a: a[:, 0]) if arrivals is not None else (lambda a: a)
+            names = ("theta0", "theta") + (("J", "G") if amplitude else ())
+            att = eikonal_attributes(field, src, grid, done["T"], done["filled"], stats=True,
+                                     **{k: np.ascontiguousarray(slot(res[k])) for k in names})
+            for k in names:
+                slot(res[k])[...] = att[k]
+            if amplitude and "kmah" in res:
+                slot(res["kmah"])[done["filled"] != 0] = 0
+            tot["eikonal_attributes"] = att["stats"]
     if stats:
         res["stats"] = tot
     return res
@@ -1899,6 +1915,78 @@ def eikonal_adjoint_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0,
                                              fill_result["T"].data_ptr(), fill_result["filled"].data_ptr(), r.data_ptr(), lam.data_ptr(),
                                              g.data_ptr(), g_src.data_ptr(), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
     res = {"lam": lam, "g": g, "g_src": g_src, "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy()}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def eikonal_attributes(field_or_n, sources, grid, T, filled, theta0=None, theta=None, J=None, G=None, *, n_src=None, ball=2.0,
+                       max_rounds=0, stats=False, _global_path=False):
+    """Launch angle, arrival direction, spreading and amplitude factor at the nodes eikonal_fill gave a value, on the device
+    (rtmi_eikonal_attributes, include/rtmi.h): what the rays know at the covered nodes -- theta0, theta, J, G
+    [S, ny, nx] of the ray-cell table, NaN where no ray reaches; None: all NaN -- carried through the fill's causal network to the
+    nodes `filled` marks, with no rays.  field_or_n, sources, grid, n_src, ball as in the eikonal_fill call that returned T and
+    filled.  The inputs are not modified.  Returns a dict of [S, ny, nx] arrays: theta0, theta (arctan2(py, px) at the written
+    nodes), px, py (the unit arrival direction, NaN at the nodes that were not written), J, G, and rounds, converged [S]; with
+    stats=True also 'stats'.  Covered nodes keep their bits.  First order, like T: see DESIGN.md 38 for the figures, and shoot the
+    full fan, since from the ball alone the launch angle is poor.  G spikes on the lines where two branches of the first arrival
+    meet."""
+    who = "eikonal_attributes"
+    n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, {"T": T, "filled": filled}, n_src)
+    S = shape[0]
+    cols = {}
+    for name, a in (("theta0", theta0), ("theta", theta), ("J", J), ("G", G)):
+        a = _eikonal_lin_array(who, name, a, shape)
+        cols[name] = np.full(shape, np.nan) if a is None else a.copy()
+    d = np.full((S, 2) + shape[1:], np.nan)
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    check(lib().rtmi_eikonal_attributes(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T), filled.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        dptr(cols["theta0"]), dptr(d), dptr(cols["J"]), dptr(cols["G"]),
+                                        rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    px, py = d[:, 0].copy(), d[:, 1].copy()
+    written = (filled != 0) & np.isfinite(T) & (np.isfinite(n) & (n > 0))[None]
+    cols["theta"][written] = np.arctan2(py[written], px[written])
+    res = {"theta0": cols["theta0"], "theta": cols["theta"], "px": px, "py": py, "J": cols["J"], "G": cols["G"],
+           "rounds": rounds[:, 0].copy(), "converged": rounds[:, 1].copy()}
+    if stats:
+        res["stats"] = eikonal_stats(st)
+    return res
+
+
+def eikonal_attributes_device(n, sources, grid, T, filled, theta0=None, theta=None, J=None, G=None, *, n_src, ball=2.0, max_rounds=0,
+                              stats=False, _global_path=False):
+    """eikonal_attributes on torch tensors of one GPU, with no host copy of the tables (rtmi_eikonal_attributes_dev): n [ny, nx],
+    sources [S, 2], n_src [S], T, theta0, theta, J, G [S, ny, nx] in fp64 and filled in uint8, contiguous.  theta0, theta, J and G
+    are completed IN PLACE and returned; None: a new tensor from an all-NaN input.  px and py are new tensors; rounds and
+    converged are numpy arrays.  The same bits."""
+    import torch
+    who = "eikonal_attributes_device"
+    if not isinstance(sources, torch.Tensor) or sources.dim() != 2:
+        raise ValueError(f"{who}: sources must be a torch tensor [S, 2]")
+    S, nx, ny = sources.shape[0], int(grid[2]), int(grid[5])
+    f64 = torch.float64
+    tab = (S, ny, nx)
+    _eikonal_lin_tensors(who, [("n", n, f64, (ny, nx)), ("sources", sources, f64, (S, 2)), ("n_src", n_src, f64, (S,)),
+                               ("T", T, f64, tab), ("filled", filled, torch.uint8, tab), ("theta0", theta0, f64, tab),
+                               ("theta", theta, f64, tab), ("J", J, f64, tab), ("G", G, f64, tab)])
+    new = lambda a, shape=tab: torch.full(shape, float("nan"), dtype=f64, device=n.device) if a is None else a     # noqa: E731
+    theta0, theta, J, G = new(theta0), new(theta), new(J), new(G)
+    d = new(None, (S, 2, ny, nx))
+    rounds = np.zeros((S, 2), dtype=np.int32)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    st = _lib.EikonalStats()
+    torch.cuda.synchronize(n.device)               # the library works on the null stream
+    with torch.cuda.device(n.device):
+        check(lib().rtmi_eikonal_attributes_dev(C.byref(ep), n.data_ptr(), S, sources.data_ptr(), n_src.data_ptr(), T.data_ptr(),
+                                                filled.data_ptr(), theta0.data_ptr(), d.data_ptr(), J.data_ptr(), G.data_ptr(),
+                                                rounds.ctypes.data_as(_lib._ip), C.byref(st)))
+    px, py = d[:, 0].contiguous(), d[:, 1].contiguous()
+    written = (filled != 0) & torch.isfinite(T) & (torch.isfinite(n) & (n > 0))[None]
+    theta[written] = torch.atan2(py[written], px[written])
+    res = {"theta0": theta0, "theta": theta, "px": px, "py": py, "J": J, "G": G, "rounds": rounds[:, 0].copy(),
+           "converged": rounds[:, 1].copy()}
     if stats:
         res["stats"] = eikonal_stats(st)
     return res
