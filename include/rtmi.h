@@ -1312,11 +1312,29 @@ int rtmi_locate_edt_pdf_dev(rtmi_locator *loc, const rtmi_edt_params *ep, const 
  * stats stay host memory); rtmi_eikonal_fill is upload, that, download: the same bits.
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null ep; nx or ny < 1; nx ny > 2^31; gdx or gdy
  * not finite or <= 0; gx0 or gy0 not finite; S < 0; a null n, src or n_src with S > 0; max_rounds < 0; a ball that is not finite;
- * ep->reserved[0] other than 0 or 1.
- * Not covered: factored or higher-order schemes (the error near the source is first order: about 1 % of the largest T where the
- * ball is the only seed); covered nodes never decrease, so a head wave does not undercut a table's geometric
- * arrival; amplitudes, launch angles and count at filled nodes; anisotropy; 3-D; several GPUs; fp32 tables. */
+ * ep->reserved[0] other than 0 or 1; a scheme that is neither RTMI_EIKONAL_PLAIN nor RTMI_EIKONAL_FACTORED.
+ * ep->scheme = RTMI_EIKONAL_FACTORED is the source-factored scheme (tests/eikonal_factored_ref.py restates
+ * it): T = T0 + u with T0 = n_src r, and u is what is differenced.  States, the ball, the sweeps, the round rule, filled and
+ * unreached are as above; the update of a free node (ix, iy) reads l, r, dn, up = T[j][i-1], T[j][i+1], T[j-1][i], T[j+1][i] and,
+ * with dx = X - xs, dy = Y - ys, rr = sqrt(dx dx + dy dy) and T0 = n_src rr at the node and at a parent alike, does
+ *     x-parent east iff r < l;  a_raw = that reading
+ *       a = a_raw == +inf ? +inf : (a_raw + (T0[x] - T0[parent])) +- px;  px = gdx (n_src (dx / rr));  + for east, - for west
+ *     y-parent north iff up < dn;  b_raw = that reading
+ *       b = b_raw == +inf ? +inf : (b_raw + (T0[x] - T0[parent])) +- py;  py = gdy (n_src (dy / rr));  + for north, - for south
+ * and then the update above on a and b.  Factoring is left out, and the update is the plain one, for a source whose n_src is not
+ * finite or <= 0 and at a node with rr == 0.  Still first order, but with 6 to 10 times less error where the ball is the only
+ * seed, and exact to rounding in a constant medium; the rounds converge geometrically, some ten in a smooth medium where the plain
+ * scheme takes two, and a round costs three sqrt and two quotients more per update.  rtmi_eikonal_fill and rtmi_eikonal_fill_dev
+ * read scheme, and rtmi_eikonal_tomo_create through them (a self-filled handle fills and re-linearises with it).  The tangent,
+ * adjoint, attributes and _multi entries ignore the field: they linearise the plain update about the table they are given, and
+ * tolerate a table that is not the plain scheme's fixed point (they recompute the node's value and drop a parent that is not
+ * strictly earlier).  RTMI_EIKONAL_PLAIN gives the bits of the scheme above.
+ * Not covered: second- or higher-order schemes (the error stays first order under either scheme: about 1 % of the largest T
+ * where the ball is the only seed under RTMI_EIKONAL_PLAIN, about 0.2 % under the other); covered nodes never
+ * decrease, so a head wave does not undercut a table's geometric arrival; amplitudes, launch angles and count at filled nodes;
+ * anisotropy; 3-D; several GPUs; fp32 tables; the linearisation of the corrected update itself; a stop tolerance on the rounds. */
 enum { RTMI_EIKONAL_LDS = 1, RTMI_EIKONAL_GLOBAL = 2 };
+enum { RTMI_EIKONAL_PLAIN = 0, RTMI_EIKONAL_FACTORED = 1 };
 typedef struct {
     double gx0, gdx;         /* as in rtmi_grid_params */
     int64_t nx;
@@ -1324,7 +1342,7 @@ typedef struct {
     int64_t ny;
     double ball;             /* the radius of the source ball in cells; negative: no ball.  The Python layer's default is 2 */
     int32_t max_rounds;      /* 0: 64 */
-    int32_t reserved0;
+    int32_t scheme;          /* RTMI_EIKONAL_PLAIN (0) or RTMI_EIKONAL_FACTORED; read by the fills alone */
     int64_t reserved[4];
 } rtmi_eikonal_params;
 typedef struct {

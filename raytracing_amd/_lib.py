@@ -210,9 +210,9 @@ class PdfResult(C.Structure):
 
 
 class EikonalParams(C.Structure):
-    """rtmi_eikonal_params: the grid as in GridParams, the source ball's radius in cells and the cap on the rounds"""
+    """rtmi_eikonal_params: the grid as in GridParams, the source ball's radius in cells, the cap on the rounds and the fill's scheme"""
     _fields_ = [("gx0", C.c_double), ("gdx", C.c_double), ("nx", C.c_int64), ("gy0", C.c_double), ("gdy", C.c_double),
-                ("ny", C.c_int64), ("ball", C.c_double), ("max_rounds", C.c_int32), ("reserved0", C.c_int32),
+                ("ny", C.c_int64), ("ball", C.c_double), ("max_rounds", C.c_int32), ("scheme", C.c_int32),
                 ("reserved", C.c_int64 * 4)]
 
 
@@ -231,6 +231,8 @@ class EikonalTomoStats(C.Structure):
 
 EIKONAL_LDS, EIKONAL_GLOBAL = 1, 2      # rtmi_eikonal_stats.path
 EIKONAL_PATHS = {EIKONAL_LDS: "lds", EIKONAL_GLOBAL: "global"}
+EIKONAL_PLAIN, EIKONAL_FACTORED = 0, 1  # rtmi_eikonal_params.scheme
+EIKONAL_SCHEMES = {"plain": EIKONAL_PLAIN, "factored": EIKONAL_FACTORED}
 
 
 class StackParams(C.Structure):

@@ -1,11 +1,13 @@
 // eikonal.hip -- the eikonal continuation of traveltime tables: the first-order Godunov upwind scheme for |grad T| = n by fast
 // sweeping, seeded by a table's covered nodes and a small analytic ball round the source (rtmi_eikonal_fill and its _dev form;
 // include/rtmi.h).  The arithmetic of a node is rt_eikonal.h's; the kernel only decides who runs it when.
-//   k_eikonal<LDS>  one workgroup per source, the round loop inside.  A sweep walks the anti-diagonals of the grid in the
+//   k_eikonal<LDS, FACTORED>  one workgroup per source, the round loop inside.  A sweep walks the anti-diagonals of the grid in the
 //                   sweep's own directions; the nodes of one diagonal do not read one another, so the lanes take them side by
 //                   side (striding where a diagonal is longer than the block) and a block barrier parts two diagonals: the
 //                   serial sweep's bits.  LDS: the source's working table, the slowness and the node states live in the block's
-//                   LDS; otherwise in a work space in global memory, which the L2 holds.
+//                   LDS; otherwise in a work space in global memory, which the L2 holds.  FACTORED: the source-factored scheme
+//                   (DESIGN.md section 39): the update is rt::eik_update_factored, which evaluates T0 = n_src r at the node and
+//                   at its two parents in registers -- no table of it, so both schemes have the same LDS rule and work space.
 // Every loop bound and every barrier is uniform across the block and max_rounds bounds the whole; no block waits for another.
 // No atomics on floating point.
 #include "rtmi_host.h"
@@ -35,7 +37,7 @@ struct EikArgs {
     unsigned long long* out;    // [S][kOutWords]
 };
 
-template <bool LDS> __global__ void __launch_bounds__(kMaxBlock) k_eikonal(const EikArgs a) {
+template <bool LDS, bool FACTORED> __global__ void __launch_bounds__(kMaxBlock) k_eikonal(const EikArgs a) {
     extern __shared__ double lds[];                     // LDS: [T | n | state]
     __shared__ unsigned long long red[2][kMaxBlock / 64];
     const int tid = (int)threadIdx.x, bd = (int)blockDim.x;
@@ -89,7 +91,9 @@ template <bool LDS> __global__ void __launch_bounds__(kMaxBlock) k_eikonal(const
                         if (st[x] != rt::kEikFree) continue;
                         const double l = i > 0 ? w[x - 1] : inf, r = i + 1 < nx ? w[x + 1] : inf;
                         const double dn = j > 0 ? w[x - nx] : inf, up = j + 1 < ny ? w[x + nx] : inf;
-                        const double t = rt::eik_update(a.g, rt::eik_min(l, r), rt::eik_min(dn, up), nv[x]);
+                        double t;
+                        if constexpr (FACTORED) t = rt::eik_update_factored(a.g, i, j, xs, ys, n_src, l, r, dn, up, nv[x]);
+                        else t = rt::eik_update(a.g, rt::eik_min(l, r), rt::eik_min(dn, up), nv[x]);
                         if (t < w[x]) {
                             w[x] = t;
                             mine++;
@@ -150,8 +154,11 @@ int eikonal_dev(const char* who, const rtmi_eikonal_params* ep, const double* d_
         }
         unsigned long long* d_out = nullptr;
         RTMI_ALLOC(mem.get(&d_out, (size_t)S * kOutWords * sizeof(unsigned long long)));
+        const bool factored = ep->scheme == RTMI_EIKONAL_FACTORED;
+        auto* const kernel = lds ? (factored ? k_eikonal<true, true> : k_eikonal<true, false>)
+                                 : (factored ? k_eikonal<false, true> : k_eikonal<false, false>);
         if (lds && lds_bytes > 65536)
-            RTMI_HIP(hipFuncSetAttribute((const void*)k_eikonal<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+            RTMI_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
         EventMarks<2> marks;
         RTMI_HIP(marks.create());
         RTMI_HIP(marks.mark(0));
@@ -162,8 +169,7 @@ int eikonal_dev(const char* who, const rtmi_eikonal_params* ep, const double* d_
             a.T = d_T ? d_T + s0 * nn : nullptr;
             a.filled = d_filled ? d_filled + s0 * nn : nullptr;
             a.out = d_out + s0 * kOutWords;
-            if (lds) hipLaunchKernelGGL(k_eikonal<true>, dim3((unsigned)gs), dim3(block), lds_bytes, nullptr, a);
-            else hipLaunchKernelGGL(k_eikonal<false>, dim3((unsigned)gs), dim3(block), 0, nullptr, a);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)gs), dim3(block), lds ? lds_bytes : 0, nullptr, a);
             RTMI_HIP(hipGetLastError());
         }
         RTMI_HIP(marks.mark(1));
@@ -196,6 +202,7 @@ RTMI_EXPORT int rtmi_eikonal_fill_dev(const rtmi_eikonal_params* ep, const doubl
                                       rtmi_eikonal_stats* stats) {
     const char* who = "rtmi_eikonal_fill_dev";
     RTMI_RC(check_eikonal(who, ep, d_n, S, d_src, d_n_src));
+    RTMI_RC(check_eikonal_scheme(who, ep));
     if (S > 0) {
         int device = 0;
         RTMI_HIP(hipGetDevice(&device));
@@ -213,6 +220,7 @@ RTMI_EXPORT int rtmi_eikonal_fill(const rtmi_eikonal_params* ep, const double* n
                                   double* T, int32_t* rounds, uint8_t* filled, rtmi_eikonal_stats* stats) {
     const char* who = "rtmi_eikonal_fill";
     RTMI_RC(check_eikonal(who, ep, n, S, src, n_src));
+    RTMI_RC(check_eikonal_scheme(who, ep));
     if (S == 0) return eikonal_dev(who, ep, nullptr, 0, nullptr, nullptr, nullptr, rounds, nullptr, stats);
     const size_t nn = (size_t)ep->nx * (size_t)ep->ny, tab = (size_t)S * nn;
     DevMem mem;

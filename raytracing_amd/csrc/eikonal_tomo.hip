@@ -464,6 +464,7 @@ RTMI_EXPORT int rtmi_eikonal_tomo_create(const rtmi_eikonal_params* ep, const do
     RTMI_ARG(out, "null out");
     *out = nullptr;
     RTMI_RC(check_eikonal(who, ep, n, S, src, n_src));
+    RTMI_RC(check_eikonal_scheme(who, ep));      // the handle's own fill and every relinearise read it
     RTMI_ARG(S >= 1, "S must be >= 1");
     RTMI_ARG(R >= 1, "R must be >= 1");
     RTMI_ARG(rec, "null rec");

@@ -24,6 +24,24 @@
 // update reading its neighbours' current values.  No round runs where no node is free or no node is seeded or of the ball
 // (rounds 0, clean); else rounds repeat until one changes nothing (clean) or max_rounds have run.  Free nodes still at +inf are
 // unreached.
+//
+// The source-factored scheme (rtmi_eikonal_params.scheme = RTMI_EIKONAL_FACTORED; DESIGN.md section 39;
+// tests/eikonal_factored_ref.py restates it) is additive factoring: T = T0 + u with T0 = n_src r.  Differencing u upwind is the
+// update above on shifted neighbour readings -- the parent's value plus the truncation error of differencing T0 across that edge
+// -- so the working table stays T, eik_update is untouched and its one-sided branch is T_x = +-s.  For node (i, j) of a source,
+// in eik_init's expressions:
+//     X = gx0 + (double)i gdx;  dx = X - xs;  Y = gy0 + (double)j gdy;  dy = Y - ys;  rr = sqrt(dx dx + dy dy);  T0 = n_src rr
+// States, the ball, the sweep orders, the round rule, filled and unreached -> NaN are unchanged.  Factoring is left out for a
+// source whose n_src is not finite or <= 0 and at a node with rr == 0: the plain update.  Otherwise the update of free node x
+// reads l = T[j][i-1], r = T[j][i+1], dn = T[j-1][i], up = T[j+1][i] as above and then
+//     x-parent east iff r < l;  a_raw = that reading
+//       a = a_raw == +inf ? +inf : (a_raw + (T0[x] - T0[parent])) +- px;  px = gdx (n_src (dx / rr));  + for east, - for west
+//     y-parent north iff up < dn;  b_raw = that reading
+//       b = b_raw == +inf ? +inf : (b_raw + (T0[x] - T0[parent])) +- py;  py = gdy (n_src (dy / rr));  + for north, - for south
+//     t = eik_update(a, b, s);  T[j][i] = t iff t < T[j][i]
+// The side is chosen on the raw readings.  T0 is a function of the node alone, so evaluating it afresh (as here: three sqrt and
+// two quotients per update) and reading it from a table give the same bits.  The corrected scheme is not strictly causal in T:
+// the rounds converge geometrically, some ten of them in a smooth medium where the plain scheme needs two.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -90,6 +108,45 @@ RT_EIK_HD double eik_update(const EikGrid& g, double a, double b, double s) {
     return d < 0.0 ? eik_min(ta, tb) : (B + std::sqrt(d)) / g.A;
 }
 
+enum : int32_t { kEikPlain = 0, kEikFactored = 1 };      // rtmi_eikonal_params.scheme
+
+// The distance rr of node (i, j) from the source, in eik_init's expressions, with its dx and dy
+RT_EIK_HD double eik_rr(const EikGrid& g, long i, long j, double xs, double ys, double* dx, double* dy) {
+    const double X = g.gx0 + (double)i * g.gdx, Y = g.gy0 + (double)j * g.gdy;
+    *dx = X - xs;
+    *dy = Y - ys;
+    return std::sqrt(*dx * *dx + *dy * *dy);
+}
+
+// The candidate value of free node (i, j) in the factored scheme from its four neighbour readings (+inf outside the grid): the
+// parents are chosen on the raw readings, each is corrected by what differencing T0 = n_src rr across its edge gets wrong, and
+// eik_update does the rest.  The plain update where n_src is an obstacle's or rr == 0.
+RT_EIK_HD double eik_update_factored(const EikGrid& g, long i, long j, double xs, double ys, double n_src, double l, double r, double dn,
+                                     double up, double s) {
+    const double inf = eik_inf();
+    const bool east = r < l, north = up < dn;
+    double a = east ? r : l, b = north ? up : dn;
+    if (a == inf && b == inf) return inf;
+    double dx, dy, pdx, pdy;                  // the node's; the parent's, not used
+    const double rr = eik_rr(g, i, j, xs, ys, &dx, &dy);
+    if (!eik_obstacle(n_src) && rr != 0.0) {
+        const double T0 = n_src * rr;
+        if (a != inf) {
+            const double T0p = n_src * eik_rr(g, east ? i + 1 : i - 1, j, xs, ys, &pdx, &pdy);
+            const double px = g.gdx * (n_src * (dx / rr));
+            a = a + (T0 - T0p);
+            a = east ? a + px : a - px;
+        }
+        if (b != inf) {
+            const double T0p = n_src * eik_rr(g, i, north ? j + 1 : j - 1, xs, ys, &pdx, &pdy);
+            const double py = g.gdy * (n_src * (dy / rr));
+            b = b + (T0 - T0p);
+            b = north ? b + py : b - py;
+        }
+    }
+    return eik_update(g, a, b, s);
+}
+
 // what one source's solve reports
 struct EikResult {
     int32_t rounds, clean;
@@ -98,9 +155,10 @@ struct EikResult {
 
 #if !(defined(__HIPCC__) || defined(__HIP__))
 // The solve of one source as the serial loop that defines it, host only.  n [ny][nx]; T [ny][nx] in place (or NULL: all NaN, no
-// table returned); w [ny][nx] doubles and st [ny][nx] bytes of work space; filled [ny][nx] or NULL.
+// table returned); w [ny][nx] doubles and st [ny][nx] bytes of work space; filled [ny][nx] or NULL; scheme kEikPlain or
+// kEikFactored.
 inline EikResult eik_solve(const EikGrid& g, long nx, long ny, const double* n, double xs, double ys, double n_src, double ball,
-                           int max_rounds, double* T, double* w, uint8_t* st, uint8_t* filled) {
+                           int max_rounds, double* T, double* w, uint8_t* st, uint8_t* filled, int32_t scheme = kEikPlain) {
     EikResult r{0, 1, 0, 0, 0};
     const double inf = eik_inf();
     long seeds = 0, free_now = 0;
@@ -126,7 +184,8 @@ inline EikResult eik_solve(const EikGrid& g, long nx, long ny, const double* n, 
                         if (st[x] != kEikFree) continue;
                         const double l = i > 0 ? w[x - 1] : inf, rr = i + 1 < nx ? w[x + 1] : inf;
                         const double dn = j > 0 ? w[x - nx] : inf, up = j + 1 < ny ? w[x + nx] : inf;
-                        const double t = eik_update(g, eik_min(l, rr), eik_min(dn, up), n[x]);
+                        const double t = scheme == kEikFactored ? eik_update_factored(g, i, j, xs, ys, n_src, l, rr, dn, up, n[x])
+                                                                : eik_update(g, eik_min(l, rr), eik_min(dn, up), n[x]);
                         if (t < w[x]) {
                             w[x] = t;
                             changed++;

@@ -43,4 +43,11 @@ int check_eikonal(const char* who, const rtmi_eikonal_params* ep, const void* n,
     return RTMI_OK;
 }
 
+// what the fills, which alone read ep->scheme, refuse on top of that
+int check_eikonal_scheme(const char* who, const rtmi_eikonal_params* ep) {
+    RTMI_ARG(ep->scheme == RTMI_EIKONAL_PLAIN || ep->scheme == RTMI_EIKONAL_FACTORED,
+             "scheme must be RTMI_EIKONAL_PLAIN or RTMI_EIKONAL_FACTORED");
+    return RTMI_OK;
+}
+
 }  // namespace

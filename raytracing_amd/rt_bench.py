@@ -1528,7 +1528,7 @@ def debug_arrival_rows(x, y, T, theta, last, theta0, grid, arrivals=1, order="ti
 
 def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_size, box, gamma=1, amplitude=False, mem_budget=0,
                      max_gap=None, max_dtheta=None, stats=False, arrivals=None, order="time", fill=None, fill_attributes=False,
-                     **batch_kw):
+                     fill_scheme="plain", **batch_kw):
     """First-arrival tables from many sources onto one grid, by public calls only: a fan of launch angles
     `thetas` per source (sources: (S, 2) array of (x, y)).  1. A count pass without a record sizes rec_rows to the longest ray.
     2. Sources are grouped so that each group's record (48 bytes per row and ray in fp64, 24 in fp32; 12 more with amplitude,
@@ -1544,9 +1544,12 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     stay as they are, 0 and NaN there, since no ray reaches them.  fill=None is the ray-cell result alone.  With
     fill_attributes=True (it needs fill="eikonal") the filled nodes also get theta0 and theta, and with amplitude=True J and G,
     carried from the covered nodes through the fill's network (eikonal_attributes), and kmah 0; with arrivals=K in
-    slot 0 only.  ray, step and count stay as they are."""
+    slot 0 only.  ray, step and count stay as they are.  fill_scheme "plain" or "factored" is eikonal_fill's scheme (DESIGN.md
+    39); covered nodes keep their bits under either."""
     if fill not in (None, "eikonal"):
         raise ValueError('traveltime_table: fill must be None or "eikonal"')
+    if fill_scheme not in _lib.EIKONAL_SCHEMES:
+        raise ValueError('traveltime_table: fill_scheme must be "plain" or "factored"')
     if fill_attributes and fill is None:
         raise ValueError('traveltime_table: fill_attributes needs fill="eikonal"')
     src = np.asarray(sources, dtype=np.float64).reshape(-1, 2)
@@ -1609,7 +1612,7 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
         g0 += len(sg)
     if fill is not None:
         T0 = np.ascontiguousarray(res["T"][:, 0] if arrivals is not None else res["T"])
-        done = eikonal_fill(field, src, grid, T0, stats=True)
+        done = eikonal_fill(field, src, grid, T0, stats=True, scheme=fill_scheme)
         if arrivals is not None:
             res["T"][:, 0] = done["T"]
         else:
@@ -1631,14 +1634,16 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     return res
 
 
-def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False, _width=0):
-    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny); _global_path and _width (the chunk width of the batched sweeps)
-    are for tests: no result depends on them"""
+def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False, _width=0, scheme="plain"):
+    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny); scheme "plain" or "factored" is read by the fills alone;
+    _global_path and _width (the chunk width of the batched sweeps) are for tests: no result depends on them"""
     gx0, gdx, nx, gy0, gdy, ny = grid
+    if scheme not in _lib.EIKONAL_SCHEMES:
+        raise ValueError('eikonal: scheme must be "plain" or "factored"')
     ep = _lib.EikonalParams()
     ep.gx0 = float(gx0); ep.gdx = float(gdx); ep.nx = int(nx)
     ep.gy0 = float(gy0); ep.gdy = float(gdy); ep.ny = int(ny)
-    ep.ball = float(ball); ep.max_rounds = int(max_rounds)
+    ep.ball = float(ball); ep.max_rounds = int(max_rounds); ep.scheme = _lib.EIKONAL_SCHEMES[scheme]
     ep.reserved[0] = int(bool(_global_path))
     ep.reserved[1] = int(_width)
     return ep
@@ -1664,7 +1669,8 @@ def _eikonal_medium(who, field_or_n, src, grid, n_src):
     return n, (np.zeros(0) if n_src is None else n_src)
 
 
-def eikonal_fill(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+def eikonal_fill(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max_rounds=0, stats=False, scheme="plain",
+                 _global_path=False):
     """Complete traveltime tables by a first-arrival eikonal solve on the device (rtmi_eikonal_fill, include/rtmi.h; DESIGN.md
     34): the first-order Godunov upwind scheme for |grad T| = n by fast sweeping, seeded by the finite nodes of T and an analytic
     ball of `ball` cells round each source (negative: none).  field_or_n: a Field, sampled at the nodes and at the sources, or
@@ -1675,7 +1681,10 @@ def eikonal_fill(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max
       filled             [S, ny, nx] uint8, 1 where the call gave the value
       rounds, converged  [S]: the rounds of four sweeps that ran (at most max_rounds, 0: 64), and whether the last changed nothing
     and with stats=True 'stats'.  The error is first order in the spacing: about 1 % of the largest T where the ball is the
-    only seed, 1e-3 to 1e-4 in a shadow of a table that rays cover elsewhere -- shoot the full fan and let this fill the rest."""
+    only seed, 1e-3 to 1e-4 in a shadow of a table that rays cover elsewhere -- shoot the full fan and let this fill the rest.
+    scheme="factored"  differences T - n_src r in place of T: still first order, but 6 to 10 times less error
+    where the ball is the only seed, exact to rounding in a constant medium, at the price of some ten rounds in place of two; far
+    from the source, in the shadow of a table, it gains nothing.  The default "plain" keeps every bit."""
     who = "eikonal_fill"
     src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
     S, nx, ny = len(src), int(grid[2]), int(grid[5])
@@ -1695,7 +1704,7 @@ def eikonal_fill(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max
             raise ValueError(f"{who}: T must be [S, ny, nx]")
     rounds = np.zeros((S, 2), dtype=np.int32)
     filled = np.zeros(shape, dtype=np.uint8)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, scheme=scheme)
     st = _lib.EikonalStats()
     check(lib().rtmi_eikonal_fill(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(out), rounds.ctypes.data_as(_lib._ip),
                                   filled.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
@@ -1705,7 +1714,8 @@ def eikonal_fill(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max
     return res
 
 
-def eikonal_fill_device(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+def eikonal_fill_device(field_or_n, sources, grid, T=None, *, n_src=None, ball=2.0, max_rounds=0, stats=False, scheme="plain",
+                        _global_path=False):
     """eikonal_fill on torch tensors of one GPU, with no host copy of the tables (rtmi_eikonal_fill_dev): n [ny, nx], sources
     [S, 2], n_src [S] and T [S, ny, nx] in fp64, contiguous; a Field in place of n is sampled as in eikonal_fill.  T is
     completed IN PLACE and returned; None: a new table from an all-NaN input.  filled is a uint8 tensor on the device; rounds
@@ -1747,7 +1757,7 @@ def eikonal_fill_device(field_or_n, sources, grid, T=None, *, n_src=None, ball=2
         raise ValueError(f"{who}: T must be [S, ny, nx]")
     filled = torch.zeros((S, ny, nx), dtype=torch.uint8, device=n.device)
     rounds = np.zeros((S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, scheme=scheme)
     st = _lib.EikonalStats()
     torch.cuda.synchronize(n.device)               # the library works on the null stream
     with torch.cuda.device(n.device):
@@ -2181,13 +2191,17 @@ class EikonalTomography:
     residual of picks, LSQR on the device and Gauss-Newton.  Row s R + k is source s, receiver k.  field_or_n, sources, grid,
     n_src, ball, max_rounds as in eikonal_fill.  fill_result: the dict of the eikonal_fill call that gave the tables (this is how
     a table seeded by rays enters); None: the handle fills its own from the ball, and only then can it be re-linearised.
+    scheme "plain" or "factored"  is the scheme of that own fill and of every relinearise; it cannot be given
+    together with fill_result, whose tables are already made.  The products linearise the plain update about the table either way.
     n_src follows the model through the bilinear weights of the source's cell where the source lies inside the grid.  A row is
     live where none of the four nodes round its receiver is an obstacle or unreached; other rows read and give 0."""
 
-    def __init__(self, field_or_n, sources, grid, receivers, *, fill_result=None, n_src=None, ball=2.0, max_rounds=0, _global_path=False,
-                 _width=0):
+    def __init__(self, field_or_n, sources, grid, receivers, *, fill_result=None, n_src=None, ball=2.0, max_rounds=0, scheme=None,
+                 _global_path=False, _width=0):
         who = "EikonalTomography"
         self._h = None
+        if scheme is not None and fill_result is not None:
+            raise ValueError(f"{who}: scheme is the scheme of the handle's own fill; it cannot be given together with fill_result")
         src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
         S, nx, ny = len(src), int(grid[2]), int(grid[5])
         n, ns = _eikonal_medium(who, field_or_n, src, grid, n_src)
@@ -2206,7 +2220,7 @@ class EikonalTomography:
                 raise ValueError(f"{who}: fill_result's T and filled must be [S, ny, nx]")
         self.grid, self.S, self.R, self.nx, self.ny = tuple(grid), S, len(rec), nx, ny
         self.n, self.sources, self.receivers = n.copy(), src, rec
-        ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+        ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, scheme="plain" if scheme is None else scheme)
         h = C.c_void_p()
         check(lib().rtmi_eikonal_tomo_create(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
                                              None if filled is None else filled.ctypes.data_as(C.POINTER(C.c_uint8)), len(rec), dptr(rec),
