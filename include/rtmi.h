@@ -1312,7 +1312,8 @@ int rtmi_locate_edt_pdf_dev(rtmi_locator *loc, const rtmi_edt_params *ep, const 
  * stats stay host memory); rtmi_eikonal_fill is upload, that, download: the same bits.
  * RTMI_ERR_ARG before any device work, with rtmi_last_error naming the argument: a null ep; nx or ny < 1; nx ny > 2^31; gdx or gdy
  * not finite or <= 0; gx0 or gy0 not finite; S < 0; a null n, src or n_src with S > 0; max_rounds < 0; a ball that is not finite;
- * ep->reserved[0] other than 0 or 1; a scheme that is neither RTMI_EIKONAL_PLAIN nor RTMI_EIKONAL_FACTORED.
+ * ep->reserved[0] other than 0 or 1; a scheme that is none of RTMI_EIKONAL_PLAIN, RTMI_EIKONAL_FACTORED and
+ * RTMI_EIKONAL_FACTORED_LIN.
  * ep->scheme = RTMI_EIKONAL_FACTORED is the source-factored scheme (tests/eikonal_factored_ref.py restates
  * it): T = T0 + u with T0 = n_src r, and u is what is differenced.  States, the ball, the sweeps, the round rule, filled and
  * unreached are as above; the update of a free node (ix, iy) reads l, r, dn, up = T[j][i-1], T[j][i+1], T[j-1][i], T[j+1][i] and,
@@ -1325,16 +1326,21 @@ int rtmi_locate_edt_pdf_dev(rtmi_locator *loc, const rtmi_edt_params *ep, const 
  * finite or <= 0 and at a node with rr == 0.  Still first order, but with 6 to 10 times less error where the ball is the only
  * seed, and exact to rounding in a constant medium; the rounds converge geometrically, some ten in a smooth medium where the plain
  * scheme takes two, and a round costs three sqrt and two quotients more per update.  rtmi_eikonal_fill and rtmi_eikonal_fill_dev
- * read scheme, and rtmi_eikonal_tomo_create through them (a self-filled handle fills and re-linearises with it).  The tangent,
- * adjoint, attributes and _multi entries ignore the field: they linearise the plain update about the table they are given, and
- * tolerate a table that is not the plain scheme's fixed point (they recompute the node's value and drop a parent that is not
- * strictly earlier).  RTMI_EIKONAL_PLAIN gives the bits of the scheme above.
+ * read scheme, and rtmi_eikonal_tomo_create through them (a self-filled handle fills and re-linearises with it).  Under
+ * RTMI_EIKONAL_PLAIN and RTMI_EIKONAL_FACTORED the tangent, adjoint and _multi entries ignore the field, and the attributes entries
+ * under every value: they linearise the plain update about the table they are given, and tolerate a table that is not the plain
+ * scheme's fixed point (they recompute the node's value and drop a parent that is not strictly earlier).  RTMI_EIKONAL_PLAIN gives
+ * the bits of the scheme above.
+ * ep->scheme = RTMI_EIKONAL_FACTORED_LIN fills exactly as RTMI_EIKONAL_FACTORED does, with the same bits, and makes the tangent,
+ * adjoint and _multi entries, and a tomography handle created with it, linearise the factored update itself: see
+ * rtmi_eikonal_tangent below.  The plain linearisation of a factored table is off by about 1 % of the largest |dT| for a smooth
+ * dn, by 10 % for a rough one and by its own size for dn_src.
  * Not covered: second- or higher-order schemes (the error stays first order under either scheme: about 1 % of the largest T
  * where the ball is the only seed under RTMI_EIKONAL_PLAIN, about 0.2 % under the other); covered nodes never
  * decrease, so a head wave does not undercut a table's geometric arrival; amplitudes, launch angles and count at filled nodes;
- * anisotropy; 3-D; several GPUs; fp32 tables; the linearisation of the corrected update itself; a stop tolerance on the rounds. */
+ * anisotropy; 3-D; several GPUs; fp32 tables; a stop tolerance on the rounds. */
 enum { RTMI_EIKONAL_LDS = 1, RTMI_EIKONAL_GLOBAL = 2 };
-enum { RTMI_EIKONAL_PLAIN = 0, RTMI_EIKONAL_FACTORED = 1 };
+enum { RTMI_EIKONAL_PLAIN = 0, RTMI_EIKONAL_FACTORED = 1, RTMI_EIKONAL_FACTORED_LIN = 3 };
 typedef struct {
     double gx0, gdx;         /* as in rtmi_grid_params */
     int64_t nx;
@@ -1342,7 +1348,8 @@ typedef struct {
     int64_t ny;
     double ball;             /* the radius of the source ball in cells; negative: no ball.  The Python layer's default is 2 */
     int32_t max_rounds;      /* 0: 64 */
-    int32_t scheme;          /* RTMI_EIKONAL_PLAIN (0) or RTMI_EIKONAL_FACTORED; read by the fills alone */
+    int32_t scheme;          /* RTMI_EIKONAL_PLAIN (0), RTMI_EIKONAL_FACTORED, or RTMI_EIKONAL_FACTORED_LIN: that fill, and the tangent and
+                                adjoint entries linearise it */
     int64_t reserved[4];
 } rtmi_eikonal_params;
 typedef struct {
@@ -1403,6 +1410,21 @@ int rtmi_eikonal_fill_dev(const rtmi_eikonal_params *ep, const double *d_n, int6
  *            in groups of at most 1 GiB).  ep->reserved[0] = 1 takes the global path, for tests.
  * The _dev forms take every array but rounds and stats as memory of the calling thread's current device; the host forms are
  * upload, that, download: the same bits.  RTMI_ERR_ARG as in rtmi_eikonal_fill, and for a null T, filled, dn, dT, r or lam with S > 0.
+ * ep->scheme = RTMI_EIKONAL_FACTORED_LIN (tests/eikonal_factored_lin_ref.py restates it) linearises the
+ * factored update, for a table that RTMI_EIKONAL_FACTORED filled; every other value of scheme gives the maps above.  Classes, seeds,
+ * nodes of the ball and dead nodes are as above.  A free node (ix, iy) of a source whose n_src is finite and > 0, with rr != 0 at
+ * the node (rtmi_eikonal_fill's dx, dy, rr), chooses its parents on the raw readings, east iff r < l and north iff up < dn, and
+ *     a, b   the corrected readings of the fill's factored update;  ca, cb, cs, the branch and the strict-parent rule are those
+ *            above on a and b, the rule testing the corrected reading (a < t, b < t)
+ *     ka = (rr - rr[x-parent]) +- gdx (dx / rr), + for east;  kb = (rr - rr[y-parent]) +- gdy (dy / rr), + for north
+ *     csrc = the sum from +0.0 of ca ka, where the node has an x-parent, and cb kb, where it has a y-parent
+ * and every other free node has the coefficients above and csrc = 0.  Tangent: a free node's constant term is (cs dn) + (csrc
+ * dn_src) in place of cs dn.  Adjoint: g_src = the sum from +0.0 over the rows in ascending iy of each row's sum from +0.0, over ix
+ * ascending, of csrc lam at the row's free nodes and nodes of the ball.  The gathers, the starting values, the sweep orders and the
+ * round rule are unchanged, but a corrected parent need not be earlier in T: the network is not provably acyclic, so here the
+ * sweeps from those starting values, capped by max_rounds, ARE the definition of the bits, and no single pass in the order of T
+ * gives them.  Some ten rounds in a smooth medium where the plain maps take two or three; a round costs the same.  The adjoint's
+ * work space grows by 8 ny bytes per source.
  * Not covered: seeds that move; anisotropy; 3-D; fp32.  Several right-hand sides in one call: the _multi entries below.  Receivers off the
  * nodes and the LSQR loop on the device: rtmi_eikonal_tomo_* below. */
 int rtmi_eikonal_tangent(const rtmi_eikonal_params *ep, const double *n, int64_t S, const double *src, const double *n_src,

@@ -231,8 +231,9 @@ class EikonalTomoStats(C.Structure):
 
 EIKONAL_LDS, EIKONAL_GLOBAL = 1, 2      # rtmi_eikonal_stats.path
 EIKONAL_PATHS = {EIKONAL_LDS: "lds", EIKONAL_GLOBAL: "global"}
-EIKONAL_PLAIN, EIKONAL_FACTORED = 0, 1  # rtmi_eikonal_params.scheme
+EIKONAL_PLAIN, EIKONAL_FACTORED, EIKONAL_FACTORED_LIN = 0, 1, 3  # rtmi_eikonal_params.scheme
 EIKONAL_SCHEMES = {"plain": EIKONAL_PLAIN, "factored": EIKONAL_FACTORED}
+EIKONAL_LINEARISE = ("plain", "factored")  # the linearisation of the tangent and adjoint entries; "factored" is EIKONAL_FACTORED_LIN
 
 
 class StackParams(C.Structure):

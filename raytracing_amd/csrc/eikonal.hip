@@ -154,7 +154,7 @@ int eikonal_dev(const char* who, const rtmi_eikonal_params* ep, const double* d_
         }
         unsigned long long* d_out = nullptr;
         RTMI_ALLOC(mem.get(&d_out, (size_t)S * kOutWords * sizeof(unsigned long long)));
-        const bool factored = ep->scheme == RTMI_EIKONAL_FACTORED;
+        const bool factored = eikonal_fills_factored(ep);
         auto* const kernel = lds ? (factored ? k_eikonal<true, true> : k_eikonal<true, false>)
                                  : (factored ? k_eikonal<false, true> : k_eikonal<false, false>);
         if (lds && lds_bytes > 65536)

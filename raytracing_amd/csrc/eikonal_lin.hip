@@ -12,6 +12,10 @@
 //                   stays in global memory on both paths: r itself (adjoint) or cs dn in a work space (tangent).
 // Every loop bound and every barrier is uniform across the block and max_rounds bounds the whole; no block waits for another.
 // No atomics on floating point; g_src is summed by one lane in node order.
+// FACT (ep->scheme == RTMI_EIKONAL_FACTORED_LIN) is the factored update linearised: only the setup differs.  A
+// free node's coefficients come from the corrected readings, T0 and rr recomputed in registers as k_eikonal<..., FACTORED> does; csrc
+// goes into the tangent's constant term, and the adjoint recomputes it from ca, cb and the code in the g_src pass, which the lanes
+// take a row each before one lane adds the ny row sums from a small work space.  The sweeps are the same code.
 #include "rtmi_host.h"
 
 #include "rt_eikonal_lin.h"
@@ -43,11 +47,14 @@ struct LinArgs {
     double* g_src;              // adjoint: [S] or NULL
     double *ca, *cb;            // global path: [S][ny][nx]
     uint8_t *code, *kids;       // global path: [S][ny][nx]; kids: adjoint
-    double* k;                  // tangent: [S][ny][nx]
+    union {                     // one slot, so that the argument block keeps its size
+        double* k;              // tangent: [S][ny][nx]
+        double* gpart;          // adjoint, FACT: [S][ny], the rows' shares of g_src
+    };
     unsigned long long* out;    // [S][kOutWords]
 };
 
-template <bool LDS, bool ADJ> __global__ void __launch_bounds__(kMaxBlock) k_eikonal_lin(const LinArgs a) {
+template <bool LDS, bool ADJ, bool FACT> __global__ void __launch_bounds__(kMaxBlock) k_eikonal_lin(const LinArgs a) {
     extern __shared__ double lds[];                     // LDS: [v | ca | cb | code | kids]
     __shared__ unsigned long long red[2][kMaxBlock / 64];
     const int tid = (int)threadIdx.x, bd = (int)blockDim.x;
@@ -82,7 +89,7 @@ template <bool LDS, bool ADJ> __global__ void __launch_bounds__(kMaxBlock) k_eik
     unsigned long long nfree = 0, nnodes = 0, nstray = 0;
     for (long x = tid; x < nn; x += bd) {
         const long i = x % nx, j = x / nx;
-        const rt::EikLinNode c = rt::eik_lin_node(a.g, nx, ny, i, j, a.n, Ts, fs, xs, ys, n_src, a.ball);
+        const rt::EikLinNode c = rt::eik_lin_node_of<FACT>(a.g, nx, ny, i, j, a.n, Ts, fs, xs, ys, n_src, a.ball);
         const uint8_t cls = rt::eik_lin_class(c.code);
         ca[x] = c.ca;
         cb[x] = c.cb;
@@ -92,7 +99,10 @@ template <bool LDS, bool ADJ> __global__ void __launch_bounds__(kMaxBlock) k_eik
             if (cls == rt::kLinBall && !(i >= bi0 && i <= bi1 && j >= bj0 && j <= bj1)) nstray++;
         } else {
             double k;
-            v[x] = rt::eik_lin_tangent_init(c, a.dn[x], a.dn_src ? a.dn_src[s] : 0.0, a.seed ? a.seed[s * (size_t)nn + x] : 0.0, &k);
+            if constexpr (FACT)
+                v[x] = rt::eik_flin_tangent_init(c, a.dn[x], a.dn_src ? a.dn_src[s] : 0.0, a.seed ? a.seed[s * (size_t)nn + x] : 0.0, &k);
+            else
+                v[x] = rt::eik_lin_tangent_init(c, a.dn[x], a.dn_src ? a.dn_src[s] : 0.0, a.seed ? a.seed[s * (size_t)nn + x] : 0.0, &k);
             a.k[s * (size_t)nn + x] = k;
         }
         if (cls >= rt::kLinFree) nnodes++;
@@ -148,12 +158,24 @@ template <bool LDS, bool ADJ> __global__ void __launch_bounds__(kMaxBlock) k_eik
             if (a.gout) {
                 double gv = 0.0;
                 if (rt::eik_lin_class(code[x]) >= rt::kLinFree)
-                    gv = rt::eik_lin_node(a.g, nx, ny, x % nx, x / nx, a.n, Ts, fs, xs, ys, n_src, a.ball).cs * val;
+                    gv = rt::eik_lin_node_of<FACT>(a.g, nx, ny, x % nx, x / nx, a.n, Ts, fs, xs, ys, n_src, a.ball).cs * val;
                 a.gout[s * (size_t)nn + x] = gv;
             }
         }
     }
-    if constexpr (ADJ) {
+    if constexpr (ADJ && FACT) {
+        if (a.g_src) {                       // uniform across the block
+            // a lane per row, then one lane over the ny row sums in ascending j
+            double* part = a.gpart + s * (size_t)ny;
+            for (long j = tid; j < ny; j += bd) rt::eik_flin_g_src_row<1>(a.g, nx, j, xs, ys, n_src, code, ca, cb, v, &part[j]);
+            __syncthreads();
+            if (tid == 0) {
+                double acc = 0.0;
+                for (long j = 0; j < ny; j++) acc = acc + part[j];
+                a.g_src[s] = acc;
+            }
+        }
+    } else if constexpr (ADJ) {
         if (a.g_src && tid == 0) {
             // nstray is 0 unless the box missed a node of the ball: then every node is looked at
             const long i0 = nstray ? 0 : bi0, i1 = nstray ? nx - 1 : bi1, j0 = nstray ? 0 : bj0, j1 = nstray ? ny - 1 : bj1;
@@ -200,10 +222,14 @@ template <bool ADJ> int lin_dev(const char* who, const rtmi_eikonal_params* ep, 
             if (ADJ) RTMI_ALLOC(mem.get(&a.kids, group * nn));
         }
         if (!ADJ) RTMI_ALLOC(mem.get(&a.k, group * nn * sizeof(double)));
+        const bool fact = ep->scheme == RTMI_EIKONAL_FACTORED_LIN;
+        if (ADJ && fact && a.g_src) RTMI_ALLOC(mem.get(&a.gpart, group * (size_t)ep->ny * sizeof(double)));
         unsigned long long* d_out = nullptr;
         RTMI_ALLOC(mem.get(&d_out, (size_t)S * kOutWords * sizeof(unsigned long long)));
+        auto* const kernel = lds ? (fact ? k_eikonal_lin<true, ADJ, true> : k_eikonal_lin<true, ADJ, false>)
+                                 : (fact ? k_eikonal_lin<false, ADJ, true> : k_eikonal_lin<false, ADJ, false>);
         if (lds && lds_bytes > 65536)
-            RTMI_HIP(hipFuncSetAttribute((const void*)k_eikonal_lin<true, ADJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+            RTMI_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
         const LinArgs all = a;
         EventMarks<2> marks;
         RTMI_HIP(marks.create());
@@ -221,8 +247,7 @@ template <bool ADJ> int lin_dev(const char* who, const rtmi_eikonal_params* ep, 
             a.gout = all.gout ? all.gout + s0 * nn : nullptr;
             a.g_src = all.g_src ? all.g_src + s0 : nullptr;
             a.out = d_out + s0 * kOutWords;
-            if (lds) hipLaunchKernelGGL((k_eikonal_lin<true, ADJ>), dim3((unsigned)gs), dim3(block), lds_bytes, nullptr, a);
-            else hipLaunchKernelGGL((k_eikonal_lin<false, ADJ>), dim3((unsigned)gs), dim3(block), 0, nullptr, a);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)gs), dim3(block), lds ? lds_bytes : 0, nullptr, a);
             RTMI_HIP(hipGetLastError());
         }
         RTMI_HIP(marks.mark(1));
@@ -426,7 +451,10 @@ struct LinMultiArgs {
     const double* n_src;        // [S]
     const double* T;            // [S][ny][nx]
     const uint8_t* filled;      // [S][ny][nx]
-    const double* dn;           // tangent: [K][ny][nx]
+    union {                     // one slot, so that the argument block keeps its size
+        const double* dn;       // tangent: [K][ny][nx]
+        double* gpart;          // adjoint, FACT: [chunks][gs][ny][C], the rows' shares of g_src
+    };
     const double* dn_src;       // tangent: [K][S] or NULL
     const double* seed;         // tangent: [K][S][ny][nx] or NULL
     const double* r;            // adjoint: [K][S][ny][nx]
@@ -440,13 +468,13 @@ struct LinMultiArgs {
     unsigned long long* out;    // [K][S][kOutWords]
 };
 
-__global__ void __launch_bounds__(256) k_eikonal_lin_setup(const LinMultiArgs a, long total) {
+template <bool FACT> __global__ void __launch_bounds__(256) k_eikonal_lin_setup(const LinMultiArgs a, long total) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
     const long nn = a.nx * a.ny, x = t % nn;
     const size_t s = a.s0 + (size_t)(t / nn);
-    const rt::EikLinNode c = rt::eik_lin_node(a.g, a.nx, a.ny, x % a.nx, x / a.nx, a.n, a.T + s * (size_t)nn, a.filled + s * (size_t)nn,
-                                              a.src[2 * s], a.src[2 * s + 1], a.n_src[s], a.ball);
+    const rt::EikLinNode c = rt::eik_lin_node_of<FACT>(a.g, a.nx, a.ny, x % a.nx, x / a.nx, a.n, a.T + s * (size_t)nn,
+                                                       a.filled + s * (size_t)nn, a.src[2 * s], a.src[2 * s + 1], a.n_src[s], a.ball);
     a.ca[t] = c.ca;
     a.cb[t] = c.cb;
     a.code[t] = c.code;
@@ -477,7 +505,7 @@ template <int C> __device__ __forceinline__ void block_sum_cols(unsigned long lo
     }
 }
 
-template <bool LDS, bool ADJ, int C> __global__ void __launch_bounds__(kMaxBlock) k_eikonal_lin_multi(const LinMultiArgs a) {
+template <bool LDS, bool ADJ, int C, bool FACT> __global__ void __launch_bounds__(kMaxBlock) k_eikonal_lin_multi(const LinMultiArgs a) {
     extern __shared__ double lds[];                     // LDS: [v [nn][C] | ca | cb | code | kids]
     __shared__ unsigned long long red[2][kMaxBlock / 64];
     __shared__ unsigned long long redc[2][kMaxBlock / 64][C];
@@ -514,7 +542,7 @@ template <bool LDS, bool ADJ, int C> __global__ void __launch_bounds__(kMaxBlock
         const long i = x % nx, j = x / nx;
         rt::EikLinNode c{0.0, 0.0, 0.0, 0.0, 0};
         if constexpr (LDS || !ADJ) {
-            c = rt::eik_lin_node(a.g, nx, ny, i, j, a.n, Ts, fs, xs, ys, n_src, a.ball);
+            c = rt::eik_lin_node_of<FACT>(a.g, nx, ny, i, j, a.n, Ts, fs, xs, ys, n_src, a.ball);
             if constexpr (LDS) {
                 ca[x] = c.ca;
                 cb[x] = c.cb;
@@ -535,8 +563,12 @@ template <bool LDS, bool ADJ, int C> __global__ void __launch_bounds__(kMaxBlock
                     k[q] = a.r[plane + x];
                     val[q] = cls == rt::kLinDead ? 0.0 : k[q];
                 } else {
-                    val[q] = rt::eik_lin_tangent_init(c, a.dn[col * (size_t)nn + x], a.dn_src ? a.dn_src[col * S + s] : 0.0,
-                                                      a.seed ? a.seed[plane + x] : 0.0, &k[q]);
+                    if constexpr (FACT)
+                        val[q] = rt::eik_flin_tangent_init(c, a.dn[col * (size_t)nn + x], a.dn_src ? a.dn_src[col * S + s] : 0.0,
+                                                           a.seed ? a.seed[plane + x] : 0.0, &k[q]);
+                    else
+                        val[q] = rt::eik_lin_tangent_init(c, a.dn[col * (size_t)nn + x], a.dn_src ? a.dn_src[col * S + s] : 0.0,
+                                                          a.seed ? a.seed[plane + x] : 0.0, &k[q]);
                 }
             }
         }
@@ -622,7 +654,7 @@ template <bool LDS, bool ADJ, int C> __global__ void __launch_bounds__(kMaxBlock
         if constexpr (ADJ) {
             if (a.gout && rt::eik_lin_class(code[x]) >= rt::kLinFree) {
                 live = true;
-                cs = rt::eik_lin_node(a.g, nx, ny, x % nx, x / nx, a.n, Ts, fs, xs, ys, n_src, a.ball).cs;
+                cs = rt::eik_lin_node_of<FACT>(a.g, nx, ny, x % nx, x / nx, a.n, Ts, fs, xs, ys, n_src, a.ball).cs;
             }
         }
 #pragma unroll
@@ -641,7 +673,24 @@ template <bool LDS, bool ADJ, int C> __global__ void __launch_bounds__(kMaxBlock
             }
         }
     }
-    if constexpr (ADJ) {
+    if constexpr (ADJ && FACT) {
+        if (a.g_src) {                       // uniform across the block
+            // a lane per row for the chunk's columns, then one lane per column over the ny row sums in ascending j
+            double* part = a.gpart + slot * (size_t)ny * C;
+            for (long j = tid; j < ny; j += bd) {
+                double row[C];
+                rt::eik_flin_g_src_row<C>(a.g, nx, j, xs, ys, n_src, code, ca, cb, v, row);
+#pragma unroll
+                for (int q = 0; q < C; q++) part[j * C + q] = row[q];
+            }
+            __syncthreads();
+            if (tid < ncol) {
+                double acc = 0.0;
+                for (long j = 0; j < ny; j++) acc = acc + part[j * C + tid];
+                a.g_src[(size_t)(col0 + tid) * S + s] = acc;
+            }
+        }
+    } else if constexpr (ADJ) {
         if (a.g_src && tid < ncol) {
             // one lane per column, in node order.  nstray is 0 unless the box missed a node of the ball: then every node is looked at
             const long i0 = nstray ? 0 : bi0, i1 = nstray ? nx - 1 : bi1, j0 = nstray ? 0 : bj0, j1 = nstray ? ny - 1 : bj1;
@@ -706,18 +755,27 @@ MultiPlan multi_choose(int K, size_t S, size_t nn, int cus, bool force_global, i
     return best;
 }
 
-template <bool ADJ, int C> int lin_multi_launch(const char* who, bool lds, size_t lds_bytes, dim3 grid, int block, const LinMultiArgs& a) {
+template <bool ADJ, int C, bool FACT> int lin_multi_launch(const char* who, bool lds, size_t lds_bytes, dim3 grid, int block,
+                                                           const LinMultiArgs& a) {
     if (lds) {
         // the kernel's static LDS (red and redc) counts against the 64 KiB that need no attribute
         if (lds_bytes + sizeof(unsigned long long) * 2 * (kMaxBlock / 64) * (1 + C) > 65536)
-            RTMI_HIP(hipFuncSetAttribute((const void*)k_eikonal_lin_multi<true, ADJ, C>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            RTMI_HIP(hipFuncSetAttribute((const void*)k_eikonal_lin_multi<true, ADJ, C, FACT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)kLdsBudget));
-        hipLaunchKernelGGL((k_eikonal_lin_multi<true, ADJ, C>), grid, dim3(block), lds_bytes, nullptr, a);
+        hipLaunchKernelGGL((k_eikonal_lin_multi<true, ADJ, C, FACT>), grid, dim3(block), lds_bytes, nullptr, a);
     } else {
-        hipLaunchKernelGGL((k_eikonal_lin_multi<false, ADJ, C>), grid, dim3(block), 0, nullptr, a);
+        hipLaunchKernelGGL((k_eikonal_lin_multi<false, ADJ, C, FACT>), grid, dim3(block), 0, nullptr, a);
     }
     RTMI_HIP(hipGetLastError());
     return RTMI_OK;
+}
+
+// the launch at the call's chunk width
+template <bool ADJ, bool FACT> int lin_multi_launch_width(const char* who, int C, bool lds, size_t lds_bytes, dim3 grid, int block,
+                                                          const LinMultiArgs& a) {
+    if (C == 1) return lin_multi_launch<ADJ, 1, FACT>(who, lds, lds_bytes, grid, block, a);
+    if (C == 4) return lin_multi_launch<ADJ, 4, FACT>(who, lds, lds_bytes, grid, block, a);
+    return lin_multi_launch<ADJ, 8, FACT>(who, lds, lds_bytes, grid, block, a);
 }
 
 // One batched call on device memory: a holds the caller's pointers for all S sources and K columns
@@ -755,6 +813,8 @@ template <bool ADJ> int lin_multi_dev(const char* who, const rtmi_eikonal_params
             RTMI_ALLOC(mem.get(&a.wv, gs * gc * nn * (size_t)C * sizeof(double)));
         }
         RTMI_ALLOC(mem.get(&a.wk, gs * gc * nn * (size_t)C * sizeof(double)));
+        const bool fact = ep->scheme == RTMI_EIKONAL_FACTORED_LIN;
+        if (ADJ && fact && a.g_src) RTMI_ALLOC(mem.get(&a.gpart, gs * gc * (size_t)ep->ny * (size_t)C * sizeof(double)));
         unsigned long long* d_out = nullptr;
         RTMI_ALLOC(mem.get(&d_out, (size_t)K * (size_t)S * kOutWords * sizeof(unsigned long long)));
         a.out = d_out;
@@ -766,7 +826,7 @@ template <bool ADJ> int lin_multi_dev(const char* who, const rtmi_eikonal_params
             a.s0 = s0;
             if (!lds) {
                 const long lanes = (long)(ns * nn);
-                hipLaunchKernelGGL(k_eikonal_lin_setup, blocks(lanes), dim3(256), 0, nullptr, a, lanes);
+                hipLaunchKernelGGL(fact ? k_eikonal_lin_setup<true> : k_eikonal_lin_setup<false>, blocks(lanes), dim3(256), 0, nullptr, a, lanes);
                 if (ADJ) hipLaunchKernelGGL(k_eikonal_lin_kids, blocks(lanes), dim3(256), 0, nullptr, a, lanes);
                 RTMI_HIP(hipGetLastError());
             }
@@ -774,9 +834,8 @@ template <bool ADJ> int lin_multi_dev(const char* who, const rtmi_eikonal_params
                 const size_t nc = std::min(gc, chunks - ch);
                 a.c0 = (int)(ch * (size_t)C);
                 const dim3 grid((unsigned)ns, (unsigned)nc);
-                if (C == 1) RTMI_RC((lin_multi_launch<ADJ, 1>(who, lds, lds_bytes, grid, block, a)));
-                else if (C == 4) RTMI_RC((lin_multi_launch<ADJ, 4>(who, lds, lds_bytes, grid, block, a)));
-                else RTMI_RC((lin_multi_launch<ADJ, 8>(who, lds, lds_bytes, grid, block, a)));
+                if (fact) RTMI_RC((lin_multi_launch_width<ADJ, true>(who, C, lds, lds_bytes, grid, block, a)));
+                else RTMI_RC((lin_multi_launch_width<ADJ, false>(who, C, lds, lds_bytes, grid, block, a)));
             }
         }
         RTMI_HIP(marks.mark(1));

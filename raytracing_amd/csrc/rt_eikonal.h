@@ -147,6 +147,39 @@ RT_EIK_HD double eik_update_factored(const EikGrid& g, long i, long j, double xs
     return eik_update(g, a, b, s);
 }
 
+// What eik_update_factored hands to eik_update at free node (i, j), in the same expressions, with the sides the raw readings chose
+// (*east, *north): what the linearisation of that update starts from (rt_eikonal_lin.h).  The raw readings where both are +inf,
+// where n_src is an obstacle's or where rr == 0.
+RT_EIK_HD void eik_factored_readings(const EikGrid& g, long i, long j, double xs, double ys, double n_src, double l, double r, double dn,
+                                     double up, double* pa, double* pb, bool* east, bool* north) {
+    const double inf = eik_inf();
+    *east = r < l;
+    *north = up < dn;
+    double a = *east ? r : l, b = *north ? up : dn;
+    *pa = a;
+    *pb = b;
+    if (a == inf && b == inf) return;
+    double dx, dy, pdx, pdy;                  // the node's; the parent's, not used
+    const double rr = eik_rr(g, i, j, xs, ys, &dx, &dy);
+    if (!eik_obstacle(n_src) && rr != 0.0) {
+        const double T0 = n_src * rr;
+        if (a != inf) {
+            const double T0p = n_src * eik_rr(g, *east ? i + 1 : i - 1, j, xs, ys, &pdx, &pdy);
+            const double px = g.gdx * (n_src * (dx / rr));
+            a = a + (T0 - T0p);
+            a = *east ? a + px : a - px;
+        }
+        if (b != inf) {
+            const double T0p = n_src * eik_rr(g, i, *north ? j + 1 : j - 1, xs, ys, &pdx, &pdy);
+            const double py = g.gdy * (n_src * (dy / rr));
+            b = b + (T0 - T0p);
+            b = *north ? b + py : b - py;
+        }
+    }
+    *pa = a;
+    *pb = b;
+}
+
 // what one source's solve reports
 struct EikResult {
     int32_t rounds, clean;

@@ -43,11 +43,16 @@ int check_eikonal(const char* who, const rtmi_eikonal_params* ep, const void* n,
     return RTMI_OK;
 }
 
-// what the fills, which alone read ep->scheme, refuse on top of that
+// what the fills, which read ep->scheme as a scheme of theirs, refuse on top of that
 int check_eikonal_scheme(const char* who, const rtmi_eikonal_params* ep) {
-    RTMI_ARG(ep->scheme == RTMI_EIKONAL_PLAIN || ep->scheme == RTMI_EIKONAL_FACTORED,
-             "scheme must be RTMI_EIKONAL_PLAIN or RTMI_EIKONAL_FACTORED");
+    RTMI_ARG(ep->scheme == RTMI_EIKONAL_PLAIN || ep->scheme == RTMI_EIKONAL_FACTORED || ep->scheme == RTMI_EIKONAL_FACTORED_LIN,
+             "scheme must be RTMI_EIKONAL_PLAIN, RTMI_EIKONAL_FACTORED or RTMI_EIKONAL_FACTORED_LIN");
     return RTMI_OK;
+}
+
+// the fill's scheme: RTMI_EIKONAL_FACTORED_LIN fills as RTMI_EIKONAL_FACTORED does
+bool eikonal_fills_factored(const rtmi_eikonal_params* ep) {
+    return ep->scheme == RTMI_EIKONAL_FACTORED || ep->scheme == RTMI_EIKONAL_FACTORED_LIN;
 }
 
 }  // namespace

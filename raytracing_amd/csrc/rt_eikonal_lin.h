@@ -37,6 +37,22 @@
 // adjoint every node that is not dead; a node changes when the bits of its value change.  No round runs where no node is free
 // (rounds 0, clean); else rounds repeat until one changes nothing (clean) or max_rounds have run.  Not clean: the values are
 // those of the last sweep, not the fixed point.
+//
+// The factored update linearised (rtmi_eikonal_params.scheme = RTMI_EIKONAL_FACTORED_LIN; DESIGN.md section 40;
+// tests/eikonal_factored_lin_ref.py restates it): the linearisation that is consistent with a table of the factored scheme
+// (rt_eikonal.h).  Classes, seeds, nodes of the ball and dead nodes are as above.  A free node x = (i, j) of a source whose n_src
+// is no obstacle's, with rr[x] != 0 (eik_rr), chooses its parents on the raw readings, east iff r < l, north iff up < dn, and
+//     a, b   eik_factored_readings' corrected readings;  ca, cb, cs, the branch and the strict-parent rule are eik_lin_coef's on a
+//            and b, the rule testing the corrected reading (a < t, b < t)
+//     ka = (rr[x] - rr[x-parent]) +- gdx (dx / rr[x]), + for east;  kb = (rr[x] - rr[y-parent]) +- gdy (dy / rr[x]), + for north
+//     csrc = the sum from +0.0 of ca ka, where the node has an x-parent, and cb kb, where it has a y-parent
+// Every other free node has the coefficients above and csrc = 0.
+// Tangent: a free node's constant term is (cs dn) + (csrc dn_src); the gather is unchanged.
+// Adjoint: the gather is unchanged; g_src = the sum from +0.0 over the rows in ascending j of each row's sum from +0.0, over i
+//     ascending, of csrc lam at the row's free nodes and nodes of the ball.
+// A corrected parent need not be earlier in T, so the network is not provably acyclic and one pass in the order of T is not its
+// fixed point: the bits are those of the sweep orders above from the starting values above, capped by max_rounds, and not clean
+// means the last sweep's values.  Some ten rounds in a smooth medium, as the factored fill.
 #pragma once
 #include "rt_eikonal.h"
 
@@ -134,6 +150,87 @@ RT_EIK_HD EikLinNode eik_lin_node(const EikGrid& g, long nx, long ny, long i, lo
     return c;
 }
 
+enum : int32_t { kEikFactoredLin = 3 };     // rtmi_eikonal_params.scheme: the factored fill, and this linearisation of it
+
+// csrc of a free node (i, j) in the factored linearisation from its parents and coefficients; 0 where the node is not factored
+RT_EIK_HD double eik_flin_csrc(const EikGrid& g, long i, long j, double xs, double ys, double n_src, uint8_t code, double ca, double cb) {
+    double dx, dy, pdx, pdy;                  // the node's; a parent's, not used
+    const double rr = eik_rr(g, i, j, xs, ys, &dx, &dy);
+    double acc = 0.0;
+    if (eik_obstacle(n_src) || rr == 0.0) return acc;
+    if (code & kLinXParent) {
+        const bool east = (code & kLinXEast) != 0;
+        const double d = rr - eik_rr(g, east ? i + 1 : i - 1, j, xs, ys, &pdx, &pdy), p = g.gdx * (dx / rr);
+        acc = acc + ca * (east ? d + p : d - p);
+    }
+    if (code & kLinYParent) {
+        const bool north = (code & kLinYNorth) != 0;
+        const double d = rr - eik_rr(g, i, north ? j + 1 : j - 1, xs, ys, &pdx, &pdy), p = g.gdy * (dy / rr);
+        acc = acc + cb * (north ? d + p : d - p);
+    }
+    return acc;
+}
+
+// The coefficients, csrc and parents of free node (i, j) in the factored linearisation from its four raw readings; the class bits
+// of code are not set.  eik_lin_coef gets the corrected reading on the side the raw readings chose and +inf on the other, so that
+// its min and its side are that reading and that side.
+RT_EIK_HD EikLinNode eik_flin_coef(const EikGrid& g, long i, long j, double xs, double ys, double n_src, double l, double r, double dn,
+                                   double up, double s, double t) {
+    const double inf = eik_inf();
+    double a, b;
+    bool east, north;
+    eik_factored_readings(g, i, j, xs, ys, n_src, l, r, dn, up, &a, &b, &east, &north);
+    EikLinNode c = eik_lin_coef(g, east ? inf : a, east ? a : inf, north ? inf : b, north ? b : inf, s, t);
+    c.csrc = eik_flin_csrc(g, i, j, xs, ys, n_src, c.code, c.ca, c.cb);
+    return c;
+}
+
+// eik_lin_node in the factored linearisation: the free nodes differ
+RT_EIK_HD EikLinNode eik_flin_node(const EikGrid& g, long nx, long ny, long i, long j, const double* n, const double* T,
+                                   const uint8_t* filled, double xs, double ys, double n_src, double ball) {
+    const long x = j * nx + i;
+    const double s = n[x], t = T[x], inf = eik_inf();
+    EikLinNode c{0.0, 0.0, 0.0, 0.0, 0};
+    if (eik_obstacle(s) || !eik_finite(t)) return c;                    // dead
+    if (!filled[x]) {
+        c.code = (uint8_t)(kLinSeed << 4);
+        return c;
+    }
+    double w;
+    if (eik_init(g, i, j, s, eik_nan(), xs, ys, n_src, ball, &w) == kEikBall) {
+        c.cs = c.csrc = eik_lin_csrc(g, i, j, xs, ys);
+        c.code = (uint8_t)(kLinBall << 4);
+        return c;
+    }
+    const double l = i > 0 ? eik_lin_read(n[x - 1], T[x - 1]) : inf, r = i + 1 < nx ? eik_lin_read(n[x + 1], T[x + 1]) : inf;
+    const double dn = j > 0 ? eik_lin_read(n[x - nx], T[x - nx]) : inf, up = j + 1 < ny ? eik_lin_read(n[x + nx], T[x + nx]) : inf;
+    c = eik_flin_coef(g, i, j, xs, ys, n_src, l, r, dn, up, s, t);
+    c.code |= (uint8_t)(kLinFree << 4);
+    return c;
+}
+
+// the node in either linearisation, for code that carries the choice as a template flag
+template <bool FACT> RT_EIK_HD EikLinNode eik_lin_node_of(const EikGrid& g, long nx, long ny, long i, long j, const double* n,
+                                                          const double* T, const uint8_t* filled, double xs, double ys, double n_src,
+                                                          double ball) {
+    if constexpr (FACT) return eik_flin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
+    else return eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
+}
+
+// One row's share of g_src in the factored linearisation, on C columns at once: acc[c] = the sum from +0.0 over i ascending of
+// csrc lam at the free nodes and the nodes of the ball of row j; v is column-minor, [ny nx][C]
+template <int C> RT_EIK_HD void eik_flin_g_src_row(const EikGrid& g, long nx, long j, double xs, double ys, double n_src,
+                                                   const uint8_t* code, const double* ca, const double* cb, const double* v, double* acc) {
+    for (int c = 0; c < C; c++) acc[c] = 0.0;
+    for (long i = 0; i < nx; i++) {
+        const long x = j * nx + i;
+        const uint8_t cls = eik_lin_class(code[x]);
+        if (cls < kLinFree) continue;
+        const double w = cls == kLinBall ? eik_lin_csrc(g, i, j, xs, ys) : eik_flin_csrc(g, i, j, xs, ys, n_src, code[x], ca[x], cb[x]);
+        for (int c = 0; c < C; c++) acc[c] = acc[c] + w * v[x * C + c];
+    }
+}
+
 // The starting value of the tangent at a node, which is final unless the node is free; *k is the free node's constant term
 RT_EIK_HD double eik_lin_tangent_init(const EikLinNode& c, double dn, double dn_src, double seed, double* k) {
     *k = 0.0;
@@ -143,6 +240,13 @@ RT_EIK_HD double eik_lin_tangent_init(const EikLinNode& c, double dn, double dn_
         case kLinFree: *k = c.cs * dn; return 0.0;
         default: return 0.0;
     }
+}
+
+// eik_lin_tangent_init in the factored linearisation: a free node's constant term has the source's share
+RT_EIK_HD double eik_flin_tangent_init(const EikLinNode& c, double dn, double dn_src, double seed, double* k) {
+    if (eik_lin_class(c.code) != kLinFree) return eik_lin_tangent_init(c, dn, dn_src, seed, k);
+    *k = c.cs * dn + c.csrc * dn_src;
+    return 0.0;
 }
 
 // The tangent's gather at free node x: v [ny][nx] the current values, k = cs dn
@@ -238,20 +342,23 @@ struct EikLinResult {
 
 #if !(defined(__HIPCC__) || defined(__HIP__))
 // Both solves of one source as the serial loops that define them, host only.  Work space: ca, cb, k [ny][nx] doubles and code,
-// kids [ny][nx] bytes.  dn_src is a value; seed, g and g_src may be NULL.
+// kids [ny][nx] bytes.  dn_src is a value; seed, g and g_src may be NULL.  factored: the factored linearisation.
 inline EikLinResult eik_lin_tangent(const EikGrid& g, long nx, long ny, const double* n, const double* T, const uint8_t* filled,
                                     double xs, double ys, double n_src, double ball, int max_rounds, const double* dn, double dn_src,
-                                    const double* seed, double* dT, double* ca, double* cb, double* k, uint8_t* code) {
+                                    const double* seed, double* dT, double* ca, double* cb, double* k, uint8_t* code,
+                                    bool factored = false) {
     EikLinResult res{0, 1, 0, 0};
     long nfree = 0;
     for (long j = 0; j < ny; j++)
         for (long i = 0; i < nx; i++) {
             const long x = j * nx + i;
-            const EikLinNode c = eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
+            const EikLinNode c = factored ? eik_flin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball)
+                                          : eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
             ca[x] = c.ca;
             cb[x] = c.cb;
             code[x] = c.code;
-            dT[x] = eik_lin_tangent_init(c, dn[x], dn_src, seed ? seed[x] : 0.0, &k[x]);
+            dT[x] = factored ? eik_flin_tangent_init(c, dn[x], dn_src, seed ? seed[x] : 0.0, &k[x])
+                             : eik_lin_tangent_init(c, dn[x], dn_src, seed ? seed[x] : 0.0, &k[x]);
             if (eik_lin_class(c.code) >= kLinFree) res.nodes++;
             if (eik_lin_class(c.code) == kLinFree) nfree++;
         }
@@ -283,13 +390,15 @@ inline EikLinResult eik_lin_tangent(const EikGrid& g, long nx, long ny, const do
 
 inline EikLinResult eik_lin_adjoint(const EikGrid& g, long nx, long ny, const double* n, const double* T, const uint8_t* filled,
                                     double xs, double ys, double n_src, double ball, int max_rounds, const double* r, double* lam,
-                                    double* gout, double* g_src, double* ca, double* cb, uint8_t* code, uint8_t* kids) {
+                                    double* gout, double* g_src, double* ca, double* cb, uint8_t* code, uint8_t* kids,
+                                    bool factored = false) {
     EikLinResult res{0, 1, 0, 0};
     long nfree = 0;
     for (long j = 0; j < ny; j++)
         for (long i = 0; i < nx; i++) {
             const long x = j * nx + i;
-            const EikLinNode c = eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
+            const EikLinNode c = factored ? eik_flin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball)
+                                          : eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
             ca[x] = c.ca;
             cb[x] = c.cb;
             code[x] = c.code;
@@ -327,10 +436,20 @@ inline EikLinResult eik_lin_adjoint(const EikGrid& g, long nx, long ny, const do
         for (long i = 0; i < nx; i++) {
             const long x = j * nx + i;
             const uint8_t cls = eik_lin_class(code[x]);
-            const EikLinNode c = cls >= kLinFree ? eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball) : EikLinNode{};
+            const EikLinNode c = cls < kLinFree ? EikLinNode{}
+                                 : factored     ? eik_flin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball)
+                                                : eik_lin_node(g, nx, ny, i, j, n, T, filled, xs, ys, n_src, ball);
             if (gout) gout[x] = cls >= kLinFree ? c.cs * lam[x] : 0.0;
             if (cls == kLinBall) acc = acc + c.csrc * lam[x];
         }
+    if (factored) {
+        acc = 0.0;
+        for (long j = 0; j < ny; j++) {
+            double row;
+            eik_flin_g_src_row<1>(g, nx, j, xs, ys, n_src, code, ca, cb, lam, &row);
+            acc = acc + row;
+        }
+    }
     if (g_src) *g_src = acc;
     return res;
 }

@@ -1634,16 +1634,22 @@ def traveltime_table(selected_func, field, sources, grid, *, thetas, step, max_s
     return res
 
 
-def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False, _width=0, scheme="plain"):
-    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny); scheme "plain" or "factored" is read by the fills alone;
-    _global_path and _width (the chunk width of the batched sweeps) are for tests: no result depends on them"""
+def eikonal_params(grid, ball=2.0, max_rounds=0, _global_path=False, _width=0, scheme="plain", linearise="plain"):
+    """rtmi_eikonal_params of grid = (gx0, gdx, nx, gy0, gdy, ny); scheme "plain" or "factored" is the fills'; linearise "plain" or
+    "factored" is the tangent's and the adjoint's, and "factored" goes with the factored fill alone: scheme is then
+    RTMI_EIKONAL_FACTORED_LIN; _global_path and _width (the chunk width of the batched sweeps) are for tests: no result depends on
+    them"""
     gx0, gdx, nx, gy0, gdy, ny = grid
     if scheme not in _lib.EIKONAL_SCHEMES:
         raise ValueError('eikonal: scheme must be "plain" or "factored"')
+    if not isinstance(linearise, str) or linearise not in _lib.EIKONAL_LINEARISE:
+        raise ValueError('eikonal: linearise must be "plain" or "factored"')
     ep = _lib.EikonalParams()
     ep.gx0 = float(gx0); ep.gdx = float(gdx); ep.nx = int(nx)
     ep.gy0 = float(gy0); ep.gdy = float(gdy); ep.ny = int(ny)
     ep.ball = float(ball); ep.max_rounds = int(max_rounds); ep.scheme = _lib.EIKONAL_SCHEMES[scheme]
+    if linearise == "factored":
+        ep.scheme = _lib.EIKONAL_FACTORED_LIN
     ep.reserved[0] = int(bool(_global_path))
     ep.reserved[1] = int(_width)
     return ep
@@ -1799,13 +1805,16 @@ def _eikonal_lin_array(who, name, a, shape):
 
 
 def eikonal_tangent(field_or_n, sources, grid, fill_result, dn, *, n_src=None, dn_src=None, dT_seed=None, ball=2.0, max_rounds=0,
-                    stats=False, _global_path=False):
+                    stats=False, linearise="plain", _global_path=False):
     """The tangent of the eikonal fill, dT = J dn, on the device (rtmi_eikonal_tangent, include/rtmi.h): what a
     perturbation dn [ny, nx] of the slowness at the nodes, dn_src [S] of the slowness at the sources (None: 0) and dT_seed
     [S, ny, nx] of the seeds (None: 0) does to the table that eikonal_fill returned.  field_or_n, sources, grid, n_src, ball as in
     the eikonal_fill call that gave fill_result (its dict: T and filled are read).  Returns a dict: dT [S, ny, nx] (0 at
     obstacles and unreached nodes, dT_seed at seeds), rounds and converged [S], and with stats=True 'stats'.  Where converged
-    is 0 the values are not final: raise max_rounds."""
+    is 0 the values are not final: raise max_rounds.  linearise="factored"  linearises the factored update, for a
+    fill_result of eikonal_fill(scheme="factored"): the plain linearisation of such a table is off by 1 to 10 % of the largest
+    |dT|, and by its own size in dn_src; some ten rounds in place of two or three.  The default "plain" keeps every bit.  The
+    same argument on eikonal_adjoint, the _multi and _device forms and eikonal_operator."""
     who = "eikonal_tangent"
     n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
     S = shape[0]
@@ -1814,7 +1823,7 @@ def eikonal_tangent(field_or_n, sources, grid, fill_result, dn, *, n_src=None, d
     dT_seed = _eikonal_lin_array(who, "dT_seed", dT_seed, shape)
     dT = np.zeros(shape)
     rounds = np.zeros((S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, linearise=linearise)
     st = _lib.EikonalStats()
     check(lib().rtmi_eikonal_tangent(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T), filled.ctypes.data_as(C.POINTER(C.c_uint8)),
                                      dptr(dn), dptr(dn_src), dptr(dT_seed), dptr(dT), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
@@ -1824,7 +1833,8 @@ def eikonal_tangent(field_or_n, sources, grid, fill_result, dn, *, n_src=None, d
     return res
 
 
-def eikonal_adjoint(field_or_n, sources, grid, fill_result, r, *, n_src=None, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+def eikonal_adjoint(field_or_n, sources, grid, fill_result, r, *, n_src=None, ball=2.0, max_rounds=0, stats=False,
+                    linearise="plain", _global_path=False):
     """The adjoint of the eikonal fill, g = J^T r, on the device (rtmi_eikonal_adjoint): the gradient with respect to
     the medium of any misfit of the table whose derivative with respect to T is r [S, ny, nx] (ignored at obstacles and
     unreached nodes), by the adjoint-state method, with no rays.  Arguments as in eikonal_tangent.  Returns a dict:
@@ -1839,7 +1849,7 @@ def eikonal_adjoint(field_or_n, sources, grid, fill_result, r, *, n_src=None, ba
     r = _eikonal_lin_array(who, "r", r, shape)
     lam, g, g_src = np.zeros(shape), np.zeros(shape), np.zeros(S)
     rounds = np.zeros((S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, linearise=linearise)
     st = _lib.EikonalStats()
     check(lib().rtmi_eikonal_adjoint(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T), filled.ctypes.data_as(C.POINTER(C.c_uint8)),
                                      dptr(r), dptr(lam), dptr(g), dptr(g_src), rounds.ctypes.data_as(_lib._ip), C.byref(st)))
@@ -1872,7 +1882,7 @@ def _eikonal_lin_tensors(who, tensors):
 
 
 def eikonal_tangent_device(n, sources, grid, fill_result, dn, *, n_src, dn_src=None, dT_seed=None, ball=2.0, max_rounds=0,
-                           stats=False, _global_path=False):
+                           stats=False, linearise="plain", _global_path=False):
     """eikonal_tangent on torch tensors of one GPU, with no host copy (rtmi_eikonal_tangent_dev): n and dn [ny, nx], sources
     [S, 2], n_src and dn_src [S], dT_seed [S, ny, nx] in fp64, contiguous; fill_result is eikonal_fill_device's dict (T fp64,
     filled uint8, on the device).  dT is a new tensor on the device; rounds and converged are numpy arrays.  The same bits."""
@@ -1887,7 +1897,7 @@ def eikonal_tangent_device(n, sources, grid, fill_result, dn, *, n_src, dn_src=N
                                ("dn", dn, f64, (ny, nx)), ("dn_src", dn_src, f64, (S,)), ("dT_seed", dT_seed, f64, (S, ny, nx))])
     dT = torch.zeros((S, ny, nx), dtype=f64, device=n.device)
     rounds = np.zeros((S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, linearise=linearise)
     st = _lib.EikonalStats()
     opt = lambda a: None if a is None else a.data_ptr()      # noqa: E731
     torch.cuda.synchronize(n.device)               # the library works on the null stream
@@ -1901,7 +1911,8 @@ def eikonal_tangent_device(n, sources, grid, fill_result, dn, *, n_src, dn_src=N
     return res
 
 
-def eikonal_adjoint_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0, max_rounds=0, stats=False, _global_path=False):
+def eikonal_adjoint_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0, max_rounds=0, stats=False,
+                           linearise="plain", _global_path=False):
     """eikonal_adjoint on torch tensors of one GPU (rtmi_eikonal_adjoint_dev): arguments as in eikonal_tangent_device, r
     [S, ny, nx].  lam, g and g_src are new tensors on the device; rounds and converged are numpy arrays.  The same bits."""
     import torch
@@ -1917,7 +1928,7 @@ def eikonal_adjoint_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0,
     g = torch.zeros((S, ny, nx), dtype=f64, device=n.device)
     g_src = torch.zeros((S,), dtype=f64, device=n.device)
     rounds = np.zeros((S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, linearise=linearise)
     st = _lib.EikonalStats()
     torch.cuda.synchronize(n.device)               # the library works on the null stream
     with torch.cuda.device(n.device):
@@ -2010,7 +2021,7 @@ def _eikonal_multi_result(out, rounds, st, stats):
 
 
 def eikonal_tangent_multi(field_or_n, sources, grid, fill_result, dn, *, n_src=None, dn_src=None, dT_seed=None, ball=2.0,
-                          max_rounds=0, stats=False, _global_path=False, _width=0):
+                          max_rounds=0, stats=False, linearise="plain", _global_path=False, _width=0):
     """eikonal_tangent on K columns in one call (rtmi_eikonal_tangent_multi): dn [K, ny, nx], dn_src [K, S] or None,
     dT_seed [K, S, ny, nx] or None, 1 <= K <= 64.  Returns a dict: dT [K, S, ny, nx], rounds and converged [K, S], and with
     stats=True 'stats' (sums over the columns).  Column c has the bits of eikonal_tangent on column c alone."""
@@ -2025,7 +2036,7 @@ def eikonal_tangent_multi(field_or_n, sources, grid, fill_result, dn, *, n_src=N
     dT_seed = _eikonal_lin_array(who, "dT_seed", dT_seed, (K,) + shape)
     dT = np.zeros((K,) + shape)
     rounds = np.zeros((K, S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, linearise=linearise)
     st = _lib.EikonalStats()
     check(lib().rtmi_eikonal_tangent_multi(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
                                            filled.ctypes.data_as(C.POINTER(C.c_uint8)), K, dptr(dn), dptr(dn_src), dptr(dT_seed),
@@ -2034,7 +2045,7 @@ def eikonal_tangent_multi(field_or_n, sources, grid, fill_result, dn, *, n_src=N
 
 
 def eikonal_adjoint_multi(field_or_n, sources, grid, fill_result, r, *, n_src=None, ball=2.0, max_rounds=0, stats=False,
-                          _global_path=False, _width=0):
+                          linearise="plain", _global_path=False, _width=0):
     """eikonal_adjoint on K columns in one call (rtmi_eikonal_adjoint_multi): r [K, S, ny, nx], 1 <= K <= 64.
     Returns a dict: lam and g [K, S, ny, nx], g_src, rounds and converged [K, S], and with stats=True 'stats'.  Column c has the
     bits of eikonal_adjoint on column c alone."""
@@ -2047,7 +2058,7 @@ def eikonal_adjoint_multi(field_or_n, sources, grid, fill_result, r, *, n_src=No
     K = r.shape[0]
     lam, g, g_src = np.zeros((K,) + shape), np.zeros((K,) + shape), np.zeros((K, S))
     rounds = np.zeros((K, S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, linearise=linearise)
     st = _lib.EikonalStats()
     check(lib().rtmi_eikonal_adjoint_multi(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
                                            filled.ctypes.data_as(C.POINTER(C.c_uint8)), K, dptr(r), dptr(lam), dptr(g), dptr(g_src),
@@ -2056,7 +2067,7 @@ def eikonal_adjoint_multi(field_or_n, sources, grid, fill_result, r, *, n_src=No
 
 
 def eikonal_tangent_multi_device(n, sources, grid, fill_result, dn, *, n_src, dn_src=None, dT_seed=None, ball=2.0, max_rounds=0,
-                                 stats=False, _global_path=False, _width=0):
+                                 stats=False, linearise="plain", _global_path=False, _width=0):
     """eikonal_tangent_multi on torch tensors of one GPU, with no host copy (rtmi_eikonal_tangent_multi_dev): as
     eikonal_tangent_device with dn [K, ny, nx], dn_src [K, S], dT_seed [K, S, ny, nx].  dT [K, S, ny, nx] is a new tensor on the
     device; rounds and converged [K, S] are numpy arrays.  The same bits."""
@@ -2074,7 +2085,7 @@ def eikonal_tangent_multi_device(n, sources, grid, fill_result, dn, *, n_src, dn
                                ("dT_seed", dT_seed, f64, (K, S, ny, nx))])
     dT = torch.zeros((K, S, ny, nx), dtype=f64, device=n.device)
     rounds = np.zeros((K, S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, linearise=linearise)
     st = _lib.EikonalStats()
     opt = lambda a: None if a is None else a.data_ptr()      # noqa: E731
     torch.cuda.synchronize(n.device)               # the library works on the null stream
@@ -2086,7 +2097,8 @@ def eikonal_tangent_multi_device(n, sources, grid, fill_result, dn, *, n_src, dn
     return _eikonal_multi_result({"dT": dT}, rounds, st, stats)
 
 
-def eikonal_adjoint_multi_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0, max_rounds=0, stats=False, _global_path=False, _width=0):
+def eikonal_adjoint_multi_device(n, sources, grid, fill_result, r, *, n_src, ball=2.0, max_rounds=0, stats=False,
+                                 linearise="plain", _global_path=False, _width=0):
     """eikonal_adjoint_multi on torch tensors of one GPU (rtmi_eikonal_adjoint_multi_dev): r [K, S, ny, nx].  lam, g
     [K, S, ny, nx] and g_src [K, S] are new tensors on the device; rounds and converged [K, S] are numpy arrays.  The same bits."""
     import torch
@@ -2104,7 +2116,7 @@ def eikonal_adjoint_multi_device(n, sources, grid, fill_result, r, *, n_src, bal
     g = torch.zeros((K, S, ny, nx), dtype=f64, device=n.device)
     g_src = torch.zeros((K, S), dtype=f64, device=n.device)
     rounds = np.zeros((K, S, 2), dtype=np.int32)
-    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width)
+    ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, linearise=linearise)
     st = _lib.EikonalStats()
     torch.cuda.synchronize(n.device)               # the library works on the null stream
     with torch.cuda.device(n.device):
@@ -2131,16 +2143,18 @@ def eikonal_source_weights(sources, grid):
     return idx, w
 
 
-def eikonal_operator(field_or_n, sources, grid, fill_result, receivers, *, n_src=None, ball=2.0, max_rounds=0):
+def eikonal_operator(field_or_n, sources, grid, fill_result, receivers, *, n_src=None, ball=2.0, max_rounds=0, linearise="plain"):
     """The Jacobian of the filled tables at receiver nodes as a scipy LinearOperator, matrix-free, for LSQR or Gauss-Newton
     (DESIGN.md 35): it maps dn [ny nx] to dT at `receivers` (node indices iy nx + ix, [R]) of every source; row s R + k is source
     s, receiver k.  matvec is eikonal_tangent_device and a gather; rmatvec a scatter, eikonal_adjoint_device and a sum over the
     sources.  n_src follows dn through the bilinear weights of the source's cell where the source lies inside the grid, else it
     is held fixed.  field_or_n, sources, grid, n_src, ball as in the eikonal_fill call that gave fill_result; everything is
-    uploaded once.  A sweep that does not converge within max_rounds raises.  Receivers off the nodes: compose an interpolation."""
+    uploaded once.  A sweep that does not converge within max_rounds raises.  Receivers off the nodes: compose an interpolation.
+    linearise as in eikonal_tangent."""
     import torch
     from scipy.sparse.linalg import LinearOperator
     who = "eikonal_operator"
+    eikonal_params(grid, ball, max_rounds, linearise=linearise)        # refuses a bad linearise before anything is uploaded
     n, src, ns, T, filled, shape = _eikonal_lin_host(who, field_or_n, sources, grid, fill_result, n_src)
     S, ny, nx = shape
     rec = np.asarray(receivers, dtype=np.int64).reshape(-1)
@@ -2152,7 +2166,7 @@ def eikonal_operator(field_or_n, sources, grid, fill_result, receivers, *, n_src
     d_fill = {"T": up(T), "filled": up(filled)}
     idx, w = eikonal_source_weights(src, grid)
     d_idx, d_w = up(idx), up(w)
-    kw = dict(n_src=d_ns, ball=ball, max_rounds=max_rounds)
+    kw = dict(n_src=d_ns, ball=ball, max_rounds=max_rounds, linearise=linearise)
 
     def done(res, what):
         if not res["converged"].all():
@@ -2192,16 +2206,21 @@ class EikonalTomography:
     n_src, ball, max_rounds as in eikonal_fill.  fill_result: the dict of the eikonal_fill call that gave the tables (this is how
     a table seeded by rays enters); None: the handle fills its own from the ball, and only then can it be re-linearised.
     scheme "plain" or "factored"  is the scheme of that own fill and of every relinearise; it cannot be given
-    together with fill_result, whose tables are already made.  The products linearise the plain update about the table either way.
+    together with fill_result, whose tables are already made.  linearise "plain" (the default, which keeps every bit) or
+    "factored"  is the linearisation of apply, transpose, lsqr, their _multi forms and of every relinearise:
+    "factored" is consistent with tables of the factored scheme, so it needs scheme="factored", or a fill_result that
+    eikonal_fill(scheme="factored") made; "plain" linearises the plain update about the table, whatever filled it.
     n_src follows the model through the bilinear weights of the source's cell where the source lies inside the grid.  A row is
     live where none of the four nodes round its receiver is an obstacle or unreached; other rows read and give 0."""
 
     def __init__(self, field_or_n, sources, grid, receivers, *, fill_result=None, n_src=None, ball=2.0, max_rounds=0, scheme=None,
-                 _global_path=False, _width=0):
+                 linearise="plain", _global_path=False, _width=0):
         who = "EikonalTomography"
         self._h = None
         if scheme is not None and fill_result is not None:
             raise ValueError(f"{who}: scheme is the scheme of the handle's own fill; it cannot be given together with fill_result")
+        if linearise == "factored" and fill_result is None and scheme != "factored" and scheme in (None, "plain"):
+            raise ValueError(f'{who}: linearise="factored" on a handle that fills its own tables needs scheme="factored"')
         src = np.ascontiguousarray(np.asarray(sources, dtype=np.float64).reshape(-1, 2))
         S, nx, ny = len(src), int(grid[2]), int(grid[5])
         n, ns = _eikonal_medium(who, field_or_n, src, grid, n_src)
@@ -2220,7 +2239,8 @@ class EikonalTomography:
                 raise ValueError(f"{who}: fill_result's T and filled must be [S, ny, nx]")
         self.grid, self.S, self.R, self.nx, self.ny = tuple(grid), S, len(rec), nx, ny
         self.n, self.sources, self.receivers = n.copy(), src, rec
-        ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, scheme="plain" if scheme is None else scheme)
+        ep = eikonal_params(grid, ball, max_rounds, _global_path, _width, scheme="plain" if scheme is None else scheme,
+                            linearise=linearise)
         h = C.c_void_p()
         check(lib().rtmi_eikonal_tomo_create(C.byref(ep), dptr(n), S, dptr(src), dptr(ns), dptr(T),
                                              None if filled is None else filled.ctypes.data_as(C.POINTER(C.c_uint8)), len(rec), dptr(rec),

@@ -14,7 +14,12 @@ difference is printed.
 Also printed: the rounds, and the two floors of a sweep kernel -- the bytes of the values, ca, cb, the codes and the constant
 term of every sweep at 6 TB/s, and the diagonals of every sweep times a dependent L2 round trip -- and which of them binds.
 
-    python tools/eikonal_lin_timing.py [--tables 32] [--reps 5] [--check 64] [--no-torch] [--out FILE.json]
+--linearise factored times the factored update linearised instead: the same 32 tables filled by the
+factored scheme from the ball alone, and on them the plain tangent and adjoint (what they were before) against the factored ones,
+alternating, medians of --reps device times with min and max; time per round (of the slowest source); and the setup pass on its
+own from calls capped at one and at two rounds, setup = 2 t(1) - t(2).  No torch yardstick in this mode.
+
+    python tools/eikonal_lin_timing.py [--tables 32] [--reps 5] [--check 64] [--no-torch] [--linearise plain|factored] [--out FILE.json]
 """
 import argparse
 import json
@@ -118,12 +123,45 @@ def torch_adjoint(torch, net, r, check, cap):
     return jacobi(torch, step, r0, check, cap)
 
 
+def time_factored(rb, a, grid, d_n, d_src, d_ns, d_dn, d_dns, d_r):
+    """the plain and the factored linearisation on the same factored tables -> the dict that is printed"""
+    f = rb.eikonal_fill_device(d_n, d_src, grid, None, n_src=d_ns, stats=True, scheme="factored")
+    assert f["converged"].all()
+    calls = {}
+    for lin in ("plain", "factored"):
+        calls["tangent", lin] = lambda mr=0, lin=lin: rb.eikonal_tangent_device(d_n, d_src, grid, f, d_dn, n_src=d_ns, dn_src=d_dns, stats=True,
+                                                                               max_rounds=mr, linearise=lin)
+        calls["adjoint", lin] = lambda mr=0, lin=lin: rb.eikonal_adjoint_device(d_n, d_src, grid, f, d_r, n_src=d_ns, stats=True, max_rounds=mr,
+                                                                               linearise=lin)
+    res = {k: c() for k, c in calls.items()}                                                                            # warm
+    assert all(r["converged"].all() for r in res.values())
+    ms = {k: [] for k in calls}
+    capped = {(k, mr): [] for k in calls for mr in (1, 2)}
+    for _ in range(a.reps):                                                                                             # alternating
+        for k, c in calls.items():
+            ms[k].append(c()["stats"]["kernel_ms"])
+        for (k, mr), v in capped.items():
+            v.append(calls[k](mr)["stats"]["kernel_ms"])
+    out = {"grid": [NX, NY], "tables": a.tables, "reps": a.reps, "fill_rounds": f["rounds"].tolist(), "fill_ms": f["stats"]["kernel_ms"],
+           "maps": []}
+    for k in calls:
+        sk, rounds = series(ms[k]), int(res[k]["stats"]["rounds_max"])
+        t1, t2 = float(np.median(capped[k, 1])), float(np.median(capped[k, 2]))
+        case = {"map": k[0], "linearise": k[1], "path": res[k]["stats"]["path"], "rounds": res[k]["rounds"].tolist(), "k_eikonal_lin": sk,
+                "ms_per_round": sk["median_ms"] / rounds, "one_round": series(capped[k, 1]), "two_rounds": series(capped[k, 2]),
+                "setup_ms": 2 * t1 - t2, "round_ms_from_the_capped_calls": t2 - t1}
+        print(json.dumps(case), file=sys.stderr, flush=True)
+        out["maps"].append(case)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tables", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--check", type=int, default=64)
     ap.add_argument("--no-torch", action="store_true", help="time the kernels alone")
+    ap.add_argument("--linearise", choices=("plain", "factored"), default="plain", help="factored: DESIGN.md section 40's comparison")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from raytracing_amd import rt_bench as rb
@@ -144,6 +182,14 @@ def main():
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()      # noqa: E731
     d_n, d_src, d_ns = up(n), up(src), up(ns)
     d_dn, d_dns, d_r = up(0.1 * n * rng.standard_normal(n.shape)), up(0.1 * ns * rng.standard_normal(P)), up(rng.standard_normal((P, NY, NX)))
+    if a.linearise == "factored":
+        text = json.dumps(time_factored(rb, a, grid, d_n, d_src, d_ns, d_dn, d_dns, d_r), indent=1)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(text + "\n")
+        return
     fill = lambda: rb.eikonal_fill_device(d_n, d_src, grid, None, n_src=d_ns, stats=True)                                  # noqa: E731
     f = fill()                                                                                                           # warm
     assert f["converged"].all()
